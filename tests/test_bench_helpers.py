@@ -99,3 +99,46 @@ def test_every_tool_a_test_runs_exists():
             if not os.path.exists(os.path.join(root, "tools", rel)):
                 missing.append((name, rel))
     assert not missing, missing
+
+
+def test_steps_beyond_the_bundled_tape_drive_more_loops():
+    # --steps is the number of steps timed: a window longer than the map's two loops (2 172 observation steps) drives more loops
+    # of the same course; a window that fits keeps the tape as it was
+    args, tape = bench.make_tape_for(bench.CONFIGS[3], 1000, None, 25)
+    assert len(tape["steps"]) == 2172 and "-NUMBER_LOOPS" not in args
+    args, tape = bench.make_tape_for(bench.CONFIGS[3], 1000, None, 5000)
+    assert len(tape["steps"]) >= 5000 and args[args.index("-NUMBER_LOOPS") + 1] > 2
+    assert bench.pick_start(len(tape["steps"]), 100, 4900, None) == 1000   # (the start of a window that fits)
+
+
+def test_dump_outputs_fits_its_budget(tmp_path):
+    # --dump-outputs: float32 / float64 .npy files, at most 64 MB, every k-th particle from particle 0 when the whole set does not fit
+    import numpy as np
+
+    class Ctx:   # what dump_outputs reads of a context: N, nf(), peek(); state that encodes the particle index
+        def __init__(self, N, nf):
+            self.N, self._nf, self.asked = N, nf, None
+
+        def nf(self):
+            return self._nf
+
+        def peek(self, landmarks=True, first=0, stride=1, count=None):
+            self.asked = (first, stride, count)
+            i = np.arange(first, first + stride * count, stride, dtype=np.float32)
+            return dict(xv=np.repeat(i[:, None], 3, 1), Pv=np.zeros((count, 3, 3), np.float32), w=i.copy(),
+                        xf=np.zeros((count, self._nf, 2), np.float32) if landmarks else None,
+                        Pf=np.zeros((count, self._nf, 2, 2), np.float32) if landmarks else None, nf=self._nf)
+
+    steps = 20
+    est, neff, res = np.random.default_rng(1).normal(size=(steps, 3)), np.full(steps, 7.0, np.float32), np.arange(steps) % 2 == 0
+    for N, nf, whole in ((1000, 35, True), (100000, 35, False), (100000, 0, True), (300, 10000, False)):
+        d = tmp_path / ("%d_%d" % (N, nf))
+        s = Ctx(N, nf)
+        info = bench.dump_outputs(str(d), s, est, neff, res)
+        files = {f[:-4]: np.load(str(d / f)) for f in os.listdir(str(d))}
+        assert set(files) == set(info["files"]) and all(a.dtype in (np.float32, np.float64) for a in files.values())
+        assert sum(os.path.getsize(str(d / f)) for f in os.listdir(str(d))) <= bench.DUMP_LIMIT_BYTES
+        assert np.array_equal(files["estimates"], est) and np.array_equal(files["estimate"], est[-1])
+        assert np.array_equal(files["resampled"], res.astype(np.float32))
+        assert (s.asked[1] == 1) == whole and s.asked[0] == 0 and s.asked[1] * (s.asked[2] - 1) < N <= s.asked[1] * s.asked[2]
+        assert np.array_equal(files["particle_index"], files["w"]) and ("xf" in files) == (nf > 0)
