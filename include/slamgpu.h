@@ -348,6 +348,25 @@ int slamgpu_update_particle(slamgpu_ctx *ctx, const float *z, int32_t nz, const 
 int slamgpu_update_labels(slamgpu_ctx *ctx, const float *z, int32_t nz, const float R[4], const int32_t *labels,
                           const slamgpu_particle_assoc *opt, const float *normals, const float *strata, int32_t report[8]);
 
+/* The per-particle step driven by the device: K iterations of the wrapper's loop with the observation made on the device and the
+ * association carried into the update, as slamgpu_run_observe does for the known association.  Iteration k does exactly what
+ * n_controls[k] calls of slamgpu_predict(V, G, Q, dt, phi_true, NULL) (controls: rows of V, G, phi_true), slamgpu_observe(xtrue +
+ * 3k, max_range, R, noise, ...) keeping the raw z, slamgpu_update_particle(z, nz, R, opt, NULL, NULL, report) when nz > 0 (nz = 0:
+ * no update, as there) and slamgpu_estimate_async do, bit for bit, on a context created with the same configuration; every
+ * per-particle decision (the census, the dead slots, the new slots, the genealogy) is taken on the device, and the call returns
+ * without waiting for it.  The association is the exhaustive scan (opt->mode SLAMGPU_ASSOC_EXHAUSTIVE or _AUTO: the labels of
+ * the grid are the same).  noise: 0 none, 2 Philox.  Estimates and history: slamgpu_estimate_fetch / slamgpu_history_fetch; the
+ * iterations' reports: slamgpu_particle_report_fetch.  Any host-side call afterwards (slamgpu_update_particle, download, peek,
+ * slamgpu_num_landmarks, slamgpu_retire_landmarks, slamgpu_associate_ex, ...) first takes the state back (one synchronisation).
+ * Refused, with nothing applied: a context without SLAMGPU_FLAG_PARTICLE_MAPS | SLAMGPU_FLAG_DEVICE_OBSERVE, no map, TAPE mode,
+ * another noise, SLAMGPU_ASSOC_GRID, bad opt fields (SLAMGPU_ERR_INVALID); K more entries than the history or the report ring
+ * (4 096 each) have room for, or N x landmark capacity x map size above 4e10 (SLAMGPU_ERR_CAPACITY). */
+int slamgpu_run_particle(slamgpu_ctx *ctx, int32_t K, const int32_t *n_controls, const float *controls, const float Q[4], float dt,
+                         const float *xtrue, float max_range, const float R[4], int32_t noise, const slamgpu_particle_assoc *opt);
+/* The reports of slamgpu_run_particle's iterations not fetched yet, oldest first (report[k][8]: slamgpu_update_particle's fields;
+ * an iteration without observations: all zeros), at most max_count of them (*count: how many); the rest stay.  Synchronises. */
+int slamgpu_particle_report_fetch(slamgpu_ctx *ctx, int32_t *report, int32_t max_count, int32_t *count);
+
 /* Retire landmarks from the gated association (round 6): landmarks ids[0 .. count) take no part in slamgpu_associate /
  * _associate_ex from now on -- no particle gates an observation against them, nothing votes for them -- and, never being
  * re-observed, they are never written again.  They stay in the particles' maps (slamgpu_num_landmarks, slamgpu_download and the

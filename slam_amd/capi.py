@@ -26,6 +26,7 @@ DECLARED_SYMBOLS = [
     "slamgpu_dist_collective_status", "slamgpu_dist_comm_id", "slamgpu_dist_comm_init", "slamgpu_dist_group_create", "slamgpu_dist_group_destroy",
     "slamgpu_dist_group_step", "slamgpu_dist_group_settle", "slamgpu_dist_group_history", "slamgpu_dist_group_download",
     "slamgpu_peek", "slamgpu_step_observe", "slamgpu_run_observe", "slamgpu_observe_fetch", "slamgpu_associate_ex", "slamgpu_update_particle", "slamgpu_update_labels", "slamgpu_dist_comm_info", "slamgpu_dist_remote_reads",
+    "slamgpu_run_particle", "slamgpu_particle_report_fetch",
 ]
 ASSOC_AUTO, ASSOC_EXHAUSTIVE, ASSOC_GRID = 0, 1, 2
 FLAG_DEVICE_OBSERVE = 1
@@ -113,6 +114,10 @@ def load_library():
     L.slamgpu_update_labels.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     if hasattr(L, "slamgpu_retire_landmarks"):
         L.slamgpu_retire_landmarks.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
+    if hasattr(L, "slamgpu_run_particle"):
+        L.slamgpu_run_particle.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_float, C.c_void_p, C.c_int32,
+                                           C.c_void_p]
+        L.slamgpu_particle_report_fetch.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]
     L.slamgpu_genealogy_rows.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     L.slamgpu_persist_info.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
     if hasattr(L, "slamgpu_persist_status"):  # (an older build loaded through SLAMGPU_LIB for an A/B lacks the round-6 entries)
@@ -768,6 +773,26 @@ class SlamGpu:
         rep = np.zeros(8, np.int32)
         _chk(self.L.slamgpu_update_particle(self.h, _ptr(z), z.shape[0], _ptr(_f32(R, 4)), C.byref(o), _ptr(nm), _ptr(st), _ptr(rep)))
         return dict(zip(self._REPORT, (int(v) for v in rep)))
+
+    def run_particle(self, controls_per_step, Q, dt, xtrue_per_step, max_range, R, noise=2, gate_reject=4.0, gate_augment=25.0, mode=ASSOC_AUTO,
+                     new_share=0.0, p_new=1.0, census_every=1, excl=(0.0, 0.0, 2.0)):
+        """slamgpu_run_particle: K iterations (k predicts + device-made observation + per-particle update + estimate each) in one C call
+        that does not wait for the device; controls_per_step: K arrays of (V, G, phi_true) rows; xtrue_per_step: K poses"""
+        K = len(controls_per_step)
+        counts = np.ascontiguousarray([np.asarray(c, np.float32).reshape(-1, 3).shape[0] for c in controls_per_step], np.int32)
+        rows = [np.asarray(c, np.float32).reshape(-1, 3) for c in controls_per_step if np.asarray(c).size]
+        ctl = _f32(np.concatenate(rows) if rows else np.zeros((0, 3), np.float32))
+        xt = _f32(np.asarray(xtrue_per_step, np.float32).reshape(K, 3))
+        o = self._particle_opt(gate_reject, gate_augment, mode, new_share, p_new, census_every, excl)
+        _chk(self.L.slamgpu_run_particle(self.h, K, _ptr(counts), _ptr(ctl), _ptr(_f32(Q, 4)), C.c_float(dt), _ptr(xt), C.c_float(max_range),
+                                         _ptr(_f32(R, 4)), int(noise), C.byref(o)))
+
+    def particle_report_fetch(self, max_count=4096):
+        """the reports of run_particle's iterations not fetched yet: int32 [count, 8] (update_particle's fields, in _REPORT order)"""
+        out = np.zeros((max(int(max_count), 0), 8), np.int32)
+        n = C.c_int32()
+        _chk(self.L.slamgpu_particle_report_fetch(self.h, _ptr(out), int(max_count), C.byref(n)))
+        return out[:n.value].copy()
 
     def update_labels(self, z, R, labels, new_share=0.0, p_new=1.0, census_every=1, normals=None, strata=None):
         """the same step with the caller's labels [N, nz] (slamgpu_update_labels)"""

@@ -67,7 +67,8 @@ static void usage(const char *a0) {
     printf("                        or the per-particle gates acted on by every particle on a map of its own\n");
     printf("    -gpus k             FastSLAM particle set distributed over k GPUs (k > devices: logical shards on device 0)\n");
     printf("    -observe host|device  where the observation of a step is made: host (default) or on the GPU (the packet never leaves\n");
-    printf("                        device memory: slamgpu_step_observe; -rng philox, known association, no -plot)\n");
+    printf("                        device memory: slamgpu_step_observe; -rng philox, known association, no -plot; with -assoc particle:\n");
+    printf("                        slamgpu_run_particle, 256 iterations per call, one with -loop step)\n");
     printf("    -loop step|batched  step: the wrapper's loop call by call (one predict per control step, estimate every iteration);\n");
     printf("                        batched (default without -plot, -rng parity, -assoc gated): one slamgpu_step per observation,\n");
     printf("                        estimates fetched 4096 at a time\n");
@@ -198,12 +199,41 @@ static int run_distributed(Simulator &sim, int k, long maxsteps, FILE *log, Plot
     return rc ? EXIT_FAILURE : 0;
 }
 
+// -assoc particle: the map of the best (largest-weight) particle: what a FastSLAM with per-particle association reports
+static void print_particle_map(slamgpu_ctx *ctx, const Simulator &sim, int N, long pp_opened, long pp_reused, long pp_dropped, int pp_most) {
+    const int slots = slamgpu_num_landmarks(ctx);
+    std::vector<float> w((size_t) N);
+    int held = 0, covered = 0, best = 0;
+    if (slots >= 0 && slamgpu_download_range(ctx, 0, N, nullptr, nullptr, w.data(), nullptr, nullptr) == 0) {
+        for (int i = 1; i < N; i++)
+            if (w[(size_t) i] > w[(size_t) best]) best = i;
+        std::vector<float> xf(2 * (size_t) std::max(slots, 1));
+        if (slots > 0 && slamgpu_download_range(ctx, best, 1, nullptr, nullptr, nullptr, xf.data(), nullptr) == 0) {
+            std::vector<char> hit((size_t) sim.map.nlm, 0);
+            for (int j = 0; j < slots; j++) {
+                if (xf[2 * (size_t) j] != xf[2 * (size_t) j]) continue;  // absent
+                held++;
+                for (int t = 0; t < sim.map.nlm; t++) {
+                    const float dx = xf[2 * (size_t) j] - sim.map.lm[(size_t) t], dy = xf[2 * (size_t) j + 1] - sim.map.lm[(size_t) sim.map.nlm + t];
+                    if (dx * dx + dy * dy < 1.0f) hit[(size_t) t] = 1;
+                }
+            }
+            for (char h : hit) covered += h;
+        }
+    }
+    printf("landmarks in map: %d (the best particle's, number %d; %d of the %d true landmarks within 1 m of one of them; %d slots in use by all particles "
+           "together, %ld opened, %ld of them dead slots reused, %ld observations dropped for want of a slot, at most %d slots rewritten in a step)\n",
+           held, best, covered, sim.map.nlm, slots, pp_opened, pp_reused, pp_dropped, pp_most);
+}
+
 // The wrapper's loop (fastslam2wrapper.cpp:51-117) for a headless run, batched: what the per-iteration form asks of the GPU
 // between two observations -- eight predict calls and eight synchronous pose estimates, only the last of which anything
 // but a plot consumes -- is ONE slamgpu_step per observation (controls + observation + update + recorded estimate, one
 // launch), and the estimates come back 4 096 at a time.  -observe device: the observation itself is made on the GPU
-// (slamgpu_step_observe): the host sends the controls and the true pose.
-static int run_batched(Simulator &sim, slamgpu_ctx *ctx, bool observe_dev, long maxsteps, FILE *log, bool gpubusy) {
+// (slamgpu_step_observe): the host sends the controls and the true pose.  -assoc particle -observe device (popt): the per-particle step
+// with the observation made on the device (slamgpu_run_particle), `chunk` iterations per call (-loop step: one).
+static int run_batched(Simulator &sim, slamgpu_ctx *ctx, bool observe_dev, long maxsteps, FILE *log, bool gpubusy,
+                       const slamgpu_particle_assoc *popt = nullptr, int chunk = 256) {
     const Conf &c = sim.conf;
     struct ObsRow {
         long iter;
@@ -220,8 +250,21 @@ static int run_batched(Simulator &sim, slamgpu_ctx *ctx, bool observe_dev, long 
     size_t run_first = 0;  // -observe device: first row of `rows` that belongs to the chunk not yet handed over
     if (observe_dev) rc = slamgpu_set_map(ctx, sim.map.lm.data(), sim.map.nlm);
     if (!rc && gpubusy) rc = slamgpu_profile(ctx, 1);
+    long pp_opened = 0, pp_reused = 0, pp_dropped = 0;
+    int pp_most = 0;
+    std::vector<int32_t> reports(popt ? 8 * 4096 : 0);
     auto fetch = [&]() -> int {
         int32_t got = 0;
+        if (popt) {
+            if (int r = slamgpu_particle_report_fetch(ctx, reports.data(), 4096, &got)) return r;
+            for (int t = 0; t < got; t++) {
+                const int32_t *rep = reports.data() + 8 * (size_t) t;
+                pp_opened += rep[1];
+                pp_reused += rep[2];
+                pp_dropped += rep[3];
+                pp_most = std::max(pp_most, (int) rep[0]);
+            }
+        }
         if (int r = slamgpu_history_fetch(ctx, xyt.data(), nullptr, nullptr, nullptr, 4096, &got)) return r;
         for (int t = 0; t < got && t < (int) rows.size(); t++) {
             const ObsRow &o = rows[(size_t) t];
@@ -237,7 +280,7 @@ static int run_batched(Simulator &sim, slamgpu_ctx *ctx, bool observe_dev, long 
     auto t_obs = t_begin;
     // (the hand-over does not wait for the GPU: round 5 found slamgpu_run_observe's queue upload blocking behind the launch before it,
     // and took the upload out: slamgpu.cpp: run_observe_persist)
-    constexpr int kRunChunk = 256;
+    const int kRunChunk = chunk;
     std::vector<int32_t> run_counts;
     std::vector<float> run_xt;
     size_t run_rows = 0;
@@ -245,8 +288,10 @@ static int run_batched(Simulator &sim, slamgpu_ctx *ctx, bool observe_dev, long 
     auto flush_run = [&]() -> int {
         if (run_counts.empty()) return 0;
         const auto t_call = std::chrono::steady_clock::now();
-        const int r = slamgpu_run_observe(ctx, (int32_t) run_counts.size(), run_counts.data(), controls.data(), sim.Qe, sim.dt, run_xt.data(), c.MAX_RANGE,
-                                          sim.Re, c.SWITCH_SENSOR_NOISE ? 2 : 0);
+        const int r = popt ? slamgpu_run_particle(ctx, (int32_t) run_counts.size(), run_counts.data(), controls.data(), sim.Qe, sim.dt, run_xt.data(),
+                                                  c.MAX_RANGE, sim.Re, c.SWITCH_SENSOR_NOISE ? 2 : 0, popt)
+                           : slamgpu_run_observe(ctx, (int32_t) run_counts.size(), run_counts.data(), controls.data(), sim.Qe, sim.dt, run_xt.data(),
+                                                 c.MAX_RANGE, sim.Re, c.SWITCH_SENSOR_NOISE ? 2 : 0);
         const auto now = std::chrono::steady_clock::now();
         us_handover += std::chrono::duration<double, std::micro>(now - t_call).count();
         const double us = std::chrono::duration<double, std::micro>(now - t_obs).count() / (double) run_counts.size();
@@ -305,17 +350,19 @@ static int run_batched(Simulator &sim, slamgpu_ctx *ctx, bool observe_dev, long 
            "rms position error %.4f m, final estimate (%.4f, %.4f, %.4f)\n",
            iter, nobs, nobs ? wall_us / nobs : 0.0, nobs ? std::sqrt(sq_err / nobs) : 0.0, est[0], est[1], est[2]);
     if (observe_dev && nobs)
-        printf("host side of that, per observation step: %.2f us inside slamgpu_run_observe (hand-over), %.2f us waiting for the GPU at the end "
-               "(the last fetch), the rest simulating the vehicle\n", us_handover / nobs, us_final / nobs);
+        printf("host side of that, per observation step: %.2f us inside %s (hand-over), %.2f us waiting for the GPU at the end "
+               "(the last fetch), the rest simulating the vehicle\n", us_handover / nobs, popt ? "slamgpu_run_particle" : "slamgpu_run_observe", us_final / nobs);
     if (!rc && gpubusy) {
         double ms = 0, tot = 0;
         int64_t n = 0;
-        for (const char *k : {"fs2_update", "fs1_update", "persist_loop", "resample", "scan", "observe", "finish", "gather", "predict", "estimate"})
+        for (const char *k : {"fs2_update", "fs1_update", "persist_loop", "resample", "scan", "observe", "finish", "gather", "predict", "estimate", "associate",
+                              "particle_book", "particle_resolve"})
             if (slamgpu_kernel_time(ctx, k, &ms, &n) == 0) tot += ms;
         printf("GPU busy (sum of kernel times between event pairs) %.2f us per observation step = %.0f %% of the wall time\n",
                nobs ? 1e3 * tot / nobs : 0.0, wall_us > 0 ? 100.0 * 1e3 * tot / wall_us : 0.0);
     }
-    printf("landmarks in map: %d\n", slamgpu_num_landmarks(ctx));
+    if (popt) print_particle_map(ctx, sim, sim.conf.NPARTICLES, pp_opened, pp_reused, pp_dropped, pp_most);
+    else printf("landmarks in map: %d\n", slamgpu_num_landmarks(ctx));
     return rc ? EXIT_FAILURE : 0;
 }
 
@@ -370,13 +417,16 @@ int main(int argc, char **argv) {
     const bool gated = c.s("assoc") == "gated";
     const bool particle = c.s("assoc") == "particle";
     const bool observe_dev = c.s("observe") == "device";
-    const bool batched = c.method != 0 && !plot.active() && !parity && !gated && !particle && c.s("loop") != "step";
+    // (-assoc particle -observe device: slamgpu_run_particle, batched; -loop step hands it one iteration per call)
+    const bool particle_dev = particle && observe_dev;
+    const bool batched = c.method != 0 && !plot.active() && !parity && !gated && (!particle || particle_dev) && (c.s("loop") != "step" || particle_dev);
     auto numkey = [&](const char *key, double dflt) { return c.s(key).empty() ? dflt : atof(c.s(key).c_str()); };
     slamgpu_particle_assoc popt{};
     long pp_opened = 0, pp_reused = 0, pp_dropped = 0;
     int pp_most = 0;
     if (observe_dev && !batched) {
-        fprintf(stderr, "-observe device needs a FastSLAM method, -rng philox, known association and no -plot / -loop step\n");
+        fprintf(stderr, "-observe device needs a FastSLAM method, -rng philox, known or per-particle association and no -plot (nor -loop step with the "
+                        "known association)\n");
         return EXIT_FAILURE;
     }
     if (c.method != 0) {
@@ -425,7 +475,8 @@ int main(int argc, char **argv) {
     }
 
     if (batched) {
-        const int rcb = run_batched(sim, ctx, observe_dev, maxsteps, log, c.s("gpubusy") == "1");
+        const int rcb = run_batched(sim, ctx, observe_dev, maxsteps, log, c.s("gpubusy") == "1", particle_dev ? &popt : nullptr,
+                                    particle_dev && c.s("loop") == "step" ? 1 : 256);
         if (log) fclose(log);
         slamgpu_destroy(ctx);
         return rcb;
@@ -681,30 +732,7 @@ int main(int argc, char **argv) {
                "left unused, %d refused as new next to a mapped landmark)\n",
                nfl - policy.n_retired, policy.n_opened, policy.n_retired, nfl - policy.n_retired, policy.n_rescued, policy.n_discarded_votes, policy.n_new_refused);
     } else if (ctx && particle) {
-        // the map of the best (largest-weight) particle: what a FastSLAM with per-particle association reports
-        const int slots = slamgpu_num_landmarks(ctx);
-        std::vector<float> w((size_t) N);
-        int held = 0, covered = 0, best = 0;
-        if (slots >= 0 && slamgpu_download_range(ctx, 0, N, nullptr, nullptr, w.data(), nullptr, nullptr) == 0) {
-            for (int i = 1; i < N; i++)
-                if (w[(size_t) i] > w[(size_t) best]) best = i;
-            std::vector<float> xf(2 * (size_t) std::max(slots, 1));
-            if (slots > 0 && slamgpu_download_range(ctx, best, 1, nullptr, nullptr, nullptr, xf.data(), nullptr) == 0) {
-                std::vector<char> hit((size_t) sim.map.nlm, 0);
-                for (int j = 0; j < slots; j++) {
-                    if (xf[2 * (size_t) j] != xf[2 * (size_t) j]) continue;  // absent
-                    held++;
-                    for (int t = 0; t < sim.map.nlm; t++) {
-                        const float dx = xf[2 * (size_t) j] - sim.map.lm[(size_t) t], dy = xf[2 * (size_t) j + 1] - sim.map.lm[(size_t) sim.map.nlm + t];
-                        if (dx * dx + dy * dy < 1.0f) hit[(size_t) t] = 1;
-                    }
-                }
-                for (char h : hit) covered += h;
-            }
-        }
-        printf("landmarks in map: %d (the best particle's, number %d; %d of the %d true landmarks within 1 m of one of them; %d slots in use by all particles "
-               "together, %ld opened, %ld of them dead slots reused, %ld observations dropped for want of a slot, at most %d slots rewritten in a step)\n",
-               held, best, covered, sim.map.nlm, slots, pp_opened, pp_reused, pp_dropped, pp_most);
+        print_particle_map(ctx, sim, N, pp_opened, pp_reused, pp_dropped, pp_most);
     } else if (ctx) printf("landmarks in map: %d\n", slamgpu_num_landmarks(ctx));
     else printf("landmarks in map: %d\n", ekf.num_features());
     if (plot.active()) {

@@ -328,7 +328,12 @@ struct PerParticle {
     const float *wf;         // [ncap] weight factor of the observations the particle leaves unexplained: p_new ^ count (log-weights: count * log p_new)
     const uint8_t *any;      // [ncap] bit 0: the particle matched a landmark, bit 1: it opens one (neither: the step leaves its pose alone)
     int32_t nz, z_lds;       // observations of the step; 1: the launch stages z in LDS (2 nz floats fit: launch_update_any)
+    // device-driven steps (slamgpu_run_particle, update_kernel<.., PPD = true>): nz is read from the observe kernel's output and the
+    // Philox step from the bookkeeping state; nz = 0 makes the launch a no-op (the host launched it without knowing)
+    const struct ObserveOut *obs_dev;
+    const uint32_t *step_dev;
 };
+
 constexpr int kPpLdsObs = 2048;  // most observations a launch stages in LDS (16 KB)
 constexpr float kAbsent = __builtin_nanf("");  // xf.x / xf.y of an absent record
 
@@ -575,6 +580,39 @@ struct AssocGridArgs {
     int32_t logw;                 // the context keeps log-weights
 };
 
+// ---- per-particle association driven by the device (slamgpu_run_particle) ---------------------------------------------------
+// The host-side per-particle state of slamgpu_update_particle (pp_partial, pp_dead, the retired mask, pp_steps, obs_step, nf and the
+// genealogy row tables) lives in device memory while a context is driven this way; pp_book_kernel does what do_update_particle does
+// on the host between its synchronisations.  book_pull / book_push hand it over.
+struct PpState {
+    int32_t updated;         // the last iteration made an update: its resampling stage is outstanding
+    uint32_t step;           // observation-step counter (slamgpu_ctx::obs_step): the Philox stream of that update
+    uint32_t steps_lo, steps_hi;  // per-particle updates made (slamgpu_ctx::pp_steps): the holders census is due every census_every
+    int32_t census_cap;      // how many partial slots the holders census counts at most (slamgpu_ctx::pp_nz_cap's rule)
+    int32_t n_rows;          // genealogy rows in use (PpArgs::rows)
+    int32_t n_dead, n_retired;
+    int32_t n_list;          // partial, non-dead slots listed for the holders census (PpArgs::list)
+    int32_t pad[7];
+};
+struct PpArgs {
+    PpState *st;
+    DevBook *book;           // nf, fresh_row (kept at -1: the update reads every record through the genealogy)
+    int32_t *erow, *live, *refcnt, *rows;  // [cap_nf] [cap_nf] [cap_rows] [cap_rows]: rows in use, ascending
+    int32_t *partial, *dead; // [cap_nf] 0 / 1
+    int32_t *first, *hold, *uidx, *list, *dlist;  // [cap_nf]: census first (preset INT_MAX), holders (preset 0), packet entry, census list, scratch
+    int32_t *news, *newk, *idn;  // [map_n]: news (preset 0), new-slot entry per observation, slots of the new entries
+    uint32_t *retired;       // [(cap_nf + 31) / 32]
+    const ObserveOut *obs;   // the iteration's observations: nz, then z[2 map_n]
+    ObsPacket *pkt;          // fixed layout, cap = cap_nf
+    int32_t *report;         // [8]: this iteration's report (slamgpu_update_particle's fields)
+    double *hist;            // history slot of this iteration (an iteration without observations records its estimate here)
+    WeightScratch ws;
+    int32_t cap_nf, cap_rows, n, need;  // need: particles that must call an observation new (max(1, ceil(new_share N)))
+    int32_t census_every;
+    float p_new;
+    int32_t logw, pad;
+};
+
 struct KernelTable {
     // the step: [resampling stage of the previous update, inline] + [gather] + [fused predicts] + per-particle observation
     // update + in-block weight prefix / totals  (+ helper blocks: genealogy copy, Ctrl words, estimate reduction)
@@ -653,6 +691,19 @@ struct KernelTable {
     void (*pp_resolve)(hipStream_t, const int32_t *labels_dev, int n, int nz, int ncap, const int32_t *uidx_dev, const int32_t *newk_dev, int m, int nn,
                        float p_new, int logw, int16_t *obs_dev, float *wf_dev, uint8_t *any_dev);
     void (*pp_holders)(hipStream_t, const Buffers &, int count, const int32_t *ids_dev, int32_t *holders_dev);  // ids (may be null: 0 .. count - 1)
+    // slamgpu_run_particle: one iteration's stages, every size read from device memory (PpArgs).  resample: the outstanding resampling
+    // stage of the previous iteration, if it updated (resample_kernel<true>); gather: the lazy gather over the rows in use, and in one
+    // more block the estimate of that stage; associate: the exhaustive scan with the label and holders census in the launch (no
+    // observation: the estimate partials instead); book: the bookkeeping, packet and report (no observation: the estimate); resolve:
+    // pp_resolve with the packet's sizes; update_particle_dev: update_kernel<.., PPD = true> (no observation: nothing)
+    void (*pp_resample)(hipStream_t, const Buffers &, const WeightScratch &, const RngArgs &, const ResampleArgs &, const PpArgs &);
+    void (*pp_gather)(hipStream_t, const Buffers &, const WeightScratch &, const PpArgs &, double *hist, int par);
+    void (*pp_associate)(hipStream_t, const Buffers &, const float *R4, float gate_reject, float gate_augment, const float *excl3, int32_t *labels_dev,
+                         const PpArgs &);
+    void (*pp_book)(hipStream_t, const Buffers &, const PpArgs &);
+    void (*pp_resolve_dev)(hipStream_t, const int32_t *labels_dev, int n, int ncap, const PpArgs &, int16_t *obs_dev, float *wf_dev, uint8_t *any_dev);
+    void (*update_particle_dev)(hipStream_t, const Buffers &, const PredictArgs &, const UpdateArgs &, const RngArgs &, const WeightScratch &,
+                                const PerParticle &);
 };
 
 const KernelTable *kernels_strict();

@@ -1344,11 +1344,26 @@ struct StepCarry {
 };
 
 // (PPT: per-particle association, kernels.h: PerParticle -- plain rows, single contexts; every other instantiation compiles the text it always did)
-template <int METHOD, int MODE, bool BIG, bool PPT = false>
+// (PPD: the same, driven by the device (slamgpu_run_particle): the observation count and the Philox step come from device memory, and a
+// step without observations leaves everything as it was -- the host launched it without knowing)
+template <int METHOD, int MODE, bool BIG, bool PPT = false, bool PPD = false>
 __global__ void __launch_bounds__(kBlock) update_kernel(const float *__restrict__ h_tot, Ctrl *h_ctrl,
                                                          const FrontState *h_front, int h_nb, int h_slot, int h_grid, int h_flags, Buffers B, PredictArgs PA,
                                                          UpdateArgs U, RngArgs rng, WeightScratch ws, PerParticle ppa) {
     static_assert(!PPT || (BIG && MODE == 0), "per-particle association: plain rows, single contexts");
+    static_assert(!PPD || PPT, "device-driven steps are per-particle steps");
+    if constexpr (PPD) {
+        const int nz_dev = ppa.obs_dev->nz;
+        if (nz_dev == 0) {  // (the set stays where it is: the next launch reads the same Ctrl words from the other slot)
+            if (blockIdx.x == 0 && threadIdx.x == 0) {
+                h_ctrl->live[h_slot ^ 1] = h_ctrl->live[h_slot];
+                h_ctrl->pend[h_slot ^ 1] = h_ctrl->pend[h_slot];
+            }
+            return;
+        }
+        ppa.nz = nz_dev;
+        rng.step = *ppa.step_dev;
+    }
     constexpr bool PERSIST = false, PP = PPT;
     const PersistStep *const qe = nullptr;
     StepCarry carry;  // (unused by a per-step launch)
@@ -1834,13 +1849,25 @@ __global__ void __launch_bounds__(kBlock) resample_ref_kernel(Buffers B, WeightS
     }
 }
 
+// (PPD: slamgpu_run_particle -- the stage of the previous iteration's update, if it made one (PpState::updated), with that update's step)
+template <bool PPD = false>
 __global__ void __launch_bounds__(kBlock) resample_kernel(Buffers B, WeightScratch ws, RngArgs rng, ResampleArgs ra,
-                                                           UpdateArgs U) {
+                                                           UpdateArgs U, const PpState *pst) {
     extern __shared__ double off[];  // [nblocks + 1] exclusive prefix of the block totals
     __shared__ double sh_a[kBlock / kWave], sh_q[kBlock / kWave];
     __shared__ EstItem sh_est[kBlock / kWave];
     Ctrl *ctrl = B.ctrl;
     const int t = threadIdx.x;
+    if constexpr (PPD) {
+        if (!pst->updated) {  // (nothing outstanding: the set stays where it is)
+            if (blockIdx.x == 0 && t == 0) {
+                ctrl->live[B.slot ^ 1] = ctrl->live[B.slot];
+                ctrl->pend[B.slot ^ 1] = ctrl->pend[B.slot];
+            }
+            return;
+        }
+        rng.step = pst->step;
+    }
     const int nb = ws.nblocks;
     // every update launch publishes where it left the set (pend = 0) and the host flips its slot: plain read here
     const int cur = ctrl->live[B.slot];
@@ -2528,6 +2555,80 @@ SLAM_DEV void assoc_gate(const AssocLm &A, float zr, float zb, float &nis, float
     nd = nis + A.ldet;
 }
 
+// ---- slamgpu_run_particle: what rides in the association launch (associate_kernel<.., DEV = true>) ----
+// an iteration without observations: the pose-estimate partials of the set, as estimate_kernel makes them
+SLAM_DEV void pp_estimate_partials(const Buffers &B, const WeightScratch &ws) {
+    __shared__ EstItem sh_est[kBlock / kWave];
+    const int t = threadIdx.x;
+    const int i = blockIdx.x * kBlock + t;
+    EstItem ei{0.0, 0.0, -3.0e38f, 0.0f, 0x7fffffff};
+    if (i < B.n) {
+        const float4 pa = B.poseA[B.ctrl->live[B.slot]][i];
+        ei = EstItem{(double) pa.x, (double) pa.y, pa.w, pa.z, i};
+    }
+    ei = block_reduce_est(ei, sh_est);
+    if (t == 0) {
+        double *p = ws.est_part[ws.wpar] + (size_t) blockIdx.x * 4;
+        p[0] = ei.sx;
+        p[1] = ei.sy;
+        p[2] = (double) ei.th;
+        p[3] = (double) ei.w;
+        if (blockIdx.x == 0) {
+            ws.est_part[ws.wpar][4 * (size_t) ws.nblocks] = (double) B.ctrl->neff;
+            ws.est_part[ws.wpar][4 * (size_t) ws.nblocks + 1] = (double) (B.ctrl->resampled | (B.ctrl->status << 1));
+        }
+    }
+}
+// the holders census, when it is due (do_update_particle's rule): particles that hold each listed slot (PpArgs::list: the partial,
+// non-dead slots in ascending order, at most census_cap of them), counted in LDS per block and added once per block and slot, as pp_holders_kernel does.  Every
+// thread of the block comes here (before the association's early return).
+SLAM_DEV void pp_count_holders(const Buffers &B, int nf, int nz, const PpArgs &P) {
+    constexpr int kChunk = 1024;
+    __shared__ int32_t sh[kChunk];
+    const uint64_t steps = ((uint64_t) P.st->steps_hi << 32) | P.st->steps_lo;
+    // (only the slots pp_book_kernel will look at: the first census_cap of the list, the cap grown for this step's observations as it grows it there)
+    const int cap = nz > P.st->census_cap ? max(64, 2 * nz) : P.st->census_cap;
+    const int count = min(P.st->n_list, cap);
+    if (!(P.census_every > 0 && nf > 0 && steps % (uint64_t) P.census_every == 0) || count == 0) return;
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    const bool on = i < B.n;
+    const int cur = B.ctrl->live[B.slot];
+    const size_t S = (size_t) B.ncap;
+    for (int l0 = 0; l0 < count; l0 += kChunk) {
+        const int ln = min(kChunk, count - l0);
+        for (int t = threadIdx.x; t < ln; t += kBlock) sh[t] = 0;
+        __syncthreads();
+        for (int l = l0; l < l0 + ln; l++) {
+            const int slot = P.list[l];
+            bool has = false;
+            if (on) {
+                float4 la;
+                float lb;
+                read_through_genealogy(B, B.lmk_live, cur, S, slot, i, la, lb);
+                has = la.x == la.x;
+            }
+            const unsigned long long hm = __ballot(has);
+            if (hm && (threadIdx.x & (kWave - 1)) == (int) __ffsll((long long) __ballot(true)) - 1) atomicAdd(sh + (l - l0), (int) __popcll(hm));
+        }
+        __syncthreads();
+        for (int t = threadIdx.x; t < ln; t += kBlock)
+            if (sh[t]) atomicAdd(P.hold + P.list[l0 + t], sh[t]);
+        __syncthreads();
+    }
+}
+// the label census (pp_census_kernel's, where the label is made): first[l] = lowest observation naming slot l, news[j] = particles calling j new
+SLAM_DEV void pp_census_label(int lab, int j, const PpArgs &P) {
+    unsigned long long todo = __ballot(lab >= 0);
+    while (todo) {
+        const int src = __ffsll((long long) todo) - 1;
+        const int lab0 = __builtin_amdgcn_readlane(lab, src);
+        if ((int) (threadIdx.x & (kWave - 1)) == src && P.first[lab0] > j) atomicMin(P.first + lab0, j);
+        todo &= ~__ballot(lab == lab0);
+    }
+    const unsigned long long nw = __ballot(lab == kAssocNew);
+    if (nw && (threadIdx.x & (kWave - 1)) == (int) __ffsll((long long) __ballot(true)) - 1) atomicAdd(P.news + j, (int) __popcll(nw));
+}
+
 // EXCL (slamgpu_particle_assoc::excl_*; slamgpu_associate never): the EXCLUSION rule of a particle's own map.  The gates measure an
 // observation against S = Hf Pf Hf^T + R -- for a converged landmark that is R, half a metre at five sigma -- and know nothing of the
 // particle's own pose error (the EKF's S carries it, ekfslam.cpp:160-176; a particle's pose is a point).  So a particle a metre off
@@ -2535,10 +2636,22 @@ SLAM_DEV void assoc_gate(const AssocLm &A, float zr, float zb, float &nis, float
 // gates is placed in the world from the particle's pose; if a landmark of the particle lies within excl_base + excl_per_m * range of
 // that point the observation cannot be new: it is matched with that landmark when no other is within unique_ratio times the distance
 // (the update then pulls pose and landmark together, at the price of the innovation's likelihood), and discarded otherwise.
-template <bool EXCL>
+// (DEV: slamgpu_run_particle -- nz, nf and the observations from device memory (PpArgs); the census of the labels and, when it is due,
+// of the holders rides in this launch; an iteration without observations takes the estimate partials instead)
+template <bool EXCL, bool DEV = false>
 __global__ void __launch_bounds__(kBlock) associate_kernel(Buffers B, int nf, const float *__restrict__ z, int nz, float r00, float r01,
                                                             float r10, float r11, float gate1, float gate2, float excl_base, float excl_per_m, float unique_ratio,
-                                                            const uint32_t *__restrict__ retired, int32_t *__restrict__ labels, int by_obs) {
+                                                            const uint32_t *__restrict__ retired, int32_t *__restrict__ labels, int by_obs, PpArgs P) {
+    if constexpr (DEV) {
+        nz = P.obs->nz;
+        if (nz == 0) {
+            pp_estimate_partials(B, P.ws);
+            return;
+        }
+        nf = P.book->nf;
+        z = reinterpret_cast<const float *>(P.obs + 1);
+        pp_count_holders(B, nf, nz, P);
+    }
     const int i = blockIdx.x * kBlock + threadIdx.x;
     if (i >= B.n) return;
     const int cur = B.ctrl->live[B.slot];
@@ -2624,6 +2737,7 @@ __global__ void __launch_bounds__(kBlock) associate_kernel(Buffers B, int nf, co
                     if (jbest[q] < 0 && d1[q] < rho * rho) label = d2[q] > unique_ratio * unique_ratio * d1[q] ? j1[q] : kAssocDiscard;
                 }
                 labels[by_obs ? (size_t) (q0 + q) * S + i : (size_t) i * nz + q0 + q] = label;  // (by_obs: [nz][ncap], what the per-particle update reads)
+                if constexpr (DEV) pp_census_label(label, q0 + q, P);
             }
     }
 }
@@ -3399,6 +3513,232 @@ __global__ void __launch_bounds__(kBlock) shard_finalize_kernel(Buffers B, Weigh
 }
 
 // ---------------------------------------------------------------------------------------------------
+// slamgpu_run_particle (kernels.h: PpState / PpArgs): the lazy gather over the rows in use (their count is device state), and in block
+// (nblocks, 0) the estimate of the stage resample_kernel<true> has just run, if it ran
+__global__ void __launch_bounds__(kBlock) pp_gather_kernel(Buffers B, WeightScratch ws, PpArgs P, double *hist, int par) {
+    __shared__ EstItem sh_est[kBlock / kWave];
+    if ((int) blockIdx.x == ws.nblocks) {
+        if (blockIdx.y == 0 && P.st->updated) finish_estimate(B, ws, par, hist, sh_est);
+        return;
+    }
+    Ctrl *ctrl = B.ctrl;
+    const int cur = ctrl->live[B.slot];
+    const bool pend = ctrl->pend[B.slot] != 0;
+    if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) {
+        ctrl->live[B.slot ^ 1] = pend ? cur ^ 1 : cur;
+        ctrl->pend[B.slot ^ 1] = 0;
+    }
+    if (!pend) return;
+    const int k = blockIdx.x * kBlock + threadIdx.x;
+    if (k >= B.n) return;
+    const int anc = ws.keep[B.slot][k];
+    const size_t S = (size_t) B.ncap;
+    if (blockIdx.y == 0) {
+        float4 pa = B.poseA[cur][anc];
+        pa.w = ctrl->inv_n;
+        B.poseA[cur ^ 1][k] = pa;
+        B.poseB[cur ^ 1][k] = B.poseB[cur][anc];
+        B.poseC[cur ^ 1][k] = B.poseC[cur][anc];
+    }
+    const int32_t *__restrict__ src = B.gen[cur];
+    int32_t *__restrict__ dst = B.gen[cur ^ 1];
+    const int r0 = blockIdx.y * kRowsPerRole, r1 = min(P.st->n_rows, r0 + kRowsPerRole);
+    for (int r = r0; r < r1; r++) {
+        const size_t e = (size_t) P.rows[r];
+        dst[e * S + k] = src[e * S + anc];
+    }
+}
+
+// The host's block of do_update_particle between its two synchronisations, in one workgroup: the touched slots ordered by (first
+// observation, slot); the holders census (dead slots leave the association); slots for the observations enough particles call new
+// (the lowest dead slot first, then growth, else dropped); the genealogy moves; the fixed-layout packet; the report.  Row numbers
+// may differ from the host's (the lowest free row is opened); what is read through the genealogy does not.  No observation: the
+// estimate of the set instead (the association launch made the partials).
+__global__ void __launch_bounds__(kBlock) pp_book_kernel(Buffers B, PpArgs P) {
+    __shared__ EstItem sh_est[kBlock / kWave];
+    __shared__ int sh[kBlock / kWave];
+    __shared__ int sh_cnt[4];  // dead slots made, retired bits set, retired bits cleared; lowest free row
+    const int t = threadIdx.x;
+    PpState *st = P.st;
+    const int nz = P.obs->nz;
+    if (nz == 0) {  // (no update: pp_steps and the step counter stay; the report is all zeros)
+        if (t < 8) P.report[t] = 0;
+        if (t == 0) st->updated = 0;
+        finish_estimate(B, P.ws, P.ws.wpar, P.hist, sh_est);
+        return;
+    }
+    const int nf0 = P.book->nf, N = P.n, cap_nf = P.cap_nf;
+    const uint64_t steps = ((uint64_t) st->steps_hi << 32) | st->steps_lo;
+    const bool due = P.census_every > 0 && nf0 > 0 && steps % (uint64_t) P.census_every == 0;
+    const int cap = nz > st->census_cap ? max(64, 2 * nz) : st->census_cap;  // (pp_reserve's rule for pp_nz_cap)
+    const int n_list = min(st->n_list, cap);
+    const bool census = due && n_list > 0;
+    if (t < 4) sh_cnt[t] = t == 3 ? 0x7fffffff : 0;
+    // touched slots: packet entry = rank by (first observation, slot)
+    int m = 0;
+    for (int l0 = 0; l0 < nf0; l0 += kBlock) {
+        const int l = l0 + t;
+        const int f = l < nf0 ? P.first[l] : 0x7fffffff;
+        const bool touched = f != 0x7fffffff;
+        if (l < nf0) {
+            int k = -1;
+            if (touched) {
+                k = 0;
+                for (int l2 = 0; l2 < nf0; l2++) {
+                    const int f2 = P.first[l2];
+                    k += (f2 < f || (f2 == f && l2 < l)) ? 1 : 0;
+                }
+            }
+            P.uidx[l] = k;
+        }
+        int tot;
+        (void) block_exclusive_count(touched ? 1 : 0, sh, tot);
+        m += tot;
+    }
+    // holders census: a slot every particle holds stays held; a slot nobody holds (and nobody matched) is dead
+    if (census)
+        for (int q = t; q < n_list; q += kBlock) {
+            const int l = P.list[q], h = P.hold[l];
+            if (h == N) P.partial[l] = 0;
+            if (h == 0 && P.first[l] == 0x7fffffff) {
+                P.dead[l] = 1;
+                atomicAdd(&sh_cnt[0], 1);
+                const uint32_t bit = 1u << (l & 31);
+                if (!(atomicOr(P.retired + (l >> 5), bit) & bit)) atomicAdd(&sh_cnt[1], 1);
+            }
+        }
+    __syncthreads();
+    // dead slots in ascending order (the host's sorted pp_dead_list, lowest first)
+    int D = 0;
+    for (int l0 = 0; l0 < nf0; l0 += kBlock) {
+        const int l = l0 + t;
+        const bool d = l < nf0 && P.dead[l];
+        int tot;
+        const int at = D + block_exclusive_count(d ? 1 : 0, sh, tot);
+        if (d) P.dlist[at] = l;
+        D += tot;
+    }
+    __syncthreads();
+    // new landmarks, in observation order: a dead slot first, then growth, else dropped
+    const int room = cap_nf - nf0;
+    int Q = 0;
+    for (int j0 = 0; j0 < nz; j0 += kBlock) {
+        const int j = j0 + t;
+        const bool qv = j < nz && P.news[j] >= P.need;
+        int tot;
+        const int at = Q + block_exclusive_count(qv ? 1 : 0, sh, tot);
+        if (j < nz) {
+            const int slot = !qv ? -1 : (at < D ? P.dlist[at] : (at - D < room ? nf0 + at - D : -1));
+            P.newk[j] = slot >= 0 ? at : -1;
+            if (slot >= 0) {
+                P.idn[at] = slot;
+                P.partial[slot] = P.news[j] < N ? 1 : 0;
+            }
+        }
+        Q += tot;
+    }
+    const int reused = min(Q, D), fresh = min(max(Q - D, 0), room), dropped = Q - reused - fresh, n = reused + fresh;
+    // a dead slot that comes back rejoins the association
+    for (int q = t; q < reused; q += kBlock) {
+        const int l = P.dlist[q];
+        P.dead[l] = 0;
+        const uint32_t bit = 1u << (l & 31);
+        if (atomicAnd(P.retired + (l >> 5), ~bit) & bit) atomicAdd(&sh_cnt[2], 1);
+    }
+    // the row this update opens: the lowest unused one
+    if (m + n > 0)
+        for (int r = t; r < P.cap_rows; r += kBlock)
+            if (P.refcnt[r] == 0) {
+                atomicMin(&sh_cnt[3], r);
+                break;
+            }
+    __syncthreads();
+    const int e_new = m + n > 0 ? sh_cnt[3] : -1;
+    int32_t *const base = reinterpret_cast<int32_t *>(P.pkt + 1);
+    int32_t *const pidf = base;
+    float *const pzf = reinterpret_cast<float *>(base + cap_nf), *const pzn = pzf + 2 * (size_t) cap_nf;
+    int32_t *const prow = reinterpret_cast<int32_t *>(pzn + 2 * (size_t) cap_nf), *const prows = prow + cap_nf;
+    // every packet entry is written by every particle and moves to the row this update opens (do_update_particle: leave_row)
+    for (int l = t; l < nf0; l += kBlock) {
+        const int k = P.uidx[l];
+        if (k < 0) continue;
+        const int r = P.erow[l];
+        prow[k] = r | (P.live[l] ? kRowLiveBit : 0);
+        pidf[k] = l;
+        pzf[2 * k] = 0.0f;  // (the observations are per particle: PerParticle::z)
+        pzf[2 * k + 1] = 0.0f;
+        P.live[l] ^= 1;
+        atomicSub(P.refcnt + r, 1);
+        P.erow[l] = e_new;
+    }
+    for (int q = t; q < n; q += kBlock) {
+        const int l = P.idn[q];
+        if (l < nf0) atomicSub(P.refcnt + P.erow[l], 1);
+        P.erow[l] = e_new;
+        P.live[l] = 0;  // a new landmark's first records go to buffer 0
+        pzn[2 * q] = 0.0f;
+        pzn[2 * q + 1] = 0.0f;
+    }
+    __syncthreads();
+    if (t == 0 && e_new >= 0) P.refcnt[e_new] = m + n;  // (it was unused)
+    __syncthreads();
+    // rows in use (ascending: what the next gather composes) and, without the one opened now, the packet's rows
+    int nr = 0, np = 0;
+    for (int r0 = 0; r0 < P.cap_rows; r0 += kBlock) {
+        const int r = r0 + t;
+        const bool in = r < P.cap_rows && P.refcnt[r] > 0;
+        int tot, totp;
+        const int at = nr + block_exclusive_count(in ? 1 : 0, sh, tot);
+        const int ap = np + block_exclusive_count((in && r != e_new) ? 1 : 0, sh, totp);
+        if (in) P.rows[at] = r;
+        if (in && r != e_new) prows[ap] = r;
+        nr += tot;
+        np += totp;
+    }
+    const int nf = nf0 + fresh;
+    const int n_dead = st->n_dead + sh_cnt[0] - reused;
+    if (t == 0) {
+        P.pkt->m = m;
+        P.pkt->n = n;
+        P.pkt->nf = nf0;
+        P.pkt->n_rows = np;
+        P.pkt->e_new = e_new;
+        P.pkt->status = 0;
+        P.pkt->cap = cap_nf;
+        P.pkt->pad = 0;
+        P.book->nf = nf;
+        P.book->fresh_row = -1;
+        st->updated = 1;
+        st->step = st->step + 1;
+        const uint64_t s2 = steps + 1;
+        st->steps_lo = (uint32_t) s2;
+        st->steps_hi = (uint32_t) (s2 >> 32);
+        st->census_cap = cap;
+        st->n_rows = nr;
+        st->n_dead = n_dead;
+        st->n_retired = st->n_retired + sh_cnt[1] - sh_cnt[2];
+        const int32_t rep[8] = {m, n, reused, dropped, nf, n_dead, P.need, census ? 1 : 0};
+        for (int q = 0; q < 8; q++) P.report[q] = rep[q];
+    }
+    // the census words back to their presets for the next iteration; the next holders census's list
+    for (int l = t; l < nf0; l += kBlock) {
+        P.first[l] = 0x7fffffff;
+        P.hold[l] = 0;
+    }
+    for (int j = t; j < nz; j += kBlock) P.news[j] = 0;
+    int nl = 0;
+    for (int l0 = 0; l0 < nf; l0 += kBlock) {
+        const int l = l0 + t;
+        const bool in = l < nf && P.partial[l] && !P.dead[l];
+        int tot;
+        const int at = nl + block_exclusive_count(in ? 1 : 0, sh, tot);
+        if (in) P.list[at] = l;
+        nl += tot;
+    }
+    if (t == 0) st->n_list = nl;
+}
+
+// ---------------------------------------------------------------------------------------------------
 // launchers
 // ---------------------------------------------------------------------------------------------------
 static void launch_shard_plan(hipStream_t st, const ShardPlanArgs &A, const RngArgs &rng, ShardPlan *out, uint32_t *seq_out,
@@ -3428,7 +3768,7 @@ static void launch_shard_finish(hipStream_t st, const Buffers &B, const WeightSc
 }
 
 static void launch_update_any(hipStream_t st, const Buffers &B, const PredictArgs &PA, const UpdateArgs &U,
-                              const RngArgs &rng, const WeightScratch &ws, const PerParticle &ppa) {
+                              const RngArgs &rng, const WeightScratch &ws, const PerParticle &ppa, bool ppd = false) {
     // compute blocks first (they are the long pole), then -- single-context pipeline only -- the copy blocks of a
     // pending lazy gather (they exit at once when nothing is pending: the host cannot know) and one helper block
     int grid = B.ncap / kBlock;
@@ -3459,7 +3799,10 @@ static void launch_update_any(hipStream_t st, const Buffers &B, const PredictArg
         PerParticle pq = ppa;
         pq.z_lds = pq.nz <= kPpLdsObs ? 1 : 0;
         const size_t lds_pp = lds + (size_t) kBigChunk * kBlock * sizeof(int32_t) + (pq.z_lds ? sizeof(float) * 2 * (size_t) pq.nz : 0);
-        if (U.method == 2) hipLaunchKernelGGL((update_kernel<2, 0, true, true>), dim3(grid), dim3(kBlock), lds_pp, st, h_tot, B.ctrl, U.front.state_in, ws.nblocks, B.slot, grid, h_flags, B, PA, U, rng, ws, pq);
+        // (ppd: pq.nz is the map's size, an upper bound of the device's count: LDS for that many)
+        if (ppd && U.method == 2) hipLaunchKernelGGL((update_kernel<2, 0, true, true, true>), dim3(grid), dim3(kBlock), lds_pp, st, h_tot, B.ctrl, U.front.state_in, ws.nblocks, B.slot, grid, h_flags, B, PA, U, rng, ws, pq);
+        else if (ppd) hipLaunchKernelGGL((update_kernel<1, 0, true, true, true>), dim3(grid), dim3(kBlock), lds_pp, st, h_tot, B.ctrl, U.front.state_in, ws.nblocks, B.slot, grid, h_flags, B, PA, U, rng, ws, pq);
+        else if (U.method == 2) hipLaunchKernelGGL((update_kernel<2, 0, true, true>), dim3(grid), dim3(kBlock), lds_pp, st, h_tot, B.ctrl, U.front.state_in, ws.nblocks, B.slot, grid, h_flags, B, PA, U, rng, ws, pq);
         else hipLaunchKernelGGL((update_kernel<1, 0, true, true>), dim3(grid), dim3(kBlock), lds_pp, st, h_tot, B.ctrl, U.front.state_in, ws.nblocks, B.slot, grid, h_flags, B, PA, U, rng, ws, pq);
         return;
     }
@@ -3507,7 +3850,7 @@ static void launch_update_persist(hipStream_t st, const Buffers &B, const Predic
 static void launch_resample(hipStream_t st, const Buffers &B, const WeightScratch &ws, const RngArgs &rng,
                             const ResampleArgs &ra, const UpdateArgs &U) {
     const size_t lds = sizeof(double) * ((size_t) ws.nblocks + 1);
-    hipLaunchKernelGGL(resample_kernel, dim3(ws.nblocks), dim3(kBlock), lds, st, B, ws, rng, ra, U);
+    hipLaunchKernelGGL(resample_kernel<false>, dim3(ws.nblocks), dim3(kBlock), lds, st, B, ws, rng, ra, U, nullptr);
 }
 
 static void launch_resample_ref(hipStream_t st, const Buffers &B, const WeightScratch &ws, const RngArgs &rng, const ResampleArgs &ra) {
@@ -3588,11 +3931,11 @@ static void launch_observe_book(hipStream_t st, const ObserveArgs &A) {
 static void launch_associate(hipStream_t st, const Buffers &B, int nf, const float *z, int nz, const float *R4, float g1, float g2, const float *excl3,
                              const uint32_t *retired, int32_t *labels, int by_obs) {
     if (excl3 && excl3[0] + excl3[1] > 0.0f)
-        hipLaunchKernelGGL(associate_kernel<true>, dim3(B.ncap / kBlock), dim3(kBlock), 0, st, B, nf, z, nz, R4[0], R4[1], R4[2], R4[3], g1, g2, excl3[0],
-                           excl3[1], excl3[2], retired, labels, by_obs);
+        hipLaunchKernelGGL((associate_kernel<true, false>), dim3(B.ncap / kBlock), dim3(kBlock), 0, st, B, nf, z, nz, R4[0], R4[1], R4[2], R4[3], g1, g2, excl3[0],
+                           excl3[1], excl3[2], retired, labels, by_obs, PpArgs{});
     else
-        hipLaunchKernelGGL(associate_kernel<false>, dim3(B.ncap / kBlock), dim3(kBlock), 0, st, B, nf, z, nz, R4[0], R4[1], R4[2], R4[3], g1, g2, 0.0f, 0.0f,
-                           0.0f, retired, labels, by_obs);
+        hipLaunchKernelGGL((associate_kernel<false, false>), dim3(B.ncap / kBlock), dim3(kBlock), 0, st, B, nf, z, nz, R4[0], R4[1], R4[2], R4[3], g1, g2, 0.0f, 0.0f,
+                           0.0f, retired, labels, by_obs, PpArgs{});
 }
 
 static void launch_kat(hipStream_t st, int op, const float *in, int n, float *out) {
@@ -3761,10 +4104,19 @@ __global__ void __launch_bounds__(kBlock) pp_census_kernel(const int32_t *__rest
 // is a bit in LDS (one column of words per thread) instead of a read of the obs row it has just initialised; contexts whose packet
 // has more entries than the LDS holds bits for -- lds_words = 0 -- read the row.  Before: 865 x two dependent trips, 0.92 ms.)
 constexpr int kResolveBatch = 8;
+// (DEV: slamgpu_run_particle -- nz from the observations, m and nn from the packet pp_book_kernel wrote; no observation: nothing to do)
+template <bool DEV = false>
 __global__ void __launch_bounds__(kBlock) pp_resolve_kernel(const int32_t *__restrict__ labels, int n, int nz, size_t S, const int32_t *__restrict__ uidx,
                                                              const int32_t *__restrict__ newk, int m, int nn, float p_new, int logw, int lds_words,
-                                                             int16_t *__restrict__ obs, float *__restrict__ wf, uint8_t *__restrict__ any) {
+                                                             int16_t *__restrict__ obs, float *__restrict__ wf, uint8_t *__restrict__ any, const ObsPacket *pkt,
+                                                             const ObserveOut *obs_out) {
     extern __shared__ uint32_t sh_claim[];  // [lds_words][kBlock]
+    if constexpr (DEV) {
+        nz = obs_out->nz;
+        if (nz == 0) return;
+        m = pkt->m;
+        nn = pkt->n;
+    }
     const int i = blockIdx.x * kBlock + threadIdx.x;
     if (i >= (int) S) return;
     for (int k = 0; k < m + nn; k++) obs[(size_t) k * S + i] = (int16_t) -1;
@@ -3863,16 +4215,45 @@ static void launch_pp_resolve(hipStream_t st, const int32_t *labels, int n, int 
                               float p_new, int logw, int16_t *obs, float *wf, uint8_t *any) {
     // claimed-entry bits in LDS while the packet's re-observed entries fit 48 KB of them (m <= 1 536: every step of the 10 000-landmark map)
     const int words = (m + 31) / 32, lds_words = words * kBlock * 4 <= 48 * 1024 ? words : 0;
-    hipLaunchKernelGGL(pp_resolve_kernel, dim3(ncap / kBlock), dim3(kBlock), (size_t) lds_words * kBlock * sizeof(uint32_t), st, labels, n, nz, (size_t) ncap, uidx, newk, m,
-                       nn, p_new, logw, lds_words, obs, wf, any);
+    hipLaunchKernelGGL(pp_resolve_kernel<false>, dim3(ncap / kBlock), dim3(kBlock), (size_t) lds_words * kBlock * sizeof(uint32_t), st, labels, n, nz, (size_t) ncap, uidx,
+                       newk, m, nn, p_new, logw, lds_words, obs, wf, any, nullptr, nullptr);
 }
 static void launch_pp_holders(hipStream_t st, const Buffers &B, int count, const int32_t *ids, int32_t *holders) {
     hipLaunchKernelGGL(pp_holders_kernel, dim3(B.ncap / kBlock), dim3(kBlock), 0, st, B, count, ids, holders);
 }
 
+static void launch_update_particle_dev(hipStream_t st, const Buffers &B, const PredictArgs &PA, const UpdateArgs &U, const RngArgs &rng,
+                                       const WeightScratch &ws, const PerParticle &ppa) {
+    launch_update_any(st, B, PA, U, rng, ws, ppa, true);
+}
+static void launch_pp_resample(hipStream_t st, const Buffers &B, const WeightScratch &ws, const RngArgs &rng, const ResampleArgs &ra, const PpArgs &P) {
+    const size_t lds = sizeof(double) * ((size_t) ws.nblocks + 1);
+    hipLaunchKernelGGL(resample_kernel<true>, dim3(ws.nblocks), dim3(kBlock), lds, st, B, ws, rng, ra, UpdateArgs{}, (const PpState *) P.st);
+}
+static void launch_pp_gather(hipStream_t st, const Buffers &B, const WeightScratch &ws, const PpArgs &P, double *hist, int par) {
+    const int gy = (P.cap_rows + kRowsPerRole - 1) / kRowsPerRole;  // (rows in use: at most cap_rows; the groups past the count leave at once)
+    hipLaunchKernelGGL(pp_gather_kernel, dim3(ws.nblocks + 1, gy), dim3(kBlock), 0, st, B, ws, P, hist, par);
+}
+static void launch_pp_associate(hipStream_t st, const Buffers &B, const float *R4, float g1, float g2, const float *excl3, int32_t *labels, const PpArgs &P) {
+    if (excl3 && excl3[0] + excl3[1] > 0.0f)
+        hipLaunchKernelGGL((associate_kernel<true, true>), dim3(B.ncap / kBlock), dim3(kBlock), 0, st, B, 0, (const float *) nullptr, 0, R4[0], R4[1], R4[2], R4[3], g1,
+                           g2, excl3[0], excl3[1], excl3[2], (const uint32_t *) P.retired, labels, 1, P);
+    else
+        hipLaunchKernelGGL((associate_kernel<false, true>), dim3(B.ncap / kBlock), dim3(kBlock), 0, st, B, 0, (const float *) nullptr, 0, R4[0], R4[1], R4[2], R4[3], g1,
+                           g2, 0.0f, 0.0f, 0.0f, (const uint32_t *) P.retired, labels, 1, P);
+}
+static void launch_pp_book(hipStream_t st, const Buffers &B, const PpArgs &P) { hipLaunchKernelGGL(pp_book_kernel, dim3(1), dim3(kBlock), 0, st, B, P); }
+static void launch_pp_resolve_dev(hipStream_t st, const int32_t *labels, int n, int ncap, const PpArgs &P, int16_t *obs, float *wf, uint8_t *any) {
+    // (the packet's entries are at most cap_nf: the claimed-entry bits for that many, when they fit)
+    const int words = (P.cap_nf + 31) / 32, lds_words = words * kBlock * 4 <= 48 * 1024 ? words : 0;
+    hipLaunchKernelGGL(pp_resolve_kernel<true>, dim3(ncap / kBlock), dim3(kBlock), (size_t) lds_words * kBlock * sizeof(uint32_t), st, labels, n, 0, (size_t) ncap,
+                       (const int32_t *) P.uidx, (const int32_t *) P.newk, 0, 0, P.p_new, P.logw, lds_words, obs, wf, any, (const ObsPacket *) P.pkt, P.obs);
+}
+
 static const KernelTable kTable = {launch_update, launch_update_particle, launch_update_persist, launch_resample, launch_resample_ref, launch_scan, launch_gather, launch_flatten, launch_identity, launch_decompact, launch_finish, launch_predict, launch_estimate, launch_jacobians, launch_kat, launch_observe, launch_observe_book, launch_associate,
                                    launch_shard_plan, launch_shard_pack, launch_shard_unpack, launch_shard_finish, launch_dist_gather, launch_dist_flags, launch_peek, launch_lmk_box, launch_assoc_grid, launch_assoc_lists, launch_vote_compact,
-                                   launch_associate_grid, launch_jacobians_multi, launch_pp_census, launch_pp_resolve, launch_pp_holders};
+                                   launch_associate_grid, launch_jacobians_multi, launch_pp_census, launch_pp_resolve, launch_pp_holders,
+                                   launch_pp_resample, launch_pp_gather, launch_pp_associate, launch_pp_book, launch_pp_resolve_dev, launch_update_particle_dev};
 
 }  // namespace SLAM_KNS
 

@@ -291,6 +291,20 @@ struct slamgpu_ctx {
     int64_t persist_launches = 0, persist_steps = 0;
     EstStage unplanned;           // the last update: resampling stage not run yet
     EstStage unreduced;           // an update whose partials exist (est_part[par]) but are not reduced yet
+    // per-particle association driven by the device (slamgpu_run_particle; kernels.h: PpState / PpArgs).  While pp_on_device the
+    // per-particle state (pp_partial, pp_dead, the retired mask, pp_steps, obs_step, nf, the row tables) lives in device memory and the
+    // host's copies are stale; pp_pull (through book_pull / flush_stages) brings it back, pp_push hands it over
+    bool pp_on_device = false;
+    PpState *pp_st_dev = nullptr;
+    int32_t *pp_words_dev = nullptr;  // partial | dead | first | hold | uidx | list | dlist [cap_nf each] | news | newk | idn [pp_words_w each]
+    int pp_words_w = 0;
+    char *pp_pkt_dev = nullptr;       // the update's packet (fixed layout, cap = cap_nf)
+    int32_t *pp_report_dev = nullptr; // [kHistCap][8] reports of the iterations not fetched yet
+    int pp_report_n = 0;
+    bool pp_stage_open = false;       // the previous iteration may have left a resampling stage (the device knows) and no gather has run since
+    double *pp_prev_hist = nullptr;   // ... its history slot and the parity of its weight scratch
+    int pp_prev_par = 0;
+    uint32_t pp_iter = 0;
 };
 
 namespace {
@@ -479,7 +493,10 @@ int front_setup(slamgpu_ctx *c) {
     return 0;
 }
 
+int pp_pull(slamgpu_ctx *c);
+
 int book_pull(slamgpu_ctx *c) {
+    if (c->pp_on_device) return pp_pull(c);
     if (!c->book_on_device) return 0;
     HIP_TRY(hipSetDevice(c->cfg.device));
     if (c->B.compact) {
@@ -645,6 +662,7 @@ int flatten(slamgpu_ctx *c) {
 // (normally the next update launches do it on the side): first the reduction of complete partials, then the plan of
 // the last update (resample_kernel: Neff, decision, ancestors into keep[], partials) and its reduction.
 int flush_stages(slamgpu_ctx *c) {
+    if (int rc = pp_pull(c)) return rc;  // (slamgpu_run_particle: the outstanding stage is known to the device only)
     if (!c->unreduced.has && !c->unplanned.has) return 0;
     HIP_TRY(hipSetDevice(c->cfg.device));
     c->B.slot = c->slot;
@@ -972,6 +990,8 @@ void slamgpu_destroy(slamgpu_ctx *c) {
     if (c->pp_tab_dev) (void) hipFree(c->pp_tab_dev);
     if (c->pp_wf_dev) (void) hipFree(c->pp_wf_dev);
     if (c->pp_any_dev) (void) hipFree(c->pp_any_dev);
+    for (void *p_ : {(void *) c->pp_st_dev, (void *) c->pp_words_dev, (void *) c->pp_pkt_dev, (void *) c->pp_report_dev})
+        if (p_) (void) hipFree(p_);
     for (void *p_ : {(void *) c->box_dev, (void *) c->assoc_ids_dev, (void *) c->cell_start_dev, (void *) c->cell_fill_dev, (void *) c->items_dev,
                      (void *) c->geom_dev})
         if (p_) (void) hipFree(p_);
@@ -3145,25 +3165,30 @@ int slamgpu_retire_landmarks(slamgpu_ctx *c, const int32_t *ids, int32_t count) 
 }
 
 namespace {
-int pp_reserve(slamgpu_ctx *c, int nz, size_t rows) {
-    const size_t S = (size_t) c->B.ncap, cap_nf = (size_t) c->B.cap_nf;
+// the census table (first / holders / news / idn) and the observations of the host-driven step, for `cap` observations: pp_nz_cap is
+// also the most partial slots the holders census counts (do_update_particle), so it only ever changes by this rule
+int pp_grow_tab(slamgpu_ctx *c, int cap) {
+    const size_t cap_nf = (size_t) c->B.cap_nf;
+    if (c->pp_z_dev) (void) hipFree(c->pp_z_dev);
+    if (c->pp_tab_dev) (void) hipFree(c->pp_tab_dev);
+    c->pp_z_dev = nullptr;
+    c->pp_tab_dev = nullptr;
+    c->pp_nz_cap = 0;
+    HIP_TRY(hipMalloc((void **) &c->pp_z_dev, sizeof(float) * 2 * (size_t) cap));
+    HIP_TRY(hipMalloc((void **) &c->pp_tab_dev, sizeof(int32_t) * (2 * cap_nf + 2 * (size_t) cap)));
+    c->pp_nz_cap = cap;
+    return 0;
+}
+
+// the per-particle buffers both paths use: labels [nz][ncap], PerParticle::obs rows, wf, any
+int pp_reserve_particles(slamgpu_ctx *c, int nz, size_t rows) {
+    const size_t S = (size_t) c->B.ncap;
     if (S * (size_t) nz > c->pp_lab_cap) {  // (by observation: [nz][ncap])
         if (c->pp_lab_dev) (void) hipFree(c->pp_lab_dev);
         c->pp_lab_dev = nullptr;
         c->pp_lab_cap = 0;
         HIP_TRY(hipMalloc((void **) &c->pp_lab_dev, sizeof(int32_t) * S * (size_t) nz));
         c->pp_lab_cap = S * (size_t) nz;
-    }
-    if (nz > c->pp_nz_cap || !c->pp_tab_dev) {
-        const int cap = std::max(64, 2 * nz);
-        if (c->pp_z_dev) (void) hipFree(c->pp_z_dev);
-        if (c->pp_tab_dev) (void) hipFree(c->pp_tab_dev);
-        c->pp_z_dev = nullptr;
-        c->pp_tab_dev = nullptr;
-        c->pp_nz_cap = 0;
-        HIP_TRY(hipMalloc((void **) &c->pp_z_dev, sizeof(float) * 2 * (size_t) cap));
-        HIP_TRY(hipMalloc((void **) &c->pp_tab_dev, sizeof(int32_t) * (2 * cap_nf + 2 * (size_t) cap)));
-        c->pp_nz_cap = cap;
     }
     if (rows > c->pp_obs_rows) {
         const size_t want = std::max<size_t>(rows, 2 * c->pp_obs_rows);
@@ -3176,6 +3201,12 @@ int pp_reserve(slamgpu_ctx *c, int nz, size_t rows) {
     if (!c->pp_wf_dev) HIP_TRY(hipMalloc((void **) &c->pp_wf_dev, sizeof(float) * S));
     if (!c->pp_any_dev) HIP_TRY(hipMalloc((void **) &c->pp_any_dev, S));
     return 0;
+}
+
+int pp_reserve(slamgpu_ctx *c, int nz, size_t rows) {
+    if (nz > c->pp_nz_cap || !c->pp_tab_dev)
+        if (int rc = pp_grow_tab(c, std::max(64, 2 * nz))) return rc;
+    return pp_reserve_particles(c, nz, rows);
 }
 
 int pp_check(slamgpu_ctx *c, const float *z, int32_t nz, const float R[4], const slamgpu_particle_assoc *opt) {
@@ -3466,6 +3497,379 @@ int slamgpu_update_labels(slamgpu_ctx *c, const float *z, int32_t nz, const floa
         HIP_TRY(hipStreamSynchronize(c->stream));  // (pageable source)
     }
     return do_update_particle(c, z, nz, R, opt, normals, strata, report);
+}
+
+// ---- per-particle association driven by the device (slamgpu_run_particle) ----
+namespace {
+constexpr int kPpWords = 7;  // int32 arrays of cap_nf words in pp_words_dev (kernels.h: PpArgs), then three of pp_words_w
+
+// device buffers of the device-driven path (grown with the map: news / newk / idn hold one word per observation)
+int pp_setup(slamgpu_ctx *c) {
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    if (int rc = book_staging(c)) return rc;  // (DevBook, refcnt_dev)
+    if (!c->retired_dev || c->retired.empty())
+        if (int rc = retired_upload(c)) return rc;
+    if (c->pp_words_w < std::max(c->map_n, c->B.cap_nf)) {
+        if (c->pp_words_dev) (void) hipFree(c->pp_words_dev);
+        c->pp_words_dev = nullptr;
+        c->pp_words_w = 0;
+        const int w = std::max(c->map_n, c->B.cap_nf);
+        HIP_TRY(hipMalloc((void **) &c->pp_words_dev, sizeof(int32_t) * ((size_t) kPpWords * c->B.cap_nf + 3 * (size_t) w)));
+        c->pp_words_w = w;
+    }
+    if (!c->pp_st_dev) HIP_TRY(hipMalloc((void **) &c->pp_st_dev, sizeof(PpState)));
+    if (!c->pp_pkt_dev) HIP_TRY(hipMalloc((void **) &c->pp_pkt_dev, c->pkt_bytes));
+    if (!c->pp_report_dev) HIP_TRY(hipMalloc((void **) &c->pp_report_dev, sizeof(int32_t) * 8 * (size_t) kHistCap));
+    return 0;
+}
+
+PpArgs pp_args(slamgpu_ctx *c) {
+    const size_t cn = (size_t) c->B.cap_nf, w = (size_t) c->pp_words_w;
+    int32_t *b = c->pp_words_dev;
+    PpArgs P{};
+    P.st = c->pp_st_dev;
+    P.book = c->book_dev;
+    P.erow = c->erow_dev;
+    P.live = c->live_dev;
+    P.refcnt = c->refcnt_dev;
+    P.rows = c->rows_dev;
+    P.partial = b;
+    P.dead = b + cn;
+    P.first = b + 2 * cn;
+    P.hold = b + 3 * cn;
+    P.uidx = b + 4 * cn;
+    P.list = b + 5 * cn;
+    P.dlist = b + 6 * cn;
+    P.news = b + kPpWords * cn;
+    P.newk = P.news + w;
+    P.idn = P.newk + w;
+    P.retired = c->retired_dev;
+    P.obs = c->obs_out_dev;
+    P.pkt = reinterpret_cast<ObsPacket *>(c->pp_pkt_dev);
+    P.report = c->pp_report_dev + 8 * (size_t) c->pp_report_n;
+    P.hist = c->hist_dev + kHistStride * (size_t) c->hist_n;
+    P.ws = c->ws;
+    P.cap_nf = c->B.cap_nf;
+    P.cap_rows = c->B.cap_rows;
+    P.n = c->B.n;
+    P.logw = c->cfg.log_weights;
+    return P;
+}
+
+// host -> device, one synchronisation: the state do_update_particle keeps on the host, and the outstanding stages of the last host-driven update
+int pp_push(slamgpu_ctx *c, int census_cap) {
+    if (c->pp_on_device) return 0;
+    if (int rc = book_pull(c)) return rc;  // (the known association's device-driven steps first)
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    // the outstanding stages of the host-driven steps and a pending lazy gather run now, as the host-driven iteration's first
+    // materialize would run them (the device-driven iterations only know of a stage their own update left, and gather through the
+    // ancestors of that stage's resample: keep[] of the slot the host was about to read)
+    if (int rc = materialize(c)) return rc;
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    const int cn = c->B.cap_nf, cr = c->B.cap_rows, nf = c->nf;
+    if (c->pp_partial.empty()) c->pp_partial.assign((size_t) cn, 0);
+    if (c->pp_dead.empty()) c->pp_dead.assign((size_t) cn, 0);
+    const size_t cnz = (size_t) cn;
+    std::vector<int32_t> words((size_t) kPpWords * cnz + 3 * (size_t) c->pp_words_w, 0);
+    int32_t *partial = words.data(), *dead = partial + cnz, *first = dead + cnz, *list = first + 3 * cnz;
+    int n_list = 0, n_dead = 0;
+    for (int l = 0; l < cn; l++) {
+        partial[l] = c->pp_partial[(size_t) l] ? 1 : 0;
+        dead[l] = c->pp_dead[(size_t) l] ? 1 : 0;
+        first[l] = 0x7fffffff;
+        n_dead += dead[l];
+        if (l < nf && partial[l] && !dead[l]) list[n_list++] = l;
+    }
+    std::vector<int32_t> rows;
+    for (int r = 0; r < cr; r++)
+        if (c->refcnt[(size_t) r] > 0) rows.push_back(r);
+    PpState st{};
+    st.updated = 0;  // (flushed above)
+    st.step = c->obs_step;
+    st.steps_lo = (uint32_t) c->pp_steps;
+    st.steps_hi = (uint32_t) (c->pp_steps >> 32);
+    st.census_cap = census_cap;
+    st.n_rows = (int32_t) rows.size();
+    st.n_dead = n_dead;
+    st.n_retired = c->n_retired;
+    st.n_list = n_list;
+    DevBook hb{};
+    hb.nf = nf;
+    hb.fresh_row = -1;
+    hb.status = c->front_status;
+    HIP_TRY(hipMemcpy(c->pp_words_dev, words.data(), sizeof(int32_t) * words.size(), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(c->pp_st_dev, &st, sizeof st, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(c->book_dev, &hb, sizeof hb, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(c->erow_dev, c->erow.data(), sizeof(int32_t) * cnz, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(c->live_dev, c->live_flag.data(), sizeof(int32_t) * cnz, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(c->refcnt_dev, c->refcnt.data(), sizeof(int32_t) * (size_t) cr, hipMemcpyHostToDevice));
+    if (!rows.empty()) HIP_TRY(hipMemcpy(c->rows_dev, rows.data(), sizeof(int32_t) * rows.size(), hipMemcpyHostToDevice));
+    if (c->retired_stale)
+        if (int rc = retired_upload(c)) return rc;
+    c->pp_stage_open = true;
+    c->pp_prev_hist = nullptr;
+    c->scan_ready = false;
+    c->B.erow = c->erow_dev;
+    c->B.rows = c->rows_dev;
+    c->B.lmk_live = c->live_dev;
+    c->pp_on_device = true;
+    return 0;
+}
+
+// device -> host, one synchronisation (book_pull / flush_stages call it)
+int pp_pull(slamgpu_ctx *c) {
+    if (!c->pp_on_device) return 0;
+    c->pp_on_device = false;
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    const int cn = c->B.cap_nf, cr = c->B.cap_rows;
+    const size_t cnz = (size_t) cn;
+    std::vector<int32_t> words(2 * cnz), erow(cnz), live(cnz), ref((size_t) cr), mask((cnz + 31) / 32);
+    PpState st{};
+    DevBook hb{};
+    HIP_TRY(hipMemcpy(words.data(), c->pp_words_dev, sizeof(int32_t) * words.size(), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&st, c->pp_st_dev, sizeof st, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&hb, c->book_dev, sizeof hb, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(erow.data(), c->erow_dev, sizeof(int32_t) * cnz, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(live.data(), c->live_dev, sizeof(int32_t) * cnz, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(ref.data(), c->refcnt_dev, sizeof(int32_t) * (size_t) cr, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(mask.data(), c->retired_dev, sizeof(uint32_t) * mask.size(), hipMemcpyDeviceToHost));
+    if (hb.nf < 0 || hb.nf > cn) return fail(SLAMGPU_ERR_INVALID, "device bookkeeping corrupt: nf = %d", hb.nf);
+    c->nf = hb.nf;
+    std::copy(erow.begin(), erow.end(), c->erow.begin());
+    std::copy(live.begin(), live.end(), c->live_flag.begin());
+    std::copy(ref.begin(), ref.end(), c->refcnt.begin());
+    book_rebuild(c);
+    c->fresh_row = -1;
+    c->pp_dead_list.clear();
+    c->n_retired = 0;
+    for (int l = 0; l < cn; l++) {
+        c->pp_partial[(size_t) l] = words[(size_t) l] ? 1 : 0;
+        c->pp_dead[(size_t) l] = words[cnz + l] ? 1 : 0;
+        c->retired[(size_t) l] = (mask[(size_t) l >> 5] >> (l & 31)) & 1u ? 1 : 0;
+        c->n_retired += c->retired[(size_t) l];
+    }
+    for (int l = cn - 1; l >= 0; l--)
+        if (c->pp_dead[(size_t) l]) c->pp_dead_list.push_back(l);  // back() = lowest dead slot
+    c->retired_stale = false;
+    c->pp_steps = ((uint64_t) st.steps_hi << 32) | st.steps_lo;
+    c->obs_step = st.step;
+    if (st.census_cap > c->pp_nz_cap)  // (the device's iterations grew it by pp_reserve's rule: the host's table follows)
+        if (int rc = pp_grow_tab(c, st.census_cap)) return rc;
+    c->pp_census_done = false;
+    // the last iteration's update (if it made one) leaves its resampling stage outstanding, as issue_update does
+    c->unplanned.has = st.updated != 0;
+    c->unplanned.par = c->pp_prev_par;
+    c->unplanned.step = st.step;
+    c->unplanned.nf = c->nf;
+    c->unplanned.hist = c->pp_prev_hist;
+    c->unreduced.has = false;
+    c->maybe_pending = false;
+    c->est_fresh = false;
+    c->scan_ready = false;
+    c->pp_stage_open = false;
+    return 0;
+}
+
+// the resampling stage the previous iteration may have left (resample_kernel<true> decides), its estimate, and the lazy gather
+int pp_dev_stage(slamgpu_ctx *c) {
+    if (!c->pp_stage_open) return 0;
+    PpArgs P = pp_args(c);
+    c->B.slot = c->slot;
+    ResampleArgs ra{};
+    ra.do_resample = c->cfg.resample;
+    ra.n_effective = c->cfg.n_effective;
+    ra.logw = c->cfg.log_weights;
+    WeightScratch ws = c->ws;
+    ws.wpar = c->pp_prev_par;
+    {
+        Timed t(c, "resample");
+        c->k->pp_resample(c->stream, c->B, ws, rng_args(c, 0), ra, P);
+    }
+    c->keep_slot = c->slot ^ 1;
+    c->slot ^= 1;
+    c->B.slot = c->slot;
+    {
+        Timed t(c, "gather");
+        c->k->pp_gather(c->stream, c->B, ws, P, c->pp_prev_hist, c->pp_prev_par);
+    }
+    c->slot ^= 1;
+    c->B.slot = c->slot;
+    c->pp_stage_open = false;
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int pp_dev_flush_predict(slamgpu_ctx *c) {
+    if (c->pending.nsteps == 0) return 0;
+    if (int rc = pp_dev_stage(c)) return rc;
+    compose_predicts(c->pending);
+    {
+        Timed t(c, "predict");
+        c->k->predict(c->stream, c->B, c->pending, rng_args(c, 0));
+    }
+    HIP_TRY(hipGetLastError());
+    c->predict_bytes += 72.0 * c->cfg.n_particles * c->pending.nsteps;
+    c->pending.nsteps = 0;
+    c->est_fresh = false;
+    return 0;
+}
+
+// one iteration of slamgpu_run_particle: nothing here waits for the device or copies memory
+int pp_dev_iteration(slamgpu_ctx *c, int32_t nc, const float *controls, const float Q[4], float dt, const float xtrue[3], float max_range,
+                     const float R[4], int32_t noise, const slamgpu_particle_assoc *opt, int need) {
+    c->pp_stage_open = true;  // (the previous iteration may have updated: only the device knows)
+    for (int k = 0; k < nc; k++) {
+        const PredictArgs &P = c->pending;  // (slamgpu_predict's own flush would go through the host's tables: flush here instead)
+        if (P.nsteps > 0 && (P.dt != dt || memcmp(P.Q, Q, sizeof P.Q) != 0 || P.nsteps == kMaxFusedPredict))
+            if (int rc = pp_dev_flush_predict(c)) return rc;
+        if (int rc = slamgpu_predict(c, controls[3 * k], controls[3 * k + 1], Q, dt, controls[3 * k + 2], nullptr)) return rc;
+    }
+    // the observation, as slamgpu_observe makes it (raw z / nz stay on the device)
+    ObserveArgs A{};
+    A.lm = c->map_dev;
+    A.table = c->table_dev;
+    A.nlm = c->map_n;
+    A.nf = c->obs_nf;
+    A.x = xtrue[0];
+    A.y = xtrue[1];
+    A.phi = xtrue[2];
+    A.max_range = max_range;
+    A.sr = sqrtf(R[0]);
+    A.sb = sqrtf(R[3]);
+    A.noise = noise;
+    A.r1 = c->obs_r_dev;
+    A.r2 = c->obs_r_dev + c->map_n;
+    A.k0 = (uint32_t) c->cfg.seed;
+    A.k1 = (uint32_t) (c->cfg.seed >> 32);
+    A.step = ++c->observe_step;
+    A.out = c->obs_out_dev;
+    {
+        Timed t(c, "observe");
+        c->k->observe(c->stream, A);
+    }
+    if (int rc = pp_dev_flush_predict(c)) return rc;
+    if (int rc = pp_dev_stage(c)) return rc;
+    c->ws.wpar = (int) (c->pp_iter++ & 1);  // (no stage is outstanding here: either scratch parity will do)
+    PpArgs P = pp_args(c);
+    P.census_every = opt->census_every;
+    P.need = need;
+    P.p_new = opt->p_new;
+    c->B.slot = c->slot;
+    const float excl3[3] = {opt->excl_base, opt->excl_per_m, opt->unique_ratio};
+    {
+        Timed t(c, "associate");
+        c->k->pp_associate(c->stream, c->B, R, opt->gate_reject, opt->gate_augment, excl3, c->pp_lab_dev, P);
+    }
+    {
+        Timed t(c, "particle_book");
+        c->k->pp_book(c->stream, c->B, P);
+    }
+    {
+        Timed t(c, "particle_resolve");
+        c->k->pp_resolve_dev(c->stream, c->pp_lab_dev, c->B.n, c->B.ncap, P, c->pp_obs_dev, c->pp_wf_dev, c->pp_any_dev);
+    }
+    UpdateArgs U{};
+    U.method = c->cfg.method;
+    U.m = c->B.cap_nf;  // (upper bounds: the kernel reads the packet's header)
+    U.n = c->map_n;
+    U.e_new = -1;
+    U.dev_packet = 1;
+    U.big = reinterpret_cast<const ObsPacket *>(c->pp_pkt_dev);
+    memcpy(U.R, R, sizeof U.R);
+    U.lazy = 1;
+    U.rows_per_role = 16;
+    U.copy_lo = U.copy_hi = 0;  // (the gather above left nothing pending)
+    U.do_resample = c->cfg.resample;
+    U.n_effective = c->cfg.n_effective;
+    U.logw = c->cfg.log_weights;
+    U.stamps = c->stamps_dev;
+    PerParticle ppa{c->pp_obs_dev, reinterpret_cast<const float *>(c->obs_out_dev + 1), P.idn, c->pp_wf_dev, c->pp_any_dev, c->map_n, 0,
+                    c->obs_out_dev, &c->pp_st_dev->step};
+    {
+        Timed t(c, c->cfg.method == SLAMGPU_FASTSLAM2 ? "fs2_update" : "fs1_update");
+        c->k->update_particle_dev(c->stream, c->B, PredictArgs{}, U, rng_args(c, 0), c->ws, ppa);
+    }
+    HIP_TRY(hipGetLastError());
+    c->slot ^= 1;
+    c->B.slot = c->slot;
+    c->maybe_pending = false;
+    c->pp_prev_hist = P.hist;
+    c->pp_prev_par = c->ws.wpar;
+    c->hist_n++;
+    c->pp_report_n++;
+    c->est_fresh = false;
+    return 0;
+}
+}  // namespace
+
+int slamgpu_run_particle(slamgpu_ctx *c, int32_t K, const int32_t *n_controls, const float *controls, const float Q[4], float dt,
+                         const float *xtrue, float max_range, const float R[4], int32_t noise, const slamgpu_particle_assoc *opt) {
+    if (int rc = check_ctx(c)) return rc;
+    // everything that can be refused is refused BEFORE the first device call: a refused call applies nothing
+    if (K < 0 || (K > 0 && (!n_controls || !xtrue || !R || !opt))) return fail(SLAMGPU_ERR_INVALID, "slamgpu_run_particle: bad arguments");
+    const uint32_t need_flags = SLAMGPU_FLAG_PARTICLE_MAPS | SLAMGPU_FLAG_DEVICE_OBSERVE;
+    if ((c->cfg.flags & need_flags) != need_flags)
+        return fail(SLAMGPU_ERR_INVALID, "slamgpu_run_particle: create the context with SLAMGPU_FLAG_PARTICLE_MAPS | SLAMGPU_FLAG_DEVICE_OBSERVE");
+    if (noise != 0 && noise != 2) return fail(SLAMGPU_ERR_INVALID, "slamgpu_run_particle: noise must be 0 or 2");
+    if (c->cfg.rng_mode == SLAMGPU_RNG_TAPE) return fail(SLAMGPU_ERR_INVALID, "slamgpu_run_particle: TAPE-mode contexts take their draws per step");
+    if (K == 0) return 0;
+    if (!c->map_dev) return fail(SLAMGPU_ERR_INVALID, "slamgpu_run_particle: no map: call slamgpu_set_map first");
+    if (opt->mode < SLAMGPU_ASSOC_AUTO || opt->mode > SLAMGPU_ASSOC_GRID) return fail(SLAMGPU_ERR_INVALID, "unknown association mode %d", opt->mode);
+    if (opt->mode == SLAMGPU_ASSOC_GRID)
+        return fail(SLAMGPU_ERR_INVALID, "slamgpu_run_particle: the association is the exhaustive scan (SLAMGPU_ASSOC_EXHAUSTIVE or _AUTO)");
+    if (int rc = pp_check(c, xtrue, 0, R, opt)) return rc;
+    size_t total = 0;
+    for (int32_t k = 0; k < K; k++) {
+        if (n_controls[k] < 0) return fail(SLAMGPU_ERR_INVALID, "slamgpu_run_particle: iteration %d has a negative control count", (int) k);
+        total += (size_t) n_controls[k];
+    }
+    if (total > 0 && (!controls || !Q)) return fail(SLAMGPU_ERR_INVALID, "slamgpu_run_particle: %zu controls but no control list / Q", total);
+    if ((int64_t) c->hist_n + K > kHistCap)
+        return fail(SLAMGPU_ERR_CAPACITY, "slamgpu_run_particle: %d iterations would overflow the estimate history (%d of %d entries in use): call "
+                                          "slamgpu_history_fetch first", (int) K, c->hist_n, kHistCap);
+    if ((int64_t) c->pp_report_n + K > kHistCap)
+        return fail(SLAMGPU_ERR_CAPACITY, "slamgpu_run_particle: %d iterations would overflow the report ring (%d of %d entries in use): call "
+                                          "slamgpu_particle_report_fetch first", (int) K, c->pp_report_n, kHistCap);
+    if ((double) c->B.n * (double) c->B.cap_nf * (double) c->map_n > 4e10)
+        return fail(SLAMGPU_ERR_CAPACITY, "slamgpu_run_particle: the exhaustive scan of %d particles x %d slots x %d observations is too much for one launch",
+                    c->B.n, c->B.cap_nf, c->map_n);
+    if (int rc = persist_check(c)) return rc;
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    const int nmax = std::min(c->map_n, c->B.cap_nf);
+    if (int rc = pp_reserve_particles(c, c->map_n, (size_t) c->B.cap_nf + nmax + 1)) return rc;  // (pp_nz_cap stays the host path's: PpState::census_cap)
+    if (int rc = pp_setup(c)) return rc;
+    if (int rc = pp_push(c, c->pp_nz_cap)) return rc;
+    const int need = std::max(1, (int) ceil((double) opt->new_share * (double) c->B.n));
+    size_t row = 0;
+    for (int32_t k = 0; k < K; k++) {
+        const int32_t nc = n_controls[k];
+        if (int rc = pp_dev_iteration(c, nc, nc ? controls + 3 * row : nullptr, Q, dt, xtrue + 3 * (size_t) k, max_range, R, noise, opt, need)) {
+            std::string why = slamgpu_last_error();
+            return fail(rc, "slamgpu_run_particle: iteration %d of %d: %s", (int) k, (int) K, why.c_str());
+        }
+        row += (size_t) nc;
+    }
+    return 0;
+}
+
+int slamgpu_particle_report_fetch(slamgpu_ctx *c, int32_t *report, int32_t max_count, int32_t *count) {
+    if (int rc = check_ctx(c)) return rc;
+    if (!count || (max_count > 0 && !report)) return fail(SLAMGPU_ERR_INVALID, "slamgpu_particle_report_fetch: null output");
+    *count = 0;
+    if (c->pp_report_n == 0) return 0;
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    const int n = std::min(c->pp_report_n, std::max(max_count, 0));
+    std::vector<int32_t> h(8 * (size_t) c->pp_report_n);
+    HIP_TRY(hipMemcpy(h.data(), c->pp_report_dev, sizeof(int32_t) * h.size(), hipMemcpyDeviceToHost));
+    if (n > 0) memcpy(report, h.data(), sizeof(int32_t) * 8 * (size_t) n);
+    const int left = c->pp_report_n - n;
+    if (left > 0 && n > 0)  // (the unfetched tail moves to the front, as the history's does)
+        HIP_TRY(hipMemcpy(c->pp_report_dev, h.data() + 8 * (size_t) n, sizeof(int32_t) * 8 * (size_t) left, hipMemcpyHostToDevice));
+    c->pp_report_n = left;
+    *count = n;
+    return 0;
 }
 
 int slamgpu_num_landmarks(slamgpu_ctx *c) {
