@@ -299,6 +299,12 @@ int slamgpu_associate(slamgpu_ctx *ctx, const float *z, int32_t nz, const float 
  * stats (may be NULL): [0] (particle, observation, landmark) triples evaluated, [1] grid entries, [2] device milliseconds of
  * the association kernels, [3] 1 if the grid was used. */
 enum { SLAMGPU_ASSOC_AUTO = 0, SLAMGPU_ASSOC_EXHAUSTIVE = 1, SLAMGPU_ASSOC_GRID = 2 };
+/* SLAMGPU_ASSOC_LISTS: the per-particle entry points only (slamgpu_update_particle, slamgpu_run_particle; slamgpu_associate_ex refuses
+ * it).  One candidate list per observation built on the device from the slots' boxes, the exclusion rule folded into the lists: the
+ * labels of the exhaustive scan, decision for decision, the rule included, with no N x capacity x map limit.  An observation whose list
+ * does not fit its share of the entry buffer is walked over every slot, alone.  At most 4 096 observations a step (slamgpu_run_particle:
+ * as many as the map can show from the true pose), else SLAMGPU_ERR_CAPACITY with nothing applied. */
+enum { SLAMGPU_ASSOC_LISTS = 3 };
 int slamgpu_associate_ex(slamgpu_ctx *ctx, const float *z, int32_t nz, const float R[4], float gate_reject, float gate_augment, int32_t mode,
                          int32_t *labels, int32_t *consensus, float *support, double stats[4]);
 
@@ -327,7 +333,7 @@ int slamgpu_associate_ex(slamgpu_ctx *ctx, const float *z, int32_t nz, const flo
  * waiting, [6] particles an observation needs to open a slot, [7] 1 if the holders were counted.  Synchronises. */
 typedef struct slamgpu_particle_assoc {
     float gate_reject, gate_augment; /* GATE_REJECT / GATE_AUGMENT of the .ini */
-    int32_t mode;                    /* SLAMGPU_ASSOC_AUTO / _EXHAUSTIVE / _GRID */
+    int32_t mode;                    /* SLAMGPU_ASSOC_AUTO / _EXHAUSTIVE / _GRID / _LISTS */
     float new_share;                 /* 0: one particle is enough to open a landmark */
     float p_new;                     /* > 0 */
     int32_t census_every;            /* 0: never */
@@ -337,8 +343,8 @@ typedef struct slamgpu_particle_assoc {
      * beside it.  With the rule on, an observation no landmark gates is placed in the world from the particle's pose; if a
      * landmark the particle holds lies within excl_base + excl_per_m * range [m] of that point the observation cannot be new: it
      * is matched with that landmark when no other lies within unique_ratio times the distance, and discarded otherwise.
-     * SLAMGPU_ASSOC_EXHAUSTIVE / _AUTO (which then scans exhaustively) only: O(N nz Nf), refused with SLAMGPU_ERR_CAPACITY beyond
-     * 4e10 gate evaluations in a step (maps of a few hundred landmarks are its range). */
+     * SLAMGPU_ASSOC_EXHAUSTIVE / _AUTO (which then scans exhaustively): O(N nz Nf), refused with SLAMGPU_ERR_CAPACITY beyond
+     * 4e10 gate evaluations in a step (maps of a few hundred landmarks are its range); SLAMGPU_ASSOC_LISTS: any map size. */
     float excl_base, excl_per_m, unique_ratio;
 } slamgpu_particle_assoc;
 int slamgpu_update_particle(slamgpu_ctx *ctx, const float *z, int32_t nz, const float R[4], const slamgpu_particle_assoc *opt,
@@ -355,7 +361,8 @@ int slamgpu_update_labels(slamgpu_ctx *ctx, const float *z, int32_t nz, const fl
  * no update, as there) and slamgpu_estimate_async do, bit for bit, on a context created with the same configuration; every
  * per-particle decision (the census, the dead slots, the new slots, the genealogy) is taken on the device, and the call returns
  * without waiting for it.  The association is the exhaustive scan (opt->mode SLAMGPU_ASSOC_EXHAUSTIVE or _AUTO: the labels of
- * the grid are the same).  noise: 0 none, 2 Philox.  Estimates and history: slamgpu_estimate_fetch / slamgpu_history_fetch; the
+ * the grid are the same) or the candidate lists (SLAMGPU_ASSOC_LISTS: the same labels; no N x capacity x map limit; an iteration
+ * whose visible landmarks may exceed 4 096 is refused with SLAMGPU_ERR_CAPACITY).  noise: 0 none, 2 Philox.  Estimates and history: slamgpu_estimate_fetch / slamgpu_history_fetch; the
  * iterations' reports: slamgpu_particle_report_fetch.  Any host-side call afterwards (slamgpu_update_particle, download, peek,
  * slamgpu_num_landmarks, slamgpu_retire_landmarks, slamgpu_associate_ex, ...) first takes the state back (one synchronisation).
  * Refused, with nothing applied: a context without SLAMGPU_FLAG_PARTICLE_MAPS | SLAMGPU_FLAG_DEVICE_OBSERVE, no map, TAPE mode,
@@ -366,6 +373,11 @@ int slamgpu_run_particle(slamgpu_ctx *ctx, int32_t K, const int32_t *n_controls,
 /* The reports of slamgpu_run_particle's iterations not fetched yet, oldest first (report[k][8]: slamgpu_update_particle's fields;
  * an iteration without observations: all zeros), at most max_count of them (*count: how many); the rest stay.  Synchronises. */
 int slamgpu_particle_report_fetch(slamgpu_ctx *ctx, int32_t *report, int32_t max_count, int32_t *count);
+/* SLAMGPU_ASSOC_LISTS, cumulative since the context was created (both per-particle entry points): out[0] steps associated through the
+ * lists, [1] list entries built, [2] observations whose list overflowed and that were walked over every slot, [3] (particle,
+ * observation, slot) triples evaluated.  (slamgpu_particle_report_fetch returns SLAMGPU_ERR_CAPACITY once if an iteration of
+ * slamgpu_run_particle saw more observations than the host's bound on them; they were walked over every slot.)  Synchronises. */
+int slamgpu_particle_list_stats(slamgpu_ctx *ctx, int64_t out[4]);
 
 /* Retire landmarks from the gated association (round 6): landmarks ids[0 .. count) take no part in slamgpu_associate /
  * _associate_ex from now on -- no particle gates an observation against them, nothing votes for them -- and, never being

@@ -26,9 +26,9 @@ DECLARED_SYMBOLS = [
     "slamgpu_dist_collective_status", "slamgpu_dist_comm_id", "slamgpu_dist_comm_init", "slamgpu_dist_group_create", "slamgpu_dist_group_destroy",
     "slamgpu_dist_group_step", "slamgpu_dist_group_settle", "slamgpu_dist_group_history", "slamgpu_dist_group_download",
     "slamgpu_peek", "slamgpu_step_observe", "slamgpu_run_observe", "slamgpu_observe_fetch", "slamgpu_associate_ex", "slamgpu_update_particle", "slamgpu_update_labels", "slamgpu_dist_comm_info", "slamgpu_dist_remote_reads",
-    "slamgpu_run_particle", "slamgpu_particle_report_fetch",
+    "slamgpu_run_particle", "slamgpu_particle_report_fetch", "slamgpu_particle_list_stats",
 ]
-ASSOC_AUTO, ASSOC_EXHAUSTIVE, ASSOC_GRID = 0, 1, 2
+ASSOC_AUTO, ASSOC_EXHAUSTIVE, ASSOC_GRID, ASSOC_LISTS = 0, 1, 2, 3
 FLAG_DEVICE_OBSERVE = 1
 FLAG_NO_REFERENCE_RESAMPLE = 2
 FLAG_PARTICLE_MAPS = 4
@@ -118,6 +118,8 @@ def load_library():
         L.slamgpu_run_particle.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_float, C.c_void_p, C.c_int32,
                                            C.c_void_p]
         L.slamgpu_particle_report_fetch.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]
+    if hasattr(L, "slamgpu_particle_list_stats"):
+        L.slamgpu_particle_list_stats.argtypes = [C.c_void_p, C.c_void_p]
     L.slamgpu_genealogy_rows.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     L.slamgpu_persist_info.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
     if hasattr(L, "slamgpu_persist_status"):  # (an older build loaded through SLAMGPU_LIB for an A/B lacks the round-6 entries)
@@ -793,6 +795,12 @@ class SlamGpu:
         n = C.c_int32()
         _chk(self.L.slamgpu_particle_report_fetch(self.h, _ptr(out), int(max_count), C.byref(n)))
         return out[:n.value].copy()
+
+    def particle_list_stats(self):
+        """SLAMGPU_ASSOC_LISTS counters since the context was created (slamgpu_particle_list_stats): dict(steps, entries, overflowed, triples)"""
+        out = np.zeros(4, np.int64)
+        _chk(self.L.slamgpu_particle_list_stats(self.h, _ptr(out)))
+        return dict(zip(("steps", "entries", "overflowed", "triples"), (int(v) for v in out)))
 
     def update_labels(self, z, R, labels, new_share=0.0, p_new=1.0, census_every=1, normals=None, strata=None):
         """the same step with the caller's labels [N, nz] (slamgpu_update_labels)"""

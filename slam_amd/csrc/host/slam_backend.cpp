@@ -14,6 +14,8 @@
 //                        landmarks, default 4), -PARTICLE_NEW_SHARE (0.02), -PARTICLE_P_NEW (default: the Gaussian at the reject
 //                        gate), -PARTICLE_EXCL_BASE (2.0 m) / -PARTICLE_EXCL_PER_M (0.05) / -PARTICLE_UNIQUE_RATIO (2): the exclusion
 //                        rule of include/slamgpu.h: slamgpu_particle_assoc.  The map reported at the end is the best particle's.
+//                        -PARTICLE_ASSOC lists: the association through candidate lists built on the device (SLAMGPU_ASSOC_LISTS:
+//                        the same labels, any map size); auto (default): SLAMGPU_ASSOC_AUTO.
 //   -plot <sinks>        the per-step output the reference sends to slam-gui (plotting/NetworkPlot.cpp), byte for byte:
 //                        tcp://127.0.0.1:4242 (the existing slam-gui) | file:<frames> | gather:<dir> (the GUI's DataGatherer
 //                        files, headless) | none (default); several separated by ','
@@ -450,6 +452,12 @@ int main(int argc, char **argv) {
         popt.gate_reject = c.GATE_REJECT;
         popt.gate_augment = c.GATE_AUGMENT;
         popt.mode = SLAMGPU_ASSOC_AUTO;
+        if (c.s("PARTICLE_ASSOC") == "lists") {
+            popt.mode = SLAMGPU_ASSOC_LISTS;
+        } else if (!c.s("PARTICLE_ASSOC").empty() && c.s("PARTICLE_ASSOC") != "auto") {
+            fprintf(stderr, "-PARTICLE_ASSOC lists|auto\n");
+            return EXIT_FAILURE;
+        }
         popt.new_share = (float) numkey("PARTICLE_NEW_SHARE", 0.02);
         popt.p_new = (float) numkey("PARTICLE_P_NEW", std::exp(-0.5 * c.GATE_REJECT) / (2.0 * 3.14159265358979323846 * std::sqrt(std::max(1e-30, (double) sim.Re[0] * sim.Re[3] - (double) sim.Re[1] * sim.Re[2]))));
         popt.census_every = (int32_t) numkey("PARTICLE_CENSUS", 1);

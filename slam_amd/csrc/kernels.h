@@ -613,6 +613,20 @@ struct PpArgs {
     int32_t logw, pad;
 };
 
+// SLAMGPU_ASSOC_LISTS (slamgpu_update_particle / slamgpu_run_particle): the per-particle association through candidate lists built
+// from the device's state.  The list of observation q is ALL of its candidates when cell_start[q] <= lcap; a longer one (cell_start[q]
+// holds its true length) is walked over every slot instead, in slot order: no call-wide overflow, no retry through the grid.
+struct AssocListArgs : AssocGridArgs {
+    const ObserveOut *obs;        // device-driven (slamgpu_run_particle): nz and z from the iteration's observation -- nz above is then the
+                                  // host's bound on it, the lists grid; an observation past it is walked over every slot -- or null
+    const DevBook *book;          // device-driven: nf
+    const uint32_t *retired;      // [(cap_nf + 31) / 32] slots that take no part (may be null)
+    float excl_base, excl_per_m, excl_ratio;  // the exclusion rule (slamgpu_particle_assoc::excl_*, unique_ratio; base + per_m = 0: off)
+    unsigned long long *lstats;   // [5] cumulative: steps associated, list entries, observations walked over every slot, triples evaluated,
+                                  // observations past the host's bound
+    PpArgs P;                     // device-driven: the holders census / estimate partials that ride in the walk
+};
+
 struct KernelTable {
     // the step: [resampling stage of the previous update, inline] + [gather] + [fused predicts] + per-particle observation
     // update + in-block weight prefix / totals  (+ helper blocks: genealogy copy, Ctrl words, estimate reduction)
@@ -704,6 +718,14 @@ struct KernelTable {
     void (*pp_resolve_dev)(hipStream_t, const int32_t *labels_dev, int n, int ncap, const PpArgs &, int16_t *obs_dev, float *wf_dev, uint8_t *any_dev);
     void (*update_particle_dev)(hipStream_t, const Buffers &, const PredictArgs &, const UpdateArgs &, const RngArgs &, const WeightScratch &,
                                 const PerParticle &);
+    // SLAMGPU_ASSOC_LISTS, one launch each.  lists_box: the boxes of the slots the previous iteration's update rewrote or opened (the
+    // packet pp_book_kernel left; all: slots 0 .. nf - 1), `blocks` workgroups walking them; lists_geom: stage 0 the partial pose boxes,
+    // 1 the geometry; lists_build: one candidate list per observation; lists_walk: the labels (+ the census of the labels, and in a
+    // device-driven iteration the holders census or the estimate partials).  Device-driven: AssocListArgs::obs set.
+    void (*lists_box)(hipStream_t, const Buffers &, const PpArgs &, int all, int blocks, LmkBox *box_dev);
+    void (*lists_geom)(hipStream_t, const Buffers &, const AssocListArgs &, int stage);
+    void (*lists_build)(hipStream_t, const Buffers &, const AssocListArgs &);
+    void (*lists_walk)(hipStream_t, const Buffers &, const AssocListArgs &, const float *R4, float gate_reject, float gate_augment, int32_t *labels_dev);
 };
 
 const KernelTable *kernels_strict();

@@ -2616,6 +2616,42 @@ SLAM_DEV void pp_count_holders(const Buffers &B, int nf, int nz, const PpArgs &P
         __syncthreads();
     }
 }
+// the same census shared out over the `parts` workgroup rows of a launch (associate_grid_kernel<.., DEV = true>: blockIdx.y): row `part`
+// counts its share of the listed slots for every particle, so that no row of the walk carries the whole census
+SLAM_DEV void pp_count_holders_part(const Buffers &B, int nf, int nz, const PpArgs &P, int part, int parts) {
+    constexpr int kChunk = 1024;
+    __shared__ int32_t sh[kChunk];
+    const uint64_t steps = ((uint64_t) P.st->steps_hi << 32) | P.st->steps_lo;
+    const int cap = nz > P.st->census_cap ? max(64, 2 * nz) : P.st->census_cap;  // (pp_count_holders' rule)
+    const int count = min(P.st->n_list, cap);
+    if (!(P.census_every > 0 && nf > 0 && steps % (uint64_t) P.census_every == 0) || count == 0) return;
+    const int lo = (int) ((int64_t) count * part / parts), hi = (int) ((int64_t) count * (part + 1) / parts);
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    const bool on = i < B.n;
+    const int cur = B.ctrl->live[B.slot];
+    const size_t S = (size_t) B.ncap;
+    for (int l0 = lo; l0 < hi; l0 += kChunk) {
+        const int ln = min(kChunk, hi - l0);
+        for (int t = threadIdx.x; t < ln; t += kBlock) sh[t] = 0;
+        __syncthreads();
+        for (int l = l0; l < l0 + ln; l++) {
+            const int slot = P.list[l];
+            bool has = false;
+            if (on) {
+                float4 la;
+                float lb;
+                read_through_genealogy(B, B.lmk_live, cur, S, slot, i, la, lb);
+                has = la.x == la.x;
+            }
+            const unsigned long long hm = __ballot(has);
+            if (hm && (threadIdx.x & (kWave - 1)) == (int) __ffsll((long long) __ballot(true)) - 1) atomicAdd(sh + (l - l0), (int) __popcll(hm));
+        }
+        __syncthreads();
+        for (int t = threadIdx.x; t < ln; t += kBlock)
+            if (sh[t]) atomicAdd(P.hold + P.list[l0 + t], sh[t]);
+        __syncthreads();
+    }
+}
 // the label census (pp_census_kernel's, where the label is made): first[l] = lowest observation naming slot l, news[j] = particles calling j new
 SLAM_DEV void pp_census_label(int lab, int j, const PpArgs &P) {
     unsigned long long todo = __ballot(lab >= 0);
@@ -2749,10 +2785,7 @@ __global__ void __launch_bounds__(kBlock) associate_kernel(Buffers B, int nf, co
 // ---------------------------------------------------------------------------------------------------
 // one block per listed landmark: box of its estimates and largest covariance trace over all particle slots of the live buffer
 // (a resample only removes particles from that set: the box stays valid until the landmark is written again)
-__global__ void __launch_bounds__(kBlock) lmk_box_kernel(Buffers B, const int32_t *__restrict__ ids, int count, const uint32_t *__restrict__ retired,
-                                                          LmkBox *__restrict__ box) {
-    __shared__ float sh[5][kBlock / kWave];
-    const int j = ids[blockIdx.x];
+SLAM_DEV void lmk_box_of(const Buffers &B, int j, const uint32_t *__restrict__ retired, LmkBox *__restrict__ box, float (*sh)[kBlock / kWave]) {
     if (retired && ((retired[j >> 5] >> (j & 31)) & 1u)) {  // the empty box: no cell (assoc_cells), so the landmark is never evaluated
         if (threadIdx.x == 0) box[j] = LmkBox{INFINITY, -INFINITY, INFINITY, -INFINITY, 0.0f, {0.0f, 0.0f, 0.0f}};
         return;
@@ -2790,6 +2823,24 @@ __global__ void __launch_bounds__(kBlock) lmk_box_kernel(Buffers B, const int32_
         o.ymax = fmaxf(fmaxf(sh[3][0], sh[3][1]), fmaxf(sh[3][2], sh[3][3]));
         o.tmax = fmaxf(fmaxf(sh[4][0], sh[4][1]), fmaxf(sh[4][2], sh[4][3]));
         box[j] = o;
+    }
+}
+__global__ void __launch_bounds__(kBlock) lmk_box_kernel(Buffers B, const int32_t *__restrict__ ids, int count, const uint32_t *__restrict__ retired,
+                                                          LmkBox *__restrict__ box) {
+    __shared__ float sh[5][kBlock / kWave];
+    lmk_box_of(B, ids[blockIdx.x], retired, box, sh);
+}
+// SLAMGPU_ASSOC_LISTS driven by the device: the slots the previous iteration's update rewrote or opened -- the packet's entries pidf[0, m)
+// and the new slots idn[0, n) pp_book_kernel left, when it made an update (PpState::updated) -- or (all) slots 0 .. nf - 1.  The grid is
+// the host's bound; a workgroup takes the slots gridDim.x apart.  (A slot the census retires keeps its box: the lists read the mask.)
+__global__ void __launch_bounds__(kBlock) lmk_box_dev_kernel(Buffers B, PpArgs P, int all, LmkBox *__restrict__ box) {
+    __shared__ float sh[5][kBlock / kWave];
+    const bool upd = !all && P.st->updated;
+    const int m = upd ? P.pkt->m : 0, count = all ? P.book->nf : (upd ? m + P.pkt->n : 0);
+    const int32_t *pidf = reinterpret_cast<const int32_t *>(P.pkt + 1);
+    for (int k = blockIdx.x; k < count; k += gridDim.x) {
+        lmk_box_of(B, all ? k : (k < m ? pidf[k] : P.idn[k - m]), P.retired, box, sh);
+        __syncthreads();  // (sh is taken again)
     }
 }
 
@@ -2838,8 +2889,14 @@ __global__ void __launch_bounds__(kBlock) assoc_geom_partial_kernel(Buffers B, f
         o[5] = fmaxf(fmaxf(sh[5][0], sh[5][1]), fmaxf(sh[5][2], sh[5][3]));
     }
 }
-__global__ void __launch_bounds__(kBlock) assoc_geom_kernel(Buffers B, AssocGridArgs A, const float *__restrict__ part) {
+// (DEV: slamgpu_run_particle -- the observations from device memory, AssocListArgs::obs)
+template <bool DEV = false>
+__global__ void __launch_bounds__(kBlock) assoc_geom_kernel(Buffers B, std::conditional_t<DEV, AssocListArgs, AssocGridArgs> A, const float *__restrict__ part) {
     __shared__ float sh[7][kBlock / kWave];
+    if constexpr (DEV) {
+        A.nz = A.obs->nz;
+        A.z = reinterpret_cast<const float *>(A.obs + 1);
+    }
     const int cur = B.ctrl->live[B.slot];
     float x0 = INFINITY, x1 = -INFINITY, y0 = INFINITY, y1 = -INFINITY, zm = 0.0f, t0 = INFINITY, t1 = -INFINITY;
     const float th_ref = B.n > 0 ? B.poseA[cur][0].z : 0.0f;
@@ -3015,9 +3072,27 @@ SLAM_DEV void arc_range(float a0, float a1, bool cosine, float &lo, float &hi) {
     if (floorf(b1 * inv) > floorf(b0 * inv) || b0 * inv == floorf(b0 * inv)) hi = 1.0f;
     if (floorf((b1 - 3.14159265358979324f) * inv) > floorf((b0 - 3.14159265358979324f) * inv)) lo = -1.0f;
 }
-__global__ void __launch_bounds__(kBlock) assoc_lists_kernel(AssocGridArgs A, const int32_t *__restrict__ erow, const int32_t *__restrict__ live) {
+// PEROBS (SLAMGPU_ASSOC_LISTS): cell_start[q] is the list's TRUE length (longer than lcap: the walk takes every slot for that observation
+// alone); retired slots are skipped here; with the exclusion rule on, the list also keeps every slot whose box lies within
+// max(1, unique_ratio) x the rule's radius of the points the observation implies -- a slot farther away can neither be the nearest one
+// inside the radius nor decide the uniqueness test (associate_kernel<EXCL>: d2 > unique_ratio^2 d1), so the rule's decision is exact;
+// the counts go to lstats.  DEV: nz, z and nf from device memory, the grid is the host's bound on nz.
+template <bool PEROBS = false, bool DEV = false>
+__global__ void __launch_bounds__(kBlock) assoc_lists_kernel(std::conditional_t<PEROBS, AssocListArgs, AssocGridArgs> A, const int32_t *__restrict__ erow,
+                                                              const int32_t *__restrict__ live) {
+    static_assert(PEROBS || !DEV, "device-driven lists are per observation");
     __shared__ int32_t sh_n;
     const int q = blockIdx.x;
+    if constexpr (DEV) {
+        const int nz = A.obs->nz;
+        if (q == 0 && threadIdx.x == 0 && nz > (int) gridDim.x) {  // (past the bound: walked over every slot, and reported)
+            atomicAdd(A.lstats + 2, (unsigned long long) (nz - (int) gridDim.x));
+            atomicAdd(A.lstats + 4, (unsigned long long) (nz - (int) gridDim.x));
+        }
+        if (q >= nz) return;
+        A.nf = A.book->nf;
+        A.z = reinterpret_cast<const float *>(A.obs + 1);
+    }
     const AssocGeom g = *A.geom;
     if (threadIdx.x == 0) sh_n = 0;
     __syncthreads();
@@ -3030,19 +3105,35 @@ __global__ void __launch_bounds__(kBlock) assoc_lists_kernel(AssocGridArgs A, co
     const float slack = 1e-3f * (1.0f + fabsf(zr)) + 1e-4f * (fabsf(g.px0) + fabsf(g.px1) + fabsf(g.py0) + fabsf(g.py1));
     const float qx0 = g.px0 + fminf(zr * cl, zr * ch) - slack, qx1 = g.px1 + fmaxf(zr * cl, zr * ch) + slack;
     const float qy0 = g.py0 + fminf(zr * sl, zr * shh) - slack, qy1 = g.py1 + fmaxf(zr * sl, zr * shh) + slack;
+    [[maybe_unused]] float rx = -1.0f;  // (PEROBS: the exclusion rule's reach, < 0: off)
+    if constexpr (PEROBS)
+        if (A.excl_base + A.excl_per_m > 0.0f) rx = fmaxf(1.0f, A.excl_ratio) * (A.excl_base + A.excl_per_m * zr) * 1.01f + 1e-3f;
     for (int j = threadIdx.x; j < A.nf; j += kBlock) {
+        if constexpr (PEROBS)
+            if (A.retired && ((A.retired[j >> 5] >> (j & 31)) & 1u)) continue;
         const LmkBox bx = A.box[j];
         if (!(bx.xmin <= bx.xmax)) continue;  // (no estimate / retired: the empty box)
         const float rho = assoc_radius(bx, g, A.r00, A.r11, A.G);
         const float gx = fmaxf(fmaxf(bx.xmin - qx1, qx0 - bx.xmax), 0.0f), gy = fmaxf(fmaxf(bx.ymin - qy1, qy0 - bx.ymax), 0.0f);
-        if (gx * gx + gy * gy > rho * rho) continue;
         // the radial ring over the pose box: some pose's distance to some estimate in the box must be within e of the range
-        const float e = 1.01f * sqrtf(A.G * (bx.tmax + A.r00)) + 1e-3f;
-        const float ex = fmaxf(fmaxf(bx.xmin - g.px1, g.px0 - bx.xmax), 0.0f), ey = fmaxf(fmaxf(bx.ymin - g.py1, g.py0 - bx.ymax), 0.0f);
-        const float fx = fmaxf(fabsf(bx.xmax - g.px0), fabsf(g.px1 - bx.xmin)), fy = fmaxf(fabsf(bx.ymax - g.py0), fabsf(g.py1 - bx.ymin));
-        const float dmin2 = ex * ex + ey * ey, dmax2 = fx * fx + fy * fy;
-        const float hi = zr + e, lo = zr - e;
-        if ((hi < 0.0f || hi * hi < dmin2 * 0.998f) || (lo > 0.0f && lo * lo > dmax2 * 1.002f)) continue;
+        float e;
+        if constexpr (PEROBS) {
+            e = 1.01f * sqrtf(A.G * (bx.tmax + A.r00)) + 1e-3f;
+            const float ex = fmaxf(fmaxf(bx.xmin - g.px1, g.px0 - bx.xmax), 0.0f), ey = fmaxf(fmaxf(bx.ymin - g.py1, g.py0 - bx.ymax), 0.0f);
+            const float fx = fmaxf(fabsf(bx.xmax - g.px0), fabsf(g.px1 - bx.xmin)), fy = fmaxf(fabsf(bx.ymax - g.py0), fabsf(g.py1 - bx.ymin));
+            const float dmin2 = ex * ex + ey * ey, dmax2 = fx * fx + fy * fy;
+            const float hi = zr + e, lo = zr - e;
+            const bool gate = !(gx * gx + gy * gy > rho * rho) && !((hi < 0.0f || hi * hi < dmin2 * 0.998f) || (lo > 0.0f && lo * lo > dmax2 * 1.002f));
+            if (!gate && !(gx * gx + gy * gy <= rx * rx)) continue;
+        } else {
+            if (gx * gx + gy * gy > rho * rho) continue;
+            e = 1.01f * sqrtf(A.G * (bx.tmax + A.r00)) + 1e-3f;
+            const float ex = fmaxf(fmaxf(bx.xmin - g.px1, g.px0 - bx.xmax), 0.0f), ey = fmaxf(fmaxf(bx.ymin - g.py1, g.py0 - bx.ymax), 0.0f);
+            const float fx = fmaxf(fabsf(bx.xmax - g.px0), fabsf(g.px1 - bx.xmin)), fy = fmaxf(fabsf(bx.ymax - g.py0), fabsf(g.py1 - bx.ymin));
+            const float dmin2 = ex * ex + ey * ey, dmax2 = fx * fx + fy * fy;
+            const float hi = zr + e, lo = zr - e;
+            if ((hi < 0.0f || hi * hi < dmin2 * 0.998f) || (lo > 0.0f && lo * lo > dmax2 * 1.002f)) continue;
+        }
         const int at = atomicAdd(&sh_n, 1);
         if (at < A.lcap) {
             const size_t w = 2 * ((size_t) q * A.lcap + at);
@@ -3052,7 +3143,14 @@ __global__ void __launch_bounds__(kBlock) assoc_lists_kernel(AssocGridArgs A, co
         }
     }
     __syncthreads();
-    if (threadIdx.x == 0) {
+    if constexpr (PEROBS) {
+        if (threadIdx.x == 0) {
+            A.cell_start[q] = sh_n;
+            if (q == 0) atomicAdd(A.lstats, 1ull);
+            atomicAdd(A.lstats + 1, (unsigned long long) min(sh_n, A.lcap));
+            if (sh_n > A.lcap) atomicAdd(A.lstats + 2, 1ull);
+        }
+    } else if (threadIdx.x == 0) {
         A.cell_start[q] = min(sh_n, A.lcap);
         atomicAdd(&A.geom->total, min(sh_n, A.lcap));
         if (sh_n > A.lcap) atomicOr(&A.geom->overflow, 1);  // (the caller takes the grid)
@@ -3079,12 +3177,60 @@ SLAM_DEV bool vote_add(VoteSlot *tab, int label, float w) {
     return false;
 }
 
-template <bool LISTS>
-__global__ void __launch_bounds__(kBlock) associate_grid_kernel(Buffers B, AssocGridArgs A, float r00, float r01, float r10, float r11, float gate1,
-                                                                 float gate2, int32_t *__restrict__ labels) {
+// PEROBS (SLAMGPU_ASSOC_LISTS; LISTS only): an observation whose list overflowed (or, DEV, lies past the lists grid) is walked over every
+// slot in slot order -- associate_kernel's scan for that observation alone -- instead of the call going to the grid.  EXCL: the exclusion
+// rule (associate_kernel<EXCL>), its nearest and second-nearest taken from the list entries (assoc_lists_kernel<PEROBS> keeps every
+// slot that can decide it), with the tie rules of the scan: j1 the lowest slot among equal distances, d2 the second smallest distance
+// counted with multiplicity.  DEV (slamgpu_run_particle): nz, z and nf from device memory; the holders census rides in this launch and
+// an iteration without observations takes the estimate partials instead, as in associate_kernel<EXCL, true>.
+// the length of observation q's list (PEROBS: 0 when it is walked over every slot instead)
+template <bool PEROBS, class Args, class CntP>
+SLAM_DEV int walk_count(const Args &A, CntP counts, int q) {
+    if constexpr (PEROBS) {
+        if (q >= A.nz) return 0;
+        const int n = counts[q];
+        return n > A.lcap ? 0 : n;
+    } else {
+        return counts[q];
+    }
+}
+// the walk's observations and slots (DEV: from device memory; the kernel argument is not written, which would put it in private memory)
+template <bool DEV, class Args>
+SLAM_DEV const float *walk_z(const Args &A) {
+    if constexpr (DEV) return reinterpret_cast<const float *>(A.obs + 1);
+    else return A.z;
+}
+template <bool DEV, class Args>
+SLAM_DEV int walk_nf(const Args &A) {
+    if constexpr (DEV) return A.book->nf;
+    else return A.nf;
+}
+// the observations of this workgroup (DEV: the true count; the last group takes any observation past the lists grid)
+template <bool DEV, class Args>
+SLAM_DEV int walk_q_hi(const Args &A, int q_lo) {
+    if constexpr (DEV) {
+        const int nz = A.obs->nz;
+        return blockIdx.y + 1 == gridDim.y ? nz : min(nz, q_lo + A.obs_per_block);
+    } else {
+        return min(A.nz, q_lo + A.obs_per_block);
+    }
+}
+template <bool LISTS, bool PEROBS = false, bool EXCL = false, bool DEV = false>
+__global__ void __launch_bounds__(kBlock) associate_grid_kernel(Buffers B, std::conditional_t<PEROBS, AssocListArgs, AssocGridArgs> A, float r00, float r01,
+                                                                 float r10, float r11, float gate1, float gate2, int32_t *__restrict__ labels) {
+    static_assert((LISTS || !PEROBS) && (PEROBS || !(EXCL || DEV)), "the exclusion rule and the device-driven walk are the lists' per observation");
     const int i = blockIdx.x * kBlock + threadIdx.x;
+    if constexpr (DEV) {
+        const int nz = A.obs->nz;  // (the true count; A.nz is the lists grid)
+        if (nz == 0) {
+            if (blockIdx.y == 0) pp_estimate_partials(B, A.P.ws);
+            return;
+        }
+        pp_count_holders_part(B, A.book->nf, nz, A.P, blockIdx.y, gridDim.y);
+    }
     const AssocGeom g = *A.geom;
-    if (g.overflow & 1) return;  // (the entry buffer was too small: the caller runs the exhaustive scan)
+    if constexpr (!PEROBS)
+        if (g.overflow & 1) return;  // (the entry buffer was too small: the caller runs the exhaustive scan)
     unsigned long long pairs = 0;
     const bool on = i < B.n;
     const int cur = B.ctrl->live[B.slot];
@@ -3096,13 +3242,13 @@ __global__ void __launch_bounds__(kBlock) associate_grid_kernel(Buffers B, Assoc
     // blockIdx.y = a group of A.obs_per_block observations: a particle's observations are independent of each other, and one
     // thread walking all of them alone (1 300 on the 10 000-landmark map, ~65 dependent record reads each) left the
     // machine two thirds empty and every read exposed: 225 ms per call at 10^5 particles
-    const int q_lo = blockIdx.y * A.obs_per_block, q_hi = min(A.nz, q_lo + A.obs_per_block);
+    const int q_lo = blockIdx.y * A.obs_per_block, q_hi = walk_q_hi<DEV>(A, q_lo);
     for (int q = q_lo; q < q_hi; q++) {
         int label = kVoteEmpty;
         [[maybe_unused]] int pbest = -1;  // (LISTS: position of jbest in the observation's list: where its vote goes)
         if (on) {
             // (uniform and written before the launch: scalar loads)
-            const auto *zc = (const __attribute__((address_space(4))) float *) reinterpret_cast<uintptr_t>(A.z);
+            const auto *zc = (const __attribute__((address_space(4))) float *) reinterpret_cast<uintptr_t>(walk_z<DEV>(A));
             const float zr = zc[2 * q], zb = zc[2 * q + 1];
             float sn, cs;
 #ifdef SLAM_FAST_MATH
@@ -3181,7 +3327,7 @@ __global__ void __launch_bounds__(kBlock) associate_grid_kernel(Buffers B, Assoc
             const ItemP items_f = (ItemP) reinterpret_cast<uintptr_t>(A.items);
             auto item_at = [&](size_t w) -> float4 { return make_float4(items_f[4 * w], items_f[4 * w + 1], items_f[4 * w + 2], items_f[4 * w + 3]); };
             const CntP counts = (CntP) reinterpret_cast<uintptr_t>(A.cell_start);
-            const int c0 = LISTS ? q * A.lcap : counts[cell], c1 = LISTS ? c0 + counts[q] : counts[cell + 1];
+            const int c0 = LISTS ? q * A.lcap : counts[cell], c1 = LISTS ? c0 + walk_count<PEROBS>(A, counts, q) : counts[cell + 1];
             // Two passes.  Whatever an observation is MATCHED with passes gate_reject, so a first walk bounded by gate_reject alone (G1:
             // radii ~ sqrt(G1 / G) of the full ones) sees every landmark that can become jbest -- same candidates, same ties: the same
             // label.  The wider bound of gate_augment is only needed to tell "new" from "discard" for an observation NOTHING matched: a
@@ -3210,7 +3356,80 @@ __global__ void __launch_bounds__(kBlock) associate_grid_kernel(Buffers B, Assoc
                     if (at + 1 < c1) visit(b1, t1, A.G, t1.x);
                 }
             }
+            // PEROBS: an observation whose list overflowed is walked over every slot (the passes above saw no entry); EXCL: the rule
+            [[maybe_unused]] int xlabel = kVoteEmpty;
+            if constexpr (PEROBS) {
+                const bool every = q >= A.nz || counts[q] > A.lcap;
+                // the exclusion rule's neighbours: the point associate_kernel<EXCL> places (its arithmetic), squared distances
+                [[maybe_unused]] float wx = 0.0f, wy = 0.0f, d1 = INFINITY, d2 = INFINITY;
+                [[maybe_unused]] int j1 = -1;
+                if constexpr (EXCL) {
+                    float sn2, cs2;
+                    sincosf(pa.z + zb, &sn2, &cs2);
+                    wx = pa.x + zr * cs2;
+                    wy = pa.y + zr * sn2;
+                }
+                if (every) {
+                    // associate_kernel's scan for this observation: every slot in order (the first minimum wins)
+                    const int nf = walk_nf<DEV>(A);
+                    for (int j = 0; j < nf; j++) {
+                        if (A.retired && ((A.retired[j >> 5] >> (j & 31)) & 1u)) continue;
+                        float4 la;
+                        float lb;
+                        read_through_genealogy(B, B.lmk_live, cur, S, j, i, la, lb);
+                        const AssocLm L = assoc_landmark(pa, la, lb, r00, r01, r10, r11);
+                        float nis, nd;
+                        assoc_gate(L, zr, zb, nis, nd);
+                        pairs++;
+                        if (nis < gate1 && nd < nbest) {
+                            nbest = nd;
+                            jbest = j;
+                        } else if (nis < outer) {
+                            outer = nis;
+                        }
+                        if constexpr (EXCL) {
+                            const float ex = la.x - wx, ey = la.y - wy, dd = ex * ex + ey * ey;
+                            if (dd < d1) {
+                                d2 = d1;
+                                d1 = dd;
+                                j1 = j;
+                            } else if (dd < d2) {
+                                d2 = dd;
+                            }
+                        }
+                    }
+                }
+                if constexpr (EXCL) {
+                    const float rho = A.excl_base + A.excl_per_m * zr;
+                    if (jbest < 0 && !every) {
+                        // the list's entries in no particular order: the lower slot wins a tie for the nearest, and the second distance
+                        // counts ties (the same two numbers as the ordered scan).  An entry whose box lies beyond max(1, ratio) x the
+                        // radius from this point can decide neither (assoc_lists_kernel<PEROBS>): its record is not read
+                        const float rr = fmaxf(1.0f, A.excl_ratio) * rho * 1.01f + 1e-3f;
+                        for (int at = c0; at < c1; at++) {
+                            const float4 bb = item_at(2 * (size_t) at), bt = item_at(2 * (size_t) at + 1);
+                            const float qx = fmaxf(fmaxf(bb.x - wx, wx - bb.y), 0.0f), qy = fmaxf(fmaxf(bb.z - wy, wy - bb.w), 0.0f);
+                            if (qx * qx + qy * qy > rr * rr) continue;
+                            const int j = __float_as_int(bt.y), rw = __float_as_int(bt.w);
+                            const int sl = B.gen[cur][gen_index(B.compact, S, rw & kRowMask, (size_t) i)];
+                            const float4 la = B.lmkA[(rw >> 30) & 1][(size_t) j * S + (size_t) sl];
+                            pairs++;
+                            const float ex = la.x - wx, ey = la.y - wy, dd = ex * ex + ey * ey;
+                            if (dd < d1 || (dd == d1 && j < j1)) {
+                                d2 = d1;
+                                d1 = dd;
+                                j1 = j;
+                            } else if (dd < d2) {
+                                d2 = dd;
+                            }
+                        }
+                    }
+                    if (jbest < 0 && d1 < rho * rho) xlabel = d2 > A.excl_ratio * A.excl_ratio * d1 ? j1 : kAssocDiscard;
+                }
+            }
             label = jbest > -1 ? jbest : (outer > gate2 ? kAssocNew : kAssocDiscard);
+            if constexpr (EXCL)
+                if (xlabel != kVoteEmpty) label = xlabel;
             if (labels) labels[A.lab_by_obs ? (size_t) q * S + i : (size_t) i * A.nz + q] = label;
         }
         if (A.census_first) {
@@ -3254,7 +3473,11 @@ __global__ void __launch_bounds__(kBlock) associate_grid_kernel(Buffers B, Assoc
     }
     if (__ballot(full) && lane == 0) atomicOr(&A.geom->overflow, 2);
     pairs = (unsigned long long) wave_sum_d((double) pairs);
-    if (lane == 0 && pairs) atomicAdd(&A.geom->pairs, pairs);
+    if constexpr (PEROBS) {
+        if (lane == 0 && pairs) atomicAdd(A.lstats + 3, pairs);
+    } else {
+        if (lane == 0 && pairs) atomicAdd(&A.geom->pairs, pairs);
+    }
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -4012,7 +4235,7 @@ static void launch_lmk_box(hipStream_t st, const Buffers &B, const int32_t *ids,
 
 static void launch_assoc_grid(hipStream_t st, const Buffers &B, const AssocGridArgs &A) {
     hipLaunchKernelGGL(assoc_geom_partial_kernel, dim3(kGeomBlocks), dim3(kBlock), 0, st, B, A.geom_part);
-    hipLaunchKernelGGL(assoc_geom_kernel, dim3(1), dim3(kBlock), 0, st, B, A, A.geom_part);
+    hipLaunchKernelGGL(assoc_geom_kernel<false>, dim3(1), dim3(kBlock), 0, st, B, A, A.geom_part);
     const int gb = (A.nf + kBlock - 1) / kBlock;
     hipLaunchKernelGGL(assoc_count_kernel, dim3(gb), dim3(kBlock), 0, st, A, 0);
     hipLaunchKernelGGL(assoc_scan_kernel, dim3(1), dim3(kBlock), 0, st, A);
@@ -4054,8 +4277,8 @@ static void launch_associate_grid(hipStream_t st, const Buffers &B, const AssocG
 }
 static void launch_assoc_lists(hipStream_t st, const Buffers &B, const AssocGridArgs &A) {
     hipLaunchKernelGGL(assoc_geom_partial_kernel, dim3(kGeomBlocks), dim3(kBlock), 0, st, B, A.geom_part);
-    hipLaunchKernelGGL(assoc_geom_kernel, dim3(1), dim3(kBlock), 0, st, B, A, A.geom_part);
-    hipLaunchKernelGGL(assoc_lists_kernel, dim3(A.nz), dim3(kBlock), 0, st, A, B.erow, B.lmk_live);
+    hipLaunchKernelGGL(assoc_geom_kernel<false>, dim3(1), dim3(kBlock), 0, st, B, A, A.geom_part);
+    hipLaunchKernelGGL(assoc_lists_kernel<false>, dim3(A.nz), dim3(kBlock), 0, st, A, B.erow, B.lmk_live);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -4250,10 +4473,37 @@ static void launch_pp_resolve_dev(hipStream_t st, const int32_t *labels, int n, 
                        (const int32_t *) P.uidx, (const int32_t *) P.newk, 0, 0, P.p_new, P.logw, lds_words, obs, wf, any, (const ObsPacket *) P.pkt, P.obs);
 }
 
+// SLAMGPU_ASSOC_LISTS (kernels.h: KernelTable::lists_*); A.nz: the observations (DEV: the host's bound on them, >= 1)
+static void launch_lists_box(hipStream_t st, const Buffers &B, const PpArgs &P, int all, int blocks, LmkBox *box) {
+    if (blocks > 0) hipLaunchKernelGGL(lmk_box_dev_kernel, dim3(blocks), dim3(kBlock), 0, st, B, P, all, box);
+}
+static void launch_lists_geom(hipStream_t st, const Buffers &B, const AssocListArgs &A, int stage) {
+    if (stage == 0) hipLaunchKernelGGL(assoc_geom_partial_kernel, dim3(kGeomBlocks), dim3(kBlock), 0, st, B, A.geom_part);
+    else if (A.obs) hipLaunchKernelGGL(assoc_geom_kernel<true>, dim3(1), dim3(kBlock), 0, st, B, A, A.geom_part);
+    else hipLaunchKernelGGL(assoc_geom_kernel<false>, dim3(1), dim3(kBlock), 0, st, B, (const AssocGridArgs &) A, A.geom_part);
+}
+static void launch_lists_build(hipStream_t st, const Buffers &B, const AssocListArgs &A) {
+    if (A.obs) hipLaunchKernelGGL((assoc_lists_kernel<true, true>), dim3(A.nz), dim3(kBlock), 0, st, A, B.erow, B.lmk_live);
+    else hipLaunchKernelGGL((assoc_lists_kernel<true, false>), dim3(A.nz), dim3(kBlock), 0, st, A, B.erow, B.lmk_live);
+}
+static void launch_lists_walk(hipStream_t st, const Buffers &B, const AssocListArgs &A, const float *R4, float g1, float g2, int32_t *labels) {
+    const dim3 grid(B.ncap / kBlock, (A.nz + A.obs_per_block - 1) / A.obs_per_block);
+    const bool excl = A.excl_base + A.excl_per_m > 0.0f;
+    if (A.obs && excl)
+        hipLaunchKernelGGL((associate_grid_kernel<true, true, true, true>), grid, dim3(kBlock), 0, st, B, A, R4[0], R4[1], R4[2], R4[3], g1, g2, labels);
+    else if (A.obs)
+        hipLaunchKernelGGL((associate_grid_kernel<true, true, false, true>), grid, dim3(kBlock), 0, st, B, A, R4[0], R4[1], R4[2], R4[3], g1, g2, labels);
+    else if (excl)
+        hipLaunchKernelGGL((associate_grid_kernel<true, true, true, false>), grid, dim3(kBlock), 0, st, B, A, R4[0], R4[1], R4[2], R4[3], g1, g2, labels);
+    else
+        hipLaunchKernelGGL((associate_grid_kernel<true, true, false, false>), grid, dim3(kBlock), 0, st, B, A, R4[0], R4[1], R4[2], R4[3], g1, g2, labels);
+}
+
 static const KernelTable kTable = {launch_update, launch_update_particle, launch_update_persist, launch_resample, launch_resample_ref, launch_scan, launch_gather, launch_flatten, launch_identity, launch_decompact, launch_finish, launch_predict, launch_estimate, launch_jacobians, launch_kat, launch_observe, launch_observe_book, launch_associate,
                                    launch_shard_plan, launch_shard_pack, launch_shard_unpack, launch_shard_finish, launch_dist_gather, launch_dist_flags, launch_peek, launch_lmk_box, launch_assoc_grid, launch_assoc_lists, launch_vote_compact,
                                    launch_associate_grid, launch_jacobians_multi, launch_pp_census, launch_pp_resolve, launch_pp_holders,
-                                   launch_pp_resample, launch_pp_gather, launch_pp_associate, launch_pp_book, launch_pp_resolve_dev, launch_update_particle_dev};
+                                   launch_pp_resample, launch_pp_gather, launch_pp_associate, launch_pp_book, launch_pp_resolve_dev, launch_update_particle_dev,
+                                   launch_lists_box, launch_lists_geom, launch_lists_build, launch_lists_walk};
 
 }  // namespace SLAM_KNS
 

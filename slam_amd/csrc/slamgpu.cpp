@@ -300,6 +300,10 @@ struct slamgpu_ctx {
     int pp_words_w = 0;
     char *pp_pkt_dev = nullptr;       // the update's packet (fixed layout, cap = cap_nf)
     int32_t *pp_report_dev = nullptr; // [kHistCap][8] reports of the iterations not fetched yet
+    // SLAMGPU_ASSOC_LISTS: cumulative counters (AssocListArgs::lstats; [4]: observations past the host's bound, reported by the next
+    // slamgpu_particle_report_fetch) and whether device-driven iterations have written slots without refreshing their boxes
+    unsigned long long *lstats_dev = nullptr;
+    bool box_dev_stale = false;
     int pp_report_n = 0;
     bool pp_stage_open = false;       // the previous iteration may have left a resampling stage (the device knows) and no gather has run since
     double *pp_prev_hist = nullptr;   // ... its history slot and the parity of its weight scratch
@@ -990,7 +994,7 @@ void slamgpu_destroy(slamgpu_ctx *c) {
     if (c->pp_tab_dev) (void) hipFree(c->pp_tab_dev);
     if (c->pp_wf_dev) (void) hipFree(c->pp_wf_dev);
     if (c->pp_any_dev) (void) hipFree(c->pp_any_dev);
-    for (void *p_ : {(void *) c->pp_st_dev, (void *) c->pp_words_dev, (void *) c->pp_pkt_dev, (void *) c->pp_report_dev})
+    for (void *p_ : {(void *) c->pp_st_dev, (void *) c->pp_words_dev, (void *) c->pp_pkt_dev, (void *) c->pp_report_dev, (void *) c->lstats_dev})
         if (p_) (void) hipFree(p_);
     for (void *p_ : {(void *) c->box_dev, (void *) c->assoc_ids_dev, (void *) c->cell_start_dev, (void *) c->cell_fill_dev, (void *) c->items_dev,
                      (void *) c->geom_dev})
@@ -2848,6 +2852,24 @@ void assoc_resolve(int nz, std::vector<int32_t> &best, const std::vector<double>
 }  // namespace
 
 namespace {
+// the boxes, grid / list and geometry buffers of the prefilter
+int grid_buffers(slamgpu_ctx *c) {
+    if (c->box_dev) return 0;
+    const int cap_nf = c->B.cap_nf;
+    // (a landmark whose estimates are scattered over the whole region lands in every cell: room for that on small
+    // maps, 64 cells per landmark + 4 Mi entries on large ones; beyond it the exhaustive scan takes over)
+    c->cap_items = (int32_t) std::min<int64_t>((int64_t) cap_nf * kAssocMaxCells * kAssocMaxCells, 64 * (int64_t) cap_nf + (4 << 20));
+    LmkBox *box = nullptr;
+    HIP_TRY(hipMalloc((void **) &box, sizeof(LmkBox) * (size_t) cap_nf));
+    HIP_TRY(hipMalloc((void **) &c->assoc_ids_dev, sizeof(int32_t) * (size_t) cap_nf));
+    HIP_TRY(hipMalloc((void **) &c->cell_start_dev, sizeof(int32_t) * (kAssocMaxCells * kAssocMaxCells + 1)));
+    HIP_TRY(hipMalloc((void **) &c->cell_fill_dev, sizeof(int32_t) * (kAssocMaxCells * kAssocMaxCells)));
+    HIP_TRY(hipMalloc((void **) &c->items_dev, sizeof(float4) * 2 * (size_t) c->cap_items));
+    HIP_TRY(hipMalloc((void **) &c->geom_dev, sizeof(AssocGeom) + sizeof(float) * 8 * 64));  // (+ the partial boxes behind it)
+    c->box_dev = box;  // (last: the buffers are complete)
+    return 0;
+}
+
 // lab_ext: a device array the labels are left in BY OBSERVATION, [nz][ncap] (slamgpu_update_particle: they never visit the host), or null
 int associate_impl(slamgpu_ctx *c, const float *z, int32_t nz, const float R[4], float gate_reject, float gate_augment, int32_t mode,
                    int32_t *labels, int32_t *consensus, float *support, double stats[4], int32_t *lab_ext, const float *excl3 = nullptr) {
@@ -2913,18 +2935,7 @@ int associate_impl(slamgpu_ctx *c, const float *z, int32_t nz, const float R[4],
     c->B.slot = c->slot;
     if (!rc && grid) {
         // boxes of the landmarks written since the last call, then geometry + grid, then the pruned scan with the vote
-        const int cap_nf = c->B.cap_nf;
-        if (!c->box_dev) {
-            // (a landmark whose estimates are scattered over the whole region lands in every cell: room for that on small
-            // maps, 64 cells per landmark + 4 Mi entries on large ones; beyond it the exhaustive scan takes over)
-            c->cap_items = (int32_t) std::min<int64_t>((int64_t) cap_nf * kAssocMaxCells * kAssocMaxCells, 64 * (int64_t) cap_nf + (4 << 20));
-            step(hipMalloc((void **) &c->box_dev, sizeof(LmkBox) * (size_t) cap_nf), "hipMalloc");
-            step(hipMalloc((void **) &c->assoc_ids_dev, sizeof(int32_t) * (size_t) cap_nf), "hipMalloc");
-            step(hipMalloc((void **) &c->cell_start_dev, sizeof(int32_t) * (kAssocMaxCells * kAssocMaxCells + 1)), "hipMalloc");
-            step(hipMalloc((void **) &c->cell_fill_dev, sizeof(int32_t) * (kAssocMaxCells * kAssocMaxCells)), "hipMalloc");
-            step(hipMalloc((void **) &c->items_dev, sizeof(float4) * 2 * (size_t) c->cap_items), "hipMalloc");
-            step(hipMalloc((void **) &c->geom_dev, sizeof(AssocGeom) + sizeof(float) * 8 * 64), "hipMalloc");  // (+ the partial boxes behind it)
-        }
+        if (!rc) rc = grid_buffers(c);
         std::vector<int32_t> ids;
         for (int j = 0; j < c->nf; j++)
             if (c->box_dirty[j]) ids.push_back(j);
@@ -3460,14 +3471,122 @@ int do_update_particle(slamgpu_ctx *c, const float *z, int32_t nz, const float R
 }
 }  // namespace
 
+namespace {
+// ---- SLAMGPU_ASSOC_LISTS: candidate lists built from the device's state (kernels.h: AssocListArgs) ----
+// the prefilter's buffers and the cumulative counters
+int lists_buffers(slamgpu_ctx *c) {
+    if (int rc = grid_buffers(c)) return rc;
+    if (!c->lstats_dev) {
+        unsigned long long *p = nullptr;
+        HIP_TRY(hipMalloc((void **) &p, sizeof(unsigned long long) * 8));
+        HIP_TRY(hipMemset(p, 0, sizeof(unsigned long long) * 8));
+        c->lstats_dev = p;
+    }
+    return 0;
+}
+
+// what every launch of the lists shares; nz: the observations (device-driven: the host's bound on them, the lists grid)
+void lists_args(slamgpu_ctx *c, int nz, const float R[4], const slamgpu_particle_assoc *opt, AssocListArgs &G) {
+    G = AssocListArgs{};
+    G.box = c->box_dev;
+    G.geom = c->geom_dev;
+    G.geom_part = reinterpret_cast<float *>(c->geom_dev + 1);
+    G.cell_start = c->cell_start_dev;
+    G.cell_fill = c->cell_fill_dev;
+    G.items = c->items_dev;
+    G.cap_items = c->cap_items;
+    G.nf = c->nf;
+    G.nz = std::max(nz, 1);
+    G.r00 = R[0];
+    G.r11 = R[3];
+    G.G = std::max(opt->gate_reject, opt->gate_augment) * 1.001f;
+    G.G1 = std::min(opt->gate_reject * 1.001f, G.G);
+    G.g1_ratio = sqrtf(G.G1 / G.G);
+    // (associate_impl's rules for the workgroup's observations and the list length, SLAMGPU_ASSOC_LCAP included)
+    G.obs_per_block = (int) std::min<int64_t>(64, std::max<int64_t>(kAssocObsPerBlock, (int64_t) (c->B.ncap / kBlock) * G.nz / 2048));
+    if (const char *e = getenv("SLAMGPU_ASSOC_OBS_PER_BLOCK")) G.obs_per_block = std::max(1, atoi(e));
+    G.lcap = (int) std::max<int64_t>(1, std::min<int64_t>(2048, (int64_t) c->cap_items / G.nz));
+    if (const char *e = getenv("SLAMGPU_ASSOC_LCAP")) G.lcap = std::min(G.lcap, std::max(1, atoi(e)));
+    G.lab_by_obs = 1;
+    G.logw = c->cfg.log_weights;
+    G.retired = c->retired_dev;
+    G.excl_base = opt->excl_base;
+    G.excl_per_m = opt->excl_per_m;
+    G.excl_ratio = opt->unique_ratio;
+    G.lstats = c->lstats_dev;
+}
+
+// slamgpu_update_particle's association through the lists: the labels into pp_lab_dev and their census into the context's table, as the
+// grid leaves them (do_update_particle: pp_census_done); nz <= kAssocMaxCells^2, pp_reserve done
+int associate_lists(slamgpu_ctx *c, const float *z, int32_t nz, const float R[4], const slamgpu_particle_assoc *opt) {
+    c->pp_census_done = false;
+    if (int rc = flush_predict(c)) return rc;
+    if (int rc = materialize(c)) return rc;  // plain set: particle k in slot k
+    if (int rc = sync_tables(c)) return rc;
+    if (int rc = lists_buffers(c)) return rc;
+    if (c->retired_stale)
+        if (int rc = retired_upload(c)) return rc;
+    c->B.slot = c->slot;
+    const int cap_nf = c->B.cap_nf;
+    // the boxes of the slots written (or retired) since the last refresh
+    std::vector<int32_t> ids;
+    for (int j = 0; j < c->nf; j++)
+        if (c->box_dirty[(size_t) j]) ids.push_back(j);
+    HIP_TRY(hipMemcpyAsync(c->pp_z_dev, z, sizeof(float) * 2 * (size_t) nz, hipMemcpyHostToDevice, c->stream));
+    if (!ids.empty()) HIP_TRY(hipMemcpyAsync(c->assoc_ids_dev, ids.data(), sizeof(int32_t) * ids.size(), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));  // (pageable sources)
+    AssocListArgs G;
+    lists_args(c, nz, R, opt, G);
+    G.z = c->pp_z_dev;
+    G.census_first = c->pp_tab_dev;  // (do_update_particle's table: first | holders | news)
+    G.census_news = c->pp_tab_dev + 2 * (size_t) cap_nf;
+    HIP_TRY(hipMemsetD32Async((hipDeviceptr_t) G.census_first, 0x7fffffff, (size_t) cap_nf, c->stream));
+    HIP_TRY(hipMemsetAsync(G.census_news, 0, sizeof(int32_t) * (size_t) nz, c->stream));
+    {
+        Timed t(c, "associate");
+        if (!ids.empty()) c->k->lmk_box(c->stream, c->B, c->assoc_ids_dev, (int) ids.size(), c->retired_dev, c->box_dev);
+        c->k->lists_geom(c->stream, c->B, G, 0);
+        c->k->lists_geom(c->stream, c->B, G, 1);
+        c->k->lists_build(c->stream, c->B, G);
+        c->k->lists_walk(c->stream, c->B, G, R, opt->gate_reject, opt->gate_augment, c->pp_lab_dev);
+    }
+    HIP_TRY(hipGetLastError());
+    for (int j : ids) c->box_dirty[(size_t) j] = 0;
+    c->pp_census_done = true;
+    return 0;
+}
+
+// an upper bound on the observations slamgpu_observe makes from pose xt: observe_kernel's visibility test, a little wider
+int nz_bound(const slamgpu_ctx *c, const float *xt, float max_range) {
+    const float x = xt[0], y = xt[1], r = max_range * 1.001f + 1e-3f;
+    const double cph = cos((double) xt[2]), sph = sin((double) xt[2]);
+    const float *lx = c->map_host.data(), *ly = lx + c->map_n;
+    int n = 0;
+    for (int j = 0; j < c->map_n; j++) {
+        const float dx = lx[j] - x, dy = ly[j] - y;
+        if (!(fabsf(dx) < r && fabsf(dy) < r)) continue;
+        const double d2 = (double) dx * dx + (double) dy * dy;
+        if (d2 < (double) r * r && dx * cph + dy * sph > -1e-3 * (1.0 + fabs(dx) + fabs(dy))) n++;
+    }
+    return n;
+}
+}  // namespace
+
 int slamgpu_update_particle(slamgpu_ctx *c, const float *z, int32_t nz, const float R[4], const slamgpu_particle_assoc *opt, const float *normals,
                             const float *strata, int32_t report[8]) {
     if (report) memset(report, 0, sizeof(int32_t) * 8);
     if (int rc = pp_check(c, z, nz, R, opt)) return rc;
-    if (opt->mode < SLAMGPU_ASSOC_AUTO || opt->mode > SLAMGPU_ASSOC_GRID) return fail(SLAMGPU_ERR_INVALID, "unknown association mode %d", opt->mode);
+    if (opt->mode < SLAMGPU_ASSOC_AUTO || opt->mode > SLAMGPU_ASSOC_LISTS) return fail(SLAMGPU_ERR_INVALID, "unknown association mode %d", opt->mode);
+    if (opt->mode == SLAMGPU_ASSOC_LISTS && nz > kAssocMaxCells * kAssocMaxCells)
+        return fail(SLAMGPU_ERR_CAPACITY, "SLAMGPU_ASSOC_LISTS: %d observations in one step (at most %d)", nz, kAssocMaxCells * kAssocMaxCells);
     if (nz == 0) return 0;  // (no observation, no update: fastslam2wrapper.cpp:84-95)
     HIP_TRY(hipSetDevice(c->cfg.device));
     if (int rc = pp_reserve(c, nz, 1)) return rc;
+    if (opt->mode == SLAMGPU_ASSOC_LISTS) {
+        if (int rc = book_pull(c)) return rc;  // (the device-driven state back first: the boxes and the mask are the host's again)
+        if (int rc = associate_lists(c, z, nz, R, opt)) return rc;
+        return do_update_particle(c, z, nz, R, opt, normals, strata, report);
+    }
     const float excl3[3] = {opt->excl_base, opt->excl_per_m, opt->unique_ratio};
     if (int rc = associate_impl(c, z, nz, R, opt->gate_reject, opt->gate_augment, opt->mode, nullptr, nullptr, nullptr, nullptr, c->pp_lab_dev, excl3)) return rc;
     return do_update_particle(c, z, nz, R, opt, normals, strata, report);
@@ -3641,6 +3760,7 @@ int pp_pull(slamgpu_ctx *c) {
     std::copy(ref.begin(), ref.end(), c->refcnt.begin());
     book_rebuild(c);
     c->fresh_row = -1;
+    c->box_dev_stale = false;  // (book_rebuild has marked every box for a refresh)
     c->pp_dead_list.clear();
     c->n_retired = 0;
     for (int l = 0; l < cn; l++) {
@@ -3716,8 +3836,9 @@ int pp_dev_flush_predict(slamgpu_ctx *c) {
 }
 
 // one iteration of slamgpu_run_particle: nothing here waits for the device or copies memory
+// (bound >= 0: SLAMGPU_ASSOC_LISTS, with the host's bound on this iteration's observations; box_all: refresh every slot's box first)
 int pp_dev_iteration(slamgpu_ctx *c, int32_t nc, const float *controls, const float Q[4], float dt, const float xtrue[3], float max_range,
-                     const float R[4], int32_t noise, const slamgpu_particle_assoc *opt, int need) {
+                     const float R[4], int32_t noise, const slamgpu_particle_assoc *opt, int need, int bound, bool box_all) {
     c->pp_stage_open = true;  // (the previous iteration may have updated: only the device knows)
     for (int k = 0; k < nc; k++) {
         const PredictArgs &P = c->pending;  // (slamgpu_predict's own flush would go through the host's tables: flush here instead)
@@ -3756,8 +3877,38 @@ int pp_dev_iteration(slamgpu_ctx *c, int32_t nc, const float *controls, const fl
     P.need = need;
     P.p_new = opt->p_new;
     c->B.slot = c->slot;
-    const float excl3[3] = {opt->excl_base, opt->excl_per_m, opt->unique_ratio};
-    {
+    if (bound >= 0) {
+        // the boxes of the slots the previous iteration wrote, the geometry, one list per observation, the walk (+ the census)
+        AssocListArgs G;
+        lists_args(c, bound, R, opt, G);
+        G.obs = c->obs_out_dev;
+        G.book = c->book_dev;
+        G.retired = P.retired;
+        G.census_first = P.first;
+        G.census_news = P.news;
+        G.P = P;
+        {
+            Timed t(c, "lmk_box");
+            c->k->lists_box(c->stream, c->B, P, box_all ? 1 : 0, std::min(c->B.cap_nf, 1024), c->box_dev);
+        }
+        {
+            Timed t(c, "assoc_geom_partial");
+            c->k->lists_geom(c->stream, c->B, G, 0);
+        }
+        {
+            Timed t(c, "assoc_geom");
+            c->k->lists_geom(c->stream, c->B, G, 1);
+        }
+        {
+            Timed t(c, "assoc_lists");
+            c->k->lists_build(c->stream, c->B, G);
+        }
+        {
+            Timed t(c, "associate");
+            c->k->lists_walk(c->stream, c->B, G, R, opt->gate_reject, opt->gate_augment, c->pp_lab_dev);
+        }
+    } else {
+        const float excl3[3] = {opt->excl_base, opt->excl_per_m, opt->unique_ratio};
         Timed t(c, "associate");
         c->k->pp_associate(c->stream, c->B, R, opt->gate_reject, opt->gate_augment, excl3, c->pp_lab_dev, P);
     }
@@ -3815,9 +3966,10 @@ int slamgpu_run_particle(slamgpu_ctx *c, int32_t K, const int32_t *n_controls, c
     if (c->cfg.rng_mode == SLAMGPU_RNG_TAPE) return fail(SLAMGPU_ERR_INVALID, "slamgpu_run_particle: TAPE-mode contexts take their draws per step");
     if (K == 0) return 0;
     if (!c->map_dev) return fail(SLAMGPU_ERR_INVALID, "slamgpu_run_particle: no map: call slamgpu_set_map first");
-    if (opt->mode < SLAMGPU_ASSOC_AUTO || opt->mode > SLAMGPU_ASSOC_GRID) return fail(SLAMGPU_ERR_INVALID, "unknown association mode %d", opt->mode);
+    if (opt->mode < SLAMGPU_ASSOC_AUTO || opt->mode > SLAMGPU_ASSOC_LISTS) return fail(SLAMGPU_ERR_INVALID, "unknown association mode %d", opt->mode);
     if (opt->mode == SLAMGPU_ASSOC_GRID)
-        return fail(SLAMGPU_ERR_INVALID, "slamgpu_run_particle: the association is the exhaustive scan (SLAMGPU_ASSOC_EXHAUSTIVE or _AUTO)");
+        return fail(SLAMGPU_ERR_INVALID, "slamgpu_run_particle: the association is the exhaustive scan or the lists (SLAMGPU_ASSOC_EXHAUSTIVE, _AUTO or _LISTS)");
+    const bool lists = opt->mode == SLAMGPU_ASSOC_LISTS;
     if (int rc = pp_check(c, xtrue, 0, R, opt)) return rc;
     size_t total = 0;
     for (int32_t k = 0; k < K; k++) {
@@ -3831,20 +3983,54 @@ int slamgpu_run_particle(slamgpu_ctx *c, int32_t K, const int32_t *n_controls, c
     if ((int64_t) c->pp_report_n + K > kHistCap)
         return fail(SLAMGPU_ERR_CAPACITY, "slamgpu_run_particle: %d iterations would overflow the report ring (%d of %d entries in use): call "
                                           "slamgpu_particle_report_fetch first", (int) K, c->pp_report_n, kHistCap);
-    if ((double) c->B.n * (double) c->B.cap_nf * (double) c->map_n > 4e10)
+    if (!lists && (double) c->B.n * (double) c->B.cap_nf * (double) c->map_n > 4e10)
         return fail(SLAMGPU_ERR_CAPACITY, "slamgpu_run_particle: the exhaustive scan of %d particles x %d slots x %d observations is too much for one launch",
                     c->B.n, c->B.cap_nf, c->map_n);
+    // (the lists: every iteration's observations bounded from the map and the true pose -- the lists grid; at most kAssocMaxCells^2)
+    std::vector<int> bounds((size_t) K, -1);
+    if (lists)
+        for (int32_t k = 0; k < K; k++) {
+            bounds[(size_t) k] = nz_bound(c, xtrue + 3 * (size_t) k, max_range);
+            if (bounds[(size_t) k] > kAssocMaxCells * kAssocMaxCells)
+                return fail(SLAMGPU_ERR_CAPACITY, "slamgpu_run_particle: iteration %d may see %d observations; SLAMGPU_ASSOC_LISTS takes at most %d", (int) k,
+                            bounds[(size_t) k], kAssocMaxCells * kAssocMaxCells);
+        }
     if (int rc = persist_check(c)) return rc;
     HIP_TRY(hipSetDevice(c->cfg.device));
     const int nmax = std::min(c->map_n, c->B.cap_nf);
     if (int rc = pp_reserve_particles(c, c->map_n, (size_t) c->B.cap_nf + nmax + 1)) return rc;  // (pp_nz_cap stays the host path's: PpState::census_cap)
     if (int rc = pp_setup(c)) return rc;
+    if (lists)
+        if (int rc = lists_buffers(c)) return rc;
+    const bool was_host = !c->pp_on_device;
     if (int rc = pp_push(c, c->pp_nz_cap)) return rc;
+    bool box_all = false;
+    if (lists) {
+        // the boxes the host's steps left stale (written or retired since its last refresh), at the hand-over; the device-driven
+        // iterations refresh what they write themselves, unless they ran without the lists (then every box, in the first iteration)
+        if (was_host) {
+            std::vector<int32_t> ids;
+            for (int j = 0; j < c->nf; j++)
+                if (c->box_dirty[(size_t) j] || c->retired[(size_t) j]) ids.push_back(j);
+            if (!ids.empty()) {
+                HIP_TRY(hipMemcpy(c->assoc_ids_dev, ids.data(), sizeof(int32_t) * ids.size(), hipMemcpyHostToDevice));
+                c->B.slot = c->slot;
+                c->k->lmk_box(c->stream, c->B, c->assoc_ids_dev, (int) ids.size(), c->retired_dev, c->box_dev);
+                HIP_TRY(hipGetLastError());
+                for (int j : ids) c->box_dirty[(size_t) j] = 0;
+            }
+        }
+        box_all = c->box_dev_stale;
+        c->box_dev_stale = false;
+    } else {
+        c->box_dev_stale = true;
+    }
     const int need = std::max(1, (int) ceil((double) opt->new_share * (double) c->B.n));
     size_t row = 0;
     for (int32_t k = 0; k < K; k++) {
         const int32_t nc = n_controls[k];
-        if (int rc = pp_dev_iteration(c, nc, nc ? controls + 3 * row : nullptr, Q, dt, xtrue + 3 * (size_t) k, max_range, R, noise, opt, need)) {
+        if (int rc = pp_dev_iteration(c, nc, nc ? controls + 3 * row : nullptr, Q, dt, xtrue + 3 * (size_t) k, max_range, R, noise, opt, need,
+                                      bounds[(size_t) k], box_all && k == 0)) {
             std::string why = slamgpu_last_error();
             return fail(rc, "slamgpu_run_particle: iteration %d of %d: %s", (int) k, (int) K, why.c_str());
         }
@@ -3857,6 +4043,17 @@ int slamgpu_particle_report_fetch(slamgpu_ctx *c, int32_t *report, int32_t max_c
     if (int rc = check_ctx(c)) return rc;
     if (!count || (max_count > 0 && !report)) return fail(SLAMGPU_ERR_INVALID, "slamgpu_particle_report_fetch: null output");
     *count = 0;
+    if (c->lstats_dev) {  // (SLAMGPU_ASSOC_LISTS: observations past the host's bound were walked over every slot -- reported once, here)
+        HIP_TRY(hipSetDevice(c->cfg.device));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        unsigned long long past = 0;
+        HIP_TRY(hipMemcpy(&past, c->lstats_dev + 4, sizeof past, hipMemcpyDeviceToHost));
+        if (past) {
+            HIP_TRY(hipMemset(c->lstats_dev + 4, 0, sizeof past));
+            return fail(SLAMGPU_ERR_CAPACITY, "slamgpu_particle_report_fetch: %llu observations exceeded the launch bound of SLAMGPU_ASSOC_LISTS (their "
+                                              "labels are the exhaustive scan's; the reports stay for the next fetch)", past);
+        }
+    }
     if (c->pp_report_n == 0) return 0;
     HIP_TRY(hipSetDevice(c->cfg.device));
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -3869,6 +4066,19 @@ int slamgpu_particle_report_fetch(slamgpu_ctx *c, int32_t *report, int32_t max_c
         HIP_TRY(hipMemcpy(c->pp_report_dev, h.data() + 8 * (size_t) n, sizeof(int32_t) * 8 * (size_t) left, hipMemcpyHostToDevice));
     c->pp_report_n = left;
     *count = n;
+    return 0;
+}
+
+int slamgpu_particle_list_stats(slamgpu_ctx *c, int64_t out[4]) {
+    if (int rc = check_ctx(c)) return rc;
+    if (!out) return fail(SLAMGPU_ERR_INVALID, "slamgpu_particle_list_stats: null output");
+    unsigned long long h[4] = {0, 0, 0, 0};
+    if (c->lstats_dev) {
+        HIP_TRY(hipSetDevice(c->cfg.device));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        HIP_TRY(hipMemcpy(h, c->lstats_dev, sizeof h, hipMemcpyDeviceToHost));
+    }
+    for (int k = 0; k < 4; k++) out[k] = (int64_t) h[k];
     return 0;
 }
 
