@@ -142,3 +142,26 @@ def test_dump_outputs_fits_its_budget(tmp_path):
         assert np.array_equal(files["resampled"], res.astype(np.float32))
         assert (s.asked[1] == 1) == whole and s.asked[0] == 0 and s.asked[1] * (s.asked[2] - 1) < N <= s.asked[1] * s.asked[2]
         assert np.array_equal(files["particle_index"], files["w"]) and ("xf" in files) == (nf > 0)
+
+
+def test_plain_run_leaves_everything_else_to_full(monkeypatch, capsys):
+    # a plain single-GPU run times the headline alone (no per-kernel event pass, nothing beside it); --full adds the rest
+    import slam_amd
+    calls = []
+
+    def line(a, config_id, math, steps, warmup, start=None, particles=None, max_range=None, event_pass=True, **kw):
+        calls.append(("line", config_id, math, steps, warmup, event_pass, kw.get("dump")))
+        return {"config": {"window_start": 1000}}, [], dict(bench.CONFIGS[3]), 100000
+
+    monkeypatch.setattr(slam_amd, "device_count", lambda: 1)
+    monkeypatch.setattr(bench, "single_gpu_line", line)
+    monkeypatch.setattr(bench, "full_extras", lambda a, out, *rest: calls.append(("full", a.no_cpu_baseline)))
+    for argv, want in ((["--gpus", "1", "--steps", "20", "--warmup", "5"], [("line", 3, "fast", 20, 5, False, None)]),
+                       (["--gpus", "1", "--steps", "20", "--warmup", "5", "--dump-outputs", "D"], [("line", 3, "fast", 20, 5, False, "D")]),
+                       (["--full", "--steps", "20", "--warmup", "5"], [("line", 3, "fast", 20, 5, True, None), ("full", False)]),
+                       (["--full", "--single-pass", "--no-cpu-baseline"], [("line", 3, "fast", 2000, 100, False, None), ("full", True)])):
+        calls.clear()
+        monkeypatch.setattr(sys, "argv", ["bench.py"] + argv)
+        bench.main()
+        assert calls == want, argv
+        assert json.loads(capsys.readouterr().out.strip().splitlines()[-1])["n_gpus"] == 1

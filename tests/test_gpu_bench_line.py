@@ -1,10 +1,13 @@
-"""bench.py end to end on the GPU: ONE JSON line on stdout carrying every field of the driver's contract (plus `roofline`
-and `cpu_baseline`), for the default single-GPU run and for the multi-GPU code path launched with one rank."""
+"""bench.py end to end on the GPU: ONE JSON line on stdout carrying every field of the driver's contract (plus `roofline`), for
+the plain single-GPU run, for the --full one (`also`, `dist_path_n1`, `particle_association`, `cpu_baseline`) and for the multi-GPU
+code path launched with one rank."""
 import json
 import os
 import subprocess
 import sys
+import time
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -35,8 +38,32 @@ def check_common(j, steps, warmup):
     assert r["bound"] == "hbm" and r["unit"] == "GB/s" and abs(r["frac"] - r["achieved"] / r["peak"]) < 1e-9
 
 
+def test_plain_line_single_gpu(tmp_path):
+    """what is run for every change: the headline alone -- the window picked from the whole run and timed --repeats times, the
+    outputs of the timed steps written -- and nothing that takes runs of its own"""
+    steps, warmup = 60, 5
+    t0 = time.time()
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", str(warmup),
+                        "--dump-outputs", str(tmp_path)], cwd=ROOT, capture_output=True, text=True, timeout=600)
+    wall = time.time() - t0
+    assert r.returncode == 0, r.stderr[-2000:]
+    j = one_line(r.stdout)
+    check_common(j, steps, warmup)
+    assert j["roofline"]["kernel"] == "fs2_update" and "kernel_ms" not in j["roofline"]
+    assert 1e9 < j["value"] < 2e10 and j["config"]["degenerate_steps"] == 0
+    assert j["window_repeats"]["repeats"] == 5 and j["ms_per_step"] == sorted(j["window_repeats"]["ms_per_step_all"])[2]
+    assert abs(j["config"]["mean_m"] / 3.535 - 1) <= 0.1 and j["whole_run"]["steps"] > 2000
+    for k in ("also", "dist_path_n1", "particle_association", "cpu_baseline"):
+        assert k not in j, k
+    d = j["dump_outputs"]
+    assert sorted(os.listdir(str(tmp_path))) == sorted(f + ".npy" for f in d["files"]) and len(d["files"]) >= 8
+    assert np.load(str(tmp_path / "estimates.npy")).shape == (steps, 3)
+    # what a plain run may spend outside its steps
+    assert wall - (steps + warmup) * j["ms_per_step"] * 1e-3 < 30.0, wall
+
+
 def test_default_line_single_gpu():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "60", "--warmup", "5", "--cpu-seconds", "2"], cwd=ROOT,
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "60", "--warmup", "5", "--cpu-seconds", "2"], cwd=ROOT,
                        capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     j = one_line(r.stdout)
