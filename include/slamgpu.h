@@ -378,6 +378,19 @@ int slamgpu_particle_report_fetch(slamgpu_ctx *ctx, int32_t *report, int32_t max
  * observation, slot) triples evaluated.  (slamgpu_particle_report_fetch returns SLAMGPU_ERR_CAPACITY once if an iteration of
  * slamgpu_run_particle saw more observations than the host's bound on them; they were walked over every slot.)  Synchronises. */
 int slamgpu_particle_list_stats(slamgpu_ctx *ctx, int64_t out[4]);
+/* The exclusion rule's radius capped by the step's own observation spacing (both per-particle entry points, any mode that takes the
+ * rule).  Observation q of a step implies the sensor-frame point p_q = (r_q cos b_q, r_q sin b_q) (float32); s_q is the smallest
+ * distance from p_q to any other p_q' of the step (+inf for a single observation).  With f > 0 the rule's radius becomes
+ * rho_q = min(excl_base + excl_per_m * r_q, f * s_q); f = 0 (the default) keeps excl_base + excl_per_m * r_q.  The rule itself is
+ * unchanged, and with the rule off (excl_base + excl_per_m = 0) the factor is ignored.  Where the map is dense the fixed radius would
+ * forbid every new landmark; the observations show the true local density, and distances between the points they imply do not depend
+ * on the pose, so rho is one array per step for every particle and path.  Applies to calls made after it (iterations of
+ * slamgpu_run_particle already enqueued keep their factor).  f finite and >= 0, else SLAMGPU_ERR_INVALID. */
+int slamgpu_set_particle_excl_spacing(slamgpu_ctx *ctx, float f);
+/* Diagnostic: the radii rho[0 .. nz) of the last step that made them (the last update or iteration with the factor and the rule on;
+ * an iteration without observations makes none: *nz = 0), at most max_count of them; *nz: how many the step had (0: none yet).
+ * Synchronises. */
+int slamgpu_particle_excl_radii(slamgpu_ctx *ctx, float *rho, int32_t max_count, int32_t *nz);
 
 /* Retire landmarks from the gated association (round 6): landmarks ids[0 .. count) take no part in slamgpu_associate /
  * _associate_ex from now on -- no particle gates an observation against them, nothing votes for them -- and, never being

@@ -27,6 +27,7 @@ DECLARED_SYMBOLS = [
     "slamgpu_dist_group_step", "slamgpu_dist_group_settle", "slamgpu_dist_group_history", "slamgpu_dist_group_download",
     "slamgpu_peek", "slamgpu_step_observe", "slamgpu_run_observe", "slamgpu_observe_fetch", "slamgpu_associate_ex", "slamgpu_update_particle", "slamgpu_update_labels", "slamgpu_dist_comm_info", "slamgpu_dist_remote_reads",
     "slamgpu_run_particle", "slamgpu_particle_report_fetch", "slamgpu_particle_list_stats",
+    "slamgpu_set_particle_excl_spacing", "slamgpu_particle_excl_radii",
 ]
 ASSOC_AUTO, ASSOC_EXHAUSTIVE, ASSOC_GRID, ASSOC_LISTS = 0, 1, 2, 3
 FLAG_DEVICE_OBSERVE = 1
@@ -120,6 +121,9 @@ def load_library():
         L.slamgpu_particle_report_fetch.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]
     if hasattr(L, "slamgpu_particle_list_stats"):
         L.slamgpu_particle_list_stats.argtypes = [C.c_void_p, C.c_void_p]
+    if hasattr(L, "slamgpu_set_particle_excl_spacing"):
+        L.slamgpu_set_particle_excl_spacing.argtypes = [C.c_void_p, C.c_float]
+        L.slamgpu_particle_excl_radii.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]
     L.slamgpu_genealogy_rows.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     L.slamgpu_persist_info.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
     if hasattr(L, "slamgpu_persist_status"):  # (an older build loaded through SLAMGPU_LIB for an A/B lacks the round-6 entries)
@@ -801,6 +805,18 @@ class SlamGpu:
         out = np.zeros(4, np.int64)
         _chk(self.L.slamgpu_particle_list_stats(self.h, _ptr(out)))
         return dict(zip(("steps", "entries", "overflowed", "triples"), (int(v) for v in out)))
+
+    def set_particle_excl_spacing(self, f):
+        """cap the exclusion rule's radius at f times each observation's distance to the step's nearest other observation (sensor-frame
+        points; slamgpu_set_particle_excl_spacing); 0: the fixed radius.  Applies to update_particle / run_particle calls made after it"""
+        _chk(self.L.slamgpu_set_particle_excl_spacing(self.h, C.c_float(f)))
+
+    def particle_excl_radii(self, max_count=32767):
+        """the exclusion rule's radii of the last step that made them (slamgpu_particle_excl_radii): float32 [nz]"""
+        out = np.zeros(max(int(max_count), 0), np.float32)
+        n = C.c_int32()
+        _chk(self.L.slamgpu_particle_excl_radii(self.h, _ptr(out), int(max_count), C.byref(n)))
+        return out[:min(n.value, out.size)].copy()
 
     def update_labels(self, z, R, labels, new_share=0.0, p_new=1.0, census_every=1, normals=None, strata=None):
         """the same step with the caller's labels [N, nz] (slamgpu_update_labels)"""

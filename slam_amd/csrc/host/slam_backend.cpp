@@ -15,7 +15,9 @@
 //                        gate), -PARTICLE_EXCL_BASE (2.0 m) / -PARTICLE_EXCL_PER_M (0.05) / -PARTICLE_UNIQUE_RATIO (2): the exclusion
 //                        rule of include/slamgpu.h: slamgpu_particle_assoc.  The map reported at the end is the best particle's.
 //                        -PARTICLE_ASSOC lists: the association through candidate lists built on the device (SLAMGPU_ASSOC_LISTS:
-//                        the same labels, any map size); auto (default): SLAMGPU_ASSOC_AUTO.
+//                        the same labels, any map size); auto (default): SLAMGPU_ASSOC_AUTO.  -PARTICLE_EXCL_SPACING f (default 0:
+//                        off) caps the exclusion rule's radius at f x each observation's distance to the step's nearest other one
+//                        (slamgpu_set_particle_excl_spacing): dense maps, where the fixed radius would forbid every new landmark.
 //   -plot <sinks>        the per-step output the reference sends to slam-gui (plotting/NetworkPlot.cpp), byte for byte:
 //                        tcp://127.0.0.1:4242 (the existing slam-gui) | file:<frames> | gather:<dir> (the GUI's DataGatherer
 //                        files, headless) | none (default); several separated by ','
@@ -67,6 +69,8 @@ static void usage(const char *a0) {
     printf("    -plot tcp://127.0.0.1:4242|file:<path>|gather:<dir>|none   -plotstride k\n");
     printf("    -assoc known|gated|particle   FastSLAM data association: the reference's table (default), the per-particle gates reduced to a vote,\n");
     printf("                        or the per-particle gates acted on by every particle on a map of its own\n");
+    printf("    -PARTICLE_EXCL_SPACING f  -assoc particle: cap the exclusion rule's radius at f x each observation's distance to the\n");
+    printf("                        step's nearest other observation (default 0: the fixed radius)\n");
     printf("    -gpus k             FastSLAM particle set distributed over k GPUs (k > devices: logical shards on device 0)\n");
     printf("    -observe host|device  where the observation of a step is made: host (default) or on the GPU (the packet never leaves\n");
     printf("                        device memory: slamgpu_step_observe; -rng philox, known association, no -plot; with -assoc particle:\n");
@@ -466,6 +470,11 @@ int main(int argc, char **argv) {
         popt.unique_ratio = (float) numkey("PARTICLE_UNIQUE_RATIO", 2.0);
         if (slamgpu_create(&g, &ctx) != 0) {
             fprintf(stderr, "slamgpu_create: %s\n", slamgpu_last_error());
+            return EXIT_FAILURE;
+        }
+        if (particle && slamgpu_set_particle_excl_spacing(ctx, (float) numkey("PARTICLE_EXCL_SPACING", 0.0)) != 0) {
+            fprintf(stderr, "-PARTICLE_EXCL_SPACING: %s\n", slamgpu_last_error());
+            slamgpu_destroy(ctx);
             return EXIT_FAILURE;
         }
         // the reference creates its accelerator object before the wrapper seeds rand() (SLAMBackendApplication.cpp:22-24,

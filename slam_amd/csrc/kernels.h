@@ -627,6 +627,16 @@ struct AssocListArgs : AssocGridArgs {
     PpArgs P;                     // device-driven: the holders census / estimate partials that ride in the walk
 };
 
+// The exclusion rule with its radius capped by the step's observation spacing (slamgpu_set_particle_excl_spacing): rho[q], q < nz, made
+// by excl_radii_kernel, replaces excl_base + excl_per_m * range in the RHO instantiations.  Derived types with the pointer last, so that
+// the instantiations without it keep their argument layout.
+struct PpRhoArgs : PpArgs {
+    const float *rho;
+};
+struct AssocRhoArgs : AssocListArgs {
+    const float *rho;
+};
+
 struct KernelTable {
     // the step: [resampling stage of the previous update, inline] + [gather] + [fused predicts] + per-particle observation
     // update + in-block weight prefix / totals  (+ helper blocks: genealogy copy, Ctrl words, estimate reduction)
@@ -672,8 +682,10 @@ struct KernelTable {
     // (slamgpu_associate): labels [n][nz] = landmark index, kAssocNew or kAssocDiscard.  Plain set required (no pending gather).
     // retired (may be null): bit j set = landmark j takes no part (slamgpu_retire_landmarks)
     // excl3 (may be null): excl_base, excl_per_m, unique_ratio of the exclusion rule (slamgpu_particle_assoc; base + per_m = 0: off)
+    // rho_dev (may be null; only with the rule on): the rule's radius per observation (excl_radii) in place of excl_base + excl_per_m * range
     void (*associate)(hipStream_t, const Buffers &, int nf, const float *z_dev, int nz, const float *R4, float gate_reject,
-                      float gate_augment, const float *excl3, const uint32_t *retired_dev, int32_t *labels_dev, int labels_by_obs);
+                      float gate_augment, const float *excl3, const uint32_t *retired_dev, int32_t *labels_dev, int labels_by_obs,
+                      const float *rho_dev);
     // seq_out != null: `out` and `seq_out` are pinned host memory; the kernel stores `seq` there last (system-scope fence)
     void (*shard_plan)(hipStream_t, const ShardPlanArgs &, const RngArgs &, ShardPlan *out, uint32_t *seq_out, uint32_t seq);
     void (*shard_pack)(hipStream_t, const Buffers &, const WeightScratch &, const ShardPackArgs &, const RngArgs &);
@@ -713,7 +725,7 @@ struct KernelTable {
     void (*pp_resample)(hipStream_t, const Buffers &, const WeightScratch &, const RngArgs &, const ResampleArgs &, const PpArgs &);
     void (*pp_gather)(hipStream_t, const Buffers &, const WeightScratch &, const PpArgs &, double *hist, int par);
     void (*pp_associate)(hipStream_t, const Buffers &, const float *R4, float gate_reject, float gate_augment, const float *excl3, int32_t *labels_dev,
-                         const PpArgs &);
+                         const PpArgs &, const float *rho_dev);
     void (*pp_book)(hipStream_t, const Buffers &, const PpArgs &);
     void (*pp_resolve_dev)(hipStream_t, const int32_t *labels_dev, int n, int ncap, const PpArgs &, int16_t *obs_dev, float *wf_dev, uint8_t *any_dev);
     void (*update_particle_dev)(hipStream_t, const Buffers &, const PredictArgs &, const UpdateArgs &, const RngArgs &, const WeightScratch &,
@@ -724,8 +736,16 @@ struct KernelTable {
     // device-driven iteration the holders census or the estimate partials).  Device-driven: AssocListArgs::obs set.
     void (*lists_box)(hipStream_t, const Buffers &, const PpArgs &, int all, int blocks, LmkBox *box_dev);
     void (*lists_geom)(hipStream_t, const Buffers &, const AssocListArgs &, int stage);
-    void (*lists_build)(hipStream_t, const Buffers &, const AssocListArgs &);
-    void (*lists_walk)(hipStream_t, const Buffers &, const AssocListArgs &, const float *R4, float gate_reject, float gate_augment, int32_t *labels_dev);
+    // (rho_dev, may be null: as `associate`'s; the lists' reach for the rule follows it)
+    void (*lists_build)(hipStream_t, const Buffers &, const AssocListArgs &, const float *rho_dev);
+    void (*lists_walk)(hipStream_t, const Buffers &, const AssocListArgs &, const float *R4, float gate_reject, float gate_augment, int32_t *labels_dev,
+                       const float *rho_dev);
+    // the exclusion rule's radius per observation from the step's observation spacing (slamgpu_set_particle_excl_spacing):
+    // rho[q] = min(excl_base + excl_per_m r_q, f s_q), s_q the distance from (r_q cos b_q, r_q sin b_q) to the nearest other such point
+    // of the step (+inf for one observation); *rho_nz = nz.  obs null: z_dev / nz from the host; else nz and z from the iteration's
+    // observation (nz <= blocks * kBlock)
+    void (*excl_radii)(hipStream_t, const ObserveOut *obs, const float *z_dev, int nz, int blocks, float excl_base, float excl_per_m, float f,
+                       float *rho_dev, int32_t *rho_nz_dev);
 };
 
 const KernelTable *kernels_strict();

@@ -2665,6 +2665,43 @@ SLAM_DEV void pp_census_label(int lab, int j, const PpArgs &P) {
     if (nw && (threadIdx.x & (kWave - 1)) == (int) __ffsll((long long) __ballot(true)) - 1) atomicAdd(P.news + j, (int) __popcll(nw));
 }
 
+// The exclusion rule's radius capped by the step's own observation spacing (slamgpu_set_particle_excl_spacing, f > 0): observation q
+// implies the sensor-frame point p_q = r_q (cos b_q, sin b_q); s_q is the distance from p_q to the nearest other p_q' of the step (+inf
+// for one observation), and rho[q] = min(excl_base + excl_per_m r_q, f s_q).  Distances between those points do not depend on the pose,
+// so rho is one array per step, the same for every particle and every path (exhaustive scan, lists, host or device driven).  O(nz^2):
+// one thread per observation, the points staged through LDS a block at a time (32 767 observations, the host path's limit: 128 blocks).
+// DEV: nz and z from the iteration's observation (the grid covers the map, the most it can hold).  *rho_nz = nz (the diagnostic fetch).
+SLAM_DEV float2 excl_point(const float *__restrict__ z, int q) {
+    float sn, cs;
+    sincosf(z[2 * q + 1], &sn, &cs);
+    return make_float2(z[2 * q] * cs, z[2 * q] * sn);
+}
+template <bool DEV>
+__global__ void __launch_bounds__(kBlock) excl_radii_kernel(const ObserveOut *__restrict__ obs, const float *__restrict__ z, int nz, float excl_base,
+                                                             float excl_per_m, float f, float *__restrict__ rho, int32_t *__restrict__ rho_nz) {
+    if constexpr (DEV) {
+        nz = obs->nz;
+        z = reinterpret_cast<const float *>(obs + 1);
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) *rho_nz = nz;
+    if ((int) (blockIdx.x * kBlock) >= nz) return;  // (uniform over the block)
+    __shared__ float2 sh[kBlock];
+    const int q = blockIdx.x * kBlock + threadIdx.x;
+    const float2 p = q < nz ? excl_point(z, q) : make_float2(0.0f, 0.0f);
+    float m = INFINITY;  // squared distance to the nearest other point
+    for (int t0 = 0; t0 < nz; t0 += kBlock) {
+        __syncthreads();
+        if (t0 + (int) threadIdx.x < nz) sh[threadIdx.x] = excl_point(z, t0 + threadIdx.x);
+        __syncthreads();
+        const int cnt = min(kBlock, nz - t0);
+        for (int u = 0; u < cnt; u++) {
+            const float dx = sh[u].x - p.x, dy = sh[u].y - p.y, dd = dx * dx + dy * dy;
+            if (t0 + u != q) m = fminf(m, dd);
+        }
+    }
+    if (q < nz) rho[q] = fminf(excl_base + excl_per_m * z[2 * q], f * sqrtf(m));
+}
+
 // EXCL (slamgpu_particle_assoc::excl_*; slamgpu_associate never): the EXCLUSION rule of a particle's own map.  The gates measure an
 // observation against S = Hf Pf Hf^T + R -- for a converged landmark that is R, half a metre at five sigma -- and know nothing of the
 // particle's own pose error (the EKF's S carries it, ekfslam.cpp:160-176; a particle's pose is a point).  So a particle a metre off
@@ -2674,10 +2711,13 @@ SLAM_DEV void pp_census_label(int lab, int j, const PpArgs &P) {
 // (the update then pulls pose and landmark together, at the price of the innovation's likelihood), and discarded otherwise.
 // (DEV: slamgpu_run_particle -- nz, nf and the observations from device memory (PpArgs); the census of the labels and, when it is due,
 // of the holders rides in this launch; an iteration without observations takes the estimate partials instead)
-template <bool EXCL, bool DEV = false>
+// (RHO, with EXCL: the rule's radius is P.rho[q], excl_radii_kernel's, instead of excl_base + excl_per_m * range)
+template <bool EXCL, bool DEV = false, bool RHO = false>
 __global__ void __launch_bounds__(kBlock) associate_kernel(Buffers B, int nf, const float *__restrict__ z, int nz, float r00, float r01,
                                                             float r10, float r11, float gate1, float gate2, float excl_base, float excl_per_m, float unique_ratio,
-                                                            const uint32_t *__restrict__ retired, int32_t *__restrict__ labels, int by_obs, PpArgs P) {
+                                                            const uint32_t *__restrict__ retired, int32_t *__restrict__ labels, int by_obs,
+                                                            std::conditional_t<RHO, PpRhoArgs, PpArgs> P) {
+    static_assert(EXCL || !RHO, "the radii are the exclusion rule's");
     if constexpr (DEV) {
         nz = P.obs->nz;
         if (nz == 0) {
@@ -2769,7 +2809,9 @@ __global__ void __launch_bounds__(kBlock) associate_kernel(Buffers B, int nf, co
             if (q0 + q < nz) {
                 int label = jbest[q] > -1 ? jbest[q] : (outer[q] > gate2 ? kAssocNew : kAssocDiscard);
                 if constexpr (EXCL) {
-                    const float rho = excl_base + excl_per_m * z[2 * (q0 + q)];
+                    float rho;
+                    if constexpr (RHO) rho = P.rho[q0 + q];
+                    else rho = excl_base + excl_per_m * z[2 * (q0 + q)];
                     if (jbest[q] < 0 && d1[q] < rho * rho) label = d2[q] > unique_ratio * unique_ratio * d1[q] ? j1[q] : kAssocDiscard;
                 }
                 labels[by_obs ? (size_t) (q0 + q) * S + i : (size_t) i * nz + q0 + q] = label;  // (by_obs: [nz][ncap], what the per-particle update reads)
@@ -3076,11 +3118,13 @@ SLAM_DEV void arc_range(float a0, float a1, bool cosine, float &lo, float &hi) {
 // alone); retired slots are skipped here; with the exclusion rule on, the list also keeps every slot whose box lies within
 // max(1, unique_ratio) x the rule's radius of the points the observation implies -- a slot farther away can neither be the nearest one
 // inside the radius nor decide the uniqueness test (associate_kernel<EXCL>: d2 > unique_ratio^2 d1), so the rule's decision is exact;
-// the counts go to lstats.  DEV: nz, z and nf from device memory, the grid is the host's bound on nz.
-template <bool PEROBS = false, bool DEV = false>
-__global__ void __launch_bounds__(kBlock) assoc_lists_kernel(std::conditional_t<PEROBS, AssocListArgs, AssocGridArgs> A, const int32_t *__restrict__ erow,
-                                                              const int32_t *__restrict__ live) {
+// the counts go to lstats.  DEV: nz, z and nf from device memory, the grid is the host's bound on nz.  RHO: the rule's radius is A.rho[q]
+// (excl_radii_kernel) -- a shorter reach, a shorter list.
+template <bool PEROBS = false, bool DEV = false, bool RHO = false>
+__global__ void __launch_bounds__(kBlock) assoc_lists_kernel(std::conditional_t<PEROBS, std::conditional_t<RHO, AssocRhoArgs, AssocListArgs>, AssocGridArgs> A,
+                                                              const int32_t *__restrict__ erow, const int32_t *__restrict__ live) {
     static_assert(PEROBS || !DEV, "device-driven lists are per observation");
+    static_assert(PEROBS || !RHO, "the radii are the exclusion rule's, per observation");
     __shared__ int32_t sh_n;
     const int q = blockIdx.x;
     if constexpr (DEV) {
@@ -3107,7 +3151,10 @@ __global__ void __launch_bounds__(kBlock) assoc_lists_kernel(std::conditional_t<
     const float qy0 = g.py0 + fminf(zr * sl, zr * shh) - slack, qy1 = g.py1 + fmaxf(zr * sl, zr * shh) + slack;
     [[maybe_unused]] float rx = -1.0f;  // (PEROBS: the exclusion rule's reach, < 0: off)
     if constexpr (PEROBS)
-        if (A.excl_base + A.excl_per_m > 0.0f) rx = fmaxf(1.0f, A.excl_ratio) * (A.excl_base + A.excl_per_m * zr) * 1.01f + 1e-3f;
+        if (A.excl_base + A.excl_per_m > 0.0f) {
+            if constexpr (RHO) rx = fmaxf(1.0f, A.excl_ratio) * A.rho[q] * 1.01f + 1e-3f;
+            else rx = fmaxf(1.0f, A.excl_ratio) * (A.excl_base + A.excl_per_m * zr) * 1.01f + 1e-3f;
+        }
     for (int j = threadIdx.x; j < A.nf; j += kBlock) {
         if constexpr (PEROBS)
             if (A.retired && ((A.retired[j >> 5] >> (j & 31)) & 1u)) continue;
@@ -3215,10 +3262,12 @@ SLAM_DEV int walk_q_hi(const Args &A, int q_lo) {
         return min(A.nz, q_lo + A.obs_per_block);
     }
 }
-template <bool LISTS, bool PEROBS = false, bool EXCL = false, bool DEV = false>
-__global__ void __launch_bounds__(kBlock) associate_grid_kernel(Buffers B, std::conditional_t<PEROBS, AssocListArgs, AssocGridArgs> A, float r00, float r01,
-                                                                 float r10, float r11, float gate1, float gate2, int32_t *__restrict__ labels) {
+// RHO (with EXCL): the rule's radius is A.rho[q] (excl_radii_kernel), the reach assoc_lists_kernel<.., RHO> kept the list for
+template <bool LISTS, bool PEROBS = false, bool EXCL = false, bool DEV = false, bool RHO = false>
+__global__ void __launch_bounds__(kBlock) associate_grid_kernel(Buffers B, std::conditional_t<PEROBS, std::conditional_t<RHO, AssocRhoArgs, AssocListArgs>, AssocGridArgs> A,
+                                                                 float r00, float r01, float r10, float r11, float gate1, float gate2, int32_t *__restrict__ labels) {
     static_assert((LISTS || !PEROBS) && (PEROBS || !(EXCL || DEV)), "the exclusion rule and the device-driven walk are the lists' per observation");
+    static_assert(EXCL || !RHO, "the radii are the exclusion rule's");
     const int i = blockIdx.x * kBlock + threadIdx.x;
     if constexpr (DEV) {
         const int nz = A.obs->nz;  // (the true count; A.nz is the lists grid)
@@ -3400,7 +3449,9 @@ __global__ void __launch_bounds__(kBlock) associate_grid_kernel(Buffers B, std::
                     }
                 }
                 if constexpr (EXCL) {
-                    const float rho = A.excl_base + A.excl_per_m * zr;
+                    float rho;
+                    if constexpr (RHO) rho = A.rho[q];
+                    else rho = A.excl_base + A.excl_per_m * zr;
                     if (jbest < 0 && !every) {
                         // the list's entries in no particular order: the lower slot wins a tie for the nearest, and the second distance
                         // counts ties (the same two numbers as the ordered scan).  An entry whose box lies beyond max(1, ratio) x the
@@ -4152,8 +4203,11 @@ static void launch_observe_book(hipStream_t st, const ObserveArgs &A) {
 }
 
 static void launch_associate(hipStream_t st, const Buffers &B, int nf, const float *z, int nz, const float *R4, float g1, float g2, const float *excl3,
-                             const uint32_t *retired, int32_t *labels, int by_obs) {
-    if (excl3 && excl3[0] + excl3[1] > 0.0f)
+                             const uint32_t *retired, int32_t *labels, int by_obs, const float *rho) {
+    if (excl3 && excl3[0] + excl3[1] > 0.0f && rho)
+        hipLaunchKernelGGL((associate_kernel<true, false, true>), dim3(B.ncap / kBlock), dim3(kBlock), 0, st, B, nf, z, nz, R4[0], R4[1], R4[2], R4[3], g1, g2,
+                           excl3[0], excl3[1], excl3[2], retired, labels, by_obs, PpRhoArgs{PpArgs{}, rho});
+    else if (excl3 && excl3[0] + excl3[1] > 0.0f)
         hipLaunchKernelGGL((associate_kernel<true, false>), dim3(B.ncap / kBlock), dim3(kBlock), 0, st, B, nf, z, nz, R4[0], R4[1], R4[2], R4[3], g1, g2, excl3[0],
                            excl3[1], excl3[2], retired, labels, by_obs, PpArgs{});
     else
@@ -4457,8 +4511,12 @@ static void launch_pp_gather(hipStream_t st, const Buffers &B, const WeightScrat
     const int gy = (P.cap_rows + kRowsPerRole - 1) / kRowsPerRole;  // (rows in use: at most cap_rows; the groups past the count leave at once)
     hipLaunchKernelGGL(pp_gather_kernel, dim3(ws.nblocks + 1, gy), dim3(kBlock), 0, st, B, ws, P, hist, par);
 }
-static void launch_pp_associate(hipStream_t st, const Buffers &B, const float *R4, float g1, float g2, const float *excl3, int32_t *labels, const PpArgs &P) {
-    if (excl3 && excl3[0] + excl3[1] > 0.0f)
+static void launch_pp_associate(hipStream_t st, const Buffers &B, const float *R4, float g1, float g2, const float *excl3, int32_t *labels, const PpArgs &P,
+                                const float *rho) {
+    if (excl3 && excl3[0] + excl3[1] > 0.0f && rho)
+        hipLaunchKernelGGL((associate_kernel<true, true, true>), dim3(B.ncap / kBlock), dim3(kBlock), 0, st, B, 0, (const float *) nullptr, 0, R4[0], R4[1], R4[2], R4[3],
+                           g1, g2, excl3[0], excl3[1], excl3[2], (const uint32_t *) P.retired, labels, 1, PpRhoArgs{P, rho});
+    else if (excl3 && excl3[0] + excl3[1] > 0.0f)
         hipLaunchKernelGGL((associate_kernel<true, true>), dim3(B.ncap / kBlock), dim3(kBlock), 0, st, B, 0, (const float *) nullptr, 0, R4[0], R4[1], R4[2], R4[3], g1,
                            g2, excl3[0], excl3[1], excl3[2], (const uint32_t *) P.retired, labels, 1, P);
     else
@@ -4482,14 +4540,25 @@ static void launch_lists_geom(hipStream_t st, const Buffers &B, const AssocListA
     else if (A.obs) hipLaunchKernelGGL(assoc_geom_kernel<true>, dim3(1), dim3(kBlock), 0, st, B, A, A.geom_part);
     else hipLaunchKernelGGL(assoc_geom_kernel<false>, dim3(1), dim3(kBlock), 0, st, B, (const AssocGridArgs &) A, A.geom_part);
 }
-static void launch_lists_build(hipStream_t st, const Buffers &B, const AssocListArgs &A) {
-    if (A.obs) hipLaunchKernelGGL((assoc_lists_kernel<true, true>), dim3(A.nz), dim3(kBlock), 0, st, A, B.erow, B.lmk_live);
+static void launch_lists_build(hipStream_t st, const Buffers &B, const AssocListArgs &A, const float *rho) {
+    const bool excl = A.excl_base + A.excl_per_m > 0.0f;
+    if (excl && rho && A.obs)
+        hipLaunchKernelGGL((assoc_lists_kernel<true, true, true>), dim3(A.nz), dim3(kBlock), 0, st, AssocRhoArgs{A, rho}, B.erow, B.lmk_live);
+    else if (excl && rho)
+        hipLaunchKernelGGL((assoc_lists_kernel<true, false, true>), dim3(A.nz), dim3(kBlock), 0, st, AssocRhoArgs{A, rho}, B.erow, B.lmk_live);
+    else if (A.obs) hipLaunchKernelGGL((assoc_lists_kernel<true, true>), dim3(A.nz), dim3(kBlock), 0, st, A, B.erow, B.lmk_live);
     else hipLaunchKernelGGL((assoc_lists_kernel<true, false>), dim3(A.nz), dim3(kBlock), 0, st, A, B.erow, B.lmk_live);
 }
-static void launch_lists_walk(hipStream_t st, const Buffers &B, const AssocListArgs &A, const float *R4, float g1, float g2, int32_t *labels) {
+static void launch_lists_walk(hipStream_t st, const Buffers &B, const AssocListArgs &A, const float *R4, float g1, float g2, int32_t *labels, const float *rho) {
     const dim3 grid(B.ncap / kBlock, (A.nz + A.obs_per_block - 1) / A.obs_per_block);
     const bool excl = A.excl_base + A.excl_per_m > 0.0f;
-    if (A.obs && excl)
+    if (excl && rho && A.obs)
+        hipLaunchKernelGGL((associate_grid_kernel<true, true, true, true, true>), grid, dim3(kBlock), 0, st, B, AssocRhoArgs{A, rho}, R4[0], R4[1], R4[2], R4[3], g1, g2,
+                           labels);
+    else if (excl && rho)
+        hipLaunchKernelGGL((associate_grid_kernel<true, true, true, false, true>), grid, dim3(kBlock), 0, st, B, AssocRhoArgs{A, rho}, R4[0], R4[1], R4[2], R4[3], g1, g2,
+                           labels);
+    else if (A.obs && excl)
         hipLaunchKernelGGL((associate_grid_kernel<true, true, true, true>), grid, dim3(kBlock), 0, st, B, A, R4[0], R4[1], R4[2], R4[3], g1, g2, labels);
     else if (A.obs)
         hipLaunchKernelGGL((associate_grid_kernel<true, true, false, true>), grid, dim3(kBlock), 0, st, B, A, R4[0], R4[1], R4[2], R4[3], g1, g2, labels);
@@ -4498,12 +4567,19 @@ static void launch_lists_walk(hipStream_t st, const Buffers &B, const AssocListA
     else
         hipLaunchKernelGGL((associate_grid_kernel<true, true, false, false>), grid, dim3(kBlock), 0, st, B, A, R4[0], R4[1], R4[2], R4[3], g1, g2, labels);
 }
+static void launch_excl_radii(hipStream_t st, const ObserveOut *obs, const float *z, int nz, int blocks, float excl_base, float excl_per_m, float f,
+                              float *rho, int32_t *rho_nz) {
+    if (obs)
+        hipLaunchKernelGGL(excl_radii_kernel<true>, dim3(blocks), dim3(kBlock), 0, st, obs, (const float *) nullptr, 0, excl_base, excl_per_m, f, rho, rho_nz);
+    else
+        hipLaunchKernelGGL(excl_radii_kernel<false>, dim3(blocks), dim3(kBlock), 0, st, (const ObserveOut *) nullptr, z, nz, excl_base, excl_per_m, f, rho, rho_nz);
+}
 
 static const KernelTable kTable = {launch_update, launch_update_particle, launch_update_persist, launch_resample, launch_resample_ref, launch_scan, launch_gather, launch_flatten, launch_identity, launch_decompact, launch_finish, launch_predict, launch_estimate, launch_jacobians, launch_kat, launch_observe, launch_observe_book, launch_associate,
                                    launch_shard_plan, launch_shard_pack, launch_shard_unpack, launch_shard_finish, launch_dist_gather, launch_dist_flags, launch_peek, launch_lmk_box, launch_assoc_grid, launch_assoc_lists, launch_vote_compact,
                                    launch_associate_grid, launch_jacobians_multi, launch_pp_census, launch_pp_resolve, launch_pp_holders,
                                    launch_pp_resample, launch_pp_gather, launch_pp_associate, launch_pp_book, launch_pp_resolve_dev, launch_update_particle_dev,
-                                   launch_lists_box, launch_lists_geom, launch_lists_build, launch_lists_walk};
+                                   launch_lists_box, launch_lists_geom, launch_lists_build, launch_lists_walk, launch_excl_radii};
 
 }  // namespace SLAM_KNS
 

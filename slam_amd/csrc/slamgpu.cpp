@@ -304,6 +304,11 @@ struct slamgpu_ctx {
     // slamgpu_particle_report_fetch) and whether device-driven iterations have written slots without refreshing their boxes
     unsigned long long *lstats_dev = nullptr;
     bool box_dev_stale = false;
+    // the exclusion rule's radius capped by the step's observation spacing (slamgpu_set_particle_excl_spacing; 0: off) and the radii of
+    // the last step that made them: excl_rho_dev[0] holds their count (int32), the radii follow from [4] (excl_rho_cap of them)
+    float excl_spacing = 0.0f;
+    int32_t *excl_rho_dev = nullptr;
+    int excl_rho_cap = 0;
     int pp_report_n = 0;
     bool pp_stage_open = false;       // the previous iteration may have left a resampling stage (the device knows) and no gather has run since
     double *pp_prev_hist = nullptr;   // ... its history slot and the parity of its weight scratch
@@ -994,7 +999,7 @@ void slamgpu_destroy(slamgpu_ctx *c) {
     if (c->pp_tab_dev) (void) hipFree(c->pp_tab_dev);
     if (c->pp_wf_dev) (void) hipFree(c->pp_wf_dev);
     if (c->pp_any_dev) (void) hipFree(c->pp_any_dev);
-    for (void *p_ : {(void *) c->pp_st_dev, (void *) c->pp_words_dev, (void *) c->pp_pkt_dev, (void *) c->pp_report_dev, (void *) c->lstats_dev})
+    for (void *p_ : {(void *) c->pp_st_dev, (void *) c->pp_words_dev, (void *) c->pp_pkt_dev, (void *) c->pp_report_dev, (void *) c->lstats_dev, (void *) c->excl_rho_dev})
         if (p_) (void) hipFree(p_);
     for (void *p_ : {(void *) c->box_dev, (void *) c->assoc_ids_dev, (void *) c->cell_start_dev, (void *) c->cell_fill_dev, (void *) c->items_dev,
                      (void *) c->geom_dev})
@@ -2852,6 +2857,31 @@ void assoc_resolve(int nz, std::vector<int32_t> &best, const std::vector<double>
 }  // namespace
 
 namespace {
+// the exclusion rule's radii from the step's observation spacing (slamgpu_set_particle_excl_spacing): on when the factor and the rule are
+bool excl_spacing_on(const slamgpu_ctx *c, const slamgpu_particle_assoc *opt) {
+    return c->excl_spacing > 0.0f && opt->excl_base + opt->excl_per_m > 0.0f;
+}
+// room for the radii of `cap` observations (and their count ahead of them)
+int excl_rho_reserve(slamgpu_ctx *c, int cap) {
+    if (cap <= c->excl_rho_cap) return 0;
+    const int want = std::max(cap, 64);
+    if (c->excl_rho_dev) (void) hipFree(c->excl_rho_dev);
+    c->excl_rho_dev = nullptr;
+    c->excl_rho_cap = 0;
+    HIP_TRY(hipMalloc((void **) &c->excl_rho_dev, sizeof(int32_t) * (4 + (size_t) want)));
+    HIP_TRY(hipMemset(c->excl_rho_dev, 0, sizeof(int32_t) * 4));
+    c->excl_rho_cap = want;
+    return 0;
+}
+// one launch: the radii of this step into the context's buffer, with the factor as it stands now (obs: the device-driven iteration's
+// observation, nz <= blocks * kBlock); returns them (device)
+const float *excl_radii(slamgpu_ctx *c, const ObserveOut *obs, const float *z_dev, int nz, int blocks, const float *excl3) {
+    float *rho = reinterpret_cast<float *>(c->excl_rho_dev + 4);
+    Timed t(c, "excl_radii");
+    c->k->excl_radii(c->stream, obs, z_dev, nz, blocks, excl3[0], excl3[1], c->excl_spacing, rho, c->excl_rho_dev);
+    return rho;
+}
+
 // the boxes, grid / list and geometry buffers of the prefilter
 int grid_buffers(slamgpu_ctx *c) {
     if (c->box_dev) return 0;
@@ -2872,7 +2902,8 @@ int grid_buffers(slamgpu_ctx *c) {
 
 // lab_ext: a device array the labels are left in BY OBSERVATION, [nz][ncap] (slamgpu_update_particle: they never visit the host), or null
 int associate_impl(slamgpu_ctx *c, const float *z, int32_t nz, const float R[4], float gate_reject, float gate_augment, int32_t mode,
-                   int32_t *labels, int32_t *consensus, float *support, double stats[4], int32_t *lab_ext, const float *excl3 = nullptr) {
+                   int32_t *labels, int32_t *consensus, float *support, double stats[4], int32_t *lab_ext, const float *excl3 = nullptr,
+                   bool spacing = false) {
     if (int rc = check_ctx(c)) return rc;
     if (mode < SLAMGPU_ASSOC_AUTO || mode > SLAMGPU_ASSOC_GRID) return fail(SLAMGPU_ERR_INVALID, "unknown association mode %d", mode);
     if (stats) stats[0] = stats[1] = stats[2] = stats[3] = 0.0;
@@ -3077,10 +3108,11 @@ int associate_impl(slamgpu_ctx *c, const float *z, int32_t nz, const float R[4],
     if (!rc && !grid) {
         need_labels();
         if (!rc) {
+            const float *rho = spacing ? excl_radii(c, nullptr, z_dev, nz, (nz + kBlock - 1) / kBlock, excl3) : nullptr;
             if (ev0) step(hipEventRecord(ev0, c->stream), "event");
             {
                 Timed t(c, "associate");
-                c->k->associate(c->stream, c->B, c->nf, z_dev, nz, R, gate_reject, gate_augment, excl3, c->retired_dev, lab_dev, lab_ext ? 1 : 0);
+                c->k->associate(c->stream, c->B, c->nf, z_dev, nz, R, gate_reject, gate_augment, excl3, c->retired_dev, lab_dev, lab_ext ? 1 : 0, rho);
             }
             if (ev1) step(hipEventRecord(ev1, c->stream), "event");
             if (stats) stats[0] = (double) N * (double) nz * (double) c->nf;
@@ -3542,13 +3574,15 @@ int associate_lists(slamgpu_ctx *c, const float *z, int32_t nz, const float R[4]
     G.census_news = c->pp_tab_dev + 2 * (size_t) cap_nf;
     HIP_TRY(hipMemsetD32Async((hipDeviceptr_t) G.census_first, 0x7fffffff, (size_t) cap_nf, c->stream));
     HIP_TRY(hipMemsetAsync(G.census_news, 0, sizeof(int32_t) * (size_t) nz, c->stream));
+    const float excl3[3] = {opt->excl_base, opt->excl_per_m, opt->unique_ratio};
+    const float *rho = excl_spacing_on(c, opt) ? excl_radii(c, nullptr, c->pp_z_dev, nz, (nz + kBlock - 1) / kBlock, excl3) : nullptr;
     {
         Timed t(c, "associate");
         if (!ids.empty()) c->k->lmk_box(c->stream, c->B, c->assoc_ids_dev, (int) ids.size(), c->retired_dev, c->box_dev);
         c->k->lists_geom(c->stream, c->B, G, 0);
         c->k->lists_geom(c->stream, c->B, G, 1);
-        c->k->lists_build(c->stream, c->B, G);
-        c->k->lists_walk(c->stream, c->B, G, R, opt->gate_reject, opt->gate_augment, c->pp_lab_dev);
+        c->k->lists_build(c->stream, c->B, G, rho);
+        c->k->lists_walk(c->stream, c->B, G, R, opt->gate_reject, opt->gate_augment, c->pp_lab_dev, rho);
     }
     HIP_TRY(hipGetLastError());
     for (int j : ids) c->box_dirty[(size_t) j] = 0;
@@ -3582,13 +3616,18 @@ int slamgpu_update_particle(slamgpu_ctx *c, const float *z, int32_t nz, const fl
     if (nz == 0) return 0;  // (no observation, no update: fastslam2wrapper.cpp:84-95)
     HIP_TRY(hipSetDevice(c->cfg.device));
     if (int rc = pp_reserve(c, nz, 1)) return rc;
+    const bool spacing = excl_spacing_on(c, opt);
+    if (spacing)
+        if (int rc = excl_rho_reserve(c, nz)) return rc;
     if (opt->mode == SLAMGPU_ASSOC_LISTS) {
         if (int rc = book_pull(c)) return rc;  // (the device-driven state back first: the boxes and the mask are the host's again)
         if (int rc = associate_lists(c, z, nz, R, opt)) return rc;
         return do_update_particle(c, z, nz, R, opt, normals, strata, report);
     }
     const float excl3[3] = {opt->excl_base, opt->excl_per_m, opt->unique_ratio};
-    if (int rc = associate_impl(c, z, nz, R, opt->gate_reject, opt->gate_augment, opt->mode, nullptr, nullptr, nullptr, nullptr, c->pp_lab_dev, excl3)) return rc;
+    if (int rc = associate_impl(c, z, nz, R, opt->gate_reject, opt->gate_augment, opt->mode, nullptr, nullptr, nullptr, nullptr, c->pp_lab_dev, excl3,
+                                spacing))
+        return rc;
     return do_update_particle(c, z, nz, R, opt, normals, strata, report);
 }
 
@@ -3877,6 +3916,9 @@ int pp_dev_iteration(slamgpu_ctx *c, int32_t nc, const float *controls, const fl
     P.need = need;
     P.p_new = opt->p_new;
     c->B.slot = c->slot;
+    const float excl3[3] = {opt->excl_base, opt->excl_per_m, opt->unique_ratio};
+    // (the radii: every observation the map allows, whatever the lists grid; the count comes from the observation)
+    const float *rho = excl_spacing_on(c, opt) ? excl_radii(c, c->obs_out_dev, nullptr, 0, (c->map_n + kBlock - 1) / kBlock, excl3) : nullptr;
     if (bound >= 0) {
         // the boxes of the slots the previous iteration wrote, the geometry, one list per observation, the walk (+ the census)
         AssocListArgs G;
@@ -3901,16 +3943,15 @@ int pp_dev_iteration(slamgpu_ctx *c, int32_t nc, const float *controls, const fl
         }
         {
             Timed t(c, "assoc_lists");
-            c->k->lists_build(c->stream, c->B, G);
+            c->k->lists_build(c->stream, c->B, G, rho);
         }
         {
             Timed t(c, "associate");
-            c->k->lists_walk(c->stream, c->B, G, R, opt->gate_reject, opt->gate_augment, c->pp_lab_dev);
+            c->k->lists_walk(c->stream, c->B, G, R, opt->gate_reject, opt->gate_augment, c->pp_lab_dev, rho);
         }
     } else {
-        const float excl3[3] = {opt->excl_base, opt->excl_per_m, opt->unique_ratio};
         Timed t(c, "associate");
-        c->k->pp_associate(c->stream, c->B, R, opt->gate_reject, opt->gate_augment, excl3, c->pp_lab_dev, P);
+        c->k->pp_associate(c->stream, c->B, R, opt->gate_reject, opt->gate_augment, excl3, c->pp_lab_dev, P, rho);
     }
     {
         Timed t(c, "particle_book");
@@ -4002,6 +4043,8 @@ int slamgpu_run_particle(slamgpu_ctx *c, int32_t K, const int32_t *n_controls, c
     if (int rc = pp_setup(c)) return rc;
     if (lists)
         if (int rc = lists_buffers(c)) return rc;
+    if (excl_spacing_on(c, opt))
+        if (int rc = excl_rho_reserve(c, c->map_n)) return rc;
     const bool was_host = !c->pp_on_device;
     if (int rc = pp_push(c, c->pp_nz_cap)) return rc;
     bool box_all = false;
@@ -4066,6 +4109,28 @@ int slamgpu_particle_report_fetch(slamgpu_ctx *c, int32_t *report, int32_t max_c
         HIP_TRY(hipMemcpy(c->pp_report_dev, h.data() + 8 * (size_t) n, sizeof(int32_t) * 8 * (size_t) left, hipMemcpyHostToDevice));
     c->pp_report_n = left;
     *count = n;
+    return 0;
+}
+
+int slamgpu_set_particle_excl_spacing(slamgpu_ctx *c, float f) {
+    if (int rc = check_ctx(c)) return rc;
+    if (!(f >= 0.0f) || !std::isfinite(f)) return fail(SLAMGPU_ERR_INVALID, "slamgpu_set_particle_excl_spacing: the factor must be finite and >= 0");
+    c->excl_spacing = f;  // (launches already enqueued carry the factor they were made with)
+    return 0;
+}
+
+int slamgpu_particle_excl_radii(slamgpu_ctx *c, float *rho, int32_t max_count, int32_t *nz) {
+    if (int rc = check_ctx(c)) return rc;
+    if (!nz || (max_count > 0 && !rho)) return fail(SLAMGPU_ERR_INVALID, "slamgpu_particle_excl_radii: null output");
+    *nz = 0;
+    if (!c->excl_rho_dev) return 0;
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    int32_t n = 0;
+    HIP_TRY(hipMemcpy(&n, c->excl_rho_dev, sizeof n, hipMemcpyDeviceToHost));
+    const int32_t k = std::min(n, std::max(max_count, 0));
+    if (k > 0) HIP_TRY(hipMemcpy(rho, c->excl_rho_dev + 4, sizeof(float) * (size_t) k, hipMemcpyDeviceToHost));
+    *nz = n;
     return 0;
 }
 

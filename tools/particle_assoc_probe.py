@@ -6,6 +6,7 @@ its entries lie further than 1 m from every true landmark, slots in use / dead a
 in one step, mean position error of the estimate, mean error of the known-association twin, milliseconds per observation step.
 A run is GOOD when the best particle's map has at most --max-landmarks entries and the mean position error is under 1 m.
 usage: tools/particle_assoc_probe.py [--seeds 7-16] [--particles 512,2048] [--map example_webmap] [--new-share 0.02] [--p-new auto]
+                                     [--excl-spacing f]
 GPU box, one process."""
 import argparse
 import os
@@ -34,6 +35,9 @@ def run(sg, host, mapname, N, seed, math, a, known):
     s = sg.SlamGpu(N, cap, method=2 if a.method == "FASTSLAM2" else 1, n_effective=int(0.75 * N), rng_mode=sg.RNG_PHILOX, seed=seed, math_mode=math,
                    particle_maps=not known, use_heading=bool(tape["conf"].SWITCH_HEADING_KNOWN), wheel_base=float(tape["conf"].WHEELBASE),
                    sigma_phi=float(tape["conf"].sigmaT))
+    spacing = getattr(a, "excl_spacing", 0.0)  # (callers that build their own namespace, tests/test_gpu_particle_assoc.py, predate it)
+    if not known and spacing > 0:
+        s.set_particle_excl_spacing(spacing)
     errs, most, dropped = [], 0, 0
     t0 = time.perf_counter()
     for st in tape["steps"]:
@@ -81,6 +85,7 @@ def main():
     ap.add_argument("--excl-base", type=float, default=2.0)
     ap.add_argument("--excl-per-m", type=float, default=0.05)
     ap.add_argument("--unique-ratio", type=float, default=2.0)
+    ap.add_argument("--excl-spacing", type=float, default=0.0, help="cap the rule's radius at f x the observation spacing (0: the fixed radius)")
     ap.add_argument("--slots", type=int, default=4, help="slot capacity as a multiple of the map's landmarks")
     ap.add_argument("--max-landmarks", type=int, default=45)
     ap.add_argument("--tag", default="")
