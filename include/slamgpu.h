@@ -391,6 +391,29 @@ int slamgpu_set_particle_excl_spacing(slamgpu_ctx *ctx, float f);
  * an iteration without observations makes none: *nz = 0), at most max_count of them; *nz: how many the step had (0: none yet).
  * Synchronises. */
 int slamgpu_particle_excl_radii(slamgpu_ctx *ctx, float *rho, int32_t max_count, int32_t *nz);
+/* Data association sampling (Montemerlo & Thrun, ICRA 2003; Nieto et al., ICRA 2003) for both per-particle entry points, in every mode
+ * that reaches the exhaustive scan or the lists (slamgpu_update_particle with SLAMGPU_ASSOC_GRID is refused while it is on; _AUTO takes
+ * the exhaustive scan).  For particle i and observation q let C be the slots the particle holds, retired ones excluded, with
+ * nis < gate_reject (nis and nd = nis + ln det S as the gates compute them).  |C| = 0: unchanged (new or discard by the gates, the
+ * exclusion rule, the spacing cap).  |C| = 1: unchanged, that slot.  |C| >= 2: the label is argmax_{j in C} (-nd_j / 2 + g_j), ties to the
+ * lower slot, g_j = -ln(-ln u_j) and u_j from Philox (key = seed) at counter (first_particle + i, the update's observation step, 4 + 8 q,
+ * j): a draw with P(j) proportional to exp(-nd_j / 2), gaussEvaluate's likelihood up to 2 pi, that does not depend on the order the
+ * candidates are visited in.  When the claim is fresh (the first on its slot), the particle's weight factor is multiplied by
+ * rho = sum_{k in C} exp(-nd_k / 2) / exp(-nd_label / 2) (log-weights: ln rho is added); the terms are summed in fixed point, so rho is
+ * the same on every path and exactly 1 when |C| = 1.  FastSLAM 1's weight becomes the marginal likelihood sum_k L_k, the importance
+ * weight of the sampled association; for FastSLAM 2 it is an approximation, since its update weighs with the proposal's S.  A second
+ * claim on a slot still costs p_new.  "New" is never sampled (the gates decide existence); slamgpu_associate(_ex), the vote and
+ * slamgpu_update_labels are untouched.  on in {0, 1} (0, the default: nearest neighbour by nd); applies to calls made after it
+ * (iterations of slamgpu_run_particle already enqueued keep their setting).  SLAMGPU_ERR_INVALID for any other value, for a context
+ * without SLAMGPU_FLAG_PARTICLE_MAPS, and for SLAMGPU_RNG_TAPE contexts (the reference's tape has no such draws). */
+int slamgpu_set_particle_assoc_sampling(slamgpu_ctx *ctx, int32_t on);
+/* Cumulative counters of the sampling: [0] steps associated with it on, [1] (particle, observation) pairs with |C| >= 2, [2] pairs whose
+ * sampled label is not the nearest one.  Synchronises. */
+int slamgpu_particle_sample_stats(slamgpu_ctx *ctx, int64_t out[3]);
+/* The last per-particle step's labels as its update consumed them, particle-major [N][nz]: slot, SLAMGPU_ASSOC_NEW or _DISCARD (at most
+ * max_count of them); *nz: the step's observations (0: none yet; an iteration of slamgpu_run_particle without observations leaves 0).
+ * With sampling on or off.  Synchronises. */
+int slamgpu_particle_labels(slamgpu_ctx *ctx, int32_t *labels, int64_t max_count, int32_t *nz);
 
 /* Retire landmarks from the gated association (round 6): landmarks ids[0 .. count) take no part in slamgpu_associate /
  * _associate_ex from now on -- no particle gates an observation against them, nothing votes for them -- and, never being

@@ -28,6 +28,7 @@ DECLARED_SYMBOLS = [
     "slamgpu_peek", "slamgpu_step_observe", "slamgpu_run_observe", "slamgpu_observe_fetch", "slamgpu_associate_ex", "slamgpu_update_particle", "slamgpu_update_labels", "slamgpu_dist_comm_info", "slamgpu_dist_remote_reads",
     "slamgpu_run_particle", "slamgpu_particle_report_fetch", "slamgpu_particle_list_stats",
     "slamgpu_set_particle_excl_spacing", "slamgpu_particle_excl_radii",
+    "slamgpu_set_particle_assoc_sampling", "slamgpu_particle_sample_stats", "slamgpu_particle_labels",
 ]
 ASSOC_AUTO, ASSOC_EXHAUSTIVE, ASSOC_GRID, ASSOC_LISTS = 0, 1, 2, 3
 FLAG_DEVICE_OBSERVE = 1
@@ -124,6 +125,10 @@ def load_library():
     if hasattr(L, "slamgpu_set_particle_excl_spacing"):
         L.slamgpu_set_particle_excl_spacing.argtypes = [C.c_void_p, C.c_float]
         L.slamgpu_particle_excl_radii.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]
+    if hasattr(L, "slamgpu_set_particle_assoc_sampling"):
+        L.slamgpu_set_particle_assoc_sampling.argtypes = [C.c_void_p, C.c_int32]
+        L.slamgpu_particle_sample_stats.argtypes = [C.c_void_p, C.c_void_p]
+        L.slamgpu_particle_labels.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int32)]
     L.slamgpu_genealogy_rows.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     L.slamgpu_persist_info.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
     if hasattr(L, "slamgpu_persist_status"):  # (an older build loaded through SLAMGPU_LIB for an A/B lacks the round-6 entries)
@@ -817,6 +822,26 @@ class SlamGpu:
         n = C.c_int32()
         _chk(self.L.slamgpu_particle_excl_radii(self.h, _ptr(out), int(max_count), C.byref(n)))
         return out[:min(n.value, out.size)].copy()
+
+    def set_particle_assoc_sampling(self, on):
+        """data association sampling for update_particle / run_particle calls made after it (slamgpu_set_particle_assoc_sampling): an
+        ambiguous observation's label drawn in proportion to its likelihood, the weight the marginal likelihood; False: nearest neighbour"""
+        _chk(self.L.slamgpu_set_particle_assoc_sampling(self.h, int(on)))
+
+    def particle_sample_stats(self):
+        """sampling counters since the context was created (slamgpu_particle_sample_stats): dict(steps, ambiguous, moved)"""
+        out = np.zeros(3, np.int64)
+        _chk(self.L.slamgpu_particle_sample_stats(self.h, _ptr(out)))
+        return dict(zip(("steps", "ambiguous", "moved"), (int(v) for v in out)))
+
+    def particle_labels(self):
+        """the last per-particle step's labels as its update consumed them (slamgpu_particle_labels): int32 [N, nz]"""
+        n = C.c_int32()
+        _chk(self.L.slamgpu_particle_labels(self.h, None, 0, C.byref(n)))
+        out = np.zeros((self.N, max(n.value, 0)), np.int32)
+        if out.size:
+            _chk(self.L.slamgpu_particle_labels(self.h, _ptr(out), out.size, C.byref(n)))
+        return out
 
     def update_labels(self, z, R, labels, new_share=0.0, p_new=1.0, census_every=1, normals=None, strata=None):
         """the same step with the caller's labels [N, nz] (slamgpu_update_labels)"""

@@ -18,6 +18,8 @@
 //                        the same labels, any map size); auto (default): SLAMGPU_ASSOC_AUTO.  -PARTICLE_EXCL_SPACING f (default 0:
 //                        off) caps the exclusion rule's radius at f x each observation's distance to the step's nearest other one
 //                        (slamgpu_set_particle_excl_spacing): dense maps, where the fixed radius would forbid every new landmark.
+//                        -PARTICLE_ASSOC_SAMPLE 1: data association sampling (slamgpu_set_particle_assoc_sampling; 0, the default:
+//                        nearest neighbour); the summary then prints the sampling counters (slamgpu_particle_sample_stats).
 //   -plot <sinks>        the per-step output the reference sends to slam-gui (plotting/NetworkPlot.cpp), byte for byte:
 //                        tcp://127.0.0.1:4242 (the existing slam-gui) | file:<frames> | gather:<dir> (the GUI's DataGatherer
 //                        files, headless) | none (default); several separated by ','
@@ -71,6 +73,8 @@ static void usage(const char *a0) {
     printf("                        or the per-particle gates acted on by every particle on a map of its own\n");
     printf("    -PARTICLE_EXCL_SPACING f  -assoc particle: cap the exclusion rule's radius at f x each observation's distance to the\n");
     printf("                        step's nearest other observation (default 0: the fixed radius)\n");
+    printf("    -PARTICLE_ASSOC_SAMPLE 0|1  -assoc particle: draw an ambiguous observation's landmark in proportion to its likelihood\n");
+    printf("                        (data association sampling, weights by the marginal likelihood; default 0: the nearest)\n");
     printf("    -gpus k             FastSLAM particle set distributed over k GPUs (k > devices: logical shards on device 0)\n");
     printf("    -observe host|device  where the observation of a step is made: host (default) or on the GPU (the packet never leaves\n");
     printf("                        device memory: slamgpu_step_observe; -rng philox, known association, no -plot; with -assoc particle:\n");
@@ -230,6 +234,10 @@ static void print_particle_map(slamgpu_ctx *ctx, const Simulator &sim, int N, lo
     printf("landmarks in map: %d (the best particle's, number %d; %d of the %d true landmarks within 1 m of one of them; %d slots in use by all particles "
            "together, %ld opened, %ld of them dead slots reused, %ld observations dropped for want of a slot, at most %d slots rewritten in a step)\n",
            held, best, covered, sim.map.nlm, slots, pp_opened, pp_reused, pp_dropped, pp_most);
+    int64_t st[3] = {0, 0, 0};
+    if (slamgpu_particle_sample_stats(ctx, st) == 0 && st[0] > 0)
+        printf("association sampling: %lld steps, %lld ambiguous (particle, observation) pairs, %lld drawn away from the nearest\n", (long long) st[0],
+               (long long) st[1], (long long) st[2]);
 }
 
 // The wrapper's loop (fastslam2wrapper.cpp:51-117) for a headless run, batched: what the per-iteration form asks of the GPU
@@ -476,6 +484,14 @@ int main(int argc, char **argv) {
             fprintf(stderr, "-PARTICLE_EXCL_SPACING: %s\n", slamgpu_last_error());
             slamgpu_destroy(ctx);
             return EXIT_FAILURE;
+        }
+        if (particle && !c.s("PARTICLE_ASSOC_SAMPLE").empty()) {
+            const std::string v = c.s("PARTICLE_ASSOC_SAMPLE");
+            if (slamgpu_set_particle_assoc_sampling(ctx, v == "1" ? 1 : (v == "0" ? 0 : -1)) != 0) {
+                fprintf(stderr, "-PARTICLE_ASSOC_SAMPLE %s: %s\n", v.c_str(), slamgpu_last_error());
+                slamgpu_destroy(ctx);
+                return EXIT_FAILURE;
+            }
         }
         // the reference creates its accelerator object before the wrapper seeds rand() (SLAMBackendApplication.cpp:22-24,
         // slamwrapper.cpp:48-52); HIP runtime initialisation draws from libc rand(), so seed (again) only now

@@ -637,6 +637,24 @@ struct AssocRhoArgs : AssocListArgs {
     const float *rho;
 };
 
+// Data association sampling (slamgpu_set_particle_assoc_sampling): a pair with two or more candidates takes the label
+// argmax_j (-nd_j / 2 + g_j), g_j Gumbel noise from Philox stream 4 at (first_particle + i, step, 4 + 8 q, j), and writes the factor
+// ratio = sum_k L_k / L_label (L = exp(-nd / 2), summed in fixed point: kernels.hip das_fix) that pp_resolve_kernel folds into the
+// weight of a fresh claim.  step: the step of the update the labels feed (host-driven; the device-driven walk reads PpState::step + 1).
+// The SAMPLE instantiations take these behind the radii (rho may be null there: RHO decides).
+struct SampleArgs {
+    float *ratio;                 // [nz][ncap], as the labels
+    unsigned long long *stats;    // [3] cumulative: steps, pairs with two or more candidates, pairs whose draw left the nearest
+    float ldet_r;                 // ln det R: every nd is at least this (S = Hf Pf Hf^T + R)
+    uint32_t k0, k1, first_particle, step, pad;
+};
+struct PpSampleArgs : PpRhoArgs {
+    SampleArgs smp;
+};
+struct AssocSampleArgs : AssocRhoArgs {
+    SampleArgs smp;
+};
+
 struct KernelTable {
     // the step: [resampling stage of the previous update, inline] + [gather] + [fused predicts] + per-particle observation
     // update + in-block weight prefix / totals  (+ helper blocks: genealogy copy, Ctrl words, estimate reduction)
@@ -685,7 +703,7 @@ struct KernelTable {
     // rho_dev (may be null; only with the rule on): the rule's radius per observation (excl_radii) in place of excl_base + excl_per_m * range
     void (*associate)(hipStream_t, const Buffers &, int nf, const float *z_dev, int nz, const float *R4, float gate_reject,
                       float gate_augment, const float *excl3, const uint32_t *retired_dev, int32_t *labels_dev, int labels_by_obs,
-                      const float *rho_dev);
+                      const float *rho_dev, const SampleArgs *smp);
     // seq_out != null: `out` and `seq_out` are pinned host memory; the kernel stores `seq` there last (system-scope fence)
     void (*shard_plan)(hipStream_t, const ShardPlanArgs &, const RngArgs &, ShardPlan *out, uint32_t *seq_out, uint32_t seq);
     void (*shard_pack)(hipStream_t, const Buffers &, const WeightScratch &, const ShardPackArgs &, const RngArgs &);
@@ -715,7 +733,7 @@ struct KernelTable {
     // the number of particles that hold each landmark slot (holders[l], preset to 0; plain set, tables in sync)
     void (*pp_census)(hipStream_t, const int32_t *labels_dev, int n, int nz, int ncap, int32_t *first_dev, int32_t *news_dev);
     void (*pp_resolve)(hipStream_t, const int32_t *labels_dev, int n, int nz, int ncap, const int32_t *uidx_dev, const int32_t *newk_dev, int m, int nn,
-                       float p_new, int logw, int16_t *obs_dev, float *wf_dev, uint8_t *any_dev);
+                       float p_new, int logw, int16_t *obs_dev, float *wf_dev, uint8_t *any_dev, const float *ratio_dev);
     void (*pp_holders)(hipStream_t, const Buffers &, int count, const int32_t *ids_dev, int32_t *holders_dev);  // ids (may be null: 0 .. count - 1)
     // slamgpu_run_particle: one iteration's stages, every size read from device memory (PpArgs).  resample: the outstanding resampling
     // stage of the previous iteration, if it updated (resample_kernel<true>); gather: the lazy gather over the rows in use, and in one
@@ -725,9 +743,10 @@ struct KernelTable {
     void (*pp_resample)(hipStream_t, const Buffers &, const WeightScratch &, const RngArgs &, const ResampleArgs &, const PpArgs &);
     void (*pp_gather)(hipStream_t, const Buffers &, const WeightScratch &, const PpArgs &, double *hist, int par);
     void (*pp_associate)(hipStream_t, const Buffers &, const float *R4, float gate_reject, float gate_augment, const float *excl3, int32_t *labels_dev,
-                         const PpArgs &, const float *rho_dev);
+                         const PpArgs &, const float *rho_dev, const SampleArgs *smp);
     void (*pp_book)(hipStream_t, const Buffers &, const PpArgs &);
-    void (*pp_resolve_dev)(hipStream_t, const int32_t *labels_dev, int n, int ncap, const PpArgs &, int16_t *obs_dev, float *wf_dev, uint8_t *any_dev);
+    void (*pp_resolve_dev)(hipStream_t, const int32_t *labels_dev, int n, int ncap, const PpArgs &, int16_t *obs_dev, float *wf_dev, uint8_t *any_dev,
+                           const float *ratio_dev);
     void (*update_particle_dev)(hipStream_t, const Buffers &, const PredictArgs &, const UpdateArgs &, const RngArgs &, const WeightScratch &,
                                 const PerParticle &);
     // SLAMGPU_ASSOC_LISTS, one launch each.  lists_box: the boxes of the slots the previous iteration's update rewrote or opened (the
@@ -739,7 +758,7 @@ struct KernelTable {
     // (rho_dev, may be null: as `associate`'s; the lists' reach for the rule follows it)
     void (*lists_build)(hipStream_t, const Buffers &, const AssocListArgs &, const float *rho_dev);
     void (*lists_walk)(hipStream_t, const Buffers &, const AssocListArgs &, const float *R4, float gate_reject, float gate_augment, int32_t *labels_dev,
-                       const float *rho_dev);
+                       const float *rho_dev, const SampleArgs *smp);
     // the exclusion rule's radius per observation from the step's observation spacing (slamgpu_set_particle_excl_spacing):
     // rho[q] = min(excl_base + excl_per_m r_q, f s_q), s_q the distance from (r_q cos b_q, r_q sin b_q) to the nearest other such point
     // of the step (+inf for one observation); *rho_nz = nz.  obs null: z_dev / nz from the host; else nz and z from the iteration's

@@ -2702,6 +2702,56 @@ __global__ void __launch_bounds__(kBlock) excl_radii_kernel(const ObserveOut *__
     if (q < nz) rho[q] = fminf(excl_base + excl_per_m * z[2 * q], f * sqrtf(m));
 }
 
+// DATA ASSOCIATION SAMPLING (SAMPLE instantiations; slamgpu_set_particle_assoc_sampling).  C = the slots a particle holds with
+// nis < gate_reject (and nd finite: what the nearest-neighbour rule can take).  |C| <= 1: the nearest-neighbour label, ratio 1, no draw.
+// |C| >= 2: the label is argmax_j (-nd_j / 2 + g_j), g_j = -ln(-ln u_j) Gumbel noise (Philox stream 4, one counter per slot), ties to the
+// lower slot -- an exact draw with P(j) ~ exp(-nd_j / 2) whatever order the candidates come in -- and the ratio sum_k t_k / t_label,
+// t = exp(-(nd - ln det R) / 2) <= 1 (S >= R; clamped for rounding) summed as integers in units of 2^-56 (128 candidates of headroom;
+// the sum saturates beyond), so that it is the same number on every path.  The first candidate waits in (jbest, nbest) until a second
+// one arrives: a pair with one candidate costs no Philox.
+struct DasPick {
+    float sbest, ndl;          // the best score and the nd of its slot
+    int jl;                    // the sampled slot (-1: fewer than two candidates so far)
+    unsigned long long sum;    // sum of das_fix over the candidates (0: fewer than two)
+};
+SLAM_DEV unsigned long long das_fix(float nd, float ldet_r) {
+    const float t = fminf(expf(-0.5f * (nd - ldet_r)), 1.0f);
+    const unsigned long long v = (unsigned long long) (t * 0x1p56f);
+    return v > 0ull ? v : 1ull;
+}
+SLAM_DEV float das_score(const SampleArgs &s, uint32_t step, int i, int q, int j, float nd) {
+    const U4 r = philox4x32((uint32_t) (s.first_particle + i), step, 4u + 8u * (uint32_t) q, (uint32_t) j, s.k0, s.k1);
+    return -0.5f * nd - logf(-logf(u01(r.x)));
+}
+SLAM_DEV void das_init(DasPick &d) {
+    d.sbest = -INFINITY;
+    d.ndl = 0.0f;
+    d.jl = -1;
+    d.sum = 0ull;
+}
+// candidate (j, nd) of observation q; (jb, nb): the nearest-neighbour pick BEFORE this candidate is taken into it.  The second candidate
+// draws for the first one too (one Philox call site, run twice)
+SLAM_DEV void das_take(DasPick &d, const SampleArgs &s, uint32_t step, int i, int q, int jb, float nb, int j, float nd) {
+    if (jb < 0 || !(nd < INFINITY)) return;  // (the first candidate: jb / nb hold it until a second arrives)
+#pragma nounroll
+    for (int k = d.jl < 0 ? 0 : 1; k < 2; k++) {
+        const int jk = k ? j : jb;
+        const float nk = k ? nd : nb;
+        const unsigned long long f = das_fix(nk, s.ldet_r);
+        d.sum = d.sum + f < d.sum ? ~0ull : d.sum + f;
+        const float sc = das_score(s, step, i, q, jk, nk);
+        if (sc > d.sbest || (sc == d.sbest && jk < d.jl) || d.jl < 0) {
+            d.sbest = sc;
+            d.jl = jk;
+            d.ndl = nk;
+        }
+    }
+}
+// the ratio of a pair (1: fewer than two candidates), rounded once
+SLAM_DEV float das_ratio(const DasPick &d, float ldet_r) {
+    return d.jl < 0 ? 1.0f : (float) ((double) d.sum / (double) das_fix(d.ndl, ldet_r));
+}
+
 // EXCL (slamgpu_particle_assoc::excl_*; slamgpu_associate never): the EXCLUSION rule of a particle's own map.  The gates measure an
 // observation against S = Hf Pf Hf^T + R -- for a converged landmark that is R, half a metre at five sigma -- and know nothing of the
 // particle's own pose error (the EKF's S carries it, ekfslam.cpp:160-176; a particle's pose is a point).  So a particle a metre off
@@ -2712,11 +2762,12 @@ __global__ void __launch_bounds__(kBlock) excl_radii_kernel(const ObserveOut *__
 // (DEV: slamgpu_run_particle -- nz, nf and the observations from device memory (PpArgs); the census of the labels and, when it is due,
 // of the holders rides in this launch; an iteration without observations takes the estimate partials instead)
 // (RHO, with EXCL: the rule's radius is P.rho[q], excl_radii_kernel's, instead of excl_base + excl_per_m * range)
-template <bool EXCL, bool DEV = false, bool RHO = false>
+// (SAMPLE: data association sampling, das_take above -- the labels by observation, the ratios beside them, the counters per wave)
+template <bool EXCL, bool DEV = false, bool RHO = false, bool SAMPLE = false>
 __global__ void __launch_bounds__(kBlock) associate_kernel(Buffers B, int nf, const float *__restrict__ z, int nz, float r00, float r01,
                                                             float r10, float r11, float gate1, float gate2, float excl_base, float excl_per_m, float unique_ratio,
                                                             const uint32_t *__restrict__ retired, int32_t *__restrict__ labels, int by_obs,
-                                                            std::conditional_t<RHO, PpRhoArgs, PpArgs> P) {
+                                                            std::conditional_t<SAMPLE, PpSampleArgs, std::conditional_t<RHO, PpRhoArgs, PpArgs>> P) {
     static_assert(EXCL || !RHO, "the radii are the exclusion rule's");
     if constexpr (DEV) {
         nz = P.obs->nz;
@@ -2733,11 +2784,18 @@ __global__ void __launch_bounds__(kBlock) associate_kernel(Buffers B, int nf, co
     const int cur = B.ctrl->live[B.slot];
     const size_t S = (size_t) B.ncap;
     const float4 pa = B.poseA[cur][i];
+    [[maybe_unused]] uint32_t das_step = 0;
+    [[maybe_unused]] unsigned long long das_amb = 0, das_moved = 0;  // (SAMPLE: wave-uniform counts)
+    if constexpr (SAMPLE) {
+        das_step = DEV ? P.st->step + 1u : P.smp.step;
+        if (i == 0) atomicAdd(P.smp.stats, 1ull);
+    }
     for (int q0 = 0; q0 < nz; q0 += kAssocBatch) {
         float nbest[kAssocBatch], outer[kAssocBatch];
         int jbest[kAssocBatch];
         [[maybe_unused]] float wx[kAssocBatch], wy[kAssocBatch], d1[kAssocBatch], d2[kAssocBatch];
         [[maybe_unused]] int j1[kAssocBatch];
+        [[maybe_unused]] uint32_t amb = 0u;  // (SAMPLE: bit q -- observation q0 + q has two or more candidates)
 #pragma unroll
         for (int q = 0; q < kAssocBatch; q++) {
             nbest[q] = INFINITY;  // the reference's `float nbest = 1e60` is +inf in float32
@@ -2759,6 +2817,8 @@ __global__ void __launch_bounds__(kBlock) associate_kernel(Buffers B, int nf, co
         // profiles/rocprof_sq_r06_assoc_exhaustive_c3.txt).  The gate arithmetic of landmarks j and j + 1 is independent; only the
         // comparisons run through both, in landmark order: the same decisions.
         auto take = [&](int q, int j, float nis, float nd, const float4 &la) {
+            if constexpr (SAMPLE)
+                if (nis < gate1 && nd < INFINITY && jbest[q] >= 0) amb |= 1u << q;
             if (nis < gate1 && nd < nbest[q]) {
                 nbest[q] = nd;
                 jbest[q] = j;
@@ -2814,10 +2874,47 @@ __global__ void __launch_bounds__(kBlock) associate_kernel(Buffers B, int nf, co
                     else rho = excl_base + excl_per_m * z[2 * (q0 + q)];
                     if (jbest[q] < 0 && d1[q] < rho * rho) label = d2[q] > unique_ratio * unique_ratio * d1[q] ? j1[q] : kAssocDiscard;
                 }
+                if constexpr (SAMPLE) {
+                    // two or more candidates (then jbest >= 0, and the rule above left the label alone): the pair's slots again, in
+                    // order, for the draws -- a pair with one candidate or none pays nothing more (the gate arithmetic is the scan's)
+                    const bool two = (amb >> q) & 1u;
+                    DasPick d;
+                    das_init(d);
+                    if (two) {
+                        const float zr = z[2 * (q0 + q)], zb = z[2 * (q0 + q) + 1];
+                        int jb = -1;
+                        float nb = INFINITY;
+                        for (int j = 0; j < nf; j++) {
+                            if (retired && ((retired[j >> 5] >> (j & 31)) & 1u)) continue;
+                            float4 la;
+                            float lb;
+                            read_through_genealogy(B, B.lmk_live, cur, S, j, i, la, lb);
+                            const AssocLm L = assoc_landmark(pa, la, lb, r00, r01, r10, r11);
+                            float nis, nd;
+                            assoc_gate(L, zr, zb, nis, nd);
+                            if (nis < gate1) {
+                                das_take(d, P.smp, das_step, i, q0 + q, jb, nb, j, nd);
+                                if (nd < nb) {
+                                    nb = nd;
+                                    jb = j;
+                                }
+                            }
+                        }
+                        label = d.jl;
+                    }
+                    das_amb += __popcll(__ballot(two));
+                    das_moved += __popcll(__ballot(two && d.jl != jbest[q]));
+                    P.smp.ratio[(size_t) (q0 + q) * S + i] = das_ratio(d, P.smp.ldet_r);
+                }
                 labels[by_obs ? (size_t) (q0 + q) * S + i : (size_t) i * nz + q0 + q] = label;  // (by_obs: [nz][ncap], what the per-particle update reads)
                 if constexpr (DEV) pp_census_label(label, q0 + q, P);
             }
     }
+    if constexpr (SAMPLE)
+        if ((das_amb | das_moved) && (threadIdx.x & (kWave - 1)) == (int) __ffsll((long long) __ballot(true)) - 1) {
+            atomicAdd(P.smp.stats + 1, das_amb);
+            atomicAdd(P.smp.stats + 2, das_moved);
+        }
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -3263,11 +3360,16 @@ SLAM_DEV int walk_q_hi(const Args &A, int q_lo) {
     }
 }
 // RHO (with EXCL): the rule's radius is A.rho[q] (excl_radii_kernel), the reach assoc_lists_kernel<.., RHO> kept the list for
-template <bool LISTS, bool PEROBS = false, bool EXCL = false, bool DEV = false, bool RHO = false>
-__global__ void __launch_bounds__(kBlock) associate_grid_kernel(Buffers B, std::conditional_t<PEROBS, std::conditional_t<RHO, AssocRhoArgs, AssocListArgs>, AssocGridArgs> A,
+// SAMPLE (PEROBS): data association sampling (das_take) in the first walk -- it visits every slot that passes gate_reject -- and in the
+// walk over every slot; the draws are per slot, so the labels and ratios are associate_kernel<.., SAMPLE>'s in any visiting order
+template <bool LISTS, bool PEROBS, bool EXCL, bool DEV, bool RHO, bool SAMPLE>
+using AssocWalkArgs = std::conditional_t<PEROBS, std::conditional_t<SAMPLE, AssocSampleArgs, std::conditional_t<RHO, AssocRhoArgs, AssocListArgs>>, AssocGridArgs>;
+template <bool LISTS, bool PEROBS = false, bool EXCL = false, bool DEV = false, bool RHO = false, bool SAMPLE = false>
+__global__ void __launch_bounds__(kBlock) associate_grid_kernel(Buffers B, AssocWalkArgs<LISTS, PEROBS, EXCL, DEV, RHO, SAMPLE> A,
                                                                  float r00, float r01, float r10, float r11, float gate1, float gate2, int32_t *__restrict__ labels) {
     static_assert((LISTS || !PEROBS) && (PEROBS || !(EXCL || DEV)), "the exclusion rule and the device-driven walk are the lists' per observation");
     static_assert(EXCL || !RHO, "the radii are the exclusion rule's");
+    static_assert(PEROBS || !SAMPLE, "sampling is the per-particle association's");
     const int i = blockIdx.x * kBlock + threadIdx.x;
     if constexpr (DEV) {
         const int nz = A.obs->nz;  // (the true count; A.nz is the lists grid)
@@ -3276,6 +3378,12 @@ __global__ void __launch_bounds__(kBlock) associate_grid_kernel(Buffers B, std::
             return;
         }
         pp_count_holders_part(B, A.book->nf, nz, A.P, blockIdx.y, gridDim.y);
+    }
+    [[maybe_unused]] uint32_t das_step = 0;
+    [[maybe_unused]] unsigned long long das_amb = 0, das_moved = 0;  // (SAMPLE: wave-uniform counts)
+    if constexpr (SAMPLE) {
+        das_step = DEV ? A.P.st->step + 1u : A.smp.step;
+        if (i == 0 && blockIdx.y == 0) atomicAdd(A.smp.stats, 1ull);
     }
     const AssocGeom g = *A.geom;
     if constexpr (!PEROBS)
@@ -3295,6 +3403,7 @@ __global__ void __launch_bounds__(kBlock) associate_grid_kernel(Buffers B, std::
     for (int q = q_lo; q < q_hi; q++) {
         int label = kVoteEmpty;
         [[maybe_unused]] int pbest = -1;  // (LISTS: position of jbest in the observation's list: where its vote goes)
+        [[maybe_unused]] bool das_two = false, das_left = false;  // (SAMPLE: two or more candidates / the draw left the nearest)
         if (on) {
             // (uniform and written before the launch: scalar loads)
             const auto *zc = (const __attribute__((address_space(4))) float *) reinterpret_cast<uintptr_t>(walk_z<DEV>(A));
@@ -3315,6 +3424,8 @@ __global__ void __launch_bounds__(kBlock) associate_grid_kernel(Buffers B, std::
             float nbest = INFINITY, outer = INFINITY;
             int jbest = -1;
             [[maybe_unused]] int pcur = 0;  // (LISTS: position of the entry being visited in the observation's list)
+            [[maybe_unused]] DasPick das;
+            if constexpr (SAMPLE) das_init(das);
             // one entry of the cell: the radial pre-test on the landmark's box alone (every estimate of j lies in the box, so its
             // distance d from this pose is within [dmin, dmax] of the box; a gate needs |d - r| < the entry's bound), on SQUARED
             // distances (round 6: no square root per entry, and the bound without the factor (1 + pi / 2) the CELL radius needs and
@@ -3356,6 +3467,8 @@ __global__ void __launch_bounds__(kBlock) associate_grid_kernel(Buffers B, std::
                 float nis, nd;
                 assoc_gate(L, zr, zb, nis, nd);
                 pairs++;
+                if constexpr (SAMPLE)
+                    if (nis < gate1) das_take(das, A.smp, das_step, i, q, jbest, nbest, j, nd);
                 // (the cell's landmarks come in no particular order: ties go to the lower index, as in the ascending scan)
                 if (nis < gate1 && (nd < nbest || (nd == nbest && j < jbest))) {
                     nbest = nd;
@@ -3430,6 +3543,8 @@ __global__ void __launch_bounds__(kBlock) associate_grid_kernel(Buffers B, std::
                         float nis, nd;
                         assoc_gate(L, zr, zb, nis, nd);
                         pairs++;
+                        if constexpr (SAMPLE)
+                            if (nis < gate1) das_take(das, A.smp, das_step, i, q, jbest, nbest, j, nd);
                         if (nis < gate1 && nd < nbest) {
                             nbest = nd;
                             jbest = j;
@@ -3481,7 +3596,17 @@ __global__ void __launch_bounds__(kBlock) associate_grid_kernel(Buffers B, std::
             label = jbest > -1 ? jbest : (outer > gate2 ? kAssocNew : kAssocDiscard);
             if constexpr (EXCL)
                 if (xlabel != kVoteEmpty) label = xlabel;
+            if constexpr (SAMPLE) {  // (two or more candidates: jbest >= 0, so the rule left the label alone)
+                das_two = das.jl >= 0;
+                das_left = das_two && das.jl != jbest;
+                if (das_two) label = das.jl;
+                A.smp.ratio[(size_t) q * S + i] = das_ratio(das, A.smp.ldet_r);
+            }
             if (labels) labels[A.lab_by_obs ? (size_t) q * S + i : (size_t) i * A.nz + q] = label;
+        }
+        if constexpr (SAMPLE) {
+            das_amb += __popcll(__ballot(das_two));
+            das_moved += __popcll(__ballot(das_left));
         }
         if (A.census_first) {
             // (slamgpu_update_particle: a wave's particles nearly always agree: one atomic per wave and distinct label, nobody waits for it)
@@ -3523,6 +3648,11 @@ __global__ void __launch_bounds__(kBlock) associate_grid_kernel(Buffers B, std::
         }
     }
     if (__ballot(full) && lane == 0) atomicOr(&A.geom->overflow, 2);
+    if constexpr (SAMPLE)
+        if ((das_amb | das_moved) && lane == 0) {
+            atomicAdd(A.smp.stats + 1, das_amb);
+            atomicAdd(A.smp.stats + 2, das_moved);
+        }
     pairs = (unsigned long long) wave_sum_d((double) pairs);
     if constexpr (PEROBS) {
         if (lane == 0 && pairs) atomicAdd(A.lstats + 3, pairs);
@@ -4203,8 +4333,21 @@ static void launch_observe_book(hipStream_t st, const ObserveArgs &A) {
 }
 
 static void launch_associate(hipStream_t st, const Buffers &B, int nf, const float *z, int nz, const float *R4, float g1, float g2, const float *excl3,
-                             const uint32_t *retired, int32_t *labels, int by_obs, const float *rho) {
-    if (excl3 && excl3[0] + excl3[1] > 0.0f && rho)
+                             const uint32_t *retired, int32_t *labels, int by_obs, const float *rho, const SampleArgs *smp) {
+    if (smp) {  // (data association sampling: the labels by observation)
+        const PpSampleArgs P{PpRhoArgs{PpArgs{}, rho}, *smp};
+        const bool excl = excl3 && excl3[0] + excl3[1] > 0.0f;
+        const float e0 = excl ? excl3[0] : 0.0f, e1 = excl ? excl3[1] : 0.0f, e2 = excl ? excl3[2] : 0.0f;
+        if (excl && rho)
+            hipLaunchKernelGGL((associate_kernel<true, false, true, true>), dim3(B.ncap / kBlock), dim3(kBlock), 0, st, B, nf, z, nz, R4[0], R4[1], R4[2], R4[3], g1, g2,
+                               e0, e1, e2, retired, labels, 1, P);
+        else if (excl)
+            hipLaunchKernelGGL((associate_kernel<true, false, false, true>), dim3(B.ncap / kBlock), dim3(kBlock), 0, st, B, nf, z, nz, R4[0], R4[1], R4[2], R4[3], g1,
+                               g2, e0, e1, e2, retired, labels, 1, P);
+        else
+            hipLaunchKernelGGL((associate_kernel<false, false, false, true>), dim3(B.ncap / kBlock), dim3(kBlock), 0, st, B, nf, z, nz, R4[0], R4[1], R4[2], R4[3], g1,
+                               g2, e0, e1, e2, retired, labels, 1, P);
+    } else if (excl3 && excl3[0] + excl3[1] > 0.0f && rho)
         hipLaunchKernelGGL((associate_kernel<true, false, true>), dim3(B.ncap / kBlock), dim3(kBlock), 0, st, B, nf, z, nz, R4[0], R4[1], R4[2], R4[3], g1, g2,
                            excl3[0], excl3[1], excl3[2], retired, labels, by_obs, PpRhoArgs{PpArgs{}, rho});
     else if (excl3 && excl3[0] + excl3[1] > 0.0f)
@@ -4382,11 +4525,15 @@ __global__ void __launch_bounds__(kBlock) pp_census_kernel(const int32_t *__rest
 // has more entries than the LDS holds bits for -- lds_words = 0 -- read the row.  Before: 865 x two dependent trips, 0.92 ms.)
 constexpr int kResolveBatch = 8;
 // (DEV: slamgpu_run_particle -- nz from the observations, m and nn from the packet pp_book_kernel wrote; no observation: nothing to do)
-template <bool DEV = false>
+// (Ratio = float, one argument more: data association sampling -- a FRESH claim multiplies the factor by ratio[j][i], the sampled pair's
+// sum_k L_k / L_label (log-weights: adds its log); a second claim still costs p_new.  Without it the argument list is the old one.)
+template <bool DEV = false, class... Ratio>
 __global__ void __launch_bounds__(kBlock) pp_resolve_kernel(const int32_t *__restrict__ labels, int n, int nz, size_t S, const int32_t *__restrict__ uidx,
                                                              const int32_t *__restrict__ newk, int m, int nn, float p_new, int logw, int lds_words,
                                                              int16_t *__restrict__ obs, float *__restrict__ wf, uint8_t *__restrict__ any, const ObsPacket *pkt,
-                                                             const ObserveOut *obs_out) {
+                                                             const ObserveOut *obs_out, const Ratio *__restrict__... ratio) {
+    static_assert(sizeof...(Ratio) <= 1, "one ratio array");
+    constexpr bool SAMPLE = sizeof...(Ratio) == 1;
     extern __shared__ uint32_t sh_claim[];  // [lds_words][kBlock]
     if constexpr (DEV) {
         nz = obs_out->nz;
@@ -4404,6 +4551,8 @@ __global__ void __launch_bounds__(kBlock) pp_resolve_kernel(const int32_t *__res
         return;
     }
     int unexplained = 0, flags = 0;
+    [[maybe_unused]] float fr;  // (SAMPLE: the fresh claims' ratios, in observation order)
+    if constexpr (SAMPLE) fr = logw ? 0.0f : 1.0f;
     for (int j0 = 0; j0 < nz; j0 += kResolveBatch) {
         int labs[kResolveBatch], ks[kResolveBatch];
 #pragma unroll
@@ -4429,6 +4578,10 @@ __global__ void __launch_bounds__(kBlock) pp_resolve_kernel(const int32_t *__res
                 if (fresh) {
                     obs[(size_t) k * S + i] = (int16_t) j;
                     flags |= 1;
+                    if constexpr (SAMPLE) {
+                        const float r = (ratio[(size_t) j * S + i], ...);
+                        fr = logw ? fr + logf(r) : fr * r;
+                    }
                 } else {
                     unexplained++;
                 }
@@ -4445,6 +4598,7 @@ __global__ void __launch_bounds__(kBlock) pp_resolve_kernel(const int32_t *__res
     float f = logw ? 0.0f : 1.0f;
     const float lp = logw ? logf(p_new) : 0.0f;
     for (int q = 0; q < unexplained; q++) f = logw ? f + lp : f * p_new;
+    if constexpr (SAMPLE) f = logw ? f + fr : f * fr;
     wf[i] = f;
     any[i] = (uint8_t) flags;
 }
@@ -4489,11 +4643,15 @@ static void launch_pp_census(hipStream_t st, const int32_t *labels, int n, int n
     hipLaunchKernelGGL(pp_census_kernel, dim3((n + kBlock - 1) / kBlock, (nz + kCensusObs - 1) / kCensusObs), dim3(kBlock), 0, st, labels, n, nz, (size_t) ncap, first, news);
 }
 static void launch_pp_resolve(hipStream_t st, const int32_t *labels, int n, int nz, int ncap, const int32_t *uidx, const int32_t *newk, int m, int nn,
-                              float p_new, int logw, int16_t *obs, float *wf, uint8_t *any) {
+                              float p_new, int logw, int16_t *obs, float *wf, uint8_t *any, const float *ratio) {
     // claimed-entry bits in LDS while the packet's re-observed entries fit 48 KB of them (m <= 1 536: every step of the 10 000-landmark map)
     const int words = (m + 31) / 32, lds_words = words * kBlock * 4 <= 48 * 1024 ? words : 0;
-    hipLaunchKernelGGL(pp_resolve_kernel<false>, dim3(ncap / kBlock), dim3(kBlock), (size_t) lds_words * kBlock * sizeof(uint32_t), st, labels, n, nz, (size_t) ncap, uidx,
-                       newk, m, nn, p_new, logw, lds_words, obs, wf, any, nullptr, nullptr);
+    if (ratio)
+        hipLaunchKernelGGL((pp_resolve_kernel<false, float>), dim3(ncap / kBlock), dim3(kBlock), (size_t) lds_words * kBlock * sizeof(uint32_t), st, labels, n, nz,
+                           (size_t) ncap, uidx, newk, m, nn, p_new, logw, lds_words, obs, wf, any, (const ObsPacket *) nullptr, (const ObserveOut *) nullptr, ratio);
+    else
+        hipLaunchKernelGGL(pp_resolve_kernel<false>, dim3(ncap / kBlock), dim3(kBlock), (size_t) lds_words * kBlock * sizeof(uint32_t), st, labels, n, nz, (size_t) ncap, uidx,
+                           newk, m, nn, p_new, logw, lds_words, obs, wf, any, nullptr, nullptr);
 }
 static void launch_pp_holders(hipStream_t st, const Buffers &B, int count, const int32_t *ids, int32_t *holders) {
     hipLaunchKernelGGL(pp_holders_kernel, dim3(B.ncap / kBlock), dim3(kBlock), 0, st, B, count, ids, holders);
@@ -4512,8 +4670,21 @@ static void launch_pp_gather(hipStream_t st, const Buffers &B, const WeightScrat
     hipLaunchKernelGGL(pp_gather_kernel, dim3(ws.nblocks + 1, gy), dim3(kBlock), 0, st, B, ws, P, hist, par);
 }
 static void launch_pp_associate(hipStream_t st, const Buffers &B, const float *R4, float g1, float g2, const float *excl3, int32_t *labels, const PpArgs &P,
-                                const float *rho) {
-    if (excl3 && excl3[0] + excl3[1] > 0.0f && rho)
+                                const float *rho, const SampleArgs *smp) {
+    if (smp) {  // (data association sampling)
+        const PpSampleArgs PS{PpRhoArgs{P, rho}, *smp};
+        const bool excl = excl3 && excl3[0] + excl3[1] > 0.0f;
+        const float e0 = excl ? excl3[0] : 0.0f, e1 = excl ? excl3[1] : 0.0f, e2 = excl ? excl3[2] : 0.0f;
+        if (excl && rho)
+            hipLaunchKernelGGL((associate_kernel<true, true, true, true>), dim3(B.ncap / kBlock), dim3(kBlock), 0, st, B, 0, (const float *) nullptr, 0, R4[0], R4[1],
+                               R4[2], R4[3], g1, g2, e0, e1, e2, (const uint32_t *) P.retired, labels, 1, PS);
+        else if (excl)
+            hipLaunchKernelGGL((associate_kernel<true, true, false, true>), dim3(B.ncap / kBlock), dim3(kBlock), 0, st, B, 0, (const float *) nullptr, 0, R4[0], R4[1],
+                               R4[2], R4[3], g1, g2, e0, e1, e2, (const uint32_t *) P.retired, labels, 1, PS);
+        else
+            hipLaunchKernelGGL((associate_kernel<false, true, false, true>), dim3(B.ncap / kBlock), dim3(kBlock), 0, st, B, 0, (const float *) nullptr, 0, R4[0], R4[1],
+                               R4[2], R4[3], g1, g2, e0, e1, e2, (const uint32_t *) P.retired, labels, 1, PS);
+    } else if (excl3 && excl3[0] + excl3[1] > 0.0f && rho)
         hipLaunchKernelGGL((associate_kernel<true, true, true>), dim3(B.ncap / kBlock), dim3(kBlock), 0, st, B, 0, (const float *) nullptr, 0, R4[0], R4[1], R4[2], R4[3],
                            g1, g2, excl3[0], excl3[1], excl3[2], (const uint32_t *) P.retired, labels, 1, PpRhoArgs{P, rho});
     else if (excl3 && excl3[0] + excl3[1] > 0.0f)
@@ -4524,11 +4695,17 @@ static void launch_pp_associate(hipStream_t st, const Buffers &B, const float *R
                            g2, 0.0f, 0.0f, 0.0f, (const uint32_t *) P.retired, labels, 1, P);
 }
 static void launch_pp_book(hipStream_t st, const Buffers &B, const PpArgs &P) { hipLaunchKernelGGL(pp_book_kernel, dim3(1), dim3(kBlock), 0, st, B, P); }
-static void launch_pp_resolve_dev(hipStream_t st, const int32_t *labels, int n, int ncap, const PpArgs &P, int16_t *obs, float *wf, uint8_t *any) {
+static void launch_pp_resolve_dev(hipStream_t st, const int32_t *labels, int n, int ncap, const PpArgs &P, int16_t *obs, float *wf, uint8_t *any,
+                                  const float *ratio) {
     // (the packet's entries are at most cap_nf: the claimed-entry bits for that many, when they fit)
     const int words = (P.cap_nf + 31) / 32, lds_words = words * kBlock * 4 <= 48 * 1024 ? words : 0;
-    hipLaunchKernelGGL(pp_resolve_kernel<true>, dim3(ncap / kBlock), dim3(kBlock), (size_t) lds_words * kBlock * sizeof(uint32_t), st, labels, n, 0, (size_t) ncap,
-                       (const int32_t *) P.uidx, (const int32_t *) P.newk, 0, 0, P.p_new, P.logw, lds_words, obs, wf, any, (const ObsPacket *) P.pkt, P.obs);
+    if (ratio)
+        hipLaunchKernelGGL((pp_resolve_kernel<true, float>), dim3(ncap / kBlock), dim3(kBlock), (size_t) lds_words * kBlock * sizeof(uint32_t), st, labels, n, 0,
+                           (size_t) ncap, (const int32_t *) P.uidx, (const int32_t *) P.newk, 0, 0, P.p_new, P.logw, lds_words, obs, wf, any, (const ObsPacket *) P.pkt,
+                           (const ObserveOut *) P.obs, ratio);
+    else
+        hipLaunchKernelGGL(pp_resolve_kernel<true>, dim3(ncap / kBlock), dim3(kBlock), (size_t) lds_words * kBlock * sizeof(uint32_t), st, labels, n, 0, (size_t) ncap,
+                           (const int32_t *) P.uidx, (const int32_t *) P.newk, 0, 0, P.p_new, P.logw, lds_words, obs, wf, any, (const ObsPacket *) P.pkt, P.obs);
 }
 
 // SLAMGPU_ASSOC_LISTS (kernels.h: KernelTable::lists_*); A.nz: the observations (DEV: the host's bound on them, >= 1)
@@ -4549,10 +4726,25 @@ static void launch_lists_build(hipStream_t st, const Buffers &B, const AssocList
     else if (A.obs) hipLaunchKernelGGL((assoc_lists_kernel<true, true>), dim3(A.nz), dim3(kBlock), 0, st, A, B.erow, B.lmk_live);
     else hipLaunchKernelGGL((assoc_lists_kernel<true, false>), dim3(A.nz), dim3(kBlock), 0, st, A, B.erow, B.lmk_live);
 }
-static void launch_lists_walk(hipStream_t st, const Buffers &B, const AssocListArgs &A, const float *R4, float g1, float g2, int32_t *labels, const float *rho) {
+static void launch_lists_walk(hipStream_t st, const Buffers &B, const AssocListArgs &A, const float *R4, float g1, float g2, int32_t *labels, const float *rho,
+                              const SampleArgs *smp) {
     const dim3 grid(B.ncap / kBlock, (A.nz + A.obs_per_block - 1) / A.obs_per_block);
     const bool excl = A.excl_base + A.excl_per_m > 0.0f;
-    if (excl && rho && A.obs)
+    if (smp) {  // (data association sampling)
+        const AssocSampleArgs AS{AssocRhoArgs{A, rho}, *smp};
+        if (excl && rho && A.obs)
+            hipLaunchKernelGGL((associate_grid_kernel<true, true, true, true, true, true>), grid, dim3(kBlock), 0, st, B, AS, R4[0], R4[1], R4[2], R4[3], g1, g2, labels);
+        else if (excl && rho)
+            hipLaunchKernelGGL((associate_grid_kernel<true, true, true, false, true, true>), grid, dim3(kBlock), 0, st, B, AS, R4[0], R4[1], R4[2], R4[3], g1, g2, labels);
+        else if (excl && A.obs)
+            hipLaunchKernelGGL((associate_grid_kernel<true, true, true, true, false, true>), grid, dim3(kBlock), 0, st, B, AS, R4[0], R4[1], R4[2], R4[3], g1, g2, labels);
+        else if (excl)
+            hipLaunchKernelGGL((associate_grid_kernel<true, true, true, false, false, true>), grid, dim3(kBlock), 0, st, B, AS, R4[0], R4[1], R4[2], R4[3], g1, g2, labels);
+        else if (A.obs)
+            hipLaunchKernelGGL((associate_grid_kernel<true, true, false, true, false, true>), grid, dim3(kBlock), 0, st, B, AS, R4[0], R4[1], R4[2], R4[3], g1, g2, labels);
+        else
+            hipLaunchKernelGGL((associate_grid_kernel<true, true, false, false, false, true>), grid, dim3(kBlock), 0, st, B, AS, R4[0], R4[1], R4[2], R4[3], g1, g2, labels);
+    } else if (excl && rho && A.obs)
         hipLaunchKernelGGL((associate_grid_kernel<true, true, true, true, true>), grid, dim3(kBlock), 0, st, B, AssocRhoArgs{A, rho}, R4[0], R4[1], R4[2], R4[3], g1, g2,
                            labels);
     else if (excl && rho)

@@ -309,6 +309,15 @@ struct slamgpu_ctx {
     float excl_spacing = 0.0f;
     int32_t *excl_rho_dev = nullptr;
     int excl_rho_cap = 0;
+    // data association sampling (slamgpu_set_particle_assoc_sampling): on / off, the ratios of the sampled pairs ([nz][ncap], as
+    // pp_lab_dev; held only while sampling is on) and the cumulative counters (SampleArgs::stats)
+    int32_t das_on = 0;
+    float *das_ratio_dev = nullptr;
+    size_t das_ratio_cap = 0;
+    unsigned long long *das_stats_dev = nullptr;
+    // the observations of the last per-particle step (slamgpu_particle_labels): the host-driven call's count, or -1: the device-driven
+    // iteration's (ObserveOut::nz)
+    int32_t pp_lab_nz = 0;
     int pp_report_n = 0;
     bool pp_stage_open = false;       // the previous iteration may have left a resampling stage (the device knows) and no gather has run since
     double *pp_prev_hist = nullptr;   // ... its history slot and the parity of its weight scratch
@@ -999,7 +1008,8 @@ void slamgpu_destroy(slamgpu_ctx *c) {
     if (c->pp_tab_dev) (void) hipFree(c->pp_tab_dev);
     if (c->pp_wf_dev) (void) hipFree(c->pp_wf_dev);
     if (c->pp_any_dev) (void) hipFree(c->pp_any_dev);
-    for (void *p_ : {(void *) c->pp_st_dev, (void *) c->pp_words_dev, (void *) c->pp_pkt_dev, (void *) c->pp_report_dev, (void *) c->lstats_dev, (void *) c->excl_rho_dev})
+    for (void *p_ : {(void *) c->pp_st_dev, (void *) c->pp_words_dev, (void *) c->pp_pkt_dev, (void *) c->pp_report_dev, (void *) c->lstats_dev, (void *) c->excl_rho_dev,
+                     (void *) c->das_ratio_dev, (void *) c->das_stats_dev})
         if (p_) (void) hipFree(p_);
     for (void *p_ : {(void *) c->box_dev, (void *) c->assoc_ids_dev, (void *) c->cell_start_dev, (void *) c->cell_fill_dev, (void *) c->items_dev,
                      (void *) c->geom_dev})
@@ -2882,6 +2892,36 @@ const float *excl_radii(slamgpu_ctx *c, const ObserveOut *obs, const float *z_de
     return rho;
 }
 
+// data association sampling (slamgpu_set_particle_assoc_sampling): room for the ratios of nz observations of every slot, and the counters
+int das_reserve(slamgpu_ctx *c, int nz) {
+    if (!c->das_stats_dev) {
+        unsigned long long *p = nullptr;
+        HIP_TRY(hipMalloc((void **) &p, sizeof(unsigned long long) * 4));
+        HIP_TRY(hipMemset(p, 0, sizeof(unsigned long long) * 4));
+        c->das_stats_dev = p;
+    }
+    const size_t want = (size_t) c->B.ncap * (size_t) std::max(nz, 1);
+    if (want <= c->das_ratio_cap) return 0;
+    if (c->das_ratio_dev) (void) hipFree(c->das_ratio_dev);
+    c->das_ratio_dev = nullptr;
+    c->das_ratio_cap = 0;
+    HIP_TRY(hipMalloc((void **) &c->das_ratio_dev, sizeof(float) * want));
+    c->das_ratio_cap = want;
+    return 0;
+}
+// what the SAMPLE instantiations read (das_reserve done); step: the update's (host-driven: obs_step + 1; the device-driven walk reads its own)
+SampleArgs das_args(const slamgpu_ctx *c, const float R[4]) {
+    SampleArgs s{};
+    s.ratio = c->das_ratio_dev;
+    s.stats = c->das_stats_dev;
+    s.ldet_r = logf(R[0] * R[3] - R[1] * R[2]);
+    s.k0 = (uint32_t) c->cfg.seed;
+    s.k1 = (uint32_t) (c->cfg.seed >> 32);
+    s.first_particle = (uint32_t) c->cfg.first_particle;
+    s.step = c->obs_step + 1u;
+    return s;
+}
+
 // the boxes, grid / list and geometry buffers of the prefilter
 int grid_buffers(slamgpu_ctx *c) {
     if (c->box_dev) return 0;
@@ -2903,7 +2943,7 @@ int grid_buffers(slamgpu_ctx *c) {
 // lab_ext: a device array the labels are left in BY OBSERVATION, [nz][ncap] (slamgpu_update_particle: they never visit the host), or null
 int associate_impl(slamgpu_ctx *c, const float *z, int32_t nz, const float R[4], float gate_reject, float gate_augment, int32_t mode,
                    int32_t *labels, int32_t *consensus, float *support, double stats[4], int32_t *lab_ext, const float *excl3 = nullptr,
-                   bool spacing = false) {
+                   bool spacing = false, const SampleArgs *smp = nullptr) {
     if (int rc = check_ctx(c)) return rc;
     if (mode < SLAMGPU_ASSOC_AUTO || mode > SLAMGPU_ASSOC_GRID) return fail(SLAMGPU_ERR_INVALID, "unknown association mode %d", mode);
     if (stats) stats[0] = stats[1] = stats[2] = stats[3] = 0.0;
@@ -2921,12 +2961,17 @@ int associate_impl(slamgpu_ctx *c, const float *z, int32_t nz, const float R[4],
         return fail(SLAMGPU_ERR_INVALID, "the association grid needs a single context (shards: SLAMGPU_ASSOC_EXHAUSTIVE)");
     const bool excl = excl3 && excl3[0] + excl3[1] > 0.0f;  // (the exclusion rule: the exhaustive scan only)
     if (excl && mode == SLAMGPU_ASSOC_GRID) return fail(SLAMGPU_ERR_INVALID, "the exclusion rule needs SLAMGPU_ASSOC_EXHAUSTIVE (or _AUTO)");
+    if (smp && mode == SLAMGPU_ASSOC_GRID)
+        return fail(SLAMGPU_ERR_INVALID, "data association sampling needs SLAMGPU_ASSOC_EXHAUSTIVE, _AUTO or _LISTS (the grid does not sample)");
+    if (smp && !excl && (double) c->B.n * (double) nz * (double) c->nf > 4e10)
+        return fail(SLAMGPU_ERR_CAPACITY, "data association sampling through the exhaustive scan: %d particles x %d observations x %d landmarks is too "
+                    "much for one launch; take SLAMGPU_ASSOC_LISTS", c->B.n, nz, c->nf);
     // (... and an exhaustive scan is O(N nz Nf): refused where it would run for seconds -- 10^5 particles x 865 observations x 10 000
     // landmarks would be 10^12 gate evaluations in one launch -- instead of looking like a hang)
     if (excl && (double) c->B.n * (double) nz * (double) c->nf > 4e10)
         return fail(SLAMGPU_ERR_CAPACITY, "the exclusion rule scans exhaustively: %d particles x %d observations x %d landmarks is too much for one launch; "
                     "turn it off (excl_base = excl_per_m = 0) on maps of this size", c->B.n, nz, c->nf);
-    bool grid = single && !excl && (mode == SLAMGPU_ASSOC_GRID || (mode == SLAMGPU_ASSOC_AUTO && c->nf >= 64));
+    bool grid = single && !excl && !smp && (mode == SLAMGPU_ASSOC_GRID || (mode == SLAMGPU_ASSOC_AUTO && c->nf >= 64));
     const bool want_vote = consensus || support;
     float *z_dev = nullptr;
     int32_t *lab_dev = nullptr;
@@ -3112,7 +3157,7 @@ int associate_impl(slamgpu_ctx *c, const float *z, int32_t nz, const float R[4],
             if (ev0) step(hipEventRecord(ev0, c->stream), "event");
             {
                 Timed t(c, "associate");
-                c->k->associate(c->stream, c->B, c->nf, z_dev, nz, R, gate_reject, gate_augment, excl3, c->retired_dev, lab_dev, lab_ext ? 1 : 0, rho);
+                c->k->associate(c->stream, c->B, c->nf, z_dev, nz, R, gate_reject, gate_augment, excl3, c->retired_dev, lab_dev, lab_ext ? 1 : 0, rho, smp);
             }
             if (ev1) step(hipEventRecord(ev1, c->stream), "event");
             if (stats) stats[0] = (double) N * (double) nz * (double) c->nf;
@@ -3271,8 +3316,9 @@ int pp_check(slamgpu_ctx *c, const float *z, int32_t nz, const float R[4], const
 
 // One observation step in which every particle acts on ITS OWN association (kernels.h: PerParticle): labels [N][nz] are in
 // c->pp_lab_dev (landmark slot, SLAMGPU_ASSOC_NEW or _DISCARD per particle and observation).
+// (ratio: the sampled pairs' factors, data association sampling -- null: the labels were not sampled)
 int do_update_particle(slamgpu_ctx *c, const float *z, int32_t nz, const float R[4], const slamgpu_particle_assoc *opt, const float *normals,
-                       const float *strata, int32_t report[8]) {
+                       const float *strata, int32_t report[8], const float *ratio = nullptr) {
     if (report) memset(report, 0, sizeof(int32_t) * 8);
     if (int rc = book_pull(c)) return rc;
     if (int rc = flush_predict(c)) return rc;
@@ -3393,10 +3439,11 @@ int do_update_particle(slamgpu_ctx *c, const float *z, int32_t nz, const float R
     {
         Timed t(c, "particle_resolve");
         c->k->pp_resolve(c->stream, c->pp_lab_dev, N, nz, c->B.ncap, first_dev, news_dev, m, n, opt->p_new, c->cfg.log_weights, c->pp_obs_dev,
-                         c->pp_wf_dev, c->pp_any_dev);
+                         c->pp_wf_dev, c->pp_any_dev, ratio);
     }
     HIP_TRY(hipGetLastError());
     c->obs_step++;
+    c->pp_lab_nz = nz;
     // genealogy bookkeeping, as do_update's: every packet entry is written by every particle (updated or copied forward) and moves
     // to the row this update opens
     int e_new = -1;
@@ -3550,7 +3597,7 @@ void lists_args(slamgpu_ctx *c, int nz, const float R[4], const slamgpu_particle
 
 // slamgpu_update_particle's association through the lists: the labels into pp_lab_dev and their census into the context's table, as the
 // grid leaves them (do_update_particle: pp_census_done); nz <= kAssocMaxCells^2, pp_reserve done
-int associate_lists(slamgpu_ctx *c, const float *z, int32_t nz, const float R[4], const slamgpu_particle_assoc *opt) {
+int associate_lists(slamgpu_ctx *c, const float *z, int32_t nz, const float R[4], const slamgpu_particle_assoc *opt, const SampleArgs *smp) {
     c->pp_census_done = false;
     if (int rc = flush_predict(c)) return rc;
     if (int rc = materialize(c)) return rc;  // plain set: particle k in slot k
@@ -3582,7 +3629,7 @@ int associate_lists(slamgpu_ctx *c, const float *z, int32_t nz, const float R[4]
         c->k->lists_geom(c->stream, c->B, G, 0);
         c->k->lists_geom(c->stream, c->B, G, 1);
         c->k->lists_build(c->stream, c->B, G, rho);
-        c->k->lists_walk(c->stream, c->B, G, R, opt->gate_reject, opt->gate_augment, c->pp_lab_dev, rho);
+        c->k->lists_walk(c->stream, c->B, G, R, opt->gate_reject, opt->gate_augment, c->pp_lab_dev, rho, smp);
     }
     HIP_TRY(hipGetLastError());
     for (int j : ids) c->box_dirty[(size_t) j] = 0;
@@ -3619,16 +3666,29 @@ int slamgpu_update_particle(slamgpu_ctx *c, const float *z, int32_t nz, const fl
     const bool spacing = excl_spacing_on(c, opt);
     if (spacing)
         if (int rc = excl_rho_reserve(c, nz)) return rc;
+    // data association sampling: the labels drawn, their ratios into the weights (the step's draws follow the host's obs_step: the
+    // device-driven state comes back first)
+    SampleArgs sa{};
+    const SampleArgs *smp = nullptr;
+    if (c->das_on) {
+        if (opt->mode == SLAMGPU_ASSOC_GRID)
+            return fail(SLAMGPU_ERR_INVALID, "data association sampling needs SLAMGPU_ASSOC_EXHAUSTIVE, _AUTO or _LISTS (the grid does not sample)");
+        if (int rc = das_reserve(c, nz)) return rc;
+        if (int rc = book_pull(c)) return rc;
+        sa = das_args(c, R);
+        smp = &sa;
+    }
+    const float *ratio = smp ? c->das_ratio_dev : nullptr;
     if (opt->mode == SLAMGPU_ASSOC_LISTS) {
         if (int rc = book_pull(c)) return rc;  // (the device-driven state back first: the boxes and the mask are the host's again)
-        if (int rc = associate_lists(c, z, nz, R, opt)) return rc;
-        return do_update_particle(c, z, nz, R, opt, normals, strata, report);
+        if (int rc = associate_lists(c, z, nz, R, opt, smp)) return rc;
+        return do_update_particle(c, z, nz, R, opt, normals, strata, report, ratio);
     }
     const float excl3[3] = {opt->excl_base, opt->excl_per_m, opt->unique_ratio};
     if (int rc = associate_impl(c, z, nz, R, opt->gate_reject, opt->gate_augment, opt->mode, nullptr, nullptr, nullptr, nullptr, c->pp_lab_dev, excl3,
-                                spacing))
+                                spacing, smp))
         return rc;
-    return do_update_particle(c, z, nz, R, opt, normals, strata, report);
+    return do_update_particle(c, z, nz, R, opt, normals, strata, report, ratio);
 }
 
 int slamgpu_update_labels(slamgpu_ctx *c, const float *z, int32_t nz, const float R[4], const int32_t *labels, const slamgpu_particle_assoc *opt,
@@ -3644,7 +3704,7 @@ int slamgpu_update_labels(slamgpu_ctx *c, const float *z, int32_t nz, const floa
             return fail(SLAMGPU_ERR_INVALID, "slamgpu_update_labels: label %d of particle %d, observation %d (%d landmarks)", (int) labels[q], (int) (q / nz), (int) (q % nz), c->nf);
     HIP_TRY(hipSetDevice(c->cfg.device));
     if (int rc = pp_reserve(c, nz, 1)) return rc;
-    c->pp_census_done = false;  // (the caller's labels: nobody has taken their census)
+    c->pp_census_done = false;  // (the caller's labels: nobody has taken their census; never sampled)
     {
         // (the device reads the labels by observation: [nz][ncap])
         const size_t S = (size_t) c->B.ncap;
@@ -3919,6 +3979,10 @@ int pp_dev_iteration(slamgpu_ctx *c, int32_t nc, const float *controls, const fl
     const float excl3[3] = {opt->excl_base, opt->excl_per_m, opt->unique_ratio};
     // (the radii: every observation the map allows, whatever the lists grid; the count comes from the observation)
     const float *rho = excl_spacing_on(c, opt) ? excl_radii(c, c->obs_out_dev, nullptr, 0, (c->map_n + kBlock - 1) / kBlock, excl3) : nullptr;
+    // (data association sampling, as the setting stands now: the walk reads the step from PpState)
+    const SampleArgs sa = das_args(c, R);
+    const SampleArgs *smp = c->das_on ? &sa : nullptr;
+    c->pp_lab_nz = -1;
     if (bound >= 0) {
         // the boxes of the slots the previous iteration wrote, the geometry, one list per observation, the walk (+ the census)
         AssocListArgs G;
@@ -3947,11 +4011,11 @@ int pp_dev_iteration(slamgpu_ctx *c, int32_t nc, const float *controls, const fl
         }
         {
             Timed t(c, "associate");
-            c->k->lists_walk(c->stream, c->B, G, R, opt->gate_reject, opt->gate_augment, c->pp_lab_dev, rho);
+            c->k->lists_walk(c->stream, c->B, G, R, opt->gate_reject, opt->gate_augment, c->pp_lab_dev, rho, smp);
         }
     } else {
         Timed t(c, "associate");
-        c->k->pp_associate(c->stream, c->B, R, opt->gate_reject, opt->gate_augment, excl3, c->pp_lab_dev, P, rho);
+        c->k->pp_associate(c->stream, c->B, R, opt->gate_reject, opt->gate_augment, excl3, c->pp_lab_dev, P, rho, smp);
     }
     {
         Timed t(c, "particle_book");
@@ -3959,7 +4023,7 @@ int pp_dev_iteration(slamgpu_ctx *c, int32_t nc, const float *controls, const fl
     }
     {
         Timed t(c, "particle_resolve");
-        c->k->pp_resolve_dev(c->stream, c->pp_lab_dev, c->B.n, c->B.ncap, P, c->pp_obs_dev, c->pp_wf_dev, c->pp_any_dev);
+        c->k->pp_resolve_dev(c->stream, c->pp_lab_dev, c->B.n, c->B.ncap, P, c->pp_obs_dev, c->pp_wf_dev, c->pp_any_dev, smp ? c->das_ratio_dev : nullptr);
     }
     UpdateArgs U{};
     U.method = c->cfg.method;
@@ -4045,6 +4109,8 @@ int slamgpu_run_particle(slamgpu_ctx *c, int32_t K, const int32_t *n_controls, c
         if (int rc = lists_buffers(c)) return rc;
     if (excl_spacing_on(c, opt))
         if (int rc = excl_rho_reserve(c, c->map_n)) return rc;
+    if (c->das_on)
+        if (int rc = das_reserve(c, c->map_n)) return rc;
     const bool was_host = !c->pp_on_device;
     if (int rc = pp_push(c, c->pp_nz_cap)) return rc;
     bool box_all = false;
@@ -4144,6 +4210,61 @@ int slamgpu_particle_list_stats(slamgpu_ctx *c, int64_t out[4]) {
         HIP_TRY(hipMemcpy(h, c->lstats_dev, sizeof h, hipMemcpyDeviceToHost));
     }
     for (int k = 0; k < 4; k++) out[k] = (int64_t) h[k];
+    return 0;
+}
+
+int slamgpu_set_particle_assoc_sampling(slamgpu_ctx *c, int32_t on) {
+    if (int rc = check_ctx(c)) return rc;
+    if (on != 0 && on != 1) return fail(SLAMGPU_ERR_INVALID, "slamgpu_set_particle_assoc_sampling: on must be 0 or 1 (%d)", (int) on);
+    if (!(c->cfg.flags & SLAMGPU_FLAG_PARTICLE_MAPS))
+        return fail(SLAMGPU_ERR_INVALID, "slamgpu_set_particle_assoc_sampling: create the context with SLAMGPU_FLAG_PARTICLE_MAPS");
+    if (c->cfg.rng_mode == SLAMGPU_RNG_TAPE)
+        return fail(SLAMGPU_ERR_INVALID, "slamgpu_set_particle_assoc_sampling: TAPE-mode contexts replay the reference's draws, which have none for the association");
+    if (!on && c->das_ratio_dev) {  // (the ratios are held only while sampling is on; launches already enqueued may still read them)
+        HIP_TRY(hipSetDevice(c->cfg.device));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        HIP_TRY(hipFree(c->das_ratio_dev));
+        c->das_ratio_dev = nullptr;
+        c->das_ratio_cap = 0;
+    }
+    c->das_on = on;
+    return 0;
+}
+
+int slamgpu_particle_sample_stats(slamgpu_ctx *c, int64_t out[3]) {
+    if (int rc = check_ctx(c)) return rc;
+    if (!out) return fail(SLAMGPU_ERR_INVALID, "slamgpu_particle_sample_stats: null output");
+    unsigned long long h[3] = {0, 0, 0};
+    if (c->das_stats_dev) {
+        HIP_TRY(hipSetDevice(c->cfg.device));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        HIP_TRY(hipMemcpy(h, c->das_stats_dev, sizeof h, hipMemcpyDeviceToHost));
+    }
+    for (int k = 0; k < 3; k++) out[k] = (int64_t) h[k];
+    return 0;
+}
+
+int slamgpu_particle_labels(slamgpu_ctx *c, int32_t *labels, int64_t max_count, int32_t *nz) {
+    if (int rc = check_ctx(c)) return rc;
+    if (!nz || (max_count > 0 && !labels)) return fail(SLAMGPU_ERR_INVALID, "slamgpu_particle_labels: null output");
+    *nz = 0;
+    if (!c->pp_lab_dev || c->pp_lab_nz == 0) return 0;
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    int32_t n = c->pp_lab_nz;
+    if (n < 0) {  // (the device-driven iteration's count)
+        ObserveOut head{};
+        HIP_TRY(hipMemcpy(&head, c->obs_out_dev, sizeof head, hipMemcpyDeviceToHost));
+        n = head.nz;
+    }
+    const size_t S = (size_t) c->B.ncap, N = (size_t) c->B.n;
+    if (n > 0 && max_count > 0) {
+        std::vector<int32_t> t(S * (size_t) n);  // (by observation on the device: [nz][ncap])
+        HIP_TRY(hipMemcpy(t.data(), c->pp_lab_dev, sizeof(int32_t) * t.size(), hipMemcpyDeviceToHost));
+        const size_t count = std::min(N * (size_t) n, (size_t) max_count);
+        for (size_t k = 0; k < count; k++) labels[k] = t[(k % (size_t) n) * S + k / (size_t) n];
+    }
+    *nz = n;
     return 0;
 }
 
