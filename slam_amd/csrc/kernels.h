@@ -655,12 +655,24 @@ struct AssocSampleArgs : AssocRhoArgs {
     SampleArgs smp;
 };
 
+// The association's rule for one call, as the launchers take it (host only: never a kernel argument).  The launchers pick the
+// instantiation from it: the exclusion rule (slamgpu_particle_assoc::excl_*, unique_ratio; excl_base + excl_per_m = 0: off), its radii
+// per observation (excl_radii; may be null, only with the rule on) in place of excl_base + excl_per_m * range, and data association
+// sampling (may be null).
+struct AssocRule {
+    float gate_reject, gate_augment;
+    float excl_base, excl_per_m, unique_ratio;
+    const float *rho;
+    const SampleArgs *smp;
+};
+
 struct KernelTable {
     // the step: [resampling stage of the previous update, inline] + [gather] + [fused predicts] + per-particle observation
     // update + in-block weight prefix / totals  (+ helper blocks: genealogy copy, Ctrl words, estimate reduction)
     void (*update)(hipStream_t, const Buffers &, const PredictArgs &, const UpdateArgs &, const RngArgs &,
                    const WeightScratch &);
-    // the same step with a per-particle association (PerParticle: update_kernel<.., PP = true>; single contexts on plain rows)
+    // the same step with a per-particle association (PerParticle: update_kernel<.., PP = true>; single contexts on plain rows); driven
+    // by the device when PerParticle::obs_dev is set (update_kernel<.., PPD = true>; no observation: nothing)
     void (*update_particle)(hipStream_t, const Buffers &, const PredictArgs &, const UpdateArgs &, const RngArgs &, const WeightScratch &,
                             const PerParticle &);
     // K steps of a compact single context in ONE launch (PersistArgs): U = what every iteration shares (front end on: the map, R)
@@ -699,11 +711,10 @@ struct KernelTable {
     // per-particle gated nearest-neighbour association of nz observations against every landmark of every particle
     // (slamgpu_associate): labels [n][nz] = landmark index, kAssocNew or kAssocDiscard.  Plain set required (no pending gather).
     // retired (may be null): bit j set = landmark j takes no part (slamgpu_retire_landmarks)
-    // excl3 (may be null): excl_base, excl_per_m, unique_ratio of the exclusion rule (slamgpu_particle_assoc; base + per_m = 0: off)
-    // rho_dev (may be null; only with the rule on): the rule's radius per observation (excl_radii) in place of excl_base + excl_per_m * range
-    void (*associate)(hipStream_t, const Buffers &, int nf, const float *z_dev, int nz, const float *R4, float gate_reject,
-                      float gate_augment, const float *excl3, const uint32_t *retired_dev, int32_t *labels_dev, int labels_by_obs,
-                      const float *rho_dev, const SampleArgs *smp);
+    // dev (may be null): device-driven (slamgpu_run_particle): nz, nf and z from PpArgs (pass 0, null, 0 and PpArgs::retired); the
+    // census of the labels and, when due, of the holders ride in the launch (no observation: the estimate partials instead)
+    void (*associate)(hipStream_t, const Buffers &, int nf, const float *z_dev, int nz, const float *R4, const AssocRule &,
+                      const uint32_t *retired_dev, int32_t *labels_dev, int labels_by_obs, const PpArgs *dev);
     // seq_out != null: `out` and `seq_out` are pinned host memory; the kernel stores `seq` there last (system-scope fence)
     void (*shard_plan)(hipStream_t, const ShardPlanArgs &, const RngArgs &, ShardPlan *out, uint32_t *seq_out, uint32_t seq);
     void (*shard_pack)(hipStream_t, const Buffers &, const WeightScratch &, const ShardPackArgs &, const RngArgs &);
@@ -732,33 +743,26 @@ struct KernelTable {
     // to INT_MAX; news[j]: particles calling observation j new, preset to 0), the labels resolved into PerParticle::obs / wf / any, and
     // the number of particles that hold each landmark slot (holders[l], preset to 0; plain set, tables in sync)
     void (*pp_census)(hipStream_t, const int32_t *labels_dev, int n, int nz, int ncap, int32_t *first_dev, int32_t *news_dev);
+    // (dev, may be null: device-driven -- nz, m and nn from the observation and the packet pp_book_kernel wrote: pass 0, 0, 0)
     void (*pp_resolve)(hipStream_t, const int32_t *labels_dev, int n, int nz, int ncap, const int32_t *uidx_dev, const int32_t *newk_dev, int m, int nn,
-                       float p_new, int logw, int16_t *obs_dev, float *wf_dev, uint8_t *any_dev, const float *ratio_dev);
+                       float p_new, int logw, int16_t *obs_dev, float *wf_dev, uint8_t *any_dev, const float *ratio_dev, const PpArgs *dev);
     void (*pp_holders)(hipStream_t, const Buffers &, int count, const int32_t *ids_dev, int32_t *holders_dev);  // ids (may be null: 0 .. count - 1)
     // slamgpu_run_particle: one iteration's stages, every size read from device memory (PpArgs).  resample: the outstanding resampling
     // stage of the previous iteration, if it updated (resample_kernel<true>); gather: the lazy gather over the rows in use, and in one
-    // more block the estimate of that stage; associate: the exhaustive scan with the label and holders census in the launch (no
-    // observation: the estimate partials instead); book: the bookkeeping, packet and report (no observation: the estimate); resolve:
-    // pp_resolve with the packet's sizes; update_particle_dev: update_kernel<.., PPD = true> (no observation: nothing)
+    // more block the estimate of that stage; book: the bookkeeping, packet and report (no observation: the estimate).  The association,
+    // the resolve and the update take the device-driven path of `associate`, `pp_resolve` and `update_particle`
     void (*pp_resample)(hipStream_t, const Buffers &, const WeightScratch &, const RngArgs &, const ResampleArgs &, const PpArgs &);
     void (*pp_gather)(hipStream_t, const Buffers &, const WeightScratch &, const PpArgs &, double *hist, int par);
-    void (*pp_associate)(hipStream_t, const Buffers &, const float *R4, float gate_reject, float gate_augment, const float *excl3, int32_t *labels_dev,
-                         const PpArgs &, const float *rho_dev, const SampleArgs *smp);
     void (*pp_book)(hipStream_t, const Buffers &, const PpArgs &);
-    void (*pp_resolve_dev)(hipStream_t, const int32_t *labels_dev, int n, int ncap, const PpArgs &, int16_t *obs_dev, float *wf_dev, uint8_t *any_dev,
-                           const float *ratio_dev);
-    void (*update_particle_dev)(hipStream_t, const Buffers &, const PredictArgs &, const UpdateArgs &, const RngArgs &, const WeightScratch &,
-                                const PerParticle &);
     // SLAMGPU_ASSOC_LISTS, one launch each.  lists_box: the boxes of the slots the previous iteration's update rewrote or opened (the
     // packet pp_book_kernel left; all: slots 0 .. nf - 1), `blocks` workgroups walking them; lists_geom: stage 0 the partial pose boxes,
     // 1 the geometry; lists_build: one candidate list per observation; lists_walk: the labels (+ the census of the labels, and in a
     // device-driven iteration the holders census or the estimate partials).  Device-driven: AssocListArgs::obs set.
     void (*lists_box)(hipStream_t, const Buffers &, const PpArgs &, int all, int blocks, LmkBox *box_dev);
     void (*lists_geom)(hipStream_t, const Buffers &, const AssocListArgs &, int stage);
-    // (rho_dev, may be null: as `associate`'s; the lists' reach for the rule follows it)
-    void (*lists_build)(hipStream_t, const Buffers &, const AssocListArgs &, const float *rho_dev);
-    void (*lists_walk)(hipStream_t, const Buffers &, const AssocListArgs &, const float *R4, float gate_reject, float gate_augment, int32_t *labels_dev,
-                       const float *rho_dev, const SampleArgs *smp);
+    // (the lists' reach for the exclusion rule follows the rule's radii, when it has them)
+    void (*lists_build)(hipStream_t, const Buffers &, const AssocListArgs &, const AssocRule &);
+    void (*lists_walk)(hipStream_t, const Buffers &, const AssocListArgs &, const float *R4, const AssocRule &, int32_t *labels_dev);
     // the exclusion rule's radius per observation from the step's observation spacing (slamgpu_set_particle_excl_spacing):
     // rho[q] = min(excl_base + excl_per_m r_q, f s_q), s_q the distance from (r_q cos b_q, r_q sin b_q) to the nearest other such point
     // of the step (+inf for one observation); *rho_nz = nz.  obs null: z_dev / nz from the host; else nz and z from the iteration's

@@ -4145,6 +4145,32 @@ __global__ void __launch_bounds__(kBlock) pp_book_kernel(Buffers B, PpArgs P) {
 // ---------------------------------------------------------------------------------------------------
 // launchers
 // ---------------------------------------------------------------------------------------------------
+// Runtime flags to template arguments: dispatch<N...>(f, v...) calls f(Flag<v>{}...), each flag v in [0, N) (a bool: N = 2) as a
+// compile-time constant, through one instantiation of the generic lambda f per combination.  f drops the combinations that must not
+// exist (if constexpr) before it names a kernel: they instantiate nothing.
+template <int V>
+using Flag = std::integral_constant<int, V>;
+template <int N, class G>
+static void bind_flag(int v, G &g) {  // g(Flag<v>{}); v outside [0, N): Flag<0>
+    if constexpr (N == 1) g(Flag<0>{});
+    else if (v == N - 1) g(Flag<N - 1>{});
+    else bind_flag<N - 1>(v, g);
+}
+template <int N0, int... N, class F, class... Bound>
+static void dispatch_from(F &f, const int *v, Bound... bound) {
+    auto next = [&](auto k) {
+        if constexpr (sizeof...(N) == 0) f(bound..., k);
+        else dispatch_from<N...>(f, v + 1, bound..., k);
+    };
+    bind_flag<N0>(*v, next);
+}
+template <int... N, class F, class... V>
+static void dispatch(F &&f, V... v) {
+    static_assert(sizeof...(N) == sizeof...(V), "a range per flag");
+    const int vs[] = {(int) v...};
+    dispatch_from<N...>(f, vs);
+}
+
 static void launch_shard_plan(hipStream_t st, const ShardPlanArgs &A, const RngArgs &rng, ShardPlan *out, uint32_t *seq_out,
                               uint32_t seq) {
     const size_t lds = sizeof(double) * ((size_t) A.nb_global + 1);
@@ -4172,17 +4198,16 @@ static void launch_shard_finish(hipStream_t st, const Buffers &B, const WeightSc
 }
 
 static void launch_update_any(hipStream_t st, const Buffers &B, const PredictArgs &PA, const UpdateArgs &U,
-                              const RngArgs &rng, const WeightScratch &ws, const PerParticle &ppa, bool ppd = false) {
+                              const RngArgs &rng, const WeightScratch &ws, const PerParticle &ppa) {
     // compute blocks first (they are the long pole), then -- single-context pipeline only -- the copy blocks of a
     // pending lazy gather (they exit at once when nothing is pending: the host cannot know) and one helper block
     int grid = B.ncap / kBlock;
     if (U.lazy) grid += (U.copy_hi - U.copy_lo) + 1;
     // inline plan only: prefix of the previous step's block totals (launches that do not plan never touch off[])
     const size_t nbg = (size_t) ws.nblocks * (U.arrivals == 2 ? (size_t) B.n_shards : 1);  // distributed: blocks of all shards
-    const size_t lds = (size_t) staging_slots(U.method, U.big != nullptr, U.m) * kBlock * (sizeof(float4) + sizeof(float)) +
-                       ((U.plan_inline && !U.scan_global) ? sizeof(double) * ((nbg + 3) & ~(size_t) 1) : 0) +
-                       (U.plan_inline ? update_window_bytes() : 0);
-    const int sel = (U.method == 2 ? 6 : 0) + 2 * U.arrivals + (U.big ? 1 : 0);
+    size_t lds = (size_t) staging_slots(U.method, U.big != nullptr, U.m) * kBlock * (sizeof(float4) + sizeof(float)) +
+                 ((U.plan_inline && !U.scan_global) ? sizeof(double) * ((nbg + 3) & ~(size_t) 1) : 0) +
+                 (U.plan_inline ? update_window_bytes() : 0);
     const float *h_tot = U.arrivals == 2 ? B.gtot[ws.wpar ^ 1] : ws.blk_w[ws.wpar ^ 1];
     // bit 5: distributed contexts: the gathered table is wider than two totals per thread and fits the LDS behind the block prefix
     // (ancestor windows + landmark staging): the scan fetches it by LDS-DMA (scan_issue_dma)
@@ -4190,49 +4215,32 @@ static void launch_update_any(hipStream_t st, const Buffers &B, const PredictArg
     const bool scan_dma = U.arrivals == 2 && U.plan_inline && !U.scan_global && !U.logw && nbg > 2 * (size_t) kBlock &&
                           2 * sizeof(float) * (((nbg + 255) / 256) * 256) <= update_window_bytes() + stage_bytes;
     const int h_flags = (U.plan_inline ? 1 : 0) | (U.scan_global ? 2 : 0) | (U.logw ? 4 : 0) | (U.lazy ? 8 : 0) | (U.front.on ? 16 : 0) | (scan_dma ? 32 : 0) | (U.count_remote ? 64 : 0);
-#define SLAM_LAUNCH_UPDATE(M, A, G)                                                                                              \
-    hipLaunchKernelGGL((update_kernel<M, A, G>), dim3(grid), dim3(kBlock), lds, st, h_tot, B.ctrl, U.front.state_in, ws.nblocks, B.slot, grid, \
-                       h_flags, B, PA, U, rng, ws, ppa)
     if (update_is_wide(U.method, U.arrivals, U.big != nullptr, ws.nblocks)) {  // (FastSLAM 1, single context, compact layout, more tiles than two rounds of CUs)
         hipLaunchKernelGGL((update_kernel_wide<1>), dim3(grid), dim3(kBlock), lds, st, h_tot, B.ctrl, U.front.state_in, ws.nblocks, B.slot, grid,
                            h_flags, B, PA, U, rng, ws);
         return;
     }
-    if (ppa.obs) {  // per-particle association (slamgpu.cpp: do_update_particle guarantees a single context on plain rows)
+    // per-particle association (slamgpu.cpp: do_update_particle guarantees a single context on plain rows: MODE 0, BIG; obs_dev: driven
+    // by the device)
+    const bool pp = ppa.obs != nullptr;
+    PerParticle pq = ppa;
+    if (pp) {
         // + the staged observation indices (update_step.inl: shJ) and, when they fit, the observations (shZ)
-        PerParticle pq = ppa;
+        // (device-driven: pq.nz is the map's size, an upper bound of the device's count: LDS for that many)
         pq.z_lds = pq.nz <= kPpLdsObs ? 1 : 0;
-        const size_t lds_pp = lds + (size_t) kBigChunk * kBlock * sizeof(int32_t) + (pq.z_lds ? sizeof(float) * 2 * (size_t) pq.nz : 0);
-        // (ppd: pq.nz is the map's size, an upper bound of the device's count: LDS for that many)
-        if (ppd && U.method == 2) hipLaunchKernelGGL((update_kernel<2, 0, true, true, true>), dim3(grid), dim3(kBlock), lds_pp, st, h_tot, B.ctrl, U.front.state_in, ws.nblocks, B.slot, grid, h_flags, B, PA, U, rng, ws, pq);
-        else if (ppd) hipLaunchKernelGGL((update_kernel<1, 0, true, true, true>), dim3(grid), dim3(kBlock), lds_pp, st, h_tot, B.ctrl, U.front.state_in, ws.nblocks, B.slot, grid, h_flags, B, PA, U, rng, ws, pq);
-        else if (U.method == 2) hipLaunchKernelGGL((update_kernel<2, 0, true, true>), dim3(grid), dim3(kBlock), lds_pp, st, h_tot, B.ctrl, U.front.state_in, ws.nblocks, B.slot, grid, h_flags, B, PA, U, rng, ws, pq);
-        else hipLaunchKernelGGL((update_kernel<1, 0, true, true>), dim3(grid), dim3(kBlock), lds_pp, st, h_tot, B.ctrl, U.front.state_in, ws.nblocks, B.slot, grid, h_flags, B, PA, U, rng, ws, pq);
-        return;
+        lds += (size_t) kBigChunk * kBlock * sizeof(int32_t) + (pq.z_lds ? sizeof(float) * 2 * (size_t) pq.nz : 0);
     }
-    switch (sel) {
-        case 11: SLAM_LAUNCH_UPDATE(2, 2, true); break;
-        case 10: SLAM_LAUNCH_UPDATE(2, 2, false); break;
-        case 9: SLAM_LAUNCH_UPDATE(2, 1, true); break;
-        case 8: SLAM_LAUNCH_UPDATE(2, 1, false); break;
-        case 7: SLAM_LAUNCH_UPDATE(2, 0, true); break;
-        case 6: SLAM_LAUNCH_UPDATE(2, 0, false); break;
-        case 5: SLAM_LAUNCH_UPDATE(1, 2, true); break;
-        case 4: SLAM_LAUNCH_UPDATE(1, 2, false); break;
-        case 3: SLAM_LAUNCH_UPDATE(1, 1, true); break;
-        case 2: SLAM_LAUNCH_UPDATE(1, 1, false); break;
-        case 1: SLAM_LAUNCH_UPDATE(1, 0, true); break;
-        default: SLAM_LAUNCH_UPDATE(1, 0, false); break;
-    }
-#undef SLAM_LAUNCH_UPDATE
+    dispatch<2, 3, 2, 2, 2>(
+        [&](auto fs2, auto mode, auto big, auto ppt, auto ppd) {
+            if constexpr ((!ppt || (big && mode == 0)) && (!ppd || ppt))
+                hipLaunchKernelGGL((update_kernel<fs2 ? 2 : 1, mode, big, ppt, ppd>), dim3(grid), dim3(kBlock), lds, st, h_tot, B.ctrl, U.front.state_in,
+                                   ws.nblocks, B.slot, grid, h_flags, B, PA, U, rng, ws, pq);
+        },
+        U.method == 2, pp ? 0 : U.arrivals, pp || U.big != nullptr, pp, pp && ppa.obs_dev != nullptr);
 }
 
 static void launch_update(hipStream_t st, const Buffers &B, const PredictArgs &PA, const UpdateArgs &U, const RngArgs &rng, const WeightScratch &ws) {
     launch_update_any(st, B, PA, U, rng, ws, PerParticle{});
-}
-static void launch_update_particle(hipStream_t st, const Buffers &B, const PredictArgs &PA, const UpdateArgs &U, const RngArgs &rng,
-                                   const WeightScratch &ws, const PerParticle &ppa) {
-    launch_update_any(st, B, PA, U, rng, ws, ppa);
 }
 
 // K iterations in one launch (kernels.h: PersistArgs): kPersistStride x (tiles + 1 helper) workgroups, of which every
@@ -4243,12 +4251,12 @@ static void launch_update_persist(hipStream_t st, const Buffers &B, const Predic
     const size_t lds = (size_t) staging_slots(U.method, false, U.m) * kBlock * (sizeof(float4) + sizeof(float)) +
                        sizeof(double) * (((size_t) ws.nblocks + 3) & ~(size_t) 1) + update_window_bytes();
     const int h_flags = 1 | (U.logw ? 4 : 0) | 8 | 16;
-    if (U.method == 2)
-        hipLaunchKernelGGL((update_persist_kernel<2>), dim3(grid), dim3(kBlock), lds, st, ws.blk_w[ws.wpar ^ 1], B.ctrl, U.front.state_in, ws.nblocks, B.slot, grid,
-                           h_flags, B, PA, U, rng, ws);
-    else
-        hipLaunchKernelGGL((update_persist_kernel<1>), dim3(grid), dim3(kBlock), lds, st, ws.blk_w[ws.wpar ^ 1], B.ctrl, U.front.state_in, ws.nblocks, B.slot, grid,
-                           h_flags, B, PA, U, rng, ws);
+    dispatch<2>(
+        [&](auto fs2) {
+            hipLaunchKernelGGL((update_persist_kernel<fs2 ? 2 : 1>), dim3(grid), dim3(kBlock), lds, st, ws.blk_w[ws.wpar ^ 1], B.ctrl, U.front.state_in,
+                               ws.nblocks, B.slot, grid, h_flags, B, PA, U, rng, ws);
+        },
+        U.method == 2);
 }
 
 static void launch_resample(hipStream_t st, const Buffers &B, const WeightScratch &ws, const RngArgs &rng,
@@ -4332,30 +4340,26 @@ static void launch_observe_book(hipStream_t st, const ObserveArgs &A) {
     hipLaunchKernelGGL(observe_book_kernel, dim3(1), dim3(kObsThreads), 0, st, A);
 }
 
-static void launch_associate(hipStream_t st, const Buffers &B, int nf, const float *z, int nz, const float *R4, float g1, float g2, const float *excl3,
-                             const uint32_t *retired, int32_t *labels, int by_obs, const float *rho, const SampleArgs *smp) {
-    if (smp) {  // (data association sampling: the labels by observation)
-        const PpSampleArgs P{PpRhoArgs{PpArgs{}, rho}, *smp};
-        const bool excl = excl3 && excl3[0] + excl3[1] > 0.0f;
-        const float e0 = excl ? excl3[0] : 0.0f, e1 = excl ? excl3[1] : 0.0f, e2 = excl ? excl3[2] : 0.0f;
-        if (excl && rho)
-            hipLaunchKernelGGL((associate_kernel<true, false, true, true>), dim3(B.ncap / kBlock), dim3(kBlock), 0, st, B, nf, z, nz, R4[0], R4[1], R4[2], R4[3], g1, g2,
-                               e0, e1, e2, retired, labels, 1, P);
-        else if (excl)
-            hipLaunchKernelGGL((associate_kernel<true, false, false, true>), dim3(B.ncap / kBlock), dim3(kBlock), 0, st, B, nf, z, nz, R4[0], R4[1], R4[2], R4[3], g1,
-                               g2, e0, e1, e2, retired, labels, 1, P);
-        else
-            hipLaunchKernelGGL((associate_kernel<false, false, false, true>), dim3(B.ncap / kBlock), dim3(kBlock), 0, st, B, nf, z, nz, R4[0], R4[1], R4[2], R4[3], g1,
-                               g2, e0, e1, e2, retired, labels, 1, P);
-    } else if (excl3 && excl3[0] + excl3[1] > 0.0f && rho)
-        hipLaunchKernelGGL((associate_kernel<true, false, true>), dim3(B.ncap / kBlock), dim3(kBlock), 0, st, B, nf, z, nz, R4[0], R4[1], R4[2], R4[3], g1, g2,
-                           excl3[0], excl3[1], excl3[2], retired, labels, by_obs, PpRhoArgs{PpArgs{}, rho});
-    else if (excl3 && excl3[0] + excl3[1] > 0.0f)
-        hipLaunchKernelGGL((associate_kernel<true, false>), dim3(B.ncap / kBlock), dim3(kBlock), 0, st, B, nf, z, nz, R4[0], R4[1], R4[2], R4[3], g1, g2, excl3[0],
-                           excl3[1], excl3[2], retired, labels, by_obs, PpArgs{});
-    else
-        hipLaunchKernelGGL((associate_kernel<false, false>), dim3(B.ncap / kBlock), dim3(kBlock), 0, st, B, nf, z, nz, R4[0], R4[1], R4[2], R4[3], g1, g2, 0.0f, 0.0f,
-                           0.0f, retired, labels, by_obs, PpArgs{});
+// the derived argument structs of the association kernels' instantiations (kernels.h: PpRhoArgs, PpSampleArgs): a launcher fills the
+// widest and hands each instantiation its own part
+template <bool RHO, bool SAMPLE>
+using PpAssocArgs = std::conditional_t<SAMPLE, PpSampleArgs, std::conditional_t<RHO, PpRhoArgs, PpArgs>>;
+static bool excl_on(const AssocRule &rule) { return rule.excl_base + rule.excl_per_m > 0.0f; }
+
+static void launch_associate(hipStream_t st, const Buffers &B, int nf, const float *z, int nz, const float *R4, const AssocRule &rule,
+                             const uint32_t *retired, int32_t *labels, int by_obs, const PpArgs *dev) {
+    const bool excl = excl_on(rule);
+    const float *rho = excl ? rule.rho : nullptr;
+    const PpSampleArgs P{PpRhoArgs{dev ? *dev : PpArgs{}, rho}, rule.smp ? *rule.smp : SampleArgs{}};
+    // (the exclusion floats are zero with the rule off; sampling lays the labels out by observation)
+    dispatch<2, 2, 2, 2>(
+        [&](auto EXCL, auto DEV, auto RHO, auto SAMPLE) {
+            if constexpr (EXCL || !RHO)
+                hipLaunchKernelGGL((associate_kernel<EXCL, DEV, RHO, SAMPLE>), dim3(B.ncap / kBlock), dim3(kBlock), 0, st, B, nf, z, nz, R4[0], R4[1], R4[2],
+                                   R4[3], rule.gate_reject, rule.gate_augment, EXCL ? rule.excl_base : 0.0f, EXCL ? rule.excl_per_m : 0.0f,
+                                   EXCL ? rule.unique_ratio : 0.0f, retired, labels, SAMPLE ? 1 : by_obs, (const PpAssocArgs<RHO, SAMPLE> &) P);
+        },
+        excl, dev != nullptr, rho != nullptr, rule.smp != nullptr);
 }
 
 static void launch_kat(hipStream_t st, int op, const float *in, int n, float *out) {
@@ -4465,12 +4469,12 @@ __global__ void __launch_bounds__(kWave) vote_compact_kernel(AssocGridArgs A) {
 static void launch_vote_compact(hipStream_t st, const AssocGridArgs &A) { hipLaunchKernelGGL(vote_compact_kernel, dim3(A.nz), dim3(kWave), 0, st, A); }
 
 static void launch_associate_grid(hipStream_t st, const Buffers &B, const AssocGridArgs &A, const float *R4, float g1, float g2, int32_t *labels) {
-    if (A.lcap > 0)
-        hipLaunchKernelGGL(associate_grid_kernel<true>, dim3(B.ncap / kBlock, (A.nz + A.obs_per_block - 1) / A.obs_per_block), dim3(kBlock), 0, st, B, A,
-                           R4[0], R4[1], R4[2], R4[3], g1, g2, labels);
-    else
-        hipLaunchKernelGGL(associate_grid_kernel<false>, dim3(B.ncap / kBlock, (A.nz + A.obs_per_block - 1) / A.obs_per_block), dim3(kBlock), 0, st, B, A,
-                           R4[0], R4[1], R4[2], R4[3], g1, g2, labels);
+    dispatch<2>(
+        [&](auto LISTS) {
+            hipLaunchKernelGGL(associate_grid_kernel<LISTS>, dim3(B.ncap / kBlock, (A.nz + A.obs_per_block - 1) / A.obs_per_block), dim3(kBlock), 0, st, B, A,
+                               R4[0], R4[1], R4[2], R4[3], g1, g2, labels);
+        },
+        A.lcap > 0);
 }
 static void launch_assoc_lists(hipStream_t st, const Buffers &B, const AssocGridArgs &A) {
     hipLaunchKernelGGL(assoc_geom_partial_kernel, dim3(kGeomBlocks), dim3(kBlock), 0, st, B, A.geom_part);
@@ -4643,24 +4647,28 @@ static void launch_pp_census(hipStream_t st, const int32_t *labels, int n, int n
     hipLaunchKernelGGL(pp_census_kernel, dim3((n + kBlock - 1) / kBlock, (nz + kCensusObs - 1) / kCensusObs), dim3(kBlock), 0, st, labels, n, nz, (size_t) ncap, first, news);
 }
 static void launch_pp_resolve(hipStream_t st, const int32_t *labels, int n, int nz, int ncap, const int32_t *uidx, const int32_t *newk, int m, int nn,
-                              float p_new, int logw, int16_t *obs, float *wf, uint8_t *any, const float *ratio) {
+                              float p_new, int logw, int16_t *obs, float *wf, uint8_t *any, const float *ratio, const PpArgs *dev) {
     // claimed-entry bits in LDS while the packet's re-observed entries fit 48 KB of them (m <= 1 536: every step of the 10 000-landmark map)
-    const int words = (m + 31) / 32, lds_words = words * kBlock * 4 <= 48 * 1024 ? words : 0;
-    if (ratio)
-        hipLaunchKernelGGL((pp_resolve_kernel<false, float>), dim3(ncap / kBlock), dim3(kBlock), (size_t) lds_words * kBlock * sizeof(uint32_t), st, labels, n, nz,
-                           (size_t) ncap, uidx, newk, m, nn, p_new, logw, lds_words, obs, wf, any, (const ObsPacket *) nullptr, (const ObserveOut *) nullptr, ratio);
-    else
-        hipLaunchKernelGGL(pp_resolve_kernel<false>, dim3(ncap / kBlock), dim3(kBlock), (size_t) lds_words * kBlock * sizeof(uint32_t), st, labels, n, nz, (size_t) ncap, uidx,
-                           newk, m, nn, p_new, logw, lds_words, obs, wf, any, nullptr, nullptr);
+    // (device-driven: the packet's entries are at most cap_nf: the bits for that many, when they fit)
+    const int words = ((dev ? dev->cap_nf : m) + 31) / 32, lds_words = words * kBlock * 4 <= 48 * 1024 ? words : 0;
+    const ObsPacket *pkt = dev ? dev->pkt : nullptr;
+    const ObserveOut *obs_out = dev ? dev->obs : nullptr;
+    dispatch<2, 2>(
+        [&](auto DEV, auto SAMPLE) {
+            auto launch = [&](auto... r) {  // (sampling: the ratios, one argument more -- pp_resolve_kernel's Ratio pack)
+                hipLaunchKernelGGL((pp_resolve_kernel<DEV, std::remove_const_t<std::remove_pointer_t<decltype(r)>>...>), dim3(ncap / kBlock), dim3(kBlock),
+                                   (size_t) lds_words * kBlock * sizeof(uint32_t), st, labels, n, nz, (size_t) ncap, uidx, newk, m, nn, p_new, logw, lds_words,
+                                   obs, wf, any, pkt, obs_out, r...);
+            };
+            if constexpr (SAMPLE) launch(ratio);
+            else launch();
+        },
+        dev != nullptr, ratio != nullptr);
 }
 static void launch_pp_holders(hipStream_t st, const Buffers &B, int count, const int32_t *ids, int32_t *holders) {
     hipLaunchKernelGGL(pp_holders_kernel, dim3(B.ncap / kBlock), dim3(kBlock), 0, st, B, count, ids, holders);
 }
 
-static void launch_update_particle_dev(hipStream_t st, const Buffers &B, const PredictArgs &PA, const UpdateArgs &U, const RngArgs &rng,
-                                       const WeightScratch &ws, const PerParticle &ppa) {
-    launch_update_any(st, B, PA, U, rng, ws, ppa, true);
-}
 static void launch_pp_resample(hipStream_t st, const Buffers &B, const WeightScratch &ws, const RngArgs &rng, const ResampleArgs &ra, const PpArgs &P) {
     const size_t lds = sizeof(double) * ((size_t) ws.nblocks + 1);
     hipLaunchKernelGGL(resample_kernel<true>, dim3(ws.nblocks), dim3(kBlock), lds, st, B, ws, rng, ra, UpdateArgs{}, (const PpState *) P.st);
@@ -4669,44 +4677,7 @@ static void launch_pp_gather(hipStream_t st, const Buffers &B, const WeightScrat
     const int gy = (P.cap_rows + kRowsPerRole - 1) / kRowsPerRole;  // (rows in use: at most cap_rows; the groups past the count leave at once)
     hipLaunchKernelGGL(pp_gather_kernel, dim3(ws.nblocks + 1, gy), dim3(kBlock), 0, st, B, ws, P, hist, par);
 }
-static void launch_pp_associate(hipStream_t st, const Buffers &B, const float *R4, float g1, float g2, const float *excl3, int32_t *labels, const PpArgs &P,
-                                const float *rho, const SampleArgs *smp) {
-    if (smp) {  // (data association sampling)
-        const PpSampleArgs PS{PpRhoArgs{P, rho}, *smp};
-        const bool excl = excl3 && excl3[0] + excl3[1] > 0.0f;
-        const float e0 = excl ? excl3[0] : 0.0f, e1 = excl ? excl3[1] : 0.0f, e2 = excl ? excl3[2] : 0.0f;
-        if (excl && rho)
-            hipLaunchKernelGGL((associate_kernel<true, true, true, true>), dim3(B.ncap / kBlock), dim3(kBlock), 0, st, B, 0, (const float *) nullptr, 0, R4[0], R4[1],
-                               R4[2], R4[3], g1, g2, e0, e1, e2, (const uint32_t *) P.retired, labels, 1, PS);
-        else if (excl)
-            hipLaunchKernelGGL((associate_kernel<true, true, false, true>), dim3(B.ncap / kBlock), dim3(kBlock), 0, st, B, 0, (const float *) nullptr, 0, R4[0], R4[1],
-                               R4[2], R4[3], g1, g2, e0, e1, e2, (const uint32_t *) P.retired, labels, 1, PS);
-        else
-            hipLaunchKernelGGL((associate_kernel<false, true, false, true>), dim3(B.ncap / kBlock), dim3(kBlock), 0, st, B, 0, (const float *) nullptr, 0, R4[0], R4[1],
-                               R4[2], R4[3], g1, g2, e0, e1, e2, (const uint32_t *) P.retired, labels, 1, PS);
-    } else if (excl3 && excl3[0] + excl3[1] > 0.0f && rho)
-        hipLaunchKernelGGL((associate_kernel<true, true, true>), dim3(B.ncap / kBlock), dim3(kBlock), 0, st, B, 0, (const float *) nullptr, 0, R4[0], R4[1], R4[2], R4[3],
-                           g1, g2, excl3[0], excl3[1], excl3[2], (const uint32_t *) P.retired, labels, 1, PpRhoArgs{P, rho});
-    else if (excl3 && excl3[0] + excl3[1] > 0.0f)
-        hipLaunchKernelGGL((associate_kernel<true, true>), dim3(B.ncap / kBlock), dim3(kBlock), 0, st, B, 0, (const float *) nullptr, 0, R4[0], R4[1], R4[2], R4[3], g1,
-                           g2, excl3[0], excl3[1], excl3[2], (const uint32_t *) P.retired, labels, 1, P);
-    else
-        hipLaunchKernelGGL((associate_kernel<false, true>), dim3(B.ncap / kBlock), dim3(kBlock), 0, st, B, 0, (const float *) nullptr, 0, R4[0], R4[1], R4[2], R4[3], g1,
-                           g2, 0.0f, 0.0f, 0.0f, (const uint32_t *) P.retired, labels, 1, P);
-}
 static void launch_pp_book(hipStream_t st, const Buffers &B, const PpArgs &P) { hipLaunchKernelGGL(pp_book_kernel, dim3(1), dim3(kBlock), 0, st, B, P); }
-static void launch_pp_resolve_dev(hipStream_t st, const int32_t *labels, int n, int ncap, const PpArgs &P, int16_t *obs, float *wf, uint8_t *any,
-                                  const float *ratio) {
-    // (the packet's entries are at most cap_nf: the claimed-entry bits for that many, when they fit)
-    const int words = (P.cap_nf + 31) / 32, lds_words = words * kBlock * 4 <= 48 * 1024 ? words : 0;
-    if (ratio)
-        hipLaunchKernelGGL((pp_resolve_kernel<true, float>), dim3(ncap / kBlock), dim3(kBlock), (size_t) lds_words * kBlock * sizeof(uint32_t), st, labels, n, 0,
-                           (size_t) ncap, (const int32_t *) P.uidx, (const int32_t *) P.newk, 0, 0, P.p_new, P.logw, lds_words, obs, wf, any, (const ObsPacket *) P.pkt,
-                           (const ObserveOut *) P.obs, ratio);
-    else
-        hipLaunchKernelGGL(pp_resolve_kernel<true>, dim3(ncap / kBlock), dim3(kBlock), (size_t) lds_words * kBlock * sizeof(uint32_t), st, labels, n, 0, (size_t) ncap,
-                           (const int32_t *) P.uidx, (const int32_t *) P.newk, 0, 0, P.p_new, P.logw, lds_words, obs, wf, any, (const ObsPacket *) P.pkt, P.obs);
-}
 
 // SLAMGPU_ASSOC_LISTS (kernels.h: KernelTable::lists_*); A.nz: the observations (DEV: the host's bound on them, >= 1)
 static void launch_lists_box(hipStream_t st, const Buffers &B, const PpArgs &P, int all, int blocks, LmkBox *box) {
@@ -4714,63 +4685,46 @@ static void launch_lists_box(hipStream_t st, const Buffers &B, const PpArgs &P, 
 }
 static void launch_lists_geom(hipStream_t st, const Buffers &B, const AssocListArgs &A, int stage) {
     if (stage == 0) hipLaunchKernelGGL(assoc_geom_partial_kernel, dim3(kGeomBlocks), dim3(kBlock), 0, st, B, A.geom_part);
-    else if (A.obs) hipLaunchKernelGGL(assoc_geom_kernel<true>, dim3(1), dim3(kBlock), 0, st, B, A, A.geom_part);
-    else hipLaunchKernelGGL(assoc_geom_kernel<false>, dim3(1), dim3(kBlock), 0, st, B, (const AssocGridArgs &) A, A.geom_part);
-}
-static void launch_lists_build(hipStream_t st, const Buffers &B, const AssocListArgs &A, const float *rho) {
-    const bool excl = A.excl_base + A.excl_per_m > 0.0f;
-    if (excl && rho && A.obs)
-        hipLaunchKernelGGL((assoc_lists_kernel<true, true, true>), dim3(A.nz), dim3(kBlock), 0, st, AssocRhoArgs{A, rho}, B.erow, B.lmk_live);
-    else if (excl && rho)
-        hipLaunchKernelGGL((assoc_lists_kernel<true, false, true>), dim3(A.nz), dim3(kBlock), 0, st, AssocRhoArgs{A, rho}, B.erow, B.lmk_live);
-    else if (A.obs) hipLaunchKernelGGL((assoc_lists_kernel<true, true>), dim3(A.nz), dim3(kBlock), 0, st, A, B.erow, B.lmk_live);
-    else hipLaunchKernelGGL((assoc_lists_kernel<true, false>), dim3(A.nz), dim3(kBlock), 0, st, A, B.erow, B.lmk_live);
-}
-static void launch_lists_walk(hipStream_t st, const Buffers &B, const AssocListArgs &A, const float *R4, float g1, float g2, int32_t *labels, const float *rho,
-                              const SampleArgs *smp) {
-    const dim3 grid(B.ncap / kBlock, (A.nz + A.obs_per_block - 1) / A.obs_per_block);
-    const bool excl = A.excl_base + A.excl_per_m > 0.0f;
-    if (smp) {  // (data association sampling)
-        const AssocSampleArgs AS{AssocRhoArgs{A, rho}, *smp};
-        if (excl && rho && A.obs)
-            hipLaunchKernelGGL((associate_grid_kernel<true, true, true, true, true, true>), grid, dim3(kBlock), 0, st, B, AS, R4[0], R4[1], R4[2], R4[3], g1, g2, labels);
-        else if (excl && rho)
-            hipLaunchKernelGGL((associate_grid_kernel<true, true, true, false, true, true>), grid, dim3(kBlock), 0, st, B, AS, R4[0], R4[1], R4[2], R4[3], g1, g2, labels);
-        else if (excl && A.obs)
-            hipLaunchKernelGGL((associate_grid_kernel<true, true, true, true, false, true>), grid, dim3(kBlock), 0, st, B, AS, R4[0], R4[1], R4[2], R4[3], g1, g2, labels);
-        else if (excl)
-            hipLaunchKernelGGL((associate_grid_kernel<true, true, true, false, false, true>), grid, dim3(kBlock), 0, st, B, AS, R4[0], R4[1], R4[2], R4[3], g1, g2, labels);
-        else if (A.obs)
-            hipLaunchKernelGGL((associate_grid_kernel<true, true, false, true, false, true>), grid, dim3(kBlock), 0, st, B, AS, R4[0], R4[1], R4[2], R4[3], g1, g2, labels);
-        else
-            hipLaunchKernelGGL((associate_grid_kernel<true, true, false, false, false, true>), grid, dim3(kBlock), 0, st, B, AS, R4[0], R4[1], R4[2], R4[3], g1, g2, labels);
-    } else if (excl && rho && A.obs)
-        hipLaunchKernelGGL((associate_grid_kernel<true, true, true, true, true>), grid, dim3(kBlock), 0, st, B, AssocRhoArgs{A, rho}, R4[0], R4[1], R4[2], R4[3], g1, g2,
-                           labels);
-    else if (excl && rho)
-        hipLaunchKernelGGL((associate_grid_kernel<true, true, true, false, true>), grid, dim3(kBlock), 0, st, B, AssocRhoArgs{A, rho}, R4[0], R4[1], R4[2], R4[3], g1, g2,
-                           labels);
-    else if (A.obs && excl)
-        hipLaunchKernelGGL((associate_grid_kernel<true, true, true, true>), grid, dim3(kBlock), 0, st, B, A, R4[0], R4[1], R4[2], R4[3], g1, g2, labels);
-    else if (A.obs)
-        hipLaunchKernelGGL((associate_grid_kernel<true, true, false, true>), grid, dim3(kBlock), 0, st, B, A, R4[0], R4[1], R4[2], R4[3], g1, g2, labels);
-    else if (excl)
-        hipLaunchKernelGGL((associate_grid_kernel<true, true, true, false>), grid, dim3(kBlock), 0, st, B, A, R4[0], R4[1], R4[2], R4[3], g1, g2, labels);
     else
-        hipLaunchKernelGGL((associate_grid_kernel<true, true, false, false>), grid, dim3(kBlock), 0, st, B, A, R4[0], R4[1], R4[2], R4[3], g1, g2, labels);
+        dispatch<2>(
+            [&](auto DEV) {
+                hipLaunchKernelGGL(assoc_geom_kernel<DEV>, dim3(1), dim3(kBlock), 0, st, B, (const std::conditional_t<DEV, AssocListArgs, AssocGridArgs> &) A,
+                                   A.geom_part);
+            },
+            A.obs != nullptr);
+}
+static void launch_lists_build(hipStream_t st, const Buffers &B, const AssocListArgs &A, const AssocRule &rule) {
+    const AssocRhoArgs AR{A, excl_on(rule) ? rule.rho : nullptr};
+    dispatch<2, 2>(
+        [&](auto DEV, auto RHO) {
+            hipLaunchKernelGGL((assoc_lists_kernel<true, DEV, RHO>), dim3(A.nz), dim3(kBlock), 0, st, (const std::conditional_t<RHO, AssocRhoArgs, AssocListArgs> &) AR,
+                               B.erow, B.lmk_live);
+        },
+        A.obs != nullptr, AR.rho != nullptr);
+}
+static void launch_lists_walk(hipStream_t st, const Buffers &B, const AssocListArgs &A, const float *R4, const AssocRule &rule, int32_t *labels) {
+    const bool excl = excl_on(rule);
+    const float *rho = excl ? rule.rho : nullptr;
+    const AssocSampleArgs AS{AssocRhoArgs{A, rho}, rule.smp ? *rule.smp : SampleArgs{}};
+    dispatch<2, 2, 2, 2>(
+        [&](auto EXCL, auto DEV, auto RHO, auto SAMPLE) {
+            if constexpr (EXCL || !RHO)
+                hipLaunchKernelGGL((associate_grid_kernel<true, true, EXCL, DEV, RHO, SAMPLE>), dim3(B.ncap / kBlock, (A.nz + A.obs_per_block - 1) / A.obs_per_block),
+                                   dim3(kBlock), 0, st, B, (const AssocWalkArgs<true, true, EXCL, DEV, RHO, SAMPLE> &) AS, R4[0], R4[1], R4[2], R4[3],
+                                   rule.gate_reject, rule.gate_augment, labels);
+        },
+        excl, A.obs != nullptr, rho != nullptr, rule.smp != nullptr);
 }
 static void launch_excl_radii(hipStream_t st, const ObserveOut *obs, const float *z, int nz, int blocks, float excl_base, float excl_per_m, float f,
                               float *rho, int32_t *rho_nz) {
-    if (obs)
-        hipLaunchKernelGGL(excl_radii_kernel<true>, dim3(blocks), dim3(kBlock), 0, st, obs, (const float *) nullptr, 0, excl_base, excl_per_m, f, rho, rho_nz);
-    else
-        hipLaunchKernelGGL(excl_radii_kernel<false>, dim3(blocks), dim3(kBlock), 0, st, (const ObserveOut *) nullptr, z, nz, excl_base, excl_per_m, f, rho, rho_nz);
+    dispatch<2>([&](auto DEV) { hipLaunchKernelGGL(excl_radii_kernel<DEV>, dim3(blocks), dim3(kBlock), 0, st, obs, z, nz, excl_base, excl_per_m, f, rho, rho_nz); },
+                obs != nullptr);
 }
 
-static const KernelTable kTable = {launch_update, launch_update_particle, launch_update_persist, launch_resample, launch_resample_ref, launch_scan, launch_gather, launch_flatten, launch_identity, launch_decompact, launch_finish, launch_predict, launch_estimate, launch_jacobians, launch_kat, launch_observe, launch_observe_book, launch_associate,
+static const KernelTable kTable = {launch_update, launch_update_any, launch_update_persist, launch_resample, launch_resample_ref, launch_scan, launch_gather, launch_flatten, launch_identity, launch_decompact, launch_finish, launch_predict, launch_estimate, launch_jacobians, launch_kat, launch_observe, launch_observe_book, launch_associate,
                                    launch_shard_plan, launch_shard_pack, launch_shard_unpack, launch_shard_finish, launch_dist_gather, launch_dist_flags, launch_peek, launch_lmk_box, launch_assoc_grid, launch_assoc_lists, launch_vote_compact,
                                    launch_associate_grid, launch_jacobians_multi, launch_pp_census, launch_pp_resolve, launch_pp_holders,
-                                   launch_pp_resample, launch_pp_gather, launch_pp_associate, launch_pp_book, launch_pp_resolve_dev, launch_update_particle_dev,
+                                   launch_pp_resample, launch_pp_gather, launch_pp_book,
                                    launch_lists_box, launch_lists_geom, launch_lists_build, launch_lists_walk, launch_excl_radii};
 
 }  // namespace SLAM_KNS

@@ -315,6 +315,7 @@ struct slamgpu_ctx {
     float *das_ratio_dev = nullptr;
     size_t das_ratio_cap = 0;
     unsigned long long *das_stats_dev = nullptr;
+    SampleArgs das_step{};  // the sampling arguments of the step being associated (AssocRule::smp points here: particle_rule)
     // the observations of the last per-particle step (slamgpu_particle_labels): the host-driven call's count, or -1: the device-driven
     // iteration's (ObserveOut::nz)
     int32_t pp_lab_nz = 0;
@@ -2883,15 +2884,6 @@ int excl_rho_reserve(slamgpu_ctx *c, int cap) {
     c->excl_rho_cap = want;
     return 0;
 }
-// one launch: the radii of this step into the context's buffer, with the factor as it stands now (obs: the device-driven iteration's
-// observation, nz <= blocks * kBlock); returns them (device)
-const float *excl_radii(slamgpu_ctx *c, const ObserveOut *obs, const float *z_dev, int nz, int blocks, const float *excl3) {
-    float *rho = reinterpret_cast<float *>(c->excl_rho_dev + 4);
-    Timed t(c, "excl_radii");
-    c->k->excl_radii(c->stream, obs, z_dev, nz, blocks, excl3[0], excl3[1], c->excl_spacing, rho, c->excl_rho_dev);
-    return rho;
-}
-
 // data association sampling (slamgpu_set_particle_assoc_sampling): room for the ratios of nz observations of every slot, and the counters
 int das_reserve(slamgpu_ctx *c, int nz) {
     if (!c->das_stats_dev) {
@@ -2922,6 +2914,30 @@ SampleArgs das_args(const slamgpu_ctx *c, const float R[4]) {
     return s;
 }
 
+// the per-particle association's rule for one step (opt, and the context's settings as they stand now): the radii and sampling buffers
+// reserved for `cap` observations; with the spacing factor on, the radii of the step's observations in one launch (obs: the device-driven
+// iteration's observation, its count <= cap; else z_dev / nz); with sampling on, its arguments (das_args, kept in the context)
+int particle_rule(slamgpu_ctx *c, const slamgpu_particle_assoc *opt, const float R[4], const ObserveOut *obs, const float *z_dev, int nz, int cap,
+                  AssocRule &rule) {
+    const bool spacing = excl_spacing_on(c, opt);
+    if (spacing)
+        if (int rc = excl_rho_reserve(c, cap)) return rc;
+    if (c->das_on)
+        if (int rc = das_reserve(c, cap)) return rc;
+    rule = AssocRule{opt->gate_reject, opt->gate_augment, opt->excl_base, opt->excl_per_m, opt->unique_ratio, nullptr, nullptr};
+    if (spacing) {
+        float *rho = reinterpret_cast<float *>(c->excl_rho_dev + 4);
+        Timed t(c, "excl_radii");
+        c->k->excl_radii(c->stream, obs, z_dev, nz, (cap + kBlock - 1) / kBlock, opt->excl_base, opt->excl_per_m, c->excl_spacing, rho, c->excl_rho_dev);
+        rule.rho = rho;
+    }
+    if (c->das_on) {
+        c->das_step = das_args(c, R);
+        rule.smp = &c->das_step;
+    }
+    return 0;
+}
+
 // the boxes, grid / list and geometry buffers of the prefilter
 int grid_buffers(slamgpu_ctx *c) {
     if (c->box_dev) return 0;
@@ -2941,9 +2957,10 @@ int grid_buffers(slamgpu_ctx *c) {
 }
 
 // lab_ext: a device array the labels are left in BY OBSERVATION, [nz][ncap] (slamgpu_update_particle: they never visit the host), or null
+// opt: the per-particle association's rule (slamgpu_update_particle: its exclusion rule and sampling), or null (slamgpu_associate_ex:
+// the gates alone)
 int associate_impl(slamgpu_ctx *c, const float *z, int32_t nz, const float R[4], float gate_reject, float gate_augment, int32_t mode,
-                   int32_t *labels, int32_t *consensus, float *support, double stats[4], int32_t *lab_ext, const float *excl3 = nullptr,
-                   bool spacing = false, const SampleArgs *smp = nullptr) {
+                   int32_t *labels, int32_t *consensus, float *support, double stats[4], int32_t *lab_ext, const slamgpu_particle_assoc *opt = nullptr) {
     if (int rc = check_ctx(c)) return rc;
     if (mode < SLAMGPU_ASSOC_AUTO || mode > SLAMGPU_ASSOC_GRID) return fail(SLAMGPU_ERR_INVALID, "unknown association mode %d", mode);
     if (stats) stats[0] = stats[1] = stats[2] = stats[3] = 0.0;
@@ -2959,7 +2976,8 @@ int associate_impl(slamgpu_ctx *c, const float *z, int32_t nz, const float R[4],
     const bool single = !c->dist && c->cfg.n_particles_global == c->cfg.n_particles && c->pool_used == 0;
     if (mode == SLAMGPU_ASSOC_GRID && !single)
         return fail(SLAMGPU_ERR_INVALID, "the association grid needs a single context (shards: SLAMGPU_ASSOC_EXHAUSTIVE)");
-    const bool excl = excl3 && excl3[0] + excl3[1] > 0.0f;  // (the exclusion rule: the exhaustive scan only)
+    const bool excl = opt && opt->excl_base + opt->excl_per_m > 0.0f;  // (the exclusion rule: the exhaustive scan only)
+    const bool smp = opt && c->das_on;
     if (excl && mode == SLAMGPU_ASSOC_GRID) return fail(SLAMGPU_ERR_INVALID, "the exclusion rule needs SLAMGPU_ASSOC_EXHAUSTIVE (or _AUTO)");
     if (smp && mode == SLAMGPU_ASSOC_GRID)
         return fail(SLAMGPU_ERR_INVALID, "data association sampling needs SLAMGPU_ASSOC_EXHAUSTIVE, _AUTO or _LISTS (the grid does not sample)");
@@ -2997,7 +3015,6 @@ int associate_impl(slamgpu_ctx *c, const float *z, int32_t nz, const float R[4],
         step(hipMalloc((void **) &c->assoc_votes_dev, sizeof(VoteSlot) * kVoteSlots * (size_t) cap), "hipMalloc");
         if (!rc) c->assoc_nz_cap = cap;
     }
-    const bool z_own = false;
     z_dev = (lab_ext && c->pp_z_dev && nz <= c->pp_nz_cap) ? c->pp_z_dev : c->assoc_z_dev;
     step(hipMemcpyAsync(z_dev, z, sizeof(float) * 2 * (size_t) nz, hipMemcpyHostToDevice, c->stream), "H2D");
     step(hipStreamSynchronize(c->stream), "sync");
@@ -3152,12 +3169,13 @@ int associate_impl(slamgpu_ctx *c, const float *z, int32_t nz, const float R[4],
     }
     if (!rc && !grid) {
         need_labels();
+        AssocRule rule{gate_reject, gate_augment, 0.0f, 0.0f, 0.0f, nullptr, nullptr};  // (slamgpu_associate_ex: the exclusion rule off)
+        if (!rc && opt) rc = particle_rule(c, opt, R, nullptr, z_dev, nz, nz, rule);
         if (!rc) {
-            const float *rho = spacing ? excl_radii(c, nullptr, z_dev, nz, (nz + kBlock - 1) / kBlock, excl3) : nullptr;
             if (ev0) step(hipEventRecord(ev0, c->stream), "event");
             {
                 Timed t(c, "associate");
-                c->k->associate(c->stream, c->B, c->nf, z_dev, nz, R, gate_reject, gate_augment, excl3, c->retired_dev, lab_dev, lab_ext ? 1 : 0, rho, smp);
+                c->k->associate(c->stream, c->B, c->nf, z_dev, nz, R, rule, c->retired_dev, lab_dev, lab_ext ? 1 : 0, nullptr);
             }
             if (ev1) step(hipEventRecord(ev1, c->stream), "event");
             if (stats) stats[0] = (double) N * (double) nz * (double) c->nf;
@@ -3176,7 +3194,6 @@ int associate_impl(slamgpu_ctx *c, const float *z, int32_t nz, const float R[4],
     }
     if (ev0) (void) hipEventDestroy(ev0);
     if (ev1) (void) hipEventDestroy(ev1);
-    if (z_dev && z_own) (void) hipFree(z_dev);
     if (lab_dev && lab_dev != lab_ext) (void) hipFree(lab_dev);
     if (rc) return rc;
     if (labels) memcpy(labels, lab.data(), sizeof(int32_t) * lab.size());
@@ -3439,7 +3456,7 @@ int do_update_particle(slamgpu_ctx *c, const float *z, int32_t nz, const float R
     {
         Timed t(c, "particle_resolve");
         c->k->pp_resolve(c->stream, c->pp_lab_dev, N, nz, c->B.ncap, first_dev, news_dev, m, n, opt->p_new, c->cfg.log_weights, c->pp_obs_dev,
-                         c->pp_wf_dev, c->pp_any_dev, ratio);
+                         c->pp_wf_dev, c->pp_any_dev, ratio, nullptr);
     }
     HIP_TRY(hipGetLastError());
     c->obs_step++;
@@ -3597,7 +3614,7 @@ void lists_args(slamgpu_ctx *c, int nz, const float R[4], const slamgpu_particle
 
 // slamgpu_update_particle's association through the lists: the labels into pp_lab_dev and their census into the context's table, as the
 // grid leaves them (do_update_particle: pp_census_done); nz <= kAssocMaxCells^2, pp_reserve done
-int associate_lists(slamgpu_ctx *c, const float *z, int32_t nz, const float R[4], const slamgpu_particle_assoc *opt, const SampleArgs *smp) {
+int associate_lists(slamgpu_ctx *c, const float *z, int32_t nz, const float R[4], const slamgpu_particle_assoc *opt) {
     c->pp_census_done = false;
     if (int rc = flush_predict(c)) return rc;
     if (int rc = materialize(c)) return rc;  // plain set: particle k in slot k
@@ -3621,15 +3638,15 @@ int associate_lists(slamgpu_ctx *c, const float *z, int32_t nz, const float R[4]
     G.census_news = c->pp_tab_dev + 2 * (size_t) cap_nf;
     HIP_TRY(hipMemsetD32Async((hipDeviceptr_t) G.census_first, 0x7fffffff, (size_t) cap_nf, c->stream));
     HIP_TRY(hipMemsetAsync(G.census_news, 0, sizeof(int32_t) * (size_t) nz, c->stream));
-    const float excl3[3] = {opt->excl_base, opt->excl_per_m, opt->unique_ratio};
-    const float *rho = excl_spacing_on(c, opt) ? excl_radii(c, nullptr, c->pp_z_dev, nz, (nz + kBlock - 1) / kBlock, excl3) : nullptr;
+    AssocRule rule;
+    if (int rc = particle_rule(c, opt, R, nullptr, c->pp_z_dev, nz, nz, rule)) return rc;
     {
         Timed t(c, "associate");
         if (!ids.empty()) c->k->lmk_box(c->stream, c->B, c->assoc_ids_dev, (int) ids.size(), c->retired_dev, c->box_dev);
         c->k->lists_geom(c->stream, c->B, G, 0);
         c->k->lists_geom(c->stream, c->B, G, 1);
-        c->k->lists_build(c->stream, c->B, G, rho);
-        c->k->lists_walk(c->stream, c->B, G, R, opt->gate_reject, opt->gate_augment, c->pp_lab_dev, rho, smp);
+        c->k->lists_build(c->stream, c->B, G, rule);
+        c->k->lists_walk(c->stream, c->B, G, R, rule, c->pp_lab_dev);
     }
     HIP_TRY(hipGetLastError());
     for (int j : ids) c->box_dirty[(size_t) j] = 0;
@@ -3663,32 +3680,20 @@ int slamgpu_update_particle(slamgpu_ctx *c, const float *z, int32_t nz, const fl
     if (nz == 0) return 0;  // (no observation, no update: fastslam2wrapper.cpp:84-95)
     HIP_TRY(hipSetDevice(c->cfg.device));
     if (int rc = pp_reserve(c, nz, 1)) return rc;
-    const bool spacing = excl_spacing_on(c, opt);
-    if (spacing)
-        if (int rc = excl_rho_reserve(c, nz)) return rc;
     // data association sampling: the labels drawn, their ratios into the weights (the step's draws follow the host's obs_step: the
     // device-driven state comes back first)
-    SampleArgs sa{};
-    const SampleArgs *smp = nullptr;
     if (c->das_on) {
         if (opt->mode == SLAMGPU_ASSOC_GRID)
             return fail(SLAMGPU_ERR_INVALID, "data association sampling needs SLAMGPU_ASSOC_EXHAUSTIVE, _AUTO or _LISTS (the grid does not sample)");
-        if (int rc = das_reserve(c, nz)) return rc;
         if (int rc = book_pull(c)) return rc;
-        sa = das_args(c, R);
-        smp = &sa;
     }
-    const float *ratio = smp ? c->das_ratio_dev : nullptr;
     if (opt->mode == SLAMGPU_ASSOC_LISTS) {
         if (int rc = book_pull(c)) return rc;  // (the device-driven state back first: the boxes and the mask are the host's again)
-        if (int rc = associate_lists(c, z, nz, R, opt, smp)) return rc;
-        return do_update_particle(c, z, nz, R, opt, normals, strata, report, ratio);
-    }
-    const float excl3[3] = {opt->excl_base, opt->excl_per_m, opt->unique_ratio};
-    if (int rc = associate_impl(c, z, nz, R, opt->gate_reject, opt->gate_augment, opt->mode, nullptr, nullptr, nullptr, nullptr, c->pp_lab_dev, excl3,
-                                spacing, smp))
+        if (int rc = associate_lists(c, z, nz, R, opt)) return rc;
+    } else if (int rc = associate_impl(c, z, nz, R, opt->gate_reject, opt->gate_augment, opt->mode, nullptr, nullptr, nullptr, nullptr, c->pp_lab_dev, opt)) {
         return rc;
-    return do_update_particle(c, z, nz, R, opt, normals, strata, report, ratio);
+    }
+    return do_update_particle(c, z, nz, R, opt, normals, strata, report, c->das_on ? c->das_ratio_dev : nullptr);
 }
 
 int slamgpu_update_labels(slamgpu_ctx *c, const float *z, int32_t nz, const float R[4], const int32_t *labels, const slamgpu_particle_assoc *opt,
@@ -3976,12 +3981,10 @@ int pp_dev_iteration(slamgpu_ctx *c, int32_t nc, const float *controls, const fl
     P.need = need;
     P.p_new = opt->p_new;
     c->B.slot = c->slot;
-    const float excl3[3] = {opt->excl_base, opt->excl_per_m, opt->unique_ratio};
-    // (the radii: every observation the map allows, whatever the lists grid; the count comes from the observation)
-    const float *rho = excl_spacing_on(c, opt) ? excl_radii(c, c->obs_out_dev, nullptr, 0, (c->map_n + kBlock - 1) / kBlock, excl3) : nullptr;
-    // (data association sampling, as the setting stands now: the walk reads the step from PpState)
-    const SampleArgs sa = das_args(c, R);
-    const SampleArgs *smp = c->das_on ? &sa : nullptr;
+    // (the radii: every observation the map allows, whatever the lists grid; the count comes from the observation.  Sampling: the walk
+    // reads the step from PpState.  The buffers: slamgpu_run_particle reserved them)
+    AssocRule rule;
+    if (int rc = particle_rule(c, opt, R, c->obs_out_dev, nullptr, 0, c->map_n, rule)) return rc;
     c->pp_lab_nz = -1;
     if (bound >= 0) {
         // the boxes of the slots the previous iteration wrote, the geometry, one list per observation, the walk (+ the census)
@@ -4007,15 +4010,15 @@ int pp_dev_iteration(slamgpu_ctx *c, int32_t nc, const float *controls, const fl
         }
         {
             Timed t(c, "assoc_lists");
-            c->k->lists_build(c->stream, c->B, G, rho);
+            c->k->lists_build(c->stream, c->B, G, rule);
         }
         {
             Timed t(c, "associate");
-            c->k->lists_walk(c->stream, c->B, G, R, opt->gate_reject, opt->gate_augment, c->pp_lab_dev, rho, smp);
+            c->k->lists_walk(c->stream, c->B, G, R, rule, c->pp_lab_dev);
         }
     } else {
         Timed t(c, "associate");
-        c->k->pp_associate(c->stream, c->B, R, opt->gate_reject, opt->gate_augment, excl3, c->pp_lab_dev, P, rho, smp);
+        c->k->associate(c->stream, c->B, 0, nullptr, 0, R, rule, P.retired, c->pp_lab_dev, 1, &P);
     }
     {
         Timed t(c, "particle_book");
@@ -4023,7 +4026,8 @@ int pp_dev_iteration(slamgpu_ctx *c, int32_t nc, const float *controls, const fl
     }
     {
         Timed t(c, "particle_resolve");
-        c->k->pp_resolve_dev(c->stream, c->pp_lab_dev, c->B.n, c->B.ncap, P, c->pp_obs_dev, c->pp_wf_dev, c->pp_any_dev, smp ? c->das_ratio_dev : nullptr);
+        c->k->pp_resolve(c->stream, c->pp_lab_dev, c->B.n, 0, c->B.ncap, P.uidx, P.newk, 0, 0, P.p_new, P.logw, c->pp_obs_dev, c->pp_wf_dev, c->pp_any_dev,
+                         rule.smp ? c->das_ratio_dev : nullptr, &P);
     }
     UpdateArgs U{};
     U.method = c->cfg.method;
@@ -4044,7 +4048,7 @@ int pp_dev_iteration(slamgpu_ctx *c, int32_t nc, const float *controls, const fl
                     c->obs_out_dev, &c->pp_st_dev->step};
     {
         Timed t(c, c->cfg.method == SLAMGPU_FASTSLAM2 ? "fs2_update" : "fs1_update");
-        c->k->update_particle_dev(c->stream, c->B, PredictArgs{}, U, rng_args(c, 0), c->ws, ppa);
+        c->k->update_particle(c->stream, c->B, PredictArgs{}, U, rng_args(c, 0), c->ws, ppa);
     }
     HIP_TRY(hipGetLastError());
     c->slot ^= 1;
