@@ -461,6 +461,25 @@ int slamgpu_download_range(slamgpu_ctx *ctx, int32_t first, int32_t count, float
  * Synchronises. */
 int slamgpu_peek(slamgpu_ctx *ctx, int32_t first, int32_t stride, int32_t count, float *xv, float *Pv9, float *w, float *xf,
                  float *Pf4);
+/* Posterior map summary: what the filter AS A WHOLE believes about landmark slots [first_slot, first_slot + count), reduced on
+ * the device over the particle set slamgpu_peek(ctx, 0, 1, N, ...) would show at this moment (queued predicts flushed, the last
+ * update's outstanding resampling stage run, a pending gather read through its ancestors with weight 1/N, records through the
+ * genealogy).  With w^_i = w_i / sum_k w_k over ALL N particles (log-weight contexts: w_i = exp(l_i - max l)) and H the particles
+ * that hold the slot (record not absent), out[slot][SLAMGPU_MAP_STRIDE] is
+ *     [0]       share s = sum_{i in H} w^_i
+ *     [1..2]    mean mu = sum_{i in H} w^_i xf_i / s
+ *     [3..5]    between-particle scatter sum_{i in H} w^_i (xf_i - mu)(xf_i - mu)^T / s: xx, xy, yy
+ *     [6..8]    mean within-particle covariance sum_{i in H} w^_i Pf_i / s: p00, p10, p11
+ * and holders[slot] (may be NULL) = |H|.  Scatter + mean covariance is the total spread of the slot: the particle filter's
+ * counterpart of the EKF's P per landmark.  A slot nobody holds: share 0, holders 0, entries 1..8 NaN; retired slots are reported
+ * like any other; without SLAMGPU_FLAG_PARTICLE_MAPS every particle holds every slot and every share is 1.  If the weights sum
+ * to zero or to nothing finite every entry is NaN and the call returns 0: the reference's normalisation does the same
+ * (SLAMGPU_STATUS_DEGENERATE).  Sums are taken in double in a fixed order: the same state gives the same bits, whether read
+ * through the genealogy or after slamgpu_download has flattened it.  Like slamgpu_peek it rewrites nothing: the state the next
+ * step works on is bit for bit what it would have been without the call.  Single contexts only (SLAMGPU_ERR_INVALID otherwise, as
+ * for slots outside [0, slamgpu_num_landmarks)); count == 0 does nothing.  Synchronises. */
+#define SLAMGPU_MAP_STRIDE 9
+int slamgpu_map_summary(slamgpu_ctx *ctx, int32_t first_slot, int32_t count, double *out, int32_t *holders);
 int slamgpu_upload(slamgpu_ctx *ctx, int32_t nf, const float *xv, const float *Pv9, const float *w, const float *xf,
                    const float *Pf4);
 int slamgpu_sync(slamgpu_ctx *ctx);

@@ -29,7 +29,9 @@ DECLARED_SYMBOLS = [
     "slamgpu_run_particle", "slamgpu_particle_report_fetch", "slamgpu_particle_list_stats",
     "slamgpu_set_particle_excl_spacing", "slamgpu_particle_excl_radii",
     "slamgpu_set_particle_assoc_sampling", "slamgpu_particle_sample_stats", "slamgpu_particle_labels",
+    "slamgpu_map_summary",
 ]
+MAP_STRIDE = 9  # SLAMGPU_MAP_STRIDE
 ASSOC_AUTO, ASSOC_EXHAUSTIVE, ASSOC_GRID, ASSOC_LISTS = 0, 1, 2, 3
 FLAG_DEVICE_OBSERVE = 1
 FLAG_NO_REFERENCE_RESAMPLE = 2
@@ -129,6 +131,8 @@ def load_library():
         L.slamgpu_set_particle_assoc_sampling.argtypes = [C.c_void_p, C.c_int32]
         L.slamgpu_particle_sample_stats.argtypes = [C.c_void_p, C.c_void_p]
         L.slamgpu_particle_labels.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int32)]
+    if hasattr(L, "slamgpu_map_summary"):
+        L.slamgpu_map_summary.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
     L.slamgpu_genealogy_rows.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     L.slamgpu_persist_info.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
     if hasattr(L, "slamgpu_persist_status"):  # (an older build loaded through SLAMGPU_LIB for an A/B lacks the round-6 entries)
@@ -509,6 +513,17 @@ class SlamGpu:
         Pf = np.zeros((N, nf, 2, 2), np.float32) if landmarks else None
         _chk(self.L.slamgpu_peek(self.h, first, stride, N, _ptr(xv), _ptr(Pv), _ptr(w), _ptr(xf), _ptr(Pf)))
         return dict(xv=xv, Pv=Pv, w=w, xf=xf, Pf=Pf, nf=nf)
+
+    def map_summary(self, first=0, count=None):
+        """slamgpu_map_summary: the posterior of landmark slots first .. first + count - 1 over the whole particle set, reduced on the
+        device: share[count] of the weight that holds the slot, the holders' weighted mean[count, 2], their scatter[count, 3] about it
+        (xx, xy, yy), their mean covariance pf[count, 3] (p00, p10, p11) and holders[count]; rewrites no state"""
+        if count is None:
+            count = self.nf() - first
+        out = np.zeros((max(count, 0), MAP_STRIDE), np.float64)
+        holders = np.zeros(max(count, 0), np.int32)
+        _chk(self.L.slamgpu_map_summary(self.h, first, count, _ptr(out), _ptr(holders)))
+        return dict(share=out[:, 0].copy(), mean=out[:, 1:3].copy(), scatter=out[:, 3:6].copy(), pf=out[:, 6:9].copy(), holders=holders)
 
     def upload(self, st):
         nf = int(st["nf"])

@@ -20,6 +20,10 @@
 //                        (slamgpu_set_particle_excl_spacing): dense maps, where the fixed radius would forbid every new landmark.
 //                        -PARTICLE_ASSOC_SAMPLE 1: data association sampling (slamgpu_set_particle_assoc_sampling; 0, the default:
 //                        nearest neighbour); the summary then prints the sampling counters (slamgpu_particle_sample_stats).
+//   -map best|posterior  the map reported at the end of a FastSLAM run.  best (default): the landmark count, with -assoc particle the best
+//                        particle's map.  posterior: one more line from slamgpu_map_summary, over ALL particles: the slots held by at
+//                        least half of the weight, how many true landmarks lie within 1 m of such a slot's weighted mean, how many such
+//                        slots lie within 1 m of no true landmark, and the slots held by less than half / by none.  Not with -gpus k > 1.
 //   -plot <sinks>        the per-step output the reference sends to slam-gui (plotting/NetworkPlot.cpp), byte for byte:
 //                        tcp://127.0.0.1:4242 (the existing slam-gui) | file:<frames> | gather:<dir> (the GUI's DataGatherer
 //                        files, headless) | none (default); several separated by ','
@@ -75,6 +79,8 @@ static void usage(const char *a0) {
     printf("                        step's nearest other observation (default 0: the fixed radius)\n");
     printf("    -PARTICLE_ASSOC_SAMPLE 0|1  -assoc particle: draw an ambiguous observation's landmark in proportion to its likelihood\n");
     printf("                        (data association sampling, weights by the marginal likelihood; default 0: the nearest)\n");
+    printf("    -map best|posterior the map reported at the end: best (default; -assoc particle: the best particle's), or posterior: one more line,\n");
+    printf("                        the landmark slots by the share of ALL particles' weight that holds them (slamgpu_map_summary; not with -gpus)\n");
     printf("    -gpus k             FastSLAM particle set distributed over k GPUs (k > devices: logical shards on device 0)\n");
     printf("    -observe host|device  where the observation of a step is made: host (default) or on the GPU (the packet never leaves\n");
     printf("                        device memory: slamgpu_step_observe; -rng philox, known association, no -plot; with -assoc particle:\n");
@@ -207,6 +213,44 @@ static int run_distributed(Simulator &sim, int k, long maxsteps, FILE *log, Plot
     slamgpu_dist_group_destroy(grp);
     for (slamgpu_ctx *x : ctx) slamgpu_destroy(x);
     return rc ? EXIT_FAILURE : 0;
+}
+
+// -map posterior: the slots as the whole particle set sees them (slamgpu_map_summary): confident = held by at least half of the weight
+static bool g_map_posterior = false;
+static void print_posterior_map(slamgpu_ctx *ctx, const Simulator &sim) {
+    if (!g_map_posterior) return;
+    const int slots = slamgpu_num_landmarks(ctx);
+    std::vector<double> sum((size_t) SLAMGPU_MAP_STRIDE * (size_t) std::max(slots, 1));
+    if (slots < 0 || slamgpu_map_summary(ctx, 0, slots, sum.data(), nullptr) != 0) {
+        fprintf(stderr, "slamgpu: %s\n", slamgpu_last_error());
+        return;
+    }
+    if (slots > 0 && sum[0] != sum[0]) {  // (every entry NaN: slamgpu_map_summary's answer to weights that sum to zero or to nothing finite)
+        printf("posterior map: not available, the weights are degenerate (SLAMGPU_STATUS_DEGENERATE: their sum is zero or not finite)\n");
+        return;
+    }
+    int confident = 0, covered = 0, stray = 0, minority = 0, dead = 0;
+    std::vector<char> hit((size_t) sim.map.nlm, 0);
+    for (int j = 0; j < slots; j++) {
+        const double *e = sum.data() + (size_t) SLAMGPU_MAP_STRIDE * (size_t) j;
+        if (e[0] >= 0.5) {
+            confident++;
+            bool near = false;
+            for (int t = 0; t < sim.map.nlm; t++) {
+                const double dx = e[1] - (double) sim.map.lm[(size_t) t], dy = e[2] - (double) sim.map.lm[(size_t) sim.map.nlm + t];
+                if (dx * dx + dy * dy < 1.0) hit[(size_t) t] = 1, near = true;
+            }
+            if (!near) stray++;
+        } else if (e[0] > 0.0) {
+            minority++;
+        } else {
+            dead++;
+        }
+    }
+    for (char h : hit) covered += h;
+    printf("posterior map: %d slots held by at least half of the weight (%d of the %d true landmarks within 1 m of the mean of one of them, %d of them "
+           "within 1 m of no true landmark); %d slots held by less than half, %d by none\n",
+           confident, covered, sim.map.nlm, stray, minority, dead);
 }
 
 // -assoc particle: the map of the best (largest-weight) particle: what a FastSLAM with per-particle association reports
@@ -377,6 +421,7 @@ static int run_batched(Simulator &sim, slamgpu_ctx *ctx, bool observe_dev, long 
     }
     if (popt) print_particle_map(ctx, sim, sim.conf.NPARTICLES, pp_opened, pp_reused, pp_dropped, pp_most);
     else printf("landmarks in map: %d\n", slamgpu_num_landmarks(ctx));
+    print_posterior_map(ctx, sim);
     return rc ? EXIT_FAILURE : 0;
 }
 
@@ -391,6 +436,16 @@ int main(int argc, char **argv) {
     if (!sim.init(argc, argv, &err)) {
         fprintf(stderr, "%s\n", err.c_str());
         return EXIT_FAILURE;
+    }
+    {
+        // -map is this program's own report option, not a setting of the run: it stays out of the settings printed below
+        const std::string m = sim.conf.s("map");
+        if (!m.empty() && m != "best" && m != "posterior") {
+            fprintf(stderr, "-map best|posterior\n");
+            return EXIT_FAILURE;
+        }
+        g_map_posterior = m == "posterior";
+        sim.conf.kv.erase("map");
     }
     const Conf &c = sim.conf;
     printf("map: %s\n", c.map_path.c_str());
@@ -411,6 +466,10 @@ int main(int argc, char **argv) {
         if (plot.active()) plot.setSimulationName(c.simulation_name);
     }
     if (c.method != 0 && !c.s("gpus").empty() && atoi(c.s("gpus").c_str()) != 1) {
+        if (g_map_posterior) {
+            fprintf(stderr, "-map posterior: single GPU only (slamgpu_map_summary has no distributed form)\n");
+            return EXIT_FAILURE;
+        }
         if (plot.active()) {
             plot.setCarSize(c.WHEELBASE, 0);
             plot.setCarSize(c.WHEELBASE, 1);
@@ -768,6 +827,7 @@ int main(int argc, char **argv) {
         print_particle_map(ctx, sim, N, pp_opened, pp_reused, pp_dropped, pp_most);
     } else if (ctx) printf("landmarks in map: %d\n", slamgpu_num_landmarks(ctx));
     else printf("landmarks in map: %d\n", ekf.num_features());
+    if (ctx) print_posterior_map(ctx, sim);
     if (plot.active()) {
         plot.endPlot();
         plot.close();

@@ -522,6 +522,33 @@ struct PeekArgs {
     float *lb;
 };
 
+// Posterior map summary (slamgpu_map_summary): per landmark slot, over the particle set slamgpu_peek would show, the share of the
+// weight that holds the slot, the holders' weighted mean position, their scatter about it and their mean covariance.
+// map_summary_kernel: grid (particle tiles, groups of kMapSlots slots); a tile is kMapTile = kBlock * kMapT particles, a lane keeps the
+// weights (and, under a pending gather, the ancestors) of its kMapT particles in registers across the group's slots.  Sums are
+// double, taken about a pivot inside the holders' cloud (the wave's first held record of the slot), lanes combined by a DPP sum in
+// the wave, waves and tiles as (W, mean, M2) by the pairwise update of Chan, Golub & LeVeque, in ascending particle order: no atomics,
+// the same bits for the same particles in the same order.  One partial per tile and slot goes to `part`; map_finish_kernel (kMapFinParts threads
+// per slot, each a stretch of the tiles, then the stretches: ascending order throughout) merges them, normalises by the sum of all weights and
+// writes out / holders.
+// Log-weight contexts: a tile's sums are of exp(l - M_t), M_t the tile's largest log-weight (wpart); the finishing pass rescales by
+// exp(M_t - max M), as the resampling scan does with its block totals.
+constexpr int kMapT = 4;                   // particles per lane
+constexpr int kMapTile = kBlock * kMapT;   // particles per tile
+constexpr int kMapSlots = 8;               // slots per workgroup
+constexpr int kMapStride = 9;              // SLAMGPU_MAP_STRIDE
+constexpr int kMapFinParts = 8;            // threads per slot in the finishing pass
+// fields of a partial, [tile][field][count]: sum w | mean x, y | M2 xx, xy, yy (sum w d d^T about the mean) | sum w Pf 00, 10, 11 | holders
+enum { kMapW = 0, kMapMx, kMapMy, kMapXX, kMapXY, kMapYY, kMapP00, kMapP10, kMapP11, kMapCnt, kMapFields };
+struct MapSummaryArgs {
+    int32_t first_slot, count;  // this launch's slots
+    int32_t tiles, logw;
+    double *part;               // [tiles][kMapFields][count]
+    double *wpart;              // [tiles][2]: the tile's sum of weights (log-weights: of exp(l - M_t)) | M_t (linear weights: 0)
+    double *out;                // [count][kMapStride]
+    int32_t *holders;           // [count]
+};
+
 // ---- gated association with a spatial prefilter (slamgpu_associate_ex) ------------------------------------------------------
 // Per landmark j, over ALL particles: the bounding box of its position estimates and the largest trace of its covariance
 // (lmk_box_kernel, recomputed when the landmark is written), and from them a radius rho_j such that a particle's estimate of j
@@ -769,6 +796,9 @@ struct KernelTable {
     // observation (nz <= blocks * kBlock)
     void (*excl_radii)(hipStream_t, const ObserveOut *obs, const float *z_dev, int nz, int blocks, float excl_base, float excl_per_m, float f,
                        float *rho_dev, int32_t *rho_nz_dev);
+    // slamgpu_map_summary (MapSummaryArgs): the partials of one chunk of slots, and their finishing pass.  Tables in sync; reads only
+    void (*map_summary)(hipStream_t, const Buffers &, const WeightScratch &, const MapSummaryArgs &);
+    void (*map_finish)(hipStream_t, const MapSummaryArgs &);
 };
 
 const KernelTable *kernels_strict();

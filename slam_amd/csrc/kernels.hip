@@ -4721,11 +4721,259 @@ static void launch_excl_radii(hipStream_t st, const ObserveOut *obs, const float
                 obs != nullptr);
 }
 
+// ---- slamgpu_map_summary (kernels.h: MapSummaryArgs) -------------------------------------------------------------------------
+// the record of landmark l behind genealogy entry sl (single contexts: read_through_genealogy past its genealogy load, so that the
+// slots of one genealogy row share that load)
+SLAM_DEV void read_record(const Buffers &B, const int32_t *__restrict__ live, size_t S, int l, int sl, float4 &la, float &lb) {
+    if (sl < 0) {
+        const size_t at = (size_t) l * B.pool_cap + (sl & ~kPoolBit);
+        la = B.poolA[at];
+        lb = B.poolB[at];
+    } else {
+        const int b = live[l];
+        la = B.lmkA[b][(size_t) l * S + sl];
+        lb = B.lmkB[b][(size_t) l * S + sl];
+    }
+}
+// one (W, mean, M2, sum w Pf, holders) summary and the pairwise update with the one that follows it in particle order
+struct MapPart {
+    double v[kMapFields];
+};
+SLAM_DEV void map_merge(MapPart &a, const MapPart &b) {
+    a.v[kMapCnt] += b.v[kMapCnt];
+    if (!(b.v[kMapW] != 0.0)) return;  // nothing of weight in b (its holders, if any, are counted)
+    if (!(a.v[kMapW] != 0.0)) {
+        const double cnt = a.v[kMapCnt];
+        a = b;
+        a.v[kMapCnt] = cnt;
+        return;
+    }
+    const double W = a.v[kMapW] + b.v[kMapW], f = b.v[kMapW] / W, g = a.v[kMapW] * f;
+    const double dx = b.v[kMapMx] - a.v[kMapMx], dy = b.v[kMapMy] - a.v[kMapMy];
+    a.v[kMapMx] += dx * f;
+    a.v[kMapMy] += dy * f;
+    a.v[kMapXX] += b.v[kMapXX] + dx * dx * g;
+    a.v[kMapXY] += b.v[kMapXY] + dx * dy * g;
+    a.v[kMapYY] += b.v[kMapYY] + dy * dy * g;
+    a.v[kMapP00] += b.v[kMapP00];
+    a.v[kMapP10] += b.v[kMapP10];
+    a.v[kMapP11] += b.v[kMapP11];
+    a.v[kMapW] = W;
+}
+
+__global__ void __launch_bounds__(kBlock) map_summary_kernel(Buffers B, WeightScratch ws, MapSummaryArgs A) {
+    constexpr int kWaves = kBlock / kWave;
+    __shared__ double sh[kMapSlots][kWaves][kMapFields];
+    __shared__ double sh_w[kWaves];
+    __shared__ float sh_m[kWaves];
+    const Ctrl *ctrl = B.ctrl;
+    const int cur = ctrl->live[B.slot];
+    const bool pend = ctrl->pend[B.slot] != 0;
+    const size_t S = (size_t) B.ncap;
+    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
+    // this lane's particles: ancestor and weight, once for every slot of the group
+    int anc[kMapT];
+    float wf[kMapT];
+    bool on[kMapT];
+    float mb = -INFINITY;
+#pragma unroll
+    for (int t = 0; t < kMapT; t++) {
+        const int i = blockIdx.x * kMapTile + t * kBlock + threadIdx.x;
+        on[t] = i < B.n;
+        anc[t] = on[t] ? (pend ? ws.keep[B.slot][i] : i) : 0;
+        wf[t] = on[t] ? (pend ? ctrl->inv_n : B.poseA[cur][anc[t]].w) : 0.0f;  // resampled particles restart at 1/N, as in peek_kernel
+        if (on[t] && A.logw) mb = fmaxf(mb, wf[t]);
+    }
+    double w[kMapT];
+    if (A.logw) {  // the tile's largest log-weight
+        for (int d = kWave / 2; d > 0; d >>= 1) mb = fmaxf(mb, __shfl_xor(mb, d, kWave));
+        if (lane == 0) sh_m[wave] = mb;
+        __syncthreads();
+        mb = sh_m[0];
+        for (int v = 1; v < kWaves; v++) mb = fmaxf(mb, sh_m[v]);
+#pragma unroll
+        for (int t = 0; t < kMapT; t++) w[t] = (on[t] && mb != -INFINITY) ? exp((double) wf[t] - (double) mb) : 0.0;
+    } else {
+        mb = 0.0f;
+#pragma unroll
+        for (int t = 0; t < kMapT; t++) w[t] = (double) wf[t];
+    }
+    if (blockIdx.y == 0) {  // the tile's sum of weights (every group of slots would find the same bits: one of them stores it)
+        double sw = 0.0;
+#pragma unroll
+        for (int t = 0; t < kMapT; t++) sw += w[t];
+        sw = wave_sum_d(sw);
+        if (lane == 0) sh_w[wave] = sw;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            double tot = sh_w[0];
+            for (int v = 1; v < kWaves; v++) tot += sh_w[v];
+            A.wpart[2 * blockIdx.x] = tot;
+            A.wpart[2 * blockIdx.x + 1] = (double) mb;
+        }
+    }
+    const int s0 = blockIdx.y * kMapSlots, sn = min(kMapSlots, A.count - s0);
+    int row = -1;
+    int sl[kMapT];
+    for (int s = 0; s < sn; s++) {
+        const int l = A.first_slot + s0 + s;
+        const int r = B.erow[l];
+        if (r != row) {  // (uniform) the slots of one genealogy row share its entries
+            row = r;
+#pragma unroll
+            for (int t = 0; t < kMapT; t++) sl[t] = on[t] ? B.gen[cur][gen_index(B.compact, S, r, (size_t) anc[t])] : 0;
+        }
+        float4 la[kMapT];
+        float lb[kMapT];
+#pragma unroll
+        for (int t = 0; t < kMapT; t++) {
+            la[t] = make_float4(NAN, NAN, NAN, NAN);
+            lb[t] = NAN;
+            if (on[t]) read_record(B, B.lmk_live, S, l, sl[t], la[t], lb[t]);
+        }
+        // pivot: the wave's first held record of this slot (a point of the holders' cloud: the sums below cancel at the cloud's size)
+        bool have = false;
+        float px = 0.0f, py = 0.0f;
+        int cnt = 0;
+#pragma unroll
+        for (int t = 0; t < kMapT; t++) {
+            const unsigned long long hm = __ballot(la[t].x == la[t].x);
+            cnt += (int) __popcll(hm);
+            if (!have && hm) {
+                const int src = __builtin_amdgcn_readfirstlane((int) __ffsll((long long) hm) - 1);
+                px = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(la[t].x), src));
+                py = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(la[t].y), src));
+                have = true;
+            }
+        }
+        double *o = sh[s][wave];
+        if (!have) {  // (uniform) nobody in this wave holds the slot
+            if (lane < kMapFields) o[lane] = 0.0;
+            continue;
+        }
+        double a[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};  // sum w | w dx, w dy | w dx^2, w dx dy, w dy^2 | w Pf
+#pragma unroll
+        for (int t = 0; t < kMapT; t++) {
+            if (la[t].x == la[t].x) {
+                const double dx = (double) la[t].x - (double) px, dy = (double) la[t].y - (double) py, wt = w[t];
+                a[0] += wt;
+                a[1] += wt * dx;
+                a[2] += wt * dy;
+                a[3] += wt * dx * dx;
+                a[4] += wt * dx * dy;
+                a[5] += wt * dy * dy;
+                a[6] += wt * (double) la[t].z;
+                a[7] += wt * (double) la[t].w;
+                a[8] += wt * (double) lb[t];
+            }
+        }
+#pragma unroll
+        for (int q = 0; q < 9; q++) a[q] = wave_sum_d(a[q]);
+        if (lane == 0) {
+            const double W = a[0];
+            const bool any = W != 0.0;  // (W == 0: holders without weight are counted, and carry nothing else)
+            const double mx = any ? a[1] / W : 0.0, my = any ? a[2] / W : 0.0;
+            o[kMapW] = W;
+            o[kMapMx] = (double) px + mx;
+            o[kMapMy] = (double) py + my;
+            o[kMapXX] = a[3] - a[1] * mx;
+            o[kMapXY] = a[4] - a[1] * my;
+            o[kMapYY] = a[5] - a[2] * my;
+            o[kMapP00] = a[6];
+            o[kMapP10] = a[7];
+            o[kMapP11] = a[8];
+            o[kMapCnt] = (double) cnt;
+        }
+    }
+    __syncthreads();
+    if ((int) threadIdx.x < sn) {  // the tile's waves in ascending order (wave v: lanes v * 64 .. of each of the tile's kMapT strides)
+        const int s = threadIdx.x;
+        MapPart m;
+        for (int q = 0; q < kMapFields; q++) m.v[q] = sh[s][0][q];
+        for (int v = 1; v < kWaves; v++) {
+            MapPart b;
+            for (int q = 0; q < kMapFields; q++) b.v[q] = sh[s][v][q];
+            map_merge(m, b);
+        }
+        double *p = A.part + (size_t) blockIdx.x * kMapFields * (size_t) A.count + (size_t) (s0 + s);
+        for (int q = 0; q < kMapFields; q++) p[(size_t) q * A.count] = m.v[q];
+    }
+}
+
+// kMapFinParts threads per slot: each merges its stretch of the tiles' partials in ascending order (and adds up that stretch's weights),
+// the slot's first thread merges the stretches in ascending order, normalises and writes the outputs
+__global__ void __launch_bounds__(kBlock) map_finish_kernel(MapSummaryArgs A) {
+    constexpr int kSlots = kBlock / kMapFinParts;
+    __shared__ double sh[kMapFinParts][kMapFields + 1][kSlots];
+    __shared__ double sh_m[kBlock / kWave];
+    const int sl = threadIdx.x % kSlots, part = threadIdx.x / kSlots;
+    const int s = blockIdx.x * kSlots + sl;
+    double M = -INFINITY;
+    if (A.logw) {  // the largest log-weight of all tiles
+        for (int t = threadIdx.x; t < A.tiles; t += kBlock) M = fmax(M, A.wpart[2 * t + 1]);
+        for (int d = kWave / 2; d > 0; d >>= 1) M = fmax(M, __shfl_xor(M, d, kWave));
+        if ((threadIdx.x & (kWave - 1)) == 0) sh_m[threadIdx.x / kWave] = M;
+        __syncthreads();
+        M = sh_m[0];
+        for (int v = 1; v < kBlock / kWave; v++) M = fmax(M, sh_m[v]);
+    }
+    const int per = (A.tiles + kMapFinParts - 1) / kMapFinParts, t0 = part * per, t1 = min(A.tiles, t0 + per);
+    MapPart m;
+    for (int q = 0; q < kMapFields; q++) m.v[q] = 0.0;
+    double wsum = 0.0;
+    for (int t = t0; t < t1; t++) {
+        const double f = A.logw ? block_scale((float) A.wpart[2 * t + 1], M) : 1.0;
+        wsum += A.wpart[2 * t] * f;
+        if (s >= A.count) continue;
+        const double *p = A.part + (size_t) t * kMapFields * (size_t) A.count + (size_t) s;
+        MapPart b;
+        for (int q = 0; q < kMapFields; q++) b.v[q] = p[(size_t) q * A.count];
+        if (A.logw) {
+            b.v[kMapW] *= f;
+            for (int q = kMapXX; q <= kMapP11; q++) b.v[q] *= f;
+        }
+        map_merge(m, b);
+    }
+    for (int q = 0; q < kMapFields; q++) sh[part][q][sl] = m.v[q];
+    sh[part][kMapFields][sl] = wsum;
+    __syncthreads();
+    if (part != 0 || s >= A.count) return;
+    double Wtot = wsum;
+    for (int v = 1; v < kMapFinParts; v++) {
+        MapPart b;
+        for (int q = 0; q < kMapFields; q++) b.v[q] = sh[v][q][sl];
+        map_merge(m, b);
+        Wtot += sh[v][kMapFields][sl];
+    }
+    double *o = A.out + (size_t) s * kMapStride;
+    A.holders[s] = (int32_t) m.v[kMapCnt];
+    const double nan = __longlong_as_double(0x7ff8000000000000ll);
+    if (!(Wtot > 0.0) || !(Wtot < INFINITY)) {  // the weights sum to zero or to nothing finite: SLAMGPU_STATUS_DEGENERATE's convention
+        for (int q = 0; q < kMapStride; q++) o[q] = nan;
+        return;
+    }
+    const double W = m.v[kMapW];
+    o[0] = W / Wtot;
+    const bool held = m.v[kMapCnt] != 0.0 && W != 0.0;
+    o[1] = held ? m.v[kMapMx] : nan;
+    o[2] = held ? m.v[kMapMy] : nan;
+    for (int q = kMapXX; q <= kMapP11; q++) o[q] = held ? m.v[q] / W : nan;
+}
+
+static void launch_map_summary(hipStream_t st, const Buffers &B, const WeightScratch &ws, const MapSummaryArgs &A) {
+    hipLaunchKernelGGL(map_summary_kernel, dim3(A.tiles, (A.count + kMapSlots - 1) / kMapSlots), dim3(kBlock), 0, st, B, ws, A);
+}
+static void launch_map_finish(hipStream_t st, const MapSummaryArgs &A) {
+    constexpr int kSlots = kBlock / kMapFinParts;
+    hipLaunchKernelGGL(map_finish_kernel, dim3((A.count + kSlots - 1) / kSlots), dim3(kBlock), 0, st, A);
+}
+
 static const KernelTable kTable = {launch_update, launch_update_any, launch_update_persist, launch_resample, launch_resample_ref, launch_scan, launch_gather, launch_flatten, launch_identity, launch_decompact, launch_finish, launch_predict, launch_estimate, launch_jacobians, launch_kat, launch_observe, launch_observe_book, launch_associate,
                                    launch_shard_plan, launch_shard_pack, launch_shard_unpack, launch_shard_finish, launch_dist_gather, launch_dist_flags, launch_peek, launch_lmk_box, launch_assoc_grid, launch_assoc_lists, launch_vote_compact,
                                    launch_associate_grid, launch_jacobians_multi, launch_pp_census, launch_pp_resolve, launch_pp_holders,
                                    launch_pp_resample, launch_pp_gather, launch_pp_book,
-                                   launch_lists_box, launch_lists_geom, launch_lists_build, launch_lists_walk, launch_excl_radii};
+                                   launch_lists_box, launch_lists_geom, launch_lists_build, launch_lists_walk, launch_excl_radii,
+                                   launch_map_summary, launch_map_finish};
 
 }  // namespace SLAM_KNS
 

@@ -265,6 +265,8 @@ struct slamgpu_ctx {
     int32_t cap_items = 0;
     char *peek_dev = nullptr;        // staging of slamgpu_peek, grown on demand
     size_t peek_bytes = 0;
+    char *msum_dev = nullptr;        // staging and partials of slamgpu_map_summary, grown on demand
+    size_t msum_bytes = 0;
     unsigned long long *stamps_dev = nullptr;  // diagnostic (SLAMGPU_STAMPS=1 + libslamgpu_stamps.so): UpdateArgs::stamps
     // persistent small-N step loop (slamgpu_run_observe, kernels.h: PersistArgs)
     bool persist_ok = true;              // SLAMGPU_NO_PERSIST=1 turns it off (diagnostic / tests: the per-step loop)
@@ -999,6 +1001,7 @@ void slamgpu_destroy(slamgpu_ctx *c) {
     if (c->hist_host) (void) hipHostFree(c->hist_host);
     if (c->stamps_dev) (void) hipFree(c->stamps_dev);
     if (c->peek_dev) (void) hipFree(c->peek_dev);
+    if (c->msum_dev) (void) hipFree(c->msum_dev);
     if (c->retired_dev) (void) hipFree(c->retired_dev);
     if (c->vote_w_dev) (void) hipFree(c->vote_w_dev);
     if (c->assoc_z_dev) (void) hipFree(c->assoc_z_dev);
@@ -4484,6 +4487,69 @@ int slamgpu_peek(slamgpu_ctx *c, int32_t first, int32_t stride, int32_t count, f
 int slamgpu_download(slamgpu_ctx *c, float *xv, float *Pv9, float *w, float *xf, float *Pf4) {
     if (int rc = check_ctx(c)) return rc;
     return slamgpu_download_range(c, 0, c->B.n, xv, Pv9, w, xf, Pf4);
+}
+
+int slamgpu_map_summary(slamgpu_ctx *c, int32_t first_slot, int32_t count, double *out, int32_t *holders) {
+    if (int rc = check_ctx(c)) return rc;
+    if (c->dist || c->cfg.n_particles_global != c->cfg.n_particles)
+        return fail(SLAMGPU_ERR_INVALID, "slamgpu_map_summary: single contexts only");
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    if (int rc = book_pull(c)) return rc;  // (device-driven steps: the number of slots lives on the device)
+    if (first_slot < 0 || count < 0 || (int64_t) first_slot + (int64_t) count > (int64_t) c->nf)
+        return fail(SLAMGPU_ERR_INVALID, "slots [%d, %d + %d) outside [0, %d)", first_slot, first_slot, count, c->nf);
+    if (count == 0) return 0;
+    if (!out) return fail(SLAMGPU_ERR_INVALID, "null output");
+    static_assert(SLAMGPU_MAP_STRIDE == kMapStride, "public / device summary layout");
+    // the particle set slamgpu_peek shows, and nothing more than it does to get there
+    if (int rc = flush_predict(c)) return rc;
+    if (int rc = flush_stages(c)) return rc;
+    if (int rc = sync_tables(c)) return rc;
+    const int tiles = (c->B.n + kMapTile - 1) / kMapTile;
+    // the slots go through the partials' table a chunk at a time: at most kMapScratch bytes of it, whatever the map's size
+    constexpr size_t kMapScratch = (size_t) 16 << 20;
+    const size_t per_slot = sizeof(double) * kMapFields * (size_t) tiles;
+    int fit = (int) std::max<size_t>(kMapSlots, kMapScratch / per_slot / kMapSlots * kMapSlots);
+    if (const char *e = getenv("SLAMGPU_MAP_CHUNK"))  // (diagnostic: the chunking of a large map on a small one)
+        fit = std::max(kMapSlots, atoi(e) / kMapSlots * kMapSlots);
+    const int chunk = std::min(fit, (count + kMapSlots - 1) / kMapSlots * kMapSlots);
+    // device staging: [out count][wpart tiles][part chunk][holders count]
+    const size_t M = (size_t) count;
+    const size_t o_out = 0, o_w = o_out + sizeof(double) * kMapStride * M, o_part = o_w + sizeof(double) * 2 * (size_t) tiles,
+                 o_hold = o_part + per_slot * (size_t) chunk, total = o_hold + sizeof(int32_t) * M;
+    if (total > c->msum_bytes) {
+        if (c->msum_dev) (void) hipFree(c->msum_dev);
+        c->msum_dev = nullptr;
+        c->msum_bytes = 0;
+        hipError_t e = hipMalloc((void **) &c->msum_dev, total);
+        if (e != hipSuccess) return fail(SLAMGPU_ERR_ALLOC, "hipMalloc(%zu): %s", total, hipGetErrorString(e));
+        c->msum_bytes = total;
+    }
+    c->B.slot = c->slot;
+    for (int at = 0; at < count; at += chunk) {
+        MapSummaryArgs A{};
+        A.first_slot = first_slot + at;
+        A.count = std::min(chunk, count - at);
+        A.tiles = tiles;
+        A.logw = c->cfg.log_weights;
+        A.part = reinterpret_cast<double *>(c->msum_dev + o_part);
+        A.wpart = reinterpret_cast<double *>(c->msum_dev + o_w);
+        A.out = reinterpret_cast<double *>(c->msum_dev + o_out) + (size_t) kMapStride * at;
+        A.holders = reinterpret_cast<int32_t *>(c->msum_dev + o_hold) + at;
+        {
+            Timed t(c, "map_summary");
+            c->k->map_summary(c->stream, c->B, c->ws, A);
+        }
+        HIP_TRY(hipGetLastError());
+        {
+            Timed t(c, "map_finish");
+            c->k->map_finish(c->stream, A);
+        }
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipMemcpyAsync(out, c->msum_dev + o_out, sizeof(double) * kMapStride * M, hipMemcpyDeviceToHost, c->stream));
+    if (holders) HIP_TRY(hipMemcpyAsync(holders, c->msum_dev + o_hold, sizeof(int32_t) * M, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return 0;
 }
 
 int slamgpu_upload(slamgpu_ctx *c, int32_t nf, const float *xv, const float *Pv9, const float *w, const float *xf,
