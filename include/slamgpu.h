@@ -414,6 +414,32 @@ int slamgpu_particle_sample_stats(slamgpu_ctx *ctx, int64_t out[3]);
  * max_count of them); *nz: the step's observations (0: none yet; an iteration of slamgpu_run_particle without observations leaves 0).
  * With sampling on or off.  Synchronises. */
 int slamgpu_particle_labels(slamgpu_ctx *ctx, int32_t *labels, int64_t max_count, int32_t *nz);
+/* Negative information (Thrun, Burgard, Fox, Probabilistic Robotics 13.6; the detection probability of RFS-SLAM, Mullane et al. 2011)
+ * for the per-particle steps (slamgpu_update_particle, slamgpu_update_labels, slamgpu_run_particle; every association mode, both
+ * methods, linear and log-weights).  The step's weight charges a particle p_new for every observation it leaves unexplained; with the
+ * view on it also charges p_miss for every landmark the particle holds, expects to see from its own pose and matched nothing with.  For
+ * a step with at least one observation, particle i (pose x, y, th as the step's association reads it, records as they stand BEFORE the
+ * step's update) and a slot j in use before the step that is not retired:
+ *     held(i, j)     the record is not absent;
+ *     inview(i, j)   dx = xf.x - x, dy = xf.y - y (float32): dx^2 + dy^2 < view_range^2 and dx cos th + dy sin th > view_front
+ *                    (the sensor's semicircle, core.cpp:250-273, shrunk by the caller's margins);
+ *     claimed(i, j)  the step gave particle i a fresh claim on j (the first of its observations labelled j).
+ * missed_i = #{ j : held, in view, not claimed } (slots opened in the step never count), and the particle's weight factor is multiplied
+ * missed_i times by p_miss (log-weights: ln p_miss added missed_i times), one multiplication at a time, so that every path and both
+ * builds give the same bits.  Nothing else changes: poses, Pv, records, labels, census and report are those of the step without it.
+ * Memoryless: the filter's resampling removes the hypotheses that keep missing, and the holders census reclaims their slots.  A step
+ * without observations makes no update and applies no factor.
+ * view_range = 0 (the default): off -- nothing is launched or allocated.  On: 0 < p_miss <= 1, view_range > 0, view_front >= 0, all
+ * finite, else SLAMGPU_ERR_INVALID (as for a context without SLAMGPU_FLAG_PARTICLE_MAPS).  p_miss = 1 with the view on only counts: the
+ * state stays bit for bit that of off.  Applies to calls made after it (iterations of slamgpu_run_particle already enqueued keep their
+ * setting).  slamgpu_associate(_ex) and the vote are untouched. */
+int slamgpu_set_particle_miss(slamgpu_ctx *ctx, float p_miss, float view_range, float view_front);
+/* Diagnostic: missed_i of the last step that counted (an iteration of slamgpu_run_particle without observations leaves the counts of
+ * the step before it), at most max_count of them; *n: the particles (0: no step has counted yet).  Synchronises. */
+int slamgpu_particle_missed(slamgpu_ctx *ctx, int32_t *count, int32_t max_count, int32_t *n);
+/* Cumulative since the context was created: [0] steps with the view on (and observations), [1] the sum of missed_i, [2] particles
+ * with missed_i > 0 (summed over the steps).  Synchronises. */
+int slamgpu_particle_miss_stats(slamgpu_ctx *ctx, int64_t out[3]);
 
 /* Retire landmarks from the gated association (round 6): landmarks ids[0 .. count) take no part in slamgpu_associate /
  * _associate_ex from now on -- no particle gates an observation against them, nothing votes for them -- and, never being
@@ -681,6 +707,10 @@ int slamgpu_dev_copy_async(slamgpu_ctx *ctx, void *dst, const void *src, uint64_
  * stamps`) writes them, and only for contexts created with SLAMGPU_STAMPS=1 in the environment; otherwise an error
  * (or zeros).  Synchronises. */
 int slamgpu_debug_stamps(slamgpu_ctx *ctx, uint64_t *out, int32_t max_blocks, int32_t *nblocks);
+
+/* Diagnostic of slamgpu_set_particle_miss: (particle, slot) records its kernel has looked at since the context was created -- with
+ * SLAMGPU_ASSOC_LISTS a workgroup passes over every slot whose box is out of reach of all of its particles.  Synchronises. */
+int slamgpu_particle_miss_visited(slamgpu_ctx *ctx, int64_t *records);
 
 #endif /* SLAMGPU_EXPERIMENTAL */
 

@@ -30,6 +30,7 @@ DECLARED_SYMBOLS = [
     "slamgpu_set_particle_excl_spacing", "slamgpu_particle_excl_radii",
     "slamgpu_set_particle_assoc_sampling", "slamgpu_particle_sample_stats", "slamgpu_particle_labels",
     "slamgpu_map_summary",
+    "slamgpu_set_particle_miss", "slamgpu_particle_missed", "slamgpu_particle_miss_stats", "slamgpu_particle_miss_visited",
 ]
 MAP_STRIDE = 9  # SLAMGPU_MAP_STRIDE
 ASSOC_AUTO, ASSOC_EXHAUSTIVE, ASSOC_GRID, ASSOC_LISTS = 0, 1, 2, 3
@@ -133,6 +134,11 @@ def load_library():
         L.slamgpu_particle_labels.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int32)]
     if hasattr(L, "slamgpu_map_summary"):
         L.slamgpu_map_summary.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
+    if hasattr(L, "slamgpu_set_particle_miss"):
+        L.slamgpu_set_particle_miss.argtypes = [C.c_void_p, C.c_float, C.c_float, C.c_float]
+        L.slamgpu_particle_missed.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]
+        L.slamgpu_particle_miss_stats.argtypes = [C.c_void_p, C.c_void_p]
+        L.slamgpu_particle_miss_visited.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
     L.slamgpu_genealogy_rows.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     L.slamgpu_persist_info.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
     if hasattr(L, "slamgpu_persist_status"):  # (an older build loaded through SLAMGPU_LIB for an A/B lacks the round-6 entries)
@@ -848,6 +854,28 @@ class SlamGpu:
         out = np.zeros(3, np.int64)
         _chk(self.L.slamgpu_particle_sample_stats(self.h, _ptr(out)))
         return dict(zip(("steps", "ambiguous", "moved"), (int(v) for v in out)))
+
+    def set_particle_miss(self, p_miss, view_range, view_front=0.0):
+        """negative information for the per-particle steps made after it (slamgpu_set_particle_miss): the factor p_miss for every slot a
+        particle holds within view_range and more than view_front ahead of its own pose without a fresh claim; view_range 0: off,
+        p_miss 1: count only"""
+        _chk(self.L.slamgpu_set_particle_miss(self.h, C.c_float(p_miss), C.c_float(view_range), C.c_float(view_front)))
+
+    def particle_missed(self):
+        """missed_i of the last step that counted (slamgpu_particle_missed): int32 [N], empty before the first"""
+        out = np.zeros(self.N, np.int32)
+        n = C.c_int32()
+        _chk(self.L.slamgpu_particle_missed(self.h, _ptr(out), self.N, C.byref(n)))
+        return out[:n.value].copy()
+
+    def particle_miss_stats(self):
+        """negative-information counters since the context was created (slamgpu_particle_miss_stats): dict(steps, missed, particles), and
+        visited: the (particle, slot) records the kernel looked at (slamgpu_particle_miss_visited)"""
+        out = np.zeros(3, np.int64)
+        _chk(self.L.slamgpu_particle_miss_stats(self.h, _ptr(out)))
+        v = C.c_int64()
+        _chk(self.L.slamgpu_particle_miss_visited(self.h, C.byref(v)))
+        return dict(steps=int(out[0]), missed=int(out[1]), particles=int(out[2]), visited=int(v.value))
 
     def particle_labels(self):
         """the last per-particle step's labels as its update consumed them (slamgpu_particle_labels): int32 [N, nz]"""

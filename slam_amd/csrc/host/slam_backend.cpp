@@ -20,6 +20,9 @@
 //                        (slamgpu_set_particle_excl_spacing): dense maps, where the fixed radius would forbid every new landmark.
 //                        -PARTICLE_ASSOC_SAMPLE 1: data association sampling (slamgpu_set_particle_assoc_sampling; 0, the default:
 //                        nearest neighbour); the summary then prints the sampling counters (slamgpu_particle_sample_stats).
+//                        -PARTICLE_MISS p -PARTICLE_MISS_MARGIN m (together): negative information (slamgpu_set_particle_miss) -- a
+//                        particle pays p for every landmark it holds closer than MAX_RANGE - m, more than m ahead of its own pose,
+//                        that it matched no observation of the step with (p = 1: count only); the summary prints the counters.
 //   -map best|posterior  the map reported at the end of a FastSLAM run.  best (default): the landmark count, with -assoc particle the best
 //                        particle's map.  posterior: one more line from slamgpu_map_summary, over ALL particles: the slots held by at
 //                        least half of the weight, how many true landmarks lie within 1 m of such a slot's weighted mean, how many such
@@ -79,6 +82,8 @@ static void usage(const char *a0) {
     printf("                        step's nearest other observation (default 0: the fixed radius)\n");
     printf("    -PARTICLE_ASSOC_SAMPLE 0|1  -assoc particle: draw an ambiguous observation's landmark in proportion to its likelihood\n");
     printf("                        (data association sampling, weights by the marginal likelihood; default 0: the nearest)\n");
+    printf("    -PARTICLE_MISS p -PARTICLE_MISS_MARGIN m  -assoc particle, both together: the weight factor p (0 < p <= 1; 1: count only) for every\n");
+    printf("                        landmark a particle holds within MAX_RANGE - m, more than m ahead of its own pose, and matched nothing with\n");
     printf("    -map best|posterior the map reported at the end: best (default; -assoc particle: the best particle's), or posterior: one more line,\n");
     printf("                        the landmark slots by the share of ALL particles' weight that holds them (slamgpu_map_summary; not with -gpus)\n");
     printf("    -gpus k             FastSLAM particle set distributed over k GPUs (k > devices: logical shards on device 0)\n");
@@ -282,6 +287,10 @@ static void print_particle_map(slamgpu_ctx *ctx, const Simulator &sim, int N, lo
     if (slamgpu_particle_sample_stats(ctx, st) == 0 && st[0] > 0)
         printf("association sampling: %lld steps, %lld ambiguous (particle, observation) pairs, %lld drawn away from the nearest\n", (long long) st[0],
                (long long) st[1], (long long) st[2]);
+    int64_t ms[3] = {0, 0, 0};
+    if (slamgpu_particle_miss_stats(ctx, ms) == 0 && ms[0] > 0)
+        printf("negative information: %lld steps, %lld held landmarks in view and unmatched (summed over particles and steps), %lld particles with one or more\n",
+               (long long) ms[0], (long long) ms[1], (long long) ms[2]);
 }
 
 // The wrapper's loop (fastslam2wrapper.cpp:51-117) for a headless run, batched: what the per-iteration form asks of the GPU
@@ -502,6 +511,13 @@ int main(int argc, char **argv) {
                         "known association)\n");
         return EXIT_FAILURE;
     }
+    const bool miss = !c.s("PARTICLE_MISS").empty() || !c.s("PARTICLE_MISS_MARGIN").empty();
+    const double miss_p = numkey("PARTICLE_MISS", 1.0), miss_m = numkey("PARTICLE_MISS_MARGIN", 0.0);
+    if (miss && (c.s("PARTICLE_MISS").empty() || c.s("PARTICLE_MISS_MARGIN").empty() || !particle || c.method == 0 || !(miss_m >= 0.0) ||
+                 !(miss_m < (double) c.MAX_RANGE) || !(miss_p > 0.0 && miss_p <= 1.0))) {
+        fprintf(stderr, "-PARTICLE_MISS p -PARTICLE_MISS_MARGIN m: both together, with -assoc particle and a FastSLAM method; 0 < p <= 1, 0 <= m < MAX_RANGE\n");
+        return EXIT_FAILURE;
+    }
     if (c.method != 0) {
         printf("%s\n\n", c.method == 2 ? "FastSLAM 2" : "FastSLAM 1");
         slamgpu_config g{};
@@ -551,6 +567,11 @@ int main(int argc, char **argv) {
                 slamgpu_destroy(ctx);
                 return EXIT_FAILURE;
             }
+        }
+        if (miss && slamgpu_set_particle_miss(ctx, (float) miss_p, (float) ((double) c.MAX_RANGE - miss_m), (float) miss_m) != 0) {
+            fprintf(stderr, "-PARTICLE_MISS: %s\n", slamgpu_last_error());
+            slamgpu_destroy(ctx);
+            return EXIT_FAILURE;
         }
         // the reference creates its accelerator object before the wrapper seeds rand() (SLAMBackendApplication.cpp:22-24,
         // slamwrapper.cpp:48-52); HIP runtime initialisation draws from libc rand(), so seed (again) only now

@@ -682,6 +682,28 @@ struct AssocSampleArgs : AssocRhoArgs {
     SampleArgs smp;
 };
 
+// Negative information (slamgpu_set_particle_miss): a particle pays p_miss for every slot it holds, expects to see from its own pose
+// and has no fresh claim on in this step.  missed_i = #{ l < nf, not retired : record (before the step's update) not absent, dx^2 + dy^2 <
+// range2 and dx cos th + dy sin th > front (float32; dx, dy from the particle's pose to the record), obs[uidx[l]][i] < 0 }; pp_missed_kernel
+// multiplies wf[i] by p_miss that many times (log-weights: adds ln p_miss), between pp_resolve and the update launch.
+struct PpMissArgs {
+    float p_miss, range2, front;  // range2 = view_range^2 (float32)
+    float reach;                  // view_range with a margin: the box test's radius (conservative against float32 rounding)
+    int32_t logw, nf;             // nf: slots in use before the step (device-driven: read from the packet)
+    const uint32_t *retired;      // [(cap_nf + 31) / 32] the mask (may be null)
+    const int32_t *uidx;          // [cap_nf] packet entry of a slot, -1: not in the step's packet
+    const int16_t *obs;           // PerParticle::obs
+    float *wf;                    // PerParticle::wf, multiplied in place
+    int32_t *missed;              // [ncap] missed_i
+    unsigned long long *stats;    // [4] cumulative: steps | sum of missed_i | particles with missed_i > 0 | (particle, slot) records looked at
+    const LmkBox *box;            // the slots' boxes as the step's lists used them, or null: every slot is looked at
+    // device-driven (slamgpu_run_particle; else null): nz from the observation (0: nothing), nf and the rows of the packet's slots before
+    // the step from the packet pp_book_kernel wrote -- it has moved erow / live of those slots to the row this update opens
+    const ObserveOut *obs_dev;
+    const ObsPacket *pkt;
+    int32_t cap_nf, pad;
+};
+
 // The association's rule for one call, as the launchers take it (host only: never a kernel argument).  The launchers pick the
 // instantiation from it: the exclusion rule (slamgpu_particle_assoc::excl_*, unique_ratio; excl_base + excl_per_m = 0: off), its radii
 // per observation (excl_radii; may be null, only with the rule on) in place of excl_base + excl_per_m * range, and data association
@@ -799,6 +821,8 @@ struct KernelTable {
     // slamgpu_map_summary (MapSummaryArgs): the partials of one chunk of slots, and their finishing pass.  Tables in sync; reads only
     void (*map_summary)(hipStream_t, const Buffers &, const WeightScratch &, const MapSummaryArgs &);
     void (*map_finish)(hipStream_t, const MapSummaryArgs &);
+    // slamgpu_set_particle_miss (PpMissArgs): the held, in-view, unclaimed slots of every particle into its weight factor; after pp_resolve
+    void (*pp_missed)(hipStream_t, const Buffers &, const PpMissArgs &);
 };
 
 const KernelTable *kernels_strict();

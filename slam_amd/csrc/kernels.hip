@@ -4968,12 +4968,166 @@ static void launch_map_finish(hipStream_t st, const MapSummaryArgs &A) {
     hipLaunchKernelGGL(map_finish_kernel, dim3((A.count + kSlots - 1) / kSlots), dim3(kBlock), 0, st, A);
 }
 
+// ---- slamgpu_set_particle_miss (kernels.h: PpMissArgs) -----------------------------------------------------------------------
+// Negative information: the slots a particle holds, expects to see from its own pose and has no fresh claim on, counted into its
+// weight factor.  One lane per particle, its pose and the heading's sine and cosine in registers across the slots; kMissT slots a trip,
+// their genealogy entries (one per genealogy row: the slots of a row share it), records and claims in flight together.  Which slots a
+// workgroup looks at at all is wave-uniform: not retired, not opened in this step, and -- when the step's lists left the slots' boxes
+// (PpMissArgs::box) -- a box within reach of the workgroup's pose bounds; a slot outside cannot be in range of any of its particles, so
+// the counts are those of the walk over every slot.
+// (DEV: slamgpu_run_particle -- pp_book_kernel has already moved erow / live of the packet's slots to the row this update opens, which
+// nothing has written yet: their rows before the step ride in the packet, and a slot on that row without a packet entry was opened now)
+constexpr int kMissT = 8;
+SLAM_DEV float2 read_record_xy(const Buffers &B, size_t S, int l, int b, int sl) {
+    const float4 *p = sl < 0 ? B.poolA + ((size_t) l * B.pool_cap + (sl & ~kPoolBit)) : B.lmkA[b] + ((size_t) l * S + sl);
+    return *reinterpret_cast<const float2 *>(p);
+}
+template <bool DEV>
+__global__ void __launch_bounds__(kBlock) pp_missed_kernel(Buffers B, PpMissArgs A) {
+    constexpr int kWaves = kBlock / kWave;
+    __shared__ float sh[4][kWaves];
+    __shared__ int sh_n[3][kWaves];
+    int nf = A.nf;
+    [[maybe_unused]] int e_new = -1;
+    [[maybe_unused]] const int32_t *__restrict__ prow = nullptr;
+    if constexpr (DEV) {
+        if (A.obs_dev->nz == 0) return;
+        nf = A.pkt->nf;
+        e_new = A.pkt->e_new;
+        prow = reinterpret_cast<const int32_t *>(A.pkt + 1) + 5 * (size_t) A.cap_nf;  // (fixed layout: idf[C] zf[2C] zn[2C] row[C])
+    }
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    const bool on = i < B.n;
+    const int cur = B.ctrl->live[B.slot];
+    const size_t S = (size_t) B.ncap;
+    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
+    const float4 pa = on ? B.poseA[cur][i] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    float sn, cs;
+    sincosf(pa.z, &sn, &cs);
+    // the workgroup's pose bounds (the box test)
+    float x0 = INFINITY, x1 = -INFINITY, y0 = INFINITY, y1 = -INFINITY;
+    const LmkBox *__restrict__ box = A.box;
+    if (box) {
+        if (on) x0 = x1 = pa.x, y0 = y1 = pa.y;
+#pragma unroll
+        for (int d = kWave / 2; d > 0; d >>= 1) {
+            x0 = fminf(x0, __shfl_xor(x0, d, kWave));
+            x1 = fmaxf(x1, __shfl_xor(x1, d, kWave));
+            y0 = fminf(y0, __shfl_xor(y0, d, kWave));
+            y1 = fmaxf(y1, __shfl_xor(y1, d, kWave));
+        }
+        if (lane == 0) {
+            sh[0][wave] = x0; sh[1][wave] = x1; sh[2][wave] = y0; sh[3][wave] = y1;
+        }
+        __syncthreads();
+        x0 = fminf(fminf(sh[0][0], sh[0][1]), fminf(sh[0][2], sh[0][3]));
+        x1 = fmaxf(fmaxf(sh[1][0], sh[1][1]), fmaxf(sh[1][2], sh[1][3]));
+        y0 = fminf(fminf(sh[2][0], sh[2][1]), fminf(sh[2][2], sh[2][3]));
+        y1 = fmaxf(fmaxf(sh[3][0], sh[3][1]), fmaxf(sh[3][2], sh[3][3]));
+    }
+    const uint32_t *__restrict__ retired = A.retired;
+    const int32_t *__restrict__ uidx = A.uidx;
+    const int16_t *__restrict__ obs = A.obs;
+    int missed = 0, visited = 0, row = -1, sl = 0;
+    for (int l0 = 0; l0 < nf; l0 += kMissT) {
+        bool use[kMissT];
+        int rw[kMissT], ks[kMissT];  // genealogy row before the step | live buffer << 30; packet entry
+        bool some = false;
+#pragma unroll
+        for (int t = 0; t < kMissT; t++) {
+            // (every word of the slot's bookkeeping is asked for at once, past the end the last slot's: the tests only combine them --
+            // one after the other they were five dependent scalar loads a trip, and at 10^5 particles a SIMD holds a wave and a half)
+            const int l = l0 + t, lc = min(l, nf - 1);
+            const uint32_t gone = retired ? (retired[lc >> 5] >> (lc & 31)) & 1u : 0u;
+            const int k = uidx[lc], er = B.erow[lc], lv = B.lmk_live[lc];
+            bool reach = true;
+            if (box) {
+                // (a record in range of a particle lies within view_range of it up to float32 rounding: reach carries the margin; the
+                // empty box of a retired slot compares false)
+                const LmkBox bx = box[lc];
+                reach = bx.xmin - x1 <= A.reach && x0 - bx.xmax <= A.reach && bx.ymin - y1 <= A.reach && y0 - bx.ymax <= A.reach;
+            }
+            int before = er | (lv ? kRowLiveBit : 0);
+            bool opened = false;  // in this step: nobody held it before
+            if constexpr (DEV) {
+                if (k >= 0) before = prow[k] & (kRowMask | kRowLiveBit);
+                else opened = er == e_new;
+            }
+            use[t] = l < nf && !gone && reach && !opened;
+            rw[t] = before;
+            ks[t] = k;
+            some |= use[t];
+        }
+        if (!some) continue;
+        int sls[kMissT];
+#pragma unroll
+        for (int t = 0; t < kMissT; t++) {
+            if (use[t] && (rw[t] & kRowMask) != row) {  // (uniform) the slots of one genealogy row share its entries
+                row = rw[t] & kRowMask;
+                sl = on ? B.gen[cur][gen_index(B.compact, S, row, (size_t) i)] : 0;
+            }
+            sls[t] = sl;
+        }
+        float2 xy[kMissT];
+        int cl[kMissT];
+#pragma unroll
+        for (int t = 0; t < kMissT; t++) {
+            xy[t] = make_float2(kAbsent, kAbsent);
+            cl[t] = -1;
+            if (use[t] && on) {
+                xy[t] = read_record_xy(B, S, l0 + t, (rw[t] & kRowLiveBit) ? 1 : 0, sls[t]);
+                if (ks[t] >= 0) cl[t] = obs[(size_t) ks[t] * S + i];
+            }
+        }
+#pragma unroll
+        for (int t = 0; t < kMissT; t++) {
+            if (!use[t]) continue;
+            visited++;
+            const float dx = xy[t].x - pa.x, dy = xy[t].y - pa.y;
+            const bool held = xy[t].x == xy[t].x;
+            const bool inview = dx * dx + dy * dy < A.range2 && dx * cs + dy * sn > A.front;
+            missed += (held && inview && cl[t] < 0) ? 1 : 0;
+        }
+    }
+    if (on) {
+        // (repeated multiplication, as pp_resolve_kernel forms the p_new factor: the same bits in both builds and on the host's restatement)
+        float f = A.wf[i];
+        const float lp = A.logw ? logf(A.p_miss) : 0.0f;
+        for (int q = 0; q < missed; q++) f = A.logw ? f + lp : f * A.p_miss;
+        A.wf[i] = f;
+    }
+    A.missed[i] = missed;
+    // the cumulative counters: the waves' counts meet in LDS, one atomic per workgroup and counter (one per wave was 1 600 atomics on
+    // one address at 10^5 particles: 0.02 ms of a 0.03 ms launch on example_webmap)
+    int tot = missed;
+#pragma unroll
+    for (int d = kWave / 2; d > 0; d >>= 1) tot += __shfl_xor(tot, d, kWave);
+    const unsigned long long some_missed = __ballot(missed > 0), act = __ballot(on);
+    if (lane == 0) {
+        sh_n[0][wave] = tot;
+        sh_n[1][wave] = (int) __popcll(some_missed);
+        sh_n[2][wave] = (int) __popcll(act);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int n[3];
+        for (int q = 0; q < 3; q++) n[q] = sh_n[q][0] + sh_n[q][1] + sh_n[q][2] + sh_n[q][3];
+        if (n[0]) atomicAdd(A.stats + 1, (unsigned long long) n[0]);
+        if (n[1]) atomicAdd(A.stats + 2, (unsigned long long) n[1]);
+        if (n[2] && visited) atomicAdd(A.stats + 3, (unsigned long long) visited * (unsigned long long) n[2]);  // (visited: the workgroup's)
+        if (blockIdx.x == 0) atomicAdd(A.stats, 1ull);
+    }
+}
+static void launch_pp_missed(hipStream_t st, const Buffers &B, const PpMissArgs &A) {
+    dispatch<2>([&](auto DEV) { hipLaunchKernelGGL(pp_missed_kernel<DEV>, dim3(B.ncap / kBlock), dim3(kBlock), 0, st, B, A); }, A.obs_dev != nullptr);
+}
+
 static const KernelTable kTable = {launch_update, launch_update_any, launch_update_persist, launch_resample, launch_resample_ref, launch_scan, launch_gather, launch_flatten, launch_identity, launch_decompact, launch_finish, launch_predict, launch_estimate, launch_jacobians, launch_kat, launch_observe, launch_observe_book, launch_associate,
                                    launch_shard_plan, launch_shard_pack, launch_shard_unpack, launch_shard_finish, launch_dist_gather, launch_dist_flags, launch_peek, launch_lmk_box, launch_assoc_grid, launch_assoc_lists, launch_vote_compact,
                                    launch_associate_grid, launch_jacobians_multi, launch_pp_census, launch_pp_resolve, launch_pp_holders,
                                    launch_pp_resample, launch_pp_gather, launch_pp_book,
                                    launch_lists_box, launch_lists_geom, launch_lists_build, launch_lists_walk, launch_excl_radii,
-                                   launch_map_summary, launch_map_finish};
+                                   launch_map_summary, launch_map_finish, launch_pp_missed};
 
 }  // namespace SLAM_KNS
 

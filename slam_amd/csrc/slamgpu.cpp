@@ -318,6 +318,12 @@ struct slamgpu_ctx {
     size_t das_ratio_cap = 0;
     unsigned long long *das_stats_dev = nullptr;
     SampleArgs das_step{};  // the sampling arguments of the step being associated (AssocRule::smp points here: particle_rule)
+    // negative information (slamgpu_set_particle_miss; pm_range = 0: off): the factor and the view, the counts of the last step that
+    // made them ([ncap]; pm_have: some step has) and the cumulative counters (PpMissArgs::stats); nothing is allocated while it is off
+    float pm_p = 1.0f, pm_range = 0.0f, pm_front = 0.0f;
+    int32_t *pm_cnt_dev = nullptr;
+    unsigned long long *pm_stats_dev = nullptr;
+    bool pm_have = false;
     // the observations of the last per-particle step (slamgpu_particle_labels): the host-driven call's count, or -1: the device-driven
     // iteration's (ObserveOut::nz)
     int32_t pp_lab_nz = 0;
@@ -1013,7 +1019,7 @@ void slamgpu_destroy(slamgpu_ctx *c) {
     if (c->pp_wf_dev) (void) hipFree(c->pp_wf_dev);
     if (c->pp_any_dev) (void) hipFree(c->pp_any_dev);
     for (void *p_ : {(void *) c->pp_st_dev, (void *) c->pp_words_dev, (void *) c->pp_pkt_dev, (void *) c->pp_report_dev, (void *) c->lstats_dev, (void *) c->excl_rho_dev,
-                     (void *) c->das_ratio_dev, (void *) c->das_stats_dev})
+                     (void *) c->das_ratio_dev, (void *) c->das_stats_dev, (void *) c->pm_cnt_dev, (void *) c->pm_stats_dev})
         if (p_) (void) hipFree(p_);
     for (void *p_ : {(void *) c->box_dev, (void *) c->assoc_ids_dev, (void *) c->cell_start_dev, (void *) c->cell_fill_dev, (void *) c->items_dev,
                      (void *) c->geom_dev})
@@ -3308,7 +3314,43 @@ int pp_reserve_particles(slamgpu_ctx *c, int nz, size_t rows) {
     }
     if (!c->pp_wf_dev) HIP_TRY(hipMalloc((void **) &c->pp_wf_dev, sizeof(float) * S));
     if (!c->pp_any_dev) HIP_TRY(hipMalloc((void **) &c->pp_any_dev, S));
+    if (c->pm_range > 0.0f && !c->pm_stats_dev) {  // (slamgpu_set_particle_miss: here, before any bookkeeping of the step moves)
+        if (!c->pm_cnt_dev) {
+            HIP_TRY(hipMalloc((void **) &c->pm_cnt_dev, sizeof(int32_t) * S));
+            HIP_TRY(hipMemset(c->pm_cnt_dev, 0, sizeof(int32_t) * S));
+        }
+        unsigned long long *p = nullptr;
+        HIP_TRY(hipMalloc((void **) &p, sizeof(unsigned long long) * 4));
+        HIP_TRY(hipMemset(p, 0, sizeof(unsigned long long) * 4));
+        c->pm_stats_dev = p;
+    }
     return 0;
+}
+
+// slamgpu_set_particle_miss: the launch between the resolve and the update (kernels.h: PpMissArgs).  nf / retired / uidx: the slots
+// before the step, the mask and the step's packet entries; boxes: the step's lists left the slots' boxes; dev: device-driven
+void pp_missed(slamgpu_ctx *c, int nf, const uint32_t *retired, const int32_t *uidx, bool boxes, const PpArgs *dev) {
+    if (!(c->pm_range > 0.0f)) return;
+    PpMissArgs A{};
+    A.p_miss = c->pm_p;
+    A.range2 = c->pm_range * c->pm_range;
+    A.front = c->pm_front;
+    A.reach = c->pm_range * 1.0001f;
+    A.logw = c->cfg.log_weights;
+    A.nf = nf;
+    A.retired = retired;
+    A.uidx = uidx;
+    A.obs = c->pp_obs_dev;
+    A.wf = c->pp_wf_dev;
+    A.missed = c->pm_cnt_dev;
+    A.stats = c->pm_stats_dev;
+    A.box = boxes ? c->box_dev : nullptr;
+    A.obs_dev = dev ? dev->obs : nullptr;
+    A.pkt = dev ? dev->pkt : nullptr;
+    A.cap_nf = c->B.cap_nf;
+    Timed t(c, "particle_missed");
+    c->k->pp_missed(c->stream, c->B, A);
+    c->pm_have = true;
 }
 
 int pp_reserve(slamgpu_ctx *c, int nz, size_t rows) {
@@ -3461,6 +3503,8 @@ int do_update_particle(slamgpu_ctx *c, const float *z, int32_t nz, const float R
         c->k->pp_resolve(c->stream, c->pp_lab_dev, N, nz, c->B.ncap, first_dev, news_dev, m, n, opt->p_new, c->cfg.log_weights, c->pp_obs_dev,
                          c->pp_wf_dev, c->pp_any_dev, ratio, nullptr);
     }
+    // (the records as they stand before the update: the device's tables are still those of sync_tables above)
+    pp_missed(c, nf0, c->retired_dev, first_dev, census_taken && opt->mode == SLAMGPU_ASSOC_LISTS, nullptr);
     HIP_TRY(hipGetLastError());
     c->obs_step++;
     c->pp_lab_nz = nz;
@@ -4032,6 +4076,7 @@ int pp_dev_iteration(slamgpu_ctx *c, int32_t nc, const float *controls, const fl
         c->k->pp_resolve(c->stream, c->pp_lab_dev, c->B.n, 0, c->B.ncap, P.uidx, P.newk, 0, 0, P.p_new, P.logw, c->pp_obs_dev, c->pp_wf_dev, c->pp_any_dev,
                          rule.smp ? c->das_ratio_dev : nullptr, &P);
     }
+    pp_missed(c, 0, P.retired, P.uidx, bound >= 0, &P);
     UpdateArgs U{};
     U.method = c->cfg.method;
     U.m = c->B.cap_nf;  // (upper bounds: the kernel reads the packet's header)
@@ -4248,6 +4293,63 @@ int slamgpu_particle_sample_stats(slamgpu_ctx *c, int64_t out[3]) {
         HIP_TRY(hipMemcpy(h, c->das_stats_dev, sizeof h, hipMemcpyDeviceToHost));
     }
     for (int k = 0; k < 3; k++) out[k] = (int64_t) h[k];
+    return 0;
+}
+
+int slamgpu_set_particle_miss(slamgpu_ctx *c, float p_miss, float view_range, float view_front) {
+    if (int rc = check_ctx(c)) return rc;
+    if (!(c->cfg.flags & SLAMGPU_FLAG_PARTICLE_MAPS))
+        return fail(SLAMGPU_ERR_INVALID, "slamgpu_set_particle_miss: create the context with SLAMGPU_FLAG_PARTICLE_MAPS");
+    if (!std::isfinite(p_miss) || !std::isfinite(view_range) || !std::isfinite(view_front) || view_range < 0.0f)
+        return fail(SLAMGPU_ERR_INVALID, "slamgpu_set_particle_miss: p_miss, view_range >= 0 and view_front must be finite");
+    if (view_range > 0.0f && (!(p_miss > 0.0f && p_miss <= 1.0f) || !(view_front >= 0.0f)))
+        return fail(SLAMGPU_ERR_INVALID, "slamgpu_set_particle_miss: 0 < p_miss <= 1 and view_front >= 0 (p_miss %g, view_front %g)", (double) p_miss,
+                    (double) view_front);
+    c->pm_p = p_miss;  // (launches already enqueued carry the setting they were made with)
+    c->pm_range = view_range;
+    c->pm_front = view_front;
+    return 0;
+}
+
+int slamgpu_particle_missed(slamgpu_ctx *c, int32_t *count, int32_t max_count, int32_t *n) {
+    if (int rc = check_ctx(c)) return rc;
+    if (!n || (max_count > 0 && !count)) return fail(SLAMGPU_ERR_INVALID, "slamgpu_particle_missed: null output");
+    *n = 0;
+    if (!c->pm_have) return 0;
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    const int32_t k = std::min(c->B.n, std::max(max_count, 0));
+    if (k > 0) HIP_TRY(hipMemcpy(count, c->pm_cnt_dev, sizeof(int32_t) * (size_t) k, hipMemcpyDeviceToHost));
+    *n = c->B.n;
+    return 0;
+}
+
+namespace {
+int pm_stats(slamgpu_ctx *c, unsigned long long h[4]) {
+    memset(h, 0, sizeof(unsigned long long) * 4);
+    if (!c->pm_stats_dev) return 0;
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipMemcpy(h, c->pm_stats_dev, sizeof(unsigned long long) * 4, hipMemcpyDeviceToHost));
+    return 0;
+}
+}  // namespace
+
+int slamgpu_particle_miss_stats(slamgpu_ctx *c, int64_t out[3]) {
+    if (int rc = check_ctx(c)) return rc;
+    if (!out) return fail(SLAMGPU_ERR_INVALID, "slamgpu_particle_miss_stats: null output");
+    unsigned long long h[4];
+    if (int rc = pm_stats(c, h)) return rc;
+    for (int k = 0; k < 3; k++) out[k] = (int64_t) h[k];
+    return 0;
+}
+
+int slamgpu_particle_miss_visited(slamgpu_ctx *c, int64_t *records) {
+    if (int rc = check_ctx(c)) return rc;
+    if (!records) return fail(SLAMGPU_ERR_INVALID, "slamgpu_particle_miss_visited: null output");
+    unsigned long long h[4];
+    if (int rc = pm_stats(c, h)) return rc;
+    *records = (int64_t) h[3];
     return 0;
 }
 
