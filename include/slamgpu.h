@@ -506,6 +506,66 @@ int slamgpu_peek(slamgpu_ctx *ctx, int32_t first, int32_t stride, int32_t count,
  * for slots outside [0, slamgpu_num_landmarks)); count == 0 does nothing.  Synchronises. */
 #define SLAMGPU_MAP_STRIDE 9
 int slamgpu_map_summary(slamgpu_ctx *ctx, int32_t first_slot, int32_t count, double *out, int32_t *holders);
+
+/* ---- path posterior: recorded ancestry, traces, the smoothed path ---------------------------------------------------
+ * FastSLAM's posterior is over paths and maps; these entry points report the path half.  "The set" at a moment is what
+ * slamgpu_peek(ctx, 0, 1, N, ...) would show at that moment (queued predicts flushed, the outstanding resampling stage run, a
+ * pending gather read through its ancestors).
+ *
+ * While recording is on the context keeps origin[k]: the particle of the NEWEST RECORD's set that particle k of the present set
+ * descends from.  It is the identity right after a record and is composed with the ancestor array at every resample
+ * (origin'[k] = origin[keep[k]]), whichever entry point made the update (decided on the device: no synchronisation is added).
+ *
+ * Record r (numbered from 0 when recording is enabled, never renumbered) holds, for every particle k of the set at the time of the
+ * record,
+ *     pose_r[k]     x, y, theta: the float32 bits slamgpu_peek would return
+ *     parent_r[k]   the particle of record r - 1's set that k descends from (origin[k] at the time of the record; the identity for
+ *                   r = 0, and whenever no update between the two records resampled).
+ * The LINEAGE of present particle i, with R - 1 the newest record: a(R - 1, i) = origin[i] and a(r - 1, i) = parent_r[a(r, i)],
+ * down to the oldest retained record.  Records live in a ring of `capacity` records in device memory (16 bytes per particle and
+ * record); when it is full the oldest record is dropped: records [first, next) are retained.  A full ring never refuses a step, and
+ * its capacity is independent of the estimate history's.
+ *
+ * Rules.  The filter does not notice the recorder: with recording on, every pose, record, weight, history entry and ancestor of a
+ * run is bit for bit that of the same run with it off.  While it is on, an update runs its resampling stage at the end of the call
+ * instead of inside the next update launch, slamgpu_run_observe takes its loop of launches where it would take the persistent
+ * one-launch loop (as SLAMGPU_NO_PERSIST=1 does), and slamgpu_run_particle is refused (SLAMGPU_ERR_INVALID, nothing applied: its
+ * resampling decisions are known to the device only).  slamgpu_upload replaces the set: the retained records are dropped
+ * (first = next, the numbering continues) and origin is the identity.  Single contexts only.  With recording never enabled no
+ * kernel of it is launched and nothing is allocated.
+ * slamgpu_path_fetch, _trace and _summary rewrite nothing, like slamgpu_peek: the state the next step works on is bit for bit what
+ * it would have been without the call.  They synchronise.  Records outside [first, next), a particle outside [-1, N), a negative
+ * count, recording off: SLAMGPU_ERR_INVALID, outputs untouched; count == 0 does nothing.
+ *
+ * What it costs (MI355X, example_webmap, fast build, FastSLAM 2; profiles/path.txt): see DESIGN.md section 7d. */
+/* capacity > 0: start (or restart: existing records are dropped, numbering restarts at 0) recording with room for `capacity`
+ * records; capacity == 0: stop and free.  SLAMGPU_ERR_ALLOC if the ring does not fit (the recording stays as it was). */
+int slamgpu_path_enable(slamgpu_ctx *ctx, int32_t capacity);
+/* Append a record of the set as it stands now.  Done automatically by slamgpu_step and slamgpu_step_observe when
+ * record_estimate != 0 and by every iteration of slamgpu_run_observe -- exactly where those append a history entry, so that for a
+ * run driven by them record r and history entry r (counted from the enable) belong to the same step.  Callers of slamgpu_update /
+ * _update_particle / _update_labels / _estimate_async call it themselves. */
+int slamgpu_path_record(slamgpu_ctx *ctx);
+/* Records [*first, *next) are retained; *capacity as enabled (0: off).  Any pointer may be NULL. */
+int slamgpu_path_info(slamgpu_ctx *ctx, int64_t *first, int64_t *next, int32_t *capacity);
+/* Record r as stored: xyt[3 N] particle-major, parent[N] (either may be NULL).  For tests and for a caller's own smoother. */
+int slamgpu_path_fetch(slamgpu_ctx *ctx, int64_t r, float *xyt, int32_t *parent);
+/* The path present particle `particle` descends from, through records [first, first + count): xyt[3 count] and index[count]
+ * (= a(r, particle); either may be NULL).  particle == -1: the particle slamgpu_estimate takes its heading from (the first with
+ * the strictly greatest weight in the present set).  One dependent chain from the newest record down to `first`. */
+int slamgpu_path_trace(slamgpu_ctx *ctx, int32_t particle, int64_t first, int32_t count, float *xyt, int32_t *index);
+/* The smoothed path over ALL present particles.  With w^_i the normalised weights of the present set exactly as
+ * slamgpu_map_summary defines them (linear, log-weights, 1/N under a pending gather) and a_i = a(r, i):
+ *   out[r - first][0..1]  sum_i w^_i (x, y) of pose_r[a_i]
+ *                [2..4]  sum_i w^_i d d^T about that mean: xx, xy, yy
+ *                [5..6]  sum_i w^_i cos(theta), sum_i w^_i sin(theta)   (theta promoted to double; the caller takes atan2)
+ *   distinct[r - first]  |{ a(r, i) : i }|, exact                        (may be NULL)
+ * Weights that sum to zero or to nothing finite: every double NaN, return 0, distinct still exact (SLAMGPU_STATUS_DEGENERATE's
+ * convention).  Sums in double in a fixed order: the same state gives the same bits on every call.  The descendants' weights are
+ * pushed down the records in 64-bit fixed point (units of 2^-62 of the normalised weight: a weight below 2^-63 of the total counts
+ * in `distinct` and not in the sums), one launch per record from the newest one down to `first`. */
+#define SLAMGPU_PATH_STRIDE 7
+int slamgpu_path_summary(slamgpu_ctx *ctx, int64_t first, int32_t count, double *out, int32_t *distinct);
 int slamgpu_upload(slamgpu_ctx *ctx, int32_t nf, const float *xv, const float *Pv9, const float *w, const float *xf,
                    const float *Pf4);
 int slamgpu_sync(slamgpu_ctx *ctx);

@@ -31,8 +31,10 @@ DECLARED_SYMBOLS = [
     "slamgpu_set_particle_assoc_sampling", "slamgpu_particle_sample_stats", "slamgpu_particle_labels",
     "slamgpu_map_summary",
     "slamgpu_set_particle_miss", "slamgpu_particle_missed", "slamgpu_particle_miss_stats", "slamgpu_particle_miss_visited",
+    "slamgpu_path_enable", "slamgpu_path_record", "slamgpu_path_info", "slamgpu_path_fetch", "slamgpu_path_trace", "slamgpu_path_summary",
 ]
 MAP_STRIDE = 9  # SLAMGPU_MAP_STRIDE
+PATH_STRIDE = 7  # SLAMGPU_PATH_STRIDE
 ASSOC_AUTO, ASSOC_EXHAUSTIVE, ASSOC_GRID, ASSOC_LISTS = 0, 1, 2, 3
 FLAG_DEVICE_OBSERVE = 1
 FLAG_NO_REFERENCE_RESAMPLE = 2
@@ -134,6 +136,13 @@ def load_library():
         L.slamgpu_particle_labels.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int32)]
     if hasattr(L, "slamgpu_map_summary"):
         L.slamgpu_map_summary.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
+    if hasattr(L, "slamgpu_path_enable"):
+        L.slamgpu_path_enable.argtypes = [C.c_void_p, C.c_int32]
+        L.slamgpu_path_record.argtypes = [C.c_void_p]
+        L.slamgpu_path_info.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
+        L.slamgpu_path_fetch.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+        L.slamgpu_path_trace.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]
+        L.slamgpu_path_summary.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]
     if hasattr(L, "slamgpu_set_particle_miss"):
         L.slamgpu_set_particle_miss.argtypes = [C.c_void_p, C.c_float, C.c_float, C.c_float]
         L.slamgpu_particle_missed.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]
@@ -530,6 +539,51 @@ class SlamGpu:
         holders = np.zeros(max(count, 0), np.int32)
         _chk(self.L.slamgpu_map_summary(self.h, first, count, _ptr(out), _ptr(holders)))
         return dict(share=out[:, 0].copy(), mean=out[:, 1:3].copy(), scatter=out[:, 3:6].copy(), pf=out[:, 6:9].copy(), holders=holders)
+
+    def path_enable(self, capacity):
+        """slamgpu_path_enable: record the path posterior in a ring of `capacity` records (0: stop and free)"""
+        _chk(self.L.slamgpu_path_enable(self.h, int(capacity)))
+
+    def path_record(self):
+        """slamgpu_path_record: append a record of the set as it stands (step / step_observe / run_observe do it themselves)"""
+        _chk(self.L.slamgpu_path_record(self.h))
+
+    def path_info(self):
+        """(first, next, capacity): records [first, next) are retained (slamgpu_path_info)"""
+        a, b, cap = C.c_int64(), C.c_int64(), C.c_int32()
+        _chk(self.L.slamgpu_path_info(self.h, C.byref(a), C.byref(b), C.byref(cap)))
+        return a.value, b.value, cap.value
+
+    def path_fetch(self, r):
+        """record r as stored: (xyt[N, 3] float32, parent[N] int32) (slamgpu_path_fetch)"""
+        xyt = np.zeros((self.N, 3), np.float32)
+        parent = np.zeros(self.N, np.int32)
+        _chk(self.L.slamgpu_path_fetch(self.h, int(r), _ptr(xyt), _ptr(parent)))
+        return xyt, parent
+
+    def _path_window(self, first, count):
+        a, b, _ = self.path_info()
+        first = a if first is None else int(first)
+        return first, (b - first if count is None else int(count))
+
+    def path_trace(self, particle=-1, first=None, count=None):
+        """the path present particle `particle` (-1: the one estimate() takes its heading from) descends from, through records
+        first .. first + count - 1 (default: all retained): (xyt[count, 3] float32, index[count] int32) (slamgpu_path_trace)"""
+        first, count = self._path_window(first, count)
+        xyt = np.zeros((max(count, 0), 3), np.float32)
+        index = np.zeros(max(count, 0), np.int32)
+        _chk(self.L.slamgpu_path_trace(self.h, int(particle), first, count, _ptr(xyt), _ptr(index)))
+        return xyt, index
+
+    def path_summary(self, first=None, count=None):
+        """slamgpu_path_summary: the smoothed path over all present particles through records first .. first + count - 1 (default: all
+        retained): mean[count, 2], scatter[count, 3] about it (xx, xy, yy), cs[count, 2] (the weighted sums of cos / sin of the heading) and
+        distinct[count] (ancestors in each record that still have a descendant); rewrites no state"""
+        first, count = self._path_window(first, count)
+        out = np.zeros((max(count, 0), PATH_STRIDE), np.float64)
+        distinct = np.zeros(max(count, 0), np.int32)
+        _chk(self.L.slamgpu_path_summary(self.h, first, count, _ptr(out), _ptr(distinct)))
+        return dict(mean=out[:, 0:2].copy(), scatter=out[:, 2:5].copy(), cs=out[:, 5:7].copy(), distinct=distinct)
 
     def upload(self, st):
         nf = int(st["nf"])

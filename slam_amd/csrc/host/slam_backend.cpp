@@ -33,6 +33,11 @@
 //   -plotstride <k>      particles / feature particles sent per step are decimated to every k-th particle (default: as
 //                        many as keep a frame below ~2 000 particles; the reference sends all of them: N = 10^5 would be
 //                        1.6 MB of poses and 56 MB of feature points per control step)
+//   -path none|smoothed  smoothed: the path posterior is recorded, one record per observation step (slamgpu_path_*; -PATH_RECORDS n records
+//                        are kept, default 4096), and one more line is printed at the end: the records kept, the mean distance of the
+//                        SMOOTHED path (the mean over the surviving particles of the path each descends from) to the true path beside that
+//                        of the filtered estimates of the same steps, and how many distinct particles of 1 / 10 / 100 records back and of
+//                        the oldest record still have a descendant.  FastSLAM on one GPU; not with -assoc particle -observe device.
 //   -gpus <k>            FastSLAM over k GPUs from this one process (slamgpu_dist_group_*): shard g = particles
 //                        [g N/k, (g+1) N/k) on device g, one launch + one RCCL all-gather per observation step, the set is
 //                        never moved; results do not depend on k.  k above the number of devices: logical shards on device 0
@@ -86,6 +91,9 @@ static void usage(const char *a0) {
     printf("                        landmark a particle holds within MAX_RANGE - m, more than m ahead of its own pose, and matched nothing with\n");
     printf("    -map best|posterior the map reported at the end: best (default; -assoc particle: the best particle's), or posterior: one more line,\n");
     printf("                        the landmark slots by the share of ALL particles' weight that holds them (slamgpu_map_summary; not with -gpus)\n");
+    printf("    -path none|smoothed smoothed: record the path posterior (one record per observation step, -PATH_RECORDS n of them kept, default 4096)\n");
+    printf("                        and print one more line: the smoothed path's distance to the true path beside the filtered estimates', and the\n");
+    printf("                        distinct ancestors 1 / 10 / 100 records back (slamgpu_path_summary; FastSLAM, one GPU, not -assoc particle -observe device)\n");
     printf("    -gpus k             FastSLAM particle set distributed over k GPUs (k > devices: logical shards on device 0)\n");
     printf("    -observe host|device  where the observation of a step is made: host (default) or on the GPU (the packet never leaves\n");
     printf("                        device memory: slamgpu_step_observe; -rng philox, known association, no -plot; with -assoc particle:\n");
@@ -258,6 +266,51 @@ static void print_posterior_map(slamgpu_ctx *ctx, const Simulator &sim) {
            confident, covered, sim.map.nlm, stray, minority, dead);
 }
 
+// -path smoothed: the recorded path posterior (slamgpu_path_*).  Record r belongs to observation step r: g_path_steps[r] holds that
+// step's true position and filtered estimate (x, y each)
+static int g_path_records = 0;  // 0: off
+static std::vector<double> g_path_steps;
+static void path_step(const float xt[3], const double est[3]) {
+    if (!g_path_records) return;
+    g_path_steps.push_back(xt[0]);
+    g_path_steps.push_back(xt[1]);
+    g_path_steps.push_back(est[0]);
+    g_path_steps.push_back(est[1]);
+}
+static void print_smoothed_path(slamgpu_ctx *ctx) {
+    if (!g_path_records) return;
+    int64_t first = 0, next = 0;
+    if (slamgpu_path_info(ctx, &first, &next, nullptr) != 0) {
+        fprintf(stderr, "slamgpu: %s\n", slamgpu_last_error());
+        return;
+    }
+    const int64_t n = next - first;
+    if (n <= 0 || (size_t) next * 4 > g_path_steps.size()) {
+        printf("smoothed path: no records\n");
+        return;
+    }
+    std::vector<double> sum((size_t) SLAMGPU_PATH_STRIDE * (size_t) n);
+    std::vector<int32_t> distinct((size_t) n);
+    if (slamgpu_path_summary(ctx, first, (int32_t) n, sum.data(), distinct.data()) != 0) {
+        fprintf(stderr, "slamgpu: %s\n", slamgpu_last_error());
+        return;
+    }
+    if (sum[0] != sum[0]) {
+        printf("smoothed path: not available, the weights are degenerate (SLAMGPU_STATUS_DEGENERATE: their sum is zero or not finite)\n");
+        return;
+    }
+    double ds = 0, df = 0;
+    for (int64_t r = first; r < next; r++) {
+        const double *e = sum.data() + (size_t) SLAMGPU_PATH_STRIDE * (size_t) (r - first), *t = g_path_steps.data() + 4 * (size_t) r;
+        ds += std::sqrt((e[0] - t[0]) * (e[0] - t[0]) + (e[1] - t[1]) * (e[1] - t[1]));
+        df += std::sqrt((t[2] - t[0]) * (t[2] - t[0]) + (t[3] - t[1]) * (t[3] - t[1]));
+    }
+    auto back = [&](int64_t k) -> std::string { return k < n ? std::to_string(distinct[(size_t) (n - 1 - k)]) : std::string("-"); };
+    printf("smoothed path: %lld records kept, mean distance to the true path %.4f m (filtered estimates of the same steps: %.4f m); distinct ancestors "
+           "1 / 10 / 100 records back %s / %s / %s, at the oldest record %d\n",
+           (long long) n, ds / (double) n, df / (double) n, back(1).c_str(), back(10).c_str(), back(100).c_str(), (int) distinct[0]);
+}
+
 // -assoc particle: the map of the best (largest-weight) particle: what a FastSLAM with per-particle association reports
 static void print_particle_map(slamgpu_ctx *ctx, const Simulator &sim, int N, long pp_opened, long pp_reused, long pp_dropped, int pp_most) {
     const int slots = slamgpu_num_landmarks(ctx);
@@ -336,6 +389,7 @@ static int run_batched(Simulator &sim, slamgpu_ctx *ctx, bool observe_dev, long 
         for (int t = 0; t < got && t < (int) rows.size(); t++) {
             const ObsRow &o = rows[(size_t) t];
             for (int q = 0; q < 3; q++) est[q] = xyt[3 * (size_t) t + q];
+            path_step(o.xt, est);
             sq_err += (est[0] - o.xt[0]) * (est[0] - o.xt[0]) + (est[1] - o.xt[1]) * (est[1] - o.xt[1]);
             if (log) fprintf(log, "%ld,%.6f,%.6f,%.6f,%.6f,%.6f,%.6f,%.1f\n", o.iter, o.xt[0], o.xt[1], o.xt[2], est[0], est[1], est[2], o.us);
         }
@@ -431,6 +485,7 @@ static int run_batched(Simulator &sim, slamgpu_ctx *ctx, bool observe_dev, long 
     if (popt) print_particle_map(ctx, sim, sim.conf.NPARTICLES, pp_opened, pp_reused, pp_dropped, pp_most);
     else printf("landmarks in map: %d\n", slamgpu_num_landmarks(ctx));
     print_posterior_map(ctx, sim);
+    if (!rc) print_smoothed_path(ctx);
     return rc ? EXIT_FAILURE : 0;
 }
 
@@ -455,6 +510,28 @@ int main(int argc, char **argv) {
         }
         g_map_posterior = m == "posterior";
         sim.conf.kv.erase("map");
+        // ... and so is -path (with -PATH_RECORDS).  What it cannot do is refused here, from the arguments alone
+        const std::string p = sim.conf.s("path"), pr = sim.conf.s("PATH_RECORDS");
+        if (!p.empty() && p != "none" && p != "smoothed") {
+            fprintf(stderr, "-path none|smoothed\n");
+            return EXIT_FAILURE;
+        }
+        if (p == "smoothed") {
+            g_path_records = pr.empty() ? 4096 : atoi(pr.c_str());
+            const std::string gp = sim.conf.s("gpus");
+            const char *why = nullptr;
+            if (g_path_records <= 0) why = "-PATH_RECORDS needs a positive number of records";
+            else if (sim.conf.method == 0) why = "FastSLAM only (the EKF has one path)";
+            else if (!gp.empty() && atoi(gp.c_str()) != 1) why = "single GPU only (slamgpu_path_* have no distributed form)";
+            else if (sim.conf.s("assoc") == "particle" && sim.conf.s("observe") == "device")
+                why = "not with -assoc particle -observe device (slamgpu_run_particle keeps its resampling decisions on the device)";
+            if (why) {
+                fprintf(stderr, "-path smoothed: %s\n", why);
+                return EXIT_FAILURE;
+            }
+        }
+        sim.conf.kv.erase("path");
+        sim.conf.kv.erase("PATH_RECORDS");
     }
     const Conf &c = sim.conf;
     printf("map: %s\n", c.map_path.c_str());
@@ -570,6 +647,11 @@ int main(int argc, char **argv) {
         }
         if (miss && slamgpu_set_particle_miss(ctx, (float) miss_p, (float) ((double) c.MAX_RANGE - miss_m), (float) miss_m) != 0) {
             fprintf(stderr, "-PARTICLE_MISS: %s\n", slamgpu_last_error());
+            slamgpu_destroy(ctx);
+            return EXIT_FAILURE;
+        }
+        if (g_path_records && slamgpu_path_enable(ctx, g_path_records) != 0) {
+            fprintf(stderr, "-path smoothed: %s\n", slamgpu_last_error());
             slamgpu_destroy(ctx);
             return EXIT_FAILURE;
         }
@@ -777,6 +859,10 @@ int main(int argc, char **argv) {
                 }
             }
             if (!rc) rc = slamgpu_estimate(ctx, est);
+            if (!rc && r == 1 && g_path_records) {  // one record per observation step (these loops make their updates themselves)
+                rc = slamgpu_path_record(ctx);
+                path_step(sim.xTrue, est);
+            }
             if (rc) {
                 fprintf(stderr, "slamgpu: %s\n", slamgpu_last_error());
                 break;
@@ -849,6 +935,7 @@ int main(int argc, char **argv) {
     } else if (ctx) printf("landmarks in map: %d\n", slamgpu_num_landmarks(ctx));
     else printf("landmarks in map: %d\n", ekf.num_features());
     if (ctx) print_posterior_map(ctx, sim);
+    if (ctx && !rc) print_smoothed_path(ctx);
     if (plot.active()) {
         plot.endPlot();
         plot.close();

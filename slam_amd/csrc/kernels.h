@@ -549,6 +549,55 @@ struct MapSummaryArgs {
     int32_t *holders;           // [count]
 };
 
+// Path posterior (slamgpu_path_*): a ring of records in device memory and the walks over it.  Record r of the ring holds, for every
+// particle k of the set at the time of the record, one float4: x, y, theta as slamgpu_peek shows them and, in .w, the BITS of
+// parent_r[k] (the particle of record r - 1's set that k descends from).  origin[k] is the particle of the newest record's set that
+// present particle k descends from: path_compose_kernel folds an update's ancestors into it (decided on the device from
+// Ctrl.resampled: no synchronisation), path_record_kernel stores it as the new record's parents and resets it to the identity.
+//   path_trace_kernel    one particle's lineage, newest record first: one dependent chain, walked by one lane (particle -1: the
+//                        workgroup first finds the present set's first particle of the strictly greatest weight)
+//   slamgpu_path_summary the descendants' weight and count are PUSHED down the records, one launch per record:
+//                        W_{r-1}[parent_r[k]] += W_r[k], C_{r-1}[parent_r[k]] += C_r[k], seeded with W_{R-1}[origin[i]] += w^_i,
+//                        C_{R-1}[origin[i]] += 1.  Weights travel as 64-bit fixed point (units of 2^-62 of the normalised weight)
+//                        and counts as integers: integer atomic adds commute, so the result does not depend on their order.  The
+//                        same launch reduces sum_k W_r[k] f(pose_r[k]) over its tile of kBlock particles (doubles about a pivot
+//                        inside the cloud; lanes by a DPP sum, waves in ascending order) into `part`; path_finish_kernel merges the
+//                        tiles in ascending order (Chan, Golub & LeVeque) and writes out / distinct.
+constexpr int kPathStride = 7;             // SLAMGPU_PATH_STRIDE
+constexpr int kPathFinParts = 8;           // threads per record in the finishing pass
+constexpr double kPathFixScale = 4611686018427387904.0;  // 2^62: fixed-point units per unit of normalised weight
+// fields of a partial, [tile][field][records of the chunk]: sum W | mean x, y | M2 xx, xy, yy | sum W cos, sum W sin | ancestors
+enum { kPathW = 0, kPathMx, kPathMy, kPathXX, kPathXY, kPathYY, kPathC, kPathS, kPathCnt, kPathFields };
+struct PathRing {
+    float4 *rec;                // [cap][ncap]
+    int32_t cap;                // records the ring holds
+};
+struct PathTraceArgs {
+    int32_t particle;           // -1: the present set's first particle of the strictly greatest weight
+    int64_t newest, first;      // walk records newest, newest - 1, ..., first
+    int32_t count;              // write those in [first, first + count)
+    const int32_t *origin;
+    float *xyt;                 // [count][3]
+    int32_t *index;             // [count]
+};
+struct PathWalkArgs {
+    int32_t tiles, logw;
+    double *wpart;              // [tiles][2]: the tile's sum of weights (log-weights: of exp(l - M_t)) | M_t (linear weights: 0)
+    double *wtot;               // [2]: M | sum of exp(l - M) (linear weights: 0 | sum of w); [1] not positive and finite: degenerate
+    const int32_t *origin;
+    unsigned long long *W[2];   // [ncap] descendants' weight of the record being walked / of the one before it
+    uint32_t *C[2];             // [ncap] descendants' count
+    int64_t r;                  // path_push: the record this launch walks
+    int32_t cur;                // ... and which of W / C holds its sums (the other receives the push)
+    int32_t push;               // ... push into record r - 1 (0: r is the oldest record asked for)
+    int32_t at;                 // ... r's place in the chunk of `part` (-1: newer than the records asked for, nothing to reduce)
+    int32_t chunk;              // records in `part`
+    double *part;               // [tiles][kPathFields][chunk]
+    double *out;                // path_finish: [chunk][kPathStride] of this chunk
+    int32_t *distinct;          // [chunk]
+    int32_t count;              // records of this chunk in use
+};
+
 // ---- gated association with a spatial prefilter (slamgpu_associate_ex) ------------------------------------------------------
 // Per landmark j, over ALL particles: the bounding box of its position estimates and the largest trace of its covariance
 // (lmk_box_kernel, recomputed when the landmark is written), and from them a radius rho_j such that a particle's estimate of j
@@ -823,6 +872,16 @@ struct KernelTable {
     void (*map_finish)(hipStream_t, const MapSummaryArgs &);
     // slamgpu_set_particle_miss (PpMissArgs): the held, in-view, unclaimed slots of every particle into its weight factor; after pp_resolve
     void (*pp_missed)(hipStream_t, const Buffers &, const PpMissArgs &);
+    // slamgpu_path_* (PathRing, PathTraceArgs, PathWalkArgs).  path_compose: dst[k] = src[ancestor of k in the last update] (keep_slot as
+    // slamgpu_ancestors reads it; src null: dst = identity).  path_record: record slot `at` of the ring from the set peek shows, parents from
+    // origin, origin = identity.  path_seed: stage 0 the tiles' sums of the present weights, 1 their total, 2 the seeding of W / C [0]
+    // (zeroed by the caller).  path_push / path_finish: one record / one chunk of records.  All of them read the particle state only
+    void (*path_compose)(hipStream_t, const Buffers &, const WeightScratch &, int keep_slot, const int32_t *src, int32_t *dst);
+    void (*path_record)(hipStream_t, const Buffers &, const WeightScratch &, const PathRing &, int at, int32_t *origin);
+    void (*path_trace)(hipStream_t, const Buffers &, const WeightScratch &, const PathRing &, const PathTraceArgs &);
+    void (*path_seed)(hipStream_t, const Buffers &, const WeightScratch &, const PathWalkArgs &, int stage);
+    void (*path_push)(hipStream_t, const Buffers &, const PathRing &, const PathWalkArgs &);
+    void (*path_finish)(hipStream_t, const PathWalkArgs &);
 };
 
 const KernelTable *kernels_strict();

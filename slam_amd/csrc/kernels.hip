@@ -4968,6 +4968,334 @@ static void launch_map_finish(hipStream_t st, const MapSummaryArgs &A) {
     hipLaunchKernelGGL(map_finish_kernel, dim3((A.count + kSlots - 1) / kSlots), dim3(kBlock), 0, st, A);
 }
 
+// ---- slamgpu_path_* (kernels.h: PathRing) --------------------------------------------------------------------------------------
+// origin'[k] = origin[ancestor of k] if the last update resampled (Ctrl.resampled and keep[keep_slot], as slamgpu_ancestors reads
+// them), a copy otherwise: the host flips its buffers either way.  src null: the identity.
+__global__ void __launch_bounds__(kBlock) path_compose_kernel(Buffers B, WeightScratch ws, int keep_slot, const int32_t *__restrict__ src,
+                                                              int32_t *__restrict__ dst) {
+    const int k = blockIdx.x * kBlock + threadIdx.x;
+    if (k >= B.n) return;
+    if (!src) {
+        dst[k] = k;
+        return;
+    }
+    int a = k;
+    if (B.ctrl->resampled) {
+        a = ws.keep[keep_slot][k];
+        if ((unsigned) a >= (unsigned) B.n) a = k;  // (a single context's ancestors are local indices: never taken, never out of bounds)
+    }
+    dst[k] = src[a];
+}
+
+// the pose exactly as peek_kernel finds it, the parents from origin, origin = identity
+__global__ void __launch_bounds__(kBlock) path_record_kernel(Buffers B, WeightScratch ws, PathRing R, int at, int32_t *__restrict__ origin) {
+    const int k = blockIdx.x * kBlock + threadIdx.x;
+    if (k >= B.n) return;
+    const Ctrl *ctrl = B.ctrl;
+    const int cur = ctrl->live[B.slot];
+    const int anc = ctrl->pend[B.slot] != 0 ? ws.keep[B.slot][k] : k;
+    float4 pa = B.poseA[cur][anc];
+    pa.w = __int_as_float(origin[k]);
+    R.rec[(size_t) at * B.ncap + k] = pa;
+    origin[k] = k;
+}
+
+// one workgroup: the particle (if -1 was asked for), then lane 0 walks the chain -- every load waits for the one before it
+__global__ void __launch_bounds__(kBlock) path_trace_kernel(Buffers B, WeightScratch ws, PathRing R, PathTraceArgs A) {
+    __shared__ float sh_w[kBlock];
+    __shared__ int sh_i[kBlock];
+    int p = A.particle;
+    if (p < 0) {  // (uniform) as est_combine: the strictly greatest weight, the lowest index among equals; under a pending gather all are 1/N
+        const Ctrl *ctrl = B.ctrl;
+        const int cur = ctrl->live[B.slot];
+        float bw = -3.0e38f;
+        int bi = 0x7fffffff;
+        if (ctrl->pend[B.slot] == 0)
+            for (int i = threadIdx.x; i < B.n; i += kBlock) {
+                const float w = B.poseA[cur][i].w;
+                if (w > bw || (w == bw && i < bi)) {
+                    bw = w;
+                    bi = i;
+                }
+            }
+        sh_w[threadIdx.x] = bw;
+        sh_i[threadIdx.x] = bi;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            for (int t = 1; t < kBlock; t++)
+                if (sh_w[t] > bw || (sh_w[t] == bw && sh_i[t] < bi)) {
+                    bw = sh_w[t];
+                    bi = sh_i[t];
+                }
+            p = bi < B.n ? bi : 0;
+        }
+    }
+    if (threadIdx.x != 0) return;
+    int a = A.origin[p];
+    for (int64_t r = A.newest; r >= A.first; r--) {
+        if ((unsigned) a >= (unsigned) B.n) return;  // (never: parents are particles of the set)
+        const float4 rec = R.rec[(size_t) (r % R.cap) * B.ncap + a];
+        const int64_t o = r - A.first;
+        if (o < A.count) {
+            if (A.xyt) {
+                A.xyt[3 * o] = rec.x;
+                A.xyt[3 * o + 1] = rec.y;
+                A.xyt[3 * o + 2] = rec.z;
+            }
+            if (A.index) A.index[o] = a;
+        }
+        a = __float_as_int(rec.w);
+    }
+}
+
+// one (W, mean, M2, sum W cos, sum W sin, ancestors) summary and the pairwise update with the one that follows it in particle order
+struct PathPart {
+    double v[kPathFields];
+};
+SLAM_DEV void path_merge(PathPart &a, const PathPart &b) {
+    a.v[kPathCnt] += b.v[kPathCnt];
+    if (!(b.v[kPathW] != 0.0)) return;  // nothing of weight in b (its ancestors, if any, are counted)
+    if (!(a.v[kPathW] != 0.0)) {
+        const double cnt = a.v[kPathCnt];
+        a = b;
+        a.v[kPathCnt] = cnt;
+        return;
+    }
+    const double W = a.v[kPathW] + b.v[kPathW], f = b.v[kPathW] / W, g = a.v[kPathW] * f;
+    const double dx = b.v[kPathMx] - a.v[kPathMx], dy = b.v[kPathMy] - a.v[kPathMy];
+    a.v[kPathMx] += dx * f;
+    a.v[kPathMy] += dy * f;
+    a.v[kPathXX] += b.v[kPathXX] + dx * dx * g;
+    a.v[kPathXY] += b.v[kPathXY] + dx * dy * g;
+    a.v[kPathYY] += b.v[kPathYY] + dy * dy * g;
+    a.v[kPathC] += b.v[kPathC];
+    a.v[kPathS] += b.v[kPathS];
+    a.v[kPathW] = W;
+}
+
+// the present weights as slamgpu_map_summary takes them.  Stage 0: a tile's sum (log-weights: of exp(l - M_t)) and M_t
+__global__ void __launch_bounds__(kBlock) path_wsum_kernel(Buffers B, WeightScratch ws, PathWalkArgs A) {
+    constexpr int kWaves = kBlock / kWave;
+    __shared__ double sh_w[kWaves];
+    __shared__ float sh_m[kWaves];
+    const Ctrl *ctrl = B.ctrl;
+    const int cur = ctrl->live[B.slot];
+    const bool pend = ctrl->pend[B.slot] != 0;
+    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    const bool on = i < B.n;
+    const float wf = on ? (pend ? ctrl->inv_n : B.poseA[cur][i].w) : 0.0f;
+    float mb = 0.0f;
+    double w = (double) wf;
+    if (A.logw) {
+        mb = on ? wf : -INFINITY;
+        for (int d = kWave / 2; d > 0; d >>= 1) mb = fmaxf(mb, __shfl_xor(mb, d, kWave));
+        if (lane == 0) sh_m[wave] = mb;
+        __syncthreads();
+        mb = sh_m[0];
+        for (int v = 1; v < kWaves; v++) mb = fmaxf(mb, sh_m[v]);
+        w = (on && mb != -INFINITY) ? exp((double) wf - (double) mb) : 0.0;
+    }
+    w = wave_sum_d(w);
+    if (lane == 0) sh_w[wave] = w;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double tot = sh_w[0];
+        for (int v = 1; v < kWaves; v++) tot += sh_w[v];
+        A.wpart[2 * blockIdx.x] = tot;
+        A.wpart[2 * blockIdx.x + 1] = (double) mb;
+    }
+}
+// stage 1 (one workgroup): M = the largest M_t, the total of exp(l - M): the tiles in kBlock stretches, ascending order throughout
+__global__ void __launch_bounds__(kBlock) path_wtot_kernel(PathWalkArgs A) {
+    __shared__ double sh[kBlock];
+    double M = -INFINITY;
+    if (A.logw) {
+        for (int t = threadIdx.x; t < A.tiles; t += kBlock) M = fmax(M, A.wpart[2 * t + 1]);
+        sh[threadIdx.x] = M;
+        __syncthreads();
+        M = sh[0];
+        for (int v = 1; v < kBlock; v++) M = fmax(M, sh[v]);
+        __syncthreads();
+    } else {
+        M = 0.0;
+    }
+    const int per = (A.tiles + kBlock - 1) / kBlock, t0 = threadIdx.x * per, t1 = min(A.tiles, t0 + per);
+    double s = 0.0;
+    for (int t = t0; t < t1; t++) s += A.wpart[2 * t] * (A.logw ? block_scale((float) A.wpart[2 * t + 1], M) : 1.0);
+    sh[threadIdx.x] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double tot = sh[0];
+        for (int v = 1; v < kBlock; v++) tot += sh[v];
+        A.wtot[0] = M;
+        A.wtot[1] = tot;
+    }
+}
+// stage 2: every present particle hands its normalised weight (fixed point) and a count of one to its ancestor in the newest record
+__global__ void __launch_bounds__(kBlock) path_seed_kernel(Buffers B, WeightScratch ws, PathWalkArgs A) {
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= B.n) return;
+    const Ctrl *ctrl = B.ctrl;
+    const int cur = ctrl->live[B.slot];
+    const float wf = ctrl->pend[B.slot] != 0 ? ctrl->inv_n : B.poseA[cur][i].w;
+    const double M = A.wtot[0], tot = A.wtot[1];
+    unsigned long long q = 0ull;
+    if (tot > 0.0 && tot < INFINITY) {  // (else: degenerate, every weight 0 -- the counts still travel)
+        const double w = (A.logw ? (M != -INFINITY ? exp((double) wf - M) : 0.0) : (double) wf) / tot;
+        if (w > 0.0) q = (unsigned long long) __double2ull_rn(fmin(w, 2.0) * kPathFixScale);
+    }
+    const int a = A.origin[i];
+    if ((unsigned) a >= (unsigned) B.n) return;  // (never)
+    if (q) atomicAdd(A.W[0] + a, q);
+    atomicAdd(A.C[0] + a, 1u);
+}
+
+// One record: this tile's particles of record r take the weight and the count their descendants left them (and leave zeros behind for
+// the record after next), push both to their parents, and reduce their poses under those weights.
+__global__ void __launch_bounds__(kBlock) path_push_kernel(Buffers B, PathRing R, PathWalkArgs A) {
+    constexpr int kWaves = kBlock / kWave;
+    __shared__ double sh[kWaves][kPathFields];
+    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
+    const int k = blockIdx.x * kBlock + threadIdx.x;
+    unsigned long long q = 0ull;
+    uint32_t c = 0u;
+    if (k < B.n) {
+        q = A.W[A.cur][k];
+        c = A.C[A.cur][k];
+        if (c) {
+            A.W[A.cur][k] = 0ull;
+            A.C[A.cur][k] = 0u;
+        }
+    }
+    float4 rec = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (c) {
+        rec = R.rec[(size_t) (A.r % R.cap) * B.ncap + k];
+        if (A.push) {
+            const int a = __float_as_int(rec.w);
+            if ((unsigned) a < (unsigned) B.n) {  // (always: parents are particles of the set)
+                if (q) atomicAdd(A.W[A.cur ^ 1] + a, q);
+                atomicAdd(A.C[A.cur ^ 1] + a, c);
+            }
+        }
+    }
+    if (A.at < 0) return;  // (uniform) newer than the records asked for
+    // pivot: the wave's first ancestor (a point of the cloud: the sums below cancel at the cloud's size)
+    const unsigned long long hm = __ballot(c != 0u);
+    double *o = sh[wave];
+    if (!hm) {  // (uniform) nobody in this wave has a descendant
+        if (lane < kPathFields) o[lane] = 0.0;
+    } else {
+        const int src = __builtin_amdgcn_readfirstlane((int) __ffsll((long long) hm) - 1);
+        const float px = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(rec.x), src));
+        const float py = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(rec.y), src));
+        double a[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};  // sum W | W dx, W dy | W dx^2, W dx dy, W dy^2 | W cos, W sin
+        if (c && q) {
+            const double wt = (double) q, dx = (double) rec.x - (double) px, dy = (double) rec.y - (double) py;
+            a[0] = wt;
+            a[1] = wt * dx;
+            a[2] = wt * dy;
+            a[3] = wt * dx * dx;
+            a[4] = wt * dx * dy;
+            a[5] = wt * dy * dy;
+            a[6] = wt * cos((double) rec.z);
+            a[7] = wt * sin((double) rec.z);
+        }
+#pragma unroll
+        for (int f = 0; f < 8; f++) a[f] = wave_sum_d(a[f]);
+        if (lane == 0) {
+            const double W = a[0];
+            const bool any = W != 0.0;
+            const double mx = any ? a[1] / W : 0.0, my = any ? a[2] / W : 0.0;
+            o[kPathW] = W;
+            o[kPathMx] = (double) px + mx;
+            o[kPathMy] = (double) py + my;
+            o[kPathXX] = a[3] - a[1] * mx;
+            o[kPathXY] = a[4] - a[1] * my;
+            o[kPathYY] = a[5] - a[2] * my;
+            o[kPathC] = a[6];
+            o[kPathS] = a[7];
+            o[kPathCnt] = (double) __popcll(hm);
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {  // the tile's waves in ascending order
+        PathPart m;
+        for (int f = 0; f < kPathFields; f++) m.v[f] = sh[0][f];
+        for (int v = 1; v < kWaves; v++) {
+            PathPart b;
+            for (int f = 0; f < kPathFields; f++) b.v[f] = sh[v][f];
+            path_merge(m, b);
+        }
+        double *p = A.part + (size_t) blockIdx.x * kPathFields * (size_t) A.chunk + (size_t) A.at;
+        for (int f = 0; f < kPathFields; f++) p[(size_t) f * A.chunk] = m.v[f];
+    }
+}
+
+// kPathFinParts threads per record: each merges its stretch of the tiles' partials in ascending order, the record's first thread merges
+// the stretches in ascending order and writes the outputs
+__global__ void __launch_bounds__(kBlock) path_finish_kernel(PathWalkArgs A) {
+    constexpr int kRecs = kBlock / kPathFinParts;
+    __shared__ double sh[kPathFinParts][kPathFields][kRecs];
+    const int sl = threadIdx.x % kRecs, part = threadIdx.x / kRecs;
+    const int s = blockIdx.x * kRecs + sl;
+    const int per = (A.tiles + kPathFinParts - 1) / kPathFinParts, t0 = part * per, t1 = min(A.tiles, t0 + per);
+    PathPart m;
+    for (int f = 0; f < kPathFields; f++) m.v[f] = 0.0;
+    if (s < A.count)
+        for (int t = t0; t < t1; t++) {
+            const double *p = A.part + (size_t) t * kPathFields * (size_t) A.chunk + (size_t) s;
+            PathPart b;
+            for (int f = 0; f < kPathFields; f++) b.v[f] = p[(size_t) f * A.chunk];
+            path_merge(m, b);
+        }
+    for (int f = 0; f < kPathFields; f++) sh[part][f][sl] = m.v[f];
+    __syncthreads();
+    if (part != 0 || s >= A.count) return;
+    for (int v = 1; v < kPathFinParts; v++) {
+        PathPart b;
+        for (int f = 0; f < kPathFields; f++) b.v[f] = sh[v][f][sl];
+        path_merge(m, b);
+    }
+    double *o = A.out + (size_t) s * kPathStride;
+    if (A.distinct) A.distinct[s] = (int32_t) m.v[kPathCnt];
+    const double tot = A.wtot[1], W = m.v[kPathW];
+    if (!(tot > 0.0) || !(tot < INFINITY) || !(W > 0.0)) {  // the weights sum to zero or to nothing finite: SLAMGPU_STATUS_DEGENERATE's convention
+        const double nan = __longlong_as_double(0x7ff8000000000000ll);
+        for (int f = 0; f < kPathStride; f++) o[f] = nan;
+        return;
+    }
+    o[0] = m.v[kPathMx];
+    o[1] = m.v[kPathMy];
+    o[2] = m.v[kPathXX] / W;
+    o[3] = m.v[kPathXY] / W;
+    o[4] = m.v[kPathYY] / W;
+    o[5] = m.v[kPathC] / W;
+    o[6] = m.v[kPathS] / W;
+}
+
+static void launch_path_compose(hipStream_t st, const Buffers &B, const WeightScratch &ws, int keep_slot, const int32_t *src, int32_t *dst) {
+    hipLaunchKernelGGL(path_compose_kernel, dim3((B.n + kBlock - 1) / kBlock), dim3(kBlock), 0, st, B, ws, keep_slot, src, dst);
+}
+static void launch_path_record(hipStream_t st, const Buffers &B, const WeightScratch &ws, const PathRing &R, int at, int32_t *origin) {
+    hipLaunchKernelGGL(path_record_kernel, dim3((B.n + kBlock - 1) / kBlock), dim3(kBlock), 0, st, B, ws, R, at, origin);
+}
+static void launch_path_trace(hipStream_t st, const Buffers &B, const WeightScratch &ws, const PathRing &R, const PathTraceArgs &A) {
+    hipLaunchKernelGGL(path_trace_kernel, dim3(1), dim3(kBlock), 0, st, B, ws, R, A);
+}
+static void launch_path_seed(hipStream_t st, const Buffers &B, const WeightScratch &ws, const PathWalkArgs &A, int stage) {
+    if (stage == 0) hipLaunchKernelGGL(path_wsum_kernel, dim3(A.tiles), dim3(kBlock), 0, st, B, ws, A);
+    else if (stage == 1) hipLaunchKernelGGL(path_wtot_kernel, dim3(1), dim3(kBlock), 0, st, A);
+    else hipLaunchKernelGGL(path_seed_kernel, dim3(A.tiles), dim3(kBlock), 0, st, B, ws, A);
+}
+static void launch_path_push(hipStream_t st, const Buffers &B, const PathRing &R, const PathWalkArgs &A) {
+    hipLaunchKernelGGL(path_push_kernel, dim3(A.tiles), dim3(kBlock), 0, st, B, R, A);
+}
+static void launch_path_finish(hipStream_t st, const PathWalkArgs &A) {
+    constexpr int kRecs = kBlock / kPathFinParts;
+    hipLaunchKernelGGL(path_finish_kernel, dim3((A.count + kRecs - 1) / kRecs), dim3(kBlock), 0, st, A);
+}
+
 // ---- slamgpu_set_particle_miss (kernels.h: PpMissArgs) -----------------------------------------------------------------------
 // Negative information: the slots a particle holds, expects to see from its own pose and has no fresh claim on, counted into its
 // weight factor.  One lane per particle, its pose and the heading's sine and cosine in registers across the slots; kMissT slots a trip,
@@ -5127,7 +5455,8 @@ static const KernelTable kTable = {launch_update, launch_update_any, launch_upda
                                    launch_associate_grid, launch_jacobians_multi, launch_pp_census, launch_pp_resolve, launch_pp_holders,
                                    launch_pp_resample, launch_pp_gather, launch_pp_book,
                                    launch_lists_box, launch_lists_geom, launch_lists_build, launch_lists_walk, launch_excl_radii,
-                                   launch_map_summary, launch_map_finish, launch_pp_missed};
+                                   launch_map_summary, launch_map_finish, launch_pp_missed,
+                                   launch_path_compose, launch_path_record, launch_path_trace, launch_path_seed, launch_path_push, launch_path_finish};
 
 }  // namespace SLAM_KNS
 

@@ -267,6 +267,15 @@ struct slamgpu_ctx {
     size_t peek_bytes = 0;
     char *msum_dev = nullptr;        // staging and partials of slamgpu_map_summary, grown on demand
     size_t msum_bytes = 0;
+    // path recording (slamgpu_path_*; kernels.h: PathRing).  path_cap = 0: off, nothing allocated, no kernel of it launched.  Records
+    // [path_first, path_next) are retained, record r in ring slot r % path_cap; origin[path_org] is the live origin array
+    int32_t path_cap = 0;
+    int64_t path_first = 0, path_next = 0;
+    float4 *path_rec_dev = nullptr;
+    int32_t *path_origin_dev[2] = {nullptr, nullptr};
+    int path_org = 0;
+    char *path_dev = nullptr;        // staging, push buffers and partials of slamgpu_path_trace / _summary, grown on demand
+    size_t path_bytes = 0;
     unsigned long long *stamps_dev = nullptr;  // diagnostic (SLAMGPU_STAMPS=1 + libslamgpu_stamps.so): UpdateArgs::stamps
     // persistent small-N step loop (slamgpu_run_observe, kernels.h: PersistArgs)
     bool persist_ok = true;              // SLAMGPU_NO_PERSIST=1 turns it off (diagnostic / tests: the per-step loop)
@@ -754,6 +763,65 @@ int flush_predict(slamgpu_ctx *c) {
     return 0;
 }
 
+// ---- path recording (slamgpu_path_*; kernels.h: PathRing) ----
+PathRing path_ring(const slamgpu_ctx *c) { return PathRing{c->path_rec_dev, c->path_cap}; }
+
+// after an update launch: its resampling stage, then origin' = origin o ancestors.  The kernel reads Ctrl.resampled itself (no
+// synchronisation); the host flips the origin buffers whatever it decides.  Once per update that RAN: issue_update calls it
+int path_compose(slamgpu_ctx *c) {
+    if (int rc = flush_stages(c)) return rc;
+    c->B.slot = c->slot;
+    {
+        Timed t(c, "path_compose");
+        c->k->path_compose(c->stream, c->B, c->ws, c->keep_slot, c->path_origin_dev[c->path_org], c->path_origin_dev[c->path_org ^ 1]);
+    }
+    HIP_TRY(hipGetLastError());
+    c->path_org ^= 1;
+    return 0;
+}
+
+// the set as slamgpu_peek would show it, into the ring's next slot (a full ring drops its oldest record)
+int path_append(slamgpu_ctx *c) {
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    if (int rc = flush_predict(c)) return rc;
+    if (int rc = flush_stages(c)) return rc;
+    c->B.slot = c->slot;
+    {
+        Timed t(c, "path_record");
+        c->k->path_record(c->stream, c->B, c->ws, path_ring(c), (int) (c->path_next % c->path_cap), c->path_origin_dev[c->path_org]);
+    }
+    HIP_TRY(hipGetLastError());
+    c->path_next++;
+    if (c->path_next - c->path_first > c->path_cap) c->path_first = c->path_next - c->path_cap;
+    return 0;
+}
+
+int path_identity(slamgpu_ctx *c) {
+    Timed t(c, "path_compose");
+    c->k->path_compose(c->stream, c->B, c->ws, 0, nullptr, c->path_origin_dev[c->path_org]);
+    return 0;
+}
+
+int path_reserve(slamgpu_ctx *c, size_t total) {
+    if (total <= c->path_bytes) return 0;
+    if (c->path_dev) (void) hipFree(c->path_dev);
+    c->path_dev = nullptr;
+    c->path_bytes = 0;
+    hipError_t e = hipMalloc((void **) &c->path_dev, total);
+    if (e != hipSuccess) return fail(SLAMGPU_ERR_ALLOC, "hipMalloc(%zu): %s", total, hipGetErrorString(e));
+    c->path_bytes = total;
+    return 0;
+}
+
+// the checks slamgpu_path_fetch / _trace / _summary share
+int path_check(slamgpu_ctx *c, const char *who, int64_t first, int64_t count) {
+    if (c->path_cap == 0) return fail(SLAMGPU_ERR_INVALID, "%s: recording is off (slamgpu_path_enable)", who);
+    if (count < 0 || first < c->path_first || first + count > c->path_next)
+        return fail(SLAMGPU_ERR_INVALID, "%s: records [%lld, %lld + %lld) outside the retained [%lld, %lld)", who, (long long) first, (long long) first,
+                    (long long) count, (long long) c->path_first, (long long) c->path_next);
+    return 0;
+}
+
 // the recorded history entries, behind everything enqueued, through the pinned mirror (a pageable destination cost the FIRST fetch of
 // a process 8.4 ms for 104 KB: 3.9 us per observation step of a whole example_webmap run of the drop-in binary, round 5)
 int history_to_host(slamgpu_ctx *c, std::vector<double> &h) {
@@ -1008,6 +1076,10 @@ void slamgpu_destroy(slamgpu_ctx *c) {
     if (c->stamps_dev) (void) hipFree(c->stamps_dev);
     if (c->peek_dev) (void) hipFree(c->peek_dev);
     if (c->msum_dev) (void) hipFree(c->msum_dev);
+    if (c->path_rec_dev) (void) hipFree(c->path_rec_dev);
+    for (int b = 0; b < 2; b++)
+        if (c->path_origin_dev[b]) (void) hipFree(c->path_origin_dev[b]);
+    if (c->path_dev) (void) hipFree(c->path_dev);
     if (c->retired_dev) (void) hipFree(c->retired_dev);
     if (c->vote_w_dev) (void) hipFree(c->vote_w_dev);
     if (c->assoc_z_dev) (void) hipFree(c->assoc_z_dev);
@@ -1257,6 +1329,9 @@ int issue_update(slamgpu_ctx *c, UpdateArgs &U, int n_new, int n_rows, bool need
         c->scan_ready = true;
     }
     HIP_TRY(hipGetLastError());
+    // path recording: this update's ancestors into origin[].  Only resample_kernel leaves them in keep[] (an inline plan finds them in
+    // registers), so the stage runs now, as launches of its own, instead of inside the next update launch
+    if (c->path_cap > 0) return path_compose(c);
     return 0;
 }
 
@@ -1635,7 +1710,10 @@ int slamgpu_step(slamgpu_ctx *c, const float *controls, int32_t n_controls, cons
     for (int k = 0; k < n_controls; k++)
         if (int rc = slamgpu_predict(c, controls[3 * k], controls[3 * k + 1], Q, dt, controls[3 * k + 2], nullptr)) return rc;
     if (int rc = slamgpu_update(c, zf, idf, m, zn, n, R, normals, strata)) return rc;
-    if (record_estimate) return slamgpu_estimate_async(c);
+    if (record_estimate) {
+        if (int rc = slamgpu_estimate_async(c)) return rc;
+        if (c->path_cap > 0) return path_append(c);  // record r beside history entry r
+    }
     return 0;
 }
 
@@ -1649,7 +1727,10 @@ int slamgpu_step_observe(slamgpu_ctx *c, const float *controls, int32_t n_contro
     for (int k = 0; k < n_controls; k++)
         if (int rc = slamgpu_predict(c, controls[3 * k], controls[3 * k + 1], Q, dt, controls[3 * k + 2], nullptr)) return rc;
     if (int rc = do_update_dev(c, xtrue, max_range, R, noise, r1, r2, normals, strata)) return rc;
-    if (record_estimate) return slamgpu_estimate_async(c);
+    if (record_estimate) {
+        if (int rc = slamgpu_estimate_async(c)) return rc;
+        if (c->path_cap > 0) return path_append(c);  // record r beside history entry r
+    }
     return 0;
 }
 
@@ -1788,7 +1869,8 @@ int slamgpu_run_observe(slamgpu_ctx *c, int32_t K, const int32_t *n_controls, co
                                           "slamgpu_history_fetch first, or hand over fewer iterations", (int) K, c->hist_n, kHistCap);
     if (int rc = persist_check(c)) return rc;
     // small compact contexts: ONE launch for all K iterations (kernels.h: PersistArgs)
-    if (K >= 2 && persist_eligible(c) && max_nc <= kMaxFusedPredict)
+    // (not while the path is recorded: the loop's resampling decisions and ancestors never leave its launch)
+    if (K >= 2 && persist_eligible(c) && max_nc <= kMaxFusedPredict && c->path_cap == 0)
         return run_observe_persist(c, K, n_controls, controls, Q, dt, xtrue, max_range, R, noise);
     size_t row = 0;
     for (int32_t k = 0; k < K; k++) {
@@ -4121,6 +4203,9 @@ int slamgpu_run_particle(slamgpu_ctx *c, int32_t K, const int32_t *n_controls, c
         return fail(SLAMGPU_ERR_INVALID, "slamgpu_run_particle: create the context with SLAMGPU_FLAG_PARTICLE_MAPS | SLAMGPU_FLAG_DEVICE_OBSERVE");
     if (noise != 0 && noise != 2) return fail(SLAMGPU_ERR_INVALID, "slamgpu_run_particle: noise must be 0 or 2");
     if (c->cfg.rng_mode == SLAMGPU_RNG_TAPE) return fail(SLAMGPU_ERR_INVALID, "slamgpu_run_particle: TAPE-mode contexts take their draws per step");
+    if (c->path_cap > 0)
+        return fail(SLAMGPU_ERR_INVALID, "slamgpu_run_particle: not while the path is recorded (its resampling decisions are known to the device only): "
+                                         "slamgpu_path_enable(ctx, 0) first, or drive the steps with slamgpu_update_particle");
     if (K == 0) return 0;
     if (!c->map_dev) return fail(SLAMGPU_ERR_INVALID, "slamgpu_run_particle: no map: call slamgpu_set_map first");
     if (opt->mode < SLAMGPU_ASSOC_AUTO || opt->mode > SLAMGPU_ASSOC_LISTS) return fail(SLAMGPU_ERR_INVALID, "unknown association mode %d", opt->mode);
@@ -4654,6 +4739,188 @@ int slamgpu_map_summary(slamgpu_ctx *c, int32_t first_slot, int32_t count, doubl
     return 0;
 }
 
+int slamgpu_path_enable(slamgpu_ctx *c, int32_t capacity) {
+    if (int rc = check_ctx(c)) return rc;
+    if (c->dist || c->cfg.n_particles_global != c->cfg.n_particles) return fail(SLAMGPU_ERR_INVALID, "slamgpu_path_enable: single contexts only");
+    if (capacity < 0) return fail(SLAMGPU_ERR_INVALID, "slamgpu_path_enable: capacity %d", capacity);
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    // the new ring first: a refused call leaves the recording as it was
+    float4 *rec = nullptr;
+    int32_t *org[2] = {nullptr, nullptr};
+    if (capacity > 0) {
+        const size_t S = (size_t) c->B.ncap, bytes = sizeof(float4) * S * (size_t) capacity;
+        hipError_t e = hipMalloc((void **) &rec, bytes);
+        for (int b = 0; b < 2 && e == hipSuccess; b++) e = hipMalloc((void **) &org[b], sizeof(int32_t) * S);
+        if (e != hipSuccess) {
+            (void) hipGetLastError();
+            if (rec) (void) hipFree(rec);
+            for (int b = 0; b < 2; b++)
+                if (org[b]) (void) hipFree(org[b]);
+            return fail(SLAMGPU_ERR_ALLOC, "slamgpu_path_enable: %d records of %d particles (%zu bytes): %s", capacity, c->B.n, bytes, hipGetErrorString(e));
+        }
+    }
+    if (c->path_cap > 0 || c->path_dev) {
+        HIP_TRY(hipStreamSynchronize(c->stream));  // (launches in flight may still use the old ring)
+        if (c->path_rec_dev) (void) hipFree(c->path_rec_dev);
+        for (int b = 0; b < 2; b++)
+            if (c->path_origin_dev[b]) (void) hipFree(c->path_origin_dev[b]);
+        if (c->path_dev) (void) hipFree(c->path_dev);
+        c->path_dev = nullptr;
+        c->path_bytes = 0;
+    }
+    c->path_rec_dev = rec;
+    c->path_origin_dev[0] = org[0];
+    c->path_origin_dev[1] = org[1];
+    c->path_org = 0;
+    c->path_cap = capacity;
+    c->path_first = c->path_next = 0;
+    if (capacity > 0) {
+        if (int rc = path_identity(c)) return rc;
+        HIP_TRY(hipGetLastError());
+    }
+    return 0;
+}
+
+int slamgpu_path_record(slamgpu_ctx *c) {
+    if (int rc = check_ctx(c)) return rc;
+    if (c->path_cap == 0) return fail(SLAMGPU_ERR_INVALID, "slamgpu_path_record: recording is off (slamgpu_path_enable)");
+    return path_append(c);
+}
+
+int slamgpu_path_info(slamgpu_ctx *c, int64_t *first, int64_t *next, int32_t *capacity) {
+    if (int rc = check_ctx(c)) return rc;
+    if (first) *first = c->path_first;
+    if (next) *next = c->path_next;
+    if (capacity) *capacity = c->path_cap;
+    return 0;
+}
+
+int slamgpu_path_fetch(slamgpu_ctx *c, int64_t r, float *xyt, int32_t *parent) {
+    if (int rc = check_ctx(c)) return rc;
+    if (int rc = path_check(c, "slamgpu_path_fetch", r, 1)) return rc;
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    const size_t N = (size_t) c->B.n;
+    std::vector<float4> rec(N);
+    HIP_TRY(hipMemcpyAsync(rec.data(), c->path_rec_dev + (size_t) (r % c->path_cap) * (size_t) c->B.ncap, sizeof(float4) * N, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    for (size_t k = 0; k < N; k++) {
+        if (xyt) {
+            xyt[3 * k] = rec[k].x;
+            xyt[3 * k + 1] = rec[k].y;
+            xyt[3 * k + 2] = rec[k].z;
+        }
+        if (parent) memcpy(parent + k, &rec[k].w, sizeof(int32_t));
+    }
+    return 0;
+}
+
+int slamgpu_path_trace(slamgpu_ctx *c, int32_t particle, int64_t first, int32_t count, float *xyt, int32_t *index) {
+    if (int rc = check_ctx(c)) return rc;
+    if (int rc = path_check(c, "slamgpu_path_trace", first, count)) return rc;
+    if (particle < -1 || particle >= c->B.n) return fail(SLAMGPU_ERR_INVALID, "slamgpu_path_trace: particle %d outside [-1, %d)", particle, c->B.n);
+    if (count == 0) return 0;
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    // the present set is what slamgpu_peek shows, and nothing more than it does to get there
+    if (int rc = flush_predict(c)) return rc;
+    if (int rc = flush_stages(c)) return rc;
+    const size_t M = (size_t) count, o_idx = (sizeof(float) * 3 * M + 15) & ~(size_t) 15;
+    if (int rc = path_reserve(c, o_idx + sizeof(int32_t) * M)) return rc;
+    PathTraceArgs A{};
+    A.particle = particle;
+    A.newest = c->path_next - 1;
+    A.first = first;
+    A.count = count;
+    A.origin = c->path_origin_dev[c->path_org];
+    A.xyt = reinterpret_cast<float *>(c->path_dev);
+    A.index = reinterpret_cast<int32_t *>(c->path_dev + o_idx);
+    c->B.slot = c->slot;
+    {
+        Timed t(c, "path_trace");
+        c->k->path_trace(c->stream, c->B, c->ws, path_ring(c), A);
+    }
+    HIP_TRY(hipGetLastError());
+    if (xyt) HIP_TRY(hipMemcpyAsync(xyt, A.xyt, sizeof(float) * 3 * M, hipMemcpyDeviceToHost, c->stream));
+    if (index) HIP_TRY(hipMemcpyAsync(index, A.index, sizeof(int32_t) * M, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+int slamgpu_path_summary(slamgpu_ctx *c, int64_t first, int32_t count, double *out, int32_t *distinct) {
+    if (int rc = check_ctx(c)) return rc;
+    if (int rc = path_check(c, "slamgpu_path_summary", first, count)) return rc;
+    if (count == 0) return 0;
+    if (!out) return fail(SLAMGPU_ERR_INVALID, "null output");
+    static_assert(SLAMGPU_PATH_STRIDE == kPathStride, "public / device summary layout");
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    if (int rc = flush_predict(c)) return rc;
+    if (int rc = flush_stages(c)) return rc;
+    const int tiles = (c->B.n + kBlock - 1) / kBlock;
+    const size_t S = (size_t) c->B.ncap, M = (size_t) count;
+    // the records go through the partials' table a chunk at a time: at most kPathScratch bytes of it, however many are asked for
+    constexpr size_t kPathScratch = (size_t) 16 << 20;
+    const size_t per_rec = sizeof(double) * kPathFields * (size_t) tiles;
+    int fit = (int) std::max<size_t>(1, kPathScratch / per_rec);
+    if (const char *e = getenv("SLAMGPU_PATH_CHUNK")) fit = std::max(1, atoi(e));  // (diagnostic: the chunking of a long window on a short one)
+    const int chunk = std::min(fit, count);
+    // device staging: [out count][wpart tiles][wtot][W 2 S][part chunk][C 2 S][distinct count]
+    const size_t o_out = 0, o_w = o_out + sizeof(double) * kPathStride * M, o_tot = o_w + sizeof(double) * 2 * (size_t) tiles, o_W = o_tot + sizeof(double) * 2,
+                 o_part = o_W + sizeof(unsigned long long) * 2 * S, o_C = o_part + per_rec * (size_t) chunk, o_d = o_C + sizeof(uint32_t) * 2 * S,
+                 total = o_d + sizeof(int32_t) * M;
+    if (int rc = path_reserve(c, total)) return rc;
+    PathWalkArgs A{};
+    A.tiles = tiles;
+    A.logw = c->cfg.log_weights;
+    A.wpart = reinterpret_cast<double *>(c->path_dev + o_w);
+    A.wtot = reinterpret_cast<double *>(c->path_dev + o_tot);
+    A.origin = c->path_origin_dev[c->path_org];
+    A.W[0] = reinterpret_cast<unsigned long long *>(c->path_dev + o_W);
+    A.W[1] = A.W[0] + S;
+    A.C[0] = reinterpret_cast<uint32_t *>(c->path_dev + o_C);
+    A.C[1] = A.C[0] + S;
+    A.part = reinterpret_cast<double *>(c->path_dev + o_part);
+    A.chunk = chunk;
+    c->B.slot = c->slot;
+    HIP_TRY(hipMemsetAsync(A.W[0], 0, sizeof(unsigned long long) * 2 * S, c->stream));
+    HIP_TRY(hipMemsetAsync(A.C[0], 0, sizeof(uint32_t) * 2 * S, c->stream));
+    for (int stage = 0; stage < 3; stage++) {
+        Timed t(c, "path_seed");
+        c->k->path_seed(c->stream, c->B, c->ws, A, stage);
+    }
+    HIP_TRY(hipGetLastError());
+    // newest record first; a chunk is finished when its oldest record has been walked
+    const PathRing R = path_ring(c);
+    int64_t lo = first + count;  // the chunk in progress is [lo, hi)
+    int64_t hi = lo;
+    int cur = 0;
+    for (int64_t r = c->path_next - 1; r >= first; r--) {
+        if (r < lo) {
+            hi = lo;
+            lo = std::max<int64_t>(first, hi - chunk);
+        }
+        A.r = r;
+        A.cur = cur;
+        A.push = r > first ? 1 : 0;
+        A.at = r < first + count ? (int32_t) (r - lo) : -1;
+        {
+            Timed t(c, "path_push");
+            c->k->path_push(c->stream, c->B, R, A);
+        }
+        cur ^= 1;
+        if (r == lo && A.at >= 0) {
+            A.count = (int32_t) (hi - lo);
+            A.out = reinterpret_cast<double *>(c->path_dev + o_out) + (size_t) kPathStride * (size_t) (lo - first);
+            A.distinct = reinterpret_cast<int32_t *>(c->path_dev + o_d) + (size_t) (lo - first);
+            Timed t(c, "path_finish");
+            c->k->path_finish(c->stream, A);
+        }
+    }
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(out, c->path_dev + o_out, sizeof(double) * kPathStride * M, hipMemcpyDeviceToHost, c->stream));
+    if (distinct) HIP_TRY(hipMemcpyAsync(distinct, c->path_dev + o_d, sizeof(int32_t) * M, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
 int slamgpu_upload(slamgpu_ctx *c, int32_t nf, const float *xv, const float *Pv9, const float *w, const float *xf,
                    const float *Pf4) {
     if (int rc = check_ctx(c)) return rc;
@@ -4717,6 +4984,11 @@ int slamgpu_upload(slamgpu_ctx *c, int32_t nf, const float *xv, const float *Pv9
     }
     c->est_fresh = false;
     c->shard_est_fresh = false;
+    if (c->path_cap > 0) {  // a new set: nothing descends from the retained records
+        c->path_first = c->path_next;
+        if (int rc = path_identity(c)) return rc;
+        HIP_TRY(hipGetLastError());
+    }
     return 0;
 }
 
