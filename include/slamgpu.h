@@ -410,6 +410,38 @@ int slamgpu_set_particle_assoc_sampling(slamgpu_ctx *ctx, int32_t on);
 /* Cumulative counters of the sampling: [0] steps associated with it on, [1] (particle, observation) pairs with |C| >= 2, [2] pairs whose
  * sampled label is not the nearest one.  Synchronises. */
 int slamgpu_particle_sample_stats(slamgpu_ctx *ctx, int64_t out[3]);
+/* Mutual exclusion for contested landmarks (Montemerlo's thesis, section 4.5; Nieto et al., ICRA 2003) for both per-particle entry points,
+ * in every association mode.  Every particle labels each observation on its own, and when two observations of a step name the same
+ * slot the lower index keeps it, however much better the other fits.  With this on the better claim keeps it and the other looks again.
+ * Take a step with nz observations and particle i; records as they stand BEFORE the step's update, read through the genealogy; L0[q] the
+ * label the association gives (gates, exclusion rule, spacing cap; nearest neighbour).  For a claim (q, l), l = L0[q] >= 0, let
+ * (nis, nd) be the gate values of (i, q, l) in the arithmetic of the context's build, and cls = 0 if nis < gate_reject (a claim the
+ * gates made), else 1 (a claim the exclusion rule made).
+ *   1. Contest.  For every slot with two or more claimants, the claimant with the lexicographically smallest (cls, nd, q) keeps the
+ *      slot: the claimants are taken in ascending q and a later one displaces the keeper only if its (cls, nd) compares smaller -- a
+ *      comparison that is false, NaN included, keeps the lower q.  The others are losers.
+ *   2. Re-match.  Losers in ascending q.  The candidates of loser q are the slots j in use before the step that are not retired or dead,
+ *      that the particle holds (record not absent), with nis(i, q, j) < gate_reject, that nobody holds after 1. and no earlier loser has
+ *      taken.  The loser takes the candidate with the smallest nd, ties to the lower slot; with no candidate its label becomes
+ *      SLAMGPU_ASSOC_DISCARD.  A loser never becomes SLAMGPU_ASSOC_NEW, and labels that were NEW or DISCARD are not touched.
+ *   3. Everything downstream runs on the final labels: the label census and the packet's slots, the new-slot decision (its counts
+ *      cannot change), the resolve (which now meets no second claim from the gates), the p_new factor of every unexplained
+ *      observation, `claimed` of slamgpu_set_particle_miss, and slamgpu_particle_labels.
+ * Order-dependence remains only among the losers, in 2.: an earlier loser takes its best free slot without asking whether a later one
+ * needs it more (a full auction would settle that; not done).  With SLAMGPU_ASSOC_LISTS the re-match walks the observation's
+ * candidate list (a superset of its candidates; an observation whose list overflowed walks every slot): the same labels on every path.
+ * slamgpu_update_labels (the caller's labels: the first claim wins), slamgpu_associate(_ex) and the vote are untouched.
+ * on in {0, 1} (0, the default: nothing is launched or allocated); applies to slamgpu_update_particle / slamgpu_run_particle calls made
+ * after it (iterations already enqueued keep their setting).  On, the context holds a table of landmark capacity x particles x 2 bytes
+ * (who holds which slot; 10^5 particles x 15 000 slots: 3 GB), freed when it is turned off.  SLAMGPU_ERR_INVALID for any other value,
+ * for a context without SLAMGPU_FLAG_PARTICLE_MAPS, and while data association sampling is on (slamgpu_set_particle_assoc_sampling(ctx,
+ * 1) is refused the same way while this is on: the sampled pair's weight ratio has no meaning for a displaced claim);
+ * SLAMGPU_ERR_ALLOC if the table does not fit (the setting stays as it was). */
+int slamgpu_set_particle_mutex(slamgpu_ctx *ctx, int32_t on);
+/* Cumulative counters of the mutual exclusion: [0] steps with it on and at least one observation, [1] contested (particle, slot) pairs,
+ * [2] claims lost (the sum over contested pairs of claimants - 1), [3] losers re-matched to another slot, [4] contests whose keeper is
+ * not the lowest-index claimant (where the result differs from the first-claim rule).  Synchronises. */
+int slamgpu_particle_mutex_stats(slamgpu_ctx *ctx, int64_t out[5]);
 /* The last per-particle step's labels as its update consumed them, particle-major [N][nz]: slot, SLAMGPU_ASSOC_NEW or _DISCARD (at most
  * max_count of them); *nz: the step's observations (0: none yet; an iteration of slamgpu_run_particle without observations leaves 0).
  * With sampling on or off.  Synchronises. */

@@ -29,7 +29,7 @@ DECLARED_SYMBOLS = [
     "slamgpu_run_particle", "slamgpu_particle_report_fetch", "slamgpu_particle_list_stats",
     "slamgpu_set_particle_excl_spacing", "slamgpu_particle_excl_radii",
     "slamgpu_set_particle_assoc_sampling", "slamgpu_particle_sample_stats", "slamgpu_particle_labels",
-    "slamgpu_map_summary",
+    "slamgpu_map_summary", "slamgpu_set_particle_mutex", "slamgpu_particle_mutex_stats",
     "slamgpu_set_particle_miss", "slamgpu_particle_missed", "slamgpu_particle_miss_stats", "slamgpu_particle_miss_visited",
     "slamgpu_path_enable", "slamgpu_path_record", "slamgpu_path_info", "slamgpu_path_fetch", "slamgpu_path_trace", "slamgpu_path_summary",
 ]
@@ -134,6 +134,9 @@ def load_library():
         L.slamgpu_set_particle_assoc_sampling.argtypes = [C.c_void_p, C.c_int32]
         L.slamgpu_particle_sample_stats.argtypes = [C.c_void_p, C.c_void_p]
         L.slamgpu_particle_labels.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int32)]
+    if hasattr(L, "slamgpu_set_particle_mutex"):
+        L.slamgpu_set_particle_mutex.argtypes = [C.c_void_p, C.c_int32]
+        L.slamgpu_particle_mutex_stats.argtypes = [C.c_void_p, C.c_void_p]
     if hasattr(L, "slamgpu_map_summary"):
         L.slamgpu_map_summary.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
     if hasattr(L, "slamgpu_path_enable"):
@@ -908,6 +911,18 @@ class SlamGpu:
         out = np.zeros(3, np.int64)
         _chk(self.L.slamgpu_particle_sample_stats(self.h, _ptr(out)))
         return dict(zip(("steps", "ambiguous", "moved"), (int(v) for v in out)))
+
+    def set_particle_mutex(self, on):
+        """mutual exclusion for contested landmarks in update_particle / run_particle calls made after it (slamgpu_set_particle_mutex): a
+        slot two observations of a step name goes to the better claim and the other is re-matched or discarded; False: the first claim"""
+        _chk(self.L.slamgpu_set_particle_mutex(self.h, int(on)))
+
+    def particle_mutex_stats(self):
+        """mutual-exclusion counters since the context was created (slamgpu_particle_mutex_stats): dict(steps, contested, lost, rematched,
+        overturned)"""
+        out = np.zeros(5, np.int64)
+        _chk(self.L.slamgpu_particle_mutex_stats(self.h, _ptr(out)))
+        return dict(zip(("steps", "contested", "lost", "rematched", "overturned"), (int(v) for v in out)))
 
     def set_particle_miss(self, p_miss, view_range, view_front=0.0):
         """negative information for the per-particle steps made after it (slamgpu_set_particle_miss): the factor p_miss for every slot a

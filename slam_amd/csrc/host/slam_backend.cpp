@@ -23,6 +23,8 @@
 //                        -PARTICLE_MISS p -PARTICLE_MISS_MARGIN m (together): negative information (slamgpu_set_particle_miss) -- a
 //                        particle pays p for every landmark it holds closer than MAX_RANGE - m, more than m ahead of its own pose,
 //                        that it matched no observation of the step with (p = 1: count only); the summary prints the counters.
+//                        -PARTICLE_MUTEX 1: mutual exclusion for contested landmarks (slamgpu_set_particle_mutex; 0, the default: the
+//                        first claim keeps a slot); the summary prints the counters (slamgpu_particle_mutex_stats).
 //   -map best|posterior  the map reported at the end of a FastSLAM run.  best (default): the landmark count, with -assoc particle the best
 //                        particle's map.  posterior: one more line from slamgpu_map_summary, over ALL particles: the slots held by at
 //                        least half of the weight, how many true landmarks lie within 1 m of such a slot's weighted mean, how many such
@@ -89,6 +91,8 @@ static void usage(const char *a0) {
     printf("                        (data association sampling, weights by the marginal likelihood; default 0: the nearest)\n");
     printf("    -PARTICLE_MISS p -PARTICLE_MISS_MARGIN m  -assoc particle, both together: the weight factor p (0 < p <= 1; 1: count only) for every\n");
     printf("                        landmark a particle holds within MAX_RANGE - m, more than m ahead of its own pose, and matched nothing with\n");
+    printf("    -PARTICLE_MUTEX 0|1  -assoc particle: a landmark two observations of a step claim goes to the better claim, the other is\n");
+    printf("                        re-matched or discarded (mutual exclusion; default 0: the first claim keeps it; not with -PARTICLE_ASSOC_SAMPLE 1)\n");
     printf("    -map best|posterior the map reported at the end: best (default; -assoc particle: the best particle's), or posterior: one more line,\n");
     printf("                        the landmark slots by the share of ALL particles' weight that holds them (slamgpu_map_summary; not with -gpus)\n");
     printf("    -path none|smoothed smoothed: record the path posterior (one record per observation step, -PATH_RECORDS n of them kept, default 4096)\n");
@@ -344,6 +348,11 @@ static void print_particle_map(slamgpu_ctx *ctx, const Simulator &sim, int N, lo
     if (slamgpu_particle_miss_stats(ctx, ms) == 0 && ms[0] > 0)
         printf("negative information: %lld steps, %lld held landmarks in view and unmatched (summed over particles and steps), %lld particles with one or more\n",
                (long long) ms[0], (long long) ms[1], (long long) ms[2]);
+    int64_t mx[5] = {0, 0, 0, 0, 0};
+    if (slamgpu_particle_mutex_stats(ctx, mx) == 0 && mx[0] > 0)
+        printf("mutual exclusion: %lld steps, %lld contested (particle, landmark) pairs, %lld claims lost, %lld of them re-matched, %lld contests "
+               "overturned (the keeper is not the first claimant)\n",
+               (long long) mx[0], (long long) mx[1], (long long) mx[2], (long long) mx[3], (long long) mx[4]);
 }
 
 // The wrapper's loop (fastslam2wrapper.cpp:51-117) for a headless run, batched: what the per-iteration form asks of the GPU
@@ -641,6 +650,19 @@ int main(int argc, char **argv) {
             const std::string v = c.s("PARTICLE_ASSOC_SAMPLE");
             if (slamgpu_set_particle_assoc_sampling(ctx, v == "1" ? 1 : (v == "0" ? 0 : -1)) != 0) {
                 fprintf(stderr, "-PARTICLE_ASSOC_SAMPLE %s: %s\n", v.c_str(), slamgpu_last_error());
+                slamgpu_destroy(ctx);
+                return EXIT_FAILURE;
+            }
+        }
+        if (!c.s("PARTICLE_MUTEX").empty()) {
+            const std::string v = c.s("PARTICLE_MUTEX");
+            if (!particle) {
+                fprintf(stderr, "-PARTICLE_MUTEX %s: with -assoc particle\n", v.c_str());
+                slamgpu_destroy(ctx);
+                return EXIT_FAILURE;
+            }
+            if (slamgpu_set_particle_mutex(ctx, v == "1" ? 1 : (v == "0" ? 0 : -1)) != 0) {
+                fprintf(stderr, "-PARTICLE_MUTEX %s: %s\n", v.c_str(), slamgpu_last_error());
                 slamgpu_destroy(ctx);
                 return EXIT_FAILURE;
             }

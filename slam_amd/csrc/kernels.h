@@ -753,6 +753,33 @@ struct PpMissArgs {
     int32_t cap_nf, pad;
 };
 
+// Mutual exclusion for contested landmarks (slamgpu_set_particle_mutex): between the association's labels and their census / resolve.
+// For every particle, a slot two or more observations of the step name goes to the claimant with the smallest (class, nd, q) -- class 0:
+// nis < gate_reject, a claim the gates made; 1: a claim the exclusion rule made; a comparison that is false keeps the lower q -- and the
+// losers, in ascending q, take the free candidate (slot in use before the step, not retired, held, nis < gate_reject, held by no
+// observation) with the smallest nd, ties to the lower slot, or are discarded.  pp_mutex_kernel rewrites the label array in place.
+// hold[l][i] = the observation that holds slot l for particle i (-1: nobody; -2 - q: q, and the slot was contested): every entry is -1
+// before and after a launch (the launch resets the entries of its final labels, which are the entries it wrote).
+struct PpMutexArgs {
+    int32_t *labels;              // [nz][ncap], rewritten in place (a loser of slot l waits as -3 - l until its re-match)
+    int16_t *hold;                // [cap_nf][ncap]
+    unsigned long long *stats;    // [5] cumulative: steps | contested (particle, slot) pairs | claims lost | losers re-matched | contests
+                                  // whose keeper is not the lowest claimant
+    const float *z;               // [2 nz] (host-driven)
+    int32_t nz, nf;               // (host-driven) the observations, the slots in use before the step
+    float r00, r01, r10, r11, gate_reject;
+    int32_t lcap, lnz;            // LISTS: entries of observation q < lnz at items[2 (q lcap + k)], k < counts[q]; counts[q] > lcap or
+                                  // q >= lnz: the observation's re-match walks every slot
+    const uint32_t *retired;      // [(cap_nf + 31) / 32] (may be null)
+    const float4 *items;          // LISTS: AssocGridArgs::items / cell_start as assoc_lists_kernel left them
+    const int32_t *counts;
+    // device-driven (slamgpu_run_particle; else null): nz and z from the observation, nf from the book; first: the census of the FINAL
+    // labels (preset to INT_MAX by the caller: the association's own census of them is discarded; news cannot change)
+    const ObserveOut *obs;
+    const DevBook *book;
+    int32_t *first;
+};
+
 // The association's rule for one call, as the launchers take it (host only: never a kernel argument).  The launchers pick the
 // instantiation from it: the exclusion rule (slamgpu_particle_assoc::excl_*, unique_ratio; excl_base + excl_per_m = 0: off), its radii
 // per observation (excl_radii; may be null, only with the rule on) in place of excl_base + excl_per_m * range, and data association
@@ -882,6 +909,9 @@ struct KernelTable {
     void (*path_seed)(hipStream_t, const Buffers &, const WeightScratch &, const PathWalkArgs &, int stage);
     void (*path_push)(hipStream_t, const Buffers &, const PathRing &, const PathWalkArgs &);
     void (*path_finish)(hipStream_t, const PathWalkArgs &);
+    // slamgpu_set_particle_mutex (PpMutexArgs): the association's labels rewritten in place, before their census and the resolve; lists:
+    // the re-match walks the observations' candidate lists; device-driven when PpMutexArgs::obs is set
+    void (*pp_mutex)(hipStream_t, const Buffers &, const PpMutexArgs &, int lists);
 };
 
 const KernelTable *kernels_strict();

@@ -5450,13 +5450,197 @@ static void launch_pp_missed(hipStream_t st, const Buffers &B, const PpMissArgs 
     dispatch<2>([&](auto DEV) { hipLaunchKernelGGL(pp_missed_kernel<DEV>, dim3(B.ncap / kBlock), dim3(kBlock), 0, st, B, A); }, A.obs_dev != nullptr);
 }
 
+// ---- slamgpu_set_particle_mutex (kernels.h: PpMutexArgs) ---------------------------------------------------------------------
+// Mutual exclusion for contested landmarks, between the association's labels and their census / resolve.  One lane per particle, three
+// walks over the particle's labels (by observation: coalesced; kMutexBatch at a time, their loads in flight together):
+//   1. the claims: observation q writes itself into hold[label][i] when nobody is there; when somebody is, the two claimants' gate values
+//      on that one record are recomputed (assoc_landmark once, assoc_gate twice: nothing per pair is stored), the smaller (class, nd)
+//      keeps the slot -- a comparison that is false keeps the incumbent, which has the lower q -- and the other one's label becomes
+//      kMutexLost - slot;
+//   2. the losers, in ascending q (only the lanes that have one): the free candidate with the smallest nd, ties to the lower slot, or
+//      discard.  LISTS: over the observation's candidate list (every slot that can pass gate_reject for any particle; in no particular
+//      order, hence the explicit tie rule), an observation whose list overflowed or that lies past the lists grid over every slot;
+//   3. hold back to -1 at the final labels (exactly the entries written) and, DEV, the census of the final labels (first; news cannot
+//      change: a loser never becomes new).
+// Order-dependence remains among the losers only (walk 2).  The counters: one atomic per wave and counter that moved.
+constexpr int kMutexBatch = 8;
+constexpr int kMutexLost = -3;
+template <bool LISTS, bool DEV>
+__global__ void __launch_bounds__(kBlock) pp_mutex_kernel(Buffers B, PpMutexArgs A) {
+    int nz = A.nz, nf = A.nf;
+    const float *__restrict__ z = A.z;
+    if constexpr (DEV) {
+        nz = A.obs->nz;
+        if (nz == 0) return;
+        nf = A.book->nf;
+        z = reinterpret_cast<const float *>(A.obs + 1);
+    }
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    const bool on = i < B.n;
+    const int lane = threadIdx.x & (kWave - 1);
+    const int cur = B.ctrl->live[B.slot];
+    const size_t S = (size_t) B.ncap;
+    const float4 pa = on ? B.poseA[cur][i] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    int32_t *labels = A.labels;
+    int16_t *hold = A.hold;
+    const uint32_t *__restrict__ retired = A.retired;
+    if (i == 0) atomicAdd(A.stats, 1ull);
+    // 1. the claims
+    int n_lost = 0, q_first = nz;
+    for (int q0 = 0; q0 < nz; q0 += kMutexBatch) {
+        int labs[kMutexBatch], hv[kMutexBatch];
+#pragma unroll
+        for (int q = 0; q < kMutexBatch; q++) labs[q] = on ? labels[(size_t) min(q0 + q, nz - 1) * S + i] : kAssocDiscard;
+#pragma unroll
+        for (int q = 0; q < kMutexBatch; q++) hv[q] = labs[q] >= 0 ? (int) hold[(size_t) labs[q] * S + i] : -1;
+#pragma unroll
+        for (int q = 0; q < kMutexBatch; q++) {
+            const int j = q0 + q, lab = labs[q];
+            if (j >= nz || lab < 0) continue;
+            int16_t *const hp = hold + ((size_t) lab * S + i);
+            bool again = false;  // (an earlier observation of this batch named the slot: the word asked for above is stale)
+#pragma unroll
+            for (int p = 0; p < q; p++) again |= labs[p] == lab;
+            const int h = again ? (int) *hp : hv[q];
+            if (h == -1) {
+                *hp = (int16_t) j;
+                continue;
+            }
+            const int k = h >= 0 ? h : -2 - h;  // the incumbent
+            float4 la;
+            float lb;
+            read_through_genealogy(B, B.lmk_live, cur, S, lab, i, la, lb);
+            const AssocLm L = assoc_landmark(pa, la, lb, A.r00, A.r01, A.r10, A.r11);
+            float nis_k, nd_k, nis_j, nd_j;
+            assoc_gate(L, z[2 * k], z[2 * k + 1], nis_k, nd_k);
+            assoc_gate(L, z[2 * j], z[2 * j + 1], nis_j, nd_j);
+            const int cls_k = nis_k < A.gate_reject ? 0 : 1, cls_j = nis_j < A.gate_reject ? 0 : 1;
+            const bool wins = cls_j < cls_k || (cls_j == cls_k && nd_j < nd_k);
+            const int keep = wins ? j : k, lose = wins ? k : j;
+            *hp = (int16_t) (-2 - keep);
+            labels[(size_t) lose * S + i] = kMutexLost - lab;
+            q_first = min(q_first, lose);
+            n_lost++;
+        }
+    }
+    // 2. the losers
+    int n_contested = 0, n_over = 0, n_rematched = 0;
+    if (n_lost) {
+        for (int q = q_first; q < nz; q++) {
+            const int code = labels[(size_t) q * S + i];
+            if (code > kMutexLost) continue;
+            const int l = kMutexLost - code;
+            int16_t *const hp = hold + ((size_t) l * S + i);
+            const int h = *hp;
+            if (h < -1) {  // (the first loser of this slot met: the lowest claimant, unless the keeper is)
+                const int k = -2 - h;
+                n_contested++;
+                n_over += q < k ? 1 : 0;
+                *hp = (int16_t) k;
+            }
+            const float zr = z[2 * q], zb = z[2 * q + 1];
+            int jb = -1;
+            float nb = INFINITY;
+            bool every = true;
+            if constexpr (LISTS) {
+                const int cnt = q < A.lnz ? A.counts[q] : A.lcap + 1;
+                every = cnt > A.lcap;
+                if (!every) {
+                    const float4 *__restrict__ it = A.items + 2 * (size_t) q * A.lcap;
+                    for (int at = 0; at < cnt; at++) {
+                        const float4 bt = it[2 * at + 1];
+                        const int j = __float_as_int(bt.y), rw = __float_as_int(bt.w);
+                        if (retired && ((retired[j >> 5] >> (j & 31)) & 1u)) continue;
+                        if (hold[(size_t) j * S + i] != -1) continue;
+                        const int sl = B.gen[cur][gen_index(B.compact, S, rw & kRowMask, (size_t) i)];
+                        const size_t rec = (size_t) j * S + (size_t) sl;
+                        const float4 la = B.lmkA[(rw >> 30) & 1][rec];
+                        const float lb = B.lmkB[(rw >> 30) & 1][rec];
+                        const AssocLm L = assoc_landmark(pa, la, lb, A.r00, A.r01, A.r10, A.r11);
+                        float nis, nd;
+                        assoc_gate(L, zr, zb, nis, nd);
+                        if (la.x == la.x && nis < A.gate_reject && (nd < nb || (nd == nb && j < jb))) {
+                            nb = nd;
+                            jb = j;
+                        }
+                    }
+                }
+            }
+            if (every) {
+                constexpr int kTogether = 4;
+                for (int j0 = 0; j0 < nf; j0 += kTogether) {
+                    int jj[kTogether];
+                    bool ok[kTogether];
+#pragma unroll
+                    for (int t = 0; t < kTogether; t++) {
+                        jj[t] = min(j0 + t, nf - 1);
+                        ok[t] = j0 + t < nf && !(retired && ((retired[jj[t] >> 5] >> (jj[t] & 31)) & 1u)) && hold[(size_t) jj[t] * S + i] == -1;
+                    }
+#pragma unroll
+                    for (int t = 0; t < kTogether; t++) {
+                        if (!ok[t]) continue;
+                        float4 la;
+                        float lb;
+                        read_through_genealogy(B, B.lmk_live, cur, S, jj[t], i, la, lb);
+                        const AssocLm L = assoc_landmark(pa, la, lb, A.r00, A.r01, A.r10, A.r11);
+                        float nis, nd;
+                        assoc_gate(L, zr, zb, nis, nd);
+                        if (la.x == la.x && nis < A.gate_reject && nd < nb) {
+                            nb = nd;
+                            jb = jj[t];
+                        }
+                    }
+                }
+            }
+            if (jb >= 0) {
+                hold[(size_t) jb * S + i] = (int16_t) q;
+                n_rematched++;
+            }
+            labels[(size_t) q * S + i] = jb >= 0 ? jb : kAssocDiscard;
+        }
+    }
+    // 3. the table back to -1; DEV: the census of the final labels
+    for (int q0 = 0; q0 < nz; q0 += kMutexBatch) {
+        int labs[kMutexBatch];
+#pragma unroll
+        for (int q = 0; q < kMutexBatch; q++) labs[q] = (on && q0 + q < nz) ? labels[(size_t) min(q0 + q, nz - 1) * S + i] : kAssocDiscard;
+#pragma unroll
+        for (int q = 0; q < kMutexBatch; q++) {
+            const int lab = labs[q];
+            if (lab >= 0) hold[(size_t) lab * S + i] = (int16_t) -1;
+            if constexpr (DEV) {
+                // (pp_census_label's first half: one atomic per wave and distinct label, and only to lower the word)
+                unsigned long long todo = __ballot(lab >= 0);
+                while (todo) {
+                    const int src = __ffsll((long long) todo) - 1;
+                    const int lab0 = __builtin_amdgcn_readlane(lab, src);
+                    if (lane == src && A.first[lab0] > q0 + q) atomicMin(A.first + lab0, q0 + q);
+                    todo &= ~__ballot(lab == lab0);
+                }
+            }
+        }
+    }
+    int tot[4] = {n_contested, n_lost, n_rematched, n_over};
+#pragma unroll
+    for (int c = 0; c < 4; c++) {
+#pragma unroll
+        for (int d = kWave / 2; d > 0; d >>= 1) tot[c] += __shfl_xor(tot[c], d, kWave);
+        if (lane == 0 && tot[c]) atomicAdd(A.stats + 1 + c, (unsigned long long) tot[c]);
+    }
+}
+static void launch_pp_mutex(hipStream_t st, const Buffers &B, const PpMutexArgs &A, int lists) {
+    dispatch<2, 2>([&](auto LISTS, auto DEV) { hipLaunchKernelGGL((pp_mutex_kernel<LISTS, DEV>), dim3(B.ncap / kBlock), dim3(kBlock), 0, st, B, A); }, lists != 0,
+                   A.obs != nullptr);
+}
+
 static const KernelTable kTable = {launch_update, launch_update_any, launch_update_persist, launch_resample, launch_resample_ref, launch_scan, launch_gather, launch_flatten, launch_identity, launch_decompact, launch_finish, launch_predict, launch_estimate, launch_jacobians, launch_kat, launch_observe, launch_observe_book, launch_associate,
                                    launch_shard_plan, launch_shard_pack, launch_shard_unpack, launch_shard_finish, launch_dist_gather, launch_dist_flags, launch_peek, launch_lmk_box, launch_assoc_grid, launch_assoc_lists, launch_vote_compact,
                                    launch_associate_grid, launch_jacobians_multi, launch_pp_census, launch_pp_resolve, launch_pp_holders,
                                    launch_pp_resample, launch_pp_gather, launch_pp_book,
                                    launch_lists_box, launch_lists_geom, launch_lists_build, launch_lists_walk, launch_excl_radii,
                                    launch_map_summary, launch_map_finish, launch_pp_missed,
-                                   launch_path_compose, launch_path_record, launch_path_trace, launch_path_seed, launch_path_push, launch_path_finish};
+                                   launch_path_compose, launch_path_record, launch_path_trace, launch_path_seed, launch_path_push, launch_path_finish,
+                                   launch_pp_mutex};
 
 }  // namespace SLAM_KNS
 

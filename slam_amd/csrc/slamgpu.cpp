@@ -333,6 +333,13 @@ struct slamgpu_ctx {
     int32_t *pm_cnt_dev = nullptr;
     unsigned long long *pm_stats_dev = nullptr;
     bool pm_have = false;
+    // mutual exclusion for contested landmarks (slamgpu_set_particle_mutex): on / off, the table of who holds which slot
+    // ([cap_nf][ncap] int16, -1 between launches; held only while it is on) and the cumulative counters (PpMutexArgs::stats)
+    int32_t mx_on = 0;
+    int16_t *mx_hold_dev = nullptr;
+    unsigned long long *mx_stats_dev = nullptr;
+    size_t mx_hold_cap = 0;
+    bool pp_lists_done = false;      // the step's association went through the lists and left the slots' boxes (pp_missed's box test)
     // the observations of the last per-particle step (slamgpu_particle_labels): the host-driven call's count, or -1: the device-driven
     // iteration's (ObserveOut::nz)
     int32_t pp_lab_nz = 0;
@@ -1091,7 +1098,8 @@ void slamgpu_destroy(slamgpu_ctx *c) {
     if (c->pp_wf_dev) (void) hipFree(c->pp_wf_dev);
     if (c->pp_any_dev) (void) hipFree(c->pp_any_dev);
     for (void *p_ : {(void *) c->pp_st_dev, (void *) c->pp_words_dev, (void *) c->pp_pkt_dev, (void *) c->pp_report_dev, (void *) c->lstats_dev, (void *) c->excl_rho_dev,
-                     (void *) c->das_ratio_dev, (void *) c->das_stats_dev, (void *) c->pm_cnt_dev, (void *) c->pm_stats_dev})
+                     (void *) c->das_ratio_dev, (void *) c->das_stats_dev, (void *) c->pm_cnt_dev, (void *) c->pm_stats_dev, (void *) c->mx_hold_dev,
+                     (void *) c->mx_stats_dev})
         if (p_) (void) hipFree(p_);
     for (void *p_ : {(void *) c->box_dev, (void *) c->assoc_ids_dev, (void *) c->cell_start_dev, (void *) c->cell_fill_dev, (void *) c->items_dev,
                      (void *) c->geom_dev})
@@ -3435,6 +3443,68 @@ void pp_missed(slamgpu_ctx *c, int nf, const uint32_t *retired, const int32_t *u
     c->pm_have = true;
 }
 
+// slamgpu_set_particle_mutex: the table of who holds which slot, every entry -1, and the counters
+int mx_reserve(slamgpu_ctx *c) {
+    if (!c->mx_stats_dev) {
+        unsigned long long *p = nullptr;
+        if (hipMalloc((void **) &p, sizeof(unsigned long long) * 8) != hipSuccess) {
+            (void) hipGetLastError();
+            return fail(SLAMGPU_ERR_ALLOC, "slamgpu_set_particle_mutex: no room for the counters");
+        }
+        HIP_TRY(hipMemset(p, 0, sizeof(unsigned long long) * 8));
+        c->mx_stats_dev = p;
+    }
+    const size_t want = (size_t) c->B.cap_nf * (size_t) c->B.ncap;
+    if (c->mx_hold_dev && want <= c->mx_hold_cap) return 0;
+    int16_t *p = nullptr;
+    if (hipMalloc((void **) &p, sizeof(int16_t) * want) != hipSuccess) {
+        (void) hipGetLastError();
+        return fail(SLAMGPU_ERR_ALLOC, "slamgpu_set_particle_mutex: the table of %d slots x %d particles (%.1f MB) does not fit", c->B.cap_nf, c->B.ncap,
+                    (double) want * 2e-6);
+    }
+    if (hipMemsetAsync(p, 0xff, sizeof(int16_t) * want, c->stream) != hipSuccess) {  // (ordered before the first launch that reads it)
+        (void) hipGetLastError();
+        (void) hipFree(p);
+        return fail(SLAMGPU_ERR_HIP, "slamgpu_set_particle_mutex: hipMemsetAsync failed");
+    }
+    if (c->mx_hold_dev) {
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        (void) hipFree(c->mx_hold_dev);
+    }
+    c->mx_hold_dev = p;
+    c->mx_hold_cap = want;
+    return 0;
+}
+
+// slamgpu_set_particle_mutex: the launch between the association and the census / resolve (kernels.h: PpMutexArgs).  G: the step's lists
+// (SLAMGPU_ASSOC_LISTS), or null: a loser's re-match walks every slot; dev: device-driven
+void pp_mutex(slamgpu_ctx *c, const float *z_dev, int nz, int nf, const float R[4], const slamgpu_particle_assoc *opt, const AssocListArgs *G,
+              const PpArgs *dev) {
+    PpMutexArgs A{};
+    A.labels = c->pp_lab_dev;
+    A.hold = c->mx_hold_dev;
+    A.stats = c->mx_stats_dev;
+    A.z = z_dev;
+    A.nz = nz;
+    A.nf = nf;
+    A.r00 = R[0], A.r01 = R[1], A.r10 = R[2], A.r11 = R[3];
+    A.gate_reject = opt->gate_reject;
+    A.retired = dev ? dev->retired : c->retired_dev;
+    if (G) {
+        A.lcap = G->lcap;
+        A.lnz = G->nz;
+        A.items = G->items;
+        A.counts = G->cell_start;
+    }
+    if (dev) {
+        A.obs = dev->obs;
+        A.book = dev->book;
+        A.first = dev->first;
+    }
+    Timed t(c, "particle_mutex");
+    c->k->pp_mutex(c->stream, c->B, A, G ? 1 : 0);
+}
+
 int pp_reserve(slamgpu_ctx *c, int nz, size_t rows) {
     if (nz > c->pp_nz_cap || !c->pp_tab_dev)
         if (int rc = pp_grow_tab(c, std::max(64, 2 * nz))) return rc;
@@ -3488,6 +3558,8 @@ int do_update_particle(slamgpu_ctx *c, const float *z, int32_t nz, const float R
     HIP_TRY(hipMemcpyAsync(c->pp_z_dev, z, sizeof(float) * 2 * (size_t) nz, hipMemcpyHostToDevice, c->stream));
     const bool census_taken = c->pp_census_done;  // (by the association kernel itself: slamgpu_update_particle through the grid / lists)
     c->pp_census_done = false;
+    const bool lists_done = c->pp_lists_done;
+    c->pp_lists_done = false;
     if (!census_taken) {
         HIP_TRY(hipMemsetD32Async((hipDeviceptr_t) first_dev, 0x7fffffff, (size_t) cap_nf, c->stream));
         HIP_TRY(hipMemsetAsync(news_dev, 0, sizeof(int32_t) * (size_t) nz, c->stream));
@@ -3586,7 +3658,7 @@ int do_update_particle(slamgpu_ctx *c, const float *z, int32_t nz, const float R
                          c->pp_wf_dev, c->pp_any_dev, ratio, nullptr);
     }
     // (the records as they stand before the update: the device's tables are still those of sync_tables above)
-    pp_missed(c, nf0, c->retired_dev, first_dev, census_taken && opt->mode == SLAMGPU_ASSOC_LISTS, nullptr);
+    pp_missed(c, nf0, c->retired_dev, first_dev, (census_taken || lists_done) && opt->mode == SLAMGPU_ASSOC_LISTS, nullptr);
     HIP_TRY(hipGetLastError());
     c->obs_step++;
     c->pp_lab_nz = nz;
@@ -3745,6 +3817,7 @@ void lists_args(slamgpu_ctx *c, int nz, const float R[4], const slamgpu_particle
 // grid leaves them (do_update_particle: pp_census_done); nz <= kAssocMaxCells^2, pp_reserve done
 int associate_lists(slamgpu_ctx *c, const float *z, int32_t nz, const float R[4], const slamgpu_particle_assoc *opt) {
     c->pp_census_done = false;
+    c->pp_lists_done = false;
     if (int rc = flush_predict(c)) return rc;
     if (int rc = materialize(c)) return rc;  // plain set: particle k in slot k
     if (int rc = sync_tables(c)) return rc;
@@ -3780,6 +3853,12 @@ int associate_lists(slamgpu_ctx *c, const float *z, int32_t nz, const float R[4]
     HIP_TRY(hipGetLastError());
     for (int j : ids) c->box_dirty[(size_t) j] = 0;
     c->pp_census_done = true;
+    if (c->mx_on) {  // (mutual exclusion: the labels change, their census is taken again by do_update_particle; the boxes stay good)
+        pp_mutex(c, c->pp_z_dev, nz, c->nf, R, opt, &G, nullptr);
+        HIP_TRY(hipGetLastError());
+        c->pp_census_done = false;
+        c->pp_lists_done = true;
+    }
     return 0;
 }
 
@@ -3816,11 +3895,20 @@ int slamgpu_update_particle(slamgpu_ctx *c, const float *z, int32_t nz, const fl
             return fail(SLAMGPU_ERR_INVALID, "data association sampling needs SLAMGPU_ASSOC_EXHAUSTIVE, _AUTO or _LISTS (the grid does not sample)");
         if (int rc = book_pull(c)) return rc;
     }
+    c->pp_lists_done = false;
+    if (c->mx_on) {  // (mutual exclusion: its table for the context as it is now; the slots in use are the host's count)
+        if (int rc = book_pull(c)) return rc;
+        if (int rc = mx_reserve(c)) return rc;
+    }
     if (opt->mode == SLAMGPU_ASSOC_LISTS) {
         if (int rc = book_pull(c)) return rc;  // (the device-driven state back first: the boxes and the mask are the host's again)
         if (int rc = associate_lists(c, z, nz, R, opt)) return rc;
     } else if (int rc = associate_impl(c, z, nz, R, opt->gate_reject, opt->gate_augment, opt->mode, nullptr, nullptr, nullptr, nullptr, c->pp_lab_dev, opt)) {
         return rc;
+    } else if (c->mx_on) {  // (the observations are in pp_z_dev: associate_impl put them there for the per-particle step)
+        pp_mutex(c, c->pp_z_dev, nz, c->nf, R, opt, nullptr, nullptr);
+        HIP_TRY(hipGetLastError());
+        c->pp_census_done = false;
     }
     return do_update_particle(c, z, nz, R, opt, normals, strata, report, c->das_on ? c->das_ratio_dev : nullptr);
 }
@@ -3839,6 +3927,7 @@ int slamgpu_update_labels(slamgpu_ctx *c, const float *z, int32_t nz, const floa
     HIP_TRY(hipSetDevice(c->cfg.device));
     if (int rc = pp_reserve(c, nz, 1)) return rc;
     c->pp_census_done = false;  // (the caller's labels: nobody has taken their census; never sampled)
+    c->pp_lists_done = false;
     {
         // (the device reads the labels by observation: [nz][ncap])
         const size_t S = (size_t) c->B.ncap;
@@ -4115,9 +4204,9 @@ int pp_dev_iteration(slamgpu_ctx *c, int32_t nc, const float *controls, const fl
     AssocRule rule;
     if (int rc = particle_rule(c, opt, R, c->obs_out_dev, nullptr, 0, c->map_n, rule)) return rc;
     c->pp_lab_nz = -1;
+    AssocListArgs G;
     if (bound >= 0) {
         // the boxes of the slots the previous iteration wrote, the geometry, one list per observation, the walk (+ the census)
-        AssocListArgs G;
         lists_args(c, bound, R, opt, G);
         G.obs = c->obs_out_dev;
         G.book = c->book_dev;
@@ -4148,6 +4237,12 @@ int pp_dev_iteration(slamgpu_ctx *c, int32_t nc, const float *controls, const fl
     } else {
         Timed t(c, "associate");
         c->k->associate(c->stream, c->B, 0, nullptr, 0, R, rule, P.retired, c->pp_lab_dev, 1, &P);
+    }
+    if (c->mx_on) {
+        // mutual exclusion: pp_book_kernel must see the census of the FINAL labels -- the association's own is dropped (first back to its
+        // preset; news cannot change) and taken again where the labels are rewritten
+        HIP_TRY(hipMemsetD32Async((hipDeviceptr_t) P.first, 0x7fffffff, (size_t) c->B.cap_nf, c->stream));
+        pp_mutex(c, nullptr, 0, 0, R, opt, bound >= 0 ? &G : nullptr, &P);
     }
     {
         Timed t(c, "particle_book");
@@ -4248,6 +4343,8 @@ int slamgpu_run_particle(slamgpu_ctx *c, int32_t K, const int32_t *n_controls, c
         if (int rc = excl_rho_reserve(c, c->map_n)) return rc;
     if (c->das_on)
         if (int rc = das_reserve(c, c->map_n)) return rc;
+    if (c->mx_on)
+        if (int rc = mx_reserve(c)) return rc;
     const bool was_host = !c->pp_on_device;
     if (int rc = pp_push(c, c->pp_nz_cap)) return rc;
     bool box_all = false;
@@ -4357,6 +4454,9 @@ int slamgpu_set_particle_assoc_sampling(slamgpu_ctx *c, int32_t on) {
         return fail(SLAMGPU_ERR_INVALID, "slamgpu_set_particle_assoc_sampling: create the context with SLAMGPU_FLAG_PARTICLE_MAPS");
     if (c->cfg.rng_mode == SLAMGPU_RNG_TAPE)
         return fail(SLAMGPU_ERR_INVALID, "slamgpu_set_particle_assoc_sampling: TAPE-mode contexts replay the reference's draws, which have none for the association");
+    if (on && c->mx_on)
+        return fail(SLAMGPU_ERR_INVALID, "slamgpu_set_particle_assoc_sampling: not while mutual exclusion is on (slamgpu_set_particle_mutex): the sampled "
+                                         "pair's weight ratio has no meaning for a displaced claim");
     if (!on && c->das_ratio_dev) {  // (the ratios are held only while sampling is on; launches already enqueued may still read them)
         HIP_TRY(hipSetDevice(c->cfg.device));
         HIP_TRY(hipStreamSynchronize(c->stream));
@@ -4365,6 +4465,40 @@ int slamgpu_set_particle_assoc_sampling(slamgpu_ctx *c, int32_t on) {
         c->das_ratio_cap = 0;
     }
     c->das_on = on;
+    return 0;
+}
+
+int slamgpu_set_particle_mutex(slamgpu_ctx *c, int32_t on) {
+    if (int rc = check_ctx(c)) return rc;
+    if (on != 0 && on != 1) return fail(SLAMGPU_ERR_INVALID, "slamgpu_set_particle_mutex: on must be 0 or 1 (%d)", (int) on);
+    if (!(c->cfg.flags & SLAMGPU_FLAG_PARTICLE_MAPS))
+        return fail(SLAMGPU_ERR_INVALID, "slamgpu_set_particle_mutex: create the context with SLAMGPU_FLAG_PARTICLE_MAPS");
+    if (on && c->das_on)
+        return fail(SLAMGPU_ERR_INVALID, "slamgpu_set_particle_mutex: not while data association sampling is on (slamgpu_set_particle_assoc_sampling): the "
+                                         "sampled pair's weight ratio has no meaning for a displaced claim");
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    if (on) {
+        if (int rc = mx_reserve(c)) return rc;  // (SLAMGPU_ERR_ALLOC: the setting stays as it was)
+    } else if (c->mx_hold_dev) {  // (the table is held only while it is on; launches already enqueued may still use it)
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        HIP_TRY(hipFree(c->mx_hold_dev));
+        c->mx_hold_dev = nullptr;
+        c->mx_hold_cap = 0;
+    }
+    c->mx_on = on;
+    return 0;
+}
+
+int slamgpu_particle_mutex_stats(slamgpu_ctx *c, int64_t out[5]) {
+    if (int rc = check_ctx(c)) return rc;
+    if (!out) return fail(SLAMGPU_ERR_INVALID, "slamgpu_particle_mutex_stats: null output");
+    unsigned long long h[5] = {0, 0, 0, 0, 0};
+    if (c->mx_stats_dev) {
+        HIP_TRY(hipSetDevice(c->cfg.device));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        HIP_TRY(hipMemcpy(h, c->mx_stats_dev, sizeof h, hipMemcpyDeviceToHost));
+    }
+    for (int k = 0; k < 5; k++) out[k] = (int64_t) h[k];
     return 0;
 }
 
