@@ -538,6 +538,28 @@ int slamgpu_peek(slamgpu_ctx *ctx, int32_t first, int32_t stride, int32_t count,
  * for slots outside [0, slamgpu_num_landmarks)); count == 0 does nothing.  Synchronises. */
 #define SLAMGPU_MAP_STRIDE 9
 int slamgpu_map_summary(slamgpu_ctx *ctx, int32_t first_slot, int32_t count, double *out, int32_t *holders);
+/* Joint shares: what the summary's marginals cannot say about TWO slots.  pairs[2k], pairs[2k + 1] are slots a, b of pair k: any
+ * slots of [0, slamgpu_num_landmarks), a == b allowed, the same pair as often as the caller likes.  The particle set, the weights
+ * w^_i and every convention are slamgpu_map_summary's: queued predicts flushed, the outstanding resampling stage run, a pending
+ * gather read through its ancestors with weight 1/N, records through the genealogy, log-weights as exp(l - max l).  With J the
+ * particles that hold BOTH slots (neither record absent) and d_i = xf_a,i - xf_b,i (taken in double from the float32 records:
+ * exact), out[k][SLAMGPU_MAP_STRIDE] is the summary's nine fields on d:
+ *     [0]       joint share s_ab = sum_{i in J} w^_i
+ *     [1..2]    mean separation delta = sum_{i in J} w^_i d_i / s_ab
+ *     [3..5]    scatter sum_{i in J} w^_i (d_i - delta)(d_i - delta)^T / s_ab: xx, xy, yy
+ *     [6..8]    sum_{i in J} w^_i (Pf_a,i + Pf_b,i) / s_ab: p00, p10, p11 -- the covariance of d INSIDE a particle, whose landmarks
+ *               are independent given its path
+ * and both[k] (may be NULL) = |J|, exact.  Two slots that are alternatives for one landmark (a particle holds one or the other)
+ * have s_ab near 0 whatever their own shares; two neighbouring landmarks have s_ab near min(s_a, s_b).  J empty: share 0, both 0,
+ * entries 1..8 NaN.  Weights that sum to zero or to nothing finite: every double NaN, the call returns 0, both still exact.
+ * Without SLAMGPU_FLAG_PARTICLE_MAPS every joint share is 1.  a == b: the summary's slot with d = 0 (delta and the scatter are
+ * exactly 0, [6..8] twice the slot's mean Pf).  Retired slots are reported like any other.  Sums are in double, in a fixed order,
+ * without floating-point atomics: the same state gives the same bits, and a pair's result does not depend on where it stands in
+ * `pairs`, on what else the list holds, or on how the call cuts the list into chunks.  Read-only like slamgpu_peek: the state the
+ * next step works on is bit for bit what it would have been without the call.  SLAMGPU_ERR_INVALID, outputs untouched: a slot
+ * outside the range, count < 0, NULL pairs or out with count > 0, a distributed or shard context.  count == 0 does nothing.
+ * Synchronises. */
+int slamgpu_map_pairs(slamgpu_ctx *ctx, const int32_t *pairs, int32_t count, double *out, int32_t *both);
 
 /* ---- path posterior: recorded ancestry, traces, the smoothed path ---------------------------------------------------
  * FastSLAM's posterior is over paths and maps; these entry points report the path half.  "The set" at a moment is what

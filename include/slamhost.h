@@ -77,6 +77,35 @@ int slamhost_gated_step(slamhost_gated *g, const float *z, int32_t nz, const int
                         int32_t *retire, int32_t *n_retire);
 void slamhost_gated_counts(const slamhost_gated *g, int32_t counts[6]);
 
+/* From the slot table of the posterior map to a table of LANDMARKS.  A run with the association unknown opens a second slot beside a
+ * mapped landmark whenever a particle off its true pose calls an observation of it new; the marginal shares of slamgpu_map_summary
+ * cannot tell such ALTERNATIVES (no particle holds both) from two NEIGHBOURING landmarks (most holders of one hold the other).  The
+ * joint share of slamgpu_map_pairs can.  Both functions are pure: no GPU, no state.
+ *
+ * summary[slots][9] is slamgpu_map_summary's output (share | mean x, y | scatter xx, xy, yy | mean Pf 00, 10, 11), joint[npairs][9]
+ * slamgpu_map_pairs' for pairs[npairs][2] (only its share, joint[k][0], is read).
+ *
+ * candidates: every a < b with both shares > 0 and the means closer than `radius`, in ascending order (a, then b), found through a
+ * uniform grid over the means.  Returns their number; the first max_pairs of them are written (pairs may be NULL with max_pairs 0:
+ * count, allocate, call again).  -1: bad arguments.
+ *
+ * merge: an edge joins a and b when both shares are > 0, |mu_a - mu_b| < radius and s_ab <= cohold * min(s_a, s_b) -- near each other and
+ * (almost) never held together.  Clusters are the connected components (single linkage), numbered in ascending order of their lowest
+ * slot; cluster[j] is slot j's, -1 for a slot of share 0.  merged[c][9], in the summary's layout, with S = sum of the members' shares:
+ *     share      sum_C s_j - sum of s_jk over the given pairs inside C (an unordered pair given twice counts once), clamped to
+ *                [max_C s_j, 1]: the second-order inclusion-exclusion (Bonferroni) lower bound of the weight that holds at least one
+ *                member.  It is exact for clusters of two and whenever no particle holds three members; pairs inside C that the
+ *                caller did not give count as never held together.
+ *     mean       sum s_j mu_j / S
+ *     [3..5]     sum s_j (scatter_j + (mu_j - mean)(mu_j - mean)^T) / S
+ *     [6..8]     sum s_j Pf_j / S
+ * A cluster of one slot reproduces the slot's nine numbers bit for bit.  *nmerged = the number of clusters.  radius and cohold are the
+ * caller's; slam-backend's defaults are 1.0 m and 0.1, and no accuracy claim rests on the 0.1 yet.  Returns 0; -1: bad arguments (a
+ * pair outside [0, slots), a NULL array that is needed). */
+int64_t slamhost_map_candidates(const double *summary, int32_t slots, double radius, int32_t *pairs, int64_t max_pairs);
+int slamhost_map_merge(const double *summary, int32_t slots, const int32_t *pairs, const double *joint, int32_t npairs, double radius,
+                       double cohold, int32_t *cluster /*[slots]*/, double *merged /*[slots][9]*/, int32_t *nmerged);
+
 void slamhost_draw_normals(int32_t count, int32_t dim, float *out); /* count x randn(dim,1): dim+1 rand() each */
 int32_t slamhost_draw_strata(int32_t N, float *out);                /* returns the reference's strata count (== N when supported) */
 double slamhost_unif_rand(void);                                    /* unifRand (core.cpp:775) */

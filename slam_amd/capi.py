@@ -29,7 +29,7 @@ DECLARED_SYMBOLS = [
     "slamgpu_run_particle", "slamgpu_particle_report_fetch", "slamgpu_particle_list_stats",
     "slamgpu_set_particle_excl_spacing", "slamgpu_particle_excl_radii",
     "slamgpu_set_particle_assoc_sampling", "slamgpu_particle_sample_stats", "slamgpu_particle_labels",
-    "slamgpu_map_summary", "slamgpu_set_particle_mutex", "slamgpu_particle_mutex_stats",
+    "slamgpu_map_summary", "slamgpu_map_pairs", "slamgpu_set_particle_mutex", "slamgpu_particle_mutex_stats",
     "slamgpu_set_particle_miss", "slamgpu_particle_missed", "slamgpu_particle_miss_stats", "slamgpu_particle_miss_visited",
     "slamgpu_path_enable", "slamgpu_path_record", "slamgpu_path_info", "slamgpu_path_fetch", "slamgpu_path_trace", "slamgpu_path_summary",
 ]
@@ -139,6 +139,8 @@ def load_library():
         L.slamgpu_particle_mutex_stats.argtypes = [C.c_void_p, C.c_void_p]
     if hasattr(L, "slamgpu_map_summary"):
         L.slamgpu_map_summary.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
+    if hasattr(L, "slamgpu_map_pairs"):
+        L.slamgpu_map_pairs.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
     if hasattr(L, "slamgpu_path_enable"):
         L.slamgpu_path_enable.argtypes = [C.c_void_p, C.c_int32]
         L.slamgpu_path_record.argtypes = [C.c_void_p]
@@ -542,6 +544,17 @@ class SlamGpu:
         holders = np.zeros(max(count, 0), np.int32)
         _chk(self.L.slamgpu_map_summary(self.h, first, count, _ptr(out), _ptr(holders)))
         return dict(share=out[:, 0].copy(), mean=out[:, 1:3].copy(), scatter=out[:, 3:6].copy(), pf=out[:, 6:9].copy(), holders=holders)
+
+    def map_pairs(self, pairs):
+        """slamgpu_map_pairs: for pairs[k] = (a, b) of landmark slots, over the particles that hold BOTH: share[count] (the joint share),
+        mean[count, 2] of d = xf_a - xf_b, its scatter[count, 3], pf[count, 3] = the mean of Pf_a + Pf_b, and both[count], the number of
+        such particles; the weights and conventions of map_summary; rewrites no state"""
+        pairs = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+        count = len(pairs)
+        out = np.zeros((count, MAP_STRIDE), np.float64)
+        both = np.zeros(count, np.int32)
+        _chk(self.L.slamgpu_map_pairs(self.h, _ptr(pairs), count, _ptr(out), _ptr(both)))
+        return dict(share=out[:, 0].copy(), mean=out[:, 1:3].copy(), scatter=out[:, 3:6].copy(), pf=out[:, 6:9].copy(), both=both)
 
     def path_enable(self, capacity):
         """slamgpu_path_enable: record the path posterior in a ring of `capacity` records (0: stop and free)"""

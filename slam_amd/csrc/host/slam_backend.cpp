@@ -29,6 +29,16 @@
 //                        particle's map.  posterior: one more line from slamgpu_map_summary, over ALL particles: the slots held by at
 //                        least half of the weight, how many true landmarks lie within 1 m of such a slot's weighted mean, how many such
 //                        slots lie within 1 m of no true landmark, and the slots held by less than half / by none.  Not with -gpus k > 1.
+//   -map merged          posterior's line, and one more: the slot table turned into a landmark table.  Slots whose means lie within
+//                        -MAP_MERGE_RADIUS (default 1.0 m: what the posterior line calls the same place) and whose JOINT share
+//                        (slamgpu_map_pairs: the weight of the particles that hold both) is at most -MAP_MERGE_COHOLD (default 0.1; a
+//                        chosen default, no accuracy claim rests on it yet) x the smaller of their shares are alternatives for ONE
+//                        landmark and are merged (slamhost_map_merge): the merged landmarks with share >= 0.5, the true landmarks within
+//                        1 m of one of them, those of them within 1 m of no true landmark, the clusters of more than one slot, and the
+//                        largest joint share among the candidate pairs.  Not with -gpus k > 1.
+//   -LOG_WEIGHTS 0|1     1: the particle weights are kept as log-weights (slamgpu_config.log_weights): dense maps, where linear weights
+//                        underflow within a few steps and -map posterior / merged could only print "not available".  Default 0; single
+//                        GPU only.
 //   -plot <sinks>        the per-step output the reference sends to slam-gui (plotting/NetworkPlot.cpp), byte for byte:
 //                        tcp://127.0.0.1:4242 (the existing slam-gui) | file:<frames> | gather:<dir> (the GUI's DataGatherer
 //                        files, headless) | none (default); several separated by ','
@@ -57,6 +67,7 @@
 #include <vector>
 
 #include "../../../include/slamgpu.h"
+#include "../../../include/slamhost.h"
 #include "ekfslam.h"
 #include "frontend.h"
 #include "gated.h"
@@ -95,6 +106,10 @@ static void usage(const char *a0) {
     printf("                        re-matched or discarded (mutual exclusion; default 0: the first claim keeps it; not with -PARTICLE_ASSOC_SAMPLE 1)\n");
     printf("    -map best|posterior the map reported at the end: best (default; -assoc particle: the best particle's), or posterior: one more line,\n");
     printf("                        the landmark slots by the share of ALL particles' weight that holds them (slamgpu_map_summary; not with -gpus)\n");
+    printf("    -map merged         posterior's line and one more: slots whose means lie within -MAP_MERGE_RADIUS (default 1.0 m) of each other and whose joint\n");
+    printf("                        share (slamgpu_map_pairs) is at most -MAP_MERGE_COHOLD (default 0.1: a chosen default, no accuracy claim rests on it yet)\n");
+    printf("                        x the smaller of their shares are merged into one landmark (slamhost_map_merge; not with -gpus)\n");
+    printf("    -LOG_WEIGHTS 0|1    keep the particle weights as log-weights (default 0; dense maps, where linear weights underflow; not with -gpus)\n");
     printf("    -path none|smoothed smoothed: record the path posterior (one record per observation step, -PATH_RECORDS n of them kept, default 4096)\n");
     printf("                        and print one more line: the smoothed path's distance to the true path beside the filtered estimates', and the\n");
     printf("                        distinct ancestors 1 / 10 / 100 records back (slamgpu_path_summary; FastSLAM, one GPU, not -assoc particle -observe device)\n");
@@ -234,6 +249,52 @@ static int run_distributed(Simulator &sim, int k, long maxsteps, FILE *log, Plot
 
 // -map posterior: the slots as the whole particle set sees them (slamgpu_map_summary): confident = held by at least half of the weight
 static bool g_map_posterior = false;
+// -map merged: the posterior line, then the landmarks left after merging the slots that are alternatives for one landmark
+static bool g_map_merged = false;
+static double g_merge_radius = 1.0, g_merge_cohold = 0.1;
+static void print_merged_map(slamgpu_ctx *ctx, const Simulator &sim, const std::vector<double> &sum, int slots) {
+    const int64_t ncand = slamhost_map_candidates(sum.data(), slots, g_merge_radius, nullptr, 0);
+    if (ncand < 0 || ncand > INT32_MAX) {
+        fprintf(stderr, "-map merged: %lld candidate pairs\n", (long long) ncand);
+        return;
+    }
+    std::vector<int32_t> pairs(2 * (size_t) std::max<int64_t>(ncand, 1)), cluster((size_t) std::max(slots, 1));
+    std::vector<double> joint((size_t) SLAMGPU_MAP_STRIDE * (size_t) std::max<int64_t>(ncand, 1)), merged((size_t) SLAMGPU_MAP_STRIDE * (size_t) std::max(slots, 1));
+    slamhost_map_candidates(sum.data(), slots, g_merge_radius, pairs.data(), ncand);
+    if (slamgpu_map_pairs(ctx, pairs.data(), (int32_t) ncand, joint.data(), nullptr) != 0) {
+        fprintf(stderr, "slamgpu: %s\n", slamgpu_last_error());
+        return;
+    }
+    int32_t nmerged = 0;
+    if (slamhost_map_merge(sum.data(), slots, pairs.data(), joint.data(), (int32_t) ncand, g_merge_radius, g_merge_cohold, cluster.data(), merged.data(),
+                           &nmerged) != 0) {
+        fprintf(stderr, "-map merged: slamhost_map_merge refused its arguments\n");
+        return;
+    }
+    int confident = 0, covered = 0, stray = 0, multi = 0;
+    std::vector<char> hit((size_t) sim.map.nlm, 0);
+    std::vector<int> members((size_t) std::max(nmerged, 1), 0);
+    for (int j = 0; j < slots; j++)
+        if (cluster[(size_t) j] >= 0) members[(size_t) cluster[(size_t) j]]++;
+    for (int q = 0; q < nmerged; q++) {
+        multi += members[(size_t) q] > 1;
+        const double *e = merged.data() + (size_t) SLAMGPU_MAP_STRIDE * (size_t) q;
+        if (!(e[0] >= 0.5)) continue;
+        confident++;
+        bool near = false;
+        for (int t = 0; t < sim.map.nlm; t++) {
+            const double dx = e[1] - (double) sim.map.lm[(size_t) t], dy = e[2] - (double) sim.map.lm[(size_t) sim.map.nlm + t];
+            if (dx * dx + dy * dy < 1.0) hit[(size_t) t] = 1, near = true;
+        }
+        if (!near) stray++;
+    }
+    for (char h : hit) covered += h;
+    double top = 0.0;
+    for (int64_t k = 0; k < ncand; k++) top = std::max(top, joint[(size_t) SLAMGPU_MAP_STRIDE * (size_t) k]);
+    printf("merged map: %d landmarks held by at least half of the weight (%d of the %d true landmarks within 1 m of one of them, %d of them within 1 m of "
+           "no true landmark); %d clusters of more than one slot; largest joint share of the %lld candidate pairs %.6f (radius %g m, cohold %g)\n",
+           confident, covered, sim.map.nlm, stray, multi, (long long) ncand, top, g_merge_radius, g_merge_cohold);
+}
 static void print_posterior_map(slamgpu_ctx *ctx, const Simulator &sim) {
     if (!g_map_posterior) return;
     const int slots = slamgpu_num_landmarks(ctx);
@@ -268,6 +329,7 @@ static void print_posterior_map(slamgpu_ctx *ctx, const Simulator &sim) {
     printf("posterior map: %d slots held by at least half of the weight (%d of the %d true landmarks within 1 m of the mean of one of them, %d of them "
            "within 1 m of no true landmark); %d slots held by less than half, %d by none\n",
            confident, covered, sim.map.nlm, stray, minority, dead);
+    if (g_map_merged) print_merged_map(ctx, sim, sum, slots);
 }
 
 // -path smoothed: the recorded path posterior (slamgpu_path_*).  Record r belongs to observation step r: g_path_steps[r] holds that
@@ -513,12 +575,22 @@ int main(int argc, char **argv) {
     {
         // -map is this program's own report option, not a setting of the run: it stays out of the settings printed below
         const std::string m = sim.conf.s("map");
-        if (!m.empty() && m != "best" && m != "posterior") {
-            fprintf(stderr, "-map best|posterior\n");
+        if (!m.empty() && m != "best" && m != "posterior" && m != "merged") {
+            fprintf(stderr, "-map best|posterior|merged\n");
             return EXIT_FAILURE;
         }
-        g_map_posterior = m == "posterior";
+        g_map_merged = m == "merged";
+        g_map_posterior = m == "posterior" || g_map_merged;
         sim.conf.kv.erase("map");
+        const std::string mr = sim.conf.s("MAP_MERGE_RADIUS"), mc = sim.conf.s("MAP_MERGE_COHOLD");
+        if (!mr.empty()) g_merge_radius = atof(mr.c_str());
+        if (!mc.empty()) g_merge_cohold = atof(mc.c_str());
+        if ((!mr.empty() || !mc.empty()) && (!g_map_merged || !(g_merge_radius > 0.0) || !(g_merge_cohold >= 0.0 && g_merge_cohold <= 1.0))) {
+            fprintf(stderr, "-MAP_MERGE_RADIUS r -MAP_MERGE_COHOLD c: with -map merged; r > 0, 0 <= c <= 1\n");
+            return EXIT_FAILURE;
+        }
+        sim.conf.kv.erase("MAP_MERGE_RADIUS");
+        sim.conf.kv.erase("MAP_MERGE_COHOLD");
         // ... and so is -path (with -PATH_RECORDS).  What it cannot do is refused here, from the arguments alone
         const std::string p = sim.conf.s("path"), pr = sim.conf.s("PATH_RECORDS");
         if (!p.empty() && p != "none" && p != "smoothed") {
@@ -562,7 +634,12 @@ int main(int argc, char **argv) {
     }
     if (c.method != 0 && !c.s("gpus").empty() && atoi(c.s("gpus").c_str()) != 1) {
         if (g_map_posterior) {
-            fprintf(stderr, "-map posterior: single GPU only (slamgpu_map_summary has no distributed form)\n");
+            fprintf(stderr, "-map %s: single GPU only (slamgpu_map_summary%s no distributed form)\n", g_map_merged ? "merged" : "posterior",
+                    g_map_merged ? " and slamgpu_map_pairs have" : " has");
+            return EXIT_FAILURE;
+        }
+        if (!c.s("LOG_WEIGHTS").empty() && c.s("LOG_WEIGHTS") != "0") {
+            fprintf(stderr, "-LOG_WEIGHTS %s: single GPU only (log-weights have no distributed form)\n", c.s("LOG_WEIGHTS").c_str());
             return EXIT_FAILURE;
         }
         if (plot.active()) {
@@ -604,6 +681,10 @@ int main(int argc, char **argv) {
         fprintf(stderr, "-PARTICLE_MISS p -PARTICLE_MISS_MARGIN m: both together, with -assoc particle and a FastSLAM method; 0 < p <= 1, 0 <= m < MAX_RANGE\n");
         return EXIT_FAILURE;
     }
+    if (!c.s("LOG_WEIGHTS").empty() && (c.method == 0 || (c.s("LOG_WEIGHTS") != "0" && c.s("LOG_WEIGHTS") != "1"))) {
+        fprintf(stderr, "-LOG_WEIGHTS 0|1, with a FastSLAM method\n");
+        return EXIT_FAILURE;
+    }
     if (c.method != 0) {
         printf("%s\n\n", c.method == 2 ? "FastSLAM 2" : "FastSLAM 1");
         slamgpu_config g{};
@@ -621,6 +702,7 @@ int main(int argc, char **argv) {
         g.rng_mode = parity ? SLAMGPU_RNG_TAPE : SLAMGPU_RNG_PHILOX;
         g.math_mode = math == "strict" ? SLAMGPU_MATH_STRICT : SLAMGPU_MATH_FAST;
         g.seed = (uint64_t) c.SWITCH_SEED_RANDOM;
+        g.log_weights = c.s("LOG_WEIGHTS") == "1";
         g.flags = (observe_dev ? SLAMGPU_FLAG_DEVICE_OBSERVE : 0) | (particle ? SLAMGPU_FLAG_PARTICLE_MAPS : 0);
         popt.gate_reject = c.GATE_REJECT;
         popt.gate_augment = c.GATE_AUGMENT;

@@ -548,6 +548,16 @@ struct MapSummaryArgs {
     double *out;                // [count][kMapStride]
     int32_t *holders;           // [count]
 };
+// Joint shares of pairs of slots (slamgpu_map_pairs): map_pairs_kernel is map_summary_kernel over the particles that hold BOTH slots
+// of a pair, on d = xf_a - xf_b (double, exact) and Pf_a + Pf_b in the place of xf and Pf: grid (particle tiles, groups of kMapSlots
+// pairs), the same weights kept in registers, the same pivoted double sums in the same order, the same partial per tile, finished
+// by map_finish_kernel as it stands (S.count pairs take the place of the slots; S.first_slot is not read).  Per pair a lane loads the
+// two genealogy entries of each of its particles (one when both slots lie in one row, none while the row is the previous pair's)
+// and asks for all 2 * kMapT records before it uses any.
+struct MapPairsArgs {
+    MapSummaryArgs S;
+    const int32_t *pairs;       // [S.count][2] slots a, b of this launch's pairs, each inside [0, number of slots)
+};
 
 // Path posterior (slamgpu_path_*): a ring of records in device memory and the walks over it.  Record r of the ring holds, for every
 // particle k of the set at the time of the record, one float4: x, y, theta as slamgpu_peek shows them and, in .w, the BITS of
@@ -897,6 +907,8 @@ struct KernelTable {
     // slamgpu_map_summary (MapSummaryArgs): the partials of one chunk of slots, and their finishing pass.  Tables in sync; reads only
     void (*map_summary)(hipStream_t, const Buffers &, const WeightScratch &, const MapSummaryArgs &);
     void (*map_finish)(hipStream_t, const MapSummaryArgs &);
+    // slamgpu_map_pairs (MapPairsArgs): the partials of one chunk of pairs, finished by map_finish on MapPairsArgs::S.  Reads only
+    void (*map_pairs)(hipStream_t, const Buffers &, const WeightScratch &, const MapPairsArgs &);
     // slamgpu_set_particle_miss (PpMissArgs): the held, in-view, unclaimed slots of every particle into its weight factor; after pp_resolve
     void (*pp_missed)(hipStream_t, const Buffers &, const PpMissArgs &);
     // slamgpu_path_* (PathRing, PathTraceArgs, PathWalkArgs).  path_compose: dst[k] = src[ancestor of k in the last update] (keep_slot as

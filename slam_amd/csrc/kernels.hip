@@ -4968,6 +4968,175 @@ static void launch_map_finish(hipStream_t st, const MapSummaryArgs &A) {
     hipLaunchKernelGGL(map_finish_kernel, dim3((A.count + kSlots - 1) / kSlots), dim3(kBlock), 0, st, A);
 }
 
+// ---- slamgpu_map_pairs (kernels.h: MapPairsArgs) -------------------------------------------------------------------------------
+// map_summary_kernel's reduction on d = xf_a - xf_b over the particles that hold both slots of a pair: the same weights, the same
+// order, the same partial (MapPart) per tile and pair, so that map_finish_kernel finishes it.  A pair's sums see nothing of the other
+// pairs of its group: its bits do not depend on its place in the list
+__global__ void __launch_bounds__(kBlock) map_pairs_kernel(Buffers B, WeightScratch ws, MapPairsArgs P) {
+    constexpr int kWaves = kBlock / kWave;
+    __shared__ double sh[kMapSlots][kWaves][kMapFields];
+    __shared__ double sh_w[kWaves];
+    __shared__ float sh_m[kWaves];
+    const MapSummaryArgs &A = P.S;
+    const Ctrl *ctrl = B.ctrl;
+    const int cur = ctrl->live[B.slot];
+    const bool pend = ctrl->pend[B.slot] != 0;
+    const size_t S = (size_t) B.ncap;
+    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
+    // this lane's particles: ancestor and weight, once for every pair of the group (map_summary_kernel's, operation for operation)
+    int anc[kMapT];
+    float wf[kMapT];
+    bool on[kMapT];
+    float mb = -INFINITY;
+#pragma unroll
+    for (int t = 0; t < kMapT; t++) {
+        const int i = blockIdx.x * kMapTile + t * kBlock + threadIdx.x;
+        on[t] = i < B.n;
+        anc[t] = on[t] ? (pend ? ws.keep[B.slot][i] : i) : 0;
+        wf[t] = on[t] ? (pend ? ctrl->inv_n : B.poseA[cur][anc[t]].w) : 0.0f;
+        if (on[t] && A.logw) mb = fmaxf(mb, wf[t]);
+    }
+    double w[kMapT];
+    if (A.logw) {
+        for (int d = kWave / 2; d > 0; d >>= 1) mb = fmaxf(mb, __shfl_xor(mb, d, kWave));
+        if (lane == 0) sh_m[wave] = mb;
+        __syncthreads();
+        mb = sh_m[0];
+        for (int v = 1; v < kWaves; v++) mb = fmaxf(mb, sh_m[v]);
+#pragma unroll
+        for (int t = 0; t < kMapT; t++) w[t] = (on[t] && mb != -INFINITY) ? exp((double) wf[t] - (double) mb) : 0.0;
+    } else {
+        mb = 0.0f;
+#pragma unroll
+        for (int t = 0; t < kMapT; t++) w[t] = (double) wf[t];
+    }
+    if (blockIdx.y == 0) {
+        double sw = 0.0;
+#pragma unroll
+        for (int t = 0; t < kMapT; t++) sw += w[t];
+        sw = wave_sum_d(sw);
+        if (lane == 0) sh_w[wave] = sw;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            double tot = sh_w[0];
+            for (int v = 1; v < kWaves; v++) tot += sh_w[v];
+            A.wpart[2 * blockIdx.x] = tot;
+            A.wpart[2 * blockIdx.x + 1] = (double) mb;
+        }
+    }
+    const int s0 = blockIdx.y * kMapSlots, sn = min(kMapSlots, A.count - s0);
+    int rowa = -1, rowb = -1;
+    int sla[kMapT], slb[kMapT];
+    for (int s = 0; s < sn; s++) {
+        const int l0 = P.pairs[2 * (s0 + s)], l1 = P.pairs[2 * (s0 + s) + 1];
+        const int r0 = B.erow[l0], r1 = B.erow[l1];
+        // (uniform) the genealogy entries: kept from the pair before while the row stays, one load for both slots of one row
+        if (r0 != rowa) {
+            rowa = r0;
+#pragma unroll
+            for (int t = 0; t < kMapT; t++) sla[t] = on[t] ? B.gen[cur][gen_index(B.compact, S, r0, (size_t) anc[t])] : 0;
+        }
+        if (r1 == r0) {
+            rowb = r1;
+#pragma unroll
+            for (int t = 0; t < kMapT; t++) slb[t] = sla[t];
+        } else if (r1 != rowb) {
+            rowb = r1;
+#pragma unroll
+            for (int t = 0; t < kMapT; t++) slb[t] = on[t] ? B.gen[cur][gen_index(B.compact, S, r1, (size_t) anc[t])] : 0;
+        }
+        // all 2 * kMapT records of the pair are asked for before any of them is used
+        float4 la[kMapT], ma[kMapT];
+        float lb[kMapT], mb2[kMapT];
+#pragma unroll
+        for (int t = 0; t < kMapT; t++) {
+            la[t] = ma[t] = make_float4(NAN, NAN, NAN, NAN);
+            lb[t] = mb2[t] = NAN;
+            if (on[t]) {
+                read_record(B, B.lmk_live, S, l0, sla[t], la[t], lb[t]);
+                read_record(B, B.lmk_live, S, l1, slb[t], ma[t], mb2[t]);
+            }
+        }
+        // d in double from the float32 records (exact); pivot: the d of the wave's first particle that holds both
+        double dx[kMapT], dy[kMapT];
+        bool both[kMapT];
+        bool have = false;
+        double px = 0.0, py = 0.0;
+        int cnt = 0;
+#pragma unroll
+        for (int t = 0; t < kMapT; t++) {
+            both[t] = la[t].x == la[t].x && ma[t].x == ma[t].x;
+            dx[t] = (double) la[t].x - (double) ma[t].x;
+            dy[t] = (double) la[t].y - (double) ma[t].y;
+            const unsigned long long hm = __ballot(both[t]);
+            cnt += (int) __popcll(hm);
+            if (!have && hm) {
+                const int src = __builtin_amdgcn_readfirstlane((int) __ffsll((long long) hm) - 1);
+                const long long bx = __double_as_longlong(dx[t]), by = __double_as_longlong(dy[t]);
+                const unsigned int xl = (unsigned int) __builtin_amdgcn_readlane((int) (unsigned int) bx, src), xh = (unsigned int) __builtin_amdgcn_readlane((int) (bx >> 32), src);
+                const unsigned int yl = (unsigned int) __builtin_amdgcn_readlane((int) (unsigned int) by, src), yh = (unsigned int) __builtin_amdgcn_readlane((int) (by >> 32), src);
+                px = __longlong_as_double((long long) (((unsigned long long) xh << 32) | xl));
+                py = __longlong_as_double((long long) (((unsigned long long) yh << 32) | yl));
+                have = true;
+            }
+        }
+        double *o = sh[s][wave];
+        if (!have) {  // (uniform) nobody in this wave holds both
+            if (lane < kMapFields) o[lane] = 0.0;
+            continue;
+        }
+        double a[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};  // sum w | w ex, w ey | w ex^2, w ex ey, w ey^2 | w (Pf_a + Pf_b); e = d - pivot
+#pragma unroll
+        for (int t = 0; t < kMapT; t++) {
+            if (both[t]) {
+                const double ex = dx[t] - px, ey = dy[t] - py, wt = w[t];
+                a[0] += wt;
+                a[1] += wt * ex;
+                a[2] += wt * ey;
+                a[3] += wt * ex * ex;
+                a[4] += wt * ex * ey;
+                a[5] += wt * ey * ey;
+                a[6] += wt * ((double) la[t].z + (double) ma[t].z);
+                a[7] += wt * ((double) la[t].w + (double) ma[t].w);
+                a[8] += wt * ((double) lb[t] + (double) mb2[t]);
+            }
+        }
+#pragma unroll
+        for (int q = 0; q < 9; q++) a[q] = wave_sum_d(a[q]);
+        if (lane == 0) {
+            const double W = a[0];
+            const bool any = W != 0.0;  // (W == 0: joint holders without weight are counted, and carry nothing else)
+            const double mx = any ? a[1] / W : 0.0, my = any ? a[2] / W : 0.0;
+            o[kMapW] = W;
+            o[kMapMx] = px + mx;
+            o[kMapMy] = py + my;
+            o[kMapXX] = a[3] - a[1] * mx;
+            o[kMapXY] = a[4] - a[1] * my;
+            o[kMapYY] = a[5] - a[2] * my;
+            o[kMapP00] = a[6];
+            o[kMapP10] = a[7];
+            o[kMapP11] = a[8];
+            o[kMapCnt] = (double) cnt;
+        }
+    }
+    __syncthreads();
+    if ((int) threadIdx.x < sn) {  // the tile's waves in ascending order, as map_summary_kernel merges them
+        const int s = threadIdx.x;
+        MapPart m;
+        for (int q = 0; q < kMapFields; q++) m.v[q] = sh[s][0][q];
+        for (int v = 1; v < kWaves; v++) {
+            MapPart b;
+            for (int q = 0; q < kMapFields; q++) b.v[q] = sh[s][v][q];
+            map_merge(m, b);
+        }
+        double *p = A.part + (size_t) blockIdx.x * kMapFields * (size_t) A.count + (size_t) (s0 + s);
+        for (int q = 0; q < kMapFields; q++) p[(size_t) q * A.count] = m.v[q];
+    }
+}
+static void launch_map_pairs(hipStream_t st, const Buffers &B, const WeightScratch &ws, const MapPairsArgs &P) {
+    hipLaunchKernelGGL(map_pairs_kernel, dim3(P.S.tiles, (P.S.count + kMapSlots - 1) / kMapSlots), dim3(kBlock), 0, st, B, ws, P);
+}
+
 // ---- slamgpu_path_* (kernels.h: PathRing) --------------------------------------------------------------------------------------
 // origin'[k] = origin[ancestor of k] if the last update resampled (Ctrl.resampled and keep[keep_slot], as slamgpu_ancestors reads
 // them), a copy otherwise: the host flips its buffers either way.  src null: the identity.
@@ -5638,7 +5807,7 @@ static const KernelTable kTable = {launch_update, launch_update_any, launch_upda
                                    launch_associate_grid, launch_jacobians_multi, launch_pp_census, launch_pp_resolve, launch_pp_holders,
                                    launch_pp_resample, launch_pp_gather, launch_pp_book,
                                    launch_lists_box, launch_lists_geom, launch_lists_build, launch_lists_walk, launch_excl_radii,
-                                   launch_map_summary, launch_map_finish, launch_pp_missed,
+                                   launch_map_summary, launch_map_finish, launch_map_pairs, launch_pp_missed,
                                    launch_path_compose, launch_path_record, launch_path_trace, launch_path_seed, launch_path_push, launch_path_finish,
                                    launch_pp_mutex};
 

@@ -4873,6 +4873,72 @@ int slamgpu_map_summary(slamgpu_ctx *c, int32_t first_slot, int32_t count, doubl
     return 0;
 }
 
+int slamgpu_map_pairs(slamgpu_ctx *c, const int32_t *pairs, int32_t count, double *out, int32_t *both) {
+    if (int rc = check_ctx(c)) return rc;
+    if (c->dist || c->cfg.n_particles_global != c->cfg.n_particles)
+        return fail(SLAMGPU_ERR_INVALID, "slamgpu_map_pairs: single contexts only");
+    if (count < 0) return fail(SLAMGPU_ERR_INVALID, "slamgpu_map_pairs: count %d", count);
+    if (count == 0) return 0;
+    if (!pairs || !out) return fail(SLAMGPU_ERR_INVALID, "slamgpu_map_pairs: null %s", pairs ? "output" : "pairs");
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    if (int rc = book_pull(c)) return rc;  // (device-driven steps: the number of slots lives on the device)
+    for (int64_t k = 0; k < 2 * (int64_t) count; k++)
+        if (pairs[k] < 0 || pairs[k] >= c->nf)
+            return fail(SLAMGPU_ERR_INVALID, "slamgpu_map_pairs: pair %lld names slot %d outside [0, %d)", (long long) (k / 2), pairs[k], c->nf);
+    // the particle set and the weights of slamgpu_map_summary, reached the same way
+    if (int rc = flush_predict(c)) return rc;
+    if (int rc = flush_stages(c)) return rc;
+    if (int rc = sync_tables(c)) return rc;
+    const int tiles = (c->B.n + kMapTile - 1) / kMapTile;
+    // the pairs go through the summary's table of partials, cut the same way (a pair's sums do not depend on the cut)
+    constexpr size_t kMapScratch = (size_t) 16 << 20;
+    const size_t per_pair = sizeof(double) * kMapFields * (size_t) tiles;
+    int fit = (int) std::max<size_t>(kMapSlots, kMapScratch / per_pair / kMapSlots * kMapSlots);
+    if (const char *e = getenv("SLAMGPU_MAP_CHUNK")) fit = std::max(kMapSlots, atoi(e) / kMapSlots * kMapSlots);
+    const int chunk = (int) std::min<int64_t>(fit, ((int64_t) count + kMapSlots - 1) / kMapSlots * kMapSlots);
+    // device staging: [out count][wpart tiles][part chunk][both count][pairs count]
+    const size_t M = (size_t) count;
+    const size_t o_out = 0, o_w = o_out + sizeof(double) * kMapStride * M, o_part = o_w + sizeof(double) * 2 * (size_t) tiles,
+                 o_both = o_part + per_pair * (size_t) chunk, o_pairs = o_both + sizeof(int32_t) * M, total = o_pairs + sizeof(int32_t) * 2 * M;
+    if (total > c->msum_bytes) {
+        if (c->msum_dev) (void) hipFree(c->msum_dev);
+        c->msum_dev = nullptr;
+        c->msum_bytes = 0;
+        hipError_t e = hipMalloc((void **) &c->msum_dev, total);
+        if (e != hipSuccess) return fail(SLAMGPU_ERR_ALLOC, "hipMalloc(%zu): %s", total, hipGetErrorString(e));
+        c->msum_bytes = total;
+    }
+    HIP_TRY(hipMemcpyAsync(c->msum_dev + o_pairs, pairs, sizeof(int32_t) * 2 * M, hipMemcpyHostToDevice, c->stream));
+    c->B.slot = c->slot;
+    for (int at = 0; at < count; at += chunk) {
+        MapPairsArgs P{};
+        MapSummaryArgs &A = P.S;
+        A.first_slot = 0;
+        A.count = std::min(chunk, count - at);
+        A.tiles = tiles;
+        A.logw = c->cfg.log_weights;
+        A.part = reinterpret_cast<double *>(c->msum_dev + o_part);
+        A.wpart = reinterpret_cast<double *>(c->msum_dev + o_w);
+        A.out = reinterpret_cast<double *>(c->msum_dev + o_out) + (size_t) kMapStride * at;
+        A.holders = reinterpret_cast<int32_t *>(c->msum_dev + o_both) + at;
+        P.pairs = reinterpret_cast<const int32_t *>(c->msum_dev + o_pairs) + (size_t) 2 * at;
+        {
+            Timed t(c, "map_pairs");
+            c->k->map_pairs(c->stream, c->B, c->ws, P);
+        }
+        HIP_TRY(hipGetLastError());
+        {
+            Timed t(c, "map_finish");
+            c->k->map_finish(c->stream, A);
+        }
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipMemcpyAsync(out, c->msum_dev + o_out, sizeof(double) * kMapStride * M, hipMemcpyDeviceToHost, c->stream));
+    if (both) HIP_TRY(hipMemcpyAsync(both, c->msum_dev + o_both, sizeof(int32_t) * M, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
 int slamgpu_path_enable(slamgpu_ctx *c, int32_t capacity) {
     if (int rc = check_ctx(c)) return rc;
     if (c->dist || c->cfg.n_particles_global != c->cfg.n_particles) return fail(SLAMGPU_ERR_INVALID, "slamgpu_path_enable: single contexts only");

@@ -15,7 +15,9 @@ DECLARED_SYMBOLS = [
     "slamhost_synthetic_landmarks", "slamhost_write_map", "slamhost_ekf_create", "slamhost_ekf_destroy", "slamhost_ekf_step",
     "slamhost_ekf_state", "slamhost_plot_open", "slamhost_plot_close", "slamhost_plot_xy", "slamhost_plot_matrix",
     "slamhost_plot_doubles", "slamhost_plot_car_size", "slamhost_plot_u32", "slamhost_plot_cmd", "slamhost_plot_name",
+    "slamhost_map_candidates", "slamhost_map_merge",
 ]
+MAP_STRIDE = 9  # SLAMGPU_MAP_STRIDE
 
 
 class HostConf(C.Structure):
@@ -80,6 +82,10 @@ def load_library():
         L.slamhost_plot_u32.argtypes = [C.c_void_p, C.c_char_p, C.c_uint32]
         L.slamhost_plot_cmd.argtypes = [C.c_void_p, C.c_char_p]
         L.slamhost_plot_name.argtypes = [C.c_void_p, C.c_char_p]
+        L.slamhost_map_candidates.restype = C.c_int64
+        L.slamhost_map_candidates.argtypes = [C.c_void_p, C.c_int32, C.c_double, C.c_void_p, C.c_int64]
+        L.slamhost_map_merge.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_double, C.c_double, C.c_void_p, C.c_void_p,
+                                         C.POINTER(C.c_int32)]
         _lib = L
     return _lib
 
@@ -112,6 +118,46 @@ def write_map(path, lm, wp):
     rc = load_library().slamhost_write_map(path.encode(), _p(lm), lm.shape[1], _p(wp), wp.shape[1])
     if rc != 0:
         raise RuntimeError("slamhost_write_map failed for %s" % path)
+
+
+def _table9(t):
+    """[rows, 9] float64 in SLAMGPU_MAP_STRIDE layout, from such an array or from the dict of SlamGpu.map_summary / map_pairs"""
+    if isinstance(t, dict):
+        t = np.concatenate([np.asarray(t["share"], np.float64).reshape(-1, 1), np.asarray(t["mean"], np.float64).reshape(-1, 2),
+                            np.asarray(t["scatter"], np.float64).reshape(-1, 3), np.asarray(t["pf"], np.float64).reshape(-1, 3)], axis=1)
+    return np.ascontiguousarray(t, np.float64).reshape(-1, MAP_STRIDE)
+
+
+def map_candidates(summary, radius):
+    """slamhost_map_candidates: pairs[count, 2] (int32), every a < b with both shares > 0 and the means closer than radius, ascending"""
+    L = load_library()
+    t = _table9(summary)
+    n = L.slamhost_map_candidates(_p(t), len(t), float(radius), None, 0)
+    if n < 0:
+        raise ValueError("slamhost_map_candidates: bad arguments")
+    pairs = np.zeros((n, 2), np.int32)
+    if n and L.slamhost_map_candidates(_p(t), len(t), float(radius), _p(pairs), n) != n:
+        raise RuntimeError("slamhost_map_candidates: the count changed between two calls")
+    return pairs
+
+
+def map_merge(summary, pairs, joint, radius=1.0, cohold=0.1):
+    """slamhost_map_merge: slots that lie within radius of each other and are (almost) never held together -- joint share <= cohold *
+    the smaller share -- become one landmark.  summary / joint: [rows, 9] arrays or the dicts of SlamGpu.map_summary / map_pairs for
+    `pairs`.  Returns cluster[slots] (-1: share 0) and the merged landmarks as merged[n, 9] and share, mean, scatter, pf of it"""
+    L = load_library()
+    t = _table9(summary)
+    pairs = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+    j = _table9(joint)
+    if len(j) != len(pairs):
+        raise ValueError("map_merge: %d pairs, %d joint rows" % (len(pairs), len(j)))
+    cluster = np.zeros(len(t), np.int32)
+    merged = np.zeros((len(t), MAP_STRIDE), np.float64)
+    n = C.c_int32()
+    if L.slamhost_map_merge(_p(t), len(t), _p(pairs), _p(j), len(pairs), float(radius), float(cohold), _p(cluster), _p(merged), C.byref(n)) != 0:
+        raise ValueError("slamhost_map_merge: bad arguments")
+    m = merged[:n.value].copy()
+    return dict(cluster=cluster, merged=m, share=m[:, 0].copy(), mean=m[:, 1:3].copy(), scatter=m[:, 3:6].copy(), pf=m[:, 6:9].copy())
 
 
 class HostSim:

@@ -14,7 +14,11 @@ warm-up, the median of 7.  Algorithmic bytes: 24 B per (particle, slot) + the we
 partial slots' holders through the same genealogy), 220 steps, a summary before each of the last 120 -- for a run under
 rocprofv3 --kernel-trace --stats; the slots the census visited are written to JSON.
 --summarize STATS_CSV JSON: time per (particle, slot) visited of pp_holders_kernel and of map_summary_kernel from that run.
---tape: config 5's whole tape (2 172 steps, run_particle through the lists, exclusion rule with the spacing cap f = 0.5, slot capacity
+--pairs: the joint shares (slamgpu_map_pairs: map_pairs_kernel + map_finish_kernel) on the same two states: on (a) all pairs a < b of the
+slots in use, on (b) all pairs of slots whose posterior means lie within 1 m (slamhost_map_candidates); kernel time and call time as above,
+beside slamgpu_map_summary on the same state in the same process per (particle, record) read, and algorithmic bytes (2 x (4 + 20) B per
+particle and pair: two genealogy entries, two records) over the kernel time; then what slamhost_map_merge makes of them (radius 1 m,
+cohold 0.1).  --tape: config 5's whole tape (2 172 steps, run_particle through the lists, exclusion rule with the spacing cap f = 0.5, slot capacity
 15 000, log-weights: tools/particle_excl_spacing_probe.py's arm), then the posterior map beside the best particle's."""
 import argparse
 import csv
@@ -68,6 +72,79 @@ def describe(name, n, ms, k, w):
             "  whole call (launches, copies of the result, sync) %.4f ms  (calls %s)" % (wm, " ".join("%.4f" % x for x in w)),
             "  per (particle, slot): %.2f ps;  algorithmic bytes %.3f GB -> %.2f TB/s = %.0f %% of 8 TB/s (copy rate of this part: %.1f-%.1f TB/s)" %
             (1e9 * km / (n * slots), b / 1e9, b / (km * 1e-3) / 1e12, 100.0 * b / (km * 1e-3) / PEAK, COPY[0] / 1e12, COPY[1] / 1e12), ""]
+
+
+def timed_pairs(s, pairs, calls=7, warm=2):
+    """(kernel ms, whole-call ms, answer) of `calls` slamgpu_map_pairs over `pairs` after `warm` of warm-up"""
+    s.profile(True)
+    for _ in range(warm):
+        s.map_pairs(pairs)
+    k, w = [], []
+    for _ in range(calls):
+        a = s.kernel_time("map_pairs")[0] + s.kernel_time("map_finish")[0]
+        s.timer_start()
+        mp = s.map_pairs(pairs)
+        w.append(s.timer_stop())
+        k.append(s.kernel_time("map_pairs")[0] + s.kernel_time("map_finish")[0] - a)
+    s.profile(False)
+    return k, w, mp
+
+
+def describe_pairs(name, n, s, pairs, how):
+    from slam_amd import host
+    ks, ws, ms = timed_summaries(s)
+    slots = len(ms["share"])
+    lines = [name]
+    if len(pairs) == 0:
+        return lines + ["  %s: none" % how, ""]
+    k, w, mp = timed_pairs(s, pairs)
+    km, wm, ksm = statistics.median(k), statistics.median(w), statistics.median(ks)
+    b = 2.0 * (4.0 + 20.0) * n * len(pairs)
+    mg = host.map_merge(ms, pairs, mp, 1.0, 0.1)
+    sizes = np.bincount(mg["cluster"][mg["cluster"] >= 0], minlength=len(mg["merged"]))
+    lines += ["  %d slots, %d pairs (%s); joint share: %d pairs 0, %d in (0, 0.1 min(s_a, s_b)], %d above; largest %.6f" %
+              (slots, len(pairs), how, int((mp["share"] == 0).sum()),
+               int(((mp["share"] > 0) & (mp["share"] <= 0.1 * np.minimum(ms["share"][pairs[:, 0]], ms["share"][pairs[:, 1]]))).sum()),
+               int((mp["share"] > 0.1 * np.minimum(ms["share"][pairs[:, 0]], ms["share"][pairs[:, 1]])).sum()), float(np.nanmax(mp["share"]))),
+              "  kernels (map_pairs + map_finish, all chunks)     %.4f ms  (calls %s)" % (km, " ".join("%.4f" % x for x in k)),
+              "  whole call (copy of the list, launches, copies of the result, sync) %.4f ms  (calls %s)" % (wm, " ".join("%.4f" % x for x in w)),
+              "  per (particle, record) read: %.2f ps;  slamgpu_map_summary of the %d slots on the same state, same process: kernels %.4f ms = %.2f ps per "
+              "(particle, record) read" % (1e9 * km / (2.0 * n * len(pairs)), slots, ksm, 1e9 * ksm / (n * slots)),
+              "  algorithmic bytes %.3f GB -> %.2f TB/s (copy rate of this part: %.1f-%.1f TB/s)" % (b / 1e9, b / (km * 1e-3) / 1e12, COPY[0] / 1e12, COPY[1] / 1e12),
+              "  slamhost_map_merge (radius 1 m, cohold 0.1): %d slots with share > 0 -> %d landmarks, %d clusters of more than one slot (largest %d slots); "
+              "share >= 0.5: %d slots -> %d landmarks" % (int((ms["share"] > 0).sum()), len(mg["merged"]), int((sizes > 1).sum()), int(sizes.max()) if len(sizes) else 0,
+                                                          int((ms["share"] >= 0.5).sum()), int((mg["share"] >= 0.5).sum())), ""]
+    return lines
+
+
+def pairs_probe(out):
+    from slam_amd import host
+    lines = ["map_summary_probe --pairs: slamgpu_map_pairs, 10^5 particles, fast build; 2 calls of warm-up, median of 7", ""]
+    web = course(os.path.join(ROOT, "data", "example_webmap.mat"), 100)
+    s = slam_amd.SlamGpu(N, web["nlm"], method=2, n_effective=int(0.75 * N), rng_mode=slam_amd.RNG_PHILOX, seed=5, device_observe=True,
+                         math_mode=slam_amd.MATH_FAST)
+    s.set_map(web["lm"])
+    s.run_observe(web["ctl"], web["Q"], web["dt"], web["xt"], web["max_range"], web["R"], noise=2)
+    s.history_fetch()
+    nf = s.nf()
+    pairs = np.array([(a, b) for a in range(nf) for b in range(a + 1, nf)], np.int32).reshape(-1, 2)
+    lines += describe_pairs("(a) example_webmap, known association, compact genealogy, after 100 observation steps", N, s, pairs, "all a < b of the slots in use")
+    s.close()
+    with tempfile.TemporaryDirectory() as d:
+        c5 = course(config5_map(d), 200)
+    s = context(c5, N, 10000)
+    device_steps(s, c5, 0, 200, dict(OPT, mode=slam_amd.capi.ASSOC_LISTS, excl=EXCL_OFF), 50)
+    s.history_fetch()
+    s.particle_report_fetch()
+    pairs = host.map_candidates(s.map_summary(), 1.0)
+    lines += describe_pairs("(b) config 5: synthetic 10^4-landmark map, per-particle association through the lists (run_particle), plain rows, log-weights, "
+                            "after 200 steps", N, s, pairs, "all a < b with the posterior means within 1 m")
+    s.close()
+    text = "\n".join(lines)
+    print(text)
+    if out:
+        with open(out, "w") as f:
+            f.write(text)
 
 
 def trace(path):
@@ -167,7 +244,13 @@ def main():
     ap.add_argument("--trace", default=None)
     ap.add_argument("--summarize", nargs=2, default=None)
     ap.add_argument("--tape", action="store_true")
+    ap.add_argument("--pairs", action="store_true")
     a = ap.parse_args()
+    if a.pairs:
+        if slam_amd.device_count() < 1:
+            raise RuntimeError("map_summary_probe needs a GPU")
+        pairs_probe(a.out)
+        return
     if a.trace:
         trace(a.trace)
         return
