@@ -729,6 +729,7 @@ int slamgpu_algorithmic_bytes(slamgpu_ctx *ctx, double *update_bytes, double *pr
  *                               measured multi-GPU run (no 8-GPU node has been available to this build in six rounds).
  *   - slamgpu_dev_*             raw device buffers for the callers of the exchange path
  *   - slamgpu_debug_stamps      instrumented build only
+ *   - slamgpu_update_special*   which instantiation of the update kernel a launch takes (tests of the selection; no device needed)
  * ================================================================================================================= */
 #ifdef SLAMGPU_EXPERIMENTAL
 
@@ -825,6 +826,19 @@ int slamgpu_debug_stamps(slamgpu_ctx *ctx, uint64_t *out, int32_t max_blocks, in
 /* Diagnostic of slamgpu_set_particle_miss: (particle, slot) records its kernel has looked at since the context was created -- with
  * SLAMGPU_ASSOC_LISTS a workgroup passes over every slot whose box is out of reach of all of its particles.  Synchronises. */
 int slamgpu_particle_miss_visited(slamgpu_ctx *ctx, int64_t *records);
+
+/* ---- update launch: specialised instantiations ----------------------------------------------------------------
+ * The update kernel of FastSLAM 2 on single compact contexts exists with some sets of launch-wide mode flags compiled in.
+ * mode_bits: bit 0 inline plan, 1 prefix from the scan kernel, 2 log-weights, 3 in-launch observation front end, 4 Philox draws,
+ * 5 queued predicts composed, 6 heading observed, 7 per-particle control noise, 8 resampling enabled (SLAMGPU_UPDATE_MODE_BITS of
+ * them).  slamgpu_update_special returns the number (> 0) of the instantiation a launch with these values takes, or 0: the general
+ * one (always when no_special is set: contexts created under SLAMGPU_NO_SPECIAL=1).  slamgpu_update_special_modes returns the
+ * mode_bits instantiation `spec` has compiled in, or -1 when there is no such instantiation.  slamgpu_update_special_launches: how
+ * many of the context's update launches so far took a specialised instantiation (host bookkeeping; does not synchronise). */
+#define SLAMGPU_UPDATE_MODE_BITS 9
+int slamgpu_update_special(int32_t method, int32_t arrivals, int32_t big, int32_t per_particle, int32_t no_special, uint32_t mode_bits);
+int slamgpu_update_special_modes(int32_t spec);
+int slamgpu_update_special_launches(slamgpu_ctx *ctx, int64_t *count);
 
 #endif /* SLAMGPU_EXPERIMENTAL */
 

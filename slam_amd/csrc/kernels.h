@@ -68,6 +68,36 @@ inline bool update_wide_off() {  // (diagnostic: SLAMGPU_NO_WIDE=1 keeps update_
 inline bool update_is_wide(int method, int arrivals, bool big, int nblocks) {
     return method == 1 && arrivals == 0 && !big && nblocks > kWideBlocks && !update_wide_off();
 }
+// Mode sets of update_kernel (kernels.hip).  Every member is a launch-wide value the host holds when it fills the launch's arguments
+// and the step text (update_step.inl) tests.  The general instantiation (SPEC = 0) tests them at run time; a specialised one
+// (SPEC = s > 0) has kUpdateSpecs[s] compiled in, and runs only launches whose values equal it member for member (update_special;
+// tests/test_special_select_cpu.py).  Specialised: FastSLAM 2, single context, compact layout, and
+//   1  linear weights, host-made packet, Philox, inline plan, block-local scan, the queued predicts composed (bench configs 3 and 4)
+//   2  the same with the heading-observed predicts (config 6)
+// for both builds (the strict build never reads comp_valid: its two instantiations differ in the predicts' heading branch alone).
+struct UpdateModes {
+    bool plan, scan_global, logw, front, philox, comp_valid, use_heading, add_noise, do_resample;
+};
+constexpr int kUpdateModeBits = 9;
+constexpr UpdateModes kUpdateSpecs[] = {
+    {false, false, false, false, false, false, false, false, false},  // (0: general -- nothing compiled in, the entry is never read)
+    {true, false, false, false, true, true, false, false, true},
+    {true, false, false, false, true, false, true, false, true},
+};
+constexpr int kUpdateSpecCount = (int) (sizeof(kUpdateSpecs) / sizeof(kUpdateSpecs[0]));
+constexpr unsigned update_mode_bits(const UpdateModes &m) {
+    return (m.plan ? 1u : 0u) | (m.scan_global ? 2u : 0u) | (m.logw ? 4u : 0u) | (m.front ? 8u : 0u) | (m.philox ? 16u : 0u) | (m.comp_valid ? 32u : 0u) |
+           (m.use_heading ? 64u : 0u) | (m.add_noise ? 128u : 0u) | (m.do_resample ? 256u : 0u);
+}
+// the instantiation a launch takes: s > 0 when its kernel is update_kernel<2, 0, false> and its mode set IS kUpdateSpecs[s]; else 0
+// (off: the context was created under SLAMGPU_NO_SPECIAL=1 -- diagnostic / tests: the general instantiation everywhere; the launcher
+// gets it beside the arguments, KernelTable::update, and returns what it took: slamgpu_update_special_launches)
+inline int update_special(int method, int arrivals, bool big, bool pp, bool wide, bool off, unsigned mode_bits) {
+    if (off || method != 2 || arrivals != 0 || big || pp || wide) return 0;
+    for (int s = 1; s < kUpdateSpecCount; s++)
+        if (update_mode_bits(kUpdateSpecs[s]) == mode_bits) return s;
+    return 0;
+}
 // status bits of an update's resampling stage (slamgpu.h: SLAMGPU_STATUS_*)
 constexpr int kStatusBadPacket = 2;   // the kernel did not find its packet where the kernel-argument layout says (never seen)
 constexpr int kStatusCapacity = 4;    // device front end: more new landmarks than the context has room for (the surplus was dropped)
@@ -804,12 +834,15 @@ struct AssocRule {
 struct KernelTable {
     // the step: [resampling stage of the previous update, inline] + [gather] + [fused predicts] + per-particle observation
     // update + in-block weight prefix / totals  (+ helper blocks: genealogy copy, Ctrl words, estimate reduction)
-    void (*update)(hipStream_t, const Buffers &, const PredictArgs &, const UpdateArgs &, const RngArgs &,
-                   const WeightScratch &);
+    // no_special: the general instantiation whatever the launch's mode set (SLAMGPU_NO_SPECIAL=1).  Returns the instantiation the
+    // launch took (update_special: 0 general, s > 0 kUpdateSpecs[s])
+    int (*update)(hipStream_t, const Buffers &, const PredictArgs &, const UpdateArgs &, const RngArgs &,
+                  const WeightScratch &, bool no_special);
     // the same step with a per-particle association (PerParticle: update_kernel<.., PP = true>; single contexts on plain rows); driven
     // by the device when PerParticle::obs_dev is set (update_kernel<.., PPD = true>; no observation: nothing)
-    void (*update_particle)(hipStream_t, const Buffers &, const PredictArgs &, const UpdateArgs &, const RngArgs &, const WeightScratch &,
-                            const PerParticle &);
+    // (no specialised instantiation: always 0)
+    int (*update_particle)(hipStream_t, const Buffers &, const PredictArgs &, const UpdateArgs &, const RngArgs &, const WeightScratch &,
+                           const PerParticle &, bool no_special);
     // K steps of a compact single context in ONE launch (PersistArgs): U = what every iteration shares (front end on: the map, R)
     void (*update_persist)(hipStream_t, const Buffers &, const PredictArgs &, const UpdateArgs &, const RngArgs &, const WeightScratch &);
     // the resampling stage as a launch of its own (on demand): Neff + decision; normalise, or the ancestors of a

@@ -52,7 +52,9 @@ SLAM_DEV void nt_store(float *p, float v) { __builtin_nontemporal_store(v, p); }
 // [+ observeHeading -> josephUpdate (fastslam2.cpp:113-125, core.cpp:294-317)] or
 // FastSLAM1::predictState (fastslam1.cpp:37-54).  P is the full 3x3 (the reference's Pv is not kept
 // symmetric by its own float arithmetic; only the stored form is packed).
+// NOISE, HEADING: 0 / 1: A.add_noise / A.use_heading as the caller knows them at compile time (update_kernel_special); -1: read from A.
 // ---------------------------------------------------------------------------------------------------
+template <int NOISE = -1, int HEADING = -1>
 SLAM_DEV void predict_steps(float &x, float &y, float &th, float P[9], const PredictArgs &A, const RngArgs &rng, int i,
                             size_t S) {
     const bool fs2 = A.method == 2;
@@ -99,7 +101,7 @@ SLAM_DEV void predict_steps(float &x, float &y, float &th, float P[9], const Pre
             P[7] = N9[7] + (u20 * gu10 + u21 * gu11);
             P[8] = N9[8] + (u20 * gu20 + u21 * gu21);
         }
-        if (A.add_noise) {
+        if (NOISE < 0 ? A.add_noise != 0 : NOISE != 0) {
             // multivariateGauss((V,G), Q, 1) (core.cpp:452): L = chol(Q), (V,G) = L*g + (V,G)
             float g0, g1, g2;
             if (rng.mode == 0) {
@@ -116,14 +118,14 @@ SLAM_DEV void predict_steps(float &x, float &y, float &th, float P[9], const Pre
             G = ng;
             sincosf(G + th, &sn, &cs);
         }
-        const float sgw = A.add_noise ? sinf(G / wb) : A.steps[s].sinGw;
+        const float sgw = (NOISE < 0 ? A.add_noise != 0 : NOISE != 0) ? sinf(G / wb) : A.steps[s].sinGw;
         const float nx = x + V * dt * cs;
         const float ny = y + V * dt * sn;
         const float nth = trig_offset(th + V * dt * sgw);  // sin(G/wheelBase): upstream quirk (:103)
         x = nx;
         y = ny;
         th = nth;
-        if (A.use_heading) {
+        if (HEADING < 0 ? A.use_heading != 0 : HEADING != 0) {
             // josephUpdate with H = [0 0 1] (core.cpp:294-317)
             const float v = trig_offset(A.steps[s].phi_true - th);
             const float R = (float) ((double) A.sigma_phi * (double) A.sigma_phi);
@@ -1365,10 +1367,35 @@ __global__ void __launch_bounds__(kBlock) update_kernel(const float *__restrict_
         rng.step = *ppa.step_dev;
     }
     constexpr bool PERSIST = false, PP = PPT;
+    constexpr int SPEC = 0;
     const PersistStep *const qe = nullptr;
     StepCarry carry;  // (unused by a per-step launch)
 #define STEP_WPAR ws.wpar
 #define STEP_PLAN (U.plan_inline != 0)
+#define STEP_FRONT U.front
+#include "update_step.inl"
+#undef STEP_WPAR
+#undef STEP_PLAN
+#undef STEP_FRONT
+}
+
+// update_kernel<2, 0, false> with a mode set compiled in (kernels.h: UpdateModes): the launch's values ARE kUpdateSpecs[SPEC]
+// (update_special, asked by launch_update_any), so the step text's tests of them fold, and what only the untaken branches read -- the
+// tape, the front end's state, the log-weight arithmetic, Ctrl.pend -- is neither loaded nor kept in scalar registers.  Same leading
+// arguments and argument layout as update_kernel, same operations on the same values: bit-identical (tests/test_gpu_special.py).
+// (A kernel of its own, not a further template parameter of update_kernel: the general instantiations keep their names.)
+template <int SPEC>
+__global__ void __launch_bounds__(kBlock) update_kernel_special(const float *__restrict__ h_tot, Ctrl *h_ctrl, const FrontState *h_front, int h_nb,
+                                                                 int h_slot, int h_grid, int h_flags, Buffers B, PredictArgs PA, UpdateArgs U,
+                                                                 RngArgs rng, WeightScratch ws) {
+    static_assert(SPEC > 0 && SPEC < kUpdateSpecCount, "kernels.h: kUpdateSpecs");
+    constexpr int METHOD = 2, MODE = 0;
+    constexpr bool BIG = false, PERSIST = false, PP = false;
+    [[maybe_unused]] const PerParticle ppa{};
+    const PersistStep *const qe = nullptr;
+    StepCarry carry;  // (unused by a per-step launch)
+#define STEP_WPAR ws.wpar
+#define STEP_PLAN kUpdateSpecs[SPEC].plan
 #define STEP_FRONT U.front
 #include "update_step.inl"
 #undef STEP_WPAR
@@ -1386,7 +1413,7 @@ template <int METHOD>
 __global__ void __launch_bounds__(kBlock, 3) update_kernel_wide(const float *__restrict__ h_tot, Ctrl *h_ctrl, const FrontState *h_front, int h_nb,
                                                                  int h_slot, int h_grid, int h_flags, Buffers B, PredictArgs PA, UpdateArgs U,
                                                                  RngArgs rng, WeightScratch ws) {
-    constexpr int MODE = 0;
+    constexpr int MODE = 0, SPEC = 0;
     constexpr bool BIG = false, PERSIST = false, PP = false;
     [[maybe_unused]] const PerParticle ppa{};
     const PersistStep *const qe = nullptr;
@@ -1407,7 +1434,7 @@ SLAM_DEV void persist_step(const float *__restrict__ h_tot, Ctrl *h_ctrl, const 
                            StepCarry &carry) {
     constexpr bool PERSIST = true, BIG = false, PP = false;
     [[maybe_unused]] const PerParticle ppa{};
-    constexpr int MODE = 0;
+    constexpr int MODE = 0, SPEC = 0;
     const PredictArgs &PA = qe->PA;
     const int wpar = __builtin_amdgcn_readfirstlane(qe->wpar);
     const bool plan_inline = __builtin_amdgcn_readfirstlane(qe->plan_inline) != 0;
@@ -4197,8 +4224,8 @@ static void launch_shard_finish(hipStream_t st, const Buffers &B, const WeightSc
     hipLaunchKernelGGL(shard_finalize_kernel, dim3(B.ncap / kBlock), dim3(kBlock), 0, st, B, ws, W, Q, neff, resampled);
 }
 
-static void launch_update_any(hipStream_t st, const Buffers &B, const PredictArgs &PA, const UpdateArgs &U,
-                              const RngArgs &rng, const WeightScratch &ws, const PerParticle &ppa) {
+static int launch_update_any(hipStream_t st, const Buffers &B, const PredictArgs &PA, const UpdateArgs &U,
+                             const RngArgs &rng, const WeightScratch &ws, const PerParticle &ppa, bool no_special) {
     // compute blocks first (they are the long pole), then -- single-context pipeline only -- the copy blocks of a
     // pending lazy gather (they exit at once when nothing is pending: the host cannot know) and one helper block
     int grid = B.ncap / kBlock;
@@ -4218,7 +4245,7 @@ static void launch_update_any(hipStream_t st, const Buffers &B, const PredictArg
     if (update_is_wide(U.method, U.arrivals, U.big != nullptr, ws.nblocks)) {  // (FastSLAM 1, single context, compact layout, more tiles than two rounds of CUs)
         hipLaunchKernelGGL((update_kernel_wide<1>), dim3(grid), dim3(kBlock), lds, st, h_tot, B.ctrl, U.front.state_in, ws.nblocks, B.slot, grid,
                            h_flags, B, PA, U, rng, ws);
-        return;
+        return 0;
     }
     // per-particle association (slamgpu.cpp: do_update_particle guarantees a single context on plain rows: MODE 0, BIG; obs_dev: driven
     // by the device)
@@ -4230,6 +4257,21 @@ static void launch_update_any(hipStream_t st, const Buffers &B, const PredictArg
         pq.z_lds = pq.nz <= kPpLdsObs ? 1 : 0;
         lds += (size_t) kBigChunk * kBlock * sizeof(int32_t) + (pq.z_lds ? sizeof(float) * 2 * (size_t) pq.nz : 0);
     }
+    // the launch's mode set, from the values that have just gone into its arguments: a specialised instantiation when one has exactly
+    // this set compiled in (kernels.h: update_special), else -- and always under SLAMGPU_NO_SPECIAL=1 -- the general one
+    const UpdateModes modes = {U.plan_inline != 0, U.scan_global != 0, U.logw != 0, U.front.on != 0, rng.mode != 0, PA.comp.valid != 0,
+                               PA.use_heading != 0, PA.add_noise != 0, U.do_resample != 0};
+    const int spec = update_special(U.method, U.arrivals, U.big != nullptr, pp, false, no_special, update_mode_bits(modes));
+    if (spec != 0) {
+        dispatch<kUpdateSpecCount>(
+            [&](auto sp) {
+                if constexpr (sp != 0)
+                    hipLaunchKernelGGL((update_kernel_special<sp>), dim3(grid), dim3(kBlock), lds, st, h_tot, B.ctrl, U.front.state_in, ws.nblocks, B.slot,
+                                       grid, h_flags, B, PA, U, rng, ws);
+            },
+            spec);
+        return spec;
+    }
     dispatch<2, 3, 2, 2, 2>(
         [&](auto fs2, auto mode, auto big, auto ppt, auto ppd) {
             if constexpr ((!ppt || (big && mode == 0)) && (!ppd || ppt))
@@ -4237,10 +4279,12 @@ static void launch_update_any(hipStream_t st, const Buffers &B, const PredictArg
                                    ws.nblocks, B.slot, grid, h_flags, B, PA, U, rng, ws, pq);
         },
         U.method == 2, pp ? 0 : U.arrivals, pp || U.big != nullptr, pp, pp && ppa.obs_dev != nullptr);
+    return 0;
 }
 
-static void launch_update(hipStream_t st, const Buffers &B, const PredictArgs &PA, const UpdateArgs &U, const RngArgs &rng, const WeightScratch &ws) {
-    launch_update_any(st, B, PA, U, rng, ws, PerParticle{});
+static int launch_update(hipStream_t st, const Buffers &B, const PredictArgs &PA, const UpdateArgs &U, const RngArgs &rng, const WeightScratch &ws,
+                         bool no_special) {
+    return launch_update_any(st, B, PA, U, rng, ws, PerParticle{}, no_special);
 }
 
 // K iterations in one launch (kernels.h: PersistArgs): kPersistStride x (tiles + 1 helper) workgroups, of which every

@@ -279,6 +279,8 @@ struct slamgpu_ctx {
     unsigned long long *stamps_dev = nullptr;  // diagnostic (SLAMGPU_STAMPS=1 + libslamgpu_stamps.so): UpdateArgs::stamps
     // persistent small-N step loop (slamgpu_run_observe, kernels.h: PersistArgs)
     bool persist_ok = true;              // SLAMGPU_NO_PERSIST=1 turns it off (diagnostic / tests: the per-step loop)
+    bool special_ok = true;              // SLAMGPU_NO_SPECIAL=1 turns it off (diagnostic / tests: update_kernel's general instantiation for every launch)
+    int64_t special_launches = 0;        // update launches that took a specialised instantiation (slamgpu_update_special_launches: tests)
     struct PersistCollect {              // while set, issue_update queues its launch instead of making it
         std::vector<PersistStep> steps;
         bool have_first = false;
@@ -930,6 +932,7 @@ int slamgpu_create(const slamgpu_config *cfg, slamgpu_ctx **out) {
             c->ref_resample = false;
     }
     c->persist_ok = getenv("SLAMGPU_NO_PERSIST") == nullptr;                               // diagnostic / tests: slamgpu_run_observe as a loop of launches
+    c->special_ok = getenv("SLAMGPU_NO_SPECIAL") == nullptr;                               // diagnostic / tests: kernels.h: update_special
     if (const char *e = getenv("SLAMGPU_CONSOLIDATE_ABOVE")) c->consolidate_above = atoi(e);
     if (const char *e = getenv("SLAMGPU_PLAIN_ROWS_TARGET")) c->plain_rows_target = atoi(e);
     const bool want_stamps = getenv("SLAMGPU_STAMPS") != nullptr;                         // diagnostic
@@ -1303,8 +1306,8 @@ int issue_update(slamgpu_ctx *c, UpdateArgs &U, int n_new, int n_rows, bool need
         c->collect->steps.push_back(q);
     } else {
         Timed t(c, c->cfg.method == SLAMGPU_FASTSLAM2 ? "fs2_update" : "fs1_update");
-        if (c->pp_launch) c->k->update_particle(c->stream, c->B, PA, U, rng, c->ws, *c->pp_launch);
-        else c->k->update(c->stream, c->B, PA, U, rng, c->ws);
+        if (c->pp_launch) c->k->update_particle(c->stream, c->B, PA, U, rng, c->ws, *c->pp_launch, !c->special_ok);
+        else if (c->k->update(c->stream, c->B, PA, U, rng, c->ws, !c->special_ok) != 0) c->special_launches++;
     }
     HIP_TRY(hipGetLastError());
     c->slot ^= 1;   // ... and where it left the set (Ctrl.live / pend of the other slot)
@@ -4273,7 +4276,7 @@ int pp_dev_iteration(slamgpu_ctx *c, int32_t nc, const float *controls, const fl
                     c->obs_out_dev, &c->pp_st_dev->step};
     {
         Timed t(c, c->cfg.method == SLAMGPU_FASTSLAM2 ? "fs2_update" : "fs1_update");
-        c->k->update_particle(c->stream, c->B, PredictArgs{}, U, rng_args(c, 0), c->ws, ppa);
+        c->k->update_particle(c->stream, c->B, PredictArgs{}, U, rng_args(c, 0), c->ws, ppa, !c->special_ok);
     }
     HIP_TRY(hipGetLastError());
     c->slot ^= 1;
@@ -4636,6 +4639,24 @@ int slamgpu_persist_status(slamgpu_ctx *c, int32_t *abandoned, int64_t *launch, 
     if (completed) *completed = ab ? (int32_t) c->pstatus_host[1] : 0;
     if (handed) *handed = ab ? (int32_t) c->pstatus_host[3] : 0;
     return 0;
+}
+
+// which instantiation of the update kernel a launch takes (kernels.h: update_special): host arithmetic only, no device, no context
+int slamgpu_update_special(int32_t method, int32_t arrivals, int32_t big, int32_t per_particle, int32_t no_special, uint32_t mode_bits) {
+    static_assert(kUpdateModeBits == SLAMGPU_UPDATE_MODE_BITS, "slamgpu.h names the mode bits");
+    return update_special(method, arrivals, big != 0, per_particle != 0, false, no_special != 0, mode_bits);
+}
+
+int slamgpu_update_special_launches(slamgpu_ctx *c, int64_t *count) {
+    if (int rc = check_ctx(c)) return rc;
+    if (!count) return fail(SLAMGPU_ERR_INVALID, "slamgpu_update_special_launches: count is null");
+    *count = c->special_launches;
+    return 0;
+}
+
+int slamgpu_update_special_modes(int32_t spec) {
+    if (spec <= 0 || spec >= kUpdateSpecCount) return -1;
+    return (int) update_mode_bits(kUpdateSpecs[spec]);
 }
 
 int slamgpu_sync(slamgpu_ctx *c) {

@@ -4,8 +4,12 @@
 // PP (constants); h_tot, h_ctrl, h_front, h_nb, h_slot, h_grid, h_flags, B, PA, U, rng, ws, ppa (update_kernel's parameters, or what stands
 // in for them in an iteration); the macros STEP_WPAR (ws.wpar), STEP_PLAN (U.plan_inline != 0) and STEP_FRONT (U.front), which a per-step
 // launch reads in place (a local copy of each costs the distributed variants a scalar register they do not have); qe (LDS copy of the iteration's queue
-// entry, PERSIST only); carry (StepCarry, PERSIST only).
+// entry, PERSIST only); carry (StepCarry, PERSIST only); SPEC (kernels.h: UpdateModes; 0 everywhere but in update_kernel's specialised
+// instantiations: every `SPECIAL ? SM.x : <run-time test>` below is then the run-time test it has always been).
     constexpr bool ARR = MODE == 1, DIST = MODE == 2;
+    constexpr bool SPECIAL = SPEC != 0;
+    [[maybe_unused]] constexpr UpdateModes SM = kUpdateSpecs[SPEC];
+    static_assert(!SPECIAL || (!PERSIST && !BIG && MODE == 0 && !PP), "specialised: update_kernel<2, 0, false> only");
     static_assert(!PERSIST || (MODE == 0 && !BIG), "the persistent loop: compact single contexts");
     const int bid = PERSIST ? (int) blockIdx.x / kPersistStride : (int) blockIdx.x;  // this workgroup's number among those that work
     __shared__ float sh_w[kBlock / kWave], sh_w2[kBlock / kWave];
@@ -19,7 +23,7 @@
     // structs have arrived): [prefix of the block totals][ancestor windows][staged records A][staged records B]
     extern __shared__ __align__(16) unsigned char dyn_lds[];
     const int nbg = DIST ? h_nb * B.n_shards : h_nb;  // blocks of the whole particle set
-    const bool h_plan = PERSIST ? STEP_PLAN : (h_flags & 1) != 0, h_scan_global = !PERSIST && (h_flags & 2) != 0;
+    const bool h_plan = PERSIST ? STEP_PLAN : (SPECIAL ? SM.plan : (h_flags & 1) != 0), h_scan_global = SPECIAL ? SM.scan_global : !PERSIST && (h_flags & 2) != 0;
     const bool lay_plan = PERSIST || h_plan;  // (the persistent launch is sized for planning iterations)
     double *const off = reinterpret_cast<double *>(dyn_lds);
     const size_t off_bytes = (lay_plan && !h_scan_global) ? sizeof(double) * (((size_t) nbg + 3) & ~(size_t) 1) : 0;
@@ -107,7 +111,7 @@
         }
     }
     // HEAD: everything whose address follows from the preloaded arguments is requested now, in one burst
-    const bool front = PERSIST || (!BIG && MODE == 0 && (h_flags & 16) != 0);
+    const bool front = SPECIAL ? SM.front : PERSIST || (!BIG && MODE == 0 && (h_flags & 16) != 0);
     FrontLm f_lm{-1, 0};
     FrontHdr f_hd{0, -1, 0, 0};
     float f_x = 0.f, f_y = 0.f;
@@ -126,7 +130,7 @@
             f_lm = h_front->lm[threadIdx.x];
         }
     }
-    const bool logw = (h_flags & 4) != 0;
+    const bool logw = SPECIAL ? SM.logw : (h_flags & 4) != 0;
     const bool do_scan = h_plan && !h_scan_global;
     ScanLoads scl{0.0f, 0.0f, 0.0f, 0.0f, -INFINITY, -INFINITY};
     // distributed contexts, table wider than two totals per thread: by LDS-DMA into the memory of the ancestor windows and the
@@ -257,7 +261,7 @@
             scan_finish(scl, tot, nbg, nb, logw, off, sh_a, sh_q, W, Q, Mx, scan_tab);
         }
         const float neff = neff_of(W, Q);  // Neff = 1 / sum((w/W)^2)  (core.cpp:784-788)
-        pend = U.do_resample && (neff < (float) U.n_effective);
+        pend = (SPECIAL ? SM.do_resample : U.do_resample != 0) && (neff < (float) U.n_effective);
         if (bid == 0 && threadIdx.x == 0) {
             ctrl->wsum = W;
             ctrl->wsq = Q;
@@ -307,13 +311,13 @@
             // whose partials are complete: this block runs beside the compute blocks instead of as launches of its own
             if (STEP_PLAN) {  // the decision is needed for `out`: recompute it from the two totals, cheaply
                 double Q;
-                if (U.scan_global) {
+                if (SPECIAL ? SM.scan_global : U.scan_global != 0) {
                     W = offp[nb + 1];
                     Q = offp[nb + 2];
                 } else {
                     scan_finish(scl, tot, nbg, nb, logw, off, sh_a, sh_q, W, Q, Mx, scan_tab);
                 }
-                pend = U.do_resample && (neff_of(W, Q) < (float) U.n_effective);
+                pend = (SPECIAL ? SM.do_resample : U.do_resample != 0) && (neff_of(W, Q) < (float) U.n_effective);
             }
             if (threadIdx.x == 0) {
                 ctrl->live[B.slot ^ 1] = pend ? cur ^ 1 : cur;
@@ -618,7 +622,7 @@
             hg0 = carry.hg0;
             hg1 = carry.hg1;
             hg2 = carry.hg2;
-        } else if (METHOD == 2 && rng.mode != 0 && (m > 0 || n > 0)) {
+        } else if (METHOD == 2 && (SPECIAL ? SM.philox : rng.mode != 0) && (m > 0 || n > 0)) {
             U4 r = philox4x32((uint32_t) (rng.first_particle + i), rng.step, 0u, 0u, rng.k0, rng.k1);
 #ifdef SLAM_FAST_MATH
             box_muller3_fast(r, hg0, hg1, hg2);
@@ -683,11 +687,11 @@
         }
         if (PA.nsteps > 0) {
 #ifdef SLAM_FAST_MATH
-            if (PA.comp.valid) {
+            if (SPECIAL ? SM.comp_valid : PA.comp.valid != 0) {
                 Sym3 P = {q00, q10, q11, q20, q21, q22};
                 predict_composite(x, y, th, P, PA.comp);
                 q00 = P.p00; q10 = P.p10; q11 = P.p11; q20 = P.p20; q21 = P.p21; q22 = P.p22;
-            } else if (METHOD == 2 && PA.use_heading && !PA.add_noise) {
+            } else if (METHOD == 2 && (SPECIAL ? SM.use_heading && !SM.add_noise : PA.use_heading && !PA.add_noise)) {
                 Sym3 P = {q00, q10, q11, q20, q21, q22};
                 predict_steps_heading_fast(x, y, th, P, PA, BIG ? nullptr : ctl);
                 q00 = P.p00; q10 = P.p10; q11 = P.p11; q20 = P.p20; q21 = P.p21; q22 = P.p22;
@@ -707,7 +711,7 @@
 #endif
             {
                 float P[9] = {q00, q10, q20, q10, q11, q21, q20, q21, q22};
-                predict_steps(x, y, th, P, PA, rng, i, S);
+                predict_steps<SPECIAL ? (int) SM.add_noise : -1, SPECIAL ? (int) SM.use_heading : -1>(x, y, th, P, PA, rng, i, S);
                 q00 = P[0]; q10 = P[3]; q11 = P[4]; q20 = P[6]; q21 = P[7]; q22 = P[8];
             }
             pose_dirty = true;
@@ -719,7 +723,7 @@
             // restructured arithmetic (device_math.h, fast section); same data flow as the strict branch below
             float g0 = 0.f, g1 = 0.f, g2 = 0.f;
             if (m > 0 || n > 0) {
-                if (rng.mode == 0) {
+                if (SPECIAL ? !SM.philox : rng.mode == 0) {
                     g0 = rng.normals[0 * S + i];
                     g1 = rng.normals[1 * S + i];
                     g2 = rng.normals[2 * S + i];
@@ -859,7 +863,7 @@
         if (METHOD == 2) {
             float g0 = 0.f, g1 = 0.f, g2 = 0.f;
             if (m > 0 || n > 0) {
-                if (rng.mode == 0) {
+                if (SPECIAL ? !SM.philox : rng.mode == 0) {
                     g0 = rng.normals[0 * S + i];
                     g1 = rng.normals[1 * S + i];
                     g2 = rng.normals[2 * S + i];
