@@ -620,6 +620,56 @@ int slamgpu_path_trace(slamgpu_ctx *ctx, int32_t particle, int64_t first, int32_
  * in `distinct` and not in the sums), one launch per record from the newest one down to `first`. */
 #define SLAMGPU_PATH_STRIDE 7
 int slamgpu_path_summary(slamgpu_ctx *ctx, int64_t first, int32_t count, double *out, int32_t *distinct);
+
+/* ---- pose posterior: weighted mean, covariance, and what a consistency test (NEES) needs ---------------------------------
+ * What the whole particle set believes about the vehicle pose NOW (the filtered posterior; slamgpu_estimate is the reference's
+ * computeEstimatedPosition: an unweighted mean and one particle's heading).  "The set" is what slamgpu_peek(ctx, 0, 1, N, ...) would
+ * show at this moment: queued predicts flushed, the outstanding resampling stage run, a pending gather read through its ancestors
+ * with weight 1/N.  The weights w^_i are exactly slamgpu_map_summary's (w_i / sum w; log-weight contexts: exp(l_i - max l),
+ * normalised).  Every pose is promoted to double, p_i = (x_i, y_i, theta_i); theta_p is the heading of particle 0 of the set, and
+ *     u_i = IEEE remainder(theta_i - theta_p, 2 pi)      (in double; 2 pi the double nearest to it)
+ * the heading's deviation from that pivot -- not from the circular mean, so that one pass over the set suffices and the contract is
+ * exact.  u and the moments built on it ([3], xu, yu, uu) are meaningful while the heading cloud spans less than pi (no deviation is
+ * then folded to the wrong side); [4..5] show when it does not: their resultant length sqrt([4]^2 + [5]^2) falls well below 1.
+ * out[SLAMGPU_POSE_STRIDE]:
+ *     [0]       sum w^_i^2: the effective sample size of the set shown is 1 / out[0]
+ *     [1..2]    sum w^ x, sum w^ y
+ *     [3]       theta_p + sum w^ u: the mean heading, NOT wrapped (the caller wraps it)
+ *     [4..5]    sum w^ cos theta, sum w^ sin theta (slamgpu_path_summary's convention: the caller takes atan2 and the resultant length)
+ *     [6..11]   scatter sum w^ d d^T about (x-, y-, u-), d = (x - x-, y - y-, u - u-): xx, xy, yy, xu, yu, uu
+ *     [12..17]  sum w^ Pv_i, the mean within-particle pose covariance as stored: p00, p10, p11, p20, p21, p22
+ * The total pose covariance is scatter + mean Pv, the same split as the map summary's scatter + mean Pf.  Weights that sum to zero
+ * or to nothing finite: every entry NaN, return 0 (SLAMGPU_STATUS_DEGENERATE's convention).  N = 1: the scatter is exactly 0.  Sums
+ * are in double, in a fixed order, about a pivot inside the cloud for x and y, without floating-point atomics: the same state gives
+ * the same bits on every call, and the same bits whether it is read under a pending gather or after slamgpu_download has settled
+ * it.  Like slamgpu_peek it rewrites nothing: the state the next step works on is bit for bit what it would have been without the
+ * call.  Single contexts only (SLAMGPU_ERR_INVALID otherwise, as for a NULL out; outputs untouched).  Synchronises. */
+#define SLAMGPU_POSE_STRIDE 18
+int slamgpu_pose_summary(slamgpu_ctx *ctx, double out[SLAMGPU_POSE_STRIDE]);
+/* The same summary per step, kept on the device: a ring of `capacity` entries of SLAMGPU_POSE_STRIDE doubles, in the style of the path
+ * recorder's.  Entries are numbered from 0 when the ring is enabled and never renumbered; entries [first, next) are retained; a full
+ * ring drops its oldest entry and never refuses a step; its capacity is independent of the estimate history's.
+ * slamgpu_pose_history_enable: capacity > 0 starts (or restarts: entries dropped, numbering from 0); 0 stops and frees;
+ * SLAMGPU_ERR_ALLOC leaves the setting as it was.  slamgpu_pose_history_record appends the summary of the set as it stands now: two
+ * launches enqueued, no synchronisation.  It is done automatically exactly where a history entry is appended -- slamgpu_step and
+ * slamgpu_step_observe with record_estimate != 0, every iteration of slamgpu_run_observe, every iteration of slamgpu_run_particle (one
+ * without observations included) -- so that entry r, counted from the enable, and history entry r belong to the same step; callers
+ * of slamgpu_update / _update_particle / _update_labels / _estimate_async call it themselves.  slamgpu_pose_history_info: any pointer
+ * may be NULL.  slamgpu_pose_history_fetch: entries [first, first + count) into out[count][SLAMGPU_POSE_STRIDE], non-consuming;
+ * synchronises; entries outside the retained range, a negative count or a NULL out: SLAMGPU_ERR_INVALID, outputs untouched;
+ * count == 0 does nothing.
+ * While the ring is on the path recorder's rules hold: an update runs its resampling stage at the end of the call instead of inside
+ * the next update launch, and slamgpu_run_observe takes its loop of launches where it would take the persistent one-launch loop.  The
+ * filter does not notice: every pose, record, weight, history entry and ancestor of a run is bit for bit that of the same run with
+ * the ring off.  slamgpu_run_particle is NOT refused: its iterations settle their resampling with kernels of their own, and an entry
+ * runs that stage right after its iteration (where the next iteration would have run it first thing), so entry k is bit for bit
+ * what slamgpu_pose_summary returns after the equivalent host-driven sequence of k + 1 iterations.  slamgpu_upload keeps the retained
+ * entries (they are plain summaries, not lineage).  Single contexts only.  With the ring never enabled and slamgpu_pose_summary
+ * never called nothing is allocated and no kernel of it is launched.  What it costs: DESIGN.md section 7e. */
+int slamgpu_pose_history_enable(slamgpu_ctx *ctx, int32_t capacity);
+int slamgpu_pose_history_record(slamgpu_ctx *ctx);
+int slamgpu_pose_history_info(slamgpu_ctx *ctx, int64_t *first, int64_t *next, int32_t *capacity);
+int slamgpu_pose_history_fetch(slamgpu_ctx *ctx, int64_t first, int32_t count, double *out);
 int slamgpu_upload(slamgpu_ctx *ctx, int32_t nf, const float *xv, const float *Pv9, const float *w, const float *xf,
                    const float *Pf4);
 int slamgpu_sync(slamgpu_ctx *ctx);

@@ -106,6 +106,18 @@ int64_t slamhost_map_candidates(const double *summary, int32_t slots, double rad
 int slamhost_map_merge(const double *summary, int32_t slots, const int32_t *pairs, const double *joint, int32_t npairs, double radius,
                        double cohold, int32_t *cluster /*[slots]*/, double *merged /*[slots][9]*/, int32_t *nmerged);
 
+/* The consistency of the pose posterior (Bailey, Nieto & Nebot, "Consistency of the FastSLAM algorithm", ICRA 2006): the normalised
+ * estimation error squared of `count` entries of slamgpu_pose_summary / slamgpu_pose_history_fetch (summary[count][18]) against the
+ * true poses xtrue[count][3].  Per entry, in double:
+ *     e    = (out[1] - x_t, out[2] - y_t, IEEE remainder(out[3] - theta_t, 2 pi))
+ *     P    = scatter + mean Pv, 3 x 3 symmetric: (out[6..11]) + (out[12..17]) in the order xx, xy, yy, xu, yu, uu
+ *     NEES = e^T P^-1 e through the Cholesky factor of P
+ * nees[k] is NaN for an entry whose P is not positive definite (N = 1, a collapsed set) or whose summary holds a NaN (degenerate
+ * weights); the return value counts such entries.  err[count][3] (may be NULL) receives e.  A consistent filter's NEES has mean 3
+ * and lies below 7.8147 -- the 95 % point of chi^2 with 3 degrees of freedom -- 95 % of the time.  -1: bad arguments (a negative
+ * count, a NULL array that is needed). */
+int32_t slamhost_pose_nees(const double *summary, int32_t count, const float *xtrue /*3 per entry*/, double *nees, double *err /*3 per entry, may be NULL*/);
+
 void slamhost_draw_normals(int32_t count, int32_t dim, float *out); /* count x randn(dim,1): dim+1 rand() each */
 int32_t slamhost_draw_strata(int32_t N, float *out);                /* returns the reference's strata count (== N when supported) */
 double slamhost_unif_rand(void);                                    /* unifRand (core.cpp:775) */

@@ -32,9 +32,12 @@ DECLARED_SYMBOLS = [
     "slamgpu_map_summary", "slamgpu_map_pairs", "slamgpu_set_particle_mutex", "slamgpu_particle_mutex_stats",
     "slamgpu_set_particle_miss", "slamgpu_particle_missed", "slamgpu_particle_miss_stats", "slamgpu_particle_miss_visited",
     "slamgpu_path_enable", "slamgpu_path_record", "slamgpu_path_info", "slamgpu_path_fetch", "slamgpu_path_trace", "slamgpu_path_summary",
+    "slamgpu_pose_summary", "slamgpu_pose_history_enable", "slamgpu_pose_history_record", "slamgpu_pose_history_info",
+    "slamgpu_pose_history_fetch",
 ]
 MAP_STRIDE = 9  # SLAMGPU_MAP_STRIDE
 PATH_STRIDE = 7  # SLAMGPU_PATH_STRIDE
+POSE_STRIDE = 18  # SLAMGPU_POSE_STRIDE
 ASSOC_AUTO, ASSOC_EXHAUSTIVE, ASSOC_GRID, ASSOC_LISTS = 0, 1, 2, 3
 FLAG_DEVICE_OBSERVE = 1
 FLAG_NO_REFERENCE_RESAMPLE = 2
@@ -141,6 +144,12 @@ def load_library():
         L.slamgpu_map_summary.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
     if hasattr(L, "slamgpu_map_pairs"):
         L.slamgpu_map_pairs.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+    if hasattr(L, "slamgpu_pose_summary"):
+        L.slamgpu_pose_summary.argtypes = [C.c_void_p, C.c_void_p]
+        L.slamgpu_pose_history_enable.argtypes = [C.c_void_p, C.c_int32]
+        L.slamgpu_pose_history_record.argtypes = [C.c_void_p]
+        L.slamgpu_pose_history_info.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
+        L.slamgpu_pose_history_fetch.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]
     if hasattr(L, "slamgpu_path_enable"):
         L.slamgpu_path_enable.argtypes = [C.c_void_p, C.c_int32]
         L.slamgpu_path_record.argtypes = [C.c_void_p]
@@ -608,6 +617,38 @@ class SlamGpu:
         distinct = np.zeros(max(count, 0), np.int32)
         _chk(self.L.slamgpu_path_summary(self.h, first, count, _ptr(out), _ptr(distinct)))
         return dict(mean=out[:, 0:2].copy(), scatter=out[:, 2:5].copy(), cs=out[:, 5:7].copy(), distinct=distinct)
+
+    def pose_summary(self):
+        """slamgpu_pose_summary: the pose posterior of the set as peek() would show it, out[18] float64: [0] sum w^2 (1 / it: the
+        effective sample size), [1..2] mean x, y, [3] mean heading (not wrapped), [4..5] sum w cos / sin, [6..11] scatter xx, xy, yy, xu,
+        yu, uu, [12..17] mean Pv p00, p10, p11, p20, p21, p22; rewrites no state"""
+        out = np.zeros(POSE_STRIDE, np.float64)
+        _chk(self.L.slamgpu_pose_summary(self.h, _ptr(out)))
+        return out
+
+    def pose_history_enable(self, capacity):
+        """slamgpu_pose_history_enable: keep pose_summary() of every recorded step in a ring of `capacity` entries (0: stop and free)"""
+        _chk(self.L.slamgpu_pose_history_enable(self.h, int(capacity)))
+
+    def pose_history_record(self):
+        """slamgpu_pose_history_record: append the summary of the set as it stands (step / step_observe / run_observe / run_particle do
+        it themselves); enqueued, no synchronisation"""
+        _chk(self.L.slamgpu_pose_history_record(self.h))
+
+    def pose_history_info(self):
+        """(first, next, capacity): entries [first, next) are retained (slamgpu_pose_history_info)"""
+        a, b, cap = C.c_int64(), C.c_int64(), C.c_int32()
+        _chk(self.L.slamgpu_pose_history_info(self.h, C.byref(a), C.byref(b), C.byref(cap)))
+        return a.value, b.value, cap.value
+
+    def pose_history_fetch(self, first=None, count=None):
+        """entries first .. first + count - 1 (default: all retained) as [count, 18] float64; non-consuming (slamgpu_pose_history_fetch)"""
+        a, b, _ = self.pose_history_info()
+        first = a if first is None else int(first)
+        count = b - first if count is None else int(count)
+        out = np.zeros((max(count, 0), POSE_STRIDE), np.float64)
+        _chk(self.L.slamgpu_pose_history_fetch(self.h, first, count, _ptr(out)))
+        return out
 
     def upload(self, st):
         nf = int(st["nf"])

@@ -45,6 +45,10 @@
 //   -plotstride <k>      particles / feature particles sent per step are decimated to every k-th particle (default: as
 //                        many as keep a frame below ~2 000 particles; the reference sends all of them: N = 10^5 would be
 //                        1.6 MB of poses and 56 MB of feature points per control step)
+//   -pose none|posterior posterior: the pose posterior of every observation step is kept (slamgpu_pose_history_*; -POSE_RECORDS n entries,
+//                        default 4096), and one more line is printed at the end: the entries kept, the mean distance of the WEIGHTED mean to the
+//                        true position beside that of the filtered estimates of the same steps, the mean NEES of the pose against the true pose
+//                        (slamhost_pose_nees), the share of steps with NEES <= 7.8147 and the median effective sample size 1 / sum w^2
 //   -path none|smoothed  smoothed: the path posterior is recorded, one record per observation step (slamgpu_path_*; -PATH_RECORDS n records
 //                        are kept, default 4096), and one more line is printed at the end: the records kept, the mean distance of the
 //                        SMOOTHED path (the mean over the surviving particles of the path each descends from) to the true path beside that
@@ -113,6 +117,10 @@ static void usage(const char *a0) {
     printf("    -path none|smoothed smoothed: record the path posterior (one record per observation step, -PATH_RECORDS n of them kept, default 4096)\n");
     printf("                        and print one more line: the smoothed path's distance to the true path beside the filtered estimates', and the\n");
     printf("                        distinct ancestors 1 / 10 / 100 records back (slamgpu_path_summary; FastSLAM, one GPU, not -assoc particle -observe device)\n");
+    printf("    -pose none|posterior posterior: keep the pose posterior of every observation step (slamgpu_pose_history_*; -POSE_RECORDS n entries kept,\n");
+    printf("                        default 4096) and print one more line: the weighted mean's distance to the true position beside the filtered\n");
+    printf("                        estimates', the mean NEES against the true pose, the share of steps with NEES <= 7.8147 (the 95 %% point of chi^2 with\n");
+    printf("                        3 degrees of freedom: a definition, not a measured bound) and the median effective sample size (FastSLAM, one GPU)\n");
     printf("    -gpus k             FastSLAM particle set distributed over k GPUs (k > devices: logical shards on device 0)\n");
     printf("    -observe host|device  where the observation of a step is made: host (default) or on the GPU (the packet never leaves\n");
     printf("                        device memory: slamgpu_step_observe; -rng philox, known association, no -plot; with -assoc particle:\n");
@@ -336,12 +344,62 @@ static void print_posterior_map(slamgpu_ctx *ctx, const Simulator &sim) {
 // step's true position and filtered estimate (x, y each)
 static int g_path_records = 0;  // 0: off
 static std::vector<double> g_path_steps;
+// -pose posterior: the per-step pose posterior (slamgpu_pose_history_*), the same bookkeeping: entry r belongs to observation step r,
+// g_pose_steps[r] holds that step's true pose (x, y, theta) and filtered estimate (x, y)
+static int g_pose_records = 0;  // 0: off
+static std::vector<double> g_pose_steps;
 static void path_step(const float xt[3], const double est[3]) {
+    if (g_pose_records) {
+        for (int q = 0; q < 3; q++) g_pose_steps.push_back(xt[q]);
+        g_pose_steps.push_back(est[0]);
+        g_pose_steps.push_back(est[1]);
+    }
     if (!g_path_records) return;
     g_path_steps.push_back(xt[0]);
     g_path_steps.push_back(xt[1]);
     g_path_steps.push_back(est[0]);
     g_path_steps.push_back(est[1]);
+}
+static void print_pose_posterior(slamgpu_ctx *ctx) {
+    if (!g_pose_records) return;
+    int64_t first = 0, next = 0;
+    if (slamgpu_pose_history_info(ctx, &first, &next, nullptr) != 0) {
+        fprintf(stderr, "slamgpu: %s\n", slamgpu_last_error());
+        return;
+    }
+    const int64_t n = next - first;
+    if (n <= 0 || (size_t) next * 5 > g_pose_steps.size()) {
+        printf("pose posterior: no entries\n");
+        return;
+    }
+    std::vector<double> sum((size_t) SLAMGPU_POSE_STRIDE * (size_t) n), nees((size_t) n), inv;
+    std::vector<float> xt(3 * (size_t) n);
+    if (slamgpu_pose_history_fetch(ctx, first, (int32_t) n, sum.data()) != 0) {
+        fprintf(stderr, "slamgpu: %s\n", slamgpu_last_error());
+        return;
+    }
+    double dw = 0, df = 0;
+    for (int64_t r = first; r < next; r++) {
+        const double *e = sum.data() + (size_t) SLAMGPU_POSE_STRIDE * (size_t) (r - first), *t = g_pose_steps.data() + 5 * (size_t) r;
+        for (int q = 0; q < 3; q++) xt[3 * (size_t) (r - first) + q] = (float) t[q];
+        dw += std::sqrt((e[1] - t[0]) * (e[1] - t[0]) + (e[2] - t[1]) * (e[2] - t[1]));
+        df += std::sqrt((t[3] - t[0]) * (t[3] - t[0]) + (t[4] - t[1]) * (t[4] - t[1]));
+        if (e[0] > 0.0) inv.push_back(1.0 / e[0]);
+    }
+    const int32_t bad = slamhost_pose_nees(sum.data(), (int32_t) n, xt.data(), nees.data(), nullptr);
+    double tot = 0;
+    int64_t ok = 0, in95 = 0;
+    for (int64_t k = 0; k < n; k++)
+        if (nees[(size_t) k] == nees[(size_t) k]) {
+            tot += nees[(size_t) k];
+            ok++;
+            in95 += nees[(size_t) k] <= 7.8147;  // the 95 % point of chi^2 with 3 degrees of freedom
+        }
+    std::sort(inv.begin(), inv.end());
+    const double med = inv.empty() ? std::nan("") : (inv.size() % 2 ? inv[inv.size() / 2] : 0.5 * (inv[inv.size() / 2 - 1] + inv[inv.size() / 2]));
+    printf("pose posterior: %lld entries kept, mean distance to the true position %.4f m (filtered estimates of the same steps: %.4f m); mean NEES %.4f, "
+           "NEES <= 7.8147 in %.4f of the steps (%d entries without a NEES); median effective sample size %.1f\n",
+           (long long) n, dw / (double) n, df / (double) n, ok ? tot / (double) ok : std::nan(""), ok ? (double) in95 / (double) ok : std::nan(""), (int) bad, med);
 }
 static void print_smoothed_path(slamgpu_ctx *ctx) {
     if (!g_path_records) return;
@@ -557,6 +615,7 @@ static int run_batched(Simulator &sim, slamgpu_ctx *ctx, bool observe_dev, long 
     else printf("landmarks in map: %d\n", slamgpu_num_landmarks(ctx));
     print_posterior_map(ctx, sim);
     if (!rc) print_smoothed_path(ctx);
+    if (!rc) print_pose_posterior(ctx);
     return rc ? EXIT_FAILURE : 0;
 }
 
@@ -613,6 +672,29 @@ int main(int argc, char **argv) {
         }
         sim.conf.kv.erase("path");
         sim.conf.kv.erase("PATH_RECORDS");
+        // ... and -pose (with -POSE_RECORDS), refused the same way
+        const std::string po = sim.conf.s("pose"), por = sim.conf.s("POSE_RECORDS");
+        if (!po.empty() && po != "none" && po != "posterior") {
+            fprintf(stderr, "-pose none|posterior\n");
+            return EXIT_FAILURE;
+        }
+        if (po == "posterior") {
+            g_pose_records = por.empty() ? 4096 : atoi(por.c_str());
+            const std::string gp = sim.conf.s("gpus");
+            const char *why = nullptr;
+            if (g_pose_records <= 0) why = "-POSE_RECORDS needs a positive number of entries";
+            else if (sim.conf.method == 0) why = "FastSLAM only (the EKF's pose posterior is its own state and P)";
+            else if (!gp.empty() && atoi(gp.c_str()) != 1) why = "single GPU only (slamgpu_pose_* have no distributed form)";
+            if (why) {
+                fprintf(stderr, "-pose posterior: %s\n", why);
+                return EXIT_FAILURE;
+            }
+        } else if (!por.empty()) {
+            fprintf(stderr, "-POSE_RECORDS n: with -pose posterior\n");
+            return EXIT_FAILURE;
+        }
+        sim.conf.kv.erase("pose");
+        sim.conf.kv.erase("POSE_RECORDS");
     }
     const Conf &c = sim.conf;
     printf("map: %s\n", c.map_path.c_str());
@@ -756,6 +838,11 @@ int main(int argc, char **argv) {
         }
         if (g_path_records && slamgpu_path_enable(ctx, g_path_records) != 0) {
             fprintf(stderr, "-path smoothed: %s\n", slamgpu_last_error());
+            slamgpu_destroy(ctx);
+            return EXIT_FAILURE;
+        }
+        if (g_pose_records && slamgpu_pose_history_enable(ctx, g_pose_records) != 0) {
+            fprintf(stderr, "-pose posterior: %s\n", slamgpu_last_error());
             slamgpu_destroy(ctx);
             return EXIT_FAILURE;
         }
@@ -963,8 +1050,9 @@ int main(int argc, char **argv) {
                 }
             }
             if (!rc) rc = slamgpu_estimate(ctx, est);
-            if (!rc && r == 1 && g_path_records) {  // one record per observation step (these loops make their updates themselves)
-                rc = slamgpu_path_record(ctx);
+            if (!rc && r == 1 && (g_path_records || g_pose_records)) {  // one record per observation step (these loops make their updates themselves)
+                if (g_path_records) rc = slamgpu_path_record(ctx);
+                if (!rc && g_pose_records) rc = slamgpu_pose_history_record(ctx);
                 path_step(sim.xTrue, est);
             }
             if (rc) {
@@ -1040,6 +1128,7 @@ int main(int argc, char **argv) {
     else printf("landmarks in map: %d\n", ekf.num_features());
     if (ctx) print_posterior_map(ctx, sim);
     if (ctx && !rc) print_smoothed_path(ctx);
+    if (ctx && !rc) print_pose_posterior(ctx);
     if (plot.active()) {
         plot.endPlot();
         plot.close();

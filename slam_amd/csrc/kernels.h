@@ -638,6 +638,30 @@ struct PathWalkArgs {
     int32_t count;              // records of this chunk in use
 };
 
+// Pose posterior (slamgpu_pose_summary, slamgpu_pose_history_*): over the particle set slamgpu_peek would show, with the weights of
+// slamgpu_map_summary, the weighted mean pose, the scatter about it, the mean within-particle covariance Pv and sum w^2.  Headings
+// enter as deviations u = IEEE remainder(theta - theta_p, 2 pi) (double) from the heading of particle 0 of the set, so that one pass
+// does it, and as sum w cos / sum w sin.  pose_summary_kernel: one workgroup per tile of kPoseTile = kBlock * kPoseT particles, 40 bytes
+// read per particle (poseA / poseB / poseC), all of a lane's loads in flight together; sums in double about the wave's first particle
+// (x, y), lanes combined by a DPP sum, waves and tiles as (W, mean, M2) by the pairwise update of Chan, Golub & LeVeque in ascending
+// particle order: no atomics, the same bits for the same particles in the same order.  One partial per tile goes to `part`;
+// pose_finish_kernel (one workgroup of kPoseFinParts threads, each a stretch of the tiles, then the stretches, ascending throughout)
+// merges them, normalises and writes the kPoseStride doubles of `out` (a staging slot, or an entry of the per-step ring).
+// Log-weight contexts: a tile's sums are of exp(l - M_t) (kPoseMt); the finishing pass rescales by exp(M_t - max M).
+constexpr int kPoseT = 4;                  // particles per lane
+constexpr int kPoseTile = kBlock * kPoseT; // particles per tile
+constexpr int kPoseStride = 18;            // SLAMGPU_POSE_STRIDE
+constexpr int kPoseFinParts = 64;          // threads of the finishing pass
+constexpr double kPoseTwoPi = 6.283185307179586476925286766559;
+// fields of a partial, [tile][field]: sum w, sum w^2 | mean x, y, u | M2 xx, xy, yy, xu, yu, uu | sum w cos, sin | sum w Pv | M_t
+enum { kPoseW = 0, kPoseW2, kPoseMx, kPoseMy, kPoseMu, kPoseXX, kPoseXY, kPoseYY, kPoseXU, kPoseYU, kPoseUU, kPoseC, kPoseS,
+       kPoseP00, kPoseP10, kPoseP11, kPoseP20, kPoseP21, kPoseP22, kPoseMt, kPoseFields };
+struct PoseSummaryArgs {
+    int32_t tiles, logw;
+    double *part;               // [tiles][kPoseFields]
+    double *out;                // [kPoseStride]
+};
+
 // ---- gated association with a spatial prefilter (slamgpu_associate_ex) ------------------------------------------------------
 // Per landmark j, over ALL particles: the bounding box of its position estimates and the largest trace of its covariance
 // (lmk_box_kernel, recomputed when the landmark is written), and from them a radius rho_j such that a particle's estimate of j
@@ -957,6 +981,10 @@ struct KernelTable {
     // slamgpu_set_particle_mutex (PpMutexArgs): the association's labels rewritten in place, before their census and the resolve; lists:
     // the re-match walks the observations' candidate lists; device-driven when PpMutexArgs::obs is set
     void (*pp_mutex)(hipStream_t, const Buffers &, const PpMutexArgs &, int lists);
+    // slamgpu_pose_summary / slamgpu_pose_history_record (PoseSummaryArgs): the tiles' partials, and their finishing pass into A.out.
+    // Both read the particle state only
+    void (*pose_summary)(hipStream_t, const Buffers &, const WeightScratch &, const PoseSummaryArgs &);
+    void (*pose_finish)(hipStream_t, const Buffers &, const WeightScratch &, const PoseSummaryArgs &);
 };
 
 const KernelTable *kernels_strict();

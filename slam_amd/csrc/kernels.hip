@@ -5846,6 +5846,205 @@ static void launch_pp_mutex(hipStream_t st, const Buffers &B, const PpMutexArgs 
                    A.obs != nullptr);
 }
 
+// ---- slamgpu_pose_summary / slamgpu_pose_history_* (kernels.h: PoseSummaryArgs) -----------------------------------------------
+// one (W, sum w^2, mean, M2, sum w cos, sum w sin, sum w Pv) summary and the pairwise update with the one that follows it in particle order
+struct PosePart {
+    double v[kPoseFields];
+};
+SLAM_DEV void pose_merge(PosePart &a, const PosePart &b) {
+    if (!(b.v[kPoseW] != 0.0)) return;  // nothing of weight in b
+    if (!(a.v[kPoseW] != 0.0)) {
+        a = b;
+        return;
+    }
+    const double W = a.v[kPoseW] + b.v[kPoseW], f = b.v[kPoseW] / W, g = a.v[kPoseW] * f;
+    const double dx = b.v[kPoseMx] - a.v[kPoseMx], dy = b.v[kPoseMy] - a.v[kPoseMy], du = b.v[kPoseMu] - a.v[kPoseMu];
+    a.v[kPoseMx] += dx * f;
+    a.v[kPoseMy] += dy * f;
+    a.v[kPoseMu] += du * f;
+    a.v[kPoseXX] += b.v[kPoseXX] + dx * dx * g;
+    a.v[kPoseXY] += b.v[kPoseXY] + dx * dy * g;
+    a.v[kPoseYY] += b.v[kPoseYY] + dy * dy * g;
+    a.v[kPoseXU] += b.v[kPoseXU] + dx * du * g;
+    a.v[kPoseYU] += b.v[kPoseYU] + dy * du * g;
+    a.v[kPoseUU] += b.v[kPoseUU] + du * du * g;
+    a.v[kPoseW2] += b.v[kPoseW2];
+    for (int q = kPoseC; q <= kPoseP22; q++) a.v[q] += b.v[q];
+    a.v[kPoseW] = W;
+}
+
+// the heading the deviations are taken about: that of particle 0 of the set peek shows
+SLAM_DEV float pose_pivot_heading(const Buffers &B, const WeightScratch &ws, int cur, bool pend) {
+    return B.poseA[cur][pend ? ws.keep[B.slot][0] : 0].z;
+}
+
+__global__ void __launch_bounds__(kBlock) pose_summary_kernel(Buffers B, WeightScratch ws, PoseSummaryArgs A) {
+    constexpr int kWaves = kBlock / kWave;
+    constexpr int kSums = kPoseP22 + 1;  // the fields a wave adds up (the tile's M_t is not one of them)
+    __shared__ double sh[kWaves][kSums];
+    __shared__ float sh_m[kWaves];
+    const Ctrl *ctrl = B.ctrl;
+    const int cur = ctrl->live[B.slot];
+    const bool pend = ctrl->pend[B.slot] != 0;
+    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
+    const double thp = (double) pose_pivot_heading(B, ws, cur, pend);
+    // this lane's particles, all their loads in flight together
+    float4 pa[kPoseT], pb[kPoseT];
+    float2 pc[kPoseT];
+    bool on[kPoseT];
+    float mb = -INFINITY;
+#pragma unroll
+    for (int t = 0; t < kPoseT; t++) {
+        const int i = blockIdx.x * kPoseTile + t * kBlock + threadIdx.x;
+        on[t] = i < B.n;
+        const int anc = on[t] ? (pend ? ws.keep[B.slot][i] : i) : 0;
+        pa[t] = on[t] ? B.poseA[cur][anc] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        pb[t] = on[t] ? B.poseB[cur][anc] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        pc[t] = on[t] ? B.poseC[cur][anc] : make_float2(0.0f, 0.0f);
+        if (on[t] && pend) pa[t].w = ctrl->inv_n;  // resampled particles restart at 1/N, as in peek_kernel
+        if (on[t] && A.logw) mb = fmaxf(mb, pa[t].w);
+    }
+    double w[kPoseT];
+    if (A.logw) {  // the tile's largest log-weight
+        for (int d = kWave / 2; d > 0; d >>= 1) mb = fmaxf(mb, __shfl_xor(mb, d, kWave));
+        if (lane == 0) sh_m[wave] = mb;
+        __syncthreads();
+        mb = sh_m[0];
+        for (int v = 1; v < kWaves; v++) mb = fmaxf(mb, sh_m[v]);
+#pragma unroll
+        for (int t = 0; t < kPoseT; t++) w[t] = (on[t] && mb != -INFINITY) ? exp((double) pa[t].w - (double) mb) : 0.0;
+    } else {
+        mb = 0.0f;
+#pragma unroll
+        for (int t = 0; t < kPoseT; t++) w[t] = (double) pa[t].w;
+    }
+    // pivot: the wave's first particle (a point of the cloud: the sums below cancel at the cloud's size).  A wave whose first
+    // particle lies beyond the set holds none (its lanes' particles only follow it)
+    const float px = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(pa[0].x)));
+    const float py = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(pa[0].y)));
+    double a[kSums];
+#pragma unroll
+    for (int q = 0; q < kSums; q++) a[q] = 0.0;
+#pragma unroll
+    for (int t = 0; t < kPoseT; t++) {
+        if (on[t]) {
+            const double wt = w[t], dx = (double) pa[t].x - (double) px, dy = (double) pa[t].y - (double) py, th = (double) pa[t].z;
+            const double du = remainder(th - thp, kPoseTwoPi);
+            a[kPoseW] += wt;
+            a[kPoseW2] += wt * wt;
+            a[kPoseMx] += wt * dx;
+            a[kPoseMy] += wt * dy;
+            a[kPoseMu] += wt * du;
+            a[kPoseXX] += wt * dx * dx;
+            a[kPoseXY] += wt * dx * dy;
+            a[kPoseYY] += wt * dy * dy;
+            a[kPoseXU] += wt * dx * du;
+            a[kPoseYU] += wt * dy * du;
+            a[kPoseUU] += wt * du * du;
+            a[kPoseC] += wt * cos(th);
+            a[kPoseS] += wt * sin(th);
+            a[kPoseP00] += wt * (double) pb[t].x;
+            a[kPoseP10] += wt * (double) pb[t].y;
+            a[kPoseP11] += wt * (double) pb[t].z;
+            a[kPoseP20] += wt * (double) pb[t].w;
+            a[kPoseP21] += wt * (double) pc[t].x;
+            a[kPoseP22] += wt * (double) pc[t].y;
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < kSums; q++) a[q] = wave_sum_d(a[q]);
+    if (lane == 0) {
+        double *o = sh[wave];
+        const double W = a[kPoseW];
+        const bool any = W != 0.0;
+        const double mx = any ? a[kPoseMx] / W : 0.0, my = any ? a[kPoseMy] / W : 0.0, mu = any ? a[kPoseMu] / W : 0.0;
+        o[kPoseW] = W;
+        o[kPoseW2] = a[kPoseW2];
+        o[kPoseMx] = (double) px + mx;
+        o[kPoseMy] = (double) py + my;
+        o[kPoseMu] = mu;
+        o[kPoseXX] = a[kPoseXX] - a[kPoseMx] * mx;
+        o[kPoseXY] = a[kPoseXY] - a[kPoseMx] * my;
+        o[kPoseYY] = a[kPoseYY] - a[kPoseMy] * my;
+        o[kPoseXU] = a[kPoseXU] - a[kPoseMx] * mu;
+        o[kPoseYU] = a[kPoseYU] - a[kPoseMy] * mu;
+        o[kPoseUU] = a[kPoseUU] - a[kPoseMu] * mu;
+        for (int q = kPoseC; q < kSums; q++) o[q] = a[q];
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {  // the tile's waves in ascending order (wave v: lanes v * 64 .. of each of the tile's kPoseT strides)
+        PosePart m;
+        for (int q = 0; q < kSums; q++) m.v[q] = sh[0][q];
+        for (int v = 1; v < kWaves; v++) {
+            PosePart b;
+            for (int q = 0; q < kSums; q++) b.v[q] = sh[v][q];
+            pose_merge(m, b);
+        }
+        m.v[kPoseMt] = (double) mb;
+        double *p = A.part + (size_t) blockIdx.x * kPoseFields;
+        for (int q = 0; q < kPoseFields; q++) p[q] = m.v[q];
+    }
+}
+
+// one workgroup of kPoseFinParts threads: each merges its stretch of the tiles' partials in ascending order, the first merges the
+// stretches in ascending order, normalises and writes the kPoseStride outputs
+__global__ void __launch_bounds__(kPoseFinParts) pose_finish_kernel(Buffers B, WeightScratch ws, PoseSummaryArgs A) {
+    __shared__ double sh[kPoseFinParts][kPoseFields];
+    const int part = threadIdx.x;
+    double M = -INFINITY;
+    if (A.logw) {  // the largest log-weight of all tiles
+        for (int t = part; t < A.tiles; t += kPoseFinParts) M = fmax(M, A.part[(size_t) t * kPoseFields + kPoseMt]);
+        for (int d = kWave / 2; d > 0; d >>= 1) M = fmax(M, __shfl_xor(M, d, kWave));
+    }
+    const int per = (A.tiles + kPoseFinParts - 1) / kPoseFinParts, t0 = part * per, t1 = min(A.tiles, t0 + per);
+    PosePart m;
+    for (int q = 0; q < kPoseFields; q++) m.v[q] = 0.0;
+    for (int t = t0; t < t1; t++) {
+        const double *p = A.part + (size_t) t * kPoseFields;
+        PosePart b;
+        for (int q = 0; q < kPoseFields; q++) b.v[q] = p[q];
+        if (A.logw) {
+            const double f = block_scale((float) b.v[kPoseMt], M);
+            b.v[kPoseW] *= f;
+            b.v[kPoseW2] *= f * f;
+            for (int q = kPoseXX; q <= kPoseP22; q++) b.v[q] *= f;
+        }
+        pose_merge(m, b);
+    }
+    for (int q = 0; q < kPoseFields; q++) sh[part][q] = m.v[q];
+    __syncthreads();
+    if (part != 0) return;
+    for (int v = 1; v < kPoseFinParts; v++) {
+        PosePart b;
+        for (int q = 0; q < kPoseFields; q++) b.v[q] = sh[v][q];
+        pose_merge(m, b);
+    }
+    double *o = A.out;
+    const double W = m.v[kPoseW];
+    if (!(W > 0.0) || !(W < INFINITY)) {  // the weights sum to zero or to nothing finite: SLAMGPU_STATUS_DEGENERATE's convention
+        const double nan = __longlong_as_double(0x7ff8000000000000ll);
+        for (int q = 0; q < kPoseStride; q++) o[q] = nan;
+        return;
+    }
+    const Ctrl *ctrl = B.ctrl;
+    const double thp = (double) pose_pivot_heading(B, ws, ctrl->live[B.slot], ctrl->pend[B.slot] != 0);
+    o[0] = m.v[kPoseW2] / (W * W);
+    o[1] = m.v[kPoseMx];
+    o[2] = m.v[kPoseMy];
+    o[3] = thp + m.v[kPoseMu];
+    o[4] = m.v[kPoseC] / W;
+    o[5] = m.v[kPoseS] / W;
+    for (int q = kPoseXX; q <= kPoseUU; q++) o[6 + q - kPoseXX] = m.v[q] / W;
+    for (int q = kPoseP00; q <= kPoseP22; q++) o[12 + q - kPoseP00] = m.v[q] / W;
+}
+
+static void launch_pose_summary(hipStream_t st, const Buffers &B, const WeightScratch &ws, const PoseSummaryArgs &A) {
+    hipLaunchKernelGGL(pose_summary_kernel, dim3(A.tiles), dim3(kBlock), 0, st, B, ws, A);
+}
+static void launch_pose_finish(hipStream_t st, const Buffers &B, const WeightScratch &ws, const PoseSummaryArgs &A) {
+    hipLaunchKernelGGL(pose_finish_kernel, dim3(1), dim3(kPoseFinParts), 0, st, B, ws, A);
+}
+
 static const KernelTable kTable = {launch_update, launch_update_any, launch_update_persist, launch_resample, launch_resample_ref, launch_scan, launch_gather, launch_flatten, launch_identity, launch_decompact, launch_finish, launch_predict, launch_estimate, launch_jacobians, launch_kat, launch_observe, launch_observe_book, launch_associate,
                                    launch_shard_plan, launch_shard_pack, launch_shard_unpack, launch_shard_finish, launch_dist_gather, launch_dist_flags, launch_peek, launch_lmk_box, launch_assoc_grid, launch_assoc_lists, launch_vote_compact,
                                    launch_associate_grid, launch_jacobians_multi, launch_pp_census, launch_pp_resolve, launch_pp_holders,
@@ -5853,7 +6052,7 @@ static const KernelTable kTable = {launch_update, launch_update_any, launch_upda
                                    launch_lists_box, launch_lists_geom, launch_lists_build, launch_lists_walk, launch_excl_radii,
                                    launch_map_summary, launch_map_finish, launch_map_pairs, launch_pp_missed,
                                    launch_path_compose, launch_path_record, launch_path_trace, launch_path_seed, launch_path_push, launch_path_finish,
-                                   launch_pp_mutex};
+                                   launch_pp_mutex, launch_pose_summary, launch_pose_finish};
 
 }  // namespace SLAM_KNS
 

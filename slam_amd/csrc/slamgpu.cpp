@@ -276,6 +276,14 @@ struct slamgpu_ctx {
     int path_org = 0;
     char *path_dev = nullptr;        // staging, push buffers and partials of slamgpu_path_trace / _summary, grown on demand
     size_t path_bytes = 0;
+    // pose posterior (slamgpu_pose_*; kernels.h: PoseSummaryArgs).  pose_cap = 0: the per-step ring is off.  Entries [pose_first, pose_next)
+    // are retained, entry r in ring slot r % pose_cap.  Nothing is allocated and no kernel of it launched until the ring is enabled or
+    // slamgpu_pose_summary is called
+    int32_t pose_cap = 0;
+    int64_t pose_first = 0, pose_next = 0;
+    double *pose_ring_dev = nullptr; // [pose_cap][kPoseStride]
+    double *pose_dev = nullptr;      // [tiles][kPoseFields] partials | [kPoseStride] staging of slamgpu_pose_summary
+    bool pp_stage_ran = false;       // slamgpu_run_particle: a pose entry has already run the stage the last iteration left (pose_append)
     unsigned long long *stamps_dev = nullptr;  // diagnostic (SLAMGPU_STAMPS=1 + libslamgpu_stamps.so): UpdateArgs::stamps
     // persistent small-N step loop (slamgpu_run_observe, kernels.h: PersistArgs)
     bool persist_ok = true;              // SLAMGPU_NO_PERSIST=1 turns it off (diagnostic / tests: the per-step loop)
@@ -805,6 +813,66 @@ int path_append(slamgpu_ctx *c) {
     return 0;
 }
 
+// ---- pose posterior (slamgpu_pose_*; kernels.h: PoseSummaryArgs) ----
+int pose_tiles(const slamgpu_ctx *c) { return (c->B.n + kPoseTile - 1) / kPoseTile; }
+
+int pose_reserve(slamgpu_ctx *c) {
+    if (c->pose_dev) return 0;
+    const size_t total = sizeof(double) * ((size_t) kPoseFields * (size_t) pose_tiles(c) + kPoseStride);
+    hipError_t e = hipMalloc((void **) &c->pose_dev, total);
+    if (e != hipSuccess) {
+        (void) hipGetLastError();
+        c->pose_dev = nullptr;
+        return fail(SLAMGPU_ERR_ALLOC, "hipMalloc(%zu): %s", total, hipGetErrorString(e));
+    }
+    return 0;
+}
+double *pose_staging(const slamgpu_ctx *c) { return c->pose_dev + (size_t) kPoseFields * (size_t) pose_tiles(c); }
+
+// the summary of the set as it stands (the caller has brought it there), into `out_dev`: two launches, nothing else
+int pose_launch(slamgpu_ctx *c, double *out_dev) {
+    PoseSummaryArgs A{};
+    A.tiles = pose_tiles(c);
+    A.logw = c->cfg.log_weights;
+    A.part = c->pose_dev;
+    A.out = out_dev;
+    c->B.slot = c->slot;
+    {
+        Timed t(c, "pose_summary");
+        c->k->pose_summary(c->stream, c->B, c->ws, A);
+    }
+    HIP_TRY(hipGetLastError());
+    {
+        Timed t(c, "pose_finish");
+        c->k->pose_finish(c->stream, c->B, c->ws, A);
+    }
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int pp_dev_stage(slamgpu_ctx *c);
+int pp_dev_flush_predict(slamgpu_ctx *c);
+
+// the summary of the set as slamgpu_peek would show it, into the ring's next slot (a full ring drops its oldest entry).  Between
+// iterations of slamgpu_run_particle the state stays on the device: the stage the last iteration left (only the device knows
+// whether it updated) is run here with the iterations' own kernels, as the next iteration would have run it first thing
+int pose_append(slamgpu_ctx *c) {
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    if (c->pp_on_device) {
+        if (!c->pp_stage_ran) c->pp_stage_open = true;
+        if (int rc = pp_dev_flush_predict(c)) return rc;
+        if (int rc = pp_dev_stage(c)) return rc;
+        c->pp_stage_ran = true;
+    } else {
+        if (int rc = flush_predict(c)) return rc;
+        if (int rc = flush_stages(c)) return rc;
+    }
+    if (int rc = pose_launch(c, c->pose_ring_dev + (size_t) kPoseStride * (size_t) (c->pose_next % c->pose_cap))) return rc;
+    c->pose_next++;
+    if (c->pose_next - c->pose_first > c->pose_cap) c->pose_first = c->pose_next - c->pose_cap;
+    return 0;
+}
+
 int path_identity(slamgpu_ctx *c) {
     Timed t(c, "path_compose");
     c->k->path_compose(c->stream, c->B, c->ws, 0, nullptr, c->path_origin_dev[c->path_org]);
@@ -1086,6 +1154,8 @@ void slamgpu_destroy(slamgpu_ctx *c) {
     if (c->stamps_dev) (void) hipFree(c->stamps_dev);
     if (c->peek_dev) (void) hipFree(c->peek_dev);
     if (c->msum_dev) (void) hipFree(c->msum_dev);
+    if (c->pose_ring_dev) (void) hipFree(c->pose_ring_dev);
+    if (c->pose_dev) (void) hipFree(c->pose_dev);
     if (c->path_rec_dev) (void) hipFree(c->path_rec_dev);
     for (int b = 0; b < 2; b++)
         if (c->path_origin_dev[b]) (void) hipFree(c->path_origin_dev[b]);
@@ -1343,6 +1413,8 @@ int issue_update(slamgpu_ctx *c, UpdateArgs &U, int n_new, int n_rows, bool need
     // path recording: this update's ancestors into origin[].  Only resample_kernel leaves them in keep[] (an inline plan finds them in
     // registers), so the stage runs now, as launches of its own, instead of inside the next update launch
     if (c->path_cap > 0) return path_compose(c);
+    // the pose ring keeps the recorder's rule: the stage runs now, as launches of its own (every entry needs it settled anyway)
+    if (c->pose_cap > 0) return flush_stages(c);
     return 0;
 }
 
@@ -1723,7 +1795,9 @@ int slamgpu_step(slamgpu_ctx *c, const float *controls, int32_t n_controls, cons
     if (int rc = slamgpu_update(c, zf, idf, m, zn, n, R, normals, strata)) return rc;
     if (record_estimate) {
         if (int rc = slamgpu_estimate_async(c)) return rc;
-        if (c->path_cap > 0) return path_append(c);  // record r beside history entry r
+        if (c->path_cap > 0)
+            if (int rc = path_append(c)) return rc;  // record r beside history entry r
+        if (c->pose_cap > 0) return pose_append(c);  // and pose entry r
     }
     return 0;
 }
@@ -1740,7 +1814,9 @@ int slamgpu_step_observe(slamgpu_ctx *c, const float *controls, int32_t n_contro
     if (int rc = do_update_dev(c, xtrue, max_range, R, noise, r1, r2, normals, strata)) return rc;
     if (record_estimate) {
         if (int rc = slamgpu_estimate_async(c)) return rc;
-        if (c->path_cap > 0) return path_append(c);  // record r beside history entry r
+        if (c->path_cap > 0)
+            if (int rc = path_append(c)) return rc;  // record r beside history entry r
+        if (c->pose_cap > 0) return pose_append(c);  // and pose entry r
     }
     return 0;
 }
@@ -1881,7 +1957,8 @@ int slamgpu_run_observe(slamgpu_ctx *c, int32_t K, const int32_t *n_controls, co
     if (int rc = persist_check(c)) return rc;
     // small compact contexts: ONE launch for all K iterations (kernels.h: PersistArgs)
     // (not while the path is recorded: the loop's resampling decisions and ancestors never leave its launch)
-    if (K >= 2 && persist_eligible(c) && max_nc <= kMaxFusedPredict && c->path_cap == 0)
+    // (nor while the pose ring is on: an entry per iteration needs the set between two iterations)
+    if (K >= 2 && persist_eligible(c) && max_nc <= kMaxFusedPredict && c->path_cap == 0 && c->pose_cap == 0)
         return run_observe_persist(c, K, n_controls, controls, Q, dt, xtrue, max_range, R, noise);
     size_t row = 0;
     for (int32_t k = 0; k < K; k++) {
@@ -4051,6 +4128,7 @@ int pp_push(slamgpu_ctx *c, int census_cap) {
     if (c->retired_stale)
         if (int rc = retired_upload(c)) return rc;
     c->pp_stage_open = true;
+    c->pp_stage_ran = false;
     c->pp_prev_hist = nullptr;
     c->scan_ready = false;
     c->B.erow = c->erow_dev;
@@ -4103,7 +4181,8 @@ int pp_pull(slamgpu_ctx *c) {
         if (int rc = pp_grow_tab(c, st.census_cap)) return rc;
     c->pp_census_done = false;
     // the last iteration's update (if it made one) leaves its resampling stage outstanding, as issue_update does
-    c->unplanned.has = st.updated != 0;
+    c->unplanned.has = st.updated != 0 && !c->pp_stage_ran;  // (unless a pose entry has run it since: pose_append)
+    c->pp_stage_ran = false;
     c->unplanned.par = c->pp_prev_par;
     c->unplanned.step = st.step;
     c->unplanned.nf = c->nf;
@@ -4164,7 +4243,8 @@ int pp_dev_flush_predict(slamgpu_ctx *c) {
 // (bound >= 0: SLAMGPU_ASSOC_LISTS, with the host's bound on this iteration's observations; box_all: refresh every slot's box first)
 int pp_dev_iteration(slamgpu_ctx *c, int32_t nc, const float *controls, const float Q[4], float dt, const float xtrue[3], float max_range,
                      const float R[4], int32_t noise, const slamgpu_particle_assoc *opt, int need, int bound, bool box_all) {
-    c->pp_stage_open = true;  // (the previous iteration may have updated: only the device knows)
+    c->pp_stage_open = !c->pp_stage_ran;  // (the previous iteration may have updated: only the device knows -- unless a pose entry has run its stage)
+    c->pp_stage_ran = false;
     for (int k = 0; k < nc; k++) {
         const PredictArgs &P = c->pending;  // (slamgpu_predict's own flush would go through the host's tables: flush here instead)
         if (P.nsteps > 0 && (P.dt != dt || memcmp(P.Q, Q, sizeof P.Q) != 0 || P.nsteps == kMaxFusedPredict))
@@ -4380,6 +4460,11 @@ int slamgpu_run_particle(slamgpu_ctx *c, int32_t K, const int32_t *n_controls, c
             std::string why = slamgpu_last_error();
             return fail(rc, "slamgpu_run_particle: iteration %d of %d: %s", (int) k, (int) K, why.c_str());
         }
+        if (c->pose_cap > 0)  // pose entry r beside history entry r
+            if (int rc = pose_append(c)) {
+                std::string why = slamgpu_last_error();
+                return fail(rc, "slamgpu_run_particle: iteration %d of %d: %s", (int) k, (int) K, why.c_str());
+            }
         row += (size_t) nc;
     }
     return 0;
@@ -4957,6 +5042,85 @@ int slamgpu_map_pairs(slamgpu_ctx *c, const int32_t *pairs, int32_t count, doubl
     HIP_TRY(hipMemcpyAsync(out, c->msum_dev + o_out, sizeof(double) * kMapStride * M, hipMemcpyDeviceToHost, c->stream));
     if (both) HIP_TRY(hipMemcpyAsync(both, c->msum_dev + o_both, sizeof(int32_t) * M, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+int slamgpu_pose_summary(slamgpu_ctx *c, double *out) {
+    if (int rc = check_ctx(c)) return rc;
+    if (c->dist || c->cfg.n_particles_global != c->cfg.n_particles) return fail(SLAMGPU_ERR_INVALID, "slamgpu_pose_summary: single contexts only");
+    if (!out) return fail(SLAMGPU_ERR_INVALID, "slamgpu_pose_summary: null output");
+    static_assert(SLAMGPU_POSE_STRIDE == kPoseStride, "public / device summary layout");
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    // the particle set slamgpu_peek shows, and nothing more than it does to get there
+    if (int rc = flush_predict(c)) return rc;
+    if (int rc = flush_stages(c)) return rc;
+    if (int rc = pose_reserve(c)) return rc;
+    if (int rc = pose_launch(c, pose_staging(c))) return rc;
+    double h[kPoseStride];
+    HIP_TRY(hipMemcpyAsync(h, pose_staging(c), sizeof h, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    memcpy(out, h, sizeof h);
+    return 0;
+}
+
+int slamgpu_pose_history_enable(slamgpu_ctx *c, int32_t capacity) {
+    if (int rc = check_ctx(c)) return rc;
+    if (c->dist || c->cfg.n_particles_global != c->cfg.n_particles) return fail(SLAMGPU_ERR_INVALID, "slamgpu_pose_history_enable: single contexts only");
+    if (capacity < 0) return fail(SLAMGPU_ERR_INVALID, "slamgpu_pose_history_enable: capacity %d", capacity);
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    // the new ring first: a refused call leaves the setting as it was
+    double *ring = nullptr;
+    if (capacity > 0) {
+        if (int rc = pose_reserve(c)) return rc;
+        const size_t bytes = sizeof(double) * kPoseStride * (size_t) capacity;
+        hipError_t e = hipMalloc((void **) &ring, bytes);
+        if (e != hipSuccess) {
+            (void) hipGetLastError();
+            return fail(SLAMGPU_ERR_ALLOC, "slamgpu_pose_history_enable: %d entries (%zu bytes): %s", capacity, bytes, hipGetErrorString(e));
+        }
+    }
+    if (c->pose_ring_dev) {
+        HIP_TRY(hipStreamSynchronize(c->stream));  // (launches in flight may still write the old ring)
+        (void) hipFree(c->pose_ring_dev);
+    }
+    c->pose_ring_dev = ring;
+    c->pose_cap = capacity;
+    c->pose_first = c->pose_next = 0;
+    return 0;
+}
+
+int slamgpu_pose_history_record(slamgpu_ctx *c) {
+    if (int rc = check_ctx(c)) return rc;
+    if (c->pose_cap == 0) return fail(SLAMGPU_ERR_INVALID, "slamgpu_pose_history_record: the ring is off (slamgpu_pose_history_enable)");
+    return pose_append(c);
+}
+
+int slamgpu_pose_history_info(slamgpu_ctx *c, int64_t *first, int64_t *next, int32_t *capacity) {
+    if (int rc = check_ctx(c)) return rc;
+    if (first) *first = c->pose_first;
+    if (next) *next = c->pose_next;
+    if (capacity) *capacity = c->pose_cap;
+    return 0;
+}
+
+int slamgpu_pose_history_fetch(slamgpu_ctx *c, int64_t first, int32_t count, double *out) {
+    if (int rc = check_ctx(c)) return rc;
+    if (count < 0 || first < c->pose_first || first + count > c->pose_next)
+        return fail(SLAMGPU_ERR_INVALID, "slamgpu_pose_history_fetch: entries [%lld, %lld + %lld) outside the retained [%lld, %lld)", (long long) first,
+                    (long long) first, (long long) count, (long long) c->pose_first, (long long) c->pose_next);
+    if (count == 0) return 0;
+    if (!out) return fail(SLAMGPU_ERR_INVALID, "slamgpu_pose_history_fetch: null output");
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    std::vector<double> h((size_t) kPoseStride * (size_t) count);
+    // at most two stretches of the ring
+    const int64_t at = first % c->pose_cap, n0 = std::min<int64_t>(count, c->pose_cap - at);
+    HIP_TRY(hipMemcpyAsync(h.data(), c->pose_ring_dev + (size_t) kPoseStride * (size_t) at, sizeof(double) * kPoseStride * (size_t) n0, hipMemcpyDeviceToHost,
+                           c->stream));
+    if (n0 < count)
+        HIP_TRY(hipMemcpyAsync(h.data() + (size_t) kPoseStride * (size_t) n0, c->pose_ring_dev, sizeof(double) * kPoseStride * (size_t) (count - n0),
+                               hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    memcpy(out, h.data(), sizeof(double) * h.size());
     return 0;
 }
 

@@ -15,9 +15,11 @@ DECLARED_SYMBOLS = [
     "slamhost_synthetic_landmarks", "slamhost_write_map", "slamhost_ekf_create", "slamhost_ekf_destroy", "slamhost_ekf_step",
     "slamhost_ekf_state", "slamhost_plot_open", "slamhost_plot_close", "slamhost_plot_xy", "slamhost_plot_matrix",
     "slamhost_plot_doubles", "slamhost_plot_car_size", "slamhost_plot_u32", "slamhost_plot_cmd", "slamhost_plot_name",
-    "slamhost_map_candidates", "slamhost_map_merge",
+    "slamhost_map_candidates", "slamhost_map_merge", "slamhost_pose_nees",
 ]
 MAP_STRIDE = 9  # SLAMGPU_MAP_STRIDE
+POSE_STRIDE = 18  # SLAMGPU_POSE_STRIDE
+NEES_CHI2_95 = 7.8147  # the 95 % point of chi^2 with 3 degrees of freedom
 
 
 class HostConf(C.Structure):
@@ -86,6 +88,8 @@ def load_library():
         L.slamhost_map_candidates.argtypes = [C.c_void_p, C.c_int32, C.c_double, C.c_void_p, C.c_int64]
         L.slamhost_map_merge.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_double, C.c_double, C.c_void_p, C.c_void_p,
                                          C.POINTER(C.c_int32)]
+        L.slamhost_pose_nees.restype = C.c_int32
+        L.slamhost_pose_nees.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
         _lib = L
     return _lib
 
@@ -158,6 +162,22 @@ def map_merge(summary, pairs, joint, radius=1.0, cohold=0.1):
         raise ValueError("slamhost_map_merge: bad arguments")
     m = merged[:n.value].copy()
     return dict(cluster=cluster, merged=m, share=m[:, 0].copy(), mean=m[:, 1:3].copy(), scatter=m[:, 3:6].copy(), pf=m[:, 6:9].copy())
+
+
+def pose_nees(summary, xtrue):
+    """slamhost_pose_nees: the NEES of pose summaries (SlamGpu.pose_summary / pose_history_fetch: [count, 18] or one [18]) against the
+    true poses xtrue [count, 3].  Returns (nees[count], err[count, 3], bad): NaN where P = scatter + mean Pv is not positive definite or
+    the summary is NaN, and how many such entries there are"""
+    t = np.ascontiguousarray(summary, np.float64).reshape(-1, POSE_STRIDE)
+    x = np.ascontiguousarray(xtrue, np.float32).reshape(-1, 3)
+    if len(t) != len(x):
+        raise ValueError("pose_nees: %d summaries, %d true poses" % (len(t), len(x)))
+    nees = np.zeros(len(t), np.float64)
+    err = np.zeros((len(t), 3), np.float64)
+    bad = load_library().slamhost_pose_nees(_p(t), len(t), _p(x), _p(nees), _p(err))
+    if bad < 0:
+        raise ValueError("slamhost_pose_nees: bad arguments")
+    return nees, err, int(bad)
 
 
 class HostSim:
