@@ -1384,17 +1384,20 @@ __global__ void __launch_bounds__(kBlock) update_kernel(const float *__restrict_
 // tape, the front end's state, the log-weight arithmetic, Ctrl.pend -- is neither loaded nor kept in scalar registers.  Same leading
 // arguments and argument layout as update_kernel, same operations on the same values: bit-identical (tests/test_gpu_special.py).
 // (A kernel of its own, not a further template parameter of update_kernel: the general instantiations keep their names.)
-template <int SPEC>
+// WPAR: the weight scratch's parity (WeightScratch::wpar), which the launcher has just written: every ws.X[parity] of the step text is
+// then one fixed kernel-argument offset, read with the head's other scalar loads (update_step.inl: WS_AT).
+template <int SPEC, int WPAR>
 __global__ void __launch_bounds__(kBlock) update_kernel_special(const float *__restrict__ h_tot, Ctrl *h_ctrl, const FrontState *h_front, int h_nb,
                                                                  int h_slot, int h_grid, int h_flags, Buffers B, PredictArgs PA, UpdateArgs U,
                                                                  RngArgs rng, WeightScratch ws) {
     static_assert(SPEC > 0 && SPEC < kUpdateSpecCount, "kernels.h: kUpdateSpecs");
+    static_assert(WPAR == 0 || WPAR == 1, "WeightScratch::wpar");
     constexpr int METHOD = 2, MODE = 0;
     constexpr bool BIG = false, PERSIST = false, PP = false;
     [[maybe_unused]] const PerParticle ppa{};
     const PersistStep *const qe = nullptr;
     StepCarry carry;  // (unused by a per-step launch)
-#define STEP_WPAR ws.wpar
+#define STEP_WPAR WPAR
 #define STEP_PLAN kUpdateSpecs[SPEC].plan
 #define STEP_FRONT U.front
 #include "update_step.inl"
@@ -4263,13 +4266,13 @@ static int launch_update_any(hipStream_t st, const Buffers &B, const PredictArgs
                                PA.use_heading != 0, PA.add_noise != 0, U.do_resample != 0};
     const int spec = update_special(U.method, U.arrivals, U.big != nullptr, pp, false, no_special, update_mode_bits(modes));
     if (spec != 0) {
-        dispatch<kUpdateSpecCount>(
-            [&](auto sp) {
+        dispatch<kUpdateSpecCount, 2>(
+            [&](auto sp, auto wp) {
                 if constexpr (sp != 0)
-                    hipLaunchKernelGGL((update_kernel_special<sp>), dim3(grid), dim3(kBlock), lds, st, h_tot, B.ctrl, U.front.state_in, ws.nblocks, B.slot,
+                    hipLaunchKernelGGL((update_kernel_special<sp, wp>), dim3(grid), dim3(kBlock), lds, st, h_tot, B.ctrl, U.front.state_in, ws.nblocks, B.slot,
                                        grid, h_flags, B, PA, U, rng, ws);
             },
-            spec);
+            spec, ws.wpar);
         return spec;
     }
     dispatch<2, 3, 2, 2, 2>(

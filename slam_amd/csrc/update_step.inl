@@ -2,7 +2,7 @@
 // are used in place: taking references to them would make the compiler keep private copies of the argument structs) and by
 // persist_step (one iteration of the persistent loop).  Names the including function provides: METHOD, MODE, BIG, PERSIST,
 // PP (constants); h_tot, h_ctrl, h_front, h_nb, h_slot, h_grid, h_flags, B, PA, U, rng, ws, ppa (update_kernel's parameters, or what stands
-// in for them in an iteration); the macros STEP_WPAR (ws.wpar), STEP_PLAN (U.plan_inline != 0) and STEP_FRONT (U.front), which a per-step
+// in for them in an iteration); the macros STEP_WPAR (ws.wpar; update_kernel_special: its template parameter WPAR), STEP_PLAN (U.plan_inline != 0) and STEP_FRONT (U.front), which a per-step
 // launch reads in place (a local copy of each costs the distributed variants a scalar register they do not have); qe (LDS copy of the iteration's queue
 // entry, PERSIST only); carry (StepCarry, PERSIST only); SPEC (kernels.h: UpdateModes; 0 everywhere but in update_kernel's specialised
 // instantiations: every `SPECIAL ? SM.x : <run-time test>` below is then the run-time test it has always been).
@@ -11,6 +11,22 @@
     [[maybe_unused]] constexpr UpdateModes SM = kUpdateSpecs[SPEC];
     static_assert(!SPECIAL || (!PERSIST && !BIG && MODE == 0 && !PP), "specialised: update_kernel<2, 0, false> only");
     static_assert(!PERSIST || (MODE == 0 && !BIG), "the persistent loop: compact single contexts");
+// The weight scratch's parity tables (ws.lcum, ws.blk_w, ws.est_part, ws.scan) are SELECTED, not indexed, like the pose buffers below:
+// `ws` is a by-value kernel argument, and a run-time index into one of its pointer tables is a load from the kernel-argument segment
+// in memory -- a VECTOR load where the index sits in a vector register, behind an s_waitcnt vmcnt(0) that waits for every store of
+// the step as well (two such round trips, one after the other, stood behind the step's last barrier).  A select reads both entries
+// with the head's other scalar loads; in update_kernel_special STEP_WPAR is a template parameter and the select folds to one fixed
+// kernel-argument offset.  (The persistent loop keeps its index: its parity lives in a scalar register and changes per iteration.;
+// so does the distributed variants' push of the block totals into the peers' tables, B.peers[h].gtot[parity]: the collectives' own text.)
+#define WS_AT(X, P) (PERSIST ? ws.X[P] : ((P) ? ws.X[1] : ws.X[0]))
+// tiles of this context's weight scratch: the head argument where it is the same number (single contexts, per-step launches)
+#define WS_NB ((MODE == 0 && !PERSIST) ? nb : ws.nblocks)
+// what this step writes: its own parity's weight prefix and block totals, the other parity's estimate partials (specialised: pinned at the head)
+// (as global-memory pointers by type: a pointer that has been through the pin is no longer known to come from the kernel arguments,
+// and a store through it would be a flat one, which every later wait for LDS waits for as well)
+#define WS_LCUM ((__attribute__((address_space(1))) float *) (SPECIAL ? t_lcum : WS_AT(lcum, STEP_WPAR)))
+#define WS_BLK ((__attribute__((address_space(1))) float *) (SPECIAL ? t_blk : WS_AT(blk_w, STEP_WPAR)))
+#define WS_EST ((__attribute__((address_space(1))) double *) (SPECIAL ? t_est : WS_AT(est_part, STEP_WPAR ^ 1)))
     const int bid = PERSIST ? (int) blockIdx.x / kPersistStride : (int) blockIdx.x;  // this workgroup's number among those that work
     __shared__ float sh_w[kBlock / kWave], sh_w2[kBlock / kWave];
     // landmarks re-observed this step, staged between the proposal pass and the likelihood/feature-update pass
@@ -204,6 +220,20 @@
     (void) ctl;  // (strict build: the predict loop reads PredictArgs itself)
     const int cur = PERSIST ? carry.cur : h_ctrl->live[h_slot];  // ... and the Ctrl words
     const bool pend_word = PERSIST ? carry.pend_word : h_ctrl->pend[h_slot] != 0;
+    // specialised launches: the three parity pointers the step stores through at its very end, each a fixed kernel-argument offset, read
+    // HERE with the head arguments and pinned -- in VECTOR registers: the step has some to spare and no scalar ones, and its last stores
+    // take their addresses from vector registers anyway -- (left alone, the compiler reads each where it is used: three scalar
+    // loads, each waited for, one after the other behind the last barrier).
+    // (Behind the Ctrl words, not at the kernel's entry: the compiler takes a volatile asm statement for a store, and a uniform load
+    // behind a possible store is a VECTOR load -- the Ctrl words then waited for the scan's loads and the packet's as well.)
+    [[maybe_unused]] float *t_lcum = nullptr, *t_blk = nullptr;
+    [[maybe_unused]] double *t_est = nullptr;
+    if constexpr (SPECIAL) {
+        t_lcum = WS_AT(lcum, STEP_WPAR);
+        t_blk = WS_AT(blk_w, STEP_WPAR);
+        t_est = WS_AT(est_part, STEP_WPAR ^ 1);
+        asm volatile("" : "+v"(t_lcum), "+v"(t_blk), "+v"(t_est));
+    }
     if constexpr (!BIG && MODE == 0 && !PERSIST) {
         // front-end launches: the packet is worked out here, while the scan's loads and the Ctrl words are in flight
         if (front && bid < h_nb) {
@@ -237,6 +267,12 @@
         const int x = bt & 7, j = bt >> 3, q = nb >> 3, r = nb & 7;
         bt = x < r ? x * (q + 1) + j : r * (q + 1) + (x - r) * q + j;
     }
+    // specialised launches: the scan's totals are first waited for HERE, behind every other request of the head.  Left alone, the
+    // compiler converts the second pair of totals to double inside the branch of scan_issue that loads them (the scan below needs
+    // them as doubles under the same condition), so every wave waited for the totals before it had requested the packet, the queued
+    // controls and the Ctrl words: two trips at the head of every launch, one behind the other.  Pinned as the floats they arrive
+    // as, the conversion stays below.  (Measured: 12.1-12.2 -> 11.84-11.91 us per step at config 3, profiles/parity_pointers.txt.)
+    if constexpr (SPECIAL) asm volatile("" : "+v"(scl.tv0), "+v"(scl.qv0), "+v"(scl.tv1), "+v"(scl.qv1));
     SLAM_STAMP(1);  // Ctrl words arrived
     // Where does particle i of the set this update works on come from?
     //   plan_inline: the resampling stage of the previous update has not run: every block redoes its scan of the block
@@ -248,7 +284,7 @@
     double W = 1.0, Mx = 0.0;
     // large contexts: the prefix comes from scan_kernel (same function, same association, run once) instead of being
     // redone by every block -- O(N^2 / 65 536) otherwise
-    const double *offp = h_scan_global ? ws.scan[STEP_WPAR ^ 1] : off;
+    const double *offp = h_scan_global ? WS_AT(scan, STEP_WPAR ^ 1) : off;
     if (h_plan && !helper) {
         double Q;
         if (h_scan_global) {
@@ -269,8 +305,8 @@
             ctrl->neff = neff;
             ctrl->resampled = pend ? 1 : 0;
             ctrl->status = weight_status(W, Q);
-            ws.est_part[STEP_WPAR ^ 1][4 * (size_t) nb] = (double) neff;  // travels with the partials into the history
-            ws.est_part[STEP_WPAR ^ 1][4 * (size_t) nb + 1] = (double) ((pend ? 1 : 0) | (weight_status(W, Q) << 1));
+            WS_EST[4 * (size_t) nb] = (double) neff;  // travels with the partials into the history
+            WS_EST[4 * (size_t) nb + 1] = (double) ((pend ? 1 : 0) | (weight_status(W, Q) << 1));
         }
         if (!(PERSIST && !logw)) __syncthreads();
     }
@@ -295,13 +331,13 @@
         const double target = valid ? (double) (PERSIST ? carry.strat : stratum_prev(rng, gk)) * W : 0.0;
         const int64_t ng = DIST ? rng.n_global : (int64_t) B.n;
         if (PERSIST && pre_win)
-            return (int) find_ancestor_win<true, true, true>(target, valid, (int) (gk >> 8), offp, nbg, win, ws.lcum[STEP_WPAR ^ 1], nb, ng,
-                                                       logw ? ws.blk_w[STEP_WPAR ^ 1] + 2 * nb : nullptr, Mx, nullptr, STEP_WPAR ^ 1);
+            return (int) find_ancestor_win<true, true, true>(target, valid, (int) (gk >> 8), offp, nbg, win, WS_AT(lcum, STEP_WPAR ^ 1), nb, ng,
+                                                       logw ? WS_AT(blk_w, STEP_WPAR ^ 1) + 2 * nb : nullptr, Mx, nullptr, STEP_WPAR ^ 1);
         // (the typed LDS pointer for the block prefix -- OFFL -- only in the persistent loop: 8.52 -> 8.29 us per iteration at config
         // 2; in the per-step kernels, which must keep the global-memory prefix of the largest contexts as well, the two copies of
         // the search cost more than the flat loads: config 3 14.02 -> 14.14 us per step, 10^6 particles 81.3 -> 85.3, same box)
-        return (int) find_ancestor_win<false, PERSIST, PERSIST>(target, valid, (int) (gk >> 8), offp, nbg, win, ws.lcum[STEP_WPAR ^ 1], nb, ng,
-                                                                (!DIST && logw) ? ws.blk_w[STEP_WPAR ^ 1] + 2 * nb : nullptr, Mx, DIST ? B.peers : nullptr, STEP_WPAR ^ 1);
+        return (int) find_ancestor_win<false, PERSIST, PERSIST>(target, valid, (int) (gk >> 8), offp, nbg, win, WS_AT(lcum, STEP_WPAR ^ 1), nb, ng,
+                                                                (!DIST && logw) ? WS_AT(blk_w, STEP_WPAR ^ 1) + 2 * nb : nullptr, Mx, DIST ? B.peers : nullptr, STEP_WPAR ^ 1);
     };
     if (bid >= nb) {
         // ---- helper blocks ---------------------------------------------------------------------------------
@@ -1201,7 +1237,7 @@
     auto est_out = [&]() {
         if (STEP_PLAN && threadIdx.x == 0) {
             const EstItem e = combine_waves_est(ei_prev, sh_est);
-            double *p = ws.est_part[STEP_WPAR ^ 1] + (size_t) bt * 4;
+            auto *p = WS_EST + (size_t) bt * 4;
             p[0] = e.sx;
             p[1] = e.sy;
             p[2] = (double) e.th;
@@ -1218,7 +1254,7 @@
         __syncthreads();
         mb = fmaxf(fmaxf(sh_w[0], sh_w[1]), fmaxf(sh_w[2], sh_w[3]));
         __syncthreads();
-        if (threadIdx.x == 0) ws.blk_w[STEP_WPAR][2 * ws.nblocks + bt] = mb;
+        if (threadIdx.x == 0) WS_BLK[2 * WS_NB + bt] = mb;
         w = (w == -INFINITY) ? 0.0f : expf(w - mb);  // NaN log-weights stay NaN and are flagged by the plan (status)
     }
     // in-block inclusive prefix of w; block totals of w and of w^2 (fixed association: deterministic).  The sum of squares
@@ -1239,7 +1275,7 @@
 #pragma unroll
     for (int k = 0; k < kBlock / kWave; k++)
         if (k < wv) base += sh_w[k];
-    __builtin_nontemporal_store(base + s, &ws.lcum[STEP_WPAR][i]);
+    __builtin_nontemporal_store(base + s, &WS_LCUM[i]);
     if (threadIdx.x == kBlock - 1) {
         const float T = base + s;
         float q = 0.0f;
@@ -1250,8 +1286,8 @@
                 q += sh_w2[k] * (f * f);
             }
         }
-        ws.blk_w[STEP_WPAR][bt] = T;
-        ws.blk_w[STEP_WPAR][ws.nblocks + bt] = q;
+        WS_BLK[bt] = T;
+        WS_BLK[WS_NB + bt] = q;
         if (DIST && U.push_totals) {
             // push collective: this block's totals straight into every shard's table, shard-major [shard][w(nb) | q(nb)]
             // (visible to the peers' next launch: the flag handshake that follows this launch orders them)
@@ -1264,3 +1300,8 @@
         }
     }
     SLAM_STAMP(9);  // weight prefix + totals written: end of the block
+#undef WS_AT
+#undef WS_NB
+#undef WS_LCUM
+#undef WS_BLK
+#undef WS_EST
