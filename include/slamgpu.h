@@ -670,6 +670,67 @@ int slamgpu_pose_history_enable(slamgpu_ctx *ctx, int32_t capacity);
 int slamgpu_pose_history_record(slamgpu_ctx *ctx);
 int slamgpu_pose_history_info(slamgpu_ctx *ctx, int64_t *first, int64_t *next, int32_t *capacity);
 int slamgpu_pose_history_fetch(slamgpu_ctx *ctx, int64_t first, int32_t count, double *out);
+
+/* ---- innovation posterior: per-observation moments and NIS, a consistency test that needs no ground truth -------------------
+ * For every re-observed landmark of a packet: how far the measurement fell from what the filter AS A WHOLE predicted, and the
+ * covariance the filter itself gives that prediction.  The caller invokes it after the predicts of a step and before that step's
+ * update, with the packet it is about to hand to slamgpu_update: zf[2q], zf[2q + 1] the range and bearing of observation q, idf[q] its
+ * landmark slot, R the measurement noise (row-major 2 x 2; R[1] is not read).  "The set" and the weights w^_i are exactly
+ * slamgpu_map_summary's: queued predicts flushed, the outstanding resampling stage run, a pending gather read through its ancestors
+ * with weight 1/N, records through the genealogy, log-weights as exp(l - max l), normalised over ALL N particles.
+ * For observation q, slot l = idf[q] and particle i the float32 pose (x, y, theta), record (xf, p00, p10, p11), z and R are promoted
+ * to double and, in double and in this order (the model of the tests evaluates the same formula),
+ *     dx = xf.x - x;  dy = xf.y - y;  d2 = dx dx + dy dy;  d = sqrt(d2)
+ *     v0 = z_r - d;   v1 = IEEE remainder(z_b - (atan2(dy, dx) - theta), 2 pi)       (2 pi the double nearest to it)
+ *     H  = [[dx / d, dy / d], [-dy / d2, dx / d2]]
+ *     S  = H Pf H^T + (R[0], R[2], R[3])                                              (s00, s10, s11)
+ *     nis = (s11 v0^2 - 2 s10 v0 v1 + s00 v1^2) / (s00 s11 - s10^2)
+ * H_q is the set of particles that hold slot l (record not absent) with d2 > 0.  out[q][SLAMGPU_INNOV_STRIDE] is
+ *     [0]       share s = sum_{H_q} w^_i
+ *     [1..2]    mean innovation v- = sum w^ v / s
+ *     [3..5]    scatter sum w^ (v - v-)(v - v-)^T / s: rr, rb, bb -- the pose (and map) uncertainty as the measurement sees it
+ *     [6..8]    mean sum w^ S_i / s: s00, s10, s11 -- the innovation covariance INSIDE a particle
+ *     [9]       mean per-particle NIS sum w^ nis_i / s
+ * and holders[q] (may be NULL) = |H_q|, exact.  A particle's S carries no pose uncertainty, so [9] alone is biased; [3..5] + [6..8]
+ * is the covariance of the filter's predicted-measurement mixture (the same split as scatter + mean Pf in the map summary and
+ * scatter + mean Pv in the pose summary), and slamhost_innovation_nis turns an entry into the mixture's NIS, chi-square with 2
+ * degrees of freedom for a consistent filter.  H_q empty: share 0, holders 0, entries 1..9 NaN.  Weights that sum to zero or to
+ * nothing finite: every double NaN, the call returns 0, holders still exact.  Without SLAMGPU_FLAG_PARTICLE_MAPS every share is 1,
+ * unless a landmark sits exactly on a pose.  The same slot may appear more than once; retired slots are reported like any other.
+ * Sums are in double, in a fixed order, about a pivot inside the holders' innovations, without floating-point atomics: the same
+ * state gives the same bits on every call, under a pending gather as well as after slamgpu_download has settled it, and an
+ * observation's result does not depend on its place in the packet, on what else the packet holds, or on how the call cuts it into
+ * chunks.  Read-only like slamgpu_peek: the state the next step works on is bit for bit what it would have been without the call.
+ * SLAMGPU_ERR_INVALID, outputs untouched: a slot outside [0, slamgpu_num_landmarks), m < 0, NULL zf / idf / R / out with m > 0, a
+ * distributed or shard context.  m == 0 does nothing.  Synchronises. */
+#define SLAMGPU_INNOV_STRIDE 10
+int slamgpu_innovation_summary(slamgpu_ctx *ctx, const float *zf, const int32_t *idf, int32_t m, const float R[4],
+                               double *out /* [m][SLAMGPU_INNOV_STRIDE] */, int32_t *holders /* [m], may be NULL */);
+/* The same entries kept on the device: a ring counted in OBSERVATION entries (m varies from step to step), not in steps.  Entries
+ * are numbered from 0 when the ring is enabled and never renumbered; entries [first, next) are retained; a full ring drops its
+ * oldest entries and never refuses a step.  slamgpu_innovation_history_enable: capacity > 0 (in entries) starts or restarts (entries
+ * dropped, numbering and the record count from 0); 0 stops and frees; SLAMGPU_ERR_ALLOC leaves the setting as it was.
+ * slamgpu_innovation_record appends the m entries of the set as it stands now, written by the finishing kernel straight into ring
+ * slots (next + q) % capacity: enqueued, no synchronisation.  Every entry carries two tags: `record`, the number of the
+ * slamgpu_innovation_record call since the enable, counted from 0, and `slot` = idf[q].  m == 0 appends nothing and still counts as a
+ * record; m > capacity: SLAMGPU_ERR_CAPACITY, nothing appended and no record counted; the ring off, or an argument
+ * slamgpu_innovation_summary refuses: SLAMGPU_ERR_INVALID, likewise.  slamgpu_innovation_history_info: any pointer may be NULL;
+ * records = calls counted so far.  slamgpu_innovation_history_fetch: entries [first, first + count) into
+ * out[count][SLAMGPU_INNOV_STRIDE], record[count], slot[count] (each may be NULL), non-consuming; synchronises; entries outside the
+ * retained range or a negative count: SLAMGPU_ERR_INVALID, outputs untouched; count == 0 does nothing.
+ * slamgpu_step records by itself while the ring is on, between its predicts and its update, with its own zf / idf / m / R (a packet
+ * larger than the ring: SLAMGPU_ERR_CAPACITY before anything of the step is applied); callers
+ * of slamgpu_predict + slamgpu_update call slamgpu_innovation_record themselves, before the update.  slamgpu_step_observe,
+ * slamgpu_run_observe and slamgpu_run_particle are NOT recorded: their packets are made on the device and never exist on the host.
+ * While the ring is on the path recorder's rule holds for slamgpu_step: the outstanding resampling stage is run and the predicts
+ * are flushed before the record, as launches of their own.  The two routes are bit for bit equivalent: every pose, record, weight,
+ * history entry and ancestor of a run is that of the same run with the ring off.  slamgpu_upload keeps the retained entries.
+ * Single contexts only.  With the ring never enabled and slamgpu_innovation_summary never called nothing is allocated and no kernel
+ * of it is launched.  What it costs: DESIGN.md section 7f. */
+int slamgpu_innovation_history_enable(slamgpu_ctx *ctx, int32_t capacity);
+int slamgpu_innovation_record(slamgpu_ctx *ctx, const float *zf, const int32_t *idf, int32_t m, const float R[4]);
+int slamgpu_innovation_history_info(slamgpu_ctx *ctx, int64_t *first, int64_t *next, int32_t *capacity, int64_t *records);
+int slamgpu_innovation_history_fetch(slamgpu_ctx *ctx, int64_t first, int32_t count, double *out, int32_t *record, int32_t *slot);
 int slamgpu_upload(slamgpu_ctx *ctx, int32_t nf, const float *xv, const float *Pv9, const float *w, const float *xf,
                    const float *Pf4);
 int slamgpu_sync(slamgpu_ctx *ctx);

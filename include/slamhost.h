@@ -118,6 +118,18 @@ int slamhost_map_merge(const double *summary, int32_t slots, const int32_t *pair
  * count, a NULL array that is needed). */
 int32_t slamhost_pose_nees(const double *summary, int32_t count, const float *xtrue /*3 per entry*/, double *nees, double *err /*3 per entry, may be NULL*/);
 
+/* The innovation test without ground truth (Bar-Shalom's NIS test): the normalised innovation squared of the filter's predicted-
+ * measurement mixture, for `count` entries of slamgpu_innovation_summary / slamgpu_innovation_history_fetch (entries[count][10]).
+ * Per entry, in double:
+ *     e   = (out[1], out[2])                                   the mean innovation
+ *     P   = scatter + mean S, 2 x 2 symmetric: (out[3..5]) + (out[6..8]) in the order 00, 10, 11
+ *     NIS = e^T P^-1 e through the Cholesky factor of P
+ * nis[k] is NaN for an entry whose share out[0] is 0 (nobody holds the slot), that holds a NaN anywhere (degenerate weights), or
+ * whose P is not positive definite; the return value counts such entries.  A consistent filter's NIS has mean 2 and lies below
+ * 5.9915 -- -2 ln 0.05, the 95 % point of chi^2 with 2 degrees of freedom -- 95 % of the time; out[9], the mean of the particles' own
+ * NIS, leaves the pose uncertainty out of S and reads too large.  -1: bad arguments (a negative count, a NULL array with count > 0). */
+int32_t slamhost_innovation_nis(const double *entries, int32_t count, double *nis);
+
 void slamhost_draw_normals(int32_t count, int32_t dim, float *out); /* count x randn(dim,1): dim+1 rand() each */
 int32_t slamhost_draw_strata(int32_t N, float *out);                /* returns the reference's strata count (== N when supported) */
 double slamhost_unif_rand(void);                                    /* unifRand (core.cpp:775) */

@@ -34,10 +34,13 @@ DECLARED_SYMBOLS = [
     "slamgpu_path_enable", "slamgpu_path_record", "slamgpu_path_info", "slamgpu_path_fetch", "slamgpu_path_trace", "slamgpu_path_summary",
     "slamgpu_pose_summary", "slamgpu_pose_history_enable", "slamgpu_pose_history_record", "slamgpu_pose_history_info",
     "slamgpu_pose_history_fetch",
+    "slamgpu_innovation_summary", "slamgpu_innovation_history_enable", "slamgpu_innovation_record", "slamgpu_innovation_history_info",
+    "slamgpu_innovation_history_fetch",
 ]
 MAP_STRIDE = 9  # SLAMGPU_MAP_STRIDE
 PATH_STRIDE = 7  # SLAMGPU_PATH_STRIDE
 POSE_STRIDE = 18  # SLAMGPU_POSE_STRIDE
+INNOV_STRIDE = 10  # SLAMGPU_INNOV_STRIDE
 ASSOC_AUTO, ASSOC_EXHAUSTIVE, ASSOC_GRID, ASSOC_LISTS = 0, 1, 2, 3
 FLAG_DEVICE_OBSERVE = 1
 FLAG_NO_REFERENCE_RESAMPLE = 2
@@ -150,6 +153,13 @@ def load_library():
         L.slamgpu_pose_history_record.argtypes = [C.c_void_p]
         L.slamgpu_pose_history_info.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
         L.slamgpu_pose_history_fetch.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]
+    if hasattr(L, "slamgpu_innovation_summary"):
+        L.slamgpu_innovation_summary.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.slamgpu_innovation_history_enable.argtypes = [C.c_void_p, C.c_int32]
+        L.slamgpu_innovation_record.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
+        L.slamgpu_innovation_history_info.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32),
+                                                      C.POINTER(C.c_int64)]
+        L.slamgpu_innovation_history_fetch.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     if hasattr(L, "slamgpu_path_enable"):
         L.slamgpu_path_enable.argtypes = [C.c_void_p, C.c_int32]
         L.slamgpu_path_record.argtypes = [C.c_void_p]
@@ -649,6 +659,53 @@ class SlamGpu:
         out = np.zeros((max(count, 0), POSE_STRIDE), np.float64)
         _chk(self.L.slamgpu_pose_history_fetch(self.h, first, count, _ptr(out)))
         return out
+
+    def innovation_summary(self, zf, idf, R):
+        """slamgpu_innovation_summary: for the packet about to go to update() (zf[m, 2] range / bearing, idf[m] slots, R 2 x 2), over the set
+        as peek() would show it: (out[m, 10] float64, holders[m] int32); out: [0] share, [1..2] mean innovation, [3..5] its scatter rr, rb,
+        bb, [6..8] mean S s00, s10, s11, [9] mean per-particle NIS; rewrites no state"""
+        zf = _f32(zf).reshape(-1, 2)
+        idf = np.ascontiguousarray(idf, np.int32).reshape(-1)
+        m = len(idf)
+        if len(zf) != m:
+            raise ValueError("innovation_summary: %d observations, %d slots" % (len(zf), m))
+        out = np.zeros((m, INNOV_STRIDE), np.float64)
+        holders = np.zeros(m, np.int32)
+        _chk(self.L.slamgpu_innovation_summary(self.h, _ptr(zf), _ptr(idf), m, _ptr(_f32(R, 4)), _ptr(out), _ptr(holders)))
+        return out, holders
+
+    def innovation_history_enable(self, capacity):
+        """slamgpu_innovation_history_enable: keep the entries of every recorded packet in a ring of `capacity` observation entries (0: stop
+        and free)"""
+        _chk(self.L.slamgpu_innovation_history_enable(self.h, int(capacity)))
+
+    def innovation_record(self, zf, idf, R):
+        """slamgpu_innovation_record: append the entries of this packet against the set as it stands (step() does it itself while the ring
+        is on; callers of predict() + update() call it before the update); enqueued, no synchronisation"""
+        zf = _f32(zf).reshape(-1, 2)
+        idf = np.ascontiguousarray(idf, np.int32).reshape(-1)
+        if len(zf) != len(idf):
+            raise ValueError("innovation_record: %d observations, %d slots" % (len(zf), len(idf)))
+        _chk(self.L.slamgpu_innovation_record(self.h, _ptr(zf), _ptr(idf), len(idf), _ptr(_f32(R, 4))))
+
+    def innovation_history_info(self):
+        """(first, next, capacity, records): entries [first, next) are retained, `records` packets were recorded since the enable
+        (slamgpu_innovation_history_info)"""
+        a, b, cap, rec = C.c_int64(), C.c_int64(), C.c_int32(), C.c_int64()
+        _chk(self.L.slamgpu_innovation_history_info(self.h, C.byref(a), C.byref(b), C.byref(cap), C.byref(rec)))
+        return a.value, b.value, cap.value, rec.value
+
+    def innovation_history_fetch(self, first=None, count=None):
+        """entries first .. first + count - 1 (default: all retained): (out[count, 10] float64, record[count] int32, slot[count] int32);
+        non-consuming (slamgpu_innovation_history_fetch)"""
+        a, b, _, _ = self.innovation_history_info()
+        first = a if first is None else int(first)
+        count = b - first if count is None else int(count)
+        out = np.zeros((max(count, 0), INNOV_STRIDE), np.float64)
+        record = np.zeros(max(count, 0), np.int32)
+        slot = np.zeros(max(count, 0), np.int32)
+        _chk(self.L.slamgpu_innovation_history_fetch(self.h, first, count, _ptr(out), _ptr(record), _ptr(slot)))
+        return out, record, slot
 
     def upload(self, st):
         nf = int(st["nf"])

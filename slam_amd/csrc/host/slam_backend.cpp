@@ -45,6 +45,11 @@
 //   -plotstride <k>      particles / feature particles sent per step are decimated to every k-th particle (default: as
 //                        many as keep a frame below ~2 000 particles; the reference sends all of them: N = 10^5 would be
 //                        1.6 MB of poses and 56 MB of feature points per control step)
+//   -innovation none|posterior  posterior: every packet handed to slamgpu_update is first summarised against the predicted set
+//                        (slamgpu_innovation_record; -INNOVATION_RECORDS n observation entries kept, default 65536), and one more line is
+//                        printed at the end: the entries summarised and retained, the mean NIS of the predicted-measurement mixture
+//                        (slamhost_innovation_nis), the share of entries with NIS <= 5.9915, the mean per-particle NIS, the mean share and
+//                        the entries without a NIS.  Needs no ground truth.  Known association or -assoc gated, one GPU, host-made packets
 //   -pose none|posterior posterior: the pose posterior of every observation step is kept (slamgpu_pose_history_*; -POSE_RECORDS n entries,
 //                        default 4096), and one more line is printed at the end: the entries kept, the mean distance of the WEIGHTED mean to the
 //                        true position beside that of the filtered estimates of the same steps, the mean NEES of the pose against the true pose
@@ -117,6 +122,11 @@ static void usage(const char *a0) {
     printf("    -path none|smoothed smoothed: record the path posterior (one record per observation step, -PATH_RECORDS n of them kept, default 4096)\n");
     printf("                        and print one more line: the smoothed path's distance to the true path beside the filtered estimates', and the\n");
     printf("                        distinct ancestors 1 / 10 / 100 records back (slamgpu_path_summary; FastSLAM, one GPU, not -assoc particle -observe device)\n");
+    printf("    -innovation none|posterior  posterior: summarise every packet against the predicted set before its update (slamgpu_innovation_record;\n");
+    printf("                        -INNOVATION_RECORDS n observation entries kept, default 65536) and print one more line: entries summarised and\n");
+    printf("                        retained, the mean NIS of the predicted-measurement mixture, the share of entries with NIS <= 5.9915 (-2 ln 0.05, the\n");
+    printf("                        95 %% point of chi^2 with 2 degrees of freedom), the mean per-particle NIS, the mean share, the bad entries (FastSLAM,\n");
+    printf("                        one GPU, known association or -assoc gated, not -observe device)\n");
     printf("    -pose none|posterior posterior: keep the pose posterior of every observation step (slamgpu_pose_history_*; -POSE_RECORDS n entries kept,\n");
     printf("                        default 4096) and print one more line: the weighted mean's distance to the true position beside the filtered\n");
     printf("                        estimates', the mean NEES against the true pose, the share of steps with NEES <= 7.8147 (the 95 %% point of chi^2 with\n");
@@ -400,6 +410,47 @@ static void print_pose_posterior(slamgpu_ctx *ctx) {
     printf("pose posterior: %lld entries kept, mean distance to the true position %.4f m (filtered estimates of the same steps: %.4f m); mean NEES %.4f, "
            "NEES <= 7.8147 in %.4f of the steps (%d entries without a NEES); median effective sample size %.1f\n",
            (long long) n, dw / (double) n, df / (double) n, ok ? tot / (double) ok : std::nan(""), ok ? (double) in95 / (double) ok : std::nan(""), (int) bad, med);
+}
+// -innovation posterior: the innovation entries of every packet handed to slamgpu_update (slamgpu_innovation_*), -INNOVATION_RECORDS n
+// entries kept
+static int g_innov_records = 0;  // 0: off
+static void print_innovation_posterior(slamgpu_ctx *ctx) {
+    if (!g_innov_records) return;
+    int64_t first = 0, next = 0;
+    if (slamgpu_innovation_history_info(ctx, &first, &next, nullptr, nullptr) != 0) {
+        fprintf(stderr, "slamgpu: %s\n", slamgpu_last_error());
+        return;
+    }
+    const int64_t n = next - first;
+    if (n <= 0) {
+        printf("innovation posterior: no entries\n");
+        return;
+    }
+    std::vector<double> ent((size_t) SLAMGPU_INNOV_STRIDE * (size_t) n), nis((size_t) n);
+    if (slamgpu_innovation_history_fetch(ctx, first, (int32_t) n, ent.data(), nullptr, nullptr) != 0) {
+        fprintf(stderr, "slamgpu: %s\n", slamgpu_last_error());
+        return;
+    }
+    const int32_t bad = slamhost_innovation_nis(ent.data(), (int32_t) n, nis.data());
+    double tot = 0, own = 0, share = 0;
+    int64_t ok = 0, in95 = 0, nown = 0;
+    for (int64_t k = 0; k < n; k++) {
+        const double *e = ent.data() + (size_t) SLAMGPU_INNOV_STRIDE * (size_t) k;
+        if (e[0] == e[0]) share += e[0];
+        if (e[9] == e[9]) {
+            own += e[9];
+            nown++;
+        }
+        if (nis[(size_t) k] == nis[(size_t) k]) {
+            tot += nis[(size_t) k];
+            ok++;
+            in95 += nis[(size_t) k] <= 5.9915;  // -2 ln 0.05: the 95 % point of chi^2 with 2 degrees of freedom
+        }
+    }
+    printf("innovation posterior: %lld entries summarised, %lld retained; mean mixture NIS %.4f, NIS <= 5.9915 in %.4f of the entries; "
+           "mean per-particle NIS %.4f; mean share %.4f; %d bad entries\n",
+           (long long) next, (long long) n, ok ? tot / (double) ok : std::nan(""), ok ? (double) in95 / (double) ok : std::nan(""),
+           nown ? own / (double) nown : std::nan(""), share / (double) n, (int) bad);
 }
 static void print_smoothed_path(slamgpu_ctx *ctx) {
     if (!g_path_records) return;
@@ -695,6 +746,31 @@ int main(int argc, char **argv) {
         }
         sim.conf.kv.erase("pose");
         sim.conf.kv.erase("POSE_RECORDS");
+        // ... and -innovation (with -INNOVATION_RECORDS): it needs the loop below that makes its own updates from host-made packets
+        const std::string in = sim.conf.s("innovation"), inr = sim.conf.s("INNOVATION_RECORDS");
+        if (!in.empty() && in != "none" && in != "posterior") {
+            fprintf(stderr, "-innovation none|posterior\n");
+            return EXIT_FAILURE;
+        }
+        if (in == "posterior") {
+            g_innov_records = inr.empty() ? 65536 : atoi(inr.c_str());
+            const std::string gp = sim.conf.s("gpus");
+            const char *why = nullptr;
+            if (g_innov_records <= 0) why = "-INNOVATION_RECORDS needs a positive number of entries";
+            else if (sim.conf.method == 0) why = "FastSLAM only (the EKF's innovation covariance is its own S)";
+            else if (!gp.empty() && atoi(gp.c_str()) != 1) why = "single GPU only (slamgpu_innovation_* have no distributed form)";
+            else if (sim.conf.s("observe") == "device") why = "not with -observe device (its packets are made on the device and never exist on the host)";
+            else if (sim.conf.s("assoc") == "particle") why = "not with -assoc particle (every particle has its own labels; the packet has one slot per observation)";
+            if (why) {
+                fprintf(stderr, "-innovation posterior: %s\n", why);
+                return EXIT_FAILURE;
+            }
+        } else if (!inr.empty()) {
+            fprintf(stderr, "-INNOVATION_RECORDS n: with -innovation posterior\n");
+            return EXIT_FAILURE;
+        }
+        sim.conf.kv.erase("innovation");
+        sim.conf.kv.erase("INNOVATION_RECORDS");
     }
     const Conf &c = sim.conf;
     printf("map: %s\n", c.map_path.c_str());
@@ -746,7 +822,9 @@ int main(int argc, char **argv) {
     const bool observe_dev = c.s("observe") == "device";
     // (-assoc particle -observe device: slamgpu_run_particle, batched; -loop step hands it one iteration per call)
     const bool particle_dev = particle && observe_dev;
-    const bool batched = c.method != 0 && !plot.active() && !parity && !gated && (!particle || particle_dev) && (c.s("loop") != "step" || particle_dev);
+    // (-innovation posterior: the loop below, which makes its own updates and holds every packet on the host)
+    const bool batched = c.method != 0 && !plot.active() && !parity && !gated && (!particle || particle_dev) && (c.s("loop") != "step" || particle_dev) &&
+                         !g_innov_records;
     auto numkey = [&](const char *key, double dflt) { return c.s(key).empty() ? dflt : atof(c.s(key).c_str()); };
     slamgpu_particle_assoc popt{};
     long pp_opened = 0, pp_reused = 0, pp_dropped = 0;
@@ -843,6 +921,11 @@ int main(int argc, char **argv) {
         }
         if (g_pose_records && slamgpu_pose_history_enable(ctx, g_pose_records) != 0) {
             fprintf(stderr, "-pose posterior: %s\n", slamgpu_last_error());
+            slamgpu_destroy(ctx);
+            return EXIT_FAILURE;
+        }
+        if (g_innov_records && slamgpu_innovation_history_enable(ctx, g_innov_records) != 0) {
+            fprintf(stderr, "-innovation posterior: %s\n", slamgpu_last_error());
             slamgpu_destroy(ctx);
             return EXIT_FAILURE;
         }
@@ -1045,7 +1128,9 @@ int main(int argc, char **argv) {
                     stratified_random(N, strata.data());
                     st = strata.data();
                 }
-                rc = slamgpu_update(ctx, zf.data(), idf.data(), (int) idf.size(), zn.data(), (int) (zn.size() / 2), sim.Re, nm, st);
+                // -innovation posterior: this packet against the predicted set, immediately before the update takes it
+                if (g_innov_records) rc = slamgpu_innovation_record(ctx, zf.data(), idf.data(), (int) idf.size(), sim.Re);
+                if (!rc) rc = slamgpu_update(ctx, zf.data(), idf.data(), (int) idf.size(), zn.data(), (int) (zn.size() / 2), sim.Re, nm, st);
                 nobs++;
                 }
             }
@@ -1129,6 +1214,7 @@ int main(int argc, char **argv) {
     if (ctx) print_posterior_map(ctx, sim);
     if (ctx && !rc) print_smoothed_path(ctx);
     if (ctx && !rc) print_pose_posterior(ctx);
+    if (ctx && !rc) print_innovation_posterior(ctx);
     if (plot.active()) {
         plot.endPlot();
         plot.close();

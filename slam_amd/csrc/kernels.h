@@ -662,6 +662,30 @@ struct PoseSummaryArgs {
     double *out;                // [kPoseStride]
 };
 
+// Innovation posterior (slamgpu_innovation_summary, slamgpu_innovation_*): per re-observed landmark of a packet, over the particle set
+// and with the weights of slamgpu_map_summary, the holders' share, the mean and scatter of the innovation v = z - h(pose, xf), the mean
+// innovation covariance S = H Pf H^T + R and the mean per-particle NIS (include/slamgpu.h states the formula and its order; it is
+// evaluated in double without contraction in both builds).  innovation_summary_kernel is map_summary_kernel on (v, S) in the place of
+// (xf, Pf): grid (particle tiles, groups of kMapSlots observations); a lane keeps ancestor, weight AND pose (one 16-byte load of poseA)
+// of its kMapT particles across the group, observations whose slots share a genealogy row share its entries, all kMapT records are
+// requested before any is used; sums in double about the wave's first holder's v, lanes by a DPP sum, waves and tiles as (W, mean,
+// M2) by map_merge in ascending particle order.  A partial is the map summary's kMapFields plus sum w nis: [tile][kInnFields][count].
+// The tile's sum of weights goes to S.wpart exactly as the map summary's does (one code path: tile_weights / finish_weights).
+// innovation_finish_kernel is map_finish_kernel's pass (the same body) with the extra field; it writes entry q to S.out[q] (staging),
+// or, with ring_cap > 0, to entry (ring_at + q) % ring_cap of the ring S.out with its tags.
+constexpr int kInnStride = 10;             // SLAMGPU_INNOV_STRIDE
+enum { kInnNis = kMapFields, kInnFields };
+struct InnovArgs {
+    MapSummaryArgs S;           // count observations of this launch (first_slot is not read); part [tiles][kInnFields][count]; holders may be null
+    const float *zf;            // [count][2] range, bearing
+    const int32_t *idf;         // [count] slots, each inside [0, number of slots)
+    float r00, r10, r11;        // R[0], R[2], R[3]
+    int32_t ring_cap;           // 0: staging
+    int64_t ring_at;            // entry number of this launch's first observation
+    int32_t *tag;               // [ring_cap][2]: record, slot
+    int32_t record;
+};
+
 // ---- gated association with a spatial prefilter (slamgpu_associate_ex) ------------------------------------------------------
 // Per landmark j, over ALL particles: the bounding box of its position estimates and the largest trace of its covariance
 // (lmk_box_kernel, recomputed when the landmark is written), and from them a radius rho_j such that a particle's estimate of j
@@ -985,6 +1009,10 @@ struct KernelTable {
     // Both read the particle state only
     void (*pose_summary)(hipStream_t, const Buffers &, const WeightScratch &, const PoseSummaryArgs &);
     void (*pose_finish)(hipStream_t, const Buffers &, const WeightScratch &, const PoseSummaryArgs &);
+    // slamgpu_innovation_summary / slamgpu_innovation_record (InnovArgs): the partials of one chunk of observations, and their finishing
+    // pass into the staging area or the ring.  Tables in sync; reads only
+    void (*innovation_summary)(hipStream_t, const Buffers &, const WeightScratch &, const InnovArgs &);
+    void (*innovation_finish)(hipStream_t, const InnovArgs &);
 };
 
 const KernelTable *kernels_strict();

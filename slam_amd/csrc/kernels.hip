@@ -4831,34 +4831,8 @@ __global__ void __launch_bounds__(kBlock) map_summary_kernel(Buffers B, WeightSc
         wf[t] = on[t] ? (pend ? ctrl->inv_n : B.poseA[cur][anc[t]].w) : 0.0f;  // resampled particles restart at 1/N, as in peek_kernel
         if (on[t] && A.logw) mb = fmaxf(mb, wf[t]);
     }
-    double w[kMapT];
-    if (A.logw) {  // the tile's largest log-weight
-        for (int d = kWave / 2; d > 0; d >>= 1) mb = fmaxf(mb, __shfl_xor(mb, d, kWave));
-        if (lane == 0) sh_m[wave] = mb;
-        __syncthreads();
-        mb = sh_m[0];
-        for (int v = 1; v < kWaves; v++) mb = fmaxf(mb, sh_m[v]);
-#pragma unroll
-        for (int t = 0; t < kMapT; t++) w[t] = (on[t] && mb != -INFINITY) ? exp((double) wf[t] - (double) mb) : 0.0;
-    } else {
-        mb = 0.0f;
-#pragma unroll
-        for (int t = 0; t < kMapT; t++) w[t] = (double) wf[t];
-    }
-    if (blockIdx.y == 0) {  // the tile's sum of weights (every group of slots would find the same bits: one of them stores it)
-        double sw = 0.0;
-#pragma unroll
-        for (int t = 0; t < kMapT; t++) sw += w[t];
-        sw = wave_sum_d(sw);
-        if (lane == 0) sh_w[wave] = sw;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            double tot = sh_w[0];
-            for (int v = 1; v < kWaves; v++) tot += sh_w[v];
-            A.wpart[2 * blockIdx.x] = tot;
-            A.wpart[2 * blockIdx.x + 1] = (double) mb;
-        }
-    }
+    // (one text for every summary of this family: w[kMapT] from wf / on / mb, and the tile's sum into A.wpart)
+#include "summary_weights.inl"
     const int s0 = blockIdx.y * kMapSlots, sn = min(kMapSlots, A.count - s0);
     int row = -1;
     int sl[kMapT];
@@ -4949,62 +4923,11 @@ __global__ void __launch_bounds__(kBlock) map_summary_kernel(Buffers B, WeightSc
 
 // kMapFinParts threads per slot: each merges its stretch of the tiles' partials in ascending order (and adds up that stretch's weights),
 // the slot's first thread merges the stretches in ascending order, normalises and writes the outputs
+// (the body is one text for this kernel and innovation_finish_kernel: summary_finish.inl)
 __global__ void __launch_bounds__(kBlock) map_finish_kernel(MapSummaryArgs A) {
-    constexpr int kSlots = kBlock / kMapFinParts;
-    __shared__ double sh[kMapFinParts][kMapFields + 1][kSlots];
-    __shared__ double sh_m[kBlock / kWave];
-    const int sl = threadIdx.x % kSlots, part = threadIdx.x / kSlots;
-    const int s = blockIdx.x * kSlots + sl;
-    double M = -INFINITY;
-    if (A.logw) {  // the largest log-weight of all tiles
-        for (int t = threadIdx.x; t < A.tiles; t += kBlock) M = fmax(M, A.wpart[2 * t + 1]);
-        for (int d = kWave / 2; d > 0; d >>= 1) M = fmax(M, __shfl_xor(M, d, kWave));
-        if ((threadIdx.x & (kWave - 1)) == 0) sh_m[threadIdx.x / kWave] = M;
-        __syncthreads();
-        M = sh_m[0];
-        for (int v = 1; v < kBlock / kWave; v++) M = fmax(M, sh_m[v]);
-    }
-    const int per = (A.tiles + kMapFinParts - 1) / kMapFinParts, t0 = part * per, t1 = min(A.tiles, t0 + per);
-    MapPart m;
-    for (int q = 0; q < kMapFields; q++) m.v[q] = 0.0;
-    double wsum = 0.0;
-    for (int t = t0; t < t1; t++) {
-        const double f = A.logw ? block_scale((float) A.wpart[2 * t + 1], M) : 1.0;
-        wsum += A.wpart[2 * t] * f;
-        if (s >= A.count) continue;
-        const double *p = A.part + (size_t) t * kMapFields * (size_t) A.count + (size_t) s;
-        MapPart b;
-        for (int q = 0; q < kMapFields; q++) b.v[q] = p[(size_t) q * A.count];
-        if (A.logw) {
-            b.v[kMapW] *= f;
-            for (int q = kMapXX; q <= kMapP11; q++) b.v[q] *= f;
-        }
-        map_merge(m, b);
-    }
-    for (int q = 0; q < kMapFields; q++) sh[part][q][sl] = m.v[q];
-    sh[part][kMapFields][sl] = wsum;
-    __syncthreads();
-    if (part != 0 || s >= A.count) return;
-    double Wtot = wsum;
-    for (int v = 1; v < kMapFinParts; v++) {
-        MapPart b;
-        for (int q = 0; q < kMapFields; q++) b.v[q] = sh[v][q][sl];
-        map_merge(m, b);
-        Wtot += sh[v][kMapFields][sl];
-    }
-    double *o = A.out + (size_t) s * kMapStride;
-    A.holders[s] = (int32_t) m.v[kMapCnt];
-    const double nan = __longlong_as_double(0x7ff8000000000000ll);
-    if (!(Wtot > 0.0) || !(Wtot < INFINITY)) {  // the weights sum to zero or to nothing finite: SLAMGPU_STATUS_DEGENERATE's convention
-        for (int q = 0; q < kMapStride; q++) o[q] = nan;
-        return;
-    }
-    const double W = m.v[kMapW];
-    o[0] = W / Wtot;
-    const bool held = m.v[kMapCnt] != 0.0 && W != 0.0;
-    o[1] = held ? m.v[kMapMx] : nan;
-    o[2] = held ? m.v[kMapMy] : nan;
-    for (int q = kMapXX; q <= kMapP11; q++) o[q] = held ? m.v[q] / W : nan;
+#define SLAM_FINISH_INNOV 0
+#include "summary_finish.inl"
+#undef SLAM_FINISH_INNOV
 }
 
 static void launch_map_summary(hipStream_t st, const Buffers &B, const WeightScratch &ws, const MapSummaryArgs &A) {
@@ -5043,34 +4966,8 @@ __global__ void __launch_bounds__(kBlock) map_pairs_kernel(Buffers B, WeightScra
         wf[t] = on[t] ? (pend ? ctrl->inv_n : B.poseA[cur][anc[t]].w) : 0.0f;
         if (on[t] && A.logw) mb = fmaxf(mb, wf[t]);
     }
-    double w[kMapT];
-    if (A.logw) {
-        for (int d = kWave / 2; d > 0; d >>= 1) mb = fmaxf(mb, __shfl_xor(mb, d, kWave));
-        if (lane == 0) sh_m[wave] = mb;
-        __syncthreads();
-        mb = sh_m[0];
-        for (int v = 1; v < kWaves; v++) mb = fmaxf(mb, sh_m[v]);
-#pragma unroll
-        for (int t = 0; t < kMapT; t++) w[t] = (on[t] && mb != -INFINITY) ? exp((double) wf[t] - (double) mb) : 0.0;
-    } else {
-        mb = 0.0f;
-#pragma unroll
-        for (int t = 0; t < kMapT; t++) w[t] = (double) wf[t];
-    }
-    if (blockIdx.y == 0) {
-        double sw = 0.0;
-#pragma unroll
-        for (int t = 0; t < kMapT; t++) sw += w[t];
-        sw = wave_sum_d(sw);
-        if (lane == 0) sh_w[wave] = sw;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            double tot = sh_w[0];
-            for (int v = 1; v < kWaves; v++) tot += sh_w[v];
-            A.wpart[2 * blockIdx.x] = tot;
-            A.wpart[2 * blockIdx.x + 1] = (double) mb;
-        }
-    }
+    // (one text for every summary of this family: w[kMapT] from wf / on / mb, and the tile's sum into A.wpart)
+#include "summary_weights.inl"
     const int s0 = blockIdx.y * kMapSlots, sn = min(kMapSlots, A.count - s0);
     int rowa = -1, rowb = -1;
     int sla[kMapT], slb[kMapT];
@@ -6048,6 +5945,180 @@ static void launch_pose_finish(hipStream_t st, const Buffers &B, const WeightScr
     hipLaunchKernelGGL(pose_finish_kernel, dim3(1), dim3(kPoseFinParts), 0, st, B, ws, A);
 }
 
+// ---- slamgpu_innovation_summary / slamgpu_innovation_* (kernels.h: InnovArgs) -------------------------------------------------
+// one particle's innovation of one observation, in double, in the order include/slamgpu.h states (no contraction in either build, so
+// that both evaluate the formula the float64 model does): v, S = H Pf H^T + R and nis; false when the landmark sits on the pose
+struct InnovTerm {
+    double v0, v1, s00, s10, s11, nis;
+};
+SLAM_DEV bool innov_term(const float4 &pose, const float4 &la, float lb, double zr, double zb, double r00, double r10, double r11, InnovTerm &o) {
+#pragma clang fp contract(off)
+    const double dx = (double) la.x - (double) pose.x, dy = (double) la.y - (double) pose.y;
+    const double d2 = dx * dx + dy * dy;
+    if (!(d2 > 0.0)) return false;
+    const double d = sqrt(d2);
+    o.v0 = zr - d;
+    o.v1 = remainder(zb - (atan2(dy, dx) - (double) pose.z), kPoseTwoPi);
+    const double h00 = dx / d, h01 = dy / d, h10 = -dy / d2, h11 = dx / d2;
+    const double p00 = (double) la.z, p10 = (double) la.w, p11 = (double) lb;
+    const double t0 = h00 * p00 + h01 * p10, t1 = h00 * p10 + h01 * p11;  // H Pf, row 0
+    const double u0 = h10 * p00 + h11 * p10, u1 = h10 * p10 + h11 * p11;  // ... row 1
+    o.s00 = t0 * h00 + t1 * h01 + r00;
+    o.s10 = u0 * h00 + u1 * h01 + r10;
+    o.s11 = u0 * h10 + u1 * h11 + r11;
+    o.nis = (o.s11 * o.v0 * o.v0 - 2.0 * o.s10 * o.v0 * o.v1 + o.s00 * o.v1 * o.v1) / (o.s00 * o.s11 - o.s10 * o.s10);
+    return true;
+}
+
+__global__ void __launch_bounds__(kBlock) innovation_summary_kernel(Buffers B, WeightScratch ws, InnovArgs I) {
+    constexpr int kWaves = kBlock / kWave;
+    __shared__ double sh[kMapSlots][kWaves][kInnFields];
+    __shared__ double sh_w[kWaves];
+    __shared__ float sh_m[kWaves];
+    const MapSummaryArgs &A = I.S;
+    const Ctrl *ctrl = B.ctrl;
+    const int cur = ctrl->live[B.slot];
+    const bool pend = ctrl->pend[B.slot] != 0;
+    const size_t S = (size_t) B.ncap;
+    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
+    // this lane's particles: ancestor, pose and weight (one 16-byte load), once for every observation of the group
+    int anc[kMapT];
+    float4 pa[kMapT];
+    float wf[kMapT];
+    bool on[kMapT];
+    float mb = -INFINITY;
+#pragma unroll
+    for (int t = 0; t < kMapT; t++) {
+        const int i = blockIdx.x * kMapTile + t * kBlock + threadIdx.x;
+        on[t] = i < B.n;
+        anc[t] = on[t] ? (pend ? ws.keep[B.slot][i] : i) : 0;
+        pa[t] = on[t] ? B.poseA[cur][anc[t]] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    }
+#pragma unroll
+    for (int t = 0; t < kMapT; t++) {
+        wf[t] = on[t] ? (pend ? ctrl->inv_n : pa[t].w) : 0.0f;  // resampled particles restart at 1/N, as in peek_kernel
+        if (on[t] && A.logw) mb = fmaxf(mb, wf[t]);
+    }
+    // (one text for every summary of this family: w[kMapT] from wf / on / mb, and the tile's sum into A.wpart)
+#include "summary_weights.inl"
+    const double r00 = (double) I.r00, r10 = (double) I.r10, r11 = (double) I.r11;
+    const int s0 = blockIdx.y * kMapSlots, sn = min(kMapSlots, A.count - s0);
+    int row = -1;
+    int sl[kMapT];
+    for (int s = 0; s < sn; s++) {
+        const int l = I.idf[s0 + s];
+        const double zr = (double) I.zf[2 * (s0 + s)], zb = (double) I.zf[2 * (s0 + s) + 1];
+        const int r = B.erow[l];
+        if (r != row) {  // (uniform) the observations whose slots lie in one genealogy row share its entries
+            row = r;
+#pragma unroll
+            for (int t = 0; t < kMapT; t++) sl[t] = on[t] ? B.gen[cur][gen_index(B.compact, S, r, (size_t) anc[t])] : 0;
+        }
+        float4 la[kMapT];
+        float lb[kMapT];
+#pragma unroll
+        for (int t = 0; t < kMapT; t++) {
+            la[t] = make_float4(NAN, NAN, NAN, NAN);
+            lb[t] = NAN;
+            if (on[t]) read_record(B, B.lmk_live, S, l, sl[t], la[t], lb[t]);
+        }
+        InnovTerm e[kMapT];
+        bool hold[kMapT];
+#pragma unroll
+        for (int t = 0; t < kMapT; t++) {
+            e[t] = InnovTerm{0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+            hold[t] = la[t].x == la[t].x && innov_term(pa[t], la[t], lb[t], zr, zb, r00, r10, r11, e[t]);
+        }
+        // pivot: the wave's first holder's innovation (a point of the holders' cloud: the sums below cancel at the cloud's size)
+        bool have = false;
+        double p0 = 0.0, p1 = 0.0;
+        int cnt = 0;
+#pragma unroll
+        for (int t = 0; t < kMapT; t++) {
+            const unsigned long long hm = __ballot(hold[t]);
+            cnt += (int) __popcll(hm);
+            if (!have && hm) {
+                const int src = __builtin_amdgcn_readfirstlane((int) __ffsll((long long) hm) - 1);
+                p0 = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(e[t].v0), src), __builtin_amdgcn_readlane(__double2loint(e[t].v0), src));
+                p1 = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(e[t].v1), src), __builtin_amdgcn_readlane(__double2loint(e[t].v1), src));
+                have = true;
+            }
+        }
+        double *o = sh[s][wave];
+        if (!have) {  // (uniform) nobody in this wave holds the slot
+            if (lane < kInnFields) o[lane] = 0.0;
+            continue;
+        }
+        double a[10] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};  // sum w | w d0, w d1 | w d0^2, w d0 d1, w d1^2 | w S | w nis
+#pragma unroll
+        for (int t = 0; t < kMapT; t++) {
+            if (hold[t]) {
+                const double d0 = e[t].v0 - p0, d1 = e[t].v1 - p1, wt = w[t];
+                a[0] += wt;
+                a[1] += wt * d0;
+                a[2] += wt * d1;
+                a[3] += wt * d0 * d0;
+                a[4] += wt * d0 * d1;
+                a[5] += wt * d1 * d1;
+                a[6] += wt * e[t].s00;
+                a[7] += wt * e[t].s10;
+                a[8] += wt * e[t].s11;
+                a[9] += wt * e[t].nis;
+            }
+        }
+#pragma unroll
+        for (int q = 0; q < 10; q++) a[q] = wave_sum_d(a[q]);
+        if (lane == 0) {
+            const double W = a[0];
+            const bool any = W != 0.0;  // (W == 0: holders without weight are counted, and carry nothing else)
+            const double m0 = any ? a[1] / W : 0.0, m1 = any ? a[2] / W : 0.0;
+            o[kMapW] = W;
+            o[kMapMx] = p0 + m0;
+            o[kMapMy] = p1 + m1;
+            o[kMapXX] = a[3] - a[1] * m0;
+            o[kMapXY] = a[4] - a[1] * m1;
+            o[kMapYY] = a[5] - a[2] * m1;
+            o[kMapP00] = a[6];
+            o[kMapP10] = a[7];
+            o[kMapP11] = a[8];
+            o[kMapCnt] = (double) cnt;
+            o[kInnNis] = any ? a[9] : 0.0;
+        }
+    }
+    __syncthreads();
+    if ((int) threadIdx.x < sn) {  // the tile's waves in ascending order, as map_summary_kernel merges them
+        const int s = threadIdx.x;
+        MapPart m;
+        for (int q = 0; q < kMapFields; q++) m.v[q] = sh[s][0][q];
+        double nis = sh[s][0][kInnNis];
+        for (int v = 1; v < kWaves; v++) {
+            MapPart b;
+            for (int q = 0; q < kMapFields; q++) b.v[q] = sh[s][v][q];
+            map_merge(m, b);
+            nis += sh[s][v][kInnNis];
+        }
+        double *p = A.part + (size_t) blockIdx.x * kInnFields * (size_t) A.count + (size_t) (s0 + s);
+        for (int q = 0; q < kMapFields; q++) p[(size_t) q * A.count] = m.v[q];
+        p[(size_t) kInnNis * A.count] = nis;
+    }
+}
+
+// map_finish_kernel's pass (the same text) with the extra field, into the staging area or the ring
+__global__ void __launch_bounds__(kBlock) innovation_finish_kernel(InnovArgs I) {
+    const MapSummaryArgs &A = I.S;
+#define SLAM_FINISH_INNOV 1
+#include "summary_finish.inl"
+#undef SLAM_FINISH_INNOV
+}
+
+static void launch_innovation_summary(hipStream_t st, const Buffers &B, const WeightScratch &ws, const InnovArgs &I) {
+    hipLaunchKernelGGL(innovation_summary_kernel, dim3(I.S.tiles, (I.S.count + kMapSlots - 1) / kMapSlots), dim3(kBlock), 0, st, B, ws, I);
+}
+static void launch_innovation_finish(hipStream_t st, const InnovArgs &I) {
+    constexpr int kSlots = kBlock / kMapFinParts;
+    hipLaunchKernelGGL(innovation_finish_kernel, dim3((I.S.count + kSlots - 1) / kSlots), dim3(kBlock), 0, st, I);
+}
+
 static const KernelTable kTable = {launch_update, launch_update_any, launch_update_persist, launch_resample, launch_resample_ref, launch_scan, launch_gather, launch_flatten, launch_identity, launch_decompact, launch_finish, launch_predict, launch_estimate, launch_jacobians, launch_kat, launch_observe, launch_observe_book, launch_associate,
                                    launch_shard_plan, launch_shard_pack, launch_shard_unpack, launch_shard_finish, launch_dist_gather, launch_dist_flags, launch_peek, launch_lmk_box, launch_assoc_grid, launch_assoc_lists, launch_vote_compact,
                                    launch_associate_grid, launch_jacobians_multi, launch_pp_census, launch_pp_resolve, launch_pp_holders,
@@ -6055,7 +6126,7 @@ static const KernelTable kTable = {launch_update, launch_update_any, launch_upda
                                    launch_lists_box, launch_lists_geom, launch_lists_build, launch_lists_walk, launch_excl_radii,
                                    launch_map_summary, launch_map_finish, launch_map_pairs, launch_pp_missed,
                                    launch_path_compose, launch_path_record, launch_path_trace, launch_path_seed, launch_path_push, launch_path_finish,
-                                   launch_pp_mutex, launch_pose_summary, launch_pose_finish};
+                                   launch_pp_mutex, launch_pose_summary, launch_pose_finish, launch_innovation_summary, launch_innovation_finish};
 
 }  // namespace SLAM_KNS
 

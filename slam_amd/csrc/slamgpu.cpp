@@ -283,6 +283,20 @@ struct slamgpu_ctx {
     int64_t pose_first = 0, pose_next = 0;
     double *pose_ring_dev = nullptr; // [pose_cap][kPoseStride]
     double *pose_dev = nullptr;      // [tiles][kPoseFields] partials | [kPoseStride] staging of slamgpu_pose_summary
+    // innovation posterior (slamgpu_innovation_*; kernels.h: InnovArgs).  innov_cap = 0: the ring is off.  Entries [innov_first, innov_next)
+    // are retained, entry e in ring slot e % innov_cap; innov_records counts the _record calls since the enable.  A packet travels
+    // through one of kInnovStage pinned staging slots (an event per slot says when the device has taken it: a record does not wait
+    // for the device unless it is kInnovStage packets ahead of it).  Nothing is allocated and no kernel of it launched until the ring
+    // is enabled or slamgpu_innovation_summary is called
+    int32_t innov_cap = 0;
+    int64_t innov_first = 0, innov_next = 0, innov_records = 0;
+    double *innov_ring_dev = nullptr;  // [innov_cap][kInnStride]
+    int32_t *innov_tag_dev = nullptr;  // [innov_cap][2]: record, slot
+    char *innov_host = nullptr;        // pinned [kInnovStage][innov_host_m] x (zf 8 B | idf 4 B)
+    size_t innov_host_m = 0;
+    uint64_t innov_seq = 0;
+    hipEvent_t innov_ev[4]{};
+    bool innov_ev_used[4]{};
     bool pp_stage_ran = false;       // slamgpu_run_particle: a pose entry has already run the stage the last iteration left (pose_append)
     unsigned long long *stamps_dev = nullptr;  // diagnostic (SLAMGPU_STAMPS=1 + libslamgpu_stamps.so): UpdateArgs::stamps
     // persistent small-N step loop (slamgpu_run_observe, kernels.h: PersistArgs)
@@ -873,6 +887,137 @@ int pose_append(slamgpu_ctx *c) {
     return 0;
 }
 
+// ---- innovation posterior (slamgpu_innovation_*; kernels.h: InnovArgs) ----
+constexpr int kInnovStage = 4;
+
+// what slamgpu_innovation_summary and slamgpu_innovation_record refuse alike (outputs untouched); m > 0 on return 0
+int innov_check(slamgpu_ctx *c, const char *fn, const float *zf, const int32_t *idf, int32_t m, const float *R) {
+    if (m < 0) return fail(SLAMGPU_ERR_INVALID, "%s: m %d", fn, m);
+    if (m == 0) return 0;
+    if (!zf || !idf || !R) return fail(SLAMGPU_ERR_INVALID, "%s: null %s", fn, !zf ? "zf" : !idf ? "idf" : "R");
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    if (int rc = book_pull(c)) return rc;  // (device-driven steps: the number of slots lives on the device)
+    for (int32_t q = 0; q < m; q++)
+        if (idf[q] < 0 || idf[q] >= c->nf)
+            return fail(SLAMGPU_ERR_INVALID, "%s: observation %d names slot %d outside [0, %d)", fn, q, idf[q], c->nf);
+    return 0;
+}
+
+// the m entries of the set as slamgpu_peek would show it: into the ring's slots (innov_next + q) % innov_cap with their tags (ring),
+// or into the staging area, from where out_dev / hold_dev point at them.  Enqueued; the caller has checked the packet (m > 0)
+int innov_launch(slamgpu_ctx *c, const float *zf, const int32_t *idf, int32_t m, const float *R, bool ring, const double **out_dev,
+                 const int32_t **hold_dev) {
+    static_assert(SLAMGPU_INNOV_STRIDE == kInnStride, "public / device summary layout");
+    static_assert(sizeof c->innov_ev / sizeof c->innov_ev[0] == kInnovStage, "staging slots");
+    // the particle set and the weights of slamgpu_map_summary, reached the same way
+    if (int rc = flush_predict(c)) return rc;
+    if (int rc = flush_stages(c)) return rc;
+    if (int rc = sync_tables(c)) return rc;
+    const int tiles = (c->B.n + kMapTile - 1) / kMapTile;
+    // the packet goes through the partials' table a chunk at a time, capped as the map summary's is
+    constexpr size_t kMapScratch = (size_t) 16 << 20;
+    const size_t per_obs = sizeof(double) * kInnFields * (size_t) tiles;
+    int fit = (int) std::max<size_t>(kMapSlots, kMapScratch / per_obs / kMapSlots * kMapSlots);
+    if (const char *e = getenv("SLAMGPU_INNOV_CHUNK"))  // (diagnostic: the chunking of a large packet on a small one)
+        fit = std::max(kMapSlots, atoi(e) / kMapSlots * kMapSlots);
+    const int chunk = (int) std::min<int64_t>(fit, ((int64_t) m + kMapSlots - 1) / kMapSlots * kMapSlots);
+    // device staging: [out m][wpart tiles][part chunk][zf m][idf m][holders m]
+    const size_t M = (size_t) m;
+    const size_t o_out = 0, o_w = o_out + sizeof(double) * kInnStride * M, o_part = o_w + sizeof(double) * 2 * (size_t) tiles,
+                 o_zf = o_part + per_obs * (size_t) chunk, o_idf = o_zf + sizeof(float) * 2 * M, o_hold = o_idf + sizeof(int32_t) * M,
+                 total = o_hold + sizeof(int32_t) * M;
+    if (total > c->msum_bytes) {
+        if (c->msum_dev) (void) hipFree(c->msum_dev);
+        c->msum_dev = nullptr;
+        c->msum_bytes = 0;
+        hipError_t e = hipMalloc((void **) &c->msum_dev, total);
+        if (e != hipSuccess) {
+            (void) hipGetLastError();
+            return fail(SLAMGPU_ERR_ALLOC, "hipMalloc(%zu): %s", total, hipGetErrorString(e));
+        }
+        c->msum_bytes = total;
+    }
+    // the packet: through a pinned slot of the context's own, so that the caller's arrays are free again when the call returns
+    if (M > c->innov_host_m) {
+        for (int k = 0; k < kInnovStage; k++)
+            if (c->innov_ev_used[k]) HIP_TRY(hipEventSynchronize(c->innov_ev[k]));
+        if (c->innov_host) (void) hipHostFree(c->innov_host);
+        c->innov_host = nullptr;
+        c->innov_host_m = 0;
+        const size_t want = std::max<size_t>(M, 64);
+        hipError_t e = hipHostMalloc((void **) &c->innov_host, 12 * want * kInnovStage, hipHostMallocDefault);
+        if (e != hipSuccess) {
+            (void) hipGetLastError();
+            c->innov_host = nullptr;
+            return fail(SLAMGPU_ERR_ALLOC, "hipHostMalloc(%zu): %s", 12 * want * kInnovStage, hipGetErrorString(e));
+        }
+        c->innov_host_m = want;
+    }
+    const int k = (int) (c->innov_seq++ % kInnovStage);
+    if (!c->innov_ev[k]) HIP_TRY(hipEventCreateWithFlags(&c->innov_ev[k], hipEventDisableTiming));
+    if (c->innov_ev_used[k]) HIP_TRY(hipEventSynchronize(c->innov_ev[k]));
+    char *h = c->innov_host + 12 * c->innov_host_m * (size_t) k;
+    memcpy(h, zf, sizeof(float) * 2 * M);
+    memcpy(h + sizeof(float) * 2 * M, idf, sizeof(int32_t) * M);
+    HIP_TRY(hipMemcpyAsync(c->msum_dev + o_zf, h, 12 * M, hipMemcpyHostToDevice, c->stream));  // (zf | idf: adjacent in both places)
+    HIP_TRY(hipEventRecord(c->innov_ev[k], c->stream));
+    c->innov_ev_used[k] = true;
+    c->B.slot = c->slot;
+    for (int at = 0; at < m; at += chunk) {
+        InnovArgs I{};
+        MapSummaryArgs &A = I.S;
+        A.first_slot = 0;
+        A.count = std::min(chunk, m - at);
+        A.tiles = tiles;
+        A.logw = c->cfg.log_weights;
+        A.part = reinterpret_cast<double *>(c->msum_dev + o_part);
+        A.wpart = reinterpret_cast<double *>(c->msum_dev + o_w);
+        I.zf = reinterpret_cast<const float *>(c->msum_dev + o_zf) + (size_t) 2 * at;
+        I.idf = reinterpret_cast<const int32_t *>(c->msum_dev + o_idf) + at;
+        I.r00 = R[0];
+        I.r10 = R[2];
+        I.r11 = R[3];
+        if (ring) {
+            A.out = c->innov_ring_dev;
+            A.holders = nullptr;
+            I.ring_cap = c->innov_cap;
+            I.ring_at = c->innov_next + at;
+            I.tag = c->innov_tag_dev;
+            I.record = (int32_t) c->innov_records;
+        } else {
+            A.out = reinterpret_cast<double *>(c->msum_dev + o_out) + (size_t) kInnStride * at;
+            A.holders = reinterpret_cast<int32_t *>(c->msum_dev + o_hold) + at;
+        }
+        {
+            Timed t(c, "innovation_summary");
+            c->k->innovation_summary(c->stream, c->B, c->ws, I);
+        }
+        HIP_TRY(hipGetLastError());
+        {
+            Timed t(c, "innovation_finish");
+            c->k->innovation_finish(c->stream, I);
+        }
+        HIP_TRY(hipGetLastError());
+    }
+    if (out_dev) *out_dev = reinterpret_cast<const double *>(c->msum_dev + o_out);
+    if (hold_dev) *hold_dev = reinterpret_cast<const int32_t *>(c->msum_dev + o_hold);
+    return 0;
+}
+
+// slamgpu_innovation_record past its context checks (slamgpu_step calls it with its own packet)
+int innov_append(slamgpu_ctx *c, const float *zf, const int32_t *idf, int32_t m, const float *R) {
+    if (int rc = innov_check(c, "slamgpu_innovation_record", zf, idf, m, R)) return rc;
+    if (m > c->innov_cap)
+        return fail(SLAMGPU_ERR_CAPACITY, "slamgpu_innovation_record: %d observations, the ring holds %d entries", m, c->innov_cap);
+    if (m > 0) {
+        if (int rc = innov_launch(c, zf, idf, m, R, true, nullptr, nullptr)) return rc;
+        c->innov_next += m;
+        if (c->innov_next - c->innov_first > c->innov_cap) c->innov_first = c->innov_next - c->innov_cap;
+    }
+    c->innov_records++;
+    return 0;
+}
+
 int path_identity(slamgpu_ctx *c) {
     Timed t(c, "path_compose");
     c->k->path_compose(c->stream, c->B, c->ws, 0, nullptr, c->path_origin_dev[c->path_org]);
@@ -1156,6 +1301,11 @@ void slamgpu_destroy(slamgpu_ctx *c) {
     if (c->msum_dev) (void) hipFree(c->msum_dev);
     if (c->pose_ring_dev) (void) hipFree(c->pose_ring_dev);
     if (c->pose_dev) (void) hipFree(c->pose_dev);
+    if (c->innov_ring_dev) (void) hipFree(c->innov_ring_dev);
+    if (c->innov_tag_dev) (void) hipFree(c->innov_tag_dev);
+    if (c->innov_host) (void) hipHostFree(c->innov_host);
+    for (hipEvent_t e : c->innov_ev)
+        if (e) (void) hipEventDestroy(e);
     if (c->path_rec_dev) (void) hipFree(c->path_rec_dev);
     for (int b = 0; b < 2; b++)
         if (c->path_origin_dev[b]) (void) hipFree(c->path_origin_dev[b]);
@@ -1790,8 +1940,12 @@ int slamgpu_step(slamgpu_ctx *c, const float *controls, int32_t n_controls, cons
     if (n_controls < 0 || (n_controls > 0 && !controls)) return fail(SLAMGPU_ERR_INVALID, "bad control list");
     if (n_controls > 0 && c->cfg.add_predict_noise && c->cfg.rng_mode == SLAMGPU_RNG_TAPE)
         return fail(SLAMGPU_ERR_INVALID, "slamgpu_step cannot carry TAPE-mode predict noise: call slamgpu_predict per control");
+    if (c->innov_cap > 0 && m > c->innov_cap)  // (refused before anything is applied: the record between predicts and update could not be made)
+        return fail(SLAMGPU_ERR_CAPACITY, "slamgpu_step: %d observations, the innovation ring holds %d entries", m, c->innov_cap);
     for (int k = 0; k < n_controls; k++)
         if (int rc = slamgpu_predict(c, controls[3 * k], controls[3 * k + 1], Q, dt, controls[3 * k + 2], nullptr)) return rc;
+    if (c->innov_cap > 0)  // the innovation ring: this step's packet against the predicted set, before the update takes it
+        if (int rc = innov_append(c, zf, idf, m, R)) return rc;
     if (int rc = slamgpu_update(c, zf, idf, m, zn, n, R, normals, strata)) return rc;
     if (record_estimate) {
         if (int rc = slamgpu_estimate_async(c)) return rc;
@@ -5121,6 +5275,101 @@ int slamgpu_pose_history_fetch(slamgpu_ctx *c, int64_t first, int32_t count, dou
                                hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     memcpy(out, h.data(), sizeof(double) * h.size());
+    return 0;
+}
+
+int slamgpu_innovation_summary(slamgpu_ctx *c, const float *zf, const int32_t *idf, int32_t m, const float R[4], double *out, int32_t *holders) {
+    if (int rc = check_ctx(c)) return rc;
+    if (c->dist || c->cfg.n_particles_global != c->cfg.n_particles)
+        return fail(SLAMGPU_ERR_INVALID, "slamgpu_innovation_summary: single contexts only");
+    if (int rc = innov_check(c, "slamgpu_innovation_summary", zf, idf, m, R)) return rc;
+    if (m == 0) return 0;
+    if (!out) return fail(SLAMGPU_ERR_INVALID, "slamgpu_innovation_summary: null output");
+    const double *out_dev = nullptr;
+    const int32_t *hold_dev = nullptr;
+    if (int rc = innov_launch(c, zf, idf, m, R, false, &out_dev, &hold_dev)) return rc;
+    HIP_TRY(hipMemcpyAsync(out, out_dev, sizeof(double) * kInnStride * (size_t) m, hipMemcpyDeviceToHost, c->stream));
+    if (holders) HIP_TRY(hipMemcpyAsync(holders, hold_dev, sizeof(int32_t) * (size_t) m, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+int slamgpu_innovation_history_enable(slamgpu_ctx *c, int32_t capacity) {
+    if (int rc = check_ctx(c)) return rc;
+    if (c->dist || c->cfg.n_particles_global != c->cfg.n_particles)
+        return fail(SLAMGPU_ERR_INVALID, "slamgpu_innovation_history_enable: single contexts only");
+    if (capacity < 0) return fail(SLAMGPU_ERR_INVALID, "slamgpu_innovation_history_enable: capacity %d", capacity);
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    // the new ring first: a refused call leaves the setting as it was
+    double *ring = nullptr;
+    int32_t *tag = nullptr;
+    if (capacity > 0) {
+        const size_t bytes = sizeof(double) * kInnStride * (size_t) capacity;
+        hipError_t e = hipMalloc((void **) &ring, bytes);
+        if (e == hipSuccess) {
+            e = hipMalloc((void **) &tag, sizeof(int32_t) * 2 * (size_t) capacity);
+            if (e != hipSuccess) (void) hipFree(ring);
+        }
+        if (e != hipSuccess) {
+            (void) hipGetLastError();
+            return fail(SLAMGPU_ERR_ALLOC, "slamgpu_innovation_history_enable: %d entries (%zu bytes): %s", capacity, bytes, hipGetErrorString(e));
+        }
+    }
+    if (c->innov_ring_dev) {
+        HIP_TRY(hipStreamSynchronize(c->stream));  // (launches in flight may still write the old ring)
+        (void) hipFree(c->innov_ring_dev);
+        (void) hipFree(c->innov_tag_dev);
+    }
+    c->innov_ring_dev = ring;
+    c->innov_tag_dev = tag;
+    c->innov_cap = capacity;
+    c->innov_first = c->innov_next = c->innov_records = 0;
+    return 0;
+}
+
+int slamgpu_innovation_record(slamgpu_ctx *c, const float *zf, const int32_t *idf, int32_t m, const float R[4]) {
+    if (int rc = check_ctx(c)) return rc;
+    if (c->dist || c->cfg.n_particles_global != c->cfg.n_particles)
+        return fail(SLAMGPU_ERR_INVALID, "slamgpu_innovation_record: single contexts only");
+    if (c->innov_cap == 0) return fail(SLAMGPU_ERR_INVALID, "slamgpu_innovation_record: the ring is off (slamgpu_innovation_history_enable)");
+    return innov_append(c, zf, idf, m, R);
+}
+
+int slamgpu_innovation_history_info(slamgpu_ctx *c, int64_t *first, int64_t *next, int32_t *capacity, int64_t *records) {
+    if (int rc = check_ctx(c)) return rc;
+    if (first) *first = c->innov_first;
+    if (next) *next = c->innov_next;
+    if (capacity) *capacity = c->innov_cap;
+    if (records) *records = c->innov_records;
+    return 0;
+}
+
+int slamgpu_innovation_history_fetch(slamgpu_ctx *c, int64_t first, int32_t count, double *out, int32_t *record, int32_t *slot) {
+    if (int rc = check_ctx(c)) return rc;
+    if (count < 0 || first < c->innov_first || first + count > c->innov_next)
+        return fail(SLAMGPU_ERR_INVALID, "slamgpu_innovation_history_fetch: entries [%lld, %lld + %lld) outside the retained [%lld, %lld)",
+                    (long long) first, (long long) first, (long long) count, (long long) c->innov_first, (long long) c->innov_next);
+    if (count == 0) return 0;
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    std::vector<double> h((size_t) kInnStride * (size_t) count);
+    std::vector<int32_t> tg((size_t) 2 * (size_t) count);
+    // at most two stretches of the ring
+    const int64_t at = first % c->innov_cap, n0 = std::min<int64_t>(count, c->innov_cap - at);
+    HIP_TRY(hipMemcpyAsync(h.data(), c->innov_ring_dev + (size_t) kInnStride * (size_t) at, sizeof(double) * kInnStride * (size_t) n0,
+                           hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(tg.data(), c->innov_tag_dev + (size_t) 2 * (size_t) at, sizeof(int32_t) * 2 * (size_t) n0, hipMemcpyDeviceToHost, c->stream));
+    if (n0 < count) {
+        HIP_TRY(hipMemcpyAsync(h.data() + (size_t) kInnStride * (size_t) n0, c->innov_ring_dev, sizeof(double) * kInnStride * (size_t) (count - n0),
+                               hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(tg.data() + (size_t) 2 * (size_t) n0, c->innov_tag_dev, sizeof(int32_t) * 2 * (size_t) (count - n0), hipMemcpyDeviceToHost,
+                               c->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (out) memcpy(out, h.data(), sizeof(double) * h.size());
+    for (int32_t q = 0; q < count; q++) {
+        if (record) record[q] = tg[2 * (size_t) q];
+        if (slot) slot[q] = tg[2 * (size_t) q + 1];
+    }
     return 0;
 }
 

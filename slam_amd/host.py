@@ -15,10 +15,11 @@ DECLARED_SYMBOLS = [
     "slamhost_synthetic_landmarks", "slamhost_write_map", "slamhost_ekf_create", "slamhost_ekf_destroy", "slamhost_ekf_step",
     "slamhost_ekf_state", "slamhost_plot_open", "slamhost_plot_close", "slamhost_plot_xy", "slamhost_plot_matrix",
     "slamhost_plot_doubles", "slamhost_plot_car_size", "slamhost_plot_u32", "slamhost_plot_cmd", "slamhost_plot_name",
-    "slamhost_map_candidates", "slamhost_map_merge", "slamhost_pose_nees",
+    "slamhost_map_candidates", "slamhost_map_merge", "slamhost_pose_nees", "slamhost_innovation_nis",
 ]
 MAP_STRIDE = 9  # SLAMGPU_MAP_STRIDE
 POSE_STRIDE = 18  # SLAMGPU_POSE_STRIDE
+INNOV_STRIDE = 10  # SLAMGPU_INNOV_STRIDE
 NEES_CHI2_95 = 7.8147  # the 95 % point of chi^2 with 3 degrees of freedom
 
 
@@ -90,6 +91,8 @@ def load_library():
                                          C.POINTER(C.c_int32)]
         L.slamhost_pose_nees.restype = C.c_int32
         L.slamhost_pose_nees.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.slamhost_innovation_nis.restype = C.c_int32
+        L.slamhost_innovation_nis.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
         _lib = L
     return _lib
 
@@ -178,6 +181,18 @@ def pose_nees(summary, xtrue):
     if bad < 0:
         raise ValueError("slamhost_pose_nees: bad arguments")
     return nees, err, int(bad)
+
+
+def innovation_nis(entries):
+    """slamhost_innovation_nis: the NIS of the predicted-measurement mixture for entries of SlamGpu.innovation_summary /
+    innovation_history_fetch ([count, 10] or one [10]).  Returns (nis[count], bad): NaN where the share is 0, anything is NaN or
+    P = scatter + mean S is not positive definite, and how many such entries there are"""
+    t = np.ascontiguousarray(entries, np.float64).reshape(-1, INNOV_STRIDE)
+    nis = np.zeros(len(t), np.float64)
+    bad = load_library().slamhost_innovation_nis(_p(t), len(t), _p(nis))
+    if bad < 0:
+        raise ValueError("slamhost_innovation_nis: bad arguments")
+    return nis, int(bad)
 
 
 class HostSim:
