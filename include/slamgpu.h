@@ -560,6 +560,37 @@ int slamgpu_map_summary(slamgpu_ctx *ctx, int32_t first_slot, int32_t count, dou
  * outside the range, count < 0, NULL pairs or out with count > 0, a distributed or shard context.  count == 0 does nothing.
  * Synchronises. */
 int slamgpu_map_pairs(slamgpu_ctx *ctx, const int32_t *pairs, int32_t count, double *out, int32_t *both);
+/* Joint posterior: the pose AND the listed landmarks together, in the ordering of an EKF-SLAM state (slamhost_ekf_state).  Every
+ * other summary is a marginal; the cross terms between pose and landmarks and between two landmarks, which a Rao-Blackwellised
+ * filter carries only in its particle set, are here.  slots[0 .. k) are any slots of [0, slamgpu_num_landmarks), 0 <= k <=
+ * SLAMGPU_JOINT_MAX_SLOTS; the same slot may appear more than once (its rows and columns then repeat).  The particle set, the
+ * weights w^_i and every convention are slamgpu_map_summary's: queued predicts flushed, the outstanding resampling stage run, a
+ * pending gather read through its ancestors with weight 1/N, records through the genealogy, log-weights as exp(l - max l),
+ * normalised over ALL N particles.  J is the particles that hold EVERY listed slot (no record absent; k == 0: all particles).  For
+ * particle i, promoted to double, D = 3 + 2 k entries
+ *     v_i = (x_i, y_i, u_i, xf_s0.x, xf_s0.y, xf_s1.x, ...),   u_i = IEEE remainder(theta_i - theta_p, 2 pi),
+ * theta_p the heading of particle 0 of the set: slamgpu_pose_summary's convention, with its caveat about heading clouds wider
+ * than pi.  out[SLAMGPU_JOINT_SIZE(k)], with T = D (D + 1) / 2:
+ *     [0]                  joint share s = sum_{i in J} w^_i
+ *     [1 .. D]             mean mu = sum_{i in J} w^_i v_i / s; entry 3 is theta_p + mean u, not wrapped
+ *     [1 + D .. 1 + D + T) between-particle scatter C = sum_{i in J} w^_i (v_i - mu)(v_i - mu)^T / s, the lower triangle row-major:
+ *                          entry (r, c), c <= r, at offset r (r + 1) / 2 + c
+ *     next 6               sum_{i in J} w^_i Pv_i / s: p00, p10, p11, p20, p21, p22 (as stored)
+ *     next 3 k             per listed slot sum_{i in J} w^_i Pf_i / s: p00, p10, p11
+ * and *both (may be NULL) = |J|, exact.  The total joint covariance is C + blockdiag(mean Pv, mean Pf_0, ...), the split of the
+ * other summaries; its off-diagonal blocks come from C alone (slamhost_joint_dense assembles it).  J empty: share 0, both 0, every
+ * other entry NaN.  Weights that sum to zero or to nothing finite: every double NaN, the call returns 0, both still exact.  N = 1:
+ * C is exactly 0.  Sums are in double about ONE pivot (the vector of the lowest-index particle of J), in a fixed order, without
+ * floating-point atomics: the same state gives the same bits on every call, under a pending gather as well as after
+ * slamgpu_download has settled it, and however the call cuts its work into chunks.  The bits are NOT promised equal under a
+ * permutation of `slots`: the products go through a matrix instruction whose two operands (w d and d) round differently, and which
+ * of two coordinates is which depends on their order.  Read-only like slamgpu_peek: the state the next step works on is bit for bit
+ * what it would have been without the call.  SLAMGPU_ERR_INVALID, outputs untouched: a slot outside the range, k < 0 or k >
+ * SLAMGPU_JOINT_MAX_SLOTS, NULL out, NULL slots with k > 0, a distributed or shard context.  Synchronises.  With the call never made
+ * nothing is allocated and no kernel of it is launched.  Cost: DESIGN.md section 7g. */
+#define SLAMGPU_JOINT_MAX_SLOTS 126                       /* D = 3 + 2k <= 255 */
+#define SLAMGPU_JOINT_SIZE(k)  (1 + (3 + 2*(k)) + (3 + 2*(k))*(4 + 2*(k))/2 + 6 + 3*(k))
+int slamgpu_joint_summary(slamgpu_ctx *ctx, const int32_t *slots, int32_t k, double *out, int32_t *both);
 
 /* ---- path posterior: recorded ancestry, traces, the smoothed path ---------------------------------------------------
  * FastSLAM's posterior is over paths and maps; these entry points report the path half.  "The set" at a moment is what

@@ -130,6 +130,15 @@ int32_t slamhost_pose_nees(const double *summary, int32_t count, const float *xt
  * NIS, leaves the pose uncertainty out of S and reads too large.  -1: bad arguments (a negative count, a NULL array with count > 0). */
 int32_t slamhost_innovation_nis(const double *entries, int32_t count, double *nis);
 
+/* The joint posterior of one slamgpu_joint_summary (joint[SLAMGPU_JOINT_SIZE(k)], k listed slots, D = 3 + 2 k) as an EKF-SLAM state
+ * in the ordering of slamhost_ekf_state: x[D] = the mean, the heading wrapped into (-pi, pi], and P (D x D, row-major, leading
+ * dimension ld >= D) = the dense symmetric total covariance: the scatter, plus mean Pv on the 3 x 3 pose block and the mean Pf of
+ * listed slot s on the 2 x 2 block at 3 + 2 s.  The off-diagonal blocks are the scatter's alone: inside a particle the landmarks are
+ * independent given its path.  Returns 0 when P is positive definite, judged by a Cholesky factorisation in double; 1 when it is not
+ * (N = 1, a collapsed set); -1 for bad arguments (a NULL array, k outside [0, 126], ld < D: nothing is written) or an
+ * input that holds a NaN (J empty, degenerate weights): x and P are then filled as far as the input goes, NaN where it is NaN. */
+int32_t slamhost_joint_dense(const double *joint, int32_t k, double *x, double *P, int32_t ld);
+
 void slamhost_draw_normals(int32_t count, int32_t dim, float *out); /* count x randn(dim,1): dim+1 rand() each */
 int32_t slamhost_draw_strata(int32_t N, float *out);                /* returns the reference's strata count (== N when supported) */
 double slamhost_unif_rand(void);                                    /* unifRand (core.cpp:775) */

@@ -29,7 +29,7 @@ DECLARED_SYMBOLS = [
     "slamgpu_run_particle", "slamgpu_particle_report_fetch", "slamgpu_particle_list_stats",
     "slamgpu_set_particle_excl_spacing", "slamgpu_particle_excl_radii",
     "slamgpu_set_particle_assoc_sampling", "slamgpu_particle_sample_stats", "slamgpu_particle_labels",
-    "slamgpu_map_summary", "slamgpu_map_pairs", "slamgpu_set_particle_mutex", "slamgpu_particle_mutex_stats",
+    "slamgpu_map_summary", "slamgpu_map_pairs", "slamgpu_joint_summary", "slamgpu_set_particle_mutex", "slamgpu_particle_mutex_stats",
     "slamgpu_set_particle_miss", "slamgpu_particle_missed", "slamgpu_particle_miss_stats", "slamgpu_particle_miss_visited",
     "slamgpu_path_enable", "slamgpu_path_record", "slamgpu_path_info", "slamgpu_path_fetch", "slamgpu_path_trace", "slamgpu_path_summary",
     "slamgpu_pose_summary", "slamgpu_pose_history_enable", "slamgpu_pose_history_record", "slamgpu_pose_history_info",
@@ -45,6 +45,14 @@ ASSOC_AUTO, ASSOC_EXHAUSTIVE, ASSOC_GRID, ASSOC_LISTS = 0, 1, 2, 3
 FLAG_DEVICE_OBSERVE = 1
 FLAG_NO_REFERENCE_RESAMPLE = 2
 FLAG_PARTICLE_MAPS = 4
+
+
+JOINT_MAX_SLOTS = 126  # SLAMGPU_JOINT_MAX_SLOTS
+
+
+def joint_size(k):
+    """SLAMGPU_JOINT_SIZE(k)"""
+    return 1 + (3 + 2 * k) + (3 + 2 * k) * (4 + 2 * k) // 2 + 6 + 3 * k
 
 
 class SlamGpuError(RuntimeError):
@@ -147,6 +155,8 @@ def load_library():
         L.slamgpu_map_summary.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
     if hasattr(L, "slamgpu_map_pairs"):
         L.slamgpu_map_pairs.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+    if hasattr(L, "slamgpu_joint_summary"):
+        L.slamgpu_joint_summary.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
     if hasattr(L, "slamgpu_pose_summary"):
         L.slamgpu_pose_summary.argtypes = [C.c_void_p, C.c_void_p]
         L.slamgpu_pose_history_enable.argtypes = [C.c_void_p, C.c_int32]
@@ -582,6 +592,24 @@ class SlamGpu:
         both = np.zeros(count, np.int32)
         _chk(self.L.slamgpu_map_pairs(self.h, _ptr(pairs), count, _ptr(out), _ptr(both)))
         return dict(share=out[:, 0].copy(), mean=out[:, 1:3].copy(), scatter=out[:, 3:6].copy(), pf=out[:, 6:9].copy(), both=both)
+
+    def joint_summary(self, slots):
+        """slamgpu_joint_summary: the pose and the listed landmark slots together, over the particles that hold EVERY listed slot, in the
+        EKF's ordering (D = 3 + 2 k): share, mean[D] (entry 2 the heading, not wrapped), scatter[D, D] (full symmetric), pv[6] (mean Pv:
+        p00, p10, p11, p20, p21, p22), pf[k, 3] (mean Pf per listed slot), both (the number of such particles) and raw (the call's flat
+        output, what host.joint_dense takes); the weights and conventions of map_summary; rewrites no state"""
+        slots = np.ascontiguousarray(slots, np.int32).reshape(-1)
+        k = len(slots)
+        D = 3 + 2 * k
+        T = D * (D + 1) // 2
+        out = np.zeros(joint_size(k), np.float64)
+        both = C.c_int32()
+        _chk(self.L.slamgpu_joint_summary(self.h, _ptr(slots) if k else None, k, _ptr(out), C.byref(both)))
+        sc = np.zeros((D, D), np.float64)
+        sc[np.tril_indices(D)] = out[1 + D:1 + D + T]
+        sc = sc + np.tril(sc, -1).T
+        return dict(share=float(out[0]), mean=out[1:1 + D].copy(), scatter=sc, pv=out[1 + D + T:1 + D + T + 6].copy(),
+                    pf=out[1 + D + T + 6:].reshape(k, 3).copy(), both=int(both.value), raw=out)
 
     def path_enable(self, capacity):
         """slamgpu_path_enable: record the path posterior in a ring of `capacity` records (0: stop and free)"""

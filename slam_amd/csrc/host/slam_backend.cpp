@@ -36,6 +36,12 @@
 //                        landmark and are merged (slamhost_map_merge): the merged landmarks with share >= 0.5, the true landmarks within
 //                        1 m of one of them, those of them within 1 m of no true landmark, the clusters of more than one slot, and the
 //                        largest joint share among the candidate pairs.  Not with -gpus k > 1.
+//   -map joint           posterior's line, and one more from slamgpu_joint_summary over the slots held by at least half of the weight
+//                        (ascending, the first SLAMGPU_JOINT_MAX_SLOTS of them): k, D = 3 + 2 k, the joint share and the particles that hold
+//                        them all; the square root of the trace of the pose position block of P = scatter + blockdiag(mean Pv, mean Pf ...)
+//                        (slamhost_joint_dense); whether P is positive definite; the largest |correlation| between a pose coordinate and
+//                        a landmark coordinate, and between coordinates of two different landmarks.  -JOINT_OUT path writes x and P as
+//                        text: first line D, then x, then the D rows of P (%.17g).  Not with -gpus k > 1, not for the EKF.
 //   -LOG_WEIGHTS 0|1     1: the particle weights are kept as log-weights (slamgpu_config.log_weights): dense maps, where linear weights
 //                        underflow within a few steps and -map posterior / merged could only print "not available".  Default 0; single
 //                        GPU only.
@@ -119,6 +125,9 @@ static void usage(const char *a0) {
     printf("                        share (slamgpu_map_pairs) is at most -MAP_MERGE_COHOLD (default 0.1: a chosen default, no accuracy claim rests on it yet)\n");
     printf("                        x the smaller of their shares are merged into one landmark (slamhost_map_merge; not with -gpus)\n");
     printf("    -LOG_WEIGHTS 0|1    keep the particle weights as log-weights (default 0; dense maps, where linear weights underflow; not with -gpus)\n");
+    printf("    -map joint          posterior's line and one more: the pose and the slots held by at least half of the weight TOGETHER (slamgpu_joint_summary):\n");
+    printf("                        k, D, joint share, holders, pose position sigma, whether P is positive definite, the largest pose-landmark and\n");
+    printf("                        landmark-landmark |correlation|.  -JOINT_OUT path: D, x and the D rows of P as text (%%.17g).  Not with -gpus k > 1 or the EKF\n");
     printf("    -path none|smoothed smoothed: record the path posterior (one record per observation step, -PATH_RECORDS n of them kept, default 4096)\n");
     printf("                        and print one more line: the smoothed path's distance to the true path beside the filtered estimates', and the\n");
     printf("                        distinct ancestors 1 / 10 / 100 records back (slamgpu_path_summary; FastSLAM, one GPU, not -assoc particle -observe device)\n");
@@ -313,6 +322,51 @@ static void print_merged_map(slamgpu_ctx *ctx, const Simulator &sim, const std::
            "no true landmark); %d clusters of more than one slot; largest joint share of the %lld candidate pairs %.6f (radius %g m, cohold %g)\n",
            confident, covered, sim.map.nlm, stray, multi, (long long) ncand, top, g_merge_radius, g_merge_cohold);
 }
+// -map joint: the posterior line, then the joint posterior of the pose and the confident slots (slamgpu_joint_summary)
+static bool g_map_joint = false;
+static std::string g_joint_out;
+static void print_joint(slamgpu_ctx *ctx, const std::vector<double> &sum, int slots) {
+    std::vector<int32_t> list;
+    for (int j = 0; j < slots && (int) list.size() < SLAMGPU_JOINT_MAX_SLOTS; j++)
+        if (sum[(size_t) SLAMGPU_MAP_STRIDE * (size_t) j] >= 0.5) list.push_back(j);
+    const int k = (int) list.size(), D = 3 + 2 * k;
+    std::vector<double> out((size_t) SLAMGPU_JOINT_SIZE(k)), x((size_t) D), P((size_t) D * (size_t) D);
+    int32_t both = 0;
+    if (slamgpu_joint_summary(ctx, list.data(), k, out.data(), &both) != 0) {
+        fprintf(stderr, "slamgpu: %s\n", slamgpu_last_error());
+        return;
+    }
+    const int32_t status = slamhost_joint_dense(out.data(), k, x.data(), P.data(), D);
+    if (status < 0) {
+        printf("joint posterior: not available, k %d, %d particles hold them all (joint share %.6f)\n", k, both, out[0]);
+        return;
+    }
+    auto corr = [&](int a, int b) {
+        const double d = P[(size_t) a * D + a] * P[(size_t) b * D + b];
+        return d > 0.0 ? fabs(P[(size_t) a * D + b]) / sqrt(d) : 0.0;
+    };
+    double cpl = 0.0, cll = 0.0;
+    for (int a = 3; a < D; a++) {
+        for (int b = 0; b < 3; b++) cpl = std::max(cpl, corr(a, b));
+        for (int b = 3; b < a; b++)
+            if ((a - 3) / 2 != (b - 3) / 2) cll = std::max(cll, corr(a, b));
+    }
+    printf("joint posterior: k %d, D %d, joint share %.6f, %d particles hold them all; pose position sigma %.6f m; P is %s; largest |correlation| "
+           "pose-landmark %.6f, landmark-landmark %.6f\n",
+           k, D, out[0], both, sqrt(P[0] + P[(size_t) D + 1]), status == 0 ? "positive definite" : "NOT positive definite", cpl, cll);
+    if (!g_joint_out.empty()) {
+        FILE *f = fopen(g_joint_out.c_str(), "w");
+        if (!f) {
+            fprintf(stderr, "-JOINT_OUT %s: cannot write\n", g_joint_out.c_str());
+            return;
+        }
+        fprintf(f, "%d\n", D);
+        for (int a = 0; a < D; a++) fprintf(f, "%.17g%c", x[(size_t) a], a + 1 < D ? ' ' : '\n');
+        for (int r = 0; r < D; r++)
+            for (int c = 0; c < D; c++) fprintf(f, "%.17g%c", P[(size_t) r * D + c], c + 1 < D ? ' ' : '\n');
+        fclose(f);
+    }
+}
 static void print_posterior_map(slamgpu_ctx *ctx, const Simulator &sim) {
     if (!g_map_posterior) return;
     const int slots = slamgpu_num_landmarks(ctx);
@@ -323,6 +377,7 @@ static void print_posterior_map(slamgpu_ctx *ctx, const Simulator &sim) {
     }
     if (slots > 0 && sum[0] != sum[0]) {  // (every entry NaN: slamgpu_map_summary's answer to weights that sum to zero or to nothing finite)
         printf("posterior map: not available, the weights are degenerate (SLAMGPU_STATUS_DEGENERATE: their sum is zero or not finite)\n");
+        if (g_map_joint) printf("joint posterior: not available, the weights are degenerate\n");
         return;
     }
     int confident = 0, covered = 0, stray = 0, minority = 0, dead = 0;
@@ -348,6 +403,7 @@ static void print_posterior_map(slamgpu_ctx *ctx, const Simulator &sim) {
            "within 1 m of no true landmark); %d slots held by less than half, %d by none\n",
            confident, covered, sim.map.nlm, stray, minority, dead);
     if (g_map_merged) print_merged_map(ctx, sim, sum, slots);
+    if (g_map_joint) print_joint(ctx, sum, slots);
 }
 
 // -path smoothed: the recorded path posterior (slamgpu_path_*).  Record r belongs to observation step r: g_path_steps[r] holds that
@@ -685,13 +741,24 @@ int main(int argc, char **argv) {
     {
         // -map is this program's own report option, not a setting of the run: it stays out of the settings printed below
         const std::string m = sim.conf.s("map");
-        if (!m.empty() && m != "best" && m != "posterior" && m != "merged") {
-            fprintf(stderr, "-map best|posterior|merged\n");
+        if (!m.empty() && m != "best" && m != "posterior" && m != "merged" && m != "joint") {
+            fprintf(stderr, "-map best|posterior|merged|joint\n");
             return EXIT_FAILURE;
         }
         g_map_merged = m == "merged";
-        g_map_posterior = m == "posterior" || g_map_merged;
+        g_map_joint = m == "joint";
+        g_map_posterior = m == "posterior" || g_map_merged || g_map_joint;
         sim.conf.kv.erase("map");
+        g_joint_out = sim.conf.s("JOINT_OUT");
+        sim.conf.kv.erase("JOINT_OUT");
+        if (!g_joint_out.empty() && !g_map_joint) {
+            fprintf(stderr, "-JOINT_OUT path: with -map joint\n");
+            return EXIT_FAILURE;
+        }
+        if (g_map_joint && sim.conf.method == 0) {
+            fprintf(stderr, "-map joint: FastSLAM only (the EKF's joint posterior is its own state and P)\n");
+            return EXIT_FAILURE;
+        }
         const std::string mr = sim.conf.s("MAP_MERGE_RADIUS"), mc = sim.conf.s("MAP_MERGE_COHOLD");
         if (!mr.empty()) g_merge_radius = atof(mr.c_str());
         if (!mc.empty()) g_merge_cohold = atof(mc.c_str());
@@ -792,8 +859,8 @@ int main(int argc, char **argv) {
     }
     if (c.method != 0 && !c.s("gpus").empty() && atoi(c.s("gpus").c_str()) != 1) {
         if (g_map_posterior) {
-            fprintf(stderr, "-map %s: single GPU only (slamgpu_map_summary%s no distributed form)\n", g_map_merged ? "merged" : "posterior",
-                    g_map_merged ? " and slamgpu_map_pairs have" : " has");
+            fprintf(stderr, "-map %s: single GPU only (slamgpu_map_summary%s no distributed form)\n", g_map_merged ? "merged" : g_map_joint ? "joint" : "posterior",
+                    g_map_merged ? " and slamgpu_map_pairs have" : g_map_joint ? " and slamgpu_joint_summary have" : " has");
             return EXIT_FAILURE;
         }
         if (!c.s("LOG_WEIGHTS").empty() && c.s("LOG_WEIGHTS") != "0") {

@@ -686,6 +686,44 @@ struct InnovArgs {
     int32_t record;
 };
 
+// Joint posterior (slamgpu_joint_summary): over the particle set and with the weights of slamgpu_map_summary, the mean and the
+// between-particle scatter of v = (x, y, u, xf_s0, xf_s1, ...) (D = 3 + 2 k entries, u the heading's deviation as in the pose summary)
+// over the particles J that hold EVERY listed slot, and the mean Pv / Pf of J.  Four passes:
+//   joint_hold_kernel    grid (tiles of kMapTile particles): hold[i] = particle i is in J; per tile the lowest such index and their number
+//                        (integers); the tile's sum of weights into S.wpart by summary_weights.inl
+//   joint_pivot_kernel   one workgroup: the lowest-index particle of J, |J|, and that particle's vector as the pivot p[0 .. D)
+//   joint_gram_kernel    grid (tiles, groups of kJointGroup block pairs): sum w d_ext d_ext^T over the tile, d_ext = (v - p, 1) padded with
+//                        zeros to Dp = a multiple of 16 columns (column D, the 1, carries sum w d and sum w), as 16 x 16 blocks of the
+//                        lower triangle (block pair R (R + 1) / 2 + C, C <= R), four particles per v_mfma_f64_16x16x4_f64 with A = w d
+//                        and B = d.  A sub-tile of kJointSub particles is centred into LDS once per workgroup (thread: one particle,
+//                        every 16th item; item 0 the pose, item 1 + s slot s; all its records requested before any is used) and each
+//                        wave runs its 4 block pairs over it.  Particles outside J enter as w = 0, d = 0.  One 16 x 16 partial per tile
+//                        and block pair goes to S.part; the group that holds block pair 0 also adds sum w Pv / Pf (plain FMAs) into pvf
+//                        (its w[] come from the same summary_weights.inl text, which stores the tile's same S.wpart again)
+//   joint_reduce_kernel  per block pair of the chunk: the tiles' partials added in ascending order (log-weights: each scaled by
+//                        exp(M_t - max M)) into `sums`
+//   joint_finish_kernel  s, delta = sum w d / s, mu = p + delta, C = sum w d d^T / s - delta delta^T, the means of Pv / Pf; out / both
+// One pivot for all tiles: partials merge by plain addition, and the only cancellation is at the size of the cloud.
+constexpr int kJointMaxSlots = 126;        // SLAMGPU_JOINT_MAX_SLOTS: D + 1 <= 256 columns
+constexpr int kJointCols = 256;            // columns at most, the padding included (one per thread of a workgroup)
+constexpr int kJointSub = 16;              // particles per LDS sub-tile
+constexpr int kJointGroup = 16;            // block pairs per workgroup: 4 per wave
+constexpr int kJointLdMax = kJointCols + 16;  // LDS row stride at most (an odd multiple of 16 doubles: two particles' rows never share banks)
+struct JointArgs {
+    MapSummaryArgs S;           // tiles, logw, wpart as everywhere; part [tiles][bp_count][256] this launch's partials; out [SLAMGPU_JOINT_SIZE(k)];
+                                // holders [1]: |J| (first_slot, count are not read)
+    int32_t k, D, Dp;           // slots listed; 3 + 2 k; D + 1 rounded up to a multiple of 16
+    int32_t bp_first, bp_count; // this launch's block pairs
+    int32_t plain;              // diagnostic (SLAMGPU_JOINT_PLAIN_FMA=1): the Gram pass by plain double FMAs in the place of the matrix instruction
+    const int32_t *slots;       // [k] each inside [0, number of slots)
+    uint8_t *hold;              // [n]
+    int32_t *tile_info;         // [tiles][2]: lowest index of J in the tile (INT_MAX: none) | members of J in the tile
+    int32_t *info;              // [2]: lowest index of J (-1: J is empty) | |J|
+    double *pivot;              // [kJointCols]: p, zero from D on
+    double *sums;               // [Dp / 16 (Dp / 16 + 1) / 2][256]: sum w d_ext d_ext^T, 16 x 16 row-major per block pair
+    double *pvf;                // [tiles][6 + 3 k]: sum w Pv (p00, p10, p11, p20, p21, p22) | per listed slot sum w Pf (p00, p10, p11)
+};
+
 // ---- gated association with a spatial prefilter (slamgpu_associate_ex) ------------------------------------------------------
 // Per landmark j, over ALL particles: the bounding box of its position estimates and the largest trace of its covariance
 // (lmk_box_kernel, recomputed when the landmark is written), and from them a radius rho_j such that a particle's estimate of j
@@ -1013,6 +1051,13 @@ struct KernelTable {
     // pass into the staging area or the ring.  Tables in sync; reads only
     void (*innovation_summary)(hipStream_t, const Buffers &, const WeightScratch &, const InnovArgs &);
     void (*innovation_finish)(hipStream_t, const InnovArgs &);
+    // slamgpu_joint_summary (JointArgs): joint_hold and joint_pivot once per call, joint_gram and joint_reduce once per chunk of block
+    // pairs, joint_finish once.  Tables in sync; all of them read the particle state only
+    void (*joint_hold)(hipStream_t, const Buffers &, const WeightScratch &, const JointArgs &);
+    void (*joint_pivot)(hipStream_t, const Buffers &, const WeightScratch &, const JointArgs &);
+    void (*joint_gram)(hipStream_t, const Buffers &, const WeightScratch &, const JointArgs &);
+    void (*joint_reduce)(hipStream_t, const JointArgs &);
+    void (*joint_finish)(hipStream_t, const Buffers &, const WeightScratch &, const JointArgs &);
 };
 
 const KernelTable *kernels_strict();

@@ -4770,7 +4770,8 @@ static void launch_excl_radii(hipStream_t st, const ObserveOut *obs, const float
 
 // ---- slamgpu_map_summary (kernels.h: MapSummaryArgs) -------------------------------------------------------------------------
 // the record of landmark l behind genealogy entry sl (single contexts: read_through_genealogy past its genealogy load, so that the
-// slots of one genealogy row share that load)
+// slots of one genealogy row share that load).  (record_held, with the joint summary's kernels, reads the x of the same record alone:
+// its addresses are these and change with them)
 SLAM_DEV void read_record(const Buffers &B, const int32_t *__restrict__ live, size_t S, int l, int sl, float4 &la, float &lb) {
     if (sl < 0) {
         const size_t at = (size_t) l * B.pool_cap + (sl & ~kPoolBit);
@@ -6119,6 +6120,431 @@ static void launch_innovation_finish(hipStream_t st, const InnovArgs &I) {
     hipLaunchKernelGGL(innovation_finish_kernel, dim3((I.S.count + kSlots - 1) / kSlots), dim3(kBlock), 0, st, I);
 }
 
+// ---- slamgpu_joint_summary (kernels.h: JointArgs) ------------------------------------------------------------------------------
+typedef double joint_d4 __attribute__((ext_vector_type(4)));
+static_assert(kJointCols == kBlock, "one column of the pivot per thread");
+static_assert(1 + kJointMaxSlots <= 8 * 16, "items per staging thread");
+
+// whether the record of landmark l behind genealogy entry sl is there (read_record's addresses, the x of its first half alone)
+SLAM_DEV bool record_held(const Buffers &B, const int32_t *__restrict__ live, size_t S, int l, int sl) {
+    const float x = sl < 0 ? B.poolA[(size_t) l * B.pool_cap + (sl & ~kPoolBit)].x : B.lmkA[live[l]][(size_t) l * S + sl].x;
+    return x == x;
+}
+
+// pivot pass, first half: membership of J per particle, the tile's lowest member and their number, the tile's sum of weights
+__global__ void __launch_bounds__(kBlock) joint_hold_kernel(Buffers B, WeightScratch ws, JointArgs J) {
+    constexpr int kWaves = kBlock / kWave;
+    __shared__ double sh_w[kWaves];
+    __shared__ float sh_m[kWaves];
+    __shared__ int sh_first, sh_cnt;
+    const MapSummaryArgs &A = J.S;
+    const Ctrl *ctrl = B.ctrl;
+    const int cur = ctrl->live[B.slot];
+    const bool pend = ctrl->pend[B.slot] != 0;
+    const size_t S = (size_t) B.ncap;
+    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
+    if (threadIdx.x == 0) {
+        sh_first = INT_MAX;
+        sh_cnt = 0;
+    }
+    // this lane's particles: ancestor and weight (map_summary_kernel's, operation for operation)
+    int anc[kMapT];
+    float wf[kMapT];
+    bool on[kMapT];
+    float mb = -INFINITY;
+#pragma unroll
+    for (int t = 0; t < kMapT; t++) {
+        const int i = blockIdx.x * kMapTile + t * kBlock + threadIdx.x;
+        on[t] = i < B.n;
+        anc[t] = on[t] ? (pend ? ws.keep[B.slot][i] : i) : 0;
+        wf[t] = on[t] ? (pend ? ctrl->inv_n : B.poseA[cur][anc[t]].w) : 0.0f;
+        if (on[t] && A.logw) mb = fmaxf(mb, wf[t]);
+    }
+    // (one text for every summary of this family: w[kMapT] from wf / on / mb, and the tile's sum into A.wpart)
+#include "summary_weights.inl"
+    bool hold[kMapT];
+#pragma unroll
+    for (int t = 0; t < kMapT; t++) hold[t] = on[t];
+    int row = -1;
+    int sl[kMapT];
+    for (int s = 0; s < J.k; s++) {
+        const int l = J.slots[s];
+        const int r = B.erow[l];
+        if (r != row) {  // (uniform) the slots of one genealogy row share its entries
+            row = r;
+#pragma unroll
+            for (int t = 0; t < kMapT; t++) sl[t] = on[t] ? B.gen[cur][gen_index(B.compact, S, r, (size_t) anc[t])] : 0;
+        }
+        bool h[kMapT];
+#pragma unroll
+        for (int t = 0; t < kMapT; t++) h[t] = hold[t] ? record_held(B, B.lmk_live, S, l, sl[t]) : false;
+#pragma unroll
+        for (int t = 0; t < kMapT; t++) hold[t] = h[t];
+    }
+    int first = INT_MAX, cnt = 0;
+#pragma unroll
+    for (int t = kMapT - 1; t >= 0; t--) {
+        const int i = blockIdx.x * kMapTile + t * kBlock + threadIdx.x;
+        if (on[t]) J.hold[i] = hold[t] ? 1 : 0;
+        if (hold[t]) {
+            first = i;
+            cnt++;
+        }
+    }
+    for (int d = kWave / 2; d > 0; d >>= 1) {
+        first = min(first, __shfl_xor(first, d, kWave));
+        cnt += __shfl_xor(cnt, d, kWave);
+    }
+    __syncthreads();
+    if (lane == 0) {  // (integer atomics: the result does not depend on their order)
+        atomicMin(&sh_first, first);
+        atomicAdd(&sh_cnt, cnt);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        J.tile_info[2 * blockIdx.x] = sh_first;
+        J.tile_info[2 * blockIdx.x + 1] = sh_cnt;
+    }
+}
+
+// pivot pass, second half (one workgroup): the lowest-index particle of J, |J| and that particle's vector
+__global__ void __launch_bounds__(kBlock) joint_pivot_kernel(Buffers B, WeightScratch ws, JointArgs J) {
+    __shared__ int sh_first, sh_cnt;
+    if (threadIdx.x == 0) {
+        sh_first = INT_MAX;
+        sh_cnt = 0;
+    }
+    __syncthreads();
+    int first = INT_MAX, cnt = 0;
+    for (int t = threadIdx.x; t < J.S.tiles; t += kBlock) {
+        first = min(first, J.tile_info[2 * t]);
+        cnt += J.tile_info[2 * t + 1];
+    }
+    for (int d = kWave / 2; d > 0; d >>= 1) {
+        first = min(first, __shfl_xor(first, d, kWave));
+        cnt += __shfl_xor(cnt, d, kWave);
+    }
+    if ((threadIdx.x & (kWave - 1)) == 0) {
+        atomicMin(&sh_first, first);
+        atomicAdd(&sh_cnt, cnt);
+    }
+    __syncthreads();
+    first = sh_first;
+    cnt = sh_cnt;
+    if (threadIdx.x == 0) {
+        J.info[0] = cnt ? first : -1;
+        J.info[1] = cnt;
+    }
+    const int c = threadIdx.x;
+    double p = 0.0;
+    if (cnt && c < J.D) {
+        const Ctrl *ctrl = B.ctrl;
+        const int cur = ctrl->live[B.slot];
+        const bool pend = ctrl->pend[B.slot] != 0;
+        const size_t S = (size_t) B.ncap;
+        const int a = pend ? ws.keep[B.slot][first] : first;
+        if (c < 3) {
+            const float4 pa = B.poseA[cur][a];
+            const double thp = (double) pose_pivot_heading(B, ws, cur, pend);
+            p = c == 0 ? (double) pa.x : c == 1 ? (double) pa.y : remainder((double) pa.z - thp, kPoseTwoPi);
+        } else {
+            const int l = J.slots[(c - 3) >> 1];
+            const int sl = B.gen[cur][gen_index(B.compact, S, B.erow[l], (size_t) a)];
+            float4 la;
+            float lb;
+            read_record(B, B.lmk_live, S, l, sl, la, lb);
+            p = ((c - 3) & 1) ? (double) la.y : (double) la.x;
+        }
+    }
+    J.pivot[c] = p;
+}
+
+// Gram pass: see kernels.h.  Thread tid stages particle tid & 15 of the sub-tile, items (tid >> 4) + 16 j.  MFMA false: the same
+// products from the same LDS tile by plain double FMAs, a lane the four entries of a block that the matrix instruction would leave it
+// (the comparison tools/joint_probe.py makes; JointArgs::plain)
+template <bool MFMA>
+__global__ void __launch_bounds__(kBlock) joint_gram_kernel(Buffers B, WeightScratch ws, JointArgs J) {
+#pragma clang fp contract(off)
+    constexpr int kWaves = kBlock / kWave;
+    constexpr int kItems = 8, kBatch = 4;  // items per staging thread, and how many of them it has in flight
+    __shared__ double sh_d[kJointSub * kJointLdMax];
+    __shared__ double sh_wt[kMapTile];
+    __shared__ double sh_p[kJointCols];
+    __shared__ int sh_anc[kMapTile];
+    __shared__ double sh_acc[8 * 16 * 3 + 3];  // sum w Pv / Pf: [item][3], then Pv's last three
+    __shared__ double sh_w[kWaves];
+    __shared__ float sh_m[kWaves];
+    const MapSummaryArgs &A = J.S;
+    const Ctrl *ctrl = B.ctrl;
+    const int cur = ctrl->live[B.slot];
+    const bool pend = ctrl->pend[B.slot] != 0;
+    const size_t S = (size_t) B.ncap;
+    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
+    // this lane's particles: ancestor and weight (map_summary_kernel's, operation for operation)
+    int anc[kMapT];
+    float wf[kMapT];
+    bool on[kMapT];
+    float mb = -INFINITY;
+#pragma unroll
+    for (int t = 0; t < kMapT; t++) {
+        const int i = blockIdx.x * kMapTile + t * kBlock + threadIdx.x;
+        on[t] = i < B.n;
+        anc[t] = on[t] ? (pend ? ws.keep[B.slot][i] : i) : 0;
+        wf[t] = on[t] ? (pend ? ctrl->inv_n : B.poseA[cur][anc[t]].w) : 0.0f;
+        if (on[t] && A.logw) mb = fmaxf(mb, wf[t]);
+    }
+    // (one text for every summary of this family: w[kMapT] from wf / on / mb, and the tile's sum into A.wpart)
+#include "summary_weights.inl"
+    for (int e = threadIdx.x; e < 8 * 16 * 3 + 3; e += kBlock) sh_acc[e] = 0.0;
+    // the tile's weights and ancestors by tile-local index; outside J: weight 0, no ancestor
+#pragma unroll
+    for (int t = 0; t < kMapT; t++) {
+        const int q = t * kBlock + threadIdx.x;
+        const bool h = on[t] && J.hold[blockIdx.x * kMapTile + q] != 0;
+        sh_wt[q] = h ? w[t] : 0.0;
+        sh_anc[q] = h ? anc[t] : -1;
+    }
+    sh_p[threadIdx.x] = J.pivot[threadIdx.x];
+    const int ld = (J.Dp & 16) ? J.Dp : J.Dp + 16;
+    for (int e = threadIdx.x; e < kJointSub * ld; e += kBlock) sh_d[e] = 0.0;  // (the padding columns stay zero)
+    __syncthreads();
+    const int p = threadIdx.x & (kJointSub - 1), jj = threadIdx.x / kJointSub;
+    const bool sums = J.bp_first == 0 && blockIdx.y == 0;  // this group also adds up sum w Pv / Pf
+    // (a sub-tile's 16 terms of such a sum: added across the item's 16 threads in a fixed order, then to the item's running sum)
+    auto add16 = [&](double v, int at) {
+        for (int d = 1; d < kJointSub; d <<= 1) v += __shfl_xor(v, d, kWave);
+        if (p == 0) sh_acc[at] += v;
+    };
+    // this wave's block pairs
+    int rb[4], cb[4];
+    bool bv[4];
+    joint_d4 acc[4];
+#pragma unroll
+    for (int b = 0; b < 4; b++) {
+        const int bpl = blockIdx.y * kJointGroup + wave * 4 + b;
+        bv[b] = bpl < J.bp_count;
+        const int bp = J.bp_first + bpl;
+        int R = 0;
+        while ((R + 1) * (R + 2) / 2 <= bp) R++;
+        rb[b] = bv[b] ? R * 16 : 0;
+        cb[b] = bv[b] ? (bp - R * (R + 1) / 2) * 16 : 0;
+        acc[b] = joint_d4{0.0, 0.0, 0.0, 0.0};
+    }
+    const double thp = (double) pose_pivot_heading(B, ws, cur, pend);
+    const int nsub = (min(kMapTile, B.n - (int) blockIdx.x * kMapTile) + kJointSub - 1) / kJointSub;
+    double *row = sh_d + p * ld;
+    for (int st = 0; st < nsub; st++) {
+        const int q = st * kJointSub + p;
+        const int a = sh_anc[q];
+        const double wq = sh_wt[q];
+        const bool in = a >= 0;
+        if (jj == 0) {  // item 0: the pose, and the column of ones
+            float4 pa = make_float4(0.0f, 0.0f, 0.0f, 0.0f), pb = pa;
+            float2 pc = make_float2(0.0f, 0.0f);
+            if (in) {
+                pa = B.poseA[cur][a];
+                if (sums) {
+                    pb = B.poseB[cur][a];
+                    pc = B.poseC[cur][a];
+                }
+            }
+            row[0] = in ? (double) pa.x - sh_p[0] : 0.0;
+            row[1] = in ? (double) pa.y - sh_p[1] : 0.0;
+            row[2] = in ? remainder((double) pa.z - thp, kPoseTwoPi) - sh_p[2] : 0.0;
+            row[J.D] = in ? 1.0 : 0.0;
+            if (sums) {  // (uniform in the item's 16 threads)
+                add16(wq * (double) pb.x, 0);
+                add16(wq * (double) pb.y, 1);
+                add16(wq * (double) pb.z, 2);
+                add16(wq * (double) pb.w, 8 * 16 * 3);
+                add16(wq * (double) pc.x, 8 * 16 * 3 + 1);
+                add16(wq * (double) pc.y, 8 * 16 * 3 + 2);
+            }
+        }
+        // the slots, kBatch items at a time: all of a batch's genealogy entries, then all of its records, before any is used
+#pragma unroll 1
+        for (int j0 = 0; j0 < kItems && 16 * j0 <= J.k; j0 += kBatch) {
+            int lj[kBatch], sl[kBatch];
+#pragma unroll
+            for (int j = 0; j < kBatch; j++) {
+                const int it = jj + 16 * (j0 + j);
+                lj[j] = (it >= 1 && it <= J.k) ? J.slots[it - 1] : -1;
+            }
+#pragma unroll
+            for (int j = 0; j < kBatch; j++) sl[j] = (in && lj[j] >= 0) ? B.gen[cur][gen_index(B.compact, S, B.erow[lj[j]], (size_t) a)] : 0;
+            float4 la[kBatch];
+            float lb[kBatch];
+#pragma unroll
+            for (int j = 0; j < kBatch; j++) {
+                la[j] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+                lb[j] = 0.0f;
+                if (in && lj[j] >= 0) read_record(B, B.lmk_live, S, lj[j], sl[j], la[j], lb[j]);
+            }
+#pragma unroll
+            for (int j = 0; j < kBatch; j++) {
+                if (lj[j] >= 0) {
+                    const int it = jj + 16 * (j0 + j), c = 1 + 2 * it;  // 3 + 2 (item - 1)
+                    row[c] = in ? (double) la[j].x - sh_p[c] : 0.0;
+                    row[c + 1] = in ? (double) la[j].y - sh_p[c + 1] : 0.0;
+                    if (sums) {
+                        add16(wq * (double) la[j].z, 3 * it);
+                        add16(wq * (double) la[j].w, 3 * it + 1);
+                        add16(wq * (double) lb[j], 3 * it + 2);
+                    }
+                }
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (int kk = 0; kk < kJointSub / 4; kk++) {  // four particles per instruction: A[m = lane & 15][k = lane >> 4] = w d, B[k][n = lane & 15] = d
+            const int pk = kk * 4 + (lane >> 4);
+            const double wk = sh_wt[st * kJointSub + pk];
+            const double *rw = sh_d + pk * ld + (lane & 15);
+#pragma unroll
+            for (int b = 0; b < 4; b++) {
+                if (bv[b]) {  // (uniform)
+                    if constexpr (MFMA) {
+                        const double av = wk * rw[rb[b]], bw = rw[cb[b]];
+                        acc[b] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bw, acc[b], 0, 0, 0);
+                    } else {  // entry (row = (lane >> 4) + 4 reg, col = lane & 15) over the instruction's four particles, in ascending order
+#pragma unroll
+                        for (int q = 0; q < 4; q++) {
+                            const double *rq = sh_d + (kk * 4 + q) * ld;
+                            const double wq4 = sh_wt[st * kJointSub + kk * 4 + q], bw = rq[cb[b] + (lane & 15)];
+#pragma unroll
+                            for (int reg = 0; reg < 4; reg++) acc[b][reg] = fma(wq4 * rq[rb[b] + (lane >> 4) + 4 * reg], bw, acc[b][reg]);
+                        }
+                    }
+                }
+            }
+        }
+        __syncthreads();
+    }
+    // C/D of the f64 form: col = lane & 15, row = (lane >> 4) + 4 reg
+#pragma unroll
+    for (int b = 0; b < 4; b++) {
+        if (bv[b]) {
+            const int bpl = blockIdx.y * kJointGroup + wave * 4 + b;
+            double *o = A.part + ((size_t) blockIdx.x * (size_t) J.bp_count + (size_t) bpl) * 256;
+#pragma unroll
+            for (int reg = 0; reg < 4; reg++) o[((lane >> 4) + 4 * reg) * 16 + (lane & 15)] = acc[b][reg];
+        }
+    }
+    if (sums) {  // (every running sum was its owner's alone; the last sub-tile's barrier has passed)
+        const int nq = 6 + 3 * J.k;
+        double *o = J.pvf + (size_t) blockIdx.x * (size_t) nq;
+        for (int q = threadIdx.x; q < nq; q += kBlock) o[q] = q < 3 ? sh_acc[q] : q < 6 ? sh_acc[8 * 16 * 3 + q - 3] : sh_acc[q - 3];
+    }
+}
+
+// the tiles' partials of one block pair, added in ascending order (log-weights: each tile's scaled to the largest M_t)
+__global__ void __launch_bounds__(kBlock) joint_reduce_kernel(JointArgs J) {
+    __shared__ double sh_m[kBlock / kWave];
+    const MapSummaryArgs &A = J.S;
+    double M = -INFINITY;
+    if (A.logw) {  // the largest log-weight of all tiles
+        for (int t = threadIdx.x; t < A.tiles; t += kBlock) M = fmax(M, A.wpart[2 * t + 1]);
+        for (int d = kWave / 2; d > 0; d >>= 1) M = fmax(M, __shfl_xor(M, d, kWave));
+        if ((threadIdx.x & (kWave - 1)) == 0) sh_m[threadIdx.x / kWave] = M;
+        __syncthreads();
+        M = sh_m[0];
+        for (int v = 1; v < kBlock / kWave; v++) M = fmax(M, sh_m[v]);
+    }
+    double s = 0.0;
+    for (int t = 0; t < A.tiles; t++) {
+        const double f = A.logw ? block_scale((float) A.wpart[2 * t + 1], M) : 1.0;
+        s += A.part[((size_t) t * (size_t) J.bp_count + blockIdx.x) * 256 + threadIdx.x] * f;
+    }
+    J.sums[(size_t) (J.bp_first + blockIdx.x) * 256 + threadIdx.x] = s;
+}
+
+// entry (r, c), c <= r, of sum w d_ext d_ext^T
+SLAM_DEV double joint_sum(const JointArgs &J, int r, int c) {
+    const int R = r >> 4;
+    return J.sums[(size_t) (R * (R + 1) / 2 + (c >> 4)) * 256 + (r & 15) * 16 + (c & 15)];
+}
+
+// one thread per output
+__global__ void __launch_bounds__(kBlock) joint_finish_kernel(Buffers B, WeightScratch ws, JointArgs J) {
+#pragma clang fp contract(off)
+    __shared__ double sh_m[kBlock / kWave];
+    __shared__ double sh_s[kBlock];
+    const MapSummaryArgs &A = J.S;
+    double M = -INFINITY;
+    if (A.logw) {  // the largest log-weight of all tiles
+        for (int t = threadIdx.x; t < A.tiles; t += kBlock) M = fmax(M, A.wpart[2 * t + 1]);
+        for (int d = kWave / 2; d > 0; d >>= 1) M = fmax(M, __shfl_xor(M, d, kWave));
+        if ((threadIdx.x & (kWave - 1)) == 0) sh_m[threadIdx.x / kWave] = M;
+        __syncthreads();
+        M = sh_m[0];
+        for (int v = 1; v < kBlock / kWave; v++) M = fmax(M, sh_m[v]);
+    }
+    // the sum of all weights: each thread its stretch of the tiles, then the stretches, ascending throughout
+    const int per = (A.tiles + kBlock - 1) / kBlock, t0 = threadIdx.x * per, t1 = min(A.tiles, t0 + per);
+    double wsum = 0.0;
+    for (int t = t0; t < t1; t++) wsum += A.wpart[2 * t] * (A.logw ? block_scale((float) A.wpart[2 * t + 1], M) : 1.0);
+    sh_s[threadIdx.x] = wsum;
+    __syncthreads();
+    double Wtot = 0.0;
+    for (int v = 0; v < kBlock; v++) Wtot += sh_s[v];
+    const int D = J.D, T = D * (D + 1) / 2, size = 1 + D + T + 6 + 3 * J.k;
+    const int e = blockIdx.x * kBlock + threadIdx.x;
+    const int cnt = J.info[1];
+    if (e == 0 && A.holders) A.holders[0] = cnt;
+    if (e >= size) return;
+    const double nan = __longlong_as_double(0x7ff8000000000000ll);
+    double *o = A.out;
+    if (!(Wtot > 0.0) || !(Wtot < INFINITY)) {  // the weights sum to zero or to nothing finite: SLAMGPU_STATUS_DEGENERATE's convention
+        o[e] = nan;
+        return;
+    }
+    const double sJ = cnt ? joint_sum(J, D, D) : 0.0;
+    if (e == 0) {
+        o[0] = sJ / Wtot;
+        return;
+    }
+    if (!(cnt != 0 && sJ != 0.0)) {  // nobody holds them all, or nobody of weight
+        o[e] = nan;
+        return;
+    }
+    if (e <= D) {
+        const int a = e - 1;
+        const double m = J.pivot[a] + joint_sum(J, D, a) / sJ;
+        const Ctrl *ctrl = B.ctrl;
+        o[e] = a == 2 ? (double) pose_pivot_heading(B, ws, ctrl->live[B.slot], ctrl->pend[B.slot] != 0) + m : m;
+    } else if (e < 1 + D + T) {
+        const int t = e - 1 - D;
+        int r = (int) ((sqrt(8.0 * (double) t + 1.0) - 1.0) * 0.5);
+        while (r * (r + 1) / 2 > t) r--;
+        while ((r + 1) * (r + 2) / 2 <= t) r++;
+        const int c = t - r * (r + 1) / 2;
+        const double dr = joint_sum(J, D, r) / sJ, dc = joint_sum(J, D, c) / sJ;
+        o[e] = joint_sum(J, r, c) / sJ - dr * dc;
+    } else {
+        const int q = e - (1 + D + T), nq = 6 + 3 * J.k;
+        double s = 0.0;
+        for (int t = 0; t < A.tiles; t++) s += J.pvf[(size_t) t * (size_t) nq + q] * (A.logw ? block_scale((float) A.wpart[2 * t + 1], M) : 1.0);
+        o[e] = s / sJ;
+    }
+}
+
+static void launch_joint_hold(hipStream_t st, const Buffers &B, const WeightScratch &ws, const JointArgs &J) {
+    hipLaunchKernelGGL(joint_hold_kernel, dim3(J.S.tiles), dim3(kBlock), 0, st, B, ws, J);
+}
+static void launch_joint_pivot(hipStream_t st, const Buffers &B, const WeightScratch &ws, const JointArgs &J) {
+    hipLaunchKernelGGL(joint_pivot_kernel, dim3(1), dim3(kBlock), 0, st, B, ws, J);
+}
+static void launch_joint_gram(hipStream_t st, const Buffers &B, const WeightScratch &ws, const JointArgs &J) {
+    const dim3 grid(J.S.tiles, (J.bp_count + kJointGroup - 1) / kJointGroup);
+    if (J.plain) hipLaunchKernelGGL(joint_gram_kernel<false>, grid, dim3(kBlock), 0, st, B, ws, J);
+    else hipLaunchKernelGGL(joint_gram_kernel<true>, grid, dim3(kBlock), 0, st, B, ws, J);
+}
+static void launch_joint_reduce(hipStream_t st, const JointArgs &J) { hipLaunchKernelGGL(joint_reduce_kernel, dim3(J.bp_count), dim3(kBlock), 0, st, J); }
+static void launch_joint_finish(hipStream_t st, const Buffers &B, const WeightScratch &ws, const JointArgs &J) {
+    const int size = 1 + J.D + J.D * (J.D + 1) / 2 + 6 + 3 * J.k;
+    hipLaunchKernelGGL(joint_finish_kernel, dim3((size + kBlock - 1) / kBlock), dim3(kBlock), 0, st, B, ws, J);
+}
+
 static const KernelTable kTable = {launch_update, launch_update_any, launch_update_persist, launch_resample, launch_resample_ref, launch_scan, launch_gather, launch_flatten, launch_identity, launch_decompact, launch_finish, launch_predict, launch_estimate, launch_jacobians, launch_kat, launch_observe, launch_observe_book, launch_associate,
                                    launch_shard_plan, launch_shard_pack, launch_shard_unpack, launch_shard_finish, launch_dist_gather, launch_dist_flags, launch_peek, launch_lmk_box, launch_assoc_grid, launch_assoc_lists, launch_vote_compact,
                                    launch_associate_grid, launch_jacobians_multi, launch_pp_census, launch_pp_resolve, launch_pp_holders,
@@ -6126,7 +6552,8 @@ static const KernelTable kTable = {launch_update, launch_update_any, launch_upda
                                    launch_lists_box, launch_lists_geom, launch_lists_build, launch_lists_walk, launch_excl_radii,
                                    launch_map_summary, launch_map_finish, launch_map_pairs, launch_pp_missed,
                                    launch_path_compose, launch_path_record, launch_path_trace, launch_path_seed, launch_path_push, launch_path_finish,
-                                   launch_pp_mutex, launch_pose_summary, launch_pose_finish, launch_innovation_summary, launch_innovation_finish};
+                                   launch_pp_mutex, launch_pose_summary, launch_pose_finish, launch_innovation_summary, launch_innovation_finish,
+                                   launch_joint_hold, launch_joint_pivot, launch_joint_gram, launch_joint_reduce, launch_joint_finish};
 
 }  // namespace SLAM_KNS
 

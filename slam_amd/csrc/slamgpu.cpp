@@ -5199,6 +5199,105 @@ int slamgpu_map_pairs(slamgpu_ctx *c, const int32_t *pairs, int32_t count, doubl
     return 0;
 }
 
+int slamgpu_joint_summary(slamgpu_ctx *c, const int32_t *slots, int32_t k, double *out, int32_t *both) {
+    if (int rc = check_ctx(c)) return rc;
+    if (c->dist || c->cfg.n_particles_global != c->cfg.n_particles)
+        return fail(SLAMGPU_ERR_INVALID, "slamgpu_joint_summary: single contexts only");
+    static_assert(SLAMGPU_JOINT_MAX_SLOTS == kJointMaxSlots && 3 + 2 * kJointMaxSlots + 1 <= kJointCols, "public / device limits");
+    if (k < 0 || k > SLAMGPU_JOINT_MAX_SLOTS) return fail(SLAMGPU_ERR_INVALID, "slamgpu_joint_summary: k %d outside [0, %d]", k, SLAMGPU_JOINT_MAX_SLOTS);
+    if (!out || (k > 0 && !slots)) return fail(SLAMGPU_ERR_INVALID, "slamgpu_joint_summary: null %s", out ? "slots" : "output");
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    if (int rc = book_pull(c)) return rc;  // (device-driven steps: the number of slots lives on the device)
+    for (int s = 0; s < k; s++)
+        if (slots[s] < 0 || slots[s] >= c->nf)
+            return fail(SLAMGPU_ERR_INVALID, "slamgpu_joint_summary: entry %d names slot %d outside [0, %d)", s, slots[s], c->nf);
+    // the particle set and the weights of slamgpu_map_summary, reached the same way
+    if (int rc = flush_predict(c)) return rc;
+    if (int rc = flush_stages(c)) return rc;
+    if (int rc = sync_tables(c)) return rc;
+    const int tiles = (c->B.n + kMapTile - 1) / kMapTile;
+    const int D = 3 + 2 * k, Dp = (D + 1 + 15) / 16 * 16, nb = Dp / 16, nbp = nb * (nb + 1) / 2;
+    const size_t size = (size_t) SLAMGPU_JOINT_SIZE(k), nq = 6 + 3 * (size_t) k;
+    // the block pairs go through the summaries' table of partials a chunk at a time (a block pair's sums do not depend on the cut)
+    constexpr size_t kMapScratch = (size_t) 16 << 20;
+    const size_t per_bp = sizeof(double) * 256 * (size_t) tiles;
+    int fit = (int) std::max<size_t>(1, kMapScratch / per_bp);
+    if (const char *e = getenv("SLAMGPU_JOINT_CHUNK")) fit = std::max(1, atoi(e));  // (diagnostic: the chunking of a wide list on a narrow one)
+    const int chunk = std::min(fit, nbp);
+    // device staging: [out][wpart tiles][pivot][sums nbp][pvf tiles][part chunk][tile_info tiles][info][slots k][hold n]
+    auto up = [](size_t v) { return (v + 15) / 16 * 16; };
+    const size_t o_out = 0, o_w = o_out + sizeof(double) * size, o_piv = o_w + sizeof(double) * 2 * (size_t) tiles,
+                 o_sums = o_piv + sizeof(double) * kJointCols, o_pvf = o_sums + sizeof(double) * 256 * (size_t) nbp,
+                 o_part = o_pvf + sizeof(double) * nq * (size_t) tiles, o_tile = o_part + per_bp * (size_t) chunk,
+                 o_info = o_tile + sizeof(int32_t) * 2 * (size_t) tiles, o_slots = o_info + sizeof(int32_t) * 4,
+                 o_hold = up(o_slots + sizeof(int32_t) * (size_t) k), total = o_hold + up((size_t) c->B.n);
+    if (total > c->msum_bytes) {
+        if (c->msum_dev) (void) hipFree(c->msum_dev);
+        c->msum_dev = nullptr;
+        c->msum_bytes = 0;
+        hipError_t e = hipMalloc((void **) &c->msum_dev, total);
+        if (e != hipSuccess) return fail(SLAMGPU_ERR_ALLOC, "hipMalloc(%zu): %s", total, hipGetErrorString(e));
+        c->msum_bytes = total;
+    }
+    if (k > 0) HIP_TRY(hipMemcpyAsync(c->msum_dev + o_slots, slots, sizeof(int32_t) * (size_t) k, hipMemcpyHostToDevice, c->stream));
+    c->B.slot = c->slot;
+    JointArgs J{};
+    J.S.tiles = tiles;
+    J.S.logw = c->cfg.log_weights;
+    J.S.part = reinterpret_cast<double *>(c->msum_dev + o_part);
+    J.S.wpart = reinterpret_cast<double *>(c->msum_dev + o_w);
+    J.S.out = reinterpret_cast<double *>(c->msum_dev + o_out);
+    J.S.holders = reinterpret_cast<int32_t *>(c->msum_dev + o_info) + 2;
+    J.k = k;
+    J.D = D;
+    J.Dp = Dp;
+    if (const char *e = getenv("SLAMGPU_JOINT_PLAIN_FMA")) J.plain = atoi(e) != 0;  // (diagnostic: tools/joint_probe.py's comparison of the two forms)
+    J.slots = reinterpret_cast<const int32_t *>(c->msum_dev + o_slots);
+    J.hold = reinterpret_cast<uint8_t *>(c->msum_dev + o_hold);
+    J.tile_info = reinterpret_cast<int32_t *>(c->msum_dev + o_tile);
+    J.info = reinterpret_cast<int32_t *>(c->msum_dev + o_info);
+    J.pivot = reinterpret_cast<double *>(c->msum_dev + o_piv);
+    J.sums = reinterpret_cast<double *>(c->msum_dev + o_sums);
+    J.pvf = reinterpret_cast<double *>(c->msum_dev + o_pvf);
+    {
+        Timed t(c, "joint_hold");
+        c->k->joint_hold(c->stream, c->B, c->ws, J);
+    }
+    HIP_TRY(hipGetLastError());
+    {
+        Timed t(c, "joint_pivot");
+        c->k->joint_pivot(c->stream, c->B, c->ws, J);
+    }
+    HIP_TRY(hipGetLastError());
+    for (int at = 0; at < nbp; at += chunk) {
+        J.bp_first = at;
+        J.bp_count = std::min(chunk, nbp - at);
+        {
+            Timed t(c, "joint_gram");
+            c->k->joint_gram(c->stream, c->B, c->ws, J);
+        }
+        HIP_TRY(hipGetLastError());
+        {
+            Timed t(c, "joint_reduce");
+            c->k->joint_reduce(c->stream, J);
+        }
+        HIP_TRY(hipGetLastError());
+    }
+    {
+        Timed t(c, "joint_finish");
+        c->k->joint_finish(c->stream, c->B, c->ws, J);
+    }
+    HIP_TRY(hipGetLastError());
+    std::vector<double> h(size);  // (outputs untouched if a copy fails)
+    int32_t hb = 0;
+    HIP_TRY(hipMemcpyAsync(h.data(), c->msum_dev + o_out, sizeof(double) * size, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(&hb, J.S.holders, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    memcpy(out, h.data(), sizeof(double) * size);
+    if (both) *both = hb;
+    return 0;
+}
+
 int slamgpu_pose_summary(slamgpu_ctx *c, double *out) {
     if (int rc = check_ctx(c)) return rc;
     if (c->dist || c->cfg.n_particles_global != c->cfg.n_particles) return fail(SLAMGPU_ERR_INVALID, "slamgpu_pose_summary: single contexts only");

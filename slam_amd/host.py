@@ -15,7 +15,7 @@ DECLARED_SYMBOLS = [
     "slamhost_synthetic_landmarks", "slamhost_write_map", "slamhost_ekf_create", "slamhost_ekf_destroy", "slamhost_ekf_step",
     "slamhost_ekf_state", "slamhost_plot_open", "slamhost_plot_close", "slamhost_plot_xy", "slamhost_plot_matrix",
     "slamhost_plot_doubles", "slamhost_plot_car_size", "slamhost_plot_u32", "slamhost_plot_cmd", "slamhost_plot_name",
-    "slamhost_map_candidates", "slamhost_map_merge", "slamhost_pose_nees", "slamhost_innovation_nis",
+    "slamhost_map_candidates", "slamhost_map_merge", "slamhost_pose_nees", "slamhost_innovation_nis", "slamhost_joint_dense",
 ]
 MAP_STRIDE = 9  # SLAMGPU_MAP_STRIDE
 POSE_STRIDE = 18  # SLAMGPU_POSE_STRIDE
@@ -93,6 +93,8 @@ def load_library():
         L.slamhost_pose_nees.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
         L.slamhost_innovation_nis.restype = C.c_int32
         L.slamhost_innovation_nis.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
+        L.slamhost_joint_dense.restype = C.c_int32
+        L.slamhost_joint_dense.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32]
         _lib = L
     return _lib
 
@@ -193,6 +195,25 @@ def innovation_nis(entries):
     if bad < 0:
         raise ValueError("slamhost_innovation_nis: bad arguments")
     return nis, int(bad)
+
+
+def joint_dense(out, k=None, ld=None):
+    """slamhost_joint_dense: the EKF-ordered state x[D] (heading wrapped into (-pi, pi]) and the dense total covariance P[D, D] =
+    scatter + blockdiag(mean Pv, mean Pf ...) of one SlamGpu.joint_summary (its dict, or its flat output with k).  Returns (x, P,
+    status): 0 P is positive definite, 1 it is not, -1 the input holds a NaN (x, P carry it)"""
+    if isinstance(out, dict):
+        k = len(out["pf"]) if k is None else k
+        out = out["raw"]
+    t = np.ascontiguousarray(out, np.float64).reshape(-1)
+    k = int(k)
+    D = 3 + 2 * k
+    if k < 0 or len(t) != 1 + D + D * (D + 1) // 2 + 6 + 3 * k:
+        raise ValueError("joint_dense: %d numbers are not a joint summary of %d slots" % (len(t), k))
+    ld = D if ld is None else int(ld)
+    x = np.zeros(D, np.float64)
+    P = np.zeros((D, max(ld, D)), np.float64)
+    status = load_library().slamhost_joint_dense(_p(t), k, _p(x), _p(P), ld)
+    return x, P[:, :D].copy() if ld == D else P, int(status)
 
 
 class HostSim:
