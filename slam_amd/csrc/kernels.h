@@ -690,7 +690,7 @@ struct InnovArgs {
 // between-particle scatter of v = (x, y, u, xf_s0, xf_s1, ...) (D = 3 + 2 k entries, u the heading's deviation as in the pose summary)
 // over the particles J that hold EVERY listed slot, and the mean Pv / Pf of J.  Four passes:
 //   joint_hold_kernel    grid (tiles of kMapTile particles): hold[i] = particle i is in J; per tile the lowest such index and their number
-//                        (integers); the tile's sum of weights into S.wpart by summary_weights.inl
+//                        (integers); the tile's sum of weights into S.wpart by summary_family.h's tile_weight_sum
 //   joint_pivot_kernel   one workgroup: the lowest-index particle of J, |J|, and that particle's vector as the pivot p[0 .. D)
 //   joint_gram_kernel    grid (tiles, groups of kJointGroup block pairs): sum w d_ext d_ext^T over the tile, d_ext = (v - p, 1) padded with
 //                        zeros to Dp = a multiple of 16 columns (column D, the 1, carries sum w d and sum w), as 16 x 16 blocks of the
@@ -699,7 +699,7 @@ struct InnovArgs {
 //                        every 16th item; item 0 the pose, item 1 + s slot s; all its records requested before any is used) and each
 //                        wave runs its 4 block pairs over it.  Particles outside J enter as w = 0, d = 0.  One 16 x 16 partial per tile
 //                        and block pair goes to S.part; the group that holds block pair 0 also adds sum w Pv / Pf (plain FMAs) into pvf
-//                        (its w[] come from the same summary_weights.inl text, which stores the tile's same S.wpart again)
+//                        (its w[] come from the same summary_lanes / tile_weights, and tile_weight_sum stores the tile's same S.wpart again)
 //   joint_reduce_kernel  per block pair of the chunk: the tiles' partials added in ascending order (log-weights: each scaled by
 //                        exp(M_t - max M)) into `sums`
 //   joint_finish_kernel  s, delta = sum w d / s, mu = p + delta, C = sum w d d^T / s - delta delta^T, the means of Pv / Pf; out / both

@@ -4769,45 +4769,9 @@ static void launch_excl_radii(hipStream_t st, const ObserveOut *obs, const float
 }
 
 // ---- slamgpu_map_summary (kernels.h: MapSummaryArgs) -------------------------------------------------------------------------
-// the record of landmark l behind genealogy entry sl (single contexts: read_through_genealogy past its genealogy load, so that the
-// slots of one genealogy row share that load).  (record_held, with the joint summary's kernels, reads the x of the same record alone:
-// its addresses are these and change with them)
-SLAM_DEV void read_record(const Buffers &B, const int32_t *__restrict__ live, size_t S, int l, int sl, float4 &la, float &lb) {
-    if (sl < 0) {
-        const size_t at = (size_t) l * B.pool_cap + (sl & ~kPoolBit);
-        la = B.poolA[at];
-        lb = B.poolB[at];
-    } else {
-        const int b = live[l];
-        la = B.lmkA[b][(size_t) l * S + sl];
-        lb = B.lmkB[b][(size_t) l * S + sl];
-    }
-}
-// one (W, mean, M2, sum w Pf, holders) summary and the pairwise update with the one that follows it in particle order
-struct MapPart {
-    double v[kMapFields];
-};
-SLAM_DEV void map_merge(MapPart &a, const MapPart &b) {
-    a.v[kMapCnt] += b.v[kMapCnt];
-    if (!(b.v[kMapW] != 0.0)) return;  // nothing of weight in b (its holders, if any, are counted)
-    if (!(a.v[kMapW] != 0.0)) {
-        const double cnt = a.v[kMapCnt];
-        a = b;
-        a.v[kMapCnt] = cnt;
-        return;
-    }
-    const double W = a.v[kMapW] + b.v[kMapW], f = b.v[kMapW] / W, g = a.v[kMapW] * f;
-    const double dx = b.v[kMapMx] - a.v[kMapMx], dy = b.v[kMapMy] - a.v[kMapMy];
-    a.v[kMapMx] += dx * f;
-    a.v[kMapMy] += dy * f;
-    a.v[kMapXX] += b.v[kMapXX] + dx * dx * g;
-    a.v[kMapXY] += b.v[kMapXY] + dx * dy * g;
-    a.v[kMapYY] += b.v[kMapYY] + dy * dy * g;
-    a.v[kMapP00] += b.v[kMapP00];
-    a.v[kMapP10] += b.v[kMapP10];
-    a.v[kMapP11] += b.v[kMapP11];
-    a.v[kMapW] = W;
-}
+}  // namespace SLAM_KNS
+#include "summary_family.h"  // the pieces every summary below shares
+namespace SLAM_KNS {
 
 __global__ void __launch_bounds__(kBlock) map_summary_kernel(Buffers B, WeightScratch ws, MapSummaryArgs A) {
     constexpr int kWaves = kBlock / kWave;
@@ -4819,21 +4783,15 @@ __global__ void __launch_bounds__(kBlock) map_summary_kernel(Buffers B, WeightSc
     const bool pend = ctrl->pend[B.slot] != 0;
     const size_t S = (size_t) B.ncap;
     const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-    // this lane's particles: ancestor and weight, once for every slot of the group
+    // this lane's particles (ancestor and weight, once for every item of the group), their weights, the tile's sum of them
     int anc[kMapT];
     float wf[kMapT];
     bool on[kMapT];
-    float mb = -INFINITY;
-#pragma unroll
-    for (int t = 0; t < kMapT; t++) {
-        const int i = blockIdx.x * kMapTile + t * kBlock + threadIdx.x;
-        on[t] = i < B.n;
-        anc[t] = on[t] ? (pend ? ws.keep[B.slot][i] : i) : 0;
-        wf[t] = on[t] ? (pend ? ctrl->inv_n : B.poseA[cur][anc[t]].w) : 0.0f;  // resampled particles restart at 1/N, as in peek_kernel
-        if (on[t] && A.logw) mb = fmaxf(mb, wf[t]);
-    }
-    // (one text for every summary of this family: w[kMapT] from wf / on / mb, and the tile's sum into A.wpart)
-#include "summary_weights.inl"
+    float mb;
+    double w[kMapT];
+    summary_lanes(B, ws, ctrl, cur, pend, A.logw, on, anc, wf, mb);
+    tile_weights(A.logw, wf, on, mb, lane, wave, sh_m, w);
+    tile_weight_sum(w, mb, lane, wave, sh_w, A.wpart);
     const int s0 = blockIdx.y * kMapSlots, sn = min(kMapSlots, A.count - s0);
     int row = -1;
     int sl[kMapT];
@@ -4891,45 +4849,15 @@ __global__ void __launch_bounds__(kBlock) map_summary_kernel(Buffers B, WeightSc
         }
 #pragma unroll
         for (int q = 0; q < 9; q++) a[q] = wave_sum_d(a[q]);
-        if (lane == 0) {
-            const double W = a[0];
-            const bool any = W != 0.0;  // (W == 0: holders without weight are counted, and carry nothing else)
-            const double mx = any ? a[1] / W : 0.0, my = any ? a[2] / W : 0.0;
-            o[kMapW] = W;
-            o[kMapMx] = (double) px + mx;
-            o[kMapMy] = (double) py + my;
-            o[kMapXX] = a[3] - a[1] * mx;
-            o[kMapXY] = a[4] - a[1] * my;
-            o[kMapYY] = a[5] - a[2] * my;
-            o[kMapP00] = a[6];
-            o[kMapP10] = a[7];
-            o[kMapP11] = a[8];
-            o[kMapCnt] = (double) cnt;
-        }
+        if (lane == 0) moments_emit(o, a, (double) px, (double) py, cnt);
     }
-    __syncthreads();
-    if ((int) threadIdx.x < sn) {  // the tile's waves in ascending order (wave v: lanes v * 64 .. of each of the tile's kMapT strides)
-        const int s = threadIdx.x;
-        MapPart m;
-        for (int q = 0; q < kMapFields; q++) m.v[q] = sh[s][0][q];
-        for (int v = 1; v < kWaves; v++) {
-            MapPart b;
-            for (int q = 0; q < kMapFields; q++) b.v[q] = sh[s][v][q];
-            map_merge(m, b);
-        }
-        double *p = A.part + (size_t) blockIdx.x * kMapFields * (size_t) A.count + (size_t) (s0 + s);
-        for (int q = 0; q < kMapFields; q++) p[(size_t) q * A.count] = m.v[q];
-    }
+    tile_merge_store(sh, sn, s0, A);
 }
 
 // kMapFinParts threads per slot: each merges its stretch of the tiles' partials in ascending order (and adds up that stretch's weights),
 // the slot's first thread merges the stretches in ascending order, normalises and writes the outputs
-// (the body is one text for this kernel and innovation_finish_kernel: summary_finish.inl)
-__global__ void __launch_bounds__(kBlock) map_finish_kernel(MapSummaryArgs A) {
-#define SLAM_FINISH_INNOV 0
-#include "summary_finish.inl"
-#undef SLAM_FINISH_INNOV
-}
+// (summary_finish: one body for this kernel and innovation_finish_kernel)
+__global__ void __launch_bounds__(kBlock) map_finish_kernel(MapSummaryArgs A) { summary_finish<false>(A, nullptr); }
 
 static void launch_map_summary(hipStream_t st, const Buffers &B, const WeightScratch &ws, const MapSummaryArgs &A) {
     hipLaunchKernelGGL(map_summary_kernel, dim3(A.tiles, (A.count + kMapSlots - 1) / kMapSlots), dim3(kBlock), 0, st, B, ws, A);
@@ -4954,21 +4882,15 @@ __global__ void __launch_bounds__(kBlock) map_pairs_kernel(Buffers B, WeightScra
     const bool pend = ctrl->pend[B.slot] != 0;
     const size_t S = (size_t) B.ncap;
     const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-    // this lane's particles: ancestor and weight, once for every pair of the group (map_summary_kernel's, operation for operation)
+    // this lane's particles (ancestor and weight, once for every item of the group), their weights, the tile's sum of them
     int anc[kMapT];
     float wf[kMapT];
     bool on[kMapT];
-    float mb = -INFINITY;
-#pragma unroll
-    for (int t = 0; t < kMapT; t++) {
-        const int i = blockIdx.x * kMapTile + t * kBlock + threadIdx.x;
-        on[t] = i < B.n;
-        anc[t] = on[t] ? (pend ? ws.keep[B.slot][i] : i) : 0;
-        wf[t] = on[t] ? (pend ? ctrl->inv_n : B.poseA[cur][anc[t]].w) : 0.0f;
-        if (on[t] && A.logw) mb = fmaxf(mb, wf[t]);
-    }
-    // (one text for every summary of this family: w[kMapT] from wf / on / mb, and the tile's sum into A.wpart)
-#include "summary_weights.inl"
+    float mb;
+    double w[kMapT];
+    summary_lanes(B, ws, ctrl, cur, pend, A.logw, on, anc, wf, mb);
+    tile_weights(A.logw, wf, on, mb, lane, wave, sh_m, w);
+    tile_weight_sum(w, mb, lane, wave, sh_w, A.wpart);
     const int s0 = blockIdx.y * kMapSlots, sn = min(kMapSlots, A.count - s0);
     int rowa = -1, rowb = -1;
     int sla[kMapT], slb[kMapT];
@@ -5048,35 +4970,9 @@ __global__ void __launch_bounds__(kBlock) map_pairs_kernel(Buffers B, WeightScra
         }
 #pragma unroll
         for (int q = 0; q < 9; q++) a[q] = wave_sum_d(a[q]);
-        if (lane == 0) {
-            const double W = a[0];
-            const bool any = W != 0.0;  // (W == 0: joint holders without weight are counted, and carry nothing else)
-            const double mx = any ? a[1] / W : 0.0, my = any ? a[2] / W : 0.0;
-            o[kMapW] = W;
-            o[kMapMx] = px + mx;
-            o[kMapMy] = py + my;
-            o[kMapXX] = a[3] - a[1] * mx;
-            o[kMapXY] = a[4] - a[1] * my;
-            o[kMapYY] = a[5] - a[2] * my;
-            o[kMapP00] = a[6];
-            o[kMapP10] = a[7];
-            o[kMapP11] = a[8];
-            o[kMapCnt] = (double) cnt;
-        }
+        if (lane == 0) moments_emit(o, a, px, py, cnt);
     }
-    __syncthreads();
-    if ((int) threadIdx.x < sn) {  // the tile's waves in ascending order, as map_summary_kernel merges them
-        const int s = threadIdx.x;
-        MapPart m;
-        for (int q = 0; q < kMapFields; q++) m.v[q] = sh[s][0][q];
-        for (int v = 1; v < kWaves; v++) {
-            MapPart b;
-            for (int q = 0; q < kMapFields; q++) b.v[q] = sh[s][v][q];
-            map_merge(m, b);
-        }
-        double *p = A.part + (size_t) blockIdx.x * kMapFields * (size_t) A.count + (size_t) (s0 + s);
-        for (int q = 0; q < kMapFields; q++) p[(size_t) q * A.count] = m.v[q];
-    }
+    tile_merge_store(sh, sn, s0, A);
 }
 static void launch_map_pairs(hipStream_t st, const Buffers &B, const WeightScratch &ws, const MapPairsArgs &P) {
     hipLaunchKernelGGL(map_pairs_kernel, dim3(P.S.tiles, (P.S.count + kMapSlots - 1) / kMapSlots), dim3(kBlock), 0, st, B, ws, P);
@@ -5197,21 +5093,14 @@ __global__ void __launch_bounds__(kBlock) path_wsum_kernel(Buffers B, WeightScra
     const bool pend = ctrl->pend[B.slot] != 0;
     const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
     const int i = blockIdx.x * kBlock + threadIdx.x;
-    const bool on = i < B.n;
-    const float wf = on ? (pend ? ctrl->inv_n : B.poseA[cur][i].w) : 0.0f;
-    float mb = 0.0f;
-    double w = (double) wf;
-    if (A.logw) {
-        mb = on ? wf : -INFINITY;
-        for (int d = kWave / 2; d > 0; d >>= 1) mb = fmaxf(mb, __shfl_xor(mb, d, kWave));
-        if (lane == 0) sh_m[wave] = mb;
-        __syncthreads();
-        mb = sh_m[0];
-        for (int v = 1; v < kWaves; v++) mb = fmaxf(mb, sh_m[v]);
-        w = (on && mb != -INFINITY) ? exp((double) wf - (double) mb) : 0.0;
-    }
-    w = wave_sum_d(w);
-    if (lane == 0) sh_w[wave] = w;
+    const bool on[1] = {i < B.n};
+    const float wf[1] = {on[0] ? (pend ? ctrl->inv_n : B.poseA[cur][i].w) : 0.0f};
+    float mb = on[0] ? wf[0] : -INFINITY;  // (the weight itself, not fmaxf's choice: a NaN log-weight stays one)
+    double w[1];
+    tile_weights(A.logw, wf, on, mb, lane, wave, sh_m, w);
+    // (not tile_weight_sum: that starts its sum from +0, this kernel from the weight itself)
+    const double sw = wave_sum_d(w[0]);
+    if (lane == 0) sh_w[wave] = sw;
     __syncthreads();
     if (threadIdx.x == 0) {
         double tot = sh_w[0];
@@ -5805,20 +5694,11 @@ __global__ void __launch_bounds__(kBlock) pose_summary_kernel(Buffers B, WeightS
         if (on[t] && pend) pa[t].w = ctrl->inv_n;  // resampled particles restart at 1/N, as in peek_kernel
         if (on[t] && A.logw) mb = fmaxf(mb, pa[t].w);
     }
+    float wf[kPoseT];
+#pragma unroll
+    for (int t = 0; t < kPoseT; t++) wf[t] = pa[t].w;
     double w[kPoseT];
-    if (A.logw) {  // the tile's largest log-weight
-        for (int d = kWave / 2; d > 0; d >>= 1) mb = fmaxf(mb, __shfl_xor(mb, d, kWave));
-        if (lane == 0) sh_m[wave] = mb;
-        __syncthreads();
-        mb = sh_m[0];
-        for (int v = 1; v < kWaves; v++) mb = fmaxf(mb, sh_m[v]);
-#pragma unroll
-        for (int t = 0; t < kPoseT; t++) w[t] = (on[t] && mb != -INFINITY) ? exp((double) pa[t].w - (double) mb) : 0.0;
-    } else {
-        mb = 0.0f;
-#pragma unroll
-        for (int t = 0; t < kPoseT; t++) w[t] = (double) pa[t].w;
-    }
+    tile_weights(A.logw, wf, on, mb, lane, wave, sh_m, w);
     // pivot: the wave's first particle (a point of the cloud: the sums below cancel at the cloud's size).  A wave whose first
     // particle lies beyond the set holds none (its lanes' particles only follow it)
     const float px = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(pa[0].x)));
@@ -5987,21 +5867,11 @@ __global__ void __launch_bounds__(kBlock) innovation_summary_kernel(Buffers B, W
     float4 pa[kMapT];
     float wf[kMapT];
     bool on[kMapT];
-    float mb = -INFINITY;
-#pragma unroll
-    for (int t = 0; t < kMapT; t++) {
-        const int i = blockIdx.x * kMapTile + t * kBlock + threadIdx.x;
-        on[t] = i < B.n;
-        anc[t] = on[t] ? (pend ? ws.keep[B.slot][i] : i) : 0;
-        pa[t] = on[t] ? B.poseA[cur][anc[t]] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    }
-#pragma unroll
-    for (int t = 0; t < kMapT; t++) {
-        wf[t] = on[t] ? (pend ? ctrl->inv_n : pa[t].w) : 0.0f;  // resampled particles restart at 1/N, as in peek_kernel
-        if (on[t] && A.logw) mb = fmaxf(mb, wf[t]);
-    }
-    // (one text for every summary of this family: w[kMapT] from wf / on / mb, and the tile's sum into A.wpart)
-#include "summary_weights.inl"
+    float mb;
+    double w[kMapT];
+    summary_lanes(B, ws, ctrl, cur, pend, A.logw, on, anc, wf, mb, &pa);
+    tile_weights(A.logw, wf, on, mb, lane, wave, sh_m, w);
+    tile_weight_sum(w, mb, lane, wave, sh_w, A.wpart);
     const double r00 = (double) I.r00, r10 = (double) I.r10, r11 = (double) I.r11;
     const int s0 = blockIdx.y * kMapSlots, sn = min(kMapSlots, A.count - s0);
     int row = -1;
@@ -6070,47 +5940,15 @@ __global__ void __launch_bounds__(kBlock) innovation_summary_kernel(Buffers B, W
 #pragma unroll
         for (int q = 0; q < 10; q++) a[q] = wave_sum_d(a[q]);
         if (lane == 0) {
-            const double W = a[0];
-            const bool any = W != 0.0;  // (W == 0: holders without weight are counted, and carry nothing else)
-            const double m0 = any ? a[1] / W : 0.0, m1 = any ? a[2] / W : 0.0;
-            o[kMapW] = W;
-            o[kMapMx] = p0 + m0;
-            o[kMapMy] = p1 + m1;
-            o[kMapXX] = a[3] - a[1] * m0;
-            o[kMapXY] = a[4] - a[1] * m1;
-            o[kMapYY] = a[5] - a[2] * m1;
-            o[kMapP00] = a[6];
-            o[kMapP10] = a[7];
-            o[kMapP11] = a[8];
-            o[kMapCnt] = (double) cnt;
-            o[kInnNis] = any ? a[9] : 0.0;
+            moments_emit(o, a, p0, p1, cnt);
+            o[kInnNis] = a[0] != 0.0 ? a[9] : 0.0;
         }
     }
-    __syncthreads();
-    if ((int) threadIdx.x < sn) {  // the tile's waves in ascending order, as map_summary_kernel merges them
-        const int s = threadIdx.x;
-        MapPart m;
-        for (int q = 0; q < kMapFields; q++) m.v[q] = sh[s][0][q];
-        double nis = sh[s][0][kInnNis];
-        for (int v = 1; v < kWaves; v++) {
-            MapPart b;
-            for (int q = 0; q < kMapFields; q++) b.v[q] = sh[s][v][q];
-            map_merge(m, b);
-            nis += sh[s][v][kInnNis];
-        }
-        double *p = A.part + (size_t) blockIdx.x * kInnFields * (size_t) A.count + (size_t) (s0 + s);
-        for (int q = 0; q < kMapFields; q++) p[(size_t) q * A.count] = m.v[q];
-        p[(size_t) kInnNis * A.count] = nis;
-    }
+    tile_merge_store(sh, sn, s0, A);
 }
 
-// map_finish_kernel's pass (the same text) with the extra field, into the staging area or the ring
-__global__ void __launch_bounds__(kBlock) innovation_finish_kernel(InnovArgs I) {
-    const MapSummaryArgs &A = I.S;
-#define SLAM_FINISH_INNOV 1
-#include "summary_finish.inl"
-#undef SLAM_FINISH_INNOV
-}
+// map_finish_kernel's pass with the extra field, into the staging area or the ring
+__global__ void __launch_bounds__(kBlock) innovation_finish_kernel(InnovArgs I) { summary_finish<true>(I.S, &I); }
 
 static void launch_innovation_summary(hipStream_t st, const Buffers &B, const WeightScratch &ws, const InnovArgs &I) {
     hipLaunchKernelGGL(innovation_summary_kernel, dim3(I.S.tiles, (I.S.count + kMapSlots - 1) / kMapSlots), dim3(kBlock), 0, st, B, ws, I);
@@ -6124,12 +5962,6 @@ static void launch_innovation_finish(hipStream_t st, const InnovArgs &I) {
 typedef double joint_d4 __attribute__((ext_vector_type(4)));
 static_assert(kJointCols == kBlock, "one column of the pivot per thread");
 static_assert(1 + kJointMaxSlots <= 8 * 16, "items per staging thread");
-
-// whether the record of landmark l behind genealogy entry sl is there (read_record's addresses, the x of its first half alone)
-SLAM_DEV bool record_held(const Buffers &B, const int32_t *__restrict__ live, size_t S, int l, int sl) {
-    const float x = sl < 0 ? B.poolA[(size_t) l * B.pool_cap + (sl & ~kPoolBit)].x : B.lmkA[live[l]][(size_t) l * S + sl].x;
-    return x == x;
-}
 
 // pivot pass, first half: membership of J per particle, the tile's lowest member and their number, the tile's sum of weights
 __global__ void __launch_bounds__(kBlock) joint_hold_kernel(Buffers B, WeightScratch ws, JointArgs J) {
@@ -6147,21 +5979,15 @@ __global__ void __launch_bounds__(kBlock) joint_hold_kernel(Buffers B, WeightScr
         sh_first = INT_MAX;
         sh_cnt = 0;
     }
-    // this lane's particles: ancestor and weight (map_summary_kernel's, operation for operation)
+    // this lane's particles (ancestor and weight, once for every item of the group), their weights, the tile's sum of them
     int anc[kMapT];
     float wf[kMapT];
     bool on[kMapT];
-    float mb = -INFINITY;
-#pragma unroll
-    for (int t = 0; t < kMapT; t++) {
-        const int i = blockIdx.x * kMapTile + t * kBlock + threadIdx.x;
-        on[t] = i < B.n;
-        anc[t] = on[t] ? (pend ? ws.keep[B.slot][i] : i) : 0;
-        wf[t] = on[t] ? (pend ? ctrl->inv_n : B.poseA[cur][anc[t]].w) : 0.0f;
-        if (on[t] && A.logw) mb = fmaxf(mb, wf[t]);
-    }
-    // (one text for every summary of this family: w[kMapT] from wf / on / mb, and the tile's sum into A.wpart)
-#include "summary_weights.inl"
+    float mb;
+    double w[kMapT];
+    summary_lanes(B, ws, ctrl, cur, pend, A.logw, on, anc, wf, mb);
+    tile_weights(A.logw, wf, on, mb, lane, wave, sh_m, w);
+    tile_weight_sum(w, mb, lane, wave, sh_w, A.wpart);
     bool hold[kMapT];
 #pragma unroll
     for (int t = 0; t < kMapT; t++) hold[t] = on[t];
@@ -6280,21 +6106,15 @@ __global__ void __launch_bounds__(kBlock) joint_gram_kernel(Buffers B, WeightScr
     const bool pend = ctrl->pend[B.slot] != 0;
     const size_t S = (size_t) B.ncap;
     const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-    // this lane's particles: ancestor and weight (map_summary_kernel's, operation for operation)
+    // this lane's particles (ancestor and weight, once for every item of the group), their weights, the tile's sum of them
     int anc[kMapT];
     float wf[kMapT];
     bool on[kMapT];
-    float mb = -INFINITY;
-#pragma unroll
-    for (int t = 0; t < kMapT; t++) {
-        const int i = blockIdx.x * kMapTile + t * kBlock + threadIdx.x;
-        on[t] = i < B.n;
-        anc[t] = on[t] ? (pend ? ws.keep[B.slot][i] : i) : 0;
-        wf[t] = on[t] ? (pend ? ctrl->inv_n : B.poseA[cur][anc[t]].w) : 0.0f;
-        if (on[t] && A.logw) mb = fmaxf(mb, wf[t]);
-    }
-    // (one text for every summary of this family: w[kMapT] from wf / on / mb, and the tile's sum into A.wpart)
-#include "summary_weights.inl"
+    float mb;
+    double w[kMapT];
+    summary_lanes(B, ws, ctrl, cur, pend, A.logw, on, anc, wf, mb);
+    tile_weights(A.logw, wf, on, mb, lane, wave, sh_m, w);
+    tile_weight_sum(w, mb, lane, wave, sh_w, A.wpart);
     for (int e = threadIdx.x; e < 8 * 16 * 3 + 3; e += kBlock) sh_acc[e] = 0.0;
     // the tile's weights and ancestors by tile-local index; outside J: weight 0, no ancestor
 #pragma unroll

@@ -1,0 +1,771 @@
+// libslamgpu.so: the posterior summaries (slamgpu_map_*, slamgpu_joint_summary, slamgpu_pose_*, slamgpu_innovation_*, slamgpu_path_*).
+// Every summary reaches the particle set slamgpu_peek shows the same way (summary_enter), cuts its work to the partials' table the
+// same way (chunk_fit), lays its staging area out with one builder (Layout over a DevArena), launches through launch() and keeps its
+// history, where it has one, in a Ring.  slamgpu.cpp calls path_compose, path_append, pose_append and innov_append from its steps.
+#include "slamgpu_ctx.h"
+
+#pragma GCC visibility push(hidden)
+
+int DevArena::reserve(size_t total) {
+    if (total <= bytes) return 0;
+    release();
+    hipError_t e = hipMalloc((void **) &p, total);
+    if (e != hipSuccess) {
+        (void) hipGetLastError();
+        p = nullptr;
+        return fail(SLAMGPU_ERR_ALLOC, "hipMalloc(%zu): %s", total, hipGetErrorString(e));
+    }
+    bytes = total;
+    return 0;
+}
+void DevArena::release() {
+    if (p) (void) hipFree(p);
+    p = nullptr;
+    bytes = 0;
+}
+
+namespace {
+
+// the fields of a staging area, one behind the other: take them in order, reserve total(), then resolve each against the arena
+struct Layout {
+    template <class T>
+    struct Field {
+        size_t off;
+        T *at(const DevArena &a) const { return reinterpret_cast<T *>(a.p + off); }
+    };
+    size_t end = 0;
+    template <class T>
+    Field<T> take(size_t n, size_t align = 1) {
+        end = (end + align - 1) / align * align;
+        const Field<T> f{end};
+        end += sizeof(T) * n;
+        return f;
+    }
+    size_t total() const { return end; }
+};
+size_t up16(size_t v) { return (v + 15) / 16 * 16; }
+
+// how many of `items` go through a table of partials at a time: at most 16 MiB of it, in whole granules, at least one granule
+// (env_name: a diagnostic override, the chunking of a large request on a small one)
+int chunk_fit(const char *env_name, size_t bytes_per_item, int granule, int64_t items) {
+    constexpr size_t kScratch = (size_t) 16 << 20;
+    int fit = (int) std::max<size_t>(granule, kScratch / bytes_per_item / granule * granule);
+    if (const char *e = getenv(env_name)) fit = std::max(granule, atoi(e) / granule * granule);
+    return (int) std::min<int64_t>(fit, (items + granule - 1) / granule * granule);
+}
+
+// The way into an entry point: the steps named in `flags`, in this order.  An entry point whose own checks lie between two of the
+// steps calls it once per stretch, so that a bad call gets the error it always got first.
+enum {
+    kCtx = 1,      // a live context
+    kSingle = 2,   // ... that is not a shard
+    kDevice = 4,   // its device current
+    kBook = 8,     // the number of slots on the host (device-driven steps keep it on the device)
+    kSettle = 16,  // the particle set slamgpu_peek shows, and nothing more than it does to get there
+    kTables = 32,  // ... and the row tables the summaries' kernels read
+};
+int summary_enter(slamgpu_ctx *c, const char *who, int flags) {
+    if (flags & kCtx)
+        if (int rc = check_ctx(c)) return rc;
+    if ((flags & kSingle) && (c->dist || c->cfg.n_particles_global != c->cfg.n_particles))
+        return fail(SLAMGPU_ERR_INVALID, "%s: single contexts only", who);
+    if (flags & kDevice) HIP_TRY(hipSetDevice(c->cfg.device));
+    if (flags & kBook)
+        if (int rc = book_pull(c)) return rc;
+    if (flags & kSettle) {
+        if (int rc = flush_predict(c)) return rc;
+        if (int rc = flush_stages(c)) return rc;
+    }
+    if (flags & kTables)
+        if (int rc = sync_tables(c)) return rc;
+    return 0;
+}
+
+// one timed launch and its error
+template <class F>
+int launch(slamgpu_ctx *c, const char *name, F &&f) {
+    {
+        Timed t(c, name);
+        f();
+    }
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int map_tiles(const slamgpu_ctx *c) { return (c->B.n + kMapTile - 1) / kMapTile; }
+
+// ---- rings ----
+int ring_check(const Ring &r, const char *who, const char *what, int64_t first, int64_t count) {
+    if (r.check(first, count)) return 0;
+    return fail(SLAMGPU_ERR_INVALID, "%s: %s [%lld, %lld + %lld) outside the retained [%lld, %lld)", who, what, (long long) first, (long long) first,
+                (long long) count, (long long) r.first, (long long) r.next);
+}
+void ring_info(const Ring &r, int64_t *first, int64_t *next, int32_t *capacity) {
+    if (first) *first = r.first;
+    if (next) *next = r.next;
+    if (capacity) *capacity = r.cap;
+}
+// entries [first, first + count) of a ring of `row` bytes per slot, enqueued: at most two stretches of it
+int ring_fetch(slamgpu_ctx *c, const Ring &r, const void *ring_dev, size_t row, int64_t first, int64_t count, void *host) {
+    const Ring::Runs s = r.stretches(first, count);
+    HIP_TRY(hipMemcpyAsync(host, (const char *) ring_dev + row * (size_t) s.at, row * (size_t) s.n0, hipMemcpyDeviceToHost, c->stream));
+    if (s.n1 > 0) HIP_TRY(hipMemcpyAsync((char *) host + row * (size_t) s.n0, ring_dev, row * (size_t) s.n1, hipMemcpyDeviceToHost, c->stream));
+    return 0;
+}
+
+// ---- path recording (slamgpu_path_*; kernels.h: PathRing) ----
+PathRing path_ring(const slamgpu_ctx *c) { return PathRing{c->path_rec_dev, c->path.cap}; }
+
+// the checks slamgpu_path_fetch / _trace / _summary share
+int path_check(slamgpu_ctx *c, const char *who, int64_t first, int64_t count) {
+    if (c->path.cap == 0) return fail(SLAMGPU_ERR_INVALID, "%s: recording is off (slamgpu_path_enable)", who);
+    return ring_check(c->path, who, "records", first, count);
+}
+
+// ---- pose posterior (slamgpu_pose_*; kernels.h: PoseSummaryArgs) ----
+int pose_tiles(const slamgpu_ctx *c) { return (c->B.n + kPoseTile - 1) / kPoseTile; }
+
+int pose_reserve(slamgpu_ctx *c) {
+    if (c->pose_dev) return 0;
+    const size_t total = sizeof(double) * ((size_t) kPoseFields * (size_t) pose_tiles(c) + kPoseStride);
+    hipError_t e = hipMalloc((void **) &c->pose_dev, total);
+    if (e != hipSuccess) {
+        (void) hipGetLastError();
+        c->pose_dev = nullptr;
+        return fail(SLAMGPU_ERR_ALLOC, "hipMalloc(%zu): %s", total, hipGetErrorString(e));
+    }
+    return 0;
+}
+double *pose_staging(const slamgpu_ctx *c) { return c->pose_dev + (size_t) kPoseFields * (size_t) pose_tiles(c); }
+
+// the summary of the set as it stands (the caller has brought it there), into `out_dev`: two launches, nothing else
+int pose_launch(slamgpu_ctx *c, double *out_dev) {
+    PoseSummaryArgs A{};
+    A.tiles = pose_tiles(c);
+    A.logw = c->cfg.log_weights;
+    A.part = c->pose_dev;
+    A.out = out_dev;
+    c->B.slot = c->slot;
+    if (int rc = launch(c, "pose_summary", [&] { c->k->pose_summary(c->stream, c->B, c->ws, A); })) return rc;
+    return launch(c, "pose_finish", [&] { c->k->pose_finish(c->stream, c->B, c->ws, A); });
+}
+
+// ---- innovation posterior (slamgpu_innovation_*; kernels.h: InnovArgs) ----
+constexpr int kInnovStage = 4;
+
+// what slamgpu_innovation_summary and slamgpu_innovation_record refuse alike (outputs untouched); m > 0 on return 0
+int innov_check(slamgpu_ctx *c, const char *fn, const float *zf, const int32_t *idf, int32_t m, const float *R) {
+    if (m < 0) return fail(SLAMGPU_ERR_INVALID, "%s: m %d", fn, m);
+    if (m == 0) return 0;
+    if (!zf || !idf || !R) return fail(SLAMGPU_ERR_INVALID, "%s: null %s", fn, !zf ? "zf" : !idf ? "idf" : "R");
+    if (int rc = summary_enter(c, fn, kDevice | kBook)) return rc;
+    for (int32_t q = 0; q < m; q++)
+        if (idf[q] < 0 || idf[q] >= c->nf)
+            return fail(SLAMGPU_ERR_INVALID, "%s: observation %d names slot %d outside [0, %d)", fn, q, idf[q], c->nf);
+    return 0;
+}
+
+// the m entries of the set as slamgpu_peek would show it: into the ring's slots slot(innov.next + q) with their tags (ring), or
+// into the staging area, from where out_dev / hold_dev point at them.  Enqueued; the caller has checked the packet (m > 0)
+int innov_launch(slamgpu_ctx *c, const float *zf, const int32_t *idf, int32_t m, const float *R, bool ring, const double **out_dev,
+                 const int32_t **hold_dev) {
+    static_assert(SLAMGPU_INNOV_STRIDE == kInnStride, "public / device summary layout");
+    static_assert(sizeof c->innov_ev / sizeof c->innov_ev[0] == kInnovStage, "staging slots");
+    if (int rc = summary_enter(c, "", kSettle | kTables)) return rc;
+    const int tiles = map_tiles(c);
+    // the packet goes through the partials' table a chunk at a time, capped as the map summary's is
+    const size_t M = (size_t) m, per_obs = sizeof(double) * kInnFields * (size_t) tiles;
+    const int chunk = chunk_fit("SLAMGPU_INNOV_CHUNK", per_obs, kMapSlots, m);
+    Layout L;
+    const auto out = L.take<double>(kInnStride * M), wpart = L.take<double>(2 * (size_t) tiles), part = L.take<double>(kInnFields * (size_t) tiles * chunk);
+    const auto zf_d = L.take<float>(2 * M);
+    const auto idf_d = L.take<int32_t>(M), hold = L.take<int32_t>(M);
+    if (int rc = c->msum.reserve(L.total())) return rc;
+    // the packet: through a pinned slot of the context's own, so that the caller's arrays are free again when the call returns
+    if (M > c->innov_host_m) {
+        for (int k = 0; k < kInnovStage; k++)
+            if (c->innov_ev_used[k]) HIP_TRY(hipEventSynchronize(c->innov_ev[k]));
+        if (c->innov_host) (void) hipHostFree(c->innov_host);
+        c->innov_host = nullptr;
+        c->innov_host_m = 0;
+        const size_t want = std::max<size_t>(M, 64);
+        hipError_t e = hipHostMalloc((void **) &c->innov_host, 12 * want * kInnovStage, hipHostMallocDefault);
+        if (e != hipSuccess) {
+            (void) hipGetLastError();
+            c->innov_host = nullptr;
+            return fail(SLAMGPU_ERR_ALLOC, "hipHostMalloc(%zu): %s", 12 * want * kInnovStage, hipGetErrorString(e));
+        }
+        c->innov_host_m = want;
+    }
+    const int k = (int) (c->innov_seq++ % kInnovStage);
+    if (!c->innov_ev[k]) HIP_TRY(hipEventCreateWithFlags(&c->innov_ev[k], hipEventDisableTiming));
+    if (c->innov_ev_used[k]) HIP_TRY(hipEventSynchronize(c->innov_ev[k]));
+    char *h = c->innov_host + 12 * c->innov_host_m * (size_t) k;
+    memcpy(h, zf, sizeof(float) * 2 * M);
+    memcpy(h + sizeof(float) * 2 * M, idf, sizeof(int32_t) * M);
+    HIP_TRY(hipMemcpyAsync(zf_d.at(c->msum), h, 12 * M, hipMemcpyHostToDevice, c->stream));  // (zf | idf: adjacent in both places)
+    HIP_TRY(hipEventRecord(c->innov_ev[k], c->stream));
+    c->innov_ev_used[k] = true;
+    c->B.slot = c->slot;
+    for (int at = 0; at < m; at += chunk) {
+        InnovArgs I{};
+        MapSummaryArgs &A = I.S;
+        A.first_slot = 0;
+        A.count = std::min(chunk, m - at);
+        A.tiles = tiles;
+        A.logw = c->cfg.log_weights;
+        A.part = part.at(c->msum);
+        A.wpart = wpart.at(c->msum);
+        I.zf = zf_d.at(c->msum) + (size_t) 2 * at;
+        I.idf = idf_d.at(c->msum) + at;
+        I.r00 = R[0];
+        I.r10 = R[2];
+        I.r11 = R[3];
+        if (ring) {
+            A.out = c->innov_ring_dev;
+            A.holders = nullptr;
+            I.ring_cap = c->innov.cap;
+            I.ring_at = c->innov.next + at;
+            I.tag = c->innov_tag_dev;
+            I.record = (int32_t) c->innov_records;
+        } else {
+            A.out = out.at(c->msum) + (size_t) kInnStride * at;
+            A.holders = hold.at(c->msum) + at;
+        }
+        if (int rc = launch(c, "innovation_summary", [&] { c->k->innovation_summary(c->stream, c->B, c->ws, I); })) return rc;
+        if (int rc = launch(c, "innovation_finish", [&] { c->k->innovation_finish(c->stream, I); })) return rc;
+    }
+    if (out_dev) *out_dev = out.at(c->msum);
+    if (hold_dev) *hold_dev = hold.at(c->msum);
+    return 0;
+}
+
+}  // namespace
+
+// after an update launch: its resampling stage, then origin' = origin o ancestors.  The kernel reads Ctrl.resampled itself (no
+// synchronisation); the host flips the origin buffers whatever it decides.  Once per update that RAN: issue_update calls it
+int path_compose(slamgpu_ctx *c) {
+    if (int rc = flush_stages(c)) return rc;
+    c->B.slot = c->slot;
+    if (int rc = launch(c, "path_compose", [&] {
+            c->k->path_compose(c->stream, c->B, c->ws, c->keep_slot, c->path_origin_dev[c->path_org], c->path_origin_dev[c->path_org ^ 1]);
+        }))
+        return rc;
+    c->path_org ^= 1;
+    return 0;
+}
+
+int path_identity(slamgpu_ctx *c) {
+    Timed t(c, "path_compose");
+    c->k->path_compose(c->stream, c->B, c->ws, 0, nullptr, c->path_origin_dev[c->path_org]);
+    return 0;
+}
+
+// the set as slamgpu_peek would show it, into the ring's next slot (a full ring drops its oldest record)
+int path_append(slamgpu_ctx *c) {
+    if (int rc = summary_enter(c, "", kDevice | kSettle)) return rc;
+    c->B.slot = c->slot;
+    if (int rc = launch(c, "path_record", [&] {
+            c->k->path_record(c->stream, c->B, c->ws, path_ring(c), (int) c->path.slot(c->path.next), c->path_origin_dev[c->path_org]);
+        }))
+        return rc;
+    c->path.advance(1);
+    return 0;
+}
+
+// the summary of the set as slamgpu_peek would show it, into the ring's next slot (a full ring drops its oldest entry).  Between
+// iterations of slamgpu_run_particle the state stays on the device: the stage the last iteration left (only the device knows
+// whether it updated) is run here with the iterations' own kernels, as the next iteration would have run it first thing
+int pose_append(slamgpu_ctx *c) {
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    if (c->pp_on_device) {
+        if (!c->pp_stage_ran) c->pp_stage_open = true;
+        if (int rc = pp_dev_flush_predict(c)) return rc;
+        if (int rc = pp_dev_stage(c)) return rc;
+        c->pp_stage_ran = true;
+    } else {
+        if (int rc = summary_enter(c, "", kSettle)) return rc;
+    }
+    if (int rc = pose_launch(c, c->pose_ring_dev + (size_t) kPoseStride * (size_t) c->pose.slot(c->pose.next))) return rc;
+    c->pose.advance(1);
+    return 0;
+}
+
+// slamgpu_innovation_record past its context checks (slamgpu_step calls it with its own packet)
+int innov_append(slamgpu_ctx *c, const float *zf, const int32_t *idf, int32_t m, const float *R) {
+    if (int rc = innov_check(c, "slamgpu_innovation_record", zf, idf, m, R)) return rc;
+    if (m > c->innov.cap)
+        return fail(SLAMGPU_ERR_CAPACITY, "slamgpu_innovation_record: %d observations, the ring holds %d entries", m, c->innov.cap);
+    if (m > 0) {
+        if (int rc = innov_launch(c, zf, idf, m, R, true, nullptr, nullptr)) return rc;
+        c->innov.advance(m);
+    }
+    c->innov_records++;
+    return 0;
+}
+
+void posterior_release(slamgpu_ctx *c) {
+    c->msum.release();
+    if (c->pose_ring_dev) (void) hipFree(c->pose_ring_dev);
+    if (c->pose_dev) (void) hipFree(c->pose_dev);
+    if (c->innov_ring_dev) (void) hipFree(c->innov_ring_dev);
+    if (c->innov_tag_dev) (void) hipFree(c->innov_tag_dev);
+    if (c->innov_host) (void) hipHostFree(c->innov_host);
+    for (hipEvent_t e : c->innov_ev)
+        if (e) (void) hipEventDestroy(e);
+    if (c->path_rec_dev) (void) hipFree(c->path_rec_dev);
+    for (int b = 0; b < 2; b++)
+        if (c->path_origin_dev[b]) (void) hipFree(c->path_origin_dev[b]);
+    c->path_arena.release();
+}
+
+#pragma GCC visibility pop
+
+extern "C" {
+
+int slamgpu_map_summary(slamgpu_ctx *c, int32_t first_slot, int32_t count, double *out, int32_t *holders) {
+    if (int rc = summary_enter(c, "slamgpu_map_summary", kCtx | kSingle | kDevice | kBook)) return rc;
+    if (first_slot < 0 || count < 0 || (int64_t) first_slot + (int64_t) count > (int64_t) c->nf)
+        return fail(SLAMGPU_ERR_INVALID, "slots [%d, %d + %d) outside [0, %d)", first_slot, first_slot, count, c->nf);
+    if (count == 0) return 0;
+    if (!out) return fail(SLAMGPU_ERR_INVALID, "null output");
+    static_assert(SLAMGPU_MAP_STRIDE == kMapStride, "public / device summary layout");
+    if (int rc = summary_enter(c, "slamgpu_map_summary", kSettle | kTables)) return rc;
+    const int tiles = map_tiles(c);
+    // the slots go through the partials' table a chunk at a time, whatever the map's size
+    const size_t M = (size_t) count, per_slot = sizeof(double) * kMapFields * (size_t) tiles;
+    const int chunk = chunk_fit("SLAMGPU_MAP_CHUNK", per_slot, kMapSlots, count);
+    Layout L;
+    const auto out_d = L.take<double>(kMapStride * M), wpart = L.take<double>(2 * (size_t) tiles), part = L.take<double>(kMapFields * (size_t) tiles * chunk);
+    const auto hold = L.take<int32_t>(M);
+    if (int rc = c->msum.reserve(L.total())) return rc;
+    c->B.slot = c->slot;
+    for (int at = 0; at < count; at += chunk) {
+        MapSummaryArgs A{};
+        A.first_slot = first_slot + at;
+        A.count = std::min(chunk, count - at);
+        A.tiles = tiles;
+        A.logw = c->cfg.log_weights;
+        A.part = part.at(c->msum);
+        A.wpart = wpart.at(c->msum);
+        A.out = out_d.at(c->msum) + (size_t) kMapStride * at;
+        A.holders = hold.at(c->msum) + at;
+        if (int rc = launch(c, "map_summary", [&] { c->k->map_summary(c->stream, c->B, c->ws, A); })) return rc;
+        if (int rc = launch(c, "map_finish", [&] { c->k->map_finish(c->stream, A); })) return rc;
+    }
+    HIP_TRY(hipMemcpyAsync(out, out_d.at(c->msum), sizeof(double) * kMapStride * M, hipMemcpyDeviceToHost, c->stream));
+    if (holders) HIP_TRY(hipMemcpyAsync(holders, hold.at(c->msum), sizeof(int32_t) * M, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+int slamgpu_map_pairs(slamgpu_ctx *c, const int32_t *pairs, int32_t count, double *out, int32_t *both) {
+    if (int rc = summary_enter(c, "slamgpu_map_pairs", kCtx | kSingle)) return rc;
+    if (count < 0) return fail(SLAMGPU_ERR_INVALID, "slamgpu_map_pairs: count %d", count);
+    if (count == 0) return 0;
+    if (!pairs || !out) return fail(SLAMGPU_ERR_INVALID, "slamgpu_map_pairs: null %s", pairs ? "output" : "pairs");
+    if (int rc = summary_enter(c, "slamgpu_map_pairs", kDevice | kBook)) return rc;
+    for (int64_t k = 0; k < 2 * (int64_t) count; k++)
+        if (pairs[k] < 0 || pairs[k] >= c->nf)
+            return fail(SLAMGPU_ERR_INVALID, "slamgpu_map_pairs: pair %lld names slot %d outside [0, %d)", (long long) (k / 2), pairs[k], c->nf);
+    if (int rc = summary_enter(c, "slamgpu_map_pairs", kSettle | kTables)) return rc;
+    const int tiles = map_tiles(c);
+    // the pairs go through the summary's table of partials, cut the same way (a pair's sums do not depend on the cut)
+    const size_t M = (size_t) count, per_pair = sizeof(double) * kMapFields * (size_t) tiles;
+    const int chunk = chunk_fit("SLAMGPU_MAP_CHUNK", per_pair, kMapSlots, count);
+    Layout L;
+    const auto out_d = L.take<double>(kMapStride * M), wpart = L.take<double>(2 * (size_t) tiles), part = L.take<double>(kMapFields * (size_t) tiles * chunk);
+    const auto both_d = L.take<int32_t>(M), pairs_d = L.take<int32_t>(2 * M);
+    if (int rc = c->msum.reserve(L.total())) return rc;
+    HIP_TRY(hipMemcpyAsync(pairs_d.at(c->msum), pairs, sizeof(int32_t) * 2 * M, hipMemcpyHostToDevice, c->stream));
+    c->B.slot = c->slot;
+    for (int at = 0; at < count; at += chunk) {
+        MapPairsArgs P{};
+        MapSummaryArgs &A = P.S;
+        A.first_slot = 0;
+        A.count = std::min(chunk, count - at);
+        A.tiles = tiles;
+        A.logw = c->cfg.log_weights;
+        A.part = part.at(c->msum);
+        A.wpart = wpart.at(c->msum);
+        A.out = out_d.at(c->msum) + (size_t) kMapStride * at;
+        A.holders = both_d.at(c->msum) + at;
+        P.pairs = pairs_d.at(c->msum) + (size_t) 2 * at;
+        if (int rc = launch(c, "map_pairs", [&] { c->k->map_pairs(c->stream, c->B, c->ws, P); })) return rc;
+        if (int rc = launch(c, "map_finish", [&] { c->k->map_finish(c->stream, A); })) return rc;
+    }
+    HIP_TRY(hipMemcpyAsync(out, out_d.at(c->msum), sizeof(double) * kMapStride * M, hipMemcpyDeviceToHost, c->stream));
+    if (both) HIP_TRY(hipMemcpyAsync(both, both_d.at(c->msum), sizeof(int32_t) * M, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+int slamgpu_joint_summary(slamgpu_ctx *c, const int32_t *slots, int32_t k, double *out, int32_t *both) {
+    if (int rc = summary_enter(c, "slamgpu_joint_summary", kCtx | kSingle)) return rc;
+    static_assert(SLAMGPU_JOINT_MAX_SLOTS == kJointMaxSlots && 3 + 2 * kJointMaxSlots + 1 <= kJointCols, "public / device limits");
+    if (k < 0 || k > SLAMGPU_JOINT_MAX_SLOTS) return fail(SLAMGPU_ERR_INVALID, "slamgpu_joint_summary: k %d outside [0, %d]", k, SLAMGPU_JOINT_MAX_SLOTS);
+    if (!out || (k > 0 && !slots)) return fail(SLAMGPU_ERR_INVALID, "slamgpu_joint_summary: null %s", out ? "slots" : "output");
+    if (int rc = summary_enter(c, "slamgpu_joint_summary", kDevice | kBook)) return rc;
+    for (int s = 0; s < k; s++)
+        if (slots[s] < 0 || slots[s] >= c->nf)
+            return fail(SLAMGPU_ERR_INVALID, "slamgpu_joint_summary: entry %d names slot %d outside [0, %d)", s, slots[s], c->nf);
+    if (int rc = summary_enter(c, "slamgpu_joint_summary", kSettle | kTables)) return rc;
+    const int tiles = map_tiles(c);
+    const int D = 3 + 2 * k, Dp = (D + 1 + 15) / 16 * 16, nb = Dp / 16, nbp = nb * (nb + 1) / 2;
+    const size_t size = (size_t) SLAMGPU_JOINT_SIZE(k), nq = 6 + 3 * (size_t) k, T = (size_t) tiles;
+    // the block pairs go through the summaries' table of partials a chunk at a time (a block pair's sums do not depend on the cut)
+    const int chunk = chunk_fit("SLAMGPU_JOINT_CHUNK", sizeof(double) * 256 * T, 1, nbp);
+    Layout L;
+    const auto out_d = L.take<double>(size), wpart = L.take<double>(2 * T), pivot = L.take<double>(kJointCols), sums = L.take<double>(256 * (size_t) nbp),
+               pvf = L.take<double>(nq * T), part = L.take<double>(256 * T * chunk);
+    const auto tile_info = L.take<int32_t>(2 * T), info = L.take<int32_t>(4), slots_d = L.take<int32_t>((size_t) k);
+    const auto hold = L.take<uint8_t>(up16((size_t) c->B.n), 16);
+    if (int rc = c->msum.reserve(L.total())) return rc;
+    if (k > 0) HIP_TRY(hipMemcpyAsync(slots_d.at(c->msum), slots, sizeof(int32_t) * (size_t) k, hipMemcpyHostToDevice, c->stream));
+    c->B.slot = c->slot;
+    JointArgs J{};
+    J.S.tiles = tiles;
+    J.S.logw = c->cfg.log_weights;
+    J.S.part = part.at(c->msum);
+    J.S.wpart = wpart.at(c->msum);
+    J.S.out = out_d.at(c->msum);
+    J.S.holders = info.at(c->msum) + 2;
+    J.k = k;
+    J.D = D;
+    J.Dp = Dp;
+    if (const char *e = getenv("SLAMGPU_JOINT_PLAIN_FMA")) J.plain = atoi(e) != 0;  // (diagnostic: tools/joint_probe.py's comparison of the two forms)
+    J.slots = slots_d.at(c->msum);
+    J.hold = hold.at(c->msum);
+    J.tile_info = tile_info.at(c->msum);
+    J.info = info.at(c->msum);
+    J.pivot = pivot.at(c->msum);
+    J.sums = sums.at(c->msum);
+    J.pvf = pvf.at(c->msum);
+    if (int rc = launch(c, "joint_hold", [&] { c->k->joint_hold(c->stream, c->B, c->ws, J); })) return rc;
+    if (int rc = launch(c, "joint_pivot", [&] { c->k->joint_pivot(c->stream, c->B, c->ws, J); })) return rc;
+    for (int at = 0; at < nbp; at += chunk) {
+        J.bp_first = at;
+        J.bp_count = std::min(chunk, nbp - at);
+        if (int rc = launch(c, "joint_gram", [&] { c->k->joint_gram(c->stream, c->B, c->ws, J); })) return rc;
+        if (int rc = launch(c, "joint_reduce", [&] { c->k->joint_reduce(c->stream, J); })) return rc;
+    }
+    if (int rc = launch(c, "joint_finish", [&] { c->k->joint_finish(c->stream, c->B, c->ws, J); })) return rc;
+    std::vector<double> h(size);  // (outputs untouched if a copy fails)
+    int32_t hb = 0;
+    HIP_TRY(hipMemcpyAsync(h.data(), out_d.at(c->msum), sizeof(double) * size, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(&hb, J.S.holders, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    memcpy(out, h.data(), sizeof(double) * size);
+    if (both) *both = hb;
+    return 0;
+}
+
+int slamgpu_pose_summary(slamgpu_ctx *c, double *out) {
+    if (int rc = summary_enter(c, "slamgpu_pose_summary", kCtx | kSingle)) return rc;
+    if (!out) return fail(SLAMGPU_ERR_INVALID, "slamgpu_pose_summary: null output");
+    static_assert(SLAMGPU_POSE_STRIDE == kPoseStride, "public / device summary layout");
+    if (int rc = summary_enter(c, "slamgpu_pose_summary", kDevice | kSettle)) return rc;
+    if (int rc = pose_reserve(c)) return rc;
+    if (int rc = pose_launch(c, pose_staging(c))) return rc;
+    double h[kPoseStride];
+    HIP_TRY(hipMemcpyAsync(h, pose_staging(c), sizeof h, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    memcpy(out, h, sizeof h);
+    return 0;
+}
+
+int slamgpu_pose_history_enable(slamgpu_ctx *c, int32_t capacity) {
+    if (int rc = summary_enter(c, "slamgpu_pose_history_enable", kCtx | kSingle)) return rc;
+    if (capacity < 0) return fail(SLAMGPU_ERR_INVALID, "slamgpu_pose_history_enable: capacity %d", capacity);
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    // the new ring first: a refused call leaves the setting as it was
+    double *ring = nullptr;
+    if (capacity > 0) {
+        if (int rc = pose_reserve(c)) return rc;
+        const size_t bytes = sizeof(double) * kPoseStride * (size_t) capacity;
+        hipError_t e = hipMalloc((void **) &ring, bytes);
+        if (e != hipSuccess) {
+            (void) hipGetLastError();
+            return fail(SLAMGPU_ERR_ALLOC, "slamgpu_pose_history_enable: %d entries (%zu bytes): %s", capacity, bytes, hipGetErrorString(e));
+        }
+    }
+    if (c->pose_ring_dev) {
+        HIP_TRY(hipStreamSynchronize(c->stream));  // (launches in flight may still write the old ring)
+        (void) hipFree(c->pose_ring_dev);
+    }
+    c->pose_ring_dev = ring;
+    c->pose.reset(capacity);
+    return 0;
+}
+
+int slamgpu_pose_history_record(slamgpu_ctx *c) {
+    if (int rc = check_ctx(c)) return rc;
+    if (c->pose.cap == 0) return fail(SLAMGPU_ERR_INVALID, "slamgpu_pose_history_record: the ring is off (slamgpu_pose_history_enable)");
+    return pose_append(c);
+}
+
+int slamgpu_pose_history_info(slamgpu_ctx *c, int64_t *first, int64_t *next, int32_t *capacity) {
+    if (int rc = check_ctx(c)) return rc;
+    ring_info(c->pose, first, next, capacity);
+    return 0;
+}
+
+int slamgpu_pose_history_fetch(slamgpu_ctx *c, int64_t first, int32_t count, double *out) {
+    if (int rc = check_ctx(c)) return rc;
+    if (int rc = ring_check(c->pose, "slamgpu_pose_history_fetch", "entries", first, count)) return rc;
+    if (count == 0) return 0;
+    if (!out) return fail(SLAMGPU_ERR_INVALID, "slamgpu_pose_history_fetch: null output");
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    std::vector<double> h((size_t) kPoseStride * (size_t) count);
+    if (int rc = ring_fetch(c, c->pose, c->pose_ring_dev, sizeof(double) * kPoseStride, first, count, h.data())) return rc;
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    memcpy(out, h.data(), sizeof(double) * h.size());
+    return 0;
+}
+
+int slamgpu_innovation_summary(slamgpu_ctx *c, const float *zf, const int32_t *idf, int32_t m, const float R[4], double *out, int32_t *holders) {
+    if (int rc = summary_enter(c, "slamgpu_innovation_summary", kCtx | kSingle)) return rc;
+    if (int rc = innov_check(c, "slamgpu_innovation_summary", zf, idf, m, R)) return rc;
+    if (m == 0) return 0;
+    if (!out) return fail(SLAMGPU_ERR_INVALID, "slamgpu_innovation_summary: null output");
+    const double *out_dev = nullptr;
+    const int32_t *hold_dev = nullptr;
+    if (int rc = innov_launch(c, zf, idf, m, R, false, &out_dev, &hold_dev)) return rc;
+    HIP_TRY(hipMemcpyAsync(out, out_dev, sizeof(double) * kInnStride * (size_t) m, hipMemcpyDeviceToHost, c->stream));
+    if (holders) HIP_TRY(hipMemcpyAsync(holders, hold_dev, sizeof(int32_t) * (size_t) m, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+int slamgpu_innovation_history_enable(slamgpu_ctx *c, int32_t capacity) {
+    if (int rc = summary_enter(c, "slamgpu_innovation_history_enable", kCtx | kSingle)) return rc;
+    if (capacity < 0) return fail(SLAMGPU_ERR_INVALID, "slamgpu_innovation_history_enable: capacity %d", capacity);
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    // the new ring first: a refused call leaves the setting as it was
+    double *ring = nullptr;
+    int32_t *tag = nullptr;
+    if (capacity > 0) {
+        const size_t bytes = sizeof(double) * kInnStride * (size_t) capacity;
+        hipError_t e = hipMalloc((void **) &ring, bytes);
+        if (e == hipSuccess) {
+            e = hipMalloc((void **) &tag, sizeof(int32_t) * 2 * (size_t) capacity);
+            if (e != hipSuccess) (void) hipFree(ring);
+        }
+        if (e != hipSuccess) {
+            (void) hipGetLastError();
+            return fail(SLAMGPU_ERR_ALLOC, "slamgpu_innovation_history_enable: %d entries (%zu bytes): %s", capacity, bytes, hipGetErrorString(e));
+        }
+    }
+    if (c->innov_ring_dev) {
+        HIP_TRY(hipStreamSynchronize(c->stream));  // (launches in flight may still write the old ring)
+        (void) hipFree(c->innov_ring_dev);
+        (void) hipFree(c->innov_tag_dev);
+    }
+    c->innov_ring_dev = ring;
+    c->innov_tag_dev = tag;
+    c->innov.reset(capacity);
+    c->innov_records = 0;
+    return 0;
+}
+
+int slamgpu_innovation_record(slamgpu_ctx *c, const float *zf, const int32_t *idf, int32_t m, const float R[4]) {
+    if (int rc = summary_enter(c, "slamgpu_innovation_record", kCtx | kSingle)) return rc;
+    if (c->innov.cap == 0) return fail(SLAMGPU_ERR_INVALID, "slamgpu_innovation_record: the ring is off (slamgpu_innovation_history_enable)");
+    return innov_append(c, zf, idf, m, R);
+}
+
+int slamgpu_innovation_history_info(slamgpu_ctx *c, int64_t *first, int64_t *next, int32_t *capacity, int64_t *records) {
+    if (int rc = check_ctx(c)) return rc;
+    ring_info(c->innov, first, next, capacity);
+    if (records) *records = c->innov_records;
+    return 0;
+}
+
+int slamgpu_innovation_history_fetch(slamgpu_ctx *c, int64_t first, int32_t count, double *out, int32_t *record, int32_t *slot) {
+    if (int rc = check_ctx(c)) return rc;
+    if (int rc = ring_check(c->innov, "slamgpu_innovation_history_fetch", "entries", first, count)) return rc;
+    if (count == 0) return 0;
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    std::vector<double> h((size_t) kInnStride * (size_t) count);
+    std::vector<int32_t> tg((size_t) 2 * (size_t) count);
+    if (int rc = ring_fetch(c, c->innov, c->innov_ring_dev, sizeof(double) * kInnStride, first, count, h.data())) return rc;
+    if (int rc = ring_fetch(c, c->innov, c->innov_tag_dev, sizeof(int32_t) * 2, first, count, tg.data())) return rc;
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (out) memcpy(out, h.data(), sizeof(double) * h.size());
+    for (int32_t q = 0; q < count; q++) {
+        if (record) record[q] = tg[2 * (size_t) q];
+        if (slot) slot[q] = tg[2 * (size_t) q + 1];
+    }
+    return 0;
+}
+
+int slamgpu_path_enable(slamgpu_ctx *c, int32_t capacity) {
+    if (int rc = summary_enter(c, "slamgpu_path_enable", kCtx | kSingle)) return rc;
+    if (capacity < 0) return fail(SLAMGPU_ERR_INVALID, "slamgpu_path_enable: capacity %d", capacity);
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    // the new ring first: a refused call leaves the recording as it was
+    float4 *rec = nullptr;
+    int32_t *org[2] = {nullptr, nullptr};
+    if (capacity > 0) {
+        const size_t S = (size_t) c->B.ncap, bytes = sizeof(float4) * S * (size_t) capacity;
+        hipError_t e = hipMalloc((void **) &rec, bytes);
+        for (int b = 0; b < 2 && e == hipSuccess; b++) e = hipMalloc((void **) &org[b], sizeof(int32_t) * S);
+        if (e != hipSuccess) {
+            (void) hipGetLastError();
+            if (rec) (void) hipFree(rec);
+            for (int b = 0; b < 2; b++)
+                if (org[b]) (void) hipFree(org[b]);
+            return fail(SLAMGPU_ERR_ALLOC, "slamgpu_path_enable: %d records of %d particles (%zu bytes): %s", capacity, c->B.n, bytes, hipGetErrorString(e));
+        }
+    }
+    if (c->path.cap > 0 || c->path_arena.p) {
+        HIP_TRY(hipStreamSynchronize(c->stream));  // (launches in flight may still use the old ring)
+        if (c->path_rec_dev) (void) hipFree(c->path_rec_dev);
+        for (int b = 0; b < 2; b++)
+            if (c->path_origin_dev[b]) (void) hipFree(c->path_origin_dev[b]);
+        c->path_arena.release();
+    }
+    c->path_rec_dev = rec;
+    c->path_origin_dev[0] = org[0];
+    c->path_origin_dev[1] = org[1];
+    c->path_org = 0;
+    c->path.reset(capacity);
+    if (capacity > 0) {
+        if (int rc = path_identity(c)) return rc;
+        HIP_TRY(hipGetLastError());
+    }
+    return 0;
+}
+
+int slamgpu_path_record(slamgpu_ctx *c) {
+    if (int rc = check_ctx(c)) return rc;
+    if (c->path.cap == 0) return fail(SLAMGPU_ERR_INVALID, "slamgpu_path_record: recording is off (slamgpu_path_enable)");
+    return path_append(c);
+}
+
+int slamgpu_path_info(slamgpu_ctx *c, int64_t *first, int64_t *next, int32_t *capacity) {
+    if (int rc = check_ctx(c)) return rc;
+    ring_info(c->path, first, next, capacity);
+    return 0;
+}
+
+int slamgpu_path_fetch(slamgpu_ctx *c, int64_t r, float *xyt, int32_t *parent) {
+    if (int rc = check_ctx(c)) return rc;
+    if (int rc = path_check(c, "slamgpu_path_fetch", r, 1)) return rc;
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    const size_t N = (size_t) c->B.n;
+    std::vector<float4> rec(N);
+    HIP_TRY(hipMemcpyAsync(rec.data(), c->path_rec_dev + (size_t) c->path.slot(r) * (size_t) c->B.ncap, sizeof(float4) * N, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    for (size_t k = 0; k < N; k++) {
+        if (xyt) {
+            xyt[3 * k] = rec[k].x;
+            xyt[3 * k + 1] = rec[k].y;
+            xyt[3 * k + 2] = rec[k].z;
+        }
+        if (parent) memcpy(parent + k, &rec[k].w, sizeof(int32_t));
+    }
+    return 0;
+}
+
+int slamgpu_path_trace(slamgpu_ctx *c, int32_t particle, int64_t first, int32_t count, float *xyt, int32_t *index) {
+    if (int rc = check_ctx(c)) return rc;
+    if (int rc = path_check(c, "slamgpu_path_trace", first, count)) return rc;
+    if (particle < -1 || particle >= c->B.n) return fail(SLAMGPU_ERR_INVALID, "slamgpu_path_trace: particle %d outside [-1, %d)", particle, c->B.n);
+    if (count == 0) return 0;
+    if (int rc = summary_enter(c, "slamgpu_path_trace", kDevice | kSettle)) return rc;
+    const size_t M = (size_t) count;
+    Layout L;
+    const auto xyt_d = L.take<float>(3 * M);
+    const auto index_d = L.take<int32_t>(M, 16);
+    if (int rc = c->path_arena.reserve(L.total())) return rc;
+    PathTraceArgs A{};
+    A.particle = particle;
+    A.newest = c->path.next - 1;
+    A.first = first;
+    A.count = count;
+    A.origin = c->path_origin_dev[c->path_org];
+    A.xyt = xyt_d.at(c->path_arena);
+    A.index = index_d.at(c->path_arena);
+    c->B.slot = c->slot;
+    if (int rc = launch(c, "path_trace", [&] { c->k->path_trace(c->stream, c->B, c->ws, path_ring(c), A); })) return rc;
+    if (xyt) HIP_TRY(hipMemcpyAsync(xyt, A.xyt, sizeof(float) * 3 * M, hipMemcpyDeviceToHost, c->stream));
+    if (index) HIP_TRY(hipMemcpyAsync(index, A.index, sizeof(int32_t) * M, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+int slamgpu_path_summary(slamgpu_ctx *c, int64_t first, int32_t count, double *out, int32_t *distinct) {
+    if (int rc = check_ctx(c)) return rc;
+    if (int rc = path_check(c, "slamgpu_path_summary", first, count)) return rc;
+    if (count == 0) return 0;
+    if (!out) return fail(SLAMGPU_ERR_INVALID, "null output");
+    static_assert(SLAMGPU_PATH_STRIDE == kPathStride, "public / device summary layout");
+    if (int rc = summary_enter(c, "slamgpu_path_summary", kDevice | kSettle)) return rc;
+    const int tiles = (c->B.n + kBlock - 1) / kBlock;
+    const size_t S = (size_t) c->B.ncap, M = (size_t) count;
+    // the records go through the partials' table a chunk at a time, however many are asked for
+    const int chunk = chunk_fit("SLAMGPU_PATH_CHUNK", sizeof(double) * kPathFields * (size_t) tiles, 1, count);
+    Layout L;
+    const auto out_d = L.take<double>(kPathStride * M), wpart = L.take<double>(2 * (size_t) tiles), wtot = L.take<double>(2);
+    const auto W = L.take<unsigned long long>(2 * S);
+    const auto part = L.take<double>(kPathFields * (size_t) tiles * chunk);
+    const auto C = L.take<uint32_t>(2 * S);
+    const auto distinct_d = L.take<int32_t>(M);
+    if (int rc = c->path_arena.reserve(L.total())) return rc;
+    PathWalkArgs A{};
+    A.tiles = tiles;
+    A.logw = c->cfg.log_weights;
+    A.wpart = wpart.at(c->path_arena);
+    A.wtot = wtot.at(c->path_arena);
+    A.origin = c->path_origin_dev[c->path_org];
+    A.W[0] = W.at(c->path_arena);
+    A.W[1] = A.W[0] + S;
+    A.C[0] = C.at(c->path_arena);
+    A.C[1] = A.C[0] + S;
+    A.part = part.at(c->path_arena);
+    A.chunk = chunk;
+    c->B.slot = c->slot;
+    HIP_TRY(hipMemsetAsync(A.W[0], 0, sizeof(unsigned long long) * 2 * S, c->stream));
+    HIP_TRY(hipMemsetAsync(A.C[0], 0, sizeof(uint32_t) * 2 * S, c->stream));
+    // (the walk's launches are checked once per loop, as they always were)
+    for (int stage = 0; stage < 3; stage++) {
+        Timed t(c, "path_seed");
+        c->k->path_seed(c->stream, c->B, c->ws, A, stage);
+    }
+    HIP_TRY(hipGetLastError());
+    // newest record first; a chunk is finished when its oldest record has been walked
+    const PathRing R = path_ring(c);
+    int64_t lo = first + count;  // the chunk in progress is [lo, hi)
+    int64_t hi = lo;
+    int cur = 0;
+    for (int64_t r = c->path.next - 1; r >= first; r--) {
+        if (r < lo) {
+            hi = lo;
+            lo = std::max<int64_t>(first, hi - chunk);
+        }
+        A.r = r;
+        A.cur = cur;
+        A.push = r > first ? 1 : 0;
+        A.at = r < first + count ? (int32_t) (r - lo) : -1;
+        {
+            Timed t(c, "path_push");
+            c->k->path_push(c->stream, c->B, R, A);
+        }
+        cur ^= 1;
+        if (r == lo && A.at >= 0) {
+            A.count = (int32_t) (hi - lo);
+            A.out = out_d.at(c->path_arena) + (size_t) kPathStride * (size_t) (lo - first);
+            A.distinct = distinct_d.at(c->path_arena) + (size_t) (lo - first);
+            Timed t(c, "path_finish");
+            c->k->path_finish(c->stream, A);
+        }
+    }
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(out, out_d.at(c->path_arena), sizeof(double) * kPathStride * M, hipMemcpyDeviceToHost, c->stream));
+    if (distinct) HIP_TRY(hipMemcpyAsync(distinct, distinct_d.at(c->path_arena), sizeof(int32_t) * M, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+}  // extern "C"

@@ -1,33 +1,13 @@
 // libslamgpu.so — C ABI over the gfx950 kernels (include/slamgpu.h).  Host side only: owns the device
 // buffers, the HIP stream, the pinned staging rings and the lazy predict queue.  No CPU compute path:
 // if there is no usable GPU every entry point fails with SLAMGPU_ERR_NO_DEVICE.
-#define SLAMGPU_EXPERIMENTAL 1  // (the library defines every entry point, the experimental ones included)
-#include "../../include/slamgpu.h"
-
-#include <hip/hip_runtime.h>
-#include <dlfcn.h>
-#include <rccl/rccl.h>
-#include <unistd.h>
-
-#include <algorithm>
-#include <atomic>
-#include <chrono>
-#include <cmath>
-#include <cstdarg>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <map>
-#include <string>
-#include <vector>
-
-#include "kernels.h"
-
-using namespace slamgpu;
+#include "slamgpu_ctx.h"
 
 namespace {
 
 thread_local char g_err[1024] = "";
+
+}  // namespace
 
 int fail(int code, const char *fmt, ...) {
     va_list ap;
@@ -36,6 +16,8 @@ int fail(int code, const char *fmt, ...) {
     va_end(ap);
     return code;
 }
+
+namespace {
 
 // RCCL is bound at run time (dlopen): the library of the process (torch's when torch is loaded, /opt/rocm's otherwise), and no
 // link-time dependency for single-GPU users.
@@ -82,301 +64,9 @@ const Rccl *rccl() {
         if (r_ != ncclSuccess) return fail(SLAMGPU_ERR_HIP, "%s: %s", #expr, rccl()->GetErrorString(r_)); \
     } while (0)
 
-
-#define HIP_TRY(expr)                                                                              \
-    do {                                                                                           \
-        hipError_t e_ = (expr);                                                                    \
-        if (e_ != hipSuccess)                                                                      \
-            return fail(SLAMGPU_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-    } while (0)
-
-constexpr int kRing = 64;       // big-packet staging slots
-constexpr int kPlainRowsTarget = 2048;  // plain-row contexts: genealogy rows in use before updates start consolidating the emptiest ones
-constexpr int kPlainConsBudget = 32;  // ... landmarks moved per update, at least
-constexpr int kMidRowsHigh = 24, kMidRowsLow = 12;  // compact contexts of mid-size maps: consolidate the emptiest rows from ... down to ... rows in use
-constexpr int kStageBound = 8;  // = kStage of kernels.hip: re-observed landmarks whose records an update launch stages in LDS
-constexpr int kConsolidateAbove = 6;  // compact contexts: genealogy rows alive before stale rows are consolidated (3..8 measure alike; profiles/consolidate_sweep_r03.txt)
-constexpr int kHistCap = 4096;  // asynchronous pose-estimate history entries
-
-struct EventPair {
-    hipEvent_t a, b;
-};
-
-struct KernelStat {
-    std::vector<EventPair> pending;
-    double ms = 0;
-    int64_t launches = 0;
-};
+int64_t n_global(const slamgpu_ctx *c) { return c->cfg.n_particles_global > 0 ? c->cfg.n_particles_global : c->cfg.n_particles; }
 
 }  // namespace
-
-struct slamgpu_ctx {
-    slamgpu_config cfg{};
-    const KernelTable *k = nullptr;
-    hipStream_t stream = nullptr;
-    Buffers B{};
-    WeightScratch ws{};
-    int nf = 0;
-    uint32_t obs_step = 0, ctl_step = 0;
-    uint32_t rng_skew = 0;  // update launches that were not filter steps (slamgpu_dist_settle): they draw nothing
-    // big-packet ring (observation packets that do not fit the kernel-argument form)
-    size_t pkt_bytes = 0;
-    char *pkt_host = nullptr;  // pinned [kRing][pkt_bytes]
-    char *pkt_dev = nullptr;
-    hipEvent_t pkt_ev[kRing]{};
-    bool pkt_ev_used[kRing]{};
-    uint64_t pkt_seq = 0;
-    // tape staging (TAPE mode)
-    float *tape_host = nullptr;  // pinned: normals [3][ncap] (or predict [2][ncap]) + strata [n_global]
-    float *normals_dev = nullptr;
-    float *strata_dev[2] = {nullptr, nullptr};  // by step parity: an update launch may still need the previous step's
-    // lazy predict queue
-    PredictArgs pending{};
-    // host mirror of ctrl for readback
-    Ctrl *ctrl_host = nullptr;  // pinned
-    // pose-estimate history
-    double *hist_dev = nullptr;  // [kHistCap][kHistStride]
-    double *hist_host = nullptr; // pinned mirror of it (history_to_host)
-    int hist_n = 0;
-    bool est_fresh = false;  // Ctrl.est / hist slot hist_n were written by the last update and nothing changed since
-    // profiling
-    bool profile = false;
-    std::map<std::string, KernelStat> stats;
-    std::vector<hipEvent_t> ev_pool;
-    hipEvent_t timer_a = nullptr, timer_b = nullptr;  // slamgpu_timer_start / _stop
-    double predict_bytes = 0;
-    bool own_stream = true;
-    ShardPlan *plan_dev = nullptr, *plan_host = nullptr;  // sharded resampling plan (device + pinned mirror)
-    uint32_t *plan_seq_host = nullptr;  // pinned: sequence number the plan kernel stores after the plan
-    uint32_t plan_seq = 0;
-    // Ctrl.live / Ctrl.pend slot the next launch reads (kernels.h: Ctrl); flipped after every launch that may
-    // change the live buffer (resample_kernel, gather_kernel, shard_commit_kernel)
-    int64_t pool_used = 0;        // arrival-pool slots handed out since the pool was last emptied (flatten / settle / upload)
-    bool shard_settled = false;   // the sharded resampling stage of this step moved everything physically (records arrived)
-    int slot = 0;
-    int keep_slot = 0;            // which WeightScratch::keep buffer holds the ancestors of the last update
-    bool maybe_pending = false;   // the last update may have left a lazy gather (only the device knows)
-    bool shard_est_fresh = false; // sharded: est_part holds this shard's partials of the last update (shard_finalize_kernel)
-    bool own_totals = true;       // ws.blk_w is this context's allocation (not a caller-provided collective buffer)
-    float *own_blk_w = nullptr;
-    // Pose-estimate pipeline of the single-context path.  The resampling stage of update t (Neff, decision, ancestors,
-    // estimate partials) normally runs INSIDE the launch of update t+1 (UpdateArgs::plan_inline) and its partials are
-    // reduced by the helper block of launch t+2; anything that needs results earlier runs them as launches of their own.
-    struct EstStage {
-        bool has = false;
-        int par = 0;              // step parity: which est_part / lcum / blk_w buffers
-        uint32_t step = 0;        // observation-step counter of that update (Philox stream of its strata)
-        int nf = 0;               // landmarks after that update
-        double *hist = nullptr;   // history slot its estimate belongs to (or null)
-    };
-    bool scan_ready = false;      // scan_kernel ran on the last update's block totals (large contexts)
-    bool mid_compact = false;     // compact layout on a map of more than 39 landmarks (kernels.h: kMidLandmarks): host-made packets only
-    bool ref_resample = false;    // the resampling stage replays the reference's order of operations (kernels.h: kRefResampleMax):
-                                  // strict build, the caller's draws (TAPE), a single context of at most 5 000 particles, linear weights
-    bool consolidate = true;      // row consolidation of compact contexts (do_update); SLAMGPU_NO_CONSOLIDATE=1 turns it off
-    int consolidate_above = kConsolidateAbove;  // (SLAMGPU_CONSOLIDATE_ABOVE: diagnostic)
-    int plain_rows_target = kPlainRowsTarget;   // (SLAMGPU_PLAIN_ROWS_TARGET: diagnostic / tests)
-    int scan_min_blocks = 1024;   // contexts with more blocks of 256 particles than this use scan_kernel (262 144 particles)
-    // Genealogy bookkeeping (kernels.h: gen).  The association is global, so the host knows which genealogy row every
-    // landmark uses: a step that writes landmarks opens a new row for them; a row whose last landmark moved on is recycled.
-    std::vector<uint32_t> seen_step; // [cap_nf] observation step that last re-observed each landmark (duplicate check)
-    std::vector<int32_t> live_flag;  // [cap_nf] which record buffer of every landmark row is live (flips when re-observed)
-    int32_t *live_dev = nullptr;     // device copy for flatten / shard pack + unpack
-    std::vector<int32_t> erow;       // [cap_nf] row of every landmark
-    std::vector<int32_t> refcnt;     // [cap_rows] landmarks using each row
-    std::vector<int32_t> free_rows;  // stack of unused rows
-    std::vector<int32_t> live_rows;  // rows with refcnt > 0
-    std::vector<int32_t> live_pos;   // [cap_rows] position in live_rows, -1 if not live
-    int32_t *erow_dev = nullptr, *rows_dev = nullptr;  // device copies for gather / flatten / shard pack + unpack
-    // distributed operation (slamgpu_dist_*)
-    bool dist = false, dist_clean = false;
-    PeerPtrs *peers_dev = nullptr;
-    float *gtot_dev[2] = {nullptr, nullptr};
-    std::vector<void *> ipc_opened;
-    void *comm = nullptr;  // ncclComm_t: when set, slamgpu_dist_step / _settle run the all-gather themselves
-    // push collective (slamgpu_dist_set_collective): the update launch stores its totals into every shard's table and a
-    // one-wave flag kernel is the barrier; flags_dev = [kMaxShards] flag words + the error word, fine-grained memory
-    bool count_remote = false;   // slamgpu_dist_remote_reads has been asked for: the update launches keep the counter from then on
-    bool dist_push = false;
-    bool dist_fold = false;  // push + the barrier folded into the head of the next update launch (SLAMGPU_DIST_FOLD)
-    uint32_t *flags_dev = nullptr;
-    uint32_t *peer_flags[kMaxShards] = {};
-    uint32_t flag_seq = 0;
-    // observation front end (slamgpu_set_map / slamgpu_observe)
-    float *map_dev = nullptr, *obs_r_dev = nullptr;
-    int32_t *table_dev = nullptr;
-    ObserveOut *obs_out_dev = nullptr;
-    int32_t map_n = 0, obs_nf = 0;
-    uint32_t observe_step = 0;
-    int fresh_row = -1;              // row the last update opened, while nothing but the resample the next update launch
-                                     // applies has touched it: records of its landmarks sit in the source slot itself
-    bool tables_dirty = true;
-    // device-resident genealogy bookkeeping (slamgpu_step_observe): while book_on_device the tables erow_dev / live_dev /
-    // refcnt_dev / book_dev are the truth and the host's vectors are stale; book_pull / book_push hand the ownership over
-    bool book_on_device = false;
-    int32_t front_status = 0;        // sticky kStatus* bits of the device front end seen by book_pull (carried back by book_push)
-    DevBook *book_dev = nullptr;
-    int32_t *refcnt_dev = nullptr, *take_dev = nullptr;
-    int32_t *book_host = nullptr;    // pinned staging of book_pull / book_push
-    hipStream_t obs_stream = nullptr;  // the front-end kernels run here, a step ahead of the update launches (events order them)
-    hipEvent_t obs_ev[kRing]{};        // observe_book of the packet in ring slot k has finished
-    char *last_pkt_dev = nullptr;    // packet of the last slamgpu_step_observe (slamgpu_observe_fetch)
-    // compact contexts: the front end runs inside the update launch (kernels.h: FrontArgs); its state lives in two device
-    // copies, read / written alternately (front_par: the one the next launch reads)
-    std::vector<float> map_host;     // [2][map_n], as slamgpu_set_map received it
-    FrontState *front_dev = nullptr, *front_host = nullptr;
-    ObsPacket *front_pkt_dev = nullptr;
-    int front_par = 0;
-    bool front_ready = false;
-    // gated association with the spatial prefilter (slamgpu_associate_ex): per-landmark boxes over all particles, refreshed
-    // for the landmarks written since (box_dirty), and the grid buffers
-    LmkBox *box_dev = nullptr;
-    std::vector<char> box_dirty;
-    // landmarks the caller has retired from the gated association (slamgpu_retire_landmarks): host flags + the device's bit mask
-    std::vector<char> retired;
-    uint32_t *retired_dev = nullptr;
-    int n_retired = 0;
-    int32_t *assoc_ids_dev = nullptr, *cell_start_dev = nullptr, *cell_fill_dev = nullptr;
-    // per-particle association (slamgpu_update_particle / _labels; kernels.h: PerParticle): device scratch, grown on demand
-    int32_t *pp_lab_dev = nullptr;   // labels BY OBSERVATION, [nz][ncap]
-    size_t pp_lab_cap = 0;
-    int16_t *pp_obs_dev = nullptr;   // PerParticle::obs [rows][ncap]
-    size_t pp_obs_rows = 0;
-    float *pp_z_dev = nullptr;       // [2 pp_nz_cap]
-    int32_t *pp_tab_dev = nullptr;   // [cap_nf] first / uidx | [cap_nf] holders | [pp_nz_cap] news / newk | [pp_nz_cap] idn
-    int pp_nz_cap = 0;
-    float *pp_wf_dev = nullptr;      // [ncap]
-    uint8_t *pp_any_dev = nullptr;   // [ncap]
-    std::vector<char> pp_partial;    // slots that NOT every particle opened: the only ones that can lose their last holder (a slot every particle
-                                     // opened is held by every descendant for good): what the holders census counts
-    std::vector<char> pp_dead;       // landmark slots no particle holds any more (their hypotheses died in a resample): out of the
-    std::vector<int32_t> pp_dead_list;  // association (retired) until a later landmark opens them again
-    float *vote_w_dev = nullptr;     // AssocGridArgs::vote_w, grown on demand
-    size_t vote_w_cap = 0;
-    float *assoc_z_dev = nullptr;    // the observations of an association call / its vote tables: kept between calls (an allocation and a release
-    VoteSlot *assoc_votes_dev = nullptr;  // per call each), grown on demand
-    int assoc_nz_cap = 0;
-    bool retired_stale = false;      // the host's retired flags have changed since the device's mask was written (retired_upload clears it)
-    uint64_t pp_steps = 0;
-    bool pp_census_done = false;     // the association kernel took the census of the labels itself (AssocGridArgs::census_first): pp_census_kernel is skipped
-    const PerParticle *pp_launch = nullptr;  // set around issue_update by do_update_particle: the launch takes update_kernel<.., PP = true>
-    float4 *items_dev = nullptr;  // [2 cap_items]: kernels.h: AssocGridArgs::items
-    AssocGeom *geom_dev = nullptr;
-    int32_t cap_items = 0;
-    char *peek_dev = nullptr;        // staging of slamgpu_peek, grown on demand
-    size_t peek_bytes = 0;
-    char *msum_dev = nullptr;        // staging and partials of slamgpu_map_summary, grown on demand
-    size_t msum_bytes = 0;
-    // path recording (slamgpu_path_*; kernels.h: PathRing).  path_cap = 0: off, nothing allocated, no kernel of it launched.  Records
-    // [path_first, path_next) are retained, record r in ring slot r % path_cap; origin[path_org] is the live origin array
-    int32_t path_cap = 0;
-    int64_t path_first = 0, path_next = 0;
-    float4 *path_rec_dev = nullptr;
-    int32_t *path_origin_dev[2] = {nullptr, nullptr};
-    int path_org = 0;
-    char *path_dev = nullptr;        // staging, push buffers and partials of slamgpu_path_trace / _summary, grown on demand
-    size_t path_bytes = 0;
-    // pose posterior (slamgpu_pose_*; kernels.h: PoseSummaryArgs).  pose_cap = 0: the per-step ring is off.  Entries [pose_first, pose_next)
-    // are retained, entry r in ring slot r % pose_cap.  Nothing is allocated and no kernel of it launched until the ring is enabled or
-    // slamgpu_pose_summary is called
-    int32_t pose_cap = 0;
-    int64_t pose_first = 0, pose_next = 0;
-    double *pose_ring_dev = nullptr; // [pose_cap][kPoseStride]
-    double *pose_dev = nullptr;      // [tiles][kPoseFields] partials | [kPoseStride] staging of slamgpu_pose_summary
-    // innovation posterior (slamgpu_innovation_*; kernels.h: InnovArgs).  innov_cap = 0: the ring is off.  Entries [innov_first, innov_next)
-    // are retained, entry e in ring slot e % innov_cap; innov_records counts the _record calls since the enable.  A packet travels
-    // through one of kInnovStage pinned staging slots (an event per slot says when the device has taken it: a record does not wait
-    // for the device unless it is kInnovStage packets ahead of it).  Nothing is allocated and no kernel of it launched until the ring
-    // is enabled or slamgpu_innovation_summary is called
-    int32_t innov_cap = 0;
-    int64_t innov_first = 0, innov_next = 0, innov_records = 0;
-    double *innov_ring_dev = nullptr;  // [innov_cap][kInnStride]
-    int32_t *innov_tag_dev = nullptr;  // [innov_cap][2]: record, slot
-    char *innov_host = nullptr;        // pinned [kInnovStage][innov_host_m] x (zf 8 B | idf 4 B)
-    size_t innov_host_m = 0;
-    uint64_t innov_seq = 0;
-    hipEvent_t innov_ev[4]{};
-    bool innov_ev_used[4]{};
-    bool pp_stage_ran = false;       // slamgpu_run_particle: a pose entry has already run the stage the last iteration left (pose_append)
-    unsigned long long *stamps_dev = nullptr;  // diagnostic (SLAMGPU_STAMPS=1 + libslamgpu_stamps.so): UpdateArgs::stamps
-    // persistent small-N step loop (slamgpu_run_observe, kernels.h: PersistArgs)
-    bool persist_ok = true;              // SLAMGPU_NO_PERSIST=1 turns it off (diagnostic / tests: the per-step loop)
-    bool special_ok = true;              // SLAMGPU_NO_SPECIAL=1 turns it off (diagnostic / tests: update_kernel's general instantiation for every launch)
-    int64_t special_launches = 0;        // update launches that took a specialised instantiation (slamgpu_update_special_launches: tests)
-    struct PersistCollect {              // while set, issue_update queues its launch instead of making it
-        std::vector<PersistStep> steps;
-        bool have_first = false;
-        Buffers B{};
-        UpdateArgs U{};
-        RngArgs rng{};
-        WeightScratch ws{};
-    } *collect = nullptr;
-    // the queue of a launch lives in PINNED HOST memory and the kernel reads it there (an entry an iteration ahead: the PCIe trip is
-    // hidden): kPqBufs buffers of pq_cap entries used in turn; a buffer is rewritten once the launch that read it has finished
-    static constexpr int kPqBufs = 4;
-    PersistStep *pq_host = nullptr;
-    size_t pq_cap = 0;
-    hipEvent_t pq_kev[kPqBufs] = {};
-    bool pq_kev_used[kPqBufs] = {};
-    int pq_next = 0;
-    uint32_t *psync_dev = nullptr, *pstatus_host = nullptr;
-    int32_t *ppk_dev = nullptr;          // [2][kSmallWords] observation packets of the loop's helper workgroup
-    PersistStep *pring_dev = nullptr;    // [4] the loop's ring of queue entries in device memory (kernels.h: PersistArgs::ring)
-    float4 *pdraw_dev = nullptr;         // [2][6][ncap] draws of the loop's drawer workgroups (FastSLAM 1, fast build)
-    int64_t persist_launches = 0, persist_steps = 0;
-    EstStage unplanned;           // the last update: resampling stage not run yet
-    EstStage unreduced;           // an update whose partials exist (est_part[par]) but are not reduced yet
-    // per-particle association driven by the device (slamgpu_run_particle; kernels.h: PpState / PpArgs).  While pp_on_device the
-    // per-particle state (pp_partial, pp_dead, the retired mask, pp_steps, obs_step, nf, the row tables) lives in device memory and the
-    // host's copies are stale; pp_pull (through book_pull / flush_stages) brings it back, pp_push hands it over
-    bool pp_on_device = false;
-    PpState *pp_st_dev = nullptr;
-    int32_t *pp_words_dev = nullptr;  // partial | dead | first | hold | uidx | list | dlist [cap_nf each] | news | newk | idn [pp_words_w each]
-    int pp_words_w = 0;
-    char *pp_pkt_dev = nullptr;       // the update's packet (fixed layout, cap = cap_nf)
-    int32_t *pp_report_dev = nullptr; // [kHistCap][8] reports of the iterations not fetched yet
-    // SLAMGPU_ASSOC_LISTS: cumulative counters (AssocListArgs::lstats; [4]: observations past the host's bound, reported by the next
-    // slamgpu_particle_report_fetch) and whether device-driven iterations have written slots without refreshing their boxes
-    unsigned long long *lstats_dev = nullptr;
-    bool box_dev_stale = false;
-    // the exclusion rule's radius capped by the step's observation spacing (slamgpu_set_particle_excl_spacing; 0: off) and the radii of
-    // the last step that made them: excl_rho_dev[0] holds their count (int32), the radii follow from [4] (excl_rho_cap of them)
-    float excl_spacing = 0.0f;
-    int32_t *excl_rho_dev = nullptr;
-    int excl_rho_cap = 0;
-    // data association sampling (slamgpu_set_particle_assoc_sampling): on / off, the ratios of the sampled pairs ([nz][ncap], as
-    // pp_lab_dev; held only while sampling is on) and the cumulative counters (SampleArgs::stats)
-    int32_t das_on = 0;
-    float *das_ratio_dev = nullptr;
-    size_t das_ratio_cap = 0;
-    unsigned long long *das_stats_dev = nullptr;
-    SampleArgs das_step{};  // the sampling arguments of the step being associated (AssocRule::smp points here: particle_rule)
-    // negative information (slamgpu_set_particle_miss; pm_range = 0: off): the factor and the view, the counts of the last step that
-    // made them ([ncap]; pm_have: some step has) and the cumulative counters (PpMissArgs::stats); nothing is allocated while it is off
-    float pm_p = 1.0f, pm_range = 0.0f, pm_front = 0.0f;
-    int32_t *pm_cnt_dev = nullptr;
-    unsigned long long *pm_stats_dev = nullptr;
-    bool pm_have = false;
-    // mutual exclusion for contested landmarks (slamgpu_set_particle_mutex): on / off, the table of who holds which slot
-    // ([cap_nf][ncap] int16, -1 between launches; held only while it is on) and the cumulative counters (PpMutexArgs::stats)
-    int32_t mx_on = 0;
-    int16_t *mx_hold_dev = nullptr;
-    unsigned long long *mx_stats_dev = nullptr;
-    size_t mx_hold_cap = 0;
-    bool pp_lists_done = false;      // the step's association went through the lists and left the slots' boxes (pp_missed's box test)
-    // the observations of the last per-particle step (slamgpu_particle_labels): the host-driven call's count, or -1: the device-driven
-    // iteration's (ObserveOut::nz)
-    int32_t pp_lab_nz = 0;
-    int pp_report_n = 0;
-    bool pp_stage_open = false;       // the previous iteration may have left a resampling stage (the device knows) and no gather has run since
-    double *pp_prev_hist = nullptr;   // ... its history slot and the parity of its weight scratch
-    int pp_prev_par = 0;
-    uint32_t pp_iter = 0;
-};
-
-namespace {
-
-int64_t n_global(const slamgpu_ctx *c) { return c->cfg.n_particles_global > 0 ? c->cfg.n_particles_global : c->cfg.n_particles; }
 
 hipEvent_t get_event(slamgpu_ctx *c) {
     if (!c->ev_pool.empty()) {
@@ -389,24 +79,7 @@ hipEvent_t get_event(slamgpu_ctx *c) {
     return e;
 }
 
-struct Timed {
-    slamgpu_ctx *c;
-    KernelStat *st = nullptr;
-    EventPair ep{};
-    Timed(slamgpu_ctx *ctx, const char *name) : c(ctx) {
-        if (!c->profile) return;
-        st = &c->stats[name];
-        ep.a = get_event(c);
-        ep.b = get_event(c);
-        if (ep.a) (void) hipEventRecord(ep.a, c->stream);
-    }
-    ~Timed() {
-        if (!st) return;
-        if (ep.b) (void) hipEventRecord(ep.b, c->stream);
-        st->pending.push_back(ep);
-        st->launches++;
-    }
-};
+namespace {
 
 void drain_stats(slamgpu_ctx *c) {
     for (auto &kv : c->stats) {
@@ -562,6 +235,8 @@ int front_setup(slamgpu_ctx *c) {
 
 int pp_pull(slamgpu_ctx *c);
 
+}  // namespace
+
 int book_pull(slamgpu_ctx *c) {
     if (c->pp_on_device) return pp_pull(c);
     if (!c->book_on_device) return 0;
@@ -618,6 +293,8 @@ int book_pull(slamgpu_ctx *c) {
     return 0;
 }
 
+namespace {
+
 int book_push(slamgpu_ctx *c) {
     if (c->book_on_device) return 0;
     HIP_TRY(hipSetDevice(c->cfg.device));
@@ -666,6 +343,8 @@ int book_push(slamgpu_ctx *c) {
     return 0;
 }
 
+}  // namespace
+
 // device copies of the row tables for the kernels that run outside the update launch
 int sync_tables(slamgpu_ctx *c) {
     if (int rc = book_pull(c)) return rc;
@@ -685,9 +364,10 @@ int sync_tables(slamgpu_ctx *c) {
     return 0;
 }
 
+namespace {
+
 // Make the particle set plain again (particle k in slot k of the live buffers) if the last update may have left a
 // lazy gather: everything except the next update launch needs that.
-int flush_stages(slamgpu_ctx *c);
 
 int materialize(slamgpu_ctx *c) {
     if (int rc = flush_stages(c)) return rc;  // the plan of the last update decides whether anything is pending
@@ -724,6 +404,8 @@ int flatten(slamgpu_ctx *c) {
     rows_reset(c, c->nf);  // ... which is what genealogy row 0 says now, for every landmark
     return 0;
 }
+
+}  // namespace
 
 // Run, as launches of their own, whatever part of the last updates' resampling / estimate stages is still outstanding
 // (normally the next update launches do it on the side): first the reduction of complete partials, then the plan of
@@ -794,255 +476,7 @@ int flush_predict(slamgpu_ctx *c) {
     return 0;
 }
 
-// ---- path recording (slamgpu_path_*; kernels.h: PathRing) ----
-PathRing path_ring(const slamgpu_ctx *c) { return PathRing{c->path_rec_dev, c->path_cap}; }
-
-// after an update launch: its resampling stage, then origin' = origin o ancestors.  The kernel reads Ctrl.resampled itself (no
-// synchronisation); the host flips the origin buffers whatever it decides.  Once per update that RAN: issue_update calls it
-int path_compose(slamgpu_ctx *c) {
-    if (int rc = flush_stages(c)) return rc;
-    c->B.slot = c->slot;
-    {
-        Timed t(c, "path_compose");
-        c->k->path_compose(c->stream, c->B, c->ws, c->keep_slot, c->path_origin_dev[c->path_org], c->path_origin_dev[c->path_org ^ 1]);
-    }
-    HIP_TRY(hipGetLastError());
-    c->path_org ^= 1;
-    return 0;
-}
-
-// the set as slamgpu_peek would show it, into the ring's next slot (a full ring drops its oldest record)
-int path_append(slamgpu_ctx *c) {
-    HIP_TRY(hipSetDevice(c->cfg.device));
-    if (int rc = flush_predict(c)) return rc;
-    if (int rc = flush_stages(c)) return rc;
-    c->B.slot = c->slot;
-    {
-        Timed t(c, "path_record");
-        c->k->path_record(c->stream, c->B, c->ws, path_ring(c), (int) (c->path_next % c->path_cap), c->path_origin_dev[c->path_org]);
-    }
-    HIP_TRY(hipGetLastError());
-    c->path_next++;
-    if (c->path_next - c->path_first > c->path_cap) c->path_first = c->path_next - c->path_cap;
-    return 0;
-}
-
-// ---- pose posterior (slamgpu_pose_*; kernels.h: PoseSummaryArgs) ----
-int pose_tiles(const slamgpu_ctx *c) { return (c->B.n + kPoseTile - 1) / kPoseTile; }
-
-int pose_reserve(slamgpu_ctx *c) {
-    if (c->pose_dev) return 0;
-    const size_t total = sizeof(double) * ((size_t) kPoseFields * (size_t) pose_tiles(c) + kPoseStride);
-    hipError_t e = hipMalloc((void **) &c->pose_dev, total);
-    if (e != hipSuccess) {
-        (void) hipGetLastError();
-        c->pose_dev = nullptr;
-        return fail(SLAMGPU_ERR_ALLOC, "hipMalloc(%zu): %s", total, hipGetErrorString(e));
-    }
-    return 0;
-}
-double *pose_staging(const slamgpu_ctx *c) { return c->pose_dev + (size_t) kPoseFields * (size_t) pose_tiles(c); }
-
-// the summary of the set as it stands (the caller has brought it there), into `out_dev`: two launches, nothing else
-int pose_launch(slamgpu_ctx *c, double *out_dev) {
-    PoseSummaryArgs A{};
-    A.tiles = pose_tiles(c);
-    A.logw = c->cfg.log_weights;
-    A.part = c->pose_dev;
-    A.out = out_dev;
-    c->B.slot = c->slot;
-    {
-        Timed t(c, "pose_summary");
-        c->k->pose_summary(c->stream, c->B, c->ws, A);
-    }
-    HIP_TRY(hipGetLastError());
-    {
-        Timed t(c, "pose_finish");
-        c->k->pose_finish(c->stream, c->B, c->ws, A);
-    }
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-
-int pp_dev_stage(slamgpu_ctx *c);
-int pp_dev_flush_predict(slamgpu_ctx *c);
-
-// the summary of the set as slamgpu_peek would show it, into the ring's next slot (a full ring drops its oldest entry).  Between
-// iterations of slamgpu_run_particle the state stays on the device: the stage the last iteration left (only the device knows
-// whether it updated) is run here with the iterations' own kernels, as the next iteration would have run it first thing
-int pose_append(slamgpu_ctx *c) {
-    HIP_TRY(hipSetDevice(c->cfg.device));
-    if (c->pp_on_device) {
-        if (!c->pp_stage_ran) c->pp_stage_open = true;
-        if (int rc = pp_dev_flush_predict(c)) return rc;
-        if (int rc = pp_dev_stage(c)) return rc;
-        c->pp_stage_ran = true;
-    } else {
-        if (int rc = flush_predict(c)) return rc;
-        if (int rc = flush_stages(c)) return rc;
-    }
-    if (int rc = pose_launch(c, c->pose_ring_dev + (size_t) kPoseStride * (size_t) (c->pose_next % c->pose_cap))) return rc;
-    c->pose_next++;
-    if (c->pose_next - c->pose_first > c->pose_cap) c->pose_first = c->pose_next - c->pose_cap;
-    return 0;
-}
-
-// ---- innovation posterior (slamgpu_innovation_*; kernels.h: InnovArgs) ----
-constexpr int kInnovStage = 4;
-
-// what slamgpu_innovation_summary and slamgpu_innovation_record refuse alike (outputs untouched); m > 0 on return 0
-int innov_check(slamgpu_ctx *c, const char *fn, const float *zf, const int32_t *idf, int32_t m, const float *R) {
-    if (m < 0) return fail(SLAMGPU_ERR_INVALID, "%s: m %d", fn, m);
-    if (m == 0) return 0;
-    if (!zf || !idf || !R) return fail(SLAMGPU_ERR_INVALID, "%s: null %s", fn, !zf ? "zf" : !idf ? "idf" : "R");
-    HIP_TRY(hipSetDevice(c->cfg.device));
-    if (int rc = book_pull(c)) return rc;  // (device-driven steps: the number of slots lives on the device)
-    for (int32_t q = 0; q < m; q++)
-        if (idf[q] < 0 || idf[q] >= c->nf)
-            return fail(SLAMGPU_ERR_INVALID, "%s: observation %d names slot %d outside [0, %d)", fn, q, idf[q], c->nf);
-    return 0;
-}
-
-// the m entries of the set as slamgpu_peek would show it: into the ring's slots (innov_next + q) % innov_cap with their tags (ring),
-// or into the staging area, from where out_dev / hold_dev point at them.  Enqueued; the caller has checked the packet (m > 0)
-int innov_launch(slamgpu_ctx *c, const float *zf, const int32_t *idf, int32_t m, const float *R, bool ring, const double **out_dev,
-                 const int32_t **hold_dev) {
-    static_assert(SLAMGPU_INNOV_STRIDE == kInnStride, "public / device summary layout");
-    static_assert(sizeof c->innov_ev / sizeof c->innov_ev[0] == kInnovStage, "staging slots");
-    // the particle set and the weights of slamgpu_map_summary, reached the same way
-    if (int rc = flush_predict(c)) return rc;
-    if (int rc = flush_stages(c)) return rc;
-    if (int rc = sync_tables(c)) return rc;
-    const int tiles = (c->B.n + kMapTile - 1) / kMapTile;
-    // the packet goes through the partials' table a chunk at a time, capped as the map summary's is
-    constexpr size_t kMapScratch = (size_t) 16 << 20;
-    const size_t per_obs = sizeof(double) * kInnFields * (size_t) tiles;
-    int fit = (int) std::max<size_t>(kMapSlots, kMapScratch / per_obs / kMapSlots * kMapSlots);
-    if (const char *e = getenv("SLAMGPU_INNOV_CHUNK"))  // (diagnostic: the chunking of a large packet on a small one)
-        fit = std::max(kMapSlots, atoi(e) / kMapSlots * kMapSlots);
-    const int chunk = (int) std::min<int64_t>(fit, ((int64_t) m + kMapSlots - 1) / kMapSlots * kMapSlots);
-    // device staging: [out m][wpart tiles][part chunk][zf m][idf m][holders m]
-    const size_t M = (size_t) m;
-    const size_t o_out = 0, o_w = o_out + sizeof(double) * kInnStride * M, o_part = o_w + sizeof(double) * 2 * (size_t) tiles,
-                 o_zf = o_part + per_obs * (size_t) chunk, o_idf = o_zf + sizeof(float) * 2 * M, o_hold = o_idf + sizeof(int32_t) * M,
-                 total = o_hold + sizeof(int32_t) * M;
-    if (total > c->msum_bytes) {
-        if (c->msum_dev) (void) hipFree(c->msum_dev);
-        c->msum_dev = nullptr;
-        c->msum_bytes = 0;
-        hipError_t e = hipMalloc((void **) &c->msum_dev, total);
-        if (e != hipSuccess) {
-            (void) hipGetLastError();
-            return fail(SLAMGPU_ERR_ALLOC, "hipMalloc(%zu): %s", total, hipGetErrorString(e));
-        }
-        c->msum_bytes = total;
-    }
-    // the packet: through a pinned slot of the context's own, so that the caller's arrays are free again when the call returns
-    if (M > c->innov_host_m) {
-        for (int k = 0; k < kInnovStage; k++)
-            if (c->innov_ev_used[k]) HIP_TRY(hipEventSynchronize(c->innov_ev[k]));
-        if (c->innov_host) (void) hipHostFree(c->innov_host);
-        c->innov_host = nullptr;
-        c->innov_host_m = 0;
-        const size_t want = std::max<size_t>(M, 64);
-        hipError_t e = hipHostMalloc((void **) &c->innov_host, 12 * want * kInnovStage, hipHostMallocDefault);
-        if (e != hipSuccess) {
-            (void) hipGetLastError();
-            c->innov_host = nullptr;
-            return fail(SLAMGPU_ERR_ALLOC, "hipHostMalloc(%zu): %s", 12 * want * kInnovStage, hipGetErrorString(e));
-        }
-        c->innov_host_m = want;
-    }
-    const int k = (int) (c->innov_seq++ % kInnovStage);
-    if (!c->innov_ev[k]) HIP_TRY(hipEventCreateWithFlags(&c->innov_ev[k], hipEventDisableTiming));
-    if (c->innov_ev_used[k]) HIP_TRY(hipEventSynchronize(c->innov_ev[k]));
-    char *h = c->innov_host + 12 * c->innov_host_m * (size_t) k;
-    memcpy(h, zf, sizeof(float) * 2 * M);
-    memcpy(h + sizeof(float) * 2 * M, idf, sizeof(int32_t) * M);
-    HIP_TRY(hipMemcpyAsync(c->msum_dev + o_zf, h, 12 * M, hipMemcpyHostToDevice, c->stream));  // (zf | idf: adjacent in both places)
-    HIP_TRY(hipEventRecord(c->innov_ev[k], c->stream));
-    c->innov_ev_used[k] = true;
-    c->B.slot = c->slot;
-    for (int at = 0; at < m; at += chunk) {
-        InnovArgs I{};
-        MapSummaryArgs &A = I.S;
-        A.first_slot = 0;
-        A.count = std::min(chunk, m - at);
-        A.tiles = tiles;
-        A.logw = c->cfg.log_weights;
-        A.part = reinterpret_cast<double *>(c->msum_dev + o_part);
-        A.wpart = reinterpret_cast<double *>(c->msum_dev + o_w);
-        I.zf = reinterpret_cast<const float *>(c->msum_dev + o_zf) + (size_t) 2 * at;
-        I.idf = reinterpret_cast<const int32_t *>(c->msum_dev + o_idf) + at;
-        I.r00 = R[0];
-        I.r10 = R[2];
-        I.r11 = R[3];
-        if (ring) {
-            A.out = c->innov_ring_dev;
-            A.holders = nullptr;
-            I.ring_cap = c->innov_cap;
-            I.ring_at = c->innov_next + at;
-            I.tag = c->innov_tag_dev;
-            I.record = (int32_t) c->innov_records;
-        } else {
-            A.out = reinterpret_cast<double *>(c->msum_dev + o_out) + (size_t) kInnStride * at;
-            A.holders = reinterpret_cast<int32_t *>(c->msum_dev + o_hold) + at;
-        }
-        {
-            Timed t(c, "innovation_summary");
-            c->k->innovation_summary(c->stream, c->B, c->ws, I);
-        }
-        HIP_TRY(hipGetLastError());
-        {
-            Timed t(c, "innovation_finish");
-            c->k->innovation_finish(c->stream, I);
-        }
-        HIP_TRY(hipGetLastError());
-    }
-    if (out_dev) *out_dev = reinterpret_cast<const double *>(c->msum_dev + o_out);
-    if (hold_dev) *hold_dev = reinterpret_cast<const int32_t *>(c->msum_dev + o_hold);
-    return 0;
-}
-
-// slamgpu_innovation_record past its context checks (slamgpu_step calls it with its own packet)
-int innov_append(slamgpu_ctx *c, const float *zf, const int32_t *idf, int32_t m, const float *R) {
-    if (int rc = innov_check(c, "slamgpu_innovation_record", zf, idf, m, R)) return rc;
-    if (m > c->innov_cap)
-        return fail(SLAMGPU_ERR_CAPACITY, "slamgpu_innovation_record: %d observations, the ring holds %d entries", m, c->innov_cap);
-    if (m > 0) {
-        if (int rc = innov_launch(c, zf, idf, m, R, true, nullptr, nullptr)) return rc;
-        c->innov_next += m;
-        if (c->innov_next - c->innov_first > c->innov_cap) c->innov_first = c->innov_next - c->innov_cap;
-    }
-    c->innov_records++;
-    return 0;
-}
-
-int path_identity(slamgpu_ctx *c) {
-    Timed t(c, "path_compose");
-    c->k->path_compose(c->stream, c->B, c->ws, 0, nullptr, c->path_origin_dev[c->path_org]);
-    return 0;
-}
-
-int path_reserve(slamgpu_ctx *c, size_t total) {
-    if (total <= c->path_bytes) return 0;
-    if (c->path_dev) (void) hipFree(c->path_dev);
-    c->path_dev = nullptr;
-    c->path_bytes = 0;
-    hipError_t e = hipMalloc((void **) &c->path_dev, total);
-    if (e != hipSuccess) return fail(SLAMGPU_ERR_ALLOC, "hipMalloc(%zu): %s", total, hipGetErrorString(e));
-    c->path_bytes = total;
-    return 0;
-}
-
-// the checks slamgpu_path_fetch / _trace / _summary share
-int path_check(slamgpu_ctx *c, const char *who, int64_t first, int64_t count) {
-    if (c->path_cap == 0) return fail(SLAMGPU_ERR_INVALID, "%s: recording is off (slamgpu_path_enable)", who);
-    if (count < 0 || first < c->path_first || first + count > c->path_next)
-        return fail(SLAMGPU_ERR_INVALID, "%s: records [%lld, %lld + %lld) outside the retained [%lld, %lld)", who, (long long) first, (long long) first,
-                    (long long) count, (long long) c->path_first, (long long) c->path_next);
-    return 0;
-}
+namespace {
 
 // the recorded history entries, behind everything enqueued, through the pinned mirror (a pageable destination cost the FIRST fetch of
 // a process 8.4 ms for 104 KB: 3.9 us per observation step of a whole example_webmap run of the drop-in binary, round 5)
@@ -1080,10 +514,14 @@ int persist_check(slamgpu_ctx *c) {
     return 0;
 }
 
+}  // namespace
+
 int check_ctx(slamgpu_ctx *c) {
     if (!c) return fail(SLAMGPU_ERR_INVALID, "null context");
     return 0;
 }
+
+namespace {
 
 // need_set: the caller is going to touch the particle buffers (not only the Ctrl words)
 int read_ctrl(slamgpu_ctx *c, bool need_set = false) {
@@ -1298,18 +736,7 @@ void slamgpu_destroy(slamgpu_ctx *c) {
     if (c->hist_host) (void) hipHostFree(c->hist_host);
     if (c->stamps_dev) (void) hipFree(c->stamps_dev);
     if (c->peek_dev) (void) hipFree(c->peek_dev);
-    if (c->msum_dev) (void) hipFree(c->msum_dev);
-    if (c->pose_ring_dev) (void) hipFree(c->pose_ring_dev);
-    if (c->pose_dev) (void) hipFree(c->pose_dev);
-    if (c->innov_ring_dev) (void) hipFree(c->innov_ring_dev);
-    if (c->innov_tag_dev) (void) hipFree(c->innov_tag_dev);
-    if (c->innov_host) (void) hipHostFree(c->innov_host);
-    for (hipEvent_t e : c->innov_ev)
-        if (e) (void) hipEventDestroy(e);
-    if (c->path_rec_dev) (void) hipFree(c->path_rec_dev);
-    for (int b = 0; b < 2; b++)
-        if (c->path_origin_dev[b]) (void) hipFree(c->path_origin_dev[b]);
-    if (c->path_dev) (void) hipFree(c->path_dev);
+    posterior_release(c);
     if (c->retired_dev) (void) hipFree(c->retired_dev);
     if (c->vote_w_dev) (void) hipFree(c->vote_w_dev);
     if (c->assoc_z_dev) (void) hipFree(c->assoc_z_dev);
@@ -1562,9 +989,9 @@ int issue_update(slamgpu_ctx *c, UpdateArgs &U, int n_new, int n_rows, bool need
     HIP_TRY(hipGetLastError());
     // path recording: this update's ancestors into origin[].  Only resample_kernel leaves them in keep[] (an inline plan finds them in
     // registers), so the stage runs now, as launches of its own, instead of inside the next update launch
-    if (c->path_cap > 0) return path_compose(c);
+    if (c->path.cap > 0) return path_compose(c);
     // the pose ring keeps the recorder's rule: the stage runs now, as launches of its own (every entry needs it settled anyway)
-    if (c->pose_cap > 0) return flush_stages(c);
+    if (c->pose.cap > 0) return flush_stages(c);
     return 0;
 }
 
@@ -1940,18 +1367,18 @@ int slamgpu_step(slamgpu_ctx *c, const float *controls, int32_t n_controls, cons
     if (n_controls < 0 || (n_controls > 0 && !controls)) return fail(SLAMGPU_ERR_INVALID, "bad control list");
     if (n_controls > 0 && c->cfg.add_predict_noise && c->cfg.rng_mode == SLAMGPU_RNG_TAPE)
         return fail(SLAMGPU_ERR_INVALID, "slamgpu_step cannot carry TAPE-mode predict noise: call slamgpu_predict per control");
-    if (c->innov_cap > 0 && m > c->innov_cap)  // (refused before anything is applied: the record between predicts and update could not be made)
-        return fail(SLAMGPU_ERR_CAPACITY, "slamgpu_step: %d observations, the innovation ring holds %d entries", m, c->innov_cap);
+    if (c->innov.cap > 0 && m > c->innov.cap)  // (refused before anything is applied: the record between predicts and update could not be made)
+        return fail(SLAMGPU_ERR_CAPACITY, "slamgpu_step: %d observations, the innovation ring holds %d entries", m, c->innov.cap);
     for (int k = 0; k < n_controls; k++)
         if (int rc = slamgpu_predict(c, controls[3 * k], controls[3 * k + 1], Q, dt, controls[3 * k + 2], nullptr)) return rc;
-    if (c->innov_cap > 0)  // the innovation ring: this step's packet against the predicted set, before the update takes it
+    if (c->innov.cap > 0)  // the innovation ring: this step's packet against the predicted set, before the update takes it
         if (int rc = innov_append(c, zf, idf, m, R)) return rc;
     if (int rc = slamgpu_update(c, zf, idf, m, zn, n, R, normals, strata)) return rc;
     if (record_estimate) {
         if (int rc = slamgpu_estimate_async(c)) return rc;
-        if (c->path_cap > 0)
+        if (c->path.cap > 0)
             if (int rc = path_append(c)) return rc;  // record r beside history entry r
-        if (c->pose_cap > 0) return pose_append(c);  // and pose entry r
+        if (c->pose.cap > 0) return pose_append(c);  // and pose entry r
     }
     return 0;
 }
@@ -1968,9 +1395,9 @@ int slamgpu_step_observe(slamgpu_ctx *c, const float *controls, int32_t n_contro
     if (int rc = do_update_dev(c, xtrue, max_range, R, noise, r1, r2, normals, strata)) return rc;
     if (record_estimate) {
         if (int rc = slamgpu_estimate_async(c)) return rc;
-        if (c->path_cap > 0)
+        if (c->path.cap > 0)
             if (int rc = path_append(c)) return rc;  // record r beside history entry r
-        if (c->pose_cap > 0) return pose_append(c);  // and pose entry r
+        if (c->pose.cap > 0) return pose_append(c);  // and pose entry r
     }
     return 0;
 }
@@ -2112,7 +1539,7 @@ int slamgpu_run_observe(slamgpu_ctx *c, int32_t K, const int32_t *n_controls, co
     // small compact contexts: ONE launch for all K iterations (kernels.h: PersistArgs)
     // (not while the path is recorded: the loop's resampling decisions and ancestors never leave its launch)
     // (nor while the pose ring is on: an entry per iteration needs the set between two iterations)
-    if (K >= 2 && persist_eligible(c) && max_nc <= kMaxFusedPredict && c->path_cap == 0 && c->pose_cap == 0)
+    if (K >= 2 && persist_eligible(c) && max_nc <= kMaxFusedPredict && c->path.cap == 0 && c->pose.cap == 0)
         return run_observe_persist(c, K, n_controls, controls, Q, dt, xtrue, max_range, R, noise);
     size_t row = 0;
     for (int32_t k = 0; k < K; k++) {
@@ -4349,8 +3776,10 @@ int pp_pull(slamgpu_ctx *c) {
     return 0;
 }
 
+}  // namespace
+
 // the resampling stage the previous iteration may have left (resample_kernel<true> decides), its estimate, and the lazy gather
-int pp_dev_stage(slamgpu_ctx *c) {
+extern "C++" int pp_dev_stage(slamgpu_ctx *c) {  // (slamgpu_ctx.h declares it outside this extern "C" block)
     if (!c->pp_stage_open) return 0;
     PpArgs P = pp_args(c);
     c->B.slot = c->slot;
@@ -4378,7 +3807,7 @@ int pp_dev_stage(slamgpu_ctx *c) {
     return 0;
 }
 
-int pp_dev_flush_predict(slamgpu_ctx *c) {
+extern "C++" int pp_dev_flush_predict(slamgpu_ctx *c) {
     if (c->pending.nsteps == 0) return 0;
     if (int rc = pp_dev_stage(c)) return rc;
     compose_predicts(c->pending);
@@ -4392,6 +3821,8 @@ int pp_dev_flush_predict(slamgpu_ctx *c) {
     c->est_fresh = false;
     return 0;
 }
+
+namespace {
 
 // one iteration of slamgpu_run_particle: nothing here waits for the device or copies memory
 // (bound >= 0: SLAMGPU_ASSOC_LISTS, with the host's bound on this iteration's observations; box_all: refresh every slot's box first)
@@ -4535,7 +3966,7 @@ int slamgpu_run_particle(slamgpu_ctx *c, int32_t K, const int32_t *n_controls, c
         return fail(SLAMGPU_ERR_INVALID, "slamgpu_run_particle: create the context with SLAMGPU_FLAG_PARTICLE_MAPS | SLAMGPU_FLAG_DEVICE_OBSERVE");
     if (noise != 0 && noise != 2) return fail(SLAMGPU_ERR_INVALID, "slamgpu_run_particle: noise must be 0 or 2");
     if (c->cfg.rng_mode == SLAMGPU_RNG_TAPE) return fail(SLAMGPU_ERR_INVALID, "slamgpu_run_particle: TAPE-mode contexts take their draws per step");
-    if (c->path_cap > 0)
+    if (c->path.cap > 0)
         return fail(SLAMGPU_ERR_INVALID, "slamgpu_run_particle: not while the path is recorded (its resampling decisions are known to the device only): "
                                          "slamgpu_path_enable(ctx, 0) first, or drive the steps with slamgpu_update_particle");
     if (K == 0) return 0;
@@ -4614,7 +4045,7 @@ int slamgpu_run_particle(slamgpu_ctx *c, int32_t K, const int32_t *n_controls, c
             std::string why = slamgpu_last_error();
             return fail(rc, "slamgpu_run_particle: iteration %d of %d: %s", (int) k, (int) K, why.c_str());
         }
-        if (c->pose_cap > 0)  // pose entry r beside history entry r
+        if (c->pose.cap > 0)  // pose entry r beside history entry r
             if (int rc = pose_append(c)) {
                 std::string why = slamgpu_last_error();
                 return fail(rc, "slamgpu_run_particle: iteration %d of %d: %s", (int) k, (int) K, why.c_str());
@@ -5070,590 +4501,6 @@ int slamgpu_download(slamgpu_ctx *c, float *xv, float *Pv9, float *w, float *xf,
     return slamgpu_download_range(c, 0, c->B.n, xv, Pv9, w, xf, Pf4);
 }
 
-int slamgpu_map_summary(slamgpu_ctx *c, int32_t first_slot, int32_t count, double *out, int32_t *holders) {
-    if (int rc = check_ctx(c)) return rc;
-    if (c->dist || c->cfg.n_particles_global != c->cfg.n_particles)
-        return fail(SLAMGPU_ERR_INVALID, "slamgpu_map_summary: single contexts only");
-    HIP_TRY(hipSetDevice(c->cfg.device));
-    if (int rc = book_pull(c)) return rc;  // (device-driven steps: the number of slots lives on the device)
-    if (first_slot < 0 || count < 0 || (int64_t) first_slot + (int64_t) count > (int64_t) c->nf)
-        return fail(SLAMGPU_ERR_INVALID, "slots [%d, %d + %d) outside [0, %d)", first_slot, first_slot, count, c->nf);
-    if (count == 0) return 0;
-    if (!out) return fail(SLAMGPU_ERR_INVALID, "null output");
-    static_assert(SLAMGPU_MAP_STRIDE == kMapStride, "public / device summary layout");
-    // the particle set slamgpu_peek shows, and nothing more than it does to get there
-    if (int rc = flush_predict(c)) return rc;
-    if (int rc = flush_stages(c)) return rc;
-    if (int rc = sync_tables(c)) return rc;
-    const int tiles = (c->B.n + kMapTile - 1) / kMapTile;
-    // the slots go through the partials' table a chunk at a time: at most kMapScratch bytes of it, whatever the map's size
-    constexpr size_t kMapScratch = (size_t) 16 << 20;
-    const size_t per_slot = sizeof(double) * kMapFields * (size_t) tiles;
-    int fit = (int) std::max<size_t>(kMapSlots, kMapScratch / per_slot / kMapSlots * kMapSlots);
-    if (const char *e = getenv("SLAMGPU_MAP_CHUNK"))  // (diagnostic: the chunking of a large map on a small one)
-        fit = std::max(kMapSlots, atoi(e) / kMapSlots * kMapSlots);
-    const int chunk = std::min(fit, (count + kMapSlots - 1) / kMapSlots * kMapSlots);
-    // device staging: [out count][wpart tiles][part chunk][holders count]
-    const size_t M = (size_t) count;
-    const size_t o_out = 0, o_w = o_out + sizeof(double) * kMapStride * M, o_part = o_w + sizeof(double) * 2 * (size_t) tiles,
-                 o_hold = o_part + per_slot * (size_t) chunk, total = o_hold + sizeof(int32_t) * M;
-    if (total > c->msum_bytes) {
-        if (c->msum_dev) (void) hipFree(c->msum_dev);
-        c->msum_dev = nullptr;
-        c->msum_bytes = 0;
-        hipError_t e = hipMalloc((void **) &c->msum_dev, total);
-        if (e != hipSuccess) return fail(SLAMGPU_ERR_ALLOC, "hipMalloc(%zu): %s", total, hipGetErrorString(e));
-        c->msum_bytes = total;
-    }
-    c->B.slot = c->slot;
-    for (int at = 0; at < count; at += chunk) {
-        MapSummaryArgs A{};
-        A.first_slot = first_slot + at;
-        A.count = std::min(chunk, count - at);
-        A.tiles = tiles;
-        A.logw = c->cfg.log_weights;
-        A.part = reinterpret_cast<double *>(c->msum_dev + o_part);
-        A.wpart = reinterpret_cast<double *>(c->msum_dev + o_w);
-        A.out = reinterpret_cast<double *>(c->msum_dev + o_out) + (size_t) kMapStride * at;
-        A.holders = reinterpret_cast<int32_t *>(c->msum_dev + o_hold) + at;
-        {
-            Timed t(c, "map_summary");
-            c->k->map_summary(c->stream, c->B, c->ws, A);
-        }
-        HIP_TRY(hipGetLastError());
-        {
-            Timed t(c, "map_finish");
-            c->k->map_finish(c->stream, A);
-        }
-        HIP_TRY(hipGetLastError());
-    }
-    HIP_TRY(hipMemcpyAsync(out, c->msum_dev + o_out, sizeof(double) * kMapStride * M, hipMemcpyDeviceToHost, c->stream));
-    if (holders) HIP_TRY(hipMemcpyAsync(holders, c->msum_dev + o_hold, sizeof(int32_t) * M, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return 0;
-}
-
-int slamgpu_map_pairs(slamgpu_ctx *c, const int32_t *pairs, int32_t count, double *out, int32_t *both) {
-    if (int rc = check_ctx(c)) return rc;
-    if (c->dist || c->cfg.n_particles_global != c->cfg.n_particles)
-        return fail(SLAMGPU_ERR_INVALID, "slamgpu_map_pairs: single contexts only");
-    if (count < 0) return fail(SLAMGPU_ERR_INVALID, "slamgpu_map_pairs: count %d", count);
-    if (count == 0) return 0;
-    if (!pairs || !out) return fail(SLAMGPU_ERR_INVALID, "slamgpu_map_pairs: null %s", pairs ? "output" : "pairs");
-    HIP_TRY(hipSetDevice(c->cfg.device));
-    if (int rc = book_pull(c)) return rc;  // (device-driven steps: the number of slots lives on the device)
-    for (int64_t k = 0; k < 2 * (int64_t) count; k++)
-        if (pairs[k] < 0 || pairs[k] >= c->nf)
-            return fail(SLAMGPU_ERR_INVALID, "slamgpu_map_pairs: pair %lld names slot %d outside [0, %d)", (long long) (k / 2), pairs[k], c->nf);
-    // the particle set and the weights of slamgpu_map_summary, reached the same way
-    if (int rc = flush_predict(c)) return rc;
-    if (int rc = flush_stages(c)) return rc;
-    if (int rc = sync_tables(c)) return rc;
-    const int tiles = (c->B.n + kMapTile - 1) / kMapTile;
-    // the pairs go through the summary's table of partials, cut the same way (a pair's sums do not depend on the cut)
-    constexpr size_t kMapScratch = (size_t) 16 << 20;
-    const size_t per_pair = sizeof(double) * kMapFields * (size_t) tiles;
-    int fit = (int) std::max<size_t>(kMapSlots, kMapScratch / per_pair / kMapSlots * kMapSlots);
-    if (const char *e = getenv("SLAMGPU_MAP_CHUNK")) fit = std::max(kMapSlots, atoi(e) / kMapSlots * kMapSlots);
-    const int chunk = (int) std::min<int64_t>(fit, ((int64_t) count + kMapSlots - 1) / kMapSlots * kMapSlots);
-    // device staging: [out count][wpart tiles][part chunk][both count][pairs count]
-    const size_t M = (size_t) count;
-    const size_t o_out = 0, o_w = o_out + sizeof(double) * kMapStride * M, o_part = o_w + sizeof(double) * 2 * (size_t) tiles,
-                 o_both = o_part + per_pair * (size_t) chunk, o_pairs = o_both + sizeof(int32_t) * M, total = o_pairs + sizeof(int32_t) * 2 * M;
-    if (total > c->msum_bytes) {
-        if (c->msum_dev) (void) hipFree(c->msum_dev);
-        c->msum_dev = nullptr;
-        c->msum_bytes = 0;
-        hipError_t e = hipMalloc((void **) &c->msum_dev, total);
-        if (e != hipSuccess) return fail(SLAMGPU_ERR_ALLOC, "hipMalloc(%zu): %s", total, hipGetErrorString(e));
-        c->msum_bytes = total;
-    }
-    HIP_TRY(hipMemcpyAsync(c->msum_dev + o_pairs, pairs, sizeof(int32_t) * 2 * M, hipMemcpyHostToDevice, c->stream));
-    c->B.slot = c->slot;
-    for (int at = 0; at < count; at += chunk) {
-        MapPairsArgs P{};
-        MapSummaryArgs &A = P.S;
-        A.first_slot = 0;
-        A.count = std::min(chunk, count - at);
-        A.tiles = tiles;
-        A.logw = c->cfg.log_weights;
-        A.part = reinterpret_cast<double *>(c->msum_dev + o_part);
-        A.wpart = reinterpret_cast<double *>(c->msum_dev + o_w);
-        A.out = reinterpret_cast<double *>(c->msum_dev + o_out) + (size_t) kMapStride * at;
-        A.holders = reinterpret_cast<int32_t *>(c->msum_dev + o_both) + at;
-        P.pairs = reinterpret_cast<const int32_t *>(c->msum_dev + o_pairs) + (size_t) 2 * at;
-        {
-            Timed t(c, "map_pairs");
-            c->k->map_pairs(c->stream, c->B, c->ws, P);
-        }
-        HIP_TRY(hipGetLastError());
-        {
-            Timed t(c, "map_finish");
-            c->k->map_finish(c->stream, A);
-        }
-        HIP_TRY(hipGetLastError());
-    }
-    HIP_TRY(hipMemcpyAsync(out, c->msum_dev + o_out, sizeof(double) * kMapStride * M, hipMemcpyDeviceToHost, c->stream));
-    if (both) HIP_TRY(hipMemcpyAsync(both, c->msum_dev + o_both, sizeof(int32_t) * M, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return 0;
-}
-
-int slamgpu_joint_summary(slamgpu_ctx *c, const int32_t *slots, int32_t k, double *out, int32_t *both) {
-    if (int rc = check_ctx(c)) return rc;
-    if (c->dist || c->cfg.n_particles_global != c->cfg.n_particles)
-        return fail(SLAMGPU_ERR_INVALID, "slamgpu_joint_summary: single contexts only");
-    static_assert(SLAMGPU_JOINT_MAX_SLOTS == kJointMaxSlots && 3 + 2 * kJointMaxSlots + 1 <= kJointCols, "public / device limits");
-    if (k < 0 || k > SLAMGPU_JOINT_MAX_SLOTS) return fail(SLAMGPU_ERR_INVALID, "slamgpu_joint_summary: k %d outside [0, %d]", k, SLAMGPU_JOINT_MAX_SLOTS);
-    if (!out || (k > 0 && !slots)) return fail(SLAMGPU_ERR_INVALID, "slamgpu_joint_summary: null %s", out ? "slots" : "output");
-    HIP_TRY(hipSetDevice(c->cfg.device));
-    if (int rc = book_pull(c)) return rc;  // (device-driven steps: the number of slots lives on the device)
-    for (int s = 0; s < k; s++)
-        if (slots[s] < 0 || slots[s] >= c->nf)
-            return fail(SLAMGPU_ERR_INVALID, "slamgpu_joint_summary: entry %d names slot %d outside [0, %d)", s, slots[s], c->nf);
-    // the particle set and the weights of slamgpu_map_summary, reached the same way
-    if (int rc = flush_predict(c)) return rc;
-    if (int rc = flush_stages(c)) return rc;
-    if (int rc = sync_tables(c)) return rc;
-    const int tiles = (c->B.n + kMapTile - 1) / kMapTile;
-    const int D = 3 + 2 * k, Dp = (D + 1 + 15) / 16 * 16, nb = Dp / 16, nbp = nb * (nb + 1) / 2;
-    const size_t size = (size_t) SLAMGPU_JOINT_SIZE(k), nq = 6 + 3 * (size_t) k;
-    // the block pairs go through the summaries' table of partials a chunk at a time (a block pair's sums do not depend on the cut)
-    constexpr size_t kMapScratch = (size_t) 16 << 20;
-    const size_t per_bp = sizeof(double) * 256 * (size_t) tiles;
-    int fit = (int) std::max<size_t>(1, kMapScratch / per_bp);
-    if (const char *e = getenv("SLAMGPU_JOINT_CHUNK")) fit = std::max(1, atoi(e));  // (diagnostic: the chunking of a wide list on a narrow one)
-    const int chunk = std::min(fit, nbp);
-    // device staging: [out][wpart tiles][pivot][sums nbp][pvf tiles][part chunk][tile_info tiles][info][slots k][hold n]
-    auto up = [](size_t v) { return (v + 15) / 16 * 16; };
-    const size_t o_out = 0, o_w = o_out + sizeof(double) * size, o_piv = o_w + sizeof(double) * 2 * (size_t) tiles,
-                 o_sums = o_piv + sizeof(double) * kJointCols, o_pvf = o_sums + sizeof(double) * 256 * (size_t) nbp,
-                 o_part = o_pvf + sizeof(double) * nq * (size_t) tiles, o_tile = o_part + per_bp * (size_t) chunk,
-                 o_info = o_tile + sizeof(int32_t) * 2 * (size_t) tiles, o_slots = o_info + sizeof(int32_t) * 4,
-                 o_hold = up(o_slots + sizeof(int32_t) * (size_t) k), total = o_hold + up((size_t) c->B.n);
-    if (total > c->msum_bytes) {
-        if (c->msum_dev) (void) hipFree(c->msum_dev);
-        c->msum_dev = nullptr;
-        c->msum_bytes = 0;
-        hipError_t e = hipMalloc((void **) &c->msum_dev, total);
-        if (e != hipSuccess) return fail(SLAMGPU_ERR_ALLOC, "hipMalloc(%zu): %s", total, hipGetErrorString(e));
-        c->msum_bytes = total;
-    }
-    if (k > 0) HIP_TRY(hipMemcpyAsync(c->msum_dev + o_slots, slots, sizeof(int32_t) * (size_t) k, hipMemcpyHostToDevice, c->stream));
-    c->B.slot = c->slot;
-    JointArgs J{};
-    J.S.tiles = tiles;
-    J.S.logw = c->cfg.log_weights;
-    J.S.part = reinterpret_cast<double *>(c->msum_dev + o_part);
-    J.S.wpart = reinterpret_cast<double *>(c->msum_dev + o_w);
-    J.S.out = reinterpret_cast<double *>(c->msum_dev + o_out);
-    J.S.holders = reinterpret_cast<int32_t *>(c->msum_dev + o_info) + 2;
-    J.k = k;
-    J.D = D;
-    J.Dp = Dp;
-    if (const char *e = getenv("SLAMGPU_JOINT_PLAIN_FMA")) J.plain = atoi(e) != 0;  // (diagnostic: tools/joint_probe.py's comparison of the two forms)
-    J.slots = reinterpret_cast<const int32_t *>(c->msum_dev + o_slots);
-    J.hold = reinterpret_cast<uint8_t *>(c->msum_dev + o_hold);
-    J.tile_info = reinterpret_cast<int32_t *>(c->msum_dev + o_tile);
-    J.info = reinterpret_cast<int32_t *>(c->msum_dev + o_info);
-    J.pivot = reinterpret_cast<double *>(c->msum_dev + o_piv);
-    J.sums = reinterpret_cast<double *>(c->msum_dev + o_sums);
-    J.pvf = reinterpret_cast<double *>(c->msum_dev + o_pvf);
-    {
-        Timed t(c, "joint_hold");
-        c->k->joint_hold(c->stream, c->B, c->ws, J);
-    }
-    HIP_TRY(hipGetLastError());
-    {
-        Timed t(c, "joint_pivot");
-        c->k->joint_pivot(c->stream, c->B, c->ws, J);
-    }
-    HIP_TRY(hipGetLastError());
-    for (int at = 0; at < nbp; at += chunk) {
-        J.bp_first = at;
-        J.bp_count = std::min(chunk, nbp - at);
-        {
-            Timed t(c, "joint_gram");
-            c->k->joint_gram(c->stream, c->B, c->ws, J);
-        }
-        HIP_TRY(hipGetLastError());
-        {
-            Timed t(c, "joint_reduce");
-            c->k->joint_reduce(c->stream, J);
-        }
-        HIP_TRY(hipGetLastError());
-    }
-    {
-        Timed t(c, "joint_finish");
-        c->k->joint_finish(c->stream, c->B, c->ws, J);
-    }
-    HIP_TRY(hipGetLastError());
-    std::vector<double> h(size);  // (outputs untouched if a copy fails)
-    int32_t hb = 0;
-    HIP_TRY(hipMemcpyAsync(h.data(), c->msum_dev + o_out, sizeof(double) * size, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpyAsync(&hb, J.S.holders, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    memcpy(out, h.data(), sizeof(double) * size);
-    if (both) *both = hb;
-    return 0;
-}
-
-int slamgpu_pose_summary(slamgpu_ctx *c, double *out) {
-    if (int rc = check_ctx(c)) return rc;
-    if (c->dist || c->cfg.n_particles_global != c->cfg.n_particles) return fail(SLAMGPU_ERR_INVALID, "slamgpu_pose_summary: single contexts only");
-    if (!out) return fail(SLAMGPU_ERR_INVALID, "slamgpu_pose_summary: null output");
-    static_assert(SLAMGPU_POSE_STRIDE == kPoseStride, "public / device summary layout");
-    HIP_TRY(hipSetDevice(c->cfg.device));
-    // the particle set slamgpu_peek shows, and nothing more than it does to get there
-    if (int rc = flush_predict(c)) return rc;
-    if (int rc = flush_stages(c)) return rc;
-    if (int rc = pose_reserve(c)) return rc;
-    if (int rc = pose_launch(c, pose_staging(c))) return rc;
-    double h[kPoseStride];
-    HIP_TRY(hipMemcpyAsync(h, pose_staging(c), sizeof h, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    memcpy(out, h, sizeof h);
-    return 0;
-}
-
-int slamgpu_pose_history_enable(slamgpu_ctx *c, int32_t capacity) {
-    if (int rc = check_ctx(c)) return rc;
-    if (c->dist || c->cfg.n_particles_global != c->cfg.n_particles) return fail(SLAMGPU_ERR_INVALID, "slamgpu_pose_history_enable: single contexts only");
-    if (capacity < 0) return fail(SLAMGPU_ERR_INVALID, "slamgpu_pose_history_enable: capacity %d", capacity);
-    HIP_TRY(hipSetDevice(c->cfg.device));
-    // the new ring first: a refused call leaves the setting as it was
-    double *ring = nullptr;
-    if (capacity > 0) {
-        if (int rc = pose_reserve(c)) return rc;
-        const size_t bytes = sizeof(double) * kPoseStride * (size_t) capacity;
-        hipError_t e = hipMalloc((void **) &ring, bytes);
-        if (e != hipSuccess) {
-            (void) hipGetLastError();
-            return fail(SLAMGPU_ERR_ALLOC, "slamgpu_pose_history_enable: %d entries (%zu bytes): %s", capacity, bytes, hipGetErrorString(e));
-        }
-    }
-    if (c->pose_ring_dev) {
-        HIP_TRY(hipStreamSynchronize(c->stream));  // (launches in flight may still write the old ring)
-        (void) hipFree(c->pose_ring_dev);
-    }
-    c->pose_ring_dev = ring;
-    c->pose_cap = capacity;
-    c->pose_first = c->pose_next = 0;
-    return 0;
-}
-
-int slamgpu_pose_history_record(slamgpu_ctx *c) {
-    if (int rc = check_ctx(c)) return rc;
-    if (c->pose_cap == 0) return fail(SLAMGPU_ERR_INVALID, "slamgpu_pose_history_record: the ring is off (slamgpu_pose_history_enable)");
-    return pose_append(c);
-}
-
-int slamgpu_pose_history_info(slamgpu_ctx *c, int64_t *first, int64_t *next, int32_t *capacity) {
-    if (int rc = check_ctx(c)) return rc;
-    if (first) *first = c->pose_first;
-    if (next) *next = c->pose_next;
-    if (capacity) *capacity = c->pose_cap;
-    return 0;
-}
-
-int slamgpu_pose_history_fetch(slamgpu_ctx *c, int64_t first, int32_t count, double *out) {
-    if (int rc = check_ctx(c)) return rc;
-    if (count < 0 || first < c->pose_first || first + count > c->pose_next)
-        return fail(SLAMGPU_ERR_INVALID, "slamgpu_pose_history_fetch: entries [%lld, %lld + %lld) outside the retained [%lld, %lld)", (long long) first,
-                    (long long) first, (long long) count, (long long) c->pose_first, (long long) c->pose_next);
-    if (count == 0) return 0;
-    if (!out) return fail(SLAMGPU_ERR_INVALID, "slamgpu_pose_history_fetch: null output");
-    HIP_TRY(hipSetDevice(c->cfg.device));
-    std::vector<double> h((size_t) kPoseStride * (size_t) count);
-    // at most two stretches of the ring
-    const int64_t at = first % c->pose_cap, n0 = std::min<int64_t>(count, c->pose_cap - at);
-    HIP_TRY(hipMemcpyAsync(h.data(), c->pose_ring_dev + (size_t) kPoseStride * (size_t) at, sizeof(double) * kPoseStride * (size_t) n0, hipMemcpyDeviceToHost,
-                           c->stream));
-    if (n0 < count)
-        HIP_TRY(hipMemcpyAsync(h.data() + (size_t) kPoseStride * (size_t) n0, c->pose_ring_dev, sizeof(double) * kPoseStride * (size_t) (count - n0),
-                               hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    memcpy(out, h.data(), sizeof(double) * h.size());
-    return 0;
-}
-
-int slamgpu_innovation_summary(slamgpu_ctx *c, const float *zf, const int32_t *idf, int32_t m, const float R[4], double *out, int32_t *holders) {
-    if (int rc = check_ctx(c)) return rc;
-    if (c->dist || c->cfg.n_particles_global != c->cfg.n_particles)
-        return fail(SLAMGPU_ERR_INVALID, "slamgpu_innovation_summary: single contexts only");
-    if (int rc = innov_check(c, "slamgpu_innovation_summary", zf, idf, m, R)) return rc;
-    if (m == 0) return 0;
-    if (!out) return fail(SLAMGPU_ERR_INVALID, "slamgpu_innovation_summary: null output");
-    const double *out_dev = nullptr;
-    const int32_t *hold_dev = nullptr;
-    if (int rc = innov_launch(c, zf, idf, m, R, false, &out_dev, &hold_dev)) return rc;
-    HIP_TRY(hipMemcpyAsync(out, out_dev, sizeof(double) * kInnStride * (size_t) m, hipMemcpyDeviceToHost, c->stream));
-    if (holders) HIP_TRY(hipMemcpyAsync(holders, hold_dev, sizeof(int32_t) * (size_t) m, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return 0;
-}
-
-int slamgpu_innovation_history_enable(slamgpu_ctx *c, int32_t capacity) {
-    if (int rc = check_ctx(c)) return rc;
-    if (c->dist || c->cfg.n_particles_global != c->cfg.n_particles)
-        return fail(SLAMGPU_ERR_INVALID, "slamgpu_innovation_history_enable: single contexts only");
-    if (capacity < 0) return fail(SLAMGPU_ERR_INVALID, "slamgpu_innovation_history_enable: capacity %d", capacity);
-    HIP_TRY(hipSetDevice(c->cfg.device));
-    // the new ring first: a refused call leaves the setting as it was
-    double *ring = nullptr;
-    int32_t *tag = nullptr;
-    if (capacity > 0) {
-        const size_t bytes = sizeof(double) * kInnStride * (size_t) capacity;
-        hipError_t e = hipMalloc((void **) &ring, bytes);
-        if (e == hipSuccess) {
-            e = hipMalloc((void **) &tag, sizeof(int32_t) * 2 * (size_t) capacity);
-            if (e != hipSuccess) (void) hipFree(ring);
-        }
-        if (e != hipSuccess) {
-            (void) hipGetLastError();
-            return fail(SLAMGPU_ERR_ALLOC, "slamgpu_innovation_history_enable: %d entries (%zu bytes): %s", capacity, bytes, hipGetErrorString(e));
-        }
-    }
-    if (c->innov_ring_dev) {
-        HIP_TRY(hipStreamSynchronize(c->stream));  // (launches in flight may still write the old ring)
-        (void) hipFree(c->innov_ring_dev);
-        (void) hipFree(c->innov_tag_dev);
-    }
-    c->innov_ring_dev = ring;
-    c->innov_tag_dev = tag;
-    c->innov_cap = capacity;
-    c->innov_first = c->innov_next = c->innov_records = 0;
-    return 0;
-}
-
-int slamgpu_innovation_record(slamgpu_ctx *c, const float *zf, const int32_t *idf, int32_t m, const float R[4]) {
-    if (int rc = check_ctx(c)) return rc;
-    if (c->dist || c->cfg.n_particles_global != c->cfg.n_particles)
-        return fail(SLAMGPU_ERR_INVALID, "slamgpu_innovation_record: single contexts only");
-    if (c->innov_cap == 0) return fail(SLAMGPU_ERR_INVALID, "slamgpu_innovation_record: the ring is off (slamgpu_innovation_history_enable)");
-    return innov_append(c, zf, idf, m, R);
-}
-
-int slamgpu_innovation_history_info(slamgpu_ctx *c, int64_t *first, int64_t *next, int32_t *capacity, int64_t *records) {
-    if (int rc = check_ctx(c)) return rc;
-    if (first) *first = c->innov_first;
-    if (next) *next = c->innov_next;
-    if (capacity) *capacity = c->innov_cap;
-    if (records) *records = c->innov_records;
-    return 0;
-}
-
-int slamgpu_innovation_history_fetch(slamgpu_ctx *c, int64_t first, int32_t count, double *out, int32_t *record, int32_t *slot) {
-    if (int rc = check_ctx(c)) return rc;
-    if (count < 0 || first < c->innov_first || first + count > c->innov_next)
-        return fail(SLAMGPU_ERR_INVALID, "slamgpu_innovation_history_fetch: entries [%lld, %lld + %lld) outside the retained [%lld, %lld)",
-                    (long long) first, (long long) first, (long long) count, (long long) c->innov_first, (long long) c->innov_next);
-    if (count == 0) return 0;
-    HIP_TRY(hipSetDevice(c->cfg.device));
-    std::vector<double> h((size_t) kInnStride * (size_t) count);
-    std::vector<int32_t> tg((size_t) 2 * (size_t) count);
-    // at most two stretches of the ring
-    const int64_t at = first % c->innov_cap, n0 = std::min<int64_t>(count, c->innov_cap - at);
-    HIP_TRY(hipMemcpyAsync(h.data(), c->innov_ring_dev + (size_t) kInnStride * (size_t) at, sizeof(double) * kInnStride * (size_t) n0,
-                           hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpyAsync(tg.data(), c->innov_tag_dev + (size_t) 2 * (size_t) at, sizeof(int32_t) * 2 * (size_t) n0, hipMemcpyDeviceToHost, c->stream));
-    if (n0 < count) {
-        HIP_TRY(hipMemcpyAsync(h.data() + (size_t) kInnStride * (size_t) n0, c->innov_ring_dev, sizeof(double) * kInnStride * (size_t) (count - n0),
-                               hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipMemcpyAsync(tg.data() + (size_t) 2 * (size_t) n0, c->innov_tag_dev, sizeof(int32_t) * 2 * (size_t) (count - n0), hipMemcpyDeviceToHost,
-                               c->stream));
-    }
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    if (out) memcpy(out, h.data(), sizeof(double) * h.size());
-    for (int32_t q = 0; q < count; q++) {
-        if (record) record[q] = tg[2 * (size_t) q];
-        if (slot) slot[q] = tg[2 * (size_t) q + 1];
-    }
-    return 0;
-}
-
-int slamgpu_path_enable(slamgpu_ctx *c, int32_t capacity) {
-    if (int rc = check_ctx(c)) return rc;
-    if (c->dist || c->cfg.n_particles_global != c->cfg.n_particles) return fail(SLAMGPU_ERR_INVALID, "slamgpu_path_enable: single contexts only");
-    if (capacity < 0) return fail(SLAMGPU_ERR_INVALID, "slamgpu_path_enable: capacity %d", capacity);
-    HIP_TRY(hipSetDevice(c->cfg.device));
-    // the new ring first: a refused call leaves the recording as it was
-    float4 *rec = nullptr;
-    int32_t *org[2] = {nullptr, nullptr};
-    if (capacity > 0) {
-        const size_t S = (size_t) c->B.ncap, bytes = sizeof(float4) * S * (size_t) capacity;
-        hipError_t e = hipMalloc((void **) &rec, bytes);
-        for (int b = 0; b < 2 && e == hipSuccess; b++) e = hipMalloc((void **) &org[b], sizeof(int32_t) * S);
-        if (e != hipSuccess) {
-            (void) hipGetLastError();
-            if (rec) (void) hipFree(rec);
-            for (int b = 0; b < 2; b++)
-                if (org[b]) (void) hipFree(org[b]);
-            return fail(SLAMGPU_ERR_ALLOC, "slamgpu_path_enable: %d records of %d particles (%zu bytes): %s", capacity, c->B.n, bytes, hipGetErrorString(e));
-        }
-    }
-    if (c->path_cap > 0 || c->path_dev) {
-        HIP_TRY(hipStreamSynchronize(c->stream));  // (launches in flight may still use the old ring)
-        if (c->path_rec_dev) (void) hipFree(c->path_rec_dev);
-        for (int b = 0; b < 2; b++)
-            if (c->path_origin_dev[b]) (void) hipFree(c->path_origin_dev[b]);
-        if (c->path_dev) (void) hipFree(c->path_dev);
-        c->path_dev = nullptr;
-        c->path_bytes = 0;
-    }
-    c->path_rec_dev = rec;
-    c->path_origin_dev[0] = org[0];
-    c->path_origin_dev[1] = org[1];
-    c->path_org = 0;
-    c->path_cap = capacity;
-    c->path_first = c->path_next = 0;
-    if (capacity > 0) {
-        if (int rc = path_identity(c)) return rc;
-        HIP_TRY(hipGetLastError());
-    }
-    return 0;
-}
-
-int slamgpu_path_record(slamgpu_ctx *c) {
-    if (int rc = check_ctx(c)) return rc;
-    if (c->path_cap == 0) return fail(SLAMGPU_ERR_INVALID, "slamgpu_path_record: recording is off (slamgpu_path_enable)");
-    return path_append(c);
-}
-
-int slamgpu_path_info(slamgpu_ctx *c, int64_t *first, int64_t *next, int32_t *capacity) {
-    if (int rc = check_ctx(c)) return rc;
-    if (first) *first = c->path_first;
-    if (next) *next = c->path_next;
-    if (capacity) *capacity = c->path_cap;
-    return 0;
-}
-
-int slamgpu_path_fetch(slamgpu_ctx *c, int64_t r, float *xyt, int32_t *parent) {
-    if (int rc = check_ctx(c)) return rc;
-    if (int rc = path_check(c, "slamgpu_path_fetch", r, 1)) return rc;
-    HIP_TRY(hipSetDevice(c->cfg.device));
-    const size_t N = (size_t) c->B.n;
-    std::vector<float4> rec(N);
-    HIP_TRY(hipMemcpyAsync(rec.data(), c->path_rec_dev + (size_t) (r % c->path_cap) * (size_t) c->B.ncap, sizeof(float4) * N, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    for (size_t k = 0; k < N; k++) {
-        if (xyt) {
-            xyt[3 * k] = rec[k].x;
-            xyt[3 * k + 1] = rec[k].y;
-            xyt[3 * k + 2] = rec[k].z;
-        }
-        if (parent) memcpy(parent + k, &rec[k].w, sizeof(int32_t));
-    }
-    return 0;
-}
-
-int slamgpu_path_trace(slamgpu_ctx *c, int32_t particle, int64_t first, int32_t count, float *xyt, int32_t *index) {
-    if (int rc = check_ctx(c)) return rc;
-    if (int rc = path_check(c, "slamgpu_path_trace", first, count)) return rc;
-    if (particle < -1 || particle >= c->B.n) return fail(SLAMGPU_ERR_INVALID, "slamgpu_path_trace: particle %d outside [-1, %d)", particle, c->B.n);
-    if (count == 0) return 0;
-    HIP_TRY(hipSetDevice(c->cfg.device));
-    // the present set is what slamgpu_peek shows, and nothing more than it does to get there
-    if (int rc = flush_predict(c)) return rc;
-    if (int rc = flush_stages(c)) return rc;
-    const size_t M = (size_t) count, o_idx = (sizeof(float) * 3 * M + 15) & ~(size_t) 15;
-    if (int rc = path_reserve(c, o_idx + sizeof(int32_t) * M)) return rc;
-    PathTraceArgs A{};
-    A.particle = particle;
-    A.newest = c->path_next - 1;
-    A.first = first;
-    A.count = count;
-    A.origin = c->path_origin_dev[c->path_org];
-    A.xyt = reinterpret_cast<float *>(c->path_dev);
-    A.index = reinterpret_cast<int32_t *>(c->path_dev + o_idx);
-    c->B.slot = c->slot;
-    {
-        Timed t(c, "path_trace");
-        c->k->path_trace(c->stream, c->B, c->ws, path_ring(c), A);
-    }
-    HIP_TRY(hipGetLastError());
-    if (xyt) HIP_TRY(hipMemcpyAsync(xyt, A.xyt, sizeof(float) * 3 * M, hipMemcpyDeviceToHost, c->stream));
-    if (index) HIP_TRY(hipMemcpyAsync(index, A.index, sizeof(int32_t) * M, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return 0;
-}
-
-int slamgpu_path_summary(slamgpu_ctx *c, int64_t first, int32_t count, double *out, int32_t *distinct) {
-    if (int rc = check_ctx(c)) return rc;
-    if (int rc = path_check(c, "slamgpu_path_summary", first, count)) return rc;
-    if (count == 0) return 0;
-    if (!out) return fail(SLAMGPU_ERR_INVALID, "null output");
-    static_assert(SLAMGPU_PATH_STRIDE == kPathStride, "public / device summary layout");
-    HIP_TRY(hipSetDevice(c->cfg.device));
-    if (int rc = flush_predict(c)) return rc;
-    if (int rc = flush_stages(c)) return rc;
-    const int tiles = (c->B.n + kBlock - 1) / kBlock;
-    const size_t S = (size_t) c->B.ncap, M = (size_t) count;
-    // the records go through the partials' table a chunk at a time: at most kPathScratch bytes of it, however many are asked for
-    constexpr size_t kPathScratch = (size_t) 16 << 20;
-    const size_t per_rec = sizeof(double) * kPathFields * (size_t) tiles;
-    int fit = (int) std::max<size_t>(1, kPathScratch / per_rec);
-    if (const char *e = getenv("SLAMGPU_PATH_CHUNK")) fit = std::max(1, atoi(e));  // (diagnostic: the chunking of a long window on a short one)
-    const int chunk = std::min(fit, count);
-    // device staging: [out count][wpart tiles][wtot][W 2 S][part chunk][C 2 S][distinct count]
-    const size_t o_out = 0, o_w = o_out + sizeof(double) * kPathStride * M, o_tot = o_w + sizeof(double) * 2 * (size_t) tiles, o_W = o_tot + sizeof(double) * 2,
-                 o_part = o_W + sizeof(unsigned long long) * 2 * S, o_C = o_part + per_rec * (size_t) chunk, o_d = o_C + sizeof(uint32_t) * 2 * S,
-                 total = o_d + sizeof(int32_t) * M;
-    if (int rc = path_reserve(c, total)) return rc;
-    PathWalkArgs A{};
-    A.tiles = tiles;
-    A.logw = c->cfg.log_weights;
-    A.wpart = reinterpret_cast<double *>(c->path_dev + o_w);
-    A.wtot = reinterpret_cast<double *>(c->path_dev + o_tot);
-    A.origin = c->path_origin_dev[c->path_org];
-    A.W[0] = reinterpret_cast<unsigned long long *>(c->path_dev + o_W);
-    A.W[1] = A.W[0] + S;
-    A.C[0] = reinterpret_cast<uint32_t *>(c->path_dev + o_C);
-    A.C[1] = A.C[0] + S;
-    A.part = reinterpret_cast<double *>(c->path_dev + o_part);
-    A.chunk = chunk;
-    c->B.slot = c->slot;
-    HIP_TRY(hipMemsetAsync(A.W[0], 0, sizeof(unsigned long long) * 2 * S, c->stream));
-    HIP_TRY(hipMemsetAsync(A.C[0], 0, sizeof(uint32_t) * 2 * S, c->stream));
-    for (int stage = 0; stage < 3; stage++) {
-        Timed t(c, "path_seed");
-        c->k->path_seed(c->stream, c->B, c->ws, A, stage);
-    }
-    HIP_TRY(hipGetLastError());
-    // newest record first; a chunk is finished when its oldest record has been walked
-    const PathRing R = path_ring(c);
-    int64_t lo = first + count;  // the chunk in progress is [lo, hi)
-    int64_t hi = lo;
-    int cur = 0;
-    for (int64_t r = c->path_next - 1; r >= first; r--) {
-        if (r < lo) {
-            hi = lo;
-            lo = std::max<int64_t>(first, hi - chunk);
-        }
-        A.r = r;
-        A.cur = cur;
-        A.push = r > first ? 1 : 0;
-        A.at = r < first + count ? (int32_t) (r - lo) : -1;
-        {
-            Timed t(c, "path_push");
-            c->k->path_push(c->stream, c->B, R, A);
-        }
-        cur ^= 1;
-        if (r == lo && A.at >= 0) {
-            A.count = (int32_t) (hi - lo);
-            A.out = reinterpret_cast<double *>(c->path_dev + o_out) + (size_t) kPathStride * (size_t) (lo - first);
-            A.distinct = reinterpret_cast<int32_t *>(c->path_dev + o_d) + (size_t) (lo - first);
-            Timed t(c, "path_finish");
-            c->k->path_finish(c->stream, A);
-        }
-    }
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(out, c->path_dev + o_out, sizeof(double) * kPathStride * M, hipMemcpyDeviceToHost, c->stream));
-    if (distinct) HIP_TRY(hipMemcpyAsync(distinct, c->path_dev + o_d, sizeof(int32_t) * M, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return 0;
-}
-
 int slamgpu_upload(slamgpu_ctx *c, int32_t nf, const float *xv, const float *Pv9, const float *w, const float *xf,
                    const float *Pf4) {
     if (int rc = check_ctx(c)) return rc;
@@ -5717,8 +4564,8 @@ int slamgpu_upload(slamgpu_ctx *c, int32_t nf, const float *xv, const float *Pv9
     }
     c->est_fresh = false;
     c->shard_est_fresh = false;
-    if (c->path_cap > 0) {  // a new set: nothing descends from the retained records
-        c->path_first = c->path_next;
+    if (c->path.cap > 0) {  // a new set: nothing descends from the retained records
+        c->path.first = c->path.next;
         if (int rc = path_identity(c)) return rc;
         HIP_TRY(hipGetLastError());
     }

@@ -1,0 +1,367 @@
+// The context of libslamgpu.so and what its translation units (slamgpu.cpp, posterior.cpp) share.  Private: not installed, and
+// no function declared here is exported (hidden visibility).
+#pragma once
+#define SLAMGPU_EXPERIMENTAL 1  // (the library defines every entry point, the experimental ones included)
+#include "../../include/slamgpu.h"
+
+#include <hip/hip_runtime.h>
+#include <dlfcn.h>
+#include <rccl/rccl.h>
+#include <unistd.h>
+
+#include <algorithm>
+#include <atomic>
+#include <chrono>
+#include <cmath>
+#include <cstdarg>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <map>
+#include <string>
+#include <vector>
+
+#include "kernels.h"
+
+using namespace slamgpu;
+
+#pragma GCC visibility push(hidden)
+#include "ring.h"
+
+int fail(int code, const char *fmt, ...);
+
+#define HIP_TRY(expr)                                                                              \
+    do {                                                                                           \
+        hipError_t e_ = (expr);                                                                    \
+        if (e_ != hipSuccess)                                                                      \
+            return fail(SLAMGPU_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
+    } while (0)
+
+constexpr int kRing = 64;       // big-packet staging slots
+constexpr int kPlainRowsTarget = 2048;  // plain-row contexts: genealogy rows in use before updates start consolidating the emptiest ones
+constexpr int kPlainConsBudget = 32;  // ... landmarks moved per update, at least
+constexpr int kMidRowsHigh = 24, kMidRowsLow = 12;  // compact contexts of mid-size maps: consolidate the emptiest rows from ... down to ... rows in use
+constexpr int kStageBound = 8;  // = kStage of kernels.hip: re-observed landmarks whose records an update launch stages in LDS
+constexpr int kConsolidateAbove = 6;  // compact contexts: genealogy rows alive before stale rows are consolidated (3..8 measure alike; profiles/consolidate_sweep_r03.txt)
+constexpr int kHistCap = 4096;  // asynchronous pose-estimate history entries
+
+struct EventPair {
+    hipEvent_t a, b;
+};
+
+struct KernelStat {
+    std::vector<EventPair> pending;
+    double ms = 0;
+    int64_t launches = 0;
+};
+
+// a grow-only staging area in device memory
+struct DevArena {
+    char *p = nullptr;
+    size_t bytes = 0;
+    int reserve(size_t total);  // (a refused growth leaves it empty)
+    void release();
+};
+
+#pragma GCC visibility pop
+
+// (default visibility, as ever: its implicit members are among the library's weak symbols)
+struct slamgpu_ctx {
+    slamgpu_config cfg{};
+    const KernelTable *k = nullptr;
+    hipStream_t stream = nullptr;
+    Buffers B{};
+    WeightScratch ws{};
+    int nf = 0;
+    uint32_t obs_step = 0, ctl_step = 0;
+    uint32_t rng_skew = 0;  // update launches that were not filter steps (slamgpu_dist_settle): they draw nothing
+    // big-packet ring (observation packets that do not fit the kernel-argument form)
+    size_t pkt_bytes = 0;
+    char *pkt_host = nullptr;  // pinned [kRing][pkt_bytes]
+    char *pkt_dev = nullptr;
+    hipEvent_t pkt_ev[kRing]{};
+    bool pkt_ev_used[kRing]{};
+    uint64_t pkt_seq = 0;
+    // tape staging (TAPE mode)
+    float *tape_host = nullptr;  // pinned: normals [3][ncap] (or predict [2][ncap]) + strata [n_global]
+    float *normals_dev = nullptr;
+    float *strata_dev[2] = {nullptr, nullptr};  // by step parity: an update launch may still need the previous step's
+    // lazy predict queue
+    PredictArgs pending{};
+    // host mirror of ctrl for readback
+    Ctrl *ctrl_host = nullptr;  // pinned
+    // pose-estimate history
+    double *hist_dev = nullptr;  // [kHistCap][kHistStride]
+    double *hist_host = nullptr; // pinned mirror of it (history_to_host)
+    int hist_n = 0;
+    bool est_fresh = false;  // Ctrl.est / hist slot hist_n were written by the last update and nothing changed since
+    // profiling
+    bool profile = false;
+    std::map<std::string, KernelStat> stats;
+    std::vector<hipEvent_t> ev_pool;
+    hipEvent_t timer_a = nullptr, timer_b = nullptr;  // slamgpu_timer_start / _stop
+    double predict_bytes = 0;
+    bool own_stream = true;
+    ShardPlan *plan_dev = nullptr, *plan_host = nullptr;  // sharded resampling plan (device + pinned mirror)
+    uint32_t *plan_seq_host = nullptr;  // pinned: sequence number the plan kernel stores after the plan
+    uint32_t plan_seq = 0;
+    // Ctrl.live / Ctrl.pend slot the next launch reads (kernels.h: Ctrl); flipped after every launch that may
+    // change the live buffer (resample_kernel, gather_kernel, shard_commit_kernel)
+    int64_t pool_used = 0;        // arrival-pool slots handed out since the pool was last emptied (flatten / settle / upload)
+    bool shard_settled = false;   // the sharded resampling stage of this step moved everything physically (records arrived)
+    int slot = 0;
+    int keep_slot = 0;            // which WeightScratch::keep buffer holds the ancestors of the last update
+    bool maybe_pending = false;   // the last update may have left a lazy gather (only the device knows)
+    bool shard_est_fresh = false; // sharded: est_part holds this shard's partials of the last update (shard_finalize_kernel)
+    bool own_totals = true;       // ws.blk_w is this context's allocation (not a caller-provided collective buffer)
+    float *own_blk_w = nullptr;
+    // Pose-estimate pipeline of the single-context path.  The resampling stage of update t (Neff, decision, ancestors,
+    // estimate partials) normally runs INSIDE the launch of update t+1 (UpdateArgs::plan_inline) and its partials are
+    // reduced by the helper block of launch t+2; anything that needs results earlier runs them as launches of their own.
+    struct EstStage {
+        bool has = false;
+        int par = 0;              // step parity: which est_part / lcum / blk_w buffers
+        uint32_t step = 0;        // observation-step counter of that update (Philox stream of its strata)
+        int nf = 0;               // landmarks after that update
+        double *hist = nullptr;   // history slot its estimate belongs to (or null)
+    };
+    bool scan_ready = false;      // scan_kernel ran on the last update's block totals (large contexts)
+    bool mid_compact = false;     // compact layout on a map of more than 39 landmarks (kernels.h: kMidLandmarks): host-made packets only
+    bool ref_resample = false;    // the resampling stage replays the reference's order of operations (kernels.h: kRefResampleMax):
+                                  // strict build, the caller's draws (TAPE), a single context of at most 5 000 particles, linear weights
+    bool consolidate = true;      // row consolidation of compact contexts (do_update); SLAMGPU_NO_CONSOLIDATE=1 turns it off
+    int consolidate_above = kConsolidateAbove;  // (SLAMGPU_CONSOLIDATE_ABOVE: diagnostic)
+    int plain_rows_target = kPlainRowsTarget;   // (SLAMGPU_PLAIN_ROWS_TARGET: diagnostic / tests)
+    int scan_min_blocks = 1024;   // contexts with more blocks of 256 particles than this use scan_kernel (262 144 particles)
+    // Genealogy bookkeeping (kernels.h: gen).  The association is global, so the host knows which genealogy row every
+    // landmark uses: a step that writes landmarks opens a new row for them; a row whose last landmark moved on is recycled.
+    std::vector<uint32_t> seen_step; // [cap_nf] observation step that last re-observed each landmark (duplicate check)
+    std::vector<int32_t> live_flag;  // [cap_nf] which record buffer of every landmark row is live (flips when re-observed)
+    int32_t *live_dev = nullptr;     // device copy for flatten / shard pack + unpack
+    std::vector<int32_t> erow;       // [cap_nf] row of every landmark
+    std::vector<int32_t> refcnt;     // [cap_rows] landmarks using each row
+    std::vector<int32_t> free_rows;  // stack of unused rows
+    std::vector<int32_t> live_rows;  // rows with refcnt > 0
+    std::vector<int32_t> live_pos;   // [cap_rows] position in live_rows, -1 if not live
+    int32_t *erow_dev = nullptr, *rows_dev = nullptr;  // device copies for gather / flatten / shard pack + unpack
+    // distributed operation (slamgpu_dist_*)
+    bool dist = false, dist_clean = false;
+    PeerPtrs *peers_dev = nullptr;
+    float *gtot_dev[2] = {nullptr, nullptr};
+    std::vector<void *> ipc_opened;
+    void *comm = nullptr;  // ncclComm_t: when set, slamgpu_dist_step / _settle run the all-gather themselves
+    // push collective (slamgpu_dist_set_collective): the update launch stores its totals into every shard's table and a
+    // one-wave flag kernel is the barrier; flags_dev = [kMaxShards] flag words + the error word, fine-grained memory
+    bool count_remote = false;   // slamgpu_dist_remote_reads has been asked for: the update launches keep the counter from then on
+    bool dist_push = false;
+    bool dist_fold = false;  // push + the barrier folded into the head of the next update launch (SLAMGPU_DIST_FOLD)
+    uint32_t *flags_dev = nullptr;
+    uint32_t *peer_flags[kMaxShards] = {};
+    uint32_t flag_seq = 0;
+    // observation front end (slamgpu_set_map / slamgpu_observe)
+    float *map_dev = nullptr, *obs_r_dev = nullptr;
+    int32_t *table_dev = nullptr;
+    ObserveOut *obs_out_dev = nullptr;
+    int32_t map_n = 0, obs_nf = 0;
+    uint32_t observe_step = 0;
+    int fresh_row = -1;              // row the last update opened, while nothing but the resample the next update launch
+                                     // applies has touched it: records of its landmarks sit in the source slot itself
+    bool tables_dirty = true;
+    // device-resident genealogy bookkeeping (slamgpu_step_observe): while book_on_device the tables erow_dev / live_dev /
+    // refcnt_dev / book_dev are the truth and the host's vectors are stale; book_pull / book_push hand the ownership over
+    bool book_on_device = false;
+    int32_t front_status = 0;        // sticky kStatus* bits of the device front end seen by book_pull (carried back by book_push)
+    DevBook *book_dev = nullptr;
+    int32_t *refcnt_dev = nullptr, *take_dev = nullptr;
+    int32_t *book_host = nullptr;    // pinned staging of book_pull / book_push
+    hipStream_t obs_stream = nullptr;  // the front-end kernels run here, a step ahead of the update launches (events order them)
+    hipEvent_t obs_ev[kRing]{};        // observe_book of the packet in ring slot k has finished
+    char *last_pkt_dev = nullptr;    // packet of the last slamgpu_step_observe (slamgpu_observe_fetch)
+    // compact contexts: the front end runs inside the update launch (kernels.h: FrontArgs); its state lives in two device
+    // copies, read / written alternately (front_par: the one the next launch reads)
+    std::vector<float> map_host;     // [2][map_n], as slamgpu_set_map received it
+    FrontState *front_dev = nullptr, *front_host = nullptr;
+    ObsPacket *front_pkt_dev = nullptr;
+    int front_par = 0;
+    bool front_ready = false;
+    // gated association with the spatial prefilter (slamgpu_associate_ex): per-landmark boxes over all particles, refreshed
+    // for the landmarks written since (box_dirty), and the grid buffers
+    LmkBox *box_dev = nullptr;
+    std::vector<char> box_dirty;
+    // landmarks the caller has retired from the gated association (slamgpu_retire_landmarks): host flags + the device's bit mask
+    std::vector<char> retired;
+    uint32_t *retired_dev = nullptr;
+    int n_retired = 0;
+    int32_t *assoc_ids_dev = nullptr, *cell_start_dev = nullptr, *cell_fill_dev = nullptr;
+    // per-particle association (slamgpu_update_particle / _labels; kernels.h: PerParticle): device scratch, grown on demand
+    int32_t *pp_lab_dev = nullptr;   // labels BY OBSERVATION, [nz][ncap]
+    size_t pp_lab_cap = 0;
+    int16_t *pp_obs_dev = nullptr;   // PerParticle::obs [rows][ncap]
+    size_t pp_obs_rows = 0;
+    float *pp_z_dev = nullptr;       // [2 pp_nz_cap]
+    int32_t *pp_tab_dev = nullptr;   // [cap_nf] first / uidx | [cap_nf] holders | [pp_nz_cap] news / newk | [pp_nz_cap] idn
+    int pp_nz_cap = 0;
+    float *pp_wf_dev = nullptr;      // [ncap]
+    uint8_t *pp_any_dev = nullptr;   // [ncap]
+    std::vector<char> pp_partial;    // slots that NOT every particle opened: the only ones that can lose their last holder (a slot every particle
+                                     // opened is held by every descendant for good): what the holders census counts
+    std::vector<char> pp_dead;       // landmark slots no particle holds any more (their hypotheses died in a resample): out of the
+    std::vector<int32_t> pp_dead_list;  // association (retired) until a later landmark opens them again
+    float *vote_w_dev = nullptr;     // AssocGridArgs::vote_w, grown on demand
+    size_t vote_w_cap = 0;
+    float *assoc_z_dev = nullptr;    // the observations of an association call / its vote tables: kept between calls (an allocation and a release
+    VoteSlot *assoc_votes_dev = nullptr;  // per call each), grown on demand
+    int assoc_nz_cap = 0;
+    bool retired_stale = false;      // the host's retired flags have changed since the device's mask was written (retired_upload clears it)
+    uint64_t pp_steps = 0;
+    bool pp_census_done = false;     // the association kernel took the census of the labels itself (AssocGridArgs::census_first): pp_census_kernel is skipped
+    const PerParticle *pp_launch = nullptr;  // set around issue_update by do_update_particle: the launch takes update_kernel<.., PP = true>
+    float4 *items_dev = nullptr;  // [2 cap_items]: kernels.h: AssocGridArgs::items
+    AssocGeom *geom_dev = nullptr;
+    int32_t cap_items = 0;
+    char *peek_dev = nullptr;        // staging of slamgpu_peek, grown on demand
+    size_t peek_bytes = 0;
+    DevArena msum;                   // staging and partials of the map, pair, innovation and joint summaries
+    // path recording (slamgpu_path_*; kernels.h: PathRing).  path.cap = 0: off, nothing allocated, no kernel of it launched.
+    // origin[path_org] is the live origin array
+    Ring path;
+    float4 *path_rec_dev = nullptr;
+    int32_t *path_origin_dev[2] = {nullptr, nullptr};
+    int path_org = 0;
+    DevArena path_arena;             // staging, push buffers and partials of slamgpu_path_trace / _summary
+    // pose posterior (slamgpu_pose_*; kernels.h: PoseSummaryArgs).  pose.cap = 0: the per-step ring is off.  Nothing is allocated and no kernel of it launched until the ring is enabled or
+    // slamgpu_pose_summary is called
+    Ring pose;
+    double *pose_ring_dev = nullptr; // [pose.cap][kPoseStride]
+    double *pose_dev = nullptr;      // [tiles][kPoseFields] partials | [kPoseStride] staging of slamgpu_pose_summary
+    // innovation posterior (slamgpu_innovation_*; kernels.h: InnovArgs).  innov.cap = 0: the ring is off.
+    // innov_records counts the _record calls since the enable.  A packet travels
+    // through one of kInnovStage pinned staging slots (an event per slot says when the device has taken it: a record does not wait
+    // for the device unless it is kInnovStage packets ahead of it).  Nothing is allocated and no kernel of it launched until the ring
+    // is enabled or slamgpu_innovation_summary is called
+    Ring innov;
+    int64_t innov_records = 0;
+    double *innov_ring_dev = nullptr;  // [innov.cap][kInnStride]
+    int32_t *innov_tag_dev = nullptr;  // [innov.cap][2]: record, slot
+    char *innov_host = nullptr;        // pinned [kInnovStage][innov_host_m] x (zf 8 B | idf 4 B)
+    size_t innov_host_m = 0;
+    uint64_t innov_seq = 0;
+    hipEvent_t innov_ev[4]{};
+    bool innov_ev_used[4]{};
+    bool pp_stage_ran = false;       // slamgpu_run_particle: a pose entry has already run the stage the last iteration left (pose_append)
+    unsigned long long *stamps_dev = nullptr;  // diagnostic (SLAMGPU_STAMPS=1 + libslamgpu_stamps.so): UpdateArgs::stamps
+    // persistent small-N step loop (slamgpu_run_observe, kernels.h: PersistArgs)
+    bool persist_ok = true;              // SLAMGPU_NO_PERSIST=1 turns it off (diagnostic / tests: the per-step loop)
+    bool special_ok = true;              // SLAMGPU_NO_SPECIAL=1 turns it off (diagnostic / tests: update_kernel's general instantiation for every launch)
+    int64_t special_launches = 0;        // update launches that took a specialised instantiation (slamgpu_update_special_launches: tests)
+    struct PersistCollect {              // while set, issue_update queues its launch instead of making it
+        std::vector<PersistStep> steps;
+        bool have_first = false;
+        Buffers B{};
+        UpdateArgs U{};
+        RngArgs rng{};
+        WeightScratch ws{};
+    } *collect = nullptr;
+    // the queue of a launch lives in PINNED HOST memory and the kernel reads it there (an entry an iteration ahead: the PCIe trip is
+    // hidden): kPqBufs buffers of pq_cap entries used in turn; a buffer is rewritten once the launch that read it has finished
+    static constexpr int kPqBufs = 4;
+    PersistStep *pq_host = nullptr;
+    size_t pq_cap = 0;
+    hipEvent_t pq_kev[kPqBufs] = {};
+    bool pq_kev_used[kPqBufs] = {};
+    int pq_next = 0;
+    uint32_t *psync_dev = nullptr, *pstatus_host = nullptr;
+    int32_t *ppk_dev = nullptr;          // [2][kSmallWords] observation packets of the loop's helper workgroup
+    PersistStep *pring_dev = nullptr;    // [4] the loop's ring of queue entries in device memory (kernels.h: PersistArgs::ring)
+    float4 *pdraw_dev = nullptr;         // [2][6][ncap] draws of the loop's drawer workgroups (FastSLAM 1, fast build)
+    int64_t persist_launches = 0, persist_steps = 0;
+    EstStage unplanned;           // the last update: resampling stage not run yet
+    EstStage unreduced;           // an update whose partials exist (est_part[par]) but are not reduced yet
+    // per-particle association driven by the device (slamgpu_run_particle; kernels.h: PpState / PpArgs).  While pp_on_device the
+    // per-particle state (pp_partial, pp_dead, the retired mask, pp_steps, obs_step, nf, the row tables) lives in device memory and the
+    // host's copies are stale; pp_pull (through book_pull / flush_stages) brings it back, pp_push hands it over
+    bool pp_on_device = false;
+    PpState *pp_st_dev = nullptr;
+    int32_t *pp_words_dev = nullptr;  // partial | dead | first | hold | uidx | list | dlist [cap_nf each] | news | newk | idn [pp_words_w each]
+    int pp_words_w = 0;
+    char *pp_pkt_dev = nullptr;       // the update's packet (fixed layout, cap = cap_nf)
+    int32_t *pp_report_dev = nullptr; // [kHistCap][8] reports of the iterations not fetched yet
+    // SLAMGPU_ASSOC_LISTS: cumulative counters (AssocListArgs::lstats; [4]: observations past the host's bound, reported by the next
+    // slamgpu_particle_report_fetch) and whether device-driven iterations have written slots without refreshing their boxes
+    unsigned long long *lstats_dev = nullptr;
+    bool box_dev_stale = false;
+    // the exclusion rule's radius capped by the step's observation spacing (slamgpu_set_particle_excl_spacing; 0: off) and the radii of
+    // the last step that made them: excl_rho_dev[0] holds their count (int32), the radii follow from [4] (excl_rho_cap of them)
+    float excl_spacing = 0.0f;
+    int32_t *excl_rho_dev = nullptr;
+    int excl_rho_cap = 0;
+    // data association sampling (slamgpu_set_particle_assoc_sampling): on / off, the ratios of the sampled pairs ([nz][ncap], as
+    // pp_lab_dev; held only while sampling is on) and the cumulative counters (SampleArgs::stats)
+    int32_t das_on = 0;
+    float *das_ratio_dev = nullptr;
+    size_t das_ratio_cap = 0;
+    unsigned long long *das_stats_dev = nullptr;
+    SampleArgs das_step{};  // the sampling arguments of the step being associated (AssocRule::smp points here: particle_rule)
+    // negative information (slamgpu_set_particle_miss; pm_range = 0: off): the factor and the view, the counts of the last step that
+    // made them ([ncap]; pm_have: some step has) and the cumulative counters (PpMissArgs::stats); nothing is allocated while it is off
+    float pm_p = 1.0f, pm_range = 0.0f, pm_front = 0.0f;
+    int32_t *pm_cnt_dev = nullptr;
+    unsigned long long *pm_stats_dev = nullptr;
+    bool pm_have = false;
+    // mutual exclusion for contested landmarks (slamgpu_set_particle_mutex): on / off, the table of who holds which slot
+    // ([cap_nf][ncap] int16, -1 between launches; held only while it is on) and the cumulative counters (PpMutexArgs::stats)
+    int32_t mx_on = 0;
+    int16_t *mx_hold_dev = nullptr;
+    unsigned long long *mx_stats_dev = nullptr;
+    size_t mx_hold_cap = 0;
+    bool pp_lists_done = false;      // the step's association went through the lists and left the slots' boxes (pp_missed's box test)
+    // the observations of the last per-particle step (slamgpu_particle_labels): the host-driven call's count, or -1: the device-driven
+    // iteration's (ObserveOut::nz)
+    int32_t pp_lab_nz = 0;
+    int pp_report_n = 0;
+    bool pp_stage_open = false;       // the previous iteration may have left a resampling stage (the device knows) and no gather has run since
+    double *pp_prev_hist = nullptr;   // ... its history slot and the parity of its weight scratch
+    int pp_prev_par = 0;
+    uint32_t pp_iter = 0;
+};
+
+#pragma GCC visibility push(hidden)
+
+hipEvent_t get_event(slamgpu_ctx *c);
+
+struct Timed {
+    slamgpu_ctx *c;
+    KernelStat *st = nullptr;
+    EventPair ep{};
+    Timed(slamgpu_ctx *ctx, const char *name) : c(ctx) {
+        if (!c->profile) return;
+        st = &c->stats[name];
+        ep.a = get_event(c);
+        ep.b = get_event(c);
+        if (ep.a) (void) hipEventRecord(ep.a, c->stream);
+    }
+    ~Timed() {
+        if (!st) return;
+        if (ep.b) (void) hipEventRecord(ep.b, c->stream);
+        st->pending.push_back(ep);
+        st->launches++;
+    }
+};
+
+// slamgpu.cpp's, as the posterior layer calls them
+int check_ctx(slamgpu_ctx *c);
+int book_pull(slamgpu_ctx *c);
+int sync_tables(slamgpu_ctx *c);
+int flush_predict(slamgpu_ctx *c);
+int flush_stages(slamgpu_ctx *c);
+int pp_dev_stage(slamgpu_ctx *c);
+int pp_dev_flush_predict(slamgpu_ctx *c);
+// posterior.cpp's, as the step entry points call them
+int path_identity(slamgpu_ctx *c);
+int path_compose(slamgpu_ctx *c);
+int path_append(slamgpu_ctx *c);
+int pose_append(slamgpu_ctx *c);
+int innov_append(slamgpu_ctx *c, const float *zf, const int32_t *idf, int32_t m, const float *R);
+void posterior_release(slamgpu_ctx *c);  // slamgpu_destroy's share of this layer
+
+#pragma GCC visibility pop

@@ -336,6 +336,36 @@ def test_read_only_and_deterministic(sg, tmp_path_factory, layout):
     _same_state(run(True), run(False), "summaries between the steps (%s)" % layout)
 
 
+# ---- the shapes at which the code the summaries share can go wrong -----------------------------------------------------------------------
+ODD_N = 9222   # ten tiles of 1 024 particles with six in the last (tests/test_gpu_map_summary.py: ODD_N)
+
+
+@pytest.mark.parametrize("layout,logw", [(layout, logw) for layout in ("compact", "plain") for logw in (False, True)])
+def test_odd_tiles_uneven_count(sg, monkeypatch, layout, logw):
+    """ODD_N particles on example_webmap (at most 16 slots in use), compact rows or plain ones (a capacity past the compact layouts'),
+    linear or log weights: straight after an update that resampled (its gather pending), a packet of 11 observations (the step's own,
+    repeated) through the partials' table 8 at a time: the model within its bounds, and the bits of the same packet in one chunk"""
+    tape = _webmap(1000)
+    s = sg.SlamGpu(ODD_N, tape["nlm"] if layout == "compact" else 300, method=2, n_effective=int(0.75 * ODD_N), rng_mode=sg.RNG_PHILOX, seed=5,
+                   math_mode=1, log_weights=logw)
+    assert (s.genealogy_rows()[1] <= 40) == (layout == "compact")
+    for k, st in enumerate(tape["steps"]):
+        zf, idf, zn = _packet(st)
+        _predicts(s, st, tape)
+        _update(s, st, tape)
+        if k >= 40 and len(idf) and s.stats()[1]:   # this update resampled: its gather is pending, and no predict is queued that would settle it
+            assert s.nf() <= 16
+            zf, idf = np.resize(zf, (11, 2)), np.resize(idf, 11)
+            monkeypatch.setenv("SLAMGPU_INNOV_CHUNK", "8")
+            got, holders, exp = _check(s, zf, idf, tape["R"], logw, "odd tiles %s %s step %d" % (layout, "log" if logw else "linear", k))
+            monkeypatch.delenv("SLAMGPU_INNOV_CHUNK")
+            whole, wh = s.innovation_summary(zf, idf, tape["R"])
+            assert whole.tobytes() == got.tobytes() and np.array_equal(wh, holders), "the packet in chunks of 8: different bits"
+            s.close()
+            return
+    raise AssertionError("no update from step 40 on resampled: no summary was taken with a gather pending")
+
+
 # ---- 7. degenerate weights, refusals --------------------------------------------------------------------------------------------------
 def test_degenerate_weights_give_nan(sg):
     """all-zero weights, one infinite weight: every double NaN, return 0, holders still exact"""

@@ -31,7 +31,7 @@ import pose_model
 from conftest import DATA
 from test_gpu_map_pairs import _grown, _pp_state
 from test_gpu_map_pairs import _bounds as _pair_bounds, _model as _pair_model
-from test_gpu_map_summary import _STATE, _known, _run
+from test_gpu_map_summary import ODD_CASES, ODD_N, _STATE, _known, _odd_pending, _run, _uneven
 from test_gpu_map_summary import _bounds as _map_bounds, _model as _map_model
 from test_gpu_particle_assoc import DISCARD, NEW, _tape
 from test_gpu_particle_device import EXCL_ON, EXE, ERR_INVALID, _course, _ctx, _finish, _opt, _same_state
@@ -329,6 +329,20 @@ def test_deterministic_and_independent_of_the_chunking(sg, monkeypatch):
     assert _bits(s.joint_summary(held)) == _bits(s.joint_summary(held))
     _note(jm.compare(s.joint_summary(np.arange(nf)), jm.model(d, False, np.arange(nf)), s.N, "flattened, every slot"))
     s.close()
+
+
+@pytest.mark.parametrize("layout,logw", ODD_CASES)
+def test_odd_tiles_uneven_count(sg, monkeypatch, layout, logw):
+    """test_gpu_map_summary's shapes: ODD_N particles (a last tile of six), a list of 11 slots (three block pairs, taken two at a
+    time), both layouts and both weight forms, a gather pending: the model within its bounds, and the bits of the call in one chunk"""
+    def check(s, tag):
+        slots = np.arange(_uneven(s.nf()))
+        assert s.N == ODD_N
+        monkeypatch.setenv("SLAMGPU_JOINT_CHUNK", "2")
+        got, m, pk = _check(s, logw, slots, tag)
+        monkeypatch.delenv("SLAMGPU_JOINT_CHUNK")
+        assert _bits(s.joint_summary(slots)) == _bits(got), "the block pairs in chunks of 2: different bits"
+    _odd_pending(sg, layout, logw, check)
 
 
 def test_per_particle_run_is_not_disturbed(sg):

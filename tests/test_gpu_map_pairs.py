@@ -20,7 +20,7 @@ import numpy as np
 import pytest
 
 from conftest import DATA
-from test_gpu_map_summary import _STATE, _known, _psum, _run
+from test_gpu_map_summary import ODD_CASES, ODD_N, _STATE, _known, _odd_pending, _psum, _run
 from test_gpu_particle_assoc import DISCARD, NEW, _predicts, _tape
 from test_gpu_particle_device import EXCL_ON, EXE, ERR_INVALID, _course, _ctx, _finish, _opt, _same_state
 from test_gpu_particle_lists import _course_of, _synthetic
@@ -314,6 +314,20 @@ def test_deterministic_and_independent_of_position(sg, monkeypatch):
     assert _bits(x) == _bits(y), "through the genealogy and flattened: different bits"
     _compare(y, _model(d, False, pairs), s.N, "flattened")
     s.close()
+
+
+@pytest.mark.parametrize("layout,logw", ODD_CASES)
+def test_odd_tiles_uneven_count(sg, monkeypatch, layout, logw):
+    """test_gpu_map_summary's shapes: ODD_N particles (a last tile of six), 11 pairs through the partials' table 8 at a time, both
+    layouts and both weight forms, a gather pending: the model within its bounds, and the bits of the same list in one chunk"""
+    def check(s, tag):
+        pairs = _all_pairs(range(s.nf()))[4:15]
+        assert len(pairs) == 11 and s.N == ODD_N
+        monkeypatch.setenv("SLAMGPU_MAP_CHUNK", "8")
+        mp, m = _check(s, logw, tag, pairs)
+        monkeypatch.delenv("SLAMGPU_MAP_CHUNK")
+        assert _bits(s.map_pairs(pairs)) == _bits(mp), "a pair's bits depend on the chunking"
+    _odd_pending(sg, layout, logw, check)
 
 
 def test_degenerate_weights_give_nan(sg):

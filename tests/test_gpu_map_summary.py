@@ -285,6 +285,54 @@ def test_read_only_and_deterministic(sg, tmp_path_factory, monkeypatch, layout):
     _same_state(run(True), run(False), "summaries between the steps (%s)" % layout)
 
 
+# ---- the shapes at which the code the summaries share can go wrong (test_gpu_map_pairs.py and test_gpu_joint.py use them too) ----------
+ODD_N = 9222   # ten tiles of 1 024 particles with six in the last: waves without a particle, and the finishing pass's eight stretches
+               # get two tiles each where they get any (three of them get none)
+ODD_CASES = [(layout, logw) for layout in ("compact", "plain") for logw in (False, True)]
+
+
+def _uneven(nf):
+    """a number of slots, pairs or observations that is no multiple of the group of 8 and needs a second chunk of 8"""
+    count = 11 if nf >= 11 else nf - (nf % 8 == 0)
+    assert count > 8, "the map holds %d slots: too few for two chunks of 8" % nf
+    return count
+
+
+def _odd_pending(sg, layout, logw, check):
+    """example_webmap (at most 16 slots in use) at ODD_N particles, in compact rows or in plain ones (a capacity past the compact
+    layouts'), with linear or log weights: check(s, tag) after every step from 170 on, until one was made straight after an update that
+    resampled, with its gather pending and nothing fetched in between"""
+    c = _course("FASTSLAM2", 200)
+    s = _known(sg, c, ODD_N, 2, 1, logw=logw, cap=None if layout == "compact" else 64)
+    assert (s.genealogy_rows()[1] <= 40) == (layout == "compact")
+    _run(s, c, 0, 170)
+    s.history_fetch()
+    for k in range(170, 200):
+        _run(s, c, k, k + 1)
+        assert s.nf() <= 16
+        check(s, "odd tiles %s %s step %d" % (layout, "log" if logw else "linear", k))
+        if s.history_fetch()[2][-1]:
+            s.close()
+            return
+    raise AssertionError("no step from 170 on resampled: no call was made with a gather pending")
+
+
+@pytest.mark.parametrize("layout,logw", ODD_CASES)
+def test_odd_tiles_uneven_count(sg, monkeypatch, layout, logw):
+    """ODD_N particles, 11 slots through the partials' table 8 at a time, both layouts and both weight forms, a gather pending: the
+    model within its bounds, and the bits of the same slots inside the whole map taken in one chunk"""
+    def check(s, tag):
+        pk = s.peek()
+        count = _uneven(s.nf())
+        monkeypatch.setenv("SLAMGPU_MAP_CHUNK", "8")
+        ms = s.map_summary(0, count)
+        monkeypatch.delenv("SLAMGPU_MAP_CHUNK")
+        _compare(ms, {q: v[:count] for q, v in _model(pk, logw).items()}, ODD_N, tag)
+        whole = s.map_summary()
+        assert _bits({q: v[:count] for q, v in whole.items()}) == _bits(ms), "a slot's bits depend on the chunking"
+    _odd_pending(sg, layout, logw, check)
+
+
 def test_far_from_the_origin(sg):
     """the N = 100 000 state of the known-association case with every landmark moved by (1e5, -1e5) m: D stays the cloud's, |mu| is
     1e5.  Raw second moments would cancel ~ sqrt(N) u x^2 = 3e-4 m^2 of noise into a scatter whose bound is ~ 1e-5 m^2"""

@@ -317,7 +317,8 @@ def _summaries_both_states(s, t, step, exp, first, k, last, logw, tag):
     return k, m
 
 
-@pytest.mark.parametrize("method,math,N,logw", [(2, 1, 100000, False), (1, 0, 1000, False), (2, 1, 3000, True)])
+# (N = 9 222: 37 tiles of 256 particles with six in the last, waves without a particle; linear and log weights)
+@pytest.mark.parametrize("method,math,N,logw", [(2, 1, 100000, False), (1, 0, 1000, False), (2, 1, 3000, True), (2, 1, 9222, False), (2, 1, 9222, True)])
 def test_summary(sg, method, math, N, logw):
     """against tests/path_model.py on the twin's records and weights; with a gather pending and with none; linear and log-weights"""
     c = _course("FASTSLAM2" if method == 2 else "FASTSLAM1", 100)

@@ -192,6 +192,24 @@ def test_log_weight_context(sg, mm):
     s.close()
 
 
+@pytest.mark.parametrize("logw", [False, True], ids=["linear", "log"])
+def test_odd_tiles_pending_gather(sg, logw):
+    """N = 9 222 (ten tiles of 1 024 particles with six in the last: waves without a particle, finishing stretches without a tile), linear
+    and log weights: a checked summary after every step until one was taken straight after an update that resampled, its gather pending"""
+    c = _course("FASTSLAM2", 100)
+    s = _known(sg, c, 9222, 1, logw=logw)
+    _run(s, c, 0, 20)
+    s.history_fetch()
+    for k in range(20, 100):
+        _step(s, c, k)
+        _check(s, logw, "odd tiles %s step %d" % ("log" if logw else "linear", k))
+        if s.history_fetch()[2][-1]:
+            break
+    else:
+        raise AssertionError("no step resampled: no summary was taken with a gather pending")
+    s.close()
+
+
 def test_degenerate_weights_give_nan(sg):
     """all-zero weights, and weights that sum to nothing finite: every entry NaN, return 0 (SLAMGPU_STATUS_DEGENERATE's convention)"""
     N = KBLOCK + 1
