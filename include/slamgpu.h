@@ -981,6 +981,11 @@ int slamgpu_particle_miss_visited(slamgpu_ctx *ctx, int64_t *records);
 int slamgpu_update_special(int32_t method, int32_t arrivals, int32_t big, int32_t per_particle, int32_t no_special, uint32_t mode_bits);
 int slamgpu_update_special_modes(int32_t spec);
 int slamgpu_update_special_launches(slamgpu_ctx *ctx, int64_t *count);
+/* A specialised launch whose packet is made by the host and re-observes m = 1 .. 8 landmarks takes an instantiation with m compiled
+ * in as well (never in contexts created under SLAMGPU_NO_COUNTED=1).  out[m], m = 1 .. 8: how many of the context's specialised
+ * launches so far took the instantiation counted for m; out[0]: how many took the plain specialised one.  Their sum is
+ * slamgpu_update_special_launches.  Host bookkeeping; does not synchronise. */
+int slamgpu_update_counted_launches(slamgpu_ctx *ctx, int64_t out[9]);
 
 #endif /* SLAMGPU_EXPERIMENTAL */
 

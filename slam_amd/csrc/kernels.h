@@ -98,6 +98,13 @@ inline int update_special(int method, int arrivals, bool big, bool pp, bool wide
         if (update_mode_bits(kUpdateSpecs[s]) == mode_bits) return s;
     return 0;
 }
+// Counted instantiations (kernels.hip: update_kernel_counted): a specialised launch whose packet re-observes 1 .. kCountedMax landmarks
+// and is made by the host has that number compiled in as well.  Returns it, or 0: the plain specialised (or general) kernel
+// (off: the context was created under SLAMGPU_NO_COUNTED=1; spec: what update_special returned).
+constexpr int kCountedMax = 8;  // (= kStage, kernels.hip: what the staging of a small packet holds)
+inline int update_counted(int spec, int m, bool front_on, bool off) {
+    return (!off && spec != 0 && !front_on && m >= 1 && m <= kCountedMax) ? m : 0;
+}
 // status bits of an update's resampling stage (slamgpu.h: SLAMGPU_STATUS_*)
 constexpr int kStatusBadPacket = 2;   // the kernel did not find its packet where the kernel-argument layout says (never seen)
 constexpr int kStatusCapacity = 4;    // device front end: more new landmarks than the context has room for (the surplus was dropped)
@@ -921,9 +928,10 @@ struct KernelTable {
     // the step: [resampling stage of the previous update, inline] + [gather] + [fused predicts] + per-particle observation
     // update + in-block weight prefix / totals  (+ helper blocks: genealogy copy, Ctrl words, estimate reduction)
     // no_special: the general instantiation whatever the launch's mode set (SLAMGPU_NO_SPECIAL=1).  Returns the instantiation the
-    // launch took (update_special: 0 general, s > 0 kUpdateSpecs[s])
+    // launch took (update_special: 0 general, s > 0 kUpdateSpecs[s]).  no_counted: never a counted instantiation (SLAMGPU_NO_COUNTED=1;
+    // otherwise a specialised launch is a counted one when update_counted says so)
     int (*update)(hipStream_t, const Buffers &, const PredictArgs &, const UpdateArgs &, const RngArgs &,
-                  const WeightScratch &, bool no_special);
+                  const WeightScratch &, bool no_special, bool no_counted);
     // the same step with a per-particle association (PerParticle: update_kernel<.., PP = true>; single contexts on plain rows); driven
     // by the device when PerParticle::obs_dev is set (update_kernel<.., PPD = true>; no observation: nothing)
     // (no specialised instantiation: always 0)

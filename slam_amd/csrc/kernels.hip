@@ -1406,6 +1406,36 @@ __global__ void __launch_bounds__(kBlock) update_kernel_special(const float *__r
 #undef STEP_FRONT
 }
 
+// update_kernel_special<SPEC, WPAR> with one more value the host holds before it enqueues the launch compiled in: MRE = U.m, the packet's
+// number of re-observed landmarks, 1 .. kCountedMax (kernels.h: update_counted, asked by launch_update_any).  The step text
+// (update_step.inl: COUNTED) then keeps the MRE records in registers from their loads through both passes: no staging in LDS between
+// the passes, exactly MRE record loads, no loop control.  Births, consolidation and the genealogy copy stay run-time loops.  Same
+// argument layout, same operations on the same values: bit-identical (tests/test_gpu_counted.py).
+// (A name of its own: the set of update_kernel_special instantiations is the rows of kUpdateSpecs, tests/test_update_tail_cpu.py.)
+static_assert(kCountedMax == kStage, "kernels.h: the counted range is what the staging holds");
+template <int SPEC, int WPAR, int MRE>
+__global__ void __launch_bounds__(kBlock) update_kernel_counted(const float *__restrict__ h_tot, Ctrl *h_ctrl, const FrontState *h_front, int h_nb,
+                                                                 int h_slot, int h_grid, int h_flags, Buffers B, PredictArgs PA, UpdateArgs U,
+                                                                 RngArgs rng, WeightScratch ws) {
+    static_assert(SPEC > 0 && SPEC < kUpdateSpecCount, "kernels.h: kUpdateSpecs");
+    static_assert(WPAR == 0 || WPAR == 1, "WeightScratch::wpar");
+    static_assert(MRE >= 1 && MRE <= kCountedMax, "kernels.h: kCountedMax");
+    constexpr int METHOD = 2, MODE = 0;
+    constexpr bool BIG = false, PERSIST = false, PP = false;
+    [[maybe_unused]] const PerParticle ppa{};
+    const PersistStep *const qe = nullptr;
+    StepCarry carry;  // (unused by a per-step launch)
+#define STEP_WPAR WPAR
+#define STEP_PLAN kUpdateSpecs[SPEC].plan
+#define STEP_FRONT U.front
+#define STEP_COUNT MRE
+#include "update_step.inl"
+#undef STEP_WPAR
+#undef STEP_PLAN
+#undef STEP_FRONT
+#undef STEP_COUNT
+}
+
 // The same step for sets of more than kWideBlocks tiles on one GPU (compact layout, single context), compiled for THREE waves per
 // SIMD (168 vector registers, 4 of them spilled: update_kernel takes 179 and gets two).  At 10^5 particles the launch is a single
 // round of tiles and the registers buy latency; from ~2 x 10^5 on the tiles queue for the CUs and a third resident tile per CU
@@ -4228,7 +4258,7 @@ static void launch_shard_finish(hipStream_t st, const Buffers &B, const WeightSc
 }
 
 static int launch_update_any(hipStream_t st, const Buffers &B, const PredictArgs &PA, const UpdateArgs &U,
-                             const RngArgs &rng, const WeightScratch &ws, const PerParticle &ppa, bool no_special) {
+                             const RngArgs &rng, const WeightScratch &ws, const PerParticle &ppa, bool no_special, bool no_counted) {
     // compute blocks first (they are the long pole), then -- single-context pipeline only -- the copy blocks of a
     // pending lazy gather (they exit at once when nothing is pending: the host cannot know) and one helper block
     int grid = B.ncap / kBlock;
@@ -4265,6 +4295,20 @@ static int launch_update_any(hipStream_t st, const Buffers &B, const PredictArgs
     const UpdateModes modes = {U.plan_inline != 0, U.scan_global != 0, U.logw != 0, U.front.on != 0, rng.mode != 0, PA.comp.valid != 0,
                                PA.use_heading != 0, PA.add_noise != 0, U.do_resample != 0};
     const int spec = update_special(U.method, U.arrivals, U.big != nullptr, pp, false, no_special, update_mode_bits(modes));
+    // ... and the counted one when the packet's number of re-observed landmarks is in its range (kernels.h: update_counted): it stages
+    // nothing, so its dynamic LDS is the block prefix and the ancestor windows alone
+    const int counted = update_counted(spec, U.m, U.front.on != 0, no_counted);
+    if (counted != 0) {
+        const size_t lds_c = lds - stage_bytes;
+        dispatch<kUpdateSpecCount, 2, kCountedMax + 1>(
+            [&](auto sp, auto wp, auto mc) {
+                if constexpr (sp != 0 && mc != 0)
+                    hipLaunchKernelGGL((update_kernel_counted<sp, wp, mc>), dim3(grid), dim3(kBlock), lds_c, st, h_tot, B.ctrl, U.front.state_in, ws.nblocks,
+                                       B.slot, grid, h_flags, B, PA, U, rng, ws);
+            },
+            spec, ws.wpar, counted);
+        return spec;
+    }
     if (spec != 0) {
         dispatch<kUpdateSpecCount, 2>(
             [&](auto sp, auto wp) {
@@ -4286,8 +4330,14 @@ static int launch_update_any(hipStream_t st, const Buffers &B, const PredictArgs
 }
 
 static int launch_update(hipStream_t st, const Buffers &B, const PredictArgs &PA, const UpdateArgs &U, const RngArgs &rng, const WeightScratch &ws,
-                         bool no_special) {
-    return launch_update_any(st, B, PA, U, rng, ws, PerParticle{}, no_special);
+                         bool no_special, bool no_counted) {
+    return launch_update_any(st, B, PA, U, rng, ws, PerParticle{}, no_special, no_counted);
+}
+
+// (per-particle association: no specialised instantiation, so no counted one)
+static int launch_update_particle(hipStream_t st, const Buffers &B, const PredictArgs &PA, const UpdateArgs &U, const RngArgs &rng,
+                                  const WeightScratch &ws, const PerParticle &ppa, bool no_special) {
+    return launch_update_any(st, B, PA, U, rng, ws, ppa, no_special, true);
 }
 
 // K iterations in one launch (kernels.h: PersistArgs): kPersistStride x (tiles + 1 helper) workgroups, of which every
@@ -6365,7 +6415,7 @@ static void launch_joint_finish(hipStream_t st, const Buffers &B, const WeightSc
     hipLaunchKernelGGL(joint_finish_kernel, dim3((size + kBlock - 1) / kBlock), dim3(kBlock), 0, st, B, ws, J);
 }
 
-static const KernelTable kTable = {launch_update, launch_update_any, launch_update_persist, launch_resample, launch_resample_ref, launch_scan, launch_gather, launch_flatten, launch_identity, launch_decompact, launch_finish, launch_predict, launch_estimate, launch_jacobians, launch_kat, launch_observe, launch_observe_book, launch_associate,
+static const KernelTable kTable = {launch_update, launch_update_particle, launch_update_persist, launch_resample, launch_resample_ref, launch_scan, launch_gather, launch_flatten, launch_identity, launch_decompact, launch_finish, launch_predict, launch_estimate, launch_jacobians, launch_kat, launch_observe, launch_observe_book, launch_associate,
                                    launch_shard_plan, launch_shard_pack, launch_shard_unpack, launch_shard_finish, launch_dist_gather, launch_dist_flags, launch_peek, launch_lmk_box, launch_assoc_grid, launch_assoc_lists, launch_vote_compact,
                                    launch_associate_grid, launch_jacobians_multi, launch_pp_census, launch_pp_resolve, launch_pp_holders,
                                    launch_pp_resample, launch_pp_gather, launch_pp_book,

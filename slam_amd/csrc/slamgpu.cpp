@@ -584,6 +584,7 @@ int slamgpu_create(const slamgpu_config *cfg, slamgpu_ctx **out) {
     }
     c->persist_ok = getenv("SLAMGPU_NO_PERSIST") == nullptr;                               // diagnostic / tests: slamgpu_run_observe as a loop of launches
     c->special_ok = getenv("SLAMGPU_NO_SPECIAL") == nullptr;                               // diagnostic / tests: kernels.h: update_special
+    c->counted_ok = getenv("SLAMGPU_NO_COUNTED") == nullptr;                               // diagnostic / tests: kernels.h: update_counted
     if (const char *e = getenv("SLAMGPU_CONSOLIDATE_ABOVE")) c->consolidate_above = atoi(e);
     if (const char *e = getenv("SLAMGPU_PLAIN_ROWS_TARGET")) c->plain_rows_target = atoi(e);
     const bool want_stamps = getenv("SLAMGPU_STAMPS") != nullptr;                         // diagnostic
@@ -954,7 +955,10 @@ int issue_update(slamgpu_ctx *c, UpdateArgs &U, int n_new, int n_rows, bool need
     } else {
         Timed t(c, c->cfg.method == SLAMGPU_FASTSLAM2 ? "fs2_update" : "fs1_update");
         if (c->pp_launch) c->k->update_particle(c->stream, c->B, PA, U, rng, c->ws, *c->pp_launch, !c->special_ok);
-        else if (c->k->update(c->stream, c->B, PA, U, rng, c->ws, !c->special_ok) != 0) c->special_launches++;
+        else if (const int spec = c->k->update(c->stream, c->B, PA, U, rng, c->ws, !c->special_ok, !c->counted_ok); spec != 0) {
+            c->special_launches++;
+            c->counted_launches[update_counted(spec, U.m, U.front.on != 0, !c->counted_ok)]++;
+        }
     }
     HIP_TRY(hipGetLastError());
     c->slot ^= 1;   // ... and where it left the set (Ctrl.live / pend of the other slot)
@@ -4321,6 +4325,14 @@ int slamgpu_update_special_launches(slamgpu_ctx *c, int64_t *count) {
     if (int rc = check_ctx(c)) return rc;
     if (!count) return fail(SLAMGPU_ERR_INVALID, "slamgpu_update_special_launches: count is null");
     *count = c->special_launches;
+    return 0;
+}
+
+int slamgpu_update_counted_launches(slamgpu_ctx *c, int64_t out[9]) {
+    static_assert(kCountedMax + 1 == 9, "slamgpu.h: slamgpu_update_counted_launches");
+    if (int rc = check_ctx(c)) return rc;
+    if (!out) return fail(SLAMGPU_ERR_INVALID, "slamgpu_update_counted_launches: out is null");
+    for (int m = 0; m <= kCountedMax; m++) out[m] = c->counted_launches[m];
     return 0;
 }
 

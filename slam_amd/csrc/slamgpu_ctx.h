@@ -253,6 +253,8 @@ struct slamgpu_ctx {
     // persistent small-N step loop (slamgpu_run_observe, kernels.h: PersistArgs)
     bool persist_ok = true;              // SLAMGPU_NO_PERSIST=1 turns it off (diagnostic / tests: the per-step loop)
     bool special_ok = true;              // SLAMGPU_NO_SPECIAL=1 turns it off (diagnostic / tests: update_kernel's general instantiation for every launch)
+    bool counted_ok = true;              // SLAMGPU_NO_COUNTED=1 turns it off (diagnostic / tests: never update_kernel_counted)
+    int64_t counted_launches[kCountedMax + 1] = {};  // specialised launches by counted instantiation, [0]: the plain specialised kernel (slamgpu_update_counted_launches: tests)
     int64_t special_launches = 0;        // update launches that took a specialised instantiation (slamgpu_update_special_launches: tests)
     struct PersistCollect {              // while set, issue_update queues its launch instead of making it
         std::vector<PersistStep> steps;

@@ -5,9 +5,19 @@
 // in for them in an iteration); the macros STEP_WPAR (ws.wpar; update_kernel_special: its template parameter WPAR), STEP_PLAN (U.plan_inline != 0) and STEP_FRONT (U.front), which a per-step
 // launch reads in place (a local copy of each costs the distributed variants a scalar register they do not have); qe (LDS copy of the iteration's queue
 // entry, PERSIST only); carry (StepCarry, PERSIST only); SPEC (kernels.h: UpdateModes; 0 everywhere but in update_kernel's specialised
-// instantiations: every `SPECIAL ? SM.x : <run-time test>` below is then the run-time test it has always been).
+// instantiations: every `SPECIAL ? SM.x : <run-time test>` below is then the run-time test it has always been); STEP_COUNT (optional macro:
+// update_kernel_counted's template parameter, the packet's number of re-observed landmarks U.m as the launcher knows it, 1 .. kStage).
     constexpr bool ARR = MODE == 1, DIST = MODE == 2;
     constexpr bool SPECIAL = SPEC != 0;
+#ifdef STEP_COUNT
+    constexpr int CNT = STEP_COUNT;
+#else
+    constexpr int CNT = 0;
+#endif
+    // counted launches (CNT = U.m, compiled in): the CNT records stay in registers from their loads through both passes -- no staging
+    // in LDS, no clamped duplicate loads, no loop control (the launcher sizes the dynamic LDS without staging slots)
+    constexpr bool COUNTED = CNT > 0;
+    static_assert(!COUNTED || (SPECIAL && CNT <= kStage), "counted: a specialised step with 1 .. kStage re-observed landmarks");
     [[maybe_unused]] constexpr UpdateModes SM = kUpdateSpecs[SPEC];
     static_assert(!SPECIAL || (!PERSIST && !BIG && MODE == 0 && !PP), "specialised: update_kernel<2, 0, false> only");
     static_assert(!PERSIST || (MODE == 0 && !BIG), "the persistent loop: compact single contexts");
@@ -48,7 +58,7 @@
     const size_t win_bytes = lay_plan ? update_window_bytes() : 0;
     float *const win = wins + (threadIdx.x / kWave) * (kWinBlocks * kBlock);  // this wave's window
     float4 *const shA = reinterpret_cast<float4 *>(dyn_lds + off_bytes + win_bytes);
-    const int nslots = staging_slots(METHOD, BIG, U.m);
+    const int nslots = COUNTED ? 0 : staging_slots(METHOD, BIG, U.m);
     float *const shB = reinterpret_cast<float *>(dyn_lds + off_bytes + win_bytes + (size_t) nslots * kBlock * sizeof(float4));
     // per-particle association (PP): behind the staged records, the particle's observation index of every staged entry and -- when
     // they fit -- the step's observations themselves (a load from global memory inside the passes' bodies makes the wave wait for
@@ -395,7 +405,7 @@
     float4 *__restrict__ poseBo = out ? B.poseB[1] : B.poseB[0];
     float2 *__restrict__ poseCo = out ? B.poseC[1] : B.poseC[0];
     const bool active = i < B.n;
-    int m = U.m, n = U.n, nf = U.nf, e_new = U.e_new;
+    int m = COUNTED ? CNT : U.m, n = U.n, nf = U.nf, e_new = U.e_new;
     int live_chunks = U.live_chunks, n_cons = U.n_cons;
     bool all_fresh = U.all_fresh != 0;
     if constexpr (!BIG && MODE == 0) {
@@ -643,7 +653,11 @@
         // the source slot, so the records are one round trip behind the pose, not two
         int ts[kStage];
         const bool early_records = !BIG && m > 0 && all_fresh;
-        if (!BIG) {
+        if constexpr (COUNTED) {
+#pragma unroll
+            for (int k = 0; k < CNT; k++) ts[k] = all_fresh ? si : slot_of(k);
+            if (early_records) issue_records(std::integral_constant<int, CNT>{}, ts);  // (m = CNT: exactly CNT loads, no clamp left)
+        } else if (!BIG) {
 #pragma unroll
             for (int k = 0; k < kStage; k++) ts[k] = all_fresh ? (DIST ? gsrc : si) : slot_of(min(k, max(m - 1, 0)));
             if (early_records) {  // fresh landmarks: the record sits in the source slot: requested with the pose
@@ -787,6 +801,13 @@
                 };
                 if constexpr (BIG) {
                     pipeline(first_pass);
+                } else if constexpr (COUNTED) {
+                    if (!early_records) issue_records(std::integral_constant<int, CNT>{}, ts);
+#pragma unroll
+                    for (int k = 0; k < CNT; k++) {
+                        if (k == 0) SLAM_STAMP(5);  // records arrived
+                        first_pass(k, sta[k], stb[k]);
+                    }
                 } else {
                     stage_landmarks(ts, early_records);
                     for (int k = 0; k < m; k++) {
@@ -830,6 +851,9 @@
                 };
                 if constexpr (BIG) {
                     pipeline(second_pass);
+                } else if constexpr (COUNTED) {
+#pragma unroll
+                    for (int k = 0; k < CNT; k++) second_pass(k, sta[k], stb[k]);
                 } else {
                     const int ms = min(m, kStage);
                     // (two landmarks per basic block, as FastSLAM 1's pair_pass below, was measured here in round 4: 14.180
@@ -957,6 +981,10 @@
                 };
                 if constexpr (BIG) {
                     pipeline(first_pass);
+                } else if constexpr (COUNTED) {
+                    if (!early_records) issue_records(std::integral_constant<int, CNT>{}, ts);
+#pragma unroll
+                    for (int k = 0; k < CNT; k++) first_pass(k, sta[k], stb[k]);
                 } else {
                     stage_landmarks(ts, early_records);
                     for (int k = 0; k < m; k++) {
@@ -1004,6 +1032,9 @@
                 // store to land (a global load after a global store costs an s_waitcnt vmcnt(0) per iteration)
                 if constexpr (BIG) {
                     pipeline(second_pass);
+                } else if constexpr (COUNTED) {
+#pragma unroll
+                    for (int k = 0; k < CNT; k++) second_pass(k, sta[k], stb[k]);
                 } else {
                     const int ms = min(m, kStage);
                     for (int k = 0; k < ms; k++) second_pass(k, shA[(k) * kBlock + threadIdx.x], shB[(k) * kBlock + threadIdx.x]);
