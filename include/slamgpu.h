@@ -737,6 +737,22 @@ int slamgpu_pose_history_fetch(slamgpu_ctx *ctx, int64_t first, int32_t count, d
 #define SLAMGPU_INNOV_STRIDE 10
 int slamgpu_innovation_summary(slamgpu_ctx *ctx, const float *zf, const int32_t *idf, int32_t m, const float R[4],
                                double *out /* [m][SLAMGPU_INNOV_STRIDE] */, int32_t *holders /* [m], may be NULL */);
+/* The per-particle form, for contexts whose particles each act on their own association (SLAMGPU_FLAG_PARTICLE_MAPS;
+ * slamgpu_update_particle, slamgpu_update_labels): labels[i * nz + q] is the slot particle i matched observation q to, i the particle's
+ * place in the set as slamgpu_peek shows it, z[2q], z[2q + 1] the observation.  A label is a slot in [0, slamgpu_num_landmarks),
+ * SLAMGPU_ASSOC_NEW or SLAMGPU_ASSOC_DISCARD, exactly what slamgpu_particle_labels returns.  H_q is the set of particles whose label l
+ * for q is a slot, that hold slot l (record not absent) with d2 > 0; NEW and DISCARD put a particle outside H_q.  Entry q is the entry
+ * above with every particle of H_q measured against ITS OWN slot: share, moments, S and NIS by the same formula in the same order, the
+ * same set, weights, sums and guarantees (the same bits on every call, under a pending gather or after slamgpu_download; an
+ * observation's entry does not depend on its place, on the other observations or on the chunking; read-only; synchronises), and
+ * holders[q] = |H_q|, exact.  Nobody matched q: share 0, holders 0, entries 1..9 NaN.  With labels[i * nz + q] = idf[q] for every i the
+ * entries are bit for bit slamgpu_innovation_summary's.  Every label >= 0 counts, a second claim of one particle on one slot under two
+ * observations included: the call does not ask how the labels came about (with slamgpu_set_particle_mutex on, the gates produce no
+ * second claims).  SLAMGPU_ERR_INVALID, outputs untouched: a label outside [-2, slamgpu_num_landmarks), a context without
+ * SLAMGPU_FLAG_PARTICLE_MAPS, nz < 0, NULL z / labels / R / out with nz > 0, a distributed or shard context.  nz == 0 does nothing.
+ * The labels travel through pinned memory of the context's own, a piece at a time. */
+int slamgpu_innovation_summary_labels(slamgpu_ctx *ctx, const float *z, int32_t nz, const int32_t *labels /* host, [N][nz] */,
+                                      const float R[4], double *out /* [nz][SLAMGPU_INNOV_STRIDE] */, int32_t *holders /* [nz], may be NULL */);
 /* The same entries kept on the device: a ring counted in OBSERVATION entries (m varies from step to step), not in steps.  Entries
  * are numbered from 0 when the ring is enabled and never renumbered; entries [first, next) are retained; a full ring drops its
  * oldest entries and never refuses a step.  slamgpu_innovation_history_enable: capacity > 0 (in entries) starts or restarts (entries
@@ -749,15 +765,22 @@ int slamgpu_innovation_summary(slamgpu_ctx *ctx, const float *zf, const int32_t 
  * records = calls counted so far.  slamgpu_innovation_history_fetch: entries [first, first + count) into
  * out[count][SLAMGPU_INNOV_STRIDE], record[count], slot[count] (each may be NULL), non-consuming; synchronises; entries outside the
  * retained range or a negative count: SLAMGPU_ERR_INVALID, outputs untouched; count == 0 does nothing.
- * slamgpu_step records by itself while the ring is on, between its predicts and its update, with its own zf / idf / m / R (a packet
- * larger than the ring: SLAMGPU_ERR_CAPACITY before anything of the step is applied); callers
- * of slamgpu_predict + slamgpu_update call slamgpu_innovation_record themselves, before the update.  slamgpu_step_observe,
- * slamgpu_run_observe and slamgpu_run_particle are NOT recorded: their packets are made on the device and never exist on the host.
+ * Three entry points record by themselves while the ring is on.  slamgpu_step: between its predicts and its update, with its own
+ * zf / idf / m / R (a packet larger than the ring: SLAMGPU_ERR_CAPACITY before anything of the step is applied).
+ * slamgpu_update_particle and slamgpu_update_labels: the nz entries of slamgpu_innovation_summary_labels, entry next + q for
+ * observation q whether anybody matched it or not, from the step's FINAL labels (after mutual exclusion, sampling, the exclusion rule
+ * and the spacing cap: the labels slamgpu_particle_labels returns after the call) and the records as they stand before the update,
+ * enqueued between the association and the update launch; tags `record` as above and `slot` = SLAMGPU_INNOV_SLOT_PER_PARTICLE;
+ * nz == 0 counts a record and appends nothing; nz > capacity: SLAMGPU_ERR_CAPACITY with the context bit for bit as it was.
+ * Callers of slamgpu_predict + slamgpu_update call slamgpu_innovation_record themselves, before the update.  slamgpu_step_observe,
+ * slamgpu_run_observe and slamgpu_run_particle are NOT recorded: their packets (and slamgpu_run_particle's nz) are made on the device
+ * and never exist on the host.
  * While the ring is on the path recorder's rule holds for slamgpu_step: the outstanding resampling stage is run and the predicts
  * are flushed before the record, as launches of their own.  The two routes are bit for bit equivalent: every pose, record, weight,
- * history entry and ancestor of a run is that of the same run with the ring off.  slamgpu_upload keeps the retained entries.
+ * history entry, label, report and ancestor of a run is that of the same run with the ring off.  slamgpu_upload keeps the retained entries.
  * Single contexts only.  With the ring never enabled and slamgpu_innovation_summary never called nothing is allocated and no kernel
  * of it is launched.  What it costs: DESIGN.md section 7f. */
+#define SLAMGPU_INNOV_SLOT_PER_PARTICLE (-3) /* the `slot` tag of an entry in which every particle has its own slot */
 int slamgpu_innovation_history_enable(slamgpu_ctx *ctx, int32_t capacity);
 int slamgpu_innovation_record(slamgpu_ctx *ctx, const float *zf, const int32_t *idf, int32_t m, const float R[4]);
 int slamgpu_innovation_history_info(slamgpu_ctx *ctx, int64_t *first, int64_t *next, int32_t *capacity, int64_t *records);

@@ -34,13 +34,14 @@ DECLARED_SYMBOLS = [
     "slamgpu_path_enable", "slamgpu_path_record", "slamgpu_path_info", "slamgpu_path_fetch", "slamgpu_path_trace", "slamgpu_path_summary",
     "slamgpu_pose_summary", "slamgpu_pose_history_enable", "slamgpu_pose_history_record", "slamgpu_pose_history_info",
     "slamgpu_pose_history_fetch",
-    "slamgpu_innovation_summary", "slamgpu_innovation_history_enable", "slamgpu_innovation_record", "slamgpu_innovation_history_info",
+    "slamgpu_innovation_summary", "slamgpu_innovation_summary_labels", "slamgpu_innovation_history_enable", "slamgpu_innovation_record", "slamgpu_innovation_history_info",
     "slamgpu_innovation_history_fetch",
 ]
 MAP_STRIDE = 9  # SLAMGPU_MAP_STRIDE
 PATH_STRIDE = 7  # SLAMGPU_PATH_STRIDE
 POSE_STRIDE = 18  # SLAMGPU_POSE_STRIDE
 INNOV_STRIDE = 10  # SLAMGPU_INNOV_STRIDE
+INNOV_SLOT_PER_PARTICLE = -3  # SLAMGPU_INNOV_SLOT_PER_PARTICLE
 ASSOC_AUTO, ASSOC_EXHAUSTIVE, ASSOC_GRID, ASSOC_LISTS = 0, 1, 2, 3
 FLAG_DEVICE_OBSERVE = 1
 FLAG_NO_REFERENCE_RESAMPLE = 2
@@ -170,6 +171,8 @@ def load_library():
         L.slamgpu_innovation_history_info.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32),
                                                       C.POINTER(C.c_int64)]
         L.slamgpu_innovation_history_fetch.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+    if hasattr(L, "slamgpu_innovation_summary_labels"):
+        L.slamgpu_innovation_summary_labels.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     if hasattr(L, "slamgpu_path_enable"):
         L.slamgpu_path_enable.argtypes = [C.c_void_p, C.c_int32]
         L.slamgpu_path_record.argtypes = [C.c_void_p]
@@ -709,6 +712,20 @@ class SlamGpu:
         out = np.zeros((m, INNOV_STRIDE), np.float64)
         holders = np.zeros(m, np.int32)
         _chk(self.L.slamgpu_innovation_summary(self.h, _ptr(zf), _ptr(idf), m, _ptr(_f32(R, 4)), _ptr(out), _ptr(holders)))
+        return out, holders
+
+    def innovation_summary_labels(self, z, labels, R):
+        """slamgpu_innovation_summary_labels: innovation_summary with every particle measured against its own slot: z[nz, 2] range /
+        bearing, labels[N, nz] as particle_labels() returns them (a slot, ASSOC_NEW or ASSOC_DISCARD; N the particles in peek() order):
+        (out[nz, 10] float64, holders[nz] int32); contexts with FLAG_PARTICLE_MAPS; rewrites no state"""
+        z = _f32(z).reshape(-1, 2)
+        nz = len(z)
+        labels = np.ascontiguousarray(labels, np.int32)
+        if labels.size != self.N * nz:
+            raise ValueError("innovation_summary_labels: %d labels for %d particles x %d observations" % (labels.size, self.N, nz))
+        out = np.zeros((nz, INNOV_STRIDE), np.float64)
+        holders = np.zeros(nz, np.int32)
+        _chk(self.L.slamgpu_innovation_summary_labels(self.h, _ptr(z), nz, _ptr(labels), _ptr(_f32(R, 4)), _ptr(out), _ptr(holders)))
         return out, holders
 
     def innovation_history_enable(self, capacity):

@@ -56,6 +56,7 @@
 //                        printed at the end: the entries summarised and retained, the mean NIS of the predicted-measurement mixture
 //                        (slamhost_innovation_nis), the share of entries with NIS <= 5.9915, the mean per-particle NIS, the mean share and
 //                        the entries without a NIS.  Needs no ground truth.  Known association or -assoc gated, one GPU, host-made packets
+//                        (the library records -assoc particle's steps too, slamgpu_innovation_summary_labels; this driver does not offer it yet)
 //   -pose none|posterior posterior: the pose posterior of every observation step is kept (slamgpu_pose_history_*; -POSE_RECORDS n entries,
 //                        default 4096), and one more line is printed at the end: the entries kept, the mean distance of the WEIGHTED mean to the
 //                        true position beside that of the filtered estimates of the same steps, the mean NEES of the pose against the true pose
@@ -826,8 +827,12 @@ int main(int argc, char **argv) {
             if (g_innov_records <= 0) why = "-INNOVATION_RECORDS needs a positive number of entries";
             else if (sim.conf.method == 0) why = "FastSLAM only (the EKF's innovation covariance is its own S)";
             else if (!gp.empty() && atoi(gp.c_str()) != 1) why = "single GPU only (slamgpu_innovation_* have no distributed form)";
-            else if (sim.conf.s("observe") == "device") why = "not with -observe device (its packets are made on the device and never exist on the host)";
-            else if (sim.conf.s("assoc") == "particle") why = "not with -assoc particle (every particle has its own labels; the packet has one slot per observation)";
+            else if (sim.conf.s("observe") == "device")
+                why = "not with -observe device (its observations are made on the device and never exist on the host: slamgpu_step_observe, slamgpu_run_observe and "
+                      "slamgpu_run_particle are not recorded)";
+            else if (sim.conf.s("assoc") == "particle")
+                why = "not with -assoc particle yet (slamgpu_update_particle records by itself while the ring is on, one entry per observation with every "
+                      "particle measured against its own match: slamgpu_innovation_summary_labels; this driver does not turn the ring on for it)";
             if (why) {
                 fprintf(stderr, "-innovation posterior: %s\n", why);
                 return EXIT_FAILURE;

@@ -680,17 +680,27 @@ struct PoseSummaryArgs {
 // The tile's sum of weights goes to S.wpart exactly as the map summary's does (one code path: tile_weights / finish_weights).
 // innovation_finish_kernel is map_finish_kernel's pass (the same body) with the extra field; it writes entry q to S.out[q] (staging),
 // or, with ring_cap > 0, to entry (ring_at + q) % ring_cap of the ring S.out with its tags.
+// The per-particle form (slamgpu_innovation_summary_labels, the ring of slamgpu_update_particle / _update_labels) is the same kernel
+// body, innovation_summary_kernel<true>: the slot of observation q is the lane's own, labels[q * lstride + i] for particle i of the
+// set (peek order; BY OBSERVATION, as the per-particle step keeps its labels: a wave reads 64 consecutive words), and only a label
+// inside [0, nf) is ever an index.  The genealogy row is the lane's too: nothing is shared between observations, every lane loads its
+// kMapT labels, then its rows, then its entries, then its records, each batch in flight together.  idf is null then; the ring's slot
+// tag is kInnSlotPerParticle.
 constexpr int kInnStride = 10;             // SLAMGPU_INNOV_STRIDE
+constexpr int kInnSlotPerParticle = -3;    // SLAMGPU_INNOV_SLOT_PER_PARTICLE
 enum { kInnNis = kMapFields, kInnFields };
 struct InnovArgs {
     MapSummaryArgs S;           // count observations of this launch (first_slot is not read); part [tiles][kInnFields][count]; holders may be null
     const float *zf;            // [count][2] range, bearing
-    const int32_t *idf;         // [count] slots, each inside [0, number of slots)
+    const int32_t *idf;         // [count] slots, each inside [0, number of slots); null: per-particle labels
     float r00, r10, r11;        // R[0], R[2], R[3]
     int32_t ring_cap;           // 0: staging
     int64_t ring_at;            // entry number of this launch's first observation
     int32_t *tag;               // [ring_cap][2]: record, slot
     int32_t record;
+    const int32_t *labels;      // per-particle form: [count][lstride], anything outside [0, nf) is "no slot"
+    int64_t lstride;            // ... words between two observations' labels (at least the number of particles)
+    int32_t nf;                 // ... the number of slots
 };
 
 // Joint posterior (slamgpu_joint_summary): over the particle set and with the weights of slamgpu_map_summary, the mean and the
@@ -1058,6 +1068,7 @@ struct KernelTable {
     // slamgpu_innovation_summary / slamgpu_innovation_record (InnovArgs): the partials of one chunk of observations, and their finishing
     // pass into the staging area or the ring.  Tables in sync; reads only
     void (*innovation_summary)(hipStream_t, const Buffers &, const WeightScratch &, const InnovArgs &);
+    void (*innovation_summary_labels)(hipStream_t, const Buffers &, const WeightScratch &, const InnovArgs &);
     void (*innovation_finish)(hipStream_t, const InnovArgs &);
     // slamgpu_joint_summary (JointArgs): joint_hold and joint_pivot once per call, joint_gram and joint_reduce once per chunk of block
     // pairs, joint_finish once.  Tables in sync; all of them read the particle state only

@@ -5901,6 +5901,9 @@ SLAM_DEV bool innov_term(const float4 &pose, const float4 &la, float lb, double 
     return true;
 }
 
+// PP: the slot is the lane's own (kernels.h: InnovArgs::labels), and so are the genealogy row and its entry; a label outside [0, nf)
+// (SLAMGPU_ASSOC_NEW, _DISCARD, anything else) is never an index: the lane keeps the absent record it starts from
+template <bool PP>
 __global__ void __launch_bounds__(kBlock) innovation_summary_kernel(Buffers B, WeightScratch ws, InnovArgs I) {
     constexpr int kWaves = kBlock / kWave;
     __shared__ double sh[kMapSlots][kWaves][kInnFields];
@@ -5927,21 +5930,47 @@ __global__ void __launch_bounds__(kBlock) innovation_summary_kernel(Buffers B, W
     int row = -1;
     int sl[kMapT];
     for (int s = 0; s < sn; s++) {
-        const int l = I.idf[s0 + s];
+        int l = 0;  // (the observation's slot; PP: the lanes have their own)
+        if constexpr (!PP) l = I.idf[s0 + s];
         const double zr = (double) I.zf[2 * (s0 + s)], zb = (double) I.zf[2 * (s0 + s) + 1];
-        const int r = B.erow[l];
-        if (r != row) {  // (uniform) the observations whose slots lie in one genealogy row share its entries
-            row = r;
-#pragma unroll
-            for (int t = 0; t < kMapT; t++) sl[t] = on[t] ? B.gen[cur][gen_index(B.compact, S, r, (size_t) anc[t])] : 0;
-        }
         float4 la[kMapT];
         float lb[kMapT];
+        if constexpr (PP) {
+            // (divergent gathers: every lane's labels, then rows, then entries, then records, each batch requested before any is used)
+            const int32_t *lab = I.labels + (size_t) (s0 + s) * (size_t) I.lstride + (size_t) blockIdx.x * kMapTile + threadIdx.x;
+            int ll[kMapT];
+            bool ok[kMapT];
 #pragma unroll
-        for (int t = 0; t < kMapT; t++) {
-            la[t] = make_float4(NAN, NAN, NAN, NAN);
-            lb[t] = NAN;
-            if (on[t]) read_record(B, B.lmk_live, S, l, sl[t], la[t], lb[t]);
+            for (int t = 0; t < kMapT; t++) ll[t] = on[t] ? lab[t * kBlock] : -1;
+#pragma unroll
+            for (int t = 0; t < kMapT; t++) {
+                ok[t] = (unsigned) ll[t] < (unsigned) I.nf;  // (on[t] included)
+                ll[t] = ok[t] ? ll[t] : 0;
+            }
+            int r[kMapT];
+#pragma unroll
+            for (int t = 0; t < kMapT; t++) r[t] = ok[t] ? B.erow[ll[t]] : 0;
+#pragma unroll
+            for (int t = 0; t < kMapT; t++) sl[t] = ok[t] ? B.gen[cur][gen_index(B.compact, S, r[t], (size_t) anc[t])] : 0;
+#pragma unroll
+            for (int t = 0; t < kMapT; t++) {
+                la[t] = make_float4(NAN, NAN, NAN, NAN);
+                lb[t] = NAN;
+                if (ok[t]) read_record(B, B.lmk_live, S, ll[t], sl[t], la[t], lb[t]);
+            }
+        } else {
+            const int r = B.erow[l];
+            if (r != row) {  // (uniform) the observations whose slots lie in one genealogy row share its entries
+                row = r;
+#pragma unroll
+                for (int t = 0; t < kMapT; t++) sl[t] = on[t] ? B.gen[cur][gen_index(B.compact, S, r, (size_t) anc[t])] : 0;
+            }
+#pragma unroll
+            for (int t = 0; t < kMapT; t++) {
+                la[t] = make_float4(NAN, NAN, NAN, NAN);
+                lb[t] = NAN;
+                if (on[t]) read_record(B, B.lmk_live, S, l, sl[t], la[t], lb[t]);
+            }
         }
         InnovTerm e[kMapT];
         bool hold[kMapT];
@@ -6001,7 +6030,10 @@ __global__ void __launch_bounds__(kBlock) innovation_summary_kernel(Buffers B, W
 __global__ void __launch_bounds__(kBlock) innovation_finish_kernel(InnovArgs I) { summary_finish<true>(I.S, &I); }
 
 static void launch_innovation_summary(hipStream_t st, const Buffers &B, const WeightScratch &ws, const InnovArgs &I) {
-    hipLaunchKernelGGL(innovation_summary_kernel, dim3(I.S.tiles, (I.S.count + kMapSlots - 1) / kMapSlots), dim3(kBlock), 0, st, B, ws, I);
+    hipLaunchKernelGGL(innovation_summary_kernel<false>, dim3(I.S.tiles, (I.S.count + kMapSlots - 1) / kMapSlots), dim3(kBlock), 0, st, B, ws, I);
+}
+static void launch_innovation_summary_labels(hipStream_t st, const Buffers &B, const WeightScratch &ws, const InnovArgs &I) {
+    hipLaunchKernelGGL(innovation_summary_kernel<true>, dim3(I.S.tiles, (I.S.count + kMapSlots - 1) / kMapSlots), dim3(kBlock), 0, st, B, ws, I);
 }
 static void launch_innovation_finish(hipStream_t st, const InnovArgs &I) {
     constexpr int kSlots = kBlock / kMapFinParts;
@@ -6422,7 +6454,8 @@ static const KernelTable kTable = {launch_update, launch_update_particle, launch
                                    launch_lists_box, launch_lists_geom, launch_lists_build, launch_lists_walk, launch_excl_radii,
                                    launch_map_summary, launch_map_finish, launch_map_pairs, launch_pp_missed,
                                    launch_path_compose, launch_path_record, launch_path_trace, launch_path_seed, launch_path_push, launch_path_finish,
-                                   launch_pp_mutex, launch_pose_summary, launch_pose_finish, launch_innovation_summary, launch_innovation_finish,
+                                   launch_pp_mutex, launch_pose_summary, launch_pose_finish, launch_innovation_summary, launch_innovation_summary_labels,
+                                   launch_innovation_finish,
                                    launch_joint_hold, launch_joint_pivot, launch_joint_gram, launch_joint_reduce, launch_joint_finish};
 
 }  // namespace SLAM_KNS

@@ -165,47 +165,138 @@ int innov_check(slamgpu_ctx *c, const char *fn, const float *zf, const int32_t *
     return 0;
 }
 
-// the m entries of the set as slamgpu_peek would show it: into the ring's slots slot(innov.next + q) with their tags (ring), or
-// into the staging area, from where out_dev / hold_dev point at them.  Enqueued; the caller has checked the packet (m > 0)
-int innov_launch(slamgpu_ctx *c, const float *zf, const int32_t *idf, int32_t m, const float *R, bool ring, const double **out_dev,
-                 const int32_t **hold_dev) {
-    static_assert(SLAMGPU_INNOV_STRIDE == kInnStride, "public / device summary layout");
-    static_assert(sizeof c->innov_ev / sizeof c->innov_ev[0] == kInnovStage, "staging slots");
-    if (int rc = summary_enter(c, "", kSettle | kTables)) return rc;
-    const int tiles = map_tiles(c);
-    // the packet goes through the partials' table a chunk at a time, capped as the map summary's is
-    const size_t M = (size_t) m, per_obs = sizeof(double) * kInnFields * (size_t) tiles;
-    const int chunk = chunk_fit("SLAMGPU_INNOV_CHUNK", per_obs, kMapSlots, m);
-    Layout L;
-    const auto out = L.take<double>(kInnStride * M), wpart = L.take<double>(2 * (size_t) tiles), part = L.take<double>(kInnFields * (size_t) tiles * chunk);
-    const auto zf_d = L.take<float>(2 * M);
-    const auto idf_d = L.take<int32_t>(M), hold = L.take<int32_t>(M);
-    if (int rc = c->msum.reserve(L.total())) return rc;
-    // the packet: through a pinned slot of the context's own, so that the caller's arrays are free again when the call returns
-    if (M > c->innov_host_m) {
-        for (int k = 0; k < kInnovStage; k++)
-            if (c->innov_ev_used[k]) HIP_TRY(hipEventSynchronize(c->innov_ev[k]));
-        if (c->innov_host) (void) hipHostFree(c->innov_host);
-        c->innov_host = nullptr;
-        c->innov_host_m = 0;
-        const size_t want = std::max<size_t>(M, 64);
-        hipError_t e = hipHostMalloc((void **) &c->innov_host, 12 * want * kInnovStage, hipHostMallocDefault);
+// what slamgpu_innovation_summary_labels refuses (outputs untouched); nz > 0 on return 0
+int innov_labels_check(slamgpu_ctx *c, const char *fn, const float *z, int32_t nz, const int32_t *labels, const float *R) {
+    if (!(c->cfg.flags & SLAMGPU_FLAG_PARTICLE_MAPS)) return fail(SLAMGPU_ERR_INVALID, "%s: create the context with SLAMGPU_FLAG_PARTICLE_MAPS", fn);
+    if (nz < 0) return fail(SLAMGPU_ERR_INVALID, "%s: nz %d", fn, nz);
+    if (nz == 0) return 0;
+    if (!z || !labels || !R) return fail(SLAMGPU_ERR_INVALID, "%s: null %s", fn, !z ? "z" : !labels ? "labels" : "R");
+    if (int rc = summary_enter(c, fn, kDevice | kBook)) return rc;
+    const size_t count = (size_t) c->B.n * (size_t) nz;
+    for (size_t k = 0; k < count; k++)
+        if (labels[k] < SLAMGPU_ASSOC_DISCARD || labels[k] >= c->nf)
+            return fail(SLAMGPU_ERR_INVALID, "%s: label %d of particle %d, observation %d outside [%d, %d)", fn, (int) labels[k], (int) (k / (size_t) nz),
+                        (int) (k % (size_t) nz), SLAMGPU_ASSOC_DISCARD, c->nf);
+    return 0;
+}
+
+// the caller's labels [N][nz] into dst [nz][N] (by observation, as the kernel reads them), through two pinned pieces in turn: a piece is
+// a stretch of dst, filled here and copied down while the next one is being filled
+// What this costs, and is sized for (nz in the tens): the caller's labels are read twice with the host's caches to help -- once by
+// innov_labels_check, once here with a stride of nz words -- and their N x nz words on the device come out of the summaries' shared
+// arena, which only grows: a call with a large N x nz keeps that room for the context's life, and the call that grows the arena pays
+// the synchronisation of its hipFree.
+constexpr size_t kInnovLabPiece = (size_t) 1 << 18;  // words
+int innov_labels_down(slamgpu_ctx *c, const int32_t *labels, int32_t nz, int32_t *dst) {
+    static_assert(sizeof c->innov_lab_ev / sizeof c->innov_lab_ev[0] == 2, "two pieces");
+    if (!c->innov_lab_host) {
+        hipError_t e = hipHostMalloc((void **) &c->innov_lab_host, sizeof(int32_t) * 2 * kInnovLabPiece, hipHostMallocDefault);
         if (e != hipSuccess) {
             (void) hipGetLastError();
-            c->innov_host = nullptr;
-            return fail(SLAMGPU_ERR_ALLOC, "hipHostMalloc(%zu): %s", 12 * want * kInnovStage, hipGetErrorString(e));
+            c->innov_lab_host = nullptr;
+            return fail(SLAMGPU_ERR_ALLOC, "hipHostMalloc(%zu): %s", sizeof(int32_t) * 2 * kInnovLabPiece, hipGetErrorString(e));
         }
-        c->innov_host_m = want;
     }
-    const int k = (int) (c->innov_seq++ % kInnovStage);
-    if (!c->innov_ev[k]) HIP_TRY(hipEventCreateWithFlags(&c->innov_ev[k], hipEventDisableTiming));
-    if (c->innov_ev_used[k]) HIP_TRY(hipEventSynchronize(c->innov_ev[k]));
-    char *h = c->innov_host + 12 * c->innov_host_m * (size_t) k;
-    memcpy(h, zf, sizeof(float) * 2 * M);
-    memcpy(h + sizeof(float) * 2 * M, idf, sizeof(int32_t) * M);
-    HIP_TRY(hipMemcpyAsync(zf_d.at(c->msum), h, 12 * M, hipMemcpyHostToDevice, c->stream));  // (zf | idf: adjacent in both places)
-    HIP_TRY(hipEventRecord(c->innov_ev[k], c->stream));
-    c->innov_ev_used[k] = true;
+    const size_t N = (size_t) c->B.n, total = N * (size_t) nz;
+    size_t q = 0, i = 0;  // dst[at] = labels of observation q, particle i
+    for (size_t at = 0; at < total; at += kInnovLabPiece) {
+        const int k = (int) (c->innov_lab_seq++ & 1);
+        if (!c->innov_lab_ev[k]) HIP_TRY(hipEventCreateWithFlags(&c->innov_lab_ev[k], hipEventDisableTiming));
+        if (c->innov_lab_ev_used[k]) HIP_TRY(hipEventSynchronize(c->innov_lab_ev[k]));
+        int32_t *h = c->innov_lab_host + kInnovLabPiece * (size_t) k;
+        const size_t n = std::min(kInnovLabPiece, total - at);
+        for (size_t d = 0; d < n; d++) {
+            h[d] = labels[i * (size_t) nz + q];
+            if (++i == N) i = 0, q++;
+        }
+        HIP_TRY(hipMemcpyAsync(dst + at, h, sizeof(int32_t) * n, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipEventRecord(c->innov_lab_ev[k], c->stream));
+        c->innov_lab_ev_used[k] = true;
+    }
+    return 0;
+}
+
+// what a launch summarises: a packet of the host's with one slot per observation (zf, idf), or observations with every particle's own
+// slot -- the caller's (zf, labels [N][m]) or the per-particle step's own, on the device already (z_dev, lab_dev [m][lstride])
+struct InnovPacket {
+    const float *zf = nullptr;
+    const int32_t *idf = nullptr;
+    const int32_t *labels = nullptr;
+    const float *z_dev = nullptr;
+    const int32_t *lab_dev = nullptr;
+    int64_t lstride = 0;
+    int32_t nf = 0;  // (per-particle) the slots a label may name
+    bool per_particle() const { return !idf; }
+};
+
+// the staging area of m entries: the layout, and the chunk its table of partials takes
+struct InnovLayout {
+    Layout L;
+    int tiles, chunk;
+    Layout::Field<double> out, wpart, part;
+    Layout::Field<float> zf;
+    Layout::Field<int32_t> idf, hold, lab;
+};
+InnovLayout innov_layout(const slamgpu_ctx *c, int32_t m, size_t label_words) {
+    InnovLayout V;
+    V.tiles = map_tiles(c);
+    // the packet goes through the partials' table a chunk at a time, capped as the map summary's is
+    const size_t M = (size_t) m, per_obs = sizeof(double) * kInnFields * (size_t) V.tiles;
+    V.chunk = chunk_fit("SLAMGPU_INNOV_CHUNK", per_obs, kMapSlots, m);
+    V.out = V.L.take<double>(kInnStride * M), V.wpart = V.L.take<double>(2 * (size_t) V.tiles);
+    V.part = V.L.take<double>(kInnFields * (size_t) V.tiles * V.chunk);
+    V.zf = V.L.take<float>(2 * M);
+    V.idf = V.L.take<int32_t>(M), V.hold = V.L.take<int32_t>(M);
+    V.lab = V.L.take<int32_t>(label_words);
+    return V;
+}
+
+// the m entries of the set as slamgpu_peek would show it: into the ring's slots slot(innov.next + q) with their tags (ring), or
+// into the staging area, from where out_dev / hold_dev point at them.  Enqueued; the caller has checked the packet (m > 0)
+int innov_launch(slamgpu_ctx *c, const InnovPacket &P, int32_t m, const float *R, bool ring, const double **out_dev, const int32_t **hold_dev) {
+    static_assert(SLAMGPU_INNOV_STRIDE == kInnStride && SLAMGPU_INNOV_SLOT_PER_PARTICLE == kInnSlotPerParticle, "public / device summary layout");
+    static_assert(sizeof c->innov_ev / sizeof c->innov_ev[0] == kInnovStage, "staging slots");
+    if (int rc = summary_enter(c, "", kSettle | kTables)) return rc;
+    const size_t M = (size_t) m;
+    const InnovLayout V = innov_layout(c, m, P.labels ? M * (size_t) c->B.n : 0);
+    const int tiles = V.tiles, chunk = V.chunk;
+    if (int rc = c->msum.reserve(V.L.total())) return rc;
+    const float *z_dev = P.z_dev;
+    if (P.zf) {
+        // the packet: through a pinned slot of the context's own, so that the caller's arrays are free again when the call returns
+        if (M > c->innov_host_m) {
+            for (int k = 0; k < kInnovStage; k++)
+                if (c->innov_ev_used[k]) HIP_TRY(hipEventSynchronize(c->innov_ev[k]));
+            if (c->innov_host) (void) hipHostFree(c->innov_host);
+            c->innov_host = nullptr;
+            c->innov_host_m = 0;
+            const size_t want = std::max<size_t>(M, 64);
+            hipError_t e = hipHostMalloc((void **) &c->innov_host, 12 * want * kInnovStage, hipHostMallocDefault);
+            if (e != hipSuccess) {
+                (void) hipGetLastError();
+                c->innov_host = nullptr;
+                return fail(SLAMGPU_ERR_ALLOC, "hipHostMalloc(%zu): %s", 12 * want * kInnovStage, hipGetErrorString(e));
+            }
+            c->innov_host_m = want;
+        }
+        const int k = (int) (c->innov_seq++ % kInnovStage);
+        if (!c->innov_ev[k]) HIP_TRY(hipEventCreateWithFlags(&c->innov_ev[k], hipEventDisableTiming));
+        if (c->innov_ev_used[k]) HIP_TRY(hipEventSynchronize(c->innov_ev[k]));
+        char *h = c->innov_host + 12 * c->innov_host_m * (size_t) k;
+        memcpy(h, P.zf, sizeof(float) * 2 * M);
+        if (P.idf) memcpy(h + sizeof(float) * 2 * M, P.idf, sizeof(int32_t) * M);
+        HIP_TRY(hipMemcpyAsync(V.zf.at(c->msum), h, P.idf ? 12 * M : 8 * M, hipMemcpyHostToDevice, c->stream));  // (zf | idf: adjacent in both places)
+        HIP_TRY(hipEventRecord(c->innov_ev[k], c->stream));
+        c->innov_ev_used[k] = true;
+        z_dev = V.zf.at(c->msum);
+    }
+    const int32_t *lab_dev = P.lab_dev;
+    int64_t lstride = P.lstride;
+    if (P.labels) {
+        if (int rc = innov_labels_down(c, P.labels, m, V.lab.at(c->msum))) return rc;
+        lab_dev = V.lab.at(c->msum);
+        lstride = c->B.n;
+    }
     c->B.slot = c->slot;
     for (int at = 0; at < m; at += chunk) {
         InnovArgs I{};
@@ -214,10 +305,16 @@ int innov_launch(slamgpu_ctx *c, const float *zf, const int32_t *idf, int32_t m,
         A.count = std::min(chunk, m - at);
         A.tiles = tiles;
         A.logw = c->cfg.log_weights;
-        A.part = part.at(c->msum);
-        A.wpart = wpart.at(c->msum);
-        I.zf = zf_d.at(c->msum) + (size_t) 2 * at;
-        I.idf = idf_d.at(c->msum) + at;
+        A.part = V.part.at(c->msum);
+        A.wpart = V.wpart.at(c->msum);
+        I.zf = z_dev + (size_t) 2 * at;
+        if (P.per_particle()) {
+            I.labels = lab_dev + (size_t) lstride * (size_t) at;
+            I.lstride = lstride;
+            I.nf = P.nf;  // (the slots BEFORE the step for its own record, where the step may already have opened new ones: c->nf for the caller's)
+        } else {
+            I.idf = V.idf.at(c->msum) + at;
+        }
         I.r00 = R[0];
         I.r10 = R[2];
         I.r11 = R[3];
@@ -229,14 +326,18 @@ int innov_launch(slamgpu_ctx *c, const float *zf, const int32_t *idf, int32_t m,
             I.tag = c->innov_tag_dev;
             I.record = (int32_t) c->innov_records;
         } else {
-            A.out = out.at(c->msum) + (size_t) kInnStride * at;
-            A.holders = hold.at(c->msum) + at;
+            A.out = V.out.at(c->msum) + (size_t) kInnStride * at;
+            A.holders = V.hold.at(c->msum) + at;
         }
-        if (int rc = launch(c, "innovation_summary", [&] { c->k->innovation_summary(c->stream, c->B, c->ws, I); })) return rc;
+        if (P.per_particle()) {
+            if (int rc = launch(c, "innovation_summary_labels", [&] { c->k->innovation_summary_labels(c->stream, c->B, c->ws, I); })) return rc;
+        } else if (int rc = launch(c, "innovation_summary", [&] { c->k->innovation_summary(c->stream, c->B, c->ws, I); })) {
+            return rc;
+        }
         if (int rc = launch(c, "innovation_finish", [&] { c->k->innovation_finish(c->stream, I); })) return rc;
     }
-    if (out_dev) *out_dev = out.at(c->msum);
-    if (hold_dev) *hold_dev = hold.at(c->msum);
+    if (out_dev) *out_dev = V.out.at(c->msum);
+    if (hold_dev) *hold_dev = V.hold.at(c->msum);
     return 0;
 }
 
@@ -297,9 +398,24 @@ int innov_append(slamgpu_ctx *c, const float *zf, const int32_t *idf, int32_t m,
     if (m > c->innov.cap)
         return fail(SLAMGPU_ERR_CAPACITY, "slamgpu_innovation_record: %d observations, the ring holds %d entries", m, c->innov.cap);
     if (m > 0) {
-        if (int rc = innov_launch(c, zf, idf, m, R, true, nullptr, nullptr)) return rc;
+        InnovPacket P;
+        P.zf = zf, P.idf = idf;
+        if (int rc = innov_launch(c, P, m, R, true, nullptr, nullptr)) return rc;
         c->innov.advance(m);
     }
+    c->innov_records++;
+    return 0;
+}
+
+// the per-particle step's record (do_update_particle, beside its pp_missed): the nz observations in pp_z_dev against the labels in
+// pp_lab_dev, the set and the records as they stand before the update; nf: the slots before the step.  pp_check has seen to the
+// ring's capacity; innov_labels_room, which the entry points call right after pp_check, to the staging area
+int innov_labels_room(slamgpu_ctx *c, int32_t nz) { return c->msum.reserve(innov_layout(c, nz, 0).L.total()); }
+int innov_append_labels(slamgpu_ctx *c, int32_t nz, int32_t nf, const float *R) {
+    InnovPacket P;
+    P.z_dev = c->pp_z_dev, P.lab_dev = c->pp_lab_dev, P.lstride = c->B.ncap, P.nf = nf;
+    if (int rc = innov_launch(c, P, nz, R, true, nullptr, nullptr)) return rc;
+    c->innov.advance(nz);
     c->innov_records++;
     return 0;
 }
@@ -312,6 +428,9 @@ void posterior_release(slamgpu_ctx *c) {
     if (c->innov_tag_dev) (void) hipFree(c->innov_tag_dev);
     if (c->innov_host) (void) hipHostFree(c->innov_host);
     for (hipEvent_t e : c->innov_ev)
+        if (e) (void) hipEventDestroy(e);
+    if (c->innov_lab_host) (void) hipHostFree(c->innov_lab_host);
+    for (hipEvent_t e : c->innov_lab_ev)
         if (e) (void) hipEventDestroy(e);
     if (c->path_rec_dev) (void) hipFree(c->path_rec_dev);
     for (int b = 0; b < 2; b++)
@@ -530,9 +649,27 @@ int slamgpu_innovation_summary(slamgpu_ctx *c, const float *zf, const int32_t *i
     if (!out) return fail(SLAMGPU_ERR_INVALID, "slamgpu_innovation_summary: null output");
     const double *out_dev = nullptr;
     const int32_t *hold_dev = nullptr;
-    if (int rc = innov_launch(c, zf, idf, m, R, false, &out_dev, &hold_dev)) return rc;
+    InnovPacket P;
+    P.zf = zf, P.idf = idf;
+    if (int rc = innov_launch(c, P, m, R, false, &out_dev, &hold_dev)) return rc;
     HIP_TRY(hipMemcpyAsync(out, out_dev, sizeof(double) * kInnStride * (size_t) m, hipMemcpyDeviceToHost, c->stream));
     if (holders) HIP_TRY(hipMemcpyAsync(holders, hold_dev, sizeof(int32_t) * (size_t) m, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+int slamgpu_innovation_summary_labels(slamgpu_ctx *c, const float *z, int32_t nz, const int32_t *labels, const float R[4], double *out, int32_t *holders) {
+    if (int rc = summary_enter(c, "slamgpu_innovation_summary_labels", kCtx | kSingle)) return rc;
+    if (int rc = innov_labels_check(c, "slamgpu_innovation_summary_labels", z, nz, labels, R)) return rc;
+    if (nz == 0) return 0;
+    if (!out) return fail(SLAMGPU_ERR_INVALID, "slamgpu_innovation_summary_labels: null output");
+    const double *out_dev = nullptr;
+    const int32_t *hold_dev = nullptr;
+    InnovPacket P;
+    P.zf = z, P.labels = labels, P.nf = c->nf;
+    if (int rc = innov_launch(c, P, nz, R, false, &out_dev, &hold_dev)) return rc;
+    HIP_TRY(hipMemcpyAsync(out, out_dev, sizeof(double) * kInnStride * (size_t) nz, hipMemcpyDeviceToHost, c->stream));
+    if (holders) HIP_TRY(hipMemcpyAsync(holders, hold_dev, sizeof(int32_t) * (size_t) nz, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return 0;
 }

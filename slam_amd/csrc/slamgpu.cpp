@@ -3186,6 +3186,8 @@ int pp_check(slamgpu_ctx *c, const float *z, int32_t nz, const float R[4], const
         return fail(SLAMGPU_ERR_INVALID, "per-particle association: excl_base, excl_per_m, unique_ratio >= 0");
     if (c->dist || c->cfg.n_particles_global != c->cfg.n_particles || c->pool_used != 0)
         return fail(SLAMGPU_ERR_INVALID, "per-particle association: single contexts only");
+    if (c->innov.cap > 0 && nz > c->innov.cap)  // (refused before anything of the step has moved: its record could not be made)
+        return fail(SLAMGPU_ERR_CAPACITY, "per-particle association: %d observations, the innovation ring holds %d entries", nz, c->innov.cap);
     if (c->mid_compact)
         if (int rc = demote_to_plain(c)) return rc;
     if (c->B.compact)
@@ -3325,6 +3327,8 @@ int do_update_particle(slamgpu_ctx *c, const float *z, int32_t nz, const float R
     // (the records as they stand before the update: the device's tables are still those of sync_tables above)
     pp_missed(c, nf0, c->retired_dev, first_dev, (census_taken || lists_done) && opt->mode == SLAMGPU_ASSOC_LISTS, nullptr);
     HIP_TRY(hipGetLastError());
+    if (c->innov.cap > 0)  // the innovation ring: every particle against its own match, the same records, before the update takes them
+        if (int rc = innov_append_labels(c, nz, nf0, R)) return rc;
     c->obs_step++;
     c->pp_lab_nz = nz;
     // genealogy bookkeeping, as do_update's: every packet entry is written by every particle (updated or copied forward) and moves
@@ -3550,8 +3554,13 @@ int slamgpu_update_particle(slamgpu_ctx *c, const float *z, int32_t nz, const fl
     if (opt->mode < SLAMGPU_ASSOC_AUTO || opt->mode > SLAMGPU_ASSOC_LISTS) return fail(SLAMGPU_ERR_INVALID, "unknown association mode %d", opt->mode);
     if (opt->mode == SLAMGPU_ASSOC_LISTS && nz > kAssocMaxCells * kAssocMaxCells)
         return fail(SLAMGPU_ERR_CAPACITY, "SLAMGPU_ASSOC_LISTS: %d observations in one step (at most %d)", nz, kAssocMaxCells * kAssocMaxCells);
-    if (nz == 0) return 0;  // (no observation, no update: fastslam2wrapper.cpp:84-95)
+    if (nz == 0) {  // (no observation, no update: fastslam2wrapper.cpp:84-95)
+        if (c->innov.cap > 0) c->innov_records++;  // (the innovation ring: a record without entries)
+        return 0;
+    }
     HIP_TRY(hipSetDevice(c->cfg.device));
+    if (c->innov.cap > 0)  // (the innovation ring: room for this step's record, before the association or anything else of the step runs)
+        if (int rc = innov_labels_room(c, nz)) return rc;
     if (int rc = pp_reserve(c, nz, 1)) return rc;
     // data association sampling: the labels drawn, their ratios into the weights (the step's draws follow the host's obs_step: the
     // device-driven state comes back first)
@@ -3583,13 +3592,18 @@ int slamgpu_update_labels(slamgpu_ctx *c, const float *z, int32_t nz, const floa
     if (report) memset(report, 0, sizeof(int32_t) * 8);
     if (int rc = pp_check(c, z, nz, R, opt)) return rc;
     if (nz > 0 && !labels) return fail(SLAMGPU_ERR_INVALID, "slamgpu_update_labels: labels[N * nz]");
-    if (nz == 0) return 0;
+    if (nz == 0) {
+        if (c->innov.cap > 0) c->innov_records++;  // (the innovation ring: a record without entries)
+        return 0;
+    }
     if (int rc = book_pull(c)) return rc;
     const size_t count = (size_t) c->B.n * (size_t) nz;
     for (size_t q = 0; q < count; q++)
         if (labels[q] >= c->nf || labels[q] < SLAMGPU_ASSOC_DISCARD)
             return fail(SLAMGPU_ERR_INVALID, "slamgpu_update_labels: label %d of particle %d, observation %d (%d landmarks)", (int) labels[q], (int) (q / nz), (int) (q % nz), c->nf);
     HIP_TRY(hipSetDevice(c->cfg.device));
+    if (c->innov.cap > 0)  // (the innovation ring: room for this step's record, before the labels go down or anything else of the step runs)
+        if (int rc = innov_labels_room(c, nz)) return rc;
     if (int rc = pp_reserve(c, nz, 1)) return rc;
     c->pp_census_done = false;  // (the caller's labels: nobody has taken their census; never sampled)
     c->pp_lists_done = false;

@@ -248,6 +248,10 @@ struct slamgpu_ctx {
     uint64_t innov_seq = 0;
     hipEvent_t innov_ev[4]{};
     bool innov_ev_used[4]{};
+    int32_t *innov_lab_host = nullptr;  // pinned, two pieces: the labels of slamgpu_innovation_summary_labels on their way down
+    uint64_t innov_lab_seq = 0;
+    hipEvent_t innov_lab_ev[2]{};
+    bool innov_lab_ev_used[2]{};
     bool pp_stage_ran = false;       // slamgpu_run_particle: a pose entry has already run the stage the last iteration left (pose_append)
     unsigned long long *stamps_dev = nullptr;  // diagnostic (SLAMGPU_STAMPS=1 + libslamgpu_stamps.so): UpdateArgs::stamps
     // persistent small-N step loop (slamgpu_run_observe, kernels.h: PersistArgs)
@@ -364,6 +368,8 @@ int path_compose(slamgpu_ctx *c);
 int path_append(slamgpu_ctx *c);
 int pose_append(slamgpu_ctx *c);
 int innov_append(slamgpu_ctx *c, const float *zf, const int32_t *idf, int32_t m, const float *R);
+int innov_labels_room(slamgpu_ctx *c, int32_t nz);
+int innov_append_labels(slamgpu_ctx *c, int32_t nz, int32_t nf, const float *R);
 void posterior_release(slamgpu_ctx *c);  // slamgpu_destroy's share of this layer
 
 #pragma GCC visibility pop

@@ -215,7 +215,7 @@ SLAM_DEV void summary_finish(const MapSummaryArgs &A, const InnovArgs *I) {
         if (I->ring_cap > 0) {  // entry ring_at + s of the ring, with its tags
             at = (size_t) ((I->ring_at + (int64_t) s) % (int64_t) I->ring_cap);
             I->tag[2 * at] = I->record;
-            I->tag[2 * at + 1] = I->idf[s];
+            I->tag[2 * at + 1] = I->idf ? I->idf[s] : kInnSlotPerParticle;
         }
     }
     double *o = A.out + at * kFinStride;
