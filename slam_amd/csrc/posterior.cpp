@@ -1,7 +1,7 @@
 // libslamgpu.so: the posterior summaries (slamgpu_map_*, slamgpu_joint_summary, slamgpu_pose_*, slamgpu_innovation_*, slamgpu_path_*).
 // Every summary reaches the particle set slamgpu_peek shows the same way (summary_enter), cuts its work to the partials' table the
 // same way (chunk_fit), lays its staging area out with one builder (Layout over a DevArena), launches through launch() and keeps its
-// history, where it has one, in a Ring.  slamgpu.cpp calls path_compose, path_append, pose_append and innov_append from its steps.
+// history, where it has one, in a Ring.  slamgpu.cpp and association.cpp call path_compose, path_append, pose_append and innov_append* from their steps.
 #include "slamgpu_ctx.h"
 
 #pragma GCC visibility push(hidden)
@@ -379,11 +379,11 @@ int path_append(slamgpu_ctx *c) {
 // whether it updated) is run here with the iterations' own kernels, as the next iteration would have run it first thing
 int pose_append(slamgpu_ctx *c) {
     HIP_TRY(hipSetDevice(c->cfg.device));
-    if (c->pp_on_device) {
-        if (!c->pp_stage_ran) c->pp_stage_open = true;
+    if (c->as.pp_on_device) {
+        if (!c->as.pp_stage_ran) c->as.pp_stage_open = true;
         if (int rc = pp_dev_flush_predict(c)) return rc;
         if (int rc = pp_dev_stage(c)) return rc;
-        c->pp_stage_ran = true;
+        c->as.pp_stage_ran = true;
     } else {
         if (int rc = summary_enter(c, "", kSettle)) return rc;
     }
@@ -413,7 +413,7 @@ int innov_append(slamgpu_ctx *c, const float *zf, const int32_t *idf, int32_t m,
 int innov_labels_room(slamgpu_ctx *c, int32_t nz) { return c->msum.reserve(innov_layout(c, nz, 0).L.total()); }
 int innov_append_labels(slamgpu_ctx *c, int32_t nz, int32_t nf, const float *R) {
     InnovPacket P;
-    P.z_dev = c->pp_z_dev, P.lab_dev = c->pp_lab_dev, P.lstride = c->B.ncap, P.nf = nf;
+    P.z_dev = c->as.pp_z_dev, P.lab_dev = c->as.pp_lab_dev, P.lstride = c->B.ncap, P.nf = nf;
     if (int rc = innov_launch(c, P, nz, R, true, nullptr, nullptr)) return rc;
     c->innov.advance(nz);
     c->innov_records++;

@@ -1,5 +1,5 @@
-// The context of libslamgpu.so and what its translation units (slamgpu.cpp, posterior.cpp) share.  Private: not installed, and
-// no function declared here is exported (hidden visibility).
+// The context of libslamgpu.so and what its translation units (slamgpu.cpp, association.cpp, posterior.cpp) share.  Private: not
+// installed, and no function declared here is exported (hidden visibility).
 #pragma once
 #define SLAMGPU_EXPERIMENTAL 1  // (the library defines every entry point, the experimental ones included)
 #include "../../include/slamgpu.h"
@@ -61,6 +61,102 @@ struct DevArena {
     size_t bytes = 0;
     int reserve(size_t total);  // (a refused growth leaves it empty)
     void release();
+};
+
+// a typed, grow-only buffer in device memory: cap elements at p.  A refused growth leaves it empty, clears HIP's last error and returns
+// SLAMGPU_ERR_ALLOC with `what` in the text
+int dev_grow(void **p, size_t *cap, size_t n, size_t elem, const char *what, bool zeroed);
+template <typename T>
+struct DevBuf {
+    T *p = nullptr;
+    size_t cap = 0;
+    operator T *() const { return p; }
+    int reserve(size_t n, const char *what) { return n <= cap ? 0 : dev_grow((void **) &p, &cap, n, sizeof(T), what, false); }
+    int reserve_zeroed(size_t n, const char *what) { return n <= cap ? 0 : dev_grow((void **) &p, &cap, n, sizeof(T), what, true); }  // (what a growth adds is new memory: all of it zero)
+    void release() {
+        if (p) (void) hipFree(p);
+        p = nullptr;
+        cap = 0;
+    }
+};
+using DevCounters = DevBuf<unsigned long long>;  // cumulative counters a kernel adds to: allocated zeroed at first use
+
+// The state of the association layer (association.cpp): slamgpu_ctx::as.  association_release frees it.
+struct Assoc {
+    // gated association with the spatial prefilter (slamgpu_associate_ex): per-landmark boxes over all particles, refreshed
+    // for the landmarks written since (box_dirty), and the grid buffers
+    DevBuf<LmkBox> box_dev;
+    std::vector<char> box_dirty;
+    // landmarks the caller has retired from the gated association (slamgpu_retire_landmarks): host flags + the device's bit mask
+    std::vector<char> retired;
+    DevBuf<uint32_t> retired_dev;
+    int n_retired = 0;
+    bool retired_stale = false;      // the host's retired flags have changed since the device's mask was written (retired_upload clears it)
+    DevBuf<int32_t> assoc_ids_dev, cell_start_dev, cell_fill_dev;
+    DevBuf<float4> items_dev;        // [2 cap_items]: kernels.h: AssocGridArgs::items
+    DevBuf<AssocGeom> geom_dev;      // (the partial boxes behind it)
+    int32_t cap_items = 0;
+    DevBuf<float> vote_w_dev;        // AssocGridArgs::vote_w, grown on demand
+    DevBuf<float> assoc_z_dev;       // the observations of an association call / its vote tables: kept between calls (an allocation and a release
+    DevBuf<VoteSlot> assoc_votes_dev;  // per call each), grown on demand: room for assoc_nz_cap observations
+    int assoc_nz_cap = 0;
+    // per-particle association (slamgpu_update_particle / _labels; kernels.h: PerParticle): device scratch, grown on demand
+    DevBuf<int32_t> pp_lab_dev;      // labels BY OBSERVATION, [nz][ncap]
+    DevBuf<int16_t> pp_obs_dev;      // PerParticle::obs [rows][ncap]
+    DevBuf<float> pp_z_dev;          // [2 pp_nz_cap]
+    DevBuf<int32_t> pp_tab_dev;      // [cap_nf] first / uidx | [cap_nf] holders | [pp_nz_cap] news / newk | [pp_nz_cap] idn
+    int pp_nz_cap = 0;
+    DevBuf<float> pp_wf_dev;         // [ncap]
+    DevBuf<uint8_t> pp_any_dev;      // [ncap]
+    std::vector<char> pp_partial;    // slots that NOT every particle opened: the only ones that can lose their last holder (a slot every particle
+                                     // opened is held by every descendant for good): what the holders census counts
+    std::vector<char> pp_dead;       // landmark slots no particle holds any more (their hypotheses died in a resample): out of the
+    std::vector<int32_t> pp_dead_list;  // association (retired) until a later landmark opens them again
+    uint64_t pp_steps = 0;
+    bool pp_census_done = false;     // the association kernel took the census of the labels itself (AssocGridArgs::census_first): pp_census_kernel is skipped
+    bool pp_lists_done = false;      // the step's association went through the lists and left the slots' boxes (pp_missed's box test)
+    const PerParticle *pp_launch = nullptr;  // set around issue_update by do_update_particle: the launch takes update_kernel<.., PP = true>
+    int32_t pp_lab_nz = 0;           // the observations of the last per-particle step (slamgpu_particle_labels); -1: the device-driven iteration's (ObserveOut::nz)
+    // per-particle association driven by the device (slamgpu_run_particle; kernels.h: PpState / PpArgs).  While pp_on_device the
+    // per-particle state (pp_partial, pp_dead, the retired mask, pp_steps, obs_step, nf, the row tables) lives in device memory and the
+    // host's copies are stale; pp_pull (through book_pull / flush_stages) brings it back, pp_push hands it over
+    bool pp_on_device = false;
+    DevBuf<PpState> pp_st_dev;
+    DevBuf<int32_t> pp_words_dev;     // partial | dead | first | hold | uidx | list | dlist [cap_nf each] | news | newk | idn [pp_words_w each]
+    int pp_words_w = 0;
+    DevBuf<char> pp_pkt_dev;          // the update's packet (fixed layout, cap = cap_nf)
+    DevBuf<int32_t> pp_report_dev;    // [kHistCap][8] reports of the iterations not fetched yet
+    int pp_report_n = 0;
+    bool pp_stage_ran = false;        // slamgpu_run_particle: a pose entry has already run the stage the last iteration left (pose_append)
+    bool pp_stage_open = false;       // the previous iteration may have left a resampling stage (the device knows) and no gather has run since
+    double *pp_prev_hist = nullptr;   // ... its history slot and the parity of its weight scratch
+    int pp_prev_par = 0;
+    uint32_t pp_iter = 0;
+    // SLAMGPU_ASSOC_LISTS: cumulative counters (AssocListArgs::lstats; [4]: observations past the host's bound, reported by the next
+    // slamgpu_particle_report_fetch) and whether device-driven iterations have written slots without refreshing their boxes
+    DevCounters lstats_dev;
+    bool box_dev_stale = false;
+    // the exclusion rule's radius capped by the step's observation spacing (slamgpu_set_particle_excl_spacing; 0: off) and the radii of
+    // the last step that made them: excl_rho_dev[0] holds their count (int32), the radii follow from [4]
+    float excl_spacing = 0.0f;
+    DevBuf<int32_t> excl_rho_dev;
+    // data association sampling (slamgpu_set_particle_assoc_sampling): on / off, the ratios of the sampled pairs ([nz][ncap], as
+    // pp_lab_dev; held only while sampling is on) and the cumulative counters (SampleArgs::stats)
+    int32_t das_on = 0;
+    DevBuf<float> das_ratio_dev;
+    DevCounters das_stats_dev;
+    SampleArgs das_step{};  // the sampling arguments of the step being associated (AssocRule::smp points here: particle_rule)
+    // negative information (slamgpu_set_particle_miss; pm_range = 0: off): the factor and the view, the counts of the last step that
+    // made them ([ncap]; pm_have: some step has) and the cumulative counters (PpMissArgs::stats); nothing is allocated while it is off
+    float pm_p = 1.0f, pm_range = 0.0f, pm_front = 0.0f;
+    DevBuf<int32_t> pm_cnt_dev;
+    DevCounters pm_stats_dev;
+    bool pm_have = false;
+    // mutual exclusion for contested landmarks (slamgpu_set_particle_mutex): on / off, the table of who holds which slot
+    // ([cap_nf][ncap] int16, -1 between launches; held only while it is on) and the cumulative counters (PpMutexArgs::stats)
+    int32_t mx_on = 0;
+    DevBuf<int16_t> mx_hold_dev;
+    DevCounters mx_stats_dev;
 };
 
 #pragma GCC visibility pop
@@ -184,41 +280,7 @@ struct slamgpu_ctx {
     ObsPacket *front_pkt_dev = nullptr;
     int front_par = 0;
     bool front_ready = false;
-    // gated association with the spatial prefilter (slamgpu_associate_ex): per-landmark boxes over all particles, refreshed
-    // for the landmarks written since (box_dirty), and the grid buffers
-    LmkBox *box_dev = nullptr;
-    std::vector<char> box_dirty;
-    // landmarks the caller has retired from the gated association (slamgpu_retire_landmarks): host flags + the device's bit mask
-    std::vector<char> retired;
-    uint32_t *retired_dev = nullptr;
-    int n_retired = 0;
-    int32_t *assoc_ids_dev = nullptr, *cell_start_dev = nullptr, *cell_fill_dev = nullptr;
-    // per-particle association (slamgpu_update_particle / _labels; kernels.h: PerParticle): device scratch, grown on demand
-    int32_t *pp_lab_dev = nullptr;   // labels BY OBSERVATION, [nz][ncap]
-    size_t pp_lab_cap = 0;
-    int16_t *pp_obs_dev = nullptr;   // PerParticle::obs [rows][ncap]
-    size_t pp_obs_rows = 0;
-    float *pp_z_dev = nullptr;       // [2 pp_nz_cap]
-    int32_t *pp_tab_dev = nullptr;   // [cap_nf] first / uidx | [cap_nf] holders | [pp_nz_cap] news / newk | [pp_nz_cap] idn
-    int pp_nz_cap = 0;
-    float *pp_wf_dev = nullptr;      // [ncap]
-    uint8_t *pp_any_dev = nullptr;   // [ncap]
-    std::vector<char> pp_partial;    // slots that NOT every particle opened: the only ones that can lose their last holder (a slot every particle
-                                     // opened is held by every descendant for good): what the holders census counts
-    std::vector<char> pp_dead;       // landmark slots no particle holds any more (their hypotheses died in a resample): out of the
-    std::vector<int32_t> pp_dead_list;  // association (retired) until a later landmark opens them again
-    float *vote_w_dev = nullptr;     // AssocGridArgs::vote_w, grown on demand
-    size_t vote_w_cap = 0;
-    float *assoc_z_dev = nullptr;    // the observations of an association call / its vote tables: kept between calls (an allocation and a release
-    VoteSlot *assoc_votes_dev = nullptr;  // per call each), grown on demand
-    int assoc_nz_cap = 0;
-    bool retired_stale = false;      // the host's retired flags have changed since the device's mask was written (retired_upload clears it)
-    uint64_t pp_steps = 0;
-    bool pp_census_done = false;     // the association kernel took the census of the labels itself (AssocGridArgs::census_first): pp_census_kernel is skipped
-    const PerParticle *pp_launch = nullptr;  // set around issue_update by do_update_particle: the launch takes update_kernel<.., PP = true>
-    float4 *items_dev = nullptr;  // [2 cap_items]: kernels.h: AssocGridArgs::items
-    AssocGeom *geom_dev = nullptr;
-    int32_t cap_items = 0;
+    Assoc as;                        // the gated and per-particle association (association.cpp)
     char *peek_dev = nullptr;        // staging of slamgpu_peek, grown on demand
     size_t peek_bytes = 0;
     DevArena msum;                   // staging and partials of the map, pair, innovation and joint summaries
@@ -252,7 +314,6 @@ struct slamgpu_ctx {
     uint64_t innov_lab_seq = 0;
     hipEvent_t innov_lab_ev[2]{};
     bool innov_lab_ev_used[2]{};
-    bool pp_stage_ran = false;       // slamgpu_run_particle: a pose entry has already run the stage the last iteration left (pose_append)
     unsigned long long *stamps_dev = nullptr;  // diagnostic (SLAMGPU_STAMPS=1 + libslamgpu_stamps.so): UpdateArgs::stamps
     // persistent small-N step loop (slamgpu_run_observe, kernels.h: PersistArgs)
     bool persist_ok = true;              // SLAMGPU_NO_PERSIST=1 turns it off (diagnostic / tests: the per-step loop)
@@ -283,52 +344,6 @@ struct slamgpu_ctx {
     int64_t persist_launches = 0, persist_steps = 0;
     EstStage unplanned;           // the last update: resampling stage not run yet
     EstStage unreduced;           // an update whose partials exist (est_part[par]) but are not reduced yet
-    // per-particle association driven by the device (slamgpu_run_particle; kernels.h: PpState / PpArgs).  While pp_on_device the
-    // per-particle state (pp_partial, pp_dead, the retired mask, pp_steps, obs_step, nf, the row tables) lives in device memory and the
-    // host's copies are stale; pp_pull (through book_pull / flush_stages) brings it back, pp_push hands it over
-    bool pp_on_device = false;
-    PpState *pp_st_dev = nullptr;
-    int32_t *pp_words_dev = nullptr;  // partial | dead | first | hold | uidx | list | dlist [cap_nf each] | news | newk | idn [pp_words_w each]
-    int pp_words_w = 0;
-    char *pp_pkt_dev = nullptr;       // the update's packet (fixed layout, cap = cap_nf)
-    int32_t *pp_report_dev = nullptr; // [kHistCap][8] reports of the iterations not fetched yet
-    // SLAMGPU_ASSOC_LISTS: cumulative counters (AssocListArgs::lstats; [4]: observations past the host's bound, reported by the next
-    // slamgpu_particle_report_fetch) and whether device-driven iterations have written slots without refreshing their boxes
-    unsigned long long *lstats_dev = nullptr;
-    bool box_dev_stale = false;
-    // the exclusion rule's radius capped by the step's observation spacing (slamgpu_set_particle_excl_spacing; 0: off) and the radii of
-    // the last step that made them: excl_rho_dev[0] holds their count (int32), the radii follow from [4] (excl_rho_cap of them)
-    float excl_spacing = 0.0f;
-    int32_t *excl_rho_dev = nullptr;
-    int excl_rho_cap = 0;
-    // data association sampling (slamgpu_set_particle_assoc_sampling): on / off, the ratios of the sampled pairs ([nz][ncap], as
-    // pp_lab_dev; held only while sampling is on) and the cumulative counters (SampleArgs::stats)
-    int32_t das_on = 0;
-    float *das_ratio_dev = nullptr;
-    size_t das_ratio_cap = 0;
-    unsigned long long *das_stats_dev = nullptr;
-    SampleArgs das_step{};  // the sampling arguments of the step being associated (AssocRule::smp points here: particle_rule)
-    // negative information (slamgpu_set_particle_miss; pm_range = 0: off): the factor and the view, the counts of the last step that
-    // made them ([ncap]; pm_have: some step has) and the cumulative counters (PpMissArgs::stats); nothing is allocated while it is off
-    float pm_p = 1.0f, pm_range = 0.0f, pm_front = 0.0f;
-    int32_t *pm_cnt_dev = nullptr;
-    unsigned long long *pm_stats_dev = nullptr;
-    bool pm_have = false;
-    // mutual exclusion for contested landmarks (slamgpu_set_particle_mutex): on / off, the table of who holds which slot
-    // ([cap_nf][ncap] int16, -1 between launches; held only while it is on) and the cumulative counters (PpMutexArgs::stats)
-    int32_t mx_on = 0;
-    int16_t *mx_hold_dev = nullptr;
-    unsigned long long *mx_stats_dev = nullptr;
-    size_t mx_hold_cap = 0;
-    bool pp_lists_done = false;      // the step's association went through the lists and left the slots' boxes (pp_missed's box test)
-    // the observations of the last per-particle step (slamgpu_particle_labels): the host-driven call's count, or -1: the device-driven
-    // iteration's (ObserveOut::nz)
-    int32_t pp_lab_nz = 0;
-    int pp_report_n = 0;
-    bool pp_stage_open = false;       // the previous iteration may have left a resampling stage (the device knows) and no gather has run since
-    double *pp_prev_hist = nullptr;   // ... its history slot and the parity of its weight scratch
-    int pp_prev_par = 0;
-    uint32_t pp_iter = 0;
 };
 
 #pragma GCC visibility push(hidden)
@@ -354,14 +369,28 @@ struct Timed {
     }
 };
 
-// slamgpu.cpp's, as the posterior layer calls them
+// slamgpu.cpp's, as the association and posterior layers call them
 int check_ctx(slamgpu_ctx *c);
 int book_pull(slamgpu_ctx *c);
 int sync_tables(slamgpu_ctx *c);
 int flush_predict(slamgpu_ctx *c);
 int flush_stages(slamgpu_ctx *c);
+int materialize(slamgpu_ctx *c);
+int read_ctrl(slamgpu_ctx *c, bool need_set = false);
+int persist_check(slamgpu_ctx *c);
+int demote_to_plain(slamgpu_ctx *c);
+int issue_update(slamgpu_ctx *c, UpdateArgs &U, int n_new, int n_rows, bool need_normals, const float *normals, const float *strata, bool sharded);
+int book_staging(slamgpu_ctx *c);
+void book_rebuild(slamgpu_ctx *c);
+void rows_add_live(slamgpu_ctx *c, int r);
+void rows_remove_live(slamgpu_ctx *c, int r);
+void compose_predicts(PredictArgs &P);
+RngArgs rng_args(const slamgpu_ctx *c, uint32_t step);
+// association.cpp's, as the steps and the posterior layer call them
+int pp_pull(slamgpu_ctx *c);
 int pp_dev_stage(slamgpu_ctx *c);
 int pp_dev_flush_predict(slamgpu_ctx *c);
+void association_release(slamgpu_ctx *c);  // slamgpu_destroy's share of this layer
 // posterior.cpp's, as the step entry points call them
 int path_identity(slamgpu_ctx *c);
 int path_compose(slamgpu_ctx *c);
