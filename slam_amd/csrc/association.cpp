@@ -229,7 +229,7 @@ int AssocCall::check(bool &empty) {
     if (int rc = flush_predict(c)) return rc;
     if (int rc = materialize(c)) return rc;  // plain set: particle k in slot k
     if (int rc = sync_tables(c)) return rc;
-    const bool single = !c->dist && c->cfg.n_particles_global == c->cfg.n_particles && c->pool_used == 0;
+    const bool single = is_single(c) && c->mg.pool_used == 0;
     if (mode == SLAMGPU_ASSOC_GRID && !single)
         return fail(SLAMGPU_ERR_INVALID, "the association grid needs a single context (shards: SLAMGPU_ASSOC_EXHAUSTIVE)");
     const bool excl = opt && opt->excl_base + opt->excl_per_m > 0.0f;  // (the exclusion rule: the exhaustive scan only)
@@ -492,7 +492,7 @@ int slamgpu_associate_ex(slamgpu_ctx *c, const float *z, int32_t nz, const float
 int slamgpu_retire_landmarks(slamgpu_ctx *c, const int32_t *ids, int32_t count) {
     if (int rc = check_ctx(c)) return rc;
     if (count < 0 || (count > 0 && !ids)) return fail(SLAMGPU_ERR_INVALID, "slamgpu_retire_landmarks: bad list");
-    if (c->dist || c->cfg.n_particles_global != c->cfg.n_particles) return fail(SLAMGPU_ERR_INVALID, "slamgpu_retire_landmarks: single contexts only");
+    if (!is_single(c)) return fail(SLAMGPU_ERR_INVALID, "slamgpu_retire_landmarks: single contexts only");
     if (int rc = book_pull(c)) return rc;
     for (int32_t k = 0; k < count; k++)
         if (ids[k] < 0 || ids[k] >= c->nf) return fail(SLAMGPU_ERR_INVALID, "slamgpu_retire_landmarks: landmark %d of %d", (int) ids[k], c->nf);
@@ -630,7 +630,7 @@ int pp_check(slamgpu_ctx *c, const float *z, int32_t nz, const float R[4], const
         return fail(SLAMGPU_ERR_INVALID, "per-particle association: p_new > 0, 0 <= new_share <= 1, census_every >= 0");
     if (!(opt->excl_base >= 0.0f) || !(opt->excl_per_m >= 0.0f) || !(opt->unique_ratio >= 0.0f))
         return fail(SLAMGPU_ERR_INVALID, "per-particle association: excl_base, excl_per_m, unique_ratio >= 0");
-    if (c->dist || c->cfg.n_particles_global != c->cfg.n_particles || c->pool_used != 0)
+    if (!is_single(c) || c->mg.pool_used != 0)
         return fail(SLAMGPU_ERR_INVALID, "per-particle association: single contexts only");
     if (c->innov.cap > 0 && nz > c->innov.cap)  // (refused before anything of the step has moved: its record could not be made)
         return fail(SLAMGPU_ERR_CAPACITY, "per-particle association: %d observations, the innovation ring holds %d entries", nz, c->innov.cap);

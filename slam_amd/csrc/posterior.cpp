@@ -67,7 +67,7 @@ enum {
 int summary_enter(slamgpu_ctx *c, const char *who, int flags) {
     if (flags & kCtx)
         if (int rc = check_ctx(c)) return rc;
-    if ((flags & kSingle) && (c->dist || c->cfg.n_particles_global != c->cfg.n_particles))
+    if ((flags & kSingle) && !is_single(c))
         return fail(SLAMGPU_ERR_INVALID, "%s: single contexts only", who);
     if (flags & kDevice) HIP_TRY(hipSetDevice(c->cfg.device));
     if (flags & kBook)

@@ -38,57 +38,6 @@ int dev_grow(void **p, size_t *cap, size_t n, size_t elem, const char *what, boo
     return 0;
 }
 
-namespace {
-
-// RCCL is bound at run time (dlopen): the library of the process (torch's when torch is loaded, /opt/rocm's otherwise), and no
-// link-time dependency for single-GPU users.
-struct Rccl {
-    decltype(&ncclGetUniqueId) GetUniqueId = nullptr;
-    decltype(&ncclCommInitRank) CommInitRank = nullptr;
-    decltype(&ncclCommInitAll) CommInitAll = nullptr;
-    decltype(&ncclCommDestroy) CommDestroy = nullptr;
-    decltype(&ncclAllGather) AllGather = nullptr;
-    decltype(&ncclGroupStart) GroupStart = nullptr;
-    decltype(&ncclGroupEnd) GroupEnd = nullptr;
-    decltype(&ncclGetErrorString) GetErrorString = nullptr;
-    decltype(&ncclCommCount) CommCount = nullptr;
-    decltype(&ncclCommUserRank) CommUserRank = nullptr;
-    bool ok = false;
-};
-const Rccl *rccl() {
-    static Rccl R;
-    static bool tried = false;
-    if (tried) return R.ok ? &R : nullptr;
-    tried = true;
-    void *h = nullptr;
-    for (const char *name : {"librccl.so.1", "librccl.so", "/opt/rocm/lib/librccl.so.1"})
-        if ((h = dlopen(name, RTLD_NOW | RTLD_GLOBAL))) break;
-    if (!h) return nullptr;
-#define SLAM_SYM(f) R.f = reinterpret_cast<decltype(R.f)>(dlsym(h, "nccl" #f))
-    SLAM_SYM(GetUniqueId);
-    SLAM_SYM(CommInitRank);
-    SLAM_SYM(CommInitAll);
-    SLAM_SYM(CommDestroy);
-    SLAM_SYM(AllGather);
-    SLAM_SYM(GroupStart);
-    SLAM_SYM(GroupEnd);
-    SLAM_SYM(GetErrorString);
-    SLAM_SYM(CommCount);
-    SLAM_SYM(CommUserRank);
-#undef SLAM_SYM
-    R.ok = R.GetUniqueId && R.CommInitRank && R.CommInitAll && R.CommDestroy && R.AllGather && R.GroupStart && R.GroupEnd && R.GetErrorString;
-    return R.ok ? &R : nullptr;
-}
-#define RCCL_TRY(expr)                                                                                  \
-    do {                                                                                                \
-        ncclResult_t r_ = (expr);                                                                       \
-        if (r_ != ncclSuccess) return fail(SLAMGPU_ERR_HIP, "%s: %s", #expr, rccl()->GetErrorString(r_)); \
-    } while (0)
-
-int64_t n_global(const slamgpu_ctx *c) { return c->cfg.n_particles_global > 0 ? c->cfg.n_particles_global : c->cfg.n_particles; }
-
-}  // namespace
-
 hipEvent_t get_event(slamgpu_ctx *c) {
     if (!c->ev_pool.empty()) {
         hipEvent_t e = c->ev_pool.back();
@@ -189,7 +138,7 @@ void rows_remove_live(slamgpu_ctx *c, int r) {
 }
 
 // every landmark [0, nf) in row 0 (own slot): after upload, flatten, a settling unpack
-static void rows_reset(slamgpu_ctx *c, int nf) {
+void rows_reset(slamgpu_ctx *c, int nf) {
     const int cap_rows = c->B.cap_rows;
     c->fresh_row = -1;
     std::fill(c->refcnt.begin(), c->refcnt.end(), 0);
@@ -420,7 +369,7 @@ static int flatten(slamgpu_ctx *c) {
     }
     HIP_TRY(hipGetLastError());
     for (int j = 0; j < c->nf; j++) c->live_flag[j] ^= 1;  // every row's records now live in its other buffer
-    c->pool_used = 0;  // every record is in its particle's own slot again
+    c->mg.pool_used = 0;  // every record is in its particle's own slot again
     rows_reset(c, c->nf);  // ... which is what genealogy row 0 says now, for every landmark
     return 0;
 }
@@ -438,7 +387,7 @@ int flush_stages(slamgpu_ctx *c) {
         c->k->finish(c->stream, c->B, c->ws, c->unreduced.hist, c->unreduced.par);
         c->unreduced.has = false;
     }
-    if (c->unplanned.has && c->dist)
+    if (c->unplanned.has && c->mg.dist)
         // the resampling stage of a distributed context needs every shard's totals: it only ever runs inside the next
         // update launch (slamgpu_dist_step / slamgpu_dist_settle)
         return fail(SLAMGPU_ERR_INVALID, "distributed context: call slamgpu_dist_settle on every shard (and all-gather) before reading results");
@@ -519,6 +468,30 @@ int keep_history_tail(slamgpu_ctx *c, const std::vector<double> &h, int taken) {
 }
 
 }  // namespace
+
+int history_take(slamgpu_ctx *c, int32_t max_count, int32_t *count, const std::function<void(int, const double *)> &per_entry,
+                 int (*ready)(slamgpu_ctx *)) {
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    if (int rc = flush_stages(c)) return rc;
+    std::vector<double> h;
+    if (int rc = history_to_host(c, h)) return rc;
+    if (ready)
+        if (int rc = ready(c)) return rc;
+    const int n = c->hist_n < std::max(max_count, 0) ? c->hist_n : std::max(max_count, 0);
+    for (int i = 0; i < n; i++) per_entry(i, h.data() + (size_t) kHistStride * i);
+    *count = n;
+    if (int rc = keep_history_tail(c, h, n)) return rc;
+    c->est_fresh = false;
+    return 0;
+}
+
+int estimate_now(slamgpu_ctx *c, double *hist) {
+    if (int rc = materialize(c)) return rc;
+    if (int rc = flush_stages(c)) return rc;
+    Timed t(c, "estimate");
+    c->k->estimate(c->stream, c->B, c->ws, hist);
+    return 0;
+}
 
 // The abort word of the persistent step loop is sticky, like the barrier error of the push collective: whoever synchronises with
 // the device reports it (the kernel stores it into pinned host memory: no copy needed here).
@@ -621,10 +594,9 @@ int slamgpu_create(const slamgpu_config *cfg, slamgpu_ctx **out) {
     } else {
         CTX_TRY(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
     }
-    CTX_TRY(hipMalloc((void **) &c->plan_dev, sizeof(ShardPlan)));
-    CTX_TRY(hipHostMalloc((void **) &c->plan_host, sizeof(ShardPlan), hipHostMallocDefault));
-    CTX_TRY(hipHostMalloc((void **) &c->plan_seq_host, sizeof(uint32_t), hipHostMallocDefault));
-    *c->plan_seq_host = 0;
+    CTX_TRY(hipHostMalloc((void **) &c->mg.plan_host, sizeof(ShardPlan), hipHostMallocDefault));
+    CTX_TRY(hipHostMalloc((void **) &c->mg.plan_seq_host, sizeof(uint32_t), hipHostMallocDefault));
+    *c->mg.plan_seq_host = 0;
     const size_t S = (size_t) ncap;
     for (int b = 0; b < 2; b++) {
         CTX_TRY(hipMalloc((void **) &c->B.poseA[b], sizeof(float4) * S));
@@ -733,20 +705,9 @@ void slamgpu_destroy(slamgpu_ctx *c) {
         if (c->B.lmkA[b]) (void) hipFree(c->B.lmkA[b]);
         if (c->B.lmkB[b]) (void) hipFree(c->B.lmkB[b]);
         if (c->B.gen[b]) (void) hipFree(c->B.gen[b]);
-        if (b == 0 && c->B.poolA) (void) hipFree(c->B.poolA);
-        if (b == 0 && c->B.poolB) (void) hipFree(c->B.poolB);
     }
     if (c->B.ctrl) (void) hipFree(c->B.ctrl);
     if (c->ctrl_host) (void) hipHostFree(c->ctrl_host);
-    if (!c->own_totals) c->ws.blk_w[0] = c->own_blk_w;
-    for (int b = 0; b < 2; b++) {
-        if (c->ws.lcum[b]) (void) hipFree(c->ws.lcum[b]);
-        if (c->ws.blk_w[b]) (void) hipFree(c->ws.blk_w[b]);
-        if (c->ws.est_part[b]) (void) hipFree(c->ws.est_part[b]);
-        if (c->ws.scan[b]) (void) hipFree(c->ws.scan[b]);
-    }
-    for (int b = 0; b < 2; b++)
-        if (c->ws.keep[b]) (void) hipFree(c->ws.keep[b]);
     if (c->hist_dev) (void) hipFree(c->hist_dev);
     if (c->hist_host) (void) hipHostFree(c->hist_host);
     if (c->stamps_dev) (void) hipFree(c->stamps_dev);
@@ -771,12 +732,16 @@ void slamgpu_destroy(slamgpu_ctx *c) {
         (void) hipStreamSynchronize(c->obs_stream);
         (void) hipStreamDestroy(c->obs_stream);
     }
-    if (c->comm && rccl()) (void) rccl()->CommDestroy((ncclComm_t) c->comm);
-    for (void *p : c->ipc_opened) (void) hipIpcCloseMemHandle(p);
-    if (c->peers_dev) (void) hipFree(c->peers_dev);
+    multigpu_release(c);
+    // (the weight scratch after it: ws.blk_w[0] is the context's own again, not a caller's totals buffer)
+    for (int b = 0; b < 2; b++) {
+        if (c->ws.lcum[b]) (void) hipFree(c->ws.lcum[b]);
+        if (c->ws.blk_w[b]) (void) hipFree(c->ws.blk_w[b]);
+        if (c->ws.est_part[b]) (void) hipFree(c->ws.est_part[b]);
+        if (c->ws.scan[b]) (void) hipFree(c->ws.scan[b]);
+    }
     for (int b = 0; b < 2; b++)
-        if (c->gtot_dev[b]) (void) hipFree(c->gtot_dev[b]);
-    if (c->flags_dev) (void) hipFree(c->flags_dev);
+        if (c->ws.keep[b]) (void) hipFree(c->ws.keep[b]);
     if (c->front_dev) (void) hipFree(c->front_dev);
     if (c->front_host) (void) hipHostFree(c->front_host);
     if (c->front_pkt_dev) (void) hipFree(c->front_pkt_dev);
@@ -797,9 +762,6 @@ void slamgpu_destroy(slamgpu_ctx *c) {
     if (c->normals_dev) (void) hipFree(c->normals_dev);
     for (int b = 0; b < 2; b++)
         if (c->strata_dev[b]) (void) hipFree(c->strata_dev[b]);
-    if (c->plan_dev) (void) hipFree(c->plan_dev);
-    if (c->plan_host) (void) hipHostFree(c->plan_host);
-    if (c->plan_seq_host) (void) hipHostFree(c->plan_seq_host);
     if (c->stream && c->own_stream) (void) hipStreamDestroy(c->stream);
     delete c;
 }
@@ -834,7 +796,7 @@ int slamgpu_predict(slamgpu_ctx *c, float V, float G, const float Q[4], float dt
     s.sinGw = sinf(G / c->cfg.wheel_base);
     s.pad = 0;
     c->est_fresh = false;
-    c->shard_est_fresh = false;
+    c->mg.shard_est_fresh = false;
     if (tape_noise) {
         HIP_TRY(hipSetDevice(c->cfg.device));
         HIP_TRY(hipStreamSynchronize(c->stream));  // tape_host is single-buffered (parity mode only)
@@ -860,7 +822,7 @@ int issue_update(slamgpu_ctx *c, UpdateArgs &U, int n_new, int n_rows, bool need
     const int n = n_new;
     // reference-order resampling (strict build, TAPE draws, small contexts): the stage of the previous update never rides in this
     // launch: it runs now, as launches of its own, through resample_ref_kernel
-    if (c->ref_resample && !sharded && !c->dist && c->unplanned.has)
+    if (c->ref_resample && !sharded && !c->mg.dist && c->unplanned.has)
         if (int rc = flush_stages(c)) return rc;
     // pending predicts ride inside the update launch (state stays in registers) unless their noise is a host tape
     PredictArgs PA{};
@@ -888,7 +850,7 @@ int issue_update(slamgpu_ctx *c, UpdateArgs &U, int n_new, int n_rows, bool need
     }
 
     RngArgs rng = rng_args(c, c->obs_step);
-    if (c->dist) {
+    if (c->mg.dist) {
         rng.step = c->obs_step - c->rng_skew;  // (device noise only: the tape buffers above do not apply)
         rng.prev_step = c->unplanned.step;
     }
@@ -897,14 +859,14 @@ int issue_update(slamgpu_ctx *c, UpdateArgs &U, int n_new, int n_rows, bool need
     c->B.slot = c->slot;
     c->ws.wpar = sharded ? 0 : (int) (c->obs_step & 1);
     U.lazy = 1;
-    U.arrivals = c->dist ? 2 : (sharded ? 1 : 0);
-    if (c->dist) {
-        c->B.gtot[0] = c->gtot_dev[0];
-        c->B.gtot[1] = c->gtot_dev[1];
-        c->dist_clean = false;
-        U.push_totals = (c->dist_push || c->dist_fold) ? 1 : 0;
-        U.count_remote = c->count_remote ? 1 : 0;
-        U.fold_seq = c->dist_fold ? ++c->flag_seq : 0;
+    U.arrivals = c->mg.dist ? 2 : (sharded ? 1 : 0);
+    if (c->mg.dist) {
+        c->B.gtot[0] = c->mg.gtot_dev[0];
+        c->B.gtot[1] = c->mg.gtot_dev[1];
+        c->mg.dist_clean = false;
+        U.push_totals = (c->mg.dist_push || c->mg.dist_fold) ? 1 : 0;
+        U.count_remote = c->mg.count_remote ? 1 : 0;
+        U.fold_seq = c->mg.dist_fold ? ++c->mg.flag_seq : 0;
         U.fold_spins = 1u << 20;
     }
     // a pending gather's genealogy composition: small packets: by the compute threads themselves; device packets: by copy
@@ -965,7 +927,7 @@ int issue_update(slamgpu_ctx *c, UpdateArgs &U, int n_new, int n_rows, bool need
         // the resampling stage is driven by the caller through slamgpu_shard_* (needs collectives)
         c->unreduced.has = false;  // reduced by the helper block of this launch
         c->est_fresh = false;
-        c->shard_est_fresh = false;
+        c->mg.shard_est_fresh = false;
         return 0;
     }
     // stage bookkeeping: the helper block reduced `unreduced`; the inline plan left the partials of `unplanned`;
@@ -981,7 +943,7 @@ int issue_update(slamgpu_ctx *c, UpdateArgs &U, int n_new, int n_rows, bool need
     // large contexts: one block prepares the prefix of this step's block totals for the next launch, instead of every
     // block of that launch redoing it (a second, tiny launch; negligible at these sizes)
     c->scan_ready = false;
-    if (c->ws.nblocks > c->scan_min_blocks && !c->dist) {
+    if (c->ws.nblocks > c->scan_min_blocks && !c->mg.dist) {
         Timed t(c, "scan");
         c->k->scan(c->stream, c->ws, c->cfg.log_weights);
         c->scan_ready = true;
@@ -1033,8 +995,6 @@ int demote_to_plain(slamgpu_ctx *c) {
     return 0;
 }
 
-namespace {
-
 int do_update(slamgpu_ctx *c, const float *zf, const int32_t *idf, int32_t m, const float *zn, int32_t n,
               const float R[4], const float *normals, const float *strata, bool sharded) {
     if (m < 0 || n < 0 || !R || (m > 0 && (!zf || !idf)) || (n > 0 && !zn)) return fail(SLAMGPU_ERR_INVALID, "bad observation packet");
@@ -1085,7 +1045,7 @@ int do_update(slamgpu_ctx *c, const float *zf, const int32_t *idf, int32_t m, co
     // landmarks each on that map -- down to kMidRowsLow, as many as the packet has room for; 40 rows are never exceeded (past
     // kSmallRows - 2 the context would go to plain rows: do_update's guard).
     const bool mid_cons = c->mid_compact && !sharded && c->consolidate && (int) c->live_rows.size() > kMidRowsHigh;
-    if (mid_cons || (!c->B.compact && !sharded && !c->dist && c->consolidate && (int) c->live_rows.size() > c->plain_rows_target)) {
+    if (mid_cons || (!c->B.compact && !sharded && !c->mg.dist && c->consolidate && (int) c->live_rows.size() > c->plain_rows_target)) {
         const int budget = mid_cons ? std::max(0, kSmallObs - m) : std::max(kPlainConsBudget, m / 16);
         const int target = mid_cons ? kMidRowsLow : c->plain_rows_target;
         std::vector<int32_t> order(c->live_rows);
@@ -1225,6 +1185,14 @@ int do_update(slamgpu_ctx *c, const float *zf, const int32_t *idf, int32_t m, co
     return issue_update(c, U, n, n_rows, need_normals, normals, strata, sharded);
 }
 
+int predict_controls(slamgpu_ctx *c, const float *controls, int32_t n_controls, const float Q[4], float dt) {
+    for (int k = 0; k < n_controls; k++)
+        if (int rc = slamgpu_predict(c, controls[3 * k], controls[3 * k + 1], Q, dt, controls[3 * k + 2], nullptr)) return rc;
+    return 0;
+}
+
+namespace {
+
 // FastSLAM{1,2}::update with the observation made on the device (slamgpu_step_observe): observe_book_kernel writes the packet
 // and the genealogy bookkeeping into device memory, the update launch reads them there.
 int do_update_dev(slamgpu_ctx *c, const float xtrue[3], float max_range, const float R[4], int32_t noise, const float *r1,
@@ -1232,7 +1200,7 @@ int do_update_dev(slamgpu_ctx *c, const float xtrue[3], float max_range, const f
     if (!c->map_dev) return fail(SLAMGPU_ERR_INVALID, "no map: call slamgpu_set_map first");
     if ((!c->B.compact || c->mid_compact) && !(c->cfg.flags & SLAMGPU_FLAG_DEVICE_OBSERVE))
         return fail(SLAMGPU_ERR_INVALID, "create the context with SLAMGPU_FLAG_DEVICE_OBSERVE (its observation packets live in device memory)");
-    if (c->dist || c->cfg.n_particles_global != c->cfg.n_particles) return fail(SLAMGPU_ERR_INVALID, "slamgpu_step_observe: single contexts only");
+    if (!is_single(c)) return fail(SLAMGPU_ERR_INVALID, "slamgpu_step_observe: single contexts only");
     if (c->map_n > c->B.cap_nf) return fail(SLAMGPU_ERR_CAPACITY, "map of %d landmarks, capacity %d", c->map_n, c->B.cap_nf);
     if (!xtrue || !R || noise < 0 || noise > 2 || (noise == 1 && (!r1 || !r2))) return fail(SLAMGPU_ERR_INVALID, "bad arguments");
     const bool tape = c->cfg.rng_mode == SLAMGPU_RNG_TAPE;
@@ -1355,7 +1323,7 @@ extern "C" {
 int slamgpu_update(slamgpu_ctx *c, const float *zf, const int32_t *idf, int32_t m, const float *zn, int32_t n,
                    const float R[4], const float *normals, const float *strata) {
     if (int rc = check_ctx(c)) return rc;
-    if (c->dist) return fail(SLAMGPU_ERR_INVALID, "distributed context: use slamgpu_dist_step (an update here would skip the all-gather)");
+    if (c->mg.dist) return fail(SLAMGPU_ERR_INVALID, "distributed context: use slamgpu_dist_step (an update here would skip the all-gather)");
     if (c->cfg.n_particles_global != c->cfg.n_particles)
         return fail(SLAMGPU_ERR_INVALID, "this context is a shard (%d of %lld particles): use slamgpu_shard_update + slamgpu_shard_*",
                     c->cfg.n_particles, (long long) c->cfg.n_particles_global);
@@ -1371,8 +1339,7 @@ int slamgpu_step(slamgpu_ctx *c, const float *controls, int32_t n_controls, cons
         return fail(SLAMGPU_ERR_INVALID, "slamgpu_step cannot carry TAPE-mode predict noise: call slamgpu_predict per control");
     if (c->innov.cap > 0 && m > c->innov.cap)  // (refused before anything is applied: the record between predicts and update could not be made)
         return fail(SLAMGPU_ERR_CAPACITY, "slamgpu_step: %d observations, the innovation ring holds %d entries", m, c->innov.cap);
-    for (int k = 0; k < n_controls; k++)
-        if (int rc = slamgpu_predict(c, controls[3 * k], controls[3 * k + 1], Q, dt, controls[3 * k + 2], nullptr)) return rc;
+    if (int rc = predict_controls(c, controls, n_controls, Q, dt)) return rc;
     if (c->innov.cap > 0)  // the innovation ring: this step's packet against the predicted set, before the update takes it
         if (int rc = innov_append(c, zf, idf, m, R)) return rc;
     if (int rc = slamgpu_update(c, zf, idf, m, zn, n, R, normals, strata)) return rc;
@@ -1392,8 +1359,7 @@ int slamgpu_step_observe(slamgpu_ctx *c, const float *controls, int32_t n_contro
     if (n_controls < 0 || (n_controls > 0 && (!controls || !Q))) return fail(SLAMGPU_ERR_INVALID, "bad control list");
     if (n_controls > 0 && c->cfg.add_predict_noise && c->cfg.rng_mode == SLAMGPU_RNG_TAPE)
         return fail(SLAMGPU_ERR_INVALID, "slamgpu_step_observe cannot carry TAPE-mode predict noise: call slamgpu_predict per control");
-    for (int k = 0; k < n_controls; k++)
-        if (int rc = slamgpu_predict(c, controls[3 * k], controls[3 * k + 1], Q, dt, controls[3 * k + 2], nullptr)) return rc;
+    if (int rc = predict_controls(c, controls, n_controls, Q, dt)) return rc;
     if (int rc = do_update_dev(c, xtrue, max_range, R, noise, r1, r2, normals, strata)) return rc;
     if (record_estimate) {
         if (int rc = slamgpu_estimate_async(c)) return rc;
@@ -1435,7 +1401,7 @@ static int persist_setup(slamgpu_ctx *c, int32_t K) {
 }
 
 static bool persist_eligible(const slamgpu_ctx *c) {
-    return c->persist_ok && c->B.compact && !c->mid_compact && !c->dist && c->cfg.n_particles_global == c->cfg.n_particles &&
+    return c->persist_ok && c->B.compact && !c->mid_compact && is_single(c) &&
            c->cfg.rng_mode == SLAMGPU_RNG_PHILOX && c->ws.nblocks <= kPersistMaxBlocks && c->ws.nblocks <= c->scan_min_blocks;
 }
 
@@ -1522,7 +1488,7 @@ int slamgpu_run_observe(slamgpu_ctx *c, int32_t K, const int32_t *n_controls, co
     if (!c->map_dev) return fail(SLAMGPU_ERR_INVALID, "slamgpu_run_observe: no map: call slamgpu_set_map first");
     if ((!c->B.compact || c->mid_compact) && !(c->cfg.flags & SLAMGPU_FLAG_DEVICE_OBSERVE))
         return fail(SLAMGPU_ERR_INVALID, "slamgpu_run_observe: create the context with SLAMGPU_FLAG_DEVICE_OBSERVE (its observation packets live in device memory)");
-    if (c->dist || c->cfg.n_particles_global != c->cfg.n_particles) return fail(SLAMGPU_ERR_INVALID, "slamgpu_run_observe: single contexts only");
+    if (!is_single(c)) return fail(SLAMGPU_ERR_INVALID, "slamgpu_run_observe: single contexts only");
     if (c->map_n > c->B.cap_nf) return fail(SLAMGPU_ERR_CAPACITY, "slamgpu_run_observe: map of %d landmarks, capacity %d", c->map_n, c->B.cap_nf);
     size_t total = 0;
     int32_t max_nc = 0;
@@ -1583,720 +1549,6 @@ int slamgpu_observe_fetch(slamgpu_ctx *c, float *z, int32_t *vis, int32_t *nz, f
     return 0;
 }
 
-int slamgpu_shard_step(slamgpu_ctx *c, const float *controls, int32_t n_controls, const float Q[4], float dt, const float *zf,
-                       const int32_t *idf, int32_t m, const float *zn, int32_t n, const float R[4], const float *normals,
-                       const float *strata) {
-    if (int rc = check_ctx(c)) return rc;
-    if (n_controls < 0 || (n_controls > 0 && !controls)) return fail(SLAMGPU_ERR_INVALID, "bad control list");
-    if (n_controls > 0 && c->cfg.add_predict_noise && c->cfg.rng_mode == SLAMGPU_RNG_TAPE)
-        return fail(SLAMGPU_ERR_INVALID, "slamgpu_shard_step cannot carry TAPE-mode predict noise: call slamgpu_predict per control");
-    for (int k = 0; k < n_controls; k++)
-        if (int rc = slamgpu_predict(c, controls[3 * k], controls[3 * k + 1], Q, dt, controls[3 * k + 2], nullptr)) return rc;
-    return slamgpu_shard_update(c, zf, idf, m, zn, n, R, normals, strata);
-}
-
-// ---- sharded operation -------------------------------------------------------------------------------
-int slamgpu_shard_update(slamgpu_ctx *c, const float *zf, const int32_t *idf, int32_t m, const float *zn, int32_t n,
-                         const float R[4], const float *normals, const float *strata) {
-    if (int rc = check_ctx(c)) return rc;
-    if (c->cfg.n_particles % kBlock != 0 || c->cfg.first_particle % kBlock != 0)
-        return fail(SLAMGPU_ERR_INVALID, "shards must hold a multiple of %d particles", kBlock);
-    if (c->cfg.log_weights) return fail(SLAMGPU_ERR_INVALID, "the sharded resampling stage works on linear weights (log_weights contexts: slamgpu_update)");
-    if (c->dist) return fail(SLAMGPU_ERR_INVALID, "distributed context: use slamgpu_dist_step");
-    return do_update(c, zf, idf, m, zn, n, R, normals, strata, true);
-}
-
-int slamgpu_shard_set_totals_buffer(slamgpu_ctx *c, float *totals_dev) {
-    if (int rc = check_ctx(c)) return rc;
-    HIP_TRY(hipSetDevice(c->cfg.device));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    if (c->own_totals) c->own_blk_w = c->ws.blk_w[0];
-    float *p = totals_dev ? totals_dev : c->own_blk_w;
-    c->own_totals = totals_dev == nullptr;
-    c->ws.blk_w[0] = p;  // shard contexts only use parity 0 of the weight scratch
-    return 0;
-}
-
-int slamgpu_shard_block_totals(slamgpu_ctx *c, const float **totals_dev, int32_t *nblocks) {
-    if (int rc = check_ctx(c)) return rc;
-    if (totals_dev) *totals_dev = c->ws.blk_w[0];  // [w(nblocks) | w2(nblocks)]
-    if (nblocks) *nblocks = c->ws.nblocks;
-    return 0;
-}
-
-int slamgpu_shard_record_floats(slamgpu_ctx *c) { return c ? 10 + 5 * c->nf : SLAMGPU_ERR_INVALID; }
-
-int slamgpu_shard_plan(slamgpu_ctx *c, const float *gtot, int32_t nb_global, int32_t n_shards, slamgpu_shard_plan_t *out) {
-    if (int rc = check_ctx(c)) return rc;
-    if (!gtot || !out) return fail(SLAMGPU_ERR_INVALID, "null argument");
-    if (n_shards < 1 || n_shards > kMaxShards) return fail(SLAMGPU_ERR_INVALID, "n_shards %d out of range [1,%d]", n_shards, kMaxShards);
-    if (nb_global > kMaxScanBlocks || nb_global % n_shards != 0 || (int64_t) nb_global * kBlock != n_global(c))
-        return fail(SLAMGPU_ERR_INVALID, "nb_global %d inconsistent with %lld particles over %d shards", nb_global, (long long) n_global(c), n_shards);
-    static_assert(sizeof(slamgpu_shard_plan_t) == sizeof(ShardPlan), "public / device plan layout");
-    HIP_TRY(hipSetDevice(c->cfg.device));
-    ShardPlanArgs A{};
-    A.gblk = gtot;
-    A.nb_global = nb_global;
-    A.nb_per_shard = nb_global / n_shards;
-    A.n_shards = n_shards;
-    A.do_resample = c->cfg.resample;
-    A.n_effective = c->cfg.n_effective;
-    // the plan goes straight into pinned host memory and the host polls a sequence word the kernel stores last: a
-    // stream synchronisation costs several microseconds more than the store takes to arrive.  Bounded: after 2 ms
-    // without the word (e.g. a profiler serialising the queue) fall back to synchronising the stream.
-    const uint32_t seq = ++c->plan_seq;
-    {
-        Timed t(c, "shard_plan");
-        c->k->shard_plan(c->stream, A, rng_args(c, c->obs_step), c->plan_host, c->plan_seq_host, seq);
-    }
-    HIP_TRY(hipGetLastError());
-    const auto t0 = std::chrono::steady_clock::now();
-    volatile uint32_t *flag = c->plan_seq_host;
-    bool arrived = false;
-    for (uint64_t spin = 0;; spin++) {
-        if (*flag == seq) {
-            arrived = true;
-            break;
-        }
-        if ((spin & 1023) == 1023 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(2)) break;
-    }
-    if (!arrived) HIP_TRY(hipStreamSynchronize(c->stream));
-    std::atomic_thread_fence(std::memory_order_acquire);
-    memcpy(out, c->plan_host, sizeof(ShardPlan));
-    return 0;
-}
-
-int slamgpu_shard_pack(slamgpu_ctx *c, const float *gtot, int32_t nb_global, int32_t n_shards, int32_t shard,
-                       const slamgpu_shard_plan_t *plan, float *send_dev, int64_t *send_counts, int64_t *recv_counts) {
-    if (int rc = check_ctx(c)) return rc;
-    if (!gtot || !plan || !send_counts || !recv_counts) return fail(SLAMGPU_ERR_INVALID, "null argument");
-    if (n_shards < 1 || nb_global % n_shards != 0) return fail(SLAMGPU_ERR_INVALID, "bad shard geometry");
-    if (shard < 0 || shard >= n_shards || n_shards > kMaxShards) return fail(SLAMGPU_ERR_INVALID, "bad shard index");
-    const int64_t n = c->cfg.n_particles;
-    const int64_t k_lo = plan->K[shard], k_hi = plan->K[shard + 1];
-    // records this shard sends to d / receives from s: overlaps of offspring ranges with output ranges
-    for (int d = 0; d < n_shards; d++) {
-        const int64_t a = std::max(k_lo, (int64_t) d * n), b = std::min(k_hi, (int64_t) (d + 1) * n);
-        send_counts[d] = (b > a && d != shard) ? b - a : 0;  // own offspring are gathered in place by the pack kernel
-        const int64_t ra = std::max(plan->K[d], (int64_t) shard * n), rb = std::min(plan->K[d + 1], (int64_t) (shard + 1) * n);
-        recv_counts[d] = (rb > ra && d != shard) ? rb - ra : 0;
-    }
-    int64_t to_send = 0;
-    for (int d = 0; d < n_shards; d++) to_send += send_counts[d];
-    if (to_send > 0 && !send_dev) return fail(SLAMGPU_ERR_INVALID, "null send buffer");
-    HIP_TRY(hipSetDevice(c->cfg.device));
-    ShardPackArgs A{};
-    A.gblk = gtot;
-    A.nb_global = nb_global;
-    A.nb_per_shard = nb_global / n_shards;
-    A.first_block = (int32_t) (c->cfg.first_particle / kBlock);
-    A.k_lo = k_lo;
-    A.k_hi = k_hi;
-    A.n_per_shard = n;
-    A.nf = c->nf;
-    A.fields = 10 + 5 * c->nf;
-    A.shard = shard;
-    A.send = send_dev;
-    if (int rc = sync_tables(c)) return rc;  // the pack kernel reads records through the genealogy (B.erow)
-    c->B.slot = c->slot;
-    c->shard_settled = false;
-    {
-        Timed t(c, "shard_pack");
-        c->k->shard_pack(c->stream, c->B, c->ws, A, rng_args(c, c->obs_step));
-    }
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-
-int slamgpu_shard_unpack(slamgpu_ctx *c, const float *recv_dev, int32_t n_shards, int32_t shard,
-                         const slamgpu_shard_plan_t *plan) {
-    if (int rc = check_ctx(c)) return rc;
-    if (!plan) return fail(SLAMGPU_ERR_INVALID, "null argument");
-    if (shard < 0 || shard >= n_shards || n_shards > kMaxShards) return fail(SLAMGPU_ERR_INVALID, "bad shard index");
-    HIP_TRY(hipSetDevice(c->cfg.device));
-    const int64_t n = c->cfg.n_particles, first = (int64_t) shard * n;
-    {
-        // nothing to scatter when every output slot of this shard was produced locally
-        const int64_t own_lo = std::min(std::max(plan->K[shard] - first, (int64_t) 0), n);
-        const int64_t own_hi = std::min(std::max(plan->K[shard + 1] - first, (int64_t) 0), n);
-        if (own_lo == 0 && own_hi == n) return 0;
-        if (!recv_dev) return fail(SLAMGPU_ERR_INVALID, "null receive buffer");
-    }
-    ShardUnpackArgs A{};
-    A.recv = recv_dev;
-    A.n_shards = n_shards;
-    A.nf = c->nf;
-    A.fields = 10 + 5 * c->nf;
-    A.shard = shard;
-    for (int s = 0; s <= n_shards; s++) A.src_lo[s] = std::min(std::max(plan->K[s] - first, (int64_t) 0), n);
-    // the arrivals' landmark records go into the arrival pool (allocated on first use); when it cannot take this step's,
-    // the kernel settles the whole shard instead, which also empties the pool
-    const int64_t arrivals = n - (A.src_lo[shard + 1] - A.src_lo[shard]);
-    if (!c->B.poolA) {
-        const int64_t budget = (int64_t) 256 << 20;  // bytes
-        int64_t cap = budget / (20 * (int64_t) c->B.cap_nf);
-        cap = std::max<int64_t>(256, std::min<int64_t>(cap, 32768));
-        if (const char *e = getenv("SLAMGPU_POOL_CAP")) cap = std::max(1, atoi(e));  // diagnostic / tests
-        HIP_TRY(hipMalloc((void **) &c->B.poolA, sizeof(float4) * (size_t) cap * c->B.cap_nf));
-        HIP_TRY(hipMalloc((void **) &c->B.poolB, sizeof(float) * (size_t) cap * c->B.cap_nf));
-        c->B.pool_cap = (int32_t) cap;
-        c->pool_used = 0;
-    }
-    const bool settle = c->pool_used + arrivals > c->B.pool_cap;
-    A.pool_base = settle ? -1 : (int32_t) c->pool_used;
-    A.own_lo = (int32_t) A.src_lo[shard];
-    A.own_hi = (int32_t) A.src_lo[shard + 1];
-    if (int rc = sync_tables(c)) return rc;  // arrivals: every live row points at the pool; settling reads through B.erow
-    c->B.slot = c->slot;
-    {
-        Timed t(c, "shard_unpack");
-        c->k->shard_unpack(c->stream, c->B, c->ws, A);
-    }
-    HIP_TRY(hipGetLastError());
-    if (settle) {
-        // the kernel rewrote the whole shard physically and flipped every landmark row; nothing references the pool now
-        c->shard_settled = true;
-        for (int j = 0; j < c->nf; j++) c->live_flag[j] ^= 1;
-        c->pool_used = 0;
-        rows_reset(c, c->nf);  // every landmark of every output particle in its own slot: genealogy row 0
-    } else {
-        c->pool_used += arrivals;
-    }
-    return 0;
-}
-
-int slamgpu_shard_finish(slamgpu_ctx *c, const slamgpu_shard_plan_t *plan) {
-    if (int rc = check_ctx(c)) return rc;
-    if (!plan) return fail(SLAMGPU_ERR_INVALID, "null plan");
-    HIP_TRY(hipSetDevice(c->cfg.device));
-    const int mode = !plan->resampled ? 0 : (c->shard_settled ? 2 : 1);
-    c->B.slot = c->slot;
-    {
-        Timed t(c, "shard_finish");
-        c->k->shard_finish(c->stream, c->B, c->ws, plan->wsum, plan->wsq, plan->neff, mode);
-    }
-    c->keep_slot = c->slot ^ 1;  // pack / unpack wrote the ancestors there
-    c->slot ^= 1;  // shard_finalize_kernel published the live / pending state in the other slot
-    c->B.slot = c->slot;
-    c->maybe_pending = mode == 1;
-    c->shard_settled = false;
-    c->est_fresh = false;
-    c->shard_est_fresh = true;  // est_part holds this shard's partials of this update
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-
-// ---- distributed operation ---------------------------------------------------------------------------------------------
-namespace {
-// the all-gather that follows an update launch of a distributed context, on the context's stream
-int launch_flags(slamgpu_ctx *c);
-int gather_totals(slamgpu_ctx *c) {
-    if (c->dist_fold) return 0;                // ... and the barrier rides at the head of the next launch
-    if (c->dist_push) return launch_flags(c);  // the totals are in every table already: only the barrier is left
-    if (!c->comm) return 0;
-    const int par = (int) (c->obs_step & 1);
-    Timed t(c, "allgather");  // (slamgpu_profile: an event pair around the collective, like around every launch)
-    RCCL_TRY(rccl()->AllGather(c->ws.blk_w[par], c->gtot_dev[par], (size_t) 2 * c->ws.nblocks, ncclFloat, (ncclComm_t) c->comm, c->stream));
-    return 0;
-}
-
-// The barrier error word of the push / fold collective is sticky (a kernel that finds it set does not wait again): whoever
-// synchronises with the device anyway -- history fetch, settle + read, the status query -- reports it, so that a C caller
-// that never polls slamgpu_dist_collective_status still cannot read results of unsynchronised steps as valid.
-int barrier_check(slamgpu_ctx *c) {
-    if (!c->dist || !c->flags_dev || !(c->dist_push || c->dist_fold)) return 0;
-    uint32_t err = 0;
-    HIP_TRY(hipMemcpy(&err, c->flags_dev + kMaxShards, sizeof err, hipMemcpyDeviceToHost));
-    if (err != 0)
-        return fail(SLAMGPU_ERR_BARRIER, "flag barrier %u of the push collective timed out: a peer did not arrive; the steps since then are void "
-                                         "(recreate the contexts, or use SLAMGPU_DIST_GATHER)", err);
-    return 0;
-}
-
-constexpr int kDistArrays = 17;
-constexpr int kFlagWords = kGoBase + kGoStride * kGoWords;  // flags [0, kMaxShards), error word at kMaxShards, then the go words
-struct DistBlob {
-    int64_t pid;
-    int32_t device, ncap, cap_nf, compact;
-    void *ptr[kDistArrays];
-    hipIpcMemHandle_t handle[kDistArrays];
-};
-void dist_arrays(slamgpu_ctx *c, void **a) {
-    int k = 0;
-    for (int b = 0; b < 2; b++) a[k++] = c->B.poseA[b];
-    for (int b = 0; b < 2; b++) a[k++] = c->B.poseB[b];
-    for (int b = 0; b < 2; b++) a[k++] = c->B.poseC[b];
-    for (int b = 0; b < 2; b++) a[k++] = c->B.lmkA[b];
-    for (int b = 0; b < 2; b++) a[k++] = c->B.lmkB[b];
-    for (int b = 0; b < 2; b++) a[k++] = c->B.gen[b];
-    for (int b = 0; b < 2; b++) a[k++] = c->ws.lcum[b];
-    for (int b = 0; b < 2; b++) a[k++] = c->gtot_dev[b];
-    a[k++] = c->flags_dev;
-}
-
-// the table of everybody's block totals (by step parity) and the flag words: allocated before the export, because the
-// peers map them too (push collective)
-int dist_alloc_shared(slamgpu_ctx *c) {
-    if (c->gtot_dev[0]) return 0;
-    const int64_t n_shards = std::max<int64_t>(1, n_global(c) / std::max(1, c->cfg.n_particles));
-    for (int b = 0; b < 2; b++) {
-        HIP_TRY(hipMalloc((void **) &c->gtot_dev[b], sizeof(float) * 3 * (size_t) c->ws.nblocks * (size_t) n_shards));
-        HIP_TRY(hipMemset(c->gtot_dev[b], 0, sizeof(float) * 3 * (size_t) c->ws.nblocks * (size_t) n_shards));
-    }
-    // (fine-grained device memory: polled by a running kernel while another GPU stores into it.  A stack that cannot
-    // provide it loses the push collective, nothing else.)
-    if (hipExtMallocWithFlags((void **) &c->flags_dev, sizeof(uint32_t) * kFlagWords, hipDeviceMallocFinegrained) != hipSuccess) {
-        (void) hipGetLastError();
-        c->flags_dev = nullptr;
-    } else {
-        HIP_TRY(hipMemset(c->flags_dev, 0, sizeof(uint32_t) * kFlagWords));
-    }
-    HIP_TRY(hipDeviceSynchronize());
-    return 0;
-}
-
-int launch_flags(slamgpu_ctx *c) {
-    DistFlagArgs A{};
-    for (int h = 0; h < c->B.n_shards; h++) A.peer_flags[h] = c->peer_flags[h];
-    A.my_flags = c->flags_dev;
-    A.err = c->flags_dev + kMaxShards;
-    A.n_shards = c->B.n_shards;
-    A.shard = c->B.shard;
-    A.seq = ++c->flag_seq;
-    A.max_spins = 1u << 20;  // (~a second: a peer that never arrives is reported, not waited for)
-    c->k->dist_flags(c->stream, A);
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-}  // namespace
-
-int slamgpu_dist_export_size(void) { return (int) sizeof(DistBlob); }
-
-int slamgpu_dist_export(slamgpu_ctx *c, void *blob) {
-    if (int rc = check_ctx(c)) return rc;
-    if (!blob) return fail(SLAMGPU_ERR_INVALID, "null blob");
-    HIP_TRY(hipSetDevice(c->cfg.device));
-    DistBlob b{};
-    b.pid = (int64_t) getpid();
-    b.device = c->cfg.device;
-    b.ncap = c->B.ncap;
-    b.cap_nf = c->B.cap_nf;
-    b.compact = c->B.compact;
-    if (int rc = dist_alloc_shared(c)) return rc;
-    dist_arrays(c, b.ptr);
-    for (int k = 0; k < kDistArrays; k++)
-        if (b.ptr[k]) HIP_TRY(hipIpcGetMemHandle(&b.handle[k], b.ptr[k]));  // (null: no flag words on that shard)
-    memcpy(blob, &b, sizeof b);
-    return 0;
-}
-
-int slamgpu_dist_connect(slamgpu_ctx *c, int32_t n_shards, int32_t shard, const void *blobs) {
-    if (int rc = check_ctx(c)) return rc;
-    if (!blobs || n_shards < 1 || n_shards > kMaxShards || shard < 0 || shard >= n_shards) return fail(SLAMGPU_ERR_INVALID, "bad shard geometry");
-    if (c->cfg.log_weights && n_shards > 1) return fail(SLAMGPU_ERR_INVALID, "log_weights is not available for distributed contexts");
-    const int64_t n = c->cfg.n_particles;
-    if (n_shards > 1 && (n % kBlock != 0 || c->cfg.first_particle != (int64_t) shard * n || n_global(c) != n * n_shards))
-        return fail(SLAMGPU_ERR_INVALID, "shard %d of %d must hold global particles [%lld, %lld) of %lld, a multiple of %d each", shard, n_shards,
-                    (long long) (shard * n), (long long) ((shard + 1) * n), (long long) (n * n_shards), kBlock);
-    if ((int64_t) c->ws.nblocks * n_shards > kMaxScanBlocks)
-        return fail(SLAMGPU_ERR_INVALID, "%lld particles exceed %d blocks of 256", (long long) (n * n_shards), kMaxScanBlocks);
-    if (c->obs_step != 0 || c->nf != 0) return fail(SLAMGPU_ERR_INVALID, "connect a distributed context before its first update");
-    HIP_TRY(hipSetDevice(c->cfg.device));
-    const DistBlob *all = static_cast<const DistBlob *>(blobs);
-    std::vector<PeerPtrs> table((size_t) n_shards);
-    for (int h = 0; h < n_shards; h++) {
-        const DistBlob &b = all[h];
-        if (b.ncap != c->B.ncap || b.cap_nf != c->B.cap_nf || b.compact != c->B.compact)
-            return fail(SLAMGPU_ERR_INVALID, "shard %d was created with different sizes", h);
-        void *p[kDistArrays];
-        if (h == shard) {
-            if (int rc = dist_alloc_shared(c)) return rc;
-            dist_arrays(c, p);
-        } else if (b.pid == (int64_t) getpid()) {
-            for (int k = 0; k < kDistArrays; k++) p[k] = b.ptr[k];
-            if (b.device != c->cfg.device) {
-                hipError_t e = hipDeviceEnablePeerAccess(b.device, 0);
-                if (e != hipSuccess && e != hipErrorPeerAccessAlreadyEnabled)
-                    return fail(SLAMGPU_ERR_HIP, "no peer access from device %d to device %d: %s", c->cfg.device, b.device, hipGetErrorString(e));
-                (void) hipGetLastError();
-            }
-        } else {
-            for (int k = 0; k < kDistArrays; k++) {
-                if (!b.ptr[k]) {
-                    p[k] = nullptr;
-                    continue;
-                }
-                hipError_t e = hipIpcOpenMemHandle(&p[k], b.handle[k], hipIpcMemLazyEnablePeerAccess);
-                if (e != hipSuccess) return fail(SLAMGPU_ERR_HIP, "hipIpcOpenMemHandle (shard %d, array %d): %s", h, k, hipGetErrorString(e));
-                c->ipc_opened.push_back(p[k]);
-            }
-        }
-        PeerPtrs &t = table[(size_t) h];
-        int k = 0;
-        for (int q = 0; q < 2; q++) t.poseA[q] = (float4 *) p[k++];
-        for (int q = 0; q < 2; q++) t.poseB[q] = (float4 *) p[k++];
-        for (int q = 0; q < 2; q++) t.poseC[q] = (float2 *) p[k++];
-        for (int q = 0; q < 2; q++) t.lmkA[q] = (float4 *) p[k++];
-        for (int q = 0; q < 2; q++) t.lmkB[q] = (float *) p[k++];
-        for (int q = 0; q < 2; q++) t.gen[q] = (int32_t *) p[k++];
-        for (int q = 0; q < 2; q++) t.lcum[q] = (float *) p[k++];
-        for (int q = 0; q < 2; q++) t.gtot[q] = (float *) p[k++];
-        c->peer_flags[h] = (uint32_t *) p[k++];
-        t.flags = c->peer_flags[h];
-    }
-    HIP_TRY(hipMalloc((void **) &c->peers_dev, sizeof(PeerPtrs) * (size_t) n_shards));
-    HIP_TRY(hipMemcpy(c->peers_dev, table.data(), sizeof(PeerPtrs) * (size_t) n_shards, hipMemcpyHostToDevice));
-    HIP_TRY(hipDeviceSynchronize());
-    c->B.peers = c->peers_dev;
-    c->B.n_shards = n_shards;
-    c->B.shard = shard;
-    c->B.first = (int32_t) c->cfg.first_particle;
-    c->B.div_n = (unsigned long long) (~0ull / (unsigned long long) c->B.ncap) + 1ull;
-    c->dist = true;
-    return 0;
-}
-
-int slamgpu_dist_step(slamgpu_ctx *c, const float *controls, int32_t n_controls, const float Q[4], float dt, const float *zf,
-                      const int32_t *idf, int32_t m, const float *zn, int32_t n, const float R[4], int32_t record_estimate) {
-    if (int rc = check_ctx(c)) return rc;
-    if (!c->dist) return fail(SLAMGPU_ERR_INVALID, "not a distributed context: call slamgpu_dist_connect first");
-    if (c->cfg.rng_mode != SLAMGPU_RNG_PHILOX) return fail(SLAMGPU_ERR_INVALID, "distributed contexts draw their noise on the device (SLAMGPU_RNG_PHILOX)");
-    if (n_controls < 0 || (n_controls > 0 && !controls)) return fail(SLAMGPU_ERR_INVALID, "bad control list");
-    for (int k = 0; k < n_controls; k++)
-        if (int rc = slamgpu_predict(c, controls[3 * k], controls[3 * k + 1], Q, dt, controls[3 * k + 2], nullptr)) return rc;
-    if (record_estimate && c->hist_n >= kHistCap) return fail(SLAMGPU_ERR_CAPACITY, "estimate history full (%d): fetch it", kHistCap);
-    if (int rc = do_update(c, zf, idf, m, zn, n, R, nullptr, nullptr, false)) return rc;
-    if (record_estimate) {
-        c->hist_n++;  // slot filled when the partials of this update are reduced (next launch / fetch)
-        c->est_fresh = false;
-    }
-    return gather_totals(c);
-}
-
-int slamgpu_dist_comm_id(void *id, int32_t bytes) {
-    if (!id || bytes < (int32_t) sizeof(ncclUniqueId)) return fail(SLAMGPU_ERR_INVALID, "id buffer must hold %d bytes", (int) sizeof(ncclUniqueId));
-    if (!rccl()) return fail(SLAMGPU_ERR_HIP, "librccl.so.1 not found: %s", dlerror());
-    ncclUniqueId u;
-    RCCL_TRY(rccl()->GetUniqueId(&u));
-    memcpy(id, &u, sizeof u);
-    return (int) sizeof u > 0 ? 0 : 0;
-}
-
-int slamgpu_dist_comm_init(slamgpu_ctx *c, const void *id, int32_t n_ranks, int32_t rank) {
-    if (int rc = check_ctx(c)) return rc;
-    if (!c->dist) return fail(SLAMGPU_ERR_INVALID, "not a distributed context: call slamgpu_dist_connect first");
-    if (!id || n_ranks != c->B.n_shards || rank != c->B.shard) return fail(SLAMGPU_ERR_INVALID, "communicator geometry differs from the shard geometry");
-    if (c->comm) return fail(SLAMGPU_ERR_INVALID, "communicator already initialised");
-    if (!rccl()) return fail(SLAMGPU_ERR_HIP, "librccl.so.1 not found: %s", dlerror());
-    HIP_TRY(hipSetDevice(c->cfg.device));
-    ncclUniqueId u;
-    memcpy(&u, id, sizeof u);
-    ncclComm_t comm = nullptr;
-    RCCL_TRY(rccl()->CommInitRank(&comm, n_ranks, u, rank));
-    c->comm = comm;
-    return 0;
-}
-
-int slamgpu_dist_comm_info(slamgpu_ctx *c, int32_t *n_ranks, int32_t *rank) {
-    if (int rc = check_ctx(c)) return rc;
-    if (!c->comm) return fail(SLAMGPU_ERR_INVALID, "no communicator inside the library (slamgpu_dist_comm_init)");
-    if (!rccl() || !rccl()->CommCount || !rccl()->CommUserRank) return fail(SLAMGPU_ERR_HIP, "this librccl has no ncclCommCount / ncclCommUserRank");
-    int n = 0, r = 0;
-    RCCL_TRY(rccl()->CommCount(static_cast<ncclComm_t>(c->comm), &n));
-    RCCL_TRY(rccl()->CommUserRank(static_cast<ncclComm_t>(c->comm), &r));
-    if (n_ranks) *n_ranks = n;
-    if (rank) *rank = r;
-    return 0;
-}
-
-int slamgpu_dist_remote_reads(slamgpu_ctx *c, uint64_t *particles) {
-    if (int rc = check_ctx(c)) return rc;
-    if (!particles) return fail(SLAMGPU_ERR_INVALID, "null output");
-    if (!c->dist) return fail(SLAMGPU_ERR_INVALID, "not a distributed context");
-    HIP_TRY(hipSetDevice(c->cfg.device));
-    // (only this word, and without running any outstanding stage: a distributed context's stages need the other shards)
-    unsigned long long v = 0;
-    HIP_TRY(hipMemcpyAsync(&v, &c->B.ctrl->remote_reads, sizeof v, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    *particles = v;
-    c->count_remote = true;  // (the counter is kept from the first time it is asked for: ADVICE r4)
-    return 0;
-}
-
-int slamgpu_dist_totals(slamgpu_ctx *c, const float **local_dev, float **gathered_dev, int32_t *floats_per_shard) {
-    if (int rc = check_ctx(c)) return rc;
-    if (!c->dist) return fail(SLAMGPU_ERR_INVALID, "not a distributed context");
-    const int par = (int) (c->obs_step & 1);
-    if (local_dev) *local_dev = c->ws.blk_w[par];
-    if (gathered_dev) *gathered_dev = c->gtot_dev[par];
-    if (floats_per_shard) *floats_per_shard = 2 * c->ws.nblocks;  // [w | q] (linear weights)
-    return 0;
-}
-
-int slamgpu_dist_set_collective(slamgpu_ctx *c, int32_t mode) {
-    if (int rc = check_ctx(c)) return rc;
-    if (!c->dist) return fail(SLAMGPU_ERR_INVALID, "not a distributed context");
-    if (mode != SLAMGPU_DIST_GATHER && mode != SLAMGPU_DIST_PUSH && mode != SLAMGPU_DIST_FOLD)
-        return fail(SLAMGPU_ERR_INVALID, "unknown collective %d", mode);
-    if (mode != SLAMGPU_DIST_GATHER)
-        for (int h = 0; h < c->B.n_shards; h++)
-            if (!c->peer_flags[h]) return fail(SLAMGPU_ERR_INVALID, "push collective unavailable: shard %d has no flag words (fine-grained memory)", h);
-    if (c->unplanned.has && !c->dist_clean) return fail(SLAMGPU_ERR_INVALID, "switch the collective between settled steps (slamgpu_dist_settle)");
-    c->dist_push = mode == SLAMGPU_DIST_PUSH;
-    c->dist_fold = mode == SLAMGPU_DIST_FOLD;
-    return 0;
-}
-
-int slamgpu_dist_handshake_test(slamgpu_ctx *c, int32_t iters, double *usec, int32_t *ok) {
-    if (int rc = check_ctx(c)) return rc;
-    if (!c->dist) return fail(SLAMGPU_ERR_INVALID, "not a distributed context");
-    for (int h = 0; h < c->B.n_shards; h++)
-        if (!c->peer_flags[h]) return fail(SLAMGPU_ERR_INVALID, "push collective unavailable: shard %d has no flag words (fine-grained memory)", h);
-    if (iters < 1 || iters > 100000) return fail(SLAMGPU_ERR_INVALID, "iters out of range");
-    HIP_TRY(hipSetDevice(c->cfg.device));
-    if (!usec && !ok) {  // enqueue only: several contexts driven by one thread must all have theirs queued before anybody waits
-        for (int i = 0; i < iters; i++)
-            if (int rc = launch_flags(c)) return rc;
-        return 0;
-    }
-    hipEvent_t e0, e1;
-    HIP_TRY(hipEventCreate(&e0));
-    HIP_TRY(hipEventCreate(&e1));
-    HIP_TRY(hipEventRecord(e0, c->stream));
-    for (int i = 0; i < iters; i++)
-        if (int rc = launch_flags(c)) return rc;
-    HIP_TRY(hipEventRecord(e1, c->stream));
-    HIP_TRY(hipEventSynchronize(e1));
-    float ms = 0.0f;
-    HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
-    (void) hipEventDestroy(e0);
-    (void) hipEventDestroy(e1);
-    uint32_t err = 0;
-    HIP_TRY(hipMemcpy(&err, c->flags_dev + kMaxShards, sizeof err, hipMemcpyDeviceToHost));
-    if (usec) *usec = 1e3 * (double) ms / iters;
-    if (ok) *ok = err == 0 ? 1 : 0;
-    return 0;
-}
-
-int slamgpu_dist_collective_status(slamgpu_ctx *c, int32_t *ok) {
-    if (int rc = check_ctx(c)) return rc;
-    if (!c->dist || !ok) return fail(SLAMGPU_ERR_INVALID, "not a distributed context / null output");
-    if (!c->flags_dev) {
-        *ok = 1;  // (no flag words: the push collective was never in use)
-        return 0;
-    }
-    HIP_TRY(hipSetDevice(c->cfg.device));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    uint32_t err = 0;
-    HIP_TRY(hipMemcpy(&err, c->flags_dev + kMaxShards, sizeof err, hipMemcpyDeviceToHost));
-    *ok = err == 0 ? 1 : 0;
-    return 0;
-}
-
-int slamgpu_dist_gather(slamgpu_ctx *c) {
-    if (int rc = check_ctx(c)) return rc;
-    if (!c->dist || !c->comm) return fail(SLAMGPU_ERR_INVALID, "no communicator: slamgpu_dist_comm_init first");
-    HIP_TRY(hipSetDevice(c->cfg.device));
-    const int par = (int) (c->obs_step & 1);
-    Timed t(c, "allgather");  // (slamgpu_profile: an event pair around the collective, like around every launch)
-    RCCL_TRY(rccl()->AllGather(c->ws.blk_w[par], c->gtot_dev[par], (size_t) 2 * c->ws.nblocks, ncclFloat, (ncclComm_t) c->comm, c->stream));
-    return 0;
-}
-
-int slamgpu_dist_settle(slamgpu_ctx *c) {
-    if (int rc = check_ctx(c)) return rc;
-    if (!c->dist) return fail(SLAMGPU_ERR_INVALID, "not a distributed context");
-    if (c->dist_clean || !c->unplanned.has) return 0;
-    // an update without observations and without predicts: applies the pending resampling stage (inline plan) and leaves
-    // a stage that is a no-op.  It must not consume an observation-step number: the Philox streams of later steps would shift.
-    const float R[4] = {1.0f, 0.0f, 0.0f, 1.0f};
-    if (int rc = flush_predict(c)) return rc;
-    if (int rc = do_update(c, nullptr, nullptr, 0, nullptr, 0, R, nullptr, nullptr, false)) return rc;
-    c->rng_skew++;
-    c->unplanned.has = false;  // the stage this launch leaves is a no-op: weights normalised, nothing to resample
-    c->dist_clean = true;
-    if (c->dist_fold) return launch_flags(c);  // no next launch to carry the barrier: a flag kernel closes the step
-    return gather_totals(c);
-}
-
-// ---- all shards of a distributed run in ONE process (slam-backend -gpus k, rehearsals on one GPU) ------------------------
-struct slamgpu_dist_group {
-    std::vector<slamgpu_ctx *> ctx;
-    std::vector<ncclComm_t> comms;  // one per context when every context has a device of its own
-    bool shared = false;            // all contexts on one device and one stream: dist_gather_kernel instead of RCCL
-    bool push = false;              // push collective in use (slamgpu_dist_step runs the flag barrier itself)
-};
-
-namespace {
-int group_gather(slamgpu_dist_group *g) {
-    const int k = (int) g->ctx.size();
-    if (g->push) return 0;
-    if (g->shared) {
-        DistGatherArgs A{};
-        A.n_shards = k;
-        A.floats_per_shard = 2 * g->ctx[0]->ws.nblocks;
-        for (int i = 0; i < k; i++) {
-            const int par = (int) (g->ctx[i]->obs_step & 1);
-            A.local[i] = g->ctx[i]->ws.blk_w[par];
-            A.gathered[i] = g->ctx[i]->gtot_dev[par];
-        }
-        HIP_TRY(hipSetDevice(g->ctx[0]->cfg.device));
-        g->ctx[0]->k->dist_gather(g->ctx[0]->stream, A);
-        HIP_TRY(hipGetLastError());
-        return 0;
-    }
-    RCCL_TRY(rccl()->GroupStart());
-    for (int i = 0; i < k; i++) {
-        slamgpu_ctx *c = g->ctx[i];
-        const int par = (int) (c->obs_step & 1);
-        RCCL_TRY(rccl()->AllGather(c->ws.blk_w[par], c->gtot_dev[par], (size_t) 2 * c->ws.nblocks, ncclFloat, g->comms[i], c->stream));
-    }
-    RCCL_TRY(rccl()->GroupEnd());
-    return 0;
-}
-}  // namespace
-
-int slamgpu_dist_group_create(slamgpu_ctx **ctxs, int32_t k, slamgpu_dist_group **out) {
-    if (!ctxs || !out || k < 1 || k > kMaxShards) return fail(SLAMGPU_ERR_INVALID, "bad context list");
-    for (int i = 0; i < k; i++)
-        if (!ctxs[i]) return fail(SLAMGPU_ERR_INVALID, "null context %d", i);
-    bool same = true, distinct = true;
-    for (int i = 0; i < k; i++)
-        for (int j = 0; j < i; j++) {
-            if (ctxs[i]->cfg.device == ctxs[j]->cfg.device) distinct = false;
-            else same = false;
-        }
-    if (k > 1 && !same && !distinct) return fail(SLAMGPU_ERR_INVALID, "contexts must all share one device or each have a device of its own");
-    const bool shared = k > 1 ? same : true;
-    if (shared)
-        for (int i = 1; i < k; i++)
-            if (ctxs[i]->stream != ctxs[0]->stream)
-                return fail(SLAMGPU_ERR_INVALID, "contexts sharing a device must share a stream (slamgpu_config.external_stream)");
-    std::vector<DistBlob> blobs((size_t) k);
-    for (int i = 0; i < k; i++)
-        if (int rc = slamgpu_dist_export(ctxs[i], &blobs[(size_t) i])) return rc;
-    for (int i = 0; i < k; i++)
-        if (int rc = slamgpu_dist_connect(ctxs[i], k, i, blobs.data())) return rc;
-    auto *g = new slamgpu_dist_group();
-    g->ctx.assign(ctxs, ctxs + k);
-    g->shared = shared;
-    if (!shared) {
-        // every shard has a device (hence hardware queues) of its own: try the push collective first -- a few barriers with
-        // everybody's queued before anybody is waited for -- and keep the RCCL all-gather for when a peer does not arrive
-        bool push = getenv("SLAMGPU_GROUP_NO_PUSH") == nullptr;
-        for (int i = 0; i < k && push; i++) push = slamgpu_dist_handshake_test(ctxs[i], 5, nullptr, nullptr) == 0;
-        for (int i = 0; i < k; i++) {
-            int32_t ok = 0;
-            if (slamgpu_dist_collective_status(ctxs[i], &ok) != 0 || !ok) push = false;
-        }
-        if (push) {
-            for (int i = 0; i < k; i++)
-                if (int rc = slamgpu_dist_set_collective(ctxs[i], SLAMGPU_DIST_PUSH)) {
-                    delete g;
-                    return rc;
-                }
-            g->push = true;
-            *out = g;
-            return 0;
-        }
-        if (!rccl()) {
-            delete g;
-            return fail(SLAMGPU_ERR_HIP, "librccl.so.1 not found: %s", dlerror());
-        }
-        std::vector<int> devs((size_t) k);
-        for (int i = 0; i < k; i++) devs[(size_t) i] = ctxs[i]->cfg.device;
-        g->comms.resize((size_t) k);
-        ncclResult_t r = rccl()->CommInitAll(g->comms.data(), k, devs.data());
-        if (r != ncclSuccess) {
-            delete g;
-            return fail(SLAMGPU_ERR_HIP, "ncclCommInitAll: %s", rccl()->GetErrorString(r));
-        }
-    }
-    *out = g;
-    return 0;
-}
-
-void slamgpu_dist_group_destroy(slamgpu_dist_group *g) {
-    if (!g) return;
-    for (slamgpu_ctx *c : g->ctx) {
-        (void) hipSetDevice(c->cfg.device);
-        (void) hipStreamSynchronize(c->stream);
-    }
-    for (ncclComm_t c : g->comms) (void) rccl()->CommDestroy(c);
-    delete g;
-}
-
-int slamgpu_dist_group_step(slamgpu_dist_group *g, const float *controls, int32_t n_controls, const float Q[4], float dt, const float *zf,
-                            const int32_t *idf, int32_t m, const float *zn, int32_t n, const float R[4], int32_t record_estimate) {
-    if (!g) return fail(SLAMGPU_ERR_INVALID, "null group");
-    for (slamgpu_ctx *c : g->ctx)
-        if (int rc = slamgpu_dist_step(c, controls, n_controls, Q, dt, zf, idf, m, zn, n, R, record_estimate)) return rc;
-    return group_gather(g);
-}
-
-int slamgpu_dist_group_settle(slamgpu_dist_group *g) {
-    if (!g) return fail(SLAMGPU_ERR_INVALID, "null group");
-    for (slamgpu_ctx *c : g->ctx)
-        if (int rc = slamgpu_dist_settle(c)) return rc;
-    if (int rc = group_gather(g)) return rc;
-    for (slamgpu_ctx *c : g->ctx) {  // reads of one shard (flatten) follow: every shard's launch must have finished
-        HIP_TRY(hipSetDevice(c->cfg.device));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-    }
-    for (slamgpu_ctx *c : g->ctx)
-        if (int rc = barrier_check(c)) return rc;
-    return 0;
-}
-
-int slamgpu_dist_group_history(slamgpu_dist_group *g, double *xyt, float *neff, int32_t *resampled, int32_t *status, int32_t max_count,
-                               int32_t *count) {
-    if (!g || !count) return fail(SLAMGPU_ERR_INVALID, "null group / count");
-    if (int rc = slamgpu_dist_group_settle(g)) return rc;
-    const int k = (int) g->ctx.size();
-    int nmin = std::max(max_count, 0);
-    for (slamgpu_ctx *c : g->ctx) nmin = std::min(nmin, c->hist_n);
-    std::vector<double> raw((size_t) 4 * std::max(nmin, 1)), best((size_t) std::max(nmin, 1), -1.0e300);
-    if (xyt) std::fill(xyt, xyt + 3 * (size_t) nmin, 0.0);
-    const double n_all = (double) g->ctx[0]->B.n * k;
-    for (int i = 0; i < k; i++) {
-        int32_t got = 0;
-        // (Neff / decision / status of a stage are the same on every shard: the last shard's copy stays)
-        if (int rc = slamgpu_dist_history_fetch(g->ctx[i], raw.data(), neff, resampled, status, nmin, &got)) return rc;
-        if (got != nmin) return fail(SLAMGPU_ERR_INVALID, "shard %d recorded %d steps, expected %d", i, got, nmin);
-        if (xyt)
-            for (int t = 0; t < nmin; t++) {
-                xyt[3 * t] += raw[4 * (size_t) t];
-                xyt[3 * t + 1] += raw[4 * (size_t) t + 1];
-                if (raw[4 * (size_t) t + 3] > best[(size_t) t]) {  // strict: ties keep the lowest global index
-                    best[(size_t) t] = raw[4 * (size_t) t + 3];
-                    xyt[3 * t + 2] = raw[4 * (size_t) t + 2];
-                }
-            }
-    }
-    if (xyt)
-        for (int t = 0; t < nmin; t++) {
-            xyt[3 * t] /= n_all;
-            xyt[3 * t + 1] /= n_all;
-        }
-    *count = nmin;
-    return 0;
-}
-
-int slamgpu_dist_group_download(slamgpu_dist_group *g, float *xv, float *Pv9, float *w, float *xf, float *Pf4) {
-    if (!g) return fail(SLAMGPU_ERR_INVALID, "null group");
-    if (int rc = slamgpu_dist_group_settle(g)) return rc;
-    const size_t n = (size_t) g->ctx[0]->B.n, nf = (size_t) g->ctx[0]->nf;
-    for (size_t i = 0; i < g->ctx.size(); i++)
-        if (int rc = slamgpu_download(g->ctx[i], xv ? xv + 3 * n * i : nullptr, Pv9 ? Pv9 + 9 * n * i : nullptr, w ? w + n * i : nullptr,
-                                      xf ? xf + 2 * nf * n * i : nullptr, Pf4 ? Pf4 + 4 * nf * n * i : nullptr))
-            return rc;
-    for (slamgpu_ctx *c : g->ctx) {  // a shard's flatten reads its peers: nobody may step before everybody has read
-        HIP_TRY(hipSetDevice(c->cfg.device));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-    }
-    return 0;
-}
-
 int slamgpu_dev_alloc(slamgpu_ctx *c, uint64_t bytes, void **ptr) {
     if (int rc = check_ctx(c)) return rc;
     if (!ptr) return fail(SLAMGPU_ERR_INVALID, "null pointer");
@@ -2332,75 +1584,13 @@ int slamgpu_dev_copy_async(slamgpu_ctx *c, void *dst, const void *src, uint64_t 
     return 0;
 }
 
-int slamgpu_shard_estimate_async(slamgpu_ctx *c) {
-    if (int rc = check_ctx(c)) return rc;
-    if (c->hist_n >= kHistCap) return fail(SLAMGPU_ERR_CAPACITY, "estimate history full (%d)", kHistCap);
-    HIP_TRY(hipSetDevice(c->cfg.device));
-    if (int rc = flush_predict(c)) return rc;
-    if (c->shard_est_fresh) {
-        // nothing moved since shard_finalize_kernel left this update's partials: their one-block reduction rides in the
-        // next update launch (or runs when the history is fetched)
-        if (int rc = flush_stages(c)) return rc;  // (an older reduction still outstanding)
-        c->unreduced.has = true;
-        c->unreduced.par = 0;
-        c->unreduced.hist = c->hist_dev + kHistStride * (size_t) c->hist_n;
-        c->shard_est_fresh = false;
-    } else {
-        if (int rc = materialize(c)) return rc;
-        if (int rc = flush_stages(c)) return rc;
-        Timed t(c, "estimate");
-        c->k->estimate(c->stream, c->B, c->ws, c->hist_dev + kHistStride * (size_t) c->hist_n);
-    }
-    c->hist_n++;
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-
-int slamgpu_shard_estimate_fetch(slamgpu_ctx *c, double *raw4, int32_t max_count, int32_t *count) {
-    if (int rc = check_ctx(c)) return rc;
-    if (!count) return fail(SLAMGPU_ERR_INVALID, "null count");
-    HIP_TRY(hipSetDevice(c->cfg.device));
-    if (int rc = flush_stages(c)) return rc;
-    std::vector<double> h;
-    if (int rc = history_to_host(c, h)) return rc;
-    const int n = c->hist_n < std::max(max_count, 0) ? c->hist_n : std::max(max_count, 0);
-    if (raw4)
-        for (int i = 0; i < n; i++)
-            for (int k = 0; k < 4; k++) raw4[4 * (size_t) i + k] = h[(size_t) kHistStride * i + k];
-    *count = n;
-    if (int rc = keep_history_tail(c, h, n)) return rc;
-    c->est_fresh = false;
-    return 0;
-}
-
-int slamgpu_shard_estimate(slamgpu_ctx *c, double out[4]) {
-    if (int rc = check_ctx(c)) return rc;
-    if (!out) return fail(SLAMGPU_ERR_INVALID, "null output");
-    HIP_TRY(hipSetDevice(c->cfg.device));
-    if (int rc = flush_predict(c)) return rc;
-    if (int rc = materialize(c)) return rc;
-    if (int rc = flush_stages(c)) return rc;
-    {
-        Timed t(c, "estimate");
-        c->k->estimate(c->stream, c->B, c->ws, nullptr);
-    }
-    HIP_TRY(hipGetLastError());
-    if (int rc = read_ctrl(c)) return rc;
-    for (int i = 0; i < 4; i++) out[i] = c->ctrl_host->est[i];
-    return 0;
-}
-
 int slamgpu_estimate(slamgpu_ctx *c, double xyt[3]) {
     if (int rc = check_ctx(c)) return rc;
     if (!xyt) return fail(SLAMGPU_ERR_INVALID, "null output");
     HIP_TRY(hipSetDevice(c->cfg.device));
     if (int rc = flush_predict(c)) return rc;
-    if (!c->est_fresh) {
-        if (int rc = materialize(c)) return rc;
-        if (int rc = flush_stages(c)) return rc;
-        Timed t(c, "estimate");
-        c->k->estimate(c->stream, c->B, c->ws, nullptr);
-    }
+    if (!c->est_fresh)
+        if (int rc = estimate_now(c, nullptr)) return rc;
     HIP_TRY(hipGetLastError());
     if (int rc = read_ctrl(c)) return rc;
     xyt[0] = c->ctrl_host->est[0] / (double) c->B.n;
@@ -2416,10 +1606,7 @@ int slamgpu_estimate_async(slamgpu_ctx *c) {
     if (int rc = flush_predict(c)) return rc;
     if (!c->est_fresh) {
         // the particle set changed since the last update (predicts / upload): reduce it now
-        if (int rc = materialize(c)) return rc;
-        if (int rc = flush_stages(c)) return rc;
-        Timed t(c, "estimate");
-        c->k->estimate(c->stream, c->B, c->ws, c->hist_dev + kHistStride * (size_t) c->hist_n);
+        if (int rc = estimate_now(c, c->hist_dev + kHistStride * (size_t) c->hist_n)) return rc;
         HIP_TRY(hipGetLastError());
     }
     // else: slot hist_n is filled when the partials of the last update are reduced (next update launch / finish)
@@ -2432,14 +1619,7 @@ int slamgpu_history_fetch(slamgpu_ctx *c, double *xyt, float *neff, int32_t *res
                           int32_t *count) {
     if (int rc = check_ctx(c)) return rc;
     if (!count) return fail(SLAMGPU_ERR_INVALID, "null count");
-    HIP_TRY(hipSetDevice(c->cfg.device));
-    if (int rc = flush_stages(c)) return rc;
-    std::vector<double> h;
-    if (int rc = history_to_host(c, h)) return rc;
-    if (int rc = persist_check(c)) return rc;
-    const int n = c->hist_n < std::max(max_count, 0) ? c->hist_n : std::max(max_count, 0);
-    for (int i = 0; i < n; i++) {
-        const double *e = h.data() + (size_t) kHistStride * i;
+    return history_take(c, max_count, count, [&](int i, const double *e) {
         if (xyt) {
             xyt[3 * i] = e[0] / (double) c->B.n;
             xyt[3 * i + 1] = e[1] / (double) c->B.n;
@@ -2448,34 +1628,7 @@ int slamgpu_history_fetch(slamgpu_ctx *c, double *xyt, float *neff, int32_t *res
         if (neff) neff[i] = (float) e[4];
         if (resampled) resampled[i] = ((int32_t) e[5]) & 1;
         if (status) status[i] = ((int32_t) e[5]) >> 1;
-    }
-    *count = n;
-    if (int rc = keep_history_tail(c, h, n)) return rc;
-    c->est_fresh = false;
-    return 0;
-}
-
-int slamgpu_dist_history_fetch(slamgpu_ctx *c, double *raw4, float *neff, int32_t *resampled, int32_t *status, int32_t max_count,
-                               int32_t *count) {
-    if (int rc = check_ctx(c)) return rc;
-    if (!count) return fail(SLAMGPU_ERR_INVALID, "null count");
-    HIP_TRY(hipSetDevice(c->cfg.device));
-    if (int rc = flush_stages(c)) return rc;
-    std::vector<double> h;
-    if (int rc = history_to_host(c, h)) return rc;
-    const int n = c->hist_n < std::max(max_count, 0) ? c->hist_n : std::max(max_count, 0);
-    for (int i = 0; i < n; i++) {
-        const double *e = h.data() + (size_t) kHistStride * i;
-        if (raw4)
-            for (int k = 0; k < 4; k++) raw4[4 * (size_t) i + k] = e[k];
-        if (neff) neff[i] = (float) e[4];
-        if (resampled) resampled[i] = ((int32_t) e[5]) & 1;
-        if (status) status[i] = ((int32_t) e[5]) >> 1;
-    }
-    *count = n;
-    if (int rc = keep_history_tail(c, h, n)) return rc;
-    c->est_fresh = false;
-    return barrier_check(c);
+    }, persist_check);
 }
 
 int slamgpu_estimate_fetch(slamgpu_ctx *c, double *xyt, int32_t max_count, int32_t *count) {
@@ -2671,7 +1824,7 @@ int slamgpu_update_special_modes(int32_t spec) {
 int slamgpu_sync(slamgpu_ctx *c) {
     if (int rc = check_ctx(c)) return rc;
     HIP_TRY(hipSetDevice(c->cfg.device));
-    if (!c->dist) {  // (a distributed context's outstanding stage needs the other shards: it stays queued)
+    if (!c->mg.dist) {  // (a distributed context's outstanding stage needs the other shards: it stays queued)
         if (int rc = flush_predict(c)) return rc;
         if (int rc = flush_stages(c)) return rc;
     }
@@ -2754,7 +1907,7 @@ int slamgpu_download_range(slamgpu_ctx *c, int32_t first, int32_t count, float *
 int slamgpu_peek(slamgpu_ctx *c, int32_t first, int32_t stride, int32_t count, float *xv, float *Pv9, float *w, float *xf,
                  float *Pf4) {
     if (int rc = check_ctx(c)) return rc;
-    if (c->dist || c->cfg.n_particles_global != c->cfg.n_particles)
+    if (!is_single(c))
         return fail(SLAMGPU_ERR_INVALID, "slamgpu_peek: single contexts only (shards: slamgpu_download / slamgpu_dist_group_download)");
     if (first < 0 || count < 0 || stride < 1 || (count > 0 && (int64_t) first + (int64_t) (count - 1) * stride >= c->B.n))
         return fail(SLAMGPU_ERR_INVALID, "particles %d + k * %d, k < %d, outside [0, %d)", first, stride, count, c->B.n);
@@ -2883,7 +2036,7 @@ int slamgpu_upload(slamgpu_ctx *c, int32_t nf, const float *xv, const float *Pv9
         HIP_TRY(hipMemcpy(c->B.lmkB[0], lb.data(), sizeof(float) * lb.size(), hipMemcpyHostToDevice));
     }
     // every landmark row live in buffer 0, every record in its particle's own slot
-    c->pool_used = 0;
+    c->mg.pool_used = 0;
     std::fill(c->live_flag.begin(), c->live_flag.end(), 0);
     c->B.slot = c->slot;
     c->k->identity(c->stream, c->B, cur, 0);  // every landmark in genealogy row 0: own slot
@@ -2902,7 +2055,7 @@ int slamgpu_upload(slamgpu_ctx *c, int32_t nf, const float *xv, const float *Pv9
         if (c->as.retired_dev) HIP_TRY(hipMemset(c->as.retired_dev, 0, sizeof(uint32_t) * (((size_t) c->B.cap_nf + 31) / 32)));
     }
     c->est_fresh = false;
-    c->shard_est_fresh = false;
+    c->mg.shard_est_fresh = false;
     if (c->path.cap > 0) {  // a new set: nothing descends from the retained records
         c->path.first = c->path.next;
         if (int rc = path_identity(c)) return rc;

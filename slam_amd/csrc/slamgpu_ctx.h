@@ -1,4 +1,4 @@
-// The context of libslamgpu.so and what its translation units (slamgpu.cpp, association.cpp, posterior.cpp) share.  Private: not
+// The context of libslamgpu.so and what its translation units (slamgpu.cpp, association.cpp, posterior.cpp, multigpu.cpp) share.  Private: not
 // installed, and no function declared here is exported (hidden visibility).
 #pragma once
 #define SLAMGPU_EXPERIMENTAL 1  // (the library defines every entry point, the experimental ones included)
@@ -17,6 +17,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <map>
 #include <string>
 #include <vector>
@@ -159,6 +160,38 @@ struct Assoc {
     DevCounters mx_stats_dev;
 };
 
+// The state of the multi-GPU layer (multigpu.cpp): slamgpu_ctx::mg.  multigpu_release frees it.
+struct Multi {
+    // sharded operation (slamgpu_shard_*): the resampling plan comes back through a pinned mirror and a sequence word the plan kernel
+    // stores after it (both allocated with the context: slamgpu_shard_plan allocates nothing)
+    ShardPlan *plan_host = nullptr;
+    uint32_t *plan_seq_host = nullptr;
+    uint32_t plan_seq = 0;
+    DevBuf<float4> poolA_dev;     // the arrival pool (Buffers::poolA / poolB point here), allocated by the first unpack that needs it
+    DevBuf<float> poolB_dev;
+    int64_t pool_used = 0;        // arrival-pool slots handed out since the pool was last emptied (flatten / settle / upload)
+    bool shard_settled = false;   // the sharded resampling stage of this step moved everything physically (records arrived)
+    bool shard_est_fresh = false; // est_part holds this shard's partials of the last update (shard_finalize_kernel)
+    bool own_totals = true;       // ws.blk_w[0] is this context's allocation (not a caller-provided collective buffer) ...
+    float *own_blk_w = nullptr;   // ... which waits here meanwhile (slamgpu_shard_set_totals_buffer)
+    // distributed operation (slamgpu_dist_*)
+    bool dist = false, dist_clean = false;
+    DevBuf<PeerPtrs> peers_dev;
+    DevBuf<float> gtot_dev[2];    // everybody's block totals, by step parity
+    std::vector<void *> ipc_opened;
+    void *comm = nullptr;  // ncclComm_t: when set, slamgpu_dist_step / _settle run the all-gather themselves
+    // push collective (slamgpu_dist_set_collective): the update launch stores its totals into every shard's table and a
+    // one-wave flag kernel is the barrier
+    bool count_remote = false;   // slamgpu_dist_remote_reads has been asked for: the update launches keep the counter from then on
+    bool dist_push = false;
+    bool dist_fold = false;  // push + the barrier folded into the head of the next update launch (SLAMGPU_DIST_FOLD)
+    // [kMaxShards] flag words + the error word + the go words.  A raw pointer, not a DevBuf: fine-grained memory from
+    // hipExtMallocWithFlags, and null is a supported state (a stack without it loses the push collective, nothing else)
+    uint32_t *flags_dev = nullptr;
+    uint32_t *peer_flags[kMaxShards] = {};
+    uint32_t flag_seq = 0;
+};
+
 #pragma GCC visibility pop
 
 // (default visibility, as ever: its implicit members are among the library's weak symbols)
@@ -198,19 +231,11 @@ struct slamgpu_ctx {
     hipEvent_t timer_a = nullptr, timer_b = nullptr;  // slamgpu_timer_start / _stop
     double predict_bytes = 0;
     bool own_stream = true;
-    ShardPlan *plan_dev = nullptr, *plan_host = nullptr;  // sharded resampling plan (device + pinned mirror)
-    uint32_t *plan_seq_host = nullptr;  // pinned: sequence number the plan kernel stores after the plan
-    uint32_t plan_seq = 0;
     // Ctrl.live / Ctrl.pend slot the next launch reads (kernels.h: Ctrl); flipped after every launch that may
     // change the live buffer (resample_kernel, gather_kernel, shard_commit_kernel)
-    int64_t pool_used = 0;        // arrival-pool slots handed out since the pool was last emptied (flatten / settle / upload)
-    bool shard_settled = false;   // the sharded resampling stage of this step moved everything physically (records arrived)
     int slot = 0;
     int keep_slot = 0;            // which WeightScratch::keep buffer holds the ancestors of the last update
     bool maybe_pending = false;   // the last update may have left a lazy gather (only the device knows)
-    bool shard_est_fresh = false; // sharded: est_part holds this shard's partials of the last update (shard_finalize_kernel)
-    bool own_totals = true;       // ws.blk_w is this context's allocation (not a caller-provided collective buffer)
-    float *own_blk_w = nullptr;
     // Pose-estimate pipeline of the single-context path.  The resampling stage of update t (Neff, decision, ancestors,
     // estimate partials) normally runs INSIDE the launch of update t+1 (UpdateArgs::plan_inline) and its partials are
     // reduced by the helper block of launch t+2; anything that needs results earlier runs them as launches of their own.
@@ -240,20 +265,7 @@ struct slamgpu_ctx {
     std::vector<int32_t> live_rows;  // rows with refcnt > 0
     std::vector<int32_t> live_pos;   // [cap_rows] position in live_rows, -1 if not live
     int32_t *erow_dev = nullptr, *rows_dev = nullptr;  // device copies for gather / flatten / shard pack + unpack
-    // distributed operation (slamgpu_dist_*)
-    bool dist = false, dist_clean = false;
-    PeerPtrs *peers_dev = nullptr;
-    float *gtot_dev[2] = {nullptr, nullptr};
-    std::vector<void *> ipc_opened;
-    void *comm = nullptr;  // ncclComm_t: when set, slamgpu_dist_step / _settle run the all-gather themselves
-    // push collective (slamgpu_dist_set_collective): the update launch stores its totals into every shard's table and a
-    // one-wave flag kernel is the barrier; flags_dev = [kMaxShards] flag words + the error word, fine-grained memory
-    bool count_remote = false;   // slamgpu_dist_remote_reads has been asked for: the update launches keep the counter from then on
-    bool dist_push = false;
-    bool dist_fold = false;  // push + the barrier folded into the head of the next update launch (SLAMGPU_DIST_FOLD)
-    uint32_t *flags_dev = nullptr;
-    uint32_t *peer_flags[kMaxShards] = {};
-    uint32_t flag_seq = 0;
+    Multi mg;                        // sharded and distributed operation (multigpu.cpp)
     // observation front end (slamgpu_set_map / slamgpu_observe)
     float *map_dev = nullptr, *obs_r_dev = nullptr;
     int32_t *table_dev = nullptr;
@@ -369,7 +381,11 @@ struct Timed {
     }
 };
 
-// slamgpu.cpp's, as the association and posterior layers call them
+inline int64_t n_global(const slamgpu_ctx *c) { return c->cfg.n_particles_global > 0 ? c->cfg.n_particles_global : c->cfg.n_particles; }
+// a context that holds the whole particle set: neither connected to peers nor a shard of a larger set
+inline bool is_single(const slamgpu_ctx *c) { return !c->mg.dist && c->cfg.n_particles_global == c->cfg.n_particles; }
+
+// slamgpu.cpp's, as the association, posterior and multi-GPU layers call them
 int check_ctx(slamgpu_ctx *c);
 int book_pull(slamgpu_ctx *c);
 int sync_tables(slamgpu_ctx *c);
@@ -386,6 +402,20 @@ void rows_add_live(slamgpu_ctx *c, int r);
 void rows_remove_live(slamgpu_ctx *c, int r);
 void compose_predicts(PredictArgs &P);
 RngArgs rng_args(const slamgpu_ctx *c, uint32_t step);
+int do_update(slamgpu_ctx *c, const float *zf, const int32_t *idf, int32_t m, const float *zn, int32_t n, const float R[4], const float *normals,
+              const float *strata, bool sharded);
+void rows_reset(slamgpu_ctx *c, int nf);
+// the control list of a step entry point as slamgpu_predict calls (controls: [n_controls][3]: V, G, phi_true)
+int predict_controls(slamgpu_ctx *c, const float *controls, int32_t n_controls, const float Q[4], float dt);
+// the set as it stands, reduced now: the outstanding stages, then estimate_kernel into history slot `hist` (null: Ctrl.est only)
+int estimate_now(slamgpu_ctx *c, double *hist);
+// The body of the history fetches: the outstanding stages, the recorded entries to the host, per_entry(i, entry) for the first
+// min(hist_n, max_count) of them, *count, the rest kept (keep_history_tail).  `ready`, where given, is asked once the device has
+// been waited for and before an entry is handed out
+int history_take(slamgpu_ctx *c, int32_t max_count, int32_t *count, const std::function<void(int, const double *)> &per_entry,
+                 int (*ready)(slamgpu_ctx *) = nullptr);
+// multigpu.cpp's
+void multigpu_release(slamgpu_ctx *c);  // slamgpu_destroy's share of this layer
 // association.cpp's, as the steps and the posterior layer call them
 int pp_pull(slamgpu_ctx *c);
 int pp_dev_stage(slamgpu_ctx *c);
