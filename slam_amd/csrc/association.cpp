@@ -632,8 +632,8 @@ int pp_check(slamgpu_ctx *c, const float *z, int32_t nz, const float R[4], const
         return fail(SLAMGPU_ERR_INVALID, "per-particle association: excl_base, excl_per_m, unique_ratio >= 0");
     if (!is_single(c) || c->mg.pool_used != 0)
         return fail(SLAMGPU_ERR_INVALID, "per-particle association: single contexts only");
-    if (c->innov.cap > 0 && nz > c->innov.cap)  // (refused before anything of the step has moved: its record could not be made)
-        return fail(SLAMGPU_ERR_CAPACITY, "per-particle association: %d observations, the innovation ring holds %d entries", nz, c->innov.cap);
+    if (c->po.innov.cap > 0 && nz > c->po.innov.cap)  // (refused before anything of the step has moved: its record could not be made)
+        return fail(SLAMGPU_ERR_CAPACITY, "per-particle association: %d observations, the innovation ring holds %d entries", nz, c->po.innov.cap);
     if (c->mid_compact)
         if (int rc = demote_to_plain(c)) return rc;
     if (c->B.compact)
@@ -771,7 +771,7 @@ int do_update_particle(slamgpu_ctx *c, const float *z, int32_t nz, const float R
     // (the records as they stand before the update: the device's tables are still those of sync_tables above)
     pp_missed(c, nf0, c->as.retired_dev, first_dev, (census_taken || lists_done) && opt->mode == SLAMGPU_ASSOC_LISTS, nullptr);
     HIP_TRY(hipGetLastError());
-    if (c->innov.cap > 0)  // the innovation ring: every particle against its own match, the same records, before the update takes them
+    if (c->po.innov.cap > 0)  // the innovation ring: every particle against its own match, the same records, before the update takes them
         if (int rc = innov_append_labels(c, nz, nf0, R)) return rc;
     c->obs_step++;
     c->as.pp_lab_nz = nz;
@@ -830,19 +830,9 @@ int do_update_particle(slamgpu_ctx *c, const float *z, int32_t nz, const float R
     c->fresh_row = e_new;
     memcpy(U.R, R, sizeof U.R);
     {
-        const int slot = (int) (c->pkt_seq++ % kRing);
-        if (c->pkt_ev_used[slot]) HIP_TRY(hipEventSynchronize(c->pkt_ev[slot]));
-        char *ph = c->pkt_host + (size_t) slot * c->pkt_bytes;
-        ObsPacket *hp = reinterpret_cast<ObsPacket *>(ph);
-        hp->m = m;
-        hp->n = n;
-        hp->nf = nf0;
-        hp->n_rows = n_rows;
-        hp->e_new = e_new;
-        hp->status = 0;
-        hp->cap = 0;  // dense layout
-        hp->pad = 0;
-        int32_t *hidf = reinterpret_cast<int32_t *>(hp + 1);
+        BigPacket bp;
+        if (int rc = bp.begin(c, m, n, nf0, n_rows, e_new)) return rc;
+        int32_t *hidf = reinterpret_cast<int32_t *>(bp.host + 1);
         float *hzf = reinterpret_cast<float *>(hidf + m);
         float *hzn = hzf + 2 * m;
         for (int k = 0; k < m; k++) hidf[k] = touched[(size_t) k].second;
@@ -851,11 +841,8 @@ int do_update_particle(slamgpu_ctx *c, const float *z, int32_t nz, const float R
         if (m) memcpy(hrow, rows_of.data(), sizeof(int32_t) * (size_t) m);
         if (n_rows) memcpy(hrow + m, c->live_rows.data(), sizeof(int32_t) * (size_t) n_rows);
         const size_t used = sizeof(ObsPacket) + sizeof(int32_t) * (size_t) m + sizeof(float) * 2 * ((size_t) m + n) + sizeof(int32_t) * ((size_t) m + n_rows);
-        char *pd = c->pkt_dev + (size_t) slot * c->pkt_bytes;
-        HIP_TRY(hipMemcpyAsync(pd, ph, used, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipEventRecord(c->pkt_ev[slot], c->stream));
-        c->pkt_ev_used[slot] = true;
-        U.big = reinterpret_cast<const ObsPacket *>(pd);
+        if (int rc = bp.commit(c, used)) return rc;
+        U.big = reinterpret_cast<const ObsPacket *>(bp.dev);
     }
     if (e_new >= 0) {
         if (c->refcnt[(size_t) e_new] > 0) rows_add_live(c, e_new);
@@ -946,9 +933,9 @@ int associate_lists(slamgpu_ctx *c, const float *z, int32_t nz, const float R[4]
 int nz_bound(const slamgpu_ctx *c, const float *xt, float max_range) {
     const float x = xt[0], y = xt[1], r = max_range * 1.001f + 1e-3f;
     const double cph = cos((double) xt[2]), sph = sin((double) xt[2]);
-    const float *lx = c->map_host.data(), *ly = lx + c->map_n;
+    const float *lx = c->fe.map_host.data(), *ly = lx + c->fe.map_n;
     int n = 0;
-    for (int j = 0; j < c->map_n; j++) {
+    for (int j = 0; j < c->fe.map_n; j++) {
         const float dx = lx[j] - x, dy = ly[j] - y;
         if (!(fabsf(dx) < r && fabsf(dy) < r)) continue;
         const double d2 = (double) dx * dx + (double) dy * dy;
@@ -966,11 +953,11 @@ int slamgpu_update_particle(slamgpu_ctx *c, const float *z, int32_t nz, const fl
     if (opt->mode == SLAMGPU_ASSOC_LISTS && nz > kAssocMaxCells * kAssocMaxCells)
         return fail(SLAMGPU_ERR_CAPACITY, "SLAMGPU_ASSOC_LISTS: %d observations in one step (at most %d)", nz, kAssocMaxCells * kAssocMaxCells);
     if (nz == 0) {  // (no observation, no update: fastslam2wrapper.cpp:84-95)
-        if (c->innov.cap > 0) c->innov_records++;  // (the innovation ring: a record without entries)
+        if (c->po.innov.cap > 0) c->po.innov_records++;  // (the innovation ring: a record without entries)
         return 0;
     }
     HIP_TRY(hipSetDevice(c->cfg.device));
-    if (c->innov.cap > 0)  // (the innovation ring: room for this step's record, before the association or anything else of the step runs)
+    if (c->po.innov.cap > 0)  // (the innovation ring: room for this step's record, before the association or anything else of the step runs)
         if (int rc = innov_labels_room(c, nz)) return rc;
     if (int rc = pp_reserve(c, nz, 1)) return rc;
     // data association sampling: the labels drawn, their ratios into the weights (the step's draws follow the host's obs_step: the
@@ -1004,7 +991,7 @@ int slamgpu_update_labels(slamgpu_ctx *c, const float *z, int32_t nz, const floa
     if (int rc = pp_check(c, z, nz, R, opt)) return rc;
     if (nz > 0 && !labels) return fail(SLAMGPU_ERR_INVALID, "slamgpu_update_labels: labels[N * nz]");
     if (nz == 0) {
-        if (c->innov.cap > 0) c->innov_records++;  // (the innovation ring: a record without entries)
+        if (c->po.innov.cap > 0) c->po.innov_records++;  // (the innovation ring: a record without entries)
         return 0;
     }
     if (int rc = book_pull(c)) return rc;
@@ -1013,7 +1000,7 @@ int slamgpu_update_labels(slamgpu_ctx *c, const float *z, int32_t nz, const floa
         if (labels[q] >= c->nf || labels[q] < SLAMGPU_ASSOC_DISCARD)
             return fail(SLAMGPU_ERR_INVALID, "slamgpu_update_labels: label %d of particle %d, observation %d (%d landmarks)", (int) labels[q], (int) (q / nz), (int) (q % nz), c->nf);
     HIP_TRY(hipSetDevice(c->cfg.device));
-    if (c->innov.cap > 0)  // (the innovation ring: room for this step's record, before the labels go down or anything else of the step runs)
+    if (c->po.innov.cap > 0)  // (the innovation ring: room for this step's record, before the labels go down or anything else of the step runs)
         if (int rc = innov_labels_room(c, nz)) return rc;
     if (int rc = pp_reserve(c, nz, 1)) return rc;
     c->as.pp_census_done = false;  // (the caller's labels: nobody has taken their census; never sampled)
@@ -1040,7 +1027,7 @@ int pp_setup(slamgpu_ctx *c) {
     if (int rc = book_staging(c)) return rc;  // (DevBook, refcnt_dev)
     if (!c->as.retired_dev || c->as.retired.empty())
         if (int rc = retired_upload(c)) return rc;
-    const int w = std::max(c->map_n, c->B.cap_nf);
+    const int w = std::max(c->fe.map_n, c->B.cap_nf);
     if (c->as.pp_words_w < w) {
         c->as.pp_words_w = 0;
         if (int rc = c->as.pp_words_dev.reserve((size_t) kPpWords * c->B.cap_nf + 3 * (size_t) w, "the device-driven step's tables")) return rc;
@@ -1056,10 +1043,10 @@ PpArgs pp_args(slamgpu_ctx *c) {
     int32_t *b = c->as.pp_words_dev;
     PpArgs P{};
     P.st = c->as.pp_st_dev;
-    P.book = c->book_dev;
+    P.book = c->fe.book_dev;
     P.erow = c->erow_dev;
     P.live = c->live_dev;
-    P.refcnt = c->refcnt_dev;
+    P.refcnt = c->fe.refcnt_dev;
     P.rows = c->rows_dev;
     P.partial = b;
     P.dead = b + cn;
@@ -1072,7 +1059,7 @@ PpArgs pp_args(slamgpu_ctx *c) {
     P.newk = P.news + w;
     P.idn = P.newk + w;
     P.retired = c->as.retired_dev;
-    P.obs = c->obs_out_dev;
+    P.obs = c->fe.obs_out_dev;
     P.pkt = reinterpret_cast<ObsPacket *>(c->as.pp_pkt_dev.p);
     P.report = c->as.pp_report_dev + 8 * (size_t) c->as.pp_report_n;
     P.hist = c->hist_dev + kHistStride * (size_t) c->hist_n;
@@ -1124,13 +1111,13 @@ int pp_push(slamgpu_ctx *c, int census_cap) {
     DevBook hb{};
     hb.nf = nf;
     hb.fresh_row = -1;
-    hb.status = c->front_status;
+    hb.status = c->fe.front_status;
     HIP_TRY(hipMemcpy(c->as.pp_words_dev, words.data(), sizeof(int32_t) * words.size(), hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(c->as.pp_st_dev, &st, sizeof st, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(c->book_dev, &hb, sizeof hb, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(c->fe.book_dev, &hb, sizeof hb, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(c->erow_dev, c->erow.data(), sizeof(int32_t) * cnz, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(c->live_dev, c->live_flag.data(), sizeof(int32_t) * cnz, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(c->refcnt_dev, c->refcnt.data(), sizeof(int32_t) * (size_t) cr, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(c->fe.refcnt_dev, c->refcnt.data(), sizeof(int32_t) * (size_t) cr, hipMemcpyHostToDevice));
     if (!rows.empty()) HIP_TRY(hipMemcpy(c->rows_dev, rows.data(), sizeof(int32_t) * rows.size(), hipMemcpyHostToDevice));
     if (c->as.retired_stale)
         if (int rc = retired_upload(c)) return rc;
@@ -1160,10 +1147,10 @@ int pp_pull(slamgpu_ctx *c) {
     DevBook hb{};
     HIP_TRY(hipMemcpy(words.data(), c->as.pp_words_dev, sizeof(int32_t) * words.size(), hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(&st, c->as.pp_st_dev, sizeof st, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(&hb, c->book_dev, sizeof hb, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&hb, c->fe.book_dev, sizeof hb, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(erow.data(), c->erow_dev, sizeof(int32_t) * cnz, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(live.data(), c->live_dev, sizeof(int32_t) * cnz, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(ref.data(), c->refcnt_dev, sizeof(int32_t) * (size_t) cr, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(ref.data(), c->fe.refcnt_dev, sizeof(int32_t) * (size_t) cr, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(mask.data(), c->as.retired_dev, sizeof(uint32_t) * mask.size(), hipMemcpyDeviceToHost));
     if (hb.nf < 0 || hb.nf > cn) return fail(SLAMGPU_ERR_INVALID, "device bookkeeping corrupt: nf = %d", hb.nf);
     c->nf = hb.nf;
@@ -1263,24 +1250,7 @@ int pp_dev_iteration(slamgpu_ctx *c, int32_t nc, const float *controls, const fl
         if (int rc = slamgpu_predict(c, controls[3 * k], controls[3 * k + 1], Q, dt, controls[3 * k + 2], nullptr)) return rc;
     }
     // the observation, as slamgpu_observe makes it (raw z / nz stay on the device)
-    ObserveArgs A{};
-    A.lm = c->map_dev;
-    A.table = c->table_dev;
-    A.nlm = c->map_n;
-    A.nf = c->obs_nf;
-    A.x = xtrue[0];
-    A.y = xtrue[1];
-    A.phi = xtrue[2];
-    A.max_range = max_range;
-    A.sr = sqrtf(R[0]);
-    A.sb = sqrtf(R[3]);
-    A.noise = noise;
-    A.r1 = c->obs_r_dev;
-    A.r2 = c->obs_r_dev + c->map_n;
-    A.k0 = (uint32_t) c->cfg.seed;
-    A.k1 = (uint32_t) (c->cfg.seed >> 32);
-    A.step = ++c->observe_step;
-    A.out = c->obs_out_dev;
+    const ObserveArgs A = observe_args(c, xtrue, max_range, R, noise);
     {
         Timed t(c, "observe");
         c->k->observe(c->stream, A);
@@ -1296,14 +1266,14 @@ int pp_dev_iteration(slamgpu_ctx *c, int32_t nc, const float *controls, const fl
     // (the radii: every observation the map allows, whatever the lists grid; the count comes from the observation.  Sampling: the walk
     // reads the step from PpState.  The buffers: slamgpu_run_particle reserved them)
     AssocRule rule;
-    if (int rc = particle_rule(c, opt, R, c->obs_out_dev, nullptr, 0, c->map_n, rule)) return rc;
+    if (int rc = particle_rule(c, opt, R, c->fe.obs_out_dev, nullptr, 0, c->fe.map_n, rule)) return rc;
     c->as.pp_lab_nz = -1;
     AssocListArgs G;
     if (bound >= 0) {
         // the boxes of the slots the previous iteration wrote, the geometry, one list per observation, the walk (+ the census)
         lists_args(c, bound, R, opt, G);
-        G.obs = c->obs_out_dev;
-        G.book = c->book_dev;
+        G.obs = c->fe.obs_out_dev;
+        G.book = c->fe.book_dev;
         G.retired = P.retired;
         G.census_first = P.first;
         G.census_news = P.news;
@@ -1351,7 +1321,7 @@ int pp_dev_iteration(slamgpu_ctx *c, int32_t nc, const float *controls, const fl
     UpdateArgs U{};
     U.method = c->cfg.method;
     U.m = c->B.cap_nf;  // (upper bounds: the kernel reads the packet's header)
-    U.n = c->map_n;
+    U.n = c->fe.map_n;
     U.e_new = -1;
     U.dev_packet = 1;
     U.big = reinterpret_cast<const ObsPacket *>(c->as.pp_pkt_dev.p);
@@ -1363,8 +1333,8 @@ int pp_dev_iteration(slamgpu_ctx *c, int32_t nc, const float *controls, const fl
     U.n_effective = c->cfg.n_effective;
     U.logw = c->cfg.log_weights;
     U.stamps = c->stamps_dev;
-    PerParticle ppa{c->as.pp_obs_dev, reinterpret_cast<const float *>(c->obs_out_dev + 1), P.idn, c->as.pp_wf_dev, c->as.pp_any_dev, c->map_n, 0,
-                    c->obs_out_dev, &c->as.pp_st_dev.p->step};
+    PerParticle ppa{c->as.pp_obs_dev, reinterpret_cast<const float *>(c->fe.obs_out_dev + 1), P.idn, c->as.pp_wf_dev, c->as.pp_any_dev, c->fe.map_n, 0,
+                    c->fe.obs_out_dev, &c->as.pp_st_dev.p->step};
     {
         Timed t(c, c->cfg.method == SLAMGPU_FASTSLAM2 ? "fs2_update" : "fs1_update");
         c->k->update_particle(c->stream, c->B, PredictArgs{}, U, rng_args(c, 0), c->ws, ppa, !c->special_ok);
@@ -1392,11 +1362,11 @@ int slamgpu_run_particle(slamgpu_ctx *c, int32_t K, const int32_t *n_controls, c
         return fail(SLAMGPU_ERR_INVALID, "slamgpu_run_particle: create the context with SLAMGPU_FLAG_PARTICLE_MAPS | SLAMGPU_FLAG_DEVICE_OBSERVE");
     if (noise != 0 && noise != 2) return fail(SLAMGPU_ERR_INVALID, "slamgpu_run_particle: noise must be 0 or 2");
     if (c->cfg.rng_mode == SLAMGPU_RNG_TAPE) return fail(SLAMGPU_ERR_INVALID, "slamgpu_run_particle: TAPE-mode contexts take their draws per step");
-    if (c->path.cap > 0)
+    if (c->po.path.cap > 0)
         return fail(SLAMGPU_ERR_INVALID, "slamgpu_run_particle: not while the path is recorded (its resampling decisions are known to the device only): "
                                          "slamgpu_path_enable(ctx, 0) first, or drive the steps with slamgpu_update_particle");
     if (K == 0) return 0;
-    if (!c->map_dev) return fail(SLAMGPU_ERR_INVALID, "slamgpu_run_particle: no map: call slamgpu_set_map first");
+    if (!c->fe.map_dev) return fail(SLAMGPU_ERR_INVALID, "slamgpu_run_particle: no map: call slamgpu_set_map first");
     if (opt->mode < SLAMGPU_ASSOC_AUTO || opt->mode > SLAMGPU_ASSOC_LISTS) return fail(SLAMGPU_ERR_INVALID, "unknown association mode %d", opt->mode);
     if (opt->mode == SLAMGPU_ASSOC_GRID)
         return fail(SLAMGPU_ERR_INVALID, "slamgpu_run_particle: the association is the exhaustive scan or the lists (SLAMGPU_ASSOC_EXHAUSTIVE, _AUTO or _LISTS)");
@@ -1414,9 +1384,9 @@ int slamgpu_run_particle(slamgpu_ctx *c, int32_t K, const int32_t *n_controls, c
     if ((int64_t) c->as.pp_report_n + K > kHistCap)
         return fail(SLAMGPU_ERR_CAPACITY, "slamgpu_run_particle: %d iterations would overflow the report ring (%d of %d entries in use): call "
                                           "slamgpu_particle_report_fetch first", (int) K, c->as.pp_report_n, kHistCap);
-    if (!lists && (double) c->B.n * (double) c->B.cap_nf * (double) c->map_n > 4e10)
+    if (!lists && (double) c->B.n * (double) c->B.cap_nf * (double) c->fe.map_n > 4e10)
         return fail(SLAMGPU_ERR_CAPACITY, "slamgpu_run_particle: the exhaustive scan of %d particles x %d slots x %d observations is too much for one launch",
-                    c->B.n, c->B.cap_nf, c->map_n);
+                    c->B.n, c->B.cap_nf, c->fe.map_n);
     // (the lists: every iteration's observations bounded from the map and the true pose -- the lists grid; at most kAssocMaxCells^2)
     std::vector<int> bounds((size_t) K, -1);
     if (lists)
@@ -1428,15 +1398,15 @@ int slamgpu_run_particle(slamgpu_ctx *c, int32_t K, const int32_t *n_controls, c
         }
     if (int rc = persist_check(c)) return rc;
     HIP_TRY(hipSetDevice(c->cfg.device));
-    const int nmax = std::min(c->map_n, c->B.cap_nf);
-    if (int rc = pp_reserve_particles(c, c->map_n, (size_t) c->B.cap_nf + nmax + 1)) return rc;  // (pp_nz_cap stays the host path's: PpState::census_cap)
+    const int nmax = std::min(c->fe.map_n, c->B.cap_nf);
+    if (int rc = pp_reserve_particles(c, c->fe.map_n, (size_t) c->B.cap_nf + nmax + 1)) return rc;  // (pp_nz_cap stays the host path's: PpState::census_cap)
     if (int rc = pp_setup(c)) return rc;
     if (lists)
         if (int rc = lists_buffers(c)) return rc;
     if (excl_spacing_on(c, opt))
-        if (int rc = excl_rho_reserve(c, c->map_n)) return rc;
+        if (int rc = excl_rho_reserve(c, c->fe.map_n)) return rc;
     if (c->as.das_on)
-        if (int rc = das_reserve(c, c->map_n)) return rc;
+        if (int rc = das_reserve(c, c->fe.map_n)) return rc;
     if (c->as.mx_on)
         if (int rc = mx_reserve(c)) return rc;
     const bool was_host = !c->as.pp_on_device;
@@ -1469,7 +1439,7 @@ int slamgpu_run_particle(slamgpu_ctx *c, int32_t K, const int32_t *n_controls, c
             std::string why = slamgpu_last_error();
             return fail(rc, "slamgpu_run_particle: iteration %d of %d: %s", (int) k, (int) K, why.c_str());
         }
-        if (c->pose.cap > 0)  // pose entry r beside history entry r
+        if (c->po.pose.cap > 0)  // pose entry r beside history entry r
             if (int rc = pose_append(c)) {
                 std::string why = slamgpu_last_error();
                 return fail(rc, "slamgpu_run_particle: iteration %d of %d: %s", (int) k, (int) K, why.c_str());
@@ -1640,7 +1610,7 @@ int slamgpu_particle_labels(slamgpu_ctx *c, int32_t *labels, int64_t max_count, 
     int32_t n = c->as.pp_lab_nz;
     if (n < 0) {  // (the device-driven iteration's count)
         ObserveOut head{};
-        HIP_TRY(hipMemcpy(&head, c->obs_out_dev, sizeof head, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(&head, c->fe.obs_out_dev, sizeof head, hipMemcpyDeviceToHost));
         n = head.nz;
     }
     const size_t S = (size_t) c->B.ncap, N = (size_t) c->B.n;

@@ -114,36 +114,36 @@ int ring_fetch(slamgpu_ctx *c, const Ring &r, const void *ring_dev, size_t row, 
 }
 
 // ---- path recording (slamgpu_path_*; kernels.h: PathRing) ----
-PathRing path_ring(const slamgpu_ctx *c) { return PathRing{c->path_rec_dev, c->path.cap}; }
+PathRing path_ring(const slamgpu_ctx *c) { return PathRing{c->po.path_rec_dev, c->po.path.cap}; }
 
 // the checks slamgpu_path_fetch / _trace / _summary share
 int path_check(slamgpu_ctx *c, const char *who, int64_t first, int64_t count) {
-    if (c->path.cap == 0) return fail(SLAMGPU_ERR_INVALID, "%s: recording is off (slamgpu_path_enable)", who);
-    return ring_check(c->path, who, "records", first, count);
+    if (c->po.path.cap == 0) return fail(SLAMGPU_ERR_INVALID, "%s: recording is off (slamgpu_path_enable)", who);
+    return ring_check(c->po.path, who, "records", first, count);
 }
 
 // ---- pose posterior (slamgpu_pose_*; kernels.h: PoseSummaryArgs) ----
 int pose_tiles(const slamgpu_ctx *c) { return (c->B.n + kPoseTile - 1) / kPoseTile; }
 
 int pose_reserve(slamgpu_ctx *c) {
-    if (c->pose_dev) return 0;
+    if (c->po.pose_dev) return 0;
     const size_t total = sizeof(double) * ((size_t) kPoseFields * (size_t) pose_tiles(c) + kPoseStride);
-    hipError_t e = hipMalloc((void **) &c->pose_dev, total);
+    hipError_t e = hipMalloc((void **) &c->po.pose_dev, total);
     if (e != hipSuccess) {
         (void) hipGetLastError();
-        c->pose_dev = nullptr;
+        c->po.pose_dev = nullptr;
         return fail(SLAMGPU_ERR_ALLOC, "hipMalloc(%zu): %s", total, hipGetErrorString(e));
     }
     return 0;
 }
-double *pose_staging(const slamgpu_ctx *c) { return c->pose_dev + (size_t) kPoseFields * (size_t) pose_tiles(c); }
+double *pose_staging(const slamgpu_ctx *c) { return c->po.pose_dev + (size_t) kPoseFields * (size_t) pose_tiles(c); }
 
 // the summary of the set as it stands (the caller has brought it there), into `out_dev`: two launches, nothing else
 int pose_launch(slamgpu_ctx *c, double *out_dev) {
     PoseSummaryArgs A{};
     A.tiles = pose_tiles(c);
     A.logw = c->cfg.log_weights;
-    A.part = c->pose_dev;
+    A.part = c->po.pose_dev;
     A.out = out_dev;
     c->B.slot = c->slot;
     if (int rc = launch(c, "pose_summary", [&] { c->k->pose_summary(c->stream, c->B, c->ws, A); })) return rc;
@@ -188,30 +188,30 @@ int innov_labels_check(slamgpu_ctx *c, const char *fn, const float *z, int32_t n
 // the synchronisation of its hipFree.
 constexpr size_t kInnovLabPiece = (size_t) 1 << 18;  // words
 int innov_labels_down(slamgpu_ctx *c, const int32_t *labels, int32_t nz, int32_t *dst) {
-    static_assert(sizeof c->innov_lab_ev / sizeof c->innov_lab_ev[0] == 2, "two pieces");
-    if (!c->innov_lab_host) {
-        hipError_t e = hipHostMalloc((void **) &c->innov_lab_host, sizeof(int32_t) * 2 * kInnovLabPiece, hipHostMallocDefault);
+    static_assert(sizeof c->po.innov_lab_ev / sizeof c->po.innov_lab_ev[0] == 2, "two pieces");
+    if (!c->po.innov_lab_host) {
+        hipError_t e = hipHostMalloc((void **) &c->po.innov_lab_host, sizeof(int32_t) * 2 * kInnovLabPiece, hipHostMallocDefault);
         if (e != hipSuccess) {
             (void) hipGetLastError();
-            c->innov_lab_host = nullptr;
+            c->po.innov_lab_host = nullptr;
             return fail(SLAMGPU_ERR_ALLOC, "hipHostMalloc(%zu): %s", sizeof(int32_t) * 2 * kInnovLabPiece, hipGetErrorString(e));
         }
     }
     const size_t N = (size_t) c->B.n, total = N * (size_t) nz;
     size_t q = 0, i = 0;  // dst[at] = labels of observation q, particle i
     for (size_t at = 0; at < total; at += kInnovLabPiece) {
-        const int k = (int) (c->innov_lab_seq++ & 1);
-        if (!c->innov_lab_ev[k]) HIP_TRY(hipEventCreateWithFlags(&c->innov_lab_ev[k], hipEventDisableTiming));
-        if (c->innov_lab_ev_used[k]) HIP_TRY(hipEventSynchronize(c->innov_lab_ev[k]));
-        int32_t *h = c->innov_lab_host + kInnovLabPiece * (size_t) k;
+        const int k = (int) (c->po.innov_lab_seq++ & 1);
+        if (!c->po.innov_lab_ev[k]) HIP_TRY(hipEventCreateWithFlags(&c->po.innov_lab_ev[k], hipEventDisableTiming));
+        if (c->po.innov_lab_ev_used[k]) HIP_TRY(hipEventSynchronize(c->po.innov_lab_ev[k]));
+        int32_t *h = c->po.innov_lab_host + kInnovLabPiece * (size_t) k;
         const size_t n = std::min(kInnovLabPiece, total - at);
         for (size_t d = 0; d < n; d++) {
             h[d] = labels[i * (size_t) nz + q];
             if (++i == N) i = 0, q++;
         }
         HIP_TRY(hipMemcpyAsync(dst + at, h, sizeof(int32_t) * n, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipEventRecord(c->innov_lab_ev[k], c->stream));
-        c->innov_lab_ev_used[k] = true;
+        HIP_TRY(hipEventRecord(c->po.innov_lab_ev[k], c->stream));
+        c->po.innov_lab_ev_used[k] = true;
     }
     return 0;
 }
@@ -255,46 +255,46 @@ InnovLayout innov_layout(const slamgpu_ctx *c, int32_t m, size_t label_words) {
 // into the staging area, from where out_dev / hold_dev point at them.  Enqueued; the caller has checked the packet (m > 0)
 int innov_launch(slamgpu_ctx *c, const InnovPacket &P, int32_t m, const float *R, bool ring, const double **out_dev, const int32_t **hold_dev) {
     static_assert(SLAMGPU_INNOV_STRIDE == kInnStride && SLAMGPU_INNOV_SLOT_PER_PARTICLE == kInnSlotPerParticle, "public / device summary layout");
-    static_assert(sizeof c->innov_ev / sizeof c->innov_ev[0] == kInnovStage, "staging slots");
+    static_assert(sizeof c->po.innov_ev / sizeof c->po.innov_ev[0] == kInnovStage, "staging slots");
     if (int rc = summary_enter(c, "", kSettle | kTables)) return rc;
     const size_t M = (size_t) m;
     const InnovLayout V = innov_layout(c, m, P.labels ? M * (size_t) c->B.n : 0);
     const int tiles = V.tiles, chunk = V.chunk;
-    if (int rc = c->msum.reserve(V.L.total())) return rc;
+    if (int rc = c->po.msum.reserve(V.L.total())) return rc;
     const float *z_dev = P.z_dev;
     if (P.zf) {
         // the packet: through a pinned slot of the context's own, so that the caller's arrays are free again when the call returns
-        if (M > c->innov_host_m) {
+        if (M > c->po.innov_host_m) {
             for (int k = 0; k < kInnovStage; k++)
-                if (c->innov_ev_used[k]) HIP_TRY(hipEventSynchronize(c->innov_ev[k]));
-            if (c->innov_host) (void) hipHostFree(c->innov_host);
-            c->innov_host = nullptr;
-            c->innov_host_m = 0;
+                if (c->po.innov_ev_used[k]) HIP_TRY(hipEventSynchronize(c->po.innov_ev[k]));
+            if (c->po.innov_host) (void) hipHostFree(c->po.innov_host);
+            c->po.innov_host = nullptr;
+            c->po.innov_host_m = 0;
             const size_t want = std::max<size_t>(M, 64);
-            hipError_t e = hipHostMalloc((void **) &c->innov_host, 12 * want * kInnovStage, hipHostMallocDefault);
+            hipError_t e = hipHostMalloc((void **) &c->po.innov_host, 12 * want * kInnovStage, hipHostMallocDefault);
             if (e != hipSuccess) {
                 (void) hipGetLastError();
-                c->innov_host = nullptr;
+                c->po.innov_host = nullptr;
                 return fail(SLAMGPU_ERR_ALLOC, "hipHostMalloc(%zu): %s", 12 * want * kInnovStage, hipGetErrorString(e));
             }
-            c->innov_host_m = want;
+            c->po.innov_host_m = want;
         }
-        const int k = (int) (c->innov_seq++ % kInnovStage);
-        if (!c->innov_ev[k]) HIP_TRY(hipEventCreateWithFlags(&c->innov_ev[k], hipEventDisableTiming));
-        if (c->innov_ev_used[k]) HIP_TRY(hipEventSynchronize(c->innov_ev[k]));
-        char *h = c->innov_host + 12 * c->innov_host_m * (size_t) k;
+        const int k = (int) (c->po.innov_seq++ % kInnovStage);
+        if (!c->po.innov_ev[k]) HIP_TRY(hipEventCreateWithFlags(&c->po.innov_ev[k], hipEventDisableTiming));
+        if (c->po.innov_ev_used[k]) HIP_TRY(hipEventSynchronize(c->po.innov_ev[k]));
+        char *h = c->po.innov_host + 12 * c->po.innov_host_m * (size_t) k;
         memcpy(h, P.zf, sizeof(float) * 2 * M);
         if (P.idf) memcpy(h + sizeof(float) * 2 * M, P.idf, sizeof(int32_t) * M);
-        HIP_TRY(hipMemcpyAsync(V.zf.at(c->msum), h, P.idf ? 12 * M : 8 * M, hipMemcpyHostToDevice, c->stream));  // (zf | idf: adjacent in both places)
-        HIP_TRY(hipEventRecord(c->innov_ev[k], c->stream));
-        c->innov_ev_used[k] = true;
-        z_dev = V.zf.at(c->msum);
+        HIP_TRY(hipMemcpyAsync(V.zf.at(c->po.msum), h, P.idf ? 12 * M : 8 * M, hipMemcpyHostToDevice, c->stream));  // (zf | idf: adjacent in both places)
+        HIP_TRY(hipEventRecord(c->po.innov_ev[k], c->stream));
+        c->po.innov_ev_used[k] = true;
+        z_dev = V.zf.at(c->po.msum);
     }
     const int32_t *lab_dev = P.lab_dev;
     int64_t lstride = P.lstride;
     if (P.labels) {
-        if (int rc = innov_labels_down(c, P.labels, m, V.lab.at(c->msum))) return rc;
-        lab_dev = V.lab.at(c->msum);
+        if (int rc = innov_labels_down(c, P.labels, m, V.lab.at(c->po.msum))) return rc;
+        lab_dev = V.lab.at(c->po.msum);
         lstride = c->B.n;
     }
     c->B.slot = c->slot;
@@ -305,29 +305,29 @@ int innov_launch(slamgpu_ctx *c, const InnovPacket &P, int32_t m, const float *R
         A.count = std::min(chunk, m - at);
         A.tiles = tiles;
         A.logw = c->cfg.log_weights;
-        A.part = V.part.at(c->msum);
-        A.wpart = V.wpart.at(c->msum);
+        A.part = V.part.at(c->po.msum);
+        A.wpart = V.wpart.at(c->po.msum);
         I.zf = z_dev + (size_t) 2 * at;
         if (P.per_particle()) {
             I.labels = lab_dev + (size_t) lstride * (size_t) at;
             I.lstride = lstride;
             I.nf = P.nf;  // (the slots BEFORE the step for its own record, where the step may already have opened new ones: c->nf for the caller's)
         } else {
-            I.idf = V.idf.at(c->msum) + at;
+            I.idf = V.idf.at(c->po.msum) + at;
         }
         I.r00 = R[0];
         I.r10 = R[2];
         I.r11 = R[3];
         if (ring) {
-            A.out = c->innov_ring_dev;
+            A.out = c->po.innov_ring_dev;
             A.holders = nullptr;
-            I.ring_cap = c->innov.cap;
-            I.ring_at = c->innov.next + at;
-            I.tag = c->innov_tag_dev;
-            I.record = (int32_t) c->innov_records;
+            I.ring_cap = c->po.innov.cap;
+            I.ring_at = c->po.innov.next + at;
+            I.tag = c->po.innov_tag_dev;
+            I.record = (int32_t) c->po.innov_records;
         } else {
-            A.out = V.out.at(c->msum) + (size_t) kInnStride * at;
-            A.holders = V.hold.at(c->msum) + at;
+            A.out = V.out.at(c->po.msum) + (size_t) kInnStride * at;
+            A.holders = V.hold.at(c->po.msum) + at;
         }
         if (P.per_particle()) {
             if (int rc = launch(c, "innovation_summary_labels", [&] { c->k->innovation_summary_labels(c->stream, c->B, c->ws, I); })) return rc;
@@ -336,8 +336,8 @@ int innov_launch(slamgpu_ctx *c, const InnovPacket &P, int32_t m, const float *R
         }
         if (int rc = launch(c, "innovation_finish", [&] { c->k->innovation_finish(c->stream, I); })) return rc;
     }
-    if (out_dev) *out_dev = V.out.at(c->msum);
-    if (hold_dev) *hold_dev = V.hold.at(c->msum);
+    if (out_dev) *out_dev = V.out.at(c->po.msum);
+    if (hold_dev) *hold_dev = V.hold.at(c->po.msum);
     return 0;
 }
 
@@ -349,16 +349,16 @@ int path_compose(slamgpu_ctx *c) {
     if (int rc = flush_stages(c)) return rc;
     c->B.slot = c->slot;
     if (int rc = launch(c, "path_compose", [&] {
-            c->k->path_compose(c->stream, c->B, c->ws, c->keep_slot, c->path_origin_dev[c->path_org], c->path_origin_dev[c->path_org ^ 1]);
+            c->k->path_compose(c->stream, c->B, c->ws, c->keep_slot, c->po.path_origin_dev[c->po.path_org], c->po.path_origin_dev[c->po.path_org ^ 1]);
         }))
         return rc;
-    c->path_org ^= 1;
+    c->po.path_org ^= 1;
     return 0;
 }
 
 int path_identity(slamgpu_ctx *c) {
     Timed t(c, "path_compose");
-    c->k->path_compose(c->stream, c->B, c->ws, 0, nullptr, c->path_origin_dev[c->path_org]);
+    c->k->path_compose(c->stream, c->B, c->ws, 0, nullptr, c->po.path_origin_dev[c->po.path_org]);
     return 0;
 }
 
@@ -367,10 +367,10 @@ int path_append(slamgpu_ctx *c) {
     if (int rc = summary_enter(c, "", kDevice | kSettle)) return rc;
     c->B.slot = c->slot;
     if (int rc = launch(c, "path_record", [&] {
-            c->k->path_record(c->stream, c->B, c->ws, path_ring(c), (int) c->path.slot(c->path.next), c->path_origin_dev[c->path_org]);
+            c->k->path_record(c->stream, c->B, c->ws, path_ring(c), (int) c->po.path.slot(c->po.path.next), c->po.path_origin_dev[c->po.path_org]);
         }))
         return rc;
-    c->path.advance(1);
+    c->po.path.advance(1);
     return 0;
 }
 
@@ -387,55 +387,55 @@ int pose_append(slamgpu_ctx *c) {
     } else {
         if (int rc = summary_enter(c, "", kSettle)) return rc;
     }
-    if (int rc = pose_launch(c, c->pose_ring_dev + (size_t) kPoseStride * (size_t) c->pose.slot(c->pose.next))) return rc;
-    c->pose.advance(1);
+    if (int rc = pose_launch(c, c->po.pose_ring_dev + (size_t) kPoseStride * (size_t) c->po.pose.slot(c->po.pose.next))) return rc;
+    c->po.pose.advance(1);
     return 0;
 }
 
 // slamgpu_innovation_record past its context checks (slamgpu_step calls it with its own packet)
 int innov_append(slamgpu_ctx *c, const float *zf, const int32_t *idf, int32_t m, const float *R) {
     if (int rc = innov_check(c, "slamgpu_innovation_record", zf, idf, m, R)) return rc;
-    if (m > c->innov.cap)
-        return fail(SLAMGPU_ERR_CAPACITY, "slamgpu_innovation_record: %d observations, the ring holds %d entries", m, c->innov.cap);
+    if (m > c->po.innov.cap)
+        return fail(SLAMGPU_ERR_CAPACITY, "slamgpu_innovation_record: %d observations, the ring holds %d entries", m, c->po.innov.cap);
     if (m > 0) {
         InnovPacket P;
         P.zf = zf, P.idf = idf;
         if (int rc = innov_launch(c, P, m, R, true, nullptr, nullptr)) return rc;
-        c->innov.advance(m);
+        c->po.innov.advance(m);
     }
-    c->innov_records++;
+    c->po.innov_records++;
     return 0;
 }
 
 // the per-particle step's record (do_update_particle, beside its pp_missed): the nz observations in pp_z_dev against the labels in
 // pp_lab_dev, the set and the records as they stand before the update; nf: the slots before the step.  pp_check has seen to the
 // ring's capacity; innov_labels_room, which the entry points call right after pp_check, to the staging area
-int innov_labels_room(slamgpu_ctx *c, int32_t nz) { return c->msum.reserve(innov_layout(c, nz, 0).L.total()); }
+int innov_labels_room(slamgpu_ctx *c, int32_t nz) { return c->po.msum.reserve(innov_layout(c, nz, 0).L.total()); }
 int innov_append_labels(slamgpu_ctx *c, int32_t nz, int32_t nf, const float *R) {
     InnovPacket P;
     P.z_dev = c->as.pp_z_dev, P.lab_dev = c->as.pp_lab_dev, P.lstride = c->B.ncap, P.nf = nf;
     if (int rc = innov_launch(c, P, nz, R, true, nullptr, nullptr)) return rc;
-    c->innov.advance(nz);
-    c->innov_records++;
+    c->po.innov.advance(nz);
+    c->po.innov_records++;
     return 0;
 }
 
 void posterior_release(slamgpu_ctx *c) {
-    c->msum.release();
-    if (c->pose_ring_dev) (void) hipFree(c->pose_ring_dev);
-    if (c->pose_dev) (void) hipFree(c->pose_dev);
-    if (c->innov_ring_dev) (void) hipFree(c->innov_ring_dev);
-    if (c->innov_tag_dev) (void) hipFree(c->innov_tag_dev);
-    if (c->innov_host) (void) hipHostFree(c->innov_host);
-    for (hipEvent_t e : c->innov_ev)
+    c->po.msum.release();
+    if (c->po.pose_ring_dev) (void) hipFree(c->po.pose_ring_dev);
+    if (c->po.pose_dev) (void) hipFree(c->po.pose_dev);
+    if (c->po.innov_ring_dev) (void) hipFree(c->po.innov_ring_dev);
+    if (c->po.innov_tag_dev) (void) hipFree(c->po.innov_tag_dev);
+    if (c->po.innov_host) (void) hipHostFree(c->po.innov_host);
+    for (hipEvent_t e : c->po.innov_ev)
         if (e) (void) hipEventDestroy(e);
-    if (c->innov_lab_host) (void) hipHostFree(c->innov_lab_host);
-    for (hipEvent_t e : c->innov_lab_ev)
+    if (c->po.innov_lab_host) (void) hipHostFree(c->po.innov_lab_host);
+    for (hipEvent_t e : c->po.innov_lab_ev)
         if (e) (void) hipEventDestroy(e);
-    if (c->path_rec_dev) (void) hipFree(c->path_rec_dev);
+    if (c->po.path_rec_dev) (void) hipFree(c->po.path_rec_dev);
     for (int b = 0; b < 2; b++)
-        if (c->path_origin_dev[b]) (void) hipFree(c->path_origin_dev[b]);
-    c->path_arena.release();
+        if (c->po.path_origin_dev[b]) (void) hipFree(c->po.path_origin_dev[b]);
+    c->po.path_arena.release();
 }
 
 #pragma GCC visibility pop
@@ -457,7 +457,7 @@ int slamgpu_map_summary(slamgpu_ctx *c, int32_t first_slot, int32_t count, doubl
     Layout L;
     const auto out_d = L.take<double>(kMapStride * M), wpart = L.take<double>(2 * (size_t) tiles), part = L.take<double>(kMapFields * (size_t) tiles * chunk);
     const auto hold = L.take<int32_t>(M);
-    if (int rc = c->msum.reserve(L.total())) return rc;
+    if (int rc = c->po.msum.reserve(L.total())) return rc;
     c->B.slot = c->slot;
     for (int at = 0; at < count; at += chunk) {
         MapSummaryArgs A{};
@@ -465,15 +465,15 @@ int slamgpu_map_summary(slamgpu_ctx *c, int32_t first_slot, int32_t count, doubl
         A.count = std::min(chunk, count - at);
         A.tiles = tiles;
         A.logw = c->cfg.log_weights;
-        A.part = part.at(c->msum);
-        A.wpart = wpart.at(c->msum);
-        A.out = out_d.at(c->msum) + (size_t) kMapStride * at;
-        A.holders = hold.at(c->msum) + at;
+        A.part = part.at(c->po.msum);
+        A.wpart = wpart.at(c->po.msum);
+        A.out = out_d.at(c->po.msum) + (size_t) kMapStride * at;
+        A.holders = hold.at(c->po.msum) + at;
         if (int rc = launch(c, "map_summary", [&] { c->k->map_summary(c->stream, c->B, c->ws, A); })) return rc;
         if (int rc = launch(c, "map_finish", [&] { c->k->map_finish(c->stream, A); })) return rc;
     }
-    HIP_TRY(hipMemcpyAsync(out, out_d.at(c->msum), sizeof(double) * kMapStride * M, hipMemcpyDeviceToHost, c->stream));
-    if (holders) HIP_TRY(hipMemcpyAsync(holders, hold.at(c->msum), sizeof(int32_t) * M, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(out, out_d.at(c->po.msum), sizeof(double) * kMapStride * M, hipMemcpyDeviceToHost, c->stream));
+    if (holders) HIP_TRY(hipMemcpyAsync(holders, hold.at(c->po.msum), sizeof(int32_t) * M, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return 0;
 }
@@ -495,8 +495,8 @@ int slamgpu_map_pairs(slamgpu_ctx *c, const int32_t *pairs, int32_t count, doubl
     Layout L;
     const auto out_d = L.take<double>(kMapStride * M), wpart = L.take<double>(2 * (size_t) tiles), part = L.take<double>(kMapFields * (size_t) tiles * chunk);
     const auto both_d = L.take<int32_t>(M), pairs_d = L.take<int32_t>(2 * M);
-    if (int rc = c->msum.reserve(L.total())) return rc;
-    HIP_TRY(hipMemcpyAsync(pairs_d.at(c->msum), pairs, sizeof(int32_t) * 2 * M, hipMemcpyHostToDevice, c->stream));
+    if (int rc = c->po.msum.reserve(L.total())) return rc;
+    HIP_TRY(hipMemcpyAsync(pairs_d.at(c->po.msum), pairs, sizeof(int32_t) * 2 * M, hipMemcpyHostToDevice, c->stream));
     c->B.slot = c->slot;
     for (int at = 0; at < count; at += chunk) {
         MapPairsArgs P{};
@@ -505,16 +505,16 @@ int slamgpu_map_pairs(slamgpu_ctx *c, const int32_t *pairs, int32_t count, doubl
         A.count = std::min(chunk, count - at);
         A.tiles = tiles;
         A.logw = c->cfg.log_weights;
-        A.part = part.at(c->msum);
-        A.wpart = wpart.at(c->msum);
-        A.out = out_d.at(c->msum) + (size_t) kMapStride * at;
-        A.holders = both_d.at(c->msum) + at;
-        P.pairs = pairs_d.at(c->msum) + (size_t) 2 * at;
+        A.part = part.at(c->po.msum);
+        A.wpart = wpart.at(c->po.msum);
+        A.out = out_d.at(c->po.msum) + (size_t) kMapStride * at;
+        A.holders = both_d.at(c->po.msum) + at;
+        P.pairs = pairs_d.at(c->po.msum) + (size_t) 2 * at;
         if (int rc = launch(c, "map_pairs", [&] { c->k->map_pairs(c->stream, c->B, c->ws, P); })) return rc;
         if (int rc = launch(c, "map_finish", [&] { c->k->map_finish(c->stream, A); })) return rc;
     }
-    HIP_TRY(hipMemcpyAsync(out, out_d.at(c->msum), sizeof(double) * kMapStride * M, hipMemcpyDeviceToHost, c->stream));
-    if (both) HIP_TRY(hipMemcpyAsync(both, both_d.at(c->msum), sizeof(int32_t) * M, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(out, out_d.at(c->po.msum), sizeof(double) * kMapStride * M, hipMemcpyDeviceToHost, c->stream));
+    if (both) HIP_TRY(hipMemcpyAsync(both, both_d.at(c->po.msum), sizeof(int32_t) * M, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return 0;
 }
@@ -539,27 +539,27 @@ int slamgpu_joint_summary(slamgpu_ctx *c, const int32_t *slots, int32_t k, doubl
                pvf = L.take<double>(nq * T), part = L.take<double>(256 * T * chunk);
     const auto tile_info = L.take<int32_t>(2 * T), info = L.take<int32_t>(4), slots_d = L.take<int32_t>((size_t) k);
     const auto hold = L.take<uint8_t>(up16((size_t) c->B.n), 16);
-    if (int rc = c->msum.reserve(L.total())) return rc;
-    if (k > 0) HIP_TRY(hipMemcpyAsync(slots_d.at(c->msum), slots, sizeof(int32_t) * (size_t) k, hipMemcpyHostToDevice, c->stream));
+    if (int rc = c->po.msum.reserve(L.total())) return rc;
+    if (k > 0) HIP_TRY(hipMemcpyAsync(slots_d.at(c->po.msum), slots, sizeof(int32_t) * (size_t) k, hipMemcpyHostToDevice, c->stream));
     c->B.slot = c->slot;
     JointArgs J{};
     J.S.tiles = tiles;
     J.S.logw = c->cfg.log_weights;
-    J.S.part = part.at(c->msum);
-    J.S.wpart = wpart.at(c->msum);
-    J.S.out = out_d.at(c->msum);
-    J.S.holders = info.at(c->msum) + 2;
+    J.S.part = part.at(c->po.msum);
+    J.S.wpart = wpart.at(c->po.msum);
+    J.S.out = out_d.at(c->po.msum);
+    J.S.holders = info.at(c->po.msum) + 2;
     J.k = k;
     J.D = D;
     J.Dp = Dp;
     if (const char *e = getenv("SLAMGPU_JOINT_PLAIN_FMA")) J.plain = atoi(e) != 0;  // (diagnostic: tools/joint_probe.py's comparison of the two forms)
-    J.slots = slots_d.at(c->msum);
-    J.hold = hold.at(c->msum);
-    J.tile_info = tile_info.at(c->msum);
-    J.info = info.at(c->msum);
-    J.pivot = pivot.at(c->msum);
-    J.sums = sums.at(c->msum);
-    J.pvf = pvf.at(c->msum);
+    J.slots = slots_d.at(c->po.msum);
+    J.hold = hold.at(c->po.msum);
+    J.tile_info = tile_info.at(c->po.msum);
+    J.info = info.at(c->po.msum);
+    J.pivot = pivot.at(c->po.msum);
+    J.sums = sums.at(c->po.msum);
+    J.pvf = pvf.at(c->po.msum);
     if (int rc = launch(c, "joint_hold", [&] { c->k->joint_hold(c->stream, c->B, c->ws, J); })) return rc;
     if (int rc = launch(c, "joint_pivot", [&] { c->k->joint_pivot(c->stream, c->B, c->ws, J); })) return rc;
     for (int at = 0; at < nbp; at += chunk) {
@@ -571,7 +571,7 @@ int slamgpu_joint_summary(slamgpu_ctx *c, const int32_t *slots, int32_t k, doubl
     if (int rc = launch(c, "joint_finish", [&] { c->k->joint_finish(c->stream, c->B, c->ws, J); })) return rc;
     std::vector<double> h(size);  // (outputs untouched if a copy fails)
     int32_t hb = 0;
-    HIP_TRY(hipMemcpyAsync(h.data(), out_d.at(c->msum), sizeof(double) * size, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(h.data(), out_d.at(c->po.msum), sizeof(double) * size, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipMemcpyAsync(&hb, J.S.holders, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     memcpy(out, h.data(), sizeof(double) * size);
@@ -608,35 +608,35 @@ int slamgpu_pose_history_enable(slamgpu_ctx *c, int32_t capacity) {
             return fail(SLAMGPU_ERR_ALLOC, "slamgpu_pose_history_enable: %d entries (%zu bytes): %s", capacity, bytes, hipGetErrorString(e));
         }
     }
-    if (c->pose_ring_dev) {
+    if (c->po.pose_ring_dev) {
         HIP_TRY(hipStreamSynchronize(c->stream));  // (launches in flight may still write the old ring)
-        (void) hipFree(c->pose_ring_dev);
+        (void) hipFree(c->po.pose_ring_dev);
     }
-    c->pose_ring_dev = ring;
-    c->pose.reset(capacity);
+    c->po.pose_ring_dev = ring;
+    c->po.pose.reset(capacity);
     return 0;
 }
 
 int slamgpu_pose_history_record(slamgpu_ctx *c) {
     if (int rc = check_ctx(c)) return rc;
-    if (c->pose.cap == 0) return fail(SLAMGPU_ERR_INVALID, "slamgpu_pose_history_record: the ring is off (slamgpu_pose_history_enable)");
+    if (c->po.pose.cap == 0) return fail(SLAMGPU_ERR_INVALID, "slamgpu_pose_history_record: the ring is off (slamgpu_pose_history_enable)");
     return pose_append(c);
 }
 
 int slamgpu_pose_history_info(slamgpu_ctx *c, int64_t *first, int64_t *next, int32_t *capacity) {
     if (int rc = check_ctx(c)) return rc;
-    ring_info(c->pose, first, next, capacity);
+    ring_info(c->po.pose, first, next, capacity);
     return 0;
 }
 
 int slamgpu_pose_history_fetch(slamgpu_ctx *c, int64_t first, int32_t count, double *out) {
     if (int rc = check_ctx(c)) return rc;
-    if (int rc = ring_check(c->pose, "slamgpu_pose_history_fetch", "entries", first, count)) return rc;
+    if (int rc = ring_check(c->po.pose, "slamgpu_pose_history_fetch", "entries", first, count)) return rc;
     if (count == 0) return 0;
     if (!out) return fail(SLAMGPU_ERR_INVALID, "slamgpu_pose_history_fetch: null output");
     HIP_TRY(hipSetDevice(c->cfg.device));
     std::vector<double> h((size_t) kPoseStride * (size_t) count);
-    if (int rc = ring_fetch(c, c->pose, c->pose_ring_dev, sizeof(double) * kPoseStride, first, count, h.data())) return rc;
+    if (int rc = ring_fetch(c, c->po.pose, c->po.pose_ring_dev, sizeof(double) * kPoseStride, first, count, h.data())) return rc;
     HIP_TRY(hipStreamSynchronize(c->stream));
     memcpy(out, h.data(), sizeof(double) * h.size());
     return 0;
@@ -693,40 +693,40 @@ int slamgpu_innovation_history_enable(slamgpu_ctx *c, int32_t capacity) {
             return fail(SLAMGPU_ERR_ALLOC, "slamgpu_innovation_history_enable: %d entries (%zu bytes): %s", capacity, bytes, hipGetErrorString(e));
         }
     }
-    if (c->innov_ring_dev) {
+    if (c->po.innov_ring_dev) {
         HIP_TRY(hipStreamSynchronize(c->stream));  // (launches in flight may still write the old ring)
-        (void) hipFree(c->innov_ring_dev);
-        (void) hipFree(c->innov_tag_dev);
+        (void) hipFree(c->po.innov_ring_dev);
+        (void) hipFree(c->po.innov_tag_dev);
     }
-    c->innov_ring_dev = ring;
-    c->innov_tag_dev = tag;
-    c->innov.reset(capacity);
-    c->innov_records = 0;
+    c->po.innov_ring_dev = ring;
+    c->po.innov_tag_dev = tag;
+    c->po.innov.reset(capacity);
+    c->po.innov_records = 0;
     return 0;
 }
 
 int slamgpu_innovation_record(slamgpu_ctx *c, const float *zf, const int32_t *idf, int32_t m, const float R[4]) {
     if (int rc = summary_enter(c, "slamgpu_innovation_record", kCtx | kSingle)) return rc;
-    if (c->innov.cap == 0) return fail(SLAMGPU_ERR_INVALID, "slamgpu_innovation_record: the ring is off (slamgpu_innovation_history_enable)");
+    if (c->po.innov.cap == 0) return fail(SLAMGPU_ERR_INVALID, "slamgpu_innovation_record: the ring is off (slamgpu_innovation_history_enable)");
     return innov_append(c, zf, idf, m, R);
 }
 
 int slamgpu_innovation_history_info(slamgpu_ctx *c, int64_t *first, int64_t *next, int32_t *capacity, int64_t *records) {
     if (int rc = check_ctx(c)) return rc;
-    ring_info(c->innov, first, next, capacity);
-    if (records) *records = c->innov_records;
+    ring_info(c->po.innov, first, next, capacity);
+    if (records) *records = c->po.innov_records;
     return 0;
 }
 
 int slamgpu_innovation_history_fetch(slamgpu_ctx *c, int64_t first, int32_t count, double *out, int32_t *record, int32_t *slot) {
     if (int rc = check_ctx(c)) return rc;
-    if (int rc = ring_check(c->innov, "slamgpu_innovation_history_fetch", "entries", first, count)) return rc;
+    if (int rc = ring_check(c->po.innov, "slamgpu_innovation_history_fetch", "entries", first, count)) return rc;
     if (count == 0) return 0;
     HIP_TRY(hipSetDevice(c->cfg.device));
     std::vector<double> h((size_t) kInnStride * (size_t) count);
     std::vector<int32_t> tg((size_t) 2 * (size_t) count);
-    if (int rc = ring_fetch(c, c->innov, c->innov_ring_dev, sizeof(double) * kInnStride, first, count, h.data())) return rc;
-    if (int rc = ring_fetch(c, c->innov, c->innov_tag_dev, sizeof(int32_t) * 2, first, count, tg.data())) return rc;
+    if (int rc = ring_fetch(c, c->po.innov, c->po.innov_ring_dev, sizeof(double) * kInnStride, first, count, h.data())) return rc;
+    if (int rc = ring_fetch(c, c->po.innov, c->po.innov_tag_dev, sizeof(int32_t) * 2, first, count, tg.data())) return rc;
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (out) memcpy(out, h.data(), sizeof(double) * h.size());
     for (int32_t q = 0; q < count; q++) {
@@ -755,18 +755,18 @@ int slamgpu_path_enable(slamgpu_ctx *c, int32_t capacity) {
             return fail(SLAMGPU_ERR_ALLOC, "slamgpu_path_enable: %d records of %d particles (%zu bytes): %s", capacity, c->B.n, bytes, hipGetErrorString(e));
         }
     }
-    if (c->path.cap > 0 || c->path_arena.p) {
+    if (c->po.path.cap > 0 || c->po.path_arena.p) {
         HIP_TRY(hipStreamSynchronize(c->stream));  // (launches in flight may still use the old ring)
-        if (c->path_rec_dev) (void) hipFree(c->path_rec_dev);
+        if (c->po.path_rec_dev) (void) hipFree(c->po.path_rec_dev);
         for (int b = 0; b < 2; b++)
-            if (c->path_origin_dev[b]) (void) hipFree(c->path_origin_dev[b]);
-        c->path_arena.release();
+            if (c->po.path_origin_dev[b]) (void) hipFree(c->po.path_origin_dev[b]);
+        c->po.path_arena.release();
     }
-    c->path_rec_dev = rec;
-    c->path_origin_dev[0] = org[0];
-    c->path_origin_dev[1] = org[1];
-    c->path_org = 0;
-    c->path.reset(capacity);
+    c->po.path_rec_dev = rec;
+    c->po.path_origin_dev[0] = org[0];
+    c->po.path_origin_dev[1] = org[1];
+    c->po.path_org = 0;
+    c->po.path.reset(capacity);
     if (capacity > 0) {
         if (int rc = path_identity(c)) return rc;
         HIP_TRY(hipGetLastError());
@@ -776,13 +776,13 @@ int slamgpu_path_enable(slamgpu_ctx *c, int32_t capacity) {
 
 int slamgpu_path_record(slamgpu_ctx *c) {
     if (int rc = check_ctx(c)) return rc;
-    if (c->path.cap == 0) return fail(SLAMGPU_ERR_INVALID, "slamgpu_path_record: recording is off (slamgpu_path_enable)");
+    if (c->po.path.cap == 0) return fail(SLAMGPU_ERR_INVALID, "slamgpu_path_record: recording is off (slamgpu_path_enable)");
     return path_append(c);
 }
 
 int slamgpu_path_info(slamgpu_ctx *c, int64_t *first, int64_t *next, int32_t *capacity) {
     if (int rc = check_ctx(c)) return rc;
-    ring_info(c->path, first, next, capacity);
+    ring_info(c->po.path, first, next, capacity);
     return 0;
 }
 
@@ -792,7 +792,7 @@ int slamgpu_path_fetch(slamgpu_ctx *c, int64_t r, float *xyt, int32_t *parent) {
     HIP_TRY(hipSetDevice(c->cfg.device));
     const size_t N = (size_t) c->B.n;
     std::vector<float4> rec(N);
-    HIP_TRY(hipMemcpyAsync(rec.data(), c->path_rec_dev + (size_t) c->path.slot(r) * (size_t) c->B.ncap, sizeof(float4) * N, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(rec.data(), c->po.path_rec_dev + (size_t) c->po.path.slot(r) * (size_t) c->B.ncap, sizeof(float4) * N, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     for (size_t k = 0; k < N; k++) {
         if (xyt) {
@@ -815,15 +815,15 @@ int slamgpu_path_trace(slamgpu_ctx *c, int32_t particle, int64_t first, int32_t 
     Layout L;
     const auto xyt_d = L.take<float>(3 * M);
     const auto index_d = L.take<int32_t>(M, 16);
-    if (int rc = c->path_arena.reserve(L.total())) return rc;
+    if (int rc = c->po.path_arena.reserve(L.total())) return rc;
     PathTraceArgs A{};
     A.particle = particle;
-    A.newest = c->path.next - 1;
+    A.newest = c->po.path.next - 1;
     A.first = first;
     A.count = count;
-    A.origin = c->path_origin_dev[c->path_org];
-    A.xyt = xyt_d.at(c->path_arena);
-    A.index = index_d.at(c->path_arena);
+    A.origin = c->po.path_origin_dev[c->po.path_org];
+    A.xyt = xyt_d.at(c->po.path_arena);
+    A.index = index_d.at(c->po.path_arena);
     c->B.slot = c->slot;
     if (int rc = launch(c, "path_trace", [&] { c->k->path_trace(c->stream, c->B, c->ws, path_ring(c), A); })) return rc;
     if (xyt) HIP_TRY(hipMemcpyAsync(xyt, A.xyt, sizeof(float) * 3 * M, hipMemcpyDeviceToHost, c->stream));
@@ -849,18 +849,18 @@ int slamgpu_path_summary(slamgpu_ctx *c, int64_t first, int32_t count, double *o
     const auto part = L.take<double>(kPathFields * (size_t) tiles * chunk);
     const auto C = L.take<uint32_t>(2 * S);
     const auto distinct_d = L.take<int32_t>(M);
-    if (int rc = c->path_arena.reserve(L.total())) return rc;
+    if (int rc = c->po.path_arena.reserve(L.total())) return rc;
     PathWalkArgs A{};
     A.tiles = tiles;
     A.logw = c->cfg.log_weights;
-    A.wpart = wpart.at(c->path_arena);
-    A.wtot = wtot.at(c->path_arena);
-    A.origin = c->path_origin_dev[c->path_org];
-    A.W[0] = W.at(c->path_arena);
+    A.wpart = wpart.at(c->po.path_arena);
+    A.wtot = wtot.at(c->po.path_arena);
+    A.origin = c->po.path_origin_dev[c->po.path_org];
+    A.W[0] = W.at(c->po.path_arena);
     A.W[1] = A.W[0] + S;
-    A.C[0] = C.at(c->path_arena);
+    A.C[0] = C.at(c->po.path_arena);
     A.C[1] = A.C[0] + S;
-    A.part = part.at(c->path_arena);
+    A.part = part.at(c->po.path_arena);
     A.chunk = chunk;
     c->B.slot = c->slot;
     HIP_TRY(hipMemsetAsync(A.W[0], 0, sizeof(unsigned long long) * 2 * S, c->stream));
@@ -876,7 +876,7 @@ int slamgpu_path_summary(slamgpu_ctx *c, int64_t first, int32_t count, double *o
     int64_t lo = first + count;  // the chunk in progress is [lo, hi)
     int64_t hi = lo;
     int cur = 0;
-    for (int64_t r = c->path.next - 1; r >= first; r--) {
+    for (int64_t r = c->po.path.next - 1; r >= first; r--) {
         if (r < lo) {
             hi = lo;
             lo = std::max<int64_t>(first, hi - chunk);
@@ -892,15 +892,15 @@ int slamgpu_path_summary(slamgpu_ctx *c, int64_t first, int32_t count, double *o
         cur ^= 1;
         if (r == lo && A.at >= 0) {
             A.count = (int32_t) (hi - lo);
-            A.out = out_d.at(c->path_arena) + (size_t) kPathStride * (size_t) (lo - first);
-            A.distinct = distinct_d.at(c->path_arena) + (size_t) (lo - first);
+            A.out = out_d.at(c->po.path_arena) + (size_t) kPathStride * (size_t) (lo - first);
+            A.distinct = distinct_d.at(c->po.path_arena) + (size_t) (lo - first);
             Timed t(c, "path_finish");
             c->k->path_finish(c->stream, A);
         }
     }
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(out, out_d.at(c->path_arena), sizeof(double) * kPathStride * M, hipMemcpyDeviceToHost, c->stream));
-    if (distinct) HIP_TRY(hipMemcpyAsync(distinct, distinct_d.at(c->path_arena), sizeof(int32_t) * M, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(out, out_d.at(c->po.path_arena), sizeof(double) * kPathStride * M, hipMemcpyDeviceToHost, c->stream));
+    if (distinct) HIP_TRY(hipMemcpyAsync(distinct, distinct_d.at(c->po.path_arena), sizeof(int32_t) * M, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return 0;
 }

@@ -38,6 +38,38 @@ int dev_grow(void **p, size_t *cap, size_t n, size_t elem, const char *what, boo
     return 0;
 }
 
+int pin_grow(void **p, size_t *cap, size_t n, size_t elem, const char *what) {
+    if (*p) (void) hipHostFree(*p);
+    *p = nullptr;
+    *cap = 0;
+    const hipError_t e = hipHostMalloc(p, n * elem, hipHostMallocDefault);
+    if (e != hipSuccess) {
+        (void) hipGetLastError();
+        *p = nullptr;
+        return fail(SLAMGPU_ERR_ALLOC, "%s: hipHostMalloc(%zu): %s", what, n * elem, hipGetErrorString(e));
+    }
+    *cap = n;
+    return 0;
+}
+
+int pkt_take_slot(slamgpu_ctx *c) { return (int) (c->pkt_seq++ % kRing); }
+
+int BigPacket::begin(slamgpu_ctx *c, int32_t m, int32_t n, int32_t nf, int32_t n_rows, int32_t e_new) {
+    slot = pkt_take_slot(c);
+    if (c->pkt_ev_used[slot]) HIP_TRY(hipEventSynchronize(c->pkt_ev[slot]));
+    host = reinterpret_cast<ObsPacket *>(c->pkt_host + (size_t) slot * c->pkt_bytes);
+    dev = c->pkt_dev + (size_t) slot * c->pkt_bytes;
+    *host = ObsPacket{m, n, nf, n_rows, e_new, 0, 0 /* dense layout */, 0};
+    return 0;
+}
+
+int BigPacket::commit(slamgpu_ctx *c, size_t used) {
+    HIP_TRY(hipMemcpyAsync(dev, host, used, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipEventRecord(c->pkt_ev[slot], c->stream));
+    c->pkt_ev_used[slot] = true;
+    return 0;
+}
+
 hipEvent_t get_event(slamgpu_ctx *c) {
     if (!c->ev_pool.empty()) {
         hipEvent_t e = c->ev_pool.back();
@@ -153,169 +185,6 @@ void rows_reset(slamgpu_ctx *c, int nf) {
     }
     c->tables_dirty = true;
 }
-
-// ---- genealogy bookkeeping on the device (slamgpu_step_observe) <-> on the host ----
-// The device-driven steps keep erow / live flags / reference counts / nf / fresh row in device memory (observe_book_kernel).
-// Anything host-side that needs them (a host-made packet, download, flatten, peek, the landmark count) first pulls them back
-// -- one synchronisation -- and the host is authoritative again; the next device-driven step pushes them.
-// (All copies go through one pinned staging buffer.)
-int book_staging(slamgpu_ctx *c) {
-    if (c->book_host) return 0;
-    const size_t words = sizeof(DevBook) / 4 + 2 * (size_t) c->B.cap_nf + (size_t) c->B.cap_rows;
-    HIP_TRY(hipHostMalloc((void **) &c->book_host, 4 * words, hipHostMallocDefault));
-    HIP_TRY(hipMalloc((void **) &c->book_dev, sizeof(DevBook)));
-    HIP_TRY(hipMalloc((void **) &c->refcnt_dev, sizeof(int32_t) * (size_t) c->B.cap_rows));
-    HIP_TRY(hipMalloc((void **) &c->take_dev, sizeof(int32_t) * (size_t) c->B.cap_rows));
-    HIP_TRY(hipStreamCreateWithFlags(&c->obs_stream, hipStreamNonBlocking));
-    for (int i = 0; i < kRing; i++) HIP_TRY(hipEventCreateWithFlags(&c->obs_ev[i], hipEventDisableTiming));
-    return 0;
-}
-
-// the row lists follow from the reference counts (book_pull)
-void book_rebuild(slamgpu_ctx *c) {
-    std::fill(c->live_pos.begin(), c->live_pos.end(), -1);
-    c->live_rows.clear();
-    c->free_rows.clear();
-    for (int r = c->B.cap_rows - 1; r >= 0; r--)
-        if (c->refcnt[r] == 0) c->free_rows.push_back(r);  // back() = lowest free row
-    for (int r = 0; r < c->B.cap_rows; r++)
-        if (c->refcnt[r] > 0) rows_add_live(c, r);
-    c->tables_dirty = true;
-    c->book_on_device = false;
-    std::fill(c->as.box_dirty.begin(), c->as.box_dirty.end(), 1);  // (which landmarks the device-driven steps wrote is not known here)
-}
-
-namespace {
-
-// compact contexts: the front end's state (kernels.h: FrontState), both copies holding the map, no landmark seen yet
-int front_setup(slamgpu_ctx *c) {
-    if (c->front_ready) return 0;
-    if (c->map_n > kFrontLanes || c->map_n > kSmallObs - 1) return fail(SLAMGPU_ERR_CAPACITY, "map of %d landmarks in a compact context", c->map_n);
-    if (!c->front_dev) {
-        HIP_TRY(hipMalloc((void **) &c->front_dev, 2 * sizeof(FrontState)));
-        HIP_TRY(hipHostMalloc((void **) &c->front_host, sizeof(FrontState), hipHostMallocDefault));
-        HIP_TRY(hipMalloc((void **) &c->front_pkt_dev, sizeof(ObsPacket) + 4 * (6 * (size_t) kFrontLanes + kSmallRows)));
-    }
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    FrontState *h = c->front_host;
-    memset(h, 0, sizeof *h);
-    h->hdr = FrontHdr{0, -1, 0, 0};
-    for (int t = 0; t < kFrontLanes; t++) h->lm[t] = FrontLm{-1, 0};
-    for (int q = 0; q < 2; q++) HIP_TRY(hipMemcpy(c->front_dev + q, h, sizeof *h, hipMemcpyHostToDevice));
-    c->front_par = 0;
-    c->front_ready = true;
-    return 0;
-}
-
-}  // namespace
-
-int book_pull(slamgpu_ctx *c) {
-    if (c->as.pp_on_device) return pp_pull(c);
-    if (!c->book_on_device) return 0;
-    HIP_TRY(hipSetDevice(c->cfg.device));
-    if (c->B.compact) {
-        FrontState *h = c->front_host;
-        HIP_TRY(hipMemcpyAsync(h, c->front_dev + c->front_par, sizeof *h, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        const int nf = h->hdr.nf;
-        if (nf < 0 || nf > c->B.cap_nf) return fail(SLAMGPU_ERR_INVALID, "device bookkeeping corrupt: nf = %d", nf);
-        std::fill(c->refcnt.begin(), c->refcnt.end(), 0);
-        int seen = 0;
-        for (int t = 0; t < c->map_n; t++) {
-            const FrontLm &l = h->lm[t];
-            if (l.idf < 0) continue;
-            const int r = l.row & kRowMask;
-            if (l.idf >= nf || r >= c->B.cap_rows) return fail(SLAMGPU_ERR_INVALID, "device bookkeeping corrupt: landmark %d -> feature %d, row %d", t, l.idf, r);
-            c->erow[l.idf] = r;
-            c->live_flag[l.idf] = (l.row & kRowLiveBit) ? 1 : 0;
-            c->refcnt[r]++;
-            seen++;
-        }
-        if (seen != nf) return fail(SLAMGPU_ERR_INVALID, "device bookkeeping corrupt: %d landmarks of the map seen, nf = %d", seen, nf);
-        c->nf = nf;
-        c->fresh_row = h->hdr.fresh_row;
-        book_rebuild(c);
-        const bool first_seen = (h->hdr.status & kStatusCapacity) && !(c->front_status & kStatusCapacity);
-        c->front_status |= h->hdr.status;
-        if (first_seen)  // (reported as an error once; the bit stays: slamgpu_step_status)
-            return fail(SLAMGPU_ERR_CAPACITY, "the device front end dropped new landmarks: landmark capacity %d exceeded", c->B.cap_nf);
-        return 0;
-    }
-    const size_t cn = (size_t) c->B.cap_nf, cr = (size_t) c->B.cap_rows;
-    DevBook *hb = reinterpret_cast<DevBook *>(c->book_host);
-    int32_t *h_erow = c->book_host + sizeof(DevBook) / 4, *h_live = h_erow + cn, *h_ref = h_live + cn;
-    HIP_TRY(hipStreamSynchronize(c->obs_stream));  // (the last front-end kernel writes these tables)
-    HIP_TRY(hipMemcpyAsync(hb, c->book_dev, sizeof(DevBook), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpyAsync(h_erow, c->erow_dev, 4 * cn, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpyAsync(h_live, c->live_dev, 4 * cn, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpyAsync(h_ref, c->refcnt_dev, 4 * cr, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    const int nf = hb->nf;
-    if (nf < 0 || nf > c->B.cap_nf) return fail(SLAMGPU_ERR_INVALID, "device bookkeeping corrupt: nf = %d", nf);
-    std::copy(h_erow, h_erow + nf, c->erow.begin());
-    std::copy(h_live, h_live + nf, c->live_flag.begin());
-    std::copy(h_ref, h_ref + cr, c->refcnt.begin());
-    c->nf = nf;
-    c->fresh_row = hb->fresh_row;
-    book_rebuild(c);
-    const bool first_seen = (hb->status & kStatusCapacity) && !(c->front_status & kStatusCapacity);
-    c->front_status |= hb->status;
-    if (first_seen)
-        return fail(SLAMGPU_ERR_CAPACITY, "the device front end dropped new landmarks: landmark capacity %d exceeded", c->B.cap_nf);
-    return 0;
-}
-
-namespace {
-
-int book_push(slamgpu_ctx *c) {
-    if (c->book_on_device) return 0;
-    HIP_TRY(hipSetDevice(c->cfg.device));
-    if (c->B.compact) {
-        // the landmark -> feature table lives in the front end's state and nowhere else: every feature the context knows must
-        // have come from it (a context is driven by one front end, the host's or the device's, from its first landmark on)
-        if (int rc = front_setup(c)) return rc;
-        FrontState *h = c->front_host;
-        HIP_TRY(hipMemcpyAsync(h, c->front_dev + c->front_par, sizeof *h, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));  // (and nothing in flight still reads this copy)
-        int seen = 0;
-        for (int t = 0; t < c->map_n; t++) {
-            FrontLm &l = h->lm[t];
-            if (l.idf < 0) continue;
-            if (l.idf >= c->nf) return fail(SLAMGPU_ERR_INVALID, "the device's landmark table knows feature %d, the context only %d", l.idf, c->nf);
-            l.row = c->erow[l.idf] | (c->live_flag[l.idf] ? kRowLiveBit : 0);
-            seen++;
-        }
-        if (seen != c->nf)
-            return fail(SLAMGPU_ERR_INVALID, "slamgpu_step_observe on a compact context: %d of its %d landmarks came from host-made packets, "
-                        "which the device's landmark table does not know", c->nf - seen, c->nf);
-        h->hdr = FrontHdr{c->nf, c->fresh_row, c->front_status, 0};
-        HIP_TRY(hipMemcpyAsync(c->front_dev + c->front_par, h, sizeof *h, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        c->book_on_device = true;
-        return 0;
-    }
-    if (int rc = book_staging(c)) return rc;
-    HIP_TRY(hipStreamSynchronize(c->stream));  // (nothing in flight may still read the old tables or the staging buffer)
-    const size_t cn = (size_t) c->B.cap_nf, cr = (size_t) c->B.cap_rows;
-    DevBook *hb = reinterpret_cast<DevBook *>(c->book_host);
-    int32_t *h_erow = c->book_host + sizeof(DevBook) / 4, *h_live = h_erow + cn, *h_ref = h_live + cn;
-    *hb = DevBook{};
-    hb->nf = c->nf;
-    hb->fresh_row = c->fresh_row;
-    hb->status = c->front_status;
-    std::copy(c->erow.begin(), c->erow.begin() + cn, h_erow);
-    std::copy(c->live_flag.begin(), c->live_flag.begin() + cn, h_live);
-    std::copy(c->refcnt.begin(), c->refcnt.begin() + cr, h_ref);
-    HIP_TRY(hipMemcpyAsync(c->book_dev, hb, sizeof(DevBook), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(c->erow_dev, h_erow, 4 * cn, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(c->live_dev, h_live, 4 * cn, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(c->refcnt_dev, h_ref, 4 * cr, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    c->book_on_device = true;
-    return 0;
-}
-
-}  // namespace
 
 // device copies of the row tables for the kernels that run outside the update launch
 int sync_tables(slamgpu_ctx *c) {
@@ -493,20 +362,6 @@ int estimate_now(slamgpu_ctx *c, double *hist) {
     return 0;
 }
 
-// The abort word of the persistent step loop is sticky, like the barrier error of the push collective: whoever synchronises with
-// the device reports it (the kernel stores it into pinned host memory: no copy needed here).
-int persist_check(slamgpu_ctx *c) {
-    if (c->pstatus_host && __atomic_load_n(c->pstatus_host, __ATOMIC_ACQUIRE) != 0) {
-        const volatile uint32_t *h = c->pstatus_host;
-        return fail(SLAMGPU_ERR_BARRIER, "persistent step loop (slamgpu_run_observe): a workgroup waited too long at the in-launch barrier and launch %u of "
-                                         "this context was abandoned after %u of its %u iterations (every workgroup had completed those; the iteration in "
-                                         "flight is partially applied, so the state is undefined and everything handed over since is void: recreate the "
-                                         "context and replay from there; slamgpu_persist_status returns these counts; SLAMGPU_NO_PERSIST=1 selects the "
-                                         "per-step loop)", (unsigned) h[2], (unsigned) h[1], (unsigned) h[3]);
-    }
-    return 0;
-}
-
 int check_ctx(slamgpu_ctx *c) {
     if (!c) return fail(SLAMGPU_ERR_INVALID, "null context");
     return 0;
@@ -569,7 +424,7 @@ int slamgpu_create(const slamgpu_config *cfg, slamgpu_ctx **out) {
         if (hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, cfg->device) != hipSuccess || (size_t) lds_max < sizeof(float) * 2 * (size_t) n + 4096)
             c->ref_resample = false;
     }
-    c->persist_ok = getenv("SLAMGPU_NO_PERSIST") == nullptr;                               // diagnostic / tests: slamgpu_run_observe as a loop of launches
+    c->ps.persist_ok = getenv("SLAMGPU_NO_PERSIST") == nullptr;                               // diagnostic / tests: slamgpu_run_observe as a loop of launches
     c->special_ok = getenv("SLAMGPU_NO_SPECIAL") == nullptr;                               // diagnostic / tests: kernels.h: update_special
     c->counted_ok = getenv("SLAMGPU_NO_COUNTED") == nullptr;                               // diagnostic / tests: kernels.h: update_counted
     if (const char *e = getenv("SLAMGPU_CONSOLIDATE_ABOVE")) c->consolidate_above = atoi(e);
@@ -714,24 +569,7 @@ void slamgpu_destroy(slamgpu_ctx *c) {
     if (c->peek_dev) (void) hipFree(c->peek_dev);
     posterior_release(c);
     association_release(c);
-    if (c->pq_host) (void) hipHostFree(c->pq_host);
-    for (int b = 0; b < slamgpu_ctx::kPqBufs; b++)
-        if (c->pq_kev[b]) (void) hipEventDestroy(c->pq_kev[b]);
-    if (c->psync_dev) (void) hipFree(c->psync_dev);
-    if (c->ppk_dev) (void) hipFree(c->ppk_dev);
-    if (c->pring_dev) (void) hipFree(c->pring_dev);
-    if (c->pdraw_dev) (void) hipFree(c->pdraw_dev);
-    if (c->pstatus_host) (void) hipHostFree(c->pstatus_host);
-    if (c->book_dev) (void) hipFree(c->book_dev);
-    if (c->refcnt_dev) (void) hipFree(c->refcnt_dev);
-    if (c->take_dev) (void) hipFree(c->take_dev);
-    if (c->book_host) (void) hipHostFree(c->book_host);
-    for (int i = 0; i < kRing; i++)
-        if (c->obs_ev[i]) (void) hipEventDestroy(c->obs_ev[i]);
-    if (c->obs_stream) {
-        (void) hipStreamSynchronize(c->obs_stream);
-        (void) hipStreamDestroy(c->obs_stream);
-    }
+    observe_release(c);
     multigpu_release(c);
     // (the weight scratch after it: ws.blk_w[0] is the context's own again, not a caller's totals buffer)
     for (int b = 0; b < 2; b++) {
@@ -742,13 +580,6 @@ void slamgpu_destroy(slamgpu_ctx *c) {
     }
     for (int b = 0; b < 2; b++)
         if (c->ws.keep[b]) (void) hipFree(c->ws.keep[b]);
-    if (c->front_dev) (void) hipFree(c->front_dev);
-    if (c->front_host) (void) hipHostFree(c->front_host);
-    if (c->front_pkt_dev) (void) hipFree(c->front_pkt_dev);
-    if (c->map_dev) (void) hipFree(c->map_dev);
-    if (c->obs_r_dev) (void) hipFree(c->obs_r_dev);
-    if (c->table_dev) (void) hipFree(c->table_dev);
-    if (c->obs_out_dev) (void) hipFree(c->obs_out_dev);
     if (c->erow_dev) (void) hipFree(c->erow_dev);
     if (c->live_dev) (void) hipFree(c->live_dev);
     if (c->rows_dev) (void) hipFree(c->rows_dev);
@@ -886,7 +717,7 @@ int issue_update(slamgpu_ctx *c, UpdateArgs &U, int n_new, int n_rows, bool need
     U.finalize = c->unreduced.has ? 1 : 0;  // (sharded: this shard's partials of the previous step, shard_finalize_kernel)
     U.finalize_hist = c->unreduced.hist;
     U.finalize_par = c->unreduced.par;
-    if (c->collect) {
+    if (c->ps.collect) {
         // persistent loop: this iteration rides in the queue of ONE launch (slamgpu_run_observe); everything the host keeps
         // track of moves on exactly as if the launch had been made
         PersistStep q{};
@@ -902,14 +733,14 @@ int issue_update(slamgpu_ctx *c, UpdateArgs &U, int n_new, int n_rows, bool need
         q.finalize = U.finalize;
         q.finalize_par = U.finalize_par;
         q.finalize_hist = U.finalize_hist;
-        if (!c->collect->have_first) {
-            c->collect->have_first = true;
-            c->collect->B = c->B;
-            c->collect->U = U;
-            c->collect->rng = rng;
-            c->collect->ws = c->ws;
+        if (!c->ps.collect->have_first) {
+            c->ps.collect->have_first = true;
+            c->ps.collect->B = c->B;
+            c->ps.collect->U = U;
+            c->ps.collect->rng = rng;
+            c->ps.collect->ws = c->ws;
         }
-        c->collect->steps.push_back(q);
+        c->ps.collect->steps.push_back(q);
     } else {
         Timed t(c, c->cfg.method == SLAMGPU_FASTSLAM2 ? "fs2_update" : "fs1_update");
         if (c->as.pp_launch) c->k->update_particle(c->stream, c->B, PA, U, rng, c->ws, *c->as.pp_launch, !c->special_ok);
@@ -951,9 +782,9 @@ int issue_update(slamgpu_ctx *c, UpdateArgs &U, int n_new, int n_rows, bool need
     HIP_TRY(hipGetLastError());
     // path recording: this update's ancestors into origin[].  Only resample_kernel leaves them in keep[] (an inline plan finds them in
     // registers), so the stage runs now, as launches of its own, instead of inside the next update launch
-    if (c->path.cap > 0) return path_compose(c);
+    if (c->po.path.cap > 0) return path_compose(c);
     // the pose ring keeps the recorder's rule: the stage runs now, as launches of its own (every entry needs it settled anyway)
-    if (c->pose.cap > 0) return flush_stages(c);
+    if (c->po.pose.cap > 0) return flush_stages(c);
     return 0;
 }
 
@@ -1140,19 +971,9 @@ int do_update(slamgpu_ctx *c, const float *zf, const int32_t *idf, int32_t m, co
         U.small.magic = kSmallMagic;
         U.big = nullptr;
     } else {
-        const int slot = (int) (c->pkt_seq++ % kRing);
-        if (c->pkt_ev_used[slot]) HIP_TRY(hipEventSynchronize(c->pkt_ev[slot]));
-        char *ph = c->pkt_host + (size_t) slot * c->pkt_bytes;
-        ObsPacket *hp = reinterpret_cast<ObsPacket *>(ph);
-        hp->m = m;
-        hp->n = n;
-        hp->nf = c->nf;
-        hp->n_rows = n_rows;
-        hp->e_new = e_new;
-        hp->status = 0;
-        hp->cap = 0;  // dense layout
-        hp->pad = 0;
-        int32_t *hidf = reinterpret_cast<int32_t *>(hp + 1);
+        BigPacket bp;
+        if (int rc = bp.begin(c, m, n, c->nf, n_rows, e_new)) return rc;
+        int32_t *hidf = reinterpret_cast<int32_t *>(bp.host + 1);
         float *hzf = reinterpret_cast<float *>(hidf + m + nc);
         float *hzn = hzf + 2 * m;
         if (m) {
@@ -1166,11 +987,8 @@ int do_update(slamgpu_ctx *c, const float *zf, const int32_t *idf, int32_t m, co
         if (n_rows) memcpy(hrow + m + nc, c->live_rows.data(), sizeof(int32_t) * n_rows);
         const size_t used = sizeof(ObsPacket) + sizeof(int32_t) * ((size_t) m + nc) + sizeof(float) * 2 * (m + n) + sizeof(int32_t) * ((size_t) m + nc + n_rows);
         U.n_cons = nc;
-        char *pd = c->pkt_dev + (size_t) slot * c->pkt_bytes;
-        HIP_TRY(hipMemcpyAsync(pd, ph, used, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipEventRecord(c->pkt_ev[slot], c->stream));
-        c->pkt_ev_used[slot] = true;
-        U.big = reinterpret_cast<const ObsPacket *>(pd);
+        if (int rc = bp.commit(c, used)) return rc;
+        U.big = reinterpret_cast<const ObsPacket *>(bp.dev);
     }
     // the row this update opens is in use from now on; the rows it emptied can be opened again by a later update
     if (e_new >= 0) {
@@ -1191,132 +1009,13 @@ int predict_controls(slamgpu_ctx *c, const float *controls, int32_t n_controls, 
     return 0;
 }
 
-namespace {
-
-// FastSLAM{1,2}::update with the observation made on the device (slamgpu_step_observe): observe_book_kernel writes the packet
-// and the genealogy bookkeeping into device memory, the update launch reads them there.
-int do_update_dev(slamgpu_ctx *c, const float xtrue[3], float max_range, const float R[4], int32_t noise, const float *r1,
-                  const float *r2, const float *normals, const float *strata) {
-    if (!c->map_dev) return fail(SLAMGPU_ERR_INVALID, "no map: call slamgpu_set_map first");
-    if ((!c->B.compact || c->mid_compact) && !(c->cfg.flags & SLAMGPU_FLAG_DEVICE_OBSERVE))
-        return fail(SLAMGPU_ERR_INVALID, "create the context with SLAMGPU_FLAG_DEVICE_OBSERVE (its observation packets live in device memory)");
-    if (!is_single(c)) return fail(SLAMGPU_ERR_INVALID, "slamgpu_step_observe: single contexts only");
-    if (c->map_n > c->B.cap_nf) return fail(SLAMGPU_ERR_CAPACITY, "map of %d landmarks, capacity %d", c->map_n, c->B.cap_nf);
-    if (!xtrue || !R || noise < 0 || noise > 2 || (noise == 1 && (!r1 || !r2))) return fail(SLAMGPU_ERR_INVALID, "bad arguments");
-    const bool tape = c->cfg.rng_mode == SLAMGPU_RNG_TAPE;
-    if (tape && !strata) return fail(SLAMGPU_ERR_INVALID, "TAPE mode needs strata[N] (and normals[3N] for FastSLAM2)");
-    HIP_TRY(hipSetDevice(c->cfg.device));
-    if (int rc = book_push(c)) return rc;
-    c->obs_step++;
-    if (c->B.compact) {
-        // compact context: no front-end launch at all: every block of the update launch works the packet out for itself from
-        // the state the previous launch left (kernels.h: FrontArgs; kernels.hip: front_make)
-        UpdateArgs U{};
-        U.method = c->cfg.method;
-        U.m = kStageBound;  // (sizes the launch's record staging: the kernel learns m from the packet it makes)
-        U.e_new = -1;
-        U.small.magic = kSmallMagic;
-        for (int q = 0; q < c->map_n; q++) {  // the map rides in the words of the new landmarks' observations
-            U.small.zn[q] = c->map_host[(size_t) q];
-            U.small.zn[kSmallObs + q] = c->map_host[(size_t) c->map_n + q];
-        }
-        if (noise == 1)
-            for (int q = 0; q < c->map_n; q++) {
-                U.small.zf[q] = r1[q];
-                U.small.zf[kSmallObs + q] = r2[q];
-            }
-        FrontArgs &F = U.front;
-        F.on = 1;
-        F.nlm = c->map_n;
-        F.cap_nf = c->B.cap_nf;
-        F.noise = noise;
-        F.x = xtrue[0];
-        F.y = xtrue[1];
-        F.phi = xtrue[2];
-        F.max_range = max_range;
-        F.sr = sqrtf(R[0]);
-        F.sb = sqrtf(R[3]);
-        F.k0 = (uint32_t) c->cfg.seed;
-        F.k1 = (uint32_t) (c->cfg.seed >> 32);
-        F.step = ++c->observe_step;
-        F.cons_above = c->consolidate ? c->consolidate_above : -1;
-        F.state_in = c->front_dev + c->front_par;
-        F.state_out = c->front_dev + (c->front_par ^ 1);
-        F.out = c->obs_out_dev;
-        F.pkt = c->front_pkt_dev;
-        memcpy(U.R, R, sizeof U.R);
-        const bool need_normals = c->cfg.method == SLAMGPU_FASTSLAM2 && normals != nullptr;
-        if (int rc = issue_update(c, U, -1, -1, need_normals, normals, strata, false)) return rc;
-        c->front_par ^= 1;
-        c->last_pkt_dev = reinterpret_cast<char *>(c->front_pkt_dev);
-        c->fresh_row = -1;  // (the device's book knows)
-        return 0;
-    }
-    const size_t nl = (size_t) c->map_n;
-    // The front-end kernel runs on a stream of its own, ahead of the update launches: packet t is made while update t - 1
-    // still computes (it depends on the true pose and on the previous front-end kernel only); events order the two streams:
-    // update t waits for packet t, and a ring slot is rewritten only after the update that read it has finished.
-    if (noise == 1) {
-        HIP_TRY(hipStreamSynchronize(c->obs_stream));  // (parity mode only: single-buffered normals, pageable sources)
-        HIP_TRY(hipMemcpyAsync(c->obs_r_dev, r1, sizeof(float) * nl, hipMemcpyHostToDevice, c->obs_stream));
-        HIP_TRY(hipMemcpyAsync(c->obs_r_dev + nl, r2, sizeof(float) * nl, hipMemcpyHostToDevice, c->obs_stream));
-        HIP_TRY(hipStreamSynchronize(c->obs_stream));
-    }
-    const int slot = (int) (c->pkt_seq++ % kRing);
-    if (c->pkt_ev_used[slot]) HIP_TRY(hipStreamWaitEvent(c->obs_stream, c->pkt_ev[slot], 0));
-    char *pd = c->pkt_dev + (size_t) slot * c->pkt_bytes;
-    ObserveArgs A{};
-    A.lm = c->map_dev;
-    A.table = c->table_dev;
-    A.nlm = c->map_n;
-    A.x = xtrue[0];
-    A.y = xtrue[1];
-    A.phi = xtrue[2];
-    A.max_range = max_range;
-    A.sr = sqrtf(R[0]);
-    A.sb = sqrtf(R[3]);
-    A.noise = noise;
-    A.r1 = c->obs_r_dev;
-    A.r2 = c->obs_r_dev + nl;
-    A.k0 = (uint32_t) c->cfg.seed;
-    A.k1 = (uint32_t) (c->cfg.seed >> 32);
-    A.step = ++c->observe_step;
-    A.out = c->obs_out_dev;
-    A.pkt = reinterpret_cast<ObsPacket *>(pd);
-    A.book = c->book_dev;
-    A.erow = c->erow_dev;
-    A.live = c->live_dev;
-    A.refcnt = c->refcnt_dev;
-    A.cap_nf = c->B.cap_nf;
-    A.cap_rows = c->B.cap_rows;
-    A.cons_target = c->consolidate ? c->plain_rows_target : -1;
-    A.cons_budget = kPlainConsBudget;
-    A.take = c->take_dev;
-    c->k->observe_book(c->obs_stream, A);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(c->obs_ev[slot], c->obs_stream));
-    HIP_TRY(hipStreamWaitEvent(c->stream, c->obs_ev[slot], 0));
-    c->last_pkt_dev = pd;
-    c->fresh_row = -1;  // (the device's book knows)
-
-    UpdateArgs U{};
-    U.method = c->cfg.method;
-    U.m = c->map_n;  // upper bounds: the kernel reads the packet's header
-    U.n = c->map_n;
-    U.nf = 0;
-    U.e_new = -1;
-    U.n_rows = c->B.cap_rows;
-    U.dev_packet = 1;
-    U.big = reinterpret_cast<const ObsPacket *>(pd);
-    memcpy(U.R, R, sizeof U.R);
-    const bool need_normals = c->cfg.method == SLAMGPU_FASTSLAM2 && normals != nullptr;
-    if (int rc = issue_update(c, U, -1, -1, need_normals, normals, strata, false)) return rc;
-    HIP_TRY(hipEventRecord(c->pkt_ev[slot], c->stream));  // the launch that reads this ring slot: the slot may be rewritten after it
-    c->pkt_ev_used[slot] = true;
+int record_step(slamgpu_ctx *c) {
+    if (int rc = slamgpu_estimate_async(c)) return rc;
+    if (c->po.path.cap > 0)
+        if (int rc = path_append(c)) return rc;  // record r beside history entry r
+    if (c->po.pose.cap > 0) return pose_append(c);  // and pose entry r
     return 0;
 }
-
-}  // namespace
 
 extern "C" {
 
@@ -1337,216 +1036,13 @@ int slamgpu_step(slamgpu_ctx *c, const float *controls, int32_t n_controls, cons
     if (n_controls < 0 || (n_controls > 0 && !controls)) return fail(SLAMGPU_ERR_INVALID, "bad control list");
     if (n_controls > 0 && c->cfg.add_predict_noise && c->cfg.rng_mode == SLAMGPU_RNG_TAPE)
         return fail(SLAMGPU_ERR_INVALID, "slamgpu_step cannot carry TAPE-mode predict noise: call slamgpu_predict per control");
-    if (c->innov.cap > 0 && m > c->innov.cap)  // (refused before anything is applied: the record between predicts and update could not be made)
-        return fail(SLAMGPU_ERR_CAPACITY, "slamgpu_step: %d observations, the innovation ring holds %d entries", m, c->innov.cap);
+    if (c->po.innov.cap > 0 && m > c->po.innov.cap)  // (refused before anything is applied: the record between predicts and update could not be made)
+        return fail(SLAMGPU_ERR_CAPACITY, "slamgpu_step: %d observations, the innovation ring holds %d entries", m, c->po.innov.cap);
     if (int rc = predict_controls(c, controls, n_controls, Q, dt)) return rc;
-    if (c->innov.cap > 0)  // the innovation ring: this step's packet against the predicted set, before the update takes it
+    if (c->po.innov.cap > 0)  // the innovation ring: this step's packet against the predicted set, before the update takes it
         if (int rc = innov_append(c, zf, idf, m, R)) return rc;
     if (int rc = slamgpu_update(c, zf, idf, m, zn, n, R, normals, strata)) return rc;
-    if (record_estimate) {
-        if (int rc = slamgpu_estimate_async(c)) return rc;
-        if (c->path.cap > 0)
-            if (int rc = path_append(c)) return rc;  // record r beside history entry r
-        if (c->pose.cap > 0) return pose_append(c);  // and pose entry r
-    }
-    return 0;
-}
-
-int slamgpu_step_observe(slamgpu_ctx *c, const float *controls, int32_t n_controls, const float Q[4], float dt, const float xtrue[3],
-                         float max_range, const float R[4], int32_t noise, const float *r1, const float *r2, const float *normals,
-                         const float *strata, int32_t record_estimate) {
-    if (int rc = check_ctx(c)) return rc;
-    if (n_controls < 0 || (n_controls > 0 && (!controls || !Q))) return fail(SLAMGPU_ERR_INVALID, "bad control list");
-    if (n_controls > 0 && c->cfg.add_predict_noise && c->cfg.rng_mode == SLAMGPU_RNG_TAPE)
-        return fail(SLAMGPU_ERR_INVALID, "slamgpu_step_observe cannot carry TAPE-mode predict noise: call slamgpu_predict per control");
-    if (int rc = predict_controls(c, controls, n_controls, Q, dt)) return rc;
-    if (int rc = do_update_dev(c, xtrue, max_range, R, noise, r1, r2, normals, strata)) return rc;
-    if (record_estimate) {
-        if (int rc = slamgpu_estimate_async(c)) return rc;
-        if (c->path.cap > 0)
-            if (int rc = path_append(c)) return rc;  // record r beside history entry r
-        if (c->pose.cap > 0) return pose_append(c);  // and pose entry r
-    }
-    return 0;
-}
-
-// K iterations of the wrapper's loop as ONE launch (kernels.h: PersistArgs): the K calls of slamgpu_step_observe are made with
-// the context in collect mode -- every piece of host bookkeeping moves on as usual, the update launches are queued instead of
-// made -- then the queue is uploaded and update_persist runs it.
-// what the persistent loop needs beside the context's own state (allocated once: at slamgpu_set_map for contexts that qualify, so
-// that a caller's first slamgpu_run_observe does not pay for it; K: entries per queue buffer)
-static int persist_setup(slamgpu_ctx *c, int32_t K) {
-    HIP_TRY(hipSetDevice(c->cfg.device));
-    if (!c->psync_dev) {
-        HIP_TRY(hipMalloc((void **) &c->psync_dev, sizeof(uint32_t) * kPersistSyncAlloc));
-        HIP_TRY(hipMemsetAsync(c->psync_dev, 0, sizeof(uint32_t) * kPersistSyncAlloc, c->stream));
-        HIP_TRY(hipMalloc((void **) &c->ppk_dev, sizeof(int32_t) * 2 * kSmallWords));
-        HIP_TRY(hipMalloc((void **) &c->pring_dev, sizeof(PersistStep) * 4));
-        HIP_TRY(hipMalloc((void **) &c->pdraw_dev, sizeof(float4) * 2 * 6 * (size_t) c->B.ncap));
-        HIP_TRY(hipHostMalloc((void **) &c->pstatus_host, kPersistHostWords * sizeof(uint32_t), hipHostMallocDefault));
-        for (int w = 0; w < kPersistHostWords; w++) c->pstatus_host[w] = 0;
-        for (int b = 0; b < slamgpu_ctx::kPqBufs; b++) HIP_TRY(hipEventCreateWithFlags(&c->pq_kev[b], hipEventDisableTiming));
-    }
-    if ((size_t) K > c->pq_cap) {
-        HIP_TRY(hipStreamSynchronize(c->stream));  // (a launch in flight may still read the old queue)
-        if (c->pq_host) (void) hipHostFree(c->pq_host);
-        c->pq_host = nullptr;
-        c->pq_cap = 0;
-        const size_t cap = std::max<size_t>((size_t) K, 256);
-        HIP_TRY(hipHostMalloc((void **) &c->pq_host, sizeof(PersistStep) * slamgpu_ctx::kPqBufs * cap, hipHostMallocDefault));
-        c->pq_cap = cap;
-        for (int b = 0; b < slamgpu_ctx::kPqBufs; b++) c->pq_kev_used[b] = false;
-    }
-    return 0;
-}
-
-static bool persist_eligible(const slamgpu_ctx *c) {
-    return c->persist_ok && c->B.compact && !c->mid_compact && is_single(c) &&
-           c->cfg.rng_mode == SLAMGPU_RNG_PHILOX && c->ws.nblocks <= kPersistMaxBlocks && c->ws.nblocks <= c->scan_min_blocks;
-}
-
-static int run_observe_persist(slamgpu_ctx *c, int32_t K, const int32_t *n_controls, const float *controls, const float Q[4], float dt,
-                               const float *xtrue, float max_range, const float R[4], int32_t noise) {
-    if (int rc = persist_setup(c, K)) return rc;
-    // everything that can fail without a launch having been made comes BEFORE the host's bookkeeping moves on by K iterations
-    // (a failing hipEventSynchronize / hipMemsetAsync behind the collect loop left the host K iterations ahead of the
-    // device).  The queue buffer of kPqBufs calls ago must be free (bounds the host's run-ahead), and the loop's meeting words
-    // are zeroed in stream order behind the previous launch.
-    const int b = c->pq_next;
-    if (c->pq_kev_used[b]) HIP_TRY(hipEventSynchronize(c->pq_kev[b]));
-    HIP_TRY(hipMemsetAsync(c->psync_dev, 0, sizeof(uint32_t) * kPersistSyncWords, c->stream));
-    slamgpu_ctx::PersistCollect col;
-    col.steps.reserve((size_t) K);
-    c->collect = &col;
-    int rc = 0;
-    std::string why;
-    size_t row = 0;
-    int32_t k = 0;
-    for (; k < K; k++) {
-        const int32_t nc = n_controls[k];
-        rc = slamgpu_step_observe(c, nc ? controls + 3 * row : nullptr, nc, Q, dt, xtrue + 3 * (size_t) k, max_range, R, noise, nullptr, nullptr, nullptr,
-                                  nullptr, 1);
-        if (rc) {
-            why = slamgpu_last_error();
-            break;
-        }
-        row += (size_t) nc;
-    }
-    c->collect = nullptr;
-    if (!col.steps.empty()) {  // (after a failure: the iterations before the failing one are applied, as the header promises)
-        const size_t n = col.steps.size();
-        // The queue is NOT uploaded (round 5, measured with the drop-in binary at 1 000 particles): a hipMemcpyAsync enqueued behind a
-        // running launch made the CALL wait for that launch -- 270-520 us per call of 32 iterations, on the context's stream or on one
-        // of its own -- so the host simulated its next iterations only after the GPU had finished the last ones.  The kernel reads
-        // the entries out of pinned host memory instead, each an iteration before it needs it.
-        c->pq_next = (c->pq_next + 1) % slamgpu_ctx::kPqBufs;
-        PersistStep *qh = c->pq_host + (size_t) b * c->pq_cap;
-        memcpy(qh, col.steps.data(), sizeof(PersistStep) * n);
-        UpdateArgs U = col.U;
-        U.persist.queue = qh;
-        U.persist.K = (int32_t) n;
-        // one wait is bounded in time (2 s of the 100 MHz constant clock: a member workgroup that is dispatched that late -- another
-        // process holding the CUs -- abandons the launch) and, for the tests of the abandon path, in polls
-        U.persist.max_spins = 0xffffffffu;
-        U.persist.max_ticks = 200000000ull;
-        if (const char *e = getenv("SLAMGPU_PERSIST_MAX_SPINS")) U.persist.max_spins = (uint32_t) std::max(0, atoi(e));
-        if (const char *e = getenv("SLAMGPU_PERSIST_MAX_MS")) U.persist.max_ticks = 100000ull * (unsigned long long) std::max(0, atoi(e));
-        U.persist.serial = (int32_t) (c->persist_launches + 1);
-        U.persist.abort_at = -1;
-        if (const char *e = getenv("SLAMGPU_PERSIST_ABORT_AT")) U.persist.abort_at = atoi(e);
-        U.persist.sync = c->psync_dev;
-        U.persist.host_status = c->pstatus_host;
-        U.persist.state_final = c->front_dev + c->front_par;  // (the copy the next launch reads)
-        U.persist.packets = c->ppk_dev;
-        U.persist.ring = c->pring_dev;
-        U.persist.draws = c->pdraw_dev;
-        // drawer workgroups (one per tile): FastSLAM 1 in the fast build, whose predicts draw eight Philox blocks per particle and step
-        U.persist.drawers = (c->cfg.method == SLAMGPU_FASTSLAM1 && c->cfg.math_mode == SLAMGPU_MATH_FAST && c->cfg.add_predict_noise &&
-                             !c->cfg.use_heading && getenv("SLAMGPU_NO_DRAWERS") == nullptr) ? c->ws.nblocks : 0;
-        {
-            Timed t(c, "persist_loop");
-            c->k->update_persist(c->stream, col.B, PredictArgs{}, U, col.rng, col.ws);
-        }
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventRecord(c->pq_kev[b], c->stream));
-        c->pq_kev_used[b] = true;
-        c->persist_launches++;
-        c->persist_steps += (int64_t) n;
-    }
-    if (rc) return fail(rc, "slamgpu_run_observe: iteration %d of %d: %s", (int) k, (int) K, why.c_str());
-    return 0;
-}
-
-int slamgpu_run_observe(slamgpu_ctx *c, int32_t K, const int32_t *n_controls, const float *controls, const float Q[4], float dt,
-                        const float *xtrue, float max_range, const float R[4], int32_t noise) {
-    if (int rc = check_ctx(c)) return rc;
-    // everything that can be refused is refused BEFORE the first device call: a failing call applies no iteration at all
-    if (K < 0 || (K > 0 && (!n_controls || !xtrue || !R))) return fail(SLAMGPU_ERR_INVALID, "slamgpu_run_observe: bad arguments");
-    if (noise != 0 && noise != 2) return fail(SLAMGPU_ERR_INVALID, "slamgpu_run_observe: noise must be 0 or 2 (a tape is per iteration: slamgpu_step_observe)");
-    if (c->cfg.rng_mode == SLAMGPU_RNG_TAPE) return fail(SLAMGPU_ERR_INVALID, "slamgpu_run_observe: TAPE-mode contexts take their draws per iteration (slamgpu_step_observe)");
-    if (K == 0) return 0;
-    if (!c->map_dev) return fail(SLAMGPU_ERR_INVALID, "slamgpu_run_observe: no map: call slamgpu_set_map first");
-    if ((!c->B.compact || c->mid_compact) && !(c->cfg.flags & SLAMGPU_FLAG_DEVICE_OBSERVE))
-        return fail(SLAMGPU_ERR_INVALID, "slamgpu_run_observe: create the context with SLAMGPU_FLAG_DEVICE_OBSERVE (its observation packets live in device memory)");
-    if (!is_single(c)) return fail(SLAMGPU_ERR_INVALID, "slamgpu_run_observe: single contexts only");
-    if (c->map_n > c->B.cap_nf) return fail(SLAMGPU_ERR_CAPACITY, "slamgpu_run_observe: map of %d landmarks, capacity %d", c->map_n, c->B.cap_nf);
-    size_t total = 0;
-    int32_t max_nc = 0;
-    for (int32_t k = 0; k < K; k++) {
-        if (n_controls[k] < 0) return fail(SLAMGPU_ERR_INVALID, "slamgpu_run_observe: iteration %d has a negative control count", (int) k);
-        total += (size_t) n_controls[k];
-        max_nc = std::max(max_nc, n_controls[k]);
-    }
-    if (total > 0 && (!controls || !Q)) return fail(SLAMGPU_ERR_INVALID, "slamgpu_run_observe: %zu controls but no control list / Q", total);
-    if (total > 0 && c->cfg.add_predict_noise && c->cfg.rng_mode == SLAMGPU_RNG_TAPE)
-        return fail(SLAMGPU_ERR_INVALID, "slamgpu_run_observe cannot carry TAPE-mode predict noise");
-    if ((int64_t) c->hist_n + K > kHistCap)
-        return fail(SLAMGPU_ERR_CAPACITY, "slamgpu_run_observe: %d iterations would overflow the estimate history (%d of %d entries in use): call "
-                                          "slamgpu_history_fetch first, or hand over fewer iterations", (int) K, c->hist_n, kHistCap);
-    if (int rc = persist_check(c)) return rc;
-    // small compact contexts: ONE launch for all K iterations (kernels.h: PersistArgs)
-    // (not while the path is recorded: the loop's resampling decisions and ancestors never leave its launch)
-    // (nor while the pose ring is on: an entry per iteration needs the set between two iterations)
-    if (K >= 2 && persist_eligible(c) && max_nc <= kMaxFusedPredict && c->path.cap == 0 && c->pose.cap == 0)
-        return run_observe_persist(c, K, n_controls, controls, Q, dt, xtrue, max_range, R, noise);
-    size_t row = 0;
-    for (int32_t k = 0; k < K; k++) {
-        const int32_t nc = n_controls[k];
-        if (int rc = slamgpu_step_observe(c, nc ? controls + 3 * row : nullptr, nc, Q, dt, xtrue + 3 * (size_t) k, max_range, R, noise, nullptr, nullptr,
-                                          nullptr, nullptr, 1)) {
-            std::string why = slamgpu_last_error();
-            return fail(rc, "slamgpu_run_observe: iteration %d of %d: %s", (int) k, (int) K, why.c_str());
-        }
-        row += (size_t) nc;
-    }
-    return 0;
-}
-
-int slamgpu_observe_fetch(slamgpu_ctx *c, float *z, int32_t *vis, int32_t *nz, float *zf, int32_t *idf, int32_t *m, float *zn, int32_t *n) {
-    if (int rc = check_ctx(c)) return rc;
-    if (!c->last_pkt_dev) return fail(SLAMGPU_ERR_INVALID, "no device-made observation yet (slamgpu_step_observe)");
-    HIP_TRY(hipSetDevice(c->cfg.device));
-    if (c->obs_stream) HIP_TRY(hipStreamSynchronize(c->obs_stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    const size_t C = (size_t) c->map_n;
-    std::vector<char> pk(sizeof(ObsPacket) + 4 * 6 * C), ob(sizeof(ObserveOut) + 4 * 3 * C);
-    HIP_TRY(hipMemcpy(pk.data(), c->last_pkt_dev, pk.size(), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(ob.data(), c->obs_out_dev, ob.size(), hipMemcpyDeviceToHost));
-    const ObsPacket *h = reinterpret_cast<const ObsPacket *>(pk.data());
-    const int32_t *base = reinterpret_cast<const int32_t *>(h + 1);
-    const ObserveOut *o = reinterpret_cast<const ObserveOut *>(ob.data());
-    const float *hz = reinterpret_cast<const float *>(o + 1);
-    const int32_t *hvis = reinterpret_cast<const int32_t *>(hz + 2 * C);
-    if (z) memcpy(z, hz, sizeof(float) * 2 * (size_t) o->nz);
-    if (vis) memcpy(vis, hvis, sizeof(int32_t) * (size_t) o->nz);
-    if (nz) *nz = o->nz;
-    if (idf) memcpy(idf, base, sizeof(int32_t) * (size_t) h->m);
-    if (zf) memcpy(zf, base + C, sizeof(float) * 2 * (size_t) h->m);
-    if (zn) memcpy(zn, base + 3 * C, sizeof(float) * 2 * (size_t) h->n);
-    if (m) *m = h->m;
-    if (n) *n = h->n;
-    if (h->status & kStatusCapacity) return fail(SLAMGPU_ERR_CAPACITY, "the device front end dropped new landmarks: landmark capacity %d exceeded", c->B.cap_nf);
-    return 0;
+    return record_estimate ? record_step(c) : 0;
 }
 
 int slamgpu_dev_alloc(slamgpu_ctx *c, uint64_t bytes, void **ptr) {
@@ -1648,7 +1144,7 @@ int slamgpu_step_status(slamgpu_ctx *c, int32_t *status) {
     if (int rc = check_ctx(c)) return rc;
     if (!status) return fail(SLAMGPU_ERR_INVALID, "null output");
     if (int rc = read_ctrl(c)) return rc;
-    *status = c->ctrl_host->status | (c->front_status & kStatusCapacity);
+    *status = c->ctrl_host->status | (c->fe.front_status & kStatusCapacity);
     return 0;
 }
 
@@ -1668,91 +1164,6 @@ int slamgpu_ancestors(slamgpu_ctx *c, int32_t *keep) {
     return 0;
 }
 
-int slamgpu_set_map(slamgpu_ctx *c, const float *lm, int32_t nlm) {
-    if (int rc = check_ctx(c)) return rc;
-    if (!lm || nlm <= 0) return fail(SLAMGPU_ERR_INVALID, "empty map");
-    if (int rc = book_pull(c)) return rc;  // (a new map starts a new landmark table: the book goes back to the host first)
-    HIP_TRY(hipSetDevice(c->cfg.device));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    for (void *p : {(void *) c->map_dev, (void *) c->obs_r_dev, (void *) c->table_dev, (void *) c->obs_out_dev})
-        if (p) (void) hipFree(p);
-    c->map_dev = c->obs_r_dev = nullptr;
-    c->table_dev = nullptr;
-    c->obs_out_dev = nullptr;
-    const size_t n = (size_t) nlm;
-    HIP_TRY(hipMalloc((void **) &c->map_dev, sizeof(float) * 2 * n));
-    HIP_TRY(hipMalloc((void **) &c->obs_r_dev, sizeof(float) * 2 * n));
-    HIP_TRY(hipMalloc((void **) &c->table_dev, sizeof(int32_t) * n));
-    HIP_TRY(hipMalloc((void **) &c->obs_out_dev, sizeof(ObserveOut) + 4 * 8 * n));  // z 2n, vis n, zf 2n, idf n, zn 2n
-    HIP_TRY(hipMemcpy(c->map_dev, lm, sizeof(float) * 2 * n, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemsetAsync(c->table_dev, 0xff, sizeof(int32_t) * n, c->stream));  // -1: never seen
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    c->map_n = nlm;
-    c->obs_nf = 0;
-    c->map_host.assign(lm, lm + 2 * n);
-    c->front_ready = false;  // (a new map starts a new landmark table)
-    // a context that may run slamgpu_run_observe as the persistent loop gets that loop's buffers now, not inside its first call
-    if (persist_eligible(c) && nlm <= kSmallObs - 1)
-        if (int rc = persist_setup(c, 256)) return rc;
-    return 0;
-}
-
-int slamgpu_observe(slamgpu_ctx *c, const float xtrue[3], float max_range, const float R[4], int32_t noise, const float *r1,
-                    const float *r2, float *z, int32_t *vis, int32_t *nz, float *zf, int32_t *idf, int32_t *m, float *zn, int32_t *n) {
-    if (int rc = check_ctx(c)) return rc;
-    if (!c->map_dev) return fail(SLAMGPU_ERR_INVALID, "no map: call slamgpu_set_map first");
-    if (!xtrue || !R || noise < 0 || noise > 2 || (noise == 1 && (!r1 || !r2))) return fail(SLAMGPU_ERR_INVALID, "bad arguments");
-    HIP_TRY(hipSetDevice(c->cfg.device));
-    const size_t nl = (size_t) c->map_n;
-    if (noise == 1) {
-        HIP_TRY(hipMemcpyAsync(c->obs_r_dev, r1, sizeof(float) * nl, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipMemcpyAsync(c->obs_r_dev + nl, r2, sizeof(float) * nl, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));  // pageable sources
-    }
-    ObserveArgs A{};
-    A.lm = c->map_dev;
-    A.table = c->table_dev;
-    A.nlm = c->map_n;
-    A.nf = c->obs_nf;
-    A.x = xtrue[0];
-    A.y = xtrue[1];
-    A.phi = xtrue[2];
-    A.max_range = max_range;
-    A.sr = sqrtf(R[0]);
-    A.sb = sqrtf(R[3]);
-    A.noise = noise;
-    A.r1 = c->obs_r_dev;
-    A.r2 = c->obs_r_dev + nl;
-    A.k0 = (uint32_t) c->cfg.seed;
-    A.k1 = (uint32_t) (c->cfg.seed >> 32);
-    A.step = ++c->observe_step;
-    A.out = c->obs_out_dev;
-    {
-        Timed t(c, "observe");
-        c->k->observe(c->stream, A);
-    }
-    HIP_TRY(hipGetLastError());
-    std::vector<char> host(sizeof(ObserveOut) + 4 * 8 * nl);
-    HIP_TRY(hipMemcpyAsync(host.data(), c->obs_out_dev, host.size(), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    const ObserveOut *o = reinterpret_cast<const ObserveOut *>(host.data());
-    const float *hz = reinterpret_cast<const float *>(o + 1);
-    const int32_t *hvis = reinterpret_cast<const int32_t *>(hz + 2 * nl);
-    const float *hzf = reinterpret_cast<const float *>(hvis + nl);
-    const int32_t *hidf = reinterpret_cast<const int32_t *>(hzf + 2 * nl);
-    const float *hzn = reinterpret_cast<const float *>(hidf + nl);
-    if (z) memcpy(z, hz, sizeof(float) * 2 * (size_t) o->nz);
-    if (vis) memcpy(vis, hvis, sizeof(int32_t) * (size_t) o->nz);
-    if (zf) memcpy(zf, hzf, sizeof(float) * 2 * (size_t) o->m);
-    if (idf) memcpy(idf, hidf, sizeof(int32_t) * (size_t) o->m);
-    if (zn) memcpy(zn, hzn, sizeof(float) * 2 * (size_t) o->n);
-    if (nz) *nz = o->nz;
-    if (m) *m = o->m;
-    if (n) *n = o->n;
-    c->obs_nf = o->nf_after;
-    return 0;
-}
-
 int slamgpu_num_landmarks(slamgpu_ctx *c) {
     if (!c) return SLAMGPU_ERR_INVALID;
     if (int rc = book_pull(c)) return rc;  // (device-driven steps: the count lives on the device; synchronises)
@@ -1764,34 +1175,6 @@ int slamgpu_genealogy_rows(slamgpu_ctx *c, int32_t *in_use, int32_t *capacity) {
     if (int rc = book_pull(c)) return rc;
     if (in_use) *in_use = (int32_t) c->live_rows.size();
     if (capacity) *capacity = c->B.cap_rows;
-    return 0;
-}
-
-int slamgpu_persist_info(slamgpu_ctx *c, int64_t *launches, int64_t *iterations, int32_t *cross_xcd) {
-    if (int rc = check_ctx(c)) return rc;
-    if (launches) *launches = c->persist_launches;
-    if (iterations) *iterations = c->persist_steps;
-    if (cross_xcd) {
-        *cross_xcd = 0;
-        if (c->psync_dev) {
-            HIP_TRY(hipSetDevice(c->cfg.device));
-            HIP_TRY(hipStreamSynchronize(c->stream));
-            uint32_t v = 0;
-            HIP_TRY(hipMemcpy(&v, c->psync_dev + kPersistSyncCross, sizeof v, hipMemcpyDeviceToHost));
-            *cross_xcd = (int32_t) v;
-            return persist_check(c);
-        }
-    }
-    return 0;
-}
-
-int slamgpu_persist_status(slamgpu_ctx *c, int32_t *abandoned, int64_t *launch, int32_t *completed, int32_t *handed) {
-    if (int rc = check_ctx(c)) return rc;
-    const bool ab = c->pstatus_host && __atomic_load_n(c->pstatus_host, __ATOMIC_ACQUIRE) != 0;
-    if (abandoned) *abandoned = ab ? 1 : 0;
-    if (launch) *launch = ab ? (int64_t) c->pstatus_host[2] : 0;
-    if (completed) *completed = ab ? (int32_t) c->pstatus_host[1] : 0;
-    if (handed) *handed = ab ? (int32_t) c->pstatus_host[3] : 0;
     return 0;
 }
 
@@ -1832,6 +1215,46 @@ int slamgpu_sync(slamgpu_ctx *c) {
     return persist_check(c);
 }
 
+// what download and peek hand out, from the records as the device keeps them (host loops).  M pose records -> xv / Pv9 / w
+static void unpack_pose(const float4 *pa, const float4 *pb, const float2 *pc, size_t M, float *xv, float *Pv9, float *w) {
+    for (size_t i = 0; i < M; i++) {
+        if (xv) {
+            xv[3 * i] = pa[i].x;
+            xv[3 * i + 1] = pa[i].y;
+            xv[3 * i + 2] = pa[i].z;
+        }
+        if (Pv9) {
+            const float p00 = pb[i].x, p10 = pb[i].y, p11 = pb[i].z, p20 = pb[i].w, p21 = pc[i].x, p22 = pc[i].y;
+            float *P = Pv9 + 9 * i;
+            P[0] = p00; P[1] = p10; P[2] = p20;
+            P[3] = p10; P[4] = p11; P[5] = p21;
+            P[6] = p20; P[7] = p21; P[8] = p22;
+        }
+        if (w) w[i] = pa[i].w;
+    }
+}
+
+// ... and landmark records [jn][M], the landmarks [j0, j0 + jn) of nf -> xf / Pf4 [M][nf]
+static void unpack_landmarks(const float4 *la, const float *lb, size_t M, int j0, int jn, int nf, float *xf, float *Pf4) {
+    for (size_t i = 0; i < M; i++)
+        for (int j = 0; j < jn; j++) {
+            const float4 a = la[(size_t) j * M + i];
+            const float b = lb[(size_t) j * M + i];
+            const size_t at = i * (size_t) nf + (size_t) (j0 + j);
+            if (xf) {
+                xf[at * 2] = a.x;
+                xf[at * 2 + 1] = a.y;
+            }
+            if (Pf4) {
+                float *P = Pf4 + at * 4;
+                P[0] = a.z;
+                P[1] = a.w;
+                P[2] = a.w;
+                P[3] = b;
+            }
+        }
+}
+
 int slamgpu_download_range(slamgpu_ctx *c, int32_t first, int32_t count, float *xv, float *Pv9, float *w, float *xf, float *Pf4) {
     if (int rc = check_ctx(c)) return rc;
     if (first < 0 || count < 0 || (int64_t) first + count > c->B.n)
@@ -1852,21 +1275,7 @@ int slamgpu_download_range(slamgpu_ctx *c, int32_t first, int32_t count, float *
     HIP_TRY(hipMemcpy(pa.data(), c->B.poseA[cur] + first, sizeof(float4) * M, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(pb.data(), c->B.poseB[cur] + first, sizeof(float4) * M, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(pc.data(), c->B.poseC[cur] + first, sizeof(float2) * M, hipMemcpyDeviceToHost));
-    for (size_t i = 0; i < M; i++) {
-        if (xv) {
-            xv[3 * i] = pa[i].x;
-            xv[3 * i + 1] = pa[i].y;
-            xv[3 * i + 2] = pa[i].z;
-        }
-        if (Pv9) {
-            const float p00 = pb[i].x, p10 = pb[i].y, p11 = pb[i].z, p20 = pb[i].w, p21 = pc[i].x, p22 = pc[i].y;
-            float *P = Pv9 + 9 * i;
-            P[0] = p00; P[1] = p10; P[2] = p20;
-            P[3] = p10; P[4] = p11; P[5] = p21;
-            P[6] = p20; P[7] = p21; P[8] = p22;
-        }
-        if (w) w[i] = pa[i].w;
-    }
+    unpack_pose(pa.data(), pb.data(), pc.data(), M, xv, Pv9, w);
     if ((xf || Pf4) && nf > 0) {
         // every landmark row has its own live buffer (kernels.h: lmk_live); rows are fetched a bounded batch at a time so
         // that a 10 000-landmark context does not need the whole slice on the host twice
@@ -1882,23 +1291,7 @@ int slamgpu_download_range(slamgpu_ctx *c, int32_t first, int32_t count, float *
                 HIP_TRY(hipMemcpyAsync(lb.data() + (size_t) j * M, c->B.lmkB[live[j0 + j]] + row, sizeof(float) * M, hipMemcpyDeviceToHost, c->stream));
             }
             HIP_TRY(hipStreamSynchronize(c->stream));
-            for (size_t i = 0; i < M; i++)
-                for (int j = 0; j < jn; j++) {
-                    const float4 a = la[(size_t) j * M + i];
-                    const float b = lb[(size_t) j * M + i];
-                    const size_t at = i * nf + (size_t) (j0 + j);
-                    if (xf) {
-                        xf[at * 2] = a.x;
-                        xf[at * 2 + 1] = a.y;
-                    }
-                    if (Pf4) {
-                        float *P = Pf4 + at * 4;
-                        P[0] = a.z;
-                        P[1] = a.w;
-                        P[2] = a.w;
-                        P[3] = b;
-                    }
-                }
+            unpack_landmarks(la.data(), lb.data(), M, j0, jn, nf, xf, Pf4);
         }
     }
     return 0;
@@ -1956,35 +1349,8 @@ int slamgpu_peek(slamgpu_ctx *c, int32_t first, int32_t stride, int32_t count, f
         HIP_TRY(hipMemcpyAsync(lb.data(), A.lb, 4 * M * nf, hipMemcpyDeviceToHost, c->stream));
     }
     HIP_TRY(hipStreamSynchronize(c->stream));
-    for (size_t i = 0; i < M; i++) {
-        if (xv) {
-            xv[3 * i] = pa[i].x;
-            xv[3 * i + 1] = pa[i].y;
-            xv[3 * i + 2] = pa[i].z;
-        }
-        if (Pv9) {
-            float *P = Pv9 + 9 * i;
-            P[0] = pb[i].x; P[1] = pb[i].y; P[2] = pb[i].w;
-            P[3] = pb[i].y; P[4] = pb[i].z; P[5] = pc[i].x;
-            P[6] = pb[i].w; P[7] = pc[i].x; P[8] = pc[i].y;
-        }
-        if (w) w[i] = pa[i].w;
-        for (int j = 0; j < nf; j++) {
-            const float4 a = la[(size_t) j * M + i];
-            const size_t at = i * (size_t) nf + (size_t) j;
-            if (xf) {
-                xf[at * 2] = a.x;
-                xf[at * 2 + 1] = a.y;
-            }
-            if (Pf4) {
-                float *P = Pf4 + at * 4;
-                P[0] = a.z;
-                P[1] = a.w;
-                P[2] = a.w;
-                P[3] = lb[(size_t) j * M + i];
-            }
-        }
-    }
+    unpack_pose(pa.data(), pb.data(), pc.data(), M, xv, Pv9, w);
+    unpack_landmarks(la.data(), lb.data(), M, 0, nf, nf, xf, Pf4);
     return 0;
 }
 
@@ -2056,8 +1422,8 @@ int slamgpu_upload(slamgpu_ctx *c, int32_t nf, const float *xv, const float *Pv9
     }
     c->est_fresh = false;
     c->mg.shard_est_fresh = false;
-    if (c->path.cap > 0) {  // a new set: nothing descends from the retained records
-        c->path.first = c->path.next;
+    if (c->po.path.cap > 0) {  // a new set: nothing descends from the retained records
+        c->po.path.first = c->po.path.next;
         if (int rc = path_identity(c)) return rc;
         HIP_TRY(hipGetLastError());
     }

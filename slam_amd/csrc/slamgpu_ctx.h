@@ -1,4 +1,4 @@
-// The context of libslamgpu.so and what its translation units (slamgpu.cpp, association.cpp, posterior.cpp, multigpu.cpp) share.  Private: not
+// The context of libslamgpu.so and what its translation units (slamgpu.cpp, observe.cpp, association.cpp, posterior.cpp, multigpu.cpp) share.  Private: not
 // installed, and no function declared here is exported (hidden visibility).
 #pragma once
 #define SLAMGPU_EXPERIMENTAL 1  // (the library defines every entry point, the experimental ones included)
@@ -81,6 +81,20 @@ struct DevBuf {
     }
 };
 using DevCounters = DevBuf<unsigned long long>;  // cumulative counters a kernel adds to: allocated zeroed at first use
+// the same in pinned host memory (the contents are not zeroed): SLAMGPU_ERR_ALLOC with `what` in the text
+int pin_grow(void **p, size_t *cap, size_t n, size_t elem, const char *what);
+template <typename T>
+struct PinBuf {
+    T *p = nullptr;
+    size_t cap = 0;
+    operator T *() const { return p; }
+    int reserve(size_t n, const char *what) { return n <= cap ? 0 : pin_grow((void **) &p, &cap, n, sizeof(T), what); }
+    void release() {
+        if (p) (void) hipHostFree(p);
+        p = nullptr;
+        cap = 0;
+    }
+};
 
 // The state of the association layer (association.cpp): slamgpu_ctx::as.  association_release frees it.
 struct Assoc {
@@ -192,6 +206,111 @@ struct Multi {
     uint32_t flag_seq = 0;
 };
 
+// The state of the observation layer (observe.cpp): slamgpu_ctx::fe and slamgpu_ctx::ps.  observe_release frees both.
+struct Front {
+    // observation front end (slamgpu_set_map / slamgpu_observe): grow-only, a new map keeps a buffer that is large enough
+    DevBuf<float> map_dev, obs_r_dev;
+    DevBuf<int32_t> table_dev;
+    DevBuf<ObserveOut> obs_out_dev;  // the header, then 8 map_n words (two elements per landmark): z 2n, vis n, zf 2n, idf n, zn 2n
+    int32_t map_n = 0, obs_nf = 0;
+    uint32_t observe_step = 0;
+    std::vector<float> map_host;     // [2][map_n], as slamgpu_set_map received it
+    // device-resident genealogy bookkeeping (slamgpu_step_observe): while book_on_device the tables erow_dev / live_dev /
+    // refcnt_dev / book_dev are the truth and the host's vectors are stale; book_pull / book_push hand the ownership over
+    bool book_on_device = false;
+    int32_t front_status = 0;        // sticky kStatus* bits of the device front end seen by book_pull (carried back by book_push)
+    DevBuf<DevBook> book_dev;
+    DevBuf<int32_t> refcnt_dev, take_dev;
+    PinBuf<int32_t> book_host;       // pinned staging of book_pull / book_push
+    hipStream_t obs_stream = nullptr;  // the front-end kernels run here, a step ahead of the update launches (events order them)
+    hipEvent_t obs_ev[kRing]{};        // observe_book of the packet in ring slot k has finished
+    char *last_pkt_dev = nullptr;    // packet of the last slamgpu_step_observe (slamgpu_observe_fetch)
+    // compact contexts: the front end runs inside the update launch (kernels.h: FrontArgs); its state lives in two device
+    // copies, read / written alternately (front_par: the one the next launch reads)
+    DevBuf<FrontState> front_dev;
+    PinBuf<FrontState> front_host;
+    DevBuf<char> front_pkt_dev;      // an ObsPacket in the fixed layout of kFrontLanes landmarks
+    int front_par = 0;
+    bool front_ready = false;
+};
+
+// persistent small-N step loop (slamgpu_run_observe, kernels.h: PersistArgs)
+struct PersistCollect {              // while set, issue_update queues its launch instead of making it
+    std::vector<PersistStep> steps;
+    bool have_first = false;
+    Buffers B{};
+    UpdateArgs U{};
+    RngArgs rng{};
+    WeightScratch ws{};
+};
+struct Persist {
+    bool persist_ok = true;              // SLAMGPU_NO_PERSIST=1 turns it off (diagnostic / tests: the per-step loop)
+    PersistCollect *collect = nullptr;
+    // the queue of a launch lives in PINNED HOST memory and the kernel reads it there (an entry an iteration ahead: the PCIe trip is
+    // hidden): kPqBufs buffers of pq_cap entries used in turn; a buffer is rewritten once the launch that read it has finished
+    static constexpr int kPqBufs = 4;
+    PinBuf<PersistStep> pq_host;
+    size_t pq_cap = 0;
+    hipEvent_t pq_kev[kPqBufs] = {};
+    bool pq_kev_used[kPqBufs] = {};
+    int pq_next = 0;
+    DevBuf<uint32_t> psync_dev;
+    PinBuf<uint32_t> pstatus_host;
+    DevBuf<int32_t> ppk_dev;             // [2][kSmallWords] observation packets of the loop's helper workgroup
+    DevBuf<PersistStep> pring_dev;       // [4] the loop's ring of queue entries in device memory (kernels.h: PersistArgs::ring)
+    DevBuf<float4> pdraw_dev;            // [2][6][ncap] draws of the loop's drawer workgroups (FastSLAM 1, fast build)
+    int64_t persist_launches = 0, persist_steps = 0;
+    // persist_setup ran to its end: the buffers are there, the status and meeting words zeroed (the last event it makes says so)
+    bool ready() const { return pq_kev[kPqBufs - 1] != nullptr; }
+};
+
+// The state of the posterior layer (posterior.cpp): slamgpu_ctx::po.  posterior_release frees it.
+struct Posterior {
+    DevArena msum;                   // staging and partials of the map, pair, innovation and joint summaries
+    // path recording (slamgpu_path_*; kernels.h: PathRing).  path.cap = 0: off, nothing allocated, no kernel of it launched.
+    // origin[path_org] is the live origin array
+    Ring path;
+    float4 *path_rec_dev = nullptr;
+    int32_t *path_origin_dev[2] = {nullptr, nullptr};
+    int path_org = 0;
+    DevArena path_arena;             // staging, push buffers and partials of slamgpu_path_trace / _summary
+    // pose posterior (slamgpu_pose_*; kernels.h: PoseSummaryArgs).  pose.cap = 0: the per-step ring is off.  Nothing is allocated and no kernel of it launched until the ring is enabled or
+    // slamgpu_pose_summary is called
+    Ring pose;
+    double *pose_ring_dev = nullptr; // [pose.cap][kPoseStride]
+    double *pose_dev = nullptr;      // [tiles][kPoseFields] partials | [kPoseStride] staging of slamgpu_pose_summary
+    // innovation posterior (slamgpu_innovation_*; kernels.h: InnovArgs).  innov.cap = 0: the ring is off.
+    // innov_records counts the _record calls since the enable.  A packet travels
+    // through one of kInnovStage pinned staging slots (an event per slot says when the device has taken it: a record does not wait
+    // for the device unless it is kInnovStage packets ahead of it).  Nothing is allocated and no kernel of it launched until the ring
+    // is enabled or slamgpu_innovation_summary is called
+    Ring innov;
+    int64_t innov_records = 0;
+    double *innov_ring_dev = nullptr;  // [innov.cap][kInnStride]
+    int32_t *innov_tag_dev = nullptr;  // [innov.cap][2]: record, slot
+    char *innov_host = nullptr;        // pinned [kInnovStage][innov_host_m] x (zf 8 B | idf 4 B)
+    size_t innov_host_m = 0;
+    uint64_t innov_seq = 0;
+    hipEvent_t innov_ev[4]{};
+    bool innov_ev_used[4]{};
+    int32_t *innov_lab_host = nullptr;  // pinned, two pieces: the labels of slamgpu_innovation_summary_labels on their way down
+    uint64_t innov_lab_seq = 0;
+    hipEvent_t innov_lab_ev[2]{};
+    bool innov_lab_ev_used[2]{};
+};
+
+// One slot of the big-packet ring (slamgpu_ctx::pkt_*) on its way to the device.  begin takes the next slot, waits ON THE HOST for
+// the launch that last read it and sets the pinned header to the dense layout; commit uploads `used` bytes and records the slot's
+// event.  (A device-made packet takes its slot with pkt_take_slot and waits on the front end's stream instead: do_update_dev.)
+struct BigPacket {
+    int slot = 0;
+    ObsPacket *host = nullptr;
+    char *dev = nullptr;
+    int begin(slamgpu_ctx *c, int32_t m, int32_t n, int32_t nf, int32_t n_rows, int32_t e_new);
+    int commit(slamgpu_ctx *c, size_t used);
+};
+int pkt_take_slot(slamgpu_ctx *c);
+
 #pragma GCC visibility pop
 
 // (default visibility, as ever: its implicit members are among the library's weak symbols)
@@ -266,94 +385,20 @@ struct slamgpu_ctx {
     std::vector<int32_t> live_pos;   // [cap_rows] position in live_rows, -1 if not live
     int32_t *erow_dev = nullptr, *rows_dev = nullptr;  // device copies for gather / flatten / shard pack + unpack
     Multi mg;                        // sharded and distributed operation (multigpu.cpp)
-    // observation front end (slamgpu_set_map / slamgpu_observe)
-    float *map_dev = nullptr, *obs_r_dev = nullptr;
-    int32_t *table_dev = nullptr;
-    ObserveOut *obs_out_dev = nullptr;
-    int32_t map_n = 0, obs_nf = 0;
-    uint32_t observe_step = 0;
     int fresh_row = -1;              // row the last update opened, while nothing but the resample the next update launch
                                      // applies has touched it: records of its landmarks sit in the source slot itself
     bool tables_dirty = true;
-    // device-resident genealogy bookkeeping (slamgpu_step_observe): while book_on_device the tables erow_dev / live_dev /
-    // refcnt_dev / book_dev are the truth and the host's vectors are stale; book_pull / book_push hand the ownership over
-    bool book_on_device = false;
-    int32_t front_status = 0;        // sticky kStatus* bits of the device front end seen by book_pull (carried back by book_push)
-    DevBook *book_dev = nullptr;
-    int32_t *refcnt_dev = nullptr, *take_dev = nullptr;
-    int32_t *book_host = nullptr;    // pinned staging of book_pull / book_push
-    hipStream_t obs_stream = nullptr;  // the front-end kernels run here, a step ahead of the update launches (events order them)
-    hipEvent_t obs_ev[kRing]{};        // observe_book of the packet in ring slot k has finished
-    char *last_pkt_dev = nullptr;    // packet of the last slamgpu_step_observe (slamgpu_observe_fetch)
-    // compact contexts: the front end runs inside the update launch (kernels.h: FrontArgs); its state lives in two device
-    // copies, read / written alternately (front_par: the one the next launch reads)
-    std::vector<float> map_host;     // [2][map_n], as slamgpu_set_map received it
-    FrontState *front_dev = nullptr, *front_host = nullptr;
-    ObsPacket *front_pkt_dev = nullptr;
-    int front_par = 0;
-    bool front_ready = false;
-    Assoc as;                        // the gated and per-particle association (association.cpp)
+    Front fe;                        // the observation front end and the genealogy book's hand-over (observe.cpp)
+    Persist ps;                      // the persistent step loop (observe.cpp)
+    Assoc as;                       // the gated and per-particle association (association.cpp)
     char *peek_dev = nullptr;        // staging of slamgpu_peek, grown on demand
     size_t peek_bytes = 0;
-    DevArena msum;                   // staging and partials of the map, pair, innovation and joint summaries
-    // path recording (slamgpu_path_*; kernels.h: PathRing).  path.cap = 0: off, nothing allocated, no kernel of it launched.
-    // origin[path_org] is the live origin array
-    Ring path;
-    float4 *path_rec_dev = nullptr;
-    int32_t *path_origin_dev[2] = {nullptr, nullptr};
-    int path_org = 0;
-    DevArena path_arena;             // staging, push buffers and partials of slamgpu_path_trace / _summary
-    // pose posterior (slamgpu_pose_*; kernels.h: PoseSummaryArgs).  pose.cap = 0: the per-step ring is off.  Nothing is allocated and no kernel of it launched until the ring is enabled or
-    // slamgpu_pose_summary is called
-    Ring pose;
-    double *pose_ring_dev = nullptr; // [pose.cap][kPoseStride]
-    double *pose_dev = nullptr;      // [tiles][kPoseFields] partials | [kPoseStride] staging of slamgpu_pose_summary
-    // innovation posterior (slamgpu_innovation_*; kernels.h: InnovArgs).  innov.cap = 0: the ring is off.
-    // innov_records counts the _record calls since the enable.  A packet travels
-    // through one of kInnovStage pinned staging slots (an event per slot says when the device has taken it: a record does not wait
-    // for the device unless it is kInnovStage packets ahead of it).  Nothing is allocated and no kernel of it launched until the ring
-    // is enabled or slamgpu_innovation_summary is called
-    Ring innov;
-    int64_t innov_records = 0;
-    double *innov_ring_dev = nullptr;  // [innov.cap][kInnStride]
-    int32_t *innov_tag_dev = nullptr;  // [innov.cap][2]: record, slot
-    char *innov_host = nullptr;        // pinned [kInnovStage][innov_host_m] x (zf 8 B | idf 4 B)
-    size_t innov_host_m = 0;
-    uint64_t innov_seq = 0;
-    hipEvent_t innov_ev[4]{};
-    bool innov_ev_used[4]{};
-    int32_t *innov_lab_host = nullptr;  // pinned, two pieces: the labels of slamgpu_innovation_summary_labels on their way down
-    uint64_t innov_lab_seq = 0;
-    hipEvent_t innov_lab_ev[2]{};
-    bool innov_lab_ev_used[2]{};
+    Posterior po;                    // path, pose and innovation posteriors and the summaries' staging (posterior.cpp)
     unsigned long long *stamps_dev = nullptr;  // diagnostic (SLAMGPU_STAMPS=1 + libslamgpu_stamps.so): UpdateArgs::stamps
-    // persistent small-N step loop (slamgpu_run_observe, kernels.h: PersistArgs)
-    bool persist_ok = true;              // SLAMGPU_NO_PERSIST=1 turns it off (diagnostic / tests: the per-step loop)
     bool special_ok = true;              // SLAMGPU_NO_SPECIAL=1 turns it off (diagnostic / tests: update_kernel's general instantiation for every launch)
     bool counted_ok = true;              // SLAMGPU_NO_COUNTED=1 turns it off (diagnostic / tests: never update_kernel_counted)
     int64_t counted_launches[kCountedMax + 1] = {};  // specialised launches by counted instantiation, [0]: the plain specialised kernel (slamgpu_update_counted_launches: tests)
     int64_t special_launches = 0;        // update launches that took a specialised instantiation (slamgpu_update_special_launches: tests)
-    struct PersistCollect {              // while set, issue_update queues its launch instead of making it
-        std::vector<PersistStep> steps;
-        bool have_first = false;
-        Buffers B{};
-        UpdateArgs U{};
-        RngArgs rng{};
-        WeightScratch ws{};
-    } *collect = nullptr;
-    // the queue of a launch lives in PINNED HOST memory and the kernel reads it there (an entry an iteration ahead: the PCIe trip is
-    // hidden): kPqBufs buffers of pq_cap entries used in turn; a buffer is rewritten once the launch that read it has finished
-    static constexpr int kPqBufs = 4;
-    PersistStep *pq_host = nullptr;
-    size_t pq_cap = 0;
-    hipEvent_t pq_kev[kPqBufs] = {};
-    bool pq_kev_used[kPqBufs] = {};
-    int pq_next = 0;
-    uint32_t *psync_dev = nullptr, *pstatus_host = nullptr;
-    int32_t *ppk_dev = nullptr;          // [2][kSmallWords] observation packets of the loop's helper workgroup
-    PersistStep *pring_dev = nullptr;    // [4] the loop's ring of queue entries in device memory (kernels.h: PersistArgs::ring)
-    float4 *pdraw_dev = nullptr;         // [2][6][ncap] draws of the loop's drawer workgroups (FastSLAM 1, fast build)
-    int64_t persist_launches = 0, persist_steps = 0;
     EstStage unplanned;           // the last update: resampling stage not run yet
     EstStage unreduced;           // an update whose partials exist (est_part[par]) but are not reduced yet
 };
@@ -385,19 +430,15 @@ inline int64_t n_global(const slamgpu_ctx *c) { return c->cfg.n_particles_global
 // a context that holds the whole particle set: neither connected to peers nor a shard of a larger set
 inline bool is_single(const slamgpu_ctx *c) { return !c->mg.dist && c->cfg.n_particles_global == c->cfg.n_particles; }
 
-// slamgpu.cpp's, as the association, posterior and multi-GPU layers call them
+// slamgpu.cpp's, as the observation, association, posterior and multi-GPU layers call them
 int check_ctx(slamgpu_ctx *c);
-int book_pull(slamgpu_ctx *c);
 int sync_tables(slamgpu_ctx *c);
 int flush_predict(slamgpu_ctx *c);
 int flush_stages(slamgpu_ctx *c);
 int materialize(slamgpu_ctx *c);
 int read_ctrl(slamgpu_ctx *c, bool need_set = false);
-int persist_check(slamgpu_ctx *c);
 int demote_to_plain(slamgpu_ctx *c);
 int issue_update(slamgpu_ctx *c, UpdateArgs &U, int n_new, int n_rows, bool need_normals, const float *normals, const float *strata, bool sharded);
-int book_staging(slamgpu_ctx *c);
-void book_rebuild(slamgpu_ctx *c);
 void rows_add_live(slamgpu_ctx *c, int r);
 void rows_remove_live(slamgpu_ctx *c, int r);
 void compose_predicts(PredictArgs &P);
@@ -414,6 +455,16 @@ int estimate_now(slamgpu_ctx *c, double *hist);
 // been waited for and before an entry is handed out
 int history_take(slamgpu_ctx *c, int32_t max_count, int32_t *count, const std::function<void(int, const double *)> &per_entry,
                  int (*ready)(slamgpu_ctx *) = nullptr);
+// the estimate / path / pose tail of a step entry point that records
+int record_step(slamgpu_ctx *c);
+// observe.cpp's
+int book_pull(slamgpu_ctx *c);
+int book_staging(slamgpu_ctx *c);
+void book_rebuild(slamgpu_ctx *c);
+int persist_check(slamgpu_ctx *c);
+// what the observation kernels' arguments share (the map, the pose, the noise, the Philox key); takes the next observation step
+ObserveArgs observe_args(slamgpu_ctx *c, const float xtrue[3], float max_range, const float R[4], int32_t noise);
+void observe_release(slamgpu_ctx *c);  // slamgpu_destroy's share of this layer
 // multigpu.cpp's
 void multigpu_release(slamgpu_ctx *c);  // slamgpu_destroy's share of this layer
 // association.cpp's, as the steps and the posterior layer call them
