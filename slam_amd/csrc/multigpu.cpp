@@ -198,9 +198,8 @@ void multigpu_release(slamgpu_ctx *c) {
     if (g.flags_dev) (void) hipFree(g.flags_dev);
     g.poolA_dev.release();
     g.poolB_dev.release();
-    if (!g.own_totals) c->ws.blk_w[0] = g.own_blk_w;  // (the caller's buffer stays the caller's)
-    if (g.plan_host) (void) hipHostFree(g.plan_host);
-    if (g.plan_seq_host) (void) hipHostFree(g.plan_seq_host);
+    g.plan_host.release();
+    g.plan_seq_host.release();
 }
 
 extern "C" {
@@ -231,10 +230,7 @@ int slamgpu_shard_set_totals_buffer(slamgpu_ctx *c, float *totals_dev) {
     if (int rc = check_ctx(c)) return rc;
     HIP_TRY(hipSetDevice(c->cfg.device));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    if (c->mg.own_totals) c->mg.own_blk_w = c->ws.blk_w[0];
-    float *p = totals_dev ? totals_dev : c->mg.own_blk_w;
-    c->mg.own_totals = totals_dev == nullptr;
-    c->ws.blk_w[0] = p;  // shard contexts only use parity 0 of the weight scratch
+    c->ws.blk_w[0] = totals_dev ? totals_dev : c->own.blk_w[0].p;  // shard contexts only use parity 0 of the weight scratch
     return 0;
 }
 

@@ -306,7 +306,7 @@ int do_update_dev(slamgpu_ctx *c, const float xtrue[3], float max_range, const f
     }
     // (the slot's wait is the front end's stream's, not the host's as in BigPacket::begin: the device writes this packet)
     const int slot = pkt_take_slot(c);
-    if (c->pkt_ev_used[slot]) HIP_TRY(hipStreamWaitEvent(f.obs_stream, c->pkt_ev[slot], 0));
+    if (c->pkt_slots.used[slot]) HIP_TRY(hipStreamWaitEvent(f.obs_stream, c->pkt_slots.ev[slot], 0));
     char *pd = c->pkt_dev + (size_t) slot * c->pkt_bytes;
     ObserveArgs A = observe_args(c, xtrue, max_range, R, noise);
     A.nf = 0;  // (not read there: observe_book_kernel takes the count from the book)
@@ -339,9 +339,7 @@ int do_update_dev(slamgpu_ctx *c, const float xtrue[3], float max_range, const f
     memcpy(U.R, R, sizeof U.R);
     const bool need_normals = c->cfg.method == SLAMGPU_FASTSLAM2 && normals != nullptr;
     if (int rc = issue_update(c, U, -1, -1, need_normals, normals, strata, false)) return rc;
-    HIP_TRY(hipEventRecord(c->pkt_ev[slot], c->stream));  // the launch that reads this ring slot: the slot may be rewritten after it
-    c->pkt_ev_used[slot] = true;
-    return 0;
+    return c->pkt_slots.record(slot, c->stream);  // the launch that reads this ring slot: the slot may be rewritten after it
 }
 
 // K iterations of the wrapper's loop as ONE launch (kernels.h: PersistArgs): the K calls of slamgpu_step_observe are made with
@@ -361,8 +359,7 @@ int persist_setup(slamgpu_ctx *c, int32_t K) {
     if (!p.ready()) {
         HIP_TRY(hipMemsetAsync(p.psync_dev, 0, sizeof(uint32_t) * kPersistSyncAlloc, c->stream));
         for (int w = 0; w < kPersistHostWords; w++) p.pstatus_host[w] = 0;
-        for (int b = 0; b < Persist::kPqBufs; b++)
-            if (!p.pq_kev[b]) HIP_TRY(hipEventCreateWithFlags(&p.pq_kev[b], hipEventDisableTiming));
+        if (int rc = p.pq_slots.create()) return rc;
     }
     if ((size_t) K > p.pq_cap) {
         HIP_TRY(hipStreamSynchronize(c->stream));  // (a launch in flight may still read the old queue)
@@ -370,7 +367,7 @@ int persist_setup(slamgpu_ctx *c, int32_t K) {
         const size_t cap = std::max<size_t>((size_t) K, 256);
         if (int rc = p.pq_host.reserve(Persist::kPqBufs * cap, "persistent loop: queue")) return rc;
         p.pq_cap = cap;
-        for (int b = 0; b < Persist::kPqBufs; b++) p.pq_kev_used[b] = false;
+        p.pq_slots.reset();
     }
     return 0;
 }
@@ -388,8 +385,8 @@ int run_observe_persist(slamgpu_ctx *c, int32_t K, const int32_t *n_controls, co
     // (a failing hipEventSynchronize / hipMemsetAsync behind the collect loop left the host K iterations ahead of the
     // device).  The queue buffer of kPqBufs calls ago must be free (bounds the host's run-ahead), and the loop's meeting words
     // are zeroed in stream order behind the previous launch.
-    const int b = p.pq_next;
-    if (p.pq_kev_used[b]) HIP_TRY(hipEventSynchronize(p.pq_kev[b]));
+    const int b = p.pq_slots.peek();
+    if (int rc = p.pq_slots.wait(b)) return rc;
     HIP_TRY(hipMemsetAsync(p.psync_dev, 0, sizeof(uint32_t) * kPersistSyncWords, c->stream));
     PersistCollect col;
     col.steps.reserve((size_t) K);
@@ -415,7 +412,7 @@ int run_observe_persist(slamgpu_ctx *c, int32_t K, const int32_t *n_controls, co
         // running launch made the CALL wait for that launch -- 270-520 us per call of 32 iterations, on the context's stream or on one
         // of its own -- so the host simulated its next iterations only after the GPU had finished the last ones.  The kernel reads
         // the entries out of pinned host memory instead, each an iteration before it needs it.
-        p.pq_next = (p.pq_next + 1) % Persist::kPqBufs;
+        p.pq_slots.take();
         PersistStep *qh = p.pq_host + (size_t) b * p.pq_cap;
         memcpy(qh, col.steps.data(), sizeof(PersistStep) * n);
         UpdateArgs U = col.U;
@@ -444,8 +441,7 @@ int run_observe_persist(slamgpu_ctx *c, int32_t K, const int32_t *n_controls, co
             c->k->update_persist(c->stream, col.B, PredictArgs{}, U, col.rng, col.ws);
         }
         HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventRecord(p.pq_kev[b], c->stream));
-        p.pq_kev_used[b] = true;
+        if (int rc2 = p.pq_slots.record(b, c->stream)) return rc2;
         p.persist_launches++;
         p.persist_steps += (int64_t) n;
     }
@@ -458,8 +454,7 @@ int run_observe_persist(slamgpu_ctx *c, int32_t K, const int32_t *n_controls, co
 void observe_release(slamgpu_ctx *c) {
     Persist &p = c->ps;
     p.pq_host.release();
-    for (int b = 0; b < Persist::kPqBufs; b++)
-        if (p.pq_kev[b]) (void) hipEventDestroy(p.pq_kev[b]);
+    p.pq_slots.release();
     p.psync_dev.release();
     p.ppk_dev.release();
     p.pring_dev.release();

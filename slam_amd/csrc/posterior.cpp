@@ -1,48 +1,13 @@
 // libslamgpu.so: the posterior summaries (slamgpu_map_*, slamgpu_joint_summary, slamgpu_pose_*, slamgpu_innovation_*, slamgpu_path_*).
 // Every summary reaches the particle set slamgpu_peek shows the same way (summary_enter), cuts its work to the partials' table the
-// same way (chunk_fit), lays its staging area out with one builder (Layout over a DevArena), launches through launch() and keeps its
+// same way (chunk_fit), lays its staging area out with one builder (Layout over a DevBuf<char>), launches through launch() and keeps its
 // history, where it has one, in a Ring.  slamgpu.cpp and association.cpp call path_compose, path_append, pose_append and innov_append* from their steps.
 #include "slamgpu_ctx.h"
 
 #pragma GCC visibility push(hidden)
 
-int DevArena::reserve(size_t total) {
-    if (total <= bytes) return 0;
-    release();
-    hipError_t e = hipMalloc((void **) &p, total);
-    if (e != hipSuccess) {
-        (void) hipGetLastError();
-        p = nullptr;
-        return fail(SLAMGPU_ERR_ALLOC, "hipMalloc(%zu): %s", total, hipGetErrorString(e));
-    }
-    bytes = total;
-    return 0;
-}
-void DevArena::release() {
-    if (p) (void) hipFree(p);
-    p = nullptr;
-    bytes = 0;
-}
-
 namespace {
 
-// the fields of a staging area, one behind the other: take them in order, reserve total(), then resolve each against the arena
-struct Layout {
-    template <class T>
-    struct Field {
-        size_t off;
-        T *at(const DevArena &a) const { return reinterpret_cast<T *>(a.p + off); }
-    };
-    size_t end = 0;
-    template <class T>
-    Field<T> take(size_t n, size_t align = 1) {
-        end = (end + align - 1) / align * align;
-        const Field<T> f{end};
-        end += sizeof(T) * n;
-        return f;
-    }
-    size_t total() const { return end; }
-};
 size_t up16(size_t v) { return (v + 15) / 16 * 16; }
 
 // how many of `items` go through a table of partials at a time: at most 16 MiB of it, in whole granules, at least one granule
@@ -92,6 +57,7 @@ int launch(slamgpu_ctx *c, const char *name, F &&f) {
     return 0;
 }
 
+constexpr const char *kSummaryStaging = "summaries: staging";
 int map_tiles(const slamgpu_ctx *c) { return (c->B.n + kMapTile - 1) / kMapTile; }
 
 // ---- rings ----
@@ -113,6 +79,31 @@ int ring_fetch(slamgpu_ctx *c, const Ring &r, const void *ring_dev, size_t row, 
     return 0;
 }
 
+// What an *_enable entry point does to its ring's buffers.  A Fresh names one of them with the size it is to have (0: none).  The new
+// ones first, into locals, so that a refused call leaves the setting as it was; then, if there is an old ring (`had`), the launches in
+// flight that may still use it are waited for, and the new buffers take the old ones' places
+template <class T>
+struct Fresh {
+    DevBuf<T> &live;
+    size_t n;
+    const char *what;
+    DevBuf<T> fresh{};
+};
+template <class... F>
+int ring_replace(slamgpu_ctx *c, const char *who, int32_t capacity, bool had, F &&...f) {
+    int rc = 0;
+    ((rc = rc ? rc : f.fresh.reserve(f.n, f.what)), ...);
+    if (rc) {
+        const std::string why = slamgpu_last_error();
+        rc = fail(rc, "%s: capacity %d: %s", who, capacity, why.c_str());
+    } else if (had && hipStreamSynchronize(c->stream) != hipSuccess) {
+        rc = fail(SLAMGPU_ERR_HIP, "%s: hipStreamSynchronize failed", who);
+    }
+    if (!rc) (std::swap(f.live, f.fresh), ...);
+    (f.fresh.release(), ...);
+    return rc;
+}
+
 // ---- path recording (slamgpu_path_*; kernels.h: PathRing) ----
 PathRing path_ring(const slamgpu_ctx *c) { return PathRing{c->po.path_rec_dev, c->po.path.cap}; }
 
@@ -126,15 +117,7 @@ int path_check(slamgpu_ctx *c, const char *who, int64_t first, int64_t count) {
 int pose_tiles(const slamgpu_ctx *c) { return (c->B.n + kPoseTile - 1) / kPoseTile; }
 
 int pose_reserve(slamgpu_ctx *c) {
-    if (c->po.pose_dev) return 0;
-    const size_t total = sizeof(double) * ((size_t) kPoseFields * (size_t) pose_tiles(c) + kPoseStride);
-    hipError_t e = hipMalloc((void **) &c->po.pose_dev, total);
-    if (e != hipSuccess) {
-        (void) hipGetLastError();
-        c->po.pose_dev = nullptr;
-        return fail(SLAMGPU_ERR_ALLOC, "hipMalloc(%zu): %s", total, hipGetErrorString(e));
-    }
-    return 0;
+    return c->po.pose_dev.reserve((size_t) kPoseFields * (size_t) pose_tiles(c) + kPoseStride, "pose summary: partials");
 }
 double *pose_staging(const slamgpu_ctx *c) { return c->po.pose_dev + (size_t) kPoseFields * (size_t) pose_tiles(c); }
 
@@ -188,21 +171,13 @@ int innov_labels_check(slamgpu_ctx *c, const char *fn, const float *z, int32_t n
 // the synchronisation of its hipFree.
 constexpr size_t kInnovLabPiece = (size_t) 1 << 18;  // words
 int innov_labels_down(slamgpu_ctx *c, const int32_t *labels, int32_t nz, int32_t *dst) {
-    static_assert(sizeof c->po.innov_lab_ev / sizeof c->po.innov_lab_ev[0] == 2, "two pieces");
-    if (!c->po.innov_lab_host) {
-        hipError_t e = hipHostMalloc((void **) &c->po.innov_lab_host, sizeof(int32_t) * 2 * kInnovLabPiece, hipHostMallocDefault);
-        if (e != hipSuccess) {
-            (void) hipGetLastError();
-            c->po.innov_lab_host = nullptr;
-            return fail(SLAMGPU_ERR_ALLOC, "hipHostMalloc(%zu): %s", sizeof(int32_t) * 2 * kInnovLabPiece, hipGetErrorString(e));
-        }
-    }
+    static_assert(sizeof c->po.innov_lab_slots.ev / sizeof c->po.innov_lab_slots.ev[0] == 2, "two pieces");
+    if (int rc = c->po.innov_lab_host.reserve(2 * kInnovLabPiece, "innovation summary: label pieces")) return rc;
     const size_t N = (size_t) c->B.n, total = N * (size_t) nz;
     size_t q = 0, i = 0;  // dst[at] = labels of observation q, particle i
     for (size_t at = 0; at < total; at += kInnovLabPiece) {
-        const int k = (int) (c->po.innov_lab_seq++ & 1);
-        if (!c->po.innov_lab_ev[k]) HIP_TRY(hipEventCreateWithFlags(&c->po.innov_lab_ev[k], hipEventDisableTiming));
-        if (c->po.innov_lab_ev_used[k]) HIP_TRY(hipEventSynchronize(c->po.innov_lab_ev[k]));
+        const int k = c->po.innov_lab_slots.take();
+        if (int rc = c->po.innov_lab_slots.wait(k)) return rc;
         int32_t *h = c->po.innov_lab_host + kInnovLabPiece * (size_t) k;
         const size_t n = std::min(kInnovLabPiece, total - at);
         for (size_t d = 0; d < n; d++) {
@@ -210,8 +185,7 @@ int innov_labels_down(slamgpu_ctx *c, const int32_t *labels, int32_t nz, int32_t
             if (++i == N) i = 0, q++;
         }
         HIP_TRY(hipMemcpyAsync(dst + at, h, sizeof(int32_t) * n, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipEventRecord(c->po.innov_lab_ev[k], c->stream));
-        c->po.innov_lab_ev_used[k] = true;
+        if (int rc = c->po.innov_lab_slots.record(k, c->stream)) return rc;
     }
     return 0;
 }
@@ -255,39 +229,29 @@ InnovLayout innov_layout(const slamgpu_ctx *c, int32_t m, size_t label_words) {
 // into the staging area, from where out_dev / hold_dev point at them.  Enqueued; the caller has checked the packet (m > 0)
 int innov_launch(slamgpu_ctx *c, const InnovPacket &P, int32_t m, const float *R, bool ring, const double **out_dev, const int32_t **hold_dev) {
     static_assert(SLAMGPU_INNOV_STRIDE == kInnStride && SLAMGPU_INNOV_SLOT_PER_PARTICLE == kInnSlotPerParticle, "public / device summary layout");
-    static_assert(sizeof c->po.innov_ev / sizeof c->po.innov_ev[0] == kInnovStage, "staging slots");
+    static_assert(sizeof c->po.innov_slots.ev / sizeof c->po.innov_slots.ev[0] == kInnovStage, "staging slots");
     if (int rc = summary_enter(c, "", kSettle | kTables)) return rc;
     const size_t M = (size_t) m;
     const InnovLayout V = innov_layout(c, m, P.labels ? M * (size_t) c->B.n : 0);
     const int tiles = V.tiles, chunk = V.chunk;
-    if (int rc = c->po.msum.reserve(V.L.total())) return rc;
+    if (int rc = c->po.msum.reserve(V.L.total(), kSummaryStaging)) return rc;
     const float *z_dev = P.z_dev;
     if (P.zf) {
         // the packet: through a pinned slot of the context's own, so that the caller's arrays are free again when the call returns
         if (M > c->po.innov_host_m) {
-            for (int k = 0; k < kInnovStage; k++)
-                if (c->po.innov_ev_used[k]) HIP_TRY(hipEventSynchronize(c->po.innov_ev[k]));
-            if (c->po.innov_host) (void) hipHostFree(c->po.innov_host);
-            c->po.innov_host = nullptr;
+            if (int rc = c->po.innov_slots.wait_all()) return rc;  // (the copies in flight read the old one)
             c->po.innov_host_m = 0;
             const size_t want = std::max<size_t>(M, 64);
-            hipError_t e = hipHostMalloc((void **) &c->po.innov_host, 12 * want * kInnovStage, hipHostMallocDefault);
-            if (e != hipSuccess) {
-                (void) hipGetLastError();
-                c->po.innov_host = nullptr;
-                return fail(SLAMGPU_ERR_ALLOC, "hipHostMalloc(%zu): %s", 12 * want * kInnovStage, hipGetErrorString(e));
-            }
+            if (int rc = c->po.innov_host.reserve(12 * want * kInnovStage, "innovation summary: packet slots")) return rc;
             c->po.innov_host_m = want;
         }
-        const int k = (int) (c->po.innov_seq++ % kInnovStage);
-        if (!c->po.innov_ev[k]) HIP_TRY(hipEventCreateWithFlags(&c->po.innov_ev[k], hipEventDisableTiming));
-        if (c->po.innov_ev_used[k]) HIP_TRY(hipEventSynchronize(c->po.innov_ev[k]));
+        const int k = c->po.innov_slots.take();
+        if (int rc = c->po.innov_slots.wait(k)) return rc;
         char *h = c->po.innov_host + 12 * c->po.innov_host_m * (size_t) k;
         memcpy(h, P.zf, sizeof(float) * 2 * M);
         if (P.idf) memcpy(h + sizeof(float) * 2 * M, P.idf, sizeof(int32_t) * M);
         HIP_TRY(hipMemcpyAsync(V.zf.at(c->po.msum), h, P.idf ? 12 * M : 8 * M, hipMemcpyHostToDevice, c->stream));  // (zf | idf: adjacent in both places)
-        HIP_TRY(hipEventRecord(c->po.innov_ev[k], c->stream));
-        c->po.innov_ev_used[k] = true;
+        if (int rc = c->po.innov_slots.record(k, c->stream)) return rc;
         z_dev = V.zf.at(c->po.msum);
     }
     const int32_t *lab_dev = P.lab_dev;
@@ -410,7 +374,7 @@ int innov_append(slamgpu_ctx *c, const float *zf, const int32_t *idf, int32_t m,
 // the per-particle step's record (do_update_particle, beside its pp_missed): the nz observations in pp_z_dev against the labels in
 // pp_lab_dev, the set and the records as they stand before the update; nf: the slots before the step.  pp_check has seen to the
 // ring's capacity; innov_labels_room, which the entry points call right after pp_check, to the staging area
-int innov_labels_room(slamgpu_ctx *c, int32_t nz) { return c->po.msum.reserve(innov_layout(c, nz, 0).L.total()); }
+int innov_labels_room(slamgpu_ctx *c, int32_t nz) { return c->po.msum.reserve(innov_layout(c, nz, 0).L.total(), kSummaryStaging); }
 int innov_append_labels(slamgpu_ctx *c, int32_t nz, int32_t nf, const float *R) {
     InnovPacket P;
     P.z_dev = c->as.pp_z_dev, P.lab_dev = c->as.pp_lab_dev, P.lstride = c->B.ncap, P.nf = nf;
@@ -421,21 +385,14 @@ int innov_append_labels(slamgpu_ctx *c, int32_t nz, int32_t nf, const float *R) 
 }
 
 void posterior_release(slamgpu_ctx *c) {
-    c->po.msum.release();
-    if (c->po.pose_ring_dev) (void) hipFree(c->po.pose_ring_dev);
-    if (c->po.pose_dev) (void) hipFree(c->po.pose_dev);
-    if (c->po.innov_ring_dev) (void) hipFree(c->po.innov_ring_dev);
-    if (c->po.innov_tag_dev) (void) hipFree(c->po.innov_tag_dev);
-    if (c->po.innov_host) (void) hipHostFree(c->po.innov_host);
-    for (hipEvent_t e : c->po.innov_ev)
-        if (e) (void) hipEventDestroy(e);
-    if (c->po.innov_lab_host) (void) hipHostFree(c->po.innov_lab_host);
-    for (hipEvent_t e : c->po.innov_lab_ev)
-        if (e) (void) hipEventDestroy(e);
-    if (c->po.path_rec_dev) (void) hipFree(c->po.path_rec_dev);
-    for (int b = 0; b < 2; b++)
-        if (c->po.path_origin_dev[b]) (void) hipFree(c->po.path_origin_dev[b]);
-    c->po.path_arena.release();
+    Posterior &o = c->po;
+    o.msum.release();
+    o.pose_ring_dev.release(), o.pose_dev.release();
+    o.innov_ring_dev.release(), o.innov_tag_dev.release();
+    o.innov_host.release(), o.innov_slots.release();
+    o.innov_lab_host.release(), o.innov_lab_slots.release();
+    o.path_rec_dev.release(), o.path_origin_dev[0].release(), o.path_origin_dev[1].release();
+    o.path_arena.release();
 }
 
 #pragma GCC visibility pop
@@ -457,7 +414,7 @@ int slamgpu_map_summary(slamgpu_ctx *c, int32_t first_slot, int32_t count, doubl
     Layout L;
     const auto out_d = L.take<double>(kMapStride * M), wpart = L.take<double>(2 * (size_t) tiles), part = L.take<double>(kMapFields * (size_t) tiles * chunk);
     const auto hold = L.take<int32_t>(M);
-    if (int rc = c->po.msum.reserve(L.total())) return rc;
+    if (int rc = c->po.msum.reserve(L.total(), kSummaryStaging)) return rc;
     c->B.slot = c->slot;
     for (int at = 0; at < count; at += chunk) {
         MapSummaryArgs A{};
@@ -495,7 +452,7 @@ int slamgpu_map_pairs(slamgpu_ctx *c, const int32_t *pairs, int32_t count, doubl
     Layout L;
     const auto out_d = L.take<double>(kMapStride * M), wpart = L.take<double>(2 * (size_t) tiles), part = L.take<double>(kMapFields * (size_t) tiles * chunk);
     const auto both_d = L.take<int32_t>(M), pairs_d = L.take<int32_t>(2 * M);
-    if (int rc = c->po.msum.reserve(L.total())) return rc;
+    if (int rc = c->po.msum.reserve(L.total(), kSummaryStaging)) return rc;
     HIP_TRY(hipMemcpyAsync(pairs_d.at(c->po.msum), pairs, sizeof(int32_t) * 2 * M, hipMemcpyHostToDevice, c->stream));
     c->B.slot = c->slot;
     for (int at = 0; at < count; at += chunk) {
@@ -539,7 +496,7 @@ int slamgpu_joint_summary(slamgpu_ctx *c, const int32_t *slots, int32_t k, doubl
                pvf = L.take<double>(nq * T), part = L.take<double>(256 * T * chunk);
     const auto tile_info = L.take<int32_t>(2 * T), info = L.take<int32_t>(4), slots_d = L.take<int32_t>((size_t) k);
     const auto hold = L.take<uint8_t>(up16((size_t) c->B.n), 16);
-    if (int rc = c->po.msum.reserve(L.total())) return rc;
+    if (int rc = c->po.msum.reserve(L.total(), kSummaryStaging)) return rc;
     if (k > 0) HIP_TRY(hipMemcpyAsync(slots_d.at(c->po.msum), slots, sizeof(int32_t) * (size_t) k, hipMemcpyHostToDevice, c->stream));
     c->B.slot = c->slot;
     JointArgs J{};
@@ -597,22 +554,11 @@ int slamgpu_pose_history_enable(slamgpu_ctx *c, int32_t capacity) {
     if (int rc = summary_enter(c, "slamgpu_pose_history_enable", kCtx | kSingle)) return rc;
     if (capacity < 0) return fail(SLAMGPU_ERR_INVALID, "slamgpu_pose_history_enable: capacity %d", capacity);
     HIP_TRY(hipSetDevice(c->cfg.device));
-    // the new ring first: a refused call leaves the setting as it was
-    double *ring = nullptr;
-    if (capacity > 0) {
+    if (capacity > 0)
         if (int rc = pose_reserve(c)) return rc;
-        const size_t bytes = sizeof(double) * kPoseStride * (size_t) capacity;
-        hipError_t e = hipMalloc((void **) &ring, bytes);
-        if (e != hipSuccess) {
-            (void) hipGetLastError();
-            return fail(SLAMGPU_ERR_ALLOC, "slamgpu_pose_history_enable: %d entries (%zu bytes): %s", capacity, bytes, hipGetErrorString(e));
-        }
-    }
-    if (c->po.pose_ring_dev) {
-        HIP_TRY(hipStreamSynchronize(c->stream));  // (launches in flight may still write the old ring)
-        (void) hipFree(c->po.pose_ring_dev);
-    }
-    c->po.pose_ring_dev = ring;
+    if (int rc = ring_replace(c, "slamgpu_pose_history_enable", capacity, c->po.pose_ring_dev != nullptr,
+                              Fresh<double>{c->po.pose_ring_dev, kPoseStride * (size_t) capacity, "pose ring"}))
+        return rc;
     c->po.pose.reset(capacity);
     return 0;
 }
@@ -678,28 +624,10 @@ int slamgpu_innovation_history_enable(slamgpu_ctx *c, int32_t capacity) {
     if (int rc = summary_enter(c, "slamgpu_innovation_history_enable", kCtx | kSingle)) return rc;
     if (capacity < 0) return fail(SLAMGPU_ERR_INVALID, "slamgpu_innovation_history_enable: capacity %d", capacity);
     HIP_TRY(hipSetDevice(c->cfg.device));
-    // the new ring first: a refused call leaves the setting as it was
-    double *ring = nullptr;
-    int32_t *tag = nullptr;
-    if (capacity > 0) {
-        const size_t bytes = sizeof(double) * kInnStride * (size_t) capacity;
-        hipError_t e = hipMalloc((void **) &ring, bytes);
-        if (e == hipSuccess) {
-            e = hipMalloc((void **) &tag, sizeof(int32_t) * 2 * (size_t) capacity);
-            if (e != hipSuccess) (void) hipFree(ring);
-        }
-        if (e != hipSuccess) {
-            (void) hipGetLastError();
-            return fail(SLAMGPU_ERR_ALLOC, "slamgpu_innovation_history_enable: %d entries (%zu bytes): %s", capacity, bytes, hipGetErrorString(e));
-        }
-    }
-    if (c->po.innov_ring_dev) {
-        HIP_TRY(hipStreamSynchronize(c->stream));  // (launches in flight may still write the old ring)
-        (void) hipFree(c->po.innov_ring_dev);
-        (void) hipFree(c->po.innov_tag_dev);
-    }
-    c->po.innov_ring_dev = ring;
-    c->po.innov_tag_dev = tag;
+    if (int rc = ring_replace(c, "slamgpu_innovation_history_enable", capacity, c->po.innov_ring_dev != nullptr,
+                              Fresh<double>{c->po.innov_ring_dev, kInnStride * (size_t) capacity, "innovation ring"},
+                              Fresh<int32_t>{c->po.innov_tag_dev, 2 * (size_t) capacity, "innovation ring: tags"}))
+        return rc;
     c->po.innov.reset(capacity);
     c->po.innov_records = 0;
     return 0;
@@ -740,31 +668,12 @@ int slamgpu_path_enable(slamgpu_ctx *c, int32_t capacity) {
     if (int rc = summary_enter(c, "slamgpu_path_enable", kCtx | kSingle)) return rc;
     if (capacity < 0) return fail(SLAMGPU_ERR_INVALID, "slamgpu_path_enable: capacity %d", capacity);
     HIP_TRY(hipSetDevice(c->cfg.device));
-    // the new ring first: a refused call leaves the recording as it was
-    float4 *rec = nullptr;
-    int32_t *org[2] = {nullptr, nullptr};
-    if (capacity > 0) {
-        const size_t S = (size_t) c->B.ncap, bytes = sizeof(float4) * S * (size_t) capacity;
-        hipError_t e = hipMalloc((void **) &rec, bytes);
-        for (int b = 0; b < 2 && e == hipSuccess; b++) e = hipMalloc((void **) &org[b], sizeof(int32_t) * S);
-        if (e != hipSuccess) {
-            (void) hipGetLastError();
-            if (rec) (void) hipFree(rec);
-            for (int b = 0; b < 2; b++)
-                if (org[b]) (void) hipFree(org[b]);
-            return fail(SLAMGPU_ERR_ALLOC, "slamgpu_path_enable: %d records of %d particles (%zu bytes): %s", capacity, c->B.n, bytes, hipGetErrorString(e));
-        }
-    }
-    if (c->po.path.cap > 0 || c->po.path_arena.p) {
-        HIP_TRY(hipStreamSynchronize(c->stream));  // (launches in flight may still use the old ring)
-        if (c->po.path_rec_dev) (void) hipFree(c->po.path_rec_dev);
-        for (int b = 0; b < 2; b++)
-            if (c->po.path_origin_dev[b]) (void) hipFree(c->po.path_origin_dev[b]);
-        c->po.path_arena.release();
-    }
-    c->po.path_rec_dev = rec;
-    c->po.path_origin_dev[0] = org[0];
-    c->po.path_origin_dev[1] = org[1];
+    const size_t S = capacity > 0 ? (size_t) c->B.ncap : 0;  // (the traces' staging goes with the old ring: no new one)
+    if (int rc = ring_replace(c, "slamgpu_path_enable", capacity, c->po.path.cap > 0 || c->po.path_arena.p,
+                              Fresh<float4>{c->po.path_rec_dev, S * (size_t) capacity, "path records"},
+                              Fresh<int32_t>{c->po.path_origin_dev[0], S, "path origins"}, Fresh<int32_t>{c->po.path_origin_dev[1], S, "path origins"},
+                              Fresh<char>{c->po.path_arena, 0, ""}))
+        return rc;
     c->po.path_org = 0;
     c->po.path.reset(capacity);
     if (capacity > 0) {
@@ -815,7 +724,7 @@ int slamgpu_path_trace(slamgpu_ctx *c, int32_t particle, int64_t first, int32_t 
     Layout L;
     const auto xyt_d = L.take<float>(3 * M);
     const auto index_d = L.take<int32_t>(M, 16);
-    if (int rc = c->po.path_arena.reserve(L.total())) return rc;
+    if (int rc = c->po.path_arena.reserve(L.total(), "path summaries: staging")) return rc;
     PathTraceArgs A{};
     A.particle = particle;
     A.newest = c->po.path.next - 1;
@@ -849,7 +758,7 @@ int slamgpu_path_summary(slamgpu_ctx *c, int64_t first, int32_t count, double *o
     const auto part = L.take<double>(kPathFields * (size_t) tiles * chunk);
     const auto C = L.take<uint32_t>(2 * S);
     const auto distinct_d = L.take<int32_t>(M);
-    if (int rc = c->po.path_arena.reserve(L.total())) return rc;
+    if (int rc = c->po.path_arena.reserve(L.total(), "path summaries: staging")) return rc;
     PathWalkArgs A{};
     A.tiles = tiles;
     A.logw = c->cfg.log_weights;

@@ -52,11 +52,11 @@ int pin_grow(void **p, size_t *cap, size_t n, size_t elem, const char *what) {
     return 0;
 }
 
-int pkt_take_slot(slamgpu_ctx *c) { return (int) (c->pkt_seq++ % kRing); }
+int pkt_take_slot(slamgpu_ctx *c) { return c->pkt_slots.take(); }
 
 int BigPacket::begin(slamgpu_ctx *c, int32_t m, int32_t n, int32_t nf, int32_t n_rows, int32_t e_new) {
     slot = pkt_take_slot(c);
-    if (c->pkt_ev_used[slot]) HIP_TRY(hipEventSynchronize(c->pkt_ev[slot]));
+    if (int rc = c->pkt_slots.wait(slot)) return rc;
     host = reinterpret_cast<ObsPacket *>(c->pkt_host + (size_t) slot * c->pkt_bytes);
     dev = c->pkt_dev + (size_t) slot * c->pkt_bytes;
     *host = ObsPacket{m, n, nf, n_rows, e_new, 0, 0 /* dense layout */, 0};
@@ -65,9 +65,7 @@ int BigPacket::begin(slamgpu_ctx *c, int32_t m, int32_t n, int32_t nf, int32_t n
 
 int BigPacket::commit(slamgpu_ctx *c, size_t used) {
     HIP_TRY(hipMemcpyAsync(dev, host, used, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipEventRecord(c->pkt_ev[slot], c->stream));
-    c->pkt_ev_used[slot] = true;
-    return 0;
+    return c->pkt_slots.record(slot, c->stream);
 }
 
 hipEvent_t get_event(slamgpu_ctx *c) {
@@ -379,6 +377,108 @@ int read_ctrl(slamgpu_ctx *c, bool need_set) {
     return persist_check(c);
 }
 
+namespace {
+
+// slamgpu_create's allocations (sizes in c->B, c->ws.nblocks, c->pkt_bytes), and the kernels' views of them
+int core_reserve(slamgpu_ctx *c, bool want_stamps) {
+    if (c->own_stream) HIP_TRY(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
+    CoreBufs &o = c->own;
+    const size_t S = (size_t) c->B.ncap, cap_nf = (size_t) c->B.cap_nf, nb = (size_t) c->ws.nblocks, ng = (size_t) n_global(c);
+    if (int rc = c->mg.plan_host.reserve(1, "shard plan mirror")) return rc;
+    if (int rc = c->mg.plan_seq_host.reserve(1, "shard plan sequence word")) return rc;
+    for (int b = 0; b < 2; b++) {
+        if (int rc = o.poseA[b].reserve(S, "pose records A")) return rc;
+        if (int rc = o.poseB[b].reserve(S, "pose records B")) return rc;
+        if (int rc = o.poseC[b].reserve(S, "pose records C")) return rc;
+        if (int rc = o.lmkA[b].reserve(S * cap_nf, "landmark records A")) return rc;
+        if (int rc = o.lmkB[b].reserve(S * cap_nf, "landmark records B")) return rc;
+        // genealogy rows: plain [cap_rows][S], or compact [ceil(cap_rows / 4)][S][4] (kernels.h: Buffers::gen)
+        if (int rc = o.gen[b].reserve(S * ((cap_nf + 1 + 3) / 4 * 4), "genealogy rows")) return rc;
+    }
+    if (int rc = c->live_dev.reserve(cap_nf, "live flags")) return rc;
+    if (int rc = c->erow_dev.reserve(cap_nf, "landmark rows")) return rc;
+    if (int rc = c->rows_dev.reserve((size_t) c->B.cap_rows, "live rows")) return rc;
+    if (int rc = o.ctrl.reserve(1, "Ctrl")) return rc;
+    if (int rc = c->ctrl_host.reserve(1, "Ctrl mirror")) return rc;
+    for (int b = 0; b < 2; b++) {
+        if (int rc = o.lcum[b].reserve(S, "weight prefixes")) return rc;
+        if (int rc = o.blk_w[b].reserve(3 * nb, "block totals")) return rc;  // [w | w2 (| max log-weight)] contiguous
+        if (int rc = o.est_part[b].reserve(4 * nb + 2, "estimate partials")) return rc;  // + Neff, resampled
+        if (int rc = o.scan[b].reserve(nb + 4, "block scan")) return rc;
+        if (int rc = o.keep[b].reserve(S, "ancestors")) return rc;
+    }
+    if (int rc = c->hist_dev.reserve(kHistStride * (size_t) kHistCap, "estimate history")) return rc;
+    if (int rc = c->hist_host.reserve(kHistStride * (size_t) kHistCap, "estimate history mirror")) return rc;
+    if (want_stamps)
+        if (int rc = c->stamps_dev.reserve(kStampSlots * nb, "stamps")) return rc;
+    if (int rc = c->pkt_host.reserve(c->pkt_bytes * kRing, "big-packet ring (host)")) return rc;
+    if (int rc = c->pkt_dev.reserve(c->pkt_bytes * kRing, "big-packet ring")) return rc;
+    if (int rc = c->pkt_slots.create()) return rc;
+    if (c->cfg.rng_mode == SLAMGPU_RNG_TAPE) {
+        if (int rc = c->tape_host.reserve(3 * S + ng, "tape staging")) return rc;
+        if (int rc = c->normals_dev.reserve(3 * S, "tape normals")) return rc;
+        for (int b = 0; b < 2; b++)
+            if (int rc = c->strata_dev[b].reserve(ng, "tape strata")) return rc;
+    }
+    for (int b = 0; b < 2; b++) {
+        c->B.poseA[b] = o.poseA[b], c->B.poseB[b] = o.poseB[b], c->B.poseC[b] = o.poseC[b];
+        c->B.lmkA[b] = o.lmkA[b], c->B.lmkB[b] = o.lmkB[b], c->B.gen[b] = o.gen[b];
+        c->ws.lcum[b] = o.lcum[b], c->ws.blk_w[b] = o.blk_w[b], c->ws.est_part[b] = o.est_part[b];
+        c->ws.scan[b] = o.scan[b], c->ws.keep[b] = o.keep[b];
+    }
+    c->B.ctrl = o.ctrl;
+    return 0;
+}
+
+// ... and what slamgpu_create enqueues on them: the zeros (the genealogy rows get none), Ctrl, the initial particle set -- Particle()
+// then w = 1/N (ParticleSLAMWrapper.cpp:14-25) -- and genealogy row 0; waited for
+int core_start(slamgpu_ctx *c) {
+    const size_t S = (size_t) c->B.ncap, cap_nf = (size_t) c->B.cap_nf;
+    *c->mg.plan_seq_host = 0;
+    for (int b = 0; b < 2; b++) {
+        HIP_TRY(hipMemsetAsync(c->B.poseA[b], 0, sizeof(float4) * S, c->stream));
+        HIP_TRY(hipMemsetAsync(c->B.poseB[b], 0, sizeof(float4) * S, c->stream));
+        HIP_TRY(hipMemsetAsync(c->B.poseC[b], 0, sizeof(float2) * S, c->stream));
+        HIP_TRY(hipMemsetAsync(c->B.lmkA[b], 0, sizeof(float4) * S * cap_nf, c->stream));
+        HIP_TRY(hipMemsetAsync(c->B.lmkB[b], 0, sizeof(float) * S * cap_nf, c->stream));
+    }
+    memset(c->ctrl_host, 0, sizeof(Ctrl));
+    c->ctrl_host->inv_n = 1.0f / (float) n_global(c);  // core.cpp:745
+    if (c->cfg.log_weights) c->ctrl_host->inv_n = logf(c->ctrl_host->inv_n);
+    HIP_TRY(hipMemcpyAsync(c->B.ctrl, c->ctrl_host, sizeof(Ctrl), hipMemcpyHostToDevice, c->stream));
+    for (int b = 0; b < 2; b++) HIP_TRY(hipMemsetAsync(c->ws.keep[b], 0, sizeof(int32_t) * S, c->stream));
+    if (c->stamps_dev) HIP_TRY(hipMemsetAsync(c->stamps_dev, 0, sizeof(unsigned long long) * c->stamps_dev.cap, c->stream));
+    std::vector<float4> a(S, make_float4(0.f, 0.f, 0.f, 0.f));
+    const float uw = c->cfg.log_weights ? c->ctrl_host->inv_n : (float) (1.0 / (float) n_global(c));
+    for (int i = 0; i < c->B.n; i++) a[i].w = uw;
+    HIP_TRY(hipMemcpyAsync(c->B.poseA[0], a.data(), sizeof(float4) * S, hipMemcpyHostToDevice, c->stream));
+    // one launch out of the library's code object, so that the runtime loads it HERE and not inside the caller's first step
+    // (the first launch of a process pays for the module: ~10 ms, seven microseconds per observation step of a whole
+    // example_webmap run of the drop-in binary, round 5): genealogy row 0 = "own slot", which is what it means before any landmark
+    c->k->identity(c->stream, c->B, 0, 0);
+    c->k->identity(c->stream, c->B, 1, 0);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+// slamgpu_destroy's share of the core: every buffer core_reserve made (but the multi-GPU layer's two), and slamgpu_peek's staging
+void core_release(slamgpu_ctx *c) {
+    CoreBufs &o = c->own;
+    for (int b = 0; b < 2; b++) {
+        o.poseA[b].release(), o.poseB[b].release(), o.poseC[b].release(), o.lmkA[b].release(), o.lmkB[b].release(), o.gen[b].release();
+        o.lcum[b].release(), o.blk_w[b].release(), o.est_part[b].release(), o.scan[b].release(), o.keep[b].release();
+        c->strata_dev[b].release();
+    }
+    o.ctrl.release();
+    c->live_dev.release(), c->erow_dev.release(), c->rows_dev.release();
+    c->ctrl_host.release(), c->hist_dev.release(), c->hist_host.release(), c->stamps_dev.release(), c->peek_dev.release();
+    c->pkt_host.release(), c->pkt_dev.release(), c->pkt_slots.release();
+    c->tape_host.release(), c->normals_dev.release();
+}
+
+}  // namespace
+
 extern "C" {
 
 const char *slamgpu_last_error(void) { return g_err; }
@@ -429,44 +529,10 @@ int slamgpu_create(const slamgpu_config *cfg, slamgpu_ctx **out) {
     c->counted_ok = getenv("SLAMGPU_NO_COUNTED") == nullptr;                               // diagnostic / tests: kernels.h: update_counted
     if (const char *e = getenv("SLAMGPU_CONSOLIDATE_ABOVE")) c->consolidate_above = atoi(e);
     if (const char *e = getenv("SLAMGPU_PLAIN_ROWS_TARGET")) c->plain_rows_target = atoi(e);
-    const bool want_stamps = getenv("SLAMGPU_STAMPS") != nullptr;                         // diagnostic
     const int cap_nf = cfg->max_landmarks > 0 ? cfg->max_landmarks : 1;
     c->B.n = n;
     c->B.ncap = ncap;
     c->B.cap_nf = cap_nf;
-#define CTX_TRY(expr)                                                                                  \
-    do {                                                                                               \
-        hipError_t e_ = (expr);                                                                        \
-        if (e_ != hipSuccess) {                                                                        \
-            int rc_ = fail(e_ == hipErrorOutOfMemory ? SLAMGPU_ERR_ALLOC : SLAMGPU_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
-            slamgpu_destroy(c);                                                                        \
-            return rc_;                                                                                \
-        }                                                                                              \
-    } while (0)
-    if (cfg->external_stream) {
-        c->stream = reinterpret_cast<hipStream_t>(cfg->external_stream);
-        c->own_stream = false;
-    } else {
-        CTX_TRY(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
-    }
-    CTX_TRY(hipHostMalloc((void **) &c->mg.plan_host, sizeof(ShardPlan), hipHostMallocDefault));
-    CTX_TRY(hipHostMalloc((void **) &c->mg.plan_seq_host, sizeof(uint32_t), hipHostMallocDefault));
-    *c->mg.plan_seq_host = 0;
-    const size_t S = (size_t) ncap;
-    for (int b = 0; b < 2; b++) {
-        CTX_TRY(hipMalloc((void **) &c->B.poseA[b], sizeof(float4) * S));
-        CTX_TRY(hipMalloc((void **) &c->B.poseB[b], sizeof(float4) * S));
-        CTX_TRY(hipMalloc((void **) &c->B.poseC[b], sizeof(float2) * S));
-        CTX_TRY(hipMalloc((void **) &c->B.lmkA[b], sizeof(float4) * S * cap_nf));
-        CTX_TRY(hipMalloc((void **) &c->B.lmkB[b], sizeof(float) * S * cap_nf));
-        CTX_TRY(hipMemsetAsync(c->B.poseA[b], 0, sizeof(float4) * S, c->stream));
-        CTX_TRY(hipMemsetAsync(c->B.poseB[b], 0, sizeof(float4) * S, c->stream));
-        CTX_TRY(hipMemsetAsync(c->B.poseC[b], 0, sizeof(float2) * S, c->stream));
-        CTX_TRY(hipMemsetAsync(c->B.lmkA[b], 0, sizeof(float4) * S * cap_nf, c->stream));
-        CTX_TRY(hipMemsetAsync(c->B.lmkB[b], 0, sizeof(float) * S * cap_nf, c->stream));
-        // genealogy rows: plain [cap_rows][S], or compact [ceil(cap_rows / 4)][S][4] (kernels.h: Buffers::gen)
-        CTX_TRY(hipMalloc((void **) &c->B.gen[b], sizeof(int32_t) * S * (size_t) ((cap_nf + 1 + 3) / 4 * 4)));
-    }
     c->B.slot = 0;
     c->B.cap_rows = cap_nf + 1;  // at most one row per landmark, plus the one a step opens while the old ones are still read
     c->B.compact = c->B.cap_rows <= kSmallRows ? 1 : 0;
@@ -483,66 +549,26 @@ int slamgpu_create(const slamgpu_config *cfg, slamgpu_ctx **out) {
         c->B.cap_rows = cap_nf + 1;
         c->mid_compact = false;
     }
+    c->ws.nblocks = ncap / kBlock;
+    // big-packet ring: header + idf[cap] + zf[2cap] + zn[2cap]
+    c->pkt_bytes = ((sizeof(ObsPacket) + sizeof(int32_t) * cap_nf + sizeof(float) * 4 * cap_nf + sizeof(int32_t) * (2 * (size_t) cap_nf + 1)) + 255) / 256 * 256;
     c->erow.assign((size_t) cap_nf, 0);
     c->live_flag.assign((size_t) cap_nf, 0);
     c->seen_step.assign((size_t) cap_nf, 0);
     c->as.box_dirty.assign((size_t) cap_nf, 1);
-    CTX_TRY(hipMalloc((void **) &c->live_dev, sizeof(int32_t) * (size_t) cap_nf));
     c->refcnt.assign((size_t) c->B.cap_rows, 0);
     c->live_pos.assign((size_t) c->B.cap_rows, -1);
     rows_reset(c, 0);
-    CTX_TRY(hipMalloc((void **) &c->erow_dev, sizeof(int32_t) * (size_t) cap_nf));
-    CTX_TRY(hipMalloc((void **) &c->rows_dev, sizeof(int32_t) * (size_t) c->B.cap_rows));
-    CTX_TRY(hipMalloc((void **) &c->B.ctrl, sizeof(Ctrl)));
-    CTX_TRY(hipHostMalloc((void **) &c->ctrl_host, sizeof(Ctrl), hipHostMallocDefault));
-    memset(c->ctrl_host, 0, sizeof(Ctrl));
-    c->ctrl_host->inv_n = 1.0f / (float) n_global(c);  // core.cpp:745
-    if (cfg->log_weights) c->ctrl_host->inv_n = logf(c->ctrl_host->inv_n);
-    CTX_TRY(hipMemcpyAsync(c->B.ctrl, c->ctrl_host, sizeof(Ctrl), hipMemcpyHostToDevice, c->stream));
-    // weight scratch
-    c->ws.nblocks = ncap / kBlock;
-    for (int b = 0; b < 2; b++) {
-        CTX_TRY(hipMalloc((void **) &c->ws.lcum[b], sizeof(float) * S));
-        CTX_TRY(hipMalloc((void **) &c->ws.blk_w[b], sizeof(float) * 3 * (size_t) c->ws.nblocks));  // [w | w2 (| max log-weight)] contiguous
-        CTX_TRY(hipMalloc((void **) &c->ws.est_part[b], sizeof(double) * (4 * (size_t) c->ws.nblocks + 2)));  // + Neff, resampled
-        CTX_TRY(hipMalloc((void **) &c->ws.scan[b], sizeof(double) * ((size_t) c->ws.nblocks + 4)));
+    if (cfg->external_stream) {
+        c->stream = reinterpret_cast<hipStream_t>(cfg->external_stream);
+        c->own_stream = false;
     }
-    for (int b = 0; b < 2; b++) {
-        CTX_TRY(hipMalloc((void **) &c->ws.keep[b], sizeof(int32_t) * S));
-        CTX_TRY(hipMemsetAsync(c->ws.keep[b], 0, sizeof(int32_t) * S, c->stream));
+    int rc = core_reserve(c, getenv("SLAMGPU_STAMPS") != nullptr /* diagnostic */);
+    if (!rc) rc = core_start(c);
+    if (rc) {
+        slamgpu_destroy(c);
+        return rc;
     }
-    CTX_TRY(hipMalloc((void **) &c->hist_dev, sizeof(double) * kHistStride * (size_t) kHistCap));
-    CTX_TRY(hipHostMalloc((void **) &c->hist_host, sizeof(double) * kHistStride * (size_t) kHistCap, hipHostMallocDefault));
-    if (want_stamps) {
-        CTX_TRY(hipMalloc((void **) &c->stamps_dev, sizeof(unsigned long long) * kStampSlots * (size_t) c->ws.nblocks));
-        CTX_TRY(hipMemsetAsync(c->stamps_dev, 0, sizeof(unsigned long long) * kStampSlots * (size_t) c->ws.nblocks, c->stream));
-    }
-    // big-packet ring: header + idf[cap] + zf[2cap] + zn[2cap]
-    c->pkt_bytes = ((sizeof(ObsPacket) + sizeof(int32_t) * cap_nf + sizeof(float) * 4 * cap_nf + sizeof(int32_t) * (2 * (size_t) cap_nf + 1)) + 255) / 256 * 256;
-    CTX_TRY(hipHostMalloc((void **) &c->pkt_host, c->pkt_bytes * kRing, hipHostMallocDefault));
-    CTX_TRY(hipMalloc((void **) &c->pkt_dev, c->pkt_bytes * kRing));
-    for (int i = 0; i < kRing; i++) CTX_TRY(hipEventCreateWithFlags(&c->pkt_ev[i], hipEventDisableTiming));
-    if (cfg->rng_mode == SLAMGPU_RNG_TAPE) {
-        const size_t tape_floats = 3 * S + (size_t) n_global(c);
-        CTX_TRY(hipHostMalloc((void **) &c->tape_host, sizeof(float) * tape_floats, hipHostMallocDefault));
-        CTX_TRY(hipMalloc((void **) &c->normals_dev, sizeof(float) * 3 * S));
-        for (int b = 0; b < 2; b++) CTX_TRY(hipMalloc((void **) &c->strata_dev[b], sizeof(float) * (size_t) n_global(c)));
-    }
-    // initial particle set: Particle() then w = 1/N (ParticleSLAMWrapper.cpp:14-25)
-    {
-        std::vector<float4> a(S, make_float4(0.f, 0.f, 0.f, 0.f));
-        const float uw = cfg->log_weights ? c->ctrl_host->inv_n : (float) (1.0 / (float) n_global(c));
-        for (int i = 0; i < n; i++) a[i].w = uw;
-        CTX_TRY(hipMemcpyAsync(c->B.poseA[0], a.data(), sizeof(float4) * S, hipMemcpyHostToDevice, c->stream));
-        // one launch out of the library's code object, so that the runtime loads it HERE and not inside the caller's first step
-        // (the first launch of a process pays for the module: ~10 ms, seven microseconds per observation step of a whole
-        // example_webmap run of the drop-in binary, round 5): genealogy row 0 = "own slot", which is what it means before any landmark
-        c->k->identity(c->stream, c->B, 0, 0);
-        c->k->identity(c->stream, c->B, 1, 0);
-        CTX_TRY(hipGetLastError());
-        CTX_TRY(hipStreamSynchronize(c->stream));
-    }
-#undef CTX_TRY
     *out = c;
     return 0;
 }
@@ -553,46 +579,13 @@ void slamgpu_destroy(slamgpu_ctx *c) {
     if (c->stream) (void) hipStreamSynchronize(c->stream);
     drain_stats(c);
     for (auto e : c->ev_pool) (void) hipEventDestroy(e);
-    for (int b = 0; b < 2; b++) {
-        if (c->B.poseA[b]) (void) hipFree(c->B.poseA[b]);
-        if (c->B.poseB[b]) (void) hipFree(c->B.poseB[b]);
-        if (c->B.poseC[b]) (void) hipFree(c->B.poseC[b]);
-        if (c->B.lmkA[b]) (void) hipFree(c->B.lmkA[b]);
-        if (c->B.lmkB[b]) (void) hipFree(c->B.lmkB[b]);
-        if (c->B.gen[b]) (void) hipFree(c->B.gen[b]);
-    }
-    if (c->B.ctrl) (void) hipFree(c->B.ctrl);
-    if (c->ctrl_host) (void) hipHostFree(c->ctrl_host);
-    if (c->hist_dev) (void) hipFree(c->hist_dev);
-    if (c->hist_host) (void) hipHostFree(c->hist_host);
-    if (c->stamps_dev) (void) hipFree(c->stamps_dev);
-    if (c->peek_dev) (void) hipFree(c->peek_dev);
+    if (c->timer_a) (void) hipEventDestroy(c->timer_a);
+    if (c->timer_b) (void) hipEventDestroy(c->timer_b);
     posterior_release(c);
     association_release(c);
     observe_release(c);
     multigpu_release(c);
-    // (the weight scratch after it: ws.blk_w[0] is the context's own again, not a caller's totals buffer)
-    for (int b = 0; b < 2; b++) {
-        if (c->ws.lcum[b]) (void) hipFree(c->ws.lcum[b]);
-        if (c->ws.blk_w[b]) (void) hipFree(c->ws.blk_w[b]);
-        if (c->ws.est_part[b]) (void) hipFree(c->ws.est_part[b]);
-        if (c->ws.scan[b]) (void) hipFree(c->ws.scan[b]);
-    }
-    for (int b = 0; b < 2; b++)
-        if (c->ws.keep[b]) (void) hipFree(c->ws.keep[b]);
-    if (c->erow_dev) (void) hipFree(c->erow_dev);
-    if (c->live_dev) (void) hipFree(c->live_dev);
-    if (c->rows_dev) (void) hipFree(c->rows_dev);
-    if (c->pkt_host) (void) hipHostFree(c->pkt_host);
-    if (c->pkt_dev) (void) hipFree(c->pkt_dev);
-    for (int i = 0; i < kRing; i++)
-        if (c->pkt_ev[i]) (void) hipEventDestroy(c->pkt_ev[i]);
-    if (c->timer_a) (void) hipEventDestroy(c->timer_a);
-    if (c->timer_b) (void) hipEventDestroy(c->timer_b);
-    if (c->tape_host) (void) hipHostFree(c->tape_host);
-    if (c->normals_dev) (void) hipFree(c->normals_dev);
-    for (int b = 0; b < 2; b++)
-        if (c->strata_dev[b]) (void) hipFree(c->strata_dev[b]);
+    core_release(c);
     if (c->stream && c->own_stream) (void) hipStreamDestroy(c->stream);
     delete c;
 }
@@ -797,8 +790,8 @@ int demote_to_plain(slamgpu_ctx *c) {
     if (int rc = materialize(c)) return rc;  // (no pending gather: the set is plain in the live buffers)
     HIP_TRY(hipSetDevice(c->cfg.device));
     const size_t S = (size_t) c->B.ncap, words = S * (size_t) kSmallRows;
-    int32_t *tmp = nullptr;
-    HIP_TRY(hipMalloc((void **) &tmp, sizeof(int32_t) * words));
+    DevBuf<int32_t> tmp;
+    if (int rc = tmp.reserve(words, "demotion: genealogy rows")) return rc;
     hipError_t er = hipSuccess;  // (no early return between the allocation and its release: ADVICE r5)
     for (int b = 0; b < 2 && er == hipSuccess; b++) {
         er = hipMemcpyAsync(tmp, c->B.gen[b], sizeof(int32_t) * words, hipMemcpyDeviceToDevice, c->stream);
@@ -807,7 +800,7 @@ int demote_to_plain(slamgpu_ctx *c) {
         er = hipGetLastError();
     }
     const hipError_t er2 = hipStreamSynchronize(c->stream);
-    (void) hipFree(tmp);
+    tmp.release();
     HIP_TRY(er);
     HIP_TRY(er2);
     const int old_rows = c->B.cap_rows, new_rows = c->B.cap_nf + 1;
@@ -818,9 +811,7 @@ int demote_to_plain(slamgpu_ctx *c) {
     c->live_pos.resize((size_t) new_rows, -1);
     for (int r = old_rows; r < new_rows; r++) c->free_rows.push_back(r);
     std::sort(c->free_rows.begin(), c->free_rows.end(), std::greater<int32_t>());  // back() = lowest free row
-    (void) hipFree(c->rows_dev);
-    c->rows_dev = nullptr;
-    HIP_TRY(hipMalloc((void **) &c->rows_dev, sizeof(int32_t) * (size_t) new_rows));
+    if (int rc = c->rows_dev.reserve((size_t) new_rows, "live rows")) return rc;
     c->fresh_row = -1;
     c->tables_dirty = true;
     return 0;
@@ -1311,27 +1302,23 @@ int slamgpu_peek(slamgpu_ctx *c, int32_t first, int32_t stride, int32_t count, f
     if (int rc = sync_tables(c)) return rc;
     const int nf = (xf || Pf4) ? c->nf : 0;
     const size_t M = (size_t) count;
-    // device staging: [oa M][ob M][oc M][la nf M][lb nf M], every part 16-byte aligned
-    const size_t o_a = 0, o_b = o_a + 16 * M, o_c = o_b + 16 * M, o_la = (o_c + 8 * M + 15) & ~(size_t) 15,
-                 o_lb = o_la + 16 * M * nf, total = o_lb + 4 * M * nf + 16;
-    if (total > c->peek_bytes) {
-        if (c->peek_dev) (void) hipFree(c->peek_dev);
-        c->peek_dev = nullptr;
-        c->peek_bytes = 0;
-        hipError_t e = hipMalloc((void **) &c->peek_dev, total);
-        if (e != hipSuccess) return fail(SLAMGPU_ERR_ALLOC, "hipMalloc(%zu): %s", total, hipGetErrorString(e));
-        c->peek_bytes = total;
-    }
+    // device staging: [oa M][ob M][oc M][la nf M][lb nf M], every part 16-byte aligned, and 16 bytes to spare
+    Layout L;
+    const auto oa = L.take<float4>(M), ob = L.take<float4>(M);
+    const auto oc = L.take<float2>(M);
+    const auto la_d = L.take<float4>(M * nf, 16);
+    const auto lb_d = L.take<float>(M * nf);
+    if (int rc = c->peek_dev.reserve(L.total() + 16, "slamgpu_peek: staging")) return rc;
     PeekArgs A{};
     A.first = first;
     A.stride = stride;
     A.count = count;
     A.nf = nf;
-    A.oa = reinterpret_cast<float4 *>(c->peek_dev + o_a);
-    A.ob = reinterpret_cast<float4 *>(c->peek_dev + o_b);
-    A.oc = reinterpret_cast<float2 *>(c->peek_dev + o_c);
-    A.la = reinterpret_cast<float4 *>(c->peek_dev + o_la);
-    A.lb = reinterpret_cast<float *>(c->peek_dev + o_lb);
+    A.oa = oa.at(c->peek_dev);
+    A.ob = ob.at(c->peek_dev);
+    A.oc = oc.at(c->peek_dev);
+    A.la = la_d.at(c->peek_dev);
+    A.lb = lb_d.at(c->peek_dev);
     c->B.slot = c->slot;
     {
         Timed t(c, "peek");

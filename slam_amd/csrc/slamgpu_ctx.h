@@ -56,14 +56,6 @@ struct KernelStat {
     int64_t launches = 0;
 };
 
-// a grow-only staging area in device memory
-struct DevArena {
-    char *p = nullptr;
-    size_t bytes = 0;
-    int reserve(size_t total);  // (a refused growth leaves it empty)
-    void release();
-};
-
 // a typed, grow-only buffer in device memory: cap elements at p.  A refused growth leaves it empty, clears HIP's last error and returns
 // SLAMGPU_ERR_ALLOC with `what` in the text
 int dev_grow(void **p, size_t *cap, size_t n, size_t elem, const char *what, bool zeroed);
@@ -88,12 +80,86 @@ struct PinBuf {
     T *p = nullptr;
     size_t cap = 0;
     operator T *() const { return p; }
+    T *operator->() const { return p; }
     int reserve(size_t n, const char *what) { return n <= cap ? 0 : pin_grow((void **) &p, &cap, n, sizeof(T), what); }
     void release() {
         if (p) (void) hipHostFree(p);
         p = nullptr;
         cap = 0;
     }
+};
+
+// the fields of a staging area, one behind the other: take them in order, reserve total(), then resolve each against the area
+struct Layout {
+    template <class T>
+    struct Field {
+        size_t off;
+        T *at(const DevBuf<char> &a) const { return reinterpret_cast<T *>(a.p + off); }
+    };
+    size_t end = 0;
+    template <class T>
+    Field<T> take(size_t n, size_t align = 1) {
+        end = (end + align - 1) / align * align;
+        const Field<T> f{end};
+        end += sizeof(T) * n;
+        return f;
+    }
+    size_t total() const { return end; }
+};
+
+// K pinned staging slots used in turn, an event per slot: the event says when the device is done with what the slot held (the copy
+// that took it, or the launch that read it), so that the host may write the slot again.  An event is made at its slot's first
+// wait(), or all of them at once by create(), so that no later call pays for one
+template <int K>
+struct SlotRing {
+    hipEvent_t ev[K]{};
+    bool used[K]{};
+    uint64_t seq = 0;
+    int create() {
+        for (int k = 0; k < K; k++)
+            if (!ev[k]) HIP_TRY(hipEventCreateWithFlags(&ev[k], hipEventDisableTiming));
+        return 0;
+    }
+    bool created() const { return ev[K - 1] != nullptr; }  // create() ran to its end
+    int peek() const { return (int) (seq % K); }           // the slot the next take() hands out
+    int take() { return (int) (seq++ % K); }               // (without a wait: wait(k), or a stream's wait for ev[k] where used[k])
+    int wait(int k) {                                      // on the host, for whatever was last recorded on slot k
+        if (!ev[k]) HIP_TRY(hipEventCreateWithFlags(&ev[k], hipEventDisableTiming));
+        if (used[k]) HIP_TRY(hipEventSynchronize(ev[k]));
+        return 0;
+    }
+    int wait_all() {
+        for (int k = 0; k < K; k++)
+            if (used[k]) HIP_TRY(hipEventSynchronize(ev[k]));
+        return 0;
+    }
+    int record(int k, hipStream_t s) {
+        HIP_TRY(hipEventRecord(ev[k], s));
+        used[k] = true;
+        return 0;
+    }
+    void reset() { std::fill(used, used + K, false); }     // nothing in flight reads a slot any more (the caller has seen to that)
+    void release() {
+        for (int k = 0; k < K; k++) {
+            if (ev[k]) (void) hipEventDestroy(ev[k]);
+            ev[k] = nullptr;
+            used[k] = false;
+        }
+    }
+};
+
+// The owners of what the kernels reach through Buffers and WeightScratch: slamgpu_ctx::own.  slamgpu_ctx::B and ::ws are views of
+// it, filled once by slamgpu_create (ws.blk_w[0] may point at a caller's buffer instead: slamgpu_shard_set_totals_buffer).
+// core_release frees it, with the core's other buffers
+struct CoreBufs {
+    DevBuf<float4> poseA[2], poseB[2], lmkA[2];
+    DevBuf<float2> poseC[2];
+    DevBuf<float> lmkB[2];
+    DevBuf<int32_t> gen[2];
+    DevBuf<Ctrl> ctrl;
+    DevBuf<float> lcum[2], blk_w[2];
+    DevBuf<double> est_part[2], scan[2];
+    DevBuf<int32_t> keep[2];
 };
 
 // The state of the association layer (association.cpp): slamgpu_ctx::as.  association_release frees it.
@@ -178,16 +244,14 @@ struct Assoc {
 struct Multi {
     // sharded operation (slamgpu_shard_*): the resampling plan comes back through a pinned mirror and a sequence word the plan kernel
     // stores after it (both allocated with the context: slamgpu_shard_plan allocates nothing)
-    ShardPlan *plan_host = nullptr;
-    uint32_t *plan_seq_host = nullptr;
+    PinBuf<ShardPlan> plan_host;
+    PinBuf<uint32_t> plan_seq_host;
     uint32_t plan_seq = 0;
     DevBuf<float4> poolA_dev;     // the arrival pool (Buffers::poolA / poolB point here), allocated by the first unpack that needs it
     DevBuf<float> poolB_dev;
     int64_t pool_used = 0;        // arrival-pool slots handed out since the pool was last emptied (flatten / settle / upload)
     bool shard_settled = false;   // the sharded resampling stage of this step moved everything physically (records arrived)
     bool shard_est_fresh = false; // est_part holds this shard's partials of the last update (shard_finalize_kernel)
-    bool own_totals = true;       // ws.blk_w[0] is this context's allocation (not a caller-provided collective buffer) ...
-    float *own_blk_w = nullptr;   // ... which waits here meanwhile (slamgpu_shard_set_totals_buffer)
     // distributed operation (slamgpu_dist_*)
     bool dist = false, dist_clean = false;
     DevBuf<PeerPtrs> peers_dev;
@@ -251,9 +315,7 @@ struct Persist {
     static constexpr int kPqBufs = 4;
     PinBuf<PersistStep> pq_host;
     size_t pq_cap = 0;
-    hipEvent_t pq_kev[kPqBufs] = {};
-    bool pq_kev_used[kPqBufs] = {};
-    int pq_next = 0;
+    SlotRing<kPqBufs> pq_slots;
     DevBuf<uint32_t> psync_dev;
     PinBuf<uint32_t> pstatus_host;
     DevBuf<int32_t> ppk_dev;             // [2][kSmallWords] observation packets of the loop's helper workgroup
@@ -261,45 +323,41 @@ struct Persist {
     DevBuf<float4> pdraw_dev;            // [2][6][ncap] draws of the loop's drawer workgroups (FastSLAM 1, fast build)
     int64_t persist_launches = 0, persist_steps = 0;
     // persist_setup ran to its end: the buffers are there, the status and meeting words zeroed (the last event it makes says so)
-    bool ready() const { return pq_kev[kPqBufs - 1] != nullptr; }
+    bool ready() const { return pq_slots.created(); }
 };
 
 // The state of the posterior layer (posterior.cpp): slamgpu_ctx::po.  posterior_release frees it.
 struct Posterior {
-    DevArena msum;                   // staging and partials of the map, pair, innovation and joint summaries
+    DevBuf<char> msum;               // staging and partials of the map, pair, innovation and joint summaries
     // path recording (slamgpu_path_*; kernels.h: PathRing).  path.cap = 0: off, nothing allocated, no kernel of it launched.
     // origin[path_org] is the live origin array
     Ring path;
-    float4 *path_rec_dev = nullptr;
-    int32_t *path_origin_dev[2] = {nullptr, nullptr};
+    DevBuf<float4> path_rec_dev;
+    DevBuf<int32_t> path_origin_dev[2];
     int path_org = 0;
-    DevArena path_arena;             // staging, push buffers and partials of slamgpu_path_trace / _summary
+    DevBuf<char> path_arena;         // staging, push buffers and partials of slamgpu_path_trace / _summary
     // pose posterior (slamgpu_pose_*; kernels.h: PoseSummaryArgs).  pose.cap = 0: the per-step ring is off.  Nothing is allocated and no kernel of it launched until the ring is enabled or
     // slamgpu_pose_summary is called
     Ring pose;
-    double *pose_ring_dev = nullptr; // [pose.cap][kPoseStride]
-    double *pose_dev = nullptr;      // [tiles][kPoseFields] partials | [kPoseStride] staging of slamgpu_pose_summary
+    DevBuf<double> pose_ring_dev;    // [pose.cap][kPoseStride]
+    DevBuf<double> pose_dev;         // [tiles][kPoseFields] partials | [kPoseStride] staging of slamgpu_pose_summary
     // innovation posterior (slamgpu_innovation_*; kernels.h: InnovArgs).  innov.cap = 0: the ring is off.
     // innov_records counts the _record calls since the enable.  A packet travels
-    // through one of kInnovStage pinned staging slots (an event per slot says when the device has taken it: a record does not wait
-    // for the device unless it is kInnovStage packets ahead of it).  Nothing is allocated and no kernel of it launched until the ring
+    // through one of kInnovStage pinned staging slots (innov_slots: a record does not wait for the device unless it is
+    // kInnovStage packets ahead of it).  Nothing is allocated and no kernel of it launched until the ring
     // is enabled or slamgpu_innovation_summary is called
     Ring innov;
     int64_t innov_records = 0;
-    double *innov_ring_dev = nullptr;  // [innov.cap][kInnStride]
-    int32_t *innov_tag_dev = nullptr;  // [innov.cap][2]: record, slot
-    char *innov_host = nullptr;        // pinned [kInnovStage][innov_host_m] x (zf 8 B | idf 4 B)
+    DevBuf<double> innov_ring_dev;     // [innov.cap][kInnStride]
+    DevBuf<int32_t> innov_tag_dev;     // [innov.cap][2]: record, slot
+    PinBuf<char> innov_host;           // [kInnovStage][innov_host_m] x (zf 8 B | idf 4 B)
     size_t innov_host_m = 0;
-    uint64_t innov_seq = 0;
-    hipEvent_t innov_ev[4]{};
-    bool innov_ev_used[4]{};
-    int32_t *innov_lab_host = nullptr;  // pinned, two pieces: the labels of slamgpu_innovation_summary_labels on their way down
-    uint64_t innov_lab_seq = 0;
-    hipEvent_t innov_lab_ev[2]{};
-    bool innov_lab_ev_used[2]{};
+    SlotRing<4> innov_slots;
+    PinBuf<int32_t> innov_lab_host;    // two pieces: the labels of slamgpu_innovation_summary_labels on their way down
+    SlotRing<2> innov_lab_slots;
 };
 
-// One slot of the big-packet ring (slamgpu_ctx::pkt_*) on its way to the device.  begin takes the next slot, waits ON THE HOST for
+// One slot of the big-packet ring (slamgpu_ctx::pkt_*, the slots' turns and events in pkt_slots) on its way to the device.  begin takes the next slot, waits ON THE HOST for
 // the launch that last read it and sets the pinned header to the dense layout; commit uploads `used` bytes and records the slot's
 // event.  (A device-made packet takes its slot with pkt_take_slot and waits on the front end's stream instead: do_update_dev.)
 struct BigPacket {
@@ -318,6 +376,7 @@ struct slamgpu_ctx {
     slamgpu_config cfg{};
     const KernelTable *k = nullptr;
     hipStream_t stream = nullptr;
+    CoreBufs own;
     Buffers B{};
     WeightScratch ws{};
     int nf = 0;
@@ -325,22 +384,20 @@ struct slamgpu_ctx {
     uint32_t rng_skew = 0;  // update launches that were not filter steps (slamgpu_dist_settle): they draw nothing
     // big-packet ring (observation packets that do not fit the kernel-argument form)
     size_t pkt_bytes = 0;
-    char *pkt_host = nullptr;  // pinned [kRing][pkt_bytes]
-    char *pkt_dev = nullptr;
-    hipEvent_t pkt_ev[kRing]{};
-    bool pkt_ev_used[kRing]{};
-    uint64_t pkt_seq = 0;
+    PinBuf<char> pkt_host;     // [kRing][pkt_bytes]
+    DevBuf<char> pkt_dev;
+    SlotRing<kRing> pkt_slots;  // (its events are made with the context: no step pays for one)
     // tape staging (TAPE mode)
-    float *tape_host = nullptr;  // pinned: normals [3][ncap] (or predict [2][ncap]) + strata [n_global]
-    float *normals_dev = nullptr;
-    float *strata_dev[2] = {nullptr, nullptr};  // by step parity: an update launch may still need the previous step's
+    PinBuf<float> tape_host;   // normals [3][ncap] (or predict [2][ncap]) + strata [n_global]
+    DevBuf<float> normals_dev;
+    DevBuf<float> strata_dev[2];  // by step parity: an update launch may still need the previous step's
     // lazy predict queue
     PredictArgs pending{};
     // host mirror of ctrl for readback
-    Ctrl *ctrl_host = nullptr;  // pinned
+    PinBuf<Ctrl> ctrl_host;
     // pose-estimate history
-    double *hist_dev = nullptr;  // [kHistCap][kHistStride]
-    double *hist_host = nullptr; // pinned mirror of it (history_to_host)
+    DevBuf<double> hist_dev;   // [kHistCap][kHistStride]
+    PinBuf<double> hist_host;  // mirror of it (history_to_host)
     int hist_n = 0;
     bool est_fresh = false;  // Ctrl.est / hist slot hist_n were written by the last update and nothing changed since
     // profiling
@@ -377,13 +434,13 @@ struct slamgpu_ctx {
     // landmark uses: a step that writes landmarks opens a new row for them; a row whose last landmark moved on is recycled.
     std::vector<uint32_t> seen_step; // [cap_nf] observation step that last re-observed each landmark (duplicate check)
     std::vector<int32_t> live_flag;  // [cap_nf] which record buffer of every landmark row is live (flips when re-observed)
-    int32_t *live_dev = nullptr;     // device copy for flatten / shard pack + unpack
+    DevBuf<int32_t> live_dev;        // device copy for flatten / shard pack + unpack
     std::vector<int32_t> erow;       // [cap_nf] row of every landmark
     std::vector<int32_t> refcnt;     // [cap_rows] landmarks using each row
     std::vector<int32_t> free_rows;  // stack of unused rows
     std::vector<int32_t> live_rows;  // rows with refcnt > 0
     std::vector<int32_t> live_pos;   // [cap_rows] position in live_rows, -1 if not live
-    int32_t *erow_dev = nullptr, *rows_dev = nullptr;  // device copies for gather / flatten / shard pack + unpack
+    DevBuf<int32_t> erow_dev, rows_dev;  // device copies for gather / flatten / shard pack + unpack
     Multi mg;                        // sharded and distributed operation (multigpu.cpp)
     int fresh_row = -1;              // row the last update opened, while nothing but the resample the next update launch
                                      // applies has touched it: records of its landmarks sit in the source slot itself
@@ -391,10 +448,9 @@ struct slamgpu_ctx {
     Front fe;                        // the observation front end and the genealogy book's hand-over (observe.cpp)
     Persist ps;                      // the persistent step loop (observe.cpp)
     Assoc as;                       // the gated and per-particle association (association.cpp)
-    char *peek_dev = nullptr;        // staging of slamgpu_peek, grown on demand
-    size_t peek_bytes = 0;
+    DevBuf<char> peek_dev;           // staging of slamgpu_peek, grown on demand
     Posterior po;                    // path, pose and innovation posteriors and the summaries' staging (posterior.cpp)
-    unsigned long long *stamps_dev = nullptr;  // diagnostic (SLAMGPU_STAMPS=1 + libslamgpu_stamps.so): UpdateArgs::stamps
+    DevBuf<unsigned long long> stamps_dev;  // diagnostic (SLAMGPU_STAMPS=1 + libslamgpu_stamps.so): UpdateArgs::stamps
     bool special_ok = true;              // SLAMGPU_NO_SPECIAL=1 turns it off (diagnostic / tests: update_kernel's general instantiation for every launch)
     bool counted_ok = true;              // SLAMGPU_NO_COUNTED=1 turns it off (diagnostic / tests: never update_kernel_counted)
     int64_t counted_launches[kCountedMax + 1] = {};  // specialised launches by counted instantiation, [0]: the plain specialised kernel (slamgpu_update_counted_launches: tests)

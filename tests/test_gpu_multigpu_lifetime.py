@@ -97,7 +97,30 @@ def test_callers_totals_buffer_outlives_the_context(tape):
     a = next(steps(tape))
     s.shard_step(*a)  # (the update launch writes this shard's totals into the caller's buffer)
     s.sync()
-    s.close()  # not restored: the context must put its own buffer back and free that one
+    s.close()  # not restored: the context must free its own buffer and leave that one alone
     assert owner.L.slamgpu_dev_free(owner.h, buf) == 0, owner.L.slamgpu_last_error()
+    owner.close()
+    usable_context(sg, tape)
+
+
+def test_callers_totals_buffer_handed_back_before_the_context_closes(tape):
+    """a caller's buffer, then null: the context's own buffer is the one in use again, and the caller's still takes a copy and a free"""
+    import slam_amd as sg
+    owner = sg.SlamGpu(SHARD, tape["nlm"], method=sg.FASTSLAM2, n_effective=int(0.75 * SHARD), rng_mode=sg.RNG_PHILOX, seed=3, math_mode=1)
+    s = sg.SlamGpu(SHARD, tape["nlm"], method=sg.FASTSLAM2, n_effective=int(0.75 * N), rng_mode=sg.RNG_PHILOX, seed=9, math_mode=1,
+                   first_particle=0, n_particles_global=N)
+    own, nb = s.shard_block_totals()
+    buf, other = owner.dev_alloc(4 * 3 * nb), owner.dev_alloc(4 * 3 * nb)
+    assert own not in (buf, other)
+    s.shard_set_totals_buffer(buf)
+    assert s.shard_block_totals()[0] == buf
+    s.shard_step(*next(steps(tape)))
+    s.sync()
+    s.shard_set_totals_buffer(None)
+    assert s.shard_block_totals()[0] == own
+    s.close()
+    owner.dev_copy(other, buf, 4 * 3 * nb)
+    for p in (buf, other):
+        assert owner.L.slamgpu_dev_free(owner.h, p) == 0, owner.L.slamgpu_last_error()
     owner.close()
     usable_context(sg, tape)
