@@ -1009,6 +1009,10 @@ int slamgpu_update_special_launches(slamgpu_ctx *ctx, int64_t *count);
  * launches so far took the instantiation counted for m; out[0]: how many took the plain specialised one.  Their sum is
  * slamgpu_update_special_launches.  Host bookkeeping; does not synchronise. */
 int slamgpu_update_counted_launches(slamgpu_ctx *ctx, int64_t out[9]);
+/* FastSLAM 1 on single compact contexts of more than 768 tiles of 256 particles runs a variant of the update kernel built for three
+ * waves per SIMD (never in contexts created under SLAMGPU_NO_WIDE=1).  count: how many of the context's update launches so far took
+ * it.  Such a launch is never a specialised one.  Host bookkeeping; does not synchronise. */
+int slamgpu_update_wide_launches(slamgpu_ctx *ctx, int64_t *count);
 
 #endif /* SLAMGPU_EXPERIMENTAL */
 

@@ -16,7 +16,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 DECLARED_SYMBOLS = [
     "slamgpu_last_error", "slamgpu_abi_version", "slamgpu_device_count", "slamgpu_jacobians", "slamgpu_jacobians_multi", "slamgpu_create",
     "slamgpu_destroy", "slamgpu_predict", "slamgpu_update", "slamgpu_estimate", "slamgpu_estimate_async", "slamgpu_estimate_fetch", "slamgpu_stats", "slamgpu_ancestors",
-    "slamgpu_num_landmarks", "slamgpu_retire_landmarks", "slamgpu_genealogy_rows", "slamgpu_persist_info", "slamgpu_persist_status", "slamgpu_update_special", "slamgpu_update_special_modes", "slamgpu_update_special_launches", "slamgpu_update_counted_launches", "slamgpu_download", "slamgpu_upload", "slamgpu_sync", "slamgpu_step", "slamgpu_history_fetch", "slamgpu_shard_set_totals_buffer", "slamgpu_shard_step", "slamgpu_timer_start", "slamgpu_timer_stop", "slamgpu_stream", "slamgpu_profile",
+    "slamgpu_num_landmarks", "slamgpu_retire_landmarks", "slamgpu_genealogy_rows", "slamgpu_persist_info", "slamgpu_persist_status", "slamgpu_update_special", "slamgpu_update_special_modes", "slamgpu_update_special_launches", "slamgpu_update_counted_launches", "slamgpu_update_wide_launches", "slamgpu_download", "slamgpu_upload", "slamgpu_sync", "slamgpu_step", "slamgpu_history_fetch", "slamgpu_shard_set_totals_buffer", "slamgpu_shard_step", "slamgpu_timer_start", "slamgpu_timer_stop", "slamgpu_stream", "slamgpu_profile",
     "slamgpu_kernel_time", "slamgpu_algorithmic_bytes", "slamgpu_shard_update", "slamgpu_shard_block_totals", "slamgpu_shard_plan",
     "slamgpu_shard_record_floats", "slamgpu_shard_pack", "slamgpu_shard_unpack", "slamgpu_shard_finish", "slamgpu_shard_estimate",
     "slamgpu_dev_alloc", "slamgpu_dev_free", "slamgpu_dev_copy", "slamgpu_dev_copy_async", "slamgpu_shard_estimate_async",
@@ -191,6 +191,8 @@ def load_library():
         L.slamgpu_update_special_launches.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
     if hasattr(L, "slamgpu_update_counted_launches"):
         L.slamgpu_update_counted_launches.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
+    if hasattr(L, "slamgpu_update_wide_launches"):
+        L.slamgpu_update_wide_launches.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
     if hasattr(L, "slamgpu_persist_status"):  # (an older build loaded through SLAMGPU_LIB for an A/B lacks the round-6 entries)
         L.slamgpu_persist_status.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     L.slamgpu_download.argtypes = [C.c_void_p] * 6
@@ -549,6 +551,12 @@ class SlamGpu:
         """how many of the context's update launches took a specialised instantiation of the kernel (slamgpu_update_special_launches)"""
         n = C.c_int64()
         _chk(self.L.slamgpu_update_special_launches(self.h, C.byref(n)))
+        return n.value
+
+    def wide_launches(self):
+        """how many of the context's update launches took update_kernel_wide (slamgpu_update_wide_launches)"""
+        n = C.c_int64()
+        _chk(self.L.slamgpu_update_wide_launches(self.h, C.byref(n)))
         return n.value
 
     def counted_launches(self):

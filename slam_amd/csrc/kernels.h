@@ -57,16 +57,15 @@ constexpr int kHistStride = 6;      // doubles per pose-estimate history entry: 
 constexpr int kMaxScanBlocks = 8192;
 // single contexts on the compact layout with more tiles than this run update_kernel_wide (kernels.hip)
 constexpr int kWideBlocks = 768;
-inline bool update_wide_off() {  // (diagnostic: SLAMGPU_NO_WIDE=1 keeps update_kernel at every size)
-    static const bool off = getenv("SLAMGPU_NO_WIDE") != nullptr;
-    return off;
-}
+// (off: the context was created under SLAMGPU_NO_WIDE=1 -- diagnostic / tests: update_kernel at every size; it travels to the launcher
+// beside no_special, and a launch that took the wide kernel says so: kUpdateTookWide, slamgpu_update_wide_launches)
+constexpr int kUpdateTookWide = -1;  // KernelTable::update's answer for a launch of update_kernel_wide (never a specialised one)
 // (round 6: FastSLAM 1 only.  Without the SLP vectoriser update_kernel<2, 0, false> needs 154 registers and holds three waves per
 // SIMD by itself; the wide kernel, squeezed under __launch_bounds__(256, 3), then LOSES to it: 10^6 particles 88.0 against 84.3 us per
 // step, same box -- and 84.4 for round 5's build, where the SLP vectoriser had update_kernel at 171 registers and the wide kernel won
 // 84.8 against 97.0.  tests/test_host_frontend.py holds update_kernel<2, 0, false> to 168 registers, the most that leaves three waves.)
-inline bool update_is_wide(int method, int arrivals, bool big, int nblocks) {
-    return method == 1 && arrivals == 0 && !big && nblocks > kWideBlocks && !update_wide_off();
+inline bool update_is_wide(int method, int arrivals, bool big, int nblocks, bool off) {
+    return method == 1 && arrivals == 0 && !big && nblocks > kWideBlocks && !off;
 }
 // Mode sets of update_kernel (kernels.hip).  Every member is a launch-wide value the host holds when it fills the launch's arguments
 // and the step text (update_step.inl) tests.  The general instantiation (SPEC = 0) tests them at run time; a specialised one
@@ -938,10 +937,11 @@ struct KernelTable {
     // the step: [resampling stage of the previous update, inline] + [gather] + [fused predicts] + per-particle observation
     // update + in-block weight prefix / totals  (+ helper blocks: genealogy copy, Ctrl words, estimate reduction)
     // no_special: the general instantiation whatever the launch's mode set (SLAMGPU_NO_SPECIAL=1).  Returns the instantiation the
-    // launch took (update_special: 0 general, s > 0 kUpdateSpecs[s]).  no_counted: never a counted instantiation (SLAMGPU_NO_COUNTED=1;
-    // otherwise a specialised launch is a counted one when update_counted says so)
+    // launch took (update_special: 0 general, s > 0 kUpdateSpecs[s]; kUpdateTookWide: update_kernel_wide).  no_counted: never a counted
+    // instantiation (SLAMGPU_NO_COUNTED=1; otherwise a specialised launch is a counted one when update_counted says so).  no_wide: never
+    // update_kernel_wide (SLAMGPU_NO_WIDE=1)
     int (*update)(hipStream_t, const Buffers &, const PredictArgs &, const UpdateArgs &, const RngArgs &,
-                  const WeightScratch &, bool no_special, bool no_counted);
+                  const WeightScratch &, bool no_special, bool no_counted, bool no_wide);
     // the same step with a per-particle association (PerParticle: update_kernel<.., PP = true>; single contexts on plain rows); driven
     // by the device when PerParticle::obs_dev is set (update_kernel<.., PPD = true>; no observation: nothing)
     // (no specialised instantiation: always 0)

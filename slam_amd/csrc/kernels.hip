@@ -4258,7 +4258,8 @@ static void launch_shard_finish(hipStream_t st, const Buffers &B, const WeightSc
 }
 
 static int launch_update_any(hipStream_t st, const Buffers &B, const PredictArgs &PA, const UpdateArgs &U,
-                             const RngArgs &rng, const WeightScratch &ws, const PerParticle &ppa, bool no_special, bool no_counted) {
+                             const RngArgs &rng, const WeightScratch &ws, const PerParticle &ppa, bool no_special, bool no_counted,
+                             bool no_wide) {
     // compute blocks first (they are the long pole), then -- single-context pipeline only -- the copy blocks of a
     // pending lazy gather (they exit at once when nothing is pending: the host cannot know) and one helper block
     int grid = B.ncap / kBlock;
@@ -4275,10 +4276,10 @@ static int launch_update_any(hipStream_t st, const Buffers &B, const PredictArgs
     const bool scan_dma = U.arrivals == 2 && U.plan_inline && !U.scan_global && !U.logw && nbg > 2 * (size_t) kBlock &&
                           2 * sizeof(float) * (((nbg + 255) / 256) * 256) <= update_window_bytes() + stage_bytes;
     const int h_flags = (U.plan_inline ? 1 : 0) | (U.scan_global ? 2 : 0) | (U.logw ? 4 : 0) | (U.lazy ? 8 : 0) | (U.front.on ? 16 : 0) | (scan_dma ? 32 : 0) | (U.count_remote ? 64 : 0);
-    if (update_is_wide(U.method, U.arrivals, U.big != nullptr, ws.nblocks)) {  // (FastSLAM 1, single context, compact layout, more tiles than two rounds of CUs)
+    if (update_is_wide(U.method, U.arrivals, U.big != nullptr, ws.nblocks, no_wide)) {  // (FastSLAM 1, single context, compact layout, more tiles than two rounds of CUs)
         hipLaunchKernelGGL((update_kernel_wide<1>), dim3(grid), dim3(kBlock), lds, st, h_tot, B.ctrl, U.front.state_in, ws.nblocks, B.slot, grid,
                            h_flags, B, PA, U, rng, ws);
-        return 0;
+        return kUpdateTookWide;
     }
     // per-particle association (slamgpu.cpp: do_update_particle guarantees a single context on plain rows: MODE 0, BIG; obs_dev: driven
     // by the device)
@@ -4330,14 +4331,14 @@ static int launch_update_any(hipStream_t st, const Buffers &B, const PredictArgs
 }
 
 static int launch_update(hipStream_t st, const Buffers &B, const PredictArgs &PA, const UpdateArgs &U, const RngArgs &rng, const WeightScratch &ws,
-                         bool no_special, bool no_counted) {
-    return launch_update_any(st, B, PA, U, rng, ws, PerParticle{}, no_special, no_counted);
+                         bool no_special, bool no_counted, bool no_wide) {
+    return launch_update_any(st, B, PA, U, rng, ws, PerParticle{}, no_special, no_counted, no_wide);
 }
 
-// (per-particle association: no specialised instantiation, so no counted one)
+// (per-particle association: no specialised instantiation, so no counted one; plain rows, so never the wide kernel)
 static int launch_update_particle(hipStream_t st, const Buffers &B, const PredictArgs &PA, const UpdateArgs &U, const RngArgs &rng,
                                   const WeightScratch &ws, const PerParticle &ppa, bool no_special) {
-    return launch_update_any(st, B, PA, U, rng, ws, ppa, no_special, true);
+    return launch_update_any(st, B, PA, U, rng, ws, ppa, no_special, true, true);
 }
 
 // K iterations in one launch (kernels.h: PersistArgs): kPersistStride x (tiles + 1 helper) workgroups, of which every

@@ -527,6 +527,7 @@ int slamgpu_create(const slamgpu_config *cfg, slamgpu_ctx **out) {
     c->ps.persist_ok = getenv("SLAMGPU_NO_PERSIST") == nullptr;                               // diagnostic / tests: slamgpu_run_observe as a loop of launches
     c->special_ok = getenv("SLAMGPU_NO_SPECIAL") == nullptr;                               // diagnostic / tests: kernels.h: update_special
     c->counted_ok = getenv("SLAMGPU_NO_COUNTED") == nullptr;                               // diagnostic / tests: kernels.h: update_counted
+    c->wide_ok = getenv("SLAMGPU_NO_WIDE") == nullptr;                                     // diagnostic / tests: kernels.h: update_is_wide
     if (const char *e = getenv("SLAMGPU_CONSOLIDATE_ABOVE")) c->consolidate_above = atoi(e);
     if (const char *e = getenv("SLAMGPU_PLAIN_ROWS_TARGET")) c->plain_rows_target = atoi(e);
     const int cap_nf = cfg->max_landmarks > 0 ? cfg->max_landmarks : 1;
@@ -737,7 +738,9 @@ int issue_update(slamgpu_ctx *c, UpdateArgs &U, int n_new, int n_rows, bool need
     } else {
         Timed t(c, c->cfg.method == SLAMGPU_FASTSLAM2 ? "fs2_update" : "fs1_update");
         if (c->as.pp_launch) c->k->update_particle(c->stream, c->B, PA, U, rng, c->ws, *c->as.pp_launch, !c->special_ok);
-        else if (const int spec = c->k->update(c->stream, c->B, PA, U, rng, c->ws, !c->special_ok, !c->counted_ok); spec != 0) {
+        else if (const int spec = c->k->update(c->stream, c->B, PA, U, rng, c->ws, !c->special_ok, !c->counted_ok, !c->wide_ok); spec == kUpdateTookWide)
+            c->wide_launches++;
+        else if (spec != 0) {
             c->special_launches++;
             c->counted_launches[update_counted(spec, U.m, U.front.on != 0, !c->counted_ok)]++;
         }
@@ -1179,6 +1182,13 @@ int slamgpu_update_special_launches(slamgpu_ctx *c, int64_t *count) {
     if (int rc = check_ctx(c)) return rc;
     if (!count) return fail(SLAMGPU_ERR_INVALID, "slamgpu_update_special_launches: count is null");
     *count = c->special_launches;
+    return 0;
+}
+
+int slamgpu_update_wide_launches(slamgpu_ctx *c, int64_t *count) {
+    if (int rc = check_ctx(c)) return rc;
+    if (!count) return fail(SLAMGPU_ERR_INVALID, "slamgpu_update_wide_launches: count is null");
+    *count = c->wide_launches;
     return 0;
 }
 

@@ -452,6 +452,8 @@ struct slamgpu_ctx {
     Posterior po;                    // path, pose and innovation posteriors and the summaries' staging (posterior.cpp)
     DevBuf<unsigned long long> stamps_dev;  // diagnostic (SLAMGPU_STAMPS=1 + libslamgpu_stamps.so): UpdateArgs::stamps
     bool special_ok = true;              // SLAMGPU_NO_SPECIAL=1 turns it off (diagnostic / tests: update_kernel's general instantiation for every launch)
+    bool wide_ok = true;                 // SLAMGPU_NO_WIDE=1 turns it off (diagnostic / tests: update_kernel where update_kernel_wide would run)
+    int64_t wide_launches = 0;           // update launches that took update_kernel_wide (slamgpu_update_wide_launches: tests)
     bool counted_ok = true;              // SLAMGPU_NO_COUNTED=1 turns it off (diagnostic / tests: never update_kernel_counted)
     int64_t counted_launches[kCountedMax + 1] = {};  // specialised launches by counted instantiation, [0]: the plain specialised kernel (slamgpu_update_counted_launches: tests)
     int64_t special_launches = 0;        // update launches that took a specialised instantiation (slamgpu_update_special_launches: tests)

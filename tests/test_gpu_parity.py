@@ -403,23 +403,22 @@ def test_many_landmarks_big_packet_path(sg, oracle, tmp_path, math_mode):
     o.close()
 
 
-@pytest.mark.parametrize("math_mode", [0, 1], ids=["strict", "fast"])
-def test_full_size_philox_vs_oracle(sg, oracle, math_mode):
-    """BASELINE configs[2] size (100 000 particles, example_webmap) in the throughput RNG mode: the device's
-    Philox4x32-10 + Box-Muller stream against the oracle's restatement of the same generator, teacher-forced for
-    the first observation steps, plus the size-independent invariants of the update."""
-    N = 100000
-    o = oracle.sim(sim_args("example_webmap", "FASTSLAM2", N, 7))
-    o.set_rng(1, 7)  # particle noise from Philox(seed 7); control / sensor noise from libc rand() as always
+def philox_steps_vs_oracle(sg, oracle, method, N, max_steps, math_mode, seed=7):
+    """The first max_steps observation steps of example_webmap in the throughput RNG mode, teacher-forced: the device's
+    Philox4x32-10 + Box-Muller stream against the oracle's restatement of the same generator.  Returns (steps that resampled, steps
+    that did not, update_kernel_wide launches of the context, of its shadow)."""
+    fs2 = method == 2
+    o = oracle.sim(sim_args("example_webmap", "FASTSLAM2" if fs2 else "FASTSLAM1", N, seed))
+    o.set_rng(1, seed)  # particle noise from Philox(seed); control / sensor noise from libc rand() as always
     algo = o.algo()
     Q, R, dt = o.noise()
-    s = sg.SlamGpu(N, o.nlm, method=2, n_effective=algo.n_effective, wheel_base=algo.wheel_base, rng_mode=sg.RNG_PHILOX, seed=7,
+    s = sg.SlamGpu(N, o.nlm, method=method, n_effective=algo.n_effective, wheel_base=algo.wheel_base, rng_mode=sg.RNG_PHILOX, seed=seed,
                    math_mode=math_mode)
     # a shadow context that never resamples (NEFFECTIVE 0), stepped in lockstep from the same teacher-forced states with the same
     # Philox keys: its download is the real context's PRE-resample set with the device's own normalised weights
-    shadow = sg.SlamGpu(N, o.nlm, method=2, n_effective=0, wheel_base=algo.wheel_base, rng_mode=sg.RNG_PHILOX, seed=7, math_mode=math_mode)
-    k = resamples = 0
-    while k < 8:   # (the sixth observation step is the first that resamples)
+    shadow = sg.SlamGpu(N, o.nlm, method=method, n_effective=0, wheel_base=algo.wheel_base, rng_mode=sg.RNG_PHILOX, seed=seed, math_mode=math_mode)
+    k = resamples = plain = 0
+    while k < max_steps:
         a = o.control()
         x, vg = o.true_pose()
         s.predict(float(vg[0]), float(vg[1]), Q, float(dt), float(x[2]))
@@ -468,9 +467,13 @@ def test_full_size_philox_vs_oracle(sg, oracle, math_mode):
                 assert np.all((sel < hi + tol) | last), (k, int(np.argmax(sel - hi - tol)), float((sel - hi - tol)[~last].max()))
                 # (for the record: how far the oracle's own list, drawn from ITS weights, is from the device's)
                 d = np.abs(keep.astype(np.int64) - own_keep.astype(np.int64))
-                print("N=1e5 %s step %d: ancestors vs the oracle's own list: identical %.3f, one off %.3f, more than eight off %.4f"
-                      % (("strict", "fast")[math_mode], k, (d == 0).mean(), (d == 1).mean(), (d > 8).mean()))
+                print("N=%d %s step %d: ancestors vs the oracle's own list: identical %.3f, one off %.3f, more than eight off %.4f"
+                      % (N, ("strict", "fast")[math_mode], k, (d == 0).mean(), (d == 1).mean(), (d > 8).mean()))
+            elif not fs2:
+                plain += 1
+                compare_state(got, exp, fs2=False, tag="FASTSLAM1 N=%d obs %d" % (N, k), math_mode=math_mode)
             else:
+                plain += 1
                 # same Philox bits; Box-Muller through device libm (fast build: the hardware v_log / v_sin / v_cos) instead of
                 # glibc: poses agree to ~1e-5
                 assert np.abs(got["xv"] - exp["xv"]).max() <= 5e-4, (k, np.abs(got["xv"] - exp["xv"]).max())
@@ -480,10 +483,20 @@ def test_full_size_philox_vs_oracle(sg, oracle, math_mode):
             np.testing.assert_allclose(s.estimate()[:2], o.estimate()[:2], atol=2e-3)
             s.upload(exp)
             shadow.upload(exp)
-    assert resamples >= 1
+    wide = (s.wide_launches(), shadow.wide_launches())
     s.close()
     shadow.close()
     o.close()
+    return (resamples, plain) + wide
+
+
+@pytest.mark.parametrize("math_mode", [0, 1], ids=["strict", "fast"])
+def test_full_size_philox_vs_oracle(sg, oracle, math_mode):
+    """BASELINE configs[2] size (100 000 particles, example_webmap) in the throughput RNG mode: the device's
+    Philox4x32-10 + Box-Muller stream against the oracle's restatement of the same generator, teacher-forced for
+    the first observation steps, plus the size-independent invariants of the update."""
+    resamples = philox_steps_vs_oracle(sg, oracle, 2, 100000, 8, math_mode)[0]   # (the sixth observation step is the first that resamples)
+    assert resamples >= 1
 
 
 def test_step_call_equals_separate_calls(sg):
