@@ -312,10 +312,17 @@ SLAM_DEV void mvgauss3(float &x0, float &x1, float &x2, const L3 &L, float g0, f
 // each, two per double): the six-step scans and reductions of the update kernel spent ~1.5 us per launch in them
 // (profiles/update_kernel_levels_r02_before_*.txt: levels 2 and 9).  DPP moves are VALU operands (~8 cycles).  gfx9
 // wave64 scan: row_shr 1, 2, 4, 8 inside each row of 16 lanes, then row_bcast:15 into rows 1 and 3 and row_bcast:31
-// into rows 2 and 3; lanes without a source read 0 (old = 0, bound_ctrl off), which is the identity of the sum.
+// into rows 2 and 3; lanes without a source read 0, which is the identity of the sum.
 // The association is fixed by the lane layout, so every block, kernel and shard computes bit-identical sums.
+// How a lane without a source gets its 0: the row_shr steps run over every row and bank (masks 0xf), so bound_ctrl supplies it and
+// `old` is dead -- with old = 0 and bound_ctrl off every DPP move that the compiler cannot fold into its consumer (the halves of a
+// double: v_add_f64 takes no DPP operand) was preceded by a v_mov_b32 of the zero it would keep, two per step of a double scan.
+// The row_bcast steps write only the rows of their mask; the others keep `old`, so they keep old = 0 and bound_ctrl off.
 template <int CTRL, int ROW_MASK>
-SLAM_DEV int dpp_i(int v) { return __builtin_amdgcn_update_dpp(0, v, CTRL, ROW_MASK, 0xf, false); }
+SLAM_DEV int dpp_i(int v) {
+    constexpr bool shr_all = (CTRL & 0x1f0) == 0x110 && ROW_MASK == 0xf;  // row_shr:1 .. 15, every row
+    return __builtin_amdgcn_update_dpp(0, v, CTRL, ROW_MASK, 0xf, shr_all);
+}
 template <int CTRL, int ROW_MASK>
 SLAM_DEV float dpp_f(float v) { return __int_as_float(dpp_i<CTRL, ROW_MASK>(__float_as_int(v))); }
 template <int CTRL, int ROW_MASK>

@@ -624,8 +624,18 @@ SLAM_DEV void scan_issue_dma(const float *__restrict__ tot, int nb, int nbl, flo
     }
 }
 
-SLAM_DEV void scan_finish(const ScanLoads L, const float *__restrict__ tot, int nb, int nbl, bool logw, double *off, double *sh_a,
-                          double *sh_q, double &W, double &Q, double &M, const float *stab = nullptr) {
+// In two halves.  scan_totals: the sums W and Q (and M), which is all the decision to resample needs -- and all that a launch which
+// does not resample, a helper block or a copy role without a pending gather ever reads.  scan_prefix: the exclusive prefix off[0 .. nb],
+// which only the ancestor search reads: a caller that knows the decision calls it on resampling launches alone (update_step.inl, in
+// front of the barrier that stands behind the decision anyway; two LDS stores, two loads, two stores and the adds between them per
+// thread otherwise spent on every launch).  The additions and their order are those of the one function this was: scan_finish below.
+struct ScanSeg {
+    double a, sa;  // this thread's segment total, and the wave's inclusive scan of it
+    float w0;      // linear weights, at most two totals per thread: the segment's first total as it was loaded -- the one term the
+                   // prefix adds again (every other table: the segment's terms are stashed in off[], as they arrive)
+};
+SLAM_DEV ScanSeg scan_totals(const ScanLoads L, const float *__restrict__ tot, int nb, int nbl, bool logw, double *off, double *sh_a,
+                             double *sh_q, double &W, double &Q, double &M, const float *stab = nullptr) {
     const int t = threadIdx.x, lane = t & (kWave - 1), wv = t / kWave;
     const int per = (nb + kBlock - 1) / kBlock;
     const int lo = min(nb, t * per), hi = min(nb, lo + per);
@@ -648,7 +658,7 @@ SLAM_DEV void scan_finish(const ScanLoads L, const float *__restrict__ tot, int 
     auto acc = [&](int k, float tk_f, float qk_f, float mk_f) {
         const double sc = logw ? block_scale(mk_f, M) : 1.0;
         const double tk = (double) tk_f * sc;
-        off[k] = tk;  // this thread's own segment: read back below
+        if (!two || logw) off[k] = tk;  // this thread's own segment: read back by scan_prefix
         a += tk;
         q += (double) qk_f * (tk * tk);  // second row: sum (w_i / T)^2 of the block (update_kernel's tail)
     };
@@ -701,19 +711,38 @@ SLAM_DEV void scan_finish(const ScanLoads L, const float *__restrict__ tot, int 
     if (lane == kWave - 1) sh_a[wv] = sa;
     if (lane == 0) sh_q[wv] = sq;
     __syncthreads();
+    W = ((sh_a[0] + sh_a[1]) + sh_a[2]) + sh_a[3];
+    Q = ((sh_q[0] + sh_q[1]) + sh_q[2]) + sh_q[3];
+    return ScanSeg{a, sa, L.tv0};
+}
+// (sh_a: as scan_totals left it -- nothing may have written it in between; the caller's next barrier publishes off[])
+SLAM_DEV void scan_prefix(const ScanSeg &S, int nb, bool logw, double W, double *off, const double *sh_a) {
+    const int t = threadIdx.x, wv = t / kWave;
+    const int per = (nb + kBlock - 1) / kBlock;
+    const int lo = min(nb, t * per), hi = min(nb, lo + per);
     double base = 0.0;
 #pragma unroll
     for (int k = 0; k < kBlock / kWave; k++)
         if (k < wv) base += sh_a[k];
-    double run = base + sa - a;  // exclusive prefix of this thread's segment
-    for (int k = lo; k < hi; k++) {
-        const double tk = off[k];
-        off[k] = run;
-        run += tk;
+    double run = base + S.sa - S.a;  // exclusive prefix of this thread's segment
+    if (per <= 2 && !logw) {
+        // (the term as scan_totals added it: (double) w0 * 1.0)
+        if (lo < hi) off[lo] = run;
+        run += (double) S.w0;
+        if (lo + 1 < hi) off[lo + 1] = run;
+    } else {
+        for (int k = lo; k < hi; k++) {
+            const double tk = off[k];
+            off[k] = run;
+            run += tk;
+        }
     }
-    W = ((sh_a[0] + sh_a[1]) + sh_a[2]) + sh_a[3];
-    Q = ((sh_q[0] + sh_q[1]) + sh_q[2]) + sh_q[3];
     if (t == 0) off[nb] = W;
+}
+SLAM_DEV void scan_finish(const ScanLoads L, const float *__restrict__ tot, int nb, int nbl, bool logw, double *off, double *sh_a,
+                          double *sh_q, double &W, double &Q, double &M, const float *stab = nullptr) {
+    const ScanSeg S = scan_totals(L, tot, nb, nbl, logw, off, sh_a, sh_q, W, Q, M, stab);
+    scan_prefix(S, nb, logw, W, off, sh_a);
 }
 
 template <class After = NoOp>
@@ -896,34 +925,43 @@ SLAM_DEV int64_t find_ancestor_win(double target, bool valid, int guess, const d
     (void) block_ptr;
     const double o = off[b0];
     const double sc = blk_m ? block_scale(ldg<BYP>(blk_m + b0), M) : 1.0;  // (another tile's block maximum: as the prefixes)
-    float pv[16], ev[16];
-    int seg = 15, r = 15;
-    if (b0 - lo < kWinBlocks) {
-        const float *lc = win + (b0 - lo) * kBlock;
-#pragma unroll
-        for (int q = 0; q < 16; q++) pv[q] = lc[16 * q + 15];
+    // first of 16 non-decreasing entries with o + e > target; the last if rounding hides it
+    auto ladder = [&](const float (&e)[16]) -> int {
+        int at = 15;
 #pragma unroll
         for (int q = 14; q >= 0; q--)
-            if (o + (double) pv[q] * sc > target) seg = q;
-        const float4 *l4 = reinterpret_cast<const float4 *>(lc + 16 * seg);
-        const float4 e0 = l4[0], e1 = l4[1], e2 = l4[2], e3 = l4[3];
+            if (o + (double) e[q] * sc > target) at = q;
+        return at;
+    };
+    float pv[16], ev[16];
+    int seg, r;
+    // Two arms, each with ladders of its own.  The window is read through a pointer typed as LDS: with one generic pointer for both
+    // arms the compiler merged them, and the window's 16 pivots and four 16-byte reads were FLAT loads -- the vector-memory path, each
+    // behind a wait for vmcnt and lgkmcnt -- on every resampling launch, for the sake of an arm that the bundled maps never take.
+    // (no __builtin_expect: it lays the per-lane arm out behind the end of the kernel, and the text behind the step's last barrier
+    // must stay free of loads: tests/test_update_tail_cpu.py reads it to the end of the function)
+    if (b0 - lo < kWinBlocks) {
+        const auto *lc = (const __attribute__((address_space(3))) float *) win + (b0 - lo) * kBlock;
+#pragma unroll
+        for (int q = 0; q < 16; q++) pv[q] = lc[16 * q + 15];
+        seg = ladder(pv);
+        using F4 = float __attribute__((ext_vector_type(4)));  // (float4 is a class: no copy out of an address space)
+        const auto *l4 = reinterpret_cast<const __attribute__((address_space(3))) F4 *>(lc + 16 * seg);
+        const F4 e0 = l4[0], e1 = l4[1], e2 = l4[2], e3 = l4[3];
         ev[0] = e0.x; ev[1] = e0.y; ev[2] = e0.z; ev[3] = e0.w; ev[4] = e1.x; ev[5] = e1.y; ev[6] = e1.z; ev[7] = e1.w;
         ev[8] = e2.x; ev[9] = e2.y; ev[10] = e2.z; ev[11] = e2.w; ev[12] = e3.x; ev[13] = e3.y; ev[14] = e3.z; ev[15] = e3.w;
+        r = ladder(ev);
     } else {
         const float *lc = block_ptr(b0);
 #pragma unroll
         for (int q = 0; q < 16; q++) pv[q] = ldg<BYP>(lc + 16 * q + 15);
-#pragma unroll
-        for (int q = 14; q >= 0; q--)
-            if (o + (double) pv[q] * sc > target) seg = q;
+        seg = ladder(pv);
         const float4 *l4 = reinterpret_cast<const float4 *>(lc + 16 * seg);
         const float4 e0 = ldg<BYP>(l4), e1 = ldg<BYP>(l4 + 1), e2 = ldg<BYP>(l4 + 2), e3 = ldg<BYP>(l4 + 3);
         ev[0] = e0.x; ev[1] = e0.y; ev[2] = e0.z; ev[3] = e0.w; ev[4] = e1.x; ev[5] = e1.y; ev[6] = e1.z; ev[7] = e1.w;
         ev[8] = e2.x; ev[9] = e2.y; ev[10] = e2.z; ev[11] = e2.w; ev[12] = e3.x; ev[13] = e3.y; ev[14] = e3.z; ev[15] = e3.w;
+        r = ladder(ev);
     }
-#pragma unroll
-    for (int q = 14; q >= 0; q--)
-        if (o + (double) ev[q] * sc > target) r = q;
     return min((int64_t) b0 * kBlock + 16 * seg + r, n_global - 1);
 }
 

@@ -297,6 +297,8 @@
     const double *offp = h_scan_global ? WS_AT(scan, STEP_WPAR ^ 1) : off;
     if (h_plan && !helper) {
         double Q;
+        ScanSeg seg{0.0, 0.0, 0.0f};
+        bool seg_on = false;
         if (h_scan_global) {
             W = offp[nb + 1];
             Q = offp[nb + 2];
@@ -304,10 +306,14 @@
         } else if (PERSIST && !logw) {
             scan_small(scl, nb, off, W, Q);  // (every wave for itself: no barrier)
         } else {
-            scan_finish(scl, tot, nbg, nb, logw, off, sh_a, sh_q, W, Q, Mx, scan_tab);
+            seg = scan_totals(scl, tot, nbg, nb, logw, off, sh_a, sh_q, W, Q, Mx, scan_tab);
+            seg_on = true;
         }
         const float neff = neff_of(W, Q);  // Neff = 1 / sum((w/W)^2)  (core.cpp:784-788)
         pend = (SPECIAL ? SM.do_resample : U.do_resample != 0) && (neff < (float) U.n_effective);
+        // the exclusive prefix of the totals: only the ancestor search reads it, so only a launch that resamples writes it (uniform);
+        // the barrier below stands between these stores and the search's reads
+        if (seg_on && pend) scan_prefix(seg, nbg, logw, W, off, sh_a);
         if (bid == 0 && threadIdx.x == 0) {
             ctrl->wsum = W;
             ctrl->wsq = Q;
@@ -344,8 +350,11 @@
             return (int) find_ancestor_win<true, true, true>(target, valid, (int) (gk >> 8), offp, nbg, win, WS_AT(lcum, STEP_WPAR ^ 1), nb, ng,
                                                        logw ? WS_AT(blk_w, STEP_WPAR ^ 1) + 2 * nb : nullptr, Mx, nullptr, STEP_WPAR ^ 1);
         // (the typed LDS pointer for the block prefix -- OFFL -- only in the persistent loop: 8.52 -> 8.29 us per iteration at config
-        // 2; in the per-step kernels, which must keep the global-memory prefix of the largest contexts as well, the two copies of
-        // the search cost more than the flat loads: config 3 14.02 -> 14.14 us per step, 10^6 particles 81.3 -> 85.3, same box)
+        // 2; in the GENERAL per-step kernels, which must keep the global-memory prefix of the largest contexts as well, the two copies
+        // of the search cost more than the flat loads: config 3 14.02 -> 14.14 us per step, 10^6 particles 81.3 -> 85.3, same box.
+        // The specialised and counted kernels need no OFFL: where the prefix lives is compiled in -- SM.scan_global -- so `offp` is
+        // `off`, which the compiler knows to be LDS, and the search's probes are ds_read as they stand.  The ancestor WINDOW is read as
+        // LDS in every instantiation: find_ancestor_win types that pointer itself.)
         return (int) find_ancestor_win<false, PERSIST, PERSIST>(target, valid, (int) (gk >> 8), offp, nbg, win, WS_AT(lcum, STEP_WPAR ^ 1), nb, ng,
                                                                 (!DIST && logw) ? WS_AT(blk_w, STEP_WPAR ^ 1) + 2 * nb : nullptr, Mx, DIST ? B.peers : nullptr, STEP_WPAR ^ 1);
     };
@@ -361,7 +370,7 @@
                     W = offp[nb + 1];
                     Q = offp[nb + 2];
                 } else {
-                    scan_finish(scl, tot, nbg, nb, logw, off, sh_a, sh_q, W, Q, Mx, scan_tab);
+                    (void) scan_totals(scl, tot, nbg, nb, logw, off, sh_a, sh_q, W, Q, Mx, scan_tab);  // (no search here: no prefix)
                 }
                 pend = (SPECIAL ? SM.do_resample : U.do_resample != 0) && (neff_of(W, Q) < (float) U.n_effective);
             }
