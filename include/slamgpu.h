@@ -789,6 +789,58 @@ int slamgpu_upload(slamgpu_ctx *ctx, int32_t nf, const float *xv, const float *P
                    const float *Pf4);
 int slamgpu_sync(slamgpu_ctx *ctx);
 
+/* ---- EKF-SLAM on the device: one joint filter, x and the dense P resident in device memory ------------------------------
+ * EKFSLAM::sim (algorithms/ekfslam.cpp:17-43) = predict, heading observation, gated nearest-neighbour or known association,
+ * batch update, augment, in float32, stage by stage what slamhost_ekf_sim computes on the CPU.  A handle of its own, not a
+ * slamgpu_ctx: slamgpu_create keeps refusing the EKF method.  State dimension dim = 3 + 2 nf; P is allocated ONCE at capacity,
+ * row-major with leading dimension ld = 3 + 2 max_landmarks rounded up to a multiple of 32 floats, both triangles stored, and
+ * P == P^T bit for bit after every call.  SLAMGPU_ERR_NO_DEVICE without a GPU (no CPU fallback), SLAMGPU_ERR_ALLOC if P does not fit.
+ *
+ * sim: one EKFSLAM::sim.  With association_known `ids` are the true landmark ids of the nz observations and the handle keeps the
+ *      id -> feature table (persistent, sized by the largest id seen; upload resets it to id f <-> feature f for the uploaded
+ *      features); otherwise ids is ignored and the gates decide.  sim equals the stages below called in order, bit for bit.
+ * associate: labels_out[nz] of EKFSLAM::dataAssociate (ekfslam.cpp:151-189): feature >= 0, SLAMGPU_ASSOC_NEW or
+ *      SLAMGPU_ASSOC_DISCARD.  One synchronisation.
+ * update: EKFSLAM::batchUpdate -> choleskyUpdate (core.cpp:275-291), in chunks of at most 64 observations.  m <= 64 is the
+ *      reference's single batch.  DEVIATION for m > 64 (the reference never has more than 35): the chunks are applied one after
+ *      another in observation order, each linearised at the state the previous chunk left.  A chunk whose innovation covariance
+ *      has a non-positive (or NaN) Cholesky pivot is SKIPPED -- neither x nor P changes -- and SLAMGPU_EKF_STATUS_NOT_PD is
+ *      set (sticky; status reads it); the reference carries on with the broken factor there.
+ * augment: appends n features (ekfslam.cpp:269-323).  More features than max_landmarks: SLAMGPU_ERR_CAPACITY, nothing applied
+ *      by that call.  In sim the check comes before anything is applied when the association is known; with the gates the
+ *      number of new features is known only after the predict and heading stages, which then have been applied (the update
+ *      and the augment have not).
+ * pose: x[0..2] and the 3 x 3 pose block.  state: x[dim] and, unless NULL, P (dim x dim into leading dimension ld_out >= dim);
+ *      returns dim.  block: out[k][k] = P[idx[a]][idx[b]] for k listed state indices (a 20 003-state filter inspected without
+ *      moving 1.6 GB); indices up to the capacity 3 + 2 max_landmarks may be listed: beyond dim lies what was uploaded there, or zeros.  upload: x[dim] and P (leading dimension ld_in); what lies beyond dim in the device's P is left alone.
+ * Bad arguments: SLAMGPU_ERR_INVALID, nothing applied.  What it costs: DESIGN.md section 7h. */
+typedef struct slamgpu_ekf slamgpu_ekf;
+typedef struct {
+    uint32_t struct_size; /* sizeof(slamgpu_ekf_config) */
+    int32_t device;
+    int32_t max_landmarks;
+    int32_t use_heading, batch_update, association_known;
+    float wheel_base, sigma_phi, gate_reject, gate_augment;
+    uint64_t external_stream; /* hipStream_t, 0: a stream of the handle's own */
+} slamgpu_ekf_config;
+#define SLAMGPU_EKF_STATUS_NOT_PD 1 /* a chunk of a batch update was skipped: its innovation covariance had no Cholesky factor */
+int slamgpu_ekf_create(const slamgpu_ekf_config *cfg, slamgpu_ekf **out);
+void slamgpu_ekf_destroy(slamgpu_ekf *e);
+int slamgpu_ekf_sim(slamgpu_ekf *e, float V, float G, const float Q[4], float dt, float phi, const float *z, const int32_t *ids, int32_t nz,
+                    const float Re[4], const float R[4], int32_t observe);
+int slamgpu_ekf_predict(slamgpu_ekf *e, float V, float G, const float Q[4], float dt);
+int slamgpu_ekf_observe_heading(slamgpu_ekf *e, float phi);
+int slamgpu_ekf_associate(slamgpu_ekf *e, const float *z, int32_t nz, const float Re[4], int32_t *labels_out);
+int slamgpu_ekf_update(slamgpu_ekf *e, const float *zf, const int32_t *idf, int32_t m, const float R[4]);
+int slamgpu_ekf_augment(slamgpu_ekf *e, const float *zn, int32_t n, const float Re[4]);
+int slamgpu_ekf_dim(slamgpu_ekf *e);
+int slamgpu_ekf_pose(slamgpu_ekf *e, double xyt[3], double Pvv[9]);
+int slamgpu_ekf_state(slamgpu_ekf *e, float *x, float *P, int32_t ld_out);
+int slamgpu_ekf_block(slamgpu_ekf *e, const int32_t *idx, int32_t k, float *out);
+int slamgpu_ekf_upload(slamgpu_ekf *e, int32_t dim, const float *x, const float *P, int32_t ld_in);
+int slamgpu_ekf_status(slamgpu_ekf *e, int32_t *status);
+int slamgpu_ekf_sync(slamgpu_ekf *e);
+
 /* ---- distributed operation (the multi-GPU path: nothing migrates) ---------------------------------------------------
  * One context per GPU; shard g holds the contiguous global particles [g*n, (g+1)*n), n a multiple of 256; contexts may
  * live in one process (peer access) or one process per GPU (hipIpc).  Every context maps every other shard's state arrays

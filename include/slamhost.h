@@ -58,6 +58,18 @@ slamhost_ekf *slamhost_ekf_create(const slamhost_sim *s);
 void slamhost_ekf_destroy(slamhost_ekf *e);
 int slamhost_ekf_step(slamhost_ekf *e, slamhost_sim *s); /* -1 finished, 0 control step, 1 with observation */
 int slamhost_ekf_state(const slamhost_ekf *e, float *x, float *P, int32_t cap); /* returns dim; P row-major, ld = cap */
+/* The same filter with explicit inputs, so that a device filter (slamgpu.h: the slamgpu_ekf entry points) can be fed exactly what a
+ * host run was fed.  last_inputs: the noisy controls V, G, the heading observation phi and whether slamhost_sim_last_z was observed, as
+ * the last slamhost_ekf_step handed them to EKFSLAM::sim; slamhost_sim_noise: the simulator's Q, R, Qe, Re (slamwrapper.cpp:25-37) and
+ * its control period, any pointer may be NULL.  sim: one EKFSLAM::sim on these inputs (ids: the visible landmark ids, read with
+ * SWITCH_ASSOCIATION_KNOWN only); fed last_inputs and last_z it reproduces slamhost_ekf_step bit for bit.  upload: x[dim] and P
+ * (row-major, leading dimension ld) replace the state; the id table of the known association starts over with id f = feature f
+ * for the uploaded features.  0, or -1 for bad arguments. */
+int slamhost_ekf_last_inputs(const slamhost_ekf *e, float vgphi[3], int32_t *observe);
+int slamhost_sim_noise(const slamhost_sim *s, float Q[4], float R[4], float Qe[4], float Re[4], float *dt);
+int slamhost_ekf_sim(slamhost_ekf *e, float V, float G, const float Q[4], float dt, float phi, const float *z, const int32_t *ids, int32_t nz,
+                     const float Re[4], const float R[4], int32_t observe);
+int slamhost_ekf_upload(slamhost_ekf *e, int32_t dim, const float *x, const float *P, int32_t ld);
 
 /* libc rand() tape in the reference's draw order */
 /* The policy that turns the vote of the gated per-particle association (slamgpu_associate: labels by EKFSLAM::dataAssociate,

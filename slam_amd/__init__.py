@@ -6,5 +6,7 @@ PyTorch fallback: importing works anywhere, but every compute call needs the bui
 from .capi import (Config, ShardPlan, SlamGpu, SlamGpuError, FASTSLAM1, FASTSLAM2, RNG_TAPE, RNG_PHILOX, MATH_STRICT, MATH_FAST,
                    lib_path, load_library, jacobians, kat, device_count, DECLARED_SYMBOLS, DistGroup, dist_comm_id)
 
-__all__ = ["Config", "ShardPlan", "SlamGpu", "SlamGpuError", "FASTSLAM1", "FASTSLAM2", "RNG_TAPE", "RNG_PHILOX", "MATH_STRICT",
+from .ekf import EkfGpu, EkfConfig, EKF_STATUS_NOT_PD
+
+__all__ = ["EkfGpu", "EkfConfig", "EKF_STATUS_NOT_PD", "Config", "ShardPlan", "SlamGpu", "SlamGpuError", "FASTSLAM1", "FASTSLAM2", "RNG_TAPE", "RNG_PHILOX", "MATH_STRICT",
            "MATH_FAST", "lib_path", "load_library", "jacobians", "kat", "device_count", "DECLARED_SYMBOLS", "DistGroup", "dist_comm_id"]

@@ -36,6 +36,9 @@ DECLARED_SYMBOLS = [
     "slamgpu_pose_history_fetch",
     "slamgpu_innovation_summary", "slamgpu_innovation_summary_labels", "slamgpu_innovation_history_enable", "slamgpu_innovation_record", "slamgpu_innovation_history_info",
     "slamgpu_innovation_history_fetch",
+    "slamgpu_ekf_create", "slamgpu_ekf_destroy", "slamgpu_ekf_sim", "slamgpu_ekf_predict", "slamgpu_ekf_observe_heading", "slamgpu_ekf_associate",
+    "slamgpu_ekf_update", "slamgpu_ekf_augment", "slamgpu_ekf_dim", "slamgpu_ekf_pose", "slamgpu_ekf_state", "slamgpu_ekf_block", "slamgpu_ekf_upload",
+    "slamgpu_ekf_status", "slamgpu_ekf_sync",
 ]
 MAP_STRIDE = 9  # SLAMGPU_MAP_STRIDE
 PATH_STRIDE = 7  # SLAMGPU_PATH_STRIDE

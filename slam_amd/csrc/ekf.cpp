@@ -1,0 +1,882 @@
+// EKF-SLAM on the device (include/slamgpu.h: slamgpu_ekf_*): one joint filter, x and the dense P resident in device memory.
+// Kernels and host side in one unit.  The arithmetic restates slam_amd/csrc/host/ekfslam.cpp (itself the restatement of
+// matzipan/slam algorithms/ekfslam.cpp:17-323 and core.cpp:275-317) stage by stage; where the order of a sum or the form of an
+// update differs from the host's, the kernel says so.  The host tracks dim (it knows the labels): no dimension lives on the device.
+#include "slamgpu_ctx.h"
+
+namespace {
+
+constexpr int kEkfBlock = 256;
+constexpr int kChunk = 64;         // observations per chunk of the batch update
+constexpr int kKMax = 2 * kChunk;  // rows of a chunk's innovation: the K extent of the rank update
+constexpr int kTile = 128;         // tile of P per workgroup of ekf_syrk_kernel
+constexpr int kKStep = 32;         // k columns of W1 staged in LDS at a time; a chunk's K is padded with zeros to a multiple of it
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+
+// a chunk of the batch update, by value
+struct EkfObs {
+    float z[2 * kChunk];
+    int32_t idf[kChunk];
+    float R[4];
+    int32_t m;
+};
+
+// the small device work area, by value.  flag: [0] the chunk's factorisation succeeded, [1] sticky status bits, [2] ekf_predict_kernel's ticket
+struct EkfWork {
+    float *H5;  // [kChunk][10]
+    float *v;   // [kKMax] innovation
+    float *t;   // [kKMax] U^-T v
+    float *Ui;  // [kKMax][kKMax] inverse of the upper factor
+    float *hv;  // [2] heading update: innovation, S
+    float *c2;  // [ld] heading update: column 2 of P before it
+    float *Wh;  // [ld] heading update: gain
+    int32_t *flag;
+};
+
+__device__ inline float ekf_trig_offset(float ang) {  // core.cpp:460-477
+    const double pi = 3.14159265358979323846;
+    if (((double) ang < -2 * pi) || ((double) ang > 2 * pi)) {
+        const int n = (int) floor((double) ang / (2 * pi));
+        ang = (float) ((double) ang - n * (2 * pi));
+    }
+    if ((double) ang > pi) ang = (float) ((double) ang - (2 * pi));
+    if ((double) ang < -pi) ang = (float) ((double) ang + (2 * pi));
+    return ang;
+}
+
+// EkfSlam::observe_model: H restricted to its five non-zero columns {0, 1, 2, fpos, fpos + 1}
+__device__ inline void ekf_observe_model(const float *__restrict__ x, int idf, bool want_zp, float zp[2], float H5[10]) {
+#pragma clang fp contract(off)
+    const int fpos = 3 + idf * 2;
+    const float dx = x[fpos] - x[0], dy = x[fpos + 1] - x[1];
+    const float d2 = dx * dx + dy * dy;
+    const float d = sqrtf(d2);
+    const float xd = dx / d, yd = dy / d, xd2 = dx / d2, yd2 = dy / d2;
+    zp[0] = d;
+    zp[1] = want_zp ? atan2f(dy, dx) - x[2] : 0.0f;
+    H5[0] = -xd; H5[1] = -yd; H5[2] = 0; H5[3] = xd; H5[4] = yd;
+    H5[5] = yd2; H5[6] = -xd2; H5[7] = -1; H5[8] = -yd2; H5[9] = xd2;
+}
+
+// 2x2 inverse / determinant through partial-pivot LU, as the host's inverse2
+__device__ inline void ekf_inverse2(const float S[4], float X[4], float *det) {
+#pragma clang fp contract(off)
+    const bool swap = fabsf(S[2]) > fabsf(S[0]);
+    const float u00 = swap ? S[2] : S[0], u01 = swap ? S[3] : S[1];
+    float l10 = swap ? S[0] : S[2];
+    const float r11 = swap ? S[1] : S[3];
+    if (u00 != 0.0f) l10 = l10 * (1.0f / u00);
+    const float u11 = r11 - l10 * u01;
+    float b00 = swap ? 0.0f : 1.0f, b01 = swap ? 1.0f : 0.0f, b10 = swap ? 1.0f : 0.0f, b11 = swap ? 0.0f : 1.0f;
+    b10 -= b00 * l10;
+    b11 -= b01 * l10;
+    float a = 1.0f / u11;
+    b10 *= a;
+    b11 *= a;
+    b00 -= b10 * u01;
+    b01 -= b11 * u01;
+    a = 1.0f / u00;
+    X[0] = b00 * a;
+    X[1] = b01 * a;
+    X[2] = b10;
+    X[3] = b11;
+    *det = (swap ? -1.0f : 1.0f) * (u00 * u11);
+}
+
+// EkfSlam::predict.  The pose rows Gv P[0:3, j] over j >= 3 with their mirror, one lane per column; the workgroup that finishes
+// last (a ticket) then writes the 3x3 pose block and the pose, which every workgroup has read by then
+__global__ void __launch_bounds__(kEkfBlock) ekf_predict_kernel(float *__restrict__ P, int ld, int dim, float *__restrict__ x, float V, float G,
+                                                                 float q00, float q01, float q10, float q11, float dt, float wheel_base,
+                                                                 int32_t *ticket) {
+    const float th = x[2];
+    const float s = sinf(G + th), c = cosf(G + th);
+    const float vts = V * dt * s, vtc = V * dt * c;
+    const int j = 3 + blockIdx.x * kEkfBlock + threadIdx.x;
+    if (j < dim) {
+        const float p0 = P[j], p1 = P[(size_t) ld + j], p2 = P[2 * (size_t) ld + j];
+        const float n0 = p0 + (-vts) * p2, n1 = p1 + vtc * p2;  // Gv = [1 0 -vts; 0 1 vtc; 0 0 1]: row 2 stays
+        P[j] = n0;
+        P[(size_t) ld + j] = n1;
+        P[(size_t) j * ld] = n0;
+        P[(size_t) j * ld + 1] = n1;
+    }
+    __shared__ int last;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        __threadfence();
+        last = atomicAdd(ticket, 1) == (int) gridDim.x - 1;
+    }
+    __syncthreads();
+    if (!last || threadIdx.x != 0) return;
+    *ticket = 0;
+    float Gv[3][3] = {{1, 0, -vts}, {0, 1, vtc}, {0, 0, 1}};
+    float Gu[3][2] = {{dt * c, -vts}, {dt * s, vtc}, {dt * sinf(G) / wheel_base, V * dt * cosf(G) / wheel_base}};
+    const float Q[2][2] = {{q00, q01}, {q10, q11}};
+    float Pvv[3][3], T[3][3], U[3][2];
+#pragma unroll
+    for (int i = 0; i < 3; i++)
+#pragma unroll
+        for (int k = 0; k < 3; k++) Pvv[i][k] = P[(size_t) i * ld + k];
+#pragma unroll
+    for (int i = 0; i < 3; i++) {
+#pragma unroll
+        for (int k = 0; k < 3; k++) {
+            float acc = 0.0f;
+#pragma unroll
+            for (int q = 0; q < 3; q++) acc = acc + Gv[i][q] * Pvv[q][k];
+            T[i][k] = acc;
+        }
+#pragma unroll
+        for (int k = 0; k < 2; k++) {
+            float acc = 0.0f;
+#pragma unroll
+            for (int q = 0; q < 2; q++) acc = acc + Gu[i][q] * Q[q][k];
+            U[i][k] = acc;
+        }
+    }
+    // (the host's dense products leave (i, k) and (k, i) an ulp apart; here the lower triangle is computed and mirrored: P == P^T)
+#pragma unroll
+    for (int i = 0; i < 3; i++)
+#pragma unroll
+        for (int k = 0; k <= i; k++) {
+            float a = 0.0f, b = 0.0f;
+#pragma unroll
+            for (int q = 0; q < 3; q++) a = a + T[i][q] * Gv[k][q];
+#pragma unroll
+            for (int q = 0; q < 2; q++) b = b + U[i][q] * Gu[k][q];
+            P[(size_t) i * ld + k] = a + b;
+            P[(size_t) k * ld + i] = a + b;
+        }
+    x[0] = x[0] + vtc;
+    x[1] = x[1] + vts;
+    x[2] = ekf_trig_offset(th + V * dt * sinf(G) / wheel_base);
+}
+
+// EkfSlam::observe_heading, first half: the gain W = P[:, 2] / (P22 + R), the column it came from and the innovation.  P and x stay
+__global__ void __launch_bounds__(kEkfBlock) ekf_heading_gain_kernel(const float *__restrict__ P, int ld, int dim, const float *__restrict__ x,
+                                                                      float phi, float R, EkfWork w) {
+    const float S = P[2 * (size_t) ld + 2] + R;
+    const float Si = 1.0f / S;
+    const int i = blockIdx.x * kEkfBlock + threadIdx.x;
+    if (i < dim) {
+        const float c = P[2 * (size_t) ld + i];  // row 2 = column 2: P is symmetric bit for bit
+        w.c2[i] = c;
+        w.Wh[i] = c * Si;
+    }
+    if (i == 0) {
+        w.hv[0] = ekf_trig_offset(phi - x[2]);
+        w.hv[1] = S;
+    }
+}
+
+// ... second half: josephUpdate (core.cpp:294-317) with H = e_2^T.  C = I - W H differs from I in column 2 only, so
+// C P C^T + W R W^T + eps I = P - W P[2, :] - P[:, 2] W^T + W (P22 + R) W^T + eps I, ONE element-wise pass over P (the host forms
+// the products densely).  Entry (i, j) and (j, i) evaluate the same expression on commuted operands -- every product and sum
+// rounded on its own, no contraction -- so P stays symmetric bit for bit.  The workgroups of the first row also apply x += W v
+__global__ void __launch_bounds__(kEkfBlock) ekf_heading_kernel(float *__restrict__ P, int ld, int dim, float *__restrict__ x, EkfWork w) {
+    const int j = blockIdx.x * kEkfBlock + threadIdx.x;
+    if (j >= dim) return;
+    const float S = w.hv[1];
+    const float wj = w.Wh[j], cj = w.c2[j];
+    if (blockIdx.y == 0) x[j] = x[j] + wj * w.hv[0];
+    const float eps = (float) 2.2204e-16;
+    for (int i = blockIdx.y; i < dim; i += gridDim.y) {
+        const float wi = w.Wh[i], ci = w.c2[i];
+        const float a = __fmul_rn(wi, cj), b = __fmul_rn(ci, wj);
+        const float q = __fmul_rn(__fmul_rn(wi, wj), S);
+        float p = __fadd_rn(__fsub_rn(P[(size_t) i * ld + j], __fadd_rn(a, b)), q);
+        if (i == j) p = __fadd_rn(p, eps);
+        P[(size_t) i * ld + j] = p;
+    }
+}
+
+// EKFSLAM::dataAssociate (ekfslam.cpp:151-189) as EkfSlam::associate evaluates it, operation by operation (no contraction): one
+// workgroup per observation, its lanes over the features; then the first minimum of nd among the gated pairs, else the plain
+// minimum of nis against the augment gate
+__global__ void __launch_bounds__(kEkfBlock) ekf_gate_kernel(const float *__restrict__ P, int ld, int nf, const float *__restrict__ x,
+                                                              const float *__restrict__ z, float r00, float r01, float r10, float r11,
+                                                              float gate_reject, float gate_augment, int32_t *__restrict__ labels) {
+#pragma clang fp contract(off)
+    const int i = blockIdx.x, tid = threadIdx.x;
+    const float z0 = z[2 * i], z1 = z[2 * i + 1];
+    const float R[4] = {r00, r01, r10, r11};
+    float M[5][5];
+#pragma unroll
+    for (int a = 0; a < 3; a++)
+#pragma unroll
+        for (int b = 0; b < 3; b++) M[a][b] = P[(size_t) a * ld + b];
+    const float inf = __builtin_huge_valf();
+    float nbest = inf, outer = inf;
+    int jbest = -1;
+    for (int j = tid; j < nf; j += kEkfBlock) {
+        float zp[2], H5[10];
+        ekf_observe_model(x, j, true, zp, H5);
+        const float v0 = z0 - zp[0];
+        const float v1 = ekf_trig_offset(z1 - zp[1]);
+        const int f = 3 + 2 * j;
+#pragma unroll
+        for (int a = 0; a < 3; a++)
+#pragma unroll
+            for (int q = 0; q < 2; q++) M[a][3 + q] = M[3 + q][a] = P[(size_t) a * ld + f + q];
+        M[3][3] = P[(size_t) f * ld + f];
+        M[3][4] = M[4][3] = P[(size_t) f * ld + f + 1];
+        M[4][4] = P[(size_t) (f + 1) * ld + f + 1];
+        float HP[2][5];
+#pragma unroll
+        for (int r = 0; r < 2; r++)
+#pragma unroll
+            for (int c = 0; c < 5; c++) {
+                float acc = 0.0f;
+#pragma unroll
+                for (int k = 0; k < 5; k++) acc = acc + H5[5 * r + k] * M[k][c];
+                HP[r][c] = acc;
+            }
+        float S[4];
+#pragma unroll
+        for (int r = 0; r < 2; r++)
+#pragma unroll
+            for (int c = 0; c < 2; c++) {
+                float acc = 0.0f;
+#pragma unroll
+                for (int k = 0; k < 5; k++) acc = acc + HP[r][k] * H5[5 * c + k];
+                S[2 * r + c] = acc + R[2 * r + c];
+            }
+        float Si[4], det;
+        ekf_inverse2(S, Si, &det);
+        const float t0 = v0 * Si[0] + v1 * Si[2], t1 = v0 * Si[1] + v1 * Si[3];
+        const float nis = t0 * v0 + t1 * v1;
+        const float nd = nis + logf(det);
+        if (nis < gate_reject && nd < nbest) {
+            nbest = nd;
+            jbest = j;
+        } else if (nis < outer) {
+            outer = nis;
+        }
+    }
+    __shared__ float s_nd[kEkfBlock], s_out[kEkfBlock];
+    __shared__ int s_j[kEkfBlock];
+    s_nd[tid] = nbest;
+    s_out[tid] = outer;
+    s_j[tid] = jbest;
+    __syncthreads();
+    for (int step = kEkfBlock / 2; step > 0; step >>= 1) {
+        if (tid < step) {
+            const float nb = s_nd[tid + step], ob = s_out[tid + step];
+            const int jb = s_j[tid + step];
+            // (a lane holds the first minimum of its own features; between lanes the lower feature wins a tie)
+            if (jb >= 0 && (s_j[tid] < 0 || nb < s_nd[tid] || (nb == s_nd[tid] && jb < s_j[tid]))) {
+                s_nd[tid] = nb;
+                s_j[tid] = jb;
+            }
+            if (ob < s_out[tid]) s_out[tid] = ob;
+        }
+        __syncthreads();
+    }
+    if (tid == 0) labels[i] = s_j[0] >= 0 ? s_j[0] : (s_out[0] > gate_augment ? SLAMGPU_ASSOC_NEW : SLAMGPU_ASSOC_DISCARD);
+}
+
+// EkfSlam::batch_update, a chunk: H5, the innovation v (workgroup column 0) and PHt[2i + a][r] = sum_k H5_i[a][k] P[cols_i[k]][r], k
+// ascending as the host's mulT(P, H).  Five ROWS of P per observation, coalesced along r: symmetry makes them the columns.  PHt is
+// stored k-major, [kKMax][ld]
+__global__ void __launch_bounds__(kEkfBlock) ekf_innov_kernel(const float *__restrict__ P, int ld, int dim, const float *__restrict__ x, EkfObs O,
+                                                               float *__restrict__ PHt, EkfWork w) {
+    const int i = blockIdx.y, r = blockIdx.x * kEkfBlock + threadIdx.x;
+    const int idf = O.idf[i];
+    const bool writer = blockIdx.x == 0 && threadIdx.x == 0;
+    float zp[2], H5[10];
+    ekf_observe_model(x, idf, writer, zp, H5);
+    if (writer) {
+#pragma unroll
+        for (int k = 0; k < 10; k++) w.H5[10 * i + k] = H5[k];
+        w.v[2 * i] = O.z[2 * i] - zp[0];
+        w.v[2 * i + 1] = ekf_trig_offset(O.z[2 * i + 1] - zp[1]);
+    }
+    if (r >= dim) return;
+    const size_t f = 3 + 2 * (size_t) idf;
+    const float p[5] = {P[r], P[(size_t) ld + r], P[2 * (size_t) ld + r], P[f * ld + r], P[(f + 1) * ld + r]};
+#pragma unroll
+    for (int a = 0; a < 2; a++) {
+        float acc = 0.0f;
+#pragma unroll
+        for (int k = 0; k < 5; k++) acc = acc + p[k] * H5[5 * a + k];
+        PHt[(size_t) (2 * i + a) * ld + r] = acc;
+    }
+}
+
+// ... S = H PHt + R with the host's in-place symmetrisation (the factorisation reads the lower triangle: the true average), then the
+// host's llt_lower, upper_inverse and t = U^-T v in ONE workgroup with S in LDS.  The lower triangle holds L, the strictly upper one
+// the inverse of U = L^T (upper triangular itself; its diagonal is 1 / L's).  Rows are rotated by their index so that neither a walk
+// along a row nor one down a column meets a bank twice.  A pivot that is not positive: flag[0] = 0 -- the chunk's gain and rank
+// update do nothing -- and SLAMGPU_EKF_STATUS_NOT_PD
+__global__ void __launch_bounds__(kEkfBlock) ekf_chol_kernel(const float *__restrict__ PHt, int ld, EkfObs O, EkfWork w) {
+    __shared__ float A[kKMax * kKMax];  // (all of the 64 KB a workgroup may declare: the pivot's verdict travels in the diagonal itself)
+    bool bad = false;
+    const int tid = threadIdx.x, n = 2 * O.m;
+#define AT(i, j) A[(i) * kKMax + (((i) + (j)) & (kKMax - 1))]
+    for (int e = tid; e < n * n; e += kEkfBlock) {
+        const int a = e / n, b = e - a * n;
+        const float *h = w.H5 + 10 * (a >> 1) + 5 * (a & 1);
+        const size_t f = 3 + 2 * (size_t) O.idf[a >> 1];
+        const float *row = PHt + (size_t) b * ld;
+        float acc = 0.0f;
+        acc = acc + h[0] * row[0];
+        acc = acc + h[1] * row[1];
+        acc = acc + h[2] * row[2];
+        acc = acc + h[3] * row[f];
+        acc = acc + h[4] * row[f + 1];
+        AT(a, b) = acc + (((a >> 1) == (b >> 1)) ? O.R[2 * (a & 1) + (b & 1)] : 0.0f);
+    }
+    __syncthreads();
+    for (int e = tid; e < n * n; e += kEkfBlock) {
+        const int a = e / n, b = e - a * n;
+        if (a > b) {
+            AT(a, b) = (AT(a, b) + AT(b, a)) * 0.5f;
+            AT(b, a) = 0.0f;
+        }
+    }
+    __syncthreads();
+    for (int k = 0; k < n; k++) {
+        float acc = 0.0f;
+        if (tid == k) {
+            float xk = AT(k, k);
+            if (k > 0) {
+                float sq = AT(k, 0) * AT(k, 0);
+                for (int j = 1; j < k; j++) sq = sq + AT(k, j) * AT(k, j);
+                xk = xk - sq;
+            }
+            AT(k, k) = xk > 0.0f ? sqrtf(xk) : -1.0f;  // (NaN fails the test too)
+        } else if (tid > k && tid < n) {
+            acc = AT(tid, k);
+            for (int j = 0; j < k; j++) acc = acc + AT(tid, j) * (-1.0f * AT(k, j));
+        }
+        __syncthreads();
+        const float dk = AT(k, k);
+        bad = dk < 0.0f;
+        if (bad) break;
+        if (tid > k && tid < n) AT(tid, k) = acc * (1.0f / dk);
+        __syncthreads();
+    }
+    if (bad) {
+        if (tid == 0) {
+            w.flag[0] = 0;
+            atomicOr(&w.flag[1], SLAMGPU_EKF_STATUS_NOT_PD);
+        }
+        return;
+    }
+    // upper_inverse: column j of X = U^-1 belongs to lane j alone
+    if (tid < n) {
+        const int j = tid;
+        for (int i = n - 1; i >= 0; i--) {
+            if (j < i) continue;  // (X(i, j) is an exact zero there: the host multiplies and subtracts zeros)
+            const float a = 1.0f / AT(i, i);
+            const float b = j == i ? a : AT(i, j) * a;
+            if (j > i) AT(i, j) = b;
+            for (int r = 0; r < i; r++) AT(r, j) = AT(r, j) - b * AT(i, r);
+        }
+        float acc = 0.0f;
+        for (int k = 0; k <= j; k++) {
+            const float xkj = k == j ? 1.0f / AT(j, j) : AT(k, j);
+            w.Ui[k * kKMax + j] = xkj;
+            acc = acc + xkj * w.v[k];
+        }
+        for (int k = j + 1; k < n; k++) w.Ui[k * kKMax + j] = 0.0f;
+        w.t[j] = acc;
+    }
+    if (tid == 0) w.flag[0] = 1;
+#undef AT
+}
+
+// ... W1 = PHt U^-1 (k ascending, as the host's mul) and x += W1 t (the host forms W = W1 U^-T and W v: the same sum, associated
+// the other way).  32 state rows per workgroup; W1 is stored [rows][kKMax], zero in columns n .. npad - 1
+__global__ void __launch_bounds__(kEkfBlock) ekf_gain_kernel(const float *__restrict__ PHt, int ld, int dim, float *__restrict__ x, int n, int npad,
+                                                              float *__restrict__ W1, EkfWork w) {
+    if (!w.flag[0]) return;
+    __shared__ float Ps[kKMax][32];
+    __shared__ float Ws[32][kKMax + 1];
+    const int tid = threadIdx.x, lr = tid & 31, q = tid >> 5;
+    const int r0 = blockIdx.x * 32, r = r0 + lr;
+    for (int k = q; k < n; k += 8) Ps[k][lr] = r < dim ? PHt[(size_t) k * ld + r] : 0.0f;
+    __syncthreads();
+    for (int c = q; c < npad; c += 8) {
+        float acc = 0.0f;
+        if (c < n)
+            for (int k = 0; k <= c; k++) acc = acc + Ps[k][lr] * w.Ui[k * kKMax + c];
+        Ws[lr][c] = acc;
+    }
+    __syncthreads();
+    for (int e = tid; e < 32 * npad; e += kEkfBlock) {
+        const int row = e / npad, c = e - row * npad;
+        if (r0 + row < dim) W1[(size_t) (r0 + row) * kKMax + c] = Ws[row][c];
+    }
+    if (q == 0 && r < dim) {
+        float acc = 0.0f;
+        for (int c = 0; c < n; c++) acc = acc + Ws[lr][c] * w.t[c];
+        x[r] = x[r] + acc;
+    }
+}
+
+// ... P -= W1 W1^T on the exact-float32 MFMA (v_mfma_f32_32x32x2_f32: a k-ordered f32 fma chain per element).  A 128 x 128 tile of P
+// per workgroup, 64 x 64 per wave = 2 x 2 accumulators of 16 registers; the two W1 panels are staged in LDS kKStep k columns at a
+// time, k-major, so that a lane's operand is one conflict-free read.  Only tiles on or below the diagonal are computed; an
+// off-diagonal tile is written twice, the second time transposed, and inside a diagonal tile (i, j) and (j, i) are the same chain
+// on commuted products: P == P^T bit for bit.  Rows and columns >= dim of P are neither read nor written; W1's rows there
+// (allocated, never data) only reach accumulators that are not stored
+__global__ void __launch_bounds__(kEkfBlock) ekf_syrk_kernel(float *__restrict__ P, int ld, int dim, const float *__restrict__ W1, int npad,
+                                                              const int32_t *__restrict__ flag) {
+    const int bi = blockIdx.y, bj = blockIdx.x;
+    if (bj > bi || !flag[0]) return;
+    __shared__ float As[kKStep][kTile + 4], Bs[kKStep][kTile + 4];
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int wi = wave >> 1, wj = wave & 1, li = lane & 31, h = lane >> 5;
+    const int I0 = bi * kTile, J0 = bj * kTile;
+    f32x16 acc[2][2];
+#pragma unroll
+    for (int a = 0; a < 2; a++)
+#pragma unroll
+        for (int b = 0; b < 2; b++)
+#pragma unroll
+            for (int g = 0; g < 16; g++) acc[a][b][g] = 0.0f;
+    for (int kc = 0; kc < npad; kc += kKStep) {
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+            const int idx = tid + kEkfBlock * q, row = idx >> 3, k4 = (idx & 7) * 4;
+            const float4 a = *reinterpret_cast<const float4 *>(W1 + (size_t) (I0 + row) * kKMax + kc + k4);
+            const float4 b = *reinterpret_cast<const float4 *>(W1 + (size_t) (J0 + row) * kKMax + kc + k4);
+            As[k4][row] = a.x; As[k4 + 1][row] = a.y; As[k4 + 2][row] = a.z; As[k4 + 3][row] = a.w;
+            Bs[k4][row] = b.x; Bs[k4 + 1][row] = b.y; Bs[k4 + 2][row] = b.z; Bs[k4 + 3][row] = b.w;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int kk = 0; kk < kKStep; kk += 2) {
+            const float a0 = As[kk + h][wi * 64 + li], a1 = As[kk + h][wi * 64 + 32 + li];
+            const float b0 = Bs[kk + h][wj * 64 + li], b1 = Bs[kk + h][wj * 64 + 32 + li];
+            acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc[0][0], 0, 0, 0);
+            acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b1, acc[0][1], 0, 0, 0);
+            acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b0, acc[1][0], 0, 0, 0);
+            acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, acc[1][1], 0, 0, 0);
+        }
+        __syncthreads();
+    }
+    // accumulator register g of lane (li, h): row (g & 3) + 8 (g >> 2) + 4 h, column li of its 32 x 32 tile
+#pragma unroll
+    for (int a = 0; a < 2; a++)
+#pragma unroll
+        for (int b = 0; b < 2; b++) {
+            const int col = J0 + wj * 64 + b * 32 + li;
+            if (col >= dim) continue;
+#pragma unroll
+            for (int g4 = 0; g4 < 4; g4++) {
+                const int row0 = I0 + wi * 64 + a * 32 + 8 * g4 + 4 * h;
+                float p[4];
+#pragma unroll
+                for (int e = 0; e < 4; e++)
+                    if (row0 + e < dim) {
+                        p[e] = P[(size_t) (row0 + e) * ld + col] - acc[a][b][4 * g4 + e];
+                        P[(size_t) (row0 + e) * ld + col] = p[e];
+                    }
+                if (bi == bj) continue;
+                if (row0 + 3 < dim) {
+                    *reinterpret_cast<float4 *>(P + (size_t) col * ld + row0) = make_float4(p[0], p[1], p[2], p[3]);
+                } else {
+#pragma unroll
+                    for (int e = 0; e < 4; e++)
+                        if (row0 + e < dim) P[(size_t) col * ld + row0 + e] = p[e];
+                }
+            }
+        }
+}
+
+// EkfSlam::augment, one feature appended at len: the two new rows and columns Gv P[0:3, :] with Gv = [1 0 -r s; 0 1 r c], the
+// 2x2 block and the feature itself
+__global__ void __launch_bounds__(kEkfBlock) ekf_augment_kernel(float *__restrict__ P, int ld, int len, float *__restrict__ x, float r, float b,
+                                                                 float re00, float re01, float re10, float re11) {
+    const float s = sinf(x[2] + b), c = cosf(x[2] + b);
+    const float g02 = -r * s, g12 = r * c;
+    const int j = blockIdx.x * kEkfBlock + threadIdx.x;
+    if (j < len) {
+        const float p0 = P[j], p1 = P[(size_t) ld + j], p2 = P[2 * (size_t) ld + j];
+        const float d0 = p0 + g02 * p2, d1 = p1 + g12 * p2;
+        P[(size_t) len * ld + j] = d0;
+        P[(size_t) (len + 1) * ld + j] = d1;
+        P[(size_t) j * ld + len] = d0;
+        P[(size_t) j * ld + len + 1] = d1;
+    }
+    if (j != 0) return;
+    x[len] = x[0] + r * c;
+    x[len + 1] = x[1] + r * s;
+    const float Gv[2][3] = {{1, 0, g02}, {0, 1, g12}};
+    const float Gz[2][2] = {{c, g02}, {s, g12}};
+    const float Re[2][2] = {{re00, re01}, {re10, re11}};
+    float T[2][3], U[2][2];
+#pragma unroll
+    for (int i = 0; i < 2; i++) {
+#pragma unroll
+        for (int k = 0; k < 3; k++) {
+            float acc = 0.0f;
+#pragma unroll
+            for (int q = 0; q < 3; q++) acc = acc + Gv[i][q] * P[(size_t) q * ld + k];
+            T[i][k] = acc;
+        }
+#pragma unroll
+        for (int k = 0; k < 2; k++) {
+            float acc = 0.0f;
+#pragma unroll
+            for (int q = 0; q < 2; q++) acc = acc + Gz[i][q] * Re[q][k];
+            U[i][k] = acc;
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < 2; i++)
+#pragma unroll
+        for (int k = 0; k <= i; k++) {  // (the lower triangle, mirrored, as in ekf_predict_kernel)
+            float a2 = 0.0f, b2 = 0.0f;
+#pragma unroll
+            for (int q = 0; q < 3; q++) a2 = a2 + T[i][q] * Gv[k][q];
+#pragma unroll
+            for (int q = 0; q < 2; q++) b2 = b2 + U[i][q] * Gz[k][q];
+            P[(size_t) (len + i) * ld + len + k] = a2 + b2;
+            P[(size_t) (len + k) * ld + len + i] = a2 + b2;
+        }
+}
+
+// slamgpu_ekf_block: out[a][b] = P[idx[a]][idx[b]]
+__global__ void __launch_bounds__(kEkfBlock) ekf_block_kernel(const float *__restrict__ P, int ld, const int32_t *__restrict__ idx, int k,
+                                                               float *__restrict__ out) {
+    const size_t e = (size_t) blockIdx.x * kEkfBlock + threadIdx.x;
+    if (e >= (size_t) k * k) return;
+    const int a = (int) (e / k), b = (int) (e - (size_t) a * k);
+    out[e] = P[(size_t) idx[a] * ld + idx[b]];
+}
+
+}  // namespace
+
+struct slamgpu_ekf {
+    slamgpu_ekf_config cfg{};
+    hipStream_t stream = nullptr;
+    bool own_stream = true;
+    int dim = 3, ld = 0, cap_dim = 0;
+    DevBuf<float> P, x, PHt, W1, work, z_dev, blk_dev;
+    DevBuf<int32_t> flag, lab_dev, idx_dev;
+    PinBuf<char> pin;
+    EkfWork w{};
+    std::vector<int32_t> table;  // association_known: id -> feature, -1 not seen yet
+};
+
+namespace {
+
+int ekf_check(slamgpu_ekf *e) {
+    if (!e) return fail(SLAMGPU_ERR_INVALID, "null EKF handle");
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    return 0;
+}
+
+int ekf_launched(const char *what) {
+    const hipError_t err = hipGetLastError();
+    if (err != hipSuccess) return fail(SLAMGPU_ERR_HIP, "%s launch: %s", what, hipGetErrorString(err));
+    return 0;
+}
+
+inline int nf_of(const slamgpu_ekf *e) { return (e->dim - 3) / 2; }
+
+int ekf_predict(slamgpu_ekf *e, float V, float G, const float Q[4], float dt) {
+    const int nb = std::max(1, (e->dim - 3 + kEkfBlock - 1) / kEkfBlock);
+    ekf_predict_kernel<<<nb, kEkfBlock, 0, e->stream>>>(e->P, e->ld, e->dim, e->x, V, G, Q[0], Q[1], Q[2], Q[3], dt, e->cfg.wheel_base, e->flag.p + 2);
+    return ekf_launched("ekf_predict_kernel");
+}
+
+int ekf_heading(slamgpu_ekf *e, float phi) {
+    const float R = (float) std::pow((double) e->cfg.sigma_phi, 2);
+    const int nb = (e->dim + kEkfBlock - 1) / kEkfBlock;
+    ekf_heading_gain_kernel<<<nb, kEkfBlock, 0, e->stream>>>(e->P, e->ld, e->dim, e->x, phi, R, e->w);
+    if (int rc = ekf_launched("ekf_heading_gain_kernel")) return rc;
+    ekf_heading_kernel<<<dim3(nb, std::min(e->dim, 16384)), kEkfBlock, 0, e->stream>>>(e->P, e->ld, e->dim, e->x, e->w);
+    return ekf_launched("ekf_heading_kernel");
+}
+
+// labels of the gates for z[nz] against the state as it stands: one synchronisation
+int ekf_associate(slamgpu_ekf *e, const float *z, int32_t nz, const float Re[4], int32_t *labels) {
+    if (nz == 0) return 0;
+    if (int rc = e->z_dev.reserve(2 * (size_t) nz, "EKF observations")) return rc;
+    if (int rc = e->lab_dev.reserve((size_t) nz, "EKF labels")) return rc;
+    if (int rc = e->pin.reserve(12 * (size_t) nz, "EKF association staging")) return rc;
+    float *zh = reinterpret_cast<float *>(e->pin.p);
+    int32_t *lh = reinterpret_cast<int32_t *>(e->pin.p + 8 * (size_t) nz);
+    memcpy(zh, z, 8 * (size_t) nz);
+    HIP_TRY(hipMemcpyAsync(e->z_dev, zh, 8 * (size_t) nz, hipMemcpyHostToDevice, e->stream));
+    ekf_gate_kernel<<<nz, kEkfBlock, 0, e->stream>>>(e->P, e->ld, nf_of(e), e->x, e->z_dev, Re[0], Re[1], Re[2], Re[3], e->cfg.gate_reject,
+                                                      e->cfg.gate_augment, e->lab_dev);
+    if (int rc = ekf_launched("ekf_gate_kernel")) return rc;
+    HIP_TRY(hipMemcpyAsync(lh, e->lab_dev, 4 * (size_t) nz, hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    memcpy(labels, lh, 4 * (size_t) nz);
+    return 0;
+}
+
+int ekf_update(slamgpu_ekf *e, const float *zf, const int32_t *idf, int32_t m, const float R[4]) {
+    const int nf = nf_of(e);
+    for (int32_t i = 0; i < m; i++)
+        if (idf[i] < 0 || idf[i] >= nf) return fail(SLAMGPU_ERR_INVALID, "idf[%d] = %d outside [0, %d)", i, idf[i], nf);
+    for (int32_t at = 0; at < m; at += kChunk) {
+        EkfObs O{};
+        O.m = std::min(kChunk, m - at);
+        memcpy(O.z, zf + 2 * (size_t) at, 8 * (size_t) O.m);
+        memcpy(O.idf, idf + at, 4 * (size_t) O.m);
+        memcpy(O.R, R, 16);
+        const int n = 2 * O.m, npad = (n + kKStep - 1) / kKStep * kKStep;
+        ekf_innov_kernel<<<dim3((e->dim + kEkfBlock - 1) / kEkfBlock, O.m), kEkfBlock, 0, e->stream>>>(e->P, e->ld, e->dim, e->x, O, e->PHt, e->w);
+        if (int rc = ekf_launched("ekf_innov_kernel")) return rc;
+        ekf_chol_kernel<<<1, kEkfBlock, 0, e->stream>>>(e->PHt, e->ld, O, e->w);
+        if (int rc = ekf_launched("ekf_chol_kernel")) return rc;
+        ekf_gain_kernel<<<(e->dim + 31) / 32, kEkfBlock, 0, e->stream>>>(e->PHt, e->ld, e->dim, e->x, n, npad, e->W1, e->w);
+        if (int rc = ekf_launched("ekf_gain_kernel")) return rc;
+        const int tiles = (e->dim + kTile - 1) / kTile;
+        ekf_syrk_kernel<<<dim3(tiles, tiles), kEkfBlock, 0, e->stream>>>(e->P, e->ld, e->dim, e->W1, npad, e->flag);
+        if (int rc = ekf_launched("ekf_syrk_kernel")) return rc;
+    }
+    return 0;
+}
+
+int ekf_augment(slamgpu_ekf *e, const float *zn, int32_t n, const float Re[4]) {
+    if (nf_of(e) + n > e->cfg.max_landmarks)
+        return fail(SLAMGPU_ERR_CAPACITY, "%d features + %d new exceed max_landmarks %d", nf_of(e), n, e->cfg.max_landmarks);
+    for (int32_t q = 0; q < n; q++) {  // serial by nature: each feature's rows start from the pose rows, which the previous one left alone
+        ekf_augment_kernel<<<(e->dim + kEkfBlock - 1) / kEkfBlock, kEkfBlock, 0, e->stream>>>(e->P, e->ld, e->dim, e->x, zn[2 * q], zn[2 * q + 1], Re[0],
+                                                                                              Re[1], Re[2], Re[3]);
+        if (int rc = ekf_launched("ekf_augment_kernel")) return rc;
+        e->dim += 2;
+    }
+    return 0;
+}
+
+void ekf_release(slamgpu_ekf *e) {
+    e->P.release();
+    e->x.release();
+    e->PHt.release();
+    e->W1.release();
+    e->work.release();
+    e->z_dev.release();
+    e->blk_dev.release();
+    e->flag.release();
+    e->lab_dev.release();
+    e->idx_dev.release();
+    e->pin.release();
+    if (e->own_stream && e->stream) (void) hipStreamDestroy(e->stream);
+    delete e;
+}
+
+int ekf_reserve(slamgpu_ekf *e) {
+    if (e->own_stream) HIP_TRY(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking));
+    const size_t ld = (size_t) e->ld, rows = ((size_t) e->cap_dim + kTile - 1) / kTile * kTile;
+    if (int rc = e->P.reserve_zeroed(ld * e->cap_dim, "EKF covariance P")) return rc;
+    if (int rc = e->x.reserve_zeroed(ld, "EKF state x")) return rc;
+    if (int rc = e->PHt.reserve_zeroed(ld * kKMax, "EKF P H^T")) return rc;
+    if (int rc = e->W1.reserve_zeroed(rows * kKMax, "EKF W1")) return rc;
+    Layout L;
+    const auto H5 = L.take<float>(10 * kChunk), v = L.take<float>(kKMax), t = L.take<float>(kKMax), Ui = L.take<float>(kKMax * kKMax),
+               hv = L.take<float>(2), c2 = L.take<float>(ld), Wh = L.take<float>(ld);
+    if (int rc = e->work.reserve_zeroed(L.total() / sizeof(float), "EKF work area")) return rc;
+    if (int rc = e->flag.reserve_zeroed(4, "EKF flags")) return rc;
+    char *base = reinterpret_cast<char *>(e->work.p);
+    auto at = [&](size_t off) { return reinterpret_cast<float *>(base + off); };
+    e->w = EkfWork{at(H5.off), at(v.off), at(t.off), at(Ui.off), at(hv.off), at(c2.off), at(Wh.off), e->flag.p};
+    if (int rc = e->pin.reserve(4096, "EKF staging")) return rc;
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int slamgpu_ekf_create(const slamgpu_ekf_config *cfg, slamgpu_ekf **out) {
+    if (!cfg || !out) return fail(SLAMGPU_ERR_INVALID, "null argument");
+    *out = nullptr;
+    if (cfg->struct_size != sizeof(slamgpu_ekf_config))
+        return fail(SLAMGPU_ERR_INVALID, "slamgpu_ekf_config.struct_size %u != %zu (ABI mismatch)", cfg->struct_size, sizeof(slamgpu_ekf_config));
+    if (cfg->max_landmarks < 0 || cfg->max_landmarks > 32000) return fail(SLAMGPU_ERR_INVALID, "max_landmarks %d outside [0, 32000]", cfg->max_landmarks);
+    if (!(cfg->wheel_base > 0.0f) || !(cfg->sigma_phi >= 0.0f) || !(cfg->gate_reject >= 0.0f) || !(cfg->gate_augment >= 0.0f))
+        return fail(SLAMGPU_ERR_INVALID, "wheel_base must be positive, sigma_phi and the gates non-negative");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(SLAMGPU_ERR_NO_DEVICE, "no HIP device: libslamgpu has no CPU fallback");
+    if (cfg->device < 0 || cfg->device >= ndev) return fail(SLAMGPU_ERR_INVALID, "device %d out of range (%d devices)", cfg->device, ndev);
+    HIP_TRY(hipSetDevice(cfg->device));
+    slamgpu_ekf *e = new slamgpu_ekf();
+    e->cfg = *cfg;
+    e->cap_dim = 3 + 2 * cfg->max_landmarks;
+    e->ld = (e->cap_dim + 31) / 32 * 32;
+    if (cfg->external_stream) {
+        e->stream = reinterpret_cast<hipStream_t>(cfg->external_stream);
+        e->own_stream = false;
+    }
+    if (int rc = ekf_reserve(e)) {
+        ekf_release(e);
+        return rc;
+    }
+    *out = e;
+    return 0;
+}
+
+void slamgpu_ekf_destroy(slamgpu_ekf *e) {
+    if (!e) return;
+    (void) hipSetDevice(e->cfg.device);
+    if (e->stream) (void) hipStreamSynchronize(e->stream);
+    ekf_release(e);
+}
+
+int slamgpu_ekf_predict(slamgpu_ekf *e, float V, float G, const float Q[4], float dt) {
+    if (int rc = ekf_check(e)) return rc;
+    if (!Q) return fail(SLAMGPU_ERR_INVALID, "null Q");
+    return ekf_predict(e, V, G, Q, dt);
+}
+
+int slamgpu_ekf_observe_heading(slamgpu_ekf *e, float phi) {
+    if (int rc = ekf_check(e)) return rc;
+    return ekf_heading(e, phi);
+}
+
+int slamgpu_ekf_associate(slamgpu_ekf *e, const float *z, int32_t nz, const float Re[4], int32_t *labels_out) {
+    if (int rc = ekf_check(e)) return rc;
+    if (nz < 0 || !Re || (nz > 0 && (!z || !labels_out))) return fail(SLAMGPU_ERR_INVALID, "bad association arguments");
+    return ekf_associate(e, z, nz, Re, labels_out);
+}
+
+int slamgpu_ekf_update(slamgpu_ekf *e, const float *zf, const int32_t *idf, int32_t m, const float R[4]) {
+    if (int rc = ekf_check(e)) return rc;
+    if (m < 0 || !R || (m > 0 && (!zf || !idf))) return fail(SLAMGPU_ERR_INVALID, "bad update arguments");
+    return ekf_update(e, zf, idf, m, R);
+}
+
+int slamgpu_ekf_augment(slamgpu_ekf *e, const float *zn, int32_t n, const float Re[4]) {
+    if (int rc = ekf_check(e)) return rc;
+    if (n < 0 || !Re || (n > 0 && !zn)) return fail(SLAMGPU_ERR_INVALID, "bad augment arguments");
+    return ekf_augment(e, zn, n, Re);
+}
+
+int slamgpu_ekf_sim(slamgpu_ekf *e, float V, float G, const float Q[4], float dt, float phi, const float *z, const int32_t *ids, int32_t nz,
+                    const float Re[4], const float R[4], int32_t observe) {
+    if (int rc = ekf_check(e)) return rc;
+    if (!Q) return fail(SLAMGPU_ERR_INVALID, "null Q");
+    const bool known = e->cfg.association_known != 0;
+    if (observe && (nz < 0 || !Re || !R || (nz > 0 && (!z || (known && !ids))))) return fail(SLAMGPU_ERR_INVALID, "bad observation arguments");
+    std::vector<float> zf, zn;
+    std::vector<int32_t> idf, idn;
+    if (observe && known) {  // EkfSlam::associate_known: it does not look at the state, so the capacity is checked before anything runs
+        for (int32_t i = 0; i < nz; i++) {
+            if (ids[i] < 0) return fail(SLAMGPU_ERR_INVALID, "ids[%d] = %d", i, ids[i]);
+            if ((size_t) ids[i] >= e->table.size()) e->table.resize((size_t) ids[i] + 1, -1);
+            const int32_t f = e->table[ids[i]];
+            if (f < 0) {
+                zn.insert(zn.end(), {z[2 * i], z[2 * i + 1]});
+                idn.push_back(ids[i]);
+            } else {
+                zf.insert(zf.end(), {z[2 * i], z[2 * i + 1]});
+                idf.push_back(f);
+            }
+        }
+        if (nf_of(e) + (int) idn.size() > e->cfg.max_landmarks)
+            return fail(SLAMGPU_ERR_CAPACITY, "%d features + %d new exceed max_landmarks %d", nf_of(e), (int) idn.size(), e->cfg.max_landmarks);
+    }
+    if (int rc = ekf_predict(e, V, G, Q, dt)) return rc;
+    if (e->cfg.use_heading)
+        if (int rc = ekf_heading(e, phi)) return rc;
+    if (!observe) return 0;
+    if (!known) {
+        std::vector<int32_t> lab((size_t) nz);
+        if (int rc = ekf_associate(e, z, nz, Re, lab.data())) return rc;
+        for (int32_t i = 0; i < nz; i++) {
+            if (lab[i] >= 0) {
+                zf.insert(zf.end(), {z[2 * i], z[2 * i + 1]});
+                idf.push_back(lab[i]);
+            } else if (lab[i] == SLAMGPU_ASSOC_NEW) {
+                zn.insert(zn.end(), {z[2 * i], z[2 * i + 1]});
+            }
+        }
+        if (nf_of(e) + (int) (zn.size() / 2) > e->cfg.max_landmarks)
+            return fail(SLAMGPU_ERR_CAPACITY, "%d features + %d new exceed max_landmarks %d (the predict and heading stages have been applied)", nf_of(e),
+                        (int) (zn.size() / 2), e->cfg.max_landmarks);
+    }
+    const int nf0 = nf_of(e);
+    if (e->cfg.batch_update)
+        if (int rc = ekf_update(e, zf.data(), idf.data(), (int32_t) idf.size(), R)) return rc;
+    if (int rc = ekf_augment(e, zn.data(), (int32_t) (zn.size() / 2), Re)) return rc;
+    for (size_t i = 0; i < idn.size(); i++) e->table[idn[i]] = nf0 + (int32_t) i;
+    return 0;
+}
+
+int slamgpu_ekf_dim(slamgpu_ekf *e) {
+    if (!e) return fail(SLAMGPU_ERR_INVALID, "null EKF handle");
+    return e->dim;
+}
+
+int slamgpu_ekf_pose(slamgpu_ekf *e, double xyt[3], double Pvv[9]) {
+    if (int rc = ekf_check(e)) return rc;
+    if (!xyt && !Pvv) return fail(SLAMGPU_ERR_INVALID, "null outputs");
+    float *h = reinterpret_cast<float *>(e->pin.p);
+    HIP_TRY(hipMemcpyAsync(h, e->x, 12, hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipMemcpy2DAsync(h + 3, 12, e->P, sizeof(float) * (size_t) e->ld, 12, 3, hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    for (int i = 0; i < 3 && xyt; i++) xyt[i] = h[i];
+    for (int i = 0; i < 9 && Pvv; i++) Pvv[i] = h[3 + i];
+    return 0;
+}
+
+int slamgpu_ekf_state(slamgpu_ekf *e, float *x, float *P, int32_t ld_out) {
+    if (int rc = ekf_check(e)) return rc;
+    if (P && ld_out < e->dim) return fail(SLAMGPU_ERR_INVALID, "ld_out %d < dim %d", ld_out, e->dim);
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    if (x) HIP_TRY(hipMemcpy(x, e->x, sizeof(float) * (size_t) e->dim, hipMemcpyDeviceToHost));
+    if (P)
+        HIP_TRY(hipMemcpy2D(P, sizeof(float) * (size_t) ld_out, e->P, sizeof(float) * (size_t) e->ld, sizeof(float) * (size_t) e->dim, (size_t) e->dim,
+                            hipMemcpyDeviceToHost));
+    return e->dim;
+}
+
+int slamgpu_ekf_block(slamgpu_ekf *e, const int32_t *idx, int32_t k, float *out) {
+    if (int rc = ekf_check(e)) return rc;
+    if (k < 0 || (k > 0 && (!idx || !out))) return fail(SLAMGPU_ERR_INVALID, "bad block arguments");
+    for (int32_t a = 0; a < k; a++)
+        if (idx[a] < 0 || idx[a] >= e->cap_dim) return fail(SLAMGPU_ERR_INVALID, "idx[%d] = %d outside [0, %d)", a, idx[a], e->cap_dim);
+    if (k == 0) return 0;
+    const size_t kk = (size_t) k * k;
+    if (int rc = e->idx_dev.reserve((size_t) k, "EKF block indices")) return rc;
+    if (int rc = e->blk_dev.reserve(kk, "EKF block")) return rc;
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    HIP_TRY(hipMemcpy(e->idx_dev, idx, sizeof(int32_t) * (size_t) k, hipMemcpyHostToDevice));
+    ekf_block_kernel<<<(unsigned) ((kk + kEkfBlock - 1) / kEkfBlock), kEkfBlock, 0, e->stream>>>(e->P, e->ld, e->idx_dev, k, e->blk_dev);
+    if (int rc = ekf_launched("ekf_block_kernel")) return rc;
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    HIP_TRY(hipMemcpy(out, e->blk_dev, sizeof(float) * kk, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int slamgpu_ekf_upload(slamgpu_ekf *e, int32_t dim, const float *x, const float *P, int32_t ld_in) {
+    if (int rc = ekf_check(e)) return rc;
+    if (dim < 3 || dim > e->cap_dim || ((dim - 3) & 1) || !x || !P || ld_in < dim)
+        return fail(SLAMGPU_ERR_INVALID, "bad upload: dim %d (3 + 2 nf up to %d), ld_in %d", dim, e->cap_dim, ld_in);
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    HIP_TRY(hipMemcpy(e->x, x, sizeof(float) * (size_t) dim, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy2D(e->P, sizeof(float) * (size_t) e->ld, P, sizeof(float) * (size_t) ld_in, sizeof(float) * (size_t) dim, (size_t) dim,
+                        hipMemcpyHostToDevice));
+    e->dim = dim;
+    e->table.assign((size_t) nf_of(e), 0);
+    for (int f = 0; f < nf_of(e); f++) e->table[f] = f;
+    return 0;
+}
+
+int slamgpu_ekf_status(slamgpu_ekf *e, int32_t *status) {
+    if (int rc = ekf_check(e)) return rc;
+    if (!status) return fail(SLAMGPU_ERR_INVALID, "null output");
+    int32_t *h = reinterpret_cast<int32_t *>(e->pin.p);
+    HIP_TRY(hipMemcpyAsync(h, e->flag.p + 1, 4, hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    *status = *h;
+    return 0;
+}
+
+int slamgpu_ekf_sync(slamgpu_ekf *e) {
+    if (int rc = ekf_check(e)) return rc;
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    return 0;
+}
+
+}  // extern "C"

@@ -546,6 +546,8 @@ int64_t slamhost_sim_control_steps(const slamhost_sim *s) { return s->sim.contro
 struct slamhost_ekf {
     slamhost::EkfSlam ekf;
     std::vector<float> table;
+    float last_vgphi[3] = {0, 0, 0};  // what the last slamhost_ekf_step fed the filter
+    int32_t last_observe = 0;
 };
 
 slamhost_ekf *slamhost_ekf_create(const slamhost_sim *s) {
@@ -572,8 +574,63 @@ int slamhost_ekf_step(slamhost_ekf *e, slamhost_sim *s) {
     if (r < 0) return r;
     if (r == 1) sim.observe();
     const float phi = (float) (sim.xTrue[2] + sim.conf.sigmaT * slamhost::unif_rand());
+    e->last_vgphi[0] = sim.Vnoisy;
+    e->last_vgphi[1] = sim.Gnoisy;
+    e->last_vgphi[2] = phi;
+    e->last_observe = r == 1;
     e->ekf.sim(sim.Vnoisy, sim.Gnoisy, sim.Qe, sim.dt, phi, sim.z, sim.vis, sim.Re, r == 1, sim.R, e->table);
     return r;
+}
+
+int slamhost_ekf_last_inputs(const slamhost_ekf *e, float vgphi[3], int32_t *observe) {
+    if (!e) return -1;
+    if (vgphi) memcpy(vgphi, e->last_vgphi, sizeof e->last_vgphi);
+    if (observe) *observe = e->last_observe;
+    return 0;
+}
+
+int slamhost_ekf_sim(slamhost_ekf *e, float V, float G, const float Q[4], float dt, float phi, const float *z, const int32_t *ids, int32_t nz,
+                     const float Re[4], const float R[4], int32_t observe) {
+    if (!e || !Q || (observe && (nz < 0 || !Re || !R || (nz > 0 && (!z || (e->ekf.associationKnown && !ids)))))) return -1;
+    std::vector<float> vz;
+    std::vector<int32_t> vid;
+    if (observe && nz > 0) {
+        vz.assign(z, z + 2 * (size_t) nz);
+        if (e->ekf.associationKnown) {
+            vid.assign(ids, ids + nz);
+            for (int32_t id : vid) {
+                if (id < 0) return -1;
+                if ((size_t) id >= e->table.size()) e->table.resize((size_t) id + 1, -1.0f);
+            }
+        }
+    }
+    const float zero[4] = {0, 0, 0, 0};
+    e->ekf.sim(V, G, Q, dt, phi, vz, vid, Re ? Re : zero, observe != 0, R ? R : zero, e->table);
+    return 0;
+}
+
+int slamhost_ekf_upload(slamhost_ekf *e, int32_t dim, const float *x, const float *P, int32_t ld) {
+    if (!e || dim < 3 || ((dim - 3) & 1) || !x || !P || ld < dim) return -1;
+    e->ekf.x.assign(x, x + dim);
+    e->ekf.P = slamhost::Mat(dim, dim);
+    for (int i = 0; i < dim; i++)
+        for (int j = 0; j < dim; j++) e->ekf.P(i, j) = P[(size_t) i * ld + j];
+    // the id table starts over: id f is feature f for the uploaded features, every other id has not been seen
+    const size_t nf = (size_t) (dim - 3) / 2;
+    std::fill(e->table.begin(), e->table.end(), -1.0f);
+    if (e->table.size() < nf) e->table.resize(nf, -1.0f);
+    for (size_t f = 0; f < nf; f++) e->table[f] = (float) f;
+    return 0;
+}
+
+int slamhost_sim_noise(const slamhost_sim *s, float Q[4], float R[4], float Qe[4], float Re[4], float *dt) {
+    if (!s) return -1;
+    if (Q) memcpy(Q, s->sim.Q, 16);
+    if (R) memcpy(R, s->sim.R, 16);
+    if (Qe) memcpy(Qe, s->sim.Qe, 16);
+    if (Re) memcpy(Re, s->sim.Re, 16);
+    if (dt) *dt = s->sim.dt;
+    return 0;
 }
 
 int slamhost_ekf_state(const slamhost_ekf *e, float *x, float *P, int32_t cap) {

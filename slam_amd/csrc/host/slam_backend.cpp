@@ -129,6 +129,8 @@ static void usage(const char *a0) {
     printf("    -map joint          posterior's line and one more: the pose and the slots held by at least half of the weight TOGETHER (slamgpu_joint_summary):\n");
     printf("                        k, D, joint share, holders, pose position sigma, whether P is positive definite, the largest pose-landmark and\n");
     printf("                        landmark-landmark |correlation|.  -JOINT_OUT path: D, x and the D rows of P as text (%%.17g).  Not with -gpus k > 1 or the EKF\n");
+    printf("    -ekf host|device    -method EKF1: where the filter runs.  host (default): float32 loops on the CPU.  device: x and the dense P resident on\n");
+    printf("                        the GPU (slamgpu_ekf_sim), same output; refused with a FastSLAM method, and fails without a GPU (no CPU fallback)\n");
     printf("    -path none|smoothed smoothed: record the path posterior (one record per observation step, -PATH_RECORDS n of them kept, default 4096)\n");
     printf("                        and print one more line: the smoothed path's distance to the true path beside the filtered estimates', and the\n");
     printf("                        distinct ancestors 1 / 10 / 100 records back (slamgpu_path_summary; FastSLAM, one GPU, not -assoc particle -observe device)\n");
@@ -325,6 +327,7 @@ static void print_merged_map(slamgpu_ctx *ctx, const Simulator &sim, const std::
 }
 // -map joint: the posterior line, then the joint posterior of the pose and the confident slots (slamgpu_joint_summary)
 static bool g_map_joint = false;
+static bool g_ekf_device = false;  // -ekf device: EKF1 on the GPU (slamgpu_ekf_*)
 static std::string g_joint_out;
 static void print_joint(slamgpu_ctx *ctx, const std::vector<double> &sum, int slots) {
     std::vector<int32_t> list;
@@ -760,6 +763,18 @@ int main(int argc, char **argv) {
             fprintf(stderr, "-map joint: FastSLAM only (the EKF's joint posterior is its own state and P)\n");
             return EXIT_FAILURE;
         }
+        // ... and -ekf: where the EKF runs.  Refused from the arguments alone where it cannot apply
+        const std::string ek = sim.conf.s("ekf");
+        sim.conf.kv.erase("ekf");
+        if (!ek.empty() && ek != "host" && ek != "device") {
+            fprintf(stderr, "-ekf host|device\n");
+            return EXIT_FAILURE;
+        }
+        if (ek == "device" && sim.conf.method != 0) {
+            fprintf(stderr, "-ekf device: with -method EKF1 only (the FastSLAM methods keep no joint filter; they run on the device as they are)\n");
+            return EXIT_FAILURE;
+        }
+        g_ekf_device = ek == "device";
         const std::string mr = sim.conf.s("MAP_MERGE_RADIUS"), mc = sim.conf.s("MAP_MERGE_COHOLD");
         if (!mr.empty()) g_merge_radius = atof(mr.c_str());
         if (!mc.empty()) g_merge_cohold = atof(mc.c_str());
@@ -886,6 +901,7 @@ int main(int argc, char **argv) {
     }
     slamgpu_ctx *ctx = nullptr;
     EkfSlam ekf;
+    slamgpu_ekf *ekf_dev = nullptr;
     std::vector<float> ekf_table((size_t) sim.map.nlm, -1.0f);
     const int N = c.NPARTICLES;
     const bool parity = rng == "parity";
@@ -1013,6 +1029,26 @@ int main(int argc, char **argv) {
         ekf.gateAugment = c.GATE_AUGMENT;
         ekf.associationKnown = c.SWITCH_ASSOCIATION_KNOWN;
         ekf.sigmaPhi = c.sigmaT;
+        if (g_ekf_device) {  // the same filter resident on the GPU; without one this fails loudly (no CPU fallback behind -ekf device)
+            slamgpu_ekf_config ec{};
+            ec.struct_size = sizeof ec;
+            ec.device = 0;
+            ec.max_landmarks = sim.map.nlm;
+            ec.use_heading = ekf.useHeading;
+            ec.batch_update = ekf.enableBatchUpdate;
+            ec.association_known = ekf.associationKnown;
+            ec.wheel_base = ekf.wheelBase;
+            ec.sigma_phi = ekf.sigmaPhi;
+            ec.gate_reject = ekf.gateReject;
+            ec.gate_augment = ekf.gateAugment;
+            if (slamgpu_ekf_create(&ec, &ekf_dev) != 0) {
+                fprintf(stderr, "-ekf device: %s\n", slamgpu_last_error());
+                if (log) fclose(log);
+                return EXIT_FAILURE;
+            }
+            printf("EKF on the device: P allocated for %d landmarks\n\n", sim.map.nlm);
+            sim.seed();  // (HIP runtime initialisation draws from libc rand(), as above)
+        }
     }
 
     if (batched) {
@@ -1223,10 +1259,20 @@ int main(int argc, char **argv) {
                 nobs++;
             }
             const float phi = (float) (sim.xTrue[2] + c.sigmaT * unif_rand());  // ekfslamwrapper.cpp:82
-            ekf.sim(sim.Vnoisy, sim.Gnoisy, sim.Qe, sim.dt, phi, sim.z, sim.vis, sim.Re, r == 1, sim.R, ekf_table);
-            est[0] = ekf.x[0];
-            est[1] = ekf.x[1];
-            est[2] = ekf.x[2];
+            if (ekf_dev) {
+                rc = slamgpu_ekf_sim(ekf_dev, sim.Vnoisy, sim.Gnoisy, sim.Qe, sim.dt, phi, sim.z.data(), sim.vis.data(), r == 1 ? (int32_t) sim.vis.size() : 0,
+                                     sim.Re, sim.R, r == 1);
+                if (!rc) rc = slamgpu_ekf_pose(ekf_dev, est, nullptr);
+                if (rc) {
+                    fprintf(stderr, "slamgpu: %s\n", slamgpu_last_error());
+                    break;
+                }
+            } else {
+                ekf.sim(sim.Vnoisy, sim.Gnoisy, sim.Qe, sim.dt, phi, sim.z, sim.vis, sim.Re, r == 1, sim.R, ekf_table);
+                est[0] = ekf.x[0];
+                est[1] = ekf.x[1];
+                est[2] = ekf.x[2];
+            }
         }
         iter++;
         if (plot.active()) {
@@ -1282,7 +1328,12 @@ int main(int argc, char **argv) {
     } else if (ctx && particle) {
         print_particle_map(ctx, sim, N, pp_opened, pp_reused, pp_dropped, pp_most);
     } else if (ctx) printf("landmarks in map: %d\n", slamgpu_num_landmarks(ctx));
-    else printf("landmarks in map: %d\n", ekf.num_features());
+    else if (ekf_dev) {
+        int32_t st = 0;
+        (void) slamgpu_ekf_status(ekf_dev, &st);
+        printf("landmarks in map: %d\n", (slamgpu_ekf_dim(ekf_dev) - 3) / 2);
+        if (st & SLAMGPU_EKF_STATUS_NOT_PD) printf("EKF on the device: a batch update was skipped (innovation covariance not positive definite)\n");
+    } else printf("landmarks in map: %d\n", ekf.num_features());
     if (ctx) print_posterior_map(ctx, sim);
     if (ctx && !rc) print_smoothed_path(ctx);
     if (ctx && !rc) print_pose_posterior(ctx);
@@ -1294,5 +1345,6 @@ int main(int argc, char **argv) {
     if (log) fclose(log);
     if (alog) fclose(alog);
     if (ctx) slamgpu_destroy(ctx);
+    if (ekf_dev) slamgpu_ekf_destroy(ekf_dev);
     return rc ? EXIT_FAILURE : 0;
 }

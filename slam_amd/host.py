@@ -13,7 +13,7 @@ DECLARED_SYMBOLS = [
     "slamhost_sim_control_steps", "slamhost_gated_create", "slamhost_gated_destroy", "slamhost_gated_set", "slamhost_gated_step",
     "slamhost_gated_counts", "slamhost_draw_normals", "slamhost_draw_strata", "slamhost_unif_rand",
     "slamhost_synthetic_landmarks", "slamhost_write_map", "slamhost_ekf_create", "slamhost_ekf_destroy", "slamhost_ekf_step",
-    "slamhost_ekf_state", "slamhost_plot_open", "slamhost_plot_close", "slamhost_plot_xy", "slamhost_plot_matrix",
+    "slamhost_ekf_state", "slamhost_ekf_last_inputs", "slamhost_sim_noise", "slamhost_ekf_sim", "slamhost_ekf_upload", "slamhost_plot_open", "slamhost_plot_close", "slamhost_plot_xy", "slamhost_plot_matrix",
     "slamhost_plot_doubles", "slamhost_plot_car_size", "slamhost_plot_u32", "slamhost_plot_cmd", "slamhost_plot_name",
     "slamhost_map_candidates", "slamhost_map_merge", "slamhost_pose_nees", "slamhost_innovation_nis", "slamhost_joint_dense",
 ]
@@ -74,6 +74,11 @@ def load_library():
         L.slamhost_ekf_destroy.restype = None
         L.slamhost_ekf_step.argtypes = [C.c_void_p, C.c_void_p]
         L.slamhost_ekf_state.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]
+        L.slamhost_ekf_last_inputs.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]
+        L.slamhost_sim_noise.argtypes = [C.c_void_p] * 5 + [C.POINTER(C.c_float)]
+        L.slamhost_ekf_sim.argtypes = [C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_int32,
+                                       C.c_void_p, C.c_void_p, C.c_int32]
+        L.slamhost_ekf_upload.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32]
         L.slamhost_plot_open.restype = C.c_void_p
         L.slamhost_plot_open.argtypes = [C.c_char_p]
         L.slamhost_plot_close.argtypes = [C.c_void_p]
@@ -272,6 +277,13 @@ class HostSim:
         f = lambda a: np.array(list(a), np.float32).reshape(2, 2)
         return f(self.conf.Qe), f(self.conf.Re), np.float32(self.conf.DT_CONTROLS)
 
+    def sim_noise(self):
+        """slamhost_sim_noise: the simulator's own Q, R, Qe, Re (each [2, 2]) and its control period, as the EKF loop hands them on"""
+        m = [np.zeros((2, 2), np.float32) for _ in range(4)]
+        dt = C.c_float()
+        self.L.slamhost_sim_noise(self.h, _p(m[0]), _p(m[1]), _p(m[2]), _p(m[3]), C.byref(dt))
+        return dict(Q=m[0], R=m[1], Qe=m[2], Re=m[3], dt=float(dt.value))
+
 
 class GatedPolicy:
     """the policy between the gated association's vote and the update's packet (include/slamhost.h: slamhost_gated_*;
@@ -334,6 +346,28 @@ class HostEkf:
         P = np.zeros((cap, cap), np.float32) if want_P else None
         d = self.L.slamhost_ekf_state(self.h, _p(x), _p(P), cap)
         return x[:d].copy(), (P[:d, :d].copy() if want_P else None)
+
+    def last_inputs(self):
+        """what the last step() fed the filter: V, G, phi and whether sim.last_z() was observed"""
+        v = np.zeros(3, np.float32)
+        ob = C.c_int32()
+        self.L.slamhost_ekf_last_inputs(self.h, _p(v), C.byref(ob))
+        return float(v[0]), float(v[1]), float(v[2]), int(ob.value)
+
+    def sim_step(self, V, G, Q, dt, phi, z=None, ids=None, Re=None, R=None, observe=0):
+        """slamhost_ekf_sim: one EKFSLAM::sim on explicit inputs"""
+        z = np.zeros((0, 2), np.float32) if z is None else np.ascontiguousarray(z, np.float32).reshape(-1, 2)
+        ids = None if ids is None else np.ascontiguousarray(ids, np.int32)
+        f = lambda a: None if a is None else np.ascontiguousarray(a, np.float32)
+        Q, Re, R = f(Q), f(Re), f(R)
+        if self.L.slamhost_ekf_sim(self.h, V, G, _p(Q), dt, phi, _p(z), _p(ids), z.shape[0], _p(Re), _p(R), int(observe)) != 0:
+            raise ValueError("slamhost_ekf_sim: bad arguments")
+
+    def upload(self, x, P):
+        x = np.ascontiguousarray(x, np.float32)
+        P = np.ascontiguousarray(P, np.float32)
+        if self.L.slamhost_ekf_upload(self.h, x.shape[0], _p(x), _p(P), P.shape[1]) != 0:
+            raise ValueError("slamhost_ekf_upload: bad arguments")
 
     def close(self):
         if self.h:

@@ -1,0 +1,185 @@
+"""The numbers of DESIGN.md section 7h (not a test): the device EKF (slamgpu_ekf_*) beside the host filter, and at the size of
+BASELINE config 5.  Appends to profiles/ekf.txt (or --out).
+
+    python tools/ekf_probe.py [--out profiles/ekf.txt] [--no-small] [--no-large] [--no-kernels] [--max-range 20] [--obs-steps 200]
+
+Times are wall-clock around a region that ends in slamgpu_ekf_sync, after one untimed pass over the same calls; a kernel's own
+time is that of a region holding nothing else (the update chunk: four kernels, so its rate is a LOWER bound on ekf_syrk_kernel's).
+"""
+import argparse
+import os
+import sys
+import tempfile
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+f32 = np.float32
+
+
+def dev_for(slam_amd, c, nlm, **over):
+    kw = dict(use_heading=c.SWITCH_HEADING_KNOWN == 1, batch_update=c.SWITCH_BATCH_UPDATE == 1, association_known=c.SWITCH_ASSOCIATION_KNOWN != 0,
+              wheel_base=c.WHEELBASE, sigma_phi=c.sigmaT, gate_reject=c.GATE_REJECT, gate_augment=c.GATE_AUGMENT)
+    kw.update(over)
+    return slam_amd.EkfGpu(nlm, **kw)
+
+
+def small_map(slam_amd, host, name, seed, max_controls, say):
+    sim = host.HostSim(["-m", os.path.join(ROOT, "data", name + ".mat"), "-method", "EKF1", "-SWITCH_SEED_RANDOM", seed])
+    ekf = host.HostEkf(sim)
+    nz = sim.sim_noise()
+    steps, t_host = [], 0.0
+    while len(steps) < max_controls:
+        t0 = time.perf_counter()
+        r = ekf.step()
+        t_host += time.perf_counter() - t0
+        if r < 0:
+            break
+        V, G, phi, ob = ekf.last_inputs()
+        z, vis = sim.last_z() if ob else (np.zeros((0, 2), f32), np.zeros(0, np.int32))
+        steps.append((V, G, phi, ob, z, vis))
+    dim_host = ekf.state(cap=512, want_P=False)[0].shape[0]
+    dev = dev_for(slam_amd, sim.conf, sim.nlm)
+    t_ctl = t_obs = 0.0
+    for (V, G, phi, ob, z, vis) in steps:
+        t0 = time.perf_counter()
+        dev.sim(V, G, nz["Qe"], nz["dt"], phi, z, vis, nz["Re"], nz["R"], ob)
+        if ob:
+            dev.sync()
+            t_obs += time.perf_counter() - t0
+        else:
+            t_ctl += time.perf_counter() - t0
+    dev.sync()
+    nobs = sum(s[3] for s in steps)
+    say("%s seed %d, %d control steps (%d with an observation), final dim host %d device %d, status %d" % (name, seed, len(steps), nobs, dim_host, dev.dim, dev.status()))
+    say("    host filter      %9.1f us per control step (all steps)" % (1e6 * t_host / len(steps)))
+    say("    device filter    %9.1f us per control step without an observation (enqueue only), %9.1f us per observation step (synchronised)" %
+        (1e6 * t_ctl / max(len(steps) - nobs, 1), 1e6 * t_obs / max(nobs, 1)))
+    dev.close()
+    ekf.close()
+    sim.close()
+
+
+def timed(dev, fn, reps=5):
+    fn()
+    dev.sync()
+    t0 = time.perf_counter()
+    for _ in range(reps):
+        fn()
+    dev.sync()
+    return (time.perf_counter() - t0) / reps
+
+
+def large(slam_amd, host, max_range, obs_steps, kernels, say):
+    nlm = 10000
+    lm = host.synthetic_landmarks(12345, nlm, -130, 100, -100, 90)
+    s0 = host.HostSim(["-m", os.path.join(ROOT, "data", "example_webmap.mat"), "-method", "EKF1"])
+    _, wp = s0.map()
+    s0.close()
+    with tempfile.TemporaryDirectory() as wd:
+        mp = os.path.join(wd, "synthetic10k.mat")
+        host.write_map(mp, lm, wp)
+        open(os.path.join(wd, "synthetic10k.ini"), "w").write(open(os.path.join(ROOT, "data", "example_webmap.ini")).read())
+        sim = host.HostSim(["-m", mp, "-method", "EKF1", "-SWITCH_SEED_RANDOM", 7, "-MAX_RANGE", max_range, "-SWITCH_ASSOCIATION_KNOWN", 1])
+        nz = sim.sim_noise()
+        try:
+            dev = dev_for(slam_amd, sim.conf, nlm)
+        except slam_amd.SlamGpuError as e:
+            say("config-5 size: the filter does not fit: %s" % e)
+            return
+        table, nobs, t_obs, m_sum, t0_all = {}, 0, 0.0, 0, time.perf_counter()
+        while nobs < obs_steps:
+            r, V, G, phi = sim.control()
+            if r < 0:
+                break
+            z, vis = (np.zeros((0, 2), f32), np.zeros(0, np.int32))
+            if r == 1:
+                sim.observe(0)
+                z, vis = sim.last_z()
+            t0 = time.perf_counter()
+            dev.sim(V, G, nz["Qe"], nz["dt"], phi, z, vis, nz["Re"], nz["R"], r)
+            if r == 1:
+                dev.sync()
+                t_obs += time.perf_counter() - t0
+                m_sum += sum(1 for i in vis if int(i) in table)
+                for i in vis:
+                    table.setdefault(int(i), len(table))
+                nobs += 1
+        x, _ = dev.state(want_P=False)
+        nf = (x.shape[0] - 3) // 2
+        ids = np.array(sorted(table, key=table.get))
+        err = np.hypot(x[3::2] - lm[0, ids], x[4::2] - lm[1, ids])
+        diag = dev.block(np.arange(0, x.shape[0], max(1, x.shape[0] // 4096), dtype=np.int32)).diagonal()
+        say("config-5-size run: 10 000-landmark synthetic map, MAX_RANGE %g, known association, %d observation steps (%.1f s wall in all)" %
+            (max_range, nobs, time.perf_counter() - t0_all))
+        say("    %d landmarks mapped (dim %d of 20 003), mean re-observed per step %.1f, %.2f ms per observation step (synchronised)" %
+            (nf, x.shape[0], m_sum / max(nobs, 1), 1e3 * t_obs / max(nobs, 1)))
+        say("    mean landmark error %.3f m (max %.3f), pose error %.3f m, status %d, smallest sampled diagonal entry of P %.3e" %
+            (err.mean(), err.max(), float(np.hypot(*(x[:2] - sim.true_pose()[:2]))), dev.status(), diag.min()))
+        dev.close()
+        if not kernels:
+            sim.close()
+            return
+        # the kernels at FULL size: a synthetic symmetric positive definite P of dimension 20 003 (diagonal plus rank one)
+        D = 3 + 2 * nlm
+        dev = dev_for(slam_amd, sim.conf, nlm, use_heading=True, sigma_phi=0.0175)
+        rng = np.random.default_rng(1)
+        u = rng.normal(0, 0.1, D).astype(f32)
+        P = np.outer(u, u)
+        P[np.diag_indices(D)] += f32(0.5)
+        xs = np.zeros(D, f32)
+        xs[3::2], xs[4::2] = lm[0], lm[1]
+        dev.upload(xs, P)
+        del P
+        idf = np.arange(64, dtype=np.int32) * 100
+        dx, dy = xs[3 + 2 * idf], xs[4 + 2 * idf]
+        zf = np.stack([np.hypot(dx, dy), np.arctan2(dy, dx)], axis=1).astype(f32)
+        bytes_P = 4.0 * D * D
+        t = timed(dev, lambda: dev.predict(3.0, 0.01, nz["Qe"], nz["dt"]))
+        say("full size, D = 20 003 (P = %.2f GB):" % (bytes_P / 1e9))
+        say("    ekf_predict_kernel          %8.3f ms (touches 6 D floats of P, strided mirror writes)" % (1e3 * t))
+        t = timed(dev, lambda: dev.observe_heading(0.001))
+        say("    heading update (two kernels) %8.3f ms = %.2f TB/s over P read once and written once (%.2f GB)" % (1e3 * t, 2 * bytes_P / t / 1e12, 2 * bytes_P / 1e9))
+        t = timed(dev, lambda: dev.update(zf, idf, nz["R"]))
+        fl = 2.0 * 128 * (D * (D + 128.0) / 2)  # the tiles on or below the diagonal
+        say("    update chunk, 64 observations (innov + chol + gain + syrk) %8.3f ms: ekf_syrk_kernel's %.1f GFLOP at >= %.1f TFLOP/s (155 measured "
+            "FP32-MFMA peak), P read once and written once at >= %.2f TB/s" % (1e3 * t, fl / 1e9, fl / t / 1e12, 2 * bytes_P / t / 1e12))
+        x, _ = dev.state(want_P=False)
+        say("    after these calls: status %d, x finite %s" % (dev.status(), bool(np.isfinite(x).all())))
+        dev.close()
+        sim.close()
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "ekf.txt"))
+    ap.add_argument("--no-small", action="store_true", help="skip the bundled maps")
+    ap.add_argument("--no-large", action="store_true", help="skip the config-5-size run and the full-size kernels")
+    ap.add_argument("--no-kernels", action="store_true", help="skip the full-size kernels (D = 20 003)")
+    ap.add_argument("--max-range", type=float, default=20.0)
+    ap.add_argument("--obs-steps", type=int, default=200)
+    a = ap.parse_args()
+    import slam_amd
+    from slam_amd import host
+    if slam_amd.device_count() < 1:
+        raise SystemExit("ekf_probe needs a GPU: the device EKF has no CPU fallback")
+    slam_amd.EkfGpu(1).close()  # (the HIP runtime re-seeds libc rand() when it comes up: before any simulator is seeded)
+    out = open(a.out, "a")
+
+    def say(line):
+        print(line, flush=True)
+        out.write(line + "\n")
+        out.flush()
+
+    say("# tools/ekf_probe.py")
+    if not a.no_small:
+        small_map(slam_amd, host, "example_webmap", 7, 10 ** 9, say)
+        small_map(slam_amd, host, "example_loop902", 3, 2000, say)
+    if not a.no_large:
+        large(slam_amd, host, a.max_range, a.obs_steps, not a.no_kernels, say)
+
+
+if __name__ == "__main__":
+    main()
