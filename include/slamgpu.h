@@ -841,6 +841,92 @@ int slamgpu_ekf_upload(slamgpu_ekf *e, int32_t dim, const float *x, const float 
 int slamgpu_ekf_status(slamgpu_ekf *e, int32_t *status);
 int slamgpu_ekf_sync(slamgpu_ekf *e);
 
+/* ---- EKF-SLAM ensemble: `members` independent filters resident in device memory, ONE launch per EKFSLAM::sim of all of them ------
+ * A filter of the size of this project's maps (dim 73) cannot fill a GPU; many of them can, and Monte Carlo runs are how EKF-SLAM
+ * consistency is judged (Bailey et al.'s NEES averaged over runs).  One workgroup runs one member from predict to augment.  Member b
+ * owns a slab of its own: P[b] row-major with leading dimension ld = 3 + 2 max_landmarks rounded up to a multiple of 32 floats, x[b],
+ * dim[b], status[b] and six consistency accumulators.  (The entry points are slamgpu_ens_*: the prefix slamgpu_ekf_ stays the
+ * single filter's set.)  SLAMGPU_ERR_NO_DEVICE without a GPU (no CPU fallback), SLAMGPU_ERR_ALLOC if
+ * the slabs do not fit, SLAMGPU_ERR_INVALID for any other bad argument, nothing applied.
+ *
+ * Stage by stage the semantics are slamgpu_ekf_sim's (above).  DEVIATIONS from the reference, as there: float32; gated
+ * nearest-neighbour with the first-minimum tie rule, or the known association; the batch update in chunks of at most 64 observations
+ * (m <= 64 is the reference's single batch; more are applied one after another, each linearised at the state the previous chunk
+ * left); a chunk without a Cholesky factor is skipped and flagged; augment is one feature after another; both triangles of P are
+ * stored and P == P^T bit for bit after every call.
+ *
+ * nz and ids are SHARED by all members: the reference's simulator moves the true pose with the true controls and only then perturbs
+ * the measured ones, and picks the visible landmarks from the true pose (Simulator::control / ::observe), so the noise realisations of
+ * one run share the controls' true values, the visible ids and the noise-free ranges and bearings; they differ only in the noise.
+ * With association_known the host keeps ONE id -> feature table (every member then has the same dimension; a member whose dimension
+ * lacks a feature the table names -- it was uploaded apart, or refused a step -- ignores that observation); with the gates the
+ * members' dimensions differ, dim[members] lives on the device and the host never needs it to launch.  The table's rules: ids lie
+ * in [0, 2^20); an id not seen before may appear once per step (twice: SLAMGPU_ERR_INVALID, nothing applied); the table learns a step's
+ * new ids only once the step has been enqueued, so a call that fails leaves it as it was; when the table itself has no room for a
+ * step's new ids (features handed out + new > max_landmarks) NO member applies that step's update or augment and every member gets
+ * SLAMGPU_EKF_STATUS_CAPACITY, whatever its own dimension: table and members cannot part ways; upload of ANY member resets the
+ * one table to id f <-> feature f for f < that member's feature count (members of different sizes: upload the largest last).
+ *
+ * sim: explicit per-member inputs VG[members][2] (V, G), phi[members], z[members][nz][2]; shared ids[nz] (known association only),
+ *      Q, Re, R, dt, observe, and truth[3] = the true pose (NULL: the consistency accumulators are left alone).  nz <= 4096.
+ * sim_noise: the same step from the shared noise-free inputs; every member draws its own inside the launch and no per-member data
+ *      crosses the bus.  Q is the control noise that is drawn, Qe the one the filter assumes (the reference inflates it:
+ *      SWITCH_INFLATE_NOISE; NULL: Q); R is the sensor noise drawn and the update's, Re the gates' and the augment's, as in sim.
+ *      Philox4x32-10, key = seed, counter (member, step, 5, q) -- stream 5:
+ *        q = 0      g0, g1 of box_muller3:  V + L00 g0,  G + L10 g0 + L11 g1,  L the lower Cholesky factor of Q (float, host)
+ *        q = 1      phi_true + sigma_phi u01(first word): the reference's draw is unifRand() on [0, 1), UNCENTRED
+ *                   (ekfslamwrapper.cpp:81), and it is kept so
+ *        q = 2 + i  g0, g1:  range_i + g0 sqrt(R00),  bearing_i + g1 sqrt(R11), as Simulator::observe does
+ *      `noise` says which are drawn (SLAMGPU_EKF_ENS_NOISE_*); a noise that is off leaves the true value untouched bit for bit.
+ * last_inputs: the per-member VG, phi, z the last sim / sim_noise used (any may be NULL).
+ * dims: dim_out[members].  poses: out[members][12] = x, y, theta, Pvv row-major.  state: member b's x[dim] and, unless NULL, P into
+ *      leading dimension ld_out >= dim; returns dim.  slab: member b's whole slab, x[ld] and P[3 + 2 max_landmarks][ld], padding
+ *      included (tests); returns ld.  upload: as slamgpu_ekf_upload for member b; the id table of the known association starts
+ *      over with id f <-> feature f.
+ * status: status_out[members], sticky per member.  SLAMGPU_EKF_STATUS_NOT_PD as in the single filter (the chunk is skipped).
+ *      SLAMGPU_EKF_STATUS_CAPACITY: a step needed more than max_landmarks features; that member's update and augment of that step
+ *      were not applied, its predict and heading were, the other members are unaffected (the per-member form of slamgpu_ekf_sim's
+ *      SLAMGPU_ERR_CAPACITY).
+ * consistency: out[members][6], accumulated by the member's own workgroup after the last stage of every step that was given
+ *      `truth`, in double, no atomics (deterministic).  e = (x - x_t, y - y_t, IEEE remainder(theta - theta_t, 2 pi)), NEES =
+ *      e^T Pvv^-1 e through the Cholesky factor of the 3 x 3 pose block (slamhost_pose_nees's definitions):
+ *        [0] steps counted  [1] steps not counted (Pvv not positive definite -- how a filter starts, P = 0 -- or a non-finite state)
+ *        [2] sum NEES  [3] count of NEES <= 7.8147  [4] sum (ex^2 + ey^2)  [5] sum etheta^2
+ *      consistency_reset zeroes them.  What it costs: DESIGN.md section 7i. */
+typedef struct slamgpu_ekf_ens slamgpu_ekf_ens;
+typedef struct {
+    uint32_t struct_size; /* sizeof(slamgpu_ekf_ens_config) */
+    int32_t device;
+    int32_t members;       /* 1 .. 65535 */
+    int32_t max_landmarks; /* 0 .. 512 */
+    int32_t use_heading, batch_update, association_known;
+    float wheel_base, sigma_phi, gate_reject, gate_augment;
+    uint64_t seed;            /* Philox key of sim_noise */
+    uint64_t external_stream; /* hipStream_t, 0: a stream of the handle's own */
+} slamgpu_ekf_ens_config;
+#define SLAMGPU_EKF_STATUS_CAPACITY 2 /* a step needed more than max_landmarks features: its update and augment were not applied */
+#define SLAMGPU_EKF_ENS_NOISE_CONTROL 1 /* the reference's SWITCH_CONTROL_NOISE */
+#define SLAMGPU_EKF_ENS_NOISE_HEADING 2 /* the heading draw */
+#define SLAMGPU_EKF_ENS_NOISE_SENSOR 4  /* SWITCH_SENSOR_NOISE */
+int slamgpu_ens_create(const slamgpu_ekf_ens_config *cfg, slamgpu_ekf_ens **out);
+void slamgpu_ens_destroy(slamgpu_ekf_ens *e);
+int slamgpu_ens_sync(slamgpu_ekf_ens *e);
+int slamgpu_ens_sim(slamgpu_ekf_ens *e, const float *VG /*[members][2]*/, const float *phi /*[members]*/, const float *z /*[members][nz][2]*/,
+                        const int32_t *ids /*[nz]*/, int32_t nz, const float Q[4], const float Re[4], const float R[4], float dt, int32_t observe,
+                        const float *truth /*[3] or NULL*/);
+int slamgpu_ens_sim_noise(slamgpu_ekf_ens *e, float V, float G, float phi_true, const float *z_true /*[nz][2]*/, const int32_t *ids /*[nz]*/,
+                              int32_t nz, uint32_t step, const float Q[4], const float Qe[4] /*or NULL: Q*/, const float Re[4], const float R[4], float dt,
+                              int32_t observe, const float *truth /*[3] or NULL*/, uint32_t noise);
+int slamgpu_ens_last_inputs(slamgpu_ekf_ens *e, float *VG, float *phi, float *z);
+int slamgpu_ens_dims(slamgpu_ekf_ens *e, int32_t *dim_out);
+int slamgpu_ens_poses(slamgpu_ekf_ens *e, double *out);
+int slamgpu_ens_state(slamgpu_ekf_ens *e, int32_t b, float *x, float *P, int32_t ld_out);
+int slamgpu_ens_slab(slamgpu_ekf_ens *e, int32_t b, float *x, float *P);
+int slamgpu_ens_upload(slamgpu_ekf_ens *e, int32_t b, int32_t dim, const float *x, const float *P, int32_t ld_in);
+int slamgpu_ens_status(slamgpu_ekf_ens *e, int32_t *status_out);
+int slamgpu_ens_consistency(slamgpu_ekf_ens *e, double *out);
+int slamgpu_ens_consistency_reset(slamgpu_ekf_ens *e);
+
 /* ---- distributed operation (the multi-GPU path: nothing migrates) ---------------------------------------------------
  * One context per GPU; shard g holds the contiguous global particles [g*n, (g+1)*n), n a multiple of 256; contexts may
  * live in one process (peer access) or one process per GPU (hipIpc).  Every context maps every other shard's state arrays

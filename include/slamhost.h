@@ -49,6 +49,8 @@ int slamhost_sim_observe(slamhost_sim *s, int32_t nf_known, float *zf, int32_t *
 /* raw observation of the last slamhost_sim_observe: z[2*nz], visible ids */
 int slamhost_sim_last_z(const slamhost_sim *s, float *z, int32_t *vis, int32_t *nz);
 void slamhost_sim_true(const slamhost_sim *s, float x[3]);
+/* the TRUE controls of the last slamhost_sim_control, the ones that moved the true pose (what slamgpu_ens_sim_noise perturbs itself) */
+void slamhost_sim_true_controls(const slamhost_sim *s, float *V, float *G);
 int64_t slamhost_sim_control_steps(const slamhost_sim *s);
 
 /* EKF-SLAM on the host CPU (-method EKF1; BASELINE config 1): EKFSLAMWrapper::run's loop body

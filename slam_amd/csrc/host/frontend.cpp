@@ -541,6 +541,10 @@ int slamhost_sim_last_z(const slamhost_sim *s, float *z, int32_t *vis, int32_t *
 }
 
 void slamhost_sim_true(const slamhost_sim *s, float x[3]) { memcpy(x, s->sim.xTrue, 3 * sizeof(float)); }
+void slamhost_sim_true_controls(const slamhost_sim *s, float *V, float *G) {
+    if (V) *V = s->sim.Vtrue;
+    if (G) *G = s->sim.Gtrue;
+}
 int64_t slamhost_sim_control_steps(const slamhost_sim *s) { return s->sim.control_steps; }
 
 struct slamhost_ekf {

@@ -131,6 +131,7 @@ static void usage(const char *a0) {
     printf("                        landmark-landmark |correlation|.  -JOINT_OUT path: D, x and the D rows of P as text (%%.17g).  Not with -gpus k > 1 or the EKF\n");
     printf("    -ekf host|device    -method EKF1: where the filter runs.  host (default): float32 loops on the CPU.  device: x and the dense P resident on\n");
     printf("                        the GPU (slamgpu_ekf_sim), same output; refused with a FastSLAM method, and fails without a GPU (no CPU fallback)\n");
+    printf("    -runs B [-RUNS_SEED s]  with -method EKF1 -ekf device: B (1 .. 65535) noise realisations of the run as one ensemble of device filters, Monte Carlo NEES at the end; not with -plot\n");
     printf("    -path none|smoothed smoothed: record the path posterior (one record per observation step, -PATH_RECORDS n of them kept, default 4096)\n");
     printf("                        and print one more line: the smoothed path's distance to the true path beside the filtered estimates', and the\n");
     printf("                        distinct ancestors 1 / 10 / 100 records back (slamgpu_path_summary; FastSLAM, one GPU, not -assoc particle -observe device)\n");
@@ -328,6 +329,102 @@ static void print_merged_map(slamgpu_ctx *ctx, const Simulator &sim, const std::
 // -map joint: the posterior line, then the joint posterior of the pose and the confident slots (slamgpu_joint_summary)
 static bool g_map_joint = false;
 static bool g_ekf_device = false;  // -ekf device: EKF1 on the GPU (slamgpu_ekf_*)
+static int g_runs = 0;             // -runs B: B noise realisations at once (slamgpu_ens_*)
+static uint64_t g_runs_seed = 0;   // -RUNS_SEED s: the Philox key of their draws (default: SWITCH_SEED_RANDOM)
+
+// -method EKF1 -ekf device -runs B.  The true path does not depend on the noise (Simulator::control moves xTrue with the true
+// controls and only then perturbs the measured ones; Simulator::observe picks the visible landmarks from xTrue), so the host
+// simulator runs ONCE with its own control and sensor noise off and every control step is one slamgpu_ens_sim_noise: each member
+// draws its own noise on the device and the consistency accumulators take xTrue as the truth
+constexpr int kEnsHeadroom = 8;
+static int run_ekf_ensemble(Simulator &sim, long maxsteps) {
+    Conf &c = sim.conf;
+    const uint32_t noise = (c.SWITCH_CONTROL_NOISE ? SLAMGPU_EKF_ENS_NOISE_CONTROL : 0) | SLAMGPU_EKF_ENS_NOISE_HEADING |
+                           (c.SWITCH_SENSOR_NOISE ? SLAMGPU_EKF_ENS_NOISE_SENSOR : 0);
+    c.SWITCH_CONTROL_NOISE = 0;
+    c.SWITCH_SENSOR_NOISE = 0;
+    slamgpu_ekf_ens_config ec{};
+    ec.struct_size = sizeof ec;
+    ec.device = 0;
+    ec.members = g_runs;
+    // (with the gates a member may open a landmark the map does not have; without room for it the capacity rule would drop that
+    // step's whole update and shape the NEES figures below: kEnsHeadroom features more than the map, within the ensemble's limit of 512)
+    ec.max_landmarks = c.SWITCH_ASSOCIATION_KNOWN || sim.map.nlm + kEnsHeadroom > 512 ? sim.map.nlm : sim.map.nlm + kEnsHeadroom;
+    ec.use_heading = c.SWITCH_HEADING_KNOWN == 1;
+    ec.batch_update = c.SWITCH_BATCH_UPDATE == 1;
+    ec.association_known = c.SWITCH_ASSOCIATION_KNOWN;
+    ec.wheel_base = c.WHEELBASE;
+    ec.sigma_phi = c.sigmaT;
+    ec.gate_reject = c.GATE_REJECT;
+    ec.gate_augment = c.GATE_AUGMENT;
+    ec.seed = g_runs_seed;
+    slamgpu_ekf_ens *ens = nullptr;
+    if (slamgpu_ens_create(&ec, &ens) != 0) {
+        fprintf(stderr, "-ekf device -runs %d: %s\n", g_runs, slamgpu_last_error());
+        return EXIT_FAILURE;
+    }
+    printf("EKF ensemble on the device: %d members, P allocated for %d landmarks each (the map has %d), Philox key %llu\n\n", g_runs, ec.max_landmarks, sim.map.nlm,
+           (unsigned long long) g_runs_seed);
+    sim.seed();
+    long iter = 0, nobs = 0;
+    int rc = 0;
+    const auto t0 = std::chrono::steady_clock::now();
+    while ((maxsteps < 0 || iter < maxsteps) && !rc) {
+        const int r = sim.control();
+        if (r < 0) break;
+        if (r == 1) {
+            sim.observe();
+            nobs++;
+        }
+        rc = slamgpu_ens_sim_noise(ens, sim.Vtrue, sim.Gtrue, sim.xTrue[2], sim.z.data(), sim.vis.data(), r == 1 ? (int32_t) sim.vis.size() : 0,
+                                       (uint32_t) iter, sim.Q, sim.Qe, sim.Re, sim.R, sim.dt, r == 1, sim.xTrue, noise);
+        iter++;
+    }
+    if (!rc) rc = slamgpu_ens_sync(ens);
+    const double us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
+    const size_t B = (size_t) g_runs;
+    std::vector<int32_t> dims(B), status(B);
+    std::vector<double> poses(12 * B), acc(6 * B);
+    if (!rc) rc = slamgpu_ens_dims(ens, dims.data());
+    if (!rc) rc = slamgpu_ens_poses(ens, poses.data());
+    if (!rc) rc = slamgpu_ens_consistency(ens, acc.data());
+    if (!rc) rc = slamgpu_ens_status(ens, status.data());
+    if (rc) {
+        fprintf(stderr, "slamgpu: %s\n", slamgpu_last_error());
+        slamgpu_ens_destroy(ens);
+        return EXIT_FAILURE;
+    }
+    int nf_min = INT32_MAX, nf_max = 0, n_notpd = 0, n_cap = 0;
+    double nf_sum = 0, err_sum = 0, counted = 0, skipped = 0, nees = 0, inside = 0, m_min = INFINITY, m_max = -INFINITY;
+    for (size_t b = 0; b < B; b++) {
+        const int nf = (dims[b] - 3) / 2;
+        nf_min = std::min(nf_min, nf);
+        nf_max = std::max(nf_max, nf);
+        nf_sum += nf;
+        err_sum += std::hypot(poses[12 * b] - sim.xTrue[0], poses[12 * b + 1] - sim.xTrue[1]);
+        const double *a = &acc[6 * b];
+        counted += a[0];
+        skipped += a[1];
+        nees += a[2];
+        inside += a[3];
+        if (a[0] > 0) {
+            m_min = std::min(m_min, a[2] / a[0]);
+            m_max = std::max(m_max, a[2] / a[0]);
+        }
+        n_notpd += (status[b] & SLAMGPU_EKF_STATUS_NOT_PD) != 0;
+        n_cap += (status[b] & SLAMGPU_EKF_STATUS_CAPACITY) != 0;
+    }
+    printf("control steps %ld, observation steps %ld, %.1f us per control step of the ensemble, %.3g filter-steps per second\n", iter, nobs,
+           iter ? us / iter : 0.0, us > 0 ? (double) iter * B / (us * 1e-6) : 0.0);
+    printf("members %d, landmarks in map min %d mean %.2f max %d, mean final position error %.4f m\n", g_runs, nf_min, nf_sum / B, nf_max, err_sum / B);
+    printf("pose NEES over %.0f member-steps: mean %.4f, %.2f %% inside the 95 %% bound (a consistent filter: 3 and 95 %%)\n", counted,
+           counted > 0 ? nees / counted : NAN, counted > 0 ? 100.0 * inside / counted : NAN);
+    printf("member-steps not counted (pose covariance not positive definite, or a non-finite state): %.0f\n", skipped);
+    printf("per-member mean NEES: smallest %.4f, largest %.4f\n", m_min, m_max);
+    printf("members with a skipped batch update (not positive definite): %d; members that ran out of capacity: %d\n", n_notpd, n_cap);
+    slamgpu_ens_destroy(ens);
+    return 0;
+}
 static std::string g_joint_out;
 static void print_joint(slamgpu_ctx *ctx, const std::vector<double> &sum, int slots) {
     std::vector<int32_t> list;
@@ -775,6 +872,27 @@ int main(int argc, char **argv) {
             return EXIT_FAILURE;
         }
         g_ekf_device = ek == "device";
+        // ... and -runs B [-RUNS_SEED s]: B noise realisations of the run as an ensemble of device filters.  Refused from the arguments alone
+        const std::string rn = sim.conf.s("runs"), rs = sim.conf.s("RUNS_SEED");
+        sim.conf.kv.erase("runs");
+        sim.conf.kv.erase("RUNS_SEED");
+        if (!rn.empty()) {
+            const long nb = atol(rn.c_str());
+            const char *why = nullptr;
+            if (sim.conf.method != 0) why = "with -method EKF1 only (a FastSLAM run is an ensemble already: its particles)";
+            else if (!g_ekf_device) why = "with -ekf device (the ensemble lives on the GPU; there is no CPU fallback)";
+            else if (!sim.conf.s("plot").empty() && sim.conf.s("plot") != "none") why = "not with -plot (there is no single estimate to draw)";
+            else if (nb < 1 || nb > 65535) why = "B must be 1 .. 65535";
+            if (why) {
+                fprintf(stderr, "-runs B: %s\n", why);
+                return EXIT_FAILURE;
+            }
+            g_runs = (int) nb;
+            g_runs_seed = rs.empty() ? (uint64_t) sim.conf.SWITCH_SEED_RANDOM : strtoull(rs.c_str(), nullptr, 10);
+        } else if (!rs.empty()) {
+            fprintf(stderr, "-RUNS_SEED s: with -runs B\n");
+            return EXIT_FAILURE;
+        }
         const std::string mr = sim.conf.s("MAP_MERGE_RADIUS"), mc = sim.conf.s("MAP_MERGE_COHOLD");
         if (!mr.empty()) g_merge_radius = atof(mr.c_str());
         if (!mc.empty()) g_merge_cohold = atof(mc.c_str());
@@ -1022,6 +1140,11 @@ int main(int argc, char **argv) {
         sim.seed();
     } else {
         printf("EKFSLAM\n\n");
+        if (g_runs) {
+            const int rce = run_ekf_ensemble(sim, maxsteps);
+            if (log) fclose(log);
+            return rce;
+        }
         ekf.enableBatchUpdate = c.SWITCH_BATCH_UPDATE == 1;
         ekf.useHeading = c.SWITCH_HEADING_KNOWN == 1;
         ekf.wheelBase = c.WHEELBASE;

@@ -1,0 +1,151 @@
+"""ctypes binding of the device EKF-SLAM ensemble (include/slamgpu.h: slamgpu_ens_*), in the manner of ekf.py: no fallback, a
+missing library or GPU is an error."""
+import ctypes as C
+
+import numpy as np
+
+from .capi import SlamGpuError, load_library, _f32, _ptr
+
+EKF_STATUS_CAPACITY = 2  # SLAMGPU_EKF_STATUS_CAPACITY
+NOISE_CONTROL, NOISE_HEADING, NOISE_SENSOR = 1, 2, 4  # SLAMGPU_EKF_ENS_NOISE_*
+CONSISTENCY_FIELDS = ("counted", "not_counted", "sum_nees", "inside_95", "sum_pos_err2", "sum_heading_err2")
+
+
+class EkfEnsConfig(C.Structure):  # slamgpu_ekf_ens_config
+    _fields_ = [("struct_size", C.c_uint32), ("device", C.c_int32), ("members", C.c_int32), ("max_landmarks", C.c_int32),
+                ("use_heading", C.c_int32), ("batch_update", C.c_int32), ("association_known", C.c_int32), ("wheel_base", C.c_float),
+                ("sigma_phi", C.c_float), ("gate_reject", C.c_float), ("gate_augment", C.c_float), ("seed", C.c_uint64),
+                ("external_stream", C.c_uint64)]
+
+
+_bound = False
+
+
+def _lib():
+    global _bound
+    L = load_library()
+    if not _bound:
+        vp, i32, u32, f = C.c_void_p, C.c_int32, C.c_uint32, C.c_float
+        L.slamgpu_ens_create.argtypes = [C.POINTER(EkfEnsConfig), C.POINTER(vp)]
+        L.slamgpu_ens_destroy.argtypes = [vp]
+        L.slamgpu_ens_destroy.restype = None
+        L.slamgpu_ens_sync.argtypes = [vp]
+        L.slamgpu_ens_sim.argtypes = [vp, vp, vp, vp, vp, i32, vp, vp, vp, f, i32, vp]
+        L.slamgpu_ens_sim_noise.argtypes = [vp, f, f, f, vp, vp, i32, u32, vp, vp, vp, vp, f, i32, vp, u32]
+        L.slamgpu_ens_last_inputs.argtypes = [vp, vp, vp, vp]
+        L.slamgpu_ens_dims.argtypes = [vp, vp]
+        L.slamgpu_ens_poses.argtypes = [vp, vp]
+        L.slamgpu_ens_state.argtypes = [vp, i32, vp, vp, i32]
+        L.slamgpu_ens_slab.argtypes = [vp, i32, vp, vp]
+        L.slamgpu_ens_upload.argtypes = [vp, i32, i32, vp, vp, i32]
+        L.slamgpu_ens_status.argtypes = [vp, vp]
+        L.slamgpu_ens_consistency.argtypes = [vp, vp]
+        L.slamgpu_ens_consistency_reset.argtypes = [vp]
+        _bound = True
+    return L
+
+
+def _chk(rc):
+    if rc < 0:
+        raise SlamGpuError(rc, load_library().slamgpu_last_error().decode())
+    return rc
+
+
+class EkfEnsemble:
+    """`members` independent EKF-SLAM filters resident on the GPU: one launch per EKFSLAM::sim of all of them."""
+
+    def __init__(self, members, max_landmarks, use_heading=False, batch_update=True, association_known=False, wheel_base=4.0, sigma_phi=0.0,
+                 gate_reject=4.0, gate_augment=25.0, seed=0, device=0, external_stream=0):
+        self.L = _lib()
+        cfg = EkfEnsConfig(C.sizeof(EkfEnsConfig), device, members, max_landmarks, int(use_heading), int(batch_update), int(association_known),
+                           wheel_base, sigma_phi, gate_reject, gate_augment, seed, external_stream)
+        h = C.c_void_p()
+        _chk(self.L.slamgpu_ens_create(C.byref(cfg), C.byref(h)))
+        self.h, self.cfg, self.members, self.max_landmarks = h, cfg, members, max_landmarks
+        self.cap_dim = 3 + 2 * max_landmarks
+        self.ld = (self.cap_dim + 31) // 32 * 32
+        self._nz = 0
+
+    def close(self):
+        if self.h:
+            self.L.slamgpu_ens_destroy(self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def sync(self):
+        _chk(self.L.slamgpu_ens_sync(self.h))
+
+    def sim(self, VG, phi, Q, dt, z=None, ids=None, Re=None, R=None, observe=0, truth=None):
+        """explicit inputs: VG[members, 2], phi[members], z[members, nz, 2]; ids[nz] shared"""
+        B = self.members
+        VG, phi = _f32(VG, (B, 2)), _f32(phi, (B,))
+        z = None if z is None else _f32(z, (B, -1, 2))
+        ids = None if ids is None else np.ascontiguousarray(ids, np.int32)
+        Q, Re, R, truth = (None if a is None else _f32(a) for a in (Q, Re, R, truth))
+        nz = 0 if z is None else z.shape[1]
+        _chk(self.L.slamgpu_ens_sim(self.h, _ptr(VG), _ptr(phi), _ptr(z), _ptr(ids), nz, _ptr(Q), _ptr(Re), _ptr(R), dt, int(observe), _ptr(truth)))
+        self._nz = nz if observe else 0
+
+    def sim_noise(self, V, G, phi_true, Q, dt, step, z_true=None, ids=None, Re=None, R=None, observe=0, truth=None, Qe=None,
+                  noise=NOISE_CONTROL | NOISE_HEADING | NOISE_SENSOR):
+        """shared noise-free inputs; every member draws its own (Philox stream 5, counter (member, step, 5, q))"""
+        z_true = None if z_true is None else _f32(z_true, (-1, 2))
+        ids = None if ids is None else np.ascontiguousarray(ids, np.int32)
+        Q, Qe, Re, R, truth = (None if a is None else _f32(a) for a in (Q, Qe, Re, R, truth))
+        nz = 0 if z_true is None else z_true.shape[0]
+        _chk(self.L.slamgpu_ens_sim_noise(self.h, V, G, phi_true, _ptr(z_true), _ptr(ids), nz, int(step), _ptr(Q), _ptr(Qe), _ptr(Re), _ptr(R), dt,
+                                              int(observe), _ptr(truth), int(noise)))
+        self._nz = nz if observe else 0
+
+    def last_inputs(self):
+        """(VG[members, 2], phi[members], z[members, nz, 2]) the last step used"""
+        B = self.members
+        VG, phi, z = np.zeros((B, 2), np.float32), np.zeros(B, np.float32), np.zeros((B, self._nz, 2), np.float32)
+        _chk(self.L.slamgpu_ens_last_inputs(self.h, _ptr(VG), _ptr(phi), _ptr(z)))
+        return VG, phi, z
+
+    def dims(self):
+        d = np.zeros(self.members, np.int32)
+        _chk(self.L.slamgpu_ens_dims(self.h, _ptr(d)))
+        return d
+
+    def poses(self):
+        """(xyt[members, 3], Pvv[members, 3, 3]) in double"""
+        out = np.zeros((self.members, 12))
+        _chk(self.L.slamgpu_ens_poses(self.h, _ptr(out)))
+        return out[:, :3].copy(), out[:, 3:].reshape(-1, 3, 3).copy()
+
+    def state(self, b, want_P=True):
+        x = np.zeros(self.cap_dim, np.float32)
+        P = np.zeros((self.cap_dim, self.cap_dim), np.float32) if want_P else None
+        d = _chk(self.L.slamgpu_ens_state(self.h, b, _ptr(x), _ptr(P), self.cap_dim))
+        return x[:d].copy(), (np.ascontiguousarray(P[:d, :d]) if want_P else None)
+
+    def slab(self, b):
+        """member b's whole slab: x[ld], P[cap_dim, ld], padding included"""
+        x, P = np.zeros(self.ld, np.float32), np.zeros((self.cap_dim, self.ld), np.float32)
+        _chk(self.L.slamgpu_ens_slab(self.h, b, _ptr(x), _ptr(P)))
+        return x, P
+
+    def upload(self, b, x, P):
+        x, P = _f32(x), _f32(P)
+        _chk(self.L.slamgpu_ens_upload(self.h, b, x.shape[0], _ptr(x), _ptr(P), P.shape[1]))
+
+    def status(self):
+        s = np.zeros(self.members, np.int32)
+        _chk(self.L.slamgpu_ens_status(self.h, _ptr(s)))
+        return s
+
+    def consistency(self):
+        """[members, 6]: CONSISTENCY_FIELDS"""
+        out = np.zeros((self.members, 6))
+        _chk(self.L.slamgpu_ens_consistency(self.h, _ptr(out)))
+        return out
+
+    def consistency_reset(self):
+        _chk(self.L.slamgpu_ens_consistency_reset(self.h))

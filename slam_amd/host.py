@@ -9,7 +9,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 
 DECLARED_SYMBOLS = [
     "slamhost_last_error", "slamhost_sim_create", "slamhost_sim_destroy", "slamhost_sim_conf", "slamhost_sim_map",
-    "slamhost_sim_control", "slamhost_sim_observe", "slamhost_sim_last_z", "slamhost_sim_true",
+    "slamhost_sim_control", "slamhost_sim_observe", "slamhost_sim_last_z", "slamhost_sim_true", "slamhost_sim_true_controls",
     "slamhost_sim_control_steps", "slamhost_gated_create", "slamhost_gated_destroy", "slamhost_gated_set", "slamhost_gated_step",
     "slamhost_gated_counts", "slamhost_draw_normals", "slamhost_draw_strata", "slamhost_unif_rand",
     "slamhost_synthetic_landmarks", "slamhost_write_map", "slamhost_ekf_create", "slamhost_ekf_destroy", "slamhost_ekf_step",
@@ -59,6 +59,8 @@ def load_library():
         L.slamhost_sim_last_z.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]
         L.slamhost_sim_true.argtypes = [C.c_void_p, C.c_void_p]
         L.slamhost_sim_true.restype = None
+        L.slamhost_sim_true_controls.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]
+        L.slamhost_sim_true_controls.restype = None
         L.slamhost_sim_control_steps.argtypes = [C.c_void_p]
         L.slamhost_sim_control_steps.restype = C.c_int64
         L.slamhost_draw_normals.argtypes = [C.c_int32, C.c_int32, C.c_void_p]
@@ -272,6 +274,12 @@ class HostSim:
         x = np.zeros(3, np.float32)
         self.L.slamhost_sim_true(self.h, _p(x))
         return x
+
+    def true_controls(self):
+        """the true (V, G) of the last control(): the ones that moved the true pose"""
+        V, G = C.c_float(), C.c_float()
+        self.L.slamhost_sim_true_controls(self.h, C.byref(V), C.byref(G))
+        return V.value, G.value
 
     def noise(self):
         f = lambda a: np.array(list(a), np.float32).reshape(2, 2)
