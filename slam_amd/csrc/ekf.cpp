@@ -1,17 +1,14 @@
 // EKF-SLAM on the device (include/slamgpu.h: slamgpu_ekf_*): one joint filter, x and the dense P resident in device memory.
-// Kernels and host side in one unit.  The arithmetic restates slam_amd/csrc/host/ekfslam.cpp (itself the restatement of
-// matzipan/slam algorithms/ekfslam.cpp:17-323 and core.cpp:275-317) stage by stage; where the order of a sum or the form of an
-// update differs from the host's, the kernel says so.  The host tracks dim (it knows the labels): no dimension lives on the device.
+// Kernels and host side in one unit; the stages' arithmetic is in ekf_helpers.h, shared with the ensemble.  It restates host/ekfslam.cpp
+// (itself the restatement of matzipan/slam algorithms/ekfslam.cpp:17-323 and core.cpp:275-317) stage by stage; where the order of a sum
+// or the form of an update differs from the host's, the stage says so.  The host tracks dim (it knows the labels): none on the device.
 #include "slamgpu_ctx.h"
 #include "ekf_helpers.h"
 
 namespace {
 
-constexpr int kEkfBlock = 256;
-constexpr int kChunk = 64;         // observations per chunk of the batch update
-constexpr int kKMax = 2 * kChunk;  // rows of a chunk's innovation: the K extent of the rank update
-constexpr int kTile = 128;         // tile of P per workgroup of ekf_syrk_kernel
-constexpr int kKStep = 32;         // k columns of W1 staged in LDS at a time; a chunk's K is padded with zeros to a multiple of it
+constexpr int kTile = 128;   // tile of P per workgroup of ekf_syrk_kernel
+constexpr int kKStep = 32;   // k columns of W1 staged in LDS at a time; a chunk's K is padded with zeros to a multiple of it
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
@@ -35,25 +32,17 @@ struct EkfWork {
     int32_t *flag;
 };
 
-// (ekf_trig_offset, ekf_observe_model and ekf_inverse2: ekf_helpers.h, shared with the ensemble)
+// (the arithmetic of every stage but the gain and the rank update: ekf_helpers.h, shared with the ensemble)
 
-// EkfSlam::predict.  The pose rows Gv P[0:3, j] over j >= 3 with their mirror, one lane per column; the workgroup that finishes
-// last (a ticket) then writes the 3x3 pose block and the pose, which every workgroup has read by then
+// EkfSlam::predict.  One lane per column j >= 3; the workgroup that finishes last (a ticket) then writes the 3x3 pose block and the
+// pose, which every workgroup has read by then
 __global__ void __launch_bounds__(kEkfBlock) ekf_predict_kernel(float *__restrict__ P, int ld, int dim, float *__restrict__ x, float V, float G,
                                                                  float q00, float q01, float q10, float q11, float dt, float wheel_base,
                                                                  int32_t *ticket) {
     const float th = x[2];
-    const float s = sinf(G + th), c = cosf(G + th);
-    const float vts = V * dt * s, vtc = V * dt * c;
+    const EkfMotion mo = ekf_motion(V, G, th, dt);
     const int j = 3 + blockIdx.x * kEkfBlock + threadIdx.x;
-    if (j < dim) {
-        const float p0 = P[j], p1 = P[(size_t) ld + j], p2 = P[2 * (size_t) ld + j];
-        const float n0 = p0 + (-vts) * p2, n1 = p1 + vtc * p2;  // Gv = [1 0 -vts; 0 1 vtc; 0 0 1]: row 2 stays
-        P[j] = n0;
-        P[(size_t) ld + j] = n1;
-        P[(size_t) j * ld] = n0;
-        P[(size_t) j * ld + 1] = n1;
-    }
+    if (j < dim) ekf_predict_column(P, ld, j, mo.vts, mo.vtc);
     __shared__ int last;
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -63,47 +52,10 @@ __global__ void __launch_bounds__(kEkfBlock) ekf_predict_kernel(float *__restric
     __syncthreads();
     if (!last || threadIdx.x != 0) return;
     *ticket = 0;
-    float Gv[3][3] = {{1, 0, -vts}, {0, 1, vtc}, {0, 0, 1}};
-    float Gu[3][2] = {{dt * c, -vts}, {dt * s, vtc}, {dt * sinf(G) / wheel_base, V * dt * cosf(G) / wheel_base}};
-    const float Q[2][2] = {{q00, q01}, {q10, q11}};
-    float Pvv[3][3], T[3][3], U[3][2];
-#pragma unroll
-    for (int i = 0; i < 3; i++)
-#pragma unroll
-        for (int k = 0; k < 3; k++) Pvv[i][k] = P[(size_t) i * ld + k];
-#pragma unroll
-    for (int i = 0; i < 3; i++) {
-#pragma unroll
-        for (int k = 0; k < 3; k++) {
-            float acc = 0.0f;
-#pragma unroll
-            for (int q = 0; q < 3; q++) acc = acc + Gv[i][q] * Pvv[q][k];
-            T[i][k] = acc;
-        }
-#pragma unroll
-        for (int k = 0; k < 2; k++) {
-            float acc = 0.0f;
-#pragma unroll
-            for (int q = 0; q < 2; q++) acc = acc + Gu[i][q] * Q[q][k];
-            U[i][k] = acc;
-        }
-    }
-    // (the host's dense products leave (i, k) and (k, i) an ulp apart; here the lower triangle is computed and mirrored: P == P^T)
-#pragma unroll
-    for (int i = 0; i < 3; i++)
-#pragma unroll
-        for (int k = 0; k <= i; k++) {
-            float a = 0.0f, b = 0.0f;
-#pragma unroll
-            for (int q = 0; q < 3; q++) a = a + T[i][q] * Gv[k][q];
-#pragma unroll
-            for (int q = 0; q < 2; q++) b = b + U[i][q] * Gu[k][q];
-            P[(size_t) i * ld + k] = a + b;
-            P[(size_t) k * ld + i] = a + b;
-        }
-    x[0] = x[0] + vtc;
-    x[1] = x[1] + vts;
-    x[2] = ekf_trig_offset(th + V * dt * sinf(G) / wheel_base);
+    const float Q[4] = {q00, q01, q10, q11};
+    float Pvv[3][3];
+    ekf_load_pose_block(P, ld, Pvv);
+    ekf_predict_pose(P, ld, x, Pvv, x[0], x[1], th, mo, V, G, dt, wheel_base, Q);
 }
 
 // EkfSlam::observe_heading, first half: the gain W = P[:, 2] / (P22 + R), the column it came from and the innovation.  P and x stay
@@ -112,100 +64,41 @@ __global__ void __launch_bounds__(kEkfBlock) ekf_heading_gain_kernel(const float
     const float S = P[2 * (size_t) ld + 2] + R;
     const float Si = 1.0f / S;
     const int i = blockIdx.x * kEkfBlock + threadIdx.x;
-    if (i < dim) {
-        const float c = P[2 * (size_t) ld + i];  // row 2 = column 2: P is symmetric bit for bit
-        w.c2[i] = c;
-        w.Wh[i] = c * Si;
-    }
+    if (i < dim) ekf_heading_gain(P, ld, i, Si, w.c2, w.Wh);
     if (i == 0) {
         w.hv[0] = ekf_trig_offset(phi - x[2]);
         w.hv[1] = S;
     }
 }
 
-// ... second half: josephUpdate (core.cpp:294-317) with H = e_2^T.  C = I - W H differs from I in column 2 only, so
-// C P C^T + W R W^T + eps I = P - W P[2, :] - P[:, 2] W^T + W (P22 + R) W^T + eps I, ONE element-wise pass over P (the host forms
-// the products densely).  Entry (i, j) and (j, i) evaluate the same expression on commuted operands -- every product and sum
-// rounded on its own, no contraction -- so P stays symmetric bit for bit.  The workgroups of the first row also apply x += W v
+// ... second half: the one-pass Joseph update of ekf_heading_element, a lane per column and gridDim.y rows at a time.  The workgroups
+// of the first row also apply x += W v
 __global__ void __launch_bounds__(kEkfBlock) ekf_heading_kernel(float *__restrict__ P, int ld, int dim, float *__restrict__ x, EkfWork w) {
     const int j = blockIdx.x * kEkfBlock + threadIdx.x;
     if (j >= dim) return;
     const float S = w.hv[1];
     const float wj = w.Wh[j], cj = w.c2[j];
     if (blockIdx.y == 0) x[j] = x[j] + wj * w.hv[0];
-    const float eps = (float) 2.2204e-16;
-    for (int i = blockIdx.y; i < dim; i += gridDim.y) {
-        const float wi = w.Wh[i], ci = w.c2[i];
-        const float a = __fmul_rn(wi, cj), b = __fmul_rn(ci, wj);
-        const float q = __fmul_rn(__fmul_rn(wi, wj), S);
-        float p = __fadd_rn(__fsub_rn(P[(size_t) i * ld + j], __fadd_rn(a, b)), q);
-        if (i == j) p = __fadd_rn(p, eps);
-        P[(size_t) i * ld + j] = p;
-    }
+    for (int i = blockIdx.y; i < dim; i += gridDim.y)
+        P[(size_t) i * ld + j] = ekf_heading_element(P[(size_t) i * ld + j], w.Wh[i], w.c2[i], wj, cj, S, i == j);
 }
 
-// EKFSLAM::dataAssociate (ekfslam.cpp:151-189) as EkfSlam::associate evaluates it, operation by operation (no contraction): one
-// workgroup per observation, its lanes over the features; then the first minimum of nd among the gated pairs, else the plain
-// minimum of nis against the augment gate
+// The gates: one workgroup per observation, its lanes over the features, the lanes' candidates merged through LDS
 __global__ void __launch_bounds__(kEkfBlock) ekf_gate_kernel(const float *__restrict__ P, int ld, int nf, const float *__restrict__ x,
                                                               const float *__restrict__ z, float r00, float r01, float r10, float r11,
                                                               float gate_reject, float gate_augment, int32_t *__restrict__ labels) {
-#pragma clang fp contract(off)
     const int i = blockIdx.x, tid = threadIdx.x;
     const float z0 = z[2 * i], z1 = z[2 * i + 1];
     const float R[4] = {r00, r01, r10, r11};
-    float M[5][5];
-#pragma unroll
-    for (int a = 0; a < 3; a++)
-#pragma unroll
-        for (int b = 0; b < 3; b++) M[a][b] = P[(size_t) a * ld + b];
+    float Pvv[3][3];
+    ekf_load_pose_block(P, ld, Pvv);
     const float inf = __builtin_huge_valf();
     float nbest = inf, outer = inf;
     int jbest = -1;
     for (int j = tid; j < nf; j += kEkfBlock) {
-        float zp[2], H5[10];
-        ekf_observe_model(x, j, true, zp, H5);
-        const float v0 = z0 - zp[0];
-        const float v1 = ekf_trig_offset(z1 - zp[1]);
-        const int f = 3 + 2 * j;
-#pragma unroll
-        for (int a = 0; a < 3; a++)
-#pragma unroll
-            for (int q = 0; q < 2; q++) M[a][3 + q] = M[3 + q][a] = P[(size_t) a * ld + f + q];
-        M[3][3] = P[(size_t) f * ld + f];
-        M[3][4] = M[4][3] = P[(size_t) f * ld + f + 1];
-        M[4][4] = P[(size_t) (f + 1) * ld + f + 1];
-        float HP[2][5];
-#pragma unroll
-        for (int r = 0; r < 2; r++)
-#pragma unroll
-            for (int c = 0; c < 5; c++) {
-                float acc = 0.0f;
-#pragma unroll
-                for (int k = 0; k < 5; k++) acc = acc + H5[5 * r + k] * M[k][c];
-                HP[r][c] = acc;
-            }
-        float S[4];
-#pragma unroll
-        for (int r = 0; r < 2; r++)
-#pragma unroll
-            for (int c = 0; c < 2; c++) {
-                float acc = 0.0f;
-#pragma unroll
-                for (int k = 0; k < 5; k++) acc = acc + HP[r][k] * H5[5 * c + k];
-                S[2 * r + c] = acc + R[2 * r + c];
-            }
-        float Si[4], det;
-        ekf_inverse2(S, Si, &det);
-        const float t0 = v0 * Si[0] + v1 * Si[2], t1 = v0 * Si[1] + v1 * Si[3];
-        const float nis = t0 * v0 + t1 * v1;
-        const float nd = nis + logf(det);
-        if (nis < gate_reject && nd < nbest) {
-            nbest = nd;
-            jbest = j;
-        } else if (nis < outer) {
-            outer = nis;
-        }
+        float nis, nd;
+        ekf_gate_pair(P, ld, x, Pvv, R, z0, z1, j, &nis, &nd);
+        ekf_gate_keep(nbest, outer, jbest, nis, nd, j, gate_reject);
     }
     __shared__ float s_nd[kEkfBlock], s_out[kEkfBlock];
     __shared__ int s_j[kEkfBlock];
@@ -214,130 +107,47 @@ __global__ void __launch_bounds__(kEkfBlock) ekf_gate_kernel(const float *__rest
     s_j[tid] = jbest;
     __syncthreads();
     for (int step = kEkfBlock / 2; step > 0; step >>= 1) {
-        if (tid < step) {
-            const float nb = s_nd[tid + step], ob = s_out[tid + step];
-            const int jb = s_j[tid + step];
-            // (a lane holds the first minimum of its own features; between lanes the lower feature wins a tie)
-            if (jb >= 0 && (s_j[tid] < 0 || nb < s_nd[tid] || (nb == s_nd[tid] && jb < s_j[tid]))) {
-                s_nd[tid] = nb;
-                s_j[tid] = jb;
-            }
-            if (ob < s_out[tid]) s_out[tid] = ob;
-        }
+        if (tid < step) ekf_gate_merge(s_nd[tid], s_out[tid], s_j[tid], s_nd[tid + step], s_out[tid + step], s_j[tid + step]);
         __syncthreads();
     }
-    if (tid == 0) labels[i] = s_j[0] >= 0 ? s_j[0] : (s_out[0] > gate_augment ? SLAMGPU_ASSOC_NEW : SLAMGPU_ASSOC_DISCARD);
+    if (tid == 0) labels[i] = ekf_gate_label(s_out[0], s_j[0], gate_augment);
 }
 
-// EkfSlam::batch_update, a chunk: H5, the innovation v (workgroup column 0) and PHt[2i + a][r] = sum_k H5_i[a][k] P[cols_i[k]][r], k
-// ascending as the host's mulT(P, H).  Five ROWS of P per observation, coalesced along r: symmetry makes them the columns.  PHt is
-// stored k-major, [kKMax][ld]
+// EkfSlam::batch_update, a chunk: H5, the innovation v (workgroup column 0) and P H^T, observation blockIdx.y at the state rows of
+// the workgroup's lanes.  Five ROWS of P per observation, coalesced along r
 __global__ void __launch_bounds__(kEkfBlock) ekf_innov_kernel(const float *__restrict__ P, int ld, int dim, const float *__restrict__ x, EkfObs O,
                                                                float *__restrict__ PHt, EkfWork w) {
     const int i = blockIdx.y, r = blockIdx.x * kEkfBlock + threadIdx.x;
     const int idf = O.idf[i];
-    const bool writer = blockIdx.x == 0 && threadIdx.x == 0;
-    float zp[2], H5[10];
-    ekf_observe_model(x, idf, writer, zp, H5);
-    if (writer) {
-#pragma unroll
-        for (int k = 0; k < 10; k++) w.H5[10 * i + k] = H5[k];
-        w.v[2 * i] = O.z[2 * i] - zp[0];
-        w.v[2 * i + 1] = ekf_trig_offset(O.z[2 * i + 1] - zp[1]);
-    }
+    float H5[10];
+    ekf_innovation(x, idf, blockIdx.x == 0 && threadIdx.x == 0, O.z[2 * i], O.z[2 * i + 1], i, H5, w.H5, w.v);
     if (r >= dim) return;
     const size_t f = 3 + 2 * (size_t) idf;
     const float p[5] = {P[r], P[(size_t) ld + r], P[2 * (size_t) ld + r], P[f * ld + r], P[(f + 1) * ld + r]};
-#pragma unroll
-    for (int a = 0; a < 2; a++) {
-        float acc = 0.0f;
-#pragma unroll
-        for (int k = 0; k < 5; k++) acc = acc + p[k] * H5[5 * a + k];
-        PHt[(size_t) (2 * i + a) * ld + r] = acc;
-    }
+    ekf_pht(p, H5, PHt, ld, i, r);
 }
 
-// ... S = H PHt + R with the host's in-place symmetrisation (the factorisation reads the lower triangle: the true average), then the
-// host's llt_lower, upper_inverse and t = U^-T v in ONE workgroup with S in LDS.  The lower triangle holds L, the strictly upper one
-// the inverse of U = L^T (upper triangular itself; its diagonal is 1 / L's).  Rows are rotated by their index so that neither a walk
-// along a row nor one down a column meets a bank twice.  A pivot that is not positive: flag[0] = 0 -- the chunk's gain and rank
+// ... the innovation covariance, its factorisation, the inverse of the upper factor and t = U^-T v in ONE workgroup with S in LDS
+// (ekf_helpers.h), then U^-1 copied out for ekf_gain_kernel.  A pivot that is not positive: flag[0] = 0 -- the chunk's gain and rank
 // update do nothing -- and SLAMGPU_EKF_STATUS_NOT_PD
 __global__ void __launch_bounds__(kEkfBlock) ekf_chol_kernel(const float *__restrict__ PHt, int ld, EkfObs O, EkfWork w) {
     __shared__ float A[kKMax * kKMax];  // (all of the 64 KB a workgroup may declare: the pivot's verdict travels in the diagonal itself)
-    bool bad = false;
     const int tid = threadIdx.x, n = 2 * O.m;
-#define AT(i, j) A[(i) * kKMax + (((i) + (j)) & (kKMax - 1))]
-    for (int e = tid; e < n * n; e += kEkfBlock) {
-        const int a = e / n, b = e - a * n;
-        const float *h = w.H5 + 10 * (a >> 1) + 5 * (a & 1);
-        const size_t f = 3 + 2 * (size_t) O.idf[a >> 1];
-        const float *row = PHt + (size_t) b * ld;
-        float acc = 0.0f;
-        acc = acc + h[0] * row[0];
-        acc = acc + h[1] * row[1];
-        acc = acc + h[2] * row[2];
-        acc = acc + h[3] * row[f];
-        acc = acc + h[4] * row[f + 1];
-        AT(a, b) = acc + (((a >> 1) == (b >> 1)) ? O.R[2 * (a & 1) + (b & 1)] : 0.0f);
-    }
-    __syncthreads();
-    for (int e = tid; e < n * n; e += kEkfBlock) {
-        const int a = e / n, b = e - a * n;
-        if (a > b) {
-            AT(a, b) = (AT(a, b) + AT(b, a)) * 0.5f;
-            AT(b, a) = 0.0f;
-        }
-    }
-    __syncthreads();
-    for (int k = 0; k < n; k++) {
-        float acc = 0.0f;
-        if (tid == k) {
-            float xk = AT(k, k);
-            if (k > 0) {
-                float sq = AT(k, 0) * AT(k, 0);
-                for (int j = 1; j < k; j++) sq = sq + AT(k, j) * AT(k, j);
-                xk = xk - sq;
-            }
-            AT(k, k) = xk > 0.0f ? sqrtf(xk) : -1.0f;  // (NaN fails the test too)
-        } else if (tid > k && tid < n) {
-            acc = AT(tid, k);
-            for (int j = 0; j < k; j++) acc = acc + AT(tid, j) * (-1.0f * AT(k, j));
-        }
-        __syncthreads();
-        const float dk = AT(k, k);
-        bad = dk < 0.0f;
-        if (bad) break;
-        if (tid > k && tid < n) AT(tid, k) = acc * (1.0f / dk);
-        __syncthreads();
-    }
-    if (bad) {
+    ekf_innov_cov(A, kKMax, n, w.H5, PHt, ld, O.R, [&](int i) { return O.idf[i]; });
+    if (ekf_llt_lower(A, kKMax, n)) {
         if (tid == 0) {
             w.flag[0] = 0;
             atomicOr(&w.flag[1], SLAMGPU_EKF_STATUS_NOT_PD);
         }
         return;
     }
-    // upper_inverse: column j of X = U^-1 belongs to lane j alone
-    if (tid < n) {
-        const int j = tid;
-        for (int i = n - 1; i >= 0; i--) {
-            if (j < i) continue;  // (X(i, j) is an exact zero there: the host multiplies and subtracts zeros)
-            const float a = 1.0f / AT(i, i);
-            const float b = j == i ? a : AT(i, j) * a;
-            if (j > i) AT(i, j) = b;
-            for (int r = 0; r < i; r++) AT(r, j) = AT(r, j) - b * AT(i, r);
-        }
-        float acc = 0.0f;
-        for (int k = 0; k <= j; k++) {
-            const float xkj = k == j ? 1.0f / AT(j, j) : AT(k, j);
-            w.Ui[k * kKMax + j] = xkj;
-            acc = acc + xkj * w.v[k];
-        }
-        for (int k = j + 1; k < n; k++) w.Ui[k * kKMax + j] = 0.0f;
-        w.t[j] = acc;
+    ekf_upper_inverse(A, kKMax, n, w.v, w.t);
+    if (tid < n) {  // (column tid is the lane's own: no barrier)
+        for (int k = 0; k < tid; k++) w.Ui[k * kKMax + tid] = ekf_at(A, kKMax, k, tid);
+        w.Ui[tid * kKMax + tid] = 1.0f / ekf_at(A, kKMax, tid, tid);
+        for (int k = tid + 1; k < n; k++) w.Ui[k * kKMax + tid] = 0.0f;
     }
     if (tid == 0) w.flag[0] = 1;
-#undef AT
 }
 
 // ... W1 = PHt U^-1 (k ascending, as the host's mul) and x += W1 t (the host forms W = W1 U^-T and W v: the same sum, associated
@@ -440,57 +250,15 @@ __global__ void __launch_bounds__(kEkfBlock) ekf_syrk_kernel(float *__restrict__
         }
 }
 
-// EkfSlam::augment, one feature appended at len: the two new rows and columns Gv P[0:3, :] with Gv = [1 0 -r s; 0 1 r c], the
-// 2x2 block and the feature itself
+// EkfSlam::augment, one feature appended at len: a lane per column, lane 0 of the grid the 2x2 block and the feature itself
 __global__ void __launch_bounds__(kEkfBlock) ekf_augment_kernel(float *__restrict__ P, int ld, int len, float *__restrict__ x, float r, float b,
                                                                  float re00, float re01, float re10, float re11) {
-    const float s = sinf(x[2] + b), c = cosf(x[2] + b);
-    const float g02 = -r * s, g12 = r * c;
+    const EkfBearing g = ekf_bearing(x, r, b);
     const int j = blockIdx.x * kEkfBlock + threadIdx.x;
-    if (j < len) {
-        const float p0 = P[j], p1 = P[(size_t) ld + j], p2 = P[2 * (size_t) ld + j];
-        const float d0 = p0 + g02 * p2, d1 = p1 + g12 * p2;
-        P[(size_t) len * ld + j] = d0;
-        P[(size_t) (len + 1) * ld + j] = d1;
-        P[(size_t) j * ld + len] = d0;
-        P[(size_t) j * ld + len + 1] = d1;
-    }
+    if (j < len) ekf_augment_column(P, ld, len, j, g.g02, g.g12);
     if (j != 0) return;
-    x[len] = x[0] + r * c;
-    x[len + 1] = x[1] + r * s;
-    const float Gv[2][3] = {{1, 0, g02}, {0, 1, g12}};
-    const float Gz[2][2] = {{c, g02}, {s, g12}};
-    const float Re[2][2] = {{re00, re01}, {re10, re11}};
-    float T[2][3], U[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; i++) {
-#pragma unroll
-        for (int k = 0; k < 3; k++) {
-            float acc = 0.0f;
-#pragma unroll
-            for (int q = 0; q < 3; q++) acc = acc + Gv[i][q] * P[(size_t) q * ld + k];
-            T[i][k] = acc;
-        }
-#pragma unroll
-        for (int k = 0; k < 2; k++) {
-            float acc = 0.0f;
-#pragma unroll
-            for (int q = 0; q < 2; q++) acc = acc + Gz[i][q] * Re[q][k];
-            U[i][k] = acc;
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < 2; i++)
-#pragma unroll
-        for (int k = 0; k <= i; k++) {  // (the lower triangle, mirrored, as in ekf_predict_kernel)
-            float a2 = 0.0f, b2 = 0.0f;
-#pragma unroll
-            for (int q = 0; q < 3; q++) a2 = a2 + T[i][q] * Gv[k][q];
-#pragma unroll
-            for (int q = 0; q < 2; q++) b2 = b2 + U[i][q] * Gz[k][q];
-            P[(size_t) (len + i) * ld + len + k] = a2 + b2;
-            P[(size_t) (len + k) * ld + len + i] = a2 + b2;
-        }
+    const float Re[4] = {re00, re01, re10, re11};
+    ekf_augment_block(P, ld, len, x, r, g, Re);
 }
 
 // slamgpu_ekf_block: out[a][b] = P[idx[a]][idx[b]]
@@ -506,14 +274,13 @@ __global__ void __launch_bounds__(kEkfBlock) ekf_block_kernel(const float *__res
 
 struct slamgpu_ekf {
     slamgpu_ekf_config cfg{};
-    hipStream_t stream = nullptr;
-    bool own_stream = true;
+    EkfStream stream;
     int dim = 3, ld = 0, cap_dim = 0;
     DevBuf<float> P, x, PHt, W1, work, z_dev, blk_dev;
     DevBuf<int32_t> flag, lab_dev, idx_dev;
     PinBuf<char> pin;
     EkfWork w{};
-    std::vector<int32_t> table;  // association_known: id -> feature, -1 not seen yet
+    EkfIdTable table;  // association_known
 };
 
 namespace {
@@ -521,12 +288,6 @@ namespace {
 int ekf_check(slamgpu_ekf *e) {
     if (!e) return fail(SLAMGPU_ERR_INVALID, "null EKF handle");
     HIP_TRY(hipSetDevice(e->cfg.device));
-    return 0;
-}
-
-int ekf_launched(const char *what) {
-    const hipError_t err = hipGetLastError();
-    if (err != hipSuccess) return fail(SLAMGPU_ERR_HIP, "%s launch: %s", what, hipGetErrorString(err));
     return 0;
 }
 
@@ -614,12 +375,12 @@ void ekf_release(slamgpu_ekf *e) {
     e->lab_dev.release();
     e->idx_dev.release();
     e->pin.release();
-    if (e->own_stream && e->stream) (void) hipStreamDestroy(e->stream);
+    e->stream.release();
     delete e;
 }
 
 int ekf_reserve(slamgpu_ekf *e) {
-    if (e->own_stream) HIP_TRY(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking));
+    if (int rc = e->stream.create()) return rc;
     const size_t ld = (size_t) e->ld, rows = ((size_t) e->cap_dim + kTile - 1) / kTile * kTile;
     if (int rc = e->P.reserve_zeroed(ld * e->cap_dim, "EKF covariance P")) return rc;
     if (int rc = e->x.reserve_zeroed(ld, "EKF state x")) return rc;
@@ -646,21 +407,12 @@ int slamgpu_ekf_create(const slamgpu_ekf_config *cfg, slamgpu_ekf **out) {
     *out = nullptr;
     if (cfg->struct_size != sizeof(slamgpu_ekf_config))
         return fail(SLAMGPU_ERR_INVALID, "slamgpu_ekf_config.struct_size %u != %zu (ABI mismatch)", cfg->struct_size, sizeof(slamgpu_ekf_config));
-    if (cfg->max_landmarks < 0 || cfg->max_landmarks > 32000) return fail(SLAMGPU_ERR_INVALID, "max_landmarks %d outside [0, 32000]", cfg->max_landmarks);
-    if (!(cfg->wheel_base > 0.0f) || !(cfg->sigma_phi >= 0.0f) || !(cfg->gate_reject >= 0.0f) || !(cfg->gate_augment >= 0.0f))
-        return fail(SLAMGPU_ERR_INVALID, "wheel_base must be positive, sigma_phi and the gates non-negative");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(SLAMGPU_ERR_NO_DEVICE, "no HIP device: libslamgpu has no CPU fallback");
-    if (cfg->device < 0 || cfg->device >= ndev) return fail(SLAMGPU_ERR_INVALID, "device %d out of range (%d devices)", cfg->device, ndev);
-    HIP_TRY(hipSetDevice(cfg->device));
+    if (int rc = ekf_check_config(cfg, 32000)) return rc;
     slamgpu_ekf *e = new slamgpu_ekf();
     e->cfg = *cfg;
-    e->cap_dim = 3 + 2 * cfg->max_landmarks;
-    e->ld = (e->cap_dim + 31) / 32 * 32;
-    if (cfg->external_stream) {
-        e->stream = reinterpret_cast<hipStream_t>(cfg->external_stream);
-        e->own_stream = false;
-    }
+    e->cap_dim = ekf_cap_dim(cfg->max_landmarks);
+    e->ld = ekf_ld(e->cap_dim);
+    e->stream.adopt(cfg->external_stream);
     if (int rc = ekf_reserve(e)) {
         ekf_release(e);
         return rc;
@@ -716,8 +468,7 @@ int slamgpu_ekf_sim(slamgpu_ekf *e, float V, float G, const float Q[4], float dt
     if (observe && known) {  // EkfSlam::associate_known: it does not look at the state, so the capacity is checked before anything runs
         for (int32_t i = 0; i < nz; i++) {
             if (ids[i] < 0) return fail(SLAMGPU_ERR_INVALID, "ids[%d] = %d", i, ids[i]);
-            if ((size_t) ids[i] >= e->table.size()) e->table.resize((size_t) ids[i] + 1, -1);
-            const int32_t f = e->table[ids[i]];
+            const int32_t f = e->table.lookup(ids[i]);
             if (f < 0) {
                 zn.insert(zn.end(), {z[2 * i], z[2 * i + 1]});
                 idn.push_back(ids[i]);
@@ -752,7 +503,7 @@ int slamgpu_ekf_sim(slamgpu_ekf *e, float V, float G, const float Q[4], float dt
     if (e->cfg.batch_update)
         if (int rc = ekf_update(e, zf.data(), idf.data(), (int32_t) idf.size(), R)) return rc;
     if (int rc = ekf_augment(e, zn.data(), (int32_t) (zn.size() / 2), Re)) return rc;
-    for (size_t i = 0; i < idn.size(); i++) e->table[idn[i]] = nf0 + (int32_t) i;
+    e->table.learn(idn, nf0);
     return 0;
 }
 
@@ -777,10 +528,7 @@ int slamgpu_ekf_state(slamgpu_ekf *e, float *x, float *P, int32_t ld_out) {
     if (int rc = ekf_check(e)) return rc;
     if (P && ld_out < e->dim) return fail(SLAMGPU_ERR_INVALID, "ld_out %d < dim %d", ld_out, e->dim);
     HIP_TRY(hipStreamSynchronize(e->stream));
-    if (x) HIP_TRY(hipMemcpy(x, e->x, sizeof(float) * (size_t) e->dim, hipMemcpyDeviceToHost));
-    if (P)
-        HIP_TRY(hipMemcpy2D(P, sizeof(float) * (size_t) ld_out, e->P, sizeof(float) * (size_t) e->ld, sizeof(float) * (size_t) e->dim, (size_t) e->dim,
-                            hipMemcpyDeviceToHost));
+    if (int rc = ekf_state_out(e->x, e->P, e->ld, e->dim, x, P, ld_out)) return rc;
     return e->dim;
 }
 
@@ -804,15 +552,9 @@ int slamgpu_ekf_block(slamgpu_ekf *e, const int32_t *idx, int32_t k, float *out)
 
 int slamgpu_ekf_upload(slamgpu_ekf *e, int32_t dim, const float *x, const float *P, int32_t ld_in) {
     if (int rc = ekf_check(e)) return rc;
-    if (dim < 3 || dim > e->cap_dim || ((dim - 3) & 1) || !x || !P || ld_in < dim)
-        return fail(SLAMGPU_ERR_INVALID, "bad upload: dim %d (3 + 2 nf up to %d), ld_in %d", dim, e->cap_dim, ld_in);
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    HIP_TRY(hipMemcpy(e->x, x, sizeof(float) * (size_t) dim, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy2D(e->P, sizeof(float) * (size_t) e->ld, P, sizeof(float) * (size_t) ld_in, sizeof(float) * (size_t) dim, (size_t) dim,
-                        hipMemcpyHostToDevice));
+    if (int rc = ekf_state_in(e->stream, e->x, e->P, e->ld, e->cap_dim, dim, x, P, ld_in)) return rc;
     e->dim = dim;
-    e->table.assign((size_t) nf_of(e), 0);
-    for (int f = 0; f < nf_of(e); f++) e->table[f] = f;
+    e->table.identity(nf_of(e));
     return 0;
 }
 

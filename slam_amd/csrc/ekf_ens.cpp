@@ -1,7 +1,7 @@
 // EKF-SLAM ensemble on the device (include/slamgpu.h: slamgpu_ens_*): B independent filters, member-major slabs resident in
 // device memory, ONE launch per EKFSLAM::sim of all of them.  Kernels and host side in one unit.  Workgroup b owns member b from
-// predict to augment, __syncthreads() between the stages: no grid-wide meeting, no spin, no atomics.  The arithmetic is ekf.cpp's
-// stage by stage (itself the restatement of slam_amd/csrc/host/ekfslam.cpp); where the order of a sum differs, the stage says so.
+// predict to augment, __syncthreads() between the stages: no grid-wide meeting, no spin, no atomics.  The arithmetic of the
+// stages is the single filter's, the same functions (ekf_helpers.h); the ensemble's own are the in-place W1 and the VALU rank update.
 #include "slamgpu_ctx.h"
 #define SLAM_KNS slam_ekf_ens
 #include "device_math.h"  // philox4x32, u01, box_muller3, as they are
@@ -14,9 +14,6 @@ using slam_ekf_ens::philox4x32;
 using slam_ekf_ens::U4;
 using slam_ekf_ens::u01;
 
-constexpr int kEnsBlock = 256;
-constexpr int kChunk = 64;         // observations per chunk of the batch update
-constexpr int kKMax = 2 * kChunk;  // rows of a chunk's innovation
 constexpr int kWork = 10 * kChunk + 2 * kKMax;  // floats of a member's small work area: H5 [kChunk][10] | v [kKMax] | t [kKMax]
 constexpr int kMaxNz = 4096;
 constexpr int kMaxId = 1 << 20;  // known association: ids index the host's table
@@ -45,56 +42,7 @@ struct EnsArgs {
     float truth[3];
 };
 
-// EKFSLAM::dataAssociate for one (observation, feature) pair as ekf_gate_kernel evaluates it, operation by operation
-__device__ __forceinline__ void ens_gate_pair(const float *P, int ld, const float *x, const float Pvv[3][3], const float R[4], float z0, float z1, int j,
-                                     float *nis_out, float *nd_out) {
-#pragma clang fp contract(off)
-    float M[5][5];
-#pragma unroll
-    for (int a = 0; a < 3; a++)
-#pragma unroll
-        for (int b = 0; b < 3; b++) M[a][b] = Pvv[a][b];
-    float zp[2], H5[10];
-    ekf_observe_model(x, j, true, zp, H5);
-    const float v0 = z0 - zp[0];
-    const float v1 = ekf_trig_offset(z1 - zp[1]);
-    const int f = 3 + 2 * j;
-#pragma unroll
-    for (int a = 0; a < 3; a++)
-#pragma unroll
-        for (int q = 0; q < 2; q++) M[a][3 + q] = M[3 + q][a] = P[(size_t) a * ld + f + q];
-    M[3][3] = P[(size_t) f * ld + f];
-    M[3][4] = M[4][3] = P[(size_t) f * ld + f + 1];
-    M[4][4] = P[(size_t) (f + 1) * ld + f + 1];
-    float HP[2][5];
-#pragma unroll
-    for (int r = 0; r < 2; r++)
-#pragma unroll
-        for (int c = 0; c < 5; c++) {
-            float acc = 0.0f;
-#pragma unroll
-            for (int k = 0; k < 5; k++) acc = acc + H5[5 * r + k] * M[k][c];
-            HP[r][c] = acc;
-        }
-    float S[4];
-#pragma unroll
-    for (int r = 0; r < 2; r++)
-#pragma unroll
-        for (int c = 0; c < 2; c++) {
-            float acc = 0.0f;
-#pragma unroll
-            for (int k = 0; k < 5; k++) acc = acc + HP[r][k] * H5[5 * c + k];
-            S[2 * r + c] = acc + R[2 * r + c];
-        }
-    float Si[4], det;
-    ekf_inverse2(S, Si, &det);
-    const float t0 = v0 * Si[0] + v1 * Si[2], t1 = v0 * Si[1] + v1 * Si[3];
-    const float nis = t0 * v0 + t1 * v1;
-    *nis_out = nis;
-    *nd_out = nis + logf(det);
-}
-
-__global__ void __launch_bounds__(kEnsBlock) ekf_ens_kernel(EnsArgs a) {
+__global__ void __launch_bounds__(kEkfBlock) ekf_ens_kernel(EnsArgs a) {
     extern __shared__ float lds[];  // heading: column 2 of P and the gain, [2][ld]; update: the innovation covariance, [np][np]
     const int b = blockIdx.x, tid = threadIdx.x;
     const int ld = a.ld, nz = a.nz;
@@ -126,7 +74,7 @@ __global__ void __launch_bounds__(kEnsBlock) ekf_ens_kernel(EnsArgs a) {
             vg_in[1] = G;
             *phi_in = phi;
         }
-        for (int i = tid; i < nz; i += kEnsBlock) {
+        for (int i = tid; i < nz; i += kEkfBlock) {
             float zr = z_true[2 * i], zb = z_true[2 * i + 1];
             if (a.noise & SLAMGPU_EKF_ENS_NOISE_SENSOR) {  // Simulator::observe
                 float g0, g1, g2;
@@ -144,86 +92,27 @@ __global__ void __launch_bounds__(kEnsBlock) ekf_ens_kernel(EnsArgs a) {
     // ---- EkfSlam::predict: everything read into registers, a barrier, then the writes (no ticket: one workgroup) ---------------
     {
         const float th = x[2], x0 = x[0], x1 = x[1];
-        const float s = sinf(G + th), c = cosf(G + th);
-        const float vts = V * a.dt * s, vtc = V * a.dt * c;
+        const EkfMotion mo = ekf_motion(V, G, th, a.dt);
         float Pvv[3][3];
-#pragma unroll
-        for (int i = 0; i < 3; i++)
-#pragma unroll
-            for (int k = 0; k < 3; k++) Pvv[i][k] = P[(size_t) i * ld + k];
+        ekf_load_pose_block(P, ld, Pvv);
         __syncthreads();
-        for (int j = 3 + tid; j < dim; j += kEnsBlock) {
-            const float p0 = P[j], p1 = P[(size_t) ld + j], p2 = P[2 * (size_t) ld + j];
-            const float n0 = p0 + (-vts) * p2, n1 = p1 + vtc * p2;  // Gv = [1 0 -vts; 0 1 vtc; 0 0 1]: row 2 stays
-            P[j] = n0;
-            P[(size_t) ld + j] = n1;
-            P[(size_t) j * ld] = n0;
-            P[(size_t) j * ld + 1] = n1;
-        }
-        if (tid == 0) {
-            const float Gv[3][3] = {{1, 0, -vts}, {0, 1, vtc}, {0, 0, 1}};
-            const float Gu[3][2] = {{a.dt * c, -vts}, {a.dt * s, vtc}, {a.dt * sinf(G) / a.wheel_base, V * a.dt * cosf(G) / a.wheel_base}};
-            float T[3][3], U[3][2];
-#pragma unroll
-            for (int i = 0; i < 3; i++) {
-#pragma unroll
-                for (int k = 0; k < 3; k++) {
-                    float acc = 0.0f;
-#pragma unroll
-                    for (int q = 0; q < 3; q++) acc = acc + Gv[i][q] * Pvv[q][k];
-                    T[i][k] = acc;
-                }
-#pragma unroll
-                for (int k = 0; k < 2; k++) {
-                    float acc = 0.0f;
-#pragma unroll
-                    for (int q = 0; q < 2; q++) acc = acc + Gu[i][q] * a.Q[2 * q + k];
-                    U[i][k] = acc;
-                }
-            }
-#pragma unroll
-            for (int i = 0; i < 3; i++)
-#pragma unroll
-                for (int k = 0; k <= i; k++) {  // the lower triangle, mirrored, as ekf_predict_kernel does
-                    float p = 0.0f, q2 = 0.0f;
-#pragma unroll
-                    for (int q = 0; q < 3; q++) p = p + T[i][q] * Gv[k][q];
-#pragma unroll
-                    for (int q = 0; q < 2; q++) q2 = q2 + U[i][q] * Gu[k][q];
-                    P[(size_t) i * ld + k] = p + q2;
-                    P[(size_t) k * ld + i] = p + q2;
-                }
-            x[0] = x0 + vtc;
-            x[1] = x1 + vts;
-            x[2] = ekf_trig_offset(th + V * a.dt * sinf(G) / a.wheel_base);
-        }
+        for (int j = 3 + tid; j < dim; j += kEkfBlock) ekf_predict_column(P, ld, j, mo.vts, mo.vtc);
+        if (tid == 0) ekf_predict_pose(P, ld, x, Pvv, x0, x1, th, mo, V, G, a.dt, a.wheel_base, a.Q);
         __syncthreads();
     }
 
-    // ---- EkfSlam::observe_heading: the single filter's one-pass form, every product and sum rounded on its own ------------------
+    // ---- EkfSlam::observe_heading: the one-pass form, column 2 of P and the gain in LDS, a lane per column ----------------------
     if (a.use_heading) {
         float *c2 = lds, *Wh = lds + ld;
         const float S = P[2 * (size_t) ld + 2] + a.r_phi;
         const float Si = 1.0f / S;
         const float hv = ekf_trig_offset(phi - x[2]);
-        for (int i = tid; i < dim; i += kEnsBlock) {
-            const float c = P[2 * (size_t) ld + i];  // row 2 = column 2: P is symmetric bit for bit
-            c2[i] = c;
-            Wh[i] = c * Si;
-        }
+        for (int i = tid; i < dim; i += kEkfBlock) ekf_heading_gain(P, ld, i, Si, c2, Wh);
         __syncthreads();
-        const float eps = (float) 2.2204e-16;
-        for (int j = tid; j < dim; j += kEnsBlock) {
+        for (int j = tid; j < dim; j += kEkfBlock) {
             const float wj = Wh[j], cj = c2[j];
             x[j] = x[j] + wj * hv;
-            for (int i = 0; i < dim; i++) {
-                const float wi = Wh[i], ci = c2[i];
-                const float pa = __fmul_rn(wi, cj), pb = __fmul_rn(ci, wj);
-                const float q = __fmul_rn(__fmul_rn(wi, wj), S);
-                float p = __fadd_rn(__fsub_rn(P[(size_t) i * ld + j], __fadd_rn(pa, pb)), q);
-                if (i == j) p = __fadd_rn(p, eps);
-                P[(size_t) i * ld + j] = p;
-            }
+            for (int i = 0; i < dim; i++) P[(size_t) i * ld + j] = ekf_heading_element(P[(size_t) i * ld + j], Wh[i], c2[i], wj, cj, S, i == j);
         }
         __syncthreads();
     }
@@ -232,45 +121,32 @@ __global__ void __launch_bounds__(kEnsBlock) ekf_ens_kernel(EnsArgs a) {
         const int nf = (dim - 3) / 2;
         // ---- labels: the shared table's, or the gates over (observation, feature) pairs against the state as it stands --------------
         if (a.known) {
-            for (int i = tid; i < nz; i += kEnsBlock) {
+            for (int i = tid; i < nz; i += kEkfBlock) {
                 const int l = lab_known[i];
                 lab[i] = l >= nf ? SLAMGPU_ASSOC_DISCARD : l;  // (a member that lacks the feature ignores the observation)
             }
         } else {
-            // a wave per observation, its lanes over the features; a lane keeps the first minimum of its own features and between
-            // lanes the lower feature wins a tie: the first minimum of all
+            // a wave per observation, its lanes over the features, the lanes' candidates merged through the wave's shuffles
             const int wave = tid >> 6, lane = tid & 63;
             float Pvv[3][3];
-#pragma unroll
-            for (int i = 0; i < 3; i++)
-#pragma unroll
-                for (int k = 0; k < 3; k++) Pvv[i][k] = P[(size_t) i * ld + k];
+            ekf_load_pose_block(P, ld, Pvv);
             const float inf = __builtin_huge_valf();
-            for (int i = wave; i < nz; i += kEnsBlock / 64) {
+            for (int i = wave; i < nz; i += kEkfBlock / 64) {
                 const float z0 = z_in[2 * i], z1 = z_in[2 * i + 1];
                 float nbest = inf, outer = inf;
                 int jbest = -1;
                 for (int j = lane; j < nf; j += 64) {
                     float nis, nd;
-                    ens_gate_pair(P, ld, x, Pvv, a.Re, z0, z1, j, &nis, &nd);
-                    if (nis < a.gate_reject && nd < nbest) {
-                        nbest = nd;
-                        jbest = j;
-                    } else if (nis < outer) {
-                        outer = nis;
-                    }
+                    ekf_gate_pair(P, ld, x, Pvv, a.Re, z0, z1, j, &nis, &nd);
+                    ekf_gate_keep(nbest, outer, jbest, nis, nd, j, a.gate_reject);
                 }
 #pragma unroll
                 for (int s = 32; s > 0; s >>= 1) {
                     const float nb = __shfl_xor(nbest, s, 64), ob = __shfl_xor(outer, s, 64);
                     const int jb = __shfl_xor(jbest, s, 64);
-                    if (jb >= 0 && (jbest < 0 || nb < nbest || (nb == nbest && jb < jbest))) {
-                        nbest = nb;
-                        jbest = jb;
-                    }
-                    if (ob < outer) outer = ob;
+                    ekf_gate_merge(nbest, outer, jbest, nb, ob, jb);
                 }
-                if (lane == 0) lab[i] = jbest >= 0 ? jbest : (outer > a.gate_augment ? SLAMGPU_ASSOC_NEW : SLAMGPU_ASSOC_DISCARD);
+                if (lane == 0) lab[i] = ekf_gate_label(outer, jbest, a.gate_augment);
             }
         }
         __syncthreads();
@@ -291,117 +167,42 @@ __global__ void __launch_bounds__(kEnsBlock) ekf_ens_kernel(EnsArgs a) {
         __syncthreads();
         const int m = cnt[0], nn = cnt[1];
         const int np = a.np;
-#define AT(i, j) lds[(i) * np + (((i) + (j)) & (np - 1))]  // ekf_chol_kernel's rotated rows
 
         // ---- EkfSlam::batch_update, chunk by chunk ----------------------------------------------------------------------------------
         for (int at = 0; at < m; at += kChunk) {
             const int mc = min(kChunk, m - at), n = 2 * mc;
             if (tid < mc) {  // H5 and the innovation of observation at + tid
                 const int o = mi[at + tid];
-                float zp[2], H5[10];
-                ekf_observe_model(x, lab[o], true, zp, H5);
-#pragma unroll
-                for (int k = 0; k < 10; k++) H5g[10 * tid + k] = H5[k];
-                vg[2 * tid] = z_in[2 * o] - zp[0];
-                vg[2 * tid + 1] = ekf_trig_offset(z_in[2 * o + 1] - zp[1]);
+                float H5[10];
+                ekf_innovation(x, lab[o], true, z_in[2 * o], z_in[2 * o + 1], tid, H5, H5g, vg);
             }
             __syncthreads();
-            // PHt[2i + a][r] = sum_k H5_i[a][k] P[cols_i[k]][r], k ascending as the host's mulT(P, H); rows of P, coalesced along r
-            for (int r = tid; r < dim; r += kEnsBlock) {
+            for (int r = tid; r < dim; r += kEkfBlock) {  // P H^T: rows of P, coalesced along r
                 const float p0 = P[r], p1 = P[(size_t) ld + r], p2 = P[2 * (size_t) ld + r];
                 for (int i = 0; i < mc; i++) {
                     const size_t f = 3 + 2 * (size_t) lab[mi[at + i]];
-                    const float p3 = P[f * ld + r], p4 = P[(f + 1) * ld + r];
-                    const float *h = H5g + 10 * i;
-#pragma unroll
-                    for (int q = 0; q < 2; q++) {
-                        float acc = 0.0f;
-                        acc = acc + p0 * h[5 * q];
-                        acc = acc + p1 * h[5 * q + 1];
-                        acc = acc + p2 * h[5 * q + 2];
-                        acc = acc + p3 * h[5 * q + 3];
-                        acc = acc + p4 * h[5 * q + 4];
-                        PHt[(size_t) (2 * i + q) * ld + r] = acc;
-                    }
+                    const float p[5] = {p0, p1, p2, P[f * ld + r], P[(f + 1) * ld + r]};
+                    ekf_pht(p, H5g + 10 * i, PHt, ld, i, r);
                 }
             }
             __syncthreads();
-            // S = H PHt + R, the host's in-place symmetrisation, llt_lower, upper_inverse and t = U^-T v: ekf_chol_kernel's, in LDS
-            for (int e = tid; e < n * n; e += kEnsBlock) {
-                const int ra = e / n, cb = e - ra * n;
-                const float *h = H5g + 10 * (ra >> 1) + 5 * (ra & 1);
-                const size_t f = 3 + 2 * (size_t) lab[mi[at + (ra >> 1)]];
-                const float *row = PHt + (size_t) cb * ld;
-                float acc = 0.0f;
-                acc = acc + h[0] * row[0];
-                acc = acc + h[1] * row[1];
-                acc = acc + h[2] * row[2];
-                acc = acc + h[3] * row[f];
-                acc = acc + h[4] * row[f + 1];
-                AT(ra, cb) = acc + (((ra >> 1) == (cb >> 1)) ? a.R[2 * (ra & 1) + (cb & 1)] : 0.0f);
-            }
-            __syncthreads();
-            for (int e = tid; e < n * n; e += kEnsBlock) {
-                const int ra = e / n, cb = e - ra * n;
-                if (ra > cb) {
-                    AT(ra, cb) = (AT(ra, cb) + AT(cb, ra)) * 0.5f;
-                    AT(cb, ra) = 0.0f;
-                }
-            }
-            __syncthreads();
-            bool bad = false;
-            for (int k = 0; k < n; k++) {
-                float acc = 0.0f;
-                if (tid == k) {
-                    float xk = AT(k, k);
-                    if (k > 0) {
-                        float sq = AT(k, 0) * AT(k, 0);
-                        for (int j = 1; j < k; j++) sq = sq + AT(k, j) * AT(k, j);
-                        xk = xk - sq;
-                    }
-                    AT(k, k) = xk > 0.0f ? sqrtf(xk) : -1.0f;  // (NaN fails the test too)
-                } else if (tid > k && tid < n) {
-                    acc = AT(tid, k);
-                    for (int j = 0; j < k; j++) acc = acc + AT(tid, j) * (-1.0f * AT(k, j));
-                }
-                __syncthreads();
-                const float dk = AT(k, k);
-                bad = dk < 0.0f;
-                if (bad) break;
-                if (tid > k && tid < n) AT(tid, k) = acc * (1.0f / dk);
-                __syncthreads();
-            }
-            if (bad) {  // the chunk is skipped: neither x nor P changes (every lane read the same pivot: the branch is uniform)
+            ekf_innov_cov(lds, np, n, H5g, PHt, ld, a.R, [&](int i) { return lab[mi[at + i]]; });
+            if (ekf_llt_lower(lds, np, n)) {  // the chunk is skipped: neither x nor P changes (the verdict is uniform)
                 if (tid == 0) a.status[b] |= SLAMGPU_EKF_STATUS_NOT_PD;
                 __syncthreads();
                 continue;
             }
-            if (tid < n) {  // upper_inverse: column j of X = U^-1 belongs to lane j alone; the lower triangle keeps L
-                const int j = tid;
-                for (int i = n - 1; i >= 0; i--) {
-                    if (j < i) continue;
-                    const float d = 1.0f / AT(i, i);
-                    const float bj = j == i ? d : AT(i, j) * d;
-                    if (j > i) AT(i, j) = bj;
-                    for (int r = 0; r < i; r++) AT(r, j) = AT(r, j) - bj * AT(i, r);
-                }
-                float acc = 0.0f;
-                for (int k = 0; k <= j; k++) {
-                    const float xkj = k == j ? 1.0f / AT(j, j) : AT(k, j);
-                    acc = acc + xkj * vg[k];
-                }
-                tg[j] = acc;
-            }
+            ekf_upper_inverse(lds, np, n, vg, tg);
             __syncthreads();
-            if (tid < n) AT(tid, tid) = 1.0f / AT(tid, tid);  // the diagonal of U^-1 in its place: AT(k, c), k <= c, is now X(k, c)
+            if (tid < n) ekf_at(lds, np, tid, tid) = 1.0f / ekf_at(lds, np, tid, tid);  // the diagonal of U^-1 in its place: (k, c), k <= c, is now X(k, c)
             __syncthreads();
             // W1 = PHt U^-1 (k ascending, as the host's mul) IN PLACE of PHt: column c needs the columns k <= c only, so c runs
             // downwards; and x += W1 t (the host forms W = W1 U^-T and W v: the same sum, associated the other way)
-            for (int r = tid; r < dim; r += kEnsBlock) {
+            for (int r = tid; r < dim; r += kEkfBlock) {
                 float xacc = 0.0f;
                 for (int c = n - 1; c >= 0; c--) {
                     float acc = 0.0f;
-                    for (int k = 0; k <= c; k++) acc = acc + PHt[(size_t) k * ld + r] * AT(k, c);
+                    for (int k = 0; k <= c; k++) acc = acc + PHt[(size_t) k * ld + r] * ekf_at(lds, np, k, c);
                     PHt[(size_t) c * ld + r] = acc;
                     xacc = xacc + acc * tg[c];
                 }
@@ -413,7 +214,7 @@ __global__ void __launch_bounds__(kEnsBlock) ekf_ens_kernel(EnsArgs a) {
             // mirrored: P == P^T bit for bit.  W1's columns >= dim (allocated, never data) only reach accumulators that are not stored
             {
                 const int wave = tid >> 6, lane = tid & 63;
-                for (int i0 = 4 * wave; i0 < dim; i0 += 4 * (kEnsBlock / 64))
+                for (int i0 = 4 * wave; i0 < dim; i0 += 4 * (kEkfBlock / 64))
                     for (int j = lane; j <= i0 + 3 && j < dim; j += 64) {
                         float acc0 = 0.0f, acc1 = 0.0f, acc2 = 0.0f, acc3 = 0.0f;
                         for (int k = 0; k < n; k++) {
@@ -438,58 +239,14 @@ __global__ void __launch_bounds__(kEnsBlock) ekf_ens_kernel(EnsArgs a) {
             }
             __syncthreads();
         }
-#undef AT
 
         // ---- EkfSlam::augment, one feature after another: each one's rows start from the pose rows, which the previous one left alone
         for (int q = 0; q < nn; q++) {
             const int o = ni[q], len = dim;
-            const float r = z_in[2 * o], bb = z_in[2 * o + 1];
-            const float s = sinf(x[2] + bb), c = cosf(x[2] + bb);
-            const float g02 = -r * s, g12 = r * c;
-            for (int j = tid; j < len; j += kEnsBlock) {
-                const float p0 = P[j], p1 = P[(size_t) ld + j], p2 = P[2 * (size_t) ld + j];
-                const float d0 = p0 + g02 * p2, d1 = p1 + g12 * p2;
-                P[(size_t) len * ld + j] = d0;
-                P[(size_t) (len + 1) * ld + j] = d1;
-                P[(size_t) j * ld + len] = d0;
-                P[(size_t) j * ld + len + 1] = d1;
-            }
-            if (tid == 0) {
-                x[len] = x[0] + r * c;
-                x[len + 1] = x[1] + r * s;
-                const float Gv[2][3] = {{1, 0, g02}, {0, 1, g12}};
-                const float Gz[2][2] = {{c, g02}, {s, g12}};
-                float T[2][3], U[2][2];
-#pragma unroll
-                for (int i = 0; i < 2; i++) {
-#pragma unroll
-                    for (int k = 0; k < 3; k++) {
-                        float acc = 0.0f;
-#pragma unroll
-                        for (int t = 0; t < 3; t++) acc = acc + Gv[i][t] * P[(size_t) t * ld + k];
-                        T[i][k] = acc;
-                    }
-#pragma unroll
-                    for (int k = 0; k < 2; k++) {
-                        float acc = 0.0f;
-#pragma unroll
-                        for (int t = 0; t < 2; t++) acc = acc + Gz[i][t] * a.Re[2 * t + k];
-                        U[i][k] = acc;
-                    }
-                }
-#pragma unroll
-                for (int i = 0; i < 2; i++)
-#pragma unroll
-                    for (int k = 0; k <= i; k++) {  // (the lower triangle, mirrored, as in the predict stage)
-                        float a2 = 0.0f, b2 = 0.0f;
-#pragma unroll
-                        for (int t = 0; t < 3; t++) a2 = a2 + T[i][t] * Gv[k][t];
-#pragma unroll
-                        for (int t = 0; t < 2; t++) b2 = b2 + U[i][t] * Gz[k][t];
-                        P[(size_t) (len + i) * ld + len + k] = a2 + b2;
-                        P[(size_t) (len + k) * ld + len + i] = a2 + b2;
-                    }
-            }
+            const float r = z_in[2 * o];
+            const EkfBearing g = ekf_bearing(x, r, z_in[2 * o + 1]);
+            for (int j = tid; j < len; j += kEkfBlock) ekf_augment_column(P, ld, len, j, g.g02, g.g12);
+            if (tid == 0) ekf_augment_block(P, ld, len, x, r, g, a.Re);
             dim += 2;
             __syncthreads();
         }
@@ -537,9 +294,9 @@ __global__ void __launch_bounds__(kEnsBlock) ekf_ens_kernel(EnsArgs a) {
 }
 
 // slamgpu_ens_poses: out[b][12] = x, y, theta, Pvv row-major
-__global__ void __launch_bounds__(kEnsBlock) ekf_ens_pose_kernel(const float *__restrict__ P, const float *__restrict__ x, int ld, int cap_dim, int members,
+__global__ void __launch_bounds__(kEkfBlock) ekf_ens_pose_kernel(const float *__restrict__ P, const float *__restrict__ x, int ld, int cap_dim, int members,
                                                                   double *__restrict__ out) {
-    const int e = blockIdx.x * kEnsBlock + threadIdx.x;
+    const int e = blockIdx.x * kEkfBlock + threadIdx.x;
     if (e >= 12 * members) return;
     const int b = e / 12, q = e - 12 * b;
     out[e] = q < 3 ? (double) x[(size_t) b * ld + q] : (double) P[(size_t) b * cap_dim * ld + (size_t) ((q - 3) / 3) * ld + (q - 3) % 3];
@@ -549,8 +306,7 @@ __global__ void __launch_bounds__(kEnsBlock) ekf_ens_pose_kernel(const float *__
 
 struct slamgpu_ekf_ens {
     slamgpu_ekf_ens_config cfg{};
-    hipStream_t stream = nullptr;
-    bool own_stream = true;
+    EkfStream stream;
     int B = 0, ld = 0, cap_dim = 0;
     DevBuf<float> P, x, PHt, work, io;
     DevBuf<int32_t> dim, status, iw;
@@ -561,8 +317,8 @@ struct slamgpu_ekf_ens {
     PinBuf<char> pin;
     size_t slot_bytes = 0;
     SlotRing<2> slots;
-    std::vector<int32_t> table;  // association_known: id -> feature, -1 not seen yet (ONE table: every member has the same dimension)
-    int nf_known = 0;            // ... and the features it has handed out
+    EkfIdTable table;  // association_known (ONE table: every member has the same dimension)
+    int nf_known = 0;  // ... and the features it has handed out
 };
 
 namespace {
@@ -586,12 +342,12 @@ void ens_release(slamgpu_ekf_ens *e) {
     e->pose_dev.release();
     e->pin.release();
     e->slots.release();
-    if (e->own_stream && e->stream) (void) hipStreamDestroy(e->stream);
+    e->stream.release();
     delete e;
 }
 
 int ens_reserve(slamgpu_ekf_ens *e) {
-    if (e->own_stream) HIP_TRY(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking));
+    if (int rc = e->stream.create()) return rc;
     const size_t B = (size_t) e->B, ld = (size_t) e->ld;
     if (int rc = e->P.reserve_zeroed(B * ld * e->cap_dim, "EKF ensemble covariances P")) return rc;
     if (int rc = e->x.reserve_zeroed(B * ld, "EKF ensemble states x")) return rc;
@@ -631,10 +387,9 @@ int ens_room(slamgpu_ekf_ens *e, int32_t nz, size_t bytes) {
 // the shared labels of the known association, as slamgpu_ekf_sim's table makes them, WITHOUT touching the table: `idn` are the ids that
 // are new, in observation order (distinct: ens_step has refused a repeated unseen id); they take the features nf_known ... when the step
 // fits.  When it does not, the return value is true and every member refuses the step (SLAMGPU_EKF_STATUS_CAPACITY)
-inline int32_t ens_lookup(const slamgpu_ekf_ens *e, int32_t id) { return (size_t) id < e->table.size() ? e->table[id] : -1; }
 bool ens_known_labels(const slamgpu_ekf_ens *e, const int32_t *ids, int32_t nz, int32_t *lab, std::vector<int32_t> &idn) {
     for (int32_t i = 0; i < nz; i++) {
-        const int32_t f = ens_lookup(e, ids[i]);
+        const int32_t f = e->table.lookup(ids[i]);
         lab[i] = f >= 0 ? f : SLAMGPU_ASSOC_NEW;
         if (f < 0) idn.push_back(ids[i]);
     }
@@ -661,7 +416,7 @@ int ens_step(slamgpu_ekf_ens *e, const EnsStep &s, const int32_t *ids, int32_t n
         std::vector<int32_t> unseen;
         for (int32_t i = 0; i < nz; i++) {
             if (ids[i] < 0 || ids[i] >= kMaxId) return fail(SLAMGPU_ERR_INVALID, "ids[%d] = %d outside [0, %d)", i, ids[i], kMaxId);
-            if (ens_lookup(e, ids[i]) < 0) unseen.push_back(ids[i]);
+            if (e->table.lookup(ids[i]) < 0) unseen.push_back(ids[i]);
         }
         std::sort(unseen.begin(), unseen.end());
         if (std::adjacent_find(unseen.begin(), unseen.end()) != unseen.end())
@@ -724,15 +479,11 @@ int ens_step(slamgpu_ekf_ens *e, const EnsStep &s, const int32_t *ids, int32_t n
     // LDS: the heading stage's two columns or the chunk's innovation covariance, whichever is larger (at most 64 KB: np <= 128, ld <= 1056)
     size_t lds_floats = observe && e->cfg.batch_update && nz > 0 ? (size_t) np * np : 4;
     if (e->cfg.use_heading) lds_floats = std::max(lds_floats, 2 * (size_t) e->ld);
-    ekf_ens_kernel<<<e->B, kEnsBlock, sizeof(float) * lds_floats, e->stream>>>(a);
-    const hipError_t err = hipGetLastError();
-    if (err != hipSuccess) return fail(SLAMGPU_ERR_HIP, "ekf_ens_kernel launch: %s", hipGetErrorString(err));
+    ekf_ens_kernel<<<e->B, kEkfBlock, sizeof(float) * lds_floats, e->stream>>>(a);
+    if (int rc = ekf_launched("ekf_ens_kernel")) return rc;
     e->last_nz = nz;
     if (!refuse) {  // the step is on its way: only now does the table learn the new ids
-        for (size_t i = 0; i < idn.size(); i++) {
-            if ((size_t) idn[i] >= e->table.size()) e->table.resize((size_t) idn[i] + 1, -1);
-            e->table[idn[i]] = e->nf_known + (int32_t) i;
-        }
+        e->table.learn(idn, e->nf_known);
         e->nf_known += (int) idn.size();
     }
     return 0;
@@ -753,22 +504,13 @@ int slamgpu_ens_create(const slamgpu_ekf_ens_config *cfg, slamgpu_ekf_ens **out)
     if (cfg->struct_size != sizeof(slamgpu_ekf_ens_config))
         return fail(SLAMGPU_ERR_INVALID, "slamgpu_ekf_ens_config.struct_size %u != %zu (ABI mismatch)", cfg->struct_size, sizeof(slamgpu_ekf_ens_config));
     if (cfg->members < 1 || cfg->members > 65535) return fail(SLAMGPU_ERR_INVALID, "members %d outside [1, 65535]", cfg->members);
-    if (cfg->max_landmarks < 0 || cfg->max_landmarks > 512) return fail(SLAMGPU_ERR_INVALID, "max_landmarks %d outside [0, 512]", cfg->max_landmarks);
-    if (!(cfg->wheel_base > 0.0f) || !(cfg->sigma_phi >= 0.0f) || !(cfg->gate_reject >= 0.0f) || !(cfg->gate_augment >= 0.0f))
-        return fail(SLAMGPU_ERR_INVALID, "wheel_base must be positive, sigma_phi and the gates non-negative");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(SLAMGPU_ERR_NO_DEVICE, "no HIP device: libslamgpu has no CPU fallback");
-    if (cfg->device < 0 || cfg->device >= ndev) return fail(SLAMGPU_ERR_INVALID, "device %d out of range (%d devices)", cfg->device, ndev);
-    HIP_TRY(hipSetDevice(cfg->device));
+    if (int rc = ekf_check_config(cfg, 512)) return rc;
     slamgpu_ekf_ens *e = new slamgpu_ekf_ens();
     e->cfg = *cfg;
     e->B = cfg->members;
-    e->cap_dim = 3 + 2 * cfg->max_landmarks;
-    e->ld = (e->cap_dim + 31) / 32 * 32;
-    if (cfg->external_stream) {
-        e->stream = reinterpret_cast<hipStream_t>(cfg->external_stream);
-        e->own_stream = false;
-    }
+    e->cap_dim = ekf_cap_dim(cfg->max_landmarks);
+    e->ld = ekf_ld(e->cap_dim);
+    e->stream.adopt(cfg->external_stream);
     if (int rc = ens_reserve(e)) {
         ens_release(e);
         return rc;
@@ -838,9 +580,8 @@ int slamgpu_ens_dims(slamgpu_ekf_ens *e, int32_t *dim_out) {
 int slamgpu_ens_poses(slamgpu_ekf_ens *e, double *out) {
     if (int rc = ens_check(e)) return rc;
     if (!out) return fail(SLAMGPU_ERR_INVALID, "null output");
-    ekf_ens_pose_kernel<<<(12 * e->B + kEnsBlock - 1) / kEnsBlock, kEnsBlock, 0, e->stream>>>(e->P, e->x, e->ld, e->cap_dim, e->B, e->pose_dev);
-    const hipError_t err = hipGetLastError();
-    if (err != hipSuccess) return fail(SLAMGPU_ERR_HIP, "ekf_ens_pose_kernel launch: %s", hipGetErrorString(err));
+    ekf_ens_pose_kernel<<<(12 * e->B + kEkfBlock - 1) / kEkfBlock, kEkfBlock, 0, e->stream>>>(e->P, e->x, e->ld, e->cap_dim, e->B, e->pose_dev);
+    if (int rc = ekf_launched("ekf_ens_pose_kernel")) return rc;
     HIP_TRY(hipStreamSynchronize(e->stream));
     HIP_TRY(hipMemcpy(out, e->pose_dev, sizeof(double) * 12 * (size_t) e->B, hipMemcpyDeviceToHost));
     return 0;
@@ -854,10 +595,7 @@ int slamgpu_ens_state(slamgpu_ekf_ens *e, int32_t b, float *x, float *P, int32_t
     HIP_TRY(hipMemcpy(&dim, e->dim.p + b, sizeof(int32_t), hipMemcpyDeviceToHost));
     if (P && ld_out < dim) return fail(SLAMGPU_ERR_INVALID, "ld_out %d < dim %d", ld_out, dim);
     const size_t ld = (size_t) e->ld;
-    if (x) HIP_TRY(hipMemcpy(x, e->x.p + b * ld, sizeof(float) * (size_t) dim, hipMemcpyDeviceToHost));
-    if (P)
-        HIP_TRY(hipMemcpy2D(P, sizeof(float) * (size_t) ld_out, e->P.p + (size_t) b * e->cap_dim * ld, sizeof(float) * ld, sizeof(float) * (size_t) dim,
-                            (size_t) dim, hipMemcpyDeviceToHost));
+    if (int rc = ekf_state_out(e->x.p + b * ld, e->P.p + (size_t) b * e->cap_dim * ld, e->ld, dim, x, P, ld_out)) return rc;
     return dim;
 }
 
@@ -874,17 +612,11 @@ int slamgpu_ens_slab(slamgpu_ekf_ens *e, int32_t b, float *x, float *P) {
 int slamgpu_ens_upload(slamgpu_ekf_ens *e, int32_t b, int32_t dim, const float *x, const float *P, int32_t ld_in) {
     if (int rc = ens_check(e)) return rc;
     if (int rc = ens_member(e, b)) return rc;
-    if (dim < 3 || dim > e->cap_dim || ((dim - 3) & 1) || !x || !P || ld_in < dim)
-        return fail(SLAMGPU_ERR_INVALID, "bad upload: dim %d (3 + 2 nf up to %d), ld_in %d", dim, e->cap_dim, ld_in);
-    HIP_TRY(hipStreamSynchronize(e->stream));
     const size_t ld = (size_t) e->ld;
-    HIP_TRY(hipMemcpy(e->x.p + b * ld, x, sizeof(float) * (size_t) dim, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy2D(e->P.p + (size_t) b * e->cap_dim * ld, sizeof(float) * ld, P, sizeof(float) * (size_t) ld_in, sizeof(float) * (size_t) dim,
-                        (size_t) dim, hipMemcpyHostToDevice));
+    if (int rc = ekf_state_in(e->stream, e->x.p + b * ld, e->P.p + (size_t) b * e->cap_dim * ld, e->ld, e->cap_dim, dim, x, P, ld_in)) return rc;
     HIP_TRY(hipMemcpy(e->dim.p + b, &dim, sizeof(int32_t), hipMemcpyHostToDevice));
     e->nf_known = (dim - 3) / 2;
-    e->table.assign((size_t) e->nf_known, 0);
-    for (int f = 0; f < e->nf_known; f++) e->table[f] = f;
+    e->table.identity(e->nf_known);
     return 0;
 }
 
