@@ -892,7 +892,35 @@ int slamgpu_ekf_sync(slamgpu_ekf *e);
  *      e^T Pvv^-1 e through the Cholesky factor of the 3 x 3 pose block (slamhost_pose_nees's definitions):
  *        [0] steps counted  [1] steps not counted (Pvv not positive definite -- how a filter starts, P = 0 -- or a non-finite state)
  *        [2] sum NEES  [3] count of NEES <= 7.8147  [4] sum (ex^2 + ey^2)  [5] sum etheta^2
- *      consistency_reset zeroes them.  What it costs: DESIGN.md section 7i. */
+ *      consistency_reset zeroes them.  What it costs: DESIGN.md section 7i.
+ *
+ * run_noise: K steps of sim_noise in ONE launch (and one small reduction launch while the trace is on), enqueued without a
+ *      synchronisation.  The true path, the visible ids and the noise-free measurements of a run do not depend on the noise, so a
+ *      stretch of it is a small shared tape: steps[K], and z_true[total][2] / ids[total] of which step k uses [first, first + nz).
+ *      Every member draws its own inputs from the Philox counters above, which already carry the step's `step` word.  AFTER the call
+ *      every member's slab (padding included), dim, status, the six consistency accumulators, the trace, the known association's id
+ *      table and what last_inputs returns are bit for bit what K calls of sim_noise leave, made in tape order with each step's fields
+ *      and the shared Q, Qe, Re, R, noise.  K lies in [0, 4096] (0: nothing happens); longer runs are several calls.  The whole tape is
+ *      checked before anything is applied: a null pointer where one is needed, nz or first out of range, first + nz > total, an id
+ *      outside [0, 2^20), an id not seen before twice within one step, noise flags outside 0 .. 7, a Q without a Cholesky factor
+ *      while control noise is drawn -- each is SLAMGPU_ERR_INVALID and neither the members nor the table change.  THE ONE DIFFERENCE
+ *      from K single calls: the batch is refused WHOLE, where K single calls would have applied the steps before the bad one.
+ *      Known association: the labels of all K steps are resolved on the host before the launch, by the table's rules applied step by
+ *      step to a copy of the table; a step whose new ids do not fit is refused for every member (SLAMGPU_EKF_STATUS_CAPACITY) and the
+ *      copy does not learn them, so later steps meet them as unseen again, as K calls would; the copy replaces the table once the
+ *      launch is enqueued.
+ * trace: a ring on the device that retains, for every step that was given a truth, the consistency definitions above taken over
+ *      the MEMBERS of that one step (what Bailey et al.'s consistency plot averages): out[6] = members counted, members not counted,
+ *      sum NEES, count of NEES <= 7.8147, sum (ex^2 + ey^2), sum etheta^2, in double, and the step's tag: its Philox `step` word,
+ *      UINT32_MAX for slamgpu_ens_sim, which has none.  All three entry points append to it.  The member's workgroup leaves its
+ *      values of the step in a scratch; a reduction kernel, one workgroup per traced step, adds them in an order that depends on
+ *      `members` alone, without atomics, and writes the record straight into slot (next + q) % capacity: a record is deterministic and
+ *      the same whichever entry point ran the step.  trace_enable(capacity): records retained, synchronises, empties the ring; 0
+ *      turns it off and frees it (never enabled: nothing is allocated and no kernel of it is launched).  A call whose traced steps
+ *      exceed the capacity returns SLAMGPU_ERR_CAPACITY before anything is applied.  trace_info: records [first, next) are retained.
+ *      trace_fetch: synchronises, does not consume; a window outside the retained range is SLAMGPU_ERR_INVALID and the outputs are
+ *      left untouched (out, step: either may be NULL).  consistency_reset leaves the trace alone; upload keeps the retained records.
+ *      (run_noise and the trace are declared at the end of this file, behind the experimental block: STABLE all the same.) */
 typedef struct slamgpu_ekf_ens slamgpu_ekf_ens;
 typedef struct {
     uint32_t struct_size; /* sizeof(slamgpu_ekf_ens_config) */
@@ -1153,6 +1181,24 @@ int slamgpu_update_counted_launches(slamgpu_ctx *ctx, int64_t out[9]);
 int slamgpu_update_wide_launches(slamgpu_ctx *ctx, int64_t *count);
 
 #endif /* SLAMGPU_EXPERIMENTAL */
+
+/* ---- EKF-SLAM ensemble, continued: K steps per launch from a tape, and the per-step NEES trace.  STABLE (outside the block above);
+ * what they do is told with the ensemble's other entry points (run_noise, trace). */
+typedef struct {
+    float V, G, phi_true, dt;
+    float truth[3];
+    int32_t has_truth; /* 0: the consistency accumulators and the trace are left alone for this step */
+    int32_t observe;   /* 0: nz is taken as 0 */
+    int32_t nz;        /* 0 .. 4096 */
+    int32_t first;     /* index of the step's first observation in z_true / ids */
+    uint32_t step;     /* the Philox counter word, as slamgpu_ens_sim_noise's `step` */
+} slamgpu_ens_tape_step; /* 48 bytes */
+int slamgpu_ens_run_noise(slamgpu_ekf_ens *e, const slamgpu_ens_tape_step *steps, int32_t K, const float *z_true /*[total][2]*/,
+                          const int32_t *ids /*[total]*/, int32_t total, const float Q[4], const float Qe[4] /*or NULL: Q*/, const float Re[4],
+                          const float R[4], uint32_t noise);
+int slamgpu_ens_trace_enable(slamgpu_ekf_ens *e, int32_t capacity);
+int slamgpu_ens_trace_info(slamgpu_ekf_ens *e, int64_t *first, int64_t *next, int32_t *capacity);
+int slamgpu_ens_trace_fetch(slamgpu_ekf_ens *e, int64_t first, int32_t count, double *out /*[count][6]*/, uint32_t *step /*[count]*/);
 
 #ifdef __cplusplus
 }

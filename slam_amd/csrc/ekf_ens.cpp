@@ -6,6 +6,7 @@
 #define SLAM_KNS slam_ekf_ens
 #include "device_math.h"  // philox4x32, u01, box_muller3, as they are
 #include "ekf_helpers.h"
+#include "ring.h"
 
 namespace {
 
@@ -18,58 +19,130 @@ constexpr int kWork = 10 * kChunk + 2 * kKMax;  // floats of a member's small wo
 constexpr int kMaxNz = 4096;
 constexpr int kMaxId = 1 << 20;  // known association: ids index the host's table
 constexpr double kChi2_3_95 = 7.8147;
+constexpr int kMaxRun = 4096;         // steps of one slamgpu_ens_run_noise
+constexpr int kMaxTrace = 1 << 24;    // records the trace may retain
 
 // one step of every member, by value.  io is the step's packet in device memory: lab [nz] int32 (known association: feature or
 // SLAMGPU_ASSOC_NEW per observation, shared) | z_true [nz][2] (sim_noise, shared) | VG [B][2] | phi [B] | z [B][nz][2]; the last
 // three are what the members used (the host's for sim, the members' own draws for sim_noise): slamgpu_ens_last_inputs
+// a step as the device reads it, uniform across the workgroup: the single step has one inside its by-value arguments, the K-step launch
+// (slamgpu_ens_run_noise) reads them from its tape.  64 bytes.  off: where the step's lab [nz] | z_true [nz][2] start in the launch's
+// packet, in floats; np: the row stride of the innovation covariance in LDS, a power of two >= 2 min(nz, kChunk); refuse: known
+// association, the shared table has no room for the step's new ids, so NO member applies its update or augment; q: the step's row of
+// the trace scratch, -1: not traced
+struct EnsTapeRec {
+    float V, G, phi_true, dt, truth[3];
+    int32_t has_truth, observe, nz, off, refuse, np, q;
+    uint32_t step;
+    int32_t pad;
+};
+static_assert(sizeof(EnsTapeRec) == 64, "EnsTapeRec");
+
 struct EnsArgs {
     float *P;         // [B][cap_dim][ld]
     float *x;         // [B][ld]
     int32_t *dim;     // [B]
     int32_t *status;  // [B] sticky
-    double *acc;      // [B][6]
+    double *acc;      // [B][6], and behind them the trace's scratch: the members' values of the launch's traced steps, [q][B][6]
     float *PHt;       // [B][kKMax][ld]: P H^T of a chunk, k-major, then W1 in its place
     float *work;      // [B][kWork]
     int32_t *iw;      // [B][4 + 3 nzcap]: m, n_new, -, - | labels | observations matched | observations new
     float *io;
-    int32_t members, ld, cap_dim, max_landmarks, nz, nzcap, np;  // np: the row stride of the innovation covariance in LDS, a power of two >= 2 min(nz, kChunk)
-    int32_t use_heading, batch_update, known, observe, draw, has_truth;
-    int32_t refuse;  // known association: the shared table has no room for the step's new ids, so NO member applies its update or augment
-    uint32_t noise, step, k0, k1;
-    float V, G, phi_true, dt, wheel_base, sigma_phi, r_phi, gate_reject, gate_augment;
+    int32_t members, ld, cap_dim, max_landmarks, nzcap;
+    int32_t use_heading, batch_update, known, draw;
+    uint32_t noise, k0, k1;
+    float wheel_base, sigma_phi, r_phi, gate_reject, gate_augment;
     float Q[4], Re[4], R[4];
     float L00, L10, L11, sr0, sr1;  // the lower Cholesky factor of Q; sqrt(R00), sqrt(R11)
-    float truth[3];
+    EnsTapeRec st;                  // the single step's own (the K-step launch leaves it alone)
 };
 
-__global__ void __launch_bounds__(kEkfBlock) ekf_ens_kernel(EnsArgs a) {
-    extern __shared__ float lds[];  // heading: column 2 of P and the gain, [2][ld]; update: the innovation covariance, [np][np]
-    const int b = blockIdx.x, tid = threadIdx.x;
-    const int ld = a.ld, nz = a.nz;
+// ---- consistency: the member's own row, one lane, in double (slamhost_pose_nees's definitions), every operation rounded on its
+// own: the float64 model of the tests evaluates the same formulas in the same order.  With the ring on, the step's own six values go
+// to the trace scratch as well: row s.q behind the accumulators (no argument of its own: one more pointer in EnsArgs and the scalar
+// registers of ekf_ens_kernel no longer fit without a stack slot)
+template <bool kTrace>
+__device__ __forceinline__ void ens_consistency(const EnsArgs &a, const EnsTapeRec &s, int b, const float *x, const float *P, int ld) {
+#pragma clang fp contract(off)
+    double *A6 = a.acc + 6 * (size_t) b;
+    double *T6 = kTrace && s.q >= 0 ? a.acc + 6 * ((size_t) a.members * (1 + s.q) + b) : nullptr;
+    const double ex = (double) x[0] - (double) s.truth[0], ey = (double) x[1] - (double) s.truth[1];
+    const double et = remainder((double) x[2] - (double) s.truth[2], 2.0 * 3.14159265358979323846);
+    const double p00 = P[0], p10 = P[(size_t) ld], p11 = P[(size_t) ld + 1], p20 = P[2 * (size_t) ld], p21 = P[2 * (size_t) ld + 1],
+                 p22 = P[2 * (size_t) ld + 2];
+    bool ok = isfinite(ex) && isfinite(ey) && isfinite(et) && isfinite(p00) && isfinite(p10) && isfinite(p11) && isfinite(p20) && isfinite(p21) &&
+              isfinite(p22);
+    double nees = 0.0;
+    if (ok && p00 > 0.0) {
+        const double l00 = sqrt(p00), l10 = p10 / l00, l20 = p20 / l00;
+        const double d1 = p11 - l10 * l10;
+        if (d1 > 0.0) {
+            const double l11 = sqrt(d1), l21 = (p21 - l20 * l10) / l11;
+            const double d2 = p22 - l20 * l20 - l21 * l21;
+            if (d2 > 0.0) {
+                const double l22 = sqrt(d2);
+                const double y0 = ex / l00, y1 = (ey - l10 * y0) / l11, y2 = (et - l20 * y0 - l21 * y1) / l22;
+                nees = y0 * y0 + y1 * y1 + y2 * y2;
+                ok = isfinite(nees);
+            } else ok = false;
+        } else ok = false;
+    } else ok = false;
+    if (!ok) {
+        A6[1] += 1.0;
+        if (T6) {
+            T6[0] = 0.0;
+            T6[1] = 1.0;
+            T6[2] = T6[3] = T6[4] = T6[5] = 0.0;
+        }
+        return;
+    }
+    A6[0] += 1.0;
+    A6[2] += nees;
+    if (nees <= kChi2_3_95) A6[3] += 1.0;
+    A6[4] += ex * ex + ey * ey;
+    A6[5] += et * et;
+    if (T6) {
+        T6[0] = 1.0;
+        T6[1] = 0.0;
+        T6[2] = nees;
+        T6[3] = nees <= kChi2_3_95 ? 1.0 : 0.0;
+        T6[4] = ex * ex + ey * ey;
+        T6[5] = et * et;
+    }
+}
+
+// one step of member b, from its own draws to the consistency row: THE copy of the ensemble's stages, inlined into the single-step
+// kernel and into the K-step kernel's loop.  s is read where it is used (the single step's sits in the kernel's arguments, the tape's in
+// device memory that the kernel only reads); packet: the step's lab [nz] | z_true [nz][2]; own: where the member's inputs go, null: the
+// io area in the layout of this step's nz (slamgpu_ens_last_inputs reads them there).  dim is the member's dimension, held by every
+// lane from step to step: in, and returned
+template <bool kTrace>
+__device__ __forceinline__ int ens_member_step(const EnsArgs &a, const EnsTapeRec &s, const float *packet, float *own, float *lds, const int b,
+                                               const int tid, int dim) {
+    const int ld = a.ld, nz = s.nz;
     float *P = a.P + (size_t) b * a.cap_dim * ld;
     float *x = a.x + (size_t) b * ld;
     float *PHt = a.PHt + (size_t) b * kKMax * ld;
     float *H5g = a.work + (size_t) b * kWork, *vg = H5g + 10 * kChunk, *tg = vg + kKMax;
     int32_t *cnt = a.iw + (size_t) b * (4 + 3 * (size_t) a.nzcap), *lab = cnt + 4, *mi = lab + a.nzcap, *ni = mi + a.nzcap;
-    const int32_t *lab_known = reinterpret_cast<const int32_t *>(a.io);
-    const float *z_true = a.io + nz;
-    float *vg_in = a.io + 3 * (size_t) nz + 2 * (size_t) b;
-    float *phi_in = a.io + 3 * (size_t) nz + 2 * (size_t) a.members + b;
-    float *z_in = a.io + 3 * (size_t) nz + 3 * (size_t) a.members + 2 * (size_t) nz * b;
-    int dim = a.dim[b];
+    const int32_t *lab_known = reinterpret_cast<const int32_t *>(packet);
+    const float *z_true = packet + nz;
+    float *vg_in = own ? own : a.io + 3 * (size_t) nz + 2 * (size_t) b;
+    float *phi_in = own ? own + 2 : a.io + 3 * (size_t) nz + 2 * (size_t) a.members + b;
+    float *z_in = own ? own + 3 : a.io + 3 * (size_t) nz + 3 * (size_t) a.members + 2 * (size_t) nz * b;
 
     // ---- the member's own inputs (sim_noise): Philox stream 5, counter (member, step, 5, q) ------------------------------------
     if (a.draw) {
         if (tid == 0) {
-            float V = a.V, G = a.G, phi = a.phi_true;
+            float V = s.V, G = s.G, phi = s.phi_true;
             if (a.noise & SLAMGPU_EKF_ENS_NOISE_CONTROL) {  // multivariate_gauss2: x + chol(Q) g
                 float g0, g1, g2;
-                box_muller3(philox4x32((uint32_t) b, a.step, 5u, 0u, a.k0, a.k1), g0, g1, g2);
-                V = a.V + a.L00 * g0;
-                G = a.G + a.L10 * g0 + a.L11 * g1;
+                box_muller3(philox4x32((uint32_t) b, s.step, 5u, 0u, a.k0, a.k1), g0, g1, g2);
+                V = s.V + a.L00 * g0;
+                G = s.G + a.L10 * g0 + a.L11 * g1;
             }
             if (a.noise & SLAMGPU_EKF_ENS_NOISE_HEADING)  // (uncentred, as the reference's unifRand(): ekfslamwrapper.cpp:81)
-                phi = a.phi_true + a.sigma_phi * u01(philox4x32((uint32_t) b, a.step, 5u, 1u, a.k0, a.k1).x);
+                phi = s.phi_true + a.sigma_phi * u01(philox4x32((uint32_t) b, s.step, 5u, 1u, a.k0, a.k1).x);
             vg_in[0] = V;
             vg_in[1] = G;
             *phi_in = phi;
@@ -78,7 +151,7 @@ __global__ void __launch_bounds__(kEkfBlock) ekf_ens_kernel(EnsArgs a) {
             float zr = z_true[2 * i], zb = z_true[2 * i + 1];
             if (a.noise & SLAMGPU_EKF_ENS_NOISE_SENSOR) {  // Simulator::observe
                 float g0, g1, g2;
-                box_muller3(philox4x32((uint32_t) b, a.step, 5u, 2u + (uint32_t) i, a.k0, a.k1), g0, g1, g2);
+                box_muller3(philox4x32((uint32_t) b, s.step, 5u, 2u + (uint32_t) i, a.k0, a.k1), g0, g1, g2);
                 zr = zr + g0 * a.sr0;
                 zb = zb + g1 * a.sr1;
             }
@@ -92,12 +165,12 @@ __global__ void __launch_bounds__(kEkfBlock) ekf_ens_kernel(EnsArgs a) {
     // ---- EkfSlam::predict: everything read into registers, a barrier, then the writes (no ticket: one workgroup) ---------------
     {
         const float th = x[2], x0 = x[0], x1 = x[1];
-        const EkfMotion mo = ekf_motion(V, G, th, a.dt);
+        const EkfMotion mo = ekf_motion(V, G, th, s.dt);
         float Pvv[3][3];
         ekf_load_pose_block(P, ld, Pvv);
         __syncthreads();
         for (int j = 3 + tid; j < dim; j += kEkfBlock) ekf_predict_column(P, ld, j, mo.vts, mo.vtc);
-        if (tid == 0) ekf_predict_pose(P, ld, x, Pvv, x0, x1, th, mo, V, G, a.dt, a.wheel_base, a.Q);
+        if (tid == 0) ekf_predict_pose(P, ld, x, Pvv, x0, x1, th, mo, V, G, s.dt, a.wheel_base, a.Q);
         __syncthreads();
     }
 
@@ -117,7 +190,7 @@ __global__ void __launch_bounds__(kEkfBlock) ekf_ens_kernel(EnsArgs a) {
         __syncthreads();
     }
 
-    if (a.observe) {
+    if (s.observe) {
         const int nf = (dim - 3) / 2;
         // ---- labels: the shared table's, or the gates over (observation, feature) pairs against the state as it stands --------------
         if (a.known) {
@@ -157,7 +230,7 @@ __global__ void __launch_bounds__(kEkfBlock) ekf_ens_kernel(EnsArgs a) {
                 if (l >= 0) mi[m++] = i;
                 else if (l == SLAMGPU_ASSOC_NEW) ni[nn++] = i;
             }
-            if (nf + nn > a.max_landmarks || a.refuse) {  // the step does not fit: neither its update nor its augment is applied
+            if (nf + nn > a.max_landmarks || s.refuse) {  // the step does not fit: neither its update nor its augment is applied
                 a.status[b] |= SLAMGPU_EKF_STATUS_CAPACITY;
                 m = nn = 0;
             }
@@ -166,7 +239,7 @@ __global__ void __launch_bounds__(kEkfBlock) ekf_ens_kernel(EnsArgs a) {
         }
         __syncthreads();
         const int m = cnt[0], nn = cnt[1];
-        const int np = a.np;
+        const int np = s.np;
 
         // ---- EkfSlam::batch_update, chunk by chunk ----------------------------------------------------------------------------------
         for (int at = 0; at < m; at += kChunk) {
@@ -252,45 +325,69 @@ __global__ void __launch_bounds__(kEkfBlock) ekf_ens_kernel(EnsArgs a) {
         }
     }
 
-    if (tid != 0) return;
-    a.dim[b] = dim;
-    if (!a.has_truth) return;
-    // ---- consistency: the member's own row, one lane, in double (slamhost_pose_nees's definitions), every operation rounded on its
-    // own: the float64 model of the tests evaluates the same formulas in the same order
-    {
-#pragma clang fp contract(off)
-    double *A6 = a.acc + 6 * (size_t) b;
-    const double ex = (double) x[0] - (double) a.truth[0], ey = (double) x[1] - (double) a.truth[1];
-    const double et = remainder((double) x[2] - (double) a.truth[2], 2.0 * 3.14159265358979323846);
-    const double p00 = P[0], p10 = P[(size_t) ld], p11 = P[(size_t) ld + 1], p20 = P[2 * (size_t) ld], p21 = P[2 * (size_t) ld + 1],
-                 p22 = P[2 * (size_t) ld + 2];
-    bool ok = isfinite(ex) && isfinite(ey) && isfinite(et) && isfinite(p00) && isfinite(p10) && isfinite(p11) && isfinite(p20) && isfinite(p21) &&
-              isfinite(p22);
-    double nees = 0.0;
-    if (ok && p00 > 0.0) {
-        const double l00 = sqrt(p00), l10 = p10 / l00, l20 = p20 / l00;
-        const double d1 = p11 - l10 * l10;
-        if (d1 > 0.0) {
-            const double l11 = sqrt(d1), l21 = (p21 - l20 * l10) / l11;
-            const double d2 = p22 - l20 * l20 - l21 * l21;
-            if (d2 > 0.0) {
-                const double l22 = sqrt(d2);
-                const double y0 = ex / l00, y1 = (ey - l10 * y0) / l11, y2 = (et - l20 * y0 - l21 * y1) / l22;
-                nees = y0 * y0 + y1 * y1 + y2 * y2;
-                ok = isfinite(nees);
-            } else ok = false;
-        } else ok = false;
-    } else ok = false;
-    if (!ok) {
-        A6[1] += 1.0;
-        return;
+    if (tid == 0) {
+        a.dim[b] = dim;
+        if (s.has_truth) ens_consistency<kTrace>(a, s, b, x, P, ld);
     }
-    A6[0] += 1.0;
-    A6[2] += nees;
-    if (nees <= kChi2_3_95) A6[3] += 1.0;
-    A6[4] += ex * ex + ey * ey;
-    A6[5] += et * et;
+    return dim;
+}
+
+// kTrace: the step leaves its row of the trace (the ring is on and the step has a truth); without it the kernel has no trace code at all
+template <bool kTrace>
+__global__ void __launch_bounds__(kEkfBlock) ekf_ens_kernel(EnsArgs a) {
+    extern __shared__ float lds[];  // heading: column 2 of P and the gain, [2][ld]; update: the innovation covariance, [np][np]
+    const int b = blockIdx.x, tid = threadIdx.x;
+    ens_member_step<kTrace>(a, a.st, a.io, nullptr, lds, b, tid, a.dim[b]);
+}
+
+// K steps of every member in one launch (slamgpu_ens_run_noise): workgroup b owns member b from the tape's first step to its last, a
+// barrier after the last stage of each step -- it is what makes the step's global writes to P, x, status and the accumulators visible
+// to the same workgroup's next step.  tape and packet are only read.  The member's draws of the steps before the last go to its own
+// row of `draws` (3 + 2 zstride floats: steps of different nz would overlap other members' rows in the io layout while those still
+// read them); the last step's go to the io area in that step's layout
+// (tape and packet are NOT __restrict__: declared so, a step's record arrives in sixteen scalar registers at once, the scalar allocator
+// runs out, and the kernel is left with a stack slot nothing uses and a private segment; as they are it has none)
+__global__ void __launch_bounds__(kEkfBlock) ekf_ens_run_kernel(EnsArgs a, const EnsTapeRec *tape, const float *packet,
+                                                                 float *draws, int K, int zstride) {
+    extern __shared__ float lds[];  // sized by the host to the largest need of any step of the tape
+    const int b = blockIdx.x, tid = threadIdx.x;
+    float *own = draws + (size_t) b * (3 + 2 * (size_t) zstride);
+    int dim = a.dim[b];
+    for (int k = 0; k < K; k++) {
+        dim = ens_member_step<true>(a, tape[k], packet + tape[k].off, k == K - 1 ? nullptr : own, lds, b, tid, dim);
+        __syncthreads();
     }
+}
+
+// the trace's records of a launch: workgroup q sums the members' values of traced step q in an order that depends on `members` alone
+// (lane t takes members t, t + 256, ... in turn, then the lanes meet in a fixed tree) and writes the record into its slot of the ring
+// The record's tag is the step word of the tape's step whose row is q, or `tag` for a single step (tape null)
+__global__ void __launch_bounds__(kEkfBlock) ekf_ens_trace_kernel(const double *__restrict__ val, const EnsTapeRec *__restrict__ tape, int K, uint32_t tag,
+                                                                   int members, double *__restrict__ rec, uint32_t *__restrict__ rtag, long long next, int cap) {
+    __shared__ double sh[6][kEkfBlock];
+    const int q = blockIdx.x, tid = threadIdx.x;
+    double acc[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int b = tid; b < members; b += kEkfBlock) {
+        const double *v = val + 6 * ((size_t) q * members + b);
+#pragma unroll
+        for (int c = 0; c < 6; c++) acc[c] = acc[c] + v[c];
+    }
+#pragma unroll
+    for (int c = 0; c < 6; c++) sh[c][tid] = acc[c];
+    __syncthreads();
+    for (int w = kEkfBlock / 2; w > 0; w >>= 1) {
+        if (tid < w)
+#pragma unroll
+            for (int c = 0; c < 6; c++) sh[c][tid] = sh[c][tid] + sh[c][tid + w];
+        __syncthreads();
+    }
+    const size_t slot = (size_t) ((next + q) % cap);
+    if (tid < 6) rec[6 * slot + tid] = sh[tid][0];
+    if (!tape) {
+        if (tid == 0) rtag[slot] = tag;
+    } else
+        for (int k = tid; k < K; k += kEkfBlock)  // (one step of the tape has this row)
+            if (tape[k].q == q) rtag[slot] = tape[k].step;
 }
 
 // slamgpu_ens_poses: out[b][12] = x, y, theta, Pvv row-major
@@ -319,6 +416,14 @@ struct slamgpu_ekf_ens {
     SlotRing<2> slots;
     EkfIdTable table;  // association_known (ONE table: every member has the same dimension)
     int nf_known = 0;  // ... and the features it has handed out
+    // slamgpu_ens_run_noise: the launch's tape in device memory (EnsTapeRec [K] | per step lab [nz] | z_true [nz][2]) and the members'
+    // own draws of the steps before the last, [B][3 + 2 zstride]
+    DevBuf<char> tape;
+    DevBuf<float> draws;
+    // the trace: records [cap][6] and tags [cap] in device memory, the counters on the host; the scratch of one launch, grow-only
+    Ring ring;
+    DevBuf<double> tr_rec;
+    DevBuf<uint32_t> tr_rtag;
 };
 
 namespace {
@@ -340,6 +445,10 @@ void ens_release(slamgpu_ekf_ens *e) {
     e->iw.release();
     e->acc.release();
     e->pose_dev.release();
+    e->tape.release();
+    e->draws.release();
+    e->tr_rec.release();
+    e->tr_rtag.release();
     e->pin.release();
     e->slots.release();
     e->stream.release();
@@ -364,12 +473,31 @@ int ens_reserve(slamgpu_ekf_ens *e) {
     return e->slots.create();
 }
 
-// room for a step of nz observations whose packet is `bytes` long.  A buffer that has to grow is grown with the stream idle
-int ens_room(slamgpu_ekf_ens *e, int32_t nz, size_t bytes) {
+// what a launch needs room for: steps of at most nz observations, a packet of `bytes` in a pinned slot; a K-step launch also its tape and
+// the members' draws, a traced one nq rows of the trace scratch
+struct EnsNeeds {
+    int32_t nz = 0;
+    size_t bytes = 0, tape_bytes = 0, draw_floats = 0, nq = 0;
+};
+
+// A buffer that has to grow is grown with the stream idle (one synchronisation, whichever buffers grow; those that fit are left alone)
+int ens_room(slamgpu_ekf_ens *e, const EnsNeeds &n) {
     const size_t B = (size_t) e->B;
+    const int32_t nz = n.nz;
+    const size_t bytes = n.bytes, tape_bytes = n.tape_bytes, draw_floats = n.draw_floats, nq = n.nq;
     const size_t io_floats = 3 * (size_t) nz + 3 * B + 2 * B * (size_t) nz;
-    if (nz > e->nzcap || io_floats > e->io.cap || bytes > e->slot_bytes) {
+    if (nz > e->nzcap || io_floats > e->io.cap || bytes > e->slot_bytes || tape_bytes > e->tape.cap || draw_floats > e->draws.cap ||
+        6 * B * (1 + nq) > e->acc.cap) {
         HIP_TRY(hipStreamSynchronize(e->stream));
+        if (int rc = e->tape.reserve(tape_bytes, "EKF ensemble tape")) return rc;
+        if (int rc = e->draws.reserve_zeroed(draw_floats, "EKF ensemble draws")) return rc;
+        if (6 * B * (1 + nq) > e->acc.cap) {  // the trace's scratch lies behind the accumulators, which move with it
+            DevBuf<double> grown;
+            if (int rc = grown.reserve_zeroed(6 * B * (1 + nq), "EKF ensemble accumulators and trace scratch")) return rc;
+            HIP_TRY(hipMemcpy(grown.p, e->acc.p, sizeof(double) * 6 * B, hipMemcpyDeviceToDevice));
+            std::swap(grown, e->acc);
+            grown.release();
+        }
         const int cap = std::max(nz, std::max(e->nzcap, 64));
         if (int rc = e->iw.reserve_zeroed(B * (4 + 3 * (size_t) cap), "EKF ensemble labels")) return rc;
         e->nzcap = cap;
@@ -387,13 +515,82 @@ int ens_room(slamgpu_ekf_ens *e, int32_t nz, size_t bytes) {
 // the shared labels of the known association, as slamgpu_ekf_sim's table makes them, WITHOUT touching the table: `idn` are the ids that
 // are new, in observation order (distinct: ens_step has refused a repeated unseen id); they take the features nf_known ... when the step
 // fits.  When it does not, the return value is true and every member refuses the step (SLAMGPU_EKF_STATUS_CAPACITY)
-bool ens_known_labels(const slamgpu_ekf_ens *e, const int32_t *ids, int32_t nz, int32_t *lab, std::vector<int32_t> &idn) {
+bool ens_known_labels(const EkfIdTable &table, int nf_known, int max_landmarks, const int32_t *ids, int32_t nz, int32_t *lab, std::vector<int32_t> &idn) {
     for (int32_t i = 0; i < nz; i++) {
-        const int32_t f = e->table.lookup(ids[i]);
+        const int32_t f = table.lookup(ids[i]);
         lab[i] = f >= 0 ? f : SLAMGPU_ASSOC_NEW;
         if (f < 0) idn.push_back(ids[i]);
     }
-    return e->nf_known + (int) idn.size() > e->cfg.max_landmarks;
+    return nf_known + (int) idn.size() > max_landmarks;
+}
+
+// a step's ids against the table's rules: inside [0, 2^20), an id not seen before at most once
+int ens_check_ids(const EkfIdTable &table, const int32_t *ids, int32_t nz) {
+    std::vector<int32_t> unseen;
+    for (int32_t i = 0; i < nz; i++) {
+        if (ids[i] < 0 || ids[i] >= kMaxId) return fail(SLAMGPU_ERR_INVALID, "ids[%d] = %d outside [0, %d)", i, ids[i], kMaxId);
+        if (table.lookup(ids[i]) < 0) unseen.push_back(ids[i]);
+    }
+    std::sort(unseen.begin(), unseen.end());
+    if (std::adjacent_find(unseen.begin(), unseen.end()) != unseen.end())
+        return fail(SLAMGPU_ERR_INVALID, "an id not seen before appears twice in one step (it would be appended twice)");
+    return 0;
+}
+
+// the noise flags and, where control noise is drawn, the lower Cholesky factor of Q, once, in float: L = L00, L10, L11
+int ens_check_noise(const float Q[4], bool draw, uint32_t noise, float L[3]) {
+    L[0] = L[1] = L[2] = 0.0f;
+    if (draw && (noise & SLAMGPU_EKF_ENS_NOISE_CONTROL)) {
+        if (!(Q[0] > 0.0f)) return fail(SLAMGPU_ERR_INVALID, "control noise: Q is not positive definite");
+        L[0] = std::sqrt(Q[0]);
+        L[1] = Q[2] / L[0];
+        const float d = Q[3] - L[1] * L[1];
+        if (!(d > 0.0f)) return fail(SLAMGPU_ERR_INVALID, "control noise: Q is not positive definite");
+        L[2] = std::sqrt(d);
+    }
+    if (draw && (noise & ~7u)) return fail(SLAMGPU_ERR_INVALID, "noise flags %u", noise);
+    return 0;
+}
+
+// the row stride of a step's innovation covariance in LDS, and the launch's dynamic LDS in floats: the heading stage's two columns or the
+// chunk's innovation covariance, whichever is larger (at most 64 KB: np <= 128, ld <= 1056)
+int ens_np(int32_t nz) {
+    int np = 2;
+    while (np < 2 * std::min(nz, kChunk)) np *= 2;
+    return np;
+}
+size_t ens_lds_floats(const slamgpu_ekf_ens *e, int32_t observe, int32_t nz, int np) {
+    size_t lds_floats = observe && e->cfg.batch_update && nz > 0 ? (size_t) np * np : 4;
+    if (e->cfg.use_heading) lds_floats = std::max(lds_floats, 2 * (size_t) e->ld);
+    return lds_floats;
+}
+
+// what every step of a launch shares: the handle's buffers and settings, the noise matrices, the Philox key
+void ens_shared_args(const slamgpu_ekf_ens *e, EnsArgs &a, const float *Q, const float *Re, const float *R, const float L[3], bool draw, uint32_t noise) {
+    a.P = e->P; a.x = e->x; a.dim = e->dim; a.status = e->status; a.acc = e->acc; a.PHt = e->PHt; a.work = e->work; a.iw = e->iw; a.io = e->io;
+    a.members = e->B; a.ld = e->ld; a.cap_dim = e->cap_dim; a.max_landmarks = e->cfg.max_landmarks; a.nzcap = e->nzcap;
+    a.use_heading = e->cfg.use_heading != 0; a.batch_update = e->cfg.batch_update != 0; a.known = e->cfg.association_known != 0;
+    a.draw = draw; a.noise = noise; a.k0 = (uint32_t) e->cfg.seed; a.k1 = (uint32_t) (e->cfg.seed >> 32);
+    a.wheel_base = e->cfg.wheel_base; a.sigma_phi = e->cfg.sigma_phi;
+    a.r_phi = (float) std::pow((double) e->cfg.sigma_phi, 2);
+    a.gate_reject = e->cfg.gate_reject; a.gate_augment = e->cfg.gate_augment;
+    for (int q = 0; q < 4; q++) {
+        a.Q[q] = Q[q];
+        a.Re[q] = Re ? Re[q] : 0.0f;
+        a.R[q] = R ? R[q] : 0.0f;
+    }
+    a.L00 = L[0]; a.L10 = L[1]; a.L11 = L[2];
+    a.sr0 = R ? std::sqrt(R[0]) : 0.0f; a.sr1 = R ? std::sqrt(R[3]) : 0.0f;
+}
+
+// the records of a launch's nq traced steps, from the scratch into the ring's slots next, next + 1, ...
+int ens_trace_launch(slamgpu_ekf_ens *e, int nq, const EnsTapeRec *tape, int K, uint32_t tag) {
+    if (nq <= 0) return 0;
+    ekf_ens_trace_kernel<<<nq, kEkfBlock, 0, e->stream>>>(e->acc.p + 6 * (size_t) e->B, tape, K, tag, e->B, e->tr_rec, e->tr_rtag, (long long) e->ring.next,
+                                                          e->ring.cap);
+    if (int rc = ekf_launched("ekf_ens_trace_kernel")) return rc;
+    e->ring.advance(nq);
+    return 0;
 }
 
 struct EnsStep {
@@ -412,29 +609,18 @@ int ens_step(slamgpu_ekf_ens *e, const EnsStep &s, const int32_t *ids, int32_t n
     if (nz < 0 || nz > kMaxNz) return fail(SLAMGPU_ERR_INVALID, "nz %d outside [0, %d]", nz, kMaxNz);
     if (observe && (!Re || !R || (nz > 0 && (!(s.draw ? s.z_true : s.z) || (known && !ids))))) return fail(SLAMGPU_ERR_INVALID, "bad observation arguments");
     if (!s.draw && (!s.VG || !s.phi)) return fail(SLAMGPU_ERR_INVALID, "null VG or phi");
-    if (observe && known) {
-        std::vector<int32_t> unseen;
-        for (int32_t i = 0; i < nz; i++) {
-            if (ids[i] < 0 || ids[i] >= kMaxId) return fail(SLAMGPU_ERR_INVALID, "ids[%d] = %d outside [0, %d)", i, ids[i], kMaxId);
-            if (e->table.lookup(ids[i]) < 0) unseen.push_back(ids[i]);
-        }
-        std::sort(unseen.begin(), unseen.end());
-        if (std::adjacent_find(unseen.begin(), unseen.end()) != unseen.end())
-            return fail(SLAMGPU_ERR_INVALID, "an id not seen before appears twice in one step (it would be appended twice)");
-    }
-    float L00 = 0, L10 = 0, L11 = 0;
-    if (s.draw && (s.noise & SLAMGPU_EKF_ENS_NOISE_CONTROL)) {  // the lower Cholesky factor of Q, once, in float
-        if (!(Q[0] > 0.0f)) return fail(SLAMGPU_ERR_INVALID, "control noise: Q is not positive definite");
-        L00 = std::sqrt(Q[0]);
-        L10 = Q[2] / L00;
-        const float d = Q[3] - L10 * L10;
-        if (!(d > 0.0f)) return fail(SLAMGPU_ERR_INVALID, "control noise: Q is not positive definite");
-        L11 = std::sqrt(d);
-    }
-    if (s.draw && (s.noise & ~7u)) return fail(SLAMGPU_ERR_INVALID, "noise flags %u", s.noise);
+    if (observe && known)
+        if (int rc = ens_check_ids(e->table, ids, nz)) return rc;
+    float L[3];
+    if (int rc = ens_check_noise(Q, s.draw, s.noise, L)) return rc;
     const size_t B = (size_t) e->B;
     const size_t bytes = sizeof(float) * (s.draw ? 3 * (size_t) nz : 3 * (size_t) nz + 3 * B + 2 * B * (size_t) nz);
-    if (int rc = ens_room(e, nz, bytes)) return rc;
+    const bool traced = e->ring.cap > 0 && truth;  // (one record always fits: the capacity is at least 1)
+    EnsNeeds needs;
+    needs.nz = nz;
+    needs.bytes = bytes;
+    needs.nq = traced ? 1 : 0;
+    if (int rc = ens_room(e, needs)) return rc;
     // the packet: lab | z_true | VG | phi | z in the layout of THIS step's nz; sim_noise sends the first two only
     const int k = e->slots.take();
     if (int rc = e->slots.wait(k)) return rc;
@@ -443,7 +629,7 @@ int ens_step(slamgpu_ekf_ens *e, const EnsStep &s, const int32_t *ids, int32_t n
     float *hf = reinterpret_cast<float *>(h);
     std::vector<int32_t> idn;
     bool refuse = false;
-    if (observe && known) refuse = ens_known_labels(e, ids, nz, lab, idn);
+    if (observe && known) refuse = ens_known_labels(e->table, e->nf_known, e->cfg.max_landmarks, ids, nz, lab, idn);
     else std::fill(lab, lab + nz, SLAMGPU_ASSOC_DISCARD);
     if (s.draw) {
         if (nz > 0) memcpy(hf + nz, s.z_true, 8 * (size_t) nz);
@@ -457,34 +643,123 @@ int ens_step(slamgpu_ekf_ens *e, const EnsStep &s, const int32_t *ids, int32_t n
     if (int rc = e->slots.record(k, e->stream)) return rc;
 
     EnsArgs a{};
-    a.P = e->P; a.x = e->x; a.dim = e->dim; a.status = e->status; a.acc = e->acc; a.PHt = e->PHt; a.work = e->work; a.iw = e->iw; a.io = e->io;
-    a.members = e->B; a.ld = e->ld; a.cap_dim = e->cap_dim; a.max_landmarks = e->cfg.max_landmarks; a.nz = nz; a.nzcap = e->nzcap;
-    int np = 2;
-    while (np < 2 * std::min(nz, kChunk)) np *= 2;
-    a.np = np;
-    a.use_heading = e->cfg.use_heading != 0; a.batch_update = e->cfg.batch_update != 0; a.known = known; a.observe = observe != 0;
-    a.draw = s.draw; a.has_truth = truth != nullptr; a.refuse = refuse;
-    a.noise = s.noise; a.step = s.step; a.k0 = (uint32_t) e->cfg.seed; a.k1 = (uint32_t) (e->cfg.seed >> 32);
-    a.V = s.V; a.G = s.G; a.phi_true = s.phi_true; a.dt = dt; a.wheel_base = e->cfg.wheel_base; a.sigma_phi = e->cfg.sigma_phi;
-    a.r_phi = (float) std::pow((double) e->cfg.sigma_phi, 2);
-    a.gate_reject = e->cfg.gate_reject; a.gate_augment = e->cfg.gate_augment;
-    for (int q = 0; q < 4; q++) {
-        a.Q[q] = s.Qe ? s.Qe[q] : Q[q];
-        a.Re[q] = Re ? Re[q] : 0.0f;
-        a.R[q] = R ? R[q] : 0.0f;
-    }
-    a.L00 = L00; a.L10 = L10; a.L11 = L11;
-    a.sr0 = R ? std::sqrt(R[0]) : 0.0f; a.sr1 = R ? std::sqrt(R[3]) : 0.0f;
-    for (int q = 0; q < 3; q++) a.truth[q] = truth ? truth[q] : 0.0f;
-    // LDS: the heading stage's two columns or the chunk's innovation covariance, whichever is larger (at most 64 KB: np <= 128, ld <= 1056)
-    size_t lds_floats = observe && e->cfg.batch_update && nz > 0 ? (size_t) np * np : 4;
-    if (e->cfg.use_heading) lds_floats = std::max(lds_floats, 2 * (size_t) e->ld);
-    ekf_ens_kernel<<<e->B, kEkfBlock, sizeof(float) * lds_floats, e->stream>>>(a);
+    ens_shared_args(e, a, s.Qe ? s.Qe : Q, Re, R, L, s.draw, s.noise);
+    a.st.nz = nz;
+    a.st.np = ens_np(nz);
+    a.st.observe = observe != 0; a.st.has_truth = truth != nullptr; a.st.refuse = refuse;
+    a.st.q = traced ? 0 : -1;
+    a.st.step = s.step;
+    a.st.V = s.V; a.st.G = s.G; a.st.phi_true = s.phi_true; a.st.dt = dt;
+    for (int q = 0; q < 3; q++) a.st.truth[q] = truth ? truth[q] : 0.0f;
+    const size_t lds_bytes = sizeof(float) * ens_lds_floats(e, observe, nz, a.st.np);
+    if (traced) ekf_ens_kernel<true><<<e->B, kEkfBlock, lds_bytes, e->stream>>>(a);
+    else ekf_ens_kernel<false><<<e->B, kEkfBlock, lds_bytes, e->stream>>>(a);
     if (int rc = ekf_launched("ekf_ens_kernel")) return rc;
+    if (traced)
+        if (int rc = ens_trace_launch(e, 1, nullptr, 0, s.step)) return rc;
     e->last_nz = nz;
     if (!refuse) {  // the step is on its way: only now does the table learn the new ids
         e->table.learn(idn, e->nf_known);
         e->nf_known += (int) idn.size();
+    }
+    return 0;
+}
+
+// slamgpu_ens_run_noise: the whole tape is checked first, against a COPY of the id table that learns step by step as K single calls would
+// teach the table; then one copy through a pinned slot, one launch (and the trace's), and only then the copy replaces the table
+int ens_run(slamgpu_ekf_ens *e, const slamgpu_ens_tape_step *steps, int32_t K, const float *z_true, const int32_t *ids, int32_t total, const float Q[4],
+            const float Qe[4], const float Re[4], const float R[4], uint32_t noise) {
+    if (K < 0 || K > kMaxRun) return fail(SLAMGPU_ERR_INVALID, "K %d outside [0, %d]", K, kMaxRun);
+    if (K == 0) return 0;
+    if (!steps || !Q || total < 0) return fail(SLAMGPU_ERR_INVALID, "null steps or Q, or a negative total");
+    float L[3];
+    if (int rc = ens_check_noise(Q, true, noise, L)) return rc;
+    const bool known = e->cfg.association_known != 0;
+    struct Plan {
+        int32_t nz, refuse;
+        size_t off;
+        std::vector<int32_t> lab;
+    };
+    std::vector<Plan> plan((size_t) K);
+    EkfIdTable table;
+    if (known) table = e->table;
+    int nf_known = e->nf_known;
+    size_t floats = 0, lds_floats = 4;
+    int32_t nzmax = 0, nq = 0;
+    for (int32_t k = 0; k < K; k++) {
+        const slamgpu_ens_tape_step &t = steps[k];
+        Plan &p = plan[(size_t) k];
+        p.nz = t.observe ? t.nz : 0;
+        if (p.nz < 0 || p.nz > kMaxNz) return fail(SLAMGPU_ERR_INVALID, "step %d of the tape: nz %d outside [0, %d]", k, p.nz, kMaxNz);
+        if (t.observe && (!Re || !R)) return fail(SLAMGPU_ERR_INVALID, "step %d of the tape observes: null Re or R", k);
+        if (t.first < 0 || t.first > total) return fail(SLAMGPU_ERR_INVALID, "step %d of the tape: first %d outside [0, %d]", k, t.first, total);
+        if (p.nz > 0) {
+            if (p.nz > total - t.first)
+                return fail(SLAMGPU_ERR_INVALID, "step %d of the tape: observations [%d, %d + %d) outside [0, %d)", k, t.first, t.first, p.nz, total);
+            if (!z_true || (known && !ids)) return fail(SLAMGPU_ERR_INVALID, "step %d of the tape: bad observation arguments", k);
+        }
+        p.refuse = 0;
+        p.lab.assign((size_t) p.nz, SLAMGPU_ASSOC_DISCARD);
+        if (t.observe && known) {
+            if (int rc = ens_check_ids(table, ids + t.first, p.nz)) return rc;
+            std::vector<int32_t> idn;
+            p.refuse = ens_known_labels(table, nf_known, e->cfg.max_landmarks, ids + t.first, p.nz, p.lab.data(), idn);
+            if (!p.refuse) {
+                table.learn(idn, nf_known);
+                nf_known += (int) idn.size();
+            }
+        }
+        p.off = floats;
+        floats += 3 * (size_t) p.nz;
+        nzmax = std::max(nzmax, p.nz);
+        lds_floats = std::max(lds_floats, ens_lds_floats(e, t.observe, p.nz, ens_np(p.nz)));
+        nq += e->ring.cap > 0 && t.has_truth;
+    }
+    if (nq > e->ring.cap && e->ring.cap > 0)
+        return fail(SLAMGPU_ERR_CAPACITY, "the tape has %d steps with a truth, the trace retains %d records", nq, e->ring.cap);
+    const size_t B = (size_t) e->B;
+    const size_t bytes = sizeof(EnsTapeRec) * (size_t) K + sizeof(float) * floats;
+    EnsNeeds needs;
+    needs.nz = nzmax;
+    needs.bytes = needs.tape_bytes = bytes;
+    needs.draw_floats = B * (3 + 2 * (size_t) nzmax);
+    needs.nq = (size_t) nq;
+    if (int rc = ens_room(e, needs)) return rc;
+    const int slot = e->slots.take();
+    if (int rc = e->slots.wait(slot)) return rc;
+    char *h = e->pin.p + (size_t) slot * e->slot_bytes;
+    EnsTapeRec *rec = reinterpret_cast<EnsTapeRec *>(h);
+    float *pk = reinterpret_cast<float *>(h + sizeof(EnsTapeRec) * (size_t) K);
+    int32_t q = 0;
+    for (int32_t k = 0; k < K; k++) {
+        const slamgpu_ens_tape_step &t = steps[k];
+        const Plan &p = plan[(size_t) k];
+        EnsTapeRec &r = rec[k];
+        r.V = t.V; r.G = t.G; r.phi_true = t.phi_true; r.dt = t.dt;
+        for (int c = 0; c < 3; c++) r.truth[c] = t.has_truth ? t.truth[c] : 0.0f;
+        r.has_truth = t.has_truth != 0; r.observe = t.observe != 0; r.nz = p.nz; r.off = (int32_t) p.off; r.refuse = p.refuse; r.np = ens_np(p.nz);
+        r.q = e->ring.cap > 0 && t.has_truth ? q++ : -1;
+        r.step = t.step;
+        r.pad = 0;
+        if (p.nz > 0) {
+            memcpy(pk + p.off, p.lab.data(), 4 * (size_t) p.nz);
+            memcpy(pk + p.off + p.nz, z_true + 2 * (size_t) t.first, 8 * (size_t) p.nz);
+        }
+    }
+    HIP_TRY(hipMemcpyAsync(e->tape, h, bytes, hipMemcpyHostToDevice, e->stream));
+    if (int rc = e->slots.record(slot, e->stream)) return rc;
+
+    EnsArgs a{};
+    ens_shared_args(e, a, Qe ? Qe : Q, Re, R, L, true, noise);
+    const EnsTapeRec *tape = reinterpret_cast<const EnsTapeRec *>(e->tape.p);
+    const float *packet = reinterpret_cast<const float *>(e->tape.p + sizeof(EnsTapeRec) * (size_t) K);
+    ekf_ens_run_kernel<<<e->B, kEkfBlock, sizeof(float) * lds_floats, e->stream>>>(a, tape, packet, e->draws, K, nzmax);
+    if (int rc = ekf_launched("ekf_ens_run_kernel")) return rc;
+    if (int rc = ens_trace_launch(e, nq, tape, K, 0)) return rc;
+    e->last_nz = plan[(size_t) K - 1].nz;
+    if (known) {  // the launch is on its way: only now does the table learn what the tape's steps taught the copy
+        e->table = std::move(table);
+        e->nf_known = nf_known;
     }
     return 0;
 }
@@ -539,6 +814,7 @@ int slamgpu_ens_sim(slamgpu_ekf_ens *e, const float *VG, const float *phi, const
     s.VG = VG;
     s.phi = phi;
     s.z = z;
+    s.step = UINT32_MAX;  // (no Philox word: the trace's tag of such a step)
     return ens_step(e, s, ids, nz, Q, Re, R, dt, observe, truth);
 }
 
@@ -556,6 +832,49 @@ int slamgpu_ens_sim_noise(slamgpu_ekf_ens *e, float V, float G, float phi_true, 
     s.noise = noise;
     s.Qe = Qe;
     return ens_step(e, s, ids, nz, Q, Re, R, dt, observe, truth);
+}
+
+int slamgpu_ens_run_noise(slamgpu_ekf_ens *e, const slamgpu_ens_tape_step *steps, int32_t K, const float *z_true, const int32_t *ids, int32_t total,
+                          const float Q[4], const float Qe[4], const float Re[4], const float R[4], uint32_t noise) {
+    if (int rc = ens_check(e)) return rc;
+    return ens_run(e, steps, K, z_true, ids, total, Q, Qe, Re, R, noise);
+}
+
+int slamgpu_ens_trace_enable(slamgpu_ekf_ens *e, int32_t capacity) {
+    if (int rc = ens_check(e)) return rc;
+    if (capacity < 0 || capacity > kMaxTrace) return fail(SLAMGPU_ERR_INVALID, "trace capacity %d outside [0, %d]", capacity, kMaxTrace);
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    e->ring.reset(0);
+    e->tr_rec.release();
+    e->tr_rtag.release();
+    if (capacity == 0) return 0;
+    if (int rc = e->tr_rec.reserve_zeroed(6 * (size_t) capacity, "EKF ensemble trace records")) return rc;
+    if (int rc = e->tr_rtag.reserve_zeroed((size_t) capacity, "EKF ensemble trace tags")) return rc;
+    e->ring.reset(capacity);
+    return 0;
+}
+
+int slamgpu_ens_trace_info(slamgpu_ekf_ens *e, int64_t *first, int64_t *next, int32_t *capacity) {
+    if (int rc = ens_check(e)) return rc;
+    if (first) *first = e->ring.first;
+    if (next) *next = e->ring.next;
+    if (capacity) *capacity = e->ring.cap;
+    return 0;
+}
+
+int slamgpu_ens_trace_fetch(slamgpu_ekf_ens *e, int64_t first, int32_t count, double *out, uint32_t *step) {
+    if (int rc = ens_check(e)) return rc;
+    if (!e->ring.cap) return fail(SLAMGPU_ERR_INVALID, "the trace is off (slamgpu_ens_trace_enable)");
+    if (!e->ring.check(first, count))
+        return fail(SLAMGPU_ERR_INVALID, "trace records [%lld, %lld) are not retained: [%lld, %lld) are", (long long) first, (long long) first + count,
+                    (long long) e->ring.first, (long long) e->ring.next);
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    const Ring::Runs r = e->ring.stretches(first, count);
+    if (out && r.n0 > 0) HIP_TRY(hipMemcpy(out, e->tr_rec.p + 6 * r.at, sizeof(double) * 6 * (size_t) r.n0, hipMemcpyDeviceToHost));
+    if (out && r.n1 > 0) HIP_TRY(hipMemcpy(out + 6 * r.n0, e->tr_rec.p, sizeof(double) * 6 * (size_t) r.n1, hipMemcpyDeviceToHost));
+    if (step && r.n0 > 0) HIP_TRY(hipMemcpy(step, e->tr_rtag.p + r.at, sizeof(uint32_t) * (size_t) r.n0, hipMemcpyDeviceToHost));
+    if (step && r.n1 > 0) HIP_TRY(hipMemcpy(step + r.n0, e->tr_rtag.p, sizeof(uint32_t) * (size_t) r.n1, hipMemcpyDeviceToHost));
+    return 0;
 }
 
 int slamgpu_ens_last_inputs(slamgpu_ekf_ens *e, float *VG, float *phi, float *z) {

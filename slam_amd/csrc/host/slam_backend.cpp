@@ -131,6 +131,7 @@ static void usage(const char *a0) {
     printf("                        landmark-landmark |correlation|.  -JOINT_OUT path: D, x and the D rows of P as text (%%.17g).  Not with -gpus k > 1 or the EKF\n");
     printf("    -ekf host|device    -method EKF1: where the filter runs.  host (default): float32 loops on the CPU.  device: x and the dense P resident on\n");
     printf("                        the GPU (slamgpu_ekf_sim), same output; refused with a FastSLAM method, and fails without a GPU (no CPU fallback)\n");
+    printf("    -RUNS_BATCH K [-RUNS_TRACE file]  with -runs B: K (1 .. 4096; default 64 up to B = 768, 1 beyond) control steps per launch, the same figures for every K; file: one line per control step with the NEES over the members\n");
     printf("    -runs B [-RUNS_SEED s]  with -method EKF1 -ekf device: B (1 .. 65535) noise realisations of the run as one ensemble of device filters, Monte Carlo NEES at the end; not with -plot\n");
     printf("    -path none|smoothed smoothed: record the path posterior (one record per observation step, -PATH_RECORDS n of them kept, default 4096)\n");
     printf("                        and print one more line: the smoothed path's distance to the true path beside the filtered estimates', and the\n");
@@ -331,18 +332,26 @@ static bool g_map_joint = false;
 static bool g_ekf_device = false;  // -ekf device: EKF1 on the GPU (slamgpu_ekf_*)
 static int g_runs = 0;             // -runs B: B noise realisations at once (slamgpu_ens_*)
 static uint64_t g_runs_seed = 0;   // -RUNS_SEED s: the Philox key of their draws (default: SWITCH_SEED_RANDOM)
+static int g_runs_batch = 0;       // -RUNS_BATCH K: control steps per launch (slamgpu_ens_run_noise); 1: a slamgpu_ens_sim_noise per step; 0: by B (below)
+static std::string g_runs_trace;   // -RUNS_TRACE file: the per-step NEES over the members (slamgpu_ens_trace_*)
 
 // -method EKF1 -ekf device -runs B.  The true path does not depend on the noise (Simulator::control moves xTrue with the true
 // controls and only then perturbs the measured ones; Simulator::observe picks the visible landmarks from xTrue), so the host
 // simulator runs ONCE with its own control and sensor noise off and every control step is one slamgpu_ens_sim_noise: each member
-// draws its own noise on the device and the consistency accumulators take xTrue as the truth
+// draws its own noise on the device and the consistency accumulators take xTrue as the truth.  With -RUNS_BATCH K > 1 the simulator runs
+// K control steps ahead, fills a tape and the ensemble takes it in one slamgpu_ens_run_noise (bit for bit the K single calls)
 constexpr int kEnsHeadroom = 8;
+// without -RUNS_BATCH: 64 steps per launch while every member's workgroup is resident at once (the K-step kernel's registers allow three
+// workgroups on each of the 256 CUs), one step per launch beyond: measured, profiles/ekf_ensemble_run.txt (K = 64 is within 2 % of K = 256
+// and of K = 1 024 up to B = 256; at B = 4 096 the single-step kernel's six workgroups per CU win by a quarter)
+constexpr int kEnsBatch = 64, kEnsBatchMembers = 768;
 static int run_ekf_ensemble(Simulator &sim, long maxsteps) {
     Conf &c = sim.conf;
     const uint32_t noise = (c.SWITCH_CONTROL_NOISE ? SLAMGPU_EKF_ENS_NOISE_CONTROL : 0) | SLAMGPU_EKF_ENS_NOISE_HEADING |
                            (c.SWITCH_SENSOR_NOISE ? SLAMGPU_EKF_ENS_NOISE_SENSOR : 0);
     c.SWITCH_CONTROL_NOISE = 0;
     c.SWITCH_SENSOR_NOISE = 0;
+    if (!g_runs_batch) g_runs_batch = g_runs <= kEnsBatchMembers ? kEnsBatch : 1;
     slamgpu_ekf_ens_config ec{};
     ec.struct_size = sizeof ec;
     ec.device = 0;
@@ -365,22 +374,89 @@ static int run_ekf_ensemble(Simulator &sim, long maxsteps) {
     }
     printf("EKF ensemble on the device: %d members, P allocated for %d landmarks each (the map has %d), Philox key %llu\n\n", g_runs, ec.max_landmarks, sim.map.nlm,
            (unsigned long long) g_runs_seed);
+    FILE *trace = nullptr;
+    if (!g_runs_trace.empty()) {
+        trace = fopen(g_runs_trace.c_str(), "w");
+        if (!trace || slamgpu_ens_trace_enable(ens, g_runs_batch) != 0) {
+            fprintf(stderr, "-RUNS_TRACE %s: %s\n", g_runs_trace.c_str(), trace ? slamgpu_last_error() : "cannot open the file");
+            if (trace) fclose(trace);
+            slamgpu_ens_destroy(ens);
+            return EXIT_FAILURE;
+        }
+        fprintf(trace, "# step  mean NEES over the counted members  share inside the 95 %% bound  rms position error [m]  counted  not counted\n");
+    }
     sim.seed();
     long iter = 0, nobs = 0;
     int rc = 0;
-    const auto t0 = std::chrono::steady_clock::now();
-    while ((maxsteps < 0 || iter < maxsteps) && !rc) {
-        const int r = sim.control();
-        if (r < 0) break;
-        if (r == 1) {
-            sim.observe();
-            nobs++;
+    std::vector<slamgpu_ens_tape_step> tape;
+    std::vector<float> tz;
+    std::vector<int32_t> tid;
+    std::vector<double> rec;
+    std::vector<uint32_t> tag;
+    // the records the last call appended (at most the ring's capacity: nothing is lost between two visits), one line each
+    int64_t drained = 0;
+    auto drain = [&]() {
+        int64_t next = 0;
+        if (!trace || rc) return;
+        rc = slamgpu_ens_trace_info(ens, nullptr, &next, nullptr);
+        const int64_t first = drained;
+        const int32_t n = (int32_t) (next - first);
+        rec.resize(6 * (size_t) n);
+        tag.resize((size_t) n);
+        if (!rc && n > 0) rc = slamgpu_ens_trace_fetch(ens, first, n, rec.data(), tag.data());
+        for (int32_t i = 0; i < n && !rc; i++) {
+            const double *a = &rec[6 * (size_t) i];
+            fprintf(trace, "%u %.6f %.6f %.6f %.0f %.0f\n", tag[(size_t) i], a[0] > 0 ? a[2] / a[0] : NAN, a[0] > 0 ? a[3] / a[0] : NAN,
+                    a[0] > 0 ? std::sqrt(a[4] / a[0]) : NAN, a[0], a[1]);
         }
-        rc = slamgpu_ens_sim_noise(ens, sim.Vtrue, sim.Gtrue, sim.xTrue[2], sim.z.data(), sim.vis.data(), r == 1 ? (int32_t) sim.vis.size() : 0,
-                                       (uint32_t) iter, sim.Q, sim.Qe, sim.Re, sim.R, sim.dt, r == 1, sim.xTrue, noise);
-        iter++;
+        drained = next;
+    };
+    const auto t0 = std::chrono::steady_clock::now();
+    bool more = true;
+    while (more && (maxsteps < 0 || iter < maxsteps) && !rc) {
+        if (g_runs_batch == 1) {
+            const int r = sim.control();
+            if (r < 0) break;
+            if (r == 1) {
+                sim.observe();
+                nobs++;
+            }
+            rc = slamgpu_ens_sim_noise(ens, sim.Vtrue, sim.Gtrue, sim.xTrue[2], sim.z.data(), sim.vis.data(), r == 1 ? (int32_t) sim.vis.size() : 0,
+                                           (uint32_t) iter, sim.Q, sim.Qe, sim.Re, sim.R, sim.dt, r == 1, sim.xTrue, noise);
+            iter++;
+        } else {
+            tape.clear();
+            tz.clear();
+            tid.clear();
+            while ((int) tape.size() < g_runs_batch && (maxsteps < 0 || iter < maxsteps)) {
+                const int r = sim.control();
+                if (r < 0) {
+                    more = false;
+                    break;
+                }
+                slamgpu_ens_tape_step t{};
+                t.V = sim.Vtrue; t.G = sim.Gtrue; t.phi_true = sim.xTrue[2]; t.dt = sim.dt;
+                for (int q = 0; q < 3; q++) t.truth[q] = sim.xTrue[q];
+                t.has_truth = 1;
+                t.observe = r == 1;
+                t.first = (int32_t) tid.size();
+                t.step = (uint32_t) iter;
+                if (r == 1) {
+                    sim.observe();
+                    nobs++;
+                    t.nz = (int32_t) sim.vis.size();
+                    tz.insert(tz.end(), sim.z.begin(), sim.z.begin() + 2 * sim.vis.size());
+                    tid.insert(tid.end(), sim.vis.begin(), sim.vis.end());
+                }
+                tape.push_back(t);
+                iter++;
+            }
+            rc = slamgpu_ens_run_noise(ens, tape.data(), (int32_t) tape.size(), tz.data(), tid.data(), (int32_t) tid.size(), sim.Q, sim.Qe, sim.Re, sim.R, noise);
+        }
+        drain();
     }
     if (!rc) rc = slamgpu_ens_sync(ens);
+    if (trace) fclose(trace);
     const double us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
     const size_t B = (size_t) g_runs;
     std::vector<int32_t> dims(B), status(B);
@@ -891,6 +967,23 @@ int main(int argc, char **argv) {
             g_runs_seed = rs.empty() ? (uint64_t) sim.conf.SWITCH_SEED_RANDOM : strtoull(rs.c_str(), nullptr, 10);
         } else if (!rs.empty()) {
             fprintf(stderr, "-RUNS_SEED s: with -runs B\n");
+            return EXIT_FAILURE;
+        }
+        // ... and -RUNS_BATCH K, -RUNS_TRACE file: how the ensemble's run is launched and its per-step NEES; refused from the arguments alone
+        const std::string rb = sim.conf.s("RUNS_BATCH");
+        g_runs_trace = sim.conf.s("RUNS_TRACE");
+        sim.conf.kv.erase("RUNS_BATCH");
+        sim.conf.kv.erase("RUNS_TRACE");
+        if (!rb.empty()) {
+            const long k = atol(rb.c_str());
+            if (!g_runs || k < 1 || k > 4096) {
+                fprintf(stderr, "-RUNS_BATCH K: %s\n", !g_runs ? "with -runs B" : "K must be 1 .. 4096");
+                return EXIT_FAILURE;
+            }
+            g_runs_batch = (int) k;
+        }
+        if (!g_runs_trace.empty() && !g_runs) {
+            fprintf(stderr, "-RUNS_TRACE file: with -runs B\n");
             return EXIT_FAILURE;
         }
         const std::string mr = sim.conf.s("MAP_MERGE_RADIUS"), mc = sim.conf.s("MAP_MERGE_COHOLD");

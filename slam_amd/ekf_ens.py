@@ -9,6 +9,54 @@ from .capi import SlamGpuError, load_library, _f32, _ptr
 EKF_STATUS_CAPACITY = 2  # SLAMGPU_EKF_STATUS_CAPACITY
 NOISE_CONTROL, NOISE_HEADING, NOISE_SENSOR = 1, 2, 4  # SLAMGPU_EKF_ENS_NOISE_*
 CONSISTENCY_FIELDS = ("counted", "not_counted", "sum_nees", "inside_95", "sum_pos_err2", "sum_heading_err2")
+MAX_RUN = 4096  # steps of one run_noise
+TRACE_TAG_NONE = 0xFFFFFFFF  # the tag of a traced step of sim, which has no Philox step word
+# slamgpu_ens_tape_step
+TAPE_STEP_DTYPE = np.dtype([("V", np.float32), ("G", np.float32), ("phi_true", np.float32), ("dt", np.float32), ("truth", np.float32, (3,)),
+                            ("has_truth", np.int32), ("observe", np.int32), ("nz", np.int32), ("first", np.int32), ("step", np.uint32)])
+
+
+def pack_tape(list_of_steps):
+    """A list of per-step dicts -> (steps, z_true, ids) as run_noise takes them.  A step has V, G, phi_true, dt, step and may have
+    truth (3 floats; absent or None: the step is not counted), observe, z_true [nz, 2] and ids [nz].  The observations of the steps lie one
+    behind the other; a step that does not observe has nz 0 whatever it carries, and `first` is where its observations would start."""
+    steps = np.zeros(len(list_of_steps), TAPE_STEP_DTYPE)
+    zs, idl, at = [], [], 0
+    for k, d in enumerate(list_of_steps):
+        r = steps[k]
+        r["V"], r["G"], r["phi_true"], r["dt"], r["step"] = d["V"], d["G"], d["phi_true"], d["dt"], d["step"]
+        truth = d.get("truth")
+        if truth is not None:
+            r["truth"], r["has_truth"] = np.asarray(truth, np.float32), 1
+        r["observe"] = int(bool(d.get("observe", 0)))
+        z = d.get("z_true")
+        z = np.zeros((0, 2), np.float32) if z is None or not r["observe"] else np.asarray(z, np.float32).reshape(-1, 2)
+        r["nz"], r["first"] = z.shape[0], at
+        if z.shape[0]:
+            i = d.get("ids")
+            i = np.zeros(z.shape[0], np.int32) if i is None else np.asarray(i, np.int32).reshape(-1)
+            if i.shape[0] != z.shape[0]:
+                raise ValueError("step %d: %d ids for %d observations" % (k, i.shape[0], z.shape[0]))
+            zs.append(z)
+            idl.append(i)
+            at += z.shape[0]
+    z_true = np.concatenate(zs) if zs else np.zeros((0, 2), np.float32)
+    ids = np.concatenate(idl) if idl else np.zeros(0, np.int32)
+    return steps, np.ascontiguousarray(z_true, np.float32), np.ascontiguousarray(ids, np.int32)
+
+
+def trace_summary(records):
+    """The trace's records [n, 6] (trace_fetch) as the figures of a consistency plot, [n, 5] in double, one row per step: the mean NEES
+    over the counted members, the share of them inside the 95 % bound, the rms position error, the members counted and not counted
+    (what slam-backend -RUNS_TRACE writes per line).  NaN where no member was counted."""
+    r = np.asarray(records, np.float64).reshape(-1, 6)
+    out = np.full((r.shape[0], 5), np.nan)
+    ok = r[:, 0] > 0
+    out[ok, 0] = r[ok, 2] / r[ok, 0]
+    out[ok, 1] = r[ok, 3] / r[ok, 0]
+    out[ok, 2] = np.sqrt(r[ok, 4] / r[ok, 0])
+    out[:, 3], out[:, 4] = r[:, 0], r[:, 1]
+    return out
 
 
 class EkfEnsConfig(C.Structure):  # slamgpu_ekf_ens_config
@@ -41,6 +89,11 @@ def _lib():
         L.slamgpu_ens_status.argtypes = [vp, vp]
         L.slamgpu_ens_consistency.argtypes = [vp, vp]
         L.slamgpu_ens_consistency_reset.argtypes = [vp]
+        if hasattr(L, "slamgpu_ens_run_noise"):  # (an older build loaded through SLAMGPU_LIB for an A/B lacks the run and the trace)
+            L.slamgpu_ens_run_noise.argtypes = [vp, vp, i32, vp, vp, i32, vp, vp, vp, vp, u32]
+            L.slamgpu_ens_trace_enable.argtypes = [vp, i32]
+            L.slamgpu_ens_trace_info.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(i32)]
+            L.slamgpu_ens_trace_fetch.argtypes = [vp, C.c_int64, i32, vp, vp]
         _bound = True
     return L
 
@@ -149,3 +202,36 @@ class EkfEnsemble:
 
     def consistency_reset(self):
         _chk(self.L.slamgpu_ens_consistency_reset(self.h))
+
+    def run_noise(self, steps, z_true, ids, Q, Re, R, Qe=None, noise=NOISE_CONTROL | NOISE_HEADING | NOISE_SENSOR):
+        """len(steps) steps of sim_noise in one launch: steps is a TAPE_STEP_DTYPE array (pack_tape), z_true[total, 2] and ids[total] hold
+        the observations of all of them.  Bit for bit what the sim_noise calls leave; a bad tape is refused whole"""
+        if steps is not None:
+            steps = np.ascontiguousarray(steps)
+            if steps.dtype != TAPE_STEP_DTYPE:
+                raise TypeError("steps must have TAPE_STEP_DTYPE")
+        K = 0 if steps is None else steps.shape[0]
+        z_true = None if z_true is None else _f32(z_true, (-1, 2))
+        ids = None if ids is None else np.ascontiguousarray(ids, np.int32)
+        total = 0 if z_true is None else z_true.shape[0]
+        Q, Qe, Re, R = (None if a is None else _f32(a) for a in (Q, Qe, Re, R))
+        _chk(self.L.slamgpu_ens_run_noise(self.h, _ptr(steps), K, _ptr(z_true), _ptr(ids), total, _ptr(Q), _ptr(Qe), _ptr(Re), _ptr(R), int(noise)))
+        if K:
+            self._nz = int(steps[-1]["nz"]) if steps[-1]["observe"] else 0
+
+    def trace_enable(self, capacity):
+        """retain the records of the last `capacity` steps that were given a truth; 0 turns the trace off and frees it"""
+        _chk(self.L.slamgpu_ens_trace_enable(self.h, int(capacity)))
+
+    def trace_info(self):
+        """(first, next, capacity): records [first, next) are retained"""
+        first, nxt, cap = C.c_int64(), C.c_int64(), C.c_int32()
+        _chk(self.L.slamgpu_ens_trace_info(self.h, C.byref(first), C.byref(nxt), C.byref(cap)))
+        return first.value, nxt.value, cap.value
+
+    def trace_fetch(self, first, count, out=None, step=None):
+        """(records[count, 6] in double: CONSISTENCY_FIELDS over the members of one step, tags[count]) of records [first, first + count)"""
+        out = np.zeros((count, 6)) if out is None else out
+        step = np.zeros(count, np.uint32) if step is None else step
+        _chk(self.L.slamgpu_ens_trace_fetch(self.h, int(first), int(count), _ptr(out), _ptr(step)))
+        return out, step

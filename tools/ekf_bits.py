@@ -16,7 +16,9 @@ Ensemble:
   - sim_noise with each of the eight noise-flag sets: last_inputs and the slabs;
   - the consistency accumulators and poses of a 40-step run;
   - a capacity refusal (the shared table full);
-  - nz = 3, 70, 3: the buffers grow and the slot ring is reset.
+  - nz = 3, 70, 3: the buffers grow and the slot ring is reset;
+  - (libraries that have slamgpu_ens_run_noise) a 24-step tape in one call and in calls of 1 + 7 + 16: the slabs, last_inputs, the
+    accumulators and the trace's records and tags.
 Both side by side: a B = 1 ensemble and the single handle fed the same 400 steps of example_loop1, their digests on adjacent lines
 (whether they coincide is a finding, not a requirement: the rank update and the gain differ in form).
 
@@ -267,6 +269,28 @@ def ens_grow():
     ens.close()
 
 
+def ens_run():
+    """the tape of tests/test_gpu_ekf_ens_run.py::test_routes_agree_with_the_gates through slamgpu_ens_run_noise, the trace on"""
+    import ekf_ens_run_model as M
+    import test_gpu_ekf_ens_run as T3
+    sim, _, nz = T2.known_host()
+    ob = {3: [], 5: [0, 1, 2, 3], 6: [0, 1, 2, 3, 4, 5], 10: [1, 4], 15: [0, 2, 5, 6], 16: [3, 6, 7], 22: [0, 1, 2, 3, 4, 5, 6, 7]}
+    tp = M.world_tape(24, ob, nz["dt"], sim.conf.WHEELBASE, T3.LM, seed=1)
+    for name, cuts in (("one call", None), ("1 + 7 + 16", [1, 7, 16])):
+        tag = "ens run " + name
+        ens = sg.EkfEnsemble(3, 12, **T2.cfg_of(sim.conf, association_known=False), seed=1234)
+        ens.trace_enable(32)
+        M.drive_run(ens, tp, nz, cuts=cuts)
+        slabs(tag, "end", ens)
+        for what, a in zip(("VG", "phi", "z"), ens.last_inputs()):
+            digest(tag, "last_inputs " + what, a)
+        digest(tag, "consistency", ens.consistency())
+        rec, tags = ens.trace_fetch(0, 24)
+        digest(tag, "trace records", rec)
+        digest(tag, "trace tags", tags)
+        ens.close()
+
+
 # ---- both, side by side -------------------------------------------------------------------------------------------------------------------
 def side_by_side(tp):
     nz, c = tp["noise"], tp["conf"]
@@ -304,4 +328,6 @@ ens_consistency()
 ens_refusal()
 ens_grow()
 side_by_side(tapes["example_loop1"])
+if hasattr(sg.load_library(), "slamgpu_ens_run_noise"):  # new output, behind every line an older library prints
+    ens_run()
 print("ekf_bits: %d digests" % n_digests)

@@ -9,6 +9,13 @@ pipelined (the whole run enqueued, one synchronisation at the end: the time per 
 once with a synchronisation after every step (the time of a control step and of an observation step apart).  The first 200 steps of
 a third handle run untimed before either.  The baselines: slamhost_ekf_step on one core (per control step, times B), and
 slamgpu_ekf_sim fed the host run's tape.
+
+    python tools/ekf_ens_probe.py --batch 1,16,64,256,1024 [--out profiles/ekf_ensemble_run.txt] [--members 1,64,256,1024,4096]
+
+The batch table of slamgpu_ens_run_noise instead: us per control step of the whole ensemble with the run enqueued in batches of K steps
+and one synchronisation at the end, the median of five runs after a warm-up run, smallest and largest beside it.  K = 1 is the loop of
+slamgpu_ens_sim_noise calls, the comparison, taken in the same session; a library without slamgpu_ens_run_noise (an older build
+selected with SLAMGPU_LIB) gives that column alone.
 """
 import argparse
 import os
@@ -68,6 +75,51 @@ def replay(ens, rec, steps=None, sync_each=False):
     return time.perf_counter() - t0, t_ctl, t_obs
 
 
+def packed(slam_amd, rec, K):
+    """the tape in batches of K steps, as run_noise takes them (made once, outside the timed region)"""
+    nz, out = rec["noise"], []
+    dicts = [dict(V=V, G=G, phi_true=phi, dt=nz["dt"], step=k, truth=xt, observe=int(r), z_true=z, ids=vis)
+             for k, (r, V, G, phi, z, vis, xt) in enumerate(rec["tape"])]
+    for at in range(0, len(dicts), K):
+        out.append(slam_amd.pack_tape(dicts[at:at + K]))
+    return out
+
+
+def replay_batches(ens, rec, batches):
+    nz = rec["noise"]
+    t0 = time.perf_counter()
+    for steps, z_true, ids in batches:
+        ens.run_noise(steps, z_true, ids, nz["Q"], nz["Re"], nz["R"], Qe=nz["Qe"], noise=rec["flags"])
+    ens.sync()
+    return time.perf_counter() - t0
+
+
+def batch_table(slam_amd, host, a, say):
+    has_run = hasattr(slam_amd.load_library(), "slamgpu_ens_run_noise")
+    Ks = [int(k) for k in a.batch.split(",") if int(k) == 1 or has_run]
+    say("# tools/ekf_ens_probe.py --batch %s --members %s   library %s%s" % (a.batch, a.members, "SLAMGPU_LIB" if os.environ.get("SLAMGPU_LIB") else os.path.relpath(slam_amd.lib_path(), ROOT),
+                                                                          "" if has_run else " (no slamgpu_ens_run_noise: K = 1 only)"))
+    say("# us per control step of the whole ensemble, pipelined, one synchronisation at the end: median of 5 runs after a warm-up run [smallest .. largest]")
+    for name, seed in MAPS:
+        rec = record(host, name, seed)
+        n = len(rec["tape"])
+        say("%s seed %d: %d control steps, %d with an observation, noise flags %d" % (name, seed, n, sum(1 for t in rec["tape"] if t[0]), rec["flags"]))
+        say("    %6s " % "B" + " ".join("%28s" % ("K = %d" % K) for K in Ks))
+        tapes = {K: packed(slam_amd, rec, K) for K in Ks if K > 1}
+        for B in (int(b) for b in a.members.split(",")):
+            cells = []
+            for K in Ks:
+                times = []
+                for rep in range(6):
+                    e = slam_amd.EkfEnsemble(B, rec["nlm"] + HEADROOM, **cfg_of(rec["conf"]), seed=seed)
+                    t = replay(e, rec)[0] if K == 1 else replay_batches(e, rec, tapes[K])
+                    e.close()
+                    if rep:
+                        times.append(1e6 * t / n)
+                cells.append("%9.2f [%7.2f .. %7.2f]" % (float(np.median(times)), min(times), max(times)))
+            say("    %6d " % B + " ".join("%28s" % c for c in cells))
+
+
 def baselines(slam_amd, host, name, seed, say):
     sim = host.HostSim(["-m", os.path.join(ROOT, "data", name + ".mat"), "-method", "EKF1", "-SWITCH_SEED_RANDOM", seed])
     ekf = host.HostEkf(sim)
@@ -101,6 +153,7 @@ def main():
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "ekf_ensemble.txt"))
     ap.add_argument("--members", default="1,64,256,1024,4096")
     ap.add_argument("--nees-members", type=int, default=1024)
+    ap.add_argument("--batch", default=None, help="K,K,...: the batch table of slamgpu_ens_run_noise instead")
     a = ap.parse_args()
     import slam_amd
     from slam_amd import host
@@ -114,6 +167,9 @@ def main():
         out.write(line + "\n")
         out.flush()
 
+    if a.batch:
+        batch_table(slam_amd, host, a, say)
+        return
     say("# tools/ekf_ens_probe.py --members %s --nees-members %d" % (a.members, a.nees_members))
     for name, seed in MAPS:
         rec = record(host, name, seed)
