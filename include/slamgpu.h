@@ -1200,6 +1200,35 @@ int slamgpu_ens_trace_enable(slamgpu_ekf_ens *e, int32_t capacity);
 int slamgpu_ens_trace_info(slamgpu_ekf_ens *e, int64_t *first, int64_t *next, int32_t *capacity);
 int slamgpu_ens_trace_fetch(slamgpu_ekf_ens *e, int64_t first, int32_t count, double *out /*[count][6]*/, uint32_t *step /*[count]*/);
 
+/* ---- EKF-SLAM ensemble, continued: the sample mean and covariance of the members' states beside the mean of their own P.  STABLE.
+ * The accumulators and the trace judge the pose against a truth; this answers whether the filter's P is the spread the members really
+ * have, for the whole state, the map and the cross-correlations included, without one slamgpu_ens_state per member.
+ * moments: summarises the leading D components of the state in the EKF's ordering (x, y, theta, then two per feature): D odd,
+ *      3 <= D <= 3 + 2 max_landmarks, anything else SLAMGPU_ERR_INVALID.  With association_known the one id table makes feature f the
+ *      same landmark in every member, and any D up to the members' dimension is meaningful.  With the gates the ORDER OF THE FEATURES IS
+ *      EACH MEMBER'S OWN: D = 3, the pose alone, is what makes sense there (a larger D is not refused).
+ *      The call synchronises the handle's stream, only reads, and changes nothing in the handle: every slab, dim, status, the
+ *      accumulators, the trace and what last_inputs returns are bit for bit what they were.
+ *      The set J: member b is in J when dim[b] >= D, (status[b] & exclude_status) == 0, x[b][0:D] is finite and the diagonal of P[b]
+ *      over [0, D) is finite.  counted = |J| = n, left_out = members - n, pivot = the lowest member of J (-1: J is empty).
+ *      v_b = (x, y, u, features ...) with u = IEEE remainder(theta_b - theta_pivot, 2 pi) in double (the way slamgpu_pose_summary takes a
+ *      heading's deviation) and every other component x_b - x_pivot in double.  delta = sum v / n.
+ *        mean[D]    = pivot + delta; its heading is theta_pivot + delta_u wrapped into (-pi, pi] as slamhost_joint_dense wraps
+ *        C[D][D]    = sum v v^T / n - delta delta^T: the POPULATION form; the unbiased estimate is n / (n - 1) times it
+ *        Pbar[D][D] = sum P_b[0:D, 0:D] / n, summed in double
+ *      both matrices full, row-major with leading dimension D, (i, j) == (j, i) bit for bit; C or Pbar NULL: not computed (the mean of P
+ *      is the pass that costs; the other outputs' bits do not depend on which are asked for).  n = 0: mean, C and Pbar are all NaN and
+ *      the return is 0.  n = 1: C is exactly 0.
+ *      Deterministic: tiles of 256 consecutive members; every sum over members in ascending member order within a tile (the Gram
+ *      products four members per matrix instruction), the tiles in ascending order, no atomics; the results do not depend on how the
+ *      work is chunked nor on earlier calls.
+ *      Nothing is allocated and no kernel of it is launched until the first call; the workspace only grows, stays under 40 MiB whatever
+ *      `members` is (block pairs of the Gram matrix and row blocks of Pbar go through 16 MiB of per-tile partials in chunks;
+ *      SLAMGPU_ENS_MOMENTS_CHUNK, read at the call, forces smaller chunks: a diagnostic) and is released by slamgpu_ens_destroy.
+ *      A null handle, a null mean or a bad D: SLAMGPU_ERR_INVALID and the outputs are untouched.  What it costs: DESIGN.md section 7i. */
+int slamgpu_ens_moments(slamgpu_ekf_ens *e, int32_t D, uint32_t exclude_status, double *mean /*[D]*/, double *C /*[D][D] or NULL*/,
+                        double *Pbar /*[D][D] or NULL*/, int32_t *counted, int32_t *left_out, int32_t *pivot);
+
 #ifdef __cplusplus
 }
 #endif

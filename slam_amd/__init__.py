@@ -7,7 +7,7 @@ from .capi import (Config, ShardPlan, SlamGpu, SlamGpuError, FASTSLAM1, FASTSLAM
                    lib_path, load_library, jacobians, kat, device_count, DECLARED_SYMBOLS, DistGroup, dist_comm_id)
 
 from .ekf import EkfGpu, EkfConfig, EKF_STATUS_NOT_PD
-from .ekf_ens import EkfEnsemble, EkfEnsConfig, EKF_STATUS_CAPACITY, TAPE_STEP_DTYPE, pack_tape, trace_summary
+from .ekf_ens import EkfEnsemble, EkfEnsConfig, EKF_STATUS_CAPACITY, TAPE_STEP_DTYPE, pack_tape, trace_summary, moments_summary
 
-__all__ = ["EkfGpu", "EkfConfig", "EKF_STATUS_NOT_PD", "EkfEnsemble", "EkfEnsConfig", "EKF_STATUS_CAPACITY", "TAPE_STEP_DTYPE", "pack_tape", "trace_summary", "Config", "ShardPlan", "SlamGpu", "SlamGpuError", "FASTSLAM1", "FASTSLAM2", "RNG_TAPE", "RNG_PHILOX", "MATH_STRICT",
+__all__ = ["EkfGpu", "EkfConfig", "EKF_STATUS_NOT_PD", "EkfEnsemble", "EkfEnsConfig", "EKF_STATUS_CAPACITY", "TAPE_STEP_DTYPE", "pack_tape", "trace_summary", "moments_summary", "Config", "ShardPlan", "SlamGpu", "SlamGpuError", "FASTSLAM1", "FASTSLAM2", "RNG_TAPE", "RNG_PHILOX", "MATH_STRICT",
            "MATH_FAST", "lib_path", "load_library", "jacobians", "kat", "device_count", "DECLARED_SYMBOLS", "DistGroup", "dist_comm_id"]

@@ -43,6 +43,7 @@ DECLARED_SYMBOLS = [
     "slamgpu_ens_last_inputs", "slamgpu_ens_dims", "slamgpu_ens_poses", "slamgpu_ens_state", "slamgpu_ens_slab",
     "slamgpu_ens_upload", "slamgpu_ens_status", "slamgpu_ens_consistency", "slamgpu_ens_consistency_reset",
     "slamgpu_ens_run_noise", "slamgpu_ens_trace_enable", "slamgpu_ens_trace_info", "slamgpu_ens_trace_fetch",
+    "slamgpu_ens_moments",
 ]
 MAP_STRIDE = 9  # SLAMGPU_MAP_STRIDE
 PATH_STRIDE = 7  # SLAMGPU_PATH_STRIDE

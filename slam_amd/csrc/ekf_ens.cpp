@@ -399,6 +399,298 @@ __global__ void __launch_bounds__(kEkfBlock) ekf_ens_pose_kernel(const float *__
     out[e] = q < 3 ? (double) x[(size_t) b * ld + q] : (double) P[(size_t) b * cap_dim * ld + (size_t) ((q - 3) / 3) * ld + (q - 3) % 3];
 }
 
+// ---- slamgpu_ens_moments: the sample mean and covariance of the members' states and the mean of their P, over the set J of the header.
+// Tiles of kMomTile consecutive members; every sum over members ascending within a tile, the tiles ascending, no atomics.  The Gram
+// pass is slamgpu_joint_summary's (kernels.hip, joint_gram_kernel) without weights, genealogy or records: a copy of its own, because
+// that kernel lives in the particle filter's unit behind its Buffers and a shared form would change its instructions.
+constexpr int kMomTile = 256;   // consecutive members of a tile (= kEkfBlock: a lane per member where a tile's flags are staged)
+constexpr int kMomSubMax = 16;  // members centred into LDS at a time: 16 (four matrix instructions' worth) up to 320 columns of d_ext, 4 beyond
+constexpr int kMomGroup = 16;   // block pairs of a workgroup of the Gram pass: four per wave
+constexpr int kMomBatch = 32;   // members whose loads a lane of the mean-of-P pass has in flight (one word of the tile's flag bits)
+constexpr int kMomSelLanes = 4; // lanes of the select pass that share a member
+constexpr double kMomTwoPi = 6.283185307179586476925286766559;
+typedef double mom_d4 __attribute__((ext_vector_type(4)));
+
+// first, count: the chunk of block pairs (Gram, reduce) or of row blocks of `rows` rows of P (mean of P) that goes through `part`
+struct MomArgs {
+    const float *P, *x;
+    const int32_t *dim, *status;
+    int32_t members, ld, cap_dim, D, Dp, tiles, first, count, rows;
+    uint32_t exclude;
+    int32_t *flag;       // [members] 1: in J
+    int32_t *info;       // pivot (-1: J is empty), n
+    double *pivot;       // [Dp] the pivot's x[0:D], then zeros
+    double *sums;        // [block pairs][256] sum d_ext d_ext^T, lower-triangle block pairs R (R + 1) / 2 + C
+    double *part;        // the chunk's partials, per tile
+    double *mean, *C, *Pbar;
+};
+
+// the lowest member and the count of a workgroup's lanes: in every lane on return
+__device__ __forceinline__ void mom_first_count(int &first, int &cnt, int *sh) {
+    for (int d = 32; d > 0; d >>= 1) {
+        first = min(first, __shfl_xor(first, d, 64));
+        cnt += __shfl_xor(cnt, d, 64);
+    }
+    const int wave = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) {
+        sh[2 * wave] = first;
+        sh[2 * wave + 1] = cnt;
+    }
+    __syncthreads();
+    first = sh[0];
+    cnt = sh[1];
+    for (int v = 1; v < kEkfBlock / 64; v++) {
+        first = min(first, sh[2 * v]);
+        cnt += sh[2 * v + 1];
+    }
+}
+
+// select: kMomSelLanes lanes per member, each every kMomSelLanes-th component; integers only (finite: the exponent field is not all ones)
+__global__ void __launch_bounds__(kEkfBlock) ekf_ens_mom_select_kernel(MomArgs m) {
+    const int b = blockIdx.x * (kEkfBlock / kMomSelLanes) + threadIdx.x / kMomSelLanes, q = threadIdx.x & (kMomSelLanes - 1);
+    int ok = 0;
+    if (b < m.members) {
+        ok = m.dim[b] >= m.D && ((uint32_t) m.status[b] & m.exclude) == 0u;
+        if (ok) {
+            const float *xb = m.x + (size_t) b * m.ld, *Pb = m.P + (size_t) b * m.cap_dim * m.ld;
+            for (int c = q; c < m.D; c += kMomSelLanes) {
+                const uint32_t ux = __float_as_uint(xb[c]), up = __float_as_uint(Pb[(size_t) c * m.ld + c]);
+                ok &= (ux & 0x7f800000u) != 0x7f800000u && (up & 0x7f800000u) != 0x7f800000u;
+            }
+        }
+    }
+    for (int d = 1; d < kMomSelLanes; d <<= 1) ok &= __shfl_xor(ok, d, 64);
+    if (b < m.members && q == 0) m.flag[b] = ok;
+}
+
+// one workgroup: the pivot (the lowest member of J), n and the pivot's vector
+__global__ void __launch_bounds__(kEkfBlock) ekf_ens_mom_pivot_kernel(MomArgs m) {
+    __shared__ int sh[2 * (kEkfBlock / 64)];
+    int first = INT_MAX, cnt = 0;
+    for (int b = threadIdx.x; b < m.members; b += kEkfBlock)
+        if (m.flag[b]) {
+            first = min(first, b);
+            cnt++;
+        }
+    mom_first_count(first, cnt, sh);
+    if (threadIdx.x == 0) {
+        m.info[0] = cnt ? first : -1;
+        m.info[1] = cnt;
+    }
+    for (int c = threadIdx.x; c < m.Dp; c += kEkfBlock) m.pivot[c] = cnt && c < m.D ? (double) m.x[(size_t) first * m.ld + c] : 0.0;
+}
+
+// Gram pass, grid (tiles, groups of kMomGroup block pairs): d_ext = (v - pivot, 1) of SUB members at a time in LDS, rows of ldl
+// doubles (an odd multiple of 16: the four members of an instruction never share banks), zero outside J and in the padding; each wave
+// four block pairs, A[m = lane & 15][k = lane >> 4] = d[row block + m], B[k][n = lane & 15] = d[column block + n] of member k.
+// Lane tid stages member tid & (SUB - 1) of the sub-tile, columns tid / SUB + (256 / SUB) k, k < NP.  The members' floats of DEPTH
+// sub-tiles are fetched into registers at once, unconditionally (past the tile's end and past column D the last valid one again, never
+// used).  A tile is a chain of sub-tiles, each two barriers and a few LDS round trips long, and the kernel's time is that chain's: SUB is
+// 16 wherever 16 rows of d_ext fit in LDS (43 KB at 320 columns), 4 beyond.  NP, DEPTH and SUB are compiled in so that the fetched floats
+// are registers; the heading's deviation, the one remainder, is taken once per member before the loop
+template <int NP, int DEPTH, int SUB>
+__global__ void __launch_bounds__(kEkfBlock) ekf_ens_mom_gram_kernel(MomArgs m) {
+#pragma clang fp contract(off)
+    extern __shared__ double mom_lds[];  // d_ext [SUB][ldl] | pivot [Dp]
+    __shared__ int sh_flag[kMomTile];
+    __shared__ double sh_u[kMomTile];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int ldl = (m.Dp & 16) ? m.Dp : m.Dp + 16;
+    double *sh_d = mom_lds, *sh_p = mom_lds + SUB * ldl;
+    const int b0 = blockIdx.x * kMomTile;
+    {
+        const int f = b0 + tid < m.members ? m.flag[b0 + tid] : 0;
+        sh_flag[tid] = f;
+        sh_u[tid] = f ? remainder((double) m.x[(size_t) (b0 + tid) * m.ld + 2] - m.pivot[2], kMomTwoPi) : 0.0;
+    }
+    for (int c = tid; c < m.Dp; c += kEkfBlock) sh_p[c] = m.pivot[c];
+    for (int e = tid; e < SUB * ldl; e += kEkfBlock) sh_d[e] = 0.0;  // (the padding columns stay zero)
+    __syncthreads();
+    int rb[4], cb[4];
+    bool bv[4];
+    mom_d4 acc[4];
+#pragma unroll
+    for (int b = 0; b < 4; b++) {
+        const int bpl = blockIdx.y * kMomGroup + wave * 4 + b;
+        bv[b] = bpl < m.count;
+        const int bp = m.first + bpl;
+        int R = 0;
+        while ((R + 1) * (R + 2) / 2 <= bp) R++;
+        rb[b] = bv[b] ? R * 16 : 0;
+        cb[b] = bv[b] ? (bp - R * (R + 1) / 2) * 16 : 0;
+        acc[b] = mom_d4{0.0, 0.0, 0.0, 0.0};
+    }
+    const int nsub = (min(kMomTile, m.members - b0) + SUB - 1) / SUB;
+    const int p = tid & (SUB - 1), c0 = tid / SUB;
+    constexpr int kStep = kEkfBlock / SUB;
+    for (int s0 = 0; s0 < nsub; s0 += DEPTH) {
+        float xv[DEPTH][NP];
+#pragma unroll
+        for (int d = 0; d < DEPTH; d++) {
+            const float *xb = m.x + (size_t) min(b0 + (s0 + d) * SUB + p, m.members - 1) * m.ld;
+#pragma unroll
+            for (int k = 0; k < NP; k++) xv[d][k] = xb[min(c0 + kStep * k, m.D - 1)];
+        }
+#pragma unroll
+        for (int d = 0; d < DEPTH; d++) {
+            const int st = s0 + d;
+            if (st < nsub) {  // (uniform)
+                const int q = st * SUB + p;
+                const bool in = q < kMomTile && sh_flag[q] != 0;
+#pragma unroll
+                for (int k = 0; k < NP; k++) {
+                    const int c = c0 + kStep * k;
+                    if (c <= m.D) {
+                        double v = 0.0;
+                        if (in) v = c == m.D ? 1.0 : c == 2 ? sh_u[q] : (double) xv[d][k] - sh_p[c];
+                        sh_d[p * ldl + c] = v;
+                    }
+                }
+                __syncthreads();
+#pragma unroll
+                for (int kk = 0; kk < SUB / 4; kk++) {  // four members per instruction, in ascending order
+                    const double *rw = sh_d + (kk * 4 + (lane >> 4)) * ldl + (lane & 15);
+#pragma unroll
+                    for (int b = 0; b < 4; b++)  // (a wave with fewer than four block pairs computes block pair (0, 0) in their place and drops it: a
+                        acc[b] = __builtin_amdgcn_mfma_f64_16x16x4f64(rw[rb[b]], rw[cb[b]], acc[b], 0, 0, 0);  // test here costs the accumulators their registers)
+                }
+                __syncthreads();
+            }
+        }
+    }
+    // C/D of the f64 form: col = lane & 15, row = (lane >> 4) + 4 reg
+#pragma unroll
+    for (int b = 0; b < 4; b++) {
+        if (bv[b]) {
+            const int bpl = blockIdx.y * kMomGroup + wave * 4 + b;
+            double *o = m.part + ((size_t) blockIdx.x * (size_t) m.count + (size_t) bpl) * 256;
+#pragma unroll
+            for (int reg = 0; reg < 4; reg++) o[((lane >> 4) + 4 * reg) * 16 + (lane & 15)] = acc[b][reg];
+        }
+    }
+}
+
+// the tiles' partials of one block pair, added in ascending order
+__global__ void __launch_bounds__(kEkfBlock) ekf_ens_mom_reduce_kernel(MomArgs m) {
+#pragma clang fp contract(off)
+    double s = 0.0;
+    for (int t = 0; t < m.tiles; t++) s = s + m.part[((size_t) t * (size_t) m.count + blockIdx.x) * 256 + threadIdx.x];
+    m.sums[(size_t) (m.first + blockIdx.x) * 256 + threadIdx.x] = s;
+}
+
+// entry (r, c), c <= r, of sum d_ext d_ext^T
+__device__ __forceinline__ double mom_sum(const MomArgs &m, int r, int c) {
+    const int R = r >> 4;
+    return m.sums[(size_t) (R * (R + 1) / 2 + (c >> 4)) * 256 + (r & 15) * 16 + (c & 15)];
+}
+
+// mean and C, a thread per output: e < D the mean's components, then the lower triangle of C (both halves written)
+__global__ void __launch_bounds__(kEkfBlock) ekf_ens_mom_finish_kernel(MomArgs m) {
+#pragma clang fp contract(off)
+    const int D = m.D, T = m.C ? D * (D + 1) / 2 : 0;
+    const int e = blockIdx.x * kEkfBlock + threadIdx.x;
+    if (e >= D + T) return;
+    const int cnt = m.info[1];
+    const double n = (double) cnt, nan = __longlong_as_double(0x7ff8000000000000ll);
+    if (e < D) {
+        double v = nan;
+        if (cnt) {
+            v = m.pivot[e] + mom_sum(m, D, e) / n;
+            if (e == 2) {  // the heading into (-pi, pi], as slamhost_joint_dense wraps
+                v = remainder(v, kMomTwoPi);
+                if (v <= -kMomTwoPi / 2) v += kMomTwoPi;
+            }
+        }
+        m.mean[e] = v;
+        return;
+    }
+    const int t = e - D;
+    int r = (int) ((sqrt(8.0 * (double) t + 1.0) - 1.0) * 0.5);
+    while (r * (r + 1) / 2 > t) r--;
+    while ((r + 1) * (r + 2) / 2 <= t) r++;
+    const int c = t - r * (r + 1) / 2;
+    double v = nan;
+    if (cnt) {
+        const double dr = mom_sum(m, D, r) / n, dc = mom_sum(m, D, c) / n;
+        v = mom_sum(m, r, c) / n - dr * dc;
+    }
+    m.C[(size_t) r * D + c] = v;
+    m.C[(size_t) c * D + r] = v;
+}
+
+// mean of P, grid (row blocks of the chunk, tiles): the block's rows are one stretch of `rows` ld floats of a member's slab, a lane
+// four columns of it at a time (16-byte loads), the tile's members in ascending order, in double; members outside J are skipped by a
+// test of the tile's flag bits that is uniform across the workgroup.  Only the float4s that reach into the lower triangle
+__global__ void __launch_bounds__(kEkfBlock) ekf_ens_mom_pbar_kernel(MomArgs m) {
+#pragma clang fp contract(off)
+    __shared__ uint32_t sh_mask[kMomTile / 32];
+    const int tid = threadIdx.x, t = blockIdx.y;
+    const int b0 = t * kMomTile;
+    {
+        const unsigned long long bal = __ballot(b0 + tid < m.members && m.flag[b0 + tid] != 0);
+        if ((tid & 63) == 0) {
+            sh_mask[2 * (tid >> 6)] = (uint32_t) bal;
+            sh_mask[2 * (tid >> 6) + 1] = (uint32_t) (bal >> 32);
+        }
+    }
+    __syncthreads();
+    const int cnt = min(kMomTile, m.members - b0);
+    const int ld4 = m.ld / 4, r0 = (m.first + (int) blockIdx.x) * m.rows, nrow = min(m.rows, m.D - r0);
+    const size_t slab4 = (size_t) m.cap_dim * ld4;
+    double *o = m.part + ((size_t) t * (size_t) m.count + blockIdx.x) * ((size_t) m.rows * m.ld);
+    for (int e = tid; e < nrow * ld4; e += kEkfBlock) {
+        const int rl = e / ld4, c4 = e - rl * ld4;
+        if (4 * c4 > r0 + rl) continue;
+        const float4 *src = reinterpret_cast<const float4 *>(m.P) + (size_t) b0 * slab4 + (size_t) (r0 + rl) * ld4 + c4;
+        double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
+        for (int q0 = 0; q0 < cnt; q0 += kMomBatch) {
+            const uint32_t bits = (uint32_t) __builtin_amdgcn_readfirstlane((int) sh_mask[q0 >> 5]);
+            static_assert(kMomBatch == 32, "a batch is one word of the flag bits");
+            if (!bits) continue;  // (nobody of this batch is in J)
+            // every load of the batch is issued before the first sum waits for one: the loads are NOT under the flag's test (a load inside
+            // a branch made the compiler wait for each before the next: the pass ran at one load's latency per member), only the sums
+            // are; a member outside J costs its bytes, nothing else.  Past the tile's end the last member is read again and not added
+            float4 v[kMomBatch];
+#pragma unroll
+            for (int j = 0; j < kMomBatch; j++) v[j] = src[(size_t) min(q0 + j, cnt - 1) * slab4];
+#pragma unroll
+            for (int j = 0; j < kMomBatch; j++)
+                if (bits >> j & 1u) {
+                    a0 = a0 + (double) v[j].x;
+                    a1 = a1 + (double) v[j].y;
+                    a2 = a2 + (double) v[j].z;
+                    a3 = a3 + (double) v[j].w;
+                }
+        }
+        double *oe = o + (size_t) rl * m.ld + 4 * c4;
+        oe[0] = a0;
+        oe[1] = a1;
+        oe[2] = a2;
+        oe[3] = a3;
+    }
+}
+
+// ... and its finish, a thread per entry (row of the chunk, column < D): the tiles in ascending order, over n, mirrored
+__global__ void __launch_bounds__(kEkfBlock) ekf_ens_mom_pbar_finish_kernel(MomArgs m) {
+#pragma clang fp contract(off)
+    const int D = m.D, r0 = m.first * m.rows, nrow = min(m.count * m.rows, D - r0);
+    const int e = blockIdx.x * kEkfBlock + threadIdx.x;
+    if (e >= nrow * D) return;
+    const int ra = e / D, c = e - ra * D, r = r0 + ra;
+    if (c > r) return;
+    const int rbl = ra / m.rows, rl = ra - rbl * m.rows;
+    const int cnt = m.info[1];
+    double v = __longlong_as_double(0x7ff8000000000000ll);
+    if (cnt) {
+        const size_t block = (size_t) m.rows * m.ld;
+        double s = 0.0;
+        for (int t = 0; t < m.tiles; t++) s = s + m.part[((size_t) t * (size_t) m.count + rbl) * block + (size_t) rl * m.ld + c];
+        v = s / (double) cnt;
+    }
+    m.Pbar[(size_t) r * D + c] = v;
+    m.Pbar[(size_t) c * D + r] = v;
+}
+
 }  // namespace
 
 struct slamgpu_ekf_ens {
@@ -424,6 +716,8 @@ struct slamgpu_ekf_ens {
     Ring ring;
     DevBuf<double> tr_rec;
     DevBuf<uint32_t> tr_rtag;
+    // slamgpu_ens_moments: its workspace, nothing until the first call, grow-only
+    DevBuf<char> mom;
 };
 
 namespace {
@@ -449,6 +743,7 @@ void ens_release(slamgpu_ekf_ens *e) {
     e->draws.release();
     e->tr_rec.release();
     e->tr_rtag.release();
+    e->mom.release();
     e->pin.release();
     e->slots.release();
     e->stream.release();
@@ -764,6 +1059,88 @@ int ens_run(slamgpu_ekf_ens *e, const slamgpu_ens_tape_step *steps, int32_t K, c
     return 0;
 }
 
+// slamgpu_ens_moments: how many of `items` (block pairs of the Gram matrix, row blocks of P) go through the table of per-tile partials at
+// a time: at most kMomPartBytes of it, at least one.  SLAMGPU_ENS_MOMENTS_CHUNK, read at the call, forces fewer (the tests reach the
+// chunked path at small sizes with it).  With the sums of the block pairs (4.4 MB at D = 1027), the outputs' staging (mean, C and Pbar in
+// double: 16.9 MB at D = 1027), the flags (4 bytes a member, at most 65 535 of them) and the pivot, the workspace stays under 40 MiB
+// whatever the ensemble's size
+constexpr size_t kMomPartBytes = (size_t) 16 << 20;
+int mom_chunk(size_t bytes_per_item, int items) {
+    int fit = (int) std::max<size_t>(1, kMomPartBytes / bytes_per_item);
+    if (const char *s = getenv("SLAMGPU_ENS_MOMENTS_CHUNK")) fit = std::min(fit, std::max(1, atoi(s)));
+    return std::min(fit, items);
+}
+
+int ens_moments(slamgpu_ekf_ens *e, int32_t D, uint32_t exclude_status, double *mean, double *C, double *Pbar, int32_t *counted, int32_t *left_out,
+                int32_t *pivot) {
+    if (!mean) return fail(SLAMGPU_ERR_INVALID, "null mean");
+    if (D < 3 || D > e->cap_dim || !(D & 1)) return fail(SLAMGPU_ERR_INVALID, "D %d: odd, 3 .. %d", D, e->cap_dim);
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    const int B = e->B, T = (B + kMomTile - 1) / kMomTile, Dp = (D + 1 + 15) / 16 * 16, nb = Dp / 16, nbp = nb * (nb + 1) / 2;
+    const int bp_lo = C ? 0 : nb * (nb - 1) / 2;  // without C only the block row of the column of ones: sum d and n
+    const int bp_chunk = mom_chunk(sizeof(double) * 256 * (size_t) T, nbp - bp_lo);
+    const int rows = std::max(1, 512 / e->ld), nrb = (D + rows - 1) / rows;  // a row block: about 128 float4s (more workgroups, not fuller ones)
+    const size_t rb_doubles = (size_t) T * rows * e->ld;
+    const int rb_chunk = Pbar ? mom_chunk(sizeof(double) * rb_doubles, nrb) : 0;
+    const size_t DD = (size_t) D * D;
+    Layout L;  // what goes up first, in one stretch
+    const auto info = L.take<int32_t>(4, 8);
+    const auto mean_d = L.take<double>((size_t) D, 8), C_d = L.take<double>(C ? DD : 0, 8), P_d = L.take<double>(Pbar ? DD : 0, 8);
+    const size_t up = L.total();
+    const auto flag = L.take<int32_t>((size_t) B, 8);
+    const auto piv = L.take<double>((size_t) Dp, 8), sums = L.take<double>(256 * (size_t) nbp, 8);
+    const auto part = L.take<double>(std::max(256 * (size_t) T * bp_chunk, rb_doubles * rb_chunk), 8);
+    if (int rc = e->mom.reserve(L.total(), "EKF ensemble moments workspace")) return rc;
+    MomArgs m{};
+    m.P = e->P; m.x = e->x; m.dim = e->dim; m.status = e->status;
+    m.members = B; m.ld = e->ld; m.cap_dim = e->cap_dim; m.D = D; m.Dp = Dp; m.tiles = T; m.rows = rows;
+    m.exclude = exclude_status;
+    m.flag = flag.at(e->mom); m.info = info.at(e->mom);
+    m.pivot = piv.at(e->mom); m.sums = sums.at(e->mom); m.part = part.at(e->mom);
+    m.mean = mean_d.at(e->mom); m.C = C ? C_d.at(e->mom) : nullptr; m.Pbar = Pbar ? P_d.at(e->mom) : nullptr;
+    ekf_ens_mom_select_kernel<<<(B * kMomSelLanes + kEkfBlock - 1) / kEkfBlock, kEkfBlock, 0, e->stream>>>(m);
+    if (int rc = ekf_launched("ekf_ens_mom_select_kernel")) return rc;
+    ekf_ens_mom_pivot_kernel<<<1, kEkfBlock, 0, e->stream>>>(m);
+    if (int rc = ekf_launched("ekf_ens_mom_pivot_kernel")) return rc;
+    const int ldl = (Dp & 16) ? Dp : Dp + 16;
+    const int sub = D + 1 <= 320 ? kMomSubMax : 4;
+    const size_t lds_bytes = sizeof(double) * ((size_t) sub * ldl + Dp);  // at most 45 568 bytes (D = 319: 16 rows of 336), 42 112 at D = 1027
+    for (int at = bp_lo; at < nbp; at += bp_chunk) {
+        m.first = at;
+        m.count = std::min(bp_chunk, nbp - at);
+        const dim3 grid(T, (m.count + kMomGroup - 1) / kMomGroup);  // ((256 / SUB) NP columns cover d_ext's D + 1; NP x DEPTH about 32 registers)
+        if (D + 1 <= 128) ekf_ens_mom_gram_kernel<8, 4, 16><<<grid, kEkfBlock, lds_bytes, e->stream>>>(m);
+        else if (D + 1 <= 320) ekf_ens_mom_gram_kernel<20, 2, 16><<<grid, kEkfBlock, lds_bytes, e->stream>>>(m);
+        else ekf_ens_mom_gram_kernel<17, 2, 4><<<grid, kEkfBlock, lds_bytes, e->stream>>>(m);
+        if (int rc = ekf_launched("ekf_ens_mom_gram_kernel")) return rc;
+        ekf_ens_mom_reduce_kernel<<<m.count, kEkfBlock, 0, e->stream>>>(m);
+        if (int rc = ekf_launched("ekf_ens_mom_reduce_kernel")) return rc;
+    }
+    const int outs = D + (C ? D * (D + 1) / 2 : 0);
+    ekf_ens_mom_finish_kernel<<<(outs + kEkfBlock - 1) / kEkfBlock, kEkfBlock, 0, e->stream>>>(m);
+    if (int rc = ekf_launched("ekf_ens_mom_finish_kernel")) return rc;
+    for (int at = 0; Pbar && at < nrb; at += rb_chunk) {
+        m.first = at;
+        m.count = std::min(rb_chunk, nrb - at);
+        ekf_ens_mom_pbar_kernel<<<dim3(m.count, T), kEkfBlock, 0, e->stream>>>(m);
+        if (int rc = ekf_launched("ekf_ens_mom_pbar_kernel")) return rc;
+        const int entries = std::min(m.count * rows, D - at * rows) * D;
+        ekf_ens_mom_pbar_finish_kernel<<<(entries + kEkfBlock - 1) / kEkfBlock, kEkfBlock, 0, e->stream>>>(m);
+        if (int rc = ekf_launched("ekf_ens_mom_pbar_finish_kernel")) return rc;
+    }
+    std::vector<char> h(up);
+    HIP_TRY(hipMemcpyAsync(h.data(), e->mom.p, up, hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    const int32_t *hi = reinterpret_cast<const int32_t *>(h.data() + info.off);
+    memcpy(mean, h.data() + mean_d.off, sizeof(double) * (size_t) D);
+    if (C) memcpy(C, h.data() + C_d.off, sizeof(double) * DD);
+    if (Pbar) memcpy(Pbar, h.data() + P_d.off, sizeof(double) * DD);
+    if (pivot) *pivot = hi[0];
+    if (counted) *counted = hi[1];
+    if (left_out) *left_out = B - hi[1];
+    return 0;
+}
+
 int ens_member(slamgpu_ekf_ens *e, int32_t b) {
     if (b < 0 || b >= e->B) return fail(SLAMGPU_ERR_INVALID, "member %d outside [0, %d)", b, e->B);
     return 0;
@@ -953,6 +1330,12 @@ int slamgpu_ens_consistency(slamgpu_ekf_ens *e, double *out) {
     HIP_TRY(hipStreamSynchronize(e->stream));
     HIP_TRY(hipMemcpy(out, e->acc, sizeof(double) * 6 * (size_t) e->B, hipMemcpyDeviceToHost));
     return 0;
+}
+
+int slamgpu_ens_moments(slamgpu_ekf_ens *e, int32_t D, uint32_t exclude_status, double *mean, double *C, double *Pbar, int32_t *counted,
+                        int32_t *left_out, int32_t *pivot) {
+    if (int rc = ens_check(e)) return rc;
+    return ens_moments(e, D, exclude_status, mean, C, Pbar, counted, left_out, pivot);
 }
 
 int slamgpu_ens_consistency_reset(slamgpu_ekf_ens *e) {

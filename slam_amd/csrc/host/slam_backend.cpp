@@ -131,6 +131,7 @@ static void usage(const char *a0) {
     printf("                        landmark-landmark |correlation|.  -JOINT_OUT path: D, x and the D rows of P as text (%%.17g).  Not with -gpus k > 1 or the EKF\n");
     printf("    -ekf host|device    -method EKF1: where the filter runs.  host (default): float32 loops on the CPU.  device: x and the dense P resident on\n");
     printf("                        the GPU (slamgpu_ekf_sim), same output; refused with a FastSLAM method, and fails without a GPU (no CPU fallback)\n");
+    printf("    -RUNS_MOMENTS 1 [-RUNS_MOMENTS_OUT file]  with -runs B: at the end one line that sets the members' sample covariance C against the mean Pbar of their own P (slamgpu_ens_moments): tr C / tr Pbar of the position, of the heading and per feature, the largest |correlation| of each, the bias of the mean; D = 3 with the gates, the whole state with the known association; file: D, mean, the D rows of C, the D rows of Pbar as text (%%.17g)\n");
     printf("    -RUNS_BATCH K [-RUNS_TRACE file]  with -runs B: K (1 .. 4096; default 64 up to B = 768, 1 beyond) control steps per launch, the same figures for every K; file: one line per control step with the NEES over the members\n");
     printf("    -runs B [-RUNS_SEED s]  with -method EKF1 -ekf device: B (1 .. 65535) noise realisations of the run as one ensemble of device filters, Monte Carlo NEES at the end; not with -plot\n");
     printf("    -path none|smoothed smoothed: record the path posterior (one record per observation step, -PATH_RECORDS n of them kept, default 4096)\n");
@@ -334,12 +335,73 @@ static int g_runs = 0;             // -runs B: B noise realisations at once (sla
 static uint64_t g_runs_seed = 0;   // -RUNS_SEED s: the Philox key of their draws (default: SWITCH_SEED_RANDOM)
 static int g_runs_batch = 0;       // -RUNS_BATCH K: control steps per launch (slamgpu_ens_run_noise); 1: a slamgpu_ens_sim_noise per step; 0: by B (below)
 static std::string g_runs_trace;   // -RUNS_TRACE file: the per-step NEES over the members (slamgpu_ens_trace_*)
+static bool g_runs_moments = false;  // -RUNS_MOMENTS 1: the members' sample covariance against the mean of their P at the end (slamgpu_ens_moments)
+static std::string g_runs_moments_out;  // -RUNS_MOMENTS_OUT file: mean, C and Pbar as text
 
 // -method EKF1 -ekf device -runs B.  The true path does not depend on the noise (Simulator::control moves xTrue with the true
 // controls and only then perturbs the measured ones; Simulator::observe picks the visible landmarks from xTrue), so the host
 // simulator runs ONCE with its own control and sensor noise off and every control step is one slamgpu_ens_sim_noise: each member
 // draws its own noise on the device and the consistency accumulators take xTrue as the truth.  With -RUNS_BATCH K > 1 the simulator runs
 // K control steps ahead, fills a tape and the ensemble takes it in one slamgpu_ens_run_noise (bit for bit the K single calls)
+// -RUNS_MOMENTS: the figures of slam_amd.moments_summary, one line; D = 3 with the gates (the feature order is each member's own), the
+// members' common dimension with the known association, where `order` says which landmark feature f is.  A member that ran out of
+// capacity has parted from that order: the landmark bias is left out then
+static int print_ens_moments(slamgpu_ekf_ens *ens, const Simulator &sim, int D, const std::vector<int32_t> &order, int n_cap) {
+    std::vector<double> mean((size_t) D), C((size_t) D * D), Pb((size_t) D * D);
+    int32_t counted = 0, left_out = 0, pivot = -1;
+    if (slamgpu_ens_moments(ens, D, 0, mean.data(), C.data(), Pb.data(), &counted, &left_out, &pivot) != 0) {
+        fprintf(stderr, "slamgpu: %s\n", slamgpu_last_error());
+        return EXIT_FAILURE;
+    }
+    auto at = [&](const std::vector<double> &M, int a, int b) { return M[(size_t) a * D + b]; };
+    auto max_corr = [&](const std::vector<double> &M) {
+        double m = D < 2 ? NAN : 0.0;
+        for (int a = 0; a < D; a++)
+            if (!(at(M, a, a) > 0.0)) return (double) NAN;
+        for (int a = 0; a < D; a++)
+            for (int b = 0; b < a; b++) m = std::max(m, std::fabs(at(M, a, b) / std::sqrt(at(M, a, a) * at(M, b, b))));
+        return m;
+    };
+    const int nf = (D - 3) / 2;
+    double fsum = 0.0, fmin = INFINITY, fmax = -INFINITY;
+    for (int f = 0; f < nf; f++) {
+        const int a = 3 + 2 * f;
+        const double r = (at(C, a, a) + at(C, a + 1, a + 1)) / (at(Pb, a, a) + at(Pb, a + 1, a + 1));
+        fsum += r;
+        fmin = std::min(fmin, r);
+        fmax = std::max(fmax, r);
+    }
+    const double two_pi = 6.283185307179586476925286766559;
+    printf("ensemble moments: D %d, members counted %d, left out %d; tr C / tr Pbar position %.6f, heading %.6f, per feature mean %.6f smallest %.6f largest %.6f; "
+           "largest |correlation| of C %.6f, of Pbar %.6f; bias of the mean: position %.6f m, heading %.6f rad",
+           D, counted, left_out, (at(C, 0, 0) + at(C, 1, 1)) / (at(Pb, 0, 0) + at(Pb, 1, 1)), at(C, 2, 2) / at(Pb, 2, 2), nf ? fsum / nf : NAN, nf ? fmin : NAN,
+           nf ? fmax : NAN, max_corr(C), max_corr(Pb), std::hypot(mean[0] - sim.xTrue[0], mean[1] - sim.xTrue[1]),
+           std::remainder(mean[2] - (double) sim.xTrue[2], two_pi));
+    if (D == 3) printf(", landmarks: not summarised (D = 3)\n");
+    else if (n_cap > 0 || (int) order.size() < nf) printf(", landmarks: left out (%d members ran out of capacity)\n", n_cap);
+    else {
+        double dsum = 0.0;
+        for (int f = 0; f < nf; f++) {
+            const size_t id = (size_t) order[(size_t) f];
+            dsum += std::hypot(mean[3 + 2 * (size_t) f] - sim.map.lm[id], mean[4 + 2 * (size_t) f] - sim.map.lm[(size_t) sim.map.nlm + id]);
+        }
+        printf(", mean landmark distance %.6f m\n", nf ? dsum / nf : NAN);
+    }
+    if (!g_runs_moments_out.empty()) {
+        FILE *f = fopen(g_runs_moments_out.c_str(), "w");
+        if (!f) {
+            fprintf(stderr, "-RUNS_MOMENTS_OUT %s: cannot write\n", g_runs_moments_out.c_str());
+            return EXIT_FAILURE;
+        }
+        fprintf(f, "%d\n", D);
+        for (int a = 0; a < D; a++) fprintf(f, "%.17g%c", mean[(size_t) a], a + 1 < D ? ' ' : '\n');
+        for (const std::vector<double> *M : {&C, &Pb})
+            for (int r = 0; r < D; r++)
+                for (int q = 0; q < D; q++) fprintf(f, "%.17g%c", at(*M, r, q), q + 1 < D ? ' ' : '\n');
+        fclose(f);
+    }
+    return 0;
+}
 constexpr int kEnsHeadroom = 8;
 // without -RUNS_BATCH: 64 steps per launch while every member's workgroup is resident at once (the K-step kernel's registers allow three
 // workgroups on each of the 256 CUs), one step per launch beyond: measured, profiles/ekf_ensemble_run.txt (K = 64 is within 2 % of K = 256
@@ -393,6 +455,16 @@ static int run_ekf_ensemble(Simulator &sim, long maxsteps) {
     std::vector<int32_t> tid;
     std::vector<double> rec;
     std::vector<uint32_t> tag;
+    // -RUNS_MOMENTS: the ids in the order the run named them (known association: id order[f] is feature f of every member)
+    std::vector<int32_t> order;
+    std::vector<char> named((size_t) std::max(sim.map.nlm, 0), 0);
+    auto name_new = [&]() {
+        for (int32_t id : sim.vis)
+            if (id >= 0 && id < (int32_t) named.size() && !named[(size_t) id]) {
+                named[(size_t) id] = 1;
+                order.push_back(id);
+            }
+    };
     // the records the last call appended (at most the ring's capacity: nothing is lost between two visits), one line each
     int64_t drained = 0;
     auto drain = [&]() {
@@ -420,6 +492,7 @@ static int run_ekf_ensemble(Simulator &sim, long maxsteps) {
             if (r == 1) {
                 sim.observe();
                 nobs++;
+                name_new();
             }
             rc = slamgpu_ens_sim_noise(ens, sim.Vtrue, sim.Gtrue, sim.xTrue[2], sim.z.data(), sim.vis.data(), r == 1 ? (int32_t) sim.vis.size() : 0,
                                            (uint32_t) iter, sim.Q, sim.Qe, sim.Re, sim.R, sim.dt, r == 1, sim.xTrue, noise);
@@ -444,6 +517,7 @@ static int run_ekf_ensemble(Simulator &sim, long maxsteps) {
                 if (r == 1) {
                     sim.observe();
                     nobs++;
+                    name_new();
                     t.nz = (int32_t) sim.vis.size();
                     tz.insert(tz.end(), sim.z.begin(), sim.z.begin() + 2 * sim.vis.size());
                     tid.insert(tid.end(), sim.vis.begin(), sim.vis.end());
@@ -498,8 +572,10 @@ static int run_ekf_ensemble(Simulator &sim, long maxsteps) {
     printf("member-steps not counted (pose covariance not positive definite, or a non-finite state): %.0f\n", skipped);
     printf("per-member mean NEES: smallest %.4f, largest %.4f\n", m_min, m_max);
     printf("members with a skipped batch update (not positive definite): %d; members that ran out of capacity: %d\n", n_notpd, n_cap);
+    int ret = 0;
+    if (g_runs_moments) ret = print_ens_moments(ens, sim, c.SWITCH_ASSOCIATION_KNOWN ? *std::min_element(dims.begin(), dims.end()) : 3, order, n_cap);
     slamgpu_ens_destroy(ens);
-    return 0;
+    return ret;
 }
 static std::string g_joint_out;
 static void print_joint(slamgpu_ctx *ctx, const std::vector<double> &sum, int slots) {
@@ -984,6 +1060,20 @@ int main(int argc, char **argv) {
         }
         if (!g_runs_trace.empty() && !g_runs) {
             fprintf(stderr, "-RUNS_TRACE file: with -runs B\n");
+            return EXIT_FAILURE;
+        }
+        // ... and -RUNS_MOMENTS 1 [-RUNS_MOMENTS_OUT file]: the ensemble's moments at the end; refused from the arguments alone
+        const std::string rm = sim.conf.s("RUNS_MOMENTS");
+        g_runs_moments_out = sim.conf.s("RUNS_MOMENTS_OUT");
+        sim.conf.kv.erase("RUNS_MOMENTS");
+        sim.conf.kv.erase("RUNS_MOMENTS_OUT");
+        g_runs_moments = !rm.empty() && atol(rm.c_str()) != 0;
+        if (!rm.empty() && !g_runs) {
+            fprintf(stderr, "-RUNS_MOMENTS 1: with -runs B\n");
+            return EXIT_FAILURE;
+        }
+        if (!g_runs_moments_out.empty() && !g_runs_moments) {
+            fprintf(stderr, "-RUNS_MOMENTS_OUT file: with -runs B -RUNS_MOMENTS 1\n");
             return EXIT_FAILURE;
         }
         const std::string mr = sim.conf.s("MAP_MERGE_RADIUS"), mc = sim.conf.s("MAP_MERGE_COHOLD");

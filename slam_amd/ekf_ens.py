@@ -59,6 +59,49 @@ def trace_summary(records):
     return out
 
 
+def _max_corr(M):
+    """the largest |correlation| between two different components of a covariance (NaN: fewer than two, or a variance that is not
+    positive)"""
+    d = np.diag(M)
+    if M.shape[0] < 2 or not (d > 0).all():
+        return float("nan")
+    r = np.abs(M / np.sqrt(np.outer(d, d)))
+    np.fill_diagonal(r, 0.0)
+    return float(r.max())
+
+
+def moments_summary(mean, C, Pbar, truth_pose=None, truth_landmarks=None):
+    """What EkfEnsemble.moments says about the filter's consistency, as a dict.  C is the spread the members have, Pbar the spread
+    their filters claim: a consistent filter has ratios near 1 (below 1: pessimistic, above: optimistic) and a bias whose square is
+    far below Pbar.
+      pos_ratio      tr C[0:2, 0:2] / tr Pbar[0:2, 0:2]        heading_ratio  C[2, 2] / Pbar[2, 2]
+      feature_ratio_mean / _min / _max   tr C_ff / tr Pbar_ff over the features (NaN without features)
+      max_corr_C, max_corr_Pbar          the largest |correlation| between two different components
+    and with truth_pose (x, y, theta): bias_pos (m), bias_heading (rad, the short way round); with truth_landmarks [nf, 2] in the
+    features' order: bias_landmarks, the mean distance of the mean's features from them"""
+    mean, C, Pbar = np.asarray(mean, np.float64), np.asarray(C, np.float64), np.asarray(Pbar, np.float64)
+    D = mean.shape[0]
+    nf = (D - 3) // 2
+    with np.errstate(divide="ignore", invalid="ignore"):
+        out = {"pos_ratio": float((C[0, 0] + C[1, 1]) / (Pbar[0, 0] + Pbar[1, 1])), "heading_ratio": float(C[2, 2] / Pbar[2, 2])}
+        i = 3 + 2 * np.arange(nf)
+        fr = (C[i, i] + C[i + 1, i + 1]) / (Pbar[i, i] + Pbar[i + 1, i + 1])
+    out["feature_ratio_mean"] = float(fr.mean()) if nf else float("nan")
+    out["feature_ratio_min"] = float(fr.min()) if nf else float("nan")
+    out["feature_ratio_max"] = float(fr.max()) if nf else float("nan")
+    out["max_corr_C"], out["max_corr_Pbar"] = _max_corr(C), _max_corr(Pbar)
+    if truth_pose is not None:
+        t = np.asarray(truth_pose, np.float64)
+        out["bias_pos"] = float(np.hypot(mean[0] - t[0], mean[1] - t[1]))
+        out["bias_heading"] = float(np.remainder(mean[2] - t[2] + np.pi, 2 * np.pi) - np.pi)
+    if truth_landmarks is not None:
+        t = np.asarray(truth_landmarks, np.float64).reshape(-1, 2)
+        if t.shape[0] != nf:
+            raise ValueError("%d true landmarks for %d features" % (t.shape[0], nf))
+        out["bias_landmarks"] = float(np.hypot(*(mean[3:].reshape(-1, 2) - t).T).mean()) if nf else float("nan")
+    return out
+
+
 class EkfEnsConfig(C.Structure):  # slamgpu_ekf_ens_config
     _fields_ = [("struct_size", C.c_uint32), ("device", C.c_int32), ("members", C.c_int32), ("max_landmarks", C.c_int32),
                 ("use_heading", C.c_int32), ("batch_update", C.c_int32), ("association_known", C.c_int32), ("wheel_base", C.c_float),
@@ -94,6 +137,8 @@ def _lib():
             L.slamgpu_ens_trace_enable.argtypes = [vp, i32]
             L.slamgpu_ens_trace_info.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(i32)]
             L.slamgpu_ens_trace_fetch.argtypes = [vp, C.c_int64, i32, vp, vp]
+        if hasattr(L, "slamgpu_ens_moments"):  # (likewise)
+            L.slamgpu_ens_moments.argtypes = [vp, i32, u32, vp, vp, vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
         _bound = True
     return L
 
@@ -235,3 +280,18 @@ class EkfEnsemble:
         step = np.zeros(count, np.uint32) if step is None else step
         _chk(self.L.slamgpu_ens_trace_fetch(self.h, int(first), int(count), _ptr(out), _ptr(step)))
         return out, step
+
+    def moments(self, D=None, exclude_status=0, want_C=True, want_Pbar=True):
+        """The sample mean[D] and (population) covariance C[D, D] of the members' leading D state components, and the mean Pbar[D, D] of
+        their own P, over the members whose dimension reaches D, whose status has none of the bits of exclude_status and whose state is
+        finite: a dict of mean, C, Pbar (None where not wanted), counted, left_out, pivot.  D defaults to the smallest member's
+        dimension.  (slamgpu_ens_moments; moments_summary turns it into ratios)"""
+        D = int(self.dims().min()) if D is None else int(D)
+        n = max(D, 0)
+        mean = np.zeros(n)
+        Cm = np.zeros((n, n)) if want_C else None
+        Pb = np.zeros((n, n)) if want_Pbar else None
+        counted, left_out, pivot = C.c_int32(), C.c_int32(), C.c_int32()
+        _chk(self.L.slamgpu_ens_moments(self.h, D, int(exclude_status), _ptr(mean), _ptr(Cm), _ptr(Pb), C.byref(counted), C.byref(left_out),
+                                        C.byref(pivot)))
+        return {"mean": mean, "C": Cm, "Pbar": Pb, "counted": counted.value, "left_out": left_out.value, "pivot": pivot.value}
