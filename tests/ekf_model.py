@@ -92,15 +92,18 @@ class EkfModel:
         cols = np.stack([0 * f, 0 * f + 1, 0 * f + 2, f, f + 1], axis=1)
         return zp, H, cols
 
-    def associate(self, z, Re):
-        """EKFSLAM::dataAssociate (ekfslam.cpp:151-189): labels[nz]"""
+    def associate(self, z, Re, want_margin=False):
+        """EKFSLAM::dataAssociate (ekfslam.cpp:151-189): labels[nz]; with want_margin also margin[nz], how close each decision was: the
+        smallest of |nis_j - gate_reject| and |nis_j - gate_augment| over all features and, where two or more features pass the reject
+        gate, the gap between the two smallest nd_j among them (inf without features: nothing is compared)"""
         z = np.asarray(z, self.t).reshape(-1, 2)
         Re = self._m(Re)
         lab = np.full(z.shape[0], ASSOC_DISCARD, np.int32)
+        margin = np.full(z.shape[0], np.inf)
         nf = self.nf
         if nf == 0:
             lab[:] = ASSOC_NEW
-            return lab
+            return (lab, margin) if want_margin else lab
         zp, H, cols = self._model(np.arange(nf))
         M = self.P[cols[:, :, None], cols[:, None, :]]
         S = H @ M @ H.transpose(0, 2, 1) + Re
@@ -118,7 +121,13 @@ class EkfModel:
                 elif nis[j] < outer:
                     outer = nis[j]
             lab[i] = jbest if jbest >= 0 else (ASSOC_NEW if outer > self.gate_augment else ASSOC_DISCARD)
-        return lab
+            if want_margin:
+                n64 = nis.astype(np.float64)
+                margin[i] = min(np.abs(n64 - self.gate_reject).min(), np.abs(n64 - self.gate_augment).min())
+                gated = np.sort(nd.astype(np.float64)[n64 < self.gate_reject])
+                if gated.shape[0] > 1:
+                    margin[i] = min(margin[i], gated[1] - gated[0])
+        return (lab, margin) if want_margin else lab
 
     def _batch(self, zf, idf, R):
         t = self.t

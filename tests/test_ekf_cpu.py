@@ -83,6 +83,42 @@ def test_host_filter_with_explicit_inputs_is_the_host_filter(mapname, seed):
     sim.close()
 
 
+@pytest.mark.parametrize("nf", [65, 257, 512, 600])
+def test_scale_packet_is_decided_clearly_by_the_float64_model(nf):
+    """The packet of 64 readings tests/test_gpu_ekf_scale.py sends through the gates of large maps, judged by the float64 model alone
+    with EkfModel.associate's margin: at most 2 decisions within 1e-3 of a gate or of a rival, at least 40 matches and 6 new landmarks,
+    and at 600 features at least 5 winners that are not the feature the reading came from (test_gpu_ekf_scale.caps).  The model's float32
+    evaluation labels every clear decision alike, so a correct float32 kernel has room"""
+    import ekf_model
+    from test_gpu_ekf_scale import GATES, RE, caps, study
+    s = study(nf)
+    foreign = caps(s)
+    lab, margin, clear = s["lab"], s["margin"], s["clear"]
+    print("EKF scale packet nf %d: unclear %d, smallest margin %.1e, match / new / discard %d / %d / %d, foreign winners %d" %
+          (nf, (~clear).sum(), margin.min(), (lab >= 0).sum(), (lab == -1).sum(), (lab == -2).sum(), foreign))
+    assert lab.shape == (64,) and np.isfinite(margin).all() and (margin >= 0).all()
+    m32 = ekf_model.EkfModel(dtype=f32, **GATES)
+    m32.upload(s["x0"], s["P0"])
+    assert np.array_equal(m32.associate(s["z"], RE)[clear], lab[clear])
+    # the margin is what it says: each term recomputed for one reading, and the labels do not depend on asking for it
+    mdl = ekf_model.EkfModel(**GATES)
+    mdl.upload(s["x0"], s["P0"])
+    assert np.array_equal(mdl.associate(s["z"], RE), lab)
+    i = int(np.argmin(margin))
+    zp, H, cols = mdl._model(np.arange(nf))
+    S = H @ mdl.P[cols[:, :, None], cols[:, None, :]] @ H.transpose(0, 2, 1) + RE.astype(np.float64)
+    v = s["z"][i].astype(np.float64) - zp
+    v[:, 1] = (v[:, 1] + np.pi) % (2 * np.pi) - np.pi
+    nis = np.array([v[j] @ np.linalg.solve(S[j], v[j]) for j in range(nf)])
+    nd = np.sort((nis + np.log(np.linalg.det(S)))[nis < 4.0])
+    want = min(np.abs(nis - 4.0).min(), np.abs(nis - 25.0).min(), nd[1] - nd[0] if nd.shape[0] > 1 else np.inf)
+    assert abs(margin[i] - want) <= 1e-9 * max(1.0, want), (margin[i], want)
+    # no features: everything is new and nothing was compared
+    empty = ekf_model.EkfModel(**GATES)
+    l0, m0 = empty.associate(s["z"][:3], RE, want_margin=True)
+    assert (l0 == -1).all() and np.isinf(m0).all()
+
+
 EKF_SYMBOLS = ["slamgpu_ekf_create", "slamgpu_ekf_destroy", "slamgpu_ekf_sim", "slamgpu_ekf_predict", "slamgpu_ekf_observe_heading",
                "slamgpu_ekf_associate", "slamgpu_ekf_update", "slamgpu_ekf_augment", "slamgpu_ekf_dim", "slamgpu_ekf_pose", "slamgpu_ekf_state",
                "slamgpu_ekf_block", "slamgpu_ekf_upload", "slamgpu_ekf_status", "slamgpu_ekf_sync"]

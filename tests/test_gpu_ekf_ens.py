@@ -157,12 +157,15 @@ EDGE_CASES = [((0, 14, 64), 3, 1), ((1, 15, 63), 1, 5), ((30, 31, 62), 35, 0), (
               ((0, 1, 30), 0, 1)]
 
 
-@pytest.mark.parametrize("nfs,m,nnew", EDGE_CASES)
-def test_tiles_and_chunks(nfs, m, nnew):
+HOST_DIM_MOST = 523  # the host's heading update is two naive dense D^3 products: beyond this dimension the float32 model is the yardstick
+
+
+def tiles_and_chunks(nfs, m, nnew):
     """Known association, heading observed, three members of three sizes in one launch.  The ids are shared: the m observed ids are drawn
     from the largest member's features (with repeats once m exceeds them), a member observes those it holds and ignores the rest (the
     header's rule), and the new ids are new to everybody.  Per member the yardstick is the host filter on that member's own
-    observations (its single batch, m <= 64) or the float32 model with the device's chunks (m > 64)."""
+    observations (its single batch, m <= 64, and a dimension of at most HOST_DIM_MOST before the step) or the float32 model with the
+    device's chunks.  Shared with tests/test_gpu_ekf_scale.py"""
     import slam_amd
     import ekf_model
     sim, hekf, nz = known_host()
@@ -205,7 +208,7 @@ def test_tiles_and_chunks(nfs, m, nnew):
         mdl.sim(*args)
         D = 3 + 2 * (nf + nnew)
         assert mdl.dim == D == dims[b], (b, nf)
-        if mo <= 64:
+        if mo <= 64 and x0.shape[0] <= HOST_DIM_MOST:
             hekf.upload(x0, P0)
             hekf.sim_step(*args)
             xr, Pr = hekf.state(cap=D)
@@ -214,6 +217,10 @@ def test_tiles_and_chunks(nfs, m, nnew):
             m32.upload(x0, P0)
             m32.sim(*args)
             xr, Pr = m32.x, m32.P
+            if mo <= 64:  # (the host's single batch exists and is merely slow, 1.5 s at dim 1017: its error beside the yardstick's, printed only)
+                hekf.upload(x0, P0)
+                hekf.sim_step(*args)
+                print("ENS tiles nf %d m %d (+%d new): the host filter's error x %.3e P %.3e" % ((nf, mo, nnew) + errors(*hekf.state(cap=D), mdl.x, mdl.P)))
         xd, Pd = ens.state(b)
         assert xd.shape[0] == D and symmetric(Pd), (b, nf)
         # the padding: beyond dim the sentinel, beyond the capacity (never uploaded) the zeros the slab was made with
@@ -227,6 +234,11 @@ def test_tiles_and_chunks(nfs, m, nnew):
               (nf, mo, nnew, dx, dP, rx, rP, ratio(dx, rx), ratio(dP, rP)))
         assert within(dx, rx) and within(dP, rP), (b, nf, dx, rx, dP, rP)
     ens.close()
+
+
+@pytest.mark.parametrize("nfs,m,nnew", EDGE_CASES)
+def test_tiles_and_chunks(nfs, m, nnew):
+    tiles_and_chunks(nfs, m, nnew)
 
 
 def test_a_neighbours_slab_is_untouched():
