@@ -760,7 +760,8 @@ int do_update_particle(slamgpu_ctx *c, const float *z, int32_t nz, const float R
 
     const bool need_normals = c->cfg.method == SLAMGPU_FASTSLAM2 && (m > 0 || n > 0);
     if (tape && need_normals && !normals) return fail(SLAMGPU_ERR_INVALID, "TAPE mode needs normals[3N] and strata[N]");
-    // the labels resolved into what the launch reads (everything that can fail on the way there comes BEFORE the host's bookkeeping moves)
+    // the labels resolved into what the launch reads.  (The row book has not moved yet, but the association's own state has -- pp_steps, the
+    // dead list, the partial and retired flags: a call that fails from here on leaves those as this step set them)
     HIP_TRY(hipMemcpyAsync(first_dev, up.data(), sizeof(int32_t) * up.size(), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));  // (pageable source)
     {
@@ -777,41 +778,21 @@ int do_update_particle(slamgpu_ctx *c, const float *z, int32_t nz, const float R
     c->as.pp_lab_nz = nz;
     // genealogy bookkeeping, as do_update's: every packet entry is written by every particle (updated or copied forward) and moves
     // to the row this update opens
-    int e_new = -1;
-    std::vector<int32_t> rows_of((size_t) m), left;
-    if (m + n > 0) {
-        e_new = c->free_rows.back();
-        c->free_rows.pop_back();
-    }
-    auto leave_row = [&](int l) {
-        const int r = c->erow[(size_t) l];
-        if (--c->refcnt[(size_t) r] == 0) {
-            rows_remove_live(c, r);
-            left.push_back(r);
-        }
-        c->erow[(size_t) l] = e_new;
-        c->refcnt[(size_t) e_new]++;
-        c->as.box_dirty[(size_t) l] = 1;
-    };
+    RowBook &rows = c->rows;
+    std::vector<int32_t> rows_of((size_t) m);
+    const int e_new = rows.open(m + n > 0);
     for (int k = 0; k < m; k++) {
-        const int l = touched[(size_t) k].second, r = c->erow[(size_t) l];
-        rows_of[(size_t) k] = r | (c->live_flag[(size_t) l] ? kRowLiveBit : 0) | (r == c->fresh_row ? kRowFreshBit : 0);
-        c->live_flag[(size_t) l] ^= 1;
-        c->seen_step[(size_t) l] = c->obs_step;
-        leave_row(l);
+        const int l = touched[(size_t) k].second;
+        rows_of[(size_t) k] = rows.move(l, true);
+        rows.mark_seen(l, c->obs_step);
+        c->as.box_dirty[(size_t) l] = 1;
     }
     for (int q = 0; q < n; q++) {
         const int l = idn[(size_t) q];
-        if (l < nf0) {
-            leave_row(l);
-        } else {
-            c->erow[(size_t) l] = e_new;
-            c->refcnt[(size_t) e_new]++;
-            c->as.box_dirty[(size_t) l] = 1;
-        }
-        c->live_flag[(size_t) l] = 0;  // a new landmark's first records go to buffer 0
+        rows.place_new(l, l < nf0);  // (l < nf0: a dead slot opened again leaves the row it was in)
+        c->as.box_dirty[(size_t) l] = 1;
     }
-    const int n_rows = (int) c->live_rows.size();
+    const int n_rows = (int) rows.in_use().size();
     c->tables_dirty = true;
 
     UpdateArgs U{};
@@ -821,34 +802,22 @@ int do_update_particle(slamgpu_ctx *c, const float *z, int32_t nz, const float R
     U.nf = nf0;
     U.e_new = e_new;
     U.n_rows = n_rows;
-    {
-        int top = e_new;
-        for (int r : c->live_rows) top = std::max(top, r);
-        U.live_chunks = (top >> 2) + 1;
-    }
+    U.live_chunks = rows.live_chunks(e_new);
     U.all_fresh = 0;
-    c->fresh_row = e_new;
+    rows.set_fresh(e_new);
     memcpy(U.R, R, sizeof U.R);
     {
         BigPacket bp;
         if (int rc = bp.begin(c, m, n, nf0, n_rows, e_new)) return rc;
-        int32_t *hidf = reinterpret_cast<int32_t *>(bp.host + 1);
-        float *hzf = reinterpret_cast<float *>(hidf + m);
-        float *hzn = hzf + 2 * m;
-        for (int k = 0; k < m; k++) hidf[k] = touched[(size_t) k].second;
-        memset(hzf, 0, sizeof(float) * 2 * ((size_t) m + n));  // (the observations are per particle: PerParticle::z)
-        int32_t *hrow = reinterpret_cast<int32_t *>(hzn + 2 * n);
-        if (m) memcpy(hrow, rows_of.data(), sizeof(int32_t) * (size_t) m);
-        if (n_rows) memcpy(hrow + m, c->live_rows.data(), sizeof(int32_t) * (size_t) n_rows);
-        const size_t used = sizeof(ObsPacket) + sizeof(int32_t) * (size_t) m + sizeof(float) * 2 * ((size_t) m + n) + sizeof(int32_t) * ((size_t) m + n_rows);
-        if (int rc = bp.commit(c, used)) return rc;
+        const BigPacket::Dense d = bp.layout(m, m, n, n_rows);
+        for (int k = 0; k < m; k++) d.idf[k] = touched[(size_t) k].second;
+        memset(d.zf, 0, sizeof(float) * 2 * ((size_t) m + n));  // (zf and zn, one behind the other; the observations are per particle: PerParticle::z)
+        if (m) memcpy(d.row, rows_of.data(), sizeof(int32_t) * (size_t) m);
+        if (n_rows) memcpy(d.rows, rows.in_use().data(), sizeof(int32_t) * (size_t) n_rows);
+        if (int rc = bp.commit(c, d.used)) return rc;
         U.big = reinterpret_cast<const ObsPacket *>(bp.dev);
     }
-    if (e_new >= 0) {
-        if (c->refcnt[(size_t) e_new] > 0) rows_add_live(c, e_new);
-        else c->free_rows.push_back(e_new);
-    }
-    for (int r : left) c->free_rows.push_back(r);
+    rows.close(false);  // (plain rows: the free stack is never sorted again)
 
     PerParticle ppa{c->as.pp_obs_dev, c->as.pp_z_dev, idn_dev, c->as.pp_wf_dev, c->as.pp_any_dev, nz, 0};
     c->as.pp_launch = &ppa;
@@ -1095,9 +1064,9 @@ int pp_push(slamgpu_ctx *c, int census_cap) {
         n_dead += dead[l];
         if (l < nf && partial[l] && !dead[l]) list[n_list++] = l;
     }
-    std::vector<int32_t> rows;
+    std::vector<int32_t> rows;  // (ascending, not in the book's order: PpArgs::rows)
     for (int r = 0; r < cr; r++)
-        if (c->refcnt[(size_t) r] > 0) rows.push_back(r);
+        if (c->rows.count(r) > 0) rows.push_back(r);
     PpState st{};
     st.updated = 0;  // (flushed above)
     st.step = c->obs_step;
@@ -1115,9 +1084,10 @@ int pp_push(slamgpu_ctx *c, int census_cap) {
     HIP_TRY(hipMemcpy(c->as.pp_words_dev, words.data(), sizeof(int32_t) * words.size(), hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(c->as.pp_st_dev, &st, sizeof st, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(c->fe.book_dev, &hb, sizeof hb, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(c->erow_dev, c->erow.data(), sizeof(int32_t) * cnz, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(c->live_dev, c->live_flag.data(), sizeof(int32_t) * cnz, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(c->fe.refcnt_dev, c->refcnt.data(), sizeof(int32_t) * (size_t) cr, hipMemcpyHostToDevice));
+    const RowBook::Tables t = c->rows.tables();
+    HIP_TRY(hipMemcpy(c->erow_dev, t.row, sizeof(int32_t) * cnz, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(c->live_dev, t.live, sizeof(int32_t) * cnz, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(c->fe.refcnt_dev, t.count, sizeof(int32_t) * (size_t) cr, hipMemcpyHostToDevice));
     if (!rows.empty()) HIP_TRY(hipMemcpy(c->rows_dev, rows.data(), sizeof(int32_t) * rows.size(), hipMemcpyHostToDevice));
     if (c->as.retired_stale)
         if (int rc = retired_upload(c)) return rc;
@@ -1142,24 +1112,19 @@ int pp_pull(slamgpu_ctx *c) {
     HIP_TRY(hipStreamSynchronize(c->stream));
     const int cn = c->B.cap_nf, cr = c->B.cap_rows;
     const size_t cnz = (size_t) cn;
-    std::vector<int32_t> words(2 * cnz), erow(cnz), live(cnz), ref((size_t) cr), mask((cnz + 31) / 32);
+    std::vector<int32_t> words(2 * cnz), row(cnz), live(cnz), ref((size_t) cr), mask((cnz + 31) / 32);
     PpState st{};
     DevBook hb{};
     HIP_TRY(hipMemcpy(words.data(), c->as.pp_words_dev, sizeof(int32_t) * words.size(), hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(&st, c->as.pp_st_dev, sizeof st, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(&hb, c->fe.book_dev, sizeof hb, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(erow.data(), c->erow_dev, sizeof(int32_t) * cnz, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(row.data(), c->erow_dev, sizeof(int32_t) * cnz, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(live.data(), c->live_dev, sizeof(int32_t) * cnz, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(ref.data(), c->fe.refcnt_dev, sizeof(int32_t) * (size_t) cr, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(mask.data(), c->as.retired_dev, sizeof(uint32_t) * mask.size(), hipMemcpyDeviceToHost));
-    if (hb.nf < 0 || hb.nf > cn) return fail(SLAMGPU_ERR_INVALID, "device bookkeeping corrupt: nf = %d", hb.nf);
-    c->nf = hb.nf;
-    std::copy(erow.begin(), erow.end(), c->erow.begin());
-    std::copy(live.begin(), live.end(), c->live_flag.begin());
-    std::copy(ref.begin(), ref.end(), c->refcnt.begin());
-    book_rebuild(c);
-    c->fresh_row = -1;
-    c->as.box_dev_stale = false;  // (book_rebuild has marked every box for a refresh)
+    if (int rc = book_import(c, hb.nf, cn, row.data(), live.data(), ref.data())) return rc;
+    c->rows.set_fresh(-1);
+    c->as.box_dev_stale = false;  // (book_import has marked every box for a refresh)
     c->as.pp_dead_list.clear();
     c->as.n_retired = 0;
     for (int l = 0; l < cn; l++) {

@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "row_bits.h"
+
 namespace slamgpu {
 
 // ---- HBM layout ---------------------------------------------------------------------------------------
@@ -47,11 +49,7 @@ constexpr int kMidLandmarks = 256;  // (round 5) single contexts of up to this m
                                     // landmarks.  A step that does not fit the packet (more than kSmallObs re-observed or new landmarks)
                                     // or the rows moves the context to plain rows for good (slamgpu.cpp: demote_to_plain)
 constexpr int kRowsPerRole = 16;    // genealogy rows composed by one copy role (x 256 particles)
-constexpr int kRowLiveBit = 1 << 30;  // packet row[k]: the landmark's live record buffer rides in bit 30 of its genealogy row
-constexpr int kRowFreshBit = 1 << 29; // packet row[k]: the landmark was written by the PREVIOUS update and nothing has composed its
-                                      // row since (the resample this launch applies excepted): its record sits in the source
-                                      // slot itself, no genealogy lookup needed -- the usual case for a landmark in view
-constexpr int kRowMask = kRowFreshBit - 1;
+// (kRowLiveBit, kRowFreshBit, kRowMask -- the packed row word of a packet's row[k] -- live in row_bits.h, which the host's row book shares)
 constexpr int kPoolBit = (int) 0x80000000;  // genealogy entry: the record lives in the arrival pool (Buffers::poolA/B)
 constexpr int kHistStride = 6;      // doubles per pose-estimate history entry: sum x, sum y, heading, max w, Neff, resampled
 constexpr int kMaxScanBlocks = 8192;

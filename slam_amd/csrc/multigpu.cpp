@@ -373,7 +373,7 @@ int slamgpu_shard_unpack(slamgpu_ctx *c, const float *recv_dev, int32_t n_shards
     if (settle) {
         // the kernel rewrote the whole shard physically and flipped every landmark row; nothing references the pool now
         c->mg.shard_settled = true;
-        for (int j = 0; j < c->nf; j++) c->live_flag[j] ^= 1;
+        c->rows.flip_all(c->nf);
         c->mg.pool_used = 0;
         rows_reset(c, c->nf);  // every landmark of every output particle in its own slot: genealogy row 0
     } else {

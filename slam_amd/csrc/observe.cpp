@@ -4,7 +4,7 @@
 #include "slamgpu_ctx.h"
 
 // ---- genealogy bookkeeping on the device (slamgpu_step_observe) <-> on the host ----
-// The device-driven steps keep erow / live flags / reference counts / nf / fresh row in device memory (observe_book_kernel).
+// The device-driven steps keep the book's tables (rows, live flags, reference counts), nf and the fresh row in device memory (observe_book_kernel).
 // Anything host-side that needs them (a host-made packet, download, flatten, peek, the landmark count) first pulls them back
 // -- one synchronisation -- and the host is authoritative again; the next device-driven step pushes them.
 // (All copies go through one pinned staging buffer.)
@@ -22,15 +22,8 @@ int book_staging(slamgpu_ctx *c) {
     return 0;
 }
 
-// the row lists follow from the reference counts (book_pull)
-void book_rebuild(slamgpu_ctx *c) {
-    std::fill(c->live_pos.begin(), c->live_pos.end(), -1);
-    c->live_rows.clear();
-    c->free_rows.clear();
-    for (int r = c->B.cap_rows - 1; r >= 0; r--)
-        if (c->refcnt[r] == 0) c->free_rows.push_back(r);  // back() = lowest free row
-    for (int r = 0; r < c->B.cap_rows; r++)
-        if (c->refcnt[r] > 0) rows_add_live(c, r);
+// the book is the host's again (book_pull, pp_pull), its row lists rebuilt from the counts that came back
+static void book_returned(slamgpu_ctx *c) {
     c->tables_dirty = true;
     c->fe.book_on_device = false;
     std::fill(c->as.box_dirty.begin(), c->as.box_dirty.end(), 1);  // (which landmarks the device-driven steps wrote is not known here)
@@ -57,10 +50,10 @@ int front_setup(slamgpu_ctx *c) {
     return 0;
 }
 
-// the pinned staging of the plain-row hand-over: the book's header, then erow [cap_nf], live [cap_nf], refcnt [cap_rows]
+// the pinned staging of the plain-row hand-over: the book's header, then rows [cap_nf], live [cap_nf], counts [cap_rows]
 struct BookStage {
     DevBook *hb;
-    int32_t *erow, *live, *ref;
+    int32_t *row, *live, *ref;
 };
 BookStage book_carve(const slamgpu_ctx *c) {
     int32_t *e = c->fe.book_host + sizeof(DevBook) / 4;
@@ -79,6 +72,19 @@ int book_pulled(slamgpu_ctx *c, int32_t status) {
 
 }  // namespace
 
+// the tables that came back from the device into the host's book (the first n_lmk landmark entries), nf with them
+int book_import(slamgpu_ctx *c, int nf, int n_lmk, const int32_t *row, const int32_t *live, const int32_t *ref) {
+    int bad = -1;
+    switch (c->rows.import_tables(nf, n_lmk, row, live, ref, &bad)) {
+    case RowBook::kImportBadCount: return fail(SLAMGPU_ERR_INVALID, "device bookkeeping corrupt: nf = %d", nf);
+    case RowBook::kImportBadRow: return fail(SLAMGPU_ERR_INVALID, "device bookkeeping corrupt: landmark %d in row %d", bad, row[bad]);
+    case RowBook::kImportOk: break;
+    }
+    c->nf = nf;
+    book_returned(c);
+    return 0;
+}
+
 int book_pull(slamgpu_ctx *c) {
     if (c->as.pp_on_device) return pp_pull(c);
     Front &f = c->fe;
@@ -90,40 +96,34 @@ int book_pull(slamgpu_ctx *c) {
         HIP_TRY(hipStreamSynchronize(c->stream));
         const int nf = h->hdr.nf;
         if (nf < 0 || nf > c->B.cap_nf) return fail(SLAMGPU_ERR_INVALID, "device bookkeeping corrupt: nf = %d", nf);
-        std::fill(c->refcnt.begin(), c->refcnt.end(), 0);
+        c->rows.clear_counts();
         int seen = 0;
         for (int t = 0; t < f.map_n; t++) {
             const FrontLm &l = h->lm[t];
             if (l.idf < 0) continue;
             const int r = l.row & kRowMask;
             if (l.idf >= nf || r >= c->B.cap_rows) return fail(SLAMGPU_ERR_INVALID, "device bookkeeping corrupt: landmark %d -> feature %d, row %d", t, l.idf, r);
-            c->erow[l.idf] = r;
-            c->live_flag[l.idf] = (l.row & kRowLiveBit) ? 1 : 0;
-            c->refcnt[r]++;
+            c->rows.set_entry(l.idf, r, (l.row & kRowLiveBit) != 0);
             seen++;
         }
         if (seen != nf) return fail(SLAMGPU_ERR_INVALID, "device bookkeeping corrupt: %d landmarks of the map seen, nf = %d", seen, nf);
         c->nf = nf;
-        c->fresh_row = h->hdr.fresh_row;
-        book_rebuild(c);
+        c->rows.set_fresh(h->hdr.fresh_row);
+        c->rows.rebuild();
+        book_returned(c);
         return book_pulled(c, h->hdr.status);
     }
     const size_t cn = (size_t) c->B.cap_nf, cr = (size_t) c->B.cap_rows;
     const BookStage s = book_carve(c);
     HIP_TRY(hipStreamSynchronize(f.obs_stream));  // (the last front-end kernel writes these tables)
     HIP_TRY(hipMemcpyAsync(s.hb, f.book_dev, sizeof(DevBook), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpyAsync(s.erow, c->erow_dev, 4 * cn, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(s.row, c->erow_dev, 4 * cn, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipMemcpyAsync(s.live, c->live_dev, 4 * cn, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipMemcpyAsync(s.ref, f.refcnt_dev, 4 * cr, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     const int nf = s.hb->nf;
-    if (nf < 0 || nf > c->B.cap_nf) return fail(SLAMGPU_ERR_INVALID, "device bookkeeping corrupt: nf = %d", nf);
-    std::copy(s.erow, s.erow + nf, c->erow.begin());
-    std::copy(s.live, s.live + nf, c->live_flag.begin());
-    std::copy(s.ref, s.ref + cr, c->refcnt.begin());
-    c->nf = nf;
-    c->fresh_row = s.hb->fresh_row;
-    book_rebuild(c);
+    if (int rc = book_import(c, nf, nf, s.row, s.live, s.ref)) return rc;
+    c->rows.set_fresh(s.hb->fresh_row);
     return book_pulled(c, s.hb->status);
 }
 
@@ -145,13 +145,13 @@ int book_push(slamgpu_ctx *c) {
             FrontLm &l = h->lm[t];
             if (l.idf < 0) continue;
             if (l.idf >= c->nf) return fail(SLAMGPU_ERR_INVALID, "the device's landmark table knows feature %d, the context only %d", l.idf, c->nf);
-            l.row = c->erow[l.idf] | (c->live_flag[l.idf] ? kRowLiveBit : 0);
+            l.row = c->rows.row_of(l.idf) | (c->rows.live_of(l.idf) ? kRowLiveBit : 0);
             seen++;
         }
         if (seen != c->nf)
             return fail(SLAMGPU_ERR_INVALID, "slamgpu_step_observe on a compact context: %d of its %d landmarks came from host-made packets, "
                         "which the device's landmark table does not know", c->nf - seen, c->nf);
-        h->hdr = FrontHdr{c->nf, c->fresh_row, f.front_status, 0};
+        h->hdr = FrontHdr{c->nf, c->rows.fresh(), f.front_status, 0};
         HIP_TRY(hipMemcpyAsync(f.front_dev + f.front_par, h, sizeof *h, hipMemcpyHostToDevice, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
         f.book_on_device = true;
@@ -163,13 +163,11 @@ int book_push(slamgpu_ctx *c) {
     const BookStage s = book_carve(c);
     *s.hb = DevBook{};
     s.hb->nf = c->nf;
-    s.hb->fresh_row = c->fresh_row;
+    s.hb->fresh_row = c->rows.fresh();
     s.hb->status = f.front_status;
-    std::copy(c->erow.begin(), c->erow.begin() + cn, s.erow);
-    std::copy(c->live_flag.begin(), c->live_flag.begin() + cn, s.live);
-    std::copy(c->refcnt.begin(), c->refcnt.begin() + cr, s.ref);
+    c->rows.export_tables((int) cn, s.row, s.live, s.ref);
     HIP_TRY(hipMemcpyAsync(f.book_dev, s.hb, sizeof(DevBook), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(c->erow_dev, s.erow, 4 * cn, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->erow_dev, s.row, 4 * cn, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(c->live_dev, s.live, 4 * cn, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(f.refcnt_dev, s.ref, 4 * cr, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -291,7 +289,7 @@ int do_update_dev(slamgpu_ctx *c, const float xtrue[3], float max_range, const f
         if (int rc = issue_update(c, U, -1, -1, need_normals, normals, strata, false)) return rc;
         f.front_par ^= 1;
         f.last_pkt_dev = f.front_pkt_dev;
-        c->fresh_row = -1;  // (the device's book knows)
+        c->rows.set_fresh(-1);  // (the device's book knows)
         return 0;
     }
     const size_t nl = (size_t) f.map_n;
@@ -325,7 +323,7 @@ int do_update_dev(slamgpu_ctx *c, const float xtrue[3], float max_range, const f
     HIP_TRY(hipEventRecord(f.obs_ev[slot], f.obs_stream));
     HIP_TRY(hipStreamWaitEvent(c->stream, f.obs_ev[slot], 0));
     f.last_pkt_dev = pd;
-    c->fresh_row = -1;  // (the device's book knows)
+    c->rows.set_fresh(-1);  // (the device's book knows)
 
     UpdateArgs U{};
     U.method = c->cfg.method;
@@ -543,15 +541,16 @@ int slamgpu_observe_fetch(slamgpu_ctx *c, float *z, int32_t *vis, int32_t *nz, f
     if (f.obs_stream) HIP_TRY(hipStreamSynchronize(f.obs_stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     const size_t C = (size_t) f.map_n;
-    std::vector<char> pk(sizeof(ObsPacket) + 4 * 6 * C), ob(sizeof(ObserveOut) + 4 * 3 * C);
+    // (a device-made packet: the dense layout at the map's capacity, read up to its row lists)
+    std::vector<char> pk(DenseLayout::of(sizeof(ObsPacket), C, C, C, 0).used), ob(sizeof(ObserveOut) + 4 * 3 * C);
     HIP_TRY(hipMemcpy(pk.data(), f.last_pkt_dev, pk.size(), hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(ob.data(), f.obs_out_dev, ob.size(), hipMemcpyDeviceToHost));
     const ObsPacket *h = reinterpret_cast<const ObsPacket *>(pk.data());
-    const int32_t *base = reinterpret_cast<const int32_t *>(h + 1);
+    const BigPacket::Dense d = BigPacket::layout_at(pk.data(), C, C, C, 0);
     unpack_observe_out(reinterpret_cast<const ObserveOut *>(ob.data()), C, z, vis, nz);
-    if (idf) memcpy(idf, base, sizeof(int32_t) * (size_t) h->m);
-    if (zf) memcpy(zf, base + C, sizeof(float) * 2 * (size_t) h->m);
-    if (zn) memcpy(zn, base + 3 * C, sizeof(float) * 2 * (size_t) h->n);
+    if (idf) memcpy(idf, d.idf, sizeof(int32_t) * (size_t) h->m);
+    if (zf) memcpy(zf, d.zf, sizeof(float) * 2 * (size_t) h->m);
+    if (zn) memcpy(zn, d.zn, sizeof(float) * 2 * (size_t) h->n);
     if (m) *m = h->m;
     if (n) *n = h->n;
     if (h->status & kStatusCapacity) return fail(SLAMGPU_ERR_CAPACITY, "the device front end dropped new landmarks: landmark capacity %d exceeded", c->B.cap_nf);

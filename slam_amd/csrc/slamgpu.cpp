@@ -153,34 +153,10 @@ void compose_predicts(PredictArgs &P) {
     C.m22 = (float) M[2][2];
 }
 
-// ---- genealogy rows (host bookkeeping) ----
-void rows_add_live(slamgpu_ctx *c, int r) {
-    c->live_pos[r] = (int32_t) c->live_rows.size();
-    c->live_rows.push_back(r);
-}
-
-void rows_remove_live(slamgpu_ctx *c, int r) {
-    const int p = c->live_pos[r], last = c->live_rows.back();
-    c->live_rows[p] = last;
-    c->live_pos[last] = p;
-    c->live_rows.pop_back();
-    c->live_pos[r] = -1;
-}
-
+// ---- genealogy rows (the host's book: rows.h) ----
 // every landmark [0, nf) in row 0 (own slot): after upload, flatten, a settling unpack
 void rows_reset(slamgpu_ctx *c, int nf) {
-    const int cap_rows = c->B.cap_rows;
-    c->fresh_row = -1;
-    std::fill(c->refcnt.begin(), c->refcnt.end(), 0);
-    std::fill(c->live_pos.begin(), c->live_pos.end(), -1);
-    std::fill(c->erow.begin(), c->erow.end(), 0);
-    c->live_rows.clear();
-    c->free_rows.clear();
-    for (int r = cap_rows - 1; r >= (nf > 0 ? 1 : 0); r--) c->free_rows.push_back(r);  // back() = lowest free row
-    if (nf > 0) {
-        c->refcnt[0] = nf;
-        rows_add_live(c, 0);
-    }
+    c->rows.reset(nf);
     c->tables_dirty = true;
 }
 
@@ -190,14 +166,16 @@ int sync_tables(slamgpu_ctx *c) {
     c->B.erow = c->erow_dev;
     c->B.rows = c->rows_dev;
     c->B.lmk_live = c->live_dev;
-    c->B.n_rows = (int32_t) c->live_rows.size();
+    const std::vector<int32_t> &in_use = c->rows.in_use();
+    c->B.n_rows = (int32_t) in_use.size();
     if (!c->tables_dirty) return 0;
     if (c->nf > 0) {
-        HIP_TRY(hipMemcpyAsync(c->erow_dev, c->erow.data(), sizeof(int32_t) * (size_t) c->nf, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipMemcpyAsync(c->live_dev, c->live_flag.data(), sizeof(int32_t) * (size_t) c->nf, hipMemcpyHostToDevice, c->stream));
+        const RowBook::Tables t = c->rows.tables();
+        HIP_TRY(hipMemcpyAsync(c->erow_dev, t.row, sizeof(int32_t) * (size_t) c->nf, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(c->live_dev, t.live, sizeof(int32_t) * (size_t) c->nf, hipMemcpyHostToDevice, c->stream));
     }
-    if (!c->live_rows.empty())
-        HIP_TRY(hipMemcpyAsync(c->rows_dev, c->live_rows.data(), sizeof(int32_t) * c->live_rows.size(), hipMemcpyHostToDevice, c->stream));
+    if (!in_use.empty())
+        HIP_TRY(hipMemcpyAsync(c->rows_dev, in_use.data(), sizeof(int32_t) * in_use.size(), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));  // pageable sources: the vectors may change right after
     c->tables_dirty = false;
     return 0;
@@ -215,7 +193,7 @@ int materialize(slamgpu_ctx *c) {
         Timed t(c, "gather");
         c->k->gather(c->stream, c->B, c->ws);
     }
-    c->fresh_row = -1;  // rows may have been composed: no shortcut past the genealogy for the next update
+    c->rows.set_fresh(-1);  // rows may have been composed: no shortcut past the genealogy for the next update
     HIP_TRY(hipGetLastError());
     c->slot ^= 1;
     c->B.slot = c->slot;
@@ -235,7 +213,7 @@ static int flatten(slamgpu_ctx *c) {
         c->k->flatten(c->stream, c->B, c->nf);
     }
     HIP_TRY(hipGetLastError());
-    for (int j = 0; j < c->nf; j++) c->live_flag[j] ^= 1;  // every row's records now live in its other buffer
+    c->rows.flip_all(c->nf);  // every row's records now live in its other buffer
     c->mg.pool_used = 0;  // every record is in its particle's own slot again
     rows_reset(c, c->nf);  // ... which is what genealogy row 0 says now, for every landmark
     return 0;
@@ -552,14 +530,9 @@ int slamgpu_create(const slamgpu_config *cfg, slamgpu_ctx **out) {
     }
     c->ws.nblocks = ncap / kBlock;
     // big-packet ring: header + idf[cap] + zf[2cap] + zn[2cap]
-    c->pkt_bytes = ((sizeof(ObsPacket) + sizeof(int32_t) * cap_nf + sizeof(float) * 4 * cap_nf + sizeof(int32_t) * (2 * (size_t) cap_nf + 1)) + 255) / 256 * 256;
-    c->erow.assign((size_t) cap_nf, 0);
-    c->live_flag.assign((size_t) cap_nf, 0);
-    c->seen_step.assign((size_t) cap_nf, 0);
+    c->pkt_bytes = BigPacket::capacity_bytes((size_t) cap_nf);
     c->as.box_dirty.assign((size_t) cap_nf, 1);
-    c->refcnt.assign((size_t) c->B.cap_rows, 0);
-    c->live_pos.assign((size_t) c->B.cap_rows, -1);
-    rows_reset(c, 0);
+    c->rows.init(cap_nf, c->B.cap_rows);
     if (cfg->external_stream) {
         c->stream = reinterpret_cast<hipStream_t>(cfg->external_stream);
         c->own_stream = false;
@@ -806,16 +779,13 @@ int demote_to_plain(slamgpu_ctx *c) {
     tmp.release();
     HIP_TRY(er);
     HIP_TRY(er2);
-    const int old_rows = c->B.cap_rows, new_rows = c->B.cap_nf + 1;
+    const int new_rows = c->B.cap_nf + 1;
     c->B.compact = 0;
     c->B.cap_rows = new_rows;
     c->mid_compact = false;
-    c->refcnt.resize((size_t) new_rows, 0);
-    c->live_pos.resize((size_t) new_rows, -1);
-    for (int r = old_rows; r < new_rows; r++) c->free_rows.push_back(r);
-    std::sort(c->free_rows.begin(), c->free_rows.end(), std::greater<int32_t>());  // back() = lowest free row
+    c->rows.grow_rows(new_rows);
     if (int rc = c->rows_dev.reserve((size_t) new_rows, "live rows")) return rc;
-    c->fresh_row = -1;
+    c->rows.set_fresh(-1);
     c->tables_dirty = true;
     return 0;
 }
@@ -834,14 +804,14 @@ int do_update(slamgpu_ctx *c, const float *zf, const int32_t *idf, int32_t m, co
     HIP_TRY(hipSetDevice(c->cfg.device));
     // a compact context's packet rides in the kernel arguments: at most kSmallObs re-observed and kSmallObs new landmarks, and its
     // genealogy has kSmallRows rows.  Maps of up to 39 landmarks cannot exceed either; a mid-size map that does goes to plain rows
-    if (c->mid_compact && (m > kSmallObs || n > kSmallObs || c->free_rows.size() < 2))
+    if (c->mid_compact && (m > kSmallObs || n > kSmallObs || c->rows.free_stack().size() < 2))
         if (int rc = demote_to_plain(c)) return rc;
     c->obs_step++;
 
     // genealogy rows: the landmarks this update writes move to a row it opens; the rows they leave may become unused
     for (int k = 0; k < m; k++) {
-        if (c->seen_step[idf[k]] == c->obs_step) return fail(SLAMGPU_ERR_INVALID, "landmark %d re-observed twice in one update", idf[k]);
-        c->seen_step[idf[k]] = c->obs_step;
+        if (c->rows.seen(idf[k], c->obs_step)) return fail(SLAMGPU_ERR_INVALID, "landmark %d re-observed twice in one update", idf[k]);
+        c->rows.mark_seen(idf[k], c->obs_step);
     }
     // Row consolidation (compact contexts): when more than kConsolidateAbove genealogy rows are alive, the landmarks this
     // update does NOT observe are rewritten by the launch, unchanged, into the particles' own slots and join the row it opens
@@ -849,10 +819,12 @@ int do_update(slamgpu_ctx *c, const float *zf, const int32_t *idf, int32_t m, co
     // view every ~60 steps on example_webmap, so after one consolidation the map lives in one or two rows for hundreds of
     // steps, and a resample composes one 16-byte chunk per particle instead of eight.  Values never change: results are bit
     // for bit those of a run without it (SLAMGPU_NO_CONSOLIDATE=1, tests/test_gpu_parity.py).
+    RowBook &rows = c->rows;
+    const int rows_in_use = (int) rows.in_use().size();
     std::vector<int32_t> cons;
-    if (c->B.compact && !c->mid_compact && !sharded && c->consolidate && (int) c->live_rows.size() > c->consolidate_above) {
+    if (c->B.compact && !c->mid_compact && !sharded && c->consolidate && rows_in_use > c->consolidate_above) {
         for (int j = 0; j < c->nf && m + (int) cons.size() < kSmallObs; j++)
-            if (c->seen_step[j] != c->obs_step) cons.push_back(j);
+            if (!rows.seen(j, c->obs_step)) cons.push_back(j);
         // (only worth a launch's while if it empties rows: every row but the one opened now, or as many landmarks as fit)
     }
     // Plain rows (big maps): every update opens a row, and the landmarks that went out of view stay behind in the rows of the
@@ -869,63 +841,40 @@ int do_update(slamgpu_ctx *c, const float *zf, const int32_t *idf, int32_t m, co
     // rows' policy instead, with bounds that fit the layout: past kMidRowsHigh rows in use the emptiest rows are emptied -- one or two
     // landmarks each on that map -- down to kMidRowsLow, as many as the packet has room for; 40 rows are never exceeded (past
     // kSmallRows - 2 the context would go to plain rows: do_update's guard).
-    const bool mid_cons = c->mid_compact && !sharded && c->consolidate && (int) c->live_rows.size() > kMidRowsHigh;
-    if (mid_cons || (!c->B.compact && !sharded && !c->mg.dist && c->consolidate && (int) c->live_rows.size() > c->plain_rows_target)) {
+    const bool mid_cons = c->mid_compact && !sharded && c->consolidate && rows_in_use > kMidRowsHigh;
+    if (mid_cons || (!c->B.compact && !sharded && !c->mg.dist && c->consolidate && rows_in_use > c->plain_rows_target)) {
         const int budget = mid_cons ? std::max(0, kSmallObs - m) : std::max(kPlainConsBudget, m / 16);
         const int target = mid_cons ? kMidRowsLow : c->plain_rows_target;
-        std::vector<int32_t> order(c->live_rows);
-        std::sort(order.begin(), order.end(), [&](int a, int b) { return c->refcnt[a] != c->refcnt[b] ? c->refcnt[a] < c->refcnt[b] : a < b; });
+        std::vector<int32_t> order(rows.in_use());
+        std::sort(order.begin(), order.end(), [&](int a, int b) { return rows.count(a) != rows.count(b) ? rows.count(a) < rows.count(b) : a < b; });
         std::vector<char> take((size_t) c->B.cap_rows, 0);
         int planned = 0, rows_taken = 0;
         for (int r : order) {
-            if (planned >= budget || (int) c->live_rows.size() - rows_taken <= target) break;
-            if (mid_cons && planned + c->refcnt[r] > budget) break;  // (whole rows only: a row half emptied stays in use)
+            if (planned >= budget || rows_in_use - rows_taken <= target) break;
+            if (mid_cons && planned + rows.count(r) > budget) break;  // (whole rows only: a row half emptied stays in use)
             take[(size_t) r] = 1;
-            planned += c->refcnt[r];
+            planned += rows.count(r);
             rows_taken++;
         }
         if (planned > 0)
             for (int j = 0; j < c->nf && (int) cons.size() < budget; j++)
-                if (take[(size_t) c->erow[j]] && c->seen_step[j] != c->obs_step) cons.push_back(j);
+                if (take[(size_t) rows.row_of(j)] && !rows.seen(j, c->obs_step)) cons.push_back(j);
     }
+    // the step on the book: the consolidated landmarks first, then the re-observed ones (a sharded update reads every record
+    // through the genealogy: no fresh bit for them), then the new ones behind the map
     const int nc = (int) cons.size();
-    int e_new = -1;
-    std::vector<int32_t> rows_of((size_t) m + nc), dropped;
-    if (m + n + nc > 0) {
-        e_new = c->free_rows.back();
-        c->free_rows.pop_back();
-    }
-    for (int q = 0; q < nc; q++) {
-        const int j = cons[(size_t) q], r = c->erow[j];
-        rows_of[(size_t) m + q] = r | (c->live_flag[j] ? kRowLiveBit : 0) | (r == c->fresh_row ? kRowFreshBit : 0);
-        c->live_flag[j] ^= 1;
-        if (--c->refcnt[r] == 0) {
-            rows_remove_live(c, r);
-            dropped.push_back(r);
-        }
-        c->erow[j] = e_new;
-        c->refcnt[e_new]++;
-    }
+    std::vector<int32_t> rows_of((size_t) m + nc);
+    const int e_new = rows.open(m + n + nc > 0);
+    for (int q = 0; q < nc; q++) rows_of[(size_t) m + q] = rows.move(cons[(size_t) q], true);
     for (int k = 0; k < m; k++) {
-        const int r = c->erow[idf[k]];
-        rows_of[k] = r | (c->live_flag[idf[k]] ? kRowLiveBit : 0);  // the landmark's live record buffer rides in bit 30
-        if (r == c->fresh_row && !sharded) rows_of[k] |= kRowFreshBit;
-        c->live_flag[idf[k]] ^= 1;                                   // this update writes its records into the other one
-        if (--c->refcnt[r] == 0) {
-            rows_remove_live(c, r);
-            dropped.push_back(r);
-        }
-        c->erow[idf[k]] = e_new;
-        c->refcnt[e_new]++;
+        rows_of[k] = rows.move(idf[k], !sharded);
         c->as.box_dirty[idf[k]] = 1;
     }
     for (int k = 0; k < n; k++) {
         c->as.box_dirty[c->nf + k] = 1;
-        c->erow[c->nf + k] = e_new;
-        c->refcnt[e_new]++;
-        c->live_flag[c->nf + k] = 0;  // a new row's first records go to buffer 0
+        rows.place_new(c->nf + k, false);
     }
-    const int n_rows = (int) c->live_rows.size();  // still in use, without e_new: what a pending gather has to compose
+    const int n_rows = (int) rows.in_use().size();  // still in use, without e_new: what a pending gather has to compose
     c->tables_dirty = true;
 
     UpdateArgs U{};
@@ -935,14 +884,10 @@ int do_update(slamgpu_ctx *c, const float *zf, const int32_t *idf, int32_t m, co
     U.nf = c->nf;
     U.e_new = e_new;
     U.n_rows = n_rows;
-    {
-        int top = e_new;
-        for (int r : c->live_rows) top = std::max(top, r);
-        U.live_chunks = (top >> 2) + 1;  // (top = -1: 0 chunks)
-    }
+    U.live_chunks = rows.live_chunks(e_new);
     U.all_fresh = 1;
     for (int k = 0; k < std::min(m, 8); k++) U.all_fresh &= (rows_of[k] & kRowFreshBit) ? 1 : 0;
-    c->fresh_row = sharded ? -1 : e_new;
+    rows.set_fresh(sharded ? -1 : e_new);
     memcpy(U.R, R, sizeof U.R);
     if (c->B.compact) {
         // compact context (at most kSmallRows - 1 landmarks): the packet rides in the kernel-argument segment, no staging
@@ -967,33 +912,22 @@ int do_update(slamgpu_ctx *c, const float *zf, const int32_t *idf, int32_t m, co
     } else {
         BigPacket bp;
         if (int rc = bp.begin(c, m, n, c->nf, n_rows, e_new)) return rc;
-        int32_t *hidf = reinterpret_cast<int32_t *>(bp.host + 1);
-        float *hzf = reinterpret_cast<float *>(hidf + m + nc);
-        float *hzn = hzf + 2 * m;
+        const BigPacket::Dense d = bp.layout((size_t) m + nc, m, n, n_rows);
         if (m) {
-            memcpy(hidf, idf, sizeof(int32_t) * m);
-            memcpy(hzf, zf, sizeof(float) * 2 * m);
+            memcpy(d.idf, idf, sizeof(int32_t) * m);
+            memcpy(d.zf, zf, sizeof(float) * 2 * m);
         }
-        if (nc) memcpy(hidf + m, cons.data(), sizeof(int32_t) * nc);  // the consolidated landmarks ride behind the re-observed ones
-        if (n) memcpy(hzn, zn, sizeof(float) * 2 * n);
-        int32_t *hrow = reinterpret_cast<int32_t *>(hzn + 2 * n);
-        if (m + nc) memcpy(hrow, rows_of.data(), sizeof(int32_t) * ((size_t) m + nc));
-        if (n_rows) memcpy(hrow + m + nc, c->live_rows.data(), sizeof(int32_t) * n_rows);
-        const size_t used = sizeof(ObsPacket) + sizeof(int32_t) * ((size_t) m + nc) + sizeof(float) * 2 * (m + n) + sizeof(int32_t) * ((size_t) m + nc + n_rows);
+        if (nc) memcpy(d.idf + m, cons.data(), sizeof(int32_t) * nc);  // the consolidated landmarks ride behind the re-observed ones
+        if (n) memcpy(d.zn, zn, sizeof(float) * 2 * n);
+        if (m + nc) memcpy(d.row, rows_of.data(), sizeof(int32_t) * ((size_t) m + nc));
+        if (n_rows) memcpy(d.rows, rows.in_use().data(), sizeof(int32_t) * n_rows);
         U.n_cons = nc;
-        if (int rc = bp.commit(c, used)) return rc;
+        if (int rc = bp.commit(c, d.used)) return rc;
         U.big = reinterpret_cast<const ObsPacket *>(bp.dev);
     }
-    // the row this update opens is in use from now on; the rows it emptied can be opened again by a later update
-    if (e_new >= 0) {
-        if (c->refcnt[e_new] > 0) rows_add_live(c, e_new);
-        else c->free_rows.push_back(e_new);
-    }
-    for (int r : dropped) c->free_rows.push_back(r);
-    // rows are opened lowest-first, so that the rows in use stay dense at the bottom (compact contexts copy chunks
-    // [0, live_chunks) on a resample)
-    if (c->B.compact && (!dropped.empty() || (e_new >= 0 && c->refcnt[e_new] == 0)))
-        std::sort(c->free_rows.begin(), c->free_rows.end(), std::greater<int32_t>());
+    // the row this update opens is in use from now on; the rows it emptied can be opened again by a later update (compact
+    // contexts: lowest first)
+    rows.close(c->B.compact);
     return issue_update(c, U, n, n_rows, need_normals, normals, strata, sharded);
 }
 
@@ -1167,7 +1101,7 @@ int slamgpu_num_landmarks(slamgpu_ctx *c) {
 int slamgpu_genealogy_rows(slamgpu_ctx *c, int32_t *in_use, int32_t *capacity) {
     if (int rc = check_ctx(c)) return rc;
     if (int rc = book_pull(c)) return rc;
-    if (in_use) *in_use = (int32_t) c->live_rows.size();
+    if (in_use) *in_use = (int32_t) c->rows.in_use().size();
     if (capacity) *capacity = c->B.cap_rows;
     return 0;
 }
@@ -1280,7 +1214,7 @@ int slamgpu_download_range(slamgpu_ctx *c, int32_t first, int32_t count, float *
     if ((xf || Pf4) && nf > 0) {
         // every landmark row has its own live buffer (kernels.h: lmk_live); rows are fetched a bounded batch at a time so
         // that a 10 000-landmark context does not need the whole slice on the host twice
-        const std::vector<int32_t> &live = c->live_flag;
+        const int32_t *live = c->rows.tables().live;
         const int batch = (int) std::max<size_t>(1, std::min<size_t>((size_t) nf, ((size_t) 64 << 20) / (20 * M)));
         std::vector<float4> la(M * batch);
         std::vector<float> lb(M * batch);
@@ -1400,7 +1334,7 @@ int slamgpu_upload(slamgpu_ctx *c, int32_t nf, const float *xv, const float *Pv9
     }
     // every landmark row live in buffer 0, every record in its particle's own slot
     c->mg.pool_used = 0;
-    std::fill(c->live_flag.begin(), c->live_flag.end(), 0);
+    c->rows.clear_live();
     c->B.slot = c->slot;
     c->k->identity(c->stream, c->B, cur, 0);  // every landmark in genealogy row 0: own slot
     HIP_TRY(hipStreamSynchronize(c->stream));

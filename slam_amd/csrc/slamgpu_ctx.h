@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "kernels.h"
+#include "rows.h"
 
 using namespace slamgpu;
 
@@ -366,6 +367,21 @@ struct BigPacket {
     char *dev = nullptr;
     int begin(slamgpu_ctx *c, int32_t m, int32_t n, int32_t nf, int32_t n_rows, int32_t e_new);
     int commit(slamgpu_ctx *c, size_t used);
+    // the fields of the dense layout (rows.h: DenseLayout) in a packet at `pkt`, and the bytes they and the header take
+    struct Dense {
+        int32_t *idf;
+        float *zf, *zn;
+        int32_t *row, *rows;
+        size_t used;
+    };
+    static Dense layout_at(void *pkt, size_t m_plus_cons, size_t m, size_t n, size_t n_rows) {
+        const DenseLayout L = DenseLayout::of(sizeof(ObsPacket), m_plus_cons, m, n, n_rows);
+        char *b = static_cast<char *>(pkt);
+        return {reinterpret_cast<int32_t *>(b + L.idf), reinterpret_cast<float *>(b + L.zf), reinterpret_cast<float *>(b + L.zn),
+                reinterpret_cast<int32_t *>(b + L.row), reinterpret_cast<int32_t *>(b + L.rows), L.used};
+    }
+    Dense layout(size_t m_plus_cons, size_t m, size_t n, size_t n_rows) const { return layout_at(host, m_plus_cons, m, n, n_rows); }
+    static size_t capacity_bytes(size_t cap_nf) { return DenseLayout::capacity_bytes(sizeof(ObsPacket), cap_nf); }  // a ring slot
 };
 int pkt_take_slot(slamgpu_ctx *c);
 
@@ -430,21 +446,11 @@ struct slamgpu_ctx {
     int consolidate_above = kConsolidateAbove;  // (SLAMGPU_CONSOLIDATE_ABOVE: diagnostic)
     int plain_rows_target = kPlainRowsTarget;   // (SLAMGPU_PLAIN_ROWS_TARGET: diagnostic / tests)
     int scan_min_blocks = 1024;   // contexts with more blocks of 256 particles than this use scan_kernel (262 144 particles)
-    // Genealogy bookkeeping (kernels.h: gen).  The association is global, so the host knows which genealogy row every
-    // landmark uses: a step that writes landmarks opens a new row for them; a row whose last landmark moved on is recycled.
-    std::vector<uint32_t> seen_step; // [cap_nf] observation step that last re-observed each landmark (duplicate check)
-    std::vector<int32_t> live_flag;  // [cap_nf] which record buffer of every landmark row is live (flips when re-observed)
-    DevBuf<int32_t> live_dev;        // device copy for flatten / shard pack + unpack
-    std::vector<int32_t> erow;       // [cap_nf] row of every landmark
-    std::vector<int32_t> refcnt;     // [cap_rows] landmarks using each row
-    std::vector<int32_t> free_rows;  // stack of unused rows
-    std::vector<int32_t> live_rows;  // rows with refcnt > 0
-    std::vector<int32_t> live_pos;   // [cap_rows] position in live_rows, -1 if not live
-    DevBuf<int32_t> erow_dev, rows_dev;  // device copies for gather / flatten / shard pack + unpack
+    // Genealogy bookkeeping (kernels.h: gen; rows.h): which row every landmark uses, which of its record buffers is live, the rows in use
+    RowBook rows;
+    DevBuf<int32_t> erow_dev, live_dev, rows_dev;  // device copies for gather / flatten / shard pack + unpack
     Multi mg;                        // sharded and distributed operation (multigpu.cpp)
-    int fresh_row = -1;              // row the last update opened, while nothing but the resample the next update launch
-                                     // applies has touched it: records of its landmarks sit in the source slot itself
-    bool tables_dirty = true;
+    bool tables_dirty = true;        // the book has changed since sync_tables made the device copies
     Front fe;                        // the observation front end and the genealogy book's hand-over (observe.cpp)
     Persist ps;                      // the persistent step loop (observe.cpp)
     Assoc as;                       // the gated and per-particle association (association.cpp)
@@ -497,8 +503,6 @@ int materialize(slamgpu_ctx *c);
 int read_ctrl(slamgpu_ctx *c, bool need_set = false);
 int demote_to_plain(slamgpu_ctx *c);
 int issue_update(slamgpu_ctx *c, UpdateArgs &U, int n_new, int n_rows, bool need_normals, const float *normals, const float *strata, bool sharded);
-void rows_add_live(slamgpu_ctx *c, int r);
-void rows_remove_live(slamgpu_ctx *c, int r);
 void compose_predicts(PredictArgs &P);
 RngArgs rng_args(const slamgpu_ctx *c, uint32_t step);
 int do_update(slamgpu_ctx *c, const float *zf, const int32_t *idf, int32_t m, const float *zn, int32_t n, const float R[4], const float *normals,
@@ -518,7 +522,7 @@ int record_step(slamgpu_ctx *c);
 // observe.cpp's
 int book_pull(slamgpu_ctx *c);
 int book_staging(slamgpu_ctx *c);
-void book_rebuild(slamgpu_ctx *c);
+int book_import(slamgpu_ctx *c, int nf, int n_lmk, const int32_t *row, const int32_t *live, const int32_t *ref);
 int persist_check(slamgpu_ctx *c);
 // what the observation kernels' arguments share (the map, the pose, the noise, the Philox key); takes the next observation step
 ObserveArgs observe_args(slamgpu_ctx *c, const float xtrue[3], float max_range, const float R[4], int32_t noise);

@@ -12,7 +12,12 @@ example_webmap, 256 particles (one block) and 1 024.  The states:
     big-packet ring: every slot is reused and waited for), both kernel builds, FastSLAM 1 and 2, with slamgpu_profile off and on:
     stats / ancestors / status every 10th step, slamgpu_download and slamgpu_upload of it after step 35 and the steps that follow,
     slamgpu_estimate, slamgpu_estimate_async and slamgpu_estimate_fetch taken in two parts, slamgpu_peek with and without landmarks,
-    of a range and with a stride, slamgpu_download.
+    of a range and with a stride, slamgpu_download;
+  - the row policy of host-made packets (do_update), FastSLAM 2, fast build, slamgpu_genealogy_rows after every step, history and download:
+    the default compact context for the same 70 steps (its row consolidation is live); the plain-row context with
+    SLAMGPU_PLAIN_ROWS_TARGET=6 (plain consolidation on a 35-landmark map); example_loop902 (117 landmarks: a compact context of a
+    mid-size map), 256 particles, with its consolidation and -- SLAMGPU_NO_CONSOLIDATE=1, so that the 40 rows run out -- until 30 steps
+    past its demotion to plain rows (the capacity is checked to cross 40).
 
 usage: python tools/core_bits.py"""
 import hashlib
@@ -25,7 +30,7 @@ import numpy as np  # noqa: E402
 import slam_amd as sg  # noqa: E402
 from slam_amd import host  # noqa: E402
 
-STEPS, TAPE_STEPS, FIRST = 70, 20, 7
+STEPS, TAPE_STEPS, FIRST, LOOP_STEPS = 70, 20, 7, 2000
 f32 = np.float32
 KEYS = ("xv", "Pv", "w", "xf", "Pf")
 n_digests = 0
@@ -105,8 +110,46 @@ def plain_run(T, N, method, math_mode, profile, tag):
     s.close()
 
 
+def rows_run(T, N, cap, env, steps, tag, demotes=False):
+    """host-made packets only; stops `30 steps past the demotion` where one is expected"""
+    for k, v in env.items():
+        os.environ[k] = v
+    s = sg.SlamGpu(N, cap, method=sg.FASTSLAM2, n_effective=int(0.75 * N), rng_mode=sg.RNG_PHILOX, seed=7, math_mode=sg.MATH_FAST)
+    for k in env:
+        os.environ.pop(k, None)
+    rows, left = [], -1
+    for step in T["steps"][:steps]:
+        s.step([c for c in step["controls"]], T["Q"], float(T["dt"]), step["zf"], step["idf"], step["zn"], T["R"])
+        rows.append(s.genealogy_rows())
+        if demotes and left < 0 and rows[-1][1] > 40:
+            left = 30
+        if left == 0:
+            break
+        left -= left > 0
+    rows = np.array(rows, np.int32)
+    if demotes:
+        assert rows[0, 1] == 40 and rows[-1, 1] > 40 and left == 0, "no demotion to plain rows 30 steps before the end of the tape (capacity %d)" % rows[-1, 1]
+        first = int(np.argmax(rows[:, 1] > 40))
+        digest(tag, "genealogy_rows before", rows[first - 1])
+        digest(tag, "genealogy_rows after", rows[first])
+    digest(tag, "genealogy_rows", rows[9::10])
+    digest(tag, "genealogy_rows every step", rows)
+    for q, v in zip(("xyt", "neff", "resampled"), s.history_fetch()):
+        digest(tag, "history_fetch." + q, v)
+    for key, v in s.download().items():
+        digest(tag, "download.%s" % key, np.asarray(v))
+    s.close()
+
+
 for N in (256, 1024):
     T = load(N)
+    if N == 256:
+        rows_run(T, N, T["nlm"], {}, STEPS, "rows compact %d" % N)
+        rows_run(T, N, T["nlm"], {"SLAMGPU_NO_COMPACT": "1", "SLAMGPU_PLAIN_ROWS_TARGET": "6"}, STEPS, "rows plain target 6 %d" % N)
+        L = host.make_tape(["-m", os.path.join(ROOT, "data", "example_loop902.mat"), "-method", "FASTSLAM2", "-NPARTICLES", N, "-SWITCH_SEED_RANDOM", 7],
+                           max_obs=LOOP_STEPS)
+        rows_run(L, N, L["nlm"], {}, 400, "rows loop902 %d" % N)
+        rows_run(L, N, L["nlm"], {"SLAMGPU_NO_CONSOLIDATE": "1"}, LOOP_STEPS, "rows loop902 demoted %d" % N, demotes=True)
     for method in (sg.FASTSLAM1, sg.FASTSLAM2):
         tape_run(T, N, method, "tape strict fs%d %d" % (method, N))
         for math_mode in (sg.MATH_STRICT, sg.MATH_FAST):
