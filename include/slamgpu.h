@@ -840,6 +840,7 @@ int slamgpu_ekf_block(slamgpu_ekf *e, const int32_t *idx, int32_t k, float *out)
 int slamgpu_ekf_upload(slamgpu_ekf *e, int32_t dim, const float *x, const float *P, int32_t ld_in);
 int slamgpu_ekf_status(slamgpu_ekf *e, int32_t *status);
 int slamgpu_ekf_sync(slamgpu_ekf *e);
+/* (local periods of this filter, slamgpu_ekf_local_* and slamgpu_ekf_lookup: with the stable entry points at the end of this file) */
 
 /* ---- EKF-SLAM ensemble: `members` independent filters resident in device memory, ONE launch per EKFSLAM::sim of all of them ------
  * A filter of the size of this project's maps (dim 73) cannot fill a GPU; many of them can, and Monte Carlo runs are how EKF-SLAM
@@ -1228,6 +1229,33 @@ int slamgpu_ens_trace_fetch(slamgpu_ekf_ens *e, int64_t first, int32_t count, do
  *      A null handle, a null mean or a bad D: SLAMGPU_ERR_INVALID and the outputs are untouched.  What it costs: DESIGN.md section 7i. */
 int slamgpu_ens_moments(slamgpu_ekf_ens *e, int32_t D, uint32_t exclude_status, double *mean /*[D]*/, double *C /*[D][D] or NULL*/,
                         double *Pbar /*[D][D] or NULL*/, int32_t *counted, int32_t *left_out, int32_t *pivot);
+
+/* ---- EKF-SLAM on the device, continued: local periods.  STABLE (outside the block above).  The compressed EKF (Guivant and Nebot,
+ * IEEE Trans. Robotics and Automation 17(3), 2001).  Between local_begin and
+ * local_end the stages filter the pose and the k listed features (and the features the period creates) only, at a cost that grows
+ * with that active set and not with the map; what the period does to the rest of the map is carried in three small matrices and
+ * applied to P in ONE pass by local_end.  The same filter, not an approximation: after local_end x and P are what the same calls
+ * without a period leave, up to float32 rounding (DESIGN.md section 7h has the algebra, the layout and what the commit costs).
+ * The heading update's eps I is left out of the passive part's diagonal: h eps for h heading updates, eight orders below float32
+ * rounding of P.  psi, the largest of the three matrices, is summed in float64 and the commit's product with it is formed in float64.
+ * local_begin: features[k] are global feature indices, ascending and distinct, each in [0, nf); k = 0 is the pose alone.  max_new >= 0
+ *      bounds the features the period may create: an augment (or a sim step) beyond it returns SLAMGPU_ERR_CAPACITY with nothing
+ *      applied (in sim with the gates: after the predict and heading stages, as for max_landmarks) and the period stays usable; end it
+ *      and begin again.  The period's buffers are grow-only.  Does not wait for the device.  A period already open: SLAMGPU_ERR_INVALID.
+ * While a period is open predict / observe_heading / associate / update / augment / sim / pose / dim / status / sync keep their
+ *      signatures and semantics.  Feature indices in idf and in returned labels stay GLOBAL; features created in the period take the
+ *      indices nf, nf + 1, ... in creation order, where the full filter would have put them, and dim reports the full filter's
+ *      dimension.  The gates see the active and the new features only.  An idf that names a passive feature -- in sim with the known
+ *      association: an id on one, checked before the predict -- is SLAMGPU_ERR_INVALID with nothing applied.  state, block and upload
+ *      return SLAMGPU_ERR_INVALID: the passive part of P is stale by design.  destroy discards an open period.
+ * local_end: the commit.  Afterwards the handle is an ordinary filter, P == P^T bit for bit.  No period open: SLAMGPU_ERR_INVALID.
+ * local_info: out = {open, k, features created so far, max_new, stage calls that succeeded since begin (sim counts once), commits so
+ *      far}; the first five are 0 while no period is open.
+ * lookup: the known association's table, features_out[i] = the feature of ids[i] or -1 (not seen yet, or negative); host only. */
+int slamgpu_ekf_local_begin(slamgpu_ekf *e, const int32_t *features, int32_t k, int32_t max_new);
+int slamgpu_ekf_local_end(slamgpu_ekf *e);
+int slamgpu_ekf_local_info(slamgpu_ekf *e, int32_t out[6]);
+int slamgpu_ekf_lookup(slamgpu_ekf *e, const int32_t *ids, int32_t n, int32_t *features_out);
 
 #ifdef __cplusplus
 }

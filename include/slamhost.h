@@ -72,6 +72,11 @@ int slamhost_sim_noise(const slamhost_sim *s, float Q[4], float R[4], float Qe[4
 int slamhost_ekf_sim(slamhost_ekf *e, float V, float G, const float Q[4], float dt, float phi, const float *z, const int32_t *ids, int32_t nz,
                      const float Re[4], const float R[4], int32_t observe);
 int slamhost_ekf_upload(slamhost_ekf *e, int32_t dim, const float *x, const float *P, int32_t ld);
+/* The region of a local period of the device filter (slamgpu.h: slamgpu_ekf_local_begin): the features of the EKF-SLAM state x[dim]
+ * (dim = 3 + 2 nf) whose estimate lies within `radius` of the pose estimate (x[0], x[1]) -- dx dx + dy dy <= radius radius in float32,
+ * the boundary included -- ascending into features_out[max_count].  Returns their number, -1 if there are more than max_count
+ * (features_out then holds the first max_count), -2 for bad arguments.  Pure host code. */
+int slamhost_ekf_local_region(const float *x, int32_t dim, float radius, int32_t *features_out, int32_t max_count);
 
 /* libc rand() tape in the reference's draw order */
 /* The policy that turns the vote of the gated per-particle association (slamgpu_associate: labels by EKFSLAM::dataAssociate,

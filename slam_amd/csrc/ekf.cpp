@@ -2,13 +2,11 @@
 // Kernels and host side in one unit; the stages' arithmetic is in ekf_helpers.h, shared with the ensemble.  It restates host/ekfslam.cpp
 // (itself the restatement of matzipan/slam algorithms/ekfslam.cpp:17-323 and core.cpp:275-317) stage by stage; where the order of a sum
 // or the form of an update differs from the host's, the stage says so.  The host tracks dim (it knows the labels): none on the device.
-#include "slamgpu_ctx.h"
-#include "ekf_helpers.h"
+// While a local period is open (ekf_local.cpp; the handle both units share: ekf_handle.h) the same kernels run on the period's
+// extended matrix: the host functions below take what they work on from ekf_mat().
+#include "ekf_handle.h"
 
 namespace {
-
-constexpr int kTile = 128;   // tile of P per workgroup of ekf_syrk_kernel
-constexpr int kKStep = 32;   // k columns of W1 staged in LDS at a time; a chunk's K is padded with zeros to a multiple of it
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
@@ -18,18 +16,6 @@ struct EkfObs {
     int32_t idf[kChunk];
     float R[4];
     int32_t m;
-};
-
-// the small device work area, by value.  flag: [0] the chunk's factorisation succeeded, [1] sticky status bits, [2] ekf_predict_kernel's ticket
-struct EkfWork {
-    float *H5;  // [kChunk][10]
-    float *v;   // [kKMax] innovation
-    float *t;   // [kKMax] U^-T v
-    float *Ui;  // [kKMax][kKMax] inverse of the upper factor
-    float *hv;  // [2] heading update: innovation, S
-    float *c2;  // [ld] heading update: column 2 of P before it
-    float *Wh;  // [ld] heading update: gain
-    int32_t *flag;
 };
 
 // (the arithmetic of every stage but the gain and the rank update: ekf_helpers.h, shared with the ensemble)
@@ -272,45 +258,55 @@ __global__ void __launch_bounds__(kEkfBlock) ekf_block_kernel(const float *__res
 
 }  // namespace
 
-struct slamgpu_ekf {
-    slamgpu_ekf_config cfg{};
-    EkfStream stream;
-    int dim = 3, ld = 0, cap_dim = 0;
-    DevBuf<float> P, x, PHt, W1, work, z_dev, blk_dev;
-    DevBuf<int32_t> flag, lab_dev, idx_dev;
-    PinBuf<char> pin;
-    EkfWork w{};
-    EkfIdTable table;  // association_known
-};
-
-namespace {
-
 int ekf_check(slamgpu_ekf *e) {
     if (!e) return fail(SLAMGPU_ERR_INVALID, "null EKF handle");
     HIP_TRY(hipSetDevice(e->cfg.device));
     return 0;
 }
 
+namespace {
+
 inline int nf_of(const slamgpu_ekf *e) { return (e->dim - 3) / 2; }
 
+// what the stages work on: P and x, or an open local period's extended matrix
+inline EkfMat ekf_mat(slamgpu_ekf *e) {
+    if (e->loc.open) return ekf_local_mat(e);
+    return EkfMat{e->P, e->x, e->PHt, e->W1, e->ld, e->dim, nf_of(e), e->dim, e->w};
+}
+
+inline int ekf_closed(const slamgpu_ekf *e, const char *what) {
+    return e->loc.open ? fail(SLAMGPU_ERR_INVALID, "%s while a local period is open (the passive part of P is stale until slamgpu_ekf_local_end)", what) : 0;
+}
+
+// a stage entry point's tail: the period counts the calls that succeeded
+inline int ekf_counted(slamgpu_ekf *e, int rc) {
+    if (rc == 0 && e->loc.open) e->loc.calls++;
+    return rc;
+}
+
 int ekf_predict(slamgpu_ekf *e, float V, float G, const float Q[4], float dt) {
-    const int nb = std::max(1, (e->dim - 3 + kEkfBlock - 1) / kEkfBlock);
-    ekf_predict_kernel<<<nb, kEkfBlock, 0, e->stream>>>(e->P, e->ld, e->dim, e->x, V, G, Q[0], Q[1], Q[2], Q[3], dt, e->cfg.wheel_base, e->flag.p + 2);
+    const EkfMat m = ekf_mat(e);
+    const int nb = std::max(1, (m.n - 3 + kEkfBlock - 1) / kEkfBlock);
+    ekf_predict_kernel<<<nb, kEkfBlock, 0, e->stream>>>(m.P, m.ld, m.n, m.x, V, G, Q[0], Q[1], Q[2], Q[3], dt, e->cfg.wheel_base, e->flag.p + 2);
     return ekf_launched("ekf_predict_kernel");
 }
 
 int ekf_heading(slamgpu_ekf *e, float phi) {
+    const EkfMat m = ekf_mat(e);
     const float R = (float) std::pow((double) e->cfg.sigma_phi, 2);
-    const int nb = (e->dim + kEkfBlock - 1) / kEkfBlock;
-    ekf_heading_gain_kernel<<<nb, kEkfBlock, 0, e->stream>>>(e->P, e->ld, e->dim, e->x, phi, R, e->w);
+    const int nb = (m.n + kEkfBlock - 1) / kEkfBlock;
+    ekf_heading_gain_kernel<<<nb, kEkfBlock, 0, e->stream>>>(m.P, m.ld, m.n, m.x, phi, R, m.w);
     if (int rc = ekf_launched("ekf_heading_gain_kernel")) return rc;
-    ekf_heading_kernel<<<dim3(nb, std::min(e->dim, 16384)), kEkfBlock, 0, e->stream>>>(e->P, e->ld, e->dim, e->x, e->w);
-    return ekf_launched("ekf_heading_kernel");
+    ekf_heading_kernel<<<dim3(nb, std::min(m.n, 16384)), kEkfBlock, 0, e->stream>>>(m.P, m.ld, m.n, m.x, m.w);
+    if (int rc = ekf_launched("ekf_heading_kernel")) return rc;
+    return e->loc.open ? ekf_local_heading(e) : 0;
 }
 
-// labels of the gates for z[nz] against the state as it stands: one synchronisation
+// labels of the gates for z[nz] against the state as it stands: one synchronisation.  In a local period the gates see the active and
+// the new features; the labels go out in global indices
 int ekf_associate(slamgpu_ekf *e, const float *z, int32_t nz, const float Re[4], int32_t *labels) {
     if (nz == 0) return 0;
+    const EkfMat m = ekf_mat(e);
     if (int rc = e->z_dev.reserve(2 * (size_t) nz, "EKF observations")) return rc;
     if (int rc = e->lab_dev.reserve((size_t) nz, "EKF labels")) return rc;
     if (int rc = e->pin.reserve(12 * (size_t) nz, "EKF association staging")) return rc;
@@ -318,12 +314,13 @@ int ekf_associate(slamgpu_ekf *e, const float *z, int32_t nz, const float Re[4],
     int32_t *lh = reinterpret_cast<int32_t *>(e->pin.p + 8 * (size_t) nz);
     memcpy(zh, z, 8 * (size_t) nz);
     HIP_TRY(hipMemcpyAsync(e->z_dev, zh, 8 * (size_t) nz, hipMemcpyHostToDevice, e->stream));
-    ekf_gate_kernel<<<nz, kEkfBlock, 0, e->stream>>>(e->P, e->ld, nf_of(e), e->x, e->z_dev, Re[0], Re[1], Re[2], Re[3], e->cfg.gate_reject,
+    ekf_gate_kernel<<<nz, kEkfBlock, 0, e->stream>>>(m.P, m.ld, m.nf, m.x, e->z_dev, Re[0], Re[1], Re[2], Re[3], e->cfg.gate_reject,
                                                       e->cfg.gate_augment, e->lab_dev);
     if (int rc = ekf_launched("ekf_gate_kernel")) return rc;
     HIP_TRY(hipMemcpyAsync(lh, e->lab_dev, 4 * (size_t) nz, hipMemcpyDeviceToHost, e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
     memcpy(labels, lh, 4 * (size_t) nz);
+    if (e->loc.open) ekf_local_labels(e, labels, nz);
     return 0;
 }
 
@@ -331,6 +328,12 @@ int ekf_update(slamgpu_ekf *e, const float *zf, const int32_t *idf, int32_t m, c
     const int nf = nf_of(e);
     for (int32_t i = 0; i < m; i++)
         if (idf[i] < 0 || idf[i] >= nf) return fail(SLAMGPU_ERR_INVALID, "idf[%d] = %d outside [0, %d)", i, idf[i], nf);
+    std::vector<int32_t> local;
+    if (e->loc.open) {
+        if (int rc = ekf_local_features(e, idf, m, local)) return rc;
+        idf = local.data();
+    }
+    const EkfMat M = ekf_mat(e);
     for (int32_t at = 0; at < m; at += kChunk) {
         EkfObs O{};
         O.m = std::min(kChunk, m - at);
@@ -338,32 +341,47 @@ int ekf_update(slamgpu_ekf *e, const float *zf, const int32_t *idf, int32_t m, c
         memcpy(O.idf, idf + at, 4 * (size_t) O.m);
         memcpy(O.R, R, 16);
         const int n = 2 * O.m, npad = (n + kKStep - 1) / kKStep * kKStep;
-        ekf_innov_kernel<<<dim3((e->dim + kEkfBlock - 1) / kEkfBlock, O.m), kEkfBlock, 0, e->stream>>>(e->P, e->ld, e->dim, e->x, O, e->PHt, e->w);
+        ekf_innov_kernel<<<dim3((M.n + kEkfBlock - 1) / kEkfBlock, O.m), kEkfBlock, 0, e->stream>>>(M.P, M.ld, M.n, M.x, O, M.PHt, M.w);
         if (int rc = ekf_launched("ekf_innov_kernel")) return rc;
-        ekf_chol_kernel<<<1, kEkfBlock, 0, e->stream>>>(e->PHt, e->ld, O, e->w);
+        ekf_chol_kernel<<<1, kEkfBlock, 0, e->stream>>>(M.PHt, M.ld, O, M.w);
         if (int rc = ekf_launched("ekf_chol_kernel")) return rc;
-        ekf_gain_kernel<<<(e->dim + 31) / 32, kEkfBlock, 0, e->stream>>>(e->PHt, e->ld, e->dim, e->x, n, npad, e->W1, e->w);
+        ekf_gain_kernel<<<(M.n + 31) / 32, kEkfBlock, 0, e->stream>>>(M.PHt, M.ld, M.n, M.x, n, npad, M.W1, M.w);
         if (int rc = ekf_launched("ekf_gain_kernel")) return rc;
-        const int tiles = (e->dim + kTile - 1) / kTile;
-        ekf_syrk_kernel<<<dim3(tiles, tiles), kEkfBlock, 0, e->stream>>>(e->P, e->ld, e->dim, e->W1, npad, e->flag);
+        if (e->loc.open)
+            if (int rc = ekf_local_chunk(e, n)) return rc;
+        const int tiles = (M.n + kTile - 1) / kTile;
+        ekf_syrk_kernel<<<dim3(tiles, tiles), kEkfBlock, 0, e->stream>>>(M.P, M.ld, M.n, M.W1, npad, e->flag);
         if (int rc = ekf_launched("ekf_syrk_kernel")) return rc;
     }
     return 0;
 }
 
-int ekf_augment(slamgpu_ekf *e, const float *zn, int32_t n, const float Re[4]) {
+// how many features a call may still create: the handle's capacity and, in a local period, the period's
+int ekf_room(slamgpu_ekf *e, int n, const char *note) {
     if (nf_of(e) + n > e->cfg.max_landmarks)
-        return fail(SLAMGPU_ERR_CAPACITY, "%d features + %d new exceed max_landmarks %d", nf_of(e), n, e->cfg.max_landmarks);
+        return fail(SLAMGPU_ERR_CAPACITY, "%d features + %d new exceed max_landmarks %d%s", nf_of(e), n, e->cfg.max_landmarks, note);
+    if (e->loc.open && e->loc.n_new + n > e->loc.max_new)
+        return fail(SLAMGPU_ERR_CAPACITY, "%d features created in the local period + %d new exceed its max_new %d%s", e->loc.n_new, n, e->loc.max_new, note);
+    return 0;
+}
+
+int ekf_augment(slamgpu_ekf *e, const float *zn, int32_t n, const float Re[4]) {
+    if (int rc = ekf_room(e, n, "")) return rc;
     for (int32_t q = 0; q < n; q++) {  // serial by nature: each feature's rows start from the pose rows, which the previous one left alone
-        ekf_augment_kernel<<<(e->dim + kEkfBlock - 1) / kEkfBlock, kEkfBlock, 0, e->stream>>>(e->P, e->ld, e->dim, e->x, zn[2 * q], zn[2 * q + 1], Re[0],
-                                                                                              Re[1], Re[2], Re[3]);
+        const EkfMat m = ekf_mat(e);
+        if (e->loc.open)
+            if (int rc = ekf_local_augment_carried(e, zn[2 * q], zn[2 * q + 1])) return rc;
+        ekf_augment_kernel<<<(m.len + kEkfBlock - 1) / kEkfBlock, kEkfBlock, 0, e->stream>>>(m.P, m.ld, m.len, m.x, zn[2 * q], zn[2 * q + 1], Re[0],
+                                                                                             Re[1], Re[2], Re[3]);
         if (int rc = ekf_launched("ekf_augment_kernel")) return rc;
         e->dim += 2;
+        if (e->loc.open) e->loc.n_new++;
     }
     return 0;
 }
 
 void ekf_release(slamgpu_ekf *e) {
+    ekf_local_release(e);
     e->P.release();
     e->x.release();
     e->PHt.release();
@@ -431,30 +449,30 @@ void slamgpu_ekf_destroy(slamgpu_ekf *e) {
 int slamgpu_ekf_predict(slamgpu_ekf *e, float V, float G, const float Q[4], float dt) {
     if (int rc = ekf_check(e)) return rc;
     if (!Q) return fail(SLAMGPU_ERR_INVALID, "null Q");
-    return ekf_predict(e, V, G, Q, dt);
+    return ekf_counted(e, ekf_predict(e, V, G, Q, dt));
 }
 
 int slamgpu_ekf_observe_heading(slamgpu_ekf *e, float phi) {
     if (int rc = ekf_check(e)) return rc;
-    return ekf_heading(e, phi);
+    return ekf_counted(e, ekf_heading(e, phi));
 }
 
 int slamgpu_ekf_associate(slamgpu_ekf *e, const float *z, int32_t nz, const float Re[4], int32_t *labels_out) {
     if (int rc = ekf_check(e)) return rc;
     if (nz < 0 || !Re || (nz > 0 && (!z || !labels_out))) return fail(SLAMGPU_ERR_INVALID, "bad association arguments");
-    return ekf_associate(e, z, nz, Re, labels_out);
+    return ekf_counted(e, ekf_associate(e, z, nz, Re, labels_out));
 }
 
 int slamgpu_ekf_update(slamgpu_ekf *e, const float *zf, const int32_t *idf, int32_t m, const float R[4]) {
     if (int rc = ekf_check(e)) return rc;
     if (m < 0 || !R || (m > 0 && (!zf || !idf))) return fail(SLAMGPU_ERR_INVALID, "bad update arguments");
-    return ekf_update(e, zf, idf, m, R);
+    return ekf_counted(e, ekf_update(e, zf, idf, m, R));
 }
 
 int slamgpu_ekf_augment(slamgpu_ekf *e, const float *zn, int32_t n, const float Re[4]) {
     if (int rc = ekf_check(e)) return rc;
     if (n < 0 || !Re || (n > 0 && !zn)) return fail(SLAMGPU_ERR_INVALID, "bad augment arguments");
-    return ekf_augment(e, zn, n, Re);
+    return ekf_counted(e, ekf_augment(e, zn, n, Re));
 }
 
 int slamgpu_ekf_sim(slamgpu_ekf *e, float V, float G, const float Q[4], float dt, float phi, const float *z, const int32_t *ids, int32_t nz,
@@ -477,13 +495,16 @@ int slamgpu_ekf_sim(slamgpu_ekf *e, float V, float G, const float Q[4], float dt
                 idf.push_back(f);
             }
         }
-        if (nf_of(e) + (int) idn.size() > e->cfg.max_landmarks)
-            return fail(SLAMGPU_ERR_CAPACITY, "%d features + %d new exceed max_landmarks %d", nf_of(e), (int) idn.size(), e->cfg.max_landmarks);
+        if (int rc = ekf_room(e, (int) idn.size(), "")) return rc;
+        if (e->loc.open) {  // an id on a passive feature: refused before anything runs
+            std::vector<int32_t> local;
+            if (int rc = ekf_local_features(e, idf.data(), (int32_t) idf.size(), local)) return rc;
+        }
     }
     if (int rc = ekf_predict(e, V, G, Q, dt)) return rc;
     if (e->cfg.use_heading)
         if (int rc = ekf_heading(e, phi)) return rc;
-    if (!observe) return 0;
+    if (!observe) return ekf_counted(e, 0);
     if (!known) {
         std::vector<int32_t> lab((size_t) nz);
         if (int rc = ekf_associate(e, z, nz, Re, lab.data())) return rc;
@@ -495,16 +516,14 @@ int slamgpu_ekf_sim(slamgpu_ekf *e, float V, float G, const float Q[4], float dt
                 zn.insert(zn.end(), {z[2 * i], z[2 * i + 1]});
             }
         }
-        if (nf_of(e) + (int) (zn.size() / 2) > e->cfg.max_landmarks)
-            return fail(SLAMGPU_ERR_CAPACITY, "%d features + %d new exceed max_landmarks %d (the predict and heading stages have been applied)", nf_of(e),
-                        (int) (zn.size() / 2), e->cfg.max_landmarks);
+        if (int rc = ekf_room(e, (int) (zn.size() / 2), " (the predict and heading stages have been applied)")) return rc;
     }
     const int nf0 = nf_of(e);
     if (e->cfg.batch_update)
         if (int rc = ekf_update(e, zf.data(), idf.data(), (int32_t) idf.size(), R)) return rc;
     if (int rc = ekf_augment(e, zn.data(), (int32_t) (zn.size() / 2), Re)) return rc;
     e->table.learn(idn, nf0);
-    return 0;
+    return ekf_counted(e, 0);
 }
 
 int slamgpu_ekf_dim(slamgpu_ekf *e) {
@@ -516,8 +535,9 @@ int slamgpu_ekf_pose(slamgpu_ekf *e, double xyt[3], double Pvv[9]) {
     if (int rc = ekf_check(e)) return rc;
     if (!xyt && !Pvv) return fail(SLAMGPU_ERR_INVALID, "null outputs");
     float *h = reinterpret_cast<float *>(e->pin.p);
-    HIP_TRY(hipMemcpyAsync(h, e->x, 12, hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipMemcpy2DAsync(h + 3, 12, e->P, sizeof(float) * (size_t) e->ld, 12, 3, hipMemcpyDeviceToHost, e->stream));
+    const EkfMat m = ekf_mat(e);
+    HIP_TRY(hipMemcpyAsync(h, m.x, 12, hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipMemcpy2DAsync(h + 3, 12, m.P, sizeof(float) * (size_t) m.ld, 12, 3, hipMemcpyDeviceToHost, e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
     for (int i = 0; i < 3 && xyt; i++) xyt[i] = h[i];
     for (int i = 0; i < 9 && Pvv; i++) Pvv[i] = h[3 + i];
@@ -526,6 +546,7 @@ int slamgpu_ekf_pose(slamgpu_ekf *e, double xyt[3], double Pvv[9]) {
 
 int slamgpu_ekf_state(slamgpu_ekf *e, float *x, float *P, int32_t ld_out) {
     if (int rc = ekf_check(e)) return rc;
+    if (int rc = ekf_closed(e, "slamgpu_ekf_state")) return rc;
     if (P && ld_out < e->dim) return fail(SLAMGPU_ERR_INVALID, "ld_out %d < dim %d", ld_out, e->dim);
     HIP_TRY(hipStreamSynchronize(e->stream));
     if (int rc = ekf_state_out(e->x, e->P, e->ld, e->dim, x, P, ld_out)) return rc;
@@ -534,6 +555,7 @@ int slamgpu_ekf_state(slamgpu_ekf *e, float *x, float *P, int32_t ld_out) {
 
 int slamgpu_ekf_block(slamgpu_ekf *e, const int32_t *idx, int32_t k, float *out) {
     if (int rc = ekf_check(e)) return rc;
+    if (int rc = ekf_closed(e, "slamgpu_ekf_block")) return rc;
     if (k < 0 || (k > 0 && (!idx || !out))) return fail(SLAMGPU_ERR_INVALID, "bad block arguments");
     for (int32_t a = 0; a < k; a++)
         if (idx[a] < 0 || idx[a] >= e->cap_dim) return fail(SLAMGPU_ERR_INVALID, "idx[%d] = %d outside [0, %d)", a, idx[a], e->cap_dim);
@@ -552,6 +574,7 @@ int slamgpu_ekf_block(slamgpu_ekf *e, const int32_t *idx, int32_t k, float *out)
 
 int slamgpu_ekf_upload(slamgpu_ekf *e, int32_t dim, const float *x, const float *P, int32_t ld_in) {
     if (int rc = ekf_check(e)) return rc;
+    if (int rc = ekf_closed(e, "slamgpu_ekf_upload")) return rc;
     if (int rc = ekf_state_in(e->stream, e->x, e->P, e->ld, e->cap_dim, dim, x, P, ld_in)) return rc;
     e->dim = dim;
     e->table.identity(nf_of(e));

@@ -627,6 +627,19 @@ int slamhost_ekf_upload(slamhost_ekf *e, int32_t dim, const float *x, const floa
     return 0;
 }
 
+int slamhost_ekf_local_region(const float *x, int32_t dim, float radius, int32_t *features_out, int32_t max_count) {
+    if (!x || dim < 3 || ((dim - 3) & 1) || !(radius >= 0.0f) || max_count < 0 || (max_count > 0 && !features_out)) return -2;
+    const float r2 = radius * radius;
+    int32_t n = 0;
+    for (int32_t f = 0; f < (dim - 3) / 2; f++) {
+        const float dx = x[3 + 2 * f] - x[0], dy = x[4 + 2 * f] - x[1];
+        if (!(dx * dx + dy * dy <= r2)) continue;
+        if (n == max_count) return -1;
+        features_out[n++] = f;
+    }
+    return n;
+}
+
 int slamhost_sim_noise(const slamhost_sim *s, float Q[4], float R[4], float Qe[4], float Re[4], float *dt) {
     if (!s) return -1;
     if (Q) memcpy(Q, s->sim.Q, 16);

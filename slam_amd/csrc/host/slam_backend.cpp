@@ -133,6 +133,7 @@ static void usage(const char *a0) {
     printf("                        the GPU (slamgpu_ekf_sim), same output; refused with a FastSLAM method, and fails without a GPU (no CPU fallback)\n");
     printf("    -RUNS_MOMENTS 1 [-RUNS_MOMENTS_OUT file]  with -runs B: at the end one line that sets the members' sample covariance C against the mean Pbar of their own P (slamgpu_ens_moments): tr C / tr Pbar of the position, of the heading and per feature, the largest |correlation| of each, the bias of the mean; D = 3 with the gates, the whole state with the known association; file: D, mean, the D rows of C, the D rows of Pbar as text (%%.17g)\n");
     printf("    -RUNS_BATCH K [-RUNS_TRACE file]  with -runs B: K (1 .. 4096; default 64 up to B = 768, 1 beyond) control steps per launch, the same figures for every K; file: one line per control step with the NEES over the members\n");
+    printf("    -EKF_LOCAL margin [-EKF_LOCAL_NEW n]  with -method EKF1 -ekf device: the filter runs in local periods (slamgpu_ekf_local_*, the compressed EKF): only the features within MAX_RANGE + margin metres of the estimate are filtered, the rest of the map is brought up to date in one commit when the estimate has moved margin / 2 from where the period began, when a known landmark outside the region is observed, or when the period has created n (default 64) features; the same filter up to float32 rounding; the landmarks line reports the commits; not with -runs\n");
     printf("    -runs B [-RUNS_SEED s]  with -method EKF1 -ekf device: B (1 .. 65535) noise realisations of the run as one ensemble of device filters, Monte Carlo NEES at the end; not with -plot\n");
     printf("    -path none|smoothed smoothed: record the path posterior (one record per observation step, -PATH_RECORDS n of them kept, default 4096)\n");
     printf("                        and print one more line: the smoothed path's distance to the true path beside the filtered estimates', and the\n");
@@ -332,6 +333,8 @@ static void print_merged_map(slamgpu_ctx *ctx, const Simulator &sim, const std::
 static bool g_map_joint = false;
 static bool g_ekf_device = false;  // -ekf device: EKF1 on the GPU (slamgpu_ekf_*)
 static int g_runs = 0;             // -runs B: B noise realisations at once (slamgpu_ens_*)
+static double g_ekf_local = 0.0;   // -EKF_LOCAL margin: the device EKF in local periods (slamgpu_ekf_local_*); 0: off
+static int g_ekf_local_new = 64;   // -EKF_LOCAL_NEW n: the features a period may create
 static uint64_t g_runs_seed = 0;   // -RUNS_SEED s: the Philox key of their draws (default: SWITCH_SEED_RANDOM)
 static int g_runs_batch = 0;       // -RUNS_BATCH K: control steps per launch (slamgpu_ens_run_noise); 1: a slamgpu_ens_sim_noise per step; 0: by B (below)
 static std::string g_runs_trace;   // -RUNS_TRACE file: the per-step NEES over the members (slamgpu_ens_trace_*)
@@ -1045,6 +1048,28 @@ int main(int argc, char **argv) {
             fprintf(stderr, "-RUNS_SEED s: with -runs B\n");
             return EXIT_FAILURE;
         }
+        // ... and -EKF_LOCAL margin [-EKF_LOCAL_NEW n]: the device EKF in local periods.  Refused from the arguments alone
+        const std::string el = sim.conf.s("EKF_LOCAL"), eln = sim.conf.s("EKF_LOCAL_NEW");
+        sim.conf.kv.erase("EKF_LOCAL");
+        sim.conf.kv.erase("EKF_LOCAL_NEW");
+        if (!el.empty()) {
+            const char *why = nullptr;
+            if (!g_ekf_device) why = "with -method EKF1 -ekf device (the periods are the device filter's; there is no CPU fallback)";
+            else if (g_runs) why = "not with -runs B (the ensemble has no local periods)";
+            else if (!(atof(el.c_str()) > 0.0)) why = "margin must be > 0 (metres)";
+            if (why) {
+                fprintf(stderr, "-EKF_LOCAL margin: %s\n", why);
+                return EXIT_FAILURE;
+            }
+            g_ekf_local = atof(el.c_str());
+        }
+        if (!eln.empty()) {
+            if (!(g_ekf_local > 0.0) || atol(eln.c_str()) < 1) {
+                fprintf(stderr, "-EKF_LOCAL_NEW n: %s\n", !(g_ekf_local > 0.0) ? "with -EKF_LOCAL margin" : "n must be >= 1");
+                return EXIT_FAILURE;
+            }
+            g_ekf_local_new = (int) std::min<long>(atol(eln.c_str()), 1 << 20);
+        }
         // ... and -RUNS_BATCH K, -RUNS_TRACE file: how the ensemble's run is launched and its per-step NEES; refused from the arguments alone
         const std::string rb = sim.conf.s("RUNS_BATCH");
         g_runs_trace = sim.conf.s("RUNS_TRACE");
@@ -1418,6 +1443,36 @@ int main(int argc, char **argv) {
 
     std::vector<float> zf, zn, normals, strata, noise2, g_xf;
     std::vector<int32_t> idf;
+    // -EKF_LOCAL: the period that is open, where it began and which features it holds
+    struct {
+        bool open = false;
+        double cx = 0, cy = 0;
+        int nf0 = 0;
+        std::vector<char> active;
+        std::vector<float> x;
+        std::vector<int32_t> feat, looked;
+    } lp;
+    auto local_end = [&]() -> int {
+        if (!lp.open) return 0;
+        lp.open = false;
+        return slamgpu_ekf_local_end(ekf_dev);
+    };
+    auto local_begin = [&](int room) -> int {  // the features within MAX_RANGE + margin of the estimate as it stands
+        const int dim = slamgpu_ekf_dim(ekf_dev);
+        lp.nf0 = (dim - 3) / 2;
+        lp.x.resize((size_t) dim);
+        lp.feat.resize((size_t) std::max(lp.nf0, 1));
+        if (slamgpu_ekf_state(ekf_dev, lp.x.data(), nullptr, dim) < 0) return -1;
+        const int k = slamhost_ekf_local_region(lp.x.data(), dim, (float) (c.MAX_RANGE + g_ekf_local), lp.feat.data(), lp.nf0);
+        if (k < 0) return -1;
+        lp.active.assign((size_t) lp.nf0, 0);
+        for (int i = 0; i < k; i++) lp.active[(size_t) lp.feat[i]] = 1;
+        lp.cx = lp.x[0];
+        lp.cy = lp.x[1];
+        if (int rcb = slamgpu_ekf_local_begin(ekf_dev, lp.feat.data(), k, std::max(room, g_ekf_local_new))) return rcb;
+        lp.open = true;
+        return 0;
+    };
     slamhost::GatedPolicy policy;
     FILE *alog = (gated && !c.s("assoclog").empty()) ? fopen(c.s("assoclog").c_str(), "w") : nullptr;
     std::vector<int> truth_of;
@@ -1566,9 +1621,32 @@ int main(int argc, char **argv) {
             }
             const float phi = (float) (sim.xTrue[2] + c.sigmaT * unif_rand());  // ekfslamwrapper.cpp:82
             if (ekf_dev) {
-                rc = slamgpu_ekf_sim(ekf_dev, sim.Vnoisy, sim.Gnoisy, sim.Qe, sim.dt, phi, sim.z.data(), sim.vis.data(), r == 1 ? (int32_t) sim.vis.size() : 0,
-                                     sim.Re, sim.R, r == 1);
+                const int32_t nz = r == 1 ? (int32_t) sim.vis.size() : 0;
+                if (g_ekf_local > 0.0) {  // a period is open around every step; it is closed first where the step would not fit into it
+                    bool fits = lp.open;
+                    if (fits && nz > 0 && ekf.associationKnown) {  // an observed id on a feature outside the region
+                        lp.looked.resize((size_t) nz);
+                        rc = slamgpu_ekf_lookup(ekf_dev, sim.vis.data(), nz, lp.looked.data());
+                        for (int32_t i = 0; i < nz && !rc; i++)
+                            if (lp.looked[i] >= 0 && lp.looked[i] < lp.nf0 && !lp.active[(size_t) lp.looked[i]]) fits = false;
+                    }
+                    if (fits && nz > 0 && !ekf.associationKnown) {  // the gates decide after the predict: room for every observation to be new
+                        int32_t info[6];
+                        rc = slamgpu_ekf_local_info(ekf_dev, info);
+                        if (!rc && info[2] + nz > info[3]) fits = false;
+                    }
+                    if (!rc && !fits) rc = local_end();
+                    if (!rc && !lp.open) rc = local_begin(nz);
+                }
+                if (!rc)
+                    rc = slamgpu_ekf_sim(ekf_dev, sim.Vnoisy, sim.Gnoisy, sim.Qe, sim.dt, phi, sim.z.data(), sim.vis.data(), nz, sim.Re, sim.R, r == 1);
+                if (rc == SLAMGPU_ERR_CAPACITY && lp.open && ekf.associationKnown) {  // the period is full (nothing was applied): the next one has room
+                    rc = local_end();
+                    if (!rc) rc = local_begin(nz);
+                    if (!rc) rc = slamgpu_ekf_sim(ekf_dev, sim.Vnoisy, sim.Gnoisy, sim.Qe, sim.dt, phi, sim.z.data(), sim.vis.data(), nz, sim.Re, sim.R, r == 1);
+                }
                 if (!rc) rc = slamgpu_ekf_pose(ekf_dev, est, nullptr);
+                if (!rc && lp.open && std::hypot(est[0] - lp.cx, est[1] - lp.cy) > 0.5 * g_ekf_local) rc = local_end();
                 if (rc) {
                     fprintf(stderr, "slamgpu: %s\n", slamgpu_last_error());
                     break;
@@ -1624,6 +1702,10 @@ int main(int argc, char **argv) {
         sq_err += (est[0] - sim.xTrue[0]) * (est[0] - sim.xTrue[0]) + (est[1] - sim.xTrue[1]) * (est[1] - sim.xTrue[1]);
         if (log) fprintf(log, "%ld,%.6f,%.6f,%.6f,%.6f,%.6f,%.6f,%.1f\n", iter, sim.xTrue[0], sim.xTrue[1], sim.xTrue[2], est[0], est[1], est[2], us);
     }
+    if (ekf_dev && !rc && local_end() != 0) {  // before anything reads the map
+        fprintf(stderr, "slamgpu: %s\n", slamgpu_last_error());
+        rc = -1;
+    }
     printf("control steps %ld, observation steps %ld, mean loop time %.1f us, rms position error %.4f m, final estimate (%.4f, %.4f, %.4f)\n",
            iter, nobs, iter ? sum_us / iter : 0.0, iter ? std::sqrt(sq_err / iter) : 0.0, est[0], est[1], est[2]);
     if (ctx && gated) {
@@ -1637,7 +1719,12 @@ int main(int argc, char **argv) {
     else if (ekf_dev) {
         int32_t st = 0;
         (void) slamgpu_ekf_status(ekf_dev, &st);
-        printf("landmarks in map: %d\n", (slamgpu_ekf_dim(ekf_dev) - 3) / 2);
+        int32_t info[6] = {};
+        (void) slamgpu_ekf_local_info(ekf_dev, info);
+        if (g_ekf_local > 0.0)
+            printf("landmarks in map: %d (local periods of MAX_RANGE + %g m: %d commits)\n", (slamgpu_ekf_dim(ekf_dev) - 3) / 2, g_ekf_local, info[5]);
+        else
+            printf("landmarks in map: %d\n", (slamgpu_ekf_dim(ekf_dev) - 3) / 2);
         if (st & SLAMGPU_EKF_STATUS_NOT_PD) printf("EKF on the device: a batch update was skipped (innovation covariance not positive definite)\n");
     } else printf("landmarks in map: %d\n", ekf.num_features());
     if (ctx) print_posterior_map(ctx, sim);

@@ -1,5 +1,6 @@
 """ctypes binding of the device EKF-SLAM filter (include/slamgpu.h: slamgpu_ekf_*), in the manner of capi.py: no fallback, a
 missing library or GPU is an error."""
+import contextlib
 import ctypes as C
 
 import numpy as np
@@ -40,6 +41,10 @@ def _lib():
         L.slamgpu_ekf_upload.argtypes = [vp, i32, vp, vp, i32]
         L.slamgpu_ekf_status.argtypes = [vp, C.POINTER(i32)]
         L.slamgpu_ekf_sync.argtypes = [vp]
+        L.slamgpu_ekf_local_begin.argtypes = [vp, vp, i32, i32]
+        L.slamgpu_ekf_local_end.argtypes = [vp]
+        L.slamgpu_ekf_local_info.argtypes = [vp, vp]
+        L.slamgpu_ekf_lookup.argtypes = [vp, vp, i32, vp]
         _bound = True
     return L
 
@@ -134,3 +139,33 @@ class EkfGpu:
 
     def sync(self):
         _chk(self.L.slamgpu_ekf_sync(self.h))
+
+    # ---- local periods (slamgpu_ekf_local_*): the stages above on an active set, one deferred commit ----------------------------
+    def local_begin(self, features, max_new=0):
+        """features: global feature indices, ascending and distinct; max_new: the features the period may create"""
+        f = np.ascontiguousarray(features, np.int32).reshape(-1)
+        _chk(self.L.slamgpu_ekf_local_begin(self.h, _ptr(f), f.shape[0], int(max_new)))
+
+    def local_end(self):
+        _chk(self.L.slamgpu_ekf_local_end(self.h))
+
+    def local_info(self):
+        out = np.zeros(6, np.int32)
+        _chk(self.L.slamgpu_ekf_local_info(self.h, _ptr(out)))
+        return dict(zip(("open", "k", "new", "max_new", "calls", "commits"), (int(v) for v in out)))
+
+    def lookup(self, ids):
+        """known association: the feature of each id, -1 not seen yet"""
+        ids = np.ascontiguousarray(ids, np.int32).reshape(-1)
+        out = np.zeros(ids.shape[0], np.int32)
+        _chk(self.L.slamgpu_ekf_lookup(self.h, _ptr(ids), ids.shape[0], _ptr(out)))
+        return out
+
+    @contextlib.contextmanager
+    def local(self, features, max_new=0):
+        """with ekf.local(features, max_new): ... -- the period is committed on the way out, also when the body raises"""
+        self.local_begin(features, max_new)
+        try:
+            yield self
+        finally:
+            self.local_end()

@@ -13,7 +13,7 @@ DECLARED_SYMBOLS = [
     "slamhost_sim_control_steps", "slamhost_gated_create", "slamhost_gated_destroy", "slamhost_gated_set", "slamhost_gated_step",
     "slamhost_gated_counts", "slamhost_draw_normals", "slamhost_draw_strata", "slamhost_unif_rand",
     "slamhost_synthetic_landmarks", "slamhost_write_map", "slamhost_ekf_create", "slamhost_ekf_destroy", "slamhost_ekf_step",
-    "slamhost_ekf_state", "slamhost_ekf_last_inputs", "slamhost_sim_noise", "slamhost_ekf_sim", "slamhost_ekf_upload", "slamhost_plot_open", "slamhost_plot_close", "slamhost_plot_xy", "slamhost_plot_matrix",
+    "slamhost_ekf_state", "slamhost_ekf_last_inputs", "slamhost_sim_noise", "slamhost_ekf_sim", "slamhost_ekf_upload", "slamhost_ekf_local_region", "slamhost_plot_open", "slamhost_plot_close", "slamhost_plot_xy", "slamhost_plot_matrix",
     "slamhost_plot_doubles", "slamhost_plot_car_size", "slamhost_plot_u32", "slamhost_plot_cmd", "slamhost_plot_name",
     "slamhost_map_candidates", "slamhost_map_merge", "slamhost_pose_nees", "slamhost_innovation_nis", "slamhost_joint_dense",
 ]
@@ -81,6 +81,7 @@ def load_library():
         L.slamhost_ekf_sim.argtypes = [C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_int32,
                                        C.c_void_p, C.c_void_p, C.c_int32]
         L.slamhost_ekf_upload.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32]
+        L.slamhost_ekf_local_region.argtypes = [C.c_void_p, C.c_int32, C.c_float, C.c_void_p, C.c_int32]
         L.slamhost_plot_open.restype = C.c_void_p
         L.slamhost_plot_open.argtypes = [C.c_char_p]
         L.slamhost_plot_close.argtypes = [C.c_void_p]
@@ -120,6 +121,18 @@ def draw_strata(N):
     out = np.zeros(N, np.float32)
     cnt = load_library().slamhost_draw_strata(N, _p(out))
     return cnt, out
+
+
+def ekf_local_region(x, radius, max_count=None):
+    """the features of the EKF-SLAM state x within radius of its pose estimate, ascending (slamhost_ekf_local_region); None if
+    there are more than max_count (default: room for all)"""
+    x = np.ascontiguousarray(x, np.float32).reshape(-1)
+    cap = (x.shape[0] - 3) // 2 if max_count is None else int(max_count)
+    out = np.zeros(max(cap, 1), np.int32)
+    n = load_library().slamhost_ekf_local_region(_p(x), x.shape[0], radius, _p(out), cap)
+    if n < -1:
+        raise ValueError("slamhost_ekf_local_region: bad arguments")
+    return None if n < 0 else out[:n].copy()
 
 
 def synthetic_landmarks(seed, n, x0, x1, y0, y1):

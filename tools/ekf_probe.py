@@ -2,6 +2,10 @@
 BASELINE config 5.  Appends to profiles/ekf.txt (or --out).
 
     python tools/ekf_probe.py [--out profiles/ekf.txt] [--no-small] [--no-large] [--no-kernels] [--max-range 20] [--obs-steps 200]
+    python tools/ekf_probe.py --local 20 [--local-new 64] [--max-range 20] [--obs-steps 2172] [--out profiles/ekf_local.txt]
+
+--local margin: the config-5-size course once through the full filter and once in local periods (slamgpu_ekf_local_*) under the policy
+of slam-backend -EKF_LOCAL margin, the two printed side by side; nothing else runs.
 
 Times are wall-clock around a region that ends in slamgpu_ekf_sync, after one untimed pass over the same calls; a kernel's own
 time is that of a region holding nothing else (the update chunk: four kernels, so its rate is a LOWER bound on ekf_syrk_kernel's).
@@ -152,6 +156,123 @@ def large(slam_amd, host, max_range, obs_steps, kernels, say):
         sim.close()
 
 
+class LocalPolicy:
+    """slam-backend -EKF_LOCAL margin, in Python: the region is the features within MAX_RANGE + margin of the estimate at begin; the period
+    ends when the estimate is more than margin / 2 from there, when an observed id is on a passive feature, or when it is full"""
+
+    def __init__(self, dev, host, max_range, margin, max_new):
+        self.dev, self.host, self.radius, self.margin, self.max_new = dev, host, max_range + margin, margin, max_new
+        self.open, self.sizes, self.t_commit = False, [], 0.0
+
+    def begin(self, room):
+        x, _ = self.dev.state(want_P=False)
+        feats = self.host.ekf_local_region(x, self.radius)
+        self.nf0, self.centre = (x.shape[0] - 3) // 2, x[:2].astype(np.float64)
+        self.active = np.zeros(max(self.nf0, 1), bool)
+        self.active[feats] = True
+        self.dev.local_begin(feats, max(room, self.max_new))
+        self.sizes.append(3 + 2 * feats.shape[0])
+        self.open = True
+
+    def end(self):
+        if not self.open:
+            return
+        self.dev.sync()
+        t0 = time.perf_counter()
+        self.dev.local_end()
+        self.dev.sync()
+        self.t_commit += time.perf_counter() - t0
+        self.open = False
+
+    def sim(self, slam_amd, *args):
+        vis, ob = args[6], args[9]
+        nz = len(vis) if ob else 0
+        if self.open and nz:
+            f = self.dev.lookup(vis)
+            f = f[(f >= 0) & (f < self.nf0)]
+            if not self.active[f].all():
+                self.end()
+        if not self.open:
+            self.begin(nz)
+        try:
+            self.dev.sim(*args)
+        except slam_amd.SlamGpuError as e:
+            if e.code != -3:
+                raise
+            self.end()  # the period is full, nothing was applied: the next one has room
+            self.begin(nz)
+            self.dev.sim(*args)
+        if ob:
+            xyt, _ = self.dev.pose()
+            if np.hypot(*(xyt[:2] - self.centre)) > 0.5 * self.margin:
+                self.end()
+
+
+def local_course(slam_amd, host, max_range, obs_steps, margin, max_new, say):
+    """the config-5-size course, recorded once, through the full filter and through local periods"""
+    nlm = 10000
+    lm = host.synthetic_landmarks(12345, nlm, -130, 100, -100, 90)
+    s0 = host.HostSim(["-m", os.path.join(ROOT, "data", "example_webmap.mat"), "-method", "EKF1"])
+    _, wp = s0.map()
+    s0.close()
+    with tempfile.TemporaryDirectory() as wd:
+        mp = os.path.join(wd, "synthetic10k.mat")
+        host.write_map(mp, lm, wp)
+        open(os.path.join(wd, "synthetic10k.ini"), "w").write(open(os.path.join(ROOT, "data", "example_webmap.ini")).read())
+        sim = host.HostSim(["-m", mp, "-method", "EKF1", "-SWITCH_SEED_RANDOM", 7, "-MAX_RANGE", max_range, "-SWITCH_ASSOCIATION_KNOWN", 1])
+        nz = sim.sim_noise()
+        course, nobs = [], 0
+        while nobs < obs_steps:
+            r, V, G, phi = sim.control()
+            if r < 0:
+                break
+            z, vis = (np.zeros((0, 2), f32), np.zeros(0, np.int32))
+            if r == 1:
+                sim.observe(0)
+                z, vis = sim.last_z()
+                nobs += 1
+            course.append((V, G, nz["Qe"], nz["dt"], phi, z, vis, nz["Re"], nz["R"], r))
+        truth = sim.true_pose()
+        conf = sim.conf
+        sim.close()
+    say("config-5-size course: 10 000-landmark synthetic map, MAX_RANGE %g, known association, %d control steps, %d observation steps" %
+        (max_range, len(course), nobs))
+    finals = []
+    for mode in ("full filter", "local periods, margin %g m, max_new %d" % (margin, max_new)):
+        dev = dev_for(slam_amd, conf, nlm)
+        pol = LocalPolicy(dev, host, max_range, margin, max_new) if mode != "full filter" else None
+        table, t_obs, t0_all = {}, 0.0, time.perf_counter()
+        for args in course:
+            t0 = time.perf_counter()
+            if pol:
+                pol.sim(slam_amd, *args)
+            else:
+                dev.sim(*args)
+            if args[9]:
+                dev.sync()
+                t_obs += time.perf_counter() - t0
+                for i in args[6]:
+                    table.setdefault(int(i), len(table))
+        if pol:
+            pol.end()
+        dev.sync()
+        wall = time.perf_counter() - t0_all
+        x, _ = dev.state(want_P=False)
+        ids = np.array(sorted(table, key=table.get))
+        err = np.hypot(x[3::2] - lm[0, ids], x[4::2] - lm[1, ids])
+        say("  %s:" % mode)
+        say("    %.2f ms per observation step (synchronised%s), %.1f s wall in all" % (1e3 * t_obs / max(nobs, 1), ", commits included" if pol else "", wall))
+        if pol:
+            n = dev.local_info()["commits"]
+            say("    %d commits, %.2f ms per commit (synchronised); active state |A| at begin: mean %.0f, largest %d of dim %d" %
+                (n, 1e3 * pol.t_commit / max(n, 1), np.mean(pol.sizes), max(pol.sizes), x.shape[0]))
+        say("    %d landmarks mapped (dim %d), mean landmark error %.3f m (max %.3f), pose error %.3f m, status %d" %
+            ((x.shape[0] - 3) // 2, x.shape[0], err.mean(), err.max(), float(np.hypot(*(x[:2] - truth[:2]))), dev.status()))
+        finals.append(x)
+        dev.close()
+    say("  largest |x_local - x_full| at the end: %.3e (pose %.3e)" % (np.abs(finals[1] - finals[0]).max(), np.abs(finals[1][:3] - finals[0][:3]).max()))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "ekf.txt"))
@@ -160,6 +281,8 @@ def main():
     ap.add_argument("--no-kernels", action="store_true", help="skip the full-size kernels (D = 20 003)")
     ap.add_argument("--max-range", type=float, default=20.0)
     ap.add_argument("--obs-steps", type=int, default=200)
+    ap.add_argument("--local", type=float, default=0.0, metavar="MARGIN", help="the config-5-size course through local periods beside the full filter")
+    ap.add_argument("--local-new", type=int, default=64, help="with --local: the features a period may create")
     a = ap.parse_args()
     import slam_amd
     from slam_amd import host
@@ -174,6 +297,9 @@ def main():
         out.flush()
 
     say("# tools/ekf_probe.py")
+    if a.local > 0.0:
+        local_course(slam_amd, host, a.max_range, a.obs_steps, a.local, a.local_new, say)
+        return
     if not a.no_small:
         small_map(slam_amd, host, "example_webmap", 7, 10 ** 9, say)
         small_map(slam_amd, host, "example_loop902", 3, 2000, say)
