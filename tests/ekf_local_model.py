@@ -21,6 +21,7 @@ Q = np.array([[0.3 ** 2, 0], [0, (3.0 * np.pi / 180) ** 2]], np.float32)
 R = np.array([[0.1 ** 2, 0], [0, (1.0 * np.pi / 180) ** 2]], np.float32)
 DT = float(np.float32(0.025))
 CONF = dict(wheel_base=4.0, sigma_phi=0.0087, gate_reject=4.0, gate_augment=25.0)
+CHUNK = 64  # the device's chunk of a batch update (ekf_helpers.h: kChunk)
 
 
 class Invalid(Exception):
@@ -42,6 +43,7 @@ class _Ext(EkfModel):
 
 class EkfLocalModel:
     def __init__(self, **kw):
+        """kw: EkfModel's, chunk and dtype among them: the full filter and every period's extended one are built from the same"""
         self.kw = kw
         self.full = EkfModel(**kw)
         self.ext = None
@@ -231,11 +233,12 @@ def observations(x, idf, rng, noise=1.0):
 
 def build_script(x0, P0, periods, use_heading, seed):
     """The stage calls of a run, made while a float64 full EkfModel runs them (it is where the observations come from); returns
-    (script, that model).  periods: dicts of features (global, ascending), max_new, steps, m (observations of active features per
+    (script, that model).  The model applies an update in the device's chunks (ekf_model.py: chunk=64, each chunk linearised where the
+    previous one left the state; up to 64 observations that is the one batch).  periods: dicts of features (global, ascending), max_new, steps, m (observations of active features per
     step; those the period created are always among them), new (features created at step s: new[s], 0 beyond the list).  A script
     entry is (name, args); begin / end are skipped by a filter without periods"""
     rng = np.random.default_rng(seed)
-    ref = EkfModel(use_heading=use_heading, association_known=True, **CONF)
+    ref = EkfModel(chunk=CHUNK, use_heading=use_heading, association_known=True, **CONF)
     ref.upload(x0, P0)
     script = []
     for p in periods:
@@ -264,6 +267,26 @@ def build_script(x0, P0, periods, use_heading, seed):
                 ref.augment(zn, R)
         script.append(("end", ()))
     return script, ref
+
+
+BLOCKS = ("P[A,A]", "P[A,B]", "P[B,B]", "x_A", "x_B")
+
+
+def blocks_of(script, dim0, dim):
+    """(A, B) of a script of ONE period that opens on a state of dimension dim0 and leaves one of dimension dim: the state entries of
+    the pose, the begin entry's features and the features created since, and the rest"""
+    begins = [a for n, a in script if n == "begin"]
+    assert len(begins) == 1
+    f = np.asarray(begins[0][0], np.int64)
+    A = np.concatenate([np.arange(3), np.stack([3 + 2 * f, 4 + 2 * f], axis=1).reshape(-1), np.arange(dim0, dim)]).astype(np.int64)
+    return A, np.setdiff1d(np.arange(dim0), A)
+
+
+def block_errors(x, P, xm, Pm, A, B):
+    """{block: max |difference| over the block relative to the model's largest magnitude IN that block}, empty blocks left out"""
+    parts = {"P[A,A]": (P[np.ix_(A, A)], Pm[np.ix_(A, A)]), "P[A,B]": (P[np.ix_(A, B)], Pm[np.ix_(A, B)]),
+             "P[B,B]": (P[np.ix_(B, B)], Pm[np.ix_(B, B)]), "x_A": (x[A], xm[A]), "x_B": (x[B], xm[B])}
+    return {name: float(np.abs(got - want).max() / np.abs(want).max()) for name, (got, want) in parts.items() if want.size}
 
 
 def drive(f, script, periods=True):

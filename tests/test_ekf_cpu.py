@@ -119,6 +119,30 @@ def test_scale_packet_is_decided_clearly_by_the_float64_model(nf):
     assert (l0 == -1).all() and np.isinf(m0).all()
 
 
+@pytest.mark.parametrize("which", ["odd", "tail"])
+def test_scale_packet_inside_a_period_is_decided_clearly_by_the_float64_model(which):
+    """The same packet through the gates of a local period of 600 landmarks' odd features (k 300) and of features 257 .. 599 (k 343),
+    as tests/test_gpu_ekf_local_scale.py sends it, judged by the float64 local model: at most 2 unclear decisions, at least 40 / 30
+    matches, at least 5 winners at a local index of 256 or more, at least 20 labels that differ from the full map's for the same
+    reading, and in the odd-feature period, whose labels that file applies, room for every new landmark
+    (test_gpu_ekf_local_scale.period_caps).  The float32 local model labels every clear decision
+    alike, and a label is a feature of the period, by its global index"""
+    import ekf_local_model as LM
+    from test_gpu_ekf_local_scale import MAX_NEW, period_caps, period_study
+    from test_gpu_ekf_scale import GATES, RE
+    p = period_study(which)
+    matches, past, differ = period_caps(p)
+    lab, margin, clear, feats = p["lab"], p["margin"], p["clear"], p["feats"]
+    print("EKF local scale packet, %s features (k %d): unclear %d, smallest margin %.1e, match / new / discard %d / %d / %d, local index >= 256: %d, "
+          "differ from the full map's: %d" % (which, feats.shape[0], (~clear).sum(), margin.min(), matches, (lab == -1).sum(), (lab == -2).sum(), past, differ))
+    assert lab.shape == (64,) and np.isfinite(margin).all() and (margin >= 0).all()
+    assert np.isin(lab[lab >= 0], feats).all()
+    m32 = LM.EkfLocalModel(dtype=f32, **GATES)
+    m32.upload(p["x0"], p["P0"])
+    m32.local_begin(feats, MAX_NEW)
+    assert np.array_equal(m32.associate(p["z"], RE)[clear], lab[clear])
+
+
 EKF_SYMBOLS = ["slamgpu_ekf_create", "slamgpu_ekf_destroy", "slamgpu_ekf_sim", "slamgpu_ekf_predict", "slamgpu_ekf_observe_heading",
                "slamgpu_ekf_associate", "slamgpu_ekf_update", "slamgpu_ekf_augment", "slamgpu_ekf_dim", "slamgpu_ekf_pose", "slamgpu_ekf_state",
                "slamgpu_ekf_block", "slamgpu_ekf_upload", "slamgpu_ekf_status", "slamgpu_ekf_sync"]

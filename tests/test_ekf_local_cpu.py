@@ -1,7 +1,8 @@
 """Local periods of the device EKF (include/slamgpu.h: slamgpu_ekf_local_*), what can be checked without a GPU:
   1. the algebra: the float64 local model with its commit (tests/ekf_local_model.py) against the float64 full EkfModel on the same
      stage calls, max abs difference <= 1e-12 x scale (the heading update's eps on the passive diagonal, 2.2e-16 per update, is the
-     only term the two do not share);
+     only term the two do not share), both with the device's chunks of 64 observations, up to three chunks per update; and the
+     per-block error rule of tests/test_gpu_ekf_local_scale.py on an ideal device and on wrong tiles;
   2. slamhost_ekf_local_region against numpy, the radius boundary and the overflow included;
   3. the symbols, the binding, the backend's refusals, and the new unit compiled for gfx950 without scratch."""
 import os
@@ -27,6 +28,8 @@ CASES = {
     "new_reobserved": (10, False, [dict(features=[0, 2, 7], max_new=3, steps=5, m=2, new=[1, 0, 2])]),
     "two_periods": (12, True, [dict(features=[0, 5, 6], max_new=2, steps=4, m=2, new=[2]),
                                dict(features=[3, 6, 11, 12, 13], max_new=1, steps=4, m=4, new=[0, 1])]),
+    # 135, then 136 observations per update: three chunks of the device's rule (64, 64, 7 and 8), both models with chunk = 64
+    "three_chunks": (150, True, [dict(features=list(range(5, 145)), max_new=1, steps=2, m=135, new=[1])]),
 }
 
 
@@ -40,7 +43,9 @@ def test_local_model_is_the_full_filter(name):
         assert {n for n, _ in script} == {"begin", "predict", "end"}
     if name in ("new_reobserved", "two_periods"):  # a feature the period (or the one before) created is observed again
         assert any(n == "update" and (a[1] >= nf).any() for n, a in script)
-    loc = LM.EkfLocalModel(use_heading=heading, association_known=True, **LM.CONF)
+    if name == "three_chunks":
+        assert ref.chunk == LM.CHUNK and [a[1].shape[0] for n, a in script if n == "update"] == [135, 136]
+    loc = LM.EkfLocalModel(chunk=LM.CHUNK, use_heading=heading, association_known=True, **LM.CONF)
     loc.upload(x0, P0)
     LM.drive(loc, script)
     assert loc.commits == len(periods) and loc.dim == ref.dim
@@ -48,6 +53,50 @@ def test_local_model_is_the_full_filter(name):
     print("local model %s: dim %d, max |dx| %.3e, max |dP| %.3e" % (name, ref.dim, dx, dP))
     assert dx <= 1e-12 * np.abs(ref.x).max() and dP <= 1e-12 * np.abs(ref.P).max(), (dx, dP)
     assert not np.array_equal(ref.P[:3, 3 + 2 * nf - 2:3 + 2 * nf], P0[:3, -2:])  # the passive part did move
+
+
+@pytest.mark.parametrize("nf,k,heading,steps,m,new", [(128, 14, True, 4, 10, [0, 3]), (130, 15, False, 5, 15, [1]), (130, 70, True, 3, 65, [3])])
+def test_block_rule_passes_an_ideal_device_and_catches_a_wrong_tile(nf, k, heading, steps, m, new):
+    """The per-block rule of tests/test_gpu_ekf_local_scale.py on shapes of tests/test_gpu_ekf_local.py, without a device: the float64
+    local model's result rounded ONCE to float32 stands for an ideal device, the float32 full EkfModel with the device's chunks for
+    the yardstick, the float64 full model is the reference.  The ideal device meets the rule in all five blocks; a 16 x 16 tile of a
+    block that is 1 % wrong, or left as it was uploaded, misses its block's bound tenfold or more (P[A,B], whose float32 yardstick is 2e-5 .. 9e-5 of the
+    block's largest entry, at the least by 29 times)"""
+    from test_gpu_ekf_local import FACTOR, FLOOR, features_of, within
+    x0, P0 = LM.synthetic_state(nf, 7 * nf + k)
+    feats = features_of(nf, k, np.random.default_rng(100 * nf + k))
+    script, ref = LM.build_script(x0, P0, [dict(features=feats, max_new=sum(new), steps=steps, m=m, new=new)], heading, 9 * nf + k)
+    loc = LM.EkfLocalModel(chunk=LM.CHUNK, use_heading=heading, association_known=True, **LM.CONF)
+    yard = LM.EkfModel(dtype=f32, chunk=LM.CHUNK, use_heading=heading, association_known=True, **LM.CONF)
+    for f in (loc, yard):
+        f.upload(x0, P0)
+    LM.drive(loc, script)
+    LM.drive(yard, script, periods=False)
+    A, B = LM.blocks_of(script, x0.shape[0], ref.dim)
+    assert A.shape[0] == 3 + 2 * (k + sum(new)) and B.shape[0] == 2 * (nf - k) and np.array_equal(np.sort(np.concatenate([A, B])), np.arange(ref.dim))
+    x, P = loc.x.astype(f32), loc.P.astype(f32)
+    ey = LM.block_errors(yard.x, yard.P, ref.x, ref.P, A, B)
+    ei = LM.block_errors(x, P, ref.x, ref.P, A, B)
+    print("ideal device nf %d k %d: " % (nf, k) + ", ".join("%s %.3e against %.3e" % (b, ei[b], ey[b]) for b in LM.BLOCKS))
+    assert set(ei) == set(LM.BLOCKS)
+    for b in LM.BLOCKS:
+        assert within(ei[b], ey[b]), (b, ei[b], ey[b])
+    D0 = x0.shape[0]
+    for b, (I, J) in (("P[A,A]", (A, A)), ("P[A,B]", (A, B)), ("P[B,B]", (B, B))):
+        blk = ref.P[np.ix_(I, J)]
+        i, j = np.unravel_index(np.abs(blk).argmax(), blk.shape)  # the tile that holds the block's largest entry
+        i, j = min(i // 16 * 16, len(I) - 16), min(j // 16 * 16, len(J) - 16)
+        rows, cols = I[i:i + 16], J[j:j + 16]
+        for what in ("1 % wrong", "stale"):
+            Pw = P.copy()
+            if what == "stale":
+                if rows.max() >= D0 or cols.max() >= D0:
+                    continue
+                Pw[np.ix_(rows, cols)] = P0[np.ix_(rows, cols)]
+            else:
+                Pw[np.ix_(rows, cols)] *= f32(1.01)
+            e = LM.block_errors(x, Pw, ref.x, ref.P, A, B)[b]
+            assert e >= 10.0 * max(FACTOR * ey[b], FLOOR), (b, what, e, ey[b])
 
 
 def test_local_model_contract():

@@ -1,5 +1,5 @@
 """Local periods of the device EKF (include/slamgpu.h: slamgpu_ekf_local_*; slam_amd/csrc/ekf_local.cpp) on the GPU.
-The reference is the float64 full EkfModel (tests/ekf_model.py), the yardstick the full device filter -- the same handle type without
+The reference is the float64 full EkfModel (tests/ekf_model.py) with the device's chunks of 64 observations, the yardstick the full device filter -- the same handle type without
 a period -- from the same uploaded state and the same stage calls, and the rule the one of tests/test_gpu_ekf.py: the local filter's
 error is at most max(4 x the full device filter's error, 8 * 2^-24), x relative to max |x| and P relative to max |P|.  The factor was
 fixed before anything was measured; the measured ratios are in profiles/ekf_local.txt (worst 1.00; with psi kept in float32 the
@@ -49,8 +49,9 @@ def features_of(nf, k, rng):
     return np.sort(np.concatenate([ends, rest]).astype(np.int64))
 
 
-def run_both(tag, x0, P0, periods, heading, seed, cap):
-    """the script on a local and on a full device filter; the 4 x rule, symmetry and the dimension after the last commit"""
+def run_both(tag, x0, P0, periods, heading, seed, cap, out=None):
+    """the script on a local and on a full device filter; the 4 x rule, symmetry and the dimension after the last commit.  A dict
+    `out` is given the script, the model and the full device filter's state before the rule is asserted"""
     script, ref = LM.build_script(x0, P0, periods, heading, seed)
     loc, full = (make_dev(cap, use_heading=heading, association_known=True) for _ in range(2))
     for d in (loc, full):
@@ -66,6 +67,8 @@ def run_both(tag, x0, P0, periods, heading, seed, cap):
     assert symmetric(Pl) and symmetric(Pf)
     lx, lP = errors(xl, Pl, ref.x, ref.P)
     fx, fP = errors(xf, Pf, ref.x, ref.P)
+    if out is not None:
+        out.update(script=script, ref=ref, local=(xl, Pl), full=(xf, Pf))
     print("EKF local %s: dim %d, local x %.3e P %.3e, full device x %.3e P %.3e, ratio x %.3f P %.3f" %
           (tag, ref.dim, lx, lP, fx, fP, lx / max(fx, FLOOR / FACTOR), lP / max(fP, FLOOR / FACTOR)))
     assert within(lx, fx) and within(lP, fP), (lx, fx, lP, fP)
