@@ -1257,6 +1257,31 @@ int slamgpu_ekf_local_end(slamgpu_ekf *e);
 int slamgpu_ekf_local_info(slamgpu_ekf *e, int32_t out[6]);
 int slamgpu_ekf_lookup(slamgpu_ekf *e, const int32_t *ids, int32_t n, int32_t *features_out);
 
+/* ---- EKF-SLAM on the device, continued: features taken out in place, and per-feature counts.  STABLE.
+ * Deleting a feature's entries from x and its rows and columns from P is exact marginalisation of a Gaussian: no approximation.
+ * remove: features[k] are global feature indices, ascending and distinct, each in [0, nf).  With src the ascending list of the
+ *      surviving state indices (0, 1, 2, then the two entries of every kept feature), dim' = dim - 2 k and s0 = 3 + 2 features[0]:
+ *        x'[i]    = x[src[i]]
+ *        P'[i][j] = P[src[max(i, j)]][src[min(i, j)]]   wherever max(i, j) >= s0
+ *      that is the gather of the LOWER triangle, mirrored: over everything that moves P' == P'^T bit for bit whatever was uploaded
+ *      (for the symmetric P every other call leaves it is simply P[src[i]][src[j]]).  Entries with both indices below s0 do not
+ *      move and are not touched.  Rows and columns [dim', dim) of P and x[dim', dim) are zero afterwards; nothing at or beyond the
+ *      old dim is touched.  The surviving features keep their order: feature f becomes f - #{removed < f}.  In place, no second P:
+ *      one read and one write of the moved region.  Removing only the last features moves nothing and zeroes the strip.
+ *      Enqueued on the handle's stream; does not wait for the device.  k = 0 does nothing and launches nothing.  The sticky status
+ *      bits stay.  With association_known a removed feature's id is unknown again (lookup: -1; the next sim that sees it creates a
+ *      feature at the end) and the other ids follow their features.  The counts below are compacted with the features.
+ *      SLAMGPU_ERR_INVALID with nothing applied: NULL features with k > 0, k < 0, an index out of range, a list that is not ascending
+ *      and distinct, a local period open (the passive part of P is stale there: end the period first).
+ * feature_stats: host-side counts, no device work; any output may be NULL, the arrays hold nf entries; returns nf.
+ *      epoch counts every successful sim with observe != 0 and every successful direct update (sim's own update stage does not
+ *      count twice).  born[f]: the epoch at which f was appended (inside sim: that sim's; a direct augment: the epoch as it
+ *      stands).  hits[f]: the observations handed to the update stage for f, by global index, inside a local period too; with
+ *      batch_update == 0 sim's update stage does not run and hits stays 0.  last[f]: the epoch of the latest of them, else born[f].
+ *      upload: hits = 0 and born = last = epoch for the uploaded features. */
+int slamgpu_ekf_remove(slamgpu_ekf *e, const int32_t *features, int32_t k);
+int slamgpu_ekf_feature_stats(slamgpu_ekf *e, int32_t *hits, int32_t *born, int32_t *last, int32_t *epoch);
+
 #ifdef __cplusplus
 }
 #endif

@@ -72,6 +72,14 @@ int slamhost_sim_noise(const slamhost_sim *s, float Q[4], float R[4], float Qe[4
 int slamhost_ekf_sim(slamhost_ekf *e, float V, float G, const float Q[4], float dt, float phi, const float *z, const int32_t *ids, int32_t nz,
                      const float Re[4], const float R[4], int32_t observe);
 int slamhost_ekf_upload(slamhost_ekf *e, int32_t dim, const float *x, const float *P, int32_t ld);
+/* The twins of slamgpu_ekf_remove and slamgpu_ekf_feature_stats (slamgpu.h has the index map and the counters' rules) on the host
+ * filter.  remove: features[k] ascending and distinct in [0, nf); x and P become the gather over the surviving indices -- P from its
+ * LOWER triangle, mirrored, wherever an index at or beyond the first removed entry is involved, the rest as it was -- the id table
+ * forgets the removed features' ids and renumbers the others, the counters are compacted; 0, or -1 for bad arguments with nothing
+ * applied.  feature_stats: any output may be NULL, arrays [nf]; returns nf.  The host filter has no direct update: its epoch counts
+ * the sim / step calls with an observation. */
+int slamhost_ekf_remove(slamhost_ekf *e, const int32_t *features, int32_t k);
+int slamhost_ekf_feature_stats(const slamhost_ekf *e, int32_t *hits, int32_t *born, int32_t *last, int32_t *epoch);
 /* The region of a local period of the device filter (slamgpu.h: slamgpu_ekf_local_begin): the features of the EKF-SLAM state x[dim]
  * (dim = 3 + 2 nf) whose estimate lies within `radius` of the pose estimate (x[0], x[1]) -- dx dx + dy dy <= radius radius in float32,
  * the boundary included -- ascending into features_out[max_count].  Returns their number, -1 if there are more than max_count

@@ -39,6 +39,7 @@ DECLARED_SYMBOLS = [
     "slamgpu_ekf_create", "slamgpu_ekf_destroy", "slamgpu_ekf_sim", "slamgpu_ekf_predict", "slamgpu_ekf_observe_heading", "slamgpu_ekf_associate",
     "slamgpu_ekf_update", "slamgpu_ekf_augment", "slamgpu_ekf_dim", "slamgpu_ekf_pose", "slamgpu_ekf_state", "slamgpu_ekf_block", "slamgpu_ekf_upload",
     "slamgpu_ekf_status", "slamgpu_ekf_sync", "slamgpu_ekf_local_begin", "slamgpu_ekf_local_end", "slamgpu_ekf_local_info", "slamgpu_ekf_lookup",
+    "slamgpu_ekf_remove", "slamgpu_ekf_feature_stats",
     "slamgpu_ens_create", "slamgpu_ens_destroy", "slamgpu_ens_sync", "slamgpu_ens_sim", "slamgpu_ens_sim_noise",
     "slamgpu_ens_last_inputs", "slamgpu_ens_dims", "slamgpu_ens_poses", "slamgpu_ens_state", "slamgpu_ens_slab",
     "slamgpu_ens_upload", "slamgpu_ens_status", "slamgpu_ens_consistency", "slamgpu_ens_consistency_reset",

@@ -9,6 +9,7 @@
 namespace {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));  // (one 16-byte access in the IR: a float4 is four floats there, and their stores get regrouped)
 
 // a chunk of the batch update, by value
 struct EkfObs {
@@ -256,6 +257,154 @@ __global__ void __launch_bounds__(kEkfBlock) ekf_block_kernel(const float *__res
     out[e] = P[(size_t) idx[a] * ld + idx[b]];
 }
 
+// slamgpu_ekf_remove: P'[i][j] = P[src[max(i, j)]][src[min(i, j)]] IN PLACE, n = dim' rows, nothing below s0 moves.  Two transposing
+// copies of kRmTile x kRmTile tiles through LDS, the second launched after the first:
+//   gather: reads the strict LOWER triangle of the old P, writes the strict UPPER triangle of the new one at columns >= s0
+//   mirror: reads that upper triangle, writes the strict lower triangle at rows >= s0
+// In both the entries read and the entries written are disjoint sets, so the workgroups of a launch need no order among themselves.
+// The diagonal and x, which would be read and written in the same triangle, wait in the heading update's scratch vectors in between.
+constexpr int kRmTile = 64;
+
+// a lane's place in a tile pass: four consecutive columns c, c + 1, c + 2, c + 3 of row r0 (+ 16 per pass).  A 32-lane half holds 8
+// quads x 4 rows, so that with the row stride kRmTile + 1 its 32 reads t[c + e][r] (bank c + e + r mod 32) and its 32 writes
+// t[r][c + e] (bank r + c + e mod 32) each fall on 32 different banks
+struct RmLane {
+    int c, r0;
+    __device__ explicit RmLane(int tid) : c(4 * ((tid & 7) + 8 * ((tid >> 5) & 1))), r0(((tid & 31) >> 3) + 4 * (tid >> 6)) {}
+};
+
+// the entries of the new P a phase writes: the gather (i, j) with i < j and s0 <= j < n, the mirror (i, j) with j < i and s0 <= i < n
+template <bool kUpper>
+__device__ inline bool rm_writes(int i, int j, int s0, int n) {
+    return kUpper ? (i < j && j >= s0 && j < n) : (j < i && i >= s0 && i < n);
+}
+
+// ... and the tiles every entry of which is one: strictly off the diagonal and wholly inside [s0, n) on the side that counts.  Their
+// workgroups take the paths without a test, where all of a lane's loads are in flight together
+template <bool kUpper>
+__device__ inline bool rm_full_tile(int bi, int bj, int s0, int n) {
+    const int b = kUpper ? bj : bi;
+    return bi != bj && b * kRmTile >= s0 && (b + 1) * kRmTile <= n;
+}
+
+// the tile in LDS, t[a][b] = what belongs at row I0 + b, column J0 + a, out to P along its rows: 16 bytes per lane where the four
+// entries are all the phase's (J0 is a multiple of 4 and so is ld)
+template <bool kUpper>
+__device__ inline void rm_store_tile(float *__restrict__ P, int ld, const float (*t)[kRmTile + 1], int I0, int J0, int s0, int n, int tid, bool full) {
+    const RmLane L(tid);
+    const int j = J0 + L.c;
+#pragma unroll
+    for (int pass = 0; pass < 4; pass++) {
+        const int r = L.r0 + 16 * pass, i = I0 + r;
+        const float v0 = t[L.c][r], v1 = t[L.c + 1][r], v2 = t[L.c + 2][r], v3 = t[L.c + 3][r];
+        float *row = P + (size_t) i * ld + j;
+        if (full || (rm_writes<kUpper>(i, j, s0, n) && rm_writes<kUpper>(i, j + 3, s0, n))) {
+            *reinterpret_cast<f32x4 *>(row) = f32x4{v0, v1, v2, v3};
+        } else {
+            if (rm_writes<kUpper>(i, j, s0, n)) row[0] = v0;
+            if (rm_writes<kUpper>(i, j + 1, s0, n)) row[1] = v1;
+            if (rm_writes<kUpper>(i, j + 2, s0, n)) row[2] = v2;
+            if (rm_writes<kUpper>(i, j + 3, s0, n)) row[3] = v3;
+        }
+    }
+}
+
+// ... the gather.  Tile (bi, bj) of the new upper triangle, column tiles from jb0 = s0 / kRmTile on: row src[j] of the old P at the
+// columns src[I0 ..], a few contiguous runs, a lane per column.  The workgroups of the diagonal tiles also save the diagonal and x
+__global__ void __launch_bounds__(kEkfBlock) ekf_remove_gather_kernel(float *__restrict__ P, int ld, int n, int s0, int jb0, const int32_t *__restrict__ src,
+                                                                       const float *__restrict__ x, float *__restrict__ diag, float *__restrict__ xs) {
+    const int bi = blockIdx.y, bj = jb0 + blockIdx.x;
+    if (bi > bj) return;
+    __shared__ float t[kRmTile][kRmTile + 1];
+    const int tid = threadIdx.x, lane = tid & 63, I0 = bi * kRmTile, J0 = bj * kRmTile;
+    const int i = I0 + lane;
+    const int sc = i < n ? src[i] : 0;
+    const bool full = rm_full_tile<true>(bi, bj, s0, n);
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);  // (the wave's rows src[j] are the same for its lanes: scalar loads)
+    if (full) {
+        float v[kRmTile / 4];
+#pragma unroll
+        for (int pass = 0; pass < kRmTile / 4; pass++) v[pass] = P[(size_t) src[J0 + wave + 4 * pass] * ld + sc];
+#pragma unroll
+        for (int pass = 0; pass < kRmTile / 4; pass++) t[wave + 4 * pass][lane] = v[pass];
+    } else {
+#pragma unroll
+        for (int pass = 0; pass < kRmTile / 4; pass++) {
+            const int a = wave + 4 * pass, j = J0 + a;
+            if (rm_writes<true>(i, j, s0, n)) t[a][lane] = P[(size_t) src[j] * ld + sc];
+        }
+    }
+    if (bi == bj && tid < kRmTile && i >= s0 && i < n) {
+        diag[i] = P[(size_t) sc * ld + sc];
+        xs[i] = x[sc];
+    }
+    __syncthreads();
+    rm_store_tile<true>(P, ld, t, I0, J0, s0, n, tid, full);
+}
+
+// ... the mirror.  Tile (bi, bj) of the new lower triangle, row tiles from ib0 = s0 / kRmTile on: rows J0 .. of the upper triangle at
+// the columns I0 .., 16 bytes per lane where the four entries are all the phase's.  The diagonal tiles put the diagonal and x back
+__global__ void __launch_bounds__(kEkfBlock) ekf_remove_mirror_kernel(float *__restrict__ P, int ld, int n, int s0, int ib0, float *__restrict__ x,
+                                                                       const float *__restrict__ diag, const float *__restrict__ xs) {
+    const int bi = ib0 + blockIdx.y, bj = blockIdx.x;
+    if (bj > bi) return;
+    __shared__ float t[kRmTile][kRmTile + 1];
+    const int tid = threadIdx.x, I0 = bi * kRmTile, J0 = bj * kRmTile;
+    const RmLane L(tid);
+    const int i = I0 + L.c;
+    const bool full = rm_full_tile<false>(bi, bj, s0, n);
+    if (full) {
+        f32x4 v[4];
+#pragma unroll
+        for (int pass = 0; pass < 4; pass++) v[pass] = *reinterpret_cast<const f32x4 *>(P + (size_t) (J0 + L.r0 + 16 * pass) * ld + i);
+#pragma unroll
+        for (int pass = 0; pass < 4; pass++) {
+            float *at = &t[L.r0 + 16 * pass][L.c];
+            at[0] = v[pass].x;
+            at[1] = v[pass].y;
+            at[2] = v[pass].z;
+            at[3] = v[pass].w;
+        }
+    }
+#pragma unroll
+    for (int pass = 0; pass < 4 && !full; pass++) {
+        const int a = L.r0 + 16 * pass, j = J0 + a;
+        const float *row = P + (size_t) j * ld + i;
+        if (rm_writes<false>(i, j, s0, n) && i + 3 < n) {  // (i > j and i >= s0: so are i + 1 .. i + 3)
+            const f32x4 v = *reinterpret_cast<const f32x4 *>(row);
+            t[a][L.c] = v.x;
+            t[a][L.c + 1] = v.y;
+            t[a][L.c + 2] = v.z;
+            t[a][L.c + 3] = v.w;
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; e++)
+                if (rm_writes<false>(i + e, j, s0, n)) t[a][L.c + e] = row[e];
+        }
+    }
+    __syncthreads();
+    // t[a][b]: row I0 + b, column J0 + a of the lower triangle
+    rm_store_tile<false>(P, ld, t, I0, J0, s0, n, tid, full);
+    const int d = I0 + tid;
+    if (bi == bj && tid < kRmTile && d >= s0 && d < n) {
+        P[(size_t) d * ld + d] = diag[d];
+        x[d] = xs[d];
+    }
+}
+
+// ... the vacated strip: rows [n, dim) over the columns [0, dim), columns [n, dim) of the rows [0, n), and x[n, dim)
+__global__ void __launch_bounds__(kEkfBlock) ekf_remove_zero_kernel(float *__restrict__ P, int ld, int n, int dim, float *__restrict__ x) {
+    const size_t g = (size_t) blockIdx.x * kEkfBlock + threadIdx.x;
+    const size_t w = (size_t) (dim - n), below = w * (size_t) dim;
+    if (g < w) x[n + g] = 0.0f;
+    if (g < below) {
+        P[(n + g / dim) * ld + g % dim] = 0.0f;
+    } else if (g - below < w * (size_t) n) {
+        const size_t q = g - below;
+        P[(q / w) * ld + n + q % w] = 0.0f;
+    }
+}
+
 }  // namespace
 
 int ekf_check(slamgpu_ekf *e) {
@@ -392,6 +541,9 @@ void ekf_release(slamgpu_ekf *e) {
     e->flag.release();
     e->lab_dev.release();
     e->idx_dev.release();
+    e->rm_src.release();
+    e->rm_host.release();
+    if (e->rm_ev) (void) hipEventDestroy(e->rm_ev);
     e->pin.release();
     e->stream.release();
     delete e;
@@ -466,13 +618,17 @@ int slamgpu_ekf_associate(slamgpu_ekf *e, const float *z, int32_t nz, const floa
 int slamgpu_ekf_update(slamgpu_ekf *e, const float *zf, const int32_t *idf, int32_t m, const float R[4]) {
     if (int rc = ekf_check(e)) return rc;
     if (m < 0 || !R || (m > 0 && (!zf || !idf))) return fail(SLAMGPU_ERR_INVALID, "bad update arguments");
-    return ekf_counted(e, ekf_update(e, zf, idf, m, R));
+    const int rc = ekf_update(e, zf, idf, m, R);
+    if (rc == 0) e->stats.observed(idf, m, ++e->stats.epoch);
+    return ekf_counted(e, rc);
 }
 
 int slamgpu_ekf_augment(slamgpu_ekf *e, const float *zn, int32_t n, const float Re[4]) {
     if (int rc = ekf_check(e)) return rc;
     if (n < 0 || !Re || (n > 0 && !zn)) return fail(SLAMGPU_ERR_INVALID, "bad augment arguments");
-    return ekf_counted(e, ekf_augment(e, zn, n, Re));
+    const int rc = ekf_augment(e, zn, n, Re);
+    if (rc == 0) e->stats.append(n, e->stats.epoch);
+    return ekf_counted(e, rc);
 }
 
 int slamgpu_ekf_sim(slamgpu_ekf *e, float V, float G, const float Q[4], float dt, float phi, const float *z, const int32_t *ids, int32_t nz,
@@ -519,10 +675,15 @@ int slamgpu_ekf_sim(slamgpu_ekf *e, float V, float G, const float Q[4], float dt
         if (int rc = ekf_room(e, (int) (zn.size() / 2), " (the predict and heading stages have been applied)")) return rc;
     }
     const int nf0 = nf_of(e);
-    if (e->cfg.batch_update)
+    const int32_t epoch = e->stats.epoch + 1;  // this step's, once it has succeeded
+    if (e->cfg.batch_update) {
         if (int rc = ekf_update(e, zf.data(), idf.data(), (int32_t) idf.size(), R)) return rc;
+        e->stats.observed(idf.data(), (int32_t) idf.size(), epoch);
+    }
     if (int rc = ekf_augment(e, zn.data(), (int32_t) (zn.size() / 2), Re)) return rc;
+    e->stats.append((int) (zn.size() / 2), epoch);
     e->table.learn(idn, nf0);
+    e->stats.epoch = epoch;
     return ekf_counted(e, 0);
 }
 
@@ -578,7 +739,63 @@ int slamgpu_ekf_upload(slamgpu_ekf *e, int32_t dim, const float *x, const float 
     if (int rc = ekf_state_in(e->stream, e->x, e->P, e->ld, e->cap_dim, dim, x, P, ld_in)) return rc;
     e->dim = dim;
     e->table.identity(nf_of(e));
+    e->stats.uploaded(nf_of(e));
     return 0;
+}
+
+int slamgpu_ekf_remove(slamgpu_ekf *e, const int32_t *features, int32_t k) {
+    if (int rc = ekf_check(e)) return rc;
+    if (int rc = ekf_closed(e, "slamgpu_ekf_remove")) return rc;
+    if (k < 0 || (k > 0 && !features)) return fail(SLAMGPU_ERR_INVALID, "bad remove arguments");
+    const int nf = nf_of(e);
+    for (int32_t q = 0; q < k; q++) {
+        if (features[q] < 0 || features[q] >= nf) return fail(SLAMGPU_ERR_INVALID, "features[%d] = %d outside [0, %d)", q, features[q], nf);
+        if (q > 0 && features[q] <= features[q - 1]) return fail(SLAMGPU_ERR_INVALID, "features[%d] = %d after %d: not ascending and distinct", q, features[q], features[q - 1]);
+    }
+    if (k == 0) return 0;
+    const int dim = e->dim, n = dim - 2 * k, s0 = 3 + 2 * features[0];
+    if (s0 < n) {  // something moves (otherwise the removed features are the last ones)
+        if (int rc = e->rm_src.reserve((size_t) n, "EKF removal index map")) return rc;
+        if (int rc = e->rm_host.reserve((size_t) n, "EKF removal index staging")) return rc;
+        if (!e->rm_ev) HIP_TRY(hipEventCreateWithFlags(&e->rm_ev, hipEventDisableTiming));
+        if (e->rm_used) HIP_TRY(hipEventSynchronize(e->rm_ev));  // (the previous removal's map: taken long ago)
+        int32_t *src = e->rm_host.p;
+        for (int i = 0; i < 3; i++) src[i] = i;
+        for (int f = 0, q = 0, at = 3; f < nf; f++) {
+            if (q < k && features[q] == f) {
+                q++;
+                continue;
+            }
+            src[at++] = 3 + 2 * f;
+            src[at++] = 4 + 2 * f;
+        }
+        HIP_TRY(hipMemcpyAsync(e->rm_src, src, sizeof(int32_t) * (size_t) n, hipMemcpyHostToDevice, e->stream));
+        HIP_TRY(hipEventRecord(e->rm_ev, e->stream));
+        e->rm_used = true;
+        const int nt = (n + kRmTile - 1) / kRmTile, b0 = s0 / kRmTile;
+        ekf_remove_gather_kernel<<<dim3(nt - b0, nt), kEkfBlock, 0, e->stream>>>(e->P, e->ld, n, s0, b0, e->rm_src, e->x, e->w.c2, e->w.Wh);
+        if (int rc = ekf_launched("ekf_remove_gather_kernel")) return rc;
+        ekf_remove_mirror_kernel<<<dim3(nt, nt - b0), kEkfBlock, 0, e->stream>>>(e->P, e->ld, n, s0, b0, e->x, e->w.c2, e->w.Wh);
+        if (int rc = ekf_launched("ekf_remove_mirror_kernel")) return rc;
+    }
+    const size_t zeroed = (size_t) (dim - n) * ((size_t) dim + n);
+    ekf_remove_zero_kernel<<<(unsigned) ((zeroed + kEkfBlock - 1) / kEkfBlock), kEkfBlock, 0, e->stream>>>(e->P, e->ld, n, dim, e->x);
+    if (int rc = ekf_launched("ekf_remove_zero_kernel")) return rc;
+    e->dim = n;
+    e->table.remove(features, k);
+    e->stats.remove(features, k);
+    return 0;
+}
+
+int slamgpu_ekf_feature_stats(slamgpu_ekf *e, int32_t *hits, int32_t *born, int32_t *last, int32_t *epoch) {
+    if (!e) return fail(SLAMGPU_ERR_INVALID, "null EKF handle");
+    const EkfFeatureStats &s = e->stats;
+    const size_t bytes = sizeof(int32_t) * s.hits.size();
+    if (hits && bytes) memcpy(hits, s.hits.data(), bytes);
+    if (born && bytes) memcpy(born, s.born.data(), bytes);
+    if (last && bytes) memcpy(last, s.last.data(), bytes);
+    if (epoch) *epoch = s.epoch;
+    return (int) s.hits.size();
 }
 
 int slamgpu_ekf_status(slamgpu_ekf *e, int32_t *status) {

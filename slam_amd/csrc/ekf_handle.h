@@ -54,6 +54,46 @@ struct EkfLocal {
     int dimA() const { return 3 + 2 * (k + n_new); }
 };
 
+// slamgpu_ekf_feature_stats: per-feature counts, host only.  An epoch is a successful sim with observations or a successful direct
+// update; the call in progress counts hits and births at epoch + 1 and advances epoch when it has succeeded
+struct EkfFeatureStats {
+    int32_t epoch = 0;
+    std::vector<int32_t> hits, born, last;
+    void append(int n, int32_t at) {
+        hits.insert(hits.end(), (size_t) n, 0);
+        born.insert(born.end(), (size_t) n, at);
+        last.insert(last.end(), (size_t) n, at);
+    }
+    void observed(const int32_t *idf, int32_t m, int32_t at) {  // global feature indices
+        for (int32_t i = 0; i < m; i++) {
+            hits[(size_t) idf[i]]++;
+            last[(size_t) idf[i]] = at;
+        }
+    }
+    void uploaded(int nf) {
+        hits.assign((size_t) nf, 0);
+        born.assign((size_t) nf, epoch);
+        last.assign((size_t) nf, epoch);
+    }
+    void remove(const int32_t *features, int32_t k) {  // ascending and distinct
+        size_t out = 0;
+        int32_t q = 0;
+        for (size_t f = 0; f < hits.size(); f++) {
+            if (q < k && (size_t) features[q] == f) {
+                q++;
+                continue;
+            }
+            hits[out] = hits[f];
+            born[out] = born[f];
+            last[out] = last[f];
+            out++;
+        }
+        hits.resize(out);
+        born.resize(out);
+        last.resize(out);
+    }
+};
+
 struct slamgpu_ekf {
     slamgpu_ekf_config cfg{};
     EkfStream stream;
@@ -64,6 +104,12 @@ struct slamgpu_ekf {
     EkfWork w{};
     EkfIdTable table;  // association_known
     EkfLocal loc;
+    EkfFeatureStats stats;
+    // slamgpu_ekf_remove: src [dim'] the surviving state indices, staged through rm_host
+    DevBuf<int32_t> rm_src;
+    PinBuf<int32_t> rm_host;
+    hipEvent_t rm_ev = nullptr;  // the device has taken rm_host
+    bool rm_used = false;
 };
 
 #pragma GCC visibility push(hidden)

@@ -460,6 +460,14 @@ struct EkfIdTable {
         map.assign((size_t) nf, 0);
         for (int f = 0; f < nf; f++) map[f] = f;
     }
+    // after the removal of features[k] (ascending and distinct): their ids have not been seen, the others follow their features
+    void remove(const int32_t *features, int32_t k) {
+        for (int32_t &f : map) {
+            if (f < 0) continue;
+            const int32_t *at = std::lower_bound(features, features + k, f);
+            f = (at != features + k && *at == f) ? -1 : f - (int32_t) (at - features);
+        }
+    }
 };
 
 // x[dim] and P[dim][dim] of a filter at (xd, Pd, row stride ld) to the caller's arrays, either may be null; the stream is idle

@@ -149,6 +149,20 @@ bool parse_options(Simulator &sim, Options &o) {
         o.ekf_local_new = (int) std::min<long>(atol(eln.c_str()), 1 << 20);
     }
 
+    // -EKF_PRUNE_AGE a -EKF_PRUNE_HITS h: the EKF takes out, a observation steps after it was created, a feature observed fewer than h
+    // times (EkfSlam::remove on the host, slamgpu_ekf_remove with -ekf device); each feature is judged once
+    const std::string pa = take("EKF_PRUNE_AGE"), ph = take("EKF_PRUNE_HITS");
+    if (!pa.empty() || !ph.empty()) {
+        const char *why = nullptr;
+        if (pa.empty() || ph.empty()) why = "both together";
+        else if (!ekf) why = "with -method EKF1 only (the FastSLAM methods retire landmarks by their own policy: -assoc gated)";
+        else if (o.runs) why = "not with -runs B (the ensemble keeps every feature)";
+        else if (atol(pa.c_str()) < 1 || atol(ph.c_str()) < 1) why = "a >= 1 and h >= 1";
+        if (why) return refuse("-EKF_PRUNE_AGE a -EKF_PRUNE_HITS h", why);
+        o.ekf_prune_age = (int) std::min<long>(atol(pa.c_str()), 1 << 30);
+        o.ekf_prune_hits = (int) std::min<long>(atol(ph.c_str()), 1 << 30);
+    }
+
     // -RUNS_BATCH K, -RUNS_TRACE file: how the ensemble's run is launched, and its per-step NEES
     const std::string rb = take("RUNS_BATCH");
     o.runs_trace = take("RUNS_TRACE");

@@ -38,6 +38,7 @@ struct Options {
     bool ekf_device = false;
     double ekf_local = 0.0;  // -EKF_LOCAL margin; 0: off
     int ekf_local_new = 64;
+    int ekf_prune_age = 0, ekf_prune_hits = 0;  // -EKF_PRUNE_AGE a -EKF_PRUNE_HITS h (host filter too); 0: off
     int runs = 0;  // -runs B; 0: one filter
     uint64_t runs_seed = 0;
     int runs_batch = 0;  // -RUNS_BATCH K; 0: by B (run_ekf_ensemble)

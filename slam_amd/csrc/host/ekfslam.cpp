@@ -111,9 +111,69 @@ void EkfSlam::sim(float Vn, float Gn, const float Qe[4], float dt, float phi, co
             associate_known(z, ids, zf, idf, zn, table);
         else
             associate(z, Re, zf, idf, zn);
-        if (enableBatchUpdate) batch_update(zf, R, idf);
+        epoch++;
+        if (enableBatchUpdate) {
+            batch_update(zf, R, idf);
+            for (int f : idf) {
+                hits[(size_t) f]++;
+                last[(size_t) f] = epoch;
+            }
+        }
         augment(zn, Re);
+        const size_t nf = (size_t) num_features();
+        hits.resize(nf, 0);
+        born.resize(nf, epoch);
+        last.resize(nf, epoch);
     }
+}
+
+void EkfSlam::uploaded() {
+    const size_t nf = (size_t) num_features();
+    hits.assign(nf, 0);
+    born.assign(nf, epoch);
+    last.assign(nf, epoch);
+}
+
+bool EkfSlam::remove(const std::vector<int32_t> &features, std::vector<float> &table) {
+    const int nf = num_features(), k = (int) features.size();
+    for (int q = 0; q < k; q++)
+        if (features[q] < 0 || features[q] >= nf || (q > 0 && features[q] <= features[q - 1])) return false;
+    if (k == 0) return true;
+    std::vector<int> src = {0, 1, 2}, renumber((size_t) nf, -1);
+    for (int f = 0, q = 0; f < nf; f++) {
+        if (q < k && features[q] == f) {
+            q++;
+            continue;
+        }
+        renumber[(size_t) f] = f - q;
+        src.push_back(3 + 2 * f);
+        src.push_back(4 + 2 * f);
+    }
+    const int n = (int) src.size(), s0 = 3 + 2 * features[0];
+    std::vector<float> xn((size_t) n);
+    Mat Pn(n, n);
+    for (int i = 0; i < n; i++) {
+        xn[(size_t) i] = x[(size_t) src[(size_t) i]];
+        for (int j = 0; j < n; j++) {
+            const int hi = i > j ? i : j, lo = i > j ? j : i;
+            Pn(i, j) = hi >= s0 ? P(src[(size_t) hi], src[(size_t) lo]) : P(i, j);
+        }
+    }
+    x = xn;
+    P = Pn;
+    for (float &t : table)
+        if (t >= 0.0f) t = (float) renumber[(size_t) t];
+    for (int f = 0; f < nf; f++) {
+        const int g = renumber[(size_t) f];
+        if (g < 0) continue;
+        hits[(size_t) g] = hits[(size_t) f];
+        born[(size_t) g] = born[(size_t) f];
+        last[(size_t) g] = last[(size_t) f];
+    }
+    hits.resize((size_t) (nf - k));
+    born.resize((size_t) (nf - k));
+    last.resize((size_t) (nf - k));
+    return true;
 }
 
 void EkfSlam::predict(float V, float G, const float Q[4], float dt) {

@@ -33,6 +33,17 @@ class EkfSlam {
              const std::vector<int32_t> &ids, const float Re[4], bool observe, const float R[4], std::vector<float> &table);
     int num_features() const { return ((int) x.size() - 3) / 2; }
 
+    // The twin of slamgpu_ekf_remove (include/slamgpu.h): features ascending and distinct, each in [0, num_features()), anything
+    // else returns false with nothing applied.  x and P become the gather over the surviving indices, P from its LOWER triangle
+    // mirrored wherever an index at or beyond the first removed entry is involved; table (id -> feature, -1 not seen) forgets the
+    // removed features' ids and renumbers the rest; the counters below are compacted
+    bool remove(const std::vector<int32_t> &features, std::vector<float> &table);
+    // the per-feature counts of slamgpu_ekf_feature_stats, kept by sim; uploaded(): a new state of num_features() features has
+    // been put into x and P
+    int32_t epoch = 0;
+    std::vector<int32_t> hits, born, last;
+    void uploaded();
+
    private:
     void predict(float V, float G, const float Q[4], float dt);                                   // :46-77
     void observe_heading(float phi);                                                              // :86-95

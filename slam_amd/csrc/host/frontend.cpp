@@ -624,7 +624,25 @@ int slamhost_ekf_upload(slamhost_ekf *e, int32_t dim, const float *x, const floa
     std::fill(e->table.begin(), e->table.end(), -1.0f);
     if (e->table.size() < nf) e->table.resize(nf, -1.0f);
     for (size_t f = 0; f < nf; f++) e->table[f] = (float) f;
+    e->ekf.uploaded();
     return 0;
+}
+
+int slamhost_ekf_remove(slamhost_ekf *e, const int32_t *features, int32_t k) {
+    if (!e || k < 0 || (k > 0 && !features)) return -1;
+    return e->ekf.remove(std::vector<int32_t>(features, features + k), e->table) ? 0 : -1;
+}
+
+int slamhost_ekf_feature_stats(const slamhost_ekf *e, int32_t *hits, int32_t *born, int32_t *last, int32_t *epoch) {
+    if (!e) return -1;
+    const size_t nf = e->ekf.hits.size();
+    for (size_t f = 0; f < nf; f++) {
+        if (hits) hits[f] = e->ekf.hits[f];
+        if (born) born[f] = e->ekf.born[f];
+        if (last) last[f] = e->ekf.last[f];
+    }
+    if (epoch) *epoch = e->ekf.epoch;
+    return (int) nf;
 }
 
 int slamhost_ekf_local_region(const float *x, int32_t dim, float radius, int32_t *features_out, int32_t max_count) {

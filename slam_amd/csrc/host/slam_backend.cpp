@@ -882,6 +882,23 @@ struct LocalPeriods {
     bool moved_on(const double est[3]) const { return open && std::hypot(est[0] - cx, est[1] - cy) > 0.5 * margin; }
 };
 
+// -EKF_PRUNE_AGE a -EKF_PRUNE_HITS h: after an observation step, the features created a observation steps ago that the update stage
+// has been handed fewer than h times.  A feature's age passes a once, so each is judged once
+struct Prune {
+    int age, hits, removed = 0;
+    std::vector<int32_t> h, b, list;
+    explicit Prune(const Options &o) : age(o.ekf_prune_age), hits(o.ekf_prune_hits) {}
+    bool on() const { return age > 0; }
+    const std::vector<int32_t> &due(const int32_t *nhits, const int32_t *born, int nf, int32_t epoch) {
+        list.clear();
+        for (int f = 0; f < nf; f++)
+            if (epoch - born[f] == age && nhits[f] < hits) list.push_back(f);
+        removed += (int) list.size();
+        return list;
+    }
+    void print_landmarks(int nf) const { printf("landmarks in map: %d (%d removed by -EKF_PRUNE_AGE %d -EKF_PRUNE_HITS %d)\n", nf, removed, age, hits); }
+};
+
 // EKF-SLAM step by step (ekfslamwrapper.cpp:33-109): float32 loops on the host, or with -ekf device the same filter resident on the GPU;
 // without one that fails loudly (no CPU fallback behind -ekf device)
 static int run_ekf(Simulator &sim, const Options &o, Outputs &out) {
@@ -917,6 +934,7 @@ static int run_ekf(Simulator &sim, const Options &o, Outputs &out) {
     slamgpu_ekf *const dev = owner.get();
     const bool local = o.ekf_local > 0.0;
     LocalPeriods lp(dev, c, o);
+    Prune prune(o);
     StepLoop loop(sim, o, out);
     double *const est = loop.est;
     int rc = 0;
@@ -942,9 +960,23 @@ static int run_ekf(Simulator &sim, const Options &o, Outputs &out) {
             }
             if (!rc) rc = slamgpu_ekf_pose(dev, est, nullptr);
             if (!rc && lp.moved_on(est)) rc = lp.end();
+            if (!rc && prune.on() && r == 1) {
+                const size_t nf = (size_t) (slamgpu_ekf_dim(dev) - 3) / 2;
+                prune.h.resize(nf);
+                prune.b.resize(nf);
+                int32_t epoch = 0;
+                if (slamgpu_ekf_feature_stats(dev, prune.h.data(), prune.b.data(), nullptr, &epoch) < 0) rc = -1;
+                const std::vector<int32_t> &due = prune.due(prune.h.data(), prune.b.data(), (int) nf, epoch);
+                if (!rc && !due.empty()) rc = lp.end();  // (the passive part of P is stale inside a period; the next step opens one)
+                if (!rc && !due.empty()) rc = slamgpu_ekf_remove(dev, due.data(), (int32_t) due.size());
+            }
             if (rc) break;
         } else {
             ekf.sim(sim.Vnoisy, sim.Gnoisy, sim.Qe, sim.dt, phi, sim.z, sim.vis, sim.Re, r == 1, sim.R, ekf_table);
+            if (prune.on() && r == 1) {
+                const std::vector<int32_t> &due = prune.due(ekf.hits.data(), ekf.born.data(), ekf.num_features(), ekf.epoch);
+                if (!due.empty()) ekf.remove(due, ekf_table);
+            }
             est[0] = ekf.x[0];
             est[1] = ekf.x[1];
             est[2] = ekf.x[2];
@@ -962,11 +994,15 @@ static int run_ekf(Simulator &sim, const Options &o, Outputs &out) {
         (void) slamgpu_ekf_status(dev, &st);
         int32_t info[6] = {};
         (void) slamgpu_ekf_local_info(dev, info);
-        if (local)
+        if (prune.on())
+            prune.print_landmarks((slamgpu_ekf_dim(dev) - 3) / 2);
+        else if (local)
             printf("landmarks in map: %d (local periods of MAX_RANGE + %g m: %d commits)\n", (slamgpu_ekf_dim(dev) - 3) / 2, o.ekf_local, info[5]);
         else
             printf("landmarks in map: %d\n", (slamgpu_ekf_dim(dev) - 3) / 2);
         if (st & SLAMGPU_EKF_STATUS_NOT_PD) printf("EKF on the device: a batch update was skipped (innovation covariance not positive definite)\n");
+    } else if (prune.on()) {
+        prune.print_landmarks(ekf.num_features());
     } else {
         printf("landmarks in map: %d\n", ekf.num_features());
     }

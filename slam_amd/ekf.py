@@ -45,6 +45,8 @@ def _lib():
         L.slamgpu_ekf_local_end.argtypes = [vp]
         L.slamgpu_ekf_local_info.argtypes = [vp, vp]
         L.slamgpu_ekf_lookup.argtypes = [vp, vp, i32, vp]
+        L.slamgpu_ekf_remove.argtypes = [vp, vp, i32]
+        L.slamgpu_ekf_feature_stats.argtypes = [vp, vp, vp, vp, C.POINTER(i32)]
         _bound = True
     return L
 
@@ -160,6 +162,20 @@ class EkfGpu:
         out = np.zeros(ids.shape[0], np.int32)
         _chk(self.L.slamgpu_ekf_lookup(self.h, _ptr(ids), ids.shape[0], _ptr(out)))
         return out
+
+    # ---- features taken out in place (slamgpu_ekf_remove) and the per-feature counts -----------------------------------------------
+    def remove(self, features):
+        """features: global feature indices, ascending and distinct; enqueued, does not wait for the device"""
+        f = np.ascontiguousarray(features, np.int32).reshape(-1)
+        _chk(self.L.slamgpu_ekf_remove(self.h, _ptr(f), f.shape[0]))
+
+    def feature_stats(self):
+        """dict(hits, born, last: int32 [nf]; epoch: int)"""
+        nf = (self.dim - 3) // 2
+        hits, born, last = (np.zeros(nf, np.int32) for _ in range(3))
+        epoch = C.c_int32()
+        _chk(self.L.slamgpu_ekf_feature_stats(self.h, _ptr(hits), _ptr(born), _ptr(last), C.byref(epoch)))
+        return dict(hits=hits, born=born, last=last, epoch=int(epoch.value))
 
     @contextlib.contextmanager
     def local(self, features, max_new=0):

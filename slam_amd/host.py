@@ -13,7 +13,7 @@ DECLARED_SYMBOLS = [
     "slamhost_sim_control_steps", "slamhost_gated_create", "slamhost_gated_destroy", "slamhost_gated_set", "slamhost_gated_step",
     "slamhost_gated_counts", "slamhost_draw_normals", "slamhost_draw_strata", "slamhost_unif_rand",
     "slamhost_synthetic_landmarks", "slamhost_write_map", "slamhost_ekf_create", "slamhost_ekf_destroy", "slamhost_ekf_step",
-    "slamhost_ekf_state", "slamhost_ekf_last_inputs", "slamhost_sim_noise", "slamhost_ekf_sim", "slamhost_ekf_upload", "slamhost_ekf_local_region", "slamhost_plot_open", "slamhost_plot_close", "slamhost_plot_xy", "slamhost_plot_matrix",
+    "slamhost_ekf_state", "slamhost_ekf_last_inputs", "slamhost_sim_noise", "slamhost_ekf_sim", "slamhost_ekf_upload", "slamhost_ekf_local_region", "slamhost_ekf_remove", "slamhost_ekf_feature_stats", "slamhost_plot_open", "slamhost_plot_close", "slamhost_plot_xy", "slamhost_plot_matrix",
     "slamhost_plot_doubles", "slamhost_plot_car_size", "slamhost_plot_u32", "slamhost_plot_cmd", "slamhost_plot_name",
     "slamhost_map_candidates", "slamhost_map_merge", "slamhost_pose_nees", "slamhost_innovation_nis", "slamhost_joint_dense",
 ]
@@ -82,6 +82,8 @@ def load_library():
                                        C.c_void_p, C.c_void_p, C.c_int32]
         L.slamhost_ekf_upload.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32]
         L.slamhost_ekf_local_region.argtypes = [C.c_void_p, C.c_int32, C.c_float, C.c_void_p, C.c_int32]
+        L.slamhost_ekf_remove.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
+        L.slamhost_ekf_feature_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]
         L.slamhost_plot_open.restype = C.c_void_p
         L.slamhost_plot_open.argtypes = [C.c_char_p]
         L.slamhost_plot_close.argtypes = [C.c_void_p]
@@ -389,6 +391,20 @@ class HostEkf:
         P = np.ascontiguousarray(P, np.float32)
         if self.L.slamhost_ekf_upload(self.h, x.shape[0], _p(x), _p(P), P.shape[1]) != 0:
             raise ValueError("slamhost_ekf_upload: bad arguments")
+
+    def remove(self, features):
+        """slamhost_ekf_remove: features ascending and distinct"""
+        f = np.ascontiguousarray(features, np.int32).reshape(-1)
+        if self.L.slamhost_ekf_remove(self.h, _p(f), f.shape[0]) != 0:
+            raise ValueError("slamhost_ekf_remove: bad arguments")
+
+    def feature_stats(self):
+        """dict(hits, born, last: int32 [nf]; epoch: int)"""
+        nf = self.L.slamhost_ekf_feature_stats(self.h, None, None, None, None)
+        hits, born, last = (np.zeros(nf, np.int32) for _ in range(3))
+        epoch = C.c_int32()
+        self.L.slamhost_ekf_feature_stats(self.h, _p(hits), _p(born), _p(last), C.byref(epoch))
+        return dict(hits=hits, born=born, last=last, epoch=int(epoch.value))
 
     def close(self):
         if self.h:

@@ -3,6 +3,12 @@ BASELINE config 5.  Appends to profiles/ekf.txt (or --out).
 
     python tools/ekf_probe.py [--out profiles/ekf.txt] [--no-small] [--no-large] [--no-kernels] [--max-range 20] [--obs-steps 200]
     python tools/ekf_probe.py --local 20 [--local-new 64] [--max-range 20] [--obs-steps 2172] [--out profiles/ekf_local.txt]
+    python tools/ekf_probe.py --remove [--max-range 20] [--obs-steps 200] [--out profiles/ekf_remove.txt]
+
+--remove: slamgpu_ekf_remove on the synthetic D = 20 003 state of large(), hipEvent times on the handle's stream (the median of five, the
+state uploaded again before each), four removal sets, bytes and rate beside the device-to-device copy rate of profiles/copy_ceiling_r04.txt;
+the host route (state, numpy gather, upload) once at D = 4 003; then the config-5-size course with the GATES (association unknown) with and
+without the pruning rule of slam-backend -EKF_PRUNE_AGE 10 -EKF_PRUNE_HITS 3; nothing else runs.
 
 --local margin: the config-5-size course once through the full filter and once in local periods (slamgpu_ekf_local_*) under the policy
 of slam-backend -EKF_LOCAL margin, the two printed side by side; nothing else runs.
@@ -273,6 +279,177 @@ def local_course(slam_amd, host, max_range, obs_steps, margin, max_new, say):
     say("  largest |x_local - x_full| at the end: %.3e (pose %.3e)" % (np.abs(finals[1] - finals[0]).max(), np.abs(finals[1][:3] - finals[0][:3]).max()))
 
 
+COPY_CEILING = 4.90e12  # hipMemcpyDtoD, bytes read + written per second (profiles/copy_ceiling_r04.txt)
+
+
+class HipEvents:
+    """a stream of the caller's and two events on it, through the HIP runtime libslamgpu.so runs on"""
+
+    def __init__(self):
+        import ctypes as C
+        self.C = C
+        self.hip = hip = C.CDLL(next(line.split()[-1] for line in open("/proc/self/maps") if "libamdhip64" in line))
+        vp = C.c_void_p
+        hip.hipStreamCreate.argtypes = [C.POINTER(vp)]
+        hip.hipEventCreate.argtypes = [C.POINTER(vp)]
+        hip.hipEventRecord.argtypes = [vp, vp]
+        hip.hipEventElapsedTime.argtypes = [C.POINTER(C.c_float), vp, vp]
+        for fn in (hip.hipEventSynchronize, hip.hipEventDestroy, hip.hipStreamDestroy):
+            fn.argtypes = [vp]
+        self.stream, self.a, self.b = vp(), vp(), vp()
+        assert hip.hipStreamCreate(C.byref(self.stream)) == 0 and hip.hipEventCreate(C.byref(self.a)) == 0 and hip.hipEventCreate(C.byref(self.b)) == 0
+
+    def seconds(self, fn):
+        ms = self.C.c_float()
+        assert self.hip.hipEventRecord(self.a, self.stream) == 0
+        fn()
+        assert self.hip.hipEventRecord(self.b, self.stream) == 0 and self.hip.hipEventSynchronize(self.b) == 0
+        assert self.hip.hipEventElapsedTime(self.C.byref(ms), self.a, self.b) == 0
+        return 1e-3 * ms.value
+
+    def close(self):
+        self.hip.hipEventDestroy(self.a)
+        self.hip.hipEventDestroy(self.b)
+        self.hip.hipStreamDestroy(self.stream)
+
+
+def remove_traffic(dim, feats):
+    """bytes slamgpu_ekf_remove reads and writes: each triangle of the moved region once each way, the diagonal and x, the zeroed strip"""
+    n, s0 = dim - 2 * len(feats), 3 + 2 * int(feats[0])
+    tri = (n * (n - 1) - s0 * (s0 - 1)) // 2 if s0 < n else 0
+    moved = 4 * (2 * tri + 4 * max(n - s0, 0))
+    return moved + 4 * n * (s0 < n), moved + 4 * ((dim - n) * (dim + n) + dim - n)
+
+
+def gather_host(x, P, feats):
+    nf = (x.shape[0] - 3) // 2
+    keep = np.setdiff1d(np.arange(nf), feats)
+    src = np.concatenate([np.arange(3), np.stack([3 + 2 * keep, 4 + 2 * keep], axis=1).reshape(-1)])
+    return x[src], P[np.ix_(src, src)]
+
+
+def synthetic_P(D, lm):
+    rng = np.random.default_rng(1)
+    u = rng.normal(0, 0.1, D).astype(f32)
+    P = np.outer(u, u)
+    P[np.diag_indices(D)] += f32(0.5)
+    xs = np.zeros(D, f32)
+    xs[3::2], xs[4::2] = lm[0, :(D - 3) // 2], lm[1, :(D - 3) // 2]
+    return xs, P
+
+
+def remove_kernels(slam_amd, host, say):
+    nlm = 10000
+    lm = host.synthetic_landmarks(12345, nlm, -130, 100, -100, 90)
+    D = 3 + 2 * nlm
+    ev = HipEvents()
+    dev = slam_amd.EkfGpu(nlm, external_stream=ev.stream.value)
+    xs, P = synthetic_P(D, lm)
+    sets = (("feature 0", np.array([0])), ("the middle feature", np.array([nlm // 2])), ("the last 64 features", np.arange(nlm - 64, nlm)),
+            ("64 features spread evenly", np.arange(64) * (nlm // 64)))
+    say("slamgpu_ekf_remove at D = 20 003 (P = %.2f GB), hipEvent time on the handle's stream, median of 5, the state uploaded again before each;" % (4.0 * D * D / 1e9))
+    say("the copy rate to compare with: %.2f TB/s read + written (hipMemcpyDtoD, profiles/copy_ceiling_r04.txt)" % (COPY_CEILING / 1e12))
+    for name, feats in sets:
+        ts = []
+        for rep in range(6):  # (the first: untimed, it makes the staging buffers)
+            dev.upload(xs, P)
+            t = ev.seconds(lambda: dev.remove(feats))
+            if rep:
+                ts.append(t)
+        rd, wr = remove_traffic(D, feats)
+        t = float(np.median(ts))
+        say("    %-28s %8.3f ms (min %.3f, max %.3f)  read %.3f GB, written %.3f GB, %.2f TB/s = %.0f %% of the copy rate" %
+            (name, 1e3 * t, 1e3 * min(ts), 1e3 * max(ts), rd / 1e9, wr / 1e9, (rd + wr) / t / 1e12, 100.0 * (rd + wr) / t / COPY_CEILING))
+    x, _ = dev.state(want_P=False)
+    gone = np.stack([3 + 2 * sets[-1][1], 4 + 2 * sets[-1][1]]).reshape(-1)
+    xm = xs[np.setdiff1d(np.arange(D), gone)]
+    say("    after the last one: dim %d, x is the gather %s, status %d" % (dev.dim, bool(np.array_equal(x, xm)), dev.status()))
+    dev.close()
+    del P
+    # the route the library offered before: state -> numpy gather -> upload, at a size whose P the host handles comfortably
+    nf = 2000
+    D = 3 + 2 * nf
+    xs, P = synthetic_P(D, lm)
+    dev = slam_amd.EkfGpu(nf, external_stream=ev.stream.value)
+    dev.upload(xs, P)
+    feats = np.arange(64) * (nf // 64)
+    dev.sync()
+    t0 = time.perf_counter()
+    x1, P1 = dev.state()
+    t1 = time.perf_counter()
+    x2, P2 = gather_host(x1, P1, feats)
+    t2 = time.perf_counter()
+    dev.upload(x2, P2)
+    dev.sync()
+    t3 = time.perf_counter()
+    dev.upload(xs, P)
+    dev.remove(feats)  # (untimed: the staging buffers)
+    dev.upload(xs, P)
+    t = ev.seconds(lambda: dev.remove(feats))
+    x3, P3 = dev.state()
+    say("D = 4 003 (P = %.0f MB), 64 features spread evenly, once:" % (4.0 * D * D / 1e6))
+    say("    host route  %8.3f ms wall (state %.3f, numpy gather %.3f, upload %.3f); it synchronises and resets the id table" %
+        (1e3 * (t3 - t0), 1e3 * (t1 - t0), 1e3 * (t2 - t1), 1e3 * (t3 - t2)))
+    say("    slamgpu_ekf_remove %8.3f ms (hipEvent), the same bits: %s" % (1e3 * t, bool(np.array_equal(x3, x2) and np.array_equal(P3, P2))))
+    dev.close()
+    ev.close()
+
+
+def gated_course(slam_amd, host, max_range, obs_steps, age, hits, say):
+    """the config-5-size course with the gates, without and with the pruning rule of slam-backend -EKF_PRUNE_AGE age -EKF_PRUNE_HITS hits"""
+    nlm = 10000
+    lm = host.synthetic_landmarks(12345, nlm, -130, 100, -100, 90)
+    s0 = host.HostSim(["-m", os.path.join(ROOT, "data", "example_webmap.mat"), "-method", "EKF1"])
+    _, wp = s0.map()
+    s0.close()
+    with tempfile.TemporaryDirectory() as wd:
+        mp = os.path.join(wd, "synthetic10k.mat")
+        host.write_map(mp, lm, wp)
+        open(os.path.join(wd, "synthetic10k.ini"), "w").write(open(os.path.join(ROOT, "data", "example_webmap.ini")).read())
+        sim = host.HostSim(["-m", mp, "-method", "EKF1", "-SWITCH_SEED_RANDOM", 7, "-MAX_RANGE", max_range, "-SWITCH_ASSOCIATION_KNOWN", 0])
+        nz = sim.sim_noise()
+        course, nobs, seen = [], 0, set()
+        while nobs < obs_steps:
+            r, V, G, phi = sim.control()
+            if r < 0:
+                break
+            z = np.zeros((0, 2), f32)
+            if r == 1:
+                sim.observe(0)
+                z, vis = sim.last_z()
+                seen.update(int(i) for i in vis)
+                nobs += 1
+            course.append((V, G, nz["Qe"], nz["dt"], phi, z, None, nz["Re"], nz["R"], r))
+        truth, conf = sim.true_pose(), sim.conf
+        sim.close()
+    say("config-5-size course with the GATES: 10 000-landmark synthetic map, MAX_RANGE %g, association unknown, %d control steps, %d observation "
+        "steps, %d distinct landmarks seen" % (max_range, len(course), nobs, len(seen)))
+    for prune in (False, True):
+        dev = dev_for(slam_amd, conf, nlm)
+        t_obs, removed, t0_all = 0.0, 0, time.perf_counter()
+        for args in course:
+            t0 = time.perf_counter()
+            dev.sim(*args)
+            if args[9]:
+                if prune:
+                    st = dev.feature_stats()
+                    due = np.nonzero((st["epoch"] - st["born"] == age) & (st["hits"] < hits))[0]
+                    if due.shape[0]:
+                        dev.remove(due)
+                        removed += due.shape[0]
+                dev.sync()
+                t_obs += time.perf_counter() - t0
+        x, _ = dev.state(want_P=False)
+        nf = (x.shape[0] - 3) // 2
+        near = np.array([np.hypot(lm[0] - x[3 + 2 * f], lm[1] - x[4 + 2 * f]).min() for f in range(nf)]) if nf else np.zeros(1)
+        say("  %s:" % ("pruned, age %d, fewer than %d hits" % (age, hits) if prune else "every feature kept"))
+        say("    %d features in the map (%d removed) for %d landmarks seen, mean distance to the nearest true landmark %.3f m (max %.3f), "
+            "pose error %.3f m, status %d" % (nf, removed, len(seen), near.mean(), near.max(), float(np.hypot(*(x[:2] - truth[:2]))), dev.status()))
+        say("    %.2f ms per observation step (synchronised, the rule and its removals included), %.1f s wall in all" %
+            (1e3 * t_obs / max(nobs, 1), time.perf_counter() - t0_all))
+        dev.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "ekf.txt"))
@@ -283,6 +460,7 @@ def main():
     ap.add_argument("--obs-steps", type=int, default=200)
     ap.add_argument("--local", type=float, default=0.0, metavar="MARGIN", help="the config-5-size course through local periods beside the full filter")
     ap.add_argument("--local-new", type=int, default=64, help="with --local: the features a period may create")
+    ap.add_argument("--remove", action="store_true", help="slamgpu_ekf_remove at full size, the host route, the gated course with and without pruning")
     a = ap.parse_args()
     import slam_amd
     from slam_amd import host
@@ -297,6 +475,10 @@ def main():
         out.flush()
 
     say("# tools/ekf_probe.py")
+    if a.remove:
+        remove_kernels(slam_amd, host, say)
+        gated_course(slam_amd, host, a.max_range, a.obs_steps, 10, 3, say)
+        return
     if a.local > 0.0:
         local_course(slam_amd, host, a.max_range, a.obs_steps, a.local, a.local_new, say)
         return
